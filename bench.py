@@ -15,11 +15,14 @@ The workloads are BASELINE.json's configs:
   nonbmp      (not a BASELINE config) M1 + patterns with kanji outside the BMP, 100 K x 64 with about 1 % of the chars outside the BMP
 
 ONE workload over the whole 1 -> 8 curve: with no --config the `value` is configs[2] at every N (the north-star's "10 M-sentence
-synthetic batch"; it fits one GPU), so that a scaling curve built from the per-N values compares like with like.  N = 1 also
-folds configs[1], [3], [4] and the documents workload into `workloads`, each with its own parity, kernel time and roofline (configs[1] carries the
-PCIe end-to-end figures).  (--quick: the primary workload only.)
+synthetic batch"; it fits one GPU), so that a scaling curve built from the per-N values compares like with like.  A plain run does
+only that: set up, warm up, time --steps steps, write the last step's outputs when --dump-outputs DIR is given, print the line.
+--full adds everything else: parity against the CPU oracle, the CPU baseline, the writer, the tag kernels on their own, and at
+N = 1 configs[1], [3], [4] and the documents workload folded into `workloads`, each with its own parity, kernel time and roofline
+(configs[1] carries the PCIe end-to-end figures).  (--full --quick: the primary workload only.)
 
     python bench.py --gpus N --steps 20 --warmup 3        # N > 1 without WORLD_SIZE: launches its N ranks itself (below)
+    python bench.py --gpus 1 --full                       # every workload, parity and baselines (a few minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -179,6 +182,52 @@ def measured_traffic(kernel: str, model: str, workload: str):
         if e.get("kernel") == kernel and e.get("model") == model and e.get("workload") == workload and e.get("source_hash") == sha:
             return int(e["read_bytes"] + e["write_bytes"])
     return None
+
+
+DUMP_SEED = 0x5EED0D00
+DUMP_SAMPLE = 1 << 20      # boundaries (and at most as many chars' tag rows) that --dump-outputs samples
+DUMP_BLOCKS = 1024
+
+
+def dump_outputs(out_dir: str, d_scores, d_labels, nb: int, d_tags=None, n_rows: int = 0, nt: int = 0) -> None:
+    """--dump-outputs: what the last timed step left on the device, as .npy files that two builds can compare name by name.
+    boundary_index / scores / labels: one boundary drawn (seeded) from each of DUMP_SAMPLE equal strides of the batch (every one when
+    the batch is smaller); scores_block_sums / labels_block_sums: the sums over DUMP_BLOCKS contiguous blocks, so that every output
+    counts; tag workloads add char_index / tags / tags_block_sums over the (chars x n_tags) array.  About 20 MB, 44 MB with tags."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(n: int, k: int) -> np.ndarray:
+        if n <= k:
+            return np.arange(n, dtype=np.int64)
+        stride = n // k
+        return np.arange(k, dtype=np.int64) * stride + rng.integers(0, stride, size=k, dtype=np.int64)
+
+    def block_sums(v) -> np.ndarray:
+        n = int(v.numel())
+        k = max(1, min(DUMP_BLOCKS, n))
+        w = n // k
+        s = v[:k * w].view(k, w).sum(dim=1, dtype=torch.int64)
+        s[-1] += v[k * w:].sum(dtype=torch.int64)
+        return s.cpu().numpy().astype(np.float64)
+
+    def save(name: str, a: np.ndarray) -> None:
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    idx = sample(nb, DUMP_SAMPLE)
+    d_idx = torch.from_numpy(idx).to(d_scores.device)
+    save("boundary_index", idx.astype(np.float64))
+    save("scores", d_scores[d_idx].cpu().numpy().astype(np.float64))
+    save("labels", d_labels[d_idx].cpu().numpy().astype(np.float32))
+    save("scores_block_sums", block_sums(d_scores[:nb]))
+    save("labels_block_sums", block_sums(d_labels[:nb]))
+    if nt:
+        tags = d_tags[:n_rows * nt].view(n_rows, nt)
+        rows = sample(n_rows, max(1, min(DUMP_SAMPLE, (2 * DUMP_SAMPLE) // nt)))
+        save("char_index", rows.astype(np.float64))
+        save("tags", tags[torch.from_numpy(rows).to(d_tags.device)].cpu().numpy().astype(np.float64))
+        save("tags_block_sums", block_sums(d_tags[:n_rows * nt]))
 
 
 def cpu_model_name() -> str:
@@ -402,9 +451,15 @@ class Runner:
             dist.all_gather_object(gathered, mine)
             per_rank = gathered
 
+        if args.dump_outputs and primary and self.rank == 0:
+            if nt:
+                batch.expand_tags(S, nb, d_tags.data_ptr(), stream)   # the last step's tag records as the caller's dense array
+                batch.sync()
+            dump_outputs(args.dump_outputs, d_scores, d_labels, nb, d_tags, nb + S, nt)
+
         # ---- tag kernels on their own (event-free wall clock over the same steps)
         tags_info = None
-        if nt:
+        if nt and args.full:
             def timed_fill(dense_ptr):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -763,17 +818,32 @@ def parse_args(argv=None):
     ap.add_argument("--no-emit", action="store_true")
     ap.add_argument("--phases", action="store_true", help="diagnostics: per-phase shader cycles of the scoring kernel (slows it)")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="where the per-workload detail goes (the line itself carries one compact row per workload and stays below 12 KB)")
+                    help="--full: where the per-workload detail goes (the line itself carries one compact row per workload and stays below 12 KB)")
     ap.add_argument("--in-process", action="store_true", help="N > 1: skip torch.distributed, drive the N devices from this process (the fallback path)")
     ap.add_argument("--scale-sweep", default="", help="e.g. 1,2,4,8: run the primary workload at every N of the list (one line each, as --gpus N "
                     "would print it, plus `scaling_efficiency` against the N = 1 value of the same invocation)")
     ap.add_argument("--dry-scale", action="store_true", help="pre-flight of the scaling job: --scale-sweep 1,2,4,8 on whatever this box has -- N ranks on "
-                    "N devices over RCCL when it has them, else every rank on device 0 over gloo -- and a check of every line (exit code 1 when one fails)")
+                    "N devices over RCCL when it has them, else every rank on device 0 over gloo -- and a check of every line (exit code 1 when one fails; implies --full)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the other workloads, parity against the CPU oracle and "
+                    "the CPU baseline, the roofline's diagnostics launch, the writer, the tag kernels on their own, the PCIe end-to-end legs and the "
+                    "--detail-out file.  Without it the run sets up, warms up, times --steps steps of the primary workload and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, below 64 MB: a fixed, seeded "
+                         "sample of the scores and labels, their sums over 1024 contiguous blocks, and the tags of the sampled chars for tag workloads)")
     args = ap.parse_args(argv)
     if args.scale_config:
         args.config, args.quick = args.scale_config, True
+    if args.dry_scale:
+        args.full = True      # its checks are parity and per-rank kernel times
+    if not args.full:
+        # a plain run: the primary workload's timed steps and nothing else (no oracle, writer, tag timings or PCIe legs)
+        args.quick = args.no_cpu_baseline = args.no_e2e = args.no_emit = True
     if args.gpus < 1:
         die("--gpus must be at least 1")
+    if args.steps < 1:
+        die("--steps must be at least 1")
+    if args.warmup < 0:
+        die("--warmup must not be negative")
     return args
 
 
@@ -899,6 +969,13 @@ def run_in_process(args, reason: str) -> int:
     ktimes = shards[0]["batch"].kernel_times()
     kernel_ms_mean, n_tiles = shards[0]["batch"].kernel_ms()
     kernel_ms = float(np.median(ktimes)) if len(ktimes) else kernel_ms_mean
+    if args.dump_outputs:   # device 0's shard
+        sh = shards[0]
+        torch.cuda.set_device(sh["dev"])
+        if nt:
+            sh["batch"].expand_tags(sh["S"], sh["nb"], sh["d_tags"].data_ptr(), sh["stream"].cuda_stream)
+            sh["batch"].sync()
+        dump_outputs(args.dump_outputs, sh["d_scores"], sh["d_labels"], sh["nb"], sh["d_tags"], sh["nb"] + sh["S"], nt)
     parity, cpu, a_char = None, None, None
     if not args.no_cpu_baseline:
         from oracle import cbind
@@ -976,6 +1053,8 @@ def scale_sweep(args) -> int:
         if a == "--dry-scale" or a.startswith("--scale-sweep=") or a.startswith("--gpus="):
             continue
         passthrough.append(a)
+    if args.full and "--full" not in passthrough:
+        passthrough.append("--full")
     lines, failures = [], []
     for n in ns:
         env = dict(os.environ)
@@ -1110,10 +1189,11 @@ def main():
                                         "the writer's launch, wall clock per call"
         detail = dict(line, workloads=[prim] + extra) if extra else line
         try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
-            with open(args.detail_out, "w") as fh:
-                json.dump(detail, fh, indent=1)
-            line["config"]["detail_file"] = os.path.relpath(args.detail_out, ROOT)
+            if args.full:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
+                with open(args.detail_out, "w") as fh:
+                    json.dump(detail, fh, indent=1)
+                line["config"]["detail_file"] = os.path.relpath(args.detail_out, ROOT)
         except OSError:
             pass
         text = json.dumps(shorten(line))

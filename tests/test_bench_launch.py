@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,7 +44,7 @@ def test_two_ranks_on_one_device_through_the_self_launch():
     """The N-rank code path on a 1-GPU box (both ranks on device 0, gloo): bench.py launches its ranks itself, the line says
     n_gpus = 2 and names the same workload as the 1-rank line; the in-process fallback gives the same shape of line."""
     env = {"VPT_BENCH_ONE_DEVICE": "1", "VPT_BENCH_BACKEND": "gloo"}
-    common = ["--config", "2", "--sentences", "200000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1", "--no-emit", "--no-e2e"]
+    common = ["--full", "--config", "2", "--sentences", "200000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1", "--no-emit", "--no-e2e"]
     one = _run(["--gpus", "1"] + common)
     assert one.returncode == 0, one.stderr[-2000:]
     l1 = json.loads([l for l in one.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -65,7 +66,7 @@ def test_two_ranks_on_one_device_through_the_self_launch():
 def test_dry_scale_sweep_up_to_four_ranks():
     """`bench.py --dry-scale`: the scaling job's pre-flight -- N = 1, 2, 4 as jobs of their own (on a 1-GPU box every rank on
     device 0 over gloo), one line per N with the same workload, parity, per-rank figures, and the ranks' solo kernels adding up to the N = 1 kernel."""
-    r = _run(["--dry-scale", "--scale-sweep", "1,2,4", "--config", "2", "--sentences", "400000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1",
+    r = _run(["--full", "--dry-scale", "--scale-sweep", "1,2,4", "--config", "2", "--sentences", "400000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1",
               "--no-emit", "--no-e2e"])
     lines = [json.loads(l) for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert r.returncode == 0, (r.stderr[-3000:], [l.get("dry_scale_checks") for l in lines])
@@ -106,7 +107,7 @@ def test_table_broadcast_paths_and_a_failed_init_on_one_device():
     """the 2-rank job (both ranks on device 0 over gloo) with the tables travelling each of the three ways (dist.py), and with
     an init that fails (VPT_BENCH_FAIL_INIT: as if RCCL could not come up): rank 0 then drives the devices itself and the line says so -- exit code 0."""
     env = {"VPT_BENCH_ONE_DEVICE": "1", "VPT_BENCH_BACKEND": "gloo"}
-    common = ["--config", "2", "--sentences", "200000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1", "--no-emit", "--no-e2e"]
+    common = ["--full", "--config", "2", "--sentences", "200000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1", "--no-emit", "--no-e2e"]
     for path in ("view", "staged", "compile"):
         r = _run(["--gpus", "2"] + common, dict(env, VPT_TABLES_BROADCAST=path))
         assert r.returncode == 0, r.stderr[-2000:]
@@ -123,7 +124,7 @@ def test_table_broadcast_paths_and_a_failed_init_on_one_device():
 def test_dry_scale_of_the_tagged_ragged_workload_at_four_ranks():
     """BASELINE configs[4] ("8 x MI355X": tags on, 8..512-char sentences) as a sharded job: `--scale-config 4` through the dry run at N = 1 and 4 --
     parity of scores, labels and tags on every rank, and the ranks' shares balanced by CHARS (within one longest sentence of each other)."""
-    r = _run(["--dry-scale", "--scale-sweep", "1,4", "--scale-config", "4", "--sentences", "100000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1",
+    r = _run(["--full", "--dry-scale", "--scale-sweep", "1,4", "--scale-config", "4", "--sentences", "100000", "--model-scale", "0.05", "--steps", "3", "--warmup", "1",
               "--no-emit", "--no-e2e"])
     lines = [json.loads(l) for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert r.returncode == 0, (r.stderr[-3000:], [l.get("dry_scale_checks") for l in lines])
@@ -152,3 +153,96 @@ def test_the_gather_block_of_the_line():
     want = {"l1": 3.0e9 / t / 1e9 / rates["l1"], "l2": 1.1e9 / t / 1e9 / rates["l2"], "hbm": 3.3e8 / t / 1e9 / rates["hbm"]}
     assert g["bound"] == max(want, key=want.get) and abs(g["frac"] - max(want.values())) < 1e-3 and abs(g["pmc"]["tcp_busy_share"] - 0.9) < 1e-9
     assert bench.gather_block(entry, reads, 0, 3, None) is None
+
+
+def test_a_plain_run_is_lean_and_full_keeps_the_rest():
+    """`bench.py --gpus 1 --steps N --warmup W` times the primary workload and nothing else; --full (and --dry-scale, whose checks are parity)
+    keeps every other measurement and check; --steps is the number of timed steps and must be at least 1."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and not a.dump_outputs
+    assert a.quick and a.no_cpu_baseline and a.no_e2e and a.no_emit
+    f = bench.parse_args(["--gpus", "1", "--full"])
+    assert f.full and not (f.quick or f.no_cpu_baseline or f.no_e2e or f.no_emit)
+    assert bench.parse_args(["--dry-scale"]).full
+    assert bench.parse_args(["--full", "--no-emit"]).no_emit and not bench.parse_args(["--full", "--no-emit"]).no_cpu_baseline
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_a_seeded_sample_and_block_sums(tmp_path):
+    """--dump-outputs on host tensors: float32 / float64 .npy files below 64 MB in all, the sampled values are the outputs at the sampled
+    positions, the block sums cover every output, and the same outputs give the same files byte for byte."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    nb, S, nt = 3_000_001, 40_000, 3
+    scores = torch.from_numpy(rng.integers(-2**31, 2**31 - 1, nb + 1, dtype=np.int64).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, 2, nb + 1).astype(np.uint8))
+    tags = torch.from_numpy(rng.integers(-1, 1000, (nb + S) * nt + 1).astype(np.int32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), scores, labels, nb, tags, nb + S, nt)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("boundary_index", "scores", "labels", "scores_block_sums", "labels_block_sums", "char_index", "tags",
+                                                 "tags_block_sums"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64 << 20
+    for n in names:
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes(), n
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    idx = got["boundary_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[-1] < nb
+    s, l, t = scores.numpy(), labels.numpy(), tags.numpy()
+    assert np.array_equal(got["scores"], s[idx].astype(np.float64)) and np.array_equal(got["labels"], l[idx].astype(np.float32))
+    assert got["scores_block_sums"].sum() == s[:nb].astype(np.int64).sum() and len(got["scores_block_sums"]) == bench.DUMP_BLOCKS
+    assert got["labels_block_sums"].sum() == l[:nb].astype(np.int64).sum()
+    rows = got["char_index"].astype(np.int64)
+    assert np.array_equal(got["tags"], t[:(nb + S) * nt].reshape(nb + S, nt)[rows].astype(np.float64))
+    assert got["tags_block_sums"].sum() == t[:(nb + S) * nt].astype(np.int64).sum()
+
+
+def _oracle_block_sums(v, blocks):
+    k = max(1, min(blocks, len(v)))
+    w = len(v) // k
+    out = v[:k * w].astype(np.int64).reshape(k, w).sum(axis=1)
+    out[-1] += v[k * w:].astype(np.int64).sum()
+    return out.astype(np.float64)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_its_steps_and_dumps_the_last_ones(tmp_path):
+    """A plain run (no --full) of configs[2] and of the tagged configs[4]: the line has the headline fields, exactly --steps timed launches and
+    no oracle figures; what --dump-outputs wrote is the CPU oracle's scores, labels and tags at the sampled positions and its block sums."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import cbind
+    for cfg_id, sentences in ((2, 200000), (4, 20000)):
+        out = tmp_path / ("c%d" % cfg_id)
+        r = _run(["--gpus", "1", "--config", str(cfg_id), "--sentences", str(sentences), "--model-scale", "0.05", "--steps", "4", "--warmup", "1",
+                  "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+        assert line["metric"] == "boundary scores/sec" and line["unit"] == "boundaries/s" and line["higher_is_better"] is True and line["dtype"] == "int32"
+        assert line["steps"] == 4 and line["roofline"]["timed_launches"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["parity"] is None and line["cpu_baseline"] is None and "workloads" not in line and "detail_file" not in line["config"]
+        cfg = bench.CONFIGS[cfg_id]
+        raw, _ = bench.load_model_bytes(cfg["kind"], 0.05)
+        threads = min(16, os.cpu_count() or 1)
+        utf8, boff, ooff, _, _ = bench.make_shard(cfg, raw, 0, 1, threads, sentences)
+        orc = cbind.OraclePredictor(raw, cfg["tags"])
+        o_scores, o_labels, _, _ = orc.predict_batch(utf8, boff, nthreads=threads)
+        got = {n[:-4]: np.load(out / n) for n in os.listdir(out)}
+        idx = got["boundary_index"].astype(np.int64)
+        assert len(idx) == min(len(o_scores), bench.DUMP_SAMPLE)
+        assert np.array_equal(got["scores"], o_scores[idx]) and np.array_equal(got["labels"], o_labels[idx])
+        assert np.array_equal(got["scores_block_sums"], _oracle_block_sums(o_scores, bench.DUMP_BLOCKS))
+        assert np.array_equal(got["labels_block_sums"], _oracle_block_sums(o_labels, bench.DUMP_BLOCKS))
+        if cfg["tags"]:
+            o_tags, _, _ = orc.fill_tags_batch(utf8, boff, ooff, o_labels, nthreads=threads, want_scores=False)
+            rows = got["char_index"].astype(np.int64)
+            assert np.array_equal(got["tags"], o_tags[rows]) and np.array_equal(got["tags_block_sums"], _oracle_block_sums(o_tags.reshape(-1), bench.DUMP_BLOCKS))
+        else:
+            assert "tags" not in got

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 for D in 0 1 16; do
   OUT=$REPO/gpurun_out/inst_$D; mkdir -p $OUT
-  (cd /tmp && VPT_DEBUG_ABLATE=$D rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1)
+  (cd /tmp && VPT_DEBUG_ABLATE=$D rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1)
   echo "== ablate $D"; python - <<PY
 import glob,csv,collections
 agg=collections.defaultdict(list)
