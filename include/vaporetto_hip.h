@@ -355,6 +355,63 @@ vpt_status vpt_tokenize_batch(const vpt_predictor *p, const uint8_t *utf8, const
                               size_t n_sentences, unsigned flags, int tagged, uint8_t *text_out,
                               uint64_t text_capacity, uint64_t *text_offsets_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Sentence::from_tokenized over a batch                                                  (sentence.rs:285-514)
+ *
+ * Line i is utf8[byte_offsets[i] .. byte_offsets[i+1]): tokens separated by ' ', "/tag" suffixes, '\\' escaping the next char.
+ * Outputs (B = the input's bytes; each bound below holds for any input that parses):
+ *   raw_out [B]              the raw text (Sentence::as_raw_text), lines back to back; raw_offsets_out [S+1] their byte ranges;
+ *   out_offsets_out [S+1]    laid out as vpt_count_boundaries lays it out for the raw text;
+ *   labels_out [B]           the gold CharacterBoundary per boundary (Sentence::boundaries), at out_offsets[i] + b;
+ *   n_tags_out [S]           Sentence::n_tags: the largest tag count of any char of the line;
+ *   tag_index_out [B+1]      per char (out_offsets[i] + i + c) its first tag: char g has tags tag_index[g] .. tag_index[g+1]
+ *                            (slots past them, up to n_tags, are None), tag_index[total chars] = the number of tags;
+ *   span_offsets_out [B+1]   per tag its bytes in tag_bytes_out: span_offsets[k] .. span_offsets[k+1]; an empty tag is None;
+ *   tag_bytes_out [B]        the tags' bytes, escapes removed.
+ * Errors: VPT_INVALID_ARGUMENT "InvalidArgumentError: tokenized_text: " + the reference's reason + " (line i)" for the smallest failing line:
+ *   must contain at least one character (empty, or no char at all -- where the reference divides by zero, sentence.rs:450) |
+ *   must not start with a whitespace | must not contain consecutive whitespaces | must not end with a whitespace |
+ *   a slash must follow a character | must not contain NULL.
+ * The host variant runs on the host (no device).  The *_device variant: device pointers, each output buffer sized for `capacity` >= B
+ * elements (tag_index / span_offsets: capacity + 1), asynchronous on hip_stream; errors at vpt_batch_sync -- an output that would not
+ * fit `capacity` is VPT_INVALID_ARGUMENT "... text_capacity: smaller than the tokenized text" (nothing is written past the buffers). */
+vpt_status vpt_parse_tokenized_batch(const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, uint8_t *raw_out,
+                                     uint64_t *raw_offsets_out, uint64_t *out_offsets_out, uint8_t *labels_out, uint32_t *n_tags_out,
+                                     uint64_t *tag_index_out, uint64_t *span_offsets_out, uint8_t *tag_bytes_out);
+vpt_status vpt_parse_tokenized_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                            size_t n_sentences, uint64_t capacity, uint8_t *d_raw_out, uint64_t *d_raw_offsets_out,
+                                            uint64_t *d_out_offsets_out, uint8_t *d_labels_out, uint32_t *d_n_tags_out, uint64_t *d_tag_index_out,
+                                            uint64_t *d_span_offsets_out, uint8_t *d_tag_bytes_out, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The `evaluate` CLI's counters                                                          (evaluate/src/main.rs:91-193)
+ *
+ * counts: eight uint64_t, indexed by VPT_EVAL_*: the char metric's TP / TN / FP / FN over the boundaries, Nagata's word metric's
+ * n_sys / n_ref / n_cor, and the number of sentences.  (The reference's counters are i32; these do not wrap.)
+ * The word metric compares the tag vectors of a token's last char, length included; the system side's vector is
+ *   VPT_EVAL_TAGS_NONE       empty (the CLI predicts a normalised Sentence::from_raw and fills no tags): a token is correct only where the
+ *                            sentence's gold has no tags;
+ *   VPT_EVAL_TAGS_GOLD       the gold one (--no-norm without tags: the parsed sentence keeps its tags);
+ *   VPT_EVAL_TAGS_PREDICTED  fill_tags' (predictor.rs:553-562): the records vpt_fill_tags_batch_device left on this workspace for the
+ *                            same batch and the same system labels; a predictor without tag models gives empty vectors.
+ * vpt_evaluate_labels_batch_device: the compare alone (device pointers, asynchronous; the counts are ADDED to d_counts) for callers with
+ *   post-filters of their own: the gold side as vpt_parse_tokenized_batch_device wrote it, d_sys_labels laid out the same way.
+ * vpt_evaluate_batch: tokenized lines in, counts out -- Sentence::from_tokenized, [KyteaFullwidthFilter + from_raw when flags has
+ *   VPT_FLAG_KYTEA_FULLWIDTH, i.e. without --no-norm], Predictor::predict, the VPT_FLAG_WSCONST filters, [fill_tags when predict_tags],
+ *   compare.  The lines are copied in, parsed, scored and compared on the device; 64 bytes come back.  Batches above a budget
+ *   (VPT_EVAL_CHUNK_BYTES, 64 MB) run as chunks of whole lines; the pooled workspace keeps about 22 bytes of device memory per
+ *   byte of the largest chunk (the text, the raw text, two label arrays, the tag bytes, and 8-byte tag_index / span_offsets entries
+ *   sized for one per input byte): about 1.4 GB at the default.  An empty line is an error here (the CLI skips them). */
+enum { VPT_EVAL_TAGS_NONE = 0, VPT_EVAL_TAGS_GOLD = 1, VPT_EVAL_TAGS_PREDICTED = 2 };
+enum { VPT_EVAL_TP = 0, VPT_EVAL_TN = 1, VPT_EVAL_FP = 2, VPT_EVAL_FN = 3, VPT_EVAL_N_SYS = 4, VPT_EVAL_N_REF = 5, VPT_EVAL_N_COR = 6,
+       VPT_EVAL_N_SENTENCES = 7, VPT_EVAL_COUNTS = 8 };
+vpt_status vpt_evaluate_labels_batch_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_out_offsets, size_t n_sentences,
+                                            const uint8_t *d_gold_labels, const uint32_t *d_n_tags, const uint64_t *d_tag_index,
+                                            const uint64_t *d_span_offsets, const uint8_t *d_tag_bytes, const uint8_t *d_sys_labels,
+                                            int sys_tags, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_evaluate_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
+                              unsigned flags, int predict_tags, uint64_t *counts_out);
+
 /* Diagnostics: when the environment variable VPT_PROFILE_PHASES is set at vpt_batch_create, the specialised
  * kernel accumulates, per workgroup (wave 0), the shader cycles spent in 0 text scan, 1 per-char decode,
  * 2 pattern lookups, 3 barrier wait, 4 boundary output.  Reads the sums (after a device sync) and resets them;

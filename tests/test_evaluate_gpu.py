@@ -1,0 +1,182 @@
+"""Tokenized text and the `evaluate` CLI on the MI355X: the parse kernel bit for bit against the host parser, vpt_evaluate_batch /
+Predictor.evaluate against the restatement (tests/evalref.py) fed with the library's own predict / fill_tags output (themselves pinned to the
+CPU oracle by tests/test_gpu_parity.py), the chunked path, and the CLI's stdout end to end."""
+import math
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import cbind
+from tests import evalref, kat
+from tests.test_evaluate_cli import KAT_GOLD, MODES, _expected
+from tests.test_tokenized_parse import _expect, check_parsed, random_line
+from vaporetto_amd import api, build
+from vaporetto_amd.modelfmt import encode_model
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    build.build_hip()
+
+
+def _predictor(model, tags=True):
+    return api.Predictor(api.Model.read_slice(model)[0], tags)
+
+
+def test_parse_kernel_matches_host_parser():
+    """100 K random lines of 1 - 4 000 chars (lengths log-uniform), bit for bit against the host parser, a sample against the restatement"""
+    rng = random.Random(5)
+    pool = [random_line(rng, 1) for _ in range(5000)]
+    lines = []
+    for _ in range(100000):
+        n = max(1, int(math.exp(rng.uniform(0.0, math.log(4000.0)))) // 3)   # tokens average about 3 chars
+        lines.append(" ".join(rng.choices(pool, k=n)))
+    rng.shuffle(lines)
+    enc = [ln.encode("utf-8") for ln in lines]
+    utf8, boff = api.pack_texts(enc)
+    p = _predictor(encode_model(kat.predictor_test_model()))
+    d = p.parse_tokenized_packed(utf8, boff)
+    h = api.parse_tokenized_host(enc)
+    for k in h:
+        assert np.array_equal(np.asarray(d[k]), np.asarray(h[k])), k
+    check_parsed(d, lines[:2000], _expect(lines[:2000]))
+    assert max(len(ln) for ln in lines) > 3000
+
+
+def test_parse_kernel_reports_the_first_failing_line():
+    p = _predictor(encode_model(kat.predictor_test_model()))
+    utf8, boff = api.pack_texts([b"a b"] * 50 + [b"a /b"] + [b"a b"] * 10 + [b" x"])
+    with pytest.raises(api.VaporettoError) as e:
+        p.parse_tokenized_packed(utf8, boff)
+    assert str(e.value) == "InvalidArgumentError: tokenized_text: a slash must follow a character (line 50)"
+
+
+@pytest.mark.parametrize("mode", sorted(MODES))
+def test_kat_hand_counts(mode):
+    p = _predictor(encode_model(kat.predictor_test_model()))
+    for gold in KAT_GOLD:
+        r = p.evaluate([gold[0]], **MODES[mode])
+        assert {k: r[k] for k in _expected(gold, mode)} == _expected(gold, mode), gold[0]
+
+
+def _oracle_system(raw_model, tag_models, types, graphemes, predict_tags):
+    """the system side of evalref.evaluate from the CPU oracle: the CLI's loop (evaluate/src/main.rs:103-121) -- KyteaFullwidthFilter
+    on the text, predict, KyteaWsConstFilter (a boundary between two chars of one of `types` becomes NotWordBoundary,
+    kytea_wsconst.rs:26-43), ConcatGraphemeClustersFilter, fill_tags"""
+    orc = cbind.OraclePredictor(raw_model, predict_tags=True)
+
+    def system(raws, normalised):
+        texts = [api.KyteaFullwidthFilter().filter(t) for t in raws] if normalised else list(raws)
+        utf8, boff = api.pack_texts([t.encode("utf-8") for t in texts])
+        _, labels, ooff, _ = orc.predict_batch(utf8, boff)
+        labels = labels.copy()
+        for i, t in enumerate(texts):
+            ty = api._types_of(np.frombuffer(t.encode("utf-32-le"), dtype=np.uint32))
+            for b in range(len(t) - 1):
+                if ty[b] == ty[b + 1] and int(ty[b]) in types:
+                    labels[int(ooff[i]) + b] = 0
+        if graphemes:
+            api.ConcatGraphemeClustersFilter().filter_packed(texts, ooff, labels)
+        sys_b = [list(labels[int(ooff[i]):int(ooff[i + 1])]) for i in range(len(texts))]
+        nt = orc.n_tags() if predict_tags else 0
+        if not nt:
+            return sys_b, None
+        tags, _, models = orc.fill_tags_batch(utf8, boff, ooff, labels, want_scores=False)
+        rows = []
+        for i, t in enumerate(texts):
+            g0 = int(ooff[i]) + i
+            rs = []
+            for c in range(len(t)):
+                m = int(models[g0 + c])
+                cand = tag_models[m].tags if m >= 0 else []
+                rs.append([cand[j][tags[g0 + c][j]] if m >= 0 and j < len(cand) and tags[g0 + c][j] >= 0 else None for j in range(nt)])
+            rows.append(rs)
+        return sys_b, rows
+    return system
+
+
+def _corpus(pred, texts):
+    """gold lines: the model's own tokenization (tagged) with a seeded share of boundaries flipped"""
+    rng = random.Random(3)
+    toks = pred.tokenize(texts, tagged=pred.n_tags() > 0)
+    out = []
+    for t in toks:
+        if rng.random() < 0.3 and " " in t:
+            k = t.index(" ")
+            t = t[:k] + t[k + 1:] if "/" not in t[:k] else t
+        out.append(t)
+    return out
+
+
+@pytest.mark.parametrize("wsconst", [(), (5,), (5, 3), ("G",)], ids=["none", "K", "KH", "G"])
+@pytest.mark.parametrize("predict_tags,no_norm", [(False, False), (False, True), (True, False), (True, True)])
+def test_evaluate_matches_restatement(wsconst, predict_tags, no_norm):
+    models = [("model.bin", open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()),
+              ("kat", encode_model(kat.predictor_test_model()))]
+    texts = ["まぁ社長は火星猫だ", "まぁ良いだろう", "この人は地球人だ", "火星猫", "Ｒｕｓｔで良いプログラミング体験を！", "ab 12 cd"] * 7
+    for name, raw in models:
+        pred = _predictor(raw)
+        lines = _corpus(pred, texts) + open(os.path.join(ROOT, "tests", "golden", "docs.tok"), encoding="utf-8").read().splitlines()
+        types = [t for t in wsconst if t != "G"]
+        got = pred.evaluate(lines, predict_tags=predict_tags, wsconst=wsconst, no_norm=no_norm)
+        want = evalref.evaluate(lines, _oracle_system(raw, pred._model.tag_models(), types, "G" in wsconst, predict_tags),
+                                predict_tags=predict_tags, no_norm=no_norm)
+        assert {k: got[k] for k in want} == want, name
+
+
+def test_chunked_path_gives_the_same_counts():
+    raw = open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()
+    pred = _predictor(raw)
+    lines = _corpus(pred, ["まぁ社長は火星猫だ", "まぁ良いだろう", "火星猫"] * 200)
+    want = pred.evaluate(lines, predict_tags=True)
+    os.environ["VPT_EVAL_CHUNK_BYTES"] = "700"
+    try:
+        small = _predictor(raw)
+    finally:
+        del os.environ["VPT_EVAL_CHUNK_BYTES"]
+    got = small.evaluate(lines, predict_tags=True)
+    assert {k: got[k] for k in ("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences")} == \
+        {k: want[k] for k in ("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences")}
+    bad = lines[:300] + ["a  b"] + lines[300:]
+    with pytest.raises(api.VaporettoError) as e:
+        small.evaluate(bad)
+    assert str(e.value).endswith("must not contain consecutive whitespaces (line 300)")
+
+
+def test_evaluate_after_short_host_predicts():
+    """a pooled workspace that a host predict call left with a short longest-sentence hint scores long gold lines all the same"""
+    raw = open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()
+    pred = _predictor(raw)
+    lines = [" ".join(["火星", "猫", "は", "まぁ", "社長"] * n) for n in (300, 2000)]   # 2 400 and 16 000 chars
+    first = pred.evaluate(lines, predict_tags=True)
+    pred.predict_packed(*api.pack_texts([b"ab", b"cd"]))
+    again = pred.evaluate(lines, predict_tags=True)
+    assert again == first or all(again[k] == first[k] for k in ("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences"))
+
+
+def test_cli_stdout(tmp_path):
+    model = tmp_path / "kat.model"
+    model.write_bytes(encode_model(kat.predictor_test_model()))
+    stdin = ("\n".join(g[0] for g in KAT_GOLD) + "\n\n").encode("utf-8")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    run = subprocess.run([sys.executable, "-m", "vaporetto_amd.evaluate", "--model", str(model), "--predict-tags", "--metric", "word"],
+                         input=stdin, capture_output=True, timeout=300, env=env, cwd=ROOT)
+    assert run.returncode == 0, run.stderr
+    cor = sum(g[4]["pred"] for g in KAT_GOLD)
+    n_sys, n_ref = sum(g[2] for g in KAT_GOLD), sum(g[3] for g in KAT_GOLD)
+    p, r = cor / n_sys, cor / n_ref
+    from vaporetto_amd.evaluate import rust_f64
+    assert run.stdout.decode() == "Precision: %s\nRecall: %s\nF1: %s\n" % (rust_f64(p), rust_f64(r), rust_f64(2.0 * p * r / (p + r)))
+    ours = [ln for ln in run.stderr.decode().splitlines() if not ln.startswith("/opt/")]   # (the driver's libdrm may add a line of its own)
+    assert ours == ["Loading model file...", "Start tokenization"]
+    run = subprocess.run([sys.executable, "-m", "vaporetto_amd.evaluate", "--model", str(model)], input=stdin, capture_output=True,
+                         timeout=300, env=env, cwd=ROOT)
+    tp, tn, fp, fn = (sum(g[1][k] for g in KAT_GOLD) for k in range(4))
+    assert run.stdout.decode().endswith("TP: %d, TN: %d, FP: %d, FN: %d\n" % (tp, tn, fp, fn))

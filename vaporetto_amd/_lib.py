@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libvaporetto_hip.so")
 VPT_OK, VPT_INVALID_MODEL, VPT_INVALID_ARGUMENT, VPT_RUNTIME_ERROR = 0, 1, 2, 3
 VPT_FLAG_KYTEA_FULLWIDTH = 1
 VPT_FLAG_SPLIT_LINEBREAKS = 1 << 7
+VPT_EVAL_TAGS_NONE, VPT_EVAL_TAGS_GOLD, VPT_EVAL_TAGS_PREDICTED = 0, 1, 2
 
 
 def VPT_FLAG_WSCONST(char_type: int) -> int:
@@ -74,6 +75,10 @@ SIGNATURES = {
     "vpt_write_tagged_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P]),
     "vpt_fill_tags_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P]),
     "vpt_expand_tags_batch_device": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, _P, _P]),
+    "vpt_parse_tokenized_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_parse_tokenized_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_evaluate_labels_batch_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "vpt_evaluate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, C.c_int, _P]),
     "vpt_batch_create": (C.c_int, [_P, C.POINTER(_P)]),
     "vpt_batch_destroy": (None, [_P]),
     "vpt_predict_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _P]),

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import re
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -287,6 +288,37 @@ class Sentence:
     def update_raw(self, text: str) -> None:  # sentence.rs:264-283: on error the sentence becomes " "
         try:
             self._parse_raw(text)
+        except VaporettoError:
+            self._set_default()
+            raise
+
+    def _parse_tokenized(self, text: str):  # sentence.rs:285-400, through the library's host parser (vpt_parse_tokenized_batch)
+        try:
+            p = parse_tokenized_host([text.encode("utf-8")])
+        except VaporettoError as e:   # one sentence: the reference's message, without the batch's line number
+            raise VaporettoError(e.kind, str(e).replace(" (line 0)", "")) from None
+        raw = bytes(p["raw"]).decode("utf-8")
+        nt = int(p["n_tags"][0])
+        ti, so, tb = p["tag_index"], p["span_offsets"], bytes(p["tag_bytes"])
+        tags: List[Optional[str]] = []
+        for c in range(len(ti) - 1):
+            own = [tb[int(so[k]):int(so[k + 1])].decode("utf-8") for k in range(int(ti[c]), int(ti[c + 1]))]
+            own += [""] * (nt - len(own))
+            tags += [t if t else None for t in own]
+        self._parse_raw(raw)
+        self._boundaries = p["labels"].copy()
+        self._tags = tags
+        self._n_tags = nt
+
+    @staticmethod
+    def from_tokenized(text: str) -> "Sentence":  # sentence.rs:402-459
+        s = Sentence()
+        s._parse_tokenized(text)
+        return s
+
+    def update_tokenized(self, text: str) -> None:  # sentence.rs:482-514: on error the sentence becomes " "
+        try:
+            self._parse_tokenized(text)
         except VaporettoError:
             self._set_default()
             raise
@@ -725,6 +757,113 @@ class Predictor:
         return scores[:nb], labels[:nb], ooff
 
 
+    def parse_tokenized_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray) -> dict:
+        """Sentence::from_tokenized for a packed batch of tokenized lines, on the device (vpt_parse_tokenized_batch_device).  Returns
+        the arrays of parse_tokenized_host."""
+        import torch
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S = len(byte_offsets) - 1
+        B = len(utf8)
+        dev = torch.device("cuda", self.device)
+
+        def d(n, dt):
+            return torch.zeros(max(n, 1), dtype=dt, device=dev)
+        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(1, np.uint8)])).to(dev)
+        d_boff = torch.from_numpy(byte_offsets.view(np.int64)).to(dev)
+        o = {"raw": d(B, torch.uint8), "raw_offsets": d(S + 1, torch.int64), "out_offsets": d(S + 1, torch.int64), "labels": d(B, torch.uint8),
+             "n_tags": d(S, torch.int32), "tag_index": d(B + 1, torch.int64), "span_offsets": d(B + 1, torch.int64), "tag_bytes": d(B, torch.uint8)}
+        batch = DeviceBatch(self)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.load().vpt_parse_tokenized_batch_device(
+            self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, o["raw"].data_ptr(), o["raw_offsets"].data_ptr(),
+            o["out_offsets"].data_ptr(), o["labels"].data_ptr(), o["n_tags"].data_ptr(), o["tag_index"].data_ptr(),
+            o["span_offsets"].data_ptr(), o["tag_bytes"].data_ptr(), stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        batch.sync()
+        h = {k: v.cpu().numpy() for k, v in o.items()}
+        for k in ("raw_offsets", "out_offsets", "tag_index", "span_offsets"):
+            h[k] = h[k].view(np.uint64)
+        h["n_tags"] = h["n_tags"].view(np.uint32)[:S]
+        return _trim_parsed(h, S)
+
+    def evaluate(self, lines: Sequence[str], predict_tags: bool = False, wsconst: Sequence = (), no_norm: bool = False) -> dict:
+        """The `evaluate` CLI (evaluate/src/main.rs:91-193) over tokenized lines: empty lines are skipped, every other line must parse.
+        wsconst: CharacterType values and / or "G".  The "(line N)" of a parse error counts the given lines, empty ones included.  Returns the counters (tp, tn, fp, fn, n_sys, n_ref, n_cor, n_sentences) and the
+        P / R / F1 of both metrics (char_*, word_*; NaN for 0 / 0).  Without "G" the whole pipeline is one call (vpt_evaluate_batch);
+        with "G" the grapheme filter runs on the host between the device's predict and its fill_tags + compare."""
+        if predict_tags and not self._predict_tags:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: this predictor is created with predict_tags = false")
+        index = [k for k, ln in enumerate(lines) if ln]   # the input line of every line evaluated (errors name the input's line)
+        lines = [lines[k] for k in index]
+        try:
+            return self._evaluate(lines, predict_tags, wsconst, no_norm)
+        except VaporettoError as e:
+            m = re.search(r" \(line (\d+)\)$", str(e))
+            if not m or int(m.group(1)) >= len(index):
+                raise
+            raise VaporettoError(e.kind, str(e)[:m.start()] + " (line %d)" % index[int(m.group(1))]) from None
+
+    def _evaluate(self, lines, predict_tags, wsconst, no_norm) -> dict:
+        graphemes = any(isinstance(t, str) and t == "G" for t in wsconst)
+        types = [int(t) for t in wsconst if not (isinstance(t, str) and t == "G")]
+        flags = 0 if no_norm else _lib.VPT_FLAG_KYTEA_FULLWIDTH
+        for t in types:
+            flags |= _lib.VPT_FLAG_WSCONST(t)
+        utf8, boff = pack_texts([ln.encode("utf-8") for ln in lines])
+        counts = np.zeros(8, dtype=np.uint64)
+        if not graphemes or not lines:
+            st = _lib.load().vpt_evaluate_batch(self._h, utf8.ctypes.data, boff.ctypes.data, len(lines), flags, int(bool(predict_tags)),
+                                                counts.ctypes.data)
+            if st != _lib.VPT_OK:
+                _raise(st)
+        else:
+            counts = self._evaluate_graphemes(lines, utf8, boff, flags, types, predict_tags, no_norm)
+        return evaluation_result(counts)
+
+    def _evaluate_graphemes(self, lines, utf8, boff, flags, types, predict_tags, no_norm) -> np.ndarray:
+        import torch
+        dev = torch.device("cuda", self.device)
+        S, B = len(lines), len(utf8)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def d(n, dt):
+            return torch.zeros(max(n, 1), dtype=dt, device=dev)
+        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(1, np.uint8)])).to(dev)
+        d_boff = torch.from_numpy(boff.view(np.int64)).to(dev)
+        raw, roff, ooff, gold = d(B, torch.uint8), d(S + 1, torch.int64), d(S + 1, torch.int64), d(B, torch.uint8)
+        ntags, tidx, soff, tbytes = d(S, torch.int32), d(B + 1, torch.int64), d(B + 1, torch.int64), d(B, torch.uint8)
+        batch = DeviceBatch(self)
+        L = _lib.load()
+        st = L.vpt_parse_tokenized_batch_device(self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, raw.data_ptr(), roff.data_ptr(),
+                                                ooff.data_ptr(), gold.data_ptr(), ntags.data_ptr(), tidx.data_ptr(), soff.data_ptr(),
+                                                tbytes.data_ptr(), stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        batch.sync()
+        h_roff = roff[:S + 1].cpu().numpy().view(np.uint64)
+        h_raw = raw[:int(h_roff[S])].cpu().numpy()
+        texts = [bytes(h_raw[int(h_roff[i]):int(h_roff[i + 1])]).decode("utf-8") for i in range(S)]
+        fullwidth = not no_norm
+        _, labels, h_ooff = self.predict_packed(h_raw, h_roff, fullwidth=fullwidth, wsconst=tuple(types))
+        norm = KyteaFullwidthFilter()
+        ConcatGraphemeClustersFilter().filter_packed([norm.filter(t) for t in texts] if fullwidth else texts, h_ooff, labels)
+        nb = int(h_ooff[S])
+        sys_l = torch.from_numpy(np.concatenate([labels[:nb], np.zeros(1, np.uint8)])).to(dev)
+        mode = _lib.VPT_EVAL_TAGS_NONE if fullwidth else _lib.VPT_EVAL_TAGS_GOLD
+        if predict_tags and self.n_tags():
+            mode = _lib.VPT_EVAL_TAGS_PREDICTED
+            batch.set_flags(_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
+            batch.fill_tags(raw.data_ptr(), roff.data_ptr(), ooff.data_ptr(), S, nb, sys_l.data_ptr(), 0, stream)
+        counts = torch.zeros(8, dtype=torch.int64, device=dev)
+        st = L.vpt_evaluate_labels_batch_device(self._h, batch._h, ooff.data_ptr(), S, gold.data_ptr(), ntags.data_ptr(), tidx.data_ptr(),
+                                                soff.data_ptr(), tbytes.data_ptr(), sys_l.data_ptr(), mode, counts.data_ptr(), stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        batch.sync()
+        return counts.cpu().numpy().view(np.uint64)
+
     def char_types_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, fullwidth: bool = False) -> np.ndarray:
         """Sentence::char_types for a packed batch, from the device: uint8 per char (char c of sentence i at out_offsets[i] + i + c)."""
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
@@ -942,6 +1081,48 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
         return dict(zip(["unigram_nodes", "bigram_nodes", "trigram_nodes", "deep_entries", "deep_rows", "global_type_rows"], [int(x) for x in arr][:6]))
+
+
+def _trim_parsed(h: dict, S: int) -> dict:
+    ro, oo = h["raw_offsets"][:S + 1], h["out_offsets"][:S + 1]
+    n_chars = int(oo[S]) + S if S else 0
+    ti = h["tag_index"][:n_chars + 1]
+    n_t = int(ti[n_chars]) if S else 0
+    so = h["span_offsets"][:n_t + 1]
+    return {"raw": h["raw"][:int(ro[S]) if S else 0], "raw_offsets": ro, "out_offsets": oo, "labels": h["labels"][:int(oo[S]) if S else 0],
+            "n_tags": h["n_tags"][:S], "tag_index": ti, "span_offsets": so, "tag_bytes": h["tag_bytes"][:int(so[n_t]) if S else 0]}
+
+
+def parse_tokenized_host(lines: Sequence[bytes]) -> dict:
+    """vpt_parse_tokenized_batch (host): tokenized lines -> {raw, raw_offsets, out_offsets, labels, n_tags, tag_index, span_offsets,
+    tag_bytes} as include/vaporetto_hip.h describes them."""
+    utf8, boff = pack_texts(list(lines))
+    S, B = len(lines), len(utf8)
+    h = {"raw": np.zeros(max(B, 1), np.uint8), "raw_offsets": np.zeros(S + 1, np.uint64), "out_offsets": np.zeros(S + 1, np.uint64),
+         "labels": np.zeros(max(B, 1), np.uint8), "n_tags": np.zeros(max(S, 1), np.uint32), "tag_index": np.zeros(B + 1, np.uint64),
+         "span_offsets": np.zeros(B + 1, np.uint64), "tag_bytes": np.zeros(max(B, 1), np.uint8)}
+    u = utf8 if B else np.zeros(1, np.uint8)
+    st = _lib.load().vpt_parse_tokenized_batch(u.ctypes.data, boff.ctypes.data, S, *[h[k].ctypes.data for k in
+                                               ("raw", "raw_offsets", "out_offsets", "labels", "n_tags", "tag_index", "span_offsets", "tag_bytes")])
+    if st != _lib.VPT_OK:
+        _raise(st)
+    return _trim_parsed(h, S)
+
+
+def evaluation_result(counts) -> dict:
+    """The counters of vpt_evaluate_batch with the P / R / F1 the `evaluate` CLI prints (evaluate/src/main.rs:139-191), in f64."""
+    c = [int(x) for x in counts]
+    r = dict(zip(("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences"), c))
+
+    def div(a, b):
+        return float(a) / float(b) if b else (float("nan") if a == 0 else float("inf"))
+
+    def f1(p, q):
+        return div(2.0 * p * q, p + q) if not (p + q == 0 or p != p or q != q) else float("nan")
+    for name, num, den_p, den_r in (("char", r["tp"], r["tp"] + r["fp"], r["tp"] + r["fn"]), ("word", r["n_cor"], r["n_sys"], r["n_ref"])):
+        p, q = div(num, den_p), div(num, den_r)
+        r[name + "_precision"], r[name + "_recall"], r[name + "_f1"] = p, q, f1(p, q)
+    return r
 
 
 def pack_texts(raws: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:

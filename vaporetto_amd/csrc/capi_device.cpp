@@ -207,11 +207,15 @@ vpt_status vpt_batch_sync(vpt_batch* b) {
     b->cps_text = nullptr;
     if (!b->pending) return VPT_OK;
     VPT_HIP(hipSetDevice(b->device));
-    uint32_t ctrl[2] = {0, 0};
+    uint32_t ctrl[16] = {};
     VPT_HIP(hipMemcpyAsync(ctrl, b->d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, b->last_stream));
     VPT_HIP(hipStreamSynchronize(b->last_stream));
     b->pending = false;
     if (ctrl[0]) VPT_HIP(hipMemset(b->d_ctrl, 0, sizeof(uint32_t)));   // reported once; accumulates over every call enqueued since the last sync
+    if (ctrl[0] & vpt::kErrParse) {   // tokenized text (vpt_parse_tokenized_batch_device): the reason words too
+        VPT_HIP(hipMemset(b->d_ctrl + vpt::kParseErrWord, 0, 8 * sizeof(uint32_t)));
+        return parse_status(ctrl, 0);
+    }
     return status_from_bits(ctrl[0]);
 }
 

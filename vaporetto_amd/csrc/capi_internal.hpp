@@ -46,6 +46,7 @@ struct PredictorKnobs {
     uint64_t chunk_chars = 0;           // VPT_CHUNK_CHARS (0: the size rule)
     uint64_t tokenize_chunk_bytes = uint64_t(256) << 20;   // VPT_TOKENIZE_CHUNK_BYTES (the tagged pipeline's default; the fused one: an eighth of the batch, at least 4 MB)
     bool tokenize_chunk_bytes_set = false;
+    uint64_t eval_chunk_bytes = uint64_t(64) << 20;        // VPT_EVAL_CHUNK_BYTES: vpt_evaluate_batch's chunks of tokenized text (~22 device bytes per byte)
 };
 struct BatchKnobs {
     bool force_generic = false;         // VPT_FORCE_GENERIC
@@ -61,6 +62,7 @@ PredictorKnobs read_predictor_knobs() {
     if (const char* v = std::getenv("VPT_PIPE_LANES")) k.pipe_lanes = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("VPT_CHUNK_CHARS")) { const long long n = std::atoll(v); if (n > 0) k.chunk_chars = uint64_t(n); }
     if (const char* v = std::getenv("VPT_TOKENIZE_CHUNK_BYTES")) { const long long n = std::atoll(v); if (n > 0) { k.tokenize_chunk_bytes = uint64_t(n); k.tokenize_chunk_bytes_set = true; } }
+    if (const char* v = std::getenv("VPT_EVAL_CHUNK_BYTES")) { const long long n = std::atoll(v); if (n > 0) k.eval_chunk_bytes = uint64_t(n); }
     return k;
 }
 BatchKnobs read_batch_knobs() {
@@ -295,6 +297,9 @@ struct vpt_batch {
     hipStream_t s_in = nullptr, s_out = nullptr;
     hipStream_t s_tok_in = nullptr, s_tok_out = nullptr;            // vpt_tokenize_batch's copy streams (the fused path)
     uint64_t* h_off = nullptr; size_t h_off_cap = 0;                // pinned: the rebased offsets of every chunk of the call in flight
+    // vpt_parse_tokenized_batch_device's per-line tag counts (ParseParams::tag_off / tb_off) and vpt_evaluate_batch's buffers (one allocation)
+    uint64_t* d_parse_tmp = nullptr; size_t parse_tmp_cap = 0;
+    unsigned char* d_eval = nullptr; size_t eval_cap = 0;
     std::vector<hipEvent_t> chunk_ev;                               // vpt_tokenize_batch: one per chunk in flight
 };
 
@@ -358,6 +363,7 @@ void batch_release(vpt_batch* b) {
     (void)hipFree(b->d_text); (void)hipFree(b->d_boff); (void)hipFree(b->d_ooff); (void)hipFree(b->d_scores); (void)hipFree(b->d_labels);
     (void)hipFree(b->d_tags); (void)hipFree(b->d_tag_scores); (void)hipFree(b->d_tag_models); (void)hipFree(b->d_tok); (void)hipFree(b->d_tlab); (void)hipFree(b->d_toff); (void)hipFree(b->d_tag_records); (void)hipFree(b->d_rec_tags); (void)hipFree(b->d_tag_ctl); (void)hipFree(b->d_rec_str); (void)hipFree(b->d_tag_cands); (void)hipFree(b->d_tag_summary);
     (void)hipFree(b->d_types);
+    (void)hipFree(b->d_parse_tmp); (void)hipFree(b->d_eval);
     for (auto& ps : b->pipe) {
         (void)hipFree(ps.text); (void)hipFree(ps.off); (void)hipFree(ps.scores); (void)hipFree(ps.labels);
         if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
@@ -399,6 +405,20 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrOutputTooSmall)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text");
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
+}
+
+// The device's verdict on tokenized text (kErrParse): the smallest failing line over the reason words (kernels.hpp), named with
+// parse_tokenized's message (sentence.rs:285-400); line_base: the first line of the call's batch.
+vpt_status parse_status(const uint32_t* ctrl, uint64_t line_base) {
+    static const char* const msg[7] = {"", "must contain at least one character", "must not start with a whitespace",
+                                       "must not contain consecutive whitespaces", "must not end with a whitespace",
+                                       "a slash must follow a character", "must not contain NULL"};
+    uint32_t best = 0, reason = 0;
+    for (uint32_t r = 1; r <= 6; ++r)
+        if (ctrl[vpt::kParseErrWord + r] > best) { best = ctrl[vpt::kParseErrWord + r]; reason = r; }
+    if (!reason) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tokenized_text: rejected");
+    return fail(VPT_INVALID_ARGUMENT, std::string("InvalidArgumentError: tokenized_text: ") + msg[reason] + " (line " +
+                                          std::to_string(line_base + (0xFFFFFFFFu - best)) + ")");
 }
 
 // An idle workspace of the predictor's pool for one host-buffer call (created, with a stream of its own, when the

@@ -55,6 +55,10 @@ constexpr uint32_t kErrBadOffsets = 4u;       // out_offsets do not match the te
 constexpr uint32_t kErrScratchTooSmall = 8u;  // max_sentence_bytes was understated
 constexpr uint32_t kErrUnknownLabel = 16u;    // token emission: a label that is neither 0 nor 1
 constexpr uint32_t kErrOutputTooSmall = 32u;  // token emission: text_capacity is smaller than the tokenized text
+constexpr uint32_t kErrParse = 64u;           // tokenized text that parse_tokenized rejects: the reason / line in status words kParseErrWord + reason
+// the reasons (sentence.rs:285-400), each with the smallest failing line as 0xFFFFFFFF - line (atomicMax) in status word kParseErrWord + reason
+constexpr uint32_t kParseErrNoChar = 1u, kParseErrStartSpace = 2u, kParseErrDoubleSpace = 3u, kParseErrEndSpace = 4u, kParseErrSlash = 5u,
+                   kParseErrNul = 6u, kParseErrWord = 8u;
 
 
 struct ScoreParams {
@@ -209,6 +213,53 @@ hipError_t launch_emit_tokenized(const EmitParams& P, const EmitFuse& F, hipStre
 // bytes when the host knows them (0: not), which sizes the workgroups' shares
 hipError_t launch_count_boundaries(const uint8_t* text, const uint64_t* boff, uint64_t n_sent, uint64_t* ooff_out, uint64_t* scan_part, uint32_t* status,
                                    uint32_t* max_chars, uint64_t text_bytes_hint, hipStream_t stream);
+
+// tokenized text -> raw text + gold labels + gold tags (kernels_parse.hip): Sentence::from_tokenized for a batch (sentence.rs:285-400).
+// Count pass: raw_off / ooff / tag_off / tb_off [line + 1] = the line's surface bytes / boundaries / tags / tag bytes, n_tags[line]; four
+// chained scans turn them into offsets; the write pass fills raw, labels, tag_index (first tag of every char, [chars + 1]), span_off
+// (first byte of every tag in tag_bytes, [tags + 1]) and tag_bytes (escapes removed).  *_cap: what the caller's buffers hold.
+struct ParseParams {
+    const uint8_t* text;
+    const uint64_t* boff;       // [S+1]
+    uint64_t n_sent;
+    uint8_t* raw; uint64_t raw_cap;
+    uint64_t* raw_off;          // [S+1]
+    uint64_t* ooff;             // [S+1], as vpt_count_boundaries lays it out
+    uint8_t* labels; uint64_t label_cap;
+    uint32_t* n_tags;           // [S]
+    uint64_t* tag_index; uint64_t index_cap;
+    uint64_t* span_off; uint64_t span_cap;
+    uint8_t* tag_bytes; uint64_t tb_cap;
+    uint64_t* tag_off;          // [S+1] workspace: tags in front of every line
+    uint64_t* tb_off;           // [S+1] workspace: tag bytes in front of every line
+    uint32_t* status;           // the workspace's status words (kErrParse + the reason words)
+};
+hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
+// the counters of evaluate/src/main.rs:124-191, ADDED to counts[kEvalCounts]: tp, tn, fp, fn, n_sys, n_ref, n_cor, n_sentences
+constexpr uint32_t kEvalCounts = 8;
+constexpr uint32_t kEvalTagsNone = 0, kEvalTagsGold = 1, kEvalTagsPredicted = 2;
+constexpr uint32_t kWordBoundary = 1;
+struct EvalParams {
+    const uint8_t* gold;        // [total boundaries]
+    const uint8_t* sys;         // [total boundaries]
+    const uint64_t* ooff;       // [S+1]
+    uint64_t n_sent;
+    const uint32_t* gold_n_tags;   // [S]
+    const uint64_t* tag_index;  // gold tags (ParseParams)
+    const uint64_t* span_off;
+    const uint8_t* tag_bytes;
+    uint32_t mode;              // kEvalTags*: the system's tag vectors are empty / the gold ones / fill_tags' records
+    uint32_t sys_n_tags;        // kEvalTagsPredicted: the predictor's n_tags
+    const uint4* records;       // ... the records fill_tags left on the workspace (TagParams)
+    const int32_t* rec_tags;
+    const uint2* rec_str;
+    const uint64_t* run_pref;   // [n_runs + 1]: the records of run r of `run_sent` sentences are [run_pref[r], run_pref[r + 1])
+    uint64_t n_runs;
+    uint32_t run_sent;
+    const uint8_t* str_bytes;
+    uint64_t* counts;
+};
+hipError_t launch_evaluate(const EvalParams& P, hipStream_t stream);
 
 size_t score_tiles_lds_bytes();
 hipError_t launch_assign_tiles(const uint64_t* ooff, uint64_t n_sent, int pad, uint32_t tile_flat, uint32_t n_tiles,

@@ -1,0 +1,275 @@
+// Tokenized text in, gold labels out: Sentence::from_tokenized / parse_tokenized for a batch (sentence.rs:285-400), and the counters of the
+// `evaluate` CLI (evaluate/src/main.rs:91-193) over gold and system labels.
+//
+// parse_tokenized_kernel<kWrite>: a WAVE per line, the line walked in windows of 64 bytes, one byte a lane.  Every byte's part in the line
+// is a function of masks over the window (ballots) and of four positions carried from the windows before it:
+//   escaped      the previous byte is an unescaped '\\' -- the parity of the run of '\\' in front of the byte: the highest non-'\\' lane
+//                below it, or the carried escape state when the run reaches the window's start;
+//   tag mode     the last unescaped '/' before the byte lies after the last unescaped ' ' (a tag runs to the next unescaped '/' or ' ');
+//   WordBoundary the last unescaped ' ' before a surface char lies after the last surface byte before it;
+//   slot         the unescaped '/' between a char's last surface byte and the '/' in question.
+// The ' ', '/' and '\\' bytes never occur inside a multi-byte UTF-8 sequence, so the byte-level formulation is exact.  kWrite == false
+// counts (surface bytes, chars, tags, tag bytes, the largest slot count) and reports the first error of the line; a chained scan of each
+// count (kernels_emit.hip) places the lines; kWrite == true walks the line again and writes what it counted where the scans put it.
+//
+// evaluate_kernel: a wave per sentence over its boundaries, 64 a window.  The char metric is four popcounts.  Nagata's word metric
+// (evaluate/src/main.rs:149-191) carries `matched` from boundary to boundary; here it is a segmented scan: at an agreed WordBoundary b the
+// flag is "the last disagreement before b lies before the last agreed WordBoundary before b" -- two highest-bit searches per lane.
+#include "kernels.hpp"
+
+#include "device_common.h"
+#include "layout.h"
+
+namespace vpt {
+namespace {
+
+constexpr uint32_t kParseThreads = 256;   // four waves, a line each
+constexpr uint32_t kParseMaxBlocks = 8192;
+
+__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (uint64_t(1) << lane) - 1u; }
+// lanes 0 .. j (j <= 63: a shift by 64 would be one by 0)
+__device__ __forceinline__ uint64_t lanes_upto(uint32_t j) { return j >= 63u ? ~uint64_t(0) : (uint64_t(2) << j) - 1u; }
+__device__ __forceinline__ int hi_lane(uint64_t m) { return m ? 63 - __builtin_clzll(m) : -1; }
+__device__ __forceinline__ uint32_t popc(uint64_t m) { return uint32_t(__builtin_popcountll(m)); }
+// position (relative to the line) of the highest lane of m below `lane`, else `carry`
+__device__ __forceinline__ int64_t last_below(uint64_t m, uint32_t lane, int64_t w0, int64_t carry) {
+    const int j = hi_lane(m & lanes_below(lane));
+    return j >= 0 ? w0 + j : carry;
+}
+__device__ __forceinline__ int64_t last_in(uint64_t m, int64_t w0, int64_t carry) {
+    const int j = hi_lane(m);
+    return j >= 0 ? w0 + j : carry;
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(kParseThreads) void parse_tokenized_kernel(const ParseParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
+    for (uint64_t line = uint64_t(blockIdx.x) * (kParseThreads / 64) + (threadIdx.x >> 6); line < P.n_sent; line += n_waves) {
+        const uint64_t start = P.boff[line], end = P.boff[line + 1];
+        const int64_t len = end > start ? int64_t(end - start) : 0;
+        // bases of the line in the outputs (the write pass; the count pass leaves them at 0)
+        uint64_t raw_at = 0, lab_at = 0, char_at = 0, tag_at = 0, tb_at = 0;
+        if (kWrite) {
+            raw_at = P.raw_off[line];
+            lab_at = P.ooff[line];
+            char_at = P.ooff[line] + line;
+            tag_at = P.tag_off[line];
+            tb_at = P.tb_off[line];
+        }
+        int64_t last_sp = -1, last_sl = -1, last_surf = -1;
+        uint32_t esc_carry = 0, sl_since_surf = 0, n_tags = 0;
+        uint64_t raw = 0, chars = 0, tags = 0, tbytes = 0;
+        uint32_t err = 0;   // first error of the line: kParseErr* reason
+        for (int64_t w0 = 0; w0 < len; w0 += 64) {
+            const bool valid = w0 + int64_t(lane) < len;
+            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : 0x41u;
+            const uint64_t bs = __ballot(valid && c == '\\');
+            // escaped: the run of '\\' right in front of the lane is odd (through the window's start: the carried state)
+            const int jn = hi_lane(~bs & lanes_below(lane));
+            const uint32_t esc = jn >= 0 ? uint32_t(lane - 1u - uint32_t(jn)) & 1u : (lane & 1u) ^ esc_carry;
+            const bool is_sp = valid && c == ' ' && !esc, is_sl = valid && c == '/' && !esc, drop = valid && c == '\\' && !esc;
+            const bool content = valid && !is_sp && !is_sl && !drop;
+            const uint64_t spm = __ballot(is_sp), slm = __ballot(is_sl);
+            const int64_t lsp = last_below(spm, lane, w0, last_sp), lsl = last_below(slm, lane, w0, last_sl);
+            const bool in_tag = lsl > lsp;
+            const bool surf = content && !in_tag, tagb = content && in_tag;
+            const bool lead = surf && (c & 0xC0u) != 0x80u;
+            const uint64_t surfm = __ballot(surf), leadm = __ballot(lead), tagm = __ballot(tagb);
+            const int64_t lsurf = last_below(surfm, lane, w0, last_surf);
+            const bool has_surf = lsurf >= 0, prev_boundary = has_surf && lsp > lsurf;
+            // the slot of a '/': the '/' between the char's last surface byte and this one
+            const int js = hi_lane(surfm & lanes_below(lane));
+            const uint32_t slot = js >= 0 ? popc(slm & lanes_below(lane) & ~lanes_upto(uint32_t(js))) : sl_since_surf + popc(slm & lanes_below(lane));
+            // errors in the order parse_tokenized meets them (sentence.rs:308-354)
+            uint32_t e = 0;
+            if (valid && c == 0u) e = kParseErrNul;
+            else if (is_sp && !has_surf) e = kParseErrStartSpace;
+            else if (is_sp && prev_boundary) e = kParseErrDoubleSpace;
+            else if (is_sl && (!has_surf || prev_boundary)) e = kParseErrSlash;
+            const uint64_t errm = __ballot(e != 0);
+            if (errm && !err) err = uint32_t(__shfl(int(e), __builtin_ctzll(errm)));
+            if (!kWrite) {
+                n_tags = is_sl && slot + 1u > n_tags ? slot + 1u : n_tags;
+            } else {
+                const uint64_t below = lanes_below(lane);
+                if (surf) {
+                    const uint64_t k = raw_at + raw + popc(surfm & below);
+                    if (k < P.raw_cap) P.raw[k] = uint8_t(c);
+                }
+                if (lead) {
+                    const uint64_t ci = chars + popc(leadm & below);   // char of the line
+                    if (ci > 0 && lab_at + ci - 1 < P.label_cap) P.labels[lab_at + ci - 1] = prev_boundary ? 1u : 0u;
+                    if (char_at + ci < P.index_cap) P.tag_index[char_at + ci] = tag_at + tags + popc(slm & below);
+                }
+                if (is_sl) {
+                    const uint64_t k = tag_at + tags + popc(slm & below);
+                    if (k < P.span_cap) P.span_off[k] = tb_at + tbytes + popc(tagm & below);
+                }
+                if (tagb) {
+                    const uint64_t k = tb_at + tbytes + popc(tagm & below);
+                    if (k < P.tb_cap) P.tag_bytes[k] = uint8_t(c);
+                }
+            }
+            // carried to the next window
+            const uint32_t last_drop = uint32_t(__shfl(int(drop ? 1 : 0), 63));
+            esc_carry = last_drop;
+            if (surfm) {
+                const int h = hi_lane(surfm);
+                sl_since_surf = popc(slm & ~lanes_upto(uint32_t(h)));
+            } else {
+                sl_since_surf += popc(slm);
+            }
+            last_sp = last_in(spm, w0, last_sp);
+            last_sl = last_in(slm, w0, last_sl);
+            last_surf = last_in(surfm, w0, last_surf);
+            raw += popc(surfm);
+            chars += popc(leadm);
+            tags += popc(slm);
+            tbytes += popc(tagm);
+        }
+        if (!err) {
+            if (last_surf >= 0 && last_sp > last_surf) err = kParseErrEndSpace;
+            else if (chars == 0) err = kParseErrNoChar;
+        }
+        if (!kWrite) {
+            const uint32_t nt = wave_max(n_tags);
+            if (lane == 0) {
+                P.raw_off[line + 1] = raw;
+                P.ooff[line + 1] = chars ? chars - 1 : 0;
+                P.tag_off[line + 1] = tags;
+                P.tb_off[line + 1] = tbytes;
+                P.n_tags[line] = nt;
+                if (err) {
+                    atomicOr(P.status, kErrParse);
+                    atomicMax(P.status + kParseErrWord + err, 0xFFFFFFFFu - uint32_t(line));
+                }
+            }
+        } else if (lane == 0 && line + 1 == P.n_sent) {   // the CSR arrays' last entries
+            if (char_at + chars < P.index_cap) P.tag_index[char_at + chars] = tag_at + tags;
+            if (tag_at + tags < P.span_cap) P.span_off[tag_at + tags] = tb_at + tbytes;
+        }
+    }
+}
+
+// ---- evaluate
+
+// the record fill_tags left for flat char g (kernels.hpp, TagParams::records), or ~0; [lo, hi): the records of the run of sentences
+// that holds g (run_pref: fill_tags numbers a run's records contiguously, in order)
+__device__ uint64_t find_record(const EvalParams& P, uint64_t lo, uint64_t hi, uint64_t g) {
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        const uint4 r = P.records[mid];
+        const uint64_t at = uint64_t(r.x) | (uint64_t(r.y) << 32);
+        if (at == g) return (r.z & kTokModelMask) ? mid : ~uint64_t(0);
+        if (at < g) lo = mid + 1; else hi = mid;
+    }
+    return ~uint64_t(0);
+}
+
+// the tag vector of char g (sentence i) of the gold side equals that of the system side (evaluate/src/main.rs:111-122, 163, 181)
+__device__ bool tags_equal(const EvalParams& P, uint64_t rec_lo, uint64_t rec_hi, uint64_t i, uint64_t g) {
+    if (P.mode == kEvalTagsGold) return true;
+    const uint32_t nt = P.gold_n_tags[i];
+    if (P.mode == kEvalTagsNone) return nt == 0;
+    if (nt != P.sys_n_tags) return false;
+    const uint64_t t0 = P.tag_index[g], own = P.tag_index[g + 1] - t0;
+    const uint64_t rec = find_record(P, rec_lo, rec_hi, g);
+    for (uint32_t j = 0; j < nt; ++j) {
+        uint64_t gs = 0, gl = 0;   // gold: bytes of tag j (empty: None)
+        if (j < own) { gs = P.span_off[t0 + j]; gl = P.span_off[t0 + j + 1] - gs; }
+        const int32_t t = rec != ~uint64_t(0) ? P.rec_tags[rec * P.sys_n_tags + j] : -1;
+        if (t < 0 || gl == 0) {
+            if ((t < 0) != (gl == 0)) return false;
+            continue;
+        }
+        // the candidate string is stored escaped as write_tokenized_text writes it (tables.hpp, str_bytes): compare it unescaped
+        const uint2 s = P.rec_str[rec * P.sys_n_tags + j];
+        uint64_t k = 0;
+        for (uint32_t q = 0; q < s.y; ++q) {
+            uint8_t ch = P.str_bytes[s.x + q];
+            if (ch == '\\' && q + 1 < s.y) ch = P.str_bytes[s.x + ++q];
+            if (k >= gl || P.tag_bytes[gs + k] != ch) return false;
+            ++k;
+        }
+        if (k != gl) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kParseThreads) void evaluate_kernel(const EvalParams P) {
+    __shared__ uint64_t red[kParseThreads / 64][kEvalCounts];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
+    uint64_t cnt[kEvalCounts] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint64_t i = uint64_t(blockIdx.x) * (kParseThreads / 64) + wave; i < P.n_sent; i += n_waves) {
+        const uint64_t b0 = P.ooff[i], nb = P.ooff[i + 1] - b0, g0 = b0 + i;
+        int64_t last_a = -1, last_d = -2;
+        uint64_t rec_lo = 0, rec_hi = 0;
+        if (P.mode == kEvalTagsPredicted) {
+            const uint64_t run = i / P.run_sent;
+            rec_lo = P.run_pref[run];
+            rec_hi = P.run_pref[run + 1];
+        }
+        for (uint64_t w0 = 0; w0 < nb; w0 += 64) {
+            const bool valid = w0 + lane < nb;
+            const uint32_t r = valid ? P.gold[b0 + w0 + lane] : 0u, s = valid ? P.sys[b0 + w0 + lane] : 0u;
+            const uint64_t agree_wb = __ballot(valid && r == s && s == kWordBoundary), dis = __ballot(valid && r != s);
+            const uint64_t sys_wb = __ballot(valid && s == kWordBoundary), ref_wb = __ballot(valid && r == kWordBoundary);
+            const uint64_t fp = dis & sys_wb;
+            cnt[0] += popc(agree_wb);
+            cnt[1] += popc(__ballot(valid && r == s && s != kWordBoundary));
+            cnt[2] += popc(fp);
+            cnt[3] += popc(dis & ~fp);
+            cnt[4] += popc(sys_wb);
+            cnt[5] += popc(ref_wb);
+            const bool mine = (agree_wb >> lane) & 1u;
+            const bool matched = last_below(dis, lane, int64_t(w0), last_d) < last_below(agree_wb, lane, int64_t(w0), last_a);
+            const bool cor = mine && matched && tags_equal(P, rec_lo, rec_hi, i, g0 + w0 + lane);
+            cnt[6] += popc(__ballot(cor));
+            last_a = last_in(agree_wb, int64_t(w0), last_a);
+            last_d = last_in(dis, int64_t(w0), last_d);
+        }
+        // the sentence's last token (evaluate/src/main.rs:181-186)
+        const bool cor = last_d < last_a && tags_equal(P, rec_lo, rec_hi, i, g0 + nb);
+        cnt[4] += 1; cnt[5] += 1; cnt[6] += cor ? 1 : 0; cnt[7] += 1;
+    }
+    if (lane == 0)
+        for (uint32_t k = 0; k < kEvalCounts; ++k) red[wave][k] = cnt[k];
+    __syncthreads();
+    if (threadIdx.x < kEvalCounts) {
+        uint64_t v = 0;
+        for (uint32_t w = 0; w < kParseThreads / 64; ++w) v += red[w][threadIdx.x];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(P.counts + threadIdx.x), (unsigned long long)v);
+    }
+}
+
+uint32_t grid_for(uint64_t n) {
+    const uint64_t blocks = (n + kParseThreads / 64 - 1) / (kParseThreads / 64);
+    return uint32_t(blocks < kParseMaxBlocks ? (blocks ? blocks : 1) : kParseMaxBlocks);
+}
+
+}  // namespace
+
+hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
+    hipLaunchKernelGGL(parse_tokenized_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    hipError_t e = hipGetLastError();
+    uint64_t* const counts[4] = {P.raw_off, P.ooff, P.tag_off, P.tb_off};
+    const size_t part_bytes = scan_part_entries(P.n_sent) * sizeof(uint64_t);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
+        e = hipMemsetAsync(scan_part, 0, part_bytes, stream);
+        // the totals against what the caller's buffers hold: an output larger than them is kErrOutputTooSmall (the write pass stores nothing past them)
+        if (e == hipSuccess) e = launch_scan(counts[k], P.n_sent, scan_part, k == 1 ? P.label_cap : k == 0 ? P.raw_cap : k == 2 ? P.span_cap - 1 : P.tb_cap,
+                                             P.status, nullptr, stream);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(parse_tokenized_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_evaluate(const EvalParams& P, hipStream_t stream) {
+    hipLaunchKernelGGL(evaluate_kernel, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+}  // namespace vpt
