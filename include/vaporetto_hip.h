@@ -452,6 +452,75 @@ vpt_status vpt_model_read_len(const uint8_t *model_bytes, size_t len, size_t *co
 vpt_status vpt_model_inspect(const uint8_t *model_bytes, size_t len, int predict_tags, vpt_model_info *info);
 vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Trainer: boundary-model training                                 (trainer.rs:201-490, train/src/main.rs:73-190)
+ *
+ * Features are exactly Trainer::gen_features' (trainer.rs:260-318): char n-grams and CharacterType n-grams of the windows with their
+ * rel_position, dictionary words by min(length, dictn) and Left / Inside / Right for every occurrence of every word; a feature's value
+ * is its count at the boundary (trainer.rs:321-350).  Every boundary is an example, Unknown ones too; the trained problem is "y = +1 iff
+ * WordBoundary", whose coefficients the reference keeps (trainer.rs:365-374), with a bias feature 1.0 regularised as liblinear does.
+ * Solvers: 0 (L2R_LR) and 2 (L2R_L2LOSS_SVC), the primal TRON solvers of liblinear as scikit-learn bundles it (CG without a
+ * preconditioner): the reference's newer liblinear preconditions its CG, so weights agree with it to the stopping tolerance, not bit
+ * for bit.  Sums run in a fixed order: the same examples and arguments give byte-identical models on every run.
+ * Divergences: tags are not trained (the caller rejects or drops them, see the train CLI's --ignore-tags); solvers 1, 3-7 are
+ * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
+ * VPT_INVALID_ARGUMENT (the reference unwraps or fails in liblinear); typew > charw is VPT_INVALID_ARGUMENT (the reference panics).
+ * Limits: 1 <= charn, typen <= 5; charw, typew <= 16; dictn >= 1 with a non-empty dictionary; fewer than 2^32 boundaries and feature
+ * occurrences; a feature at most 65535 times at one boundary.
+ *
+ * Device memory: per boundary 5 bytes while examples are added (the label and a feature count) and 16 bytes of key per feature
+ * occurrence, kept until the trainer is destroyed.  The design matrix adds 8 bytes per boundary (CSR row pointer), 12 bytes per
+ * nonzero (CSR and CSC copies: 4-byte index + 2-byte count each), 16 bytes (sorted key) + 8 bytes (CSC column pointer) per feature,
+ * and the column segments of Xᵀv: per level 8 bytes per feature (pointers) and 12 bytes per segment (column + partial sum), with at
+ * least one segment per feature per level and ceil(log64(longest column)) levels -- about 100 bytes per feature when one column
+ * holds tens of millions of nonzeros.  Training adds 48 bytes per boundary and 56 per feature for the fp64 vectors.  While the ids
+ * are assigned, about 60 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
+ *
+ * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
+ *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0.
+ * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
+ *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
+ * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's raw text, offsets and labels): the
+ *   examples are appended after hip_stream's work so far; returns when they are.
+ * vpt_trainer_n_features: the distinct features of the examples so far (Trainer::n_features).
+ * vpt_trainer_csr: the design matrix: row_ptr[n_rows + 1], per nonzero its column (features in key order) and count; NULL outputs ask
+ *   for the sizes only.
+ * vpt_trainer_train: Trainer::train (trainer.rs:352-487): 16-bit quantisation, the model's layout, Model::to_vec without tag models.
+ *   *needed = the model's size; model_out may be NULL, else capacity must cover it.  vpt_trainer_model returns it again.
+ *   Errors: VPT_INVALID_ARGUMENT (solver, eps / cost, one class); VPT_INVALID_MODEL "all weights are zero".
+ * vpt_trainer_weights: after train, the fp64 weights of the features in key order, the bias, and the keys (two words each, low first:
+ *   kind << 120 | c0 << 99 | c1 << 78 | c2 << 57 | c3 << 36 | c4 << 15 | length << 5 | (rel_position + 16), kind 0 char, 1 type
+ *   (c = CharacterType values), 2 dictionary (c0 = min(length, dictn), c1 = 0 Left / 1 Inside / 2 Right, no length or position)).
+ * vpt_trainer_last_stats: TRON iterations, CG steps, the gradient norms at w = 0 and at the result, and the objective. */
+typedef struct vpt_train_params {
+    uint32_t charw, charn, typew, typen, dictn;
+    uint32_t flags; /* 0 */
+} vpt_train_params;
+typedef struct vpt_train_stats {
+    uint32_t iterations;
+    uint32_t cg_steps;
+    double gnorm0;
+    double gnorm;
+    double objective;
+} vpt_train_stats;
+/* The prototypes below use only the ABI's plain types: a trainer is a `void *` handle, `params` is six uint32_t (charw, charn,
+ * typew, typen, dictn, flags) laid out as vpt_train_params, `eps_cost` two doubles (eps, cost), the weights and bias doubles, the
+ * counts uint16_t, and `stats` a vpt_train_stats. */
+vpt_status vpt_trainer_create(const uint32_t *params, const uint8_t *dict_utf8, const uint64_t *dict_offsets, size_t n_dict_words,
+                              int device_id, void **out);
+void vpt_trainer_destroy(void *t);
+vpt_status vpt_trainer_add_batch(void *t, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, const uint8_t *labels,
+                                 unsigned flags);
+vpt_status vpt_trainer_add_batch_device(void *t, const uint8_t *d_utf8, const uint64_t *d_byte_offsets, const uint64_t *d_out_offsets,
+                                        size_t n_sentences, uint64_t total_boundaries, const uint8_t *d_labels, unsigned flags, void *hip_stream);
+vpt_status vpt_trainer_n_features(void *t, size_t *out);
+vpt_status vpt_trainer_csr(void *t, uint64_t *row_ptr_out, uint32_t *cols_out, void *counts_out, size_t capacity, size_t *n_rows,
+                           size_t *nnz);
+vpt_status vpt_trainer_train(void *t, const void *eps_cost, int solver, uint8_t *model_out, size_t capacity, size_t *needed);
+vpt_status vpt_trainer_model(const void *t, uint8_t *model_out, size_t capacity, size_t *needed);
+vpt_status vpt_trainer_weights(void *t, void *weights_out, void *bias_out, uint64_t *keys_out, size_t capacity, size_t *n_features);
+vpt_status vpt_trainer_last_stats(const void *t, void *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,61 @@
+"""The trainer on a synthetic corpus: random text labelled by the golden model's predictions, then api.Trainer with solver 2.
+
+Reports one JSON line: feature extraction (vpt_trainer_add_batch) and id assignment / design matrix (the first vpt_trainer_n_features)
+with keys per second, the TRON iterations and CG steps, the training time and the mean time per CG step (one Xw, one Xᵀv and the
+reductions).  Xw and Xᵀv are not timed on their own.  A CPU comparison with sklearn's liblinear is not part of it yet."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ALPHABET = "0123456789abcdefABCあいうえおかきくけこカキクケコー漢字東京都市。、"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sentences", type=int, default=1_000_000)
+    ap.add_argument("--chars", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=250_000)
+    a = ap.parse_args()
+    from vaporetto_amd import api
+    raw = open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()
+    labeler = api.Predictor(api.Model.read_slice(raw)[0], False, device=0)
+    rng = np.random.default_rng(0)
+    alpha = np.array([c.encode() for c in ALPHABET], dtype=object)
+    t = api.Trainer(3, 3, 3, 3)
+    t_add, n_b = 0.0, 0
+    for s0 in range(0, a.sentences, a.batch):
+        n = min(a.batch, a.sentences - s0)
+        idx = rng.integers(0, len(ALPHABET), (n, a.chars))
+        texts = [b"".join(alpha[row]) for row in idx]
+        utf8, boff = api.pack_texts(texts)
+        _, labels, _ = labeler.predict_packed(utf8, boff)
+        t0 = time.perf_counter()
+        t.add_packed(utf8, boff, labels)
+        t_add += time.perf_counter() - t0
+        n_b += len(labels)
+    t0 = time.perf_counter()
+    nf = t.n_features()
+    t_build = time.perf_counter() - t0
+    ptr, _, _ = t.csr()
+    nnz = int(ptr[-1])
+    t0 = time.perf_counter()
+    t.train_bytes(0.01, 1.0, 2)
+    t_train = time.perf_counter() - t0
+    st = t.last_stats()
+    out = {"sentences": a.sentences, "chars": a.chars, "boundaries": n_b, "features": nf, "nonzeros": nnz,
+           "extract_s": round(t_add, 3), "ids_and_matrix_s": round(t_build, 3),
+           "keys_per_s": round(nnz / (t_add + t_build), 1) if t_add + t_build else None,
+           "train_s": round(t_train, 3), "tron_iterations": st["iterations"], "cg_steps": st["cg_steps"],
+           "ms_per_cg_step": round(1e3 * t_train / max(st["cg_steps"], 1), 3), "xw_ms": "not measured", "xtv_ms": "not measured"}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

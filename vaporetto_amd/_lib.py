@@ -35,6 +35,16 @@ class ModelInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TrainParams(C.Structure):
+    _fields_ = [("charw", C.c_uint32), ("charn", C.c_uint32), ("typew", C.c_uint32), ("typen", C.c_uint32), ("dictn", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class TrainStats(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("cg_steps", C.c_uint32), ("gnorm0", C.c_double), ("gnorm", C.c_double),
+                ("objective", C.c_double)]
+
+
 # every symbol include/vaporetto_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -92,6 +102,16 @@ SIGNATURES = {
     "vpt_model_inspect": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(ModelInfo)]),
     "vpt_model_read_len": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vpt_predictor_info": (C.c_int, [_P, C.POINTER(ModelInfo)]),
+    "vpt_trainer_create": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(_P)]),
+    "vpt_trainer_destroy": (None, [_P]),
+    "vpt_trainer_add_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint]),
+    "vpt_trainer_add_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, C.c_uint, _P]),
+    "vpt_trainer_n_features": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
+    "vpt_trainer_csr": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "vpt_trainer_train": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vpt_trainer_model": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vpt_trainer_weights": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vpt_trainer_last_stats": (C.c_int, [_P, _P]),
 }
 
 _lib = None

@@ -323,6 +323,53 @@ class Sentence:
             self._set_default()
             raise
 
+    @staticmethod
+    def from_partial_annotation(text: str) -> "Sentence":
+        """sentence.rs:516-769, restated on the host (training input only): chars alternate with boundary marks '|' WordBoundary,
+        '-' NotWordBoundary, ' ' Unknown; '/' starts a tag of the char in front of it, '\\' escapes the next char of a tag."""
+        def err(msg):
+            return VaporettoError("InvalidArgument", "InvalidArgumentError: partial_annotation_text: " + msg)
+        if not text:
+            raise err("must contain at least one character")
+        chars, bounds, tags_tmp = [], [], []
+        tag, escape, is_char = None, False, True
+        for c in text:
+            if is_char:
+                if c == "\0":
+                    raise err("must not contain NULL")
+                chars.append(c)
+                tags_tmp.append([])
+                is_char = False
+                continue
+            if not escape and c == "\\":
+                escape = True
+            elif not escape and c in " -|":
+                if tag is not None:
+                    tags_tmp[-1].append(tag)
+                    tag = None
+                bounds.append({" ": CharacterBoundary.Unknown, "-": CharacterBoundary.NotWordBoundary, "|": CharacterBoundary.WordBoundary}[c])
+                is_char = True
+            elif not escape and c == "/":
+                if tag is not None:
+                    tags_tmp[-1].append(tag)
+                tag = ""
+            else:
+                escape = False
+                if tag is None:
+                    raise err("contains an invalid boundary character: '%s'" % c)
+                tag += c
+        if is_char:
+            raise err("invalid annotation")
+        if tag is not None:
+            tags_tmp[-1].append(tag)
+        n_tags = max(len(t) for t in tags_tmp)
+        s = Sentence()
+        s._parse_raw("".join(chars))
+        s._boundaries = np.array(bounds, dtype=np.uint8)
+        s._tags = [(t if t else None) for ts in tags_tmp for t in ts + [""] * (n_tags - len(ts))]
+        s._n_tags = n_tags
+        return s
+
     def as_raw_text(self) -> str:  # sentence.rs:782
         return self._text
 
@@ -1148,3 +1195,120 @@ def model_inspect(model_bytes: bytes, predict_tags: bool = False) -> dict:
     if st != _lib.VPT_OK:
         _raise(st)
     return mi.as_dict()
+
+
+class SolverType(enum.IntEnum):  # trainer.rs:20-45; only the primal TRON solvers 0 and 2 are implemented
+    L2RegularizedLogistic = 0
+    L2RegularizedL2LossSVCDual = 1
+    L2RegularizedL2LossSVC = 2
+    L2RegularizedL1LossSVCDual = 3
+    CrammerSingerSVC = 4
+    L1RegularizedL2LossSVC = 5
+    L1RegularizedLogistic = 6
+    L2RegularizedLogisticDual = 7
+
+
+class Trainer:
+    """Trainer (trainer.rs:201-490) for the boundary model, on the device (vpt_trainer_*).  Tag models are not trained: a sentence
+    that carries a tag is an error (the reference would train tag models from it, trainer.rs:349), unless `ignore_tags` is set, which
+    drops the tags (the train CLI's --ignore-tags) and writes a model without tag models."""
+
+    def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
+                 ignore_tags: bool = False):
+        self.ignore_tags = bool(ignore_tags)
+        self._L = _lib.load()
+        self._h = C.c_void_p()
+        self._charw, self._typew = charw, typew
+        self.dict_words = list(dict_words)
+        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, 0)
+        utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
+        st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
+        if st != _lib.VPT_OK:
+            self._h = None
+            _raise(st)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.vpt_trainer_destroy(self._h)
+            self._h = None
+
+    def add_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, labels: np.ndarray, fullwidth: bool = False) -> None:
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        st = self._L.vpt_trainer_add_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, len(byte_offsets) - 1, labels.ctypes.data,
+                                           _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def add_examples(self, sentences: Sequence["Sentence"]) -> None:
+        if not sentences:
+            return
+        if not self.ignore_tags:
+            for i, s in enumerate(sentences):
+                if any(t is not None for t in s.tags()):
+                    raise VaporettoError("InvalidArgument", "InvalidArgumentError: sentence %d: carries tags; tag models are not trained "
+                                         "(ignore_tags=True drops them)" % i)
+        utf8, boff = pack_texts([s.as_raw_text().encode("utf-8") for s in sentences])
+        labels = np.concatenate([np.asarray(s.boundaries(), dtype=np.uint8) for s in sentences])
+        self.add_packed(utf8, boff, labels)
+
+    def add_example(self, sentence: "Sentence") -> None:  # trainer.rs:321-350
+        self.add_examples([sentence])
+
+    def n_features(self) -> int:  # trainer.rs:489
+        n = C.c_size_t()
+        st = self._L.vpt_trainer_n_features(self._h, C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return n.value
+
+    def csr(self):
+        """(row_ptr, cols, counts) of the design matrix: rows = boundaries in corpus order, columns = features in key order."""
+        nr, nz = C.c_size_t(), C.c_size_t()
+        st = self._L.vpt_trainer_csr(self._h, None, None, None, 0, C.byref(nr), C.byref(nz))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        ptr = np.zeros(nr.value + 1, np.uint64)
+        cols = np.zeros(max(nz.value, 1), np.uint32)
+        cnt = np.zeros(max(nz.value, 1), np.uint16)
+        st = self._L.vpt_trainer_csr(self._h, ptr.ctypes.data, cols.ctypes.data, cnt.ctypes.data, len(cols), C.byref(nr), C.byref(nz))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return ptr, cols[:nz.value], cnt[:nz.value]
+
+    def train_bytes(self, epsilon: float, cost: float, solver: int) -> bytes:
+        need = C.c_size_t()
+        st = self._L.vpt_trainer_train(self._h, (C.c_double * 2)(float(epsilon), float(cost)), int(solver), None, 0, C.byref(need))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        buf = (C.c_uint8 * need.value)()
+        st = self._L.vpt_trainer_model(self._h, buf, need.value, C.byref(need))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return bytes(buf)
+
+    def train(self, epsilon: float, cost: float, solver: int) -> Model:  # trainer.rs:352-487
+        return Model.read_slice(self.train_bytes(epsilon, cost, solver))[0]
+
+    def weights(self):
+        """After train: (fp64 weights in key order, bias, keys as Python ints)."""
+        n = C.c_size_t()
+        st = self._L.vpt_trainer_weights(self._h, None, None, None, 0, C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        w = np.zeros(max(n.value, 1), np.float64)
+        k = np.zeros(2 * max(n.value, 1), np.uint64)
+        b = C.c_double()
+        st = self._L.vpt_trainer_weights(self._h, w.ctypes.data, C.addressof(b), k.ctypes.data, n.value, C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        keys = [int(k[2 * j]) | (int(k[2 * j + 1]) << 64) for j in range(n.value)]
+        return w[:n.value], b.value, keys
+
+    def last_stats(self) -> dict:
+        s = _lib.TrainStats()
+        st = self._L.vpt_trainer_last_stats(self._h, C.addressof(s))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return {k: getattr(s, k) for k, _ in s._fields_}

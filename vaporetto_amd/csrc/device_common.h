@@ -196,6 +196,20 @@ __device__ __forceinline__ uint32_t esc_flags(uint32_t x) {
 __device__ __forceinline__ uint32_t esc_nibble(uint32_t x) { return byte_flags_to_nibble(esc_flags(x)); }
 __device__ __forceinline__ uint32_t esc_mask16(const uint4& v) { return flag_bytes_to_mask16(esc_flags(v.x), esc_flags(v.y), esc_flags(v.z), esc_flags(v.w)); }
 
+// compare-and-swap of a 64-bit word (the trainer's key table).  The CPU emulator has no atomicCAS; its lanes switch only at cross-lane
+// operations, so a plain compare-and-swap is atomic there.
+#ifdef VPT_HIPEMU
+__device__ __forceinline__ uint64_t atomic_cas_u64(uint64_t* p, uint64_t expected, uint64_t desired) {
+    const uint64_t old = *p;
+    if (old == expected) *p = desired;
+    return old;
+}
+#else
+__device__ __forceinline__ uint64_t atomic_cas_u64(uint64_t* p, uint64_t expected, uint64_t desired) {
+    return uint64_t(atomicCAS(reinterpret_cast<unsigned long long*>(p), (unsigned long long)expected, (unsigned long long)desired));
+}
+#endif
+
 // scalar value of the UTF-8 sequence whose four bytes (lead first) are packed little-endian in b4
 __device__ __forceinline__ uint32_t utf8_scalar(uint32_t b4) {
     const uint32_t b0 = b4 & 0xFF, b1 = (b4 >> 8) & 0x3F, b2 = (b4 >> 16) & 0x3F, b3 = (b4 >> 24) & 0x3F;

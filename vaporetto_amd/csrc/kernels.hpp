@@ -279,4 +279,51 @@ hipError_t launch_assign_tiles_cut(const ScoreParams& P, const CutGeometry& G, u
 hipError_t launch_score_tiles(const ScoreParams& P, int chunks, uint32_t n_tiles, hipStream_t stream);
 hipError_t launch_score_slow(const ScoreParams& P, int chunks, uint32_t n_blocks, hipStream_t stream);
 
+// boundary-model training (kernels_train.hip)
+constexpr uint32_t kCharMaskTrain = 0x1FFFFFu;   // the scalar value of a decode_chars cps word (scored | CharacterType << 24)
+struct TrainFeatParams {
+    const uint32_t* cps;        // decode_chars' words: sentence i's char c at ooff[i] + i + c
+    const uint64_t* ooff;       // [n_sent + 1] vpt_count_boundaries' layout
+    uint64_t n_sent, total_b;
+    uint32_t charw, charn, typew, typen, dictn, dict_maxlen;
+    const uint32_t* dict_slots; // open addressing by the hash of (code points, length): word index + 1, 0 empty
+    uint64_t dict_mask;         // slots - 1; 0: no dictionary
+    const uint32_t* dict_cps;   // the words' code points, word w at dict_off[w] .. dict_off[w + 1]
+    const uint64_t* dict_off;
+    uint32_t* counts;           // count pass: features per boundary
+    const uint64_t* row_off;    // emit pass: where boundary b's keys start
+    uint64_t* keys;             // emit pass: two words per key (low, high)
+};
+hipError_t train_features(const TrainFeatParams& P, bool emit, hipStream_t st);
+uint64_t train_scan_scratch(uint64_t n);
+hipError_t train_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);   // out[n + 1], exclusive
+hipError_t train_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);
+hipError_t train_insert(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint64_t* rep, uint32_t* flag, hipStream_t st);
+hipError_t train_compact(const uint64_t* keys, const uint64_t* rep, const uint64_t* pos, uint64_t nnz, uint64_t* dkeys, uint64_t* slot, hipStream_t st);
+uint64_t train_radix_scratch(uint64_t n);
+// word_shifts[p] = u32 word << 8 | bit shift of pass p (least significant digit first)
+hipError_t train_radix_sort(const uint32_t* base, uint32_t stride, const uint32_t* word_shifts, uint32_t n_passes, uint64_t n, uint32_t* idx,
+                            uint32_t* idx_tmp, uint64_t* hist, uint64_t* hist_scan, uint64_t* scan_scratch, hipStream_t st);
+hipError_t train_ids(const uint32_t* order, uint64_t nd, uint32_t* col_of, const uint64_t* rep, const uint64_t* slot, uint64_t nnz, uint32_t* ids,
+                     const uint64_t* dkeys, uint64_t* sorted_keys, hipStream_t st);
+hipError_t train_row_sort(uint32_t* ids, const uint64_t* row_off, uint64_t nrows, uint32_t* merged, hipStream_t st);
+hipError_t train_row_merge(const uint32_t* ids, const uint64_t* row_off, const uint64_t* csr_ptr, uint64_t nrows, uint32_t* cols, uint16_t* vals,
+                           uint32_t* rows, uint32_t* status, hipStream_t st);
+hipError_t train_csc_fill(const uint32_t* order, const uint32_t* cols, const uint16_t* vals, const uint32_t* rows, uint64_t nnz, uint32_t* crow,
+                          uint16_t* cval, uint64_t* cptr, hipStream_t st);
+hipError_t train_seg_count(const uint64_t* ptr, uint64_t nd, uint64_t* cnt, hipStream_t st);
+hipError_t train_seg_col(const uint64_t* nptr, uint64_t nd, uint32_t* seg_col, hipStream_t st);
+hipError_t train_xv(const uint64_t* csr_ptr, const uint32_t* cols, const uint16_t* vals, uint64_t nrows, const double* v, uint64_t bias_col, double* out,
+                    hipStream_t st);
+hipError_t train_xtv_level(const uint64_t* ptr, const uint64_t* nptr, const uint32_t* seg_col, uint64_t nseg, const double* in, const uint32_t* crow,
+                           const uint16_t* cval, const double* u, double* out, hipStream_t st);
+uint64_t train_dot_partials(uint64_t n);
+hipError_t train_dot(const double* a, const double* b, uint64_t n, double* partial, hipStream_t st);
+hipError_t train_axpy(uint64_t n, double alpha, const double* x, double* y, hipStream_t st);
+hipError_t train_xpby(uint64_t n, const double* x, double beta, double* y, hipStream_t st);
+hipError_t train_add(uint64_t n, const double* a, const double* b, const double* bias_sum, double* y, hipStream_t st);
+hipError_t train_scale_rows(uint64_t n, const double* d, double* t, hipStream_t st);
+hipError_t train_loss(uint64_t n, const double* z, const double* y, double c, int solver, double* loss, hipStream_t st);
+hipError_t train_grad_rows(uint64_t n, const double* z, const double* y, double c, int solver, double* gz, double* D, hipStream_t st);
+
 }  // namespace vpt

@@ -1,0 +1,153 @@
+"""`python -m vaporetto_amd.train`: the reference's `train` CLI (train/src/main.rs) over this library.
+
+Reads tokenized (--tok) and partially annotated (--part) corpora and word dictionaries (--dict), normalises them with
+KyteaFullwidthFilter unless --no-norm, trains the boundary model on the device (api.Trainer: features, ids and the TRON solver all
+run there) and writes the model un-compressed (the `evaluate` CLI reads it as it is; the reference writes zstd).  Progress goes to
+stderr as the reference prints it.  Tokenized lines are parsed by the library's parser (vpt_parse_tokenized_batch) in chunks.
+
+Divergences: tag models are not trained, so a corpus or dictionary line that carries a tag is an error naming the file and line
+unless --ignore-tags (ours) drops the tags; only solvers 0 and 2 are implemented; --zstd-workers does not exist."""
+import argparse
+import sys
+
+import numpy as np
+
+from .evaluate import split_lines
+
+_CHUNK_LINES = 1 << 16
+
+
+class CorpusError(Exception):
+    pass
+
+
+def _lines(path):
+    with open(path, "rb") as fh:
+        try:
+            return split_lines(fh.read())
+        except UnicodeDecodeError:
+            raise CorpusError("%s: stream did not contain valid UTF-8" % path) from None
+
+
+def _parse_tokenized(path, lines, ignore_tags):
+    """Chunks of vpt_parse_tokenized_batch: yields (raw utf8, raw byte offsets, labels) per chunk; errors name the file and line."""
+    from . import api
+    for c0 in range(0, len(lines), _CHUNK_LINES):
+        chunk = [ln.encode("utf-8") for ln in lines[c0:c0 + _CHUNK_LINES]]
+        try:
+            p = api.parse_tokenized_host(chunk)
+        except api.VaporettoError as e:
+            msg = str(e)
+            k = msg.rfind(" (line ")
+            if k >= 0:
+                line = c0 + int(msg[k + 7:msg.index(")", k)]) + 1
+                msg = msg[:k]
+                raise CorpusError("%s:%d: %s" % (path, line, msg)) from None
+            raise CorpusError("%s: %s" % (path, msg)) from None
+        if not ignore_tags and len(p["tag_bytes"]):
+            # the first line with a non-empty tag: per char its tags tag_index[g] .. tag_index[g + 1]
+            span = np.diff(p["span_offsets"].astype(np.int64)) > 0
+            has = np.concatenate([[0], np.cumsum(span)])
+            oo, S = p["out_offsets"].astype(np.int64), len(chunk)
+            first = oo[:S] + np.arange(S)
+            last = oo[1:] + np.arange(1, S + 1)
+            ti = p["tag_index"].astype(np.int64)
+            tagged = has[ti[last]] - has[ti[first]] > 0
+            i = int(np.argmax(tagged))
+            if tagged[i]:
+                raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them)" % (path, c0 + i + 1))
+        yield p["raw"], p["raw_offsets"], p["labels"], p
+
+
+def _parse_partial(path, lines, ignore_tags):
+    from . import api
+    sents = []
+    for i, ln in enumerate(lines):
+        try:
+            s = api.Sentence.from_partial_annotation(ln)
+        except api.VaporettoError as e:
+            raise CorpusError("%s:%d: %s" % (path, i + 1, e)) from None
+        if not ignore_tags and any(t is not None for t in s.tags()):
+            raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them)" % (path, i + 1))
+        sents.append(s)
+    return sents
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="train", description="A program to train models of Vaporetto.")
+    ap.add_argument("--tok", action="append", default=[], help="A tokenized training corpus")
+    ap.add_argument("--part", action="append", default=[], help="A partially annotated training corpus")
+    ap.add_argument("--dict", action="append", default=[], help="A word dictionary file")
+    ap.add_argument("--model", required=True, help="The file to write the trained model to")
+    ap.add_argument("--charw", type=int, default=3, help="The character window to use for word segmentation")
+    ap.add_argument("--charn", type=int, default=3, help="The character n-gram length to use for word segmentation")
+    ap.add_argument("--typew", type=int, default=3, help="The character type window to use for word segmentation")
+    ap.add_argument("--typen", type=int, default=3, help="The character type n-gram length to use for word segmentation")
+    ap.add_argument("--dictn", type=int, default=4, help="Dictionary words longer than this value will be grouped together")
+    ap.add_argument("--eps", type=float, default=0.01, help="The epsilon stopping criterion for classifier training")
+    ap.add_argument("--cost", type=float, default=1.0, help="The cost hyperparameter for classifier training")
+    ap.add_argument("--solver", type=int, required=True, choices=range(8), metavar="{0..7}",
+                    help="The solver. {0, 1, 2, 3, 4, 5, 6, 7} (only 0 and 2 are implemented here)")
+    ap.add_argument("--no-norm", action="store_true", help="Do not normalize training data.")
+    ap.add_argument("--ignore-tags", action="store_true", help="Drop tags of the corpora and dictionaries (no tag models are trained).")
+    args = ap.parse_args(argv)
+    if not args.tok and not args.part:
+        ap.error("one of --tok or --part is required")
+
+    from . import api
+    fw = api.KyteaFullwidthFilter()
+    try:
+        print("Loading dataset...", file=sys.stderr)
+        batches, n_sent = [], 0
+        for path in args.tok:
+            print("Loading %r ..." % path, file=sys.stderr)
+            lines = _lines(path)
+            for raw, roff, labels, _ in _parse_tokenized(path, lines, args.ignore_tags):
+                batches.append((raw, roff, labels))
+            n_sent += len(lines)
+            print("# of sentences: %d" % n_sent, file=sys.stderr)
+        for path in args.part:
+            print("Loading %r ..." % path, file=sys.stderr)
+            sents = _parse_partial(path, _lines(path), args.ignore_tags)
+            if sents:
+                utf8, boff = api.pack_texts([s.as_raw_text().encode("utf-8") for s in sents])
+                batches.append((utf8, boff, np.concatenate([np.asarray(s.boundaries(), np.uint8) for s in sents])))
+            n_sent += len(sents)
+            print("# of sentences: %d" % n_sent, file=sys.stderr)
+        words = set()
+        for path in args.dict:
+            print("Loading %r ..." % path, file=sys.stderr)
+            lines = _lines(path)
+            for raw, roff, labels, p in _parse_tokenized(path, lines, args.ignore_tags):
+                oo = p["out_offsets"]
+                for i in range(len(roff) - 1):
+                    text = bytes(raw[int(roff[i]):int(roff[i + 1])]).decode("utf-8")
+                    if not args.no_norm:
+                        text = fw.filter(text)   # a 1:1 char map: the boundaries keep their places
+                    s = api.Sentence.from_raw(text)
+                    s._boundaries = labels[int(oo[i]):int(oo[i + 1])].copy()
+                    words.update(s.iter_tokens())
+            print("# of words: %d" % len(words), file=sys.stderr)
+        dictionary = sorted(words)   # BTreeSet<String>: code point order (main.rs:132-161)
+
+        print("Extracting into features...", file=sys.stderr)
+        trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags)
+        for utf8, boff, labels in batches:
+            trainer.add_packed(utf8, boff, labels, fullwidth=not args.no_norm)
+        print("# of features: %d" % trainer.n_features(), file=sys.stderr)
+        print("Start training...", file=sys.stderr)
+        model = trainer.train_bytes(args.eps, args.cost, args.solver)
+        print("Finish training.", file=sys.stderr)
+    except CorpusError as e:
+        print("Error: %s" % e, file=sys.stderr)
+        return 1
+    except api.VaporettoError as e:
+        print("Error: %s" % e, file=sys.stderr)
+        return 1
+    with open(args.model, "wb") as fh:
+        fh.write(model)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
