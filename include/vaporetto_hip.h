@@ -462,7 +462,8 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * Solvers: 0 (L2R_LR) and 2 (L2R_L2LOSS_SVC), the primal TRON solvers of liblinear as scikit-learn bundles it (CG without a
  * preconditioner): the reference's newer liblinear preconditions its CG, so weights agree with it to the stopping tolerance, not bit
  * for bit.  Sums run in a fixed order: the same examples and arguments give byte-identical models on every run.
- * Divergences: tags are not trained (the caller rejects or drops them, see the train CLI's --ignore-tags); solvers 1, 3-7 are
+ * Divergences: tag models are trained only by a trainer created with VPT_TRAIN_TAGS (below), without it the caller rejects or drops tags
+ * (the train CLI's --ignore-tags); solvers 1, 3-7 are
  * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
  * VPT_INVALID_ARGUMENT (the reference unwraps or fails in liblinear); typew > charw is VPT_INVALID_ARGUMENT (the reference panics).
  * Limits: 1 <= charn, typen <= 5; charw, typew <= 16; dictn >= 1 with a non-empty dictionary; fewer than 2^32 boundaries and feature
@@ -477,7 +478,8 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * are assigned, about 60 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
- *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0.
+ *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0 or VPT_TRAIN_TAGS (any other bit is
+ *   VPT_INVALID_ARGUMENT "flags: ...").
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
  * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's raw text, offsets and labels): the
@@ -494,8 +496,9 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * vpt_trainer_last_stats: TRON iterations, CG steps, the gradient norms at w = 0 and at the result, and the objective. */
 typedef struct vpt_train_params {
     uint32_t charw, charn, typew, typen, dictn;
-    uint32_t flags; /* 0 */
+    uint32_t flags; /* 0 or VPT_TRAIN_TAGS */
 } vpt_train_params;
+enum { VPT_TRAIN_TAGS = 1 };
 typedef struct vpt_train_stats {
     uint32_t iterations;
     uint32_t cg_steps;
@@ -520,6 +523,78 @@ vpt_status vpt_trainer_train(void *t, const void *eps_cost, int solver, uint8_t 
 vpt_status vpt_trainer_model(const void *t, uint8_t *model_out, size_t capacity, size_t *needed);
 vpt_status vpt_trainer_weights(void *t, void *weights_out, void *bias_out, uint64_t *keys_out, size_t capacity, size_t *n_features);
 vpt_status vpt_trainer_last_stats(const void *t, void *stats);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Tag models: TagTrainer                                            (tag_trainer.rs, trainer.rs:231-238, 338, 449)
+ *
+ * Opt-in: a trainer created with VPT_TRAIN_TAGS in params->flags.  Without it every call below is VPT_INVALID_ARGUMENT "tags: the trainer
+ * was created without VPT_TRAIN_TAGS", and the trainer behaves and writes models exactly as before.
+ * Examples: every token of Sentence::iter_tokens (tokens with an Unknown boundary inside are skipped) of a sentence with n_tags > 0, its tags
+ * those of its last char; features: the char and CharacterType n-grams that cover the token and n + 1 <= charn (typen) more chars,
+ * rel_position of them to its right (tag_trainer.rs:79-100).  Per surface (byte order) and slot with at least two candidate tags (ids in
+ * order of first appearance) a 0/1 problem with a bias feature is trained: one binary problem for two candidates (class 0 positive, class 1 its
+ * negation), one-vs-rest for more, each with liblinear's tolerance eps * max(min(pos, neg), 1) / rows.  Quantisation per slot:
+ * trunc(w / (max(1e-6, max |w|) / 32767)); an n-gram entry exists where a class's quantised weight is not zero.
+ * Where it runs: the examples, their chars and their feature keys are extracted on the device and stay there; surfaces get their ids (byte
+ * order) from a device hash table and radix sort, the examples are sorted by (surface, corpus order), and the keys of all problems are
+ * deduplicated, numbered and written as CSR and CSC in a few launches over concatenated arrays.  The host interns the tag strings and, from
+ * 8 bytes of ids an example, picks each problem's candidates, rows and y.  Every problem with 7 * (features + 1) + 3 * rows <= 7424 doubles is solved by one workgroup of one kernel
+ * launch (TRON with its vectors in LDS), a larger one by the global-memory TRON of the boundary model, a class at a time.
+ * Divergences: the in-kernel CG loop stops after 16 * (features + 1) + 64 steps (exact CG needs at most features + 1; liblinear's loop and the
+ * global-memory solver have no cap), so that a non-finite problem cannot spin on the device.  A HIP error (not an argument error) after the
+ * boundary examples of a batch were added leaves them added without the batch's tag examples: destroy the trainer then.
+ * Limits: fewer than 2^32 chars per batch; fewer than 2^24 - 1 distinct surfaces (the predictor's limit: more is VPT_INVALID_ARGUMENT at train);
+ * a tag must be UTF-8 without NUL (VPT_INVALID_ARGUMENT naming the sentence); fewer than 2^32 chars, tagged tokens, feature occurrences and
+ * nonzeros over all problems in a trainer.  Memory, on the device until the trainer is destroyed: 4 bytes per char, 16 per tagged token and 16
+ * per feature occurrence; 20 more per char while a batch is added; while the problems are built about 45 bytes per nonzero (the (key,
+ * problem) records and the sort), of which 8 per nonzero and 4 per row stay.  The host keeps about 16 bytes per tagged token and slot.
+ * No buffer is read past its stated size.
+ *
+ * vpt_trainer_add_tagged_batch[_device]: vpt_trainer_add_batch[_device]'s arguments plus the gold tags as vpt_parse_tokenized_batch[_device]
+ *   writes them: n_tags[S], tag_index[chars + 1], span_offsets[n_spans + 1], tag_bytes[n_tag_bytes] (an empty span is None).  The CSR is
+ *   checked on the device before an offset is followed: VPT_INVALID_ARGUMENT "tag_index: ..." / "span_offsets: ...", nothing added.  The
+ *   boundary examples are added exactly as the untagged call adds them.
+ * vpt_trainer_set_tag_dictionary: replaces the tag dictionary: surface i is surfaces_utf8[surface_offsets[i] .. [i+1]) with n_tags[i] slots,
+ *   whose tags are the next n_tags[i] spans of span_offsets into tag_bytes (empty: None); the first occurrence of a surface wins.  A surface
+ *   with a tag and no example gets a model of fixed tags.  Host only.
+ * vpt_trainer_train: with VPT_TRAIN_TAGS also trains the tag models and writes them into the model.
+ * vpt_trainer_set_tag_path: 0 (default) picks the solver by size, 1 sends every problem through the global-memory solver (tests, benchmarks).
+ * vpt_trainer_n_tag_problems: the trained problems (and the tag models, fixed ones included).
+ * vpt_trainer_tag_problem: problem i as a vpt_tag_problem_info, and into any non-NULL output: the surface, the candidates in id order
+ *   (cand_offsets[n_classes + 1] into cand_bytes), the sorted feature keys (two words each, low first: the boundary trainer's layout, the
+ *   chars being the left context then the right context, length = their number, rel_position = those to the right), the 0/1 CSR
+ *   (row_ptr[n_rows + 1], cols[nnz]) and the tag id per row.  info.path: 0 before training, 1 in-kernel, 2 global-memory.
+ * vpt_trainer_tag_weights: after train, problem i's fp64 weights [n_classes][n_features + 1] (the bias last) and n_classes vpt_train_stats.
+ * vpt_trainer_tag_summary: the last training's problems and seconds per path. */
+typedef struct vpt_tag_problem_info {
+    uint32_t slot, n_classes, path, model;
+    uint64_t n_rows, n_features, nnz, surface_bytes, cand_bytes;
+    double seconds_setup, seconds_solve; /* path 2 after train: the matrix upload and its CSC; the TRON runs of the classes */
+} vpt_tag_problem_info;
+typedef struct vpt_tag_train_summary {
+    uint64_t problems_in_kernel, problems_large;
+    double seconds_in_kernel;     /* upload, the one launch, and the weights back */
+    double seconds_large;         /* the large path, setup included */
+    double seconds_large_solve;   /* of which the TRON runs */
+    double seconds_construction;  /* the last build: surface ids, grouping and the problems' matrices */
+    double seconds_add_host;      /* the host's tag interning inside the add calls so far */
+    double seconds_construction_host; /* of seconds_construction, the host's grouping by tag (candidates, rows, y) */
+} vpt_tag_train_summary;
+vpt_status vpt_trainer_add_tagged_batch(void *t, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, const uint8_t *labels,
+                                        const uint32_t *n_tags, const uint64_t *tag_index, const uint64_t *span_offsets, const uint8_t *tag_bytes,
+                                        uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags);
+vpt_status vpt_trainer_add_tagged_batch_device(void *t, const uint8_t *d_utf8, const uint64_t *d_byte_offsets, const uint64_t *d_out_offsets,
+                                               size_t n_sentences, uint64_t total_boundaries, const uint8_t *d_labels, const uint32_t *d_n_tags,
+                                               const uint64_t *d_tag_index, const uint64_t *d_span_offsets, const uint8_t *d_tag_bytes,
+                                               uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, void *hip_stream);
+vpt_status vpt_trainer_set_tag_dictionary(void *t, const uint8_t *surfaces_utf8, const uint64_t *surface_offsets, size_t n_surfaces,
+                                          const uint32_t *n_tags, const uint64_t *span_offsets, const uint8_t *tag_bytes);
+vpt_status vpt_trainer_set_tag_path(void *t, int mode);
+vpt_status vpt_trainer_n_tag_problems(void *t, size_t *n_problems, size_t *n_models);
+vpt_status vpt_trainer_tag_problem(void *t, size_t i, void *info, uint8_t *surface_out, uint8_t *cand_bytes_out, uint64_t *cand_offsets_out,
+                                   uint64_t *keys_out, uint64_t *row_ptr_out, uint32_t *cols_out, uint32_t *y_out);
+vpt_status vpt_trainer_tag_weights(void *t, size_t i, void *weights_out, size_t capacity, void *stats_out);
+vpt_status vpt_trainer_tag_summary(const void *t, void *summary);
 
 #ifdef __cplusplus
 }

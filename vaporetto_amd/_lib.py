@@ -45,6 +45,21 @@ class TrainStats(C.Structure):
                 ("objective", C.c_double)]
 
 
+VPT_TRAIN_TAGS = 1
+
+
+class TagProblemInfo(C.Structure):
+    _fields_ = [("slot", C.c_uint32), ("n_classes", C.c_uint32), ("path", C.c_uint32), ("model", C.c_uint32), ("n_rows", C.c_uint64),
+                ("n_features", C.c_uint64), ("nnz", C.c_uint64), ("surface_bytes", C.c_uint64), ("cand_bytes", C.c_uint64),
+                ("seconds_setup", C.c_double), ("seconds_solve", C.c_double)]
+
+
+class TagTrainSummary(C.Structure):
+    _fields_ = [("problems_in_kernel", C.c_uint64), ("problems_large", C.c_uint64), ("seconds_in_kernel", C.c_double),
+                ("seconds_large", C.c_double), ("seconds_large_solve", C.c_double), ("seconds_construction", C.c_double),
+                ("seconds_add_host", C.c_double), ("seconds_construction_host", C.c_double)]
+
+
 # every symbol include/vaporetto_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -112,6 +127,15 @@ SIGNATURES = {
     "vpt_trainer_model": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vpt_trainer_weights": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vpt_trainer_last_stats": (C.c_int, [_P, _P]),
+    "vpt_trainer_add_tagged_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint]),
+    "vpt_trainer_add_tagged_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
+                                                      C.c_uint, _P]),
+    "vpt_trainer_set_tag_dictionary": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "vpt_trainer_set_tag_path": (C.c_int, [_P, C.c_int]),
+    "vpt_trainer_n_tag_problems": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "vpt_trainer_tag_problem": (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_trainer_tag_weights": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
+    "vpt_trainer_tag_summary": (C.c_int, [_P, _P]),
 }
 
 _lib = None

@@ -1209,22 +1209,71 @@ class SolverType(enum.IntEnum):  # trainer.rs:20-45; only the primal TRON solver
 
 
 class Trainer:
-    """Trainer (trainer.rs:201-490) for the boundary model, on the device (vpt_trainer_*).  Tag models are not trained: a sentence
-    that carries a tag is an error (the reference would train tag models from it, trainer.rs:349), unless `ignore_tags` is set, which
-    drops the tags (the train CLI's --ignore-tags) and writes a model without tag models."""
+    """Trainer (trainer.rs:201-490), on the device (vpt_trainer_*).  By default only the boundary model is trained: a sentence that
+    carries a tag is an error unless `ignore_tags` is set, which drops the tags (the train CLI's --ignore-tags) and writes a model
+    without tag models.  With `train_tags=True` the tags are kept and the tag models are trained too (tag_trainer.rs);
+    `tag_dictionary` is then the reference's tag dictionary: tagged Sentences, or (surface, tags) pairs, whose first occurrence of a
+    surface gives the tags of a surface the corpus does not contain."""
 
     def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
-                 ignore_tags: bool = False):
+                 ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = ()):
+        if ignore_tags and train_tags:
+            raise ValueError("ignore_tags and train_tags exclude each other")
+        if tag_dictionary and not train_tags:
+            raise ValueError("tag_dictionary needs train_tags=True")
         self.ignore_tags = bool(ignore_tags)
+        self.train_tags = bool(train_tags)
         self._L = _lib.load()
         self._h = C.c_void_p()
         self._charw, self._typew = charw, typew
         self.dict_words = list(dict_words)
-        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, 0)
+        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, _lib.VPT_TRAIN_TAGS if train_tags else 0)
         utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
         st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
         if st != _lib.VPT_OK:
             self._h = None
+            _raise(st)
+        if tag_dictionary:
+            self.set_tag_dictionary(tag_dictionary)
+
+    def set_tag_dictionary(self, entries: Sequence) -> None:
+        """trainer.rs:231-238: per token of the entries (Sentences, or (surface, [tag or None, ...]) pairs) its tags; the first occurrence wins."""
+        pairs = []
+        for e in entries:
+            if isinstance(e, Sentence):
+                pairs += [(tk.surface(), tk.tags()) for tk in e.tokens()]
+            else:
+                pairs.append((e[0], list(e[1])))
+        surf, soff = pack_texts([p[0].encode("utf-8") for p in pairs])
+        nt = np.array([len(p[1]) for p in pairs] + [0], np.uint32)
+        tb, so = pack_texts([(t or "").encode("utf-8") for p in pairs for t in p[1]])
+        tb = np.concatenate([tb, np.zeros(1, np.uint8)])
+        surf = np.concatenate([surf, np.zeros(1, np.uint8)])
+        st = self._L.vpt_trainer_set_tag_dictionary(self._h, surf.ctypes.data, soff.ctypes.data, len(pairs), nt.ctypes.data, so.ctypes.data, tb.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def add_packed_tagged(self, utf8: np.ndarray, byte_offsets: np.ndarray, labels: np.ndarray, n_tags: np.ndarray, tag_index: np.ndarray,
+                          span_offsets: np.ndarray, tag_bytes: np.ndarray, fullwidth: bool = False) -> None:
+        """The raw text, labels and tags as parse_tokenized_host returns them (vpt_trainer_add_tagged_batch); needs train_tags=True."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        n_tags = np.ascontiguousarray(n_tags, dtype=np.uint32)
+        tag_index = np.ascontiguousarray(tag_index, dtype=np.uint64)
+        span_offsets = np.ascontiguousarray(span_offsets, dtype=np.uint64)
+        tag_bytes = np.ascontiguousarray(tag_bytes, dtype=np.uint8)
+        S = len(byte_offsets) - 1
+        if len(n_tags) != S or len(span_offsets) < 1:
+            raise ValueError("n_tags needs an entry per sentence and span_offsets at least one entry")
+        n_chars = S + len(labels)
+        if len(tag_index) != n_chars + 1:
+            raise ValueError("tag_index needs an entry per char and one more")
+        tb = tag_bytes if len(tag_bytes) else np.zeros(1, np.uint8)
+        st = self._L.vpt_trainer_add_tagged_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, labels.ctypes.data, n_tags.ctypes.data,
+                                                  tag_index.ctypes.data, span_offsets.ctypes.data, tb.ctypes.data, len(span_offsets) - 1,
+                                                  len(tag_bytes), _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
+        if st != _lib.VPT_OK:
             _raise(st)
 
     def __del__(self):
@@ -1241,17 +1290,32 @@ class Trainer:
         if st != _lib.VPT_OK:
             _raise(st)
 
-    def add_examples(self, sentences: Sequence["Sentence"]) -> None:
+    def add_examples(self, sentences: Sequence["Sentence"], fullwidth: bool = False) -> None:
         if not sentences:
             return
-        if not self.ignore_tags:
+        if not self.ignore_tags and not self.train_tags:
             for i, s in enumerate(sentences):
                 if any(t is not None for t in s.tags()):
                     raise VaporettoError("InvalidArgument", "InvalidArgumentError: sentence %d: carries tags; tag models are not trained "
-                                         "(ignore_tags=True drops them)" % i)
+                                         "(ignore_tags=True drops them, train_tags=True trains them)" % i)
         utf8, boff = pack_texts([s.as_raw_text().encode("utf-8") for s in sentences])
         labels = np.concatenate([np.asarray(s.boundaries(), dtype=np.uint8) for s in sentences])
-        self.add_packed(utf8, boff, labels)
+        if not self.train_tags:
+            self.add_packed(utf8, boff, labels, fullwidth=fullwidth)
+            return
+        # the parser's CSR from Sentence.tags(): per char its slots up to the last Some, a None among them an empty span
+        n_tags, tindex, spans = [], [0], []
+        for s in sentences:
+            nt, tags = s.n_tags(), s.tags()
+            n_tags.append(nt)
+            for c in range(len(s)):
+                row = list(tags[c * nt:(c + 1) * nt])
+                while row and row[-1] is None:
+                    row.pop()
+                spans += [(t or "").encode("utf-8") for t in row]
+                tindex.append(len(spans))
+        tb, so = pack_texts(spans)
+        self.add_packed_tagged(utf8, boff, labels, np.array(n_tags, np.uint32), np.array(tindex, np.uint64), so, tb, fullwidth=fullwidth)
 
     def add_example(self, sentence: "Sentence") -> None:  # trainer.rs:321-350
         self.add_examples([sentence])
@@ -1312,3 +1376,83 @@ class Trainer:
         if st != _lib.VPT_OK:
             _raise(st)
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+    # ---- tag models (train_tags=True)
+    def set_tag_path(self, mode: int) -> None:
+        """0: the solver is picked by a problem's size; 1: every tag problem goes through the global-memory solver."""
+        st = self._L.vpt_trainer_set_tag_path(self._h, int(mode))
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def n_tag_models(self) -> int:
+        n, m = C.c_size_t(), C.c_size_t()
+        st = self._L.vpt_trainer_n_tag_problems(self._h, C.byref(n), C.byref(m))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return m.value
+
+    def tag_problems(self) -> List[dict]:
+        """The trained (surface, slot) problems in model order: surface, slot, candidates in id order, rows, sorted keys (Python ints),
+        row_ptr, cols, y, and `path` (0 before training, 1 in-kernel, 2 global-memory)."""
+        n = C.c_size_t()
+        st = self._L.vpt_trainer_n_tag_problems(self._h, C.byref(n), None)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        out = []
+        for i in range(n.value):
+            info = _lib.TagProblemInfo()
+            st = self._L.vpt_trainer_tag_problem(self._h, i, C.addressof(info), None, None, None, None, None, None, None)
+            if st != _lib.VPT_OK:
+                _raise(st)
+            surf = np.zeros(info.surface_bytes + 1, np.uint8)
+            cb = np.zeros(info.cand_bytes + 1, np.uint8)
+            co = np.zeros(info.n_classes + 1, np.uint64)
+            keys = np.zeros(2 * info.n_features + 2, np.uint64)
+            rp = np.zeros(info.n_rows + 1, np.uint64)
+            cols = np.zeros(info.nnz + 1, np.uint32)
+            y = np.zeros(info.n_rows + 1, np.uint32)
+            st = self._L.vpt_trainer_tag_problem(self._h, i, C.addressof(info), surf.ctypes.data, cb.ctypes.data, co.ctypes.data, keys.ctypes.data,
+                                                 rp.ctypes.data, cols.ctypes.data, y.ctypes.data)
+            if st != _lib.VPT_OK:
+                _raise(st)
+            out.append({"surface": bytes(surf[:info.surface_bytes]).decode("utf-8"), "slot": info.slot, "path": info.path, "model": info.model,
+                        "candidates": [bytes(cb[int(co[c]):int(co[c + 1])]).decode("utf-8") for c in range(info.n_classes)],
+                        "n_rows": info.n_rows, "keys": [int(keys[2 * j]) | (int(keys[2 * j + 1]) << 64) for j in range(info.n_features)],
+                        "row_ptr": rp, "cols": cols[:info.nnz], "y": y[:info.n_rows]})
+        return out
+
+    def _tag_weights_stats(self, i: int, n_classes: int, n_features: int):
+        w = np.zeros((n_classes, n_features + 1), np.float64)
+        stats = (_lib.TrainStats * n_classes)()
+        st = self._L.vpt_trainer_tag_weights(self._h, i, w.ctypes.data, w.size, C.addressof(stats))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return w, [{k: getattr(s, k) for k, _ in s._fields_} for s in stats]
+
+    def tag_weights(self, i: int) -> np.ndarray:
+        """After train: problem i's fp64 weights [classes][features + 1], the bias last."""
+        info = _lib.TagProblemInfo()
+        st = self._L.vpt_trainer_tag_problem(self._h, i, C.addressof(info), None, None, None, None, None, None, None)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return self._tag_weights_stats(i, info.n_classes, info.n_features)[0]
+
+    def tag_stats(self) -> dict:
+        """After train: {"problems": per problem {"path", "classes": [TRON stats per class]}, "summary": problems and seconds per path}."""
+        probs = []
+        n = C.c_size_t()
+        st = self._L.vpt_trainer_n_tag_problems(self._h, C.byref(n), None)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        for i in range(n.value):
+            info = _lib.TagProblemInfo()
+            st = self._L.vpt_trainer_tag_problem(self._h, i, C.addressof(info), None, None, None, None, None, None, None)
+            if st != _lib.VPT_OK:
+                _raise(st)
+            probs.append({"path": info.path, "seconds_setup": info.seconds_setup, "seconds_solve": info.seconds_solve,
+                          "classes": self._tag_weights_stats(i, info.n_classes, info.n_features)[1]})
+        sm = _lib.TagTrainSummary()
+        st = self._L.vpt_trainer_tag_summary(self._h, C.addressof(sm))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return {"problems": probs, "summary": {k: getattr(sm, k) for k, _ in sm._fields_}}

@@ -8,10 +8,12 @@
 // vaporetto_amd/modelfmt.encode_model (model.rs:99-104).
 #include "capi_internal.hpp"
 
+#include <chrono>
 #include <cmath>
 #include <map>
 #include <memory>
 #include <set>
+#include <unordered_map>
 
 namespace {
 
@@ -105,6 +107,36 @@ struct Enc {
     void weights(const std::vector<int32_t>& w) { uvar(w.size()); for (int32_t x : w) i32(x); }
 };
 
+typedef unsigned __int128 u128;
+
+// ---- tag-model training (tag_trainer.rs): what the host keeps of the examples, the problems made of them, and what was trained
+struct TagSurface {   // a distinct surface, as build_tags reads it back: index = its id, in byte order
+    std::string s;
+    std::vector<uint32_t> cps;
+    std::vector<uint8_t> types;
+};
+struct TagProblem {
+    uint32_t model, slot, class_offset;
+    std::vector<int32_t> cands;           // tag strings in id order
+    std::vector<u128> keys;               // the features in key order
+    std::vector<uint32_t> y;              // the tag id per row
+    uint32_t index = 0;
+    uint64_t nnz = 0;
+    bool fetched = false;
+    std::vector<uint32_t> rp, cols;       // the 0/1 CSR, read back from the device when asked for (fetch_rows)
+    uint32_t path = 0;                    // 1 solved inside the kernel, 2 by the global-memory TRON
+    double seconds_setup = 0, seconds_solve = 0;   // path 2: uploading the matrix and building its CSC; Tron::run over the classes
+    std::vector<double> w;                // [classes][features + 1]
+    std::vector<vpt_train_stats> stats;   // per class
+};
+struct TagModelOut {
+    std::string token;
+    const TagSurface* surf = nullptr;     // NULL: only the tag dictionary has the surface
+    std::vector<std::vector<int32_t>> tags;
+    uint32_t n_class = 0;
+    std::vector<uint32_t> problems;
+};
+
 }  // namespace
 
 struct vpt_trainer {
@@ -134,6 +166,37 @@ struct vpt_trainer {
     std::vector<uint8_t> model;
     vpt_train_stats stats{};
     bool trained = false;
+    // tag models (VPT_TRAIN_TAGS)
+    std::vector<std::string> tag_strings;
+    std::unordered_map<std::string, int32_t> tag_ids;
+    // the examples, on the device: the batches' chars, per example (first char, chars, first key, keys), and the keys
+    DBuf<uint32_t> d_tag_cps, d_tag_ex;
+    DBuf<uint64_t> d_tag_keys;
+    uint64_t n_tag_cps = 0, n_tag_ex = 0, n_tag_keys = 0;
+    // ... and on the host their tags alone: per example Token::tags().len(), and an interned tag string (-1 None) per slot
+    std::vector<uint32_t> ex_ntags;
+    std::vector<uint64_t> ex_tag0;
+    std::vector<int32_t> ex_tags;
+    // the last build: the surfaces by id, the problems' matrices on the device and where each problem's part starts
+    std::vector<TagSurface> tag_surfaces;
+    DBuf<uint32_t> b_rp, b_cols, b_cp, b_crow, b_y;
+    std::vector<uint64_t> h_prob_row_ptr, h_prob_occ0, h_key_ptr;
+    double tag_build_host_seconds = 0;
+    std::map<std::string, std::vector<int32_t>> tag_defaults;
+    bool tags_built = false, tags_trained = false;
+    int tag_path_mode = 0;                                    // 0: by size; 1: every problem through the global-memory TRON
+    std::vector<TagModelOut> tag_models;
+    std::vector<TagProblem> tag_problems;
+    vpt_tag_train_summary tag_summary{};
+    double tag_build_seconds = 0, tag_add_host_seconds = 0;
+    int32_t intern_tag(const std::string& s) {
+        auto it = tag_ids.find(s);
+        if (it != tag_ids.end()) return it->second;
+        const int32_t id = int32_t(tag_strings.size());
+        tag_strings.push_back(s);
+        tag_ids.emplace(s, id);
+        return id;
+    }
     ~vpt_trainer() { if (st) (void)hipStreamDestroy(st); }
 };
 
@@ -141,13 +204,52 @@ namespace {
 
 constexpr const char* kIA = "InvalidArgumentError: ";
 
+// the CSC copy of a CSR's nonzeros (stably sorted by column: rows ascend within a column) and the segments of Xᵀv, level by level,
+// until a column is one segment
+vpt_status csc_levels(hipStream_t st, const uint32_t* cols, const uint16_t* vals, const uint32_t* rows, uint64_t nz, uint64_t nd,
+                      DBuf<uint32_t>& crow, DBuf<uint16_t>& cval, DBuf<uint64_t>& cptr, std::vector<std::unique_ptr<XtvLevel>>& levels) {
+    levels.clear();
+    DBuf<uint32_t> order, tmp;
+    DBuf<uint64_t> hist, hist_scan, scratch;
+    VPT_HIP(order.resize(nz)); VPT_HIP(tmp.resize(nz));
+    VPT_HIP(hist.resize(vpt::train_radix_scratch(nz))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(nz) + 1));
+    VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>({nz, nd, vpt::train_radix_scratch(nz)})) + 1));
+    uint32_t ws[4];
+    uint32_t cpasses = 1;
+    while (cpasses < 4 && nd > (uint64_t(1) << (8 * cpasses))) ++cpasses;
+    for (uint32_t k = 0; k < cpasses; ++k) ws[k] = 8 * k;
+    VPT_HIP(vpt::train_radix_sort(cols, 1, ws, cpasses, nz, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
+    VPT_HIP(crow.resize(nz)); VPT_HIP(cval.resize(nz)); VPT_HIP(cptr.resize(nd + 1));
+    VPT_HIP(vpt::train_csc_fill(order.p, cols, vals, rows, nz, crow.p, cval.p, cptr.p, st));
+    VPT_HIP(hipMemcpyAsync(cptr.p + nd, &nz, 8, hipMemcpyHostToDevice, st));
+    VPT_HIP(hipStreamSynchronize(st));   // nz is the caller's
+    DBuf<uint64_t> cnt;
+    VPT_HIP(cnt.resize(nd));
+    const uint64_t* ptr = cptr.p;
+    for (;;) {
+        levels.emplace_back(new XtvLevel());
+        XtvLevel& L = *levels.back();
+        L.ptr = ptr;
+        VPT_HIP(L.nptr.resize(nd + 1));
+        VPT_HIP(vpt::train_seg_count(ptr, nd, cnt.p, st));
+        VPT_HIP(vpt::train_scan_u64(cnt.p, nd, L.nptr.p, scratch.p, st));
+        VPT_HIP(hipMemcpyAsync(&L.nseg, L.nptr.p + nd, 8, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipStreamSynchronize(st));
+        VPT_HIP(L.seg_col.resize(L.nseg)); VPT_HIP(L.out.resize(L.nseg));
+        VPT_HIP(vpt::train_seg_col(L.nptr.p, nd, L.seg_col.p, st));
+        ptr = L.nptr.p;
+        if (L.nseg == nd) break;
+    }
+    VPT_HIP(hipStreamSynchronize(st));
+    return VPT_OK;
+}
+
 vpt_status build(vpt_trainer* t) {
     if (t->built) return VPT_OK;
     hipStream_t st = t->st;
     const uint64_t nnz = t->nnz_occ, nrows = t->nrows;
     if (nnz >= (uint64_t(1) << 32) || nrows >= (uint64_t(1) << 32))
         return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 boundaries and feature occurrences");
-    t->levels.clear();
     // ---- representatives of the distinct keys
     uint64_t slots = 2;
     while (slots < 2 * nnz) slots <<= 1;
@@ -201,32 +303,9 @@ vpt_status build(vpt_trainer* t) {
     if (bad) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: a feature occurs more than 65535 times at one boundary");
     VPT_HIP(hipStreamSynchronize(st));
     ids.reset(); row_off.reset(); merged.reset();
-    // ---- CSC: the nonzeros stably sorted by column (rows ascend within a column)
-    uint32_t cpasses = 1;
-    while (cpasses < 4 && nd > (uint64_t(1) << (8 * cpasses))) ++cpasses;
-    for (uint32_t k = 0; k < cpasses; ++k) ws[k] = 8 * k;
-    VPT_HIP(vpt::train_radix_sort(t->cols.p, 1, ws, cpasses, nz, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
-    VPT_HIP(t->crow.resize(nz)); VPT_HIP(t->cval.resize(nz)); VPT_HIP(t->cptr.resize(nd + 1));
-    VPT_HIP(vpt::train_csc_fill(order.p, t->cols.p, t->vals.p, rows.p, nz, t->crow.p, t->cval.p, t->cptr.p, st));
-    VPT_HIP(hipMemcpyAsync(t->cptr.p + nd, &nz, 8, hipMemcpyHostToDevice, st));
-    // ---- the segments of Xᵀv, level by level, until a column is one segment
-    DBuf<uint64_t> cnt;
-    VPT_HIP(cnt.resize(nd));
-    const uint64_t* ptr = t->cptr.p;
-    for (;;) {
-        t->levels.emplace_back(new XtvLevel());
-        XtvLevel& L = *t->levels.back();
-        L.ptr = ptr;
-        VPT_HIP(L.nptr.resize(nd + 1));
-        VPT_HIP(vpt::train_seg_count(ptr, nd, cnt.p, st));
-        VPT_HIP(vpt::train_scan_u64(cnt.p, nd, L.nptr.p, scratch.p, st));
-        VPT_HIP(hipMemcpyAsync(&L.nseg, L.nptr.p + nd, 8, hipMemcpyDeviceToHost, st));
-        VPT_HIP(hipStreamSynchronize(st));
-        VPT_HIP(L.seg_col.resize(L.nseg)); VPT_HIP(L.out.resize(L.nseg));
-        VPT_HIP(vpt::train_seg_col(L.nptr.p, nd, L.seg_col.p, st));
-        ptr = L.nptr.p;
-        if (L.nseg == nd) break;
-    }
+    order.reset(); tmp.reset(); hist.reset(); hist_scan.reset(); scratch.reset();
+    vpt_status cs = csc_levels(st, t->cols.p, t->vals.p, rows.p, nz, nd, t->crow, t->cval, t->cptr, t->levels);
+    if (cs != VPT_OK) return cs;
     VPT_HIP(hipStreamSynchronize(st));
     t->nd = nd;
     t->nnz = nz;
@@ -235,8 +314,18 @@ vpt_status build(vpt_trainer* t) {
 }
 
 // TRON (liblinear tron.cpp as bundled by scikit-learn) for l2r_lr_fun (solver 0) / l2r_l2_svc_fun (solver 2), linear.cpp
+struct MatView {   // a design matrix on the device: CSR, CSC and the segments of Xᵀv; the bias column follows column nd - 1
+    const uint64_t* csr_ptr;
+    const uint32_t* cols;
+    const uint16_t* vals;
+    const uint32_t* crow;
+    const uint16_t* cval;
+    const std::vector<std::unique_ptr<XtvLevel>>* levels;
+    uint64_t nd;
+};
+
 struct Tron {
-    vpt_trainer* t;
+    MatView m;
     hipStream_t st;
     uint64_t n, nr;
     int solver;
@@ -270,17 +359,17 @@ struct Tron {
     // out = a + Xᵀu
     void add_xtv(const double* a, const double* u, double* out) {
         const double* in = nullptr;
-        for (auto& Lp : t->levels) {
+        for (auto& Lp : *m.levels) {
             XtvLevel& L = *Lp;
             if (err == hipSuccess)
-                err = vpt::train_xtv_level(L.ptr, L.nptr.p, L.seg_col.p, L.nseg, in, in ? nullptr : t->crow.p, t->cval.p, u, L.out.p, st);
+                err = vpt::train_xtv_level(L.ptr, L.nptr.p, L.seg_col.p, L.nseg, in, in ? nullptr : m.crow, m.cval, u, L.out.p, st);
             in = L.out.p;
         }
         const double* bias = reduce_dev(u, nullptr, nr);
         if (err == hipSuccess) err = vpt::train_add(n, a, in, bias, out, st);
     }
     double fun(const double* x) {
-        if (err == hipSuccess) err = vpt::train_xv(t->csr_ptr.p, t->cols.p, t->vals.p, nr, x, t->nd, z.p, st);
+        if (err == hipSuccess) err = vpt::train_xv(m.csr_ptr, m.cols, m.vals, nr, x, m.nd, z.p, st);
         if (err == hipSuccess) err = vpt::train_loss(nr, z.p, y.p, c, solver, loss.p, st);
         const double reg = dot(x, x, n) / 2.0;
         return reg + dot(loss.p, nullptr, nr);
@@ -290,7 +379,7 @@ struct Tron {
         add_xtv(x, gz.p, out);
     }
     void hv(const double* v, double* out) {
-        if (err == hipSuccess) err = vpt::train_xv(t->csr_ptr.p, t->cols.p, t->vals.p, nr, v, t->nd, zt.p, st);
+        if (err == hipSuccess) err = vpt::train_xv(m.csr_ptr, m.cols, m.vals, nr, v, m.nd, zt.p, st);
         if (err == hipSuccess) err = vpt::train_scale_rows(nr, D.p, zt.p, st);
         add_xtv(v, zt.p, out);
     }
@@ -376,6 +465,8 @@ struct Tron {
     }
 };
 
+void encode_tag_models(vpt_trainer* t, Enc& e);
+
 // trainer.rs:352-487: quantisation and the model's layout, then Model::to_vec
 vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
     const uint64_t nd = t->nd;
@@ -433,7 +524,8 @@ vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
     e.i32(qbias);
     e.u8(t->prm.charw);
     e.u8(t->prm.typew);
-    e.uvar(0);   // no tag models
+    if (t->prm.flags & VPT_TRAIN_TAGS) encode_tag_models(t, e);
+    else e.uvar(0);   // no tag models
     t->model = std::move(e.b);
     return VPT_OK;
 }
@@ -485,6 +577,506 @@ vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_b
     return VPT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------- tag models (tag_trainer.rs)
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// the surface ids of the examples, on the device: representatives by a hash table over (code points, length), the distinct surfaces
+// radix-sorted as rows of code points (0 past the end: byte order of UTF-8 is code point order, a prefix first), the examples sorted by
+// (surface id, corpus order).  Back come 8 bytes an example and the distinct surfaces' chars.
+vpt_status surface_ids(vpt_trainer* t, std::vector<uint32_t>& ex_order, std::vector<uint32_t>& sid) {
+    hipStream_t st = t->st;
+    const uint64_t n_ex = t->n_tag_ex;
+    t->tag_surfaces.clear();
+    ex_order.clear(); sid.clear();
+    if (n_ex == 0) return VPT_OK;
+    uint64_t slots = 2;
+    while (slots < 2 * n_ex) slots <<= 1;
+    DBuf<uint64_t> table, pos, scratch, hist, hist_scan;
+    DBuf<uint32_t> rep, flag, maxlen, slot, mat, order, tmp, id_of, d_sid, d_order;
+    VPT_HIP(table.resize(slots)); VPT_HIP(rep.resize(n_ex)); VPT_HIP(flag.resize(n_ex)); VPT_HIP(maxlen.resize(1)); VPT_HIP(pos.resize(n_ex + 1));
+    VPT_HIP(slot.resize(n_ex)); VPT_HIP(d_sid.resize(n_ex)); VPT_HIP(d_order.resize(n_ex)); VPT_HIP(tmp.resize(n_ex));
+    VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>(n_ex, vpt::train_radix_scratch(n_ex))) + 1));
+    VPT_HIP(hist.resize(vpt::train_radix_scratch(n_ex))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(n_ex) + 1));
+    VPT_HIP(hipMemsetAsync(table.p, 0, slots * 8, st));
+    VPT_HIP(hipMemsetAsync(maxlen.p, 0, 4, st));
+    VPT_HIP(vpt::train_surf_insert(t->d_tag_ex.p, n_ex, t->d_tag_cps.p, table.p, slots - 1, rep.p, flag.p, maxlen.p, st));
+    VPT_HIP(vpt::train_scan_u32(flag.p, n_ex, pos.p, scratch.p, st));
+    uint64_t n_surf = 0;
+    uint32_t ml = 0;
+    VPT_HIP(hipMemcpyAsync(&n_surf, pos.p + n_ex, 8, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(&ml, maxlen.p, 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    if (3 * uint64_t(ml) >= (1u << 20)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: a tagged token of 349525 chars or more");
+    VPT_HIP(mat.resize(n_surf * ml)); VPT_HIP(order.resize(n_surf)); VPT_HIP(id_of.resize(n_surf));
+    VPT_HIP(vpt::train_surf_matrix(t->d_tag_ex.p, n_ex, flag.p, pos.p, t->d_tag_cps.p, ml, mat.p, slot.p, st));
+    std::vector<uint32_t> ws;
+    for (uint32_t w = ml; w-- > 0;)
+        for (uint32_t sh = 0; sh < 24; sh += 8) ws.push_back((w << 8) | sh);   // the type byte above the code point is no part of the order
+    {
+        DBuf<uint32_t> stmp;
+        VPT_HIP(stmp.resize(n_surf));
+        VPT_HIP(vpt::train_radix_sort(mat.p, ml, ws.data(), uint32_t(ws.size()), n_surf, order.p, stmp.p, hist.p, hist_scan.p, scratch.p, st));
+        VPT_HIP(hipStreamSynchronize(st));
+    }
+    VPT_HIP(vpt::train_surf_ids(order.p, n_surf, id_of.p, rep.p, slot.p, n_ex, d_sid.p, st));
+    uint32_t passes = 1, ws2[4];
+    while (passes < 4 && n_surf > (uint64_t(1) << (8 * passes))) ++passes;
+    for (uint32_t k = 0; k < passes; ++k) ws2[k] = 8 * k;
+    VPT_HIP(vpt::train_radix_sort(d_sid.p, 1, ws2, passes, n_ex, d_order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
+    std::vector<uint32_t> h_mat(n_surf * ml), h_order(n_surf);
+    ex_order.resize(n_ex); sid.resize(n_ex);
+    VPT_HIP(hipMemcpyAsync(ex_order.data(), d_order.p, n_ex * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(sid.data(), d_sid.p, n_ex * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(h_mat.data(), mat.p, h_mat.size() * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(h_order.data(), order.p, n_surf * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    t->tag_surfaces.resize(n_surf);
+    for (uint64_t j = 0; j < n_surf; ++j) {
+        TagSurface& S = t->tag_surfaces[j];
+        for (uint32_t k = 0; k < ml && h_mat[uint64_t(h_order[j]) * ml + k]; ++k) {
+            const uint32_t w = h_mat[uint64_t(h_order[j]) * ml + k];
+            S.cps.push_back(w & vpt::kCharMaskTrain);
+            S.types.push_back(uint8_t(w >> 24));
+            put_utf8(S.s, w & vpt::kCharMaskTrain);
+        }
+    }
+    return VPT_OK;
+}
+
+// TagTrainer::train's grouping and train_tag's front half (tag_trainer.rs:148-180, 301-312): the models in surface order, the
+// candidates per slot in order of first appearance, and a 0/1 problem per slot with at least two candidates.  The host sees the
+// examples' surface ids and tag ids only and picks the rows; the keys are deduplicated and numbered and every problem's CSR and CSC
+// written on the device, for all problems at once over concatenated arrays.
+vpt_status build_tags(vpt_trainer* t) {
+    if (t->tags_built) return VPT_OK;
+    const double t_build = now_s();
+    hipStream_t st = t->st;
+    t->tag_models.clear();
+    t->tag_problems.clear();
+    t->tags_trained = false;
+    std::vector<uint32_t> ex_order, sid;
+    vpt_status vs = surface_ids(t, ex_order, sid);
+    if (vs != VPT_OK) return vs;
+    const double t_host = now_s();
+    // a surface's examples: a run of ex_order
+    std::vector<uint64_t> run(t->tag_surfaces.size() + 1, 0);
+    for (uint32_t x : sid) ++run[x + 1];
+    for (size_t j = 0; j < t->tag_surfaces.size(); ++j) run[j + 1] += run[j];
+    std::map<std::string, int64_t> all;   // surface -> its id, -1: only the tag dictionary has it
+    for (size_t j = 0; j < t->tag_surfaces.size(); ++j) all.emplace(t->tag_surfaces[j].s, int64_t(j));
+    for (auto& kv : t->tag_defaults) {
+        bool some = false;
+        for (int32_t x : kv.second) some = some || x >= 0;
+        if (some) all.emplace(kv.first, -1);
+    }
+    if (all.size() >= (size_t(1) << 24) - 1)
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^24 - 2 tag models (distinct token surfaces)");
+    std::vector<uint32_t> row_ex, row_prob, row_y;
+    std::vector<uint64_t> prob_row_ptr{0};
+    for (auto& kv : all) {
+        TagModelOut M;
+        M.token = kv.first;
+        M.surf = kv.second >= 0 ? &t->tag_surfaces[size_t(kv.second)] : nullptr;
+        const std::vector<int32_t>* def = M.surf ? nullptr : &t->tag_defaults[kv.first];
+        const uint64_t e0 = M.surf ? run[size_t(kv.second)] : 0, n_ex = M.surf ? run[size_t(kv.second) + 1] - e0 : 1;
+        auto tags_of = [&](uint64_t i, uint32_t* n) -> const int32_t* {
+            if (def) { *n = uint32_t(def->size()); return def->data(); }
+            const uint32_t x = ex_order[e0 + i];
+            *n = t->ex_ntags[x];
+            return t->ex_tags.data() + t->ex_tag0[x];
+        };
+        uint32_t n_tags = 0;
+        for (uint64_t i = 0; i < n_ex; ++i) { uint32_t n; tags_of(i, &n); n_tags = std::max(n_tags, n); }
+        M.tags.assign(n_tags, {});
+        for (uint64_t i = 0; i < n_ex; ++i) {
+            uint32_t n;
+            const int32_t* tg = tags_of(i, &n);
+            for (uint32_t j = 0; j < n; ++j)
+                if (tg[j] >= 0 && std::find(M.tags[j].begin(), M.tags[j].end(), tg[j]) == M.tags[j].end()) M.tags[j].push_back(tg[j]);
+        }
+        for (uint32_t j = 0; j < n_tags; ++j) {
+            if (M.tags[j].size() < 2) continue;   // a fixed tag
+            TagProblem Pb;
+            Pb.model = uint32_t(t->tag_models.size());
+            Pb.slot = j;
+            Pb.class_offset = M.n_class;
+            Pb.cands = M.tags[j];
+            for (uint64_t i = 0; i < n_ex; ++i) {
+                uint32_t n;
+                const int32_t* tg = tags_of(i, &n);
+                if (j >= n || tg[j] < 0) continue;
+                row_ex.push_back(ex_order[e0 + i]);
+                row_prob.push_back(uint32_t(t->tag_problems.size()));
+                Pb.y.push_back(uint32_t(std::find(Pb.cands.begin(), Pb.cands.end(), tg[j]) - Pb.cands.begin()));
+            }
+            row_y.insert(row_y.end(), Pb.y.begin(), Pb.y.end());
+            prob_row_ptr.push_back(row_ex.size());
+            M.problems.push_back(uint32_t(t->tag_problems.size()));
+            M.n_class += uint32_t(Pb.cands.size());
+            t->tag_problems.push_back(std::move(Pb));
+        }
+        t->tag_models.push_back(std::move(M));
+    }
+    const double host_s = now_s() - t_host;
+    // ---- the matrices, on the device
+    const uint64_t n_prob = t->tag_problems.size(), n_rows = row_ex.size();
+    t->h_prob_row_ptr = prob_row_ptr;
+    t->h_prob_occ0.assign(n_prob + 1, 0);
+    t->h_key_ptr.assign(n_prob + 1, 0);
+    if (n_rows >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 rows over the tag problems");
+    if (n_prob) {
+        DBuf<uint32_t> d_row_ex, d_row_prob, nk, occ, occ_row, order, tmp, flag;
+        DBuf<uint64_t> d_prp, occ_off, scratch, hist, hist_scan, dpos, prob_occ0, key_ptr, dkeys;
+        VPT_HIP(d_row_ex.resize(n_rows)); VPT_HIP(d_row_prob.resize(n_rows)); VPT_HIP(nk.resize(n_rows)); VPT_HIP(d_prp.resize(n_prob + 1));
+        VPT_HIP(occ_off.resize(n_rows + 1)); VPT_HIP(t->b_y.resize(n_rows));
+        VPT_HIP(hipMemcpyAsync(d_row_ex.p, row_ex.data(), n_rows * 4, hipMemcpyHostToDevice, st));
+        VPT_HIP(hipMemcpyAsync(d_row_prob.p, row_prob.data(), n_rows * 4, hipMemcpyHostToDevice, st));
+        VPT_HIP(hipMemcpyAsync(t->b_y.p, row_y.data(), n_rows * 4, hipMemcpyHostToDevice, st));
+        VPT_HIP(hipMemcpyAsync(d_prp.p, prob_row_ptr.data(), (n_prob + 1) * 8, hipMemcpyHostToDevice, st));
+        VPT_HIP(scratch.resize(vpt::train_scan_scratch(n_rows) + 1));
+        VPT_HIP(vpt::train_tag_expand(d_row_ex.p, d_row_prob.p, n_rows, t->d_tag_ex.p, nullptr, nullptr, nk.p, nullptr, st));
+        VPT_HIP(vpt::train_scan_u32(nk.p, n_rows, occ_off.p, scratch.p, st));
+        uint64_t n_occ = 0;
+        VPT_HIP(hipMemcpyAsync(&n_occ, occ_off.p + n_rows, 8, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipStreamSynchronize(st));
+        if (n_occ >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 nonzeros over the tag problems");
+        VPT_HIP(occ.resize(5 * n_occ)); VPT_HIP(occ_row.resize(n_occ)); VPT_HIP(order.resize(n_occ)); VPT_HIP(tmp.resize(n_occ)); VPT_HIP(flag.resize(n_occ));
+        VPT_HIP(dpos.resize(n_occ + 1));
+        VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>(n_occ, vpt::train_radix_scratch(n_occ))) + 1));
+        VPT_HIP(hist.resize(vpt::train_radix_scratch(n_occ))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(n_occ) + 1));
+        VPT_HIP(vpt::train_tag_expand(d_row_ex.p, d_row_prob.p, n_rows, t->d_tag_ex.p, occ_off.p, t->d_tag_keys.p, occ.p, occ_row.p, st));
+        // stably sorted by (problem, key): the key's four words least significant first, then the problem's bytes that can differ
+        uint32_t ws[20], np = 0;
+        for (uint32_t k = 0; k < 16; ++k) ws[np++] = ((k / 4) << 8) | (8 * (k % 4));
+        for (uint32_t k = 0; k < 4 && (k == 0 || n_prob > (uint64_t(1) << (8 * k))); ++k) ws[np++] = (4u << 8) | (8 * k);
+        VPT_HIP(vpt::train_radix_sort(occ.p, 5, ws, np, n_occ, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
+        VPT_HIP(vpt::train_tag_flags(occ.p, order.p, n_occ, flag.p, st));
+        VPT_HIP(vpt::train_scan_u32(flag.p, n_occ, dpos.p, scratch.p, st));
+        uint64_t n_dist = 0;
+        VPT_HIP(hipMemcpyAsync(&n_dist, dpos.p + n_occ, 8, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipStreamSynchronize(st));
+        VPT_HIP(prob_occ0.resize(n_prob + 1)); VPT_HIP(key_ptr.resize(n_prob + 1)); VPT_HIP(dkeys.resize(2 * n_dist));
+        VPT_HIP(t->b_cols.resize(n_occ)); VPT_HIP(t->b_crow.resize(n_occ)); VPT_HIP(t->b_rp.resize(n_rows + n_prob)); VPT_HIP(t->b_cp.resize(n_dist + n_prob));
+        vpt::TagBuildParams B{};
+        B.n_prob = n_prob; B.n_rows = n_rows; B.n_occ = n_occ; B.prob_row_ptr = d_prp.p; B.row_prob = d_row_prob.p; B.occ_off = occ_off.p; B.occ = occ.p;
+        B.occ_row = occ_row.p; B.order = order.p; B.flag = flag.p; B.dpos = dpos.p; B.prob_occ0 = prob_occ0.p; B.key_ptr = key_ptr.p;
+        B.occ_col = t->b_cols.p; B.dkeys = dkeys.p; B.rp = t->b_rp.p; B.cp = t->b_cp.p; B.crow = t->b_crow.p;
+        VPT_HIP(vpt::train_tag_assemble(B, st));
+        std::vector<uint64_t> h_dkeys(2 * n_dist);
+        VPT_HIP(hipMemcpyAsync(t->h_prob_occ0.data(), prob_occ0.p, (n_prob + 1) * 8, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipMemcpyAsync(t->h_key_ptr.data(), key_ptr.p, (n_prob + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (n_dist) VPT_HIP(hipMemcpyAsync(h_dkeys.data(), dkeys.p, n_dist * 16, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipStreamSynchronize(st));
+        // the distinct keys alone come back: the model's n-grams are made of them
+        for (uint64_t p = 0; p < n_prob; ++p) {
+            TagProblem& Pb = t->tag_problems[p];
+            Pb.index = uint32_t(p);
+            Pb.nnz = t->h_prob_occ0[p + 1] - t->h_prob_occ0[p];
+            for (uint64_t c = t->h_key_ptr[p]; c < t->h_key_ptr[p + 1]; ++c) Pb.keys.push_back((u128(h_dkeys[2 * c + 1]) << 64) | h_dkeys[2 * c]);
+        }
+    }
+    t->tags_built = true;
+    t->tag_build_seconds = now_s() - t_build;
+    t->tag_build_host_seconds = host_s;
+    return VPT_OK;
+}
+
+// a problem's CSR on the host, for the inspection calls and the global-memory path
+vpt_status fetch_rows(vpt_trainer* t, TagProblem& Pb) {
+    if (Pb.fetched) return VPT_OK;
+    const uint64_t p = Pb.index, l = Pb.y.size();
+    Pb.rp.assign(l + 1, 0);
+    Pb.cols.assign(Pb.nnz, 0);
+    VPT_HIP(hipMemcpy(Pb.rp.data(), t->b_rp.p + t->h_prob_row_ptr[p] + p, (l + 1) * 4, hipMemcpyDeviceToHost));
+    if (Pb.nnz) VPT_HIP(hipMemcpy(Pb.cols.data(), t->b_cols.p + t->h_prob_occ0[p], Pb.nnz * 4, hipMemcpyDeviceToHost));
+    Pb.fetched = true;
+    return VPT_OK;
+}
+
+// one problem through the global-memory TRON, a class at a time
+vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double cost, int solver) {
+    hipStream_t st = t->st;
+    const double t_setup = now_s();
+    vpt_status fs = fetch_rows(t, Pb);
+    if (fs != VPT_OK) return fs;
+    const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), nz = Pb.cols.size(), k = Pb.cands.size();
+    std::vector<uint64_t> ptr(Pb.rp.begin(), Pb.rp.end());
+    std::vector<uint32_t> rows(nz);
+    for (uint64_t r = 0; r < l; ++r)
+        for (uint32_t q = Pb.rp[r]; q < Pb.rp[r + 1]; ++q) rows[q] = uint32_t(r);
+    const std::vector<uint16_t> ones(nz, 1);
+    DBuf<uint64_t> d_ptr, cptr;
+    DBuf<uint32_t> d_cols, d_rows, crow;
+    DBuf<uint16_t> d_vals, cval;
+    std::vector<std::unique_ptr<XtvLevel>> levels;
+    VPT_HIP(d_ptr.resize(l + 1)); VPT_HIP(d_cols.resize(nz)); VPT_HIP(d_rows.resize(nz)); VPT_HIP(d_vals.resize(nz));
+    VPT_HIP(hipMemcpy(d_ptr.p, ptr.data(), (l + 1) * 8, hipMemcpyHostToDevice));
+    if (nz) {
+        VPT_HIP(hipMemcpy(d_cols.p, Pb.cols.data(), nz * 4, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(d_rows.p, rows.data(), nz * 4, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(d_vals.p, ones.data(), nz * 2, hipMemcpyHostToDevice));
+    }
+    vpt_status s = csc_levels(st, d_cols.p, d_vals.p, d_rows.p, nz, nf, crow, cval, cptr, levels);
+    if (s != VPT_OK) return s;
+    Tron T;
+    T.m = MatView{d_ptr.p, d_cols.p, d_vals.p, crow.p, cval.p, &levels, nf};
+    T.st = st; T.n = nf + 1; T.nr = l; T.solver = solver; T.c = cost;
+    for (DBuf<double>* b : {&T.w, &T.w_new, &T.g, &T.s, &T.r, &T.d, &T.Hd}) VPT_HIP(b->resize(T.n));
+    for (DBuf<double>* b : {&T.y, &T.z, &T.zt, &T.gz, &T.D, &T.loss}) VPT_HIP(b->resize(l));
+    VPT_HIP(T.part0.resize(vpt::train_dot_partials(std::max(T.n, l)))); VPT_HIP(T.part1.resize(vpt::train_dot_partials(std::max(T.n, l))));
+    std::vector<double> y(l);
+    const uint64_t n_solve = k == 2 ? 1 : k;
+    VPT_HIP(hipStreamSynchronize(st));
+    Pb.seconds_setup = now_s() - t_setup;
+    Pb.seconds_solve = 0;
+    for (uint64_t c = 0; c < n_solve; ++c) {
+        uint64_t pos = 0;
+        for (uint64_t r = 0; r < l; ++r) { y[r] = Pb.y[r] == c ? 1.0 : -1.0; pos += Pb.y[r] == c; }
+        VPT_HIP(hipMemcpy(T.y.p, y.data(), l * 8, hipMemcpyHostToDevice));
+        const double tol = eps * double(std::max<uint64_t>(std::min(pos, l - pos), 1)) / double(l);
+        const double t_run = now_s();
+        T.run(tol, &Pb.stats[c]);
+        VPT_HIP(T.err);
+        VPT_HIP(hipMemcpy(Pb.w.data() + c * T.n, T.w.p, T.n * 8, hipMemcpyDeviceToHost));
+        Pb.seconds_solve += now_s() - t_run;
+    }
+    if (k == 2) {
+        for (uint64_t i = 0; i < T.n; ++i) Pb.w[T.n + i] = -Pb.w[i];
+        Pb.stats[1] = Pb.stats[0];
+    }
+    Pb.path = 2;
+    return VPT_OK;
+}
+
+vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
+    hipStream_t st = t->st;
+    t->tag_summary = vpt_tag_train_summary{};
+    std::vector<vpt::TagSolveDesc> descs;
+    std::vector<uint32_t> small;
+    uint64_t n_w = 0, n_stats = 0;
+    for (size_t i = 0; i < t->tag_problems.size(); ++i) {
+        TagProblem& Pb = t->tag_problems[i];
+        const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), nz = Pb.nnz, k = Pb.cands.size();
+        Pb.w.assign(k * (nf + 1), 0.0);
+        Pb.stats.assign(k, vpt_train_stats{});
+        Pb.path = (t->tag_path_mode == 0 && vpt::train_tag_fits(l, nf, nz)) ? 1 : 2;
+        Pb.seconds_setup = Pb.seconds_solve = 0;
+        if (Pb.path != 1) continue;
+        // the problem where build_tags left it on the device
+        vpt::TagSolveDesc D{};
+        D.rp = t->h_prob_row_ptr[i] + i; D.cols = t->h_prob_occ0[i]; D.cp = t->h_key_ptr[i] + i; D.y = t->h_prob_row_ptr[i]; D.w = n_w; D.stats = n_stats;
+        D.nf = uint32_t(nf); D.l = uint32_t(l); D.k = uint32_t(k);
+        n_w += k * (nf + 1);
+        n_stats += k;
+        descs.push_back(D);
+        small.push_back(uint32_t(i));
+    }
+    if (!descs.empty()) {
+        const double t0 = now_s();
+        DBuf<vpt::TagSolveDesc> d_desc;
+        DBuf<double> d_w;
+        DBuf<vpt::TagClassStats> d_stats;
+        VPT_HIP(d_desc.resize(descs.size())); VPT_HIP(d_w.resize(n_w)); VPT_HIP(d_stats.resize(n_stats));
+        VPT_HIP(hipMemcpyAsync(d_desc.p, descs.data(), descs.size() * sizeof(vpt::TagSolveDesc), hipMemcpyHostToDevice, st));
+        VPT_HIP(hipMemsetAsync(d_w.p, 0, n_w * 8, st));
+        VPT_HIP(hipMemsetAsync(d_stats.p, 0, n_stats * sizeof(vpt::TagClassStats), st));
+        VPT_HIP(vpt::train_tag_solve(d_desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, eps, cost, solver, d_w.p,
+                                     d_stats.p, st));
+        std::vector<double> w(n_w);
+        std::vector<vpt::TagClassStats> stats(n_stats);
+        VPT_HIP(hipMemcpyAsync(w.data(), d_w.p, n_w * 8, hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipMemcpyAsync(stats.data(), d_stats.p, n_stats * sizeof(vpt::TagClassStats), hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipStreamSynchronize(st));
+        for (size_t q = 0; q < small.size(); ++q) {
+            TagProblem& Pb = t->tag_problems[small[q]];
+            std::copy(w.begin() + descs[q].w, w.begin() + descs[q].w + Pb.w.size(), Pb.w.begin());
+            for (size_t c = 0; c < Pb.stats.size(); ++c) {
+                const vpt::TagClassStats& S = stats[descs[q].stats + c];
+                Pb.stats[c] = vpt_train_stats{S.iterations, S.cg_steps, S.gnorm0, S.gnorm, S.objective};
+            }
+        }
+        t->tag_summary.problems_in_kernel = descs.size();
+        t->tag_summary.seconds_in_kernel = now_s() - t0;
+    }
+    const double t1 = now_s();
+    for (TagProblem& Pb : t->tag_problems) {
+        if (Pb.path != 2) continue;
+        vpt_status s = solve_tag_large(t, Pb, eps, cost, solver);
+        if (s != VPT_OK) return s;
+        ++t->tag_summary.problems_large;
+        t->tag_summary.seconds_large_solve += Pb.seconds_solve;
+    }
+    t->tag_summary.seconds_large = now_s() - t1;
+    t->tag_summary.seconds_construction = t->tag_build_seconds;
+    t->tag_summary.seconds_construction_host = t->tag_build_host_seconds;
+    t->tag_summary.seconds_add_host = t->tag_add_host_seconds;
+    t->tags_trained = true;
+    return VPT_OK;
+}
+
+// train_tag's back half (tag_trainer.rs:195-298) and the tag models of Model::to_vec
+void encode_tag_models(vpt_trainer* t, Enc& e) {
+    static const int sh[5] = {99, 78, 57, 36, 15};
+    e.uvar(t->tag_models.size());
+    for (const TagModelOut& M : t->tag_models) {
+        std::map<std::pair<std::string, uint8_t>, std::vector<int32_t>> cw, tw;
+        std::vector<int32_t> bias(M.n_class, 0);
+        for (uint32_t pi : M.problems) {
+            const TagProblem& Pb = t->tag_problems[pi];
+            const size_t nf = Pb.keys.size(), k = Pb.cands.size();
+            double wmax = 1e-6;
+            for (double x : Pb.w) wmax = std::max(wmax, std::fabs(x));
+            const double m = wmax / double((1 << 15) - 1);
+            for (size_t c = 0; c < k; ++c) bias[Pb.class_offset + c] = int32_t(Pb.w[c * (nf + 1) + nf] / m);
+            for (size_t j = 0; j < nf; ++j) {
+                std::vector<int32_t>* row = nullptr;
+                for (size_t c = 0; c < k; ++c) {
+                    const int32_t q = int32_t(Pb.w[c * (nf + 1) + j] / m);
+                    if (q == 0) continue;
+                    if (!row) {
+                        // the n-gram: the left context, the token, the right context
+                        const u128 v = Pb.keys[j];
+                        const uint32_t kind = uint32_t(v >> 120) & 3u, len = uint32_t(v >> 5) & 7u, rel = (uint32_t(v) & 31u) - 16u, left = len - rel;
+                        std::string ng;
+                        auto put = [&](uint32_t x) { if (kind == 0) put_utf8(ng, x); else ng += char(x); };
+                        for (uint32_t q2 = 0; q2 < left; ++q2) put(uint32_t(v >> sh[q2]) & 0x1FFFFFu);
+                        for (size_t q2 = 0; q2 < M.surf->cps.size(); ++q2) put(kind == 0 ? M.surf->cps[q2] : M.surf->types[q2]);
+                        for (uint32_t q2 = left; q2 < len; ++q2) put(uint32_t(v >> sh[q2]) & 0x1FFFFFu);
+                        auto& mp = kind == 0 ? cw : tw;
+                        row = &mp.emplace(std::make_pair(ng, uint8_t(rel)), std::vector<int32_t>(M.n_class, 0)).first->second;
+                    }
+                    (*row)[Pb.class_offset + c] = q;
+                }
+            }
+        }
+        e.raw(M.token);
+        e.uvar(M.tags.size());
+        for (auto& cands : M.tags) {
+            e.uvar(cands.size());
+            for (int32_t id : cands) e.raw(t->tag_strings[size_t(id)]);
+        }
+        for (auto* mp : {&cw, &tw}) {
+            size_t n_ng = 0;
+            for (auto it = mp->begin(); it != mp->end(); ++it) n_ng += it == mp->begin() || std::prev(it)->first.first != it->first.first;
+            e.uvar(n_ng);
+            for (auto it = mp->begin(); it != mp->end();) {
+                auto last = it;
+                size_t n_w = 0;
+                while (last != mp->end() && last->first.first == it->first.first) { ++last; ++n_w; }
+                e.raw(it->first.first);
+                e.uvar(n_w);
+                for (; it != last; ++it) { e.u8(it->first.second); e.weights(it->second); }
+            }
+        }
+        e.weights(bias);
+    }
+}
+
+vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_boff, const uint64_t* d_ooff, size_t n, uint64_t total_b,
+                             const uint8_t* d_labels, const uint32_t* d_n_tags, const uint64_t* d_tag_index, const uint64_t* d_span_off,
+                             const uint8_t* d_tag_bytes, uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, hipStream_t caller) {
+    if (!(t->prm.flags & VPT_TRAIN_TAGS))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: only VPT_FLAG_KYTEA_FULLWIDTH");
+    if (n == 0) return VPT_OK;
+    VPT_HIP(hipSetDevice(t->device));
+    VPT_HIP(hipStreamSynchronize(caller));
+    hipStream_t st = t->st;
+    const uint64_t total_chars = total_b + n;
+    if (total_chars >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 chars in a batch");
+    DBuf<uint32_t> cps, status, counts, is_ex;
+    VPT_HIP(cps.resize(total_chars)); VPT_HIP(status.resize(2));
+    VPT_HIP(hipMemsetAsync(status.p, 0, 8, st));
+    const bool fw = (flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
+    VPT_HIP(vpt::launch_decode_chars(d_utf8, d_boff, d_ooff, n, total_chars, fw ? t->d_cinfo.p : nullptr, cps.p, nullptr, status.p, st, fw));
+    uint32_t bad[2] = {0, 0};
+    VPT_HIP(hipMemcpyAsync(bad, status.p, 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    if (bad[0]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "out_offsets: do not match the text");
+    // the tags' CSR is checked on the device before anything follows one of its offsets
+    VPT_HIP(vpt::train_tag_validate(d_n_tags, d_ooff, n, total_chars, d_tag_index, d_span_off, n_spans, n_tag_bytes, status.p + 1, st));
+    VPT_HIP(hipMemcpyAsync(bad + 1, status.p + 1, 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    if (bad[1] & 1u) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tag_index: must not decrease, pass n_spans or give a char more tags than n_tags");
+    if (bad[1] & 2u) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "span_offsets: must not decrease or pass tag_bytes");
+    std::vector<uint64_t> ooff(n + 1), tindex(total_chars + 1), soff(n_spans + 1);
+    std::vector<uint32_t> ntags(n);
+    std::vector<uint8_t> tbytes(n_tag_bytes);
+    VPT_HIP(hipMemcpy(ooff.data(), d_ooff, (n + 1) * 8, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(ntags.data(), d_n_tags, n * 4, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(tindex.data(), d_tag_index, (total_chars + 1) * 8, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(soff.data(), d_span_off, (n_spans + 1) * 8, hipMemcpyDeviceToHost));
+    if (n_tag_bytes) VPT_HIP(hipMemcpy(tbytes.data(), d_tag_bytes, n_tag_bytes, hipMemcpyDeviceToHost));
+    // what the model format cannot hold: a NUL, or bytes that are no UTF-8
+    {
+        std::vector<uint32_t> tmp;
+        size_t sent = 0;
+        for (uint64_t g = 0; g < total_chars; ++g) {
+            while (ooff[sent + 1] + sent + 1 <= g) ++sent;
+            for (uint64_t k = tindex[g]; k < tindex[g + 1]; ++k) {
+                const uint8_t* b = tbytes.data() + soff[k];
+                const size_t len = size_t(soff[k + 1] - soff[k]);
+                if (std::find(b, b + len, uint8_t(0)) != b + len)
+                    return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: must not contain NULL (sentence " + std::to_string(sent) + ")");
+                if (!decode_utf8(b, len, tmp))
+                    return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: invalid UTF-8 (sentence " + std::to_string(sent) + ")");
+            }
+        }
+    }
+    // the boundary examples, exactly as the untagged call adds them
+    vpt_status s = add_device(t, d_utf8, d_boff, d_ooff, n, total_b, d_labels, flags, st);
+    if (s != VPT_OK) return s;
+    // the tag examples: count, place, write
+    DBuf<uint64_t> ex_off, key_off, scratch;
+    VPT_HIP(counts.resize(total_chars)); VPT_HIP(is_ex.resize(total_chars)); VPT_HIP(ex_off.resize(total_chars + 1)); VPT_HIP(key_off.resize(total_chars + 1));
+    VPT_HIP(scratch.resize(vpt::train_scan_scratch(total_chars) + 1));
+    vpt::TagFeatParams P{};
+    P.cps = cps.p; P.ooff = d_ooff; P.labels = d_labels; P.n_tags = d_n_tags; P.n_sent = n; P.total_chars = total_chars;
+    P.charn = t->prm.charn; P.typen = t->prm.typen; P.is_ex = is_ex.p; P.counts = counts.p;
+    VPT_HIP(vpt::train_tag_features(P, false, st));
+    VPT_HIP(vpt::train_scan_u32(is_ex.p, total_chars, ex_off.p, scratch.p, st));
+    VPT_HIP(vpt::train_scan_u32(counts.p, total_chars, key_off.p, scratch.p, st));
+    uint64_t n_ex = 0, n_keys = 0;
+    VPT_HIP(hipMemcpyAsync(&n_ex, ex_off.p + total_chars, 8, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(&n_keys, key_off.p + total_chars, 8, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    if (t->n_tag_cps + total_chars >= (uint64_t(1) << 32) || t->n_tag_keys + n_keys >= (uint64_t(1) << 32) || t->n_tag_ex + n_ex >= (uint64_t(1) << 32))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 chars, tagged tokens and tag feature occurrences");
+    // the examples stay on the device: the batch's chars, the records and the keys are appended to the trainer's arrays
+    DBuf<uint32_t> recs;
+    VPT_HIP(recs.resize(4 * n_ex));
+    VPT_HIP(t->d_tag_cps.grow(t->n_tag_cps + total_chars, t->n_tag_cps, st));
+    VPT_HIP(t->d_tag_ex.grow(4 * (t->n_tag_ex + n_ex), 4 * t->n_tag_ex, st));
+    VPT_HIP(t->d_tag_keys.grow(2 * (t->n_tag_keys + n_keys), 2 * t->n_tag_keys, st));
+    P.ex_off = ex_off.p; P.key_off = key_off.p; P.recs = recs.p; P.keys = t->d_tag_keys.p + 2 * t->n_tag_keys;
+    VPT_HIP(vpt::train_tag_features(P, true, st));
+    VPT_HIP(hipMemcpyAsync(t->d_tag_cps.p + t->n_tag_cps, cps.p, total_chars * 4, hipMemcpyDeviceToDevice, st));
+    VPT_HIP(vpt::train_tag_rec_finish(recs.p, n_ex, d_ooff, key_off.p, uint32_t(t->n_tag_cps), uint32_t(t->n_tag_keys), t->d_tag_ex.p + 4 * t->n_tag_ex, st));
+    std::vector<uint32_t> h_recs(4 * n_ex);
+    if (n_ex) VPT_HIP(hipMemcpyAsync(h_recs.data(), recs.p, n_ex * 16, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipStreamSynchronize(st));
+    // the tag strings are interned here, on the host: 16 bytes an example come back, no char and no key
+    const double t_host = now_s();
+    for (uint64_t x = 0; x < n_ex; ++x) {
+        const uint32_t sent = h_recs[4 * x], end = h_recs[4 * x + 2];
+        const uint64_t g = ooff[sent] + sent + end - 1;
+        t->ex_ntags.push_back(ntags[sent]);
+        t->ex_tag0.push_back(t->ex_tags.size());
+        for (uint32_t j = 0; j < ntags[sent]; ++j) {
+            const uint64_t k = tindex[g] + j;
+            if (k >= tindex[g + 1] || soff[k + 1] == soff[k]) { t->ex_tags.push_back(-1); continue; }
+            t->ex_tags.push_back(t->intern_tag(std::string(reinterpret_cast<const char*>(tbytes.data()) + soff[k], size_t(soff[k + 1] - soff[k]))));
+        }
+    }
+    t->n_tag_cps += total_chars;
+    t->n_tag_ex += n_ex;
+    t->n_tag_keys += n_keys;
+    t->tag_add_host_seconds += now_s() - t_host;
+    t->tags_built = false;
+    t->tags_trained = false;
+    return VPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -500,7 +1092,7 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     if (p.charw > 16) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "charw: must be at most 16");
     if (p.typew > 16) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "typew: must be at most 16");
     if (p.typew > p.charw) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "typew: must not exceed charw (type weights use the char window)");
-    if (p.flags != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: must be 0");
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS)) != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: must be 0 or VPT_TRAIN_TAGS");
     if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dictn: must be at least 1 with a dictionary");
     std::unique_ptr<vpt_trainer> t(new (std::nothrow) vpt_trainer());
     if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
@@ -654,7 +1246,8 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     if (pos == 0 || pos == nr)
         return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: need both WordBoundary and other boundaries");
     Tron T;
-    T.t = t; T.st = t->st; T.n = t->nd + 1; T.nr = nr; T.solver = solver; T.c = cost;
+    T.m = MatView{t->csr_ptr.p, t->cols.p, t->vals.p, t->crow.p, t->cval.p, &t->levels, t->nd};
+    T.st = t->st; T.n = t->nd + 1; T.nr = nr; T.solver = solver; T.c = cost;
     for (DBuf<double>* b : {&T.w, &T.w_new, &T.g, &T.s, &T.r, &T.d, &T.Hd}) VPT_HIP(b->resize(T.n));
     for (DBuf<double>* b : {&T.y, &T.z, &T.zt, &T.gz, &T.D, &T.loss}) VPT_HIP(b->resize(nr));
     VPT_HIP(T.part0.resize(vpt::train_dot_partials(std::max(T.n, nr)))); VPT_HIP(T.part1.resize(vpt::train_dot_partials(std::max(T.n, nr))));
@@ -667,6 +1260,10 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     VPT_HIP(hipMemcpy(t->w.data(), T.w.p, T.n * 8, hipMemcpyDeviceToHost));
     std::vector<uint64_t> keys(2 * t->nd);
     if (t->nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
+    if (t->prm.flags & VPT_TRAIN_TAGS) {
+        if ((s = build_tags(t)) != VPT_OK) return s;
+        if ((s = solve_tags(t, eps, cost, solver)) != VPT_OK) return s;
+    }
     if ((s = make_model(t, keys)) != VPT_OK) return s;
     t->trained = true;
     *needed = t->model.size();
@@ -707,6 +1304,172 @@ vpt_status vpt_trainer_last_stats(const void* th, void* out) {
     if (!t || !out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
     if (!t->trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained model");
     std::memcpy(out, &t->stats, sizeof t->stats);
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_add_tagged_batch_device(void* th, const uint8_t* d_utf8, const uint64_t* d_byte_offsets, const uint64_t* d_out_offsets,
+                                               size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels, const uint32_t* d_n_tags,
+                                               const uint64_t* d_tag_index, const uint64_t* d_span_offsets, const uint8_t* d_tag_bytes,
+                                               uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, void* hip_stream) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || (n_sentences && (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels) || !d_n_tags || !d_tag_index ||
+                               !d_span_offsets || (n_tag_bytes && !d_tag_bytes))))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    return add_tagged_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, d_n_tags, d_tag_index, d_span_offsets,
+                             d_tag_bytes, n_spans, n_tag_bytes, flags, static_cast<hipStream_t>(hip_stream));
+}
+
+vpt_status vpt_trainer_add_tagged_batch(void* th, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint8_t* labels,
+                                        const uint32_t* n_tags, const uint64_t* tag_index, const uint64_t* span_offsets, const uint8_t* tag_bytes,
+                                        uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || !byte_offsets || (n_sentences && (!utf8 || !n_tags || !tag_index || !span_offsets || (n_tag_bytes && !tag_bytes))))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!(t->prm.flags & VPT_TRAIN_TAGS))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    if (n_sentences == 0) return VPT_OK;
+    std::vector<uint64_t> ooff(n_sentences + 1);
+    vpt_status s = vpt_count_boundaries(utf8, byte_offsets, n_sentences, ooff.data());
+    if (s != VPT_OK) return s;
+    const uint64_t total_b = ooff[n_sentences], total_chars = total_b + n_sentences;
+    if (total_b && !labels) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    for (uint64_t b = 0; b < total_b; ++b)
+        if (labels[b] > 2) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "labels: must be 0, 1 or 2");
+    VPT_HIP(hipSetDevice(t->device));
+    const uint64_t b0 = byte_offsets[0], nbytes = byte_offsets[n_sentences] - b0;
+    std::vector<uint64_t> boff(byte_offsets, byte_offsets + n_sentences + 1);
+    for (auto& x : boff) x -= b0;
+    DBuf<uint8_t> d_text, d_labels, d_tb;
+    DBuf<uint64_t> d_boff, d_ooff, d_ti, d_so;
+    DBuf<uint32_t> d_nt;
+    VPT_HIP(d_text.resize(nbytes + 64)); VPT_HIP(d_labels.resize(total_b)); VPT_HIP(d_boff.resize(n_sentences + 1)); VPT_HIP(d_ooff.resize(n_sentences + 1));
+    VPT_HIP(d_nt.resize(n_sentences)); VPT_HIP(d_ti.resize(total_chars + 1)); VPT_HIP(d_so.resize(n_spans + 1)); VPT_HIP(d_tb.resize(n_tag_bytes));
+    VPT_HIP(hipMemsetAsync(d_text.p, 0, nbytes + 64, t->st));
+    VPT_HIP(hipMemcpyAsync(d_text.p, utf8 + b0, nbytes, hipMemcpyHostToDevice, t->st));
+    if (total_b) VPT_HIP(hipMemcpyAsync(d_labels.p, labels, total_b, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(d_boff.p, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(d_ooff.p, ooff.data(), ooff.size() * 8, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(d_nt.p, n_tags, n_sentences * 4, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(d_ti.p, tag_index, (total_chars + 1) * 8, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(d_so.p, span_offsets, (n_spans + 1) * 8, hipMemcpyHostToDevice, t->st));
+    if (n_tag_bytes) VPT_HIP(hipMemcpyAsync(d_tb.p, tag_bytes, n_tag_bytes, hipMemcpyHostToDevice, t->st));
+    return add_tagged_device(t, d_text.p, d_boff.p, d_ooff.p, n_sentences, total_b, d_labels.p, d_nt.p, d_ti.p, d_so.p, d_tb.p, n_spans, n_tag_bytes, flags,
+                             t->st);
+}
+
+vpt_status vpt_trainer_set_tag_dictionary(void* th, const uint8_t* surfaces_utf8, const uint64_t* surface_offsets, size_t n_surfaces,
+                                          const uint32_t* n_tags, const uint64_t* span_offsets, const uint8_t* tag_bytes) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || (n_surfaces && (!surfaces_utf8 || !surface_offsets || !n_tags || !span_offsets)))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!(t->prm.flags & VPT_TRAIN_TAGS))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    std::map<std::string, std::vector<int32_t>> defs;
+    std::vector<uint32_t> cps;
+    uint64_t k = 0;
+    for (size_t i = 0; i < n_surfaces; ++i) {
+        const std::string at = " (surface " + std::to_string(i) + ")";
+        if (surface_offsets[i + 1] <= surface_offsets[i]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "surface_offsets: must increase" + at);
+        const uint8_t* sp = surfaces_utf8 + surface_offsets[i];
+        const size_t len = size_t(surface_offsets[i + 1] - surface_offsets[i]);
+        if (!decode_utf8(sp, len, cps)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "surfaces: invalid UTF-8" + at);
+        std::vector<int32_t> tags;
+        for (uint32_t j = 0; j < n_tags[i]; ++j, ++k) {
+            if (span_offsets[k + 1] < span_offsets[k]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "span_offsets: must not decrease" + at);
+            const size_t tl = size_t(span_offsets[k + 1] - span_offsets[k]);
+            if (tl == 0) { tags.push_back(-1); continue; }
+            if (!tag_bytes) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+            const uint8_t* b = tag_bytes + span_offsets[k];
+            if (std::find(b, b + tl, uint8_t(0)) != b + tl) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: must not contain NULL" + at);
+            if (!decode_utf8(b, tl, cps)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: invalid UTF-8" + at);
+            tags.push_back(t->intern_tag(std::string(reinterpret_cast<const char*>(b), tl)));
+        }
+        defs.emplace(std::string(reinterpret_cast<const char*>(sp), len), std::move(tags));   // the first occurrence wins (trainer.rs:231-238)
+    }
+    t->tag_defaults = std::move(defs);
+    t->tags_built = false;
+    t->tags_trained = false;
+    t->trained = false;
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_set_tag_path(void* th, int mode) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (mode != 0 && mode != 1) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "mode: 0 (by size) or 1 (the global-memory solver)");
+    t->tag_path_mode = mode;
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_n_tag_problems(void* th, size_t* n_problems, size_t* n_models) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || !n_problems) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!(t->prm.flags & VPT_TRAIN_TAGS))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    vpt_status s = build_tags(t);
+    if (s != VPT_OK) return s;
+    *n_problems = t->tag_problems.size();
+    if (n_models) *n_models = t->tag_models.size();
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_tag_problem(void* th, size_t i, void* info_out, uint8_t* surface_out, uint8_t* cand_bytes_out, uint64_t* cand_offsets_out,
+                                   uint64_t* keys_out, uint64_t* row_ptr_out, uint32_t* cols_out, uint32_t* y_out) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || !info_out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!(t->prm.flags & VPT_TRAIN_TAGS))
+        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    vpt_status s = build_tags(t);
+    if (s != VPT_OK) return s;
+    if (i >= t->tag_problems.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "i: no such tag problem");
+    TagProblem& Pb = t->tag_problems[i];
+    if (row_ptr_out || cols_out) {
+        VPT_HIP(hipSetDevice(t->device));
+        if ((s = fetch_rows(t, Pb)) != VPT_OK) return s;
+    }
+    const std::string& tok = t->tag_models[Pb.model].token;
+    vpt_tag_problem_info info{};
+    info.slot = Pb.slot; info.n_classes = uint32_t(Pb.cands.size()); info.path = t->tags_trained ? Pb.path : 0; info.model = Pb.model;
+    info.seconds_setup = t->tags_trained ? Pb.seconds_setup : 0; info.seconds_solve = t->tags_trained ? Pb.seconds_solve : 0;
+    info.n_rows = Pb.y.size(); info.n_features = Pb.keys.size(); info.nnz = Pb.nnz; info.surface_bytes = tok.size();
+    for (int32_t id : Pb.cands) info.cand_bytes += t->tag_strings[size_t(id)].size();
+    std::memcpy(info_out, &info, sizeof info);
+    if (surface_out) std::memcpy(surface_out, tok.data(), tok.size());
+    uint64_t at = 0;
+    for (size_t c = 0; c < Pb.cands.size(); ++c) {
+        const std::string& tg = t->tag_strings[size_t(Pb.cands[c])];
+        if (cand_offsets_out) cand_offsets_out[c] = at;
+        if (cand_bytes_out) std::memcpy(cand_bytes_out + at, tg.data(), tg.size());
+        at += tg.size();
+    }
+    if (cand_offsets_out) cand_offsets_out[Pb.cands.size()] = at;
+    if (keys_out)
+        for (size_t j = 0; j < Pb.keys.size(); ++j) { keys_out[2 * j] = uint64_t(Pb.keys[j]); keys_out[2 * j + 1] = uint64_t(Pb.keys[j] >> 64); }
+    if (row_ptr_out) for (size_t r = 0; r < Pb.rp.size(); ++r) row_ptr_out[r] = Pb.rp[r];
+    if (cols_out && !Pb.cols.empty()) std::memcpy(cols_out, Pb.cols.data(), Pb.cols.size() * 4);
+    if (y_out && !Pb.y.empty()) std::memcpy(y_out, Pb.y.data(), Pb.y.size() * 4);
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_tag_weights(void* th, size_t i, void* weights_out, size_t capacity, void* stats_out) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t->trained || !t->tags_trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained tag models");
+    if (i >= t->tag_problems.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "i: no such tag problem");
+    const TagProblem& Pb = t->tag_problems[i];
+    if (weights_out) {
+        if (capacity < Pb.w.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than classes * (features + 1)");
+        std::memcpy(weights_out, Pb.w.data(), Pb.w.size() * 8);
+    }
+    if (stats_out) std::memcpy(stats_out, Pb.stats.data(), Pb.stats.size() * sizeof(vpt_train_stats));
+    return VPT_OK;
+}
+
+vpt_status vpt_trainer_tag_summary(const void* th, void* out) {
+    const vpt_trainer* t = static_cast<const vpt_trainer*>(th);
+    if (!t || !out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t->trained || !t->tags_trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained tag models");
+    std::memcpy(out, &t->tag_summary, sizeof t->tag_summary);
     return VPT_OK;
 }
 

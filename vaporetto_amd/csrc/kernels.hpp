@@ -326,4 +326,66 @@ hipError_t train_scale_rows(uint64_t n, const double* d, double* t, hipStream_t 
 hipError_t train_loss(uint64_t n, const double* z, const double* y, double c, int solver, double* loss, hipStream_t st);
 hipError_t train_grad_rows(uint64_t n, const double* z, const double* y, double c, int solver, double* gz, double* D, hipStream_t st);
 
+// tag-model training (kernels_train_tags.hip)
+struct TagFeatParams {
+    const uint32_t* cps;        // decode_chars' words: sentence i's char c at ooff[i] + i + c
+    const uint64_t* ooff;       // [n_sent + 1]
+    const uint8_t* labels;      // sentence i's boundary b at ooff[i] + b
+    const uint32_t* n_tags;     // [n_sent] Sentence::n_tags
+    uint64_t n_sent, total_chars;
+    uint32_t charn, typen;
+    uint32_t* is_ex;            // count pass: 1 where a token with tag slots ends at the char
+    uint32_t* counts;           // count pass: that token's features
+    const uint64_t* ex_off;     // emit pass: the scans of the two
+    const uint64_t* key_off;
+    uint32_t* recs;             // emit pass: per example (sentence, start, end, features)
+    uint64_t* keys;             // emit pass: two words per key (low, high)
+};
+hipError_t train_tag_features(const TagFeatParams& P, bool emit, hipStream_t st);
+hipError_t train_tag_validate(const uint32_t* n_tags, const uint64_t* ooff, uint64_t n_sent, uint64_t total_chars, const uint64_t* tag_index,
+                              const uint64_t* span_off, uint64_t n_spans, uint64_t n_tag_bytes, uint32_t* status, hipStream_t st);
+// the trainer's example records: (first char in its char pool, chars, first key, keys)
+hipError_t train_tag_rec_finish(const uint32_t* recs, uint64_t n_ex, const uint64_t* ooff, const uint64_t* key_off, uint32_t cps_base, uint32_t key_base,
+                                uint32_t* out, hipStream_t st);
+// surface ids: representatives by a hash table, the distinct surfaces as a padded matrix (radix-sorted by the caller), ids by rank
+hipError_t train_surf_insert(const uint32_t* ex, uint64_t n_ex, const uint32_t* cps, uint64_t* table, uint64_t mask, uint32_t* rep, uint32_t* flag,
+                             uint32_t* maxlen, hipStream_t st);
+hipError_t train_surf_matrix(const uint32_t* ex, uint64_t n_ex, const uint32_t* flag, const uint64_t* pos, const uint32_t* cps, uint32_t maxlen,
+                             uint32_t* mat, uint32_t* slot, hipStream_t st);
+hipError_t train_surf_ids(const uint32_t* order, uint64_t n_surf, uint32_t* id_of, const uint32_t* rep, const uint32_t* slot, uint64_t n_ex, uint32_t* sid,
+                          hipStream_t st);
+// all problems' matrices over concatenated arrays: occ_off NULL counts a row's keys into nk_or_occ, else writes the (key, problem) records
+hipError_t train_tag_expand(const uint32_t* row_ex, const uint32_t* row_prob, uint64_t n_rows, const uint32_t* ex, const uint64_t* occ_off,
+                            const uint64_t* keys, uint32_t* nk_or_occ, uint32_t* occ_row, hipStream_t st);
+hipError_t train_tag_flags(const uint32_t* occ, const uint32_t* order, uint64_t n, uint32_t* flag, hipStream_t st);
+struct TagBuildParams {
+    uint64_t n_prob, n_rows, n_occ;
+    const uint64_t* prob_row_ptr;   // [n_prob + 1] the problems' rows
+    const uint32_t* row_prob;       // [n_rows]
+    const uint64_t* occ_off;        // [n_rows + 1] the rows' occurrences
+    const uint32_t* occ;            // [5 * n_occ] (key, problem)
+    const uint32_t* occ_row;        // [n_occ]
+    const uint32_t* order;          // [n_occ] sorted by (problem, key), stable
+    const uint32_t* flag;           // [n_occ] first of its key
+    const uint64_t* dpos;           // [n_occ + 1] exclusive scan of flag
+    uint64_t *prob_occ0, *key_ptr;  // out [n_prob + 1]
+    uint32_t* occ_col;              // out [n_occ] the CSR's columns (rows sorted)
+    uint64_t* dkeys;                // out [2 * distinct] the problems' sorted keys, back to back
+    uint32_t *rp, *cp, *crow;       // out: row pointers [n_rows + n_prob], column pointers [distinct + n_prob], CSC rows [n_occ]
+};
+hipError_t train_tag_assemble(const TagBuildParams& B, hipStream_t st);
+// the in-kernel solver keeps 7 vectors of features + 1 and 3 of rows in LDS
+constexpr uint32_t kTagLdsDoubles = 7424;
+struct TagSolveDesc {
+    uint64_t rp, cols, cp, y, w, stats;   // where the problem's row pointers, nonzeros (CSR and CSC alike), column pointers, labels, weights and stats start
+    uint32_t nf, l, k, pad;               // features (the bias is one more), rows, classes
+};
+struct TagClassStats {
+    uint32_t iterations, cg_steps;
+    double gnorm0, gnorm, objective;
+};
+bool train_tag_fits(uint64_t rows, uint64_t features, uint64_t nnz);
+hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
+                           const uint32_t* y, double eps, double cost, int solver, double* w, TagClassStats* stats, hipStream_t st);
+
 }  // namespace vpt

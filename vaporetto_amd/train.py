@@ -5,8 +5,12 @@ KyteaFullwidthFilter unless --no-norm, trains the boundary model on the device (
 run there) and writes the model un-compressed (the `evaluate` CLI reads it as it is; the reference writes zstd).  Progress goes to
 stderr as the reference prints it.  Tokenized lines are parsed by the library's parser (vpt_parse_tokenized_batch) in chunks.
 
-Divergences: tag models are not trained, so a corpus or dictionary line that carries a tag is an error naming the file and line
-unless --ignore-tags (ours) drops the tags; only solvers 0 and 2 are implemented; --zstd-workers does not exist."""
+With --train-tags (ours) the tags of the corpora are kept and the tag models are trained on the device too (api.Trainer(train_tags=True):
+the parser's arrays go straight into add_packed_tagged), the dictionary lines become the tag dictionary (main.rs:131-157), and the
+reference's `Tags: n/n` line is printed once, at the end.
+
+Divergences: without --train-tags tag models are not trained, so a corpus or dictionary line that carries a tag is an error naming the
+file and line unless --ignore-tags (ours) drops the tags; only solvers 0 and 2 are implemented; --zstd-workers does not exist."""
 import argparse
 import sys
 
@@ -55,7 +59,7 @@ def _parse_tokenized(path, lines, ignore_tags):
             tagged = has[ti[last]] - has[ti[first]] > 0
             i = int(np.argmax(tagged))
             if tagged[i]:
-                raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them)" % (path, c0 + i + 1))
+                raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them, --train-tags trains them)" % (path, c0 + i + 1))
         yield p["raw"], p["raw_offsets"], p["labels"], p
 
 
@@ -68,7 +72,7 @@ def _parse_partial(path, lines, ignore_tags):
         except api.VaporettoError as e:
             raise CorpusError("%s:%d: %s" % (path, i + 1, e)) from None
         if not ignore_tags and any(t is not None for t in s.tags()):
-            raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them)" % (path, i + 1))
+            raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them, --train-tags trains them)" % (path, i + 1))
         sents.append(s)
     return sents
 
@@ -90,9 +94,13 @@ def main(argv=None) -> int:
                     help="The solver. {0, 1, 2, 3, 4, 5, 6, 7} (only 0 and 2 are implemented here)")
     ap.add_argument("--no-norm", action="store_true", help="Do not normalize training data.")
     ap.add_argument("--ignore-tags", action="store_true", help="Drop tags of the corpora and dictionaries (no tag models are trained).")
+    ap.add_argument("--train-tags", action="store_true", help="Keep the tags of the corpora and dictionaries and train the tag models.")
     args = ap.parse_args(argv)
     if not args.tok and not args.part:
         ap.error("one of --tok or --part is required")
+    if args.train_tags and args.ignore_tags:
+        ap.error("--train-tags and --ignore-tags exclude each other")
+    skip_tags = args.ignore_tags or args.train_tags   # either way a tag is no error
 
     from . import api
     fw = api.KyteaFullwidthFilter()
@@ -102,24 +110,27 @@ def main(argv=None) -> int:
         for path in args.tok:
             print("Loading %r ..." % path, file=sys.stderr)
             lines = _lines(path)
-            for raw, roff, labels, _ in _parse_tokenized(path, lines, args.ignore_tags):
-                batches.append((raw, roff, labels))
+            for raw, roff, labels, p in _parse_tokenized(path, lines, skip_tags):
+                batches.append((raw, roff, labels, p if args.train_tags else None))
             n_sent += len(lines)
             print("# of sentences: %d" % n_sent, file=sys.stderr)
         for path in args.part:
             print("Loading %r ..." % path, file=sys.stderr)
-            sents = _parse_partial(path, _lines(path), args.ignore_tags)
-            if sents:
+            sents = _parse_partial(path, _lines(path), skip_tags)
+            if sents and args.train_tags:
+                batches.append((sents, None, None, None))
+            elif sents:
                 utf8, boff = api.pack_texts([s.as_raw_text().encode("utf-8") for s in sents])
-                batches.append((utf8, boff, np.concatenate([np.asarray(s.boundaries(), np.uint8) for s in sents])))
+                batches.append((utf8, boff, np.concatenate([np.asarray(s.boundaries(), np.uint8) for s in sents]), None))
             n_sent += len(sents)
             print("# of sentences: %d" % n_sent, file=sys.stderr)
-        words = set()
+        words, tag_dictionary = set(), []
         for path in args.dict:
             print("Loading %r ..." % path, file=sys.stderr)
             lines = _lines(path)
-            for raw, roff, labels, p in _parse_tokenized(path, lines, args.ignore_tags):
+            for raw, roff, labels, p in _parse_tokenized(path, lines, skip_tags):
                 oo = p["out_offsets"]
+                ti, so, tb = p["tag_index"], p["span_offsets"], bytes(p["tag_bytes"])
                 for i in range(len(roff) - 1):
                     text = bytes(raw[int(roff[i]):int(roff[i + 1])]).decode("utf-8")
                     if not args.no_norm:
@@ -127,16 +138,30 @@ def main(argv=None) -> int:
                     s = api.Sentence.from_raw(text)
                     s._boundaries = labels[int(oo[i]):int(oo[i + 1])].copy()
                     words.update(s.iter_tokens())
+                    if args.train_tags:   # the tokens with the tags of their last chars, the text normalised and the tags as they are
+                        nt, g0 = int(p["n_tags"][i]), int(oo[i]) + i
+                        for a, e in s._token_ranges():
+                            own = [tb[int(so[k]):int(so[k + 1])].decode("utf-8") for k in range(int(ti[g0 + e]), int(ti[g0 + e + 1]))]
+                            tag_dictionary.append((text[a:e + 1], [(t or None) for t in own] + [None] * (nt - len(own))))
             print("# of words: %d" % len(words), file=sys.stderr)
         dictionary = sorted(words)   # BTreeSet<String>: code point order (main.rs:132-161)
 
         print("Extracting into features...", file=sys.stderr)
-        trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags)
-        for utf8, boff, labels in batches:
-            trainer.add_packed(utf8, boff, labels, fullwidth=not args.no_norm)
+        trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags,
+                              train_tags=args.train_tags, tag_dictionary=tag_dictionary)
+        for utf8, boff, labels, p in batches:
+            if boff is None:
+                trainer.add_examples(utf8, fullwidth=not args.no_norm)
+            elif p is not None:
+                trainer.add_packed_tagged(utf8, boff, labels, p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"],
+                                          fullwidth=not args.no_norm)
+            else:
+                trainer.add_packed(utf8, boff, labels, fullwidth=not args.no_norm)
         print("# of features: %d" % trainer.n_features(), file=sys.stderr)
         print("Start training...", file=sys.stderr)
         model = trainer.train_bytes(args.eps, args.cost, args.solver)
+        if args.train_tags:
+            print("Tags: %d/%d" % ((trainer.n_tag_models(),) * 2), file=sys.stderr)
         print("Finish training.", file=sys.stderr)
     except CorpusError as e:
         print("Error: %s" % e, file=sys.stderr)
