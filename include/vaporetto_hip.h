@@ -475,7 +475,7 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * and the column segments of Xᵀv: per level 8 bytes per feature (pointers) and 12 bytes per segment (column + partial sum), with at
  * least one segment per feature per level and ceil(log64(longest column)) levels -- about 100 bytes per feature when one column
  * holds tens of millions of nonzeros.  Training adds 48 bytes per boundary and 56 per feature for the fp64 vectors.  While the ids
- * are assigned, about 60 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
+ * are assigned, about 52 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
  *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0 or VPT_TRAIN_TAGS (any other bit is

@@ -310,6 +310,10 @@ def check_errors():
     nul[0] = 0
     with pytest.raises(api.VaporettoError, match=r"must not contain NULL \(sentence \d+\)"):
         t.add_packed_tagged(utf8, boff, labels, n_tags, tindex, so, nul)
+    overlong = tb.copy()
+    overlong[:2] = (0xC0, 0x80)   # an overlong NUL: no NUL byte, and no UTF-8 that the model's loader takes
+    with pytest.raises(api.VaporettoError, match=r"tags: invalid UTF-8 \(sentence \d+\)"):
+        t.add_packed_tagged(utf8, boff, labels, n_tags, tindex, so, overlong)
     assert t.n_features() == 0 and t.tag_problems() == []
     t.add_packed_tagged(*arrays)
     for solver in (1, 3, 4, 5, 6, 7):

@@ -130,6 +130,13 @@ def check_errors():
         api.Trainer(2, 2, 2, 2, ["あ"], 0)
     with pytest.raises(api.VaporettoError, match="empty word"):
         api.Trainer(2, 2, 2, 2, ["あ", ""], 2)
+    # a dictionary word that is no well-formed UTF-8 (an overlong NUL): through the C ABI, api.Trainer takes str
+    import ctypes as C
+    from vaporetto_amd import _lib
+    prm = _lib.TrainParams(2, 2, 2, 2, 2, 0)
+    word, off, h = (C.c_uint8 * 2)(0xC0, 0x80), (C.c_uint64 * 2)(0, 2), C.c_void_p()
+    assert _lib.load().vpt_trainer_create(C.addressof(prm), word, off, 1, 0, C.byref(h)) == _lib.VPT_INVALID_ARGUMENT
+    assert "dict_words: invalid UTF-8" in _lib.last_error()
     t = api.Trainer(2, 2, 2, 2)
     t.add_packed(*api.pack_texts(["あいう".encode()]), np.array([1, 0], np.uint8))
     for solver in (1, 3, 4, 5, 6, 7):

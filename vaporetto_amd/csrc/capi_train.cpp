@@ -58,39 +58,22 @@ struct XtvLevel {
     uint64_t nseg = 0;
 };
 
+struct Matrix {   // a design matrix on the device: CSR, CSC and the segments of Xᵀv (csc_levels); the bias column follows column nd - 1
+    uint64_t nd = 0, nnz = 0;
+    DBuf<uint64_t> csr_ptr, cptr;
+    DBuf<uint32_t> cols, crow;
+    DBuf<uint16_t> vals, cval;
+    std::vector<std::unique_ptr<XtvLevel>> levels;
+};
+
 void put_utf8(std::string& s, uint32_t c) {
     if (c < 0x80) s += char(c);
     else if (c < 0x800) { s += char(0xC0 | (c >> 6)); s += char(0x80 | (c & 0x3F)); }
     else if (c < 0x10000) { s += char(0xE0 | (c >> 12)); s += char(0x80 | ((c >> 6) & 0x3F)); s += char(0x80 | (c & 0x3F)); }
     else { s += char(0xF0 | (c >> 18)); s += char(0x80 | ((c >> 12) & 0x3F)); s += char(0x80 | ((c >> 6) & 0x3F)); s += char(0x80 | (c & 0x3F)); }
 }
-// valid UTF-8 -> scalar values (false if invalid)
-bool decode_utf8(const uint8_t* s, size_t len, std::vector<uint32_t>& out) {
-    out.clear();
-    for (size_t i = 0; i < len;) {
-        const uint8_t b = s[i];
-        uint32_t c, k;
-        if (b < 0x80) { c = b; k = 0; }
-        else if ((b & 0xE0) == 0xC0) { c = b & 0x1F; k = 1; }
-        else if ((b & 0xF0) == 0xE0) { c = b & 0x0F; k = 2; }
-        else if ((b & 0xF8) == 0xF0) { c = b & 0x07; k = 3; }
-        else return false;
-        for (uint32_t j = 1; j <= k; ++j) {
-            if (i + j >= len || (s[i + j] & 0xC0) != 0x80) return false;
-            c = (c << 6) | (s[i + j] & 0x3F);
-        }
-        if (c > 0x10FFFF) return false;
-        out.push_back(c);
-        i += k + 1;
-    }
-    return true;
-}
-
-uint64_t mix64h(uint64_t x) {   // kernels_train.hip's mix64
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
-}
+// a symbol of an n-gram of the model: a char as UTF-8, a char type as its byte
+void put_sym(std::string& s, uint32_t kind, uint32_t x) { if (kind == 0) put_utf8(s, x); else s += char(x); }
 
 // bincode varint encoding of Model::to_vec (modelfmt._Writer)
 struct Enc {
@@ -154,13 +137,11 @@ struct vpt_trainer {
     DBuf<uint32_t> row_cnt;   // occurrences per boundary
     DBuf<uint8_t> labels;
     uint64_t nnz_occ = 0, nrows = 0;
-    // the design matrix (valid while `built`)
+    DBuf<uint64_t> scratch;   // of the scans (scan_total, Sorter): grown on demand
+    // the design matrix and its columns' keys (valid while `built`)
     bool built = false;
-    uint64_t nd = 0, nnz = 0;
-    DBuf<uint64_t> sorted_keys, csr_ptr, cptr;
-    DBuf<uint32_t> cols, crow;
-    DBuf<uint16_t> vals, cval;
-    std::vector<std::unique_ptr<XtvLevel>> levels;
+    Matrix m;
+    DBuf<uint64_t> sorted_keys;
     // the last training
     std::vector<double> w;        // nd weights + the bias
     std::vector<uint8_t> model;
@@ -202,39 +183,87 @@ struct vpt_trainer {
 
 namespace {
 
-constexpr const char* kIA = "InvalidArgumentError: ";
+vpt_status fail_arg(const std::string& msg) { return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: " + msg); }
+#define VPT_TRY(expr)                       \
+    do {                                    \
+        const vpt_status s_ = (expr);       \
+        if (s_ != VPT_OK) return s_;        \
+    } while (0)
 
-// the CSC copy of a CSR's nonzeros (stably sorted by column: rows ascend within a column) and the segments of Xᵀv, level by level,
-// until a column is one segment
-vpt_status csc_levels(hipStream_t st, const uint32_t* cols, const uint16_t* vals, const uint32_t* rows, uint64_t nz, uint64_t nd,
-                      DBuf<uint32_t>& crow, DBuf<uint16_t>& cval, DBuf<uint64_t>& cptr, std::vector<std::unique_ptr<XtvLevel>>& levels) {
-    levels.clear();
+// the handle of a call that needs a trainer made with VPT_TRAIN_TAGS; args: the call's other pointers are there.  NULL: the error is set
+vpt_trainer* tag_trainer(void* th, bool args) {
+    vpt_trainer* t = static_cast<vpt_trainer*>(th);
+    if (!t || !args) fail_arg("NULL argument");
+    else if (!(t->prm.flags & VPT_TRAIN_TAGS)) fail_arg("tags: the trainer was created without VPT_TRAIN_TAGS");
+    else return t;
+    return nullptr;
+}
+
+// the exclusive scan of in[0 .. n) into out[0 .. n] on the trainer's stream; total: out[n] read back (NULL: not needed, nothing waits)
+template <typename T>
+vpt_status scan_total(vpt_trainer* t, const T* in, uint64_t n, uint64_t* out, uint64_t* total) {
+    VPT_HIP(t->scratch.grow(vpt::train_scan_scratch(n) + 1, 0, t->st));
+    VPT_HIP(vpt::train_scan(in, n, out, t->scratch.p, t->st));
+    if (!total) return VPT_OK;
+    VPT_HIP(hipMemcpyAsync(total, out + n, 8, hipMemcpyDeviceToHost, t->st));
+    VPT_HIP(hipStreamSynchronize(t->st));
+    return VPT_OK;
+}
+
+// slots of an open-addressing table for n items: a power of two, at most half full
+uint64_t table_slots(uint64_t n) {
+    uint64_t slots = 2;
+    while (slots < 2 * n) slots <<= 1;
+    return slots;
+}
+
+// the stable LSD radix sort of item indices: its buffers and its passes; `order` holds the result of run
+struct Sorter {
     DBuf<uint32_t> order, tmp;
-    DBuf<uint64_t> hist, hist_scan, scratch;
-    VPT_HIP(order.resize(nz)); VPT_HIP(tmp.resize(nz));
-    VPT_HIP(hist.resize(vpt::train_radix_scratch(nz))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(nz) + 1));
-    VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>({nz, nd, vpt::train_radix_scratch(nz)})) + 1));
-    uint32_t ws[4];
-    uint32_t cpasses = 1;
-    while (cpasses < 4 && nd > (uint64_t(1) << (8 * cpasses))) ++cpasses;
-    for (uint32_t k = 0; k < cpasses; ++k) ws[k] = 8 * k;
-    VPT_HIP(vpt::train_radix_sort(cols, 1, ws, cpasses, nz, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
-    VPT_HIP(crow.resize(nz)); VPT_HIP(cval.resize(nz)); VPT_HIP(cptr.resize(nd + 1));
-    VPT_HIP(vpt::train_csc_fill(order.p, cols, vals, rows, nz, crow.p, cval.p, cptr.p, st));
-    VPT_HIP(hipMemcpyAsync(cptr.p + nd, &nz, 8, hipMemcpyHostToDevice, st));
-    VPT_HIP(hipStreamSynchronize(st));   // nz is the caller's
+    DBuf<uint64_t> hist, hist_scan;
+    std::vector<uint32_t> passes;   // u32 word of the item << 8 | bit shift, least significant digit first
+    void bytes(uint32_t word, uint32_t n_bytes) {
+        for (uint32_t k = 0; k < n_bytes; ++k) passes.push_back((word << 8) | (8 * k));
+    }
+    // as many bytes as the values below n need
+    static uint32_t bytes_below(uint64_t n) {
+        uint32_t b = 1;
+        while (b < 4 && n > (uint64_t(1) << (8 * b))) ++b;
+        return b;
+    }
+    vpt_status run(vpt_trainer* t, const uint32_t* base, uint32_t stride, uint64_t n) {
+        const uint64_t nh = vpt::train_radix_scratch(n);
+        VPT_HIP(order.resize(n)); VPT_HIP(tmp.resize(n)); VPT_HIP(hist.resize(nh)); VPT_HIP(hist_scan.resize(nh + 1));
+        VPT_HIP(t->scratch.grow(vpt::train_scan_scratch(nh) + 1, 0, t->st));
+        VPT_HIP(vpt::train_radix_sort(base, stride, passes.data(), uint32_t(passes.size()), n, order.p, tmp.p, hist.p, hist_scan.p, t->scratch.p, t->st));
+        return VPT_OK;
+    }
+};
+
+// M's CSC copy of its CSR's nonzeros (stably sorted by column: rows ascend within a column) and the segments of Xᵀv, level by level,
+// until a column is one segment; rows: the row of every nonzero
+vpt_status csc_levels(vpt_trainer* t, Matrix& M, const uint32_t* rows, uint64_t nz, uint64_t nd) {
+    hipStream_t st = t->st;
+    M.levels.clear();
+    M.nd = nd;
+    M.nnz = nz;
+    Sorter S;
+    S.bytes(0, Sorter::bytes_below(nd));
+    VPT_TRY(S.run(t, M.cols.p, 1, nz));
+    VPT_HIP(M.crow.resize(nz)); VPT_HIP(M.cval.resize(nz)); VPT_HIP(M.cptr.resize(nd + 1));
+    VPT_HIP(vpt::train_csc_fill(S.order.p, M.cols.p, M.vals.p, rows, nz, M.crow.p, M.cval.p, M.cptr.p, st));
+    VPT_HIP(hipMemcpyAsync(M.cptr.p + nd, &nz, 8, hipMemcpyHostToDevice, st));
+    VPT_HIP(hipStreamSynchronize(st));   // nz is a local
     DBuf<uint64_t> cnt;
     VPT_HIP(cnt.resize(nd));
-    const uint64_t* ptr = cptr.p;
+    const uint64_t* ptr = M.cptr.p;
     for (;;) {
-        levels.emplace_back(new XtvLevel());
-        XtvLevel& L = *levels.back();
+        M.levels.emplace_back(new XtvLevel());
+        XtvLevel& L = *M.levels.back();
         L.ptr = ptr;
         VPT_HIP(L.nptr.resize(nd + 1));
         VPT_HIP(vpt::train_seg_count(ptr, nd, cnt.p, st));
-        VPT_HIP(vpt::train_scan_u64(cnt.p, nd, L.nptr.p, scratch.p, st));
-        VPT_HIP(hipMemcpyAsync(&L.nseg, L.nptr.p + nd, 8, hipMemcpyDeviceToHost, st));
-        VPT_HIP(hipStreamSynchronize(st));
+        VPT_TRY(scan_total(t, cnt.p, nd, L.nptr.p, &L.nseg));
         VPT_HIP(L.seg_col.resize(L.nseg)); VPT_HIP(L.out.resize(L.nseg));
         VPT_HIP(vpt::train_seg_col(L.nptr.p, nd, L.seg_col.p, st));
         ptr = L.nptr.p;
@@ -247,91 +276,86 @@ vpt_status csc_levels(hipStream_t st, const uint32_t* cols, const uint16_t* vals
 vpt_status build(vpt_trainer* t) {
     if (t->built) return VPT_OK;
     hipStream_t st = t->st;
+    Matrix& M = t->m;
     const uint64_t nnz = t->nnz_occ, nrows = t->nrows;
     if (nnz >= (uint64_t(1) << 32) || nrows >= (uint64_t(1) << 32))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 boundaries and feature occurrences");
+        return fail_arg("examples: at most 2^32 - 1 boundaries and feature occurrences");
     // ---- representatives of the distinct keys
-    uint64_t slots = 2;
-    while (slots < 2 * nnz) slots <<= 1;
-    DBuf<uint64_t> table, rep, pos, slot, scratch;
-    DBuf<uint32_t> flag;
+    const uint64_t slots = table_slots(nnz);
+    DBuf<uint64_t> table, pos;
+    DBuf<uint32_t> rep, slot, flag;
     VPT_HIP(table.resize(slots));
     VPT_HIP(hipMemsetAsync(table.p, 0, slots * 8, st));
     VPT_HIP(rep.resize(nnz)); VPT_HIP(flag.resize(nnz)); VPT_HIP(pos.resize(nnz + 1)); VPT_HIP(slot.resize(nnz));
-    VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>({nnz, nrows, vpt::train_radix_scratch(nnz)})) + 1));
     VPT_HIP(vpt::train_insert(t->keys.p, nnz, table.p, slots - 1, rep.p, flag.p, st));
-    VPT_HIP(vpt::train_scan_u32(flag.p, nnz, pos.p, scratch.p, st));
     uint64_t nd = 0;
-    VPT_HIP(hipMemcpyAsync(&nd, pos.p + nnz, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipStreamSynchronize(st));
+    VPT_TRY(scan_total(t, flag.p, nnz, pos.p, &nd));
     table.reset(); flag.reset();
     DBuf<uint64_t> dkeys;
     VPT_HIP(dkeys.resize(2 * nd));
     VPT_HIP(vpt::train_compact(t->keys.p, rep.p, pos.p, nnz, dkeys.p, slot.p, st));
     // ---- the distinct keys sorted: 16 passes of 8 bits over the four 32-bit words, least significant first
-    DBuf<uint32_t> order, tmp;
-    DBuf<uint64_t> hist, hist_scan;
-    const uint64_t big = std::max(nd, nnz);
-    VPT_HIP(order.resize(big)); VPT_HIP(tmp.resize(big));
-    VPT_HIP(hist.resize(vpt::train_radix_scratch(big))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(big) + 1));
-    uint32_t ws[16];
-    for (uint32_t k = 0; k < 16; ++k) ws[k] = ((k / 4) << 8) | (8 * (k % 4));
-    VPT_HIP(vpt::train_radix_sort(reinterpret_cast<const uint32_t*>(dkeys.p), 4, ws, 16, nd, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
-    DBuf<uint32_t> col_of, ids;
-    VPT_HIP(col_of.resize(nd)); VPT_HIP(ids.resize(nnz)); VPT_HIP(t->sorted_keys.resize(2 * nd));
-    VPT_HIP(vpt::train_ids(order.p, nd, col_of.p, rep.p, slot.p, nnz, ids.p, dkeys.p, t->sorted_keys.p, st));
-    VPT_HIP(hipStreamSynchronize(st));
-    rep.reset(); slot.reset(); dkeys.reset(); col_of.reset();
+    DBuf<uint32_t> ids;
+    {
+        Sorter S;
+        DBuf<uint32_t> col_of;
+        for (uint32_t w = 0; w < 4; ++w) S.bytes(w, 4);
+        VPT_TRY(S.run(t, reinterpret_cast<const uint32_t*>(dkeys.p), 4, nd));
+        VPT_HIP(col_of.resize(nd)); VPT_HIP(ids.resize(nnz)); VPT_HIP(t->sorted_keys.resize(2 * nd));
+        VPT_HIP(vpt::train_ids(S.order.p, nd, col_of.p, rep.p, slot.p, nnz, ids.p, st));
+        VPT_HIP(vpt::train_sorted_keys(dkeys.p, S.order.p, nd, t->sorted_keys.p, st));
+        VPT_HIP(hipStreamSynchronize(st));
+    }
+    rep.reset(); slot.reset(); dkeys.reset();
     // ---- CSR: rows in corpus order, ids sorted, duplicates merged into counts
     DBuf<uint64_t> row_off;
-    DBuf<uint32_t> merged, rows;
-    VPT_HIP(row_off.resize(nrows + 1)); VPT_HIP(merged.resize(nrows)); VPT_HIP(t->csr_ptr.resize(nrows + 1));
-    VPT_HIP(vpt::train_scan_u32(t->row_cnt.p, nrows, row_off.p, scratch.p, st));
+    DBuf<uint32_t> merged, rows, status;
+    VPT_HIP(row_off.resize(nrows + 1)); VPT_HIP(merged.resize(nrows)); VPT_HIP(M.csr_ptr.resize(nrows + 1));
+    VPT_TRY(scan_total(t, t->row_cnt.p, nrows, row_off.p, nullptr));
     VPT_HIP(vpt::train_row_sort(ids.p, row_off.p, nrows, merged.p, st));
-    VPT_HIP(vpt::train_scan_u32(merged.p, nrows, t->csr_ptr.p, scratch.p, st));
     uint64_t nz = 0;
-    VPT_HIP(hipMemcpyAsync(&nz, t->csr_ptr.p + nrows, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipStreamSynchronize(st));
-    DBuf<uint32_t> status;
+    VPT_TRY(scan_total(t, merged.p, nrows, M.csr_ptr.p, &nz));
     VPT_HIP(status.resize(1));
     VPT_HIP(hipMemsetAsync(status.p, 0, 4, st));
-    VPT_HIP(t->cols.resize(nz)); VPT_HIP(t->vals.resize(nz)); VPT_HIP(rows.resize(nz));
-    VPT_HIP(vpt::train_row_merge(ids.p, row_off.p, t->csr_ptr.p, nrows, t->cols.p, t->vals.p, rows.p, status.p, st));
+    VPT_HIP(M.cols.resize(nz)); VPT_HIP(M.vals.resize(nz)); VPT_HIP(rows.resize(nz));
+    VPT_HIP(vpt::train_row_merge(ids.p, row_off.p, M.csr_ptr.p, nrows, M.cols.p, M.vals.p, rows.p, status.p, st));
     uint32_t bad = 0;
     VPT_HIP(hipMemcpyAsync(&bad, status.p, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: a feature occurs more than 65535 times at one boundary");
-    VPT_HIP(hipStreamSynchronize(st));
+    if (bad) return fail_arg("examples: a feature occurs more than 65535 times at one boundary");
     ids.reset(); row_off.reset(); merged.reset();
-    order.reset(); tmp.reset(); hist.reset(); hist_scan.reset(); scratch.reset();
-    vpt_status cs = csc_levels(st, t->cols.p, t->vals.p, rows.p, nz, nd, t->crow, t->cval, t->cptr, t->levels);
-    if (cs != VPT_OK) return cs;
-    VPT_HIP(hipStreamSynchronize(st));
-    t->nd = nd;
-    t->nnz = nz;
+    VPT_TRY(csc_levels(t, M, rows.p, nz, nd));
     t->built = true;
     return VPT_OK;
 }
 
 // TRON (liblinear tron.cpp as bundled by scikit-learn) for l2r_lr_fun (solver 0) / l2r_l2_svc_fun (solver 2), linear.cpp
-struct MatView {   // a design matrix on the device: CSR, CSC and the segments of Xᵀv; the bias column follows column nd - 1
-    const uint64_t* csr_ptr;
-    const uint32_t* cols;
-    const uint16_t* vals;
-    const uint32_t* crow;
-    const uint16_t* cval;
-    const std::vector<std::unique_ptr<XtvLevel>>* levels;
-    uint64_t nd;
-};
-
 struct Tron {
-    MatView m;
+    const Matrix* m;
     hipStream_t st;
     uint64_t n, nr;
     int solver;
     double c;
     DBuf<double> w, w_new, g, s, r, d, Hd, y, z, zt, gz, D, loss, part0, part1;
     hipError_t err = hipSuccess;
+
+    // for `rows` examples over M's columns and the bias
+    vpt_status init(const Matrix& M, hipStream_t stream, uint64_t rows, int solver_, double cost) {
+        m = &M; st = stream; n = M.nd + 1; nr = rows; solver = solver_; c = cost;
+        for (DBuf<double>* b : {&w, &w_new, &g, &s, &r, &d, &Hd}) VPT_HIP(b->resize(n));
+        for (DBuf<double>* b : {&y, &z, &zt, &gz, &D, &loss}) VPT_HIP(b->resize(nr));
+        for (DBuf<double>* b : {&part0, &part1}) VPT_HIP(b->resize(vpt::train_dot_partials(std::max(n, nr))));
+        return VPT_OK;
+    }
+    // one training from w = 0: the targets (+1 / -1, `pos` of them +1) go up, the weights come back into w_out[0 .. n)
+    vpt_status solve(const std::vector<double>& targets, uint64_t pos, double eps, vpt_train_stats* stats, double* w_out) {
+        VPT_HIP(hipMemcpy(y.p, targets.data(), nr * 8, hipMemcpyHostToDevice));
+        // liblinear's primal tolerance (linear.cpp train_one): eps * max(min(pos, neg), 1) / l
+        run(eps * double(std::max<uint64_t>(std::min(pos, nr - pos), 1)) / double(nr), stats);
+        VPT_HIP(err);
+        VPT_HIP(hipMemcpy(w_out, w.p, n * 8, hipMemcpyDeviceToHost));
+        return VPT_OK;
+    }
 
     // the fixed-shape sum of a[i] * b[i] (b NULL: a[i]), left on the device; returns where
     const double* reduce_dev(const double* a, const double* b, uint64_t len) {
@@ -359,17 +383,17 @@ struct Tron {
     // out = a + Xᵀu
     void add_xtv(const double* a, const double* u, double* out) {
         const double* in = nullptr;
-        for (auto& Lp : *m.levels) {
+        for (auto& Lp : m->levels) {
             XtvLevel& L = *Lp;
             if (err == hipSuccess)
-                err = vpt::train_xtv_level(L.ptr, L.nptr.p, L.seg_col.p, L.nseg, in, in ? nullptr : m.crow, m.cval, u, L.out.p, st);
+                err = vpt::train_xtv_level(L.ptr, L.nptr.p, L.seg_col.p, L.nseg, in, in ? nullptr : m->crow.p, m->cval.p, u, L.out.p, st);
             in = L.out.p;
         }
         const double* bias = reduce_dev(u, nullptr, nr);
         if (err == hipSuccess) err = vpt::train_add(n, a, in, bias, out, st);
     }
     double fun(const double* x) {
-        if (err == hipSuccess) err = vpt::train_xv(m.csr_ptr, m.cols, m.vals, nr, x, m.nd, z.p, st);
+        if (err == hipSuccess) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, x, m->nd, z.p, st);
         if (err == hipSuccess) err = vpt::train_loss(nr, z.p, y.p, c, solver, loss.p, st);
         const double reg = dot(x, x, n) / 2.0;
         return reg + dot(loss.p, nullptr, nr);
@@ -379,7 +403,7 @@ struct Tron {
         add_xtv(x, gz.p, out);
     }
     void hv(const double* v, double* out) {
-        if (err == hipSuccess) err = vpt::train_xv(m.csr_ptr, m.cols, m.vals, nr, v, m.nd, zt.p, st);
+        if (err == hipSuccess) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, v, m->nd, zt.p, st);
         if (err == hipSuccess) err = vpt::train_scale_rows(nr, D.p, zt.p, st);
         add_xtv(v, zt.p, out);
     }
@@ -417,7 +441,6 @@ struct Tron {
         }
         return cg_iter;
     }
-    // returns the number of iterations
     void run(double eps, vpt_train_stats* stats) {
         const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sigma1 = 0.25, sigma2 = 0.5, sigma3 = 4;
         const int max_iter = 1000;
@@ -469,7 +492,7 @@ void encode_tag_models(vpt_trainer* t, Enc& e);
 
 // trainer.rs:352-487: quantisation and the model's layout, then Model::to_vec
 vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
-    const uint64_t nd = t->nd;
+    const uint64_t nd = t->m.nd;
     const double bias = t->w[nd];
     double wmax = std::fabs(bias);
     for (uint64_t j = 0; j < nd; ++j) wmax = std::max(wmax, std::fabs(t->w[j]));
@@ -479,26 +502,20 @@ vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
     const int charw = int(t->prm.charw);
     std::map<std::string, std::vector<int32_t>> cw, tw;
     std::vector<int32_t> dw(3 * size_t(t->prm.dictn), 0);
-    static const int sh[5] = {99, 78, 57, 36, 15};
     for (uint64_t j = 0; j < nd; ++j) {
         const int32_t q = int32_t(t->w[j] / m);
         if (q == 0) continue;
-        const unsigned __int128 v = ((unsigned __int128)keys[2 * j + 1] << 64) | keys[2 * j];
-        const uint32_t kind = uint32_t(v >> 120) & 3u;
-        if (kind == 2) {
-            const uint32_t cls = uint32_t(v >> 99) & 0x1FFFFFu, where = uint32_t(v >> 78) & 0x1FFFFFu;
-            dw[3 * (cls - 1) + where] = q;
+        const vpt::TrainKey k = vpt::train_key(keys[2 * j], keys[2 * j + 1]);
+        if (k.kind == 2) {   // c: the class, then Left / Inside / Right
+            dw[3 * (k.c[0] - 1) + k.c[1]] = q;
             continue;
         }
-        const int len = int(v >> 5) & 7, rel = int(v & 31u) - 16;
+        const int len = int(k.len);
         std::string ng;
-        for (int k = 0; k < len; ++k) {
-            const uint32_t c = uint32_t(v >> sh[k]) & 0x1FFFFFu;
-            if (kind == 0) put_utf8(ng, c); else ng += char(c);
-        }
+        for (int i = 0; i < len; ++i) put_sym(ng, k.kind, k.c[i]);
         // the type n-grams use the char window too (trainer.rs:433-440)
-        const int posn = charw - len - rel;
-        auto& mp = kind == 0 ? cw : tw;
+        const int posn = charw - len - k.rel;
+        auto& mp = k.kind == 0 ? cw : tw;
         auto it = mp.find(ng);
         if (it == mp.end()) it = mp.emplace(ng, std::vector<int32_t>(size_t(2 * charw - len + 1), 0)).first;
         it->second[size_t(posn)] = q;
@@ -532,7 +549,7 @@ vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
 
 vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_boff, const uint64_t* d_ooff, size_t n, uint64_t total_b,
                       const uint8_t* d_labels, unsigned flags, hipStream_t st) {
-    if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: only VPT_FLAG_KYTEA_FULLWIDTH");
+    if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail_arg("flags: only VPT_FLAG_KYTEA_FULLWIDTH");
     if (n == 0) return VPT_OK;
     VPT_HIP(hipSetDevice(t->device));
     // the caller's stream, then ours: the examples are appended in call order
@@ -540,16 +557,15 @@ vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_b
     st = t->st;
     const uint64_t total_chars = total_b + n;
     DBuf<uint32_t> cps, status, counts;
-    DBuf<uint64_t> off, scratch;
+    DBuf<uint64_t> off;
     VPT_HIP(cps.resize(total_chars)); VPT_HIP(status.resize(1)); VPT_HIP(counts.resize(total_b)); VPT_HIP(off.resize(total_b + 1));
-    VPT_HIP(scratch.resize(vpt::train_scan_scratch(total_b) + 1));
     VPT_HIP(hipMemsetAsync(status.p, 0, 4, st));
     const bool fw = (flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
     VPT_HIP(vpt::launch_decode_chars(d_utf8, d_boff, d_ooff, n, total_chars, fw ? t->d_cinfo.p : nullptr, cps.p, nullptr, status.p, st, fw));
     uint32_t bad = 0;
     VPT_HIP(hipMemcpyAsync(&bad, status.p, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "out_offsets: do not match the text");
+    if (bad) return fail_arg("out_offsets: do not match the text");
     vpt::TrainFeatParams P{};
     P.cps = cps.p; P.ooff = d_ooff; P.n_sent = n; P.total_b = total_b;
     P.charw = t->prm.charw; P.charn = t->prm.charn; P.typew = t->prm.typew; P.typen = t->prm.typen; P.dictn = t->prm.dictn;
@@ -557,10 +573,8 @@ vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_b
     P.dict_off = t->d_dict_off.p;
     P.counts = counts.p;
     VPT_HIP(vpt::train_features(P, false, st));
-    VPT_HIP(vpt::train_scan_u32(counts.p, total_b, off.p, scratch.p, st));
     uint64_t add = 0;
-    VPT_HIP(hipMemcpyAsync(&add, off.p + total_b, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipStreamSynchronize(st));
+    VPT_TRY(scan_total(t, counts.p, total_b, off.p, &add));
     VPT_HIP(t->keys.grow(2 * (t->nnz_occ + add), 2 * t->nnz_occ, st));
     VPT_HIP(t->row_cnt.grow(t->nrows + total_b, t->nrows, st));
     VPT_HIP(t->labels.grow(t->nrows + total_b, t->nrows, st));
@@ -589,46 +603,33 @@ vpt_status surface_ids(vpt_trainer* t, std::vector<uint32_t>& ex_order, std::vec
     t->tag_surfaces.clear();
     ex_order.clear(); sid.clear();
     if (n_ex == 0) return VPT_OK;
-    uint64_t slots = 2;
-    while (slots < 2 * n_ex) slots <<= 1;
-    DBuf<uint64_t> table, pos, scratch, hist, hist_scan;
-    DBuf<uint32_t> rep, flag, maxlen, slot, mat, order, tmp, id_of, d_sid, d_order;
+    const uint64_t slots = table_slots(n_ex);
+    DBuf<uint64_t> table, pos;
+    DBuf<uint32_t> rep, flag, maxlen, slot, mat, id_of, d_sid;
     VPT_HIP(table.resize(slots)); VPT_HIP(rep.resize(n_ex)); VPT_HIP(flag.resize(n_ex)); VPT_HIP(maxlen.resize(1)); VPT_HIP(pos.resize(n_ex + 1));
-    VPT_HIP(slot.resize(n_ex)); VPT_HIP(d_sid.resize(n_ex)); VPT_HIP(d_order.resize(n_ex)); VPT_HIP(tmp.resize(n_ex));
-    VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>(n_ex, vpt::train_radix_scratch(n_ex))) + 1));
-    VPT_HIP(hist.resize(vpt::train_radix_scratch(n_ex))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(n_ex) + 1));
+    VPT_HIP(slot.resize(n_ex)); VPT_HIP(d_sid.resize(n_ex));
     VPT_HIP(hipMemsetAsync(table.p, 0, slots * 8, st));
     VPT_HIP(hipMemsetAsync(maxlen.p, 0, 4, st));
     VPT_HIP(vpt::train_surf_insert(t->d_tag_ex.p, n_ex, t->d_tag_cps.p, table.p, slots - 1, rep.p, flag.p, maxlen.p, st));
-    VPT_HIP(vpt::train_scan_u32(flag.p, n_ex, pos.p, scratch.p, st));
     uint64_t n_surf = 0;
     uint32_t ml = 0;
-    VPT_HIP(hipMemcpyAsync(&n_surf, pos.p + n_ex, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipMemcpyAsync(&ml, maxlen.p, 4, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipStreamSynchronize(st));
-    if (3 * uint64_t(ml) >= (1u << 20)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: a tagged token of 349525 chars or more");
-    VPT_HIP(mat.resize(n_surf * ml)); VPT_HIP(order.resize(n_surf)); VPT_HIP(id_of.resize(n_surf));
+    VPT_TRY(scan_total(t, flag.p, n_ex, pos.p, &n_surf));
+    VPT_HIP(hipMemcpy(&ml, maxlen.p, 4, hipMemcpyDeviceToHost));
+    if (3 * uint64_t(ml) >= (1u << 20)) return fail_arg("examples: a tagged token of 349525 chars or more");
+    VPT_HIP(mat.resize(n_surf * ml)); VPT_HIP(id_of.resize(n_surf));
     VPT_HIP(vpt::train_surf_matrix(t->d_tag_ex.p, n_ex, flag.p, pos.p, t->d_tag_cps.p, ml, mat.p, slot.p, st));
-    std::vector<uint32_t> ws;
-    for (uint32_t w = ml; w-- > 0;)
-        for (uint32_t sh = 0; sh < 24; sh += 8) ws.push_back((w << 8) | sh);   // the type byte above the code point is no part of the order
-    {
-        DBuf<uint32_t> stmp;
-        VPT_HIP(stmp.resize(n_surf));
-        VPT_HIP(vpt::train_radix_sort(mat.p, ml, ws.data(), uint32_t(ws.size()), n_surf, order.p, stmp.p, hist.p, hist_scan.p, scratch.p, st));
-        VPT_HIP(hipStreamSynchronize(st));
-    }
-    VPT_HIP(vpt::train_surf_ids(order.p, n_surf, id_of.p, rep.p, slot.p, n_ex, d_sid.p, st));
-    uint32_t passes = 1, ws2[4];
-    while (passes < 4 && n_surf > (uint64_t(1) << (8 * passes))) ++passes;
-    for (uint32_t k = 0; k < passes; ++k) ws2[k] = 8 * k;
-    VPT_HIP(vpt::train_radix_sort(d_sid.p, 1, ws2, passes, n_ex, d_order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
+    Sorter S, E;   // the distinct surfaces by their chars, the examples by surface id
+    for (uint32_t w = ml; w-- > 0;) S.bytes(w, 3);   // the type byte above the code point is no part of the order
+    VPT_TRY(S.run(t, mat.p, ml, n_surf));
+    VPT_HIP(vpt::train_ids(S.order.p, n_surf, id_of.p, rep.p, slot.p, n_ex, d_sid.p, st));
+    E.bytes(0, Sorter::bytes_below(n_surf));
+    VPT_TRY(E.run(t, d_sid.p, 1, n_ex));
     std::vector<uint32_t> h_mat(n_surf * ml), h_order(n_surf);
     ex_order.resize(n_ex); sid.resize(n_ex);
-    VPT_HIP(hipMemcpyAsync(ex_order.data(), d_order.p, n_ex * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(ex_order.data(), E.order.p, n_ex * 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipMemcpyAsync(sid.data(), d_sid.p, n_ex * 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipMemcpyAsync(h_mat.data(), mat.p, h_mat.size() * 4, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipMemcpyAsync(h_order.data(), order.p, n_surf * 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(h_order.data(), S.order.p, n_surf * 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
     t->tag_surfaces.resize(n_surf);
     for (uint64_t j = 0; j < n_surf; ++j) {
@@ -655,8 +656,7 @@ vpt_status build_tags(vpt_trainer* t) {
     t->tag_problems.clear();
     t->tags_trained = false;
     std::vector<uint32_t> ex_order, sid;
-    vpt_status vs = surface_ids(t, ex_order, sid);
-    if (vs != VPT_OK) return vs;
+    VPT_TRY(surface_ids(t, ex_order, sid));
     const double t_host = now_s();
     // a surface's examples: a run of ex_order
     std::vector<uint64_t> run(t->tag_surfaces.size() + 1, 0);
@@ -670,7 +670,7 @@ vpt_status build_tags(vpt_trainer* t) {
         if (some) all.emplace(kv.first, -1);
     }
     if (all.size() >= (size_t(1) << 24) - 1)
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^24 - 2 tag models (distinct token surfaces)");
+        return fail_arg("examples: at most 2^24 - 2 tag models (distinct token surfaces)");
     std::vector<uint32_t> row_ex, row_prob, row_y;
     std::vector<uint64_t> prob_row_ptr{0};
     for (auto& kv : all) {
@@ -723,43 +723,35 @@ vpt_status build_tags(vpt_trainer* t) {
     t->h_prob_row_ptr = prob_row_ptr;
     t->h_prob_occ0.assign(n_prob + 1, 0);
     t->h_key_ptr.assign(n_prob + 1, 0);
-    if (n_rows >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 rows over the tag problems");
+    if (n_rows >= (uint64_t(1) << 32)) return fail_arg("examples: at most 2^32 - 1 rows over the tag problems");
     if (n_prob) {
-        DBuf<uint32_t> d_row_ex, d_row_prob, nk, occ, occ_row, order, tmp, flag;
-        DBuf<uint64_t> d_prp, occ_off, scratch, hist, hist_scan, dpos, prob_occ0, key_ptr, dkeys;
+        DBuf<uint32_t> d_row_ex, d_row_prob, nk, occ, occ_row, flag;
+        DBuf<uint64_t> d_prp, occ_off, dpos, prob_occ0, key_ptr, dkeys;
         VPT_HIP(d_row_ex.resize(n_rows)); VPT_HIP(d_row_prob.resize(n_rows)); VPT_HIP(nk.resize(n_rows)); VPT_HIP(d_prp.resize(n_prob + 1));
         VPT_HIP(occ_off.resize(n_rows + 1)); VPT_HIP(t->b_y.resize(n_rows));
         VPT_HIP(hipMemcpyAsync(d_row_ex.p, row_ex.data(), n_rows * 4, hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemcpyAsync(d_row_prob.p, row_prob.data(), n_rows * 4, hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemcpyAsync(t->b_y.p, row_y.data(), n_rows * 4, hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemcpyAsync(d_prp.p, prob_row_ptr.data(), (n_prob + 1) * 8, hipMemcpyHostToDevice, st));
-        VPT_HIP(scratch.resize(vpt::train_scan_scratch(n_rows) + 1));
         VPT_HIP(vpt::train_tag_expand(d_row_ex.p, d_row_prob.p, n_rows, t->d_tag_ex.p, nullptr, nullptr, nk.p, nullptr, st));
-        VPT_HIP(vpt::train_scan_u32(nk.p, n_rows, occ_off.p, scratch.p, st));
         uint64_t n_occ = 0;
-        VPT_HIP(hipMemcpyAsync(&n_occ, occ_off.p + n_rows, 8, hipMemcpyDeviceToHost, st));
-        VPT_HIP(hipStreamSynchronize(st));
-        if (n_occ >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 nonzeros over the tag problems");
-        VPT_HIP(occ.resize(5 * n_occ)); VPT_HIP(occ_row.resize(n_occ)); VPT_HIP(order.resize(n_occ)); VPT_HIP(tmp.resize(n_occ)); VPT_HIP(flag.resize(n_occ));
-        VPT_HIP(dpos.resize(n_occ + 1));
-        VPT_HIP(scratch.resize(vpt::train_scan_scratch(std::max<uint64_t>(n_occ, vpt::train_radix_scratch(n_occ))) + 1));
-        VPT_HIP(hist.resize(vpt::train_radix_scratch(n_occ))); VPT_HIP(hist_scan.resize(vpt::train_radix_scratch(n_occ) + 1));
+        VPT_TRY(scan_total(t, nk.p, n_rows, occ_off.p, &n_occ));
+        if (n_occ >= (uint64_t(1) << 32)) return fail_arg("examples: at most 2^32 - 1 nonzeros over the tag problems");
+        VPT_HIP(occ.resize(5 * n_occ)); VPT_HIP(occ_row.resize(n_occ)); VPT_HIP(flag.resize(n_occ)); VPT_HIP(dpos.resize(n_occ + 1));
         VPT_HIP(vpt::train_tag_expand(d_row_ex.p, d_row_prob.p, n_rows, t->d_tag_ex.p, occ_off.p, t->d_tag_keys.p, occ.p, occ_row.p, st));
         // stably sorted by (problem, key): the key's four words least significant first, then the problem's bytes that can differ
-        uint32_t ws[20], np = 0;
-        for (uint32_t k = 0; k < 16; ++k) ws[np++] = ((k / 4) << 8) | (8 * (k % 4));
-        for (uint32_t k = 0; k < 4 && (k == 0 || n_prob > (uint64_t(1) << (8 * k))); ++k) ws[np++] = (4u << 8) | (8 * k);
-        VPT_HIP(vpt::train_radix_sort(occ.p, 5, ws, np, n_occ, order.p, tmp.p, hist.p, hist_scan.p, scratch.p, st));
-        VPT_HIP(vpt::train_tag_flags(occ.p, order.p, n_occ, flag.p, st));
-        VPT_HIP(vpt::train_scan_u32(flag.p, n_occ, dpos.p, scratch.p, st));
+        Sorter S;
+        for (uint32_t w = 0; w < 4; ++w) S.bytes(w, 4);
+        S.bytes(4, Sorter::bytes_below(n_prob));
+        VPT_TRY(S.run(t, occ.p, 5, n_occ));
+        VPT_HIP(vpt::train_tag_flags(occ.p, S.order.p, n_occ, flag.p, st));
         uint64_t n_dist = 0;
-        VPT_HIP(hipMemcpyAsync(&n_dist, dpos.p + n_occ, 8, hipMemcpyDeviceToHost, st));
-        VPT_HIP(hipStreamSynchronize(st));
+        VPT_TRY(scan_total(t, flag.p, n_occ, dpos.p, &n_dist));
         VPT_HIP(prob_occ0.resize(n_prob + 1)); VPT_HIP(key_ptr.resize(n_prob + 1)); VPT_HIP(dkeys.resize(2 * n_dist));
         VPT_HIP(t->b_cols.resize(n_occ)); VPT_HIP(t->b_crow.resize(n_occ)); VPT_HIP(t->b_rp.resize(n_rows + n_prob)); VPT_HIP(t->b_cp.resize(n_dist + n_prob));
         vpt::TagBuildParams B{};
         B.n_prob = n_prob; B.n_rows = n_rows; B.n_occ = n_occ; B.prob_row_ptr = d_prp.p; B.row_prob = d_row_prob.p; B.occ_off = occ_off.p; B.occ = occ.p;
-        B.occ_row = occ_row.p; B.order = order.p; B.flag = flag.p; B.dpos = dpos.p; B.prob_occ0 = prob_occ0.p; B.key_ptr = key_ptr.p;
+        B.occ_row = occ_row.p; B.order = S.order.p; B.flag = flag.p; B.dpos = dpos.p; B.prob_occ0 = prob_occ0.p; B.key_ptr = key_ptr.p;
         B.occ_col = t->b_cols.p; B.dkeys = dkeys.p; B.rp = t->b_rp.p; B.cp = t->b_cp.p; B.crow = t->b_crow.p;
         VPT_HIP(vpt::train_tag_assemble(B, st));
         std::vector<uint64_t> h_dkeys(2 * n_dist);
@@ -797,33 +789,25 @@ vpt_status fetch_rows(vpt_trainer* t, TagProblem& Pb) {
 vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double cost, int solver) {
     hipStream_t st = t->st;
     const double t_setup = now_s();
-    vpt_status fs = fetch_rows(t, Pb);
-    if (fs != VPT_OK) return fs;
+    VPT_TRY(fetch_rows(t, Pb));
     const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), nz = Pb.cols.size(), k = Pb.cands.size();
     std::vector<uint64_t> ptr(Pb.rp.begin(), Pb.rp.end());
     std::vector<uint32_t> rows(nz);
     for (uint64_t r = 0; r < l; ++r)
         for (uint32_t q = Pb.rp[r]; q < Pb.rp[r + 1]; ++q) rows[q] = uint32_t(r);
     const std::vector<uint16_t> ones(nz, 1);
-    DBuf<uint64_t> d_ptr, cptr;
-    DBuf<uint32_t> d_cols, d_rows, crow;
-    DBuf<uint16_t> d_vals, cval;
-    std::vector<std::unique_ptr<XtvLevel>> levels;
-    VPT_HIP(d_ptr.resize(l + 1)); VPT_HIP(d_cols.resize(nz)); VPT_HIP(d_rows.resize(nz)); VPT_HIP(d_vals.resize(nz));
-    VPT_HIP(hipMemcpy(d_ptr.p, ptr.data(), (l + 1) * 8, hipMemcpyHostToDevice));
+    Matrix M;
+    DBuf<uint32_t> d_rows;
+    VPT_HIP(M.csr_ptr.resize(l + 1)); VPT_HIP(M.cols.resize(nz)); VPT_HIP(d_rows.resize(nz)); VPT_HIP(M.vals.resize(nz));
+    VPT_HIP(hipMemcpy(M.csr_ptr.p, ptr.data(), (l + 1) * 8, hipMemcpyHostToDevice));
     if (nz) {
-        VPT_HIP(hipMemcpy(d_cols.p, Pb.cols.data(), nz * 4, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(M.cols.p, Pb.cols.data(), nz * 4, hipMemcpyHostToDevice));
         VPT_HIP(hipMemcpy(d_rows.p, rows.data(), nz * 4, hipMemcpyHostToDevice));
-        VPT_HIP(hipMemcpy(d_vals.p, ones.data(), nz * 2, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(M.vals.p, ones.data(), nz * 2, hipMemcpyHostToDevice));
     }
-    vpt_status s = csc_levels(st, d_cols.p, d_vals.p, d_rows.p, nz, nf, crow, cval, cptr, levels);
-    if (s != VPT_OK) return s;
+    VPT_TRY(csc_levels(t, M, d_rows.p, nz, nf));
     Tron T;
-    T.m = MatView{d_ptr.p, d_cols.p, d_vals.p, crow.p, cval.p, &levels, nf};
-    T.st = st; T.n = nf + 1; T.nr = l; T.solver = solver; T.c = cost;
-    for (DBuf<double>* b : {&T.w, &T.w_new, &T.g, &T.s, &T.r, &T.d, &T.Hd}) VPT_HIP(b->resize(T.n));
-    for (DBuf<double>* b : {&T.y, &T.z, &T.zt, &T.gz, &T.D, &T.loss}) VPT_HIP(b->resize(l));
-    VPT_HIP(T.part0.resize(vpt::train_dot_partials(std::max(T.n, l)))); VPT_HIP(T.part1.resize(vpt::train_dot_partials(std::max(T.n, l))));
+    VPT_TRY(T.init(M, st, l, solver, cost));
     std::vector<double> y(l);
     const uint64_t n_solve = k == 2 ? 1 : k;
     VPT_HIP(hipStreamSynchronize(st));
@@ -832,12 +816,8 @@ vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double co
     for (uint64_t c = 0; c < n_solve; ++c) {
         uint64_t pos = 0;
         for (uint64_t r = 0; r < l; ++r) { y[r] = Pb.y[r] == c ? 1.0 : -1.0; pos += Pb.y[r] == c; }
-        VPT_HIP(hipMemcpy(T.y.p, y.data(), l * 8, hipMemcpyHostToDevice));
-        const double tol = eps * double(std::max<uint64_t>(std::min(pos, l - pos), 1)) / double(l);
         const double t_run = now_s();
-        T.run(tol, &Pb.stats[c]);
-        VPT_HIP(T.err);
-        VPT_HIP(hipMemcpy(Pb.w.data() + c * T.n, T.w.p, T.n * 8, hipMemcpyDeviceToHost));
+        VPT_TRY(T.solve(y, pos, eps, &Pb.stats[c], Pb.w.data() + c * T.n));
         Pb.seconds_solve += now_s() - t_run;
     }
     if (k == 2) {
@@ -856,10 +836,10 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
     uint64_t n_w = 0, n_stats = 0;
     for (size_t i = 0; i < t->tag_problems.size(); ++i) {
         TagProblem& Pb = t->tag_problems[i];
-        const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), nz = Pb.nnz, k = Pb.cands.size();
+        const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), k = Pb.cands.size();
         Pb.w.assign(k * (nf + 1), 0.0);
         Pb.stats.assign(k, vpt_train_stats{});
-        Pb.path = (t->tag_path_mode == 0 && vpt::train_tag_fits(l, nf, nz)) ? 1 : 2;
+        Pb.path = (t->tag_path_mode == 0 && vpt::train_tag_fits(l, nf)) ? 1 : 2;
         Pb.seconds_setup = Pb.seconds_solve = 0;
         if (Pb.path != 1) continue;
         // the problem where build_tags left it on the device
@@ -901,8 +881,7 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
     const double t1 = now_s();
     for (TagProblem& Pb : t->tag_problems) {
         if (Pb.path != 2) continue;
-        vpt_status s = solve_tag_large(t, Pb, eps, cost, solver);
-        if (s != VPT_OK) return s;
+        VPT_TRY(solve_tag_large(t, Pb, eps, cost, solver));
         ++t->tag_summary.problems_large;
         t->tag_summary.seconds_large_solve += Pb.seconds_solve;
     }
@@ -916,7 +895,6 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
 
 // train_tag's back half (tag_trainer.rs:195-298) and the tag models of Model::to_vec
 void encode_tag_models(vpt_trainer* t, Enc& e) {
-    static const int sh[5] = {99, 78, 57, 36, 15};
     e.uvar(t->tag_models.size());
     for (const TagModelOut& M : t->tag_models) {
         std::map<std::pair<std::string, uint8_t>, std::vector<int32_t>> cw, tw;
@@ -935,15 +913,14 @@ void encode_tag_models(vpt_trainer* t, Enc& e) {
                     if (q == 0) continue;
                     if (!row) {
                         // the n-gram: the left context, the token, the right context
-                        const u128 v = Pb.keys[j];
-                        const uint32_t kind = uint32_t(v >> 120) & 3u, len = uint32_t(v >> 5) & 7u, rel = (uint32_t(v) & 31u) - 16u, left = len - rel;
+                        const vpt::TrainKey K = vpt::train_key(uint64_t(Pb.keys[j]), uint64_t(Pb.keys[j] >> 64));
+                        const uint32_t kind = K.kind, left = K.len - uint32_t(K.rel);
                         std::string ng;
-                        auto put = [&](uint32_t x) { if (kind == 0) put_utf8(ng, x); else ng += char(x); };
-                        for (uint32_t q2 = 0; q2 < left; ++q2) put(uint32_t(v >> sh[q2]) & 0x1FFFFFu);
-                        for (size_t q2 = 0; q2 < M.surf->cps.size(); ++q2) put(kind == 0 ? M.surf->cps[q2] : M.surf->types[q2]);
-                        for (uint32_t q2 = left; q2 < len; ++q2) put(uint32_t(v >> sh[q2]) & 0x1FFFFFu);
+                        for (uint32_t q2 = 0; q2 < left; ++q2) put_sym(ng, kind, K.c[q2]);
+                        for (size_t q2 = 0; q2 < M.surf->cps.size(); ++q2) put_sym(ng, kind, kind == 0 ? M.surf->cps[q2] : M.surf->types[q2]);
+                        for (uint32_t q2 = left; q2 < K.len; ++q2) put_sym(ng, kind, K.c[q2]);
                         auto& mp = kind == 0 ? cw : tw;
-                        row = &mp.emplace(std::make_pair(ng, uint8_t(rel)), std::vector<int32_t>(M.n_class, 0)).first->second;
+                        row = &mp.emplace(std::make_pair(ng, uint8_t(K.rel)), std::vector<int32_t>(M.n_class, 0)).first->second;
                     }
                     (*row)[Pb.class_offset + c] = q;
                 }
@@ -975,15 +952,13 @@ void encode_tag_models(vpt_trainer* t, Enc& e) {
 vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_boff, const uint64_t* d_ooff, size_t n, uint64_t total_b,
                              const uint8_t* d_labels, const uint32_t* d_n_tags, const uint64_t* d_tag_index, const uint64_t* d_span_off,
                              const uint8_t* d_tag_bytes, uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, hipStream_t caller) {
-    if (!(t->prm.flags & VPT_TRAIN_TAGS))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
-    if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: only VPT_FLAG_KYTEA_FULLWIDTH");
+    if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail_arg("flags: only VPT_FLAG_KYTEA_FULLWIDTH");
     if (n == 0) return VPT_OK;
     VPT_HIP(hipSetDevice(t->device));
     VPT_HIP(hipStreamSynchronize(caller));
     hipStream_t st = t->st;
     const uint64_t total_chars = total_b + n;
-    if (total_chars >= (uint64_t(1) << 32)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 chars in a batch");
+    if (total_chars >= (uint64_t(1) << 32)) return fail_arg("examples: at most 2^32 - 1 chars in a batch");
     DBuf<uint32_t> cps, status, counts, is_ex;
     VPT_HIP(cps.resize(total_chars)); VPT_HIP(status.resize(2));
     VPT_HIP(hipMemsetAsync(status.p, 0, 8, st));
@@ -992,13 +967,13 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
     uint32_t bad[2] = {0, 0};
     VPT_HIP(hipMemcpyAsync(bad, status.p, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad[0]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "out_offsets: do not match the text");
+    if (bad[0]) return fail_arg("out_offsets: do not match the text");
     // the tags' CSR is checked on the device before anything follows one of its offsets
     VPT_HIP(vpt::train_tag_validate(d_n_tags, d_ooff, n, total_chars, d_tag_index, d_span_off, n_spans, n_tag_bytes, status.p + 1, st));
     VPT_HIP(hipMemcpyAsync(bad + 1, status.p + 1, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad[1] & 1u) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tag_index: must not decrease, pass n_spans or give a char more tags than n_tags");
-    if (bad[1] & 2u) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "span_offsets: must not decrease or pass tag_bytes");
+    if (bad[1] & 1u) return fail_arg("tag_index: must not decrease, pass n_spans or give a char more tags than n_tags");
+    if (bad[1] & 2u) return fail_arg("span_offsets: must not decrease or pass tag_bytes");
     std::vector<uint64_t> ooff(n + 1), tindex(total_chars + 1), soff(n_spans + 1);
     std::vector<uint32_t> ntags(n);
     std::vector<uint8_t> tbytes(n_tag_bytes);
@@ -1017,31 +992,26 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
                 const uint8_t* b = tbytes.data() + soff[k];
                 const size_t len = size_t(soff[k + 1] - soff[k]);
                 if (std::find(b, b + len, uint8_t(0)) != b + len)
-                    return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: must not contain NULL (sentence " + std::to_string(sent) + ")");
-                if (!decode_utf8(b, len, tmp))
-                    return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: invalid UTF-8 (sentence " + std::to_string(sent) + ")");
+                    return fail_arg("tags: must not contain NULL (sentence " + std::to_string(sent) + ")");
+                if (!vpt::decode_utf8(b, len, tmp))
+                    return fail_arg("tags: invalid UTF-8 (sentence " + std::to_string(sent) + ")");
             }
         }
     }
     // the boundary examples, exactly as the untagged call adds them
-    vpt_status s = add_device(t, d_utf8, d_boff, d_ooff, n, total_b, d_labels, flags, st);
-    if (s != VPT_OK) return s;
+    VPT_TRY(add_device(t, d_utf8, d_boff, d_ooff, n, total_b, d_labels, flags, st));
     // the tag examples: count, place, write
-    DBuf<uint64_t> ex_off, key_off, scratch;
+    DBuf<uint64_t> ex_off, key_off;
     VPT_HIP(counts.resize(total_chars)); VPT_HIP(is_ex.resize(total_chars)); VPT_HIP(ex_off.resize(total_chars + 1)); VPT_HIP(key_off.resize(total_chars + 1));
-    VPT_HIP(scratch.resize(vpt::train_scan_scratch(total_chars) + 1));
     vpt::TagFeatParams P{};
     P.cps = cps.p; P.ooff = d_ooff; P.labels = d_labels; P.n_tags = d_n_tags; P.n_sent = n; P.total_chars = total_chars;
     P.charn = t->prm.charn; P.typen = t->prm.typen; P.is_ex = is_ex.p; P.counts = counts.p;
     VPT_HIP(vpt::train_tag_features(P, false, st));
-    VPT_HIP(vpt::train_scan_u32(is_ex.p, total_chars, ex_off.p, scratch.p, st));
-    VPT_HIP(vpt::train_scan_u32(counts.p, total_chars, key_off.p, scratch.p, st));
     uint64_t n_ex = 0, n_keys = 0;
-    VPT_HIP(hipMemcpyAsync(&n_ex, ex_off.p + total_chars, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipMemcpyAsync(&n_keys, key_off.p + total_chars, 8, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipStreamSynchronize(st));
+    VPT_TRY(scan_total(t, is_ex.p, total_chars, ex_off.p, &n_ex));
+    VPT_TRY(scan_total(t, counts.p, total_chars, key_off.p, &n_keys));
     if (t->n_tag_cps + total_chars >= (uint64_t(1) << 32) || t->n_tag_keys + n_keys >= (uint64_t(1) << 32) || t->n_tag_ex + n_ex >= (uint64_t(1) << 32))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: at most 2^32 - 1 chars, tagged tokens and tag feature occurrences");
+        return fail_arg("examples: at most 2^32 - 1 chars, tagged tokens and tag feature occurrences");
     // the examples stay on the device: the batch's chars, the records and the keys are appended to the trainer's arrays
     DBuf<uint32_t> recs;
     VPT_HIP(recs.resize(4 * n_ex));
@@ -1077,6 +1047,44 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
     return VPT_OK;
 }
 
+// A host batch on the device, on the trainer's stream: the boundaries counted, the labels checked, the text padded and the offsets
+// rebased to its first byte.  The host copies outlive the asynchronous copies (the add that follows ends with a synchronisation).
+struct StagedBatch {
+    std::vector<uint64_t> boff, ooff;
+    uint64_t total_b = 0;
+    DBuf<uint8_t> d_text, d_labels;
+    DBuf<uint64_t> d_boff, d_ooff;
+};
+vpt_status stage_batch(vpt_trainer* t, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n, const uint8_t* labels, StagedBatch& B) {
+    B.ooff.resize(n + 1);
+    VPT_TRY(vpt_count_boundaries(utf8, byte_offsets, n, B.ooff.data()));
+    const uint64_t total_b = B.total_b = B.ooff[n];
+    if (total_b && !labels) return fail_arg("NULL argument");
+    for (uint64_t b = 0; b < total_b; ++b)
+        if (labels[b] > 2) return fail_arg("labels: must be 0, 1 or 2");
+    VPT_HIP(hipSetDevice(t->device));
+    const uint64_t b0 = byte_offsets[0], nbytes = byte_offsets[n] - b0;
+    B.boff.assign(byte_offsets, byte_offsets + n + 1);
+    for (auto& x : B.boff) x -= b0;
+    VPT_HIP(B.d_text.resize(nbytes + 64)); VPT_HIP(B.d_labels.resize(total_b)); VPT_HIP(B.d_boff.resize(n + 1)); VPT_HIP(B.d_ooff.resize(n + 1));
+    VPT_HIP(hipMemsetAsync(B.d_text.p, 0, nbytes + 64, t->st));
+    VPT_HIP(hipMemcpyAsync(B.d_text.p, utf8 + b0, nbytes, hipMemcpyHostToDevice, t->st));
+    if (total_b) VPT_HIP(hipMemcpyAsync(B.d_labels.p, labels, total_b, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(B.d_boff.p, B.boff.data(), B.boff.size() * 8, hipMemcpyHostToDevice, t->st));
+    VPT_HIP(hipMemcpyAsync(B.d_ooff.p, B.ooff.data(), B.ooff.size() * 8, hipMemcpyHostToDevice, t->st));
+    return VPT_OK;
+}
+
+// the last trained model into the caller's buffer (NULL: its size alone)
+vpt_status copy_model(const vpt_trainer* t, uint8_t* model_out, size_t capacity, size_t* needed) {
+    *needed = t->model.size();
+    if (model_out) {
+        if (capacity < t->model.size()) return fail_arg("capacity: smaller than the model");
+        std::memcpy(model_out, t->model.data(), t->model.size());
+    }
+    return VPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1084,16 +1092,16 @@ extern "C" {
 vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_utf8, const uint64_t* dict_offsets, size_t n_dict_words,
                               int device_id, void** out) {
     const vpt_train_params* params = reinterpret_cast<const vpt_train_params*>(params_words);
-    if (!params || !out || (n_dict_words && (!dict_utf8 || !dict_offsets))) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!params || !out || (n_dict_words && (!dict_utf8 || !dict_offsets))) return fail_arg("NULL argument");
     *out = nullptr;
     const vpt_train_params& p = *params;
-    if (p.charn < 1 || p.charn > 5) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "charn: must be between 1 and 5");
-    if (p.typen < 1 || p.typen > 5) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "typen: must be between 1 and 5");
-    if (p.charw > 16) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "charw: must be at most 16");
-    if (p.typew > 16) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "typew: must be at most 16");
-    if (p.typew > p.charw) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "typew: must not exceed charw (type weights use the char window)");
-    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS)) != 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "flags: must be 0 or VPT_TRAIN_TAGS");
-    if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dictn: must be at least 1 with a dictionary");
+    if (p.charn < 1 || p.charn > 5) return fail_arg("charn: must be between 1 and 5");
+    if (p.typen < 1 || p.typen > 5) return fail_arg("typen: must be between 1 and 5");
+    if (p.charw > 16) return fail_arg("charw: must be at most 16");
+    if (p.typew > 16) return fail_arg("typew: must be at most 16");
+    if (p.typew > p.charw) return fail_arg("typew: must not exceed charw (type weights use the char window)");
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS)) != 0) return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS");
+    if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail_arg("dictn: must be at least 1 with a dictionary");
     std::unique_ptr<vpt_trainer> t(new (std::nothrow) vpt_trainer());
     if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
     t->prm = p;
@@ -1101,13 +1109,13 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     std::vector<uint64_t> woff{0};
     std::set<std::string> seen;
     for (size_t i = 0; i < n_dict_words; ++i) {
-        if (dict_offsets[i + 1] < dict_offsets[i]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dict_offsets: must be non-decreasing");
+        if (dict_offsets[i + 1] < dict_offsets[i]) return fail_arg("dict_offsets: must be non-decreasing");
         const uint8_t* s = dict_utf8 + dict_offsets[i];
         const size_t len = size_t(dict_offsets[i + 1] - dict_offsets[i]);
-        if (len == 0) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dict_words: must not contain an empty word (word " + std::to_string(i) + ")");
-        if (!decode_utf8(s, len, cps)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dict_words: invalid UTF-8 (word " + std::to_string(i) + ")");
+        if (len == 0) return fail_arg("dict_words: must not contain an empty word (word " + std::to_string(i) + ")");
+        if (!vpt::decode_utf8(s, len, cps)) return fail_arg("dict_words: invalid UTF-8 (word " + std::to_string(i) + ")");
         std::string w(reinterpret_cast<const char*>(s), len);
-        if (!seen.insert(w).second) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "dict_words: duplicate word (word " + std::to_string(i) + ")");
+        if (!seen.insert(w).second) return fail_arg("dict_words: duplicate word (word " + std::to_string(i) + ")");
         t->dict_words.push_back(w);
         t->dict_len.push_back(uint32_t(cps.size()));
         t->dict_maxlen = std::max(t->dict_maxlen, uint32_t(cps.size()));
@@ -1116,7 +1124,7 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(VPT_RUNTIME_ERROR, "no HIP device available (this library has no CPU fallback)");
-    if (device_id < 0 || device_id >= n_dev) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "device_id: no such device");
+    if (device_id < 0 || device_id >= n_dev) return fail_arg("device_id: no such device");
     t->device = device_id;
     VPT_HIP(hipSetDevice(device_id));
     VPT_HIP(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
@@ -1129,13 +1137,12 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     VPT_HIP(t->d_cinfo.resize(65536));
     VPT_HIP(hipMemcpy(t->d_cinfo.p, cinfo.data(), 65536 * 4, hipMemcpyHostToDevice));
     if (n_dict_words) {
-        uint64_t slots = 2;
-        while (slots < 2 * n_dict_words) slots <<= 1;
+        const uint64_t slots = table_slots(n_dict_words);
         std::vector<uint32_t> tab(slots, 0);
-        for (size_t i = 0; i < n_dict_words; ++i) {
-            uint64_t h = 0xCBF29CE484222325ull;
-            for (uint64_t k = woff[i]; k < woff[i + 1]; ++k) h = (h ^ all_cps[k]) * 0x100000001B3ull;
-            uint64_t s = mix64h(h ^ (woff[i + 1] - woff[i])) & (slots - 1);
+        for (size_t i = 0; i < n_dict_words; ++i) {   // dict_find's probe (kernels_train.hip), through the same hash
+            uint64_t h = vpt::kCpsHashSeed;
+            for (uint64_t k = woff[i]; k < woff[i + 1]; ++k) h = vpt::cps_hash_step(h, all_cps[k]);
+            uint64_t s = vpt::cps_hash_finish(h, woff[i + 1] - woff[i]) & (slots - 1);
             while (tab[s]) s = (s + 1) & (slots - 1);
             tab[s] = uint32_t(i + 1);
         }
@@ -1160,149 +1167,112 @@ vpt_status vpt_trainer_add_batch_device(void* th, const uint8_t* d_utf8, const u
                                         size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels, unsigned flags, void* hip_stream) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
     if (!t || (n_sentences && (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels))))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+        return fail_arg("NULL argument");
     return add_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, flags, static_cast<hipStream_t>(hip_stream));
 }
 
 vpt_status vpt_trainer_add_batch(void* th, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint8_t* labels,
                                  unsigned flags) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !byte_offsets || (n_sentences && !utf8)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t || !byte_offsets || (n_sentences && !utf8)) return fail_arg("NULL argument");
     if (n_sentences == 0) return VPT_OK;
-    std::vector<uint64_t> ooff(n_sentences + 1);
-    vpt_status s = vpt_count_boundaries(utf8, byte_offsets, n_sentences, ooff.data());
-    if (s != VPT_OK) return s;
-    const uint64_t total_b = ooff[n_sentences];
-    if (total_b && !labels) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    for (uint64_t b = 0; b < total_b; ++b)
-        if (labels[b] > 2) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "labels: must be 0, 1 or 2");
-    VPT_HIP(hipSetDevice(t->device));
-    const uint64_t b0 = byte_offsets[0], nbytes = byte_offsets[n_sentences] - b0;
-    std::vector<uint64_t> boff(byte_offsets, byte_offsets + n_sentences + 1);
-    for (auto& x : boff) x -= b0;
-    DBuf<uint8_t> d_text, d_labels;
-    DBuf<uint64_t> d_boff, d_ooff;
-    VPT_HIP(d_text.resize(nbytes + 64)); VPT_HIP(d_labels.resize(total_b)); VPT_HIP(d_boff.resize(n_sentences + 1)); VPT_HIP(d_ooff.resize(n_sentences + 1));
-    VPT_HIP(hipMemsetAsync(d_text.p, 0, nbytes + 64, t->st));
-    VPT_HIP(hipMemcpyAsync(d_text.p, utf8 + b0, nbytes, hipMemcpyHostToDevice, t->st));
-    if (total_b) VPT_HIP(hipMemcpyAsync(d_labels.p, labels, total_b, hipMemcpyHostToDevice, t->st));
-    VPT_HIP(hipMemcpyAsync(d_boff.p, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, t->st));
-    VPT_HIP(hipMemcpyAsync(d_ooff.p, ooff.data(), ooff.size() * 8, hipMemcpyHostToDevice, t->st));
-    return add_device(t, d_text.p, d_boff.p, d_ooff.p, n_sentences, total_b, d_labels.p, flags, t->st);
+    StagedBatch B;
+    VPT_TRY(stage_batch(t, utf8, byte_offsets, n_sentences, labels, B));
+    return add_device(t, B.d_text.p, B.d_boff.p, B.d_ooff.p, n_sentences, B.total_b, B.d_labels.p, flags, t->st);
 }
 
 vpt_status vpt_trainer_n_features(void* th, size_t* out) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t || !out) return fail_arg("NULL argument");
     VPT_HIP(hipSetDevice(t->device));
-    vpt_status s = build(t);
-    if (s != VPT_OK) return s;
-    *out = size_t(t->nd);
+    VPT_TRY(build(t));
+    *out = size_t(t->m.nd);
     return VPT_OK;
 }
 
 vpt_status vpt_trainer_csr(void* th, uint64_t* row_ptr_out, uint32_t* cols_out, void* counts_out, size_t capacity, size_t* n_rows,
                            size_t* nnz) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !n_rows || !nnz) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t || !n_rows || !nnz) return fail_arg("NULL argument");
     VPT_HIP(hipSetDevice(t->device));
-    vpt_status s = build(t);
-    if (s != VPT_OK) return s;
+    VPT_TRY(build(t));
+    const Matrix& M = t->m;
     *n_rows = size_t(t->nrows);
-    *nnz = size_t(t->nnz);
+    *nnz = size_t(M.nnz);
     if (!row_ptr_out && !cols_out && !counts_out) return VPT_OK;
-    if (!row_ptr_out || !cols_out || !counts_out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (capacity < t->nnz) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than the nonzeros");
-    VPT_HIP(hipMemcpy(row_ptr_out, t->csr_ptr.p, (t->nrows + 1) * 8, hipMemcpyDeviceToHost));
-    if (t->nnz) {
-        VPT_HIP(hipMemcpy(cols_out, t->cols.p, t->nnz * 4, hipMemcpyDeviceToHost));
-        VPT_HIP(hipMemcpy(counts_out, t->vals.p, t->nnz * 2, hipMemcpyDeviceToHost));
+    if (!row_ptr_out || !cols_out || !counts_out) return fail_arg("NULL argument");
+    if (capacity < M.nnz) return fail_arg("capacity: smaller than the nonzeros");
+    VPT_HIP(hipMemcpy(row_ptr_out, M.csr_ptr.p, (t->nrows + 1) * 8, hipMemcpyDeviceToHost));
+    if (M.nnz) {
+        VPT_HIP(hipMemcpy(cols_out, M.cols.p, M.nnz * 4, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(counts_out, M.vals.p, M.nnz * 2, hipMemcpyDeviceToHost));
     }
     return VPT_OK;
 }
 
 vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t* model_out, size_t capacity, size_t* needed) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !needed || !eps_cost) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    if (!t || !needed || !eps_cost) return fail_arg("NULL argument");
     double ec[2];
     std::memcpy(ec, eps_cost, sizeof ec);
     const double eps = ec[0], cost = ec[1];
-    if (solver != 0 && solver != 2) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "solver: only 0 and 2 are implemented");
-    if (!(eps > 0) || !(cost > 0)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "eps and cost: must be positive");
+    if (solver != 0 && solver != 2) return fail_arg("solver: only 0 and 2 are implemented");
+    if (!(eps > 0) || !(cost > 0)) return fail_arg("eps and cost: must be positive");
     VPT_HIP(hipSetDevice(t->device));
     t->trained = false;
-    vpt_status s = build(t);
-    if (s != VPT_OK) return s;
-    const uint64_t nr = t->nrows;
+    VPT_TRY(build(t));
+    const uint64_t nr = t->nrows, nd = t->m.nd;
     std::vector<uint8_t> lab(nr);
     if (nr) VPT_HIP(hipMemcpy(lab.data(), t->labels.p, nr, hipMemcpyDeviceToHost));
     std::vector<double> y(nr);
     uint64_t pos = 0;
     for (uint64_t i = 0; i < nr; ++i) {
-        if (lab[i] > 2) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "labels: must be 0, 1 or 2");
+        if (lab[i] > 2) return fail_arg("labels: must be 0, 1 or 2");
         y[i] = lab[i] == VPT_WORD_BOUNDARY ? 1.0 : -1.0;
         pos += lab[i] == VPT_WORD_BOUNDARY;
     }
     if (pos == 0 || pos == nr)
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "examples: need both WordBoundary and other boundaries");
+        return fail_arg("examples: need both WordBoundary and other boundaries");
     Tron T;
-    T.m = MatView{t->csr_ptr.p, t->cols.p, t->vals.p, t->crow.p, t->cval.p, &t->levels, t->nd};
-    T.st = t->st; T.n = t->nd + 1; T.nr = nr; T.solver = solver; T.c = cost;
-    for (DBuf<double>* b : {&T.w, &T.w_new, &T.g, &T.s, &T.r, &T.d, &T.Hd}) VPT_HIP(b->resize(T.n));
-    for (DBuf<double>* b : {&T.y, &T.z, &T.zt, &T.gz, &T.D, &T.loss}) VPT_HIP(b->resize(nr));
-    VPT_HIP(T.part0.resize(vpt::train_dot_partials(std::max(T.n, nr)))); VPT_HIP(T.part1.resize(vpt::train_dot_partials(std::max(T.n, nr))));
-    VPT_HIP(hipMemcpy(T.y.p, y.data(), nr * 8, hipMemcpyHostToDevice));
-    // liblinear's primal tolerance (linear.cpp train_one): eps * max(min(pos, neg), 1) / l
-    const double tol = eps * double(std::max<uint64_t>(std::min(pos, nr - pos), 1)) / double(nr);
-    T.run(tol, &t->stats);
-    VPT_HIP(T.err);
+    VPT_TRY(T.init(t->m, t->st, nr, solver, cost));
     t->w.resize(T.n);
-    VPT_HIP(hipMemcpy(t->w.data(), T.w.p, T.n * 8, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> keys(2 * t->nd);
-    if (t->nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
+    VPT_TRY(T.solve(y, pos, eps, &t->stats, t->w.data()));
+    std::vector<uint64_t> keys(2 * nd);
+    if (nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
     if (t->prm.flags & VPT_TRAIN_TAGS) {
-        if ((s = build_tags(t)) != VPT_OK) return s;
-        if ((s = solve_tags(t, eps, cost, solver)) != VPT_OK) return s;
+        VPT_TRY(build_tags(t));
+        VPT_TRY(solve_tags(t, eps, cost, solver));
     }
-    if ((s = make_model(t, keys)) != VPT_OK) return s;
+    VPT_TRY(make_model(t, keys));
     t->trained = true;
-    *needed = t->model.size();
-    if (model_out) {
-        if (capacity < t->model.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than the model");
-        std::memcpy(model_out, t->model.data(), t->model.size());
-    }
-    return VPT_OK;
+    return copy_model(t, model_out, capacity, needed);
 }
 
 vpt_status vpt_trainer_model(const void* th, uint8_t* model_out, size_t capacity, size_t* needed) {
     const vpt_trainer* t = static_cast<const vpt_trainer*>(th);
-    if (!t || !needed) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!t->trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained model");
-    *needed = t->model.size();
-    if (model_out) {
-        if (capacity < t->model.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than the model");
-        std::memcpy(model_out, t->model.data(), t->model.size());
-    }
-    return VPT_OK;
+    if (!t || !needed) return fail_arg("NULL argument");
+    if (!t->trained) return fail_arg("the trainer has no trained model");
+    return copy_model(t, model_out, capacity, needed);
 }
 
 vpt_status vpt_trainer_weights(void* th, void* weights_out, void* bias_out, uint64_t* keys_out, size_t capacity, size_t* n_features) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !n_features) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!t->trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained model");
-    *n_features = size_t(t->nd);
+    if (!t || !n_features) return fail_arg("NULL argument");
+    if (!t->trained) return fail_arg("the trainer has no trained model");
+    const uint64_t nd = t->m.nd;
+    *n_features = size_t(nd);
     if (!weights_out && !bias_out && !keys_out) return VPT_OK;
-    if (capacity < t->nd) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than the features");
-    if (weights_out) std::memcpy(weights_out, t->w.data(), t->nd * 8);
-    if (bias_out) std::memcpy(bias_out, &t->w[t->nd], 8);
-    if (keys_out && t->nd) VPT_HIP(hipMemcpy(keys_out, t->sorted_keys.p, t->nd * 16, hipMemcpyDeviceToHost));
+    if (capacity < nd) return fail_arg("capacity: smaller than the features");
+    if (weights_out) std::memcpy(weights_out, t->w.data(), nd * 8);
+    if (bias_out) std::memcpy(bias_out, &t->w[nd], 8);
+    if (keys_out && nd) VPT_HIP(hipMemcpy(keys_out, t->sorted_keys.p, nd * 16, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 
 vpt_status vpt_trainer_last_stats(const void* th, void* out) {
     const vpt_trainer* t = static_cast<const vpt_trainer*>(th);
-    if (!t || !out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!t->trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained model");
+    if (!t || !out) return fail_arg("NULL argument");
+    if (!t->trained) return fail_arg("the trainer has no trained model");
     std::memcpy(out, &t->stats, sizeof t->stats);
     return VPT_OK;
 }
@@ -1311,10 +1281,9 @@ vpt_status vpt_trainer_add_tagged_batch_device(void* th, const uint8_t* d_utf8, 
                                                size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels, const uint32_t* d_n_tags,
                                                const uint64_t* d_tag_index, const uint64_t* d_span_offsets, const uint8_t* d_tag_bytes,
                                                uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, void* hip_stream) {
-    vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || (n_sentences && (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels) || !d_n_tags || !d_tag_index ||
-                               !d_span_offsets || (n_tag_bytes && !d_tag_bytes))))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+    vpt_trainer* t = tag_trainer(th, !n_sentences || (d_utf8 && d_byte_offsets && d_out_offsets && (!total_boundaries || d_labels) && d_n_tags &&
+                                                      d_tag_index && d_span_offsets && (!n_tag_bytes || d_tag_bytes)));
+    if (!t) return VPT_INVALID_ARGUMENT;
     return add_tagged_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, d_n_tags, d_tag_index, d_span_offsets,
                              d_tag_bytes, n_spans, n_tag_bytes, flags, static_cast<hipStream_t>(hip_stream));
 }
@@ -1322,66 +1291,46 @@ vpt_status vpt_trainer_add_tagged_batch_device(void* th, const uint8_t* d_utf8, 
 vpt_status vpt_trainer_add_tagged_batch(void* th, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint8_t* labels,
                                         const uint32_t* n_tags, const uint64_t* tag_index, const uint64_t* span_offsets, const uint8_t* tag_bytes,
                                         uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags) {
-    vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !byte_offsets || (n_sentences && (!utf8 || !n_tags || !tag_index || !span_offsets || (n_tag_bytes && !tag_bytes))))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!(t->prm.flags & VPT_TRAIN_TAGS))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    vpt_trainer* t = tag_trainer(th, byte_offsets && (!n_sentences || (utf8 && n_tags && tag_index && span_offsets && (!n_tag_bytes || tag_bytes))));
+    if (!t) return VPT_INVALID_ARGUMENT;
     if (n_sentences == 0) return VPT_OK;
-    std::vector<uint64_t> ooff(n_sentences + 1);
-    vpt_status s = vpt_count_boundaries(utf8, byte_offsets, n_sentences, ooff.data());
-    if (s != VPT_OK) return s;
-    const uint64_t total_b = ooff[n_sentences], total_chars = total_b + n_sentences;
-    if (total_b && !labels) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    for (uint64_t b = 0; b < total_b; ++b)
-        if (labels[b] > 2) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "labels: must be 0, 1 or 2");
-    VPT_HIP(hipSetDevice(t->device));
-    const uint64_t b0 = byte_offsets[0], nbytes = byte_offsets[n_sentences] - b0;
-    std::vector<uint64_t> boff(byte_offsets, byte_offsets + n_sentences + 1);
-    for (auto& x : boff) x -= b0;
-    DBuf<uint8_t> d_text, d_labels, d_tb;
-    DBuf<uint64_t> d_boff, d_ooff, d_ti, d_so;
+    StagedBatch B;
+    VPT_TRY(stage_batch(t, utf8, byte_offsets, n_sentences, labels, B));
+    const uint64_t total_chars = B.total_b + n_sentences;
+    DBuf<uint8_t> d_tb;
+    DBuf<uint64_t> d_ti, d_so;
     DBuf<uint32_t> d_nt;
-    VPT_HIP(d_text.resize(nbytes + 64)); VPT_HIP(d_labels.resize(total_b)); VPT_HIP(d_boff.resize(n_sentences + 1)); VPT_HIP(d_ooff.resize(n_sentences + 1));
     VPT_HIP(d_nt.resize(n_sentences)); VPT_HIP(d_ti.resize(total_chars + 1)); VPT_HIP(d_so.resize(n_spans + 1)); VPT_HIP(d_tb.resize(n_tag_bytes));
-    VPT_HIP(hipMemsetAsync(d_text.p, 0, nbytes + 64, t->st));
-    VPT_HIP(hipMemcpyAsync(d_text.p, utf8 + b0, nbytes, hipMemcpyHostToDevice, t->st));
-    if (total_b) VPT_HIP(hipMemcpyAsync(d_labels.p, labels, total_b, hipMemcpyHostToDevice, t->st));
-    VPT_HIP(hipMemcpyAsync(d_boff.p, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, t->st));
-    VPT_HIP(hipMemcpyAsync(d_ooff.p, ooff.data(), ooff.size() * 8, hipMemcpyHostToDevice, t->st));
     VPT_HIP(hipMemcpyAsync(d_nt.p, n_tags, n_sentences * 4, hipMemcpyHostToDevice, t->st));
     VPT_HIP(hipMemcpyAsync(d_ti.p, tag_index, (total_chars + 1) * 8, hipMemcpyHostToDevice, t->st));
     VPT_HIP(hipMemcpyAsync(d_so.p, span_offsets, (n_spans + 1) * 8, hipMemcpyHostToDevice, t->st));
     if (n_tag_bytes) VPT_HIP(hipMemcpyAsync(d_tb.p, tag_bytes, n_tag_bytes, hipMemcpyHostToDevice, t->st));
-    return add_tagged_device(t, d_text.p, d_boff.p, d_ooff.p, n_sentences, total_b, d_labels.p, d_nt.p, d_ti.p, d_so.p, d_tb.p, n_spans, n_tag_bytes, flags,
-                             t->st);
+    return add_tagged_device(t, B.d_text.p, B.d_boff.p, B.d_ooff.p, n_sentences, B.total_b, B.d_labels.p, d_nt.p, d_ti.p, d_so.p, d_tb.p, n_spans,
+                             n_tag_bytes, flags, t->st);
 }
 
 vpt_status vpt_trainer_set_tag_dictionary(void* th, const uint8_t* surfaces_utf8, const uint64_t* surface_offsets, size_t n_surfaces,
                                           const uint32_t* n_tags, const uint64_t* span_offsets, const uint8_t* tag_bytes) {
-    vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || (n_surfaces && (!surfaces_utf8 || !surface_offsets || !n_tags || !span_offsets)))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!(t->prm.flags & VPT_TRAIN_TAGS))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
+    vpt_trainer* t = tag_trainer(th, !n_surfaces || (surfaces_utf8 && surface_offsets && n_tags && span_offsets));
+    if (!t) return VPT_INVALID_ARGUMENT;
     std::map<std::string, std::vector<int32_t>> defs;
     std::vector<uint32_t> cps;
     uint64_t k = 0;
     for (size_t i = 0; i < n_surfaces; ++i) {
         const std::string at = " (surface " + std::to_string(i) + ")";
-        if (surface_offsets[i + 1] <= surface_offsets[i]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "surface_offsets: must increase" + at);
+        if (surface_offsets[i + 1] <= surface_offsets[i]) return fail_arg("surface_offsets: must increase" + at);
         const uint8_t* sp = surfaces_utf8 + surface_offsets[i];
         const size_t len = size_t(surface_offsets[i + 1] - surface_offsets[i]);
-        if (!decode_utf8(sp, len, cps)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "surfaces: invalid UTF-8" + at);
+        if (!vpt::decode_utf8(sp, len, cps)) return fail_arg("surfaces: invalid UTF-8" + at);
         std::vector<int32_t> tags;
         for (uint32_t j = 0; j < n_tags[i]; ++j, ++k) {
-            if (span_offsets[k + 1] < span_offsets[k]) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "span_offsets: must not decrease" + at);
+            if (span_offsets[k + 1] < span_offsets[k]) return fail_arg("span_offsets: must not decrease" + at);
             const size_t tl = size_t(span_offsets[k + 1] - span_offsets[k]);
             if (tl == 0) { tags.push_back(-1); continue; }
-            if (!tag_bytes) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
+            if (!tag_bytes) return fail_arg("NULL argument");
             const uint8_t* b = tag_bytes + span_offsets[k];
-            if (std::find(b, b + tl, uint8_t(0)) != b + tl) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: must not contain NULL" + at);
-            if (!decode_utf8(b, tl, cps)) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: invalid UTF-8" + at);
+            if (std::find(b, b + tl, uint8_t(0)) != b + tl) return fail_arg("tags: must not contain NULL" + at);
+            if (!vpt::decode_utf8(b, tl, cps)) return fail_arg("tags: invalid UTF-8" + at);
             tags.push_back(t->intern_tag(std::string(reinterpret_cast<const char*>(b), tl)));
         }
         defs.emplace(std::string(reinterpret_cast<const char*>(sp), len), std::move(tags));   // the first occurrence wins (trainer.rs:231-238)
@@ -1395,19 +1344,16 @@ vpt_status vpt_trainer_set_tag_dictionary(void* th, const uint8_t* surfaces_utf8
 
 vpt_status vpt_trainer_set_tag_path(void* th, int mode) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (mode != 0 && mode != 1) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "mode: 0 (by size) or 1 (the global-memory solver)");
+    if (!t) return fail_arg("NULL argument");
+    if (mode != 0 && mode != 1) return fail_arg("mode: 0 (by size) or 1 (the global-memory solver)");
     t->tag_path_mode = mode;
     return VPT_OK;
 }
 
 vpt_status vpt_trainer_n_tag_problems(void* th, size_t* n_problems, size_t* n_models) {
-    vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !n_problems) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!(t->prm.flags & VPT_TRAIN_TAGS))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
-    vpt_status s = build_tags(t);
-    if (s != VPT_OK) return s;
+    vpt_trainer* t = tag_trainer(th, n_problems != nullptr);
+    if (!t) return VPT_INVALID_ARGUMENT;
+    VPT_TRY(build_tags(t));
     *n_problems = t->tag_problems.size();
     if (n_models) *n_models = t->tag_models.size();
     return VPT_OK;
@@ -1415,17 +1361,14 @@ vpt_status vpt_trainer_n_tag_problems(void* th, size_t* n_problems, size_t* n_mo
 
 vpt_status vpt_trainer_tag_problem(void* th, size_t i, void* info_out, uint8_t* surface_out, uint8_t* cand_bytes_out, uint64_t* cand_offsets_out,
                                    uint64_t* keys_out, uint64_t* row_ptr_out, uint32_t* cols_out, uint32_t* y_out) {
-    vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t || !info_out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!(t->prm.flags & VPT_TRAIN_TAGS))
-        return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "tags: the trainer was created without VPT_TRAIN_TAGS");
-    vpt_status s = build_tags(t);
-    if (s != VPT_OK) return s;
-    if (i >= t->tag_problems.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "i: no such tag problem");
+    vpt_trainer* t = tag_trainer(th, info_out != nullptr);
+    if (!t) return VPT_INVALID_ARGUMENT;
+    VPT_TRY(build_tags(t));
+    if (i >= t->tag_problems.size()) return fail_arg("i: no such tag problem");
     TagProblem& Pb = t->tag_problems[i];
     if (row_ptr_out || cols_out) {
         VPT_HIP(hipSetDevice(t->device));
-        if ((s = fetch_rows(t, Pb)) != VPT_OK) return s;
+        VPT_TRY(fetch_rows(t, Pb));
     }
     const std::string& tok = t->tag_models[Pb.model].token;
     vpt_tag_problem_info info{};
@@ -1453,12 +1396,12 @@ vpt_status vpt_trainer_tag_problem(void* th, size_t i, void* info_out, uint8_t* 
 
 vpt_status vpt_trainer_tag_weights(void* th, size_t i, void* weights_out, size_t capacity, void* stats_out) {
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
-    if (!t) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!t->trained || !t->tags_trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained tag models");
-    if (i >= t->tag_problems.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "i: no such tag problem");
+    if (!t) return fail_arg("NULL argument");
+    if (!t->trained || !t->tags_trained) return fail_arg("the trainer has no trained tag models");
+    if (i >= t->tag_problems.size()) return fail_arg("i: no such tag problem");
     const TagProblem& Pb = t->tag_problems[i];
     if (weights_out) {
-        if (capacity < Pb.w.size()) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "capacity: smaller than classes * (features + 1)");
+        if (capacity < Pb.w.size()) return fail_arg("capacity: smaller than classes * (features + 1)");
         std::memcpy(weights_out, Pb.w.data(), Pb.w.size() * 8);
     }
     if (stats_out) std::memcpy(stats_out, Pb.stats.data(), Pb.stats.size() * sizeof(vpt_train_stats));
@@ -1467,8 +1410,8 @@ vpt_status vpt_trainer_tag_weights(void* th, size_t i, void* weights_out, size_t
 
 vpt_status vpt_trainer_tag_summary(const void* th, void* out) {
     const vpt_trainer* t = static_cast<const vpt_trainer*>(th);
-    if (!t || !out) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "NULL argument");
-    if (!t->trained || !t->tags_trained) return fail(VPT_INVALID_ARGUMENT, std::string(kIA) + "the trainer has no trained tag models");
+    if (!t || !out) return fail_arg("NULL argument");
+    if (!t->trained || !t->tags_trained) return fail_arg("the trainer has no trained tag models");
     std::memcpy(out, &t->tag_summary, sizeof t->tag_summary);
     return VPT_OK;
 }

@@ -219,4 +219,13 @@ __device__ __forceinline__ uint32_t utf8_scalar(uint32_t b4) {
     return ((b0 & 0x07) << 18) | (b1 << 12) | (b2 << 6) | b3;
 }
 
+// the training kernels (kernels_train.hip, kernels_train_tags.hip): a thread per item, in workgroups of kTrainThreads
+constexpr uint32_t kTrainThreads = 256;
+template <typename K, typename... A>
+hipError_t launch1(K k, uint64_t n, hipStream_t st, A... a) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k, dim3(uint32_t((n + kTrainThreads - 1) / kTrainThreads)), dim3(kTrainThreads), 0, st, a...);
+    return hipGetLastError();
+}
+
 }  // namespace vpt

@@ -281,6 +281,40 @@ hipError_t launch_score_slow(const ScoreParams& P, int chunks, uint32_t n_blocks
 
 // boundary-model training (kernels_train.hip)
 constexpr uint32_t kCharMaskTrain = 0x1FFFFFu;   // the scalar value of a decode_chars cps word (scored | CharacterType << 24)
+// TrainKey: kind << 120 | c0 << 99 | c1 << 78 | c2 << 57 | c3 << 36 | c4 << 15 | len << 5 | (rel_position + 16), as two words (low, high)
+// (kind 0 char n-gram, 1 type n-gram, 2 dictionary word: c0 = min(len, dictn), c1 = 0 Left / 1 Inside / 2 Right, len = 0, rel = -16;
+// the tag trainer's keys hold the context alone: left of the token, then right, rel = chars to the right)
+struct TrainKey {
+    uint32_t kind, c[5], len;
+    int32_t rel;
+};
+VPT_HD uint32_t train_key_shift(uint32_t k) {
+    const uint32_t sh[5] = {99, 78, 57, 36, 15};
+    return sh[k];
+}
+// the key of fields c[0 .. n) into keys[2 * at], keys[2 * at + 1]
+VPT_HD void put_train_key(uint64_t* keys, uint64_t at, uint32_t kind, const uint32_t* c, uint32_t n, uint32_t len, int32_t rel) {
+    unsigned __int128 v = ((unsigned __int128)kind << 120) | ((len << 5) | uint32_t(rel + 16));
+    for (uint32_t k = 0; k < n; ++k) v |= (unsigned __int128)(c[k] & kCharMaskTrain) << train_key_shift(k);
+    keys[2 * at] = uint64_t(v);
+    keys[2 * at + 1] = uint64_t(v >> 64);
+}
+inline TrainKey train_key(uint64_t lo, uint64_t hi) {
+    const unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;
+    TrainKey k{uint32_t(v >> 120) & 3u, {}, uint32_t(v >> 5) & 7u, int32_t(uint32_t(v) & 31u) - 16};
+    for (uint32_t q = 0; q < 5; ++q) k.c[q] = uint32_t(v >> train_key_shift(q)) & kCharMaskTrain;
+    return k;
+}
+// The hash of a string of code points, char by char (the dictionary's table, compiled on the host and probed on the device, and the
+// surfaces' table): FNV-1a over the chars, finished with the length through mix64 (which also spreads the words of a key).
+constexpr uint64_t kCpsHashSeed = 0xCBF29CE484222325ull;
+VPT_HD uint64_t mix64(uint64_t x) {
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
+    return x ^ (x >> 33);
+}
+VPT_HD uint64_t cps_hash_step(uint64_t h, uint32_t cps_word) { return (h ^ (cps_word & kCharMaskTrain)) * 0x100000001B3ull; }
+VPT_HD uint64_t cps_hash_finish(uint64_t h, uint64_t len) { return mix64(h ^ len); }
 struct TrainFeatParams {
     const uint32_t* cps;        // decode_chars' words: sentence i's char c at ooff[i] + i + c
     const uint64_t* ooff;       // [n_sent + 1] vpt_count_boundaries' layout
@@ -296,16 +330,20 @@ struct TrainFeatParams {
 };
 hipError_t train_features(const TrainFeatParams& P, bool emit, hipStream_t st);
 uint64_t train_scan_scratch(uint64_t n);
-hipError_t train_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);   // out[n + 1], exclusive
-hipError_t train_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);
-hipError_t train_insert(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint64_t* rep, uint32_t* flag, hipStream_t st);
-hipError_t train_compact(const uint64_t* keys, const uint64_t* rep, const uint64_t* pos, uint64_t nnz, uint64_t* dkeys, uint64_t* slot, hipStream_t st);
+hipError_t train_scan(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);   // out[n + 1], exclusive
+hipError_t train_scan(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);
+// Distinct items and their ranks: every item finds (or becomes) the representative of its equals through an open-addressing table
+// (rep[i]; flag[i] = 1 at a representative), the representatives are compacted in order of first occurrence (slot[i] = where, at a
+// representative) and sorted by the caller, and train_ids maps every item to its representative's rank.  Keys here, surfaces below.
+hipError_t train_insert(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint32_t* rep, uint32_t* flag, hipStream_t st);
+hipError_t train_compact(const uint64_t* keys, const uint32_t* rep, const uint64_t* pos, uint64_t nnz, uint64_t* dkeys, uint32_t* slot, hipStream_t st);
 uint64_t train_radix_scratch(uint64_t n);
 // word_shifts[p] = u32 word << 8 | bit shift of pass p (least significant digit first)
 hipError_t train_radix_sort(const uint32_t* base, uint32_t stride, const uint32_t* word_shifts, uint32_t n_passes, uint64_t n, uint32_t* idx,
                             uint32_t* idx_tmp, uint64_t* hist, uint64_t* hist_scan, uint64_t* scan_scratch, hipStream_t st);
-hipError_t train_ids(const uint32_t* order, uint64_t nd, uint32_t* col_of, const uint64_t* rep, const uint64_t* slot, uint64_t nnz, uint32_t* ids,
-                     const uint64_t* dkeys, uint64_t* sorted_keys, hipStream_t st);
+// the nd distinct items ranked by their place in `order`, then ids[i] = rank[slot[rep[i]]] for the n items
+hipError_t train_ids(const uint32_t* order, uint64_t nd, uint32_t* rank, const uint32_t* rep, const uint32_t* slot, uint64_t n, uint32_t* ids, hipStream_t st);
+hipError_t train_sorted_keys(const uint64_t* dkeys, const uint32_t* order, uint64_t nd, uint64_t* sorted_keys, hipStream_t st);
 hipError_t train_row_sort(uint32_t* ids, const uint64_t* row_off, uint64_t nrows, uint32_t* merged, hipStream_t st);
 hipError_t train_row_merge(const uint32_t* ids, const uint64_t* row_off, const uint64_t* csr_ptr, uint64_t nrows, uint32_t* cols, uint16_t* vals,
                            uint32_t* rows, uint32_t* status, hipStream_t st);
@@ -347,13 +385,11 @@ hipError_t train_tag_validate(const uint32_t* n_tags, const uint64_t* ooff, uint
 // the trainer's example records: (first char in its char pool, chars, first key, keys)
 hipError_t train_tag_rec_finish(const uint32_t* recs, uint64_t n_ex, const uint64_t* ooff, const uint64_t* key_off, uint32_t cps_base, uint32_t key_base,
                                 uint32_t* out, hipStream_t st);
-// surface ids: representatives by a hash table, the distinct surfaces as a padded matrix (radix-sorted by the caller), ids by rank
+// surface ids: representatives by a hash table, the distinct surfaces as a padded matrix (radix-sorted by the caller), ids by train_ids
 hipError_t train_surf_insert(const uint32_t* ex, uint64_t n_ex, const uint32_t* cps, uint64_t* table, uint64_t mask, uint32_t* rep, uint32_t* flag,
                              uint32_t* maxlen, hipStream_t st);
 hipError_t train_surf_matrix(const uint32_t* ex, uint64_t n_ex, const uint32_t* flag, const uint64_t* pos, const uint32_t* cps, uint32_t maxlen,
                              uint32_t* mat, uint32_t* slot, hipStream_t st);
-hipError_t train_surf_ids(const uint32_t* order, uint64_t n_surf, uint32_t* id_of, const uint32_t* rep, const uint32_t* slot, uint64_t n_ex, uint32_t* sid,
-                          hipStream_t st);
 // all problems' matrices over concatenated arrays: occ_off NULL counts a row's keys into nk_or_occ, else writes the (key, problem) records
 hipError_t train_tag_expand(const uint32_t* row_ex, const uint32_t* row_prob, uint64_t n_rows, const uint32_t* ex, const uint64_t* occ_off,
                             const uint64_t* keys, uint32_t* nk_or_occ, uint32_t* occ_row, hipStream_t st);
@@ -384,7 +420,7 @@ struct TagClassStats {
     uint32_t iterations, cg_steps;
     double gnorm0, gnorm, objective;
 };
-bool train_tag_fits(uint64_t rows, uint64_t features, uint64_t nnz);
+bool train_tag_fits(uint64_t rows, uint64_t features);
 hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
                            const uint32_t* y, double eps, double cost, int solver, double* w, TagClassStats* stats, hipStream_t st);
 

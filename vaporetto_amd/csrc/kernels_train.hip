@@ -22,35 +22,12 @@
 namespace vpt {
 namespace {
 
-constexpr uint32_t kTrainThreads = 256;
 constexpr uint32_t kTile = kTrainThreads * 16;   // items per block of the scans, the sort and the reductions
 constexpr uint32_t kSeg = 64;                     // nonzeros (partial sums) a column segment of Xᵀv adds up
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
-}
-
-// TrainKey: kind << 120 | c0 << 99 | c1 << 78 | c2 << 57 | c3 << 36 | c4 << 15 | len << 5 | (rel_position + 16)
-// (kind 0 char n-gram, 1 type n-gram, 2 dictionary word: c0 = min(len, dictn), c1 = 0 Left / 1 Inside / 2 Right)
-__device__ __forceinline__ void put_key(uint64_t* keys, uint64_t at, uint32_t kind, const uint32_t* c, uint32_t len, int32_t rel) {
-    unsigned __int128 v = (unsigned __int128)kind << 120;
-    const uint32_t sh[5] = {99, 78, 57, 36, 15};
-    for (uint32_t k = 0; k < len; ++k) v |= (unsigned __int128)(c[k] & kCharMaskTrain) << sh[k];
-    v |= (unsigned __int128)((len << 5) | uint32_t(rel + 16));
-    keys[2 * at] = uint64_t(v);
-    keys[2 * at + 1] = uint64_t(v >> 64);
-}
-__device__ __forceinline__ void put_dict_key(uint64_t* keys, uint64_t at, uint32_t cls, uint32_t where) {
-    unsigned __int128 v = ((unsigned __int128)2 << 120) | ((unsigned __int128)cls << 99) | ((unsigned __int128)where << 78);
-    keys[2 * at] = uint64_t(v);
-    keys[2 * at + 1] = uint64_t(v >> 64);
-}
-
 // word index + 1 of the dictionary word chars[at .. at + len) is, else 0
 __device__ __forceinline__ uint32_t dict_find(const TrainFeatParams& P, const uint32_t* chars, uint32_t len, uint64_t h) {
-    for (uint64_t s = mix64(h ^ len) & P.dict_mask;; s = (s + 1) & P.dict_mask) {
+    for (uint64_t s = cps_hash_finish(h, len) & P.dict_mask;; s = (s + 1) & P.dict_mask) {
         const uint32_t e = P.dict_slots[s];
         if (e == 0) return 0;
         const uint64_t w0 = P.dict_off[e - 1], w1 = P.dict_off[e];
@@ -75,7 +52,7 @@ __device__ uint32_t boundary_features(const TrainFeatParams& P, const uint32_t* 
             for (uint32_t j = lo; j < hi; ++j) {
                 if (kEmit) {
                     for (uint32_t k = 0; k <= m; ++k) tmp[k] = kind ? (chars[j + k] >> 24) : chars[j + k];
-                    put_key(P.keys, at + cnt, uint32_t(kind), tmp, m + 1, int32_t(j) - int32_t(p) - 1);
+                    put_train_key(P.keys, at + cnt, uint32_t(kind), tmp, m + 1, m + 1, int32_t(j) - int32_t(p) - 1);
                 }
                 ++cnt;
             }
@@ -85,15 +62,15 @@ __device__ uint32_t boundary_features(const TrainFeatParams& P, const uint32_t* 
         // a word chars[s .. s + L) touches boundary p as Left (s = p + 1), Right (s + L - 1 = p) or Inside (s <= p < s + L - 1)
         const uint32_t maxl = P.dict_maxlen;
         for (uint32_t s = p + 1 >= maxl ? p + 1 - maxl : 0; s <= p + 1; ++s) {
-            uint64_t h = 0xCBF29CE484222325ull;
+            uint64_t h = kCpsHashSeed;
             const uint32_t lmax = n - s < maxl ? n - s : maxl;
             for (uint32_t L = 1; L <= lmax; ++L) {
-                h = (h ^ (chars[s + L - 1] & kCharMaskTrain)) * 0x100000001B3ull;
+                h = cps_hash_step(h, chars[s + L - 1]);
                 if (s <= p && s + L - 1 < p) continue;   // ends before the boundary
                 if (!dict_find(P, chars + s, L, h)) continue;
                 if (kEmit) {
-                    const uint32_t cls = L < P.dictn ? L : P.dictn;
-                    put_dict_key(P.keys, at + cnt, cls, s == p + 1 ? 0u : (s + L - 1 == p ? 2u : 1u));
+                    const uint32_t c[2] = {L < P.dictn ? L : P.dictn, s == p + 1 ? 0u : (s + L - 1 == p ? 2u : 1u)};
+                    put_train_key(P.keys, at + cnt, 2, c, 2, 0, -16);
                 }
                 ++cnt;
             }
@@ -178,7 +155,8 @@ __device__ __forceinline__ bool key_eq(const uint64_t* keys, uint64_t a, uint64_
     return keys[2 * a] == keys[2 * b] && keys[2 * a + 1] == keys[2 * b + 1];
 }
 // every occurrence finds (or becomes) the representative of its key: the occurrence whose index the table holds
-__global__ __launch_bounds__(kTrainThreads) void insert_kernel(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint64_t* rep) {
+__global__ __launch_bounds__(kTrainThreads) void insert_kernel(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint32_t* rep,
+                                                                 uint32_t* flag) {
     const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
     if (i >= nnz) return;
     uint64_t s = mix64(keys[2 * i] ^ mix64(keys[2 * i + 1])) & mask;
@@ -186,33 +164,29 @@ __global__ __launch_bounds__(kTrainThreads) void insert_kernel(const uint64_t* k
         uint64_t e = table[s];
         if (e == 0) {
             e = atomic_cas_u64(table + s, 0, i + 1);
-            if (e == 0) { rep[i] = i; return; }
+            if (e == 0) e = i + 1;
         }
-        if (key_eq(keys, e - 1, i)) { rep[i] = e - 1; return; }
+        if (key_eq(keys, e - 1, i)) { rep[i] = uint32_t(e - 1); flag[i] = e - 1 == i ? 1u : 0u; return; }
         s = (s + 1) & mask;
     }
 }
-__global__ __launch_bounds__(kTrainThreads) void is_rep_kernel(const uint64_t* rep, uint64_t nnz, uint32_t* flag) {
-    const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
-    if (i < nnz) flag[i] = rep[i] == i ? 1u : 0u;
-}
 // the distinct keys in first-occurrence order; slot[i] of a representative = its distinct index (read back through rep)
-__global__ __launch_bounds__(kTrainThreads) void compact_kernel(const uint64_t* keys, const uint64_t* rep, const uint64_t* pos, uint64_t nnz,
-                                                                  uint64_t* dkeys, uint64_t* slot) {
+__global__ __launch_bounds__(kTrainThreads) void compact_kernel(const uint64_t* keys, const uint32_t* rep, const uint64_t* pos, uint64_t nnz,
+                                                                  uint64_t* dkeys, uint32_t* slot) {
     const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
     if (i >= nnz || rep[i] != i) return;
     const uint64_t d = pos[i];
     dkeys[2 * d] = keys[2 * i];
     dkeys[2 * d + 1] = keys[2 * i + 1];
-    slot[i] = d;
+    slot[i] = uint32_t(d);
 }
-__global__ __launch_bounds__(kTrainThreads) void rank_kernel(const uint32_t* order, uint64_t nd, uint32_t* col_of) {
+__global__ __launch_bounds__(kTrainThreads) void rank_kernel(const uint32_t* order, uint64_t nd, uint32_t* rank) {
     const uint64_t j = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
-    if (j < nd) col_of[order[j]] = uint32_t(j);
+    if (j < nd) rank[order[j]] = uint32_t(j);
 }
-__global__ __launch_bounds__(kTrainThreads) void ids_kernel(const uint64_t* rep, const uint64_t* slot, const uint32_t* col_of, uint64_t nnz, uint32_t* ids) {
+__global__ __launch_bounds__(kTrainThreads) void ids_kernel(const uint32_t* rep, const uint32_t* slot, const uint32_t* rank, uint64_t n, uint32_t* ids) {
     const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
-    if (i < nnz) ids[i] = col_of[slot[rep[i]]];
+    if (i < n) ids[i] = rank[slot[rep[i]]];
 }
 __global__ __launch_bounds__(kTrainThreads) void sorted_keys_kernel(const uint64_t* dkeys, const uint32_t* order, uint64_t nd, uint64_t* out) {
     const uint64_t j = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
@@ -421,12 +395,6 @@ __global__ __launch_bounds__(kTrainThreads) void grad_rows_kernel(uint64_t n, co
     }
 }
 
-template <typename K, typename... A>
-hipError_t launch1(K k, uint64_t n, hipStream_t st, A... a) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k, dim3(uint32_t((n + kTrainThreads - 1) / kTrainThreads)), dim3(kTrainThreads), 0, st, a...);
-    return hipGetLastError();
-}
 uint64_t tiles(uint64_t n) { return (n + kTile - 1) / kTile; }
 
 }  // namespace
@@ -439,26 +407,20 @@ hipError_t train_features(const TrainFeatParams& P, bool emit, hipStream_t st) {
     return hipGetLastError();
 }
 uint64_t train_scan_scratch(uint64_t n) { return tiles(n) + 1; }
-hipError_t train_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st) {
+template <typename T>
+hipError_t scan(const T* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st) {
     const uint64_t nb = tiles(n);
-    if (nb) hipLaunchKernelGGL(scan_reduce_kernel<uint32_t>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, scratch);
+    if (nb) hipLaunchKernelGGL(scan_reduce_kernel<T>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, scratch);
     hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(kTrainThreads), 0, st, scratch, nb, out, n);
-    if (nb) hipLaunchKernelGGL(scan_down_kernel<uint32_t>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, (const uint64_t*)scratch, out);
+    if (nb) hipLaunchKernelGGL(scan_down_kernel<T>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, (const uint64_t*)scratch, out);
     return hipGetLastError();
 }
-hipError_t train_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st) {
-    const uint64_t nb = tiles(n);
-    if (nb) hipLaunchKernelGGL(scan_reduce_kernel<uint64_t>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, scratch);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(kTrainThreads), 0, st, scratch, nb, out, n);
-    if (nb) hipLaunchKernelGGL(scan_down_kernel<uint64_t>, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, in, n, (const uint64_t*)scratch, out);
-    return hipGetLastError();
+hipError_t train_scan(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st) { return scan(in, n, out, scratch, st); }
+hipError_t train_scan(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st) { return scan(in, n, out, scratch, st); }
+hipError_t train_insert(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint32_t* rep, uint32_t* flag, hipStream_t st) {
+    return launch1(insert_kernel, nnz, st, keys, nnz, table, mask, rep, flag);
 }
-hipError_t train_insert(const uint64_t* keys, uint64_t nnz, uint64_t* table, uint64_t mask, uint64_t* rep, uint32_t* flag, hipStream_t st) {
-    hipError_t e = launch1(insert_kernel, nnz, st, keys, nnz, table, mask, rep);
-    if (e != hipSuccess) return e;
-    return launch1(is_rep_kernel, nnz, st, (const uint64_t*)rep, nnz, flag);
-}
-hipError_t train_compact(const uint64_t* keys, const uint64_t* rep, const uint64_t* pos, uint64_t nnz, uint64_t* dkeys, uint64_t* slot, hipStream_t st) {
+hipError_t train_compact(const uint64_t* keys, const uint32_t* rep, const uint64_t* pos, uint64_t nnz, uint64_t* dkeys, uint32_t* slot, hipStream_t st) {
     return launch1(compact_kernel, nnz, st, keys, rep, pos, nnz, dkeys, slot);
 }
 uint64_t train_radix_scratch(uint64_t n) { return 256 * tiles(n); }
@@ -470,7 +432,7 @@ hipError_t train_radix_sort(const uint32_t* base, uint32_t stride, const uint32_
     for (uint32_t p = 0; p < n_passes; ++p) {
         const uint32_t word = word_shifts[p] >> 8, shift = word_shifts[p] & 255u;
         hipLaunchKernelGGL(radix_hist_kernel, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, base + word, stride, shift, (const uint32_t*)idx, n, nb, hist);
-        if ((e = train_scan_u64(hist, 256 * nb, hist_scan, scan_scratch, st)) != hipSuccess) return e;
+        if ((e = train_scan(hist, 256 * nb, hist_scan, scan_scratch, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(radix_scatter_kernel, dim3(uint32_t(nb)), dim3(kTrainThreads), 0, st, base + word, stride, shift, (const uint32_t*)idx,
                            idx_tmp, n, nb, (const uint64_t*)hist_scan);
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -479,12 +441,13 @@ hipError_t train_radix_sort(const uint32_t* base, uint32_t stride, const uint32_
     if (n_passes & 1) return hipMemcpyAsync(idx_tmp, idx, n * 4, hipMemcpyDeviceToDevice, st);   // the result in the caller's idx
     return hipSuccess;
 }
-hipError_t train_ids(const uint32_t* order, uint64_t nd, uint32_t* col_of, const uint64_t* rep, const uint64_t* slot, uint64_t nnz, uint32_t* ids,
-                     const uint64_t* dkeys, uint64_t* sorted_keys, hipStream_t st) {
-    hipError_t e = launch1(rank_kernel, nd, st, order, nd, col_of);
-    if (e == hipSuccess) e = launch1(ids_kernel, nnz, st, rep, slot, (const uint32_t*)col_of, nnz, ids);
-    if (e == hipSuccess) e = launch1(sorted_keys_kernel, nd, st, dkeys, order, nd, sorted_keys);
+hipError_t train_ids(const uint32_t* order, uint64_t nd, uint32_t* rank, const uint32_t* rep, const uint32_t* slot, uint64_t n, uint32_t* ids, hipStream_t st) {
+    hipError_t e = launch1(rank_kernel, nd, st, order, nd, rank);
+    if (e == hipSuccess) e = launch1(ids_kernel, n, st, rep, slot, (const uint32_t*)rank, n, ids);
     return e;
+}
+hipError_t train_sorted_keys(const uint64_t* dkeys, const uint32_t* order, uint64_t nd, uint64_t* sorted_keys, hipStream_t st) {
+    return launch1(sorted_keys_kernel, nd, st, dkeys, order, nd, sorted_keys);
 }
 hipError_t train_row_sort(uint32_t* ids, const uint64_t* row_off, uint64_t nrows, uint32_t* merged, hipStream_t st) {
     return launch1(row_sort_kernel, nrows, st, ids, row_off, nrows, merged);

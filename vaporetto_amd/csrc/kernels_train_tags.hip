@@ -22,16 +22,7 @@
 namespace vpt {
 namespace {
 
-constexpr uint32_t kTagThreads = 256;
-
-__device__ __forceinline__ void put_tag_key(uint64_t* keys, uint64_t at, uint32_t kind, const uint32_t* c, uint32_t len, uint32_t rel) {
-    unsigned __int128 v = (unsigned __int128)kind << 120;
-    const uint32_t sh[5] = {99, 78, 57, 36, 15};
-    for (uint32_t k = 0; k < len; ++k) v |= (unsigned __int128)c[k] << sh[k];
-    v |= (unsigned __int128)((len << 5) | (rel + 16u));
-    keys[2 * at] = uint64_t(v);
-    keys[2 * at + 1] = uint64_t(v >> 64);
-}
+constexpr uint32_t kTagThreads = kTrainThreads;
 
 // the features of token [start, end) of a sentence of n chars (tag_trainer.rs:79-100); kEmit: write the keys from `at` on
 template <bool kEmit>
@@ -48,7 +39,7 @@ __device__ uint32_t token_features(const TagFeatParams& P, const uint32_t* chars
                     for (uint32_t k = 0; k < left; ++k) tmp[k] = chars[start - left + k];
                     for (uint32_t k = 0; k < right; ++k) tmp[left + k] = chars[end + k];
                     for (uint32_t k = 0; k < m; ++k) tmp[k] = kind ? (tmp[k] >> 24) : (tmp[k] & kCharMaskTrain);
-                    put_tag_key(P.keys, at + cnt, kind, tmp, m, right);
+                    put_train_key(P.keys, at + cnt, kind, tmp, m, m, int32_t(right));
                 }
                 ++cnt;
                 if (left == 0) break;
@@ -305,13 +296,7 @@ __global__ __launch_bounds__(kTagThreads) void tag_solve_kernel(const TagSolveDe
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------- surfaces and problem construction
-__device__ __forceinline__ uint64_t tag_mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
-}
 // an example's record in the trainer's own arrays: (first char in the char pool, chars, first key, keys)
 __global__ __launch_bounds__(kTagThreads) void tag_rec_finish_kernel(const uint32_t* recs, uint64_t n_ex, const uint64_t* ooff, const uint64_t* key_off,
                                                                        uint32_t cps_base, uint32_t key_base, uint32_t* out) {
@@ -332,9 +317,9 @@ __global__ __launch_bounds__(kTagThreads) void surf_insert_kernel(const uint32_t
     if (i >= n_ex) return;
     const uint32_t* c = cps + ex[4 * i];
     const uint32_t len = ex[4 * i + 1];
-    uint64_t h = 0xCBF29CE484222325ull;
-    for (uint32_t k = 0; k < len; ++k) h = (h ^ (c[k] & kCharMaskTrain)) * 0x100000001B3ull;
-    for (uint64_t s = tag_mix64(h ^ len) & mask;; s = (s + 1) & mask) {
+    uint64_t h = kCpsHashSeed;
+    for (uint32_t k = 0; k < len; ++k) h = cps_hash_step(h, c[k]);
+    for (uint64_t s = cps_hash_finish(h, len) & mask;; s = (s + 1) & mask) {
         uint64_t e = table[s];
         if (e == 0) {
             e = atomic_cas_u64(table + s, 0, i + 1);
@@ -355,14 +340,6 @@ __global__ __launch_bounds__(kTagThreads) void surf_matrix_kernel(const uint32_t
     const uint32_t len = ex[4 * i + 1];
     for (uint32_t k = 0; k < maxlen; ++k) mat[d * maxlen + k] = k < len ? cps[ex[4 * i] + k] : 0u;
     slot[i] = uint32_t(d);
-}
-__global__ __launch_bounds__(kTagThreads) void surf_rank_kernel(const uint32_t* order, uint64_t n, uint32_t* id_of) {
-    const uint64_t j = uint64_t(blockIdx.x) * kTagThreads + threadIdx.x;
-    if (j < n) id_of[order[j]] = uint32_t(j);
-}
-__global__ __launch_bounds__(kTagThreads) void surf_id_kernel(const uint32_t* rep, const uint32_t* slot, const uint32_t* id_of, uint64_t n_ex, uint32_t* sid) {
-    const uint64_t i = uint64_t(blockIdx.x) * kTagThreads + threadIdx.x;
-    if (i < n_ex) sid[i] = id_of[slot[rep[i]]];
 }
 // a row's feature occurrences as (key, problem) records of five words
 __global__ __launch_bounds__(kTagThreads) void tag_expand_kernel(const uint32_t* row_ex, const uint32_t* row_prob, uint64_t n_rows, const uint32_t* ex,
@@ -438,60 +415,47 @@ __global__ __launch_bounds__(kTagThreads) void tag_rows_kernel(const uint32_t* r
     }
 }
 
-template <typename K, typename... A>
-hipError_t launch_chars(K k, uint64_t n, hipStream_t st, A... a) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k, dim3(uint32_t((n + kTagThreads - 1) / kTagThreads)), dim3(kTagThreads), 0, st, a...);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t train_tag_features(const TagFeatParams& P, bool emit, hipStream_t st) {
-    if (emit) return launch_chars(tag_features_kernel<true>, P.total_chars, st, P);
-    return launch_chars(tag_features_kernel<false>, P.total_chars, st, P);
+    if (emit) return launch1(tag_features_kernel<true>, P.total_chars, st, P);
+    return launch1(tag_features_kernel<false>, P.total_chars, st, P);
 }
 hipError_t train_tag_validate(const uint32_t* n_tags, const uint64_t* ooff, uint64_t n_sent, uint64_t total_chars, const uint64_t* tag_index,
                               const uint64_t* span_off, uint64_t n_spans, uint64_t n_tag_bytes, uint32_t* status, hipStream_t st) {
-    return launch_chars(tag_validate_kernel, total_chars > n_spans ? total_chars : n_spans, st, n_tags, ooff, n_sent, total_chars, tag_index, span_off,
+    return launch1(tag_validate_kernel, total_chars > n_spans ? total_chars : n_spans, st, n_tags, ooff, n_sent, total_chars, tag_index, span_off,
                         n_spans, n_tag_bytes, status);
 }
 hipError_t train_tag_rec_finish(const uint32_t* recs, uint64_t n_ex, const uint64_t* ooff, const uint64_t* key_off, uint32_t cps_base, uint32_t key_base,
                                 uint32_t* out, hipStream_t st) {
-    return launch_chars(tag_rec_finish_kernel, n_ex, st, recs, n_ex, ooff, key_off, cps_base, key_base, out);
+    return launch1(tag_rec_finish_kernel, n_ex, st, recs, n_ex, ooff, key_off, cps_base, key_base, out);
 }
 hipError_t train_surf_insert(const uint32_t* ex, uint64_t n_ex, const uint32_t* cps, uint64_t* table, uint64_t mask, uint32_t* rep, uint32_t* flag,
                              uint32_t* maxlen, hipStream_t st) {
-    return launch_chars(surf_insert_kernel, n_ex, st, ex, n_ex, cps, table, mask, rep, flag, maxlen);
+    return launch1(surf_insert_kernel, n_ex, st, ex, n_ex, cps, table, mask, rep, flag, maxlen);
 }
 hipError_t train_surf_matrix(const uint32_t* ex, uint64_t n_ex, const uint32_t* flag, const uint64_t* pos, const uint32_t* cps, uint32_t maxlen,
                              uint32_t* mat, uint32_t* slot, hipStream_t st) {
-    return launch_chars(surf_matrix_kernel, n_ex, st, ex, n_ex, flag, pos, cps, maxlen, mat, slot);
-}
-hipError_t train_surf_ids(const uint32_t* order, uint64_t n_surf, uint32_t* id_of, const uint32_t* rep, const uint32_t* slot, uint64_t n_ex, uint32_t* sid,
-                          hipStream_t st) {
-    hipError_t e = launch_chars(surf_rank_kernel, n_surf, st, order, n_surf, id_of);
-    if (e == hipSuccess) e = launch_chars(surf_id_kernel, n_ex, st, rep, slot, (const uint32_t*)id_of, n_ex, sid);
-    return e;
+    return launch1(surf_matrix_kernel, n_ex, st, ex, n_ex, flag, pos, cps, maxlen, mat, slot);
 }
 hipError_t train_tag_expand(const uint32_t* row_ex, const uint32_t* row_prob, uint64_t n_rows, const uint32_t* ex, const uint64_t* occ_off,
                             const uint64_t* keys, uint32_t* nk_or_occ, uint32_t* occ_row, hipStream_t st) {
-    return launch_chars(tag_expand_kernel, n_rows, st, row_ex, row_prob, n_rows, ex, occ_off, keys, nk_or_occ, occ_row);
+    return launch1(tag_expand_kernel, n_rows, st, row_ex, row_prob, n_rows, ex, occ_off, keys, nk_or_occ, occ_row);
 }
 hipError_t train_tag_assemble(const TagBuildParams& B, hipStream_t st) {
-    hipError_t e = launch_chars(tag_prob_kernel, B.n_prob + 1, st, B.prob_row_ptr, B.n_prob, B.occ_off, B.dpos, B.n_occ, B.prob_occ0, B.key_ptr);
+    hipError_t e = launch1(tag_prob_kernel, B.n_prob + 1, st, B.prob_row_ptr, B.n_prob, B.occ_off, B.dpos, B.n_occ, B.prob_occ0, B.key_ptr);
     if (e == hipSuccess)
-        e = launch_chars(tag_finalize_kernel, B.n_occ, st, B.occ, B.order, B.flag, B.dpos, B.n_occ, B.occ_row, B.prob_row_ptr, (const uint64_t*)B.prob_occ0,
+        e = launch1(tag_finalize_kernel, B.n_occ, st, B.occ, B.order, B.flag, B.dpos, B.n_occ, B.occ_row, B.prob_row_ptr, (const uint64_t*)B.prob_occ0,
                          (const uint64_t*)B.key_ptr, B.occ_col, B.dkeys, B.cp, B.crow);
     if (e == hipSuccess)
-        e = launch_chars(tag_rows_kernel, B.n_rows, st, B.row_prob, B.n_rows, B.occ_off, B.prob_row_ptr, (const uint64_t*)B.prob_occ0,
+        e = launch1(tag_rows_kernel, B.n_rows, st, B.row_prob, B.n_rows, B.occ_off, B.prob_row_ptr, (const uint64_t*)B.prob_occ0,
                          (const uint64_t*)B.key_ptr, B.occ_col, B.rp, B.cp);
     return e;
 }
 hipError_t train_tag_flags(const uint32_t* occ, const uint32_t* order, uint64_t n, uint32_t* flag, hipStream_t st) {
-    return launch_chars(tag_flag_kernel, n, st, occ, order, n, flag);
+    return launch1(tag_flag_kernel, n, st, occ, order, n, flag);
 }
-bool train_tag_fits(uint64_t rows, uint64_t features, uint64_t) { return 7 * (features + 1) + 3 * rows <= kTagLdsDoubles; }
+bool train_tag_fits(uint64_t rows, uint64_t features) { return 7 * (features + 1) + 3 * rows <= kTagLdsDoubles; }
 hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
                            const uint32_t* y, double eps, double cost, int solver, double* w, TagClassStats* stats, hipStream_t st) {
     if (n_prob == 0) return hipSuccess;
