@@ -56,6 +56,8 @@ fn check(st: c_int) -> Result<()> {
 /// labels by then), then `fill_tags` / `write_tokenized_text` as the CLI does; `tokenize_lines` cannot take it.
 pub const FLAG_KYTEA_FULLWIDTH: u32 = 1;
 pub const FLAG_SPLIT_LINEBREAKS: u32 = 1 << 7;
+/// With `FLAG_SPLIT_LINEBREAKS`: that filter runs before the wsconst ones (the order of vaporetto_tantivy's post-filters).
+pub const FLAG_LINEBREAKS_FIRST: u32 = 1 << 8;
 pub const fn flag_wsconst(char_type: u8) -> u32 {
     1 << char_type
 }
@@ -122,6 +124,26 @@ impl HipPredictor {
             ffi::vpt_tokenize_batch(self.raw, utf8.as_ptr(), boff.as_ptr(), n, flags, tagged as c_int, text.as_mut_ptr(), cap as u64, toff.as_mut_ptr())
         })?;
         Ok((0..n).map(|i| String::from_utf8_lossy(&text[toff[i] as usize..toff[i + 1] as usize]).into_owned()).collect())
+    }
+
+    /// `VaporettoTokenizer::token_stream` (vaporetto_tantivy/src/lib.rs:160-192) for a batch of documents: `utf8[boff[i] .. boff[i + 1]]` is document i
+    /// (empty ones are allowed), `wsconst_flags` the `flag_wsconst` bits of the adapter's D R H T K O.  Returns `(token_offsets, token_ends)`: document i
+    /// owns `token_ends[token_offsets[i] .. token_offsets[i + 1]]`, the byte offset behind every one of its tokens from its first byte (the adapter's
+    /// `boundary_pos`).  The C side trusts the sizes, so they are checked here.
+    pub fn token_stream_batch(&self, utf8: &[u8], boff: &[u64], wsconst_flags: u32) -> Result<(Vec<u64>, Vec<u32>)> {
+        let bad = |what: &str| Err(HipError::InvalidArgument(format!("InvalidArgumentError: {}", what)));
+        if boff.is_empty() { return bad("byte_offsets: n + 1 entries"); }
+        let n = boff.len() - 1;
+        if boff.windows(2).any(|w| w[1] < w[0]) { return bad("offsets: must not decrease"); }
+        if (utf8.len() as u64) < boff[n] { return bad("utf8: shorter than byte_offsets[n]"); }
+        let capacity = (boff[n] - boff[0]) as usize;   // a token per char at most, a char per byte at most
+        let mut offsets = vec![0u64; n + 1];
+        let mut ends = vec![0u32; capacity.max(1)];
+        check(unsafe {
+            ffi::vpt_token_stream_batch(self.raw, utf8.as_ptr(), boff.as_ptr(), n, wsconst_flags, offsets.as_mut_ptr(), ends.as_mut_ptr(), capacity as u64)
+        })?;
+        ends.truncate(offsets[n] as usize);
+        Ok((offsets, ends))
     }
 
     /// `Predictor::serialize_to_vec` / `deserialize_from_slice_unchecked` (predictor.rs:640-664), in this library's own format

@@ -1,0 +1,31 @@
+// Example of vaporetto_tantivy's token stream over the C ABI (include/vaporetto_hip.hpp, VaporettoTokenizer): documents in, token byte spans out.
+//   g++ -O2 -std=c++17 -Iinclude -o token_stream examples/token_stream.cpp -Lvaporetto_amd/lib -lvaporetto_hip -Wl,-rpath,'$ORIGIN/vaporetto_amd/lib'
+//   ./token_stream model.bin [wsconst] < documents.txt       (one document per line; wsconst: chars of DRHTKOG, vaporetto_tantivy/src/lib.rs:69-86)
+// One line per token: doc <TAB> position <TAB> offset_from <TAB> offset_to <TAB> text   (byte offsets into the document, as tantivy's Token holds them)
+#include <cstdio>
+#include <fstream>
+#include <iostream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "vaporetto_hip.hpp"
+
+int main(int argc, char** argv) {
+    if (argc < 2) { std::fprintf(stderr, "usage: %s model.bin [wsconst] < documents\n", argv[0]); return 2; }
+    std::ifstream f(argv[1], std::ios::binary);
+    const std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    try {
+        vaporetto_hip::VaporettoTokenizer tokenizer(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argc > 2 ? argv[2] : "");
+        std::vector<std::string> docs;
+        for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
+        const auto streams = tokenizer.token_stream_batch(docs);
+        for (size_t d = 0; d < streams.size(); ++d)
+            for (const vaporetto_hip::Token& t : streams[d])
+                std::printf("%zu\t%zu\t%zu\t%zu\t%s\n", d, t.position, t.offset_from, t.offset_to, t.text.c_str());
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

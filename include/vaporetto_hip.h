@@ -49,6 +49,11 @@ enum { VPT_FLAG_KYTEA_FULLWIDTH = 1 };
  * Types are those of the scored text (after VPT_FLAG_KYTEA_FULLWIDTH, as in the CLI). */
 #define VPT_FLAG_WSCONST(char_type) (1u << (char_type))
 enum { VPT_FLAG_SPLIT_LINEBREAKS = 1 << 7, VPT_FLAG_ALL = 0xFF };
+/* VPT_FLAG_LINEBREAKS_FIRST (with VPT_FLAG_SPLIT_LINEBREAKS; vpt_predict_batch_flags and vpt_batch_set_flags take it): SplitLinebreaksFilter runs BEFORE
+ * the VPT_FLAG_WSCONST filters instead of after them -- the order of vaporetto_tantivy's post-filters (vaporetto_tantivy/src/lib.rs:69-86).  It
+ * shows where a linebreak stands next to a char of its own type under its wsconst flag ('\n', '\r' and ' ' are Other): "a\n\nb" with
+ * VPT_FLAG_WSCONST(6) gives a | \n\n | b with this bit, a | \n | \n | b without.  Not part of VPT_FLAG_ALL. */
+enum { VPT_FLAG_LINEBREAKS_FIRST = 1 << 8 };
 
 typedef struct vpt_predictor vpt_predictor;
 typedef struct vpt_batch vpt_batch;
@@ -354,6 +359,37 @@ vpt_status vpt_count_boundaries_device(const vpt_predictor *p, vpt_batch *b, con
 vpt_status vpt_tokenize_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets,
                               size_t n_sentences, unsigned flags, int tagged, uint8_t *text_out,
                               uint64_t text_capacity, uint64_t *text_offsets_out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * VaporettoTokenizer::token_stream over a batch of documents                  (vaporetto_tantivy/src/lib.rs:157-229)
+ *
+ * What an indexer takes from the tokenizer: per document the byte span of every token IN THE CALLER'S TEXT, as CSR:
+ *   token_offsets [n + 1]   document i owns the tokens token_offsets[i] .. token_offsets[i + 1]; their number is the adapter's position_length;
+ *   token_ends [capacity]   the adapter's boundary_pos (lib.rs:183-192): the byte offset, from the document's first byte, behind every token.  A
+ *                           token's offset_to; its offset_from is the entry before it in the same document, or 0; its position is its index
+ *                           minus token_offsets[i].  One entry per char always suffices.
+ * vpt_token_spans_batch_device: lib.rs:183-192 (the char_indices / boundaries zip) for labels that are on the device already -- laid out as
+ *   vpt_predict_batch_device writes them, possibly edited by the caller's own filters; one launch (kernels_tokens.hip), asynchronous on hip_stream,
+ *   no host wait between the scoring launch and this one.  Errors at vpt_batch_sync: VPT_BOUNDARY_UNKNOWN among the labels, offsets that do not
+ *   match the text, a document of 2^32 bytes or more (all VPT_INVALID_ARGUMENT), and more tokens than `capacity`
+ *   (VPT_INVALID_ARGUMENT "text_capacity: ..."): nothing is written past `capacity` entries.
+ * vpt_token_spans_batch: the same from host buffers (the labels: the caller's -- what callers with filters of their own use, and the
+ *   ConcatGraphemeClustersFilter path, whose filter runs on the host).  out_offsets from vpt_count_boundaries.
+ * vpt_token_stream_batch: lib.rs:160-192 for a batch -- an empty document has no tokens (lib.rs:161-169; not an error here), KyteaFullwidthFilter always
+ *   (lib.rs:172), Predictor::predict, SplitLinebreaksFilter, then the KyteaWsConstFilter of every VPT_FLAG_WSCONST bit of wsconst_flags (lib.rs:69-86;
+ *   any other bit is VPT_INVALID_ARGUMENT "Could not parse a wsconst value"), the spans counted on the caller's bytes.  Only the text crosses
+ *   PCIe on the way in and 8 (n + 1) + 4 x tokens bytes on the way out: char counting, scoring, filters and spans run on the device, large batches
+ *   as chunks of whole documents through vpt_tokenize_batch's pipeline.  A NUL in a document (Sentence::from_raw(..).unwrap() panics there,
+ *   lib.rs:173) is VPT_INVALID_ARGUMENT "text: must not contain NULL".  ("G", ConcatGraphemeClustersFilter, is a host filter: predict with
+ *   VPT_FLAG_LINEBREAKS_FIRST, the filter, vpt_token_spans_batch -- as include/vaporetto_hip.hpp and vaporetto_amd/api.py do.) */
+vpt_status vpt_token_spans_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                        const uint64_t *d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t *d_labels,
+                                        uint64_t *d_token_offsets, uint32_t *d_token_ends, uint64_t capacity, void *hip_stream);
+vpt_status vpt_token_spans_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                 const uint64_t *out_offsets, const uint8_t *labels, uint64_t *token_offsets_out, uint32_t *token_ends_out,
+                                 uint64_t capacity);
+vpt_status vpt_token_stream_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                  unsigned wsconst_flags, uint64_t *token_offsets_out, uint32_t *token_ends_out, uint64_t capacity);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Sentence::from_tokenized over a batch                                                  (sentence.rs:285-514)

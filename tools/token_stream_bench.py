@@ -1,0 +1,231 @@
+"""Token streams on the GPU box: the span kernel beside the untagged writer, and vpt_token_stream_batch end to end beside the two routes a caller
+had to the same arrays before it.
+    python tools/token_stream_bench.py [--configs 2,5] [--sentences N] [--steps 15] [--rounds 3] [--out profiles/token_stream_bench.json]
+Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and its documents workload):
+  (a) kernels, by device events on the labels a predict call left on the device, in ONE process, alternating, `--rounds` rounds of `--steps` calls:
+      token_spans_kernel and the untagged emit_flat_kernel (same text and labels in; the writer stores the tokens' text, the span kernel 4 bytes a
+      token).  `spread` = (max - min) / min of a kernel's per-round medians: what a difference between the two has to exceed to mean anything.
+  (b) end to end, pinned buffers, median of `--steps` calls that end in a synchronise:
+      stream   vpt_token_stream_batch
+      labels   vpt_predict_batch_flags (labels only, the adapter's filters as flags) + the numpy conversion of labels and text to the CSR
+      text     vpt_tokenize_batch + numpy parsing of the tokenized text to the CSR (same flags without the linebreak ones: the synthetic text has none)
+      and the host share of the two older routes on its own.
+  (c) bytes over PCIe each way for the three.
+Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
+on the first --parity-docs documents."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def csr_from_labels(utf8, boff, ooff, labels):
+    """The host scan a caller of vpt_predict_batch_flags needed: (token_offsets, token_ends) from labels and text, vectorised."""
+    S = len(boff) - 1
+    lead = np.flatnonzero((utf8 & 0xC0) != 0x80).astype(np.int64)        # byte position of every char
+    nchars = len(lead)
+    first = (ooff[:-1] + np.arange(S, dtype=np.uint64)).astype(np.int64)  # the documents' first chars
+    is_first = np.zeros(nchars, dtype=bool)
+    is_first[first] = True
+    doc_start = np.repeat(boff[:-1].astype(np.int64), np.diff(first, append=nchars))
+    mark = np.ones(nchars, dtype=bool)                                    # a document's first char closes the one before it
+    mark[~is_first] = labels[:nchars - S] == 1
+    mark[0] = False
+    value = lead - doc_start
+    value[first[1:]] = np.diff(boff[:-1].astype(np.int64))                # ... with that document's length
+    ends = np.concatenate([value[mark], [int(boff[-1] - boff[-2])]]).astype(np.uint32)
+    per_doc = np.add.reduceat((mark & ~is_first).astype(np.int64), first) + 1
+    toff = np.zeros(S + 1, dtype=np.uint64)
+    toff[1:] = np.cumsum(per_doc)
+    return toff, ends
+
+
+def csr_from_tokenized(text, toff_text, S):
+    """The host parse a caller of vpt_tokenize_batch needed (texts without '\\\\': the synthetic batches; else the slow exact loop)."""
+    if (text == 0x5C).any():
+        raise SystemExit("the batch needs un-escaping: not a synthetic one")
+    sep = text == 0x20
+    n_sep_before = np.cumsum(sep) - sep
+    starts = toff_text[:-1].astype(np.int64)
+    stops = toff_text[1:].astype(np.int64)
+    sep_pos = np.flatnonzero(sep)
+    line_idx = np.searchsorted(starts, sep_pos, side="right") - 1
+    raw_start = starts - n_sep_before[np.minimum(starts, len(text) - 1)]   # raw bytes in front of the line = its text position minus the separators before
+    ends_sep = sep_pos - n_sep_before[sep_pos] - raw_start[line_idx]
+    doc_len = (stops - starts) - (np.add.reduceat(sep.astype(np.int64), starts) if len(text) else 0)
+    per_doc = np.bincount(line_idx, minlength=S) + 1
+    toff = np.zeros(S + 1, dtype=np.uint64)
+    toff[1:] = np.cumsum(per_doc)
+    ends = np.zeros(int(toff[-1]), dtype=np.uint32)
+    last = toff[1:].astype(np.int64) - 1
+    ends[last] = doc_len
+    keep = np.ones(len(ends), dtype=bool)
+    keep[last] = False
+    ends[keep] = ends_sep
+    return toff, ends
+
+
+def med(xs):
+    return float(np.median(xs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="2,5")
+    ap.add_argument("--sentences", type=int, default=0, help="sentences of configs[2]'s batch (0: all of it)")
+    ap.add_argument("--steps", type=int, default=15)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--parity-docs", type=int, default=2000)
+    ap.add_argument("--wsconst", default="")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import torch
+    import bench
+    from tests import tokenref
+    from vaporetto_amd import _lib, api
+    torch.cuda.init()
+    dev = torch.device("cuda", 0)
+    ncores = min(os.cpu_count() or 1, 16)
+    stream = torch.cuda.current_stream().cuda_stream
+    L = _lib.load()
+    rows = []
+    for cid in [int(c) for c in args.configs.split(",")]:
+        cfg = bench.CONFIGS[cid]
+        raw, name = bench.load_model_bytes(cfg["kind"], 1.0)
+        utf8, boff, ooff, _, S = bench.make_shard(cfg, raw, 0, 1, ncores, args.sentences if cid == 2 else 0)
+        S = len(boff) - 1
+        nb, nbytes = int(ooff[-1]), int(boff[-1])
+        pred = api.Predictor(api.Model.read_slice(raw)[0], False, device=0)
+        ws_flags = api.wsconst_flags(args.wsconst)
+        flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH | _lib.VPT_FLAG_SPLIT_LINEBREAKS | _lib.VPT_FLAG_LINEBREAKS_FIRST | ws_flags
+        row = {"workload": cfg["name"], "model": name, "documents": S, "text_bytes": nbytes, "chars": nb + S, "wsconst": args.wsconst, "steps": args.steps}
+        # ---- (a) the kernels, alternating
+        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(64, np.uint8)])).to(dev)
+        d_boff = torch.from_numpy(boff.astype(np.int64)).to(dev)
+        d_ooff = torch.from_numpy(ooff.astype(np.int64)).to(dev)
+        max_bytes = int(np.max(np.diff(boff.astype(np.int64))))
+        batch = api.DeviceBatch(pred)
+        batch.set_flags(flags)
+        d_labels = torch.empty(nb + 16, dtype=torch.uint8, device=dev)
+        batch.predict(d_text.data_ptr(), d_boff.data_ptr(), d_ooff.data_ptr(), S, nb, max_bytes, 0, d_labels.data_ptr(), stream)
+        batch.sync()
+        cap_text, cap_ends = 3 * nbytes + 64, nb + S
+        d_out = torch.empty(cap_text + 1, dtype=torch.uint8, device=dev)
+        d_toff = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        d_ends = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
+        d_soff = torch.empty(S + 1, dtype=torch.int64, device=dev)
+
+        def emit():
+            batch.write_tokenized(d_text.data_ptr(), d_boff.data_ptr(), d_ooff.data_ptr(), S, nb, d_labels.data_ptr(), d_out.data_ptr(), cap_text, d_toff.data_ptr(), stream)
+
+        def spans():
+            batch.token_spans(d_text.data_ptr(), d_boff.data_ptr(), d_ooff.data_ptr(), S, nb, d_labels.data_ptr(), d_soff.data_ptr(), d_ends.data_ptr(), cap_ends, stream)
+        for _ in range(3):
+            emit(); spans()
+        batch.sync()
+        per_round = {"emit": [], "spans": []}
+        for _ in range(args.rounds):
+            for which, fn in (("emit", emit), ("spans", spans)):
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                per_round[which].append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        n_tokens = int(d_soff[-1].item())
+        out_text = int(d_toff[-1].item())
+        k = {}
+        for which in ("emit", "spans"):
+            r = per_round[which]
+            k[which + "_ms"] = round(med(r), 4)
+            k[which + "_rounds_ms"] = [round(x, 4) for x in r]
+            k[which + "_spread"] = round((max(r) - min(r)) / min(r), 4)
+        k["spans_over_emit"] = round(k["spans_ms"] / k["emit_ms"], 3)
+        k["emit_bytes_moved"] = nbytes + nb + out_text + 24 * S
+        k["spans_bytes_moved"] = nbytes + 2 * nb + 4 * n_tokens + 24 * S     # (the labels twice: the size pass and the pieces)
+        k["spans_frac_of_hbm"] = round(k["spans_bytes_moved"] / k["spans_ms"] / 1e6 / bench.HBM_PEAK_GBS, 4)
+        k["emit_frac_of_hbm"] = round(k["emit_bytes_moved"] / k["emit_ms"] / 1e6 / bench.HBM_PEAK_GBS, 4)
+        row["kernels"] = k
+        dev_off = d_soff.cpu().numpy().astype(np.uint64)
+        dev_ends = d_ends[:n_tokens].cpu().numpy().view(np.uint32)
+        del d_out, d_toff, d_ends, d_soff, d_labels, d_text, batch
+        # ---- (b) end to end, pinned buffers
+        p_text = api.PinnedArray(nbytes, np.uint8); p_text.array[:] = utf8
+        p_boff = api.PinnedArray(S + 1, np.uint64); p_boff.array[:] = boff
+        p_ends = api.PinnedArray(max(nbytes, 1), np.uint32)
+        p_toff = api.PinnedArray(S + 1, np.uint64)
+        p_lab = api.PinnedArray(nb + 1, np.uint8)
+        p_tok = api.PinnedArray(3 * nbytes + 64, np.uint8)
+        p_tokoff = api.PinnedArray(S + 1, np.uint64)
+        u, bo = p_text.array, p_boff.array
+
+        def route_stream():
+            return pred.token_stream_packed(u, bo, args.wsconst, ends_out=p_ends.array, offsets_out=p_toff.array)
+
+        def route_labels_device():
+            st = L.vpt_predict_batch_flags(pred.handle, u.ctypes.data, bo.ctypes.data, S, None, p_lab.array.ctypes.data, ooff.ctypes.data, flags)
+            assert st == 0, _lib.last_error()
+
+        def route_text_device():
+            return pred.tokenize_packed(u, bo, flags=_lib.VPT_FLAG_KYTEA_FULLWIDTH | ws_flags, text_out=p_tok.array, offsets_out=p_tokoff.array)
+
+        def timed(fn, n):
+            fn()
+            ts = []
+            for _ in range(n):
+                t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+            return ts
+        e = {}
+        t_stream = timed(route_stream, args.steps)
+        s_off, s_ends = route_stream()
+        s_off, s_ends = s_off.copy(), s_ends.copy()
+        t_lab_dev = timed(route_labels_device, args.steps)
+        host_n = max(3, min(args.steps, 5))
+        t_lab_host = timed(lambda: csr_from_labels(u, bo, ooff, p_lab.array), host_n)
+        l_off, l_ends = csr_from_labels(u, bo, ooff, p_lab.array)
+        t_txt_dev = timed(route_text_device, args.steps)
+        text, toff_text = route_text_device()
+        t_txt_host = timed(lambda: csr_from_tokenized(text, toff_text, S), host_n)
+        x_off, x_ends = csr_from_tokenized(text, toff_text, S)
+        e["stream_ms"] = round(med(t_stream), 3)
+        e["labels_route_ms"] = round(med(t_lab_dev) + med(t_lab_host), 3)
+        e["labels_route_device_ms"], e["labels_route_host_ms"] = round(med(t_lab_dev), 3), round(med(t_lab_host), 3)
+        e["text_route_ms"] = round(med(t_txt_dev) + med(t_txt_host), 3)
+        e["text_route_device_ms"], e["text_route_host_ms"] = round(med(t_txt_dev), 3), round(med(t_txt_host), 3)
+        e["host_scan"] = "numpy, one thread: the conversion a caller of the older routes runs after the call returns"
+        row["end_to_end"] = e
+        # ---- (c) PCIe bytes
+        row["pcie"] = {"stream": {"h2d": nbytes + 8 * (S + 1), "d2h": 8 * (S + 1) + 4 * len(s_ends)},
+                       "labels_route": {"h2d": nbytes + 16 * (S + 1), "d2h": nb},
+                       "text_route": {"h2d": nbytes + 8 * (S + 1), "d2h": int(toff_text[-1]) + 8 * (S + 1)},
+                       "note": "4 bytes a token is MORE device-to-host than 1 byte a label when tokens are shorter than four chars (mean chars per token here: %.2f)" % ((nb + S) / max(len(s_ends), 1))}
+        # ---- parity
+        par = {"stream_equals_device_call": bool(np.array_equal(s_off, dev_off) and np.array_equal(s_ends, dev_ends)),
+               "stream_equals_labels_route": bool(np.array_equal(s_off, l_off) and np.array_equal(s_ends, l_ends)),
+               "stream_equals_text_route": bool(np.array_equal(s_off, x_off) and np.array_equal(s_ends, x_ends))}
+        n_par = min(args.parity_docs, S)
+        texts = [bytes(utf8[int(boff[i]):int(boff[i + 1])]).decode("utf-8") for i in range(n_par)]
+        w_off, w_ends = tokenref.csr(tokenref.ends_batch(raw, texts, args.wsconst))
+        par["tokenref_docs"] = n_par
+        par["stream_equals_tokenref"] = bool(np.array_equal(s_off[:n_par + 1], w_off) and np.array_equal(s_ends[:int(w_off[-1])], w_ends))
+        row["parity"] = par
+        row["tokens"] = int(len(s_ends))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del p_text, p_boff, p_ends, p_toff, p_lab, p_tok, p_tokoff, pred
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump({"tool": "tools/token_stream_bench.py", "args": vars(args), "rows": rows}, fh, indent=1)
+    if not all(all(v for kk, v in r["parity"].items() if kk != "tokenref_docs") for r in rows):
+        raise SystemExit("parity FAILED")
+
+
+if __name__ == "__main__":
+    main()

@@ -777,15 +777,18 @@ class Predictor:
                 start, valid = e + 1, True
 
     def predict_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, fullwidth: bool = False,
-                       wsconst: Sequence[int] = (), split_linebreaks: bool = False):
+                       wsconst: Sequence[int] = (), split_linebreaks: bool = False, linebreaks_first: bool = False):
         """utf8: uint8[total bytes]; byte_offsets: uint64[S+1].  Returns (scores, labels, out_offsets).
         fullwidth: score the text as KyteaFullwidthFilter would rewrite it (the CLI's default normalisation).
-        wsconst: CharacterTypes for KyteaWsConstFilter; split_linebreaks: SplitLinebreaksFilter (labels only)."""
+        wsconst: CharacterTypes for KyteaWsConstFilter; split_linebreaks: SplitLinebreaksFilter (labels only), after the wsconst filters
+        unless linebreaks_first (VPT_FLAG_LINEBREAKS_FIRST: the order of vaporetto_tantivy's post-filters)."""
         flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0
         for t in wsconst:
             flags |= _lib.VPT_FLAG_WSCONST(int(t))
         if split_linebreaks:
             flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
+        if linebreaks_first:
+            flags |= _lib.VPT_FLAG_LINEBREAKS_FIRST
         L = _lib.load()
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
@@ -803,6 +806,47 @@ class Predictor:
             _raise(st)
         return scores[:nb], labels[:nb], ooff
 
+    def token_spans_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray):
+        """vpt_token_spans_batch: the token spans (vaporetto_tantivy/src/lib.rs:183-192) of a packed batch for the CALLER'S labels, on the
+        device.  Returns (token_offsets uint64 [S+1], token_ends uint32): document i owns token_ends[token_offsets[i]:token_offsets[i+1]], the
+        byte offset behind every one of its tokens from its first byte."""
+        L = _lib.load()
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        out_offsets = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        S = len(byte_offsets) - 1
+        cap = (int(out_offsets[S] - out_offsets[0]) + S) if S else 0
+        toff = np.zeros(S + 1, dtype=np.uint64)
+        ends = np.zeros(max(cap, 1), dtype=np.uint32)
+        lab = labels if len(labels) else np.zeros(1, dtype=np.uint8)
+        st = L.vpt_token_spans_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data, lab.ctypes.data,
+                                     toff.ctypes.data, ends.ctypes.data, cap)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return toff, ends[:int(toff[S])]
+
+    def token_stream_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, wsconst: str = "", ends_out: Optional[np.ndarray] = None,
+                            offsets_out: Optional[np.ndarray] = None):
+        """vpt_token_stream_batch: VaporettoTokenizer::token_stream (vaporetto_tantivy/src/lib.rs:160-192) for a packed batch of documents
+        (empty ones allowed) -- KyteaFullwidthFilter, predict, SplitLinebreaksFilter, the wsconst filters, the spans, all on the device.
+        `wsconst`: chars of "DRHTKO" ("G" is a host filter: VaporettoTokenizer takes that path).  Returns (token_offsets, token_ends) as
+        token_spans_packed; `ends_out` / `offsets_out` may be preallocated (pinned) arrays, ends_out of one uint32 per text byte."""
+        L = _lib.load()
+        flags = wsconst_flags(wsconst)
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S = len(byte_offsets) - 1
+        cap = int(byte_offsets[S] - byte_offsets[0]) if S else 0
+        if offsets_out is None:
+            offsets_out = np.zeros(S + 1, dtype=np.uint64)
+        if ends_out is None:
+            ends_out = np.zeros(max(cap, 1), dtype=np.uint32)
+        st = L.vpt_token_stream_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, flags, offsets_out.ctypes.data,
+                                      ends_out.ctypes.data, min(cap, len(ends_out)))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return offsets_out, ends_out[:int(offsets_out[S])]
 
     def parse_tokenized_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray) -> dict:
         """Sentence::from_tokenized for a packed batch of tokenized lines, on the device (vpt_parse_tokenized_batch_device).  Returns
@@ -1045,6 +1089,14 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def token_spans(self, d_utf8: int, d_boff: int, d_ooff: int, n_documents: int, total_boundaries: int, d_labels: int,
+                    d_token_offsets: int, d_token_ends: int, capacity: int, stream: int = 0) -> None:
+        """Device-resident token spans of the batch for the labels at d_labels (vpt_token_spans_batch_device); enqueues and returns."""
+        st = _lib.load().vpt_token_spans_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_documents, total_boundaries,
+                                                      d_labels or None, d_token_offsets, d_token_ends or None, capacity, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def predict_write(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, max_sentence_bytes: int,
                       d_scores: int, d_labels: int, d_text_out: int, text_capacity: int, d_text_offsets: int, stream: int = 0) -> None:
         """Predictor::predict and write_tokenized_text (no tags) in ONE scoring launch (vpt_predict_write_batch_device): the tiles of the
@@ -1170,6 +1222,101 @@ def evaluation_result(counts) -> dict:
         p, q = div(num, den_p), div(num, den_r)
         r[name + "_precision"], r[name + "_recall"], r[name + "_f1"] = p, q, f1(p, q)
     return r
+
+
+_WSCONST_TYPES = {"D": 1, "R": 2, "H": 3, "T": 4, "K": 5, "O": 6}
+
+
+def wsconst_flags(wsconst: str, allow_graphemes: bool = False) -> int:
+    """The VPT_FLAG_WSCONST bits of a wsconst string of vaporetto_tantivy (D R H T K O; vaporetto_tantivy/src/lib.rs:69-86)."""
+    flags = 0
+    for c in wsconst:
+        if c == "G" and allow_graphemes:
+            continue
+        if c not in _WSCONST_TYPES:
+            raise VaporettoError("InvalidArgument", "Could not parse a wsconst value")   # lib.rs:82
+        flags |= _lib.VPT_FLAG_WSCONST(_WSCONST_TYPES[c])
+    return flags
+
+
+class TantivyToken:
+    """tantivy's Token as VaporettoTokenStream fills it (vaporetto_tantivy/src/lib.rs:204-219): byte offsets into the caller's text."""
+    __slots__ = ("text", "offset_from", "offset_to", "position", "position_length")
+
+    def __init__(self, text: str, offset_from: int, offset_to: int, position: int, position_length: int):
+        self.text, self.offset_from, self.offset_to, self.position, self.position_length = text, offset_from, offset_to, position, position_length
+
+    def _key(self):
+        return (self.text, self.offset_from, self.offset_to, self.position, self.position_length)
+
+    def __eq__(self, other):
+        return isinstance(other, TantivyToken) and self._key() == other._key()
+
+    def __repr__(self):
+        return "Token(text=%r, offset_from=%d, offset_to=%d, position=%d, position_length=%d)" % self._key()
+
+
+class VaporettoTokenizer:
+    """vaporetto_tantivy's VaporettoTokenizer (vaporetto_tantivy/src/lib.rs:62-229) over the C ABI: KyteaFullwidthFilter always, Predictor::new(model,
+    false), SplitLinebreaksFilter first, then one filter per char of `wsconst` (D R H T K O: KyteaWsConstFilter; G: ConcatGraphemeClustersFilter).
+    Without "G" a batch is ONE call (vpt_token_stream_batch: only the text goes to the device, the spans come back); with it three -- predict with
+    the linebreaks-first flag, the grapheme filter on the host over the normalised text, vpt_token_spans_batch -- as Predictor.tokenize does."""
+
+    def __init__(self, model: Model, wsconst: str = "", device: int = 0, _predictor: Optional[Predictor] = None):
+        self._flags = wsconst_flags(wsconst, allow_graphemes=True)
+        self._wsconst = "".join(c for c in wsconst if c != "G")
+        self._graphemes = "G" in wsconst
+        self._predictor = _predictor if _predictor is not None else Predictor(model, False, device=device)
+
+    @classmethod
+    def deserialize(cls, blob, wsconst: str = "", device: int = 0) -> "VaporettoTokenizer":
+        """lib.rs:121-146, from Predictor.save_compiled's bytes (vpt_predictor_load)."""
+        wsconst_flags(wsconst, allow_graphemes=True)
+        return cls(None, wsconst, device, _predictor=Predictor.load_compiled(blob, device=device))
+
+    @property
+    def predictor(self) -> Predictor:
+        return self._predictor
+
+    def token_spans(self, texts: Sequence[str]):
+        """(utf8, byte_offsets, token_offsets, token_ends) of a batch of documents."""
+        raws = [t.encode("utf-8") for t in texts]
+        utf8, boff = pack_texts(raws)
+        if not self._graphemes:
+            toff, ends = self._predictor.token_stream_packed(utf8, boff, self._wsconst)
+            return utf8, boff, toff, ends
+        keep = [i for i, r in enumerate(raws) if r]   # an empty document has no tokens and is no sentence
+        toff = np.zeros(len(texts) + 1, dtype=np.uint64)
+        if not keep:
+            return utf8, boff, toff, np.zeros(0, dtype=np.uint32)
+        k_utf8, k_boff = pack_texts([raws[i] for i in keep])
+        types = [t for t in range(1, 7) if self._flags & _lib.VPT_FLAG_WSCONST(t)]
+        _, labels, ooff = self._predictor.predict_packed(k_utf8, k_boff, fullwidth=True, wsconst=types, split_linebreaks=True, linebreaks_first=True)
+        norm = KyteaFullwidthFilter()
+        ConcatGraphemeClustersFilter().filter_packed([norm.filter(texts[i]) for i in keep], ooff, labels)
+        k_toff, ends = self._predictor.token_spans_packed(k_utf8, k_boff, ooff, labels)
+        counts = np.zeros(len(texts), dtype=np.uint64)
+        counts[keep] = np.diff(k_toff)
+        toff[1:] = np.cumsum(counts)
+        return utf8, boff, toff, ends
+
+    def token_stream_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
+        if not texts:
+            return []
+        utf8, boff, toff, ends = self.token_spans(texts)
+        out = []
+        for i, _ in enumerate(texts):
+            raw = bytes(utf8[int(boff[i]):int(boff[i + 1])])
+            e = [int(x) for x in ends[int(toff[i]):int(toff[i + 1])]]
+            toks, start = [], 0
+            for k, end in enumerate(e):
+                toks.append(TantivyToken(raw[start:end].decode("utf-8"), start, end, k, len(e)))
+                start = end
+            out.append(toks)
+        return out
+
+    def token_stream(self, text: str) -> List[TantivyToken]:
+        return self.token_stream_batch([text])[0]
 
 
 def pack_texts(raws: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:

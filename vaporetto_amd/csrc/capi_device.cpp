@@ -20,7 +20,7 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     P.ctype = p->d_ctype;
     P.cinfo = (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) ? p->d_cinfo + 65536 : nullptr;
     P.cid = p->d_cid ? p->d_cid + ((b->flags & VPT_FLAG_KYTEA_FULLWIDTH) ? 65536 : 0) : nullptr;
-    P.post = b->flags & 0xFEu;
+    P.post = b->flags & 0x1FEu;   // (bit 8: VPT_FLAG_LINEBREAKS_FIRST)
     P.type_window = p->type_window; P.type_kind = p->type_kind; P.bias = p->bias; P.pad = p->pad;
     P.force_window_table = p->knobs.force_window_table ? 1u : 0u;
     // flat positions of the longest sentence: its chars, bounded by the caller's hint or else by its bytes
@@ -300,6 +300,46 @@ vpt_status vpt_expand_tags_batch_device(const vpt_predictor* p, vpt_batch* b, si
     return VPT_OK;
 }
 
+namespace {
+// The runs of a flat kernel over sentences (the writer, the token spans) and the state words of their chain: fills F.
+vpt_status plan_runs(const vpt_predictor* p, vpt_batch* b, size_t n_sentences, uint64_t total_boundaries, bool records, uint32_t run_sent,
+                     uint64_t* total_out, const uint64_t* chain_in, uint64_t* chain_out, hipStream_t stream, vpt::EmitFuse* F_out) {
+    // A WORKGROUP per run of sentences (emit_flat_kernel, round 5; a wave per block of 2 K chars before): 5 K chars when the batch is small (the
+    // chip wants a thousand workgroups and more), up to 20 K on a big one -- fewer look-backs and size passes per byte (measured,
+    // profiles/r05_h_*, r05_k_*, r06_t_*: configs[2] 2.03 ms at 128 sentences, 1.80 at 256; tagged configs[4] 2.39 / 2.10 / 2.04 at 5 K / 10 K / 20 K
+    // chars; without tags up to 32 K chars: 512 sentences of 64, `r06_zv_*`); at most 512 sentences (two a thread).  With tags: a whole multiple of fill_tags' runs, so that a workgroup's records are run_pref[a] .. run_pref[b].
+    vpt::EmitFuse F{};
+    {
+        const uint64_t chars = total_boundaries + n_sentences;
+        const uint64_t auto_run = std::min<uint64_t>(std::max<uint64_t>(chars / (uint64_t(16) * std::max<uint32_t>(p->n_cus, 64)), 5120), records ? 20480 : 32768);
+        const uint64_t target = auto_run;
+        uint64_t per = std::min<uint64_t>(std::max<uint64_t>((target * n_sentences + chars / 2) / chars, 1), vpt::kEmitFlatMaxBlock);   // round(target / mean chars per sentence)
+        if (records && run_sent <= vpt::kEmitFlatMaxBlock)
+            per = std::min<uint64_t>(std::max<uint64_t>((per + run_sent / 2) / run_sent, 1) * run_sent, (vpt::kEmitFlatMaxBlock / run_sent) * run_sent);
+        F.per_block = uint32_t(per);
+        if (b->knobs.emit_per_block) F.per_block = std::min<uint32_t>(b->knobs.emit_per_block, vpt::kEmitFlatMaxBlock);
+        F.n_blocks = (n_sentences + F.per_block - 1) / F.per_block;
+    }
+    const size_t words = size_t(F.n_blocks) + 1;
+    if (words > b->emit_state_cap) {
+        const size_t cap = std::max(words + words / 2, size_t(4096));
+        (void)hipFree(b->d_emit_state);   // (waits for the device)
+        b->d_emit_state = nullptr; b->emit_state_cap = 0;
+        VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_emit_state), 2 * cap * sizeof(uint64_t)));
+        VPT_HIP(hipMemsetAsync(b->d_emit_state, 0, 2 * cap * sizeof(uint64_t), stream));   // (in front of the kernel on ITS stream: a plain hipMemset is not ordered with a non-blocking stream)
+        b->emit_state_cap = cap; b->emit_dirty[0] = b->emit_dirty[1] = 0; b->emit_flip = 0;
+    }
+    F.state = b->d_emit_state + size_t(b->emit_flip) * b->emit_state_cap;
+    F.clear = b->d_emit_state + size_t(b->emit_flip ^ 1) * b->emit_state_cap;
+    F.clear_n = b->emit_dirty[b->emit_flip ^ 1];
+    F.total_out = total_out; F.chain_in = chain_in; F.chain_out = chain_out;
+    b->emit_dirty[b->emit_flip ^ 1] = 0; b->emit_dirty[b->emit_flip] = words;
+    b->emit_flip ^= 1;
+    *F_out = F;
+    return VPT_OK;
+}
+}  // namespace
+
 namespace vptc {
 vpt_status emit_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                        const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels,
@@ -326,42 +366,51 @@ vpt_status emit_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_ut
         E.records = b->d_tag_records; E.rec_str = b->d_rec_str; E.run_pref = b->d_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;
         E.n_tags = p->n_tags; E.str_bytes = p->dtag.str_bytes;
     }
-    // A WORKGROUP per run of sentences (emit_flat_kernel, round 5; a wave per block of 2 K chars before): 5 K chars when the batch is small (the
-    // chip wants a thousand workgroups and more), up to 20 K on a big one -- fewer look-backs and size passes per byte (measured,
-    // profiles/r05_h_*, r05_k_*, r06_t_*: configs[2] 2.03 ms at 128 sentences, 1.80 at 256; tagged configs[4] 2.39 / 2.10 / 2.04 at 5 K / 10 K / 20 K
-    // chars; without tags up to 32 K chars: 512 sentences of 64, `r06_zv_*`); at most 512 sentences (two a thread).  With tags: a whole multiple of fill_tags' runs, so that a workgroup's records are run_pref[a] .. run_pref[b].
     vpt::EmitFuse F{};
     {
-        const uint64_t chars = total_boundaries + n_sentences;
-        const uint64_t auto_run = std::min<uint64_t>(std::max<uint64_t>(chars / (uint64_t(16) * std::max<uint32_t>(p->n_cus, 64)), 5120), E.records ? 20480 : 32768);
-        const uint64_t target = auto_run;
-        uint64_t per = std::min<uint64_t>(std::max<uint64_t>((target * n_sentences + chars / 2) / chars, 1), vpt::kEmitFlatMaxBlock);   // round(target / mean chars per sentence)
-        if (E.records && E.run_sent <= vpt::kEmitFlatMaxBlock)
-            per = std::min<uint64_t>(std::max<uint64_t>((per + E.run_sent / 2) / E.run_sent, 1) * E.run_sent, (vpt::kEmitFlatMaxBlock / E.run_sent) * E.run_sent);
-        F.per_block = uint32_t(per);
-        if (b->knobs.emit_per_block) F.per_block = std::min<uint32_t>(b->knobs.emit_per_block, vpt::kEmitFlatMaxBlock);
-        F.n_blocks = (n_sentences + F.per_block - 1) / F.per_block;
+        const vpt_status st = plan_runs(p, b, n_sentences, total_boundaries, E.records != nullptr, E.run_sent, total_out, chain_in, chain_out, stream, &F);
+        if (st != VPT_OK) return st;
     }
-    const size_t words = size_t(F.n_blocks) + 1;
-    if (words > b->emit_state_cap) {
-        const size_t cap = std::max(words + words / 2, size_t(4096));
-        (void)hipFree(b->d_emit_state);   // (waits for the device)
-        b->d_emit_state = nullptr; b->emit_state_cap = 0;
-        VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_emit_state), 2 * cap * sizeof(uint64_t)));
-        VPT_HIP(hipMemsetAsync(b->d_emit_state, 0, 2 * cap * sizeof(uint64_t), stream));   // (in front of the kernel on ITS stream: a plain hipMemset is not ordered with a non-blocking stream)
-        b->emit_state_cap = cap; b->emit_dirty[0] = b->emit_dirty[1] = 0; b->emit_flip = 0;
-    }
-    F.state = b->d_emit_state + size_t(b->emit_flip) * b->emit_state_cap;
-    F.clear = b->d_emit_state + size_t(b->emit_flip ^ 1) * b->emit_state_cap;
-    F.clear_n = b->emit_dirty[b->emit_flip ^ 1];
-    F.total_out = total_out; F.chain_in = chain_in; F.chain_out = chain_out;
-    b->emit_dirty[b->emit_flip ^ 1] = 0; b->emit_dirty[b->emit_flip] = words;
-    b->emit_flip ^= 1;
     VPT_HIP(vpt::launch_emit_tokenized(E, F, stream));
     b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
     return VPT_OK;
 }
+// The token spans of a batch whose labels are on the device (kernels_tokens.hip), on the writer's runs; total_out / chain_in / chain_out as for
+// the writer (vpt_token_stream_batch's chunks write ONE array of end-points).
+vpt_status spans_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                        const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels,
+                        uint64_t* d_token_offsets, uint32_t* d_token_ends, uint64_t capacity, hipStream_t stream, uint64_t* total_out,
+                        const uint64_t* chain_in, uint64_t* chain_out) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!d_token_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    VPT_HIP(hipSetDevice(p->device));
+    if (n_sentences == 0) {
+        VPT_HIP(hipMemsetAsync(d_token_offsets, 0, sizeof(uint64_t), stream));
+        b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+        return VPT_OK;
+    }
+    if (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels) || (capacity && !d_token_ends))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    vpt::SpanParams S{};
+    S.text = d_utf8; S.boff = d_byte_offsets; S.ooff = d_out_offsets; S.labels = d_labels; S.n_sent = n_sentences;
+    S.total_boundaries = total_boundaries; S.token_ends = d_token_ends; S.token_offsets = d_token_offsets; S.capacity = capacity;
+    S.status = b->d_ctrl;
+    vpt::EmitFuse F{};
+    const vpt_status st = plan_runs(p, b, n_sentences, total_boundaries, false, 0, total_out, chain_in, chain_out, stream, &F);
+    if (st != VPT_OK) return st;
+    VPT_HIP(vpt::launch_token_spans(S, F, stream));
+    b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+    return VPT_OK;
+}
 }  // namespace vptc
+
+// vaporetto_tantivy/src/lib.rs:183-192 for a batch whose labels are on the device
+vpt_status vpt_token_spans_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                        const uint64_t* d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t* d_labels,
+                                        uint64_t* d_token_offsets, uint32_t* d_token_ends, uint64_t capacity, void* hip_stream) {
+    return spans_device(p, b, d_utf8, d_byte_offsets, d_out_offsets, n_documents, total_boundaries, d_labels, d_token_offsets, d_token_ends, capacity,
+                        static_cast<hipStream_t>(hip_stream), nullptr, nullptr, nullptr);
+}
 
 vpt_status vpt_write_tokenized_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                             const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,

@@ -193,7 +193,7 @@ vpt_status vpt_predict_batch(const vpt_predictor* p, const uint8_t* utf8, const 
 
 vpt_status vpt_predict_batch_flags(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
                                    int32_t* scores_out, uint8_t* labels_out, const uint64_t* out_offsets, unsigned flags) {
-    if (flags & ~unsigned(VPT_FLAG_ALL)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (n_sentences == 0) return VPT_OK;
     if (!utf8 || !byte_offsets || !out_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -332,8 +332,10 @@ namespace {
 // each chunk's text placed by an upper bound and closed up by the copies out (1.07); kernels storing STRAIGHT into a pinned caller buffer
 // (their stores cross PCIe at 27 .. 34 GB/s against the copy engine's 56: 1.15 - 1.29); every kernel of every chunk on one stream (0.97).
 // `text` = the batch's first byte; byte_offsets are the caller's (relative to byte_offsets[0]).
+// ends_out (vpt_token_stream_batch): the same pipeline with the span kernel in the writer's place -- the chunks write ONE array of token end-points
+// (four bytes each; text_capacity counts them) and the documents' ranges in it instead of text and text offsets.
 vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t* text, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
-                          uint64_t max_bytes, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out) {
+                          uint64_t max_bytes, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out, uint32_t* ends_out = nullptr) {
     (void)max_bytes;
     const uint64_t t0 = byte_offsets[0];
     const size_t nbytes = size_t(byte_offsets[n_sentences] - t0);
@@ -374,8 +376,9 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         b->off_cap = std::min(cap, cap2);
     }
     if ((st = grow(&b->d_chain, &b->chain_cap, max_chunks + 2)) != VPT_OK) return st;
-    const uint64_t out_cap = uint64_t(nbytes) * 3 + 16;
-    if ((st = grow(&b->d_tok, &b->tok_cap, size_t(out_cap) + 16)) != VPT_OK) return st;
+    const uint64_t out_cap = ends_out ? uint64_t(nbytes) : uint64_t(nbytes) * 3 + 16;   // (an end-point per char at most, a char per byte at most)
+    if (ends_out) { if ((st = grow(&b->d_tends, &b->tends_cap, size_t(out_cap) + 16)) != VPT_OK) return st; }
+    else if ((st = grow(&b->d_tok, &b->tok_cap, size_t(out_cap) + 16)) != VPT_OK) return st;
     if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 2)) != VPT_OK) return st;
     uint8_t* const d_out = b->d_tok;
     uint64_t* const d_off_out = b->d_toff;
@@ -429,7 +432,8 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         const uint64_t end = h_end[k];
         if (end > out_cap || end < at) { out_of_range = true; return VPT_OK; }   // the device found the inputs inconsistent and says so below
         if (end > text_capacity) { too_small = true; return VPT_OK; }
-        if (end > at) VPT_HIP(hipMemcpyAsync(text_out + at, d_out + at, size_t(end - at), hipMemcpyDeviceToHost, s_out));
+        if (end > at && ends_out) VPT_HIP(hipMemcpyAsync(ends_out + at, b->d_tends + at, 4 * size_t(end - at), hipMemcpyDeviceToHost, s_out));
+        else if (end > at) VPT_HIP(hipMemcpyAsync(text_out + at, d_out + at, size_t(end - at), hipMemcpyDeviceToHost, s_out));
         VPT_HIP(hipMemcpyAsync(text_offsets_out + chunks[k].a, d_off_out + chunks[k].a, 8 * (chunks[k].n + 1), hipMemcpyDeviceToHost, s_out));
         at = end;
         return VPT_OK;
@@ -449,7 +453,8 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         st = predict_device_impl(p, w, b->d_text, d_boff_k, d_ooff_k, c.n, c.nby - c.n /* boundaries of the chunk, at most */, c.mb, nullptr, w->d_tlab, s_prep);
         w->split_stream = nullptr; w->split_event = nullptr;
         if (st != VPT_OK) return st;
-        st = emit_device(p, w, b->d_text, d_boff_k, d_ooff_k, c.n, c.nby - c.n, w->d_tlab, false, d_out, out_cap, d_off_out + c.a, s, h_end + k, b->d_chain + k, b->d_chain + k + 1);
+        if (ends_out) st = spans_device(p, w, b->d_text, d_boff_k, d_ooff_k, c.n, c.nby - c.n, w->d_tlab, d_off_out + c.a, b->d_tends, out_cap, s, h_end + k, b->d_chain + k, b->d_chain + k + 1);
+        else st = emit_device(p, w, b->d_text, d_boff_k, d_ooff_k, c.n, c.nby - c.n, w->d_tlab, false, d_out, out_cap, d_off_out + c.a, s, h_end + k, b->d_chain + k, b->d_chain + k + 1);
         if (st != VPT_OK) return st;
         VPT_HIP(hipEventRecord(b->chunk_ev[3 * k + 2], s));
         if ((st = copy_in_next()) != VPT_OK) return st;
@@ -474,7 +479,7 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         for (vpt_batch* w : ws) VPT_HIP(hipMemset(w->d_ctrl, 0, sizeof(uint32_t)));
         return status_from_bits(bits);
     }
-    if (too_small) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text");
+    if (too_small) return fail(VPT_INVALID_ARGUMENT, ends_out ? "InvalidArgumentError: capacity: smaller than the number of tokens" : "InvalidArgumentError: text_capacity: smaller than the tokenized text");
     if (out_of_range || h_end[chunks.size() - 1] > out_cap) return fail(VPT_RUNTIME_ERROR, "vpt_tokenize_batch: the output size is out of range");
     return VPT_OK;
 }
@@ -626,6 +631,86 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
     text_offsets_out[0] = 0;
     for (size_t k = 1; k < chunks.size(); ++k)
         for (size_t j = 1; j <= chunks[k].n; ++j) text_offsets_out[chunks[k].a + j] += base[k];
+    return VPT_OK;
+}
+
+// vaporetto_tantivy/src/lib.rs:183-192 for a batch in host buffers, on the caller's labels
+vpt_status vpt_token_spans_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                 const uint64_t* out_offsets, const uint8_t* labels, uint64_t* token_offsets_out, uint32_t* token_ends_out,
+                                 uint64_t capacity) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    token_offsets_out[0] = 0;
+    if (n_documents == 0) return VPT_OK;
+    if (!utf8 || !byte_offsets || !out_offsets || (capacity && !token_ends_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (out_offsets[n_documents] != out_offsets[0] && !labels) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: must not be NULL");
+    for (size_t i = 0; i < n_documents; ++i)
+        if (byte_offsets[i + 1] > byte_offsets[i] && byte_offsets[i + 1] - byte_offsets[i] > 0xFFFFFFFFull)
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: a document must be shorter than 2^32 bytes");
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st = acquire(p, &w);
+    if (st != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    uint64_t total_b = 0;
+    if ((st = stage(b, utf8, byte_offsets, out_offsets, n_documents, labels, &total_b, nullptr, nullptr)) != VPT_OK) return st;
+    // the device buffer holds every end-point there can be (one per char), so a capacity that is too small is found here and nothing is
+    // copied past it
+    const uint64_t d_cap = total_b + n_documents;
+    if ((st = grow(&b->d_tends, &b->tends_cap, size_t(d_cap) + 16)) != VPT_OK) return st;
+    if ((st = grow(&b->d_toff, &b->toff_cap, n_documents + 1)) != VPT_OK) return st;
+    st = spans_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_documents, total_b, b->d_labels, b->d_toff, b->d_tends, d_cap, b->own_stream, nullptr, nullptr, nullptr);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(token_offsets_out, b->d_toff, 8 * (n_documents + 1), hipMemcpyDeviceToHost));
+    const uint64_t total = token_offsets_out[n_documents];
+    if (total > capacity) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: smaller than the number of tokens");
+    if (total) VPT_HIP(hipMemcpy(token_ends_out, b->d_tends, 4 * size_t(total), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
+// VaporettoTokenizer::token_stream (vaporetto_tantivy/src/lib.rs:160-192) for a batch of documents: only the text goes in, the spans come back.
+vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                  unsigned wsconst_flags, uint64_t* token_offsets_out, uint32_t* token_ends_out, uint64_t capacity) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (wsconst_flags & ~0x7Eu) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
+    token_offsets_out[0] = 0;
+    if (n_documents == 0) return VPT_OK;
+    if (!utf8 || !byte_offsets || (capacity && !token_ends_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    // an empty document has no tokens (lib.rs:161-169) and never reaches the device: the offsets of the others, which delimit the same text
+    std::vector<uint64_t> docs;
+    docs.reserve(n_documents + 1);
+    docs.push_back(byte_offsets[0]);
+    uint64_t max_bytes = 0;
+    for (size_t i = 0; i < n_documents; ++i) {
+        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+        if (byte_offsets[i + 1] == byte_offsets[i]) continue;
+        max_bytes = std::max<uint64_t>(max_bytes, byte_offsets[i + 1] - byte_offsets[i]);
+        docs.push_back(byte_offsets[i + 1]);
+    }
+    if (max_bytes > 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: a document must be shorter than 2^32 bytes");
+    const size_t n = docs.size() - 1;
+    if (n == 0) { std::fill(token_offsets_out, token_offsets_out + n_documents + 1, uint64_t(0)); return VPT_OK; }
+    if (capacity < n) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: smaller than the number of tokens");   // (a token per document at least)
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st = acquire(p, &w);
+    if (st != VPT_OK) return st;
+    const unsigned flags = VPT_FLAG_KYTEA_FULLWIDTH | VPT_FLAG_SPLIT_LINEBREAKS | VPT_FLAG_LINEBREAKS_FIRST | wsconst_flags;
+    std::vector<uint64_t> packed;   // (only with empty documents: the ranges of the others)
+    uint64_t* const offs = n == n_documents ? token_offsets_out : (packed.resize(n + 1), packed.data());
+    offs[0] = 0;
+    st = tokenize_chunked(p, w.b, utf8 + docs[0], docs.data(), n, flags, max_bytes, nullptr, capacity, offs, token_ends_out);
+    if (st != VPT_OK) return st;
+    if (n != n_documents) {
+        size_t k = 0;
+        for (size_t i = 0; i < n_documents; ++i) {
+            token_offsets_out[i] = packed[k];
+            if (byte_offsets[i + 1] != byte_offsets[i]) ++k;
+        }
+        token_offsets_out[n_documents] = packed[n];
+    }
     return VPT_OK;
 }
 

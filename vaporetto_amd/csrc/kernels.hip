@@ -289,8 +289,9 @@ __device__ __forceinline__ void process_tile(const ScoreParams& P, const TileMem
             uint32_t label = y > 0 ? 1u : 0u;
             if (P.post) {   // KyteaWsConstFilter / SplitLinebreaksFilter on the label
                 const uint32_t t1 = M.typ[p], t2 = M.typ[p + 1], ca = M.sym[p], cb = M.sym[p + 1];
-                if (t1 == t2 && ((P.post >> t1) & 1u) && t1 >= 1 && t1 <= 6) label = 0;
-                if ((P.post & 0x80u) && (ca == 0x0Au || ca == 0x0Du || cb == 0x0Au || cb == 0x0Du)) label = 1;
+                const bool same = t1 == t2 && ((P.post >> t1) & 1u) && t1 >= 1 && t1 <= 6;
+                if (same) label = 0;
+                if ((P.post & 0x80u) && (ca == 0x0Au || ca == 0x0Du || cb == 0x0Au || cb == 0x0Du) && !(same && (P.post & 0x100u))) label = 1;   // (bit 8, VPT_FLAG_LINEBREAKS_FIRST: the wsconst filters have the last word)
             }
             P.labels[o] = uint8_t(label);
         }

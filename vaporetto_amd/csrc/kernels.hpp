@@ -93,7 +93,7 @@ struct ScoreParams {
     uint32_t* cps_out;          // specialised kernel, optional: the batch's chars flat (char g of sentence i at ooff[i] + i + g) as scored
                                 // scalar value | CharacterType << 24 -- what decode_chars_kernel makes for the tag kernel
     uint64_t total_chars;       // what cps_out holds: total boundaries + sentences of the call
-    uint32_t post;              // label post-filters: bits 1..6 KyteaWsConstFilter per CharacterType, bit 7 SplitLinebreaksFilter
+    uint32_t post;              // label post-filters: bits 1..6 KyteaWsConstFilter per CharacterType, bit 7 SplitLinebreaksFilter, bit 8: that one FIRST
     uint32_t force_window_table;// experiment knob (read when the predictor is made): the 8^(2W) type table although type rows exist
     uint32_t debug;             // profiling ablation bits (VPT_DEBUG_ABLATE env, 0 in production)
     uint64_t* prof;             // per-phase shader-cycle counters (VPT_PROFILE_PHASES env), else nullptr
@@ -209,6 +209,19 @@ hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t c
 hipError_t launch_expand_tags(const uint4* records, const int32_t* rec_tags, const uint64_t* n_records, uint32_t n_tags, uint64_t total_chars, int32_t* tags,
                               uint32_t n_cus, hipStream_t stream);
 hipError_t launch_emit_tokenized(const EmitParams& P, const EmitFuse& F, hipStream_t stream);
+// token spans (kernels_tokens.hip): vaporetto_tantivy's boundary_pos per document (vaporetto_tantivy/src/lib.rs:183-192), the writer's runs
+struct SpanParams {
+    const uint8_t* text;
+    const uint64_t* boff;       // [S+1]
+    const uint64_t* ooff;       // [S+1]
+    const uint8_t* labels;      // [total boundaries] 0 / 1
+    uint64_t n_sent, total_boundaries;
+    uint32_t* token_ends;       // [capacity] byte offset, from the document's first byte, behind every token
+    uint64_t* token_offsets;    // [S+1] the documents' ranges in token_ends
+    uint64_t capacity;
+    uint32_t* status;
+};
+hipError_t launch_token_spans(const SpanParams& P, const EmitFuse& F, hipStream_t stream);
 // vpt_count_boundaries on the device: ooff_out[S+1]; *max_chars (atomicMax) = the longest sentence in chars; text_bytes_hint: the batch's text
 // bytes when the host knows them (0: not), which sizes the workgroups' shares
 hipError_t launch_count_boundaries(const uint8_t* text, const uint64_t* boff, uint64_t n_sent, uint64_t* ooff_out, uint64_t* scan_part, uint32_t* status,

@@ -825,8 +825,9 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
         if (lb) {
             if (post) {   // wave-uniform: KyteaWsConstFilter / SplitLinebreaksFilter on the label
                 const uint32_t t1 = (x >> 16) & 7u, t2 = (x2 >> 16) & 7u;
-                if (t1 == t2 && ((post >> t1) & 1u) && t1 != 0 && t1 != 7) label = 0;
-                if ((post & 0x80u) && ((x | x2) & kSymLinebreak)) label = 1;
+                const bool same = t1 == t2 && ((post >> t1) & 1u) && t1 != 0 && t1 != 7;
+                if (same) label = 0;
+                if ((post & 0x80u) && ((x | x2) & kSymLinebreak) && !(same && (post & 0x100u))) label = 1;   // (bit 8, VPT_FLAG_LINEBREAKS_FIRST: the wsconst filters have the last word)
             }
             lb[o] = uint8_t(label);
         }
