@@ -361,6 +361,45 @@ vpt_status vpt_tokenize_batch(const vpt_predictor *p, const uint8_t *utf8, const
                               uint64_t text_capacity, uint64_t *text_offsets_out);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The `predict` CLI's stdout for a batch of lines, with --scores and --tag-scores     (predict/src/main.rs:66-93, 122-176)
+ *
+ * Line i's bytes are out[listing_offsets[i] .. listing_offsets[i + 1]): with N the text as it was scored (KyteaFullwidthFilter's image under
+ * VPT_FLAG_KYTEA_FULLWIDTH, main.rs:154; else the line itself),
+ *   T             write_tokenized_text of the line with the labels (main.rs:135, 161-165), with "/tag" suffixes under VPT_LISTING_TAGGED;
+ *   scores block  VPT_LISTING_SCORES, print_scores (main.rs:66-75): "{i}:{N[i]}{N[i+1]} {score}\n" per boundary, then "\n";
+ *   tag block     VPT_LISTING_TAG_SCORES, print_tag_scores (main.rs:77-93): per token of N its surface, unescaped, then per slot of its tag model
+ *                 "\t" and "tag:score" joined by "," (Token::tag_candidates, sentence.rs:1228-1250: score 0 for a slot with one candidate;
+ *                 the LAST tag model of a repeated token, predictor.rs:466-478), "\n"; then "\n".  Tags are written raw.
+ * in the order  T "\n" [scores block] [tag block]  (main.rs:154-176), or with VPT_LISTING_NO_NORM_ORDER  T [scores block] "\n" [tag block]  (the
+ * --no-norm loop, main.rs:129-144: no newline between T and the first score line).
+ * Formatting runs on the device (kernels_listing.hip: a count pass, a prefix sum, a write pass; the bytes depend on the input alone).
+ * VPT_LISTING_TAG_SCORES or VPT_LISTING_TAGGED on a predictor created with predict_tags == 0 is VPT_INVALID_ARGUMENT (the reference panics).
+ * capacity: with B text bytes, C chars, S lines and b = C - S boundaries,
+ *     3 B + S                                                  T and its newline            (sentence.rs:850-886: every byte escaped, a space per char)
+ *   + C * vpt_predictor_max_tag_suffix                         with VPT_LISTING_TAGGED
+ *   + 32 b + S                                                 with VPT_LISTING_SCORES: a line is at most 10 + 1 + 4 + 4 + 1 + 11 + 1 = 32 bytes (main.rs:70)
+ *   + 3 B + C + S + C * vpt_predictor_max_tag_listing          with VPT_LISTING_TAG_SCORES: the chars of N (a fullwidth char has 3 bytes), a "\n" per
+ *                                                              token and block, the candidates of a token (main.rs:79-91)
+ * always suffices.  Too small a capacity, offsets that do not match the text and VPT_BOUNDARY_UNKNOWN among the labels are VPT_INVALID_ARGUMENT;
+ * nothing is written outside the caller's arrays.
+ * vpt_predict_listing_batch: host buffers.  labels == NULL: Sentence::from_raw's checks, Predictor::predict and the post-filters of `flags` (any
+ *   VPT_FLAG_*) run here.  labels != NULL: the caller's scores (needed with VPT_LISTING_SCORES) and labels, laid out as vpt_count_boundaries
+ *   lays them out from 0, are listed -- the path of a host filter such as ConcatGraphemeClustersFilter between predict and the listing; of
+ *   `flags` only VPT_FLAG_KYTEA_FULLWIDTH then matters.  One call holds its batch on the device: callers with streams cut them (the CLI does).
+ * vpt_predict_listing_batch_device: device pointers, asynchronous on hip_stream, errors at vpt_batch_sync; d_scores / d_labels as
+ *   vpt_predict_batch_device left them (possibly edited), VPT_FLAG_KYTEA_FULLWIDTH from vpt_batch_set_flags; text_bytes: the batch's text bytes or
+ *   an upper bound (sizes the workspace's copy of T; understated: "text_capacity" at the sync).  At most 2^32 - 257 chars per call. */
+enum { VPT_LISTING_SCORES = 1, VPT_LISTING_TAG_SCORES = 2, VPT_LISTING_TAGGED = 4, VPT_LISTING_NO_NORM_ORDER = 8, VPT_LISTING_ALL = 15 };
+vpt_status vpt_predictor_max_tag_listing(const vpt_predictor *p, uint32_t *n_bytes);
+vpt_status vpt_predict_listing_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, unsigned flags,
+                                     unsigned listing, const int32_t *scores, const uint8_t *labels, uint8_t *out, uint64_t capacity,
+                                     uint64_t *listing_offsets_out);
+vpt_status vpt_predict_listing_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                            const uint64_t *d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint64_t text_bytes,
+                                            const int32_t *d_scores, const uint8_t *d_labels, unsigned listing, uint8_t *d_out, uint64_t capacity,
+                                            uint64_t *d_listing_offsets_out, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * VaporettoTokenizer::token_stream over a batch of documents                  (vaporetto_tantivy/src/lib.rs:157-229)
  *
  * What an indexer takes from the tokenizer: per document the byte span of every token IN THE CALLER'S TEXT, as CSR:

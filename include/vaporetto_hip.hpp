@@ -269,6 +269,31 @@ public:
         return out;
     }
 
+    // The `predict` CLI's stdout per line with --scores / --tag-scores (predict/src/main.rs:66-93, 122-176), formatted on the device:
+    // listing = VPT_LISTING_* bits, flags = VPT_FLAG_* (vpt_predict_listing_batch).
+    std::vector<std::string> predict_listing(const std::vector<std::string>& lines, unsigned listing, unsigned flags = VPT_FLAG_KYTEA_FULLWIDTH) const {
+        std::vector<std::string> out;
+        if (lines.empty()) return out;
+        std::string text;
+        std::vector<uint64_t> boff(1, 0);
+        size_t chars = 0;
+        for (const std::string& l : lines) { text += l; boff.push_back(text.size()); }
+        for (unsigned char c : text) chars += (c & 0xC0) != 0x80;
+        uint32_t sfx = 0, cand = 0;
+        if (listing & VPT_LISTING_TAGGED) detail::check(vpt_predictor_max_tag_suffix(raw_->raw, &sfx));
+        if (listing & VPT_LISTING_TAG_SCORES) detail::check(vpt_predictor_max_tag_listing(raw_->raw, &cand));
+        const size_t S = lines.size(), B = text.size();
+        size_t cap = 3 * B + S + chars * sfx;
+        if (listing & VPT_LISTING_SCORES) cap += 32 * (chars - S) + S;
+        if (listing & VPT_LISTING_TAG_SCORES) cap += 3 * B + chars + S + chars * size_t(cand);
+        std::vector<uint8_t> buf(cap + 16);
+        std::vector<uint64_t> off(S + 1);
+        detail::check(vpt_predict_listing_batch(raw_->raw, reinterpret_cast<const uint8_t*>(text.data()), boff.data(), S, flags, listing, nullptr, nullptr,
+                                                buf.data(), cap, off.data()));
+        for (size_t i = 0; i < S; ++i) out.emplace_back(buf.begin() + off[i], buf.begin() + off[i + 1]);
+        return out;
+    }
+
 private:
     friend class Sentence;
     std::shared_ptr<detail::Shared> raw_;

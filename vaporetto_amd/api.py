@@ -621,6 +621,90 @@ class Predictor:
             _raise(st)
         return tags[:, :nt]
 
+    def max_tag_listing(self) -> int:
+        """vpt_predictor_max_tag_listing: the most bytes the candidates of one token take in the tag block of a listing."""
+        v = C.c_uint32(0)
+        st = _lib.load().vpt_predictor_max_tag_listing(self._h, C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
+    def listing_capacity(self, text_bytes: int, n_chars: int, n_lines: int, listing: int) -> int:
+        """The capacity bound include/vaporetto_hip.h documents for vpt_predict_listing_batch."""
+        cap = 3 * text_bytes + n_lines
+        if listing & _lib.VPT_LISTING_TAGGED:
+            cap += n_chars * self.max_tag_suffix()
+        if listing & _lib.VPT_LISTING_SCORES:
+            cap += 32 * (n_chars - n_lines) + n_lines
+        if listing & _lib.VPT_LISTING_TAG_SCORES:
+            cap += 3 * text_bytes + n_chars + n_lines + n_chars * self.max_tag_listing()
+        return cap
+
+    def predict_listing_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, listing: int, flags: int = 0,
+                               scores: Optional[np.ndarray] = None, labels: Optional[np.ndarray] = None, capacity: Optional[int] = None):
+        """vpt_predict_listing_batch over a packed batch: (uint8 bytes, uint64 [S+1] offsets) -- what the `predict` CLI writes for these lines
+        with --scores / --tag-scores (predict/src/main.rs:66-93, 122-176), formatted on the device.  `listing`: VPT_LISTING_* bits; `labels`
+        (and `scores`): list these instead of predicting (a host filter ran between predict and the listing)."""
+        L = _lib.load()
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S = len(byte_offsets) - 1
+        if capacity is None:
+            n_chars = int(np.count_nonzero((utf8 & 0xC0) != 0x80))
+            capacity = self.listing_capacity(len(utf8), n_chars, S, listing)
+        out = np.zeros(max(capacity, 1), dtype=np.uint8)
+        offs = np.zeros(S + 1, dtype=np.uint64)
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+            if len(labels) == 0:
+                labels = np.zeros(1, dtype=np.uint8)
+            if scores is not None:
+                scores = np.ascontiguousarray(scores, dtype=np.int32)
+        st = L.vpt_predict_listing_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, int(flags), int(listing),
+                                         scores.ctypes.data if (labels is not None and scores is not None and len(scores)) else None,
+                                         labels.ctypes.data if labels is not None else None, out.ctypes.data, capacity, offs.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return out[:int(offs[S])], offs
+
+    def predict_listing(self, texts: Sequence[str], scores: bool = False, tag_scores: bool = False, tagged: bool = False, fullwidth: bool = True,
+                        wsconst: Sequence = (), no_norm_order: bool = False, split_linebreaks: bool = False) -> List[bytes]:
+        """predict_listing_arena cut into one bytes object per line (a convenience for callers that want the lines apart; the CLI writes
+        the arena as it is)."""
+        if not texts:
+            return []
+        out, offs = self.predict_listing_arena(texts, scores=scores, tag_scores=tag_scores, tagged=tagged, fullwidth=fullwidth, wsconst=wsconst,
+                                               no_norm_order=no_norm_order, split_linebreaks=split_linebreaks)
+        raw = out.tobytes()
+        return [raw[int(offs[i]):int(offs[i + 1])] for i in range(len(texts))]
+
+    def predict_listing_arena(self, texts: Sequence[str], scores: bool = False, tag_scores: bool = False, tagged: bool = False,
+                              fullwidth: bool = True, wsconst: Sequence = (), no_norm_order: bool = False, split_linebreaks: bool = False):
+        """The `predict` CLI's output for these lines (predict/src/main.rs:122-176) as the device made it: (uint8 arena, uint64 [S+1] offsets
+        of the lines in it).  Per line T, the --scores block and the --tag-scores block, in the normalising loop's order or (no_norm_order)
+        the --no-norm loop's.  `wsconst` as for tokenize: "G" takes the three-call path (predict, ConcatGraphemeClustersFilter on the host,
+        the listing of the filtered labels)."""
+        if not texts:
+            return np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64)
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        listing = ((_lib.VPT_LISTING_SCORES if scores else 0) | (_lib.VPT_LISTING_TAG_SCORES if tag_scores else 0) |
+                   (_lib.VPT_LISTING_TAGGED if tagged else 0) | (_lib.VPT_LISTING_NO_NORM_ORDER if no_norm_order else 0))
+        graphemes = any(isinstance(t, str) and t == "G" for t in wsconst)
+        types = [int(t) for t in wsconst if not (isinstance(t, str) and t == "G")]
+        if graphemes:
+            sc, labels, ooff = self.predict_packed(utf8, boff, fullwidth=fullwidth, wsconst=tuple(types), split_linebreaks=split_linebreaks)
+            norm = KyteaFullwidthFilter()
+            ConcatGraphemeClustersFilter().filter_packed([norm.filter(t) for t in texts] if fullwidth else texts, ooff, labels)
+            out, offs = self.predict_listing_packed(utf8, boff, listing, flags=_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, scores=sc, labels=labels)
+        else:
+            flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0
+            for t in types:
+                flags |= _lib.VPT_FLAG_WSCONST(t)
+            if split_linebreaks:
+                flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
+            out, offs = self.predict_listing_packed(utf8, boff, listing, flags=flags)
+        return out, offs
+
     def tokenize_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, tagged: bool = False, flags: int = 0,
                         text_out: Optional[np.ndarray] = None, offsets_out: Optional[np.ndarray] = None):
         """vpt_tokenize_batch over a packed batch: (uint8 tokenized text, uint64 [S+1] offsets).  `text_out` / `offsets_out` may be
@@ -1094,6 +1178,16 @@ class DeviceBatch:
         """Device-resident token spans of the batch for the labels at d_labels (vpt_token_spans_batch_device); enqueues and returns."""
         st = _lib.load().vpt_token_spans_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_documents, total_boundaries,
                                                       d_labels or None, d_token_offsets, d_token_ends or None, capacity, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def predict_listing(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, text_bytes: int, d_scores: int,
+                        d_labels: int, listing: int, d_out: int, capacity: int, d_listing_offsets: int, stream: int = 0) -> None:
+        """The predict CLI's listing of the batch from the scores and labels on the device (vpt_predict_listing_batch_device); enqueues and
+        returns."""
+        st = _lib.load().vpt_predict_listing_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_sentences, total_boundaries, text_bytes,
+                                                          d_scores or None, d_labels or None, int(listing), d_out or None, capacity,
+                                                          d_listing_offsets, stream)
         if st != _lib.VPT_OK:
             _raise(st)
 

@@ -429,6 +429,102 @@ vpt_status vpt_write_tagged_batch_device(const vpt_predictor* p, vpt_batch* b, c
                        d_text_offsets_out, static_cast<hipStream_t>(hip_stream));
 }
 
+// The predict CLI's stdout for a batch whose scores and labels are on the device (predict/src/main.rs:66-93, 122-176): fill_tags (with its scores
+// and tag models when the tag block is wanted), the writer's T into the workspace, then the listing's count / scan / write (kernels_listing.hip).
+vpt_status vpt_predict_listing_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                            const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint64_t text_bytes,
+                                            const int32_t* d_scores, const uint8_t* d_labels, unsigned listing, uint8_t* d_out, uint64_t capacity,
+                                            uint64_t* d_listing_offsets_out, void* hip_stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (listing & ~unsigned(VPT_LISTING_ALL)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: listing: unknown bit");
+    if ((listing & (VPT_LISTING_TAG_SCORES | VPT_LISTING_TAGGED)) && !p->predict_tags)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (!d_listing_offsets_out || (capacity && !d_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    VPT_HIP(hipSetDevice(p->device));
+    if (n_sentences == 0) {
+        VPT_HIP(hipMemsetAsync(d_listing_offsets_out, 0, sizeof(uint64_t), stream));
+        b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+        return VPT_OK;
+    }
+    if (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && (!d_labels || ((listing & VPT_LISTING_SCORES) && !d_scores))))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    const uint64_t total_c = total_boundaries + n_sentences;
+    if (total_c >= 0xFFFFFF00ull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: a listing takes fewer than 2^32 - 256 chars per call");
+    const bool with_tags = (listing & (VPT_LISTING_TAG_SCORES | VPT_LISTING_TAGGED)) && p->n_tags > 0;
+    const bool tag_block = (listing & VPT_LISTING_TAG_SCORES) && p->n_tags > 0;
+    vpt_status st;
+    // the workspace of the listing: the elements' sizes / positions, the scan's state, a flag word, and the checked copy of the offsets that every
+    // launch below takes (kernels_listing.hip: offsets that decrease never reach fill_tags' runs)
+    vpt::ListingParams L{};
+    L.n_elem = 2 * total_c + n_sentences;
+    const size_t n_part = vpt::scan_part_entries(L.n_elem), n_pos = size_t(L.n_elem) + 2;
+    if ((st = grow(&b->d_lst_pos, &b->lst_pos_cap, n_pos + n_part + 2 + n_sentences + 1)) != VPT_OK) return st;
+    VPT_HIP(hipMemsetAsync(b->d_lst_pos + n_pos, 0, (n_part + 2) * sizeof(uint64_t), stream));
+    uint64_t* const ooff = b->d_lst_pos + n_pos + n_part + 2;
+    VPT_HIP(vpt::launch_listing_offsets(d_out_offsets, n_sentences, total_boundaries, ooff, reinterpret_cast<uint32_t*>(b->d_lst_pos + n_pos + n_part), b->d_ctrl, stream));
+    if (with_tags) {   // Sentence::fill_tags with store_tag_scores (main.rs:113-115, 132-134): leaves the chars in d_cps, the records for the writer
+        if (tag_block) {
+            if ((st = grow(&b->d_tag_scores, &b->tag_scores_cap, size_t(total_c) * p->max_tag_scores + 16)) != VPT_OK) return st;
+            if ((st = grow(&b->d_tag_models, &b->tag_models_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        }
+        st = vpt_fill_tags_scores_batch_device(p, b, d_utf8, d_byte_offsets, ooff, n_sentences, total_boundaries, d_labels, nullptr,
+                                               tag_block ? b->d_tag_scores : nullptr, tag_block ? b->d_tag_models : nullptr, hip_stream);
+        if (st != VPT_OK) return st;
+    } else if (listing & (VPT_LISTING_SCORES | VPT_LISTING_TAG_SCORES)) {
+        if ((st = grow(&b->d_cps, &b->cps_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        const bool fw = (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
+        VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, ooff, n_sentences, total_c, p->d_cinfo + (fw ? 65536 : 0), b->d_cps, nullptr, b->d_ctrl, stream, fw));
+    }
+    const bool tagged = (listing & VPT_LISTING_TAGGED) && p->n_tags > 0;
+    const uint64_t t_cap = 3 * text_bytes + (tagged ? total_c * p->max_tag_suffix : 0) + 16;
+    if ((st = grow(&b->d_tok, &b->tok_cap, size_t(t_cap) + 16)) != VPT_OK) return st;
+    if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 1)) != VPT_OK) return st;
+    st = emit_device(p, b, d_utf8, d_byte_offsets, ooff, n_sentences, total_boundaries, d_labels, tagged, b->d_tok, t_cap, b->d_toff, stream);
+    if (st != VPT_OK) return st;
+    L.cps = b->d_cps; L.ooff = ooff; L.scores = d_scores; L.labels = d_labels; L.n_sent = n_sentences; L.total_boundaries = total_boundaries;
+    L.t_text = b->d_tok; L.t_off = b->d_toff; L.t_cap = t_cap;
+    if (tag_block) {
+        L.tag_models = b->d_tag_models; L.tag_scores = p->max_tag_scores ? b->d_tag_scores : nullptr; L.score_stride = p->max_tag_scores;
+        L.n_models = p->dtag.n_models; L.n_strings = p->dtag.n_strings;
+        L.models = p->dtag.models; L.slots = p->dtag.slots; L.slot_str = p->dtag.slot_str; L.str_off = p->dtag.str_off; L.str_bytes = p->dtag.str_bytes;
+    }
+    L.flags = listing; L.pos = b->d_lst_pos; L.out = d_out; L.out_offsets = d_listing_offsets_out; L.capacity = capacity; L.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_listing(L, b->d_lst_pos + n_pos, stream));
+    b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+    return VPT_OK;
+}
+
+// The most bytes the candidates of one token take in the tag block: per slot "\t", per candidate its string, ":", up to 11 chars of score and ","
+vpt_status vpt_predictor_max_tag_listing(const vpt_predictor* p, uint32_t* n_bytes) {
+    if (!p || !n_bytes) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_bytes = 0;
+    if (!p->has_tags || p->dtag.n_models == 0) return VPT_OK;
+    const int64_t known = p->max_tag_listing.load(std::memory_order_acquire);
+    if (known >= 0) { *n_bytes = uint32_t(known); return VPT_OK; }
+    VPT_HIP(hipSetDevice(p->device));
+    const PredictorMeta& m = p->meta;
+    std::vector<uint32_t> models(size_t(m.sec_bytes[kSecTagModels] / 4)), slots(size_t(m.sec_bytes[kSecTagSlots] / 4)), slot_str(size_t(m.sec_bytes[kSecTagSlotStr] / 4)),
+        str_off(size_t(m.sec_bytes[kSecTagStrOff] / 4));
+    VPT_HIP(hipMemcpy(models.data(), p->dtag.models, models.size() * 4, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(slots.data(), p->dtag.slots, slots.size() * 4, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(slot_str.data(), p->dtag.slot_str, slot_str.size() * 4, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(str_off.data(), p->dtag.str_off, str_off.size() * 4, hipMemcpyDeviceToHost));
+    uint64_t best = 0;
+    for (uint32_t k = 0; k < p->dtag.n_models && 12ull * k + 9 < models.size(); ++k) {
+        uint64_t n = 0;
+        for (uint32_t s = models[12 * k + 8], e = s + models[12 * k + 9]; s < e && 2ull * s + 1 < slots.size() && s < slot_str.size(); ++s) {
+            n += 1;
+            for (uint32_t c = 0; c < slots[2 * s] && size_t(slot_str[s]) + c + 1 < str_off.size(); ++c)
+                n += uint64_t(str_off[slot_str[s] + c + 1] - str_off[slot_str[s] + c]) + 13;
+        }
+        best = std::max(best, n);
+    }
+    *n_bytes = uint32_t(std::min<uint64_t>(best, 0xFFFFFFFFull));
+    p->max_tag_listing.store(int64_t(*n_bytes), std::memory_order_release);
+    return VPT_OK;
+}
+
 namespace vptc {
 vpt_status count_boundaries_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                  size_t n_sentences, uint64_t* d_out_offsets, void* hip_stream, uint64_t text_bytes_hint) {

@@ -634,6 +634,52 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
     return VPT_OK;
 }
 
+// predict/src/main.rs:122-176 with --scores / --tag-scores for a batch in host buffers: the bytes the CLI writes for these lines.  labels == NULL:
+// Predictor::predict and the post-filters of `flags` run here; else the caller's scores and labels are taken (the three-call path of a host filter).
+vpt_status vpt_predict_listing_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
+                                     unsigned listing, const int32_t* scores, const uint8_t* labels, uint8_t* out, uint64_t capacity,
+                                     uint64_t* listing_offsets_out) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (listing & ~unsigned(VPT_LISTING_ALL)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: listing: unknown bit");
+    if ((listing & (VPT_LISTING_TAG_SCORES | VPT_LISTING_TAGGED)) && !p->predict_tags)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (!listing_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    listing_offsets_out[0] = 0;
+    if (n_sentences == 0) return VPT_OK;
+    if (!utf8 || !byte_offsets || (capacity && !out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    std::vector<uint64_t> ooff(n_sentences + 1);
+    vpt_status st = vpt_count_boundaries(utf8, byte_offsets, n_sentences, ooff.data());   // (empty sentences and NUL are rejected here)
+    if (st != VPT_OK) return st;
+    if (labels && (listing & VPT_LISTING_SCORES) && ooff[n_sentences] && !scores) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: scores: must not be NULL");
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    uint64_t total_b = 0, max_bytes = 0, max_chars = 0;
+    if ((st = stage(b, utf8, byte_offsets, ooff.data(), n_sentences, labels, &total_b, &max_bytes, &max_chars)) != VPT_OK) return st;
+    hipStream_t s = b->own_stream;
+    if (labels) {
+        b->flags = flags & VPT_FLAG_KYTEA_FULLWIDTH;
+        if (scores && total_b) VPT_HIP(hipMemcpyAsync(b->d_scores, scores, 4 * size_t(total_b), hipMemcpyHostToDevice, s));
+    } else {
+        b->flags = flags;
+        b->max_chars = max_chars;
+        if ((st = vpt_predict_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, max_bytes, b->d_scores, b->d_labels, s)) != VPT_OK) return st;
+    }
+    if ((st = grow(&b->d_lst_out, &b->lst_out_cap, size_t(capacity) + 16)) != VPT_OK) return st;
+    if ((st = grow(&b->d_lst_off, &b->lst_off_cap, n_sentences + 1)) != VPT_OK) return st;
+    st = vpt_predict_listing_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, byte_offsets[n_sentences] - byte_offsets[0], b->d_scores,
+                                          b->d_labels, listing, b->d_lst_out, capacity, b->d_lst_off, s);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(listing_offsets_out, b->d_lst_off, 8 * (n_sentences + 1), hipMemcpyDeviceToHost));
+    const uint64_t total = listing_offsets_out[n_sentences];
+    if (total > capacity) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the listing");
+    if (total) VPT_HIP(hipMemcpy(out, b->d_lst_out, size_t(total), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
 // vaporetto_tantivy/src/lib.rs:183-192 for a batch in host buffers, on the caller's labels
 vpt_status vpt_token_spans_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
                                  const uint64_t* out_offsets, const uint8_t* labels, uint64_t* token_offsets_out, uint32_t* token_ends_out,

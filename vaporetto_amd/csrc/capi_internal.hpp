@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <mutex>
 #include <new>
 #include <string>
@@ -302,6 +303,10 @@ struct vpt_batch {
     uint64_t* d_parse_tmp = nullptr; size_t parse_tmp_cap = 0;
     unsigned char* d_eval = nullptr; size_t eval_cap = 0;
     std::vector<hipEvent_t> chunk_ev;                               // vpt_tokenize_batch: one per chunk in flight
+    // vpt_predict_listing_batch[_device]: the elements' sizes / positions and the scan's state (kernels_listing.hip); the host variant's output
+    uint64_t* d_lst_pos = nullptr; size_t lst_pos_cap = 0;
+    uint8_t* d_lst_out = nullptr; size_t lst_out_cap = 0;
+    uint64_t* d_lst_off = nullptr; size_t lst_off_cap = 0;
 };
 
 struct DeviceTags {   // views into the arena
@@ -335,6 +340,7 @@ struct vpt_predictor {
     vpt::PatternTableView ct{}, tt{};
     mutable std::mutex pool_mu;
     mutable std::vector<vpt_batch*> pool;  // idle workspaces for the host-buffer entry points
+    mutable std::atomic<int64_t> max_tag_listing{-1};  // vpt_predictor_max_tag_listing: a constant of the tables, computed by the first call
 };
 
 namespace {
@@ -365,6 +371,7 @@ void batch_release(vpt_batch* b) {
     (void)hipFree(b->d_tags); (void)hipFree(b->d_tag_scores); (void)hipFree(b->d_tag_models); (void)hipFree(b->d_tok); (void)hipFree(b->d_tlab); (void)hipFree(b->d_toff); (void)hipFree(b->d_tends); (void)hipFree(b->d_tag_records); (void)hipFree(b->d_rec_tags); (void)hipFree(b->d_tag_ctl); (void)hipFree(b->d_rec_str); (void)hipFree(b->d_tag_cands); (void)hipFree(b->d_tag_summary);
     (void)hipFree(b->d_types);
     (void)hipFree(b->d_parse_tmp); (void)hipFree(b->d_eval);
+    (void)hipFree(b->d_lst_pos); (void)hipFree(b->d_lst_out); (void)hipFree(b->d_lst_off);
     for (auto& ps : b->pipe) {
         (void)hipFree(ps.text); (void)hipFree(ps.off); (void)hipFree(ps.scores); (void)hipFree(ps.labels);
         if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);

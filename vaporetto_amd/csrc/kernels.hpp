@@ -222,6 +222,34 @@ struct SpanParams {
     uint32_t* status;
 };
 hipError_t launch_token_spans(const SpanParams& P, const EmitFuse& F, hipStream_t stream);
+// the predict CLI's listings (kernels_listing.hip): per line T, the scores block and the tag block in one arena (predict/src/main.rs:66-93, 122-176)
+constexpr uint32_t kListingScores = 1u, kListingTagScores = 2u, kListingTagged = 4u, kListingNoNormOrder = 8u;   // VPT_LISTING_*
+struct ListingParams {
+    const uint32_t* cps;        // decode_chars' words of the batch: the chars as they were scored
+    const uint64_t* ooff;       // [S+1]
+    const int32_t* scores;      // [total boundaries] (kListingScores)
+    const uint8_t* labels;      // [total boundaries] 0 / 1 (kListingTagScores: the writer has checked them)
+    uint64_t n_sent, total_boundaries;
+    uint64_t n_elem;            // 2 * (total boundaries + S) + S: the elements (kernels_listing.hip)
+    const uint8_t* t_text;      // the writer's text for the same batch and labels, t_cap bytes, and its offsets [S+1]
+    const uint64_t* t_off;
+    uint64_t t_cap;
+    const int32_t* tag_models;  // fill_tags' dense arrays (TagParams::model_out / scores_out); nullptr: no token has a tag model
+    const int32_t* tag_scores;
+    uint32_t score_stride, n_models, n_strings, flags;
+    const uint32_t *models, *slots, *slot_str, *str_off;   // HostTagTables
+    const uint8_t* str_bytes;
+    uint64_t* pos;              // [n_elem + 1] workspace: the elements' sizes, then their positions
+    uint8_t* out;               // [capacity]
+    uint64_t* out_offsets;      // [S+1] the lines' ranges in out
+    uint64_t capacity;
+    uint32_t* status;
+};
+// scan_part: scan_part_entries(n_elem) zero words
+hipError_t launch_listing(const ListingParams& P, uint64_t* scan_part, hipStream_t stream);
+// copy[n_sent + 1] = ooff when it is non-decreasing and ends inside total_boundaries, else zeros and kErrBadOffsets; flag: a zero word
+hipError_t launch_listing_offsets(const uint64_t* ooff, uint64_t n_sent, uint64_t total_boundaries, uint64_t* copy, uint32_t* flag, uint32_t* status,
+                                  hipStream_t stream);
 // vpt_count_boundaries on the device: ooff_out[S+1]; *max_chars (atomicMax) = the longest sentence in chars; text_bytes_hint: the batch's text
 // bytes when the host knows them (0: not), which sizes the workgroups' shares
 hipError_t launch_count_boundaries(const uint8_t* text, const uint64_t* boff, uint64_t n_sent, uint64_t* ooff_out, uint64_t* scan_part, uint32_t* status,
