@@ -138,6 +138,62 @@ def fits(p):
 UNSTABLE = {}
 
 
+def check_class_stats(st, p, y, wg, cost, solver):
+    """The stats of one (problem, class) against the problem's 0/1 matrix alone (trainsuite's checks b and c): gnorm0 is the first
+    gradient's norm bit for bit -- at w = 0 every partial sum is a multiple of 1/2 -- and gnorm and objective are |g| and f at the
+    returned weights within the bound of fp64 summation in any order (trainref.stats_bounds).  The in-kernel solver sums in LDS and
+    shares no code with the global-memory one; both are held to the same two checks."""
+    ones = np.ones(len(p["cols"]))
+    if cost == 1.0:
+        trainref.check_gnorm0(st, p["row_ptr"], p["cols"], ones, y, len(p["keys"]), solver)
+    return trainref.check_stats(st, p["row_ptr"], p["cols"], ones, y, wg[:-1], wg[-1], cost, solver)
+
+
+LIMIT_PARAMS = (0, 0, 0, 1, 1, 1, 1)   # charn = typen = 1: a token's features are the char and the type on either side
+
+
+def limit_corpus(total):
+    """Sentences "<a|b>X<right>" of three one-char tokens whose only tag problem (surface X, two tags) has exactly
+    7 * (features + 1) + 3 * rows == total: features = 2 left chars + the right chars + 1 left type + 2 right types, and 7424 needs
+    features + 1 = 2 (mod 3), 7425 features + 1 = 0 (mod 3).  The tag follows the right char, one in ten flipped."""
+    rights = {2: "c1", 0: "cd1"}[total % 3]
+    nf = 2 + len(rights) + 1 + 2
+    rows, rem = divmod(total - 7 * (nf + 1), 3)
+    assert rem == 0
+    rng = np.random.default_rng(total)
+    flip = rng.random(rows) < 0.1
+    out = []
+    for i in range(rows):
+        right = rights[i % len(rights)]
+        tag = "t%d" % ((right == "1") ^ bool(flip[i]))
+        out.append(("ab"[(i // 3) % 2] + "X" + right, np.array([1, 1], np.uint8), 1, [None, tag, None]))
+    # the boundary model needs a boundary that is none
+    return out + [("ab", np.array([0], np.uint8), 1, [None, None])] * 3
+
+
+def check_limit(total, path, eps=0.01, cost=1.0):
+    """A problem exactly at (7424, in-kernel) and one double past (7425, global-memory) the in-kernel solver's LDS limit: the path
+    taken, and the stats of both solvers."""
+    sents = limit_corpus(total)
+    t, r = run_pair(LIMIT_PARAMS, sents, tag_dictionary=())
+    (p,) = [q for m in r.models() for q in m["problems"]]
+    assert 7 * (len(p["keys"]) + 1) + 3 * len(p["y"]) == total and fits(p) == (path == 1)
+    X = tagtrainref.design(p)
+    ((c, y),) = tagtrainref.class_targets(p)
+    for solver in (2, 0):
+        t.train_bytes(eps, cost, solver)
+        stats = t.tag_stats()
+        assert [q["path"] for q in stats["problems"]] == [path]
+        wg = t.tag_weights(0)[c]
+        pos = int((y > 0).sum())
+        tol = eps * max(min(pos, len(y) - pos), 1) / len(y)
+        g = trainref.gradient(X, y, wg, cost, solver)
+        assert np.linalg.norm(g) <= tol * np.linalg.norm(trainref.gradient(X, y, np.zeros_like(wg), cost, solver)) * 1.01
+        st = stats["problems"][0]["classes"][c]
+        assert st["iterations"] >= 1
+        check_class_stats(st, p, y, wg, cost, solver)
+
+
 def check_solver(name, solver, path=0, eps=0.01, cost=1.0):
     params = CASES[name]
     sents = corpus(params[0], params[1], params[2])
@@ -167,6 +223,7 @@ def check_solver(name, solver, path=0, eps=0.01, cost=1.0):
             fg, fr = trainref.objective(X, y, wg, cost, solver), trainref.objective(X, y, wr, cost, solver)
             assert abs(fg - fr) <= 1e-3 * abs(fr), (tok, p["slot"], c)
             st = stats["problems"][i]["classes"][c]
+            check_class_stats(st, p, y, wg, cost, solver)
             same = (st["iterations"], st["cg_steps"]) == (it, cg) and np.linalg.norm(wg - wr) <= 1e-7 * np.linalg.norm(wr)
             if not same:
                 seen_unstable.add((tok, p["slot"], c))

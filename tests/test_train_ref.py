@@ -24,6 +24,34 @@ def test_gen_features_kat(name):
         assert int(s.boundaries()[b["index"]]) == int(getattr(api.CharacterBoundary, b["label"]))
 
 
+# trainref.fast_matrix is what the shaped corpora of tests/trainsuite.py are checked against; it is trusted only because it equals the
+# per-boundary restatement here: on the suite's cases, and with dictn = 1 over nested words (every word in one bucket, counts above 1)
+NESTED = (5, 2, 2, 1, 1, 1, True)
+
+
+@pytest.mark.parametrize("case", trainsuite.CASES + [NESTED])
+def test_fast_matrix_equals_restatement(case):
+    import numpy as np
+    seed, charw, charn, typew, typen, dictn, with_dict = case
+    sents = trainsuite.corpus(seed, 200)
+    words = trainsuite.dictionary(sents, seed) if with_dict else []
+    r = trainref.RefTrainer(charw, charn, typew, typen, words, dictn)
+    for s, lab in sents:
+        r.add_example(s, lab)
+    keys, ptr, cols, cnt, y = r.matrix()
+    fkeys, fptr, fcols, fcnt, fy = trainref.fast_matrix(*trainref.pack_corpus(sents), charw, charn, typew, typen, words, dictn)
+    assert trainref.keys_as_ints(fkeys) == keys
+    assert np.array_equal(fptr, ptr) and np.array_equal(fcols, cols) and np.array_equal(fcnt, cnt) and np.array_equal(fy, y)
+    if case == NESTED:
+        assert any(a != b and a in b for a in words for b in words) and cnt.max() > 1
+        assert {trainref.decode_key(k)[1] for k in keys if trainref.decode_key(k)[0] == "dict"} == {1}
+
+
+def test_shaped_corpora_hold_their_shapes():
+    trainsuite.check_shape("medium")
+    trainsuite.check_shape("large")
+
+
 def test_keys_round_trip():
     for f in [("char", "\U00020B9Fあ", -3), ("type", (1, 6, 3), 2), ("dict", 4, "R"), ("char", "abcde", -16)]:
         assert trainref.decode_key(trainref.key_of(f)) == f

@@ -28,6 +28,12 @@ def test_every_problem_through_the_global_memory_solver(solver):
     assert {p["path"] for p in stats["problems"]} == {2}
 
 
+# a problem exactly at the in-kernel solver's limit of 7 * (features + 1) + 3 * rows = 7424 doubles of LDS, and one double past it
+@pytest.mark.parametrize("total,path", [(7424, 1), (7425, 2)])
+def test_problem_at_the_lds_limit(total, path):
+    tagtrainsuite.check_limit(total, path)
+
+
 def test_flag_and_errors():
     tagtrainsuite.check_errors()
 

@@ -2,6 +2,8 @@
 
 - gen_features / RefTrainer.add_example: Trainer::gen_features and add_example (trainer.rs:260-350), features in the reference's order;
 - keys: the library's 128-bit feature keys (include/vaporetto_hip.h, Trainer section), so that the sorted key table and the CSR compare;
+- fast_matrix: RefTrainer.matrix() over a packed corpus in vectorised numpy, for corpora of 10^5 rows (tests/test_train_ref.py holds
+  it to RefTrainer); column_sums / gnorm0_squared / stats_bounds: what vpt_train_stats must hold, from that matrix alone;
 - tron: liblinear's TRON for solvers 0 (l2r_lr_fun) and 2 (l2r_l2_svc_fun) as scikit-learn bundles it (tron.cpp, linear.cpp), in fp64;
 - build_model: quantisation and the model layout (trainer.rs:352-487), encoded by modelfmt.encode_model.
 """
@@ -97,6 +99,214 @@ class RefTrainer:
             ptr.append(len(cols))
         y = np.where(np.array(self.labels) == 1, 1.0, -1.0)
         return keys, np.array(ptr, np.int64), np.array(cols, np.int64), np.array(cnt, np.float64), y
+
+
+def pack_corpus(sents):
+    """(code points, chars per sentence, labels) of [(text, labels)]: what fast_matrix reads."""
+    cps = np.array([ord(c) for s, _ in sents for c in s], np.int64)
+    lens = np.array([len(s) for s, _ in sents], np.int64)
+    return cps, lens, np.concatenate([np.asarray(lab, np.uint8) for _, lab in sents])
+
+
+def _or_shift(hi, lo, c, s):
+    """hi:lo |= c << s, for symbols c below 2^21 (uint64 words of a 128-bit key)."""
+    c = c.astype(np.uint64)
+    if s >= 64:
+        hi |= c << np.uint64(s - 64)
+        return
+    lo |= c << np.uint64(s)   # the bits past 63 fall off the low word ...
+    if s + 21 > 64:
+        hi |= c >> np.uint64(64 - s)   # ... and arrive here
+
+
+def keys_as_ints(keys):
+    """The (n, 2) array of (low, high) words as Python ints, for a comparison with RefTrainer.matrix() or Trainer.weights()."""
+    return [int(lo) | (int(hi) << 64) for lo, hi in keys]
+
+
+def fast_matrix(cps, lens, labels, charw, charn, typew, typen, dict_words=(), dictn=0):
+    """RefTrainer.matrix() without a Python loop per boundary: Trainer::gen_features (trainer.rs:260-318) and add_example (:321-350)
+    stated per (kind, n-gram length, relative position) and per dictionary word over whole arrays.
+
+    cps: the corpus' code points, sentence after sentence; lens: chars per sentence; labels: one per boundary.  Returns (keys, row_ptr,
+    cols, counts, y): the sorted distinct keys as an (n, 2) uint64 array of (low, high) words -- the form vpt_trainer_weights gives
+    them in -- and the CSR with rows in corpus order, columns in key order and a feature's occurrences at a boundary as its count."""
+    from vaporetto_amd.api import _types_of
+    cps, lens = np.asarray(cps, np.int64), np.asarray(lens, np.int64)
+    assert lens.min() >= 1 and lens.sum() == len(cps)
+    n_sent = len(lens)
+    types = _types_of(cps).astype(np.int64)
+    cbase = np.cumsum(lens) - lens                       # a sentence's first char
+    rbase = np.concatenate([[0], np.cumsum(lens - 1)])   # ... and first boundary (row)
+    total_b = int(rbase[-1])
+    assert len(labels) == total_b
+    sent = np.repeat(np.arange(n_sent), lens - 1)
+    p = np.arange(total_b) - rbase[sent]                 # the boundary between chars p and p + 1 of its sentence
+    n = lens[sent]
+    g0 = cbase[sent] + p + 1                             # the char at relative position 0
+    rows, his, los = [], [], []
+    # n-grams of m + 1 symbols starting at j = p + 1 + rel: max(0, p + 1 - w) <= j and j + m < min(p + 1 + w, n)
+    for kind, (w, ng, sym) in enumerate(((charw, charn, cps), (typew, typen, types))):
+        for m in range(ng):
+            for rel in range(-w, w - m):
+                j = p + 1 + rel
+                r = np.flatnonzero((j >= 0) & (j + m < n))
+                hi = np.full(len(r), kind << 56, np.uint64)
+                lo = np.full(len(r), ((m + 1) << 5) | (rel + 16), np.uint64)
+                for k in range(m + 1):
+                    _or_shift(hi, lo, sym[g0[r] + rel + k], _SH[k])
+                rows.append(r)
+                his.append(hi)
+                los.append(lo)
+    # find_overlapping_iter: every occurrence of every word inside a sentence; Left of its first char, Right of its last, Inside between
+    csent = np.repeat(np.arange(n_sent), lens)
+    cloc = np.arange(len(cps)) - cbase[csent]
+    for word in sorted(set(dict_words)):
+        ln = len(word)
+        if ln > len(cps):
+            continue
+        ok = np.ones(len(cps) - ln + 1, bool)
+        for k, c in enumerate(word):
+            ok &= cps[k:len(cps) - ln + 1 + k] == ord(c)
+        at = np.flatnonzero(ok)
+        at = at[cloc[at] + ln <= lens[csent[at]]]
+        r0, a = rbase[csent[at]], cloc[at]
+        left, right = a != 0, a + ln != lens[csent[at]]
+        inside = np.repeat(r0 + a, ln - 1) + np.tile(np.arange(ln - 1), len(at))
+        for where, r in ((0, (r0 + a - 1)[left]), (1, inside), (2, (r0 + a + ln - 1)[right])):
+            rows.append(r)
+            his.append(np.full(len(r), (2 << 56) | (min(ln, dictn) << 35) | (where << 14), np.uint64))
+            los.append(np.zeros(len(r), np.uint64))
+    rows, hi, lo = np.concatenate(rows), np.concatenate(his), np.concatenate(los)
+    order = np.lexsort((lo, hi))
+    first = np.ones(len(order), bool)
+    first[1:] = (hi[order][1:] != hi[order][:-1]) | (lo[order][1:] != lo[order][:-1])
+    col = np.empty(len(order), np.int64)
+    col[order] = np.cumsum(first) - 1
+    keys = np.stack([lo[order][first], hi[order][first]], axis=1)
+    nd = len(keys)
+    assert total_b * nd < 2 ** 62
+    code, cnt = np.unique(rows * nd + col, return_counts=True)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(code // nd, minlength=total_b))]).astype(np.int64)
+    y = np.where(np.asarray(labels) == 1, 1.0, -1.0)
+    return keys, ptr, code % nd, cnt.astype(np.float64), y
+
+
+def column_lengths(cols, nd):
+    return np.bincount(cols, minlength=nd)
+
+
+def xtv_levels(col_len, seg=64):
+    """Levels of the trainer's segmented X^T v (capi_train.cpp csc_levels): a level cuts every column into segments of `seg` values, and
+    the last level is the one that leaves one segment per column."""
+    levels, ln = 0, np.asarray(col_len)
+    while True:
+        ln = (ln + seg - 1) // seg
+        levels += 1
+        if np.all(ln == 1):
+            return levels
+
+
+def column_sums(ptr, cols, cnt, y, nd):
+    """sum_i x_ij y_i per column in int64, and sum_i y_i: exact."""
+    cols = np.asarray(cols, np.int64)
+    rows = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+    t = np.asarray(cnt).astype(np.int64) * np.asarray(y).astype(np.int64)[rows]
+    order = np.argsort(cols, kind="stable")
+    return _segment_sums(t[order], np.searchsorted(cols[order], np.arange(nd)), np.int64), int(np.asarray(y).astype(np.int64).sum())
+
+
+def gnorm0_squared(ptr, cols, cnt, y, nd):
+    """S = sum_j (sum_i x_ij y_i)^2 + (sum_i y_i)^2 in Python integers.  At w = 0 every row's gz is -2 C y (solver 2) or -C y / 2
+    (solver 0: 1 / (1 + exp(-0)) is exactly 0.5), so with C = 1 the squared norm of the first gradient is 4 S or S / 4, and every
+    partial sum on the way is an integer multiple of 1/2 below 2^53: exact in fp64 in any order."""
+    cs, b = column_sums(ptr, cols, cnt, y, nd)
+    return sum(int(v) * int(v) for v in cs) + b * b
+
+
+def check_gnorm0(stats, ptr, cols, cnt, y, nd, solver):
+    """stats["gnorm0"] of a training with C = 1 is the square root of gnorm0_squared's integer times 4 (solver 2) or 1/4 (solver 0),
+    bit for bit."""
+    S = gnorm0_squared(ptr, cols, cnt, y, nd)
+    assert 4 * S < 2 ** 53
+    want = math.sqrt(4 * S) if solver == 2 else math.sqrt(S / 4)
+    assert stats["gnorm0"] == want, (stats["gnorm0"], want, S)
+
+
+_U = 2.0 ** -53
+_EXT = np.longdouble if np.finfo(np.longdouble).nmant >= 63 else None
+
+
+def _segment_sums(t, start, dtype):
+    """Sums of t[start[k] : start[k + 1]] (the last to the end; a segment may be empty) in `dtype`; dtype None: extended precision,
+    np.longdouble where it has a 64-bit significand, else math.fsum."""
+    start = np.asarray(start, np.int64)
+    ends = np.append(start[1:], len(t))
+    full = ends > start
+    if dtype is None and _EXT is None:
+        return np.array([math.fsum(t[a:e]) for a, e in zip(start, ends)])
+    out = np.zeros(len(start), dtype or _EXT)
+    if full.any():
+        out[full] = np.add.reduceat(t.astype(out.dtype), start[full])
+    return out
+
+
+def _total(t):
+    return np.sum(t.astype(_EXT)) if _EXT is not None else math.fsum(t)
+
+
+def stats_bounds(ptr, cols, cnt, y, w, b, C, solver):
+    """(f, |g|, bound on f, bound on |g|) at weights w and bias b: the objective and gradient norm of liblinear's l2r_lr_fun (solver 0) /
+    l2r_l2_svc_fun (solver 2) in extended precision, and how far an fp64 evaluation that sums in any order may lie from them.
+
+    A sum of n fp64 terms t_i in any order is within (n - 1) 2^-53 sum |t_i| of the exact sum.  That gives dz_i for z = Xw + b; it
+    reaches the loss through its Lipschitz constant (2 C |1 - y z| for solver 2, C for solver 0) and gz through 2 C or C / 4 (gz is
+    continuous at y z = 1, so a row whose activity flips within rounding stays inside); then the sums over rows and over a column's
+    nonzeros add their own term.  The whole is doubled for second-order terms and the few ulps of exp, log and the products.  Nothing
+    in it is measured on the code under test."""
+    ext = _EXT if _EXT is not None else np.float64
+    ptr, cols = np.asarray(ptr, np.int64), np.asarray(cols, np.int64)
+    w, cnt = np.asarray(w, np.float64), np.asarray(cnt, np.float64)
+    nr, nd = len(ptr) - 1, len(w)
+    row_len = np.diff(ptr)
+    rows = np.repeat(np.arange(nr), row_len)
+    wx, bx = w.astype(ext), ext(b)
+    z = _segment_sums(cnt.astype(ext) * wx[cols], ptr[:-1], None) + bx
+    dz = row_len * _U * (_segment_sums(np.abs(cnt * w[cols]), ptr[:-1], np.float64) + abs(b))   # row_len + 1 terms
+    yz = y.astype(ext) * z
+    if solver == 0:
+        loss = C * np.where(yz >= 0, np.log1p(np.exp(-np.abs(yz))), -yz + np.log1p(np.exp(np.minimum(yz, 0))))
+        gz = C * (1 / (1 + np.exp(-yz)) - 1) * y
+        lip_loss, lip_gz = np.full(nr, float(C)), C / 4
+    else:
+        d = np.maximum(1 - yz, 0)
+        loss = C * d * d
+        gz = -2 * C * y * d
+        lip_loss, lip_gz = 2 * C * np.abs(1 - yz).astype(np.float64), 2 * C
+    reg = (_total(wx * wx) + bx * bx) / 2
+    f = reg + _total(loss)
+    bound_f = nd * _U * float(reg) + (nr - 1) * _U * float(_total(np.abs(loss))) + float(np.sum(lip_loss * dz)) + _U * float(f)
+    # g_j = w_j + sum_i x_ij gz_i (len_j + 1 terms), the bias: b + sum_i gz_i (nr + 1 terms)
+    order = np.argsort(cols, kind="stable")
+    start = np.searchsorted(cols[order], np.arange(nd))
+    col_len = np.diff(np.append(start, len(cols)))
+    tg = (cnt.astype(ext) * gz[rows])[order]
+    g = np.append(wx + _segment_sums(tg, start, None), bx + _total(gz))
+    dg = (col_len * _U * (np.abs(w) + _segment_sums(np.abs(tg).astype(np.float64), start, np.float64))
+          + lip_gz * _segment_sums((cnt * dz[rows])[order], start, np.float64))
+    dg_b = nr * _U * (abs(b) + float(np.sum(np.abs(gz)))) + lip_gz * float(np.sum(dz))
+    gnorm = np.sqrt(_total(g * g))
+    bound_g = float(np.sqrt(np.sum(dg * dg) + dg_b * dg_b)) + nd * _U * float(gnorm) / 2   # the norm's own sum of nd + 1 squares
+    return f, gnorm, 2 * bound_f, 2 * bound_g
+
+
+def check_stats(stats, ptr, cols, cnt, y, w, b, C, solver):
+    """stats["objective"] and stats["gnorm"] are f and |g| at (w, b) within stats_bounds; returns the two error / bound ratios."""
+    f, gnorm, bf, bg = stats_bounds(ptr, cols, cnt, y, w, b, C, solver)
+    ext = type(f)
+    rf, rg = float(abs(ext(stats["objective"]) - f)) / bf, float(abs(ext(stats["gnorm"]) - gnorm)) / bg
+    assert rf <= 1 and rg <= 1, (rf, rg, float(f), float(gnorm), bf, bg)
+    return rf, rg
 
 
 def design(ptr, cols, cnt, nd):

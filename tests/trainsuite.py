@@ -1,5 +1,8 @@
 """TEST INFRASTRUCTURE: the trainer checks shared by the emulator tests (tests/test_train_emu.py) and the GPU tests
 (tests/test_train_gpu.py), against the restatement of tests/trainref.py."""
+import functools
+import math
+
 import numpy as np
 import pytest
 
@@ -115,6 +118,204 @@ def check_solver(case, solver, eps=0.01, cost=1.0):
     t2, _, _ = run_pair(case, solver)
     assert t2.train_bytes(eps, cost, solver) == model
     return model
+
+
+# ---------------------------------------------------------------------------------------------------- shaped corpora
+# With charw = charn = typew = typen = 1 a boundary has four n-gram features: the char and the type on either side.  A char planted k
+# times, never first or last in its sentence, therefore owns two columns of exactly k nonzeros.  The dictionary's words nest and
+# overlap and all fall into the bucket min(len, dictn) = 1, so its three columns (Left, Inside, Right) carry counts above 1.
+SHAPED_PARAMS = (1, 1, 1, 1)
+SHAPED_WORDS = ["カキ", "カキク", "キク", "キクケ"]
+SHAPED_DICTN = 1
+PLANTED = (1, 63, 64, 65, 127, 128, 129, 4095, 4096, 4097)    # the edges of seg_count_kernel and xtv_level_kernel, levels 1 and 2
+PLANTED_LARGE = (262143, 262144, 262145)                       # ... and of level 3
+_MARK0, _DIST0, _N_DIST, _PHRASE = 0x4E00, 0x5000, 2200, "カキクケ"   # planted Kanji, Kanji that occur once, the text the words lie in
+_HEAD, _TAIL, _LONE, _A, _I = ord("ノ"), ord("。"), ord("ん"), ord("あ"), ord("い")
+_SEEDS = {"medium": 41, "large": 42}
+_TILE, _SEG = 4096, 64                                         # kernels_train.hip: kTile (256 threads * 16) and kSeg
+
+
+@functools.lru_cache(maxsize=None)
+def shaped_corpus(size):
+    """"medium" or "large": (code points, chars per sentence).  A regular sentence is _HEAD, a stretch of the shuffled body, _TAIL; in
+    front of every seventh sentence and at the very end stands a sentence of one char (no boundary).  Whole arrays, no loop per char.
+
+    "large" adds 262143 あ and 2 い to the body and ends its last regular sentence with あ in place of _TAIL.  No other char is
+    Hiragana, so the columns (あ, -1), (あ, 0) and (Hiragana, -1) have 262143, 262144 and 262145 nonzeros: the three lengths around
+    64^3 from one stretch of text, not three."""
+    rng = np.random.default_rng(_SEEDS[size])
+    planted = [(_MARK0 + k, n) for k, n in enumerate(PLANTED)]
+    if size == "large":
+        planted += [(_A, PLANTED_LARGE[0]), (_I, 2)]
+    n_phrase = 300 if size == "medium" else 3000
+    # the body's tokens: a planted char, a char that occurs once, or the phrase (0; kept whole)
+    tok = np.concatenate([np.full(n, c) for c, n in planted] + [np.arange(_DIST0, _DIST0 + _N_DIST), np.zeros(n_phrase, np.int64)])
+    tok = tok[rng.permutation(len(tok))]
+    ln = np.where(tok == 0, len(_PHRASE), 1)
+    src = np.repeat(np.arange(len(tok)), ln)
+    within = np.arange(len(src)) - np.repeat(np.cumsum(ln) - ln, ln)
+    body = np.where(tok[src] == 0, np.array([ord(c) for c in _PHRASE])[within], tok[src])
+    # stretches of 1 .. 38 chars
+    cut = np.cumsum(rng.integers(1, 39, len(body)))
+    start = np.concatenate([[0], cut[cut < len(body)]])
+    lens = np.diff(np.append(start, len(body))) + 2
+    s0 = np.cumsum(lens) - lens
+    cps = np.full(int(lens.sum()), -1, np.int64)
+    cps[s0], cps[s0 + lens - 1] = _HEAD, _TAIL
+    cps[cps == -1] = body
+    if size == "large":
+        cps[-1] = _A
+    at = np.arange(0, len(lens), 7)
+    cps = np.append(np.insert(cps, s0[at], _LONE), _LONE)
+    lens = np.append(np.insert(lens, at, 1), 1)
+    cps.flags.writeable = lens.flags.writeable = False
+    return cps, lens
+
+
+@functools.lru_cache(maxsize=None)
+def shaped_reference(size):
+    """(keys, row_ptr, cols, counts) of the corpus by trainref.fast_matrix: computed once, shared, read-only."""
+    cps, lens = shaped_corpus(size)
+    out = trainref.fast_matrix(cps, lens, np.zeros(int((lens - 1).sum()), np.uint8), *SHAPED_PARAMS, SHAPED_WORDS, SHAPED_DICTN)[:4]
+    for a in out:
+        a.flags.writeable = False
+    return out
+
+
+def check_shape(size):
+    """What the corpus is for, asserted on the restatement's matrix alone: a generator that misses a shape fails here."""
+    cps, lens = shaped_corpus(size)
+    keys, ptr, cols, cnt = shaped_reference(size)
+    n_rows, nd = len(ptr) - 1, len(keys)
+    col_len = trainref.column_lengths(cols, nd)
+    occ = int(cnt.sum())
+    lone = np.flatnonzero(lens == 1)
+    assert lens[-1] == 1 and len(lone) > 2 and lone[0] == 0 and np.all(np.diff(lone) > 1)   # interleaved, and the last sentence
+    assert cnt.max() > 1 and (cnt > 1).sum() >= 0.005 * len(cnt)                             # dictionary words sharing a bucket
+    assert n_rows > _TILE and nd > _TILE                                                     # dot_kernel: a second pass over both
+    assert set(PLANTED) <= set(col_len.tolist())
+    if size == "medium":
+        assert _TILE < col_len.max() <= _SEG ** 3 and trainref.xtv_levels(col_len, _SEG) == 3
+    else:
+        assert col_len.max() > _SEG ** 3 and trainref.xtv_levels(col_len, _SEG) == 4
+        assert set(PLANTED_LARGE) <= set(col_len.tolist())
+        # the type unigram all those boundaries share
+        hira = trainref.key_of(("type", (trainref.char_type("あ"),), -1))
+        assert col_len[trainref.keys_as_ints(keys).index(hira)] == PLANTED_LARGE[2]
+        # scan_top_kernel walks the tile sums 256 at a time: its carry loop runs more than once over the occurrence flags
+        assert occ > 256 * _TILE and math.ceil(occ / _TILE) > 256
+
+
+LABELS = ("random", "all_but_one", "alternating", "learnable")
+
+
+def shaped_labels(size, name):
+    """random: a 40 / 60 split; all_but_one: WordBoundary everywhere but at one row; alternating: by row index, about 5 % Unknown (which
+    trains as -1); learnable: decided by the char behind the boundary, 10 % flipped (for a real solve)."""
+    cps, lens = shaped_corpus(size)
+    n = int((lens - 1).sum())
+    rng = np.random.default_rng(_SEEDS[size] + 7 + LABELS.index(name))
+    if name == "random":
+        return (rng.random(n) < 0.4).astype(np.uint8)
+    if name == "all_but_one":
+        lab = np.ones(n, np.uint8)
+        lab[n // 3] = 0
+        return lab
+    if name == "alternating":
+        lab = (np.arange(n) % 2).astype(np.uint8)
+        lab[rng.random(n) < 0.05] = 2
+        return lab
+    right = np.delete(cps, np.cumsum(lens) - lens)   # every char but a sentence's first: the char behind each boundary
+    return ((right % 3 == 0) ^ (rng.random(n) < 0.1)).astype(np.uint8)
+
+
+def shaped_trainer(size, labels):
+    cps, lens = shaped_corpus(size)
+    utf8 = np.frombuffer(cps.astype("<u4").tobytes().decode("utf-32-le").encode("utf-8"), np.uint8)
+    nbytes = 1 + (cps >= 0x80) + (cps >= 0x800) + (cps >= 0x10000)
+    boff = np.concatenate([[0], np.cumsum(nbytes)[np.cumsum(lens) - 1]]).astype(np.uint64)
+    t = api.Trainer(*SHAPED_PARAMS, SHAPED_WORDS, SHAPED_DICTN)
+    t.add_packed(utf8, boff, labels)
+    return t
+
+
+def loose_eps(y):
+    """TRON's relative tolerance is eps * min(pos, neg) / l (liblinear's train_one); 0.9 stops it at the first step that takes a tenth
+    off the gradient.  At 1 it would not start, and a trainer without weights has no stats to read."""
+    pos = int((y > 0).sum())
+    return 0.9 * len(y) / min(pos, len(y) - pos)
+
+
+def check_shaped_matrix(size):
+    """(a) the key table and the CSR equal the restatement's, element for element."""
+    check_shape(size)
+    keys, ptr, cols, cnt = shaped_reference(size)
+    labels = shaped_labels(size, "random")
+    t = shaped_trainer(size, labels)
+    assert t.n_features() == len(keys)
+    gptr, gcols, gcnt = t.csr()
+    assert np.array_equal(gptr.astype(np.int64), ptr)
+    assert np.array_equal(gcols.astype(np.int64), cols)
+    assert np.array_equal(gcnt.astype(np.float64), cnt)
+    t.train_bytes(loose_eps(np.where(labels == 1, 1.0, -1.0)), 1.0, 2)
+    assert t.weights()[2] == trainref.keys_as_ints(keys)
+
+
+def check_shaped_stats(size, name):
+    """(b) gnorm0 bit for bit and (c) objective and gnorm at the returned weights within the fp64 summation bound, for both solvers
+    after a step or two of TRON; returns {solver: (objective error / bound, gnorm error / bound)}."""
+    check_shape(size)
+    keys, ptr, cols, cnt = shaped_reference(size)
+    labels = shaped_labels(size, name)
+    y = np.where(labels == 1, 1.0, -1.0)
+    t = shaped_trainer(size, labels)
+    ratios = {}
+    for solver in (2, 0):
+        t.train_bytes(loose_eps(y), 1.0, solver)
+        stats = t.last_stats()
+        w, b, _ = t.weights()
+        assert stats["iterations"] >= 1
+        trainref.check_gnorm0(stats, ptr, cols, cnt, y, len(keys), solver)
+        ratios[solver] = trainref.check_stats(stats, ptr, cols, cnt, y, w, b, 1.0, solver)
+    print("error / bound (objective, gnorm) %s %s: %s" % (size, name, ratios))
+    return ratios
+
+
+def check_shaped_determinism(size, eps=0.1):
+    """(d) two trainers fed the same corpus: the same model bytes and the same stats.  On a device the insert table's compare-and-swap
+    winners differ from run to run; the order of the key sort has to hide that."""
+    labels = shaped_labels(size, "learnable")
+    t1, t2 = shaped_trainer(size, labels), shaped_trainer(size, labels)
+    m1, m2 = t1.train_bytes(eps, 1.0, 2), t2.train_bytes(eps, 1.0, 2)
+    assert m1 == m2
+    assert t1.last_stats() == t2.last_stats()
+    assert t1.last_stats()["iterations"] >= 1
+
+
+def check_shaped_solve(size, eps=0.01, cost=1.0, solver=2):
+    """(e) a real solve: check_solver's stopping rule and objective against trainref.tron over the restatement's matrix, and (c) at the
+    solution.  The pair is not in STABLE: whether its path is the restatement's step for step has not been established."""
+    keys, ptr, cols, cnt = shaped_reference(size)
+    labels = shaped_labels(size, "learnable")
+    y = np.where(labels == 1, 1.0, -1.0)
+    t = shaped_trainer(size, labels)
+    t.train_bytes(eps, cost, solver)
+    w, b, gkeys = t.weights()
+    stats = t.last_stats()
+    assert gkeys == trainref.keys_as_ints(keys)
+    X = trainref.design(ptr, cols, cnt, len(keys))
+    wr = trainref.tron(X, y, cost, eps, solver)[0]
+    wg = np.append(w, b)
+    pos = int((y > 0).sum())
+    tol = eps * max(min(pos, len(y) - pos), 1) / len(y)
+    g = trainref.gradient(X, y, wg, cost, solver)
+    assert np.linalg.norm(g) <= tol * np.linalg.norm(trainref.gradient(X, y, np.zeros_like(wg), cost, solver)) * 1.01
+    fg, fr = trainref.objective(X, y, wg, cost, solver), trainref.objective(X, y, wr, cost, solver)
+    assert abs(fg - fr) <= 1e-3 * abs(fr)
+    trainref.check_gnorm0(stats, ptr, cols, cnt, y, len(keys), solver)
+    ratios = trainref.check_stats(stats, ptr, cols, cnt, y, w, b, cost, solver)
+    print("error / bound (objective, gnorm) %s solve: %s, %d iterations, %d CG steps" % (size, ratios, stats["iterations"], stats["cg_steps"]))
+    return ratios
 
 
 def check_errors():
