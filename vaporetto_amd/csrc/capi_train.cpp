@@ -2,11 +2,12 @@
 //
 // The vpt_trainer handle keeps every example's feature keys and label on the device (kernels_train.hip); feature ids, the CSR and CSC
 // copies of the design matrix are made when they are first needed after an add, and the TRON / CG loop runs here, on the host, over
-// device vectors, reading back a scalar per reduction.  TRON is the one of the liblinear that scikit-learn bundles (tron.cpp: CG without
-// a preconditioner, eps_cg = 0.1); the reference's newer liblinear preconditions its CG and reaches the same optimum by another path, so
-// weights agree with it only to the stopping tolerance.  Quantisation and the model layout are trainer.rs:352-487; the encoder mirrors
-// vaporetto_amd/modelfmt.encode_model (model.rs:99-104).
+// device vectors, reading back a scalar per reduction: `Tron` below is the host backend of tron.h, which holds the algorithm (the
+// liblinear's that scikit-learn bundles, tron.cpp: CG without a preconditioner, eps_cg = 0.1).  The reference's newer liblinear
+// preconditions its CG and reaches the same optimum by another path, so weights agree with it only to the stopping tolerance.
+// Quantisation and the model layout are trainer.rs:352-487; the encoder mirrors vaporetto_amd/modelfmt.encode_model (model.rs:99-104).
 #include "capi_internal.hpp"
+#include "tron.h"
 
 #include <chrono>
 #include <cmath>
@@ -108,7 +109,7 @@ struct TagProblem {
     bool fetched = false;
     std::vector<uint32_t> rp, cols;       // the 0/1 CSR, read back from the device when asked for (fetch_rows)
     uint32_t path = 0;                    // 1 solved inside the kernel, 2 by the global-memory TRON
-    double seconds_setup = 0, seconds_solve = 0;   // path 2: uploading the matrix and building its CSC; Tron::run over the classes
+    double seconds_setup = 0, seconds_solve = 0;   // path 2: uploading the matrix and building its CSC; the solves of its classes
     std::vector<double> w;                // [classes][features + 1]
     std::vector<vpt_train_stats> stats;   // per class
 };
@@ -329,7 +330,7 @@ vpt_status build(vpt_trainer* t) {
     return VPT_OK;
 }
 
-// TRON (liblinear tron.cpp as bundled by scikit-learn) for l2r_lr_fun (solver 0) / l2r_l2_svc_fun (solver 2), linear.cpp
+// the host backend of tron.h: a step is a launch over device vectors, a dot product is read back
 struct Tron {
     const Matrix* m;
     hipStream_t st;
@@ -337,6 +338,7 @@ struct Tron {
     int solver;
     double c;
     DBuf<double> w, w_new, g, s, r, d, Hd, y, z, zt, gz, D, loss, part0, part1;
+    vpt::TronVectors v;
     hipError_t err = hipSuccess;
 
     // for `rows` examples over M's columns and the bias
@@ -345,13 +347,13 @@ struct Tron {
         for (DBuf<double>* b : {&w, &w_new, &g, &s, &r, &d, &Hd}) VPT_HIP(b->resize(n));
         for (DBuf<double>* b : {&y, &z, &zt, &gz, &D, &loss}) VPT_HIP(b->resize(nr));
         for (DBuf<double>* b : {&part0, &part1}) VPT_HIP(b->resize(vpt::train_dot_partials(std::max(n, nr))));
+        v = vpt::TronVectors{w.p, w_new.p, g.p, s.p, r.p, d.p, Hd.p};
         return VPT_OK;
     }
     // one training from w = 0: the targets (+1 / -1, `pos` of them +1) go up, the weights come back into w_out[0 .. n)
     vpt_status solve(const std::vector<double>& targets, uint64_t pos, double eps, vpt_train_stats* stats, double* w_out) {
         VPT_HIP(hipMemcpy(y.p, targets.data(), nr * 8, hipMemcpyHostToDevice));
-        // liblinear's primal tolerance (linear.cpp train_one): eps * max(min(pos, neg), 1) / l
-        run(eps * double(std::max<uint64_t>(std::min(pos, nr - pos), 1)) / double(nr), stats);
+        *stats = vpt::tron(*this, vpt::tron_tolerance(eps, double(pos), double(nr)));
         VPT_HIP(err);
         VPT_HIP(hipMemcpy(w_out, w.p, n * 8, hipMemcpyDeviceToHost));
         return VPT_OK;
@@ -361,9 +363,9 @@ struct Tron {
     const double* reduce_dev(const double* a, const double* b, uint64_t len) {
         double* in_out[2] = {part0.p, part1.p};
         uint64_t m = vpt::train_dot_partials(len);
-        if (err == hipSuccess) err = vpt::train_dot(a, b, len, in_out[0], st);
+        if (ok()) err = vpt::train_dot(a, b, len, in_out[0], st);
         int k = 0;
-        while (m > 1 && err == hipSuccess) {
+        while (m > 1 && ok()) {
             err = vpt::train_dot(in_out[k], nullptr, m, in_out[k ^ 1], st);
             m = vpt::train_dot_partials(m);
             k ^= 1;
@@ -373,118 +375,47 @@ struct Tron {
     double dot(const double* a, const double* b, uint64_t len) {
         if (len == 0) return 0;
         const double* r_ = reduce_dev(a, b, len);
-        double v = 0;
-        if (err == hipSuccess) err = hipMemcpyAsync(&v, r_, 8, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        return v;
+        double v_ = 0;
+        if (ok()) err = hipMemcpyAsync(&v_, r_, 8, hipMemcpyDeviceToHost, st);
+        if (ok()) err = hipStreamSynchronize(st);
+        return v_;
     }
-    double nrm2(const double* a) { return std::sqrt(dot(a, a, n)); }
-    void axpy(double a, const double* x, double* y_) { if (err == hipSuccess) err = vpt::train_axpy(n, a, x, y_, st); }
+    double dot(const double* a, const double* b) { return dot(a, b, n); }
+    void zero(double* x) { if (ok()) err = hipMemsetAsync(x, 0, n * 8, st); }
+    void copy(const double* x, double* out) { if (ok()) err = hipMemcpyAsync(out, x, n * 8, hipMemcpyDeviceToDevice, st); }
+    void axpy(double a, const double* x, double* y_) { if (ok()) err = vpt::train_axpy(n, a, x, y_, st); }
+    void xpby(const double* x, double b, double* y_) { if (ok()) err = vpt::train_xpby(n, x, b, y_, st); }
+    void add(const double* a, const double* b, double* out) { copy(a, out); axpy(1.0, b, out); }
+    void cg_start() { zero(v.s); zero(v.r); axpy(-1.0, v.g, v.r); copy(v.r, v.d); }
+    void cg_boundary(double a) { axpy(a, v.d, v.s); axpy(-a, v.Hd, v.r); }
+    bool ok() const { return err == hipSuccess; }   // a launch failed: every later step is skipped and the loops end
+    bool cg_more(int) const { return ok(); }
     // out = a + Xᵀu
     void add_xtv(const double* a, const double* u, double* out) {
         const double* in = nullptr;
         for (auto& Lp : m->levels) {
             XtvLevel& L = *Lp;
-            if (err == hipSuccess)
+            if (ok())
                 err = vpt::train_xtv_level(L.ptr, L.nptr.p, L.seg_col.p, L.nseg, in, in ? nullptr : m->crow.p, m->cval.p, u, L.out.p, st);
             in = L.out.p;
         }
         const double* bias = reduce_dev(u, nullptr, nr);
-        if (err == hipSuccess) err = vpt::train_add(n, a, in, bias, out, st);
+        if (ok()) err = vpt::train_add(n, a, in, bias, out, st);
     }
     double fun(const double* x) {
-        if (err == hipSuccess) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, x, m->nd, z.p, st);
-        if (err == hipSuccess) err = vpt::train_loss(nr, z.p, y.p, c, solver, loss.p, st);
-        const double reg = dot(x, x, n) / 2.0;
+        if (ok()) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, x, m->nd, z.p, st);
+        if (ok()) err = vpt::train_loss(nr, z.p, y.p, c, solver, loss.p, st);
+        const double reg = dot(x, x) / 2.0;
         return reg + dot(loss.p, nullptr, nr);
     }
     void grad(const double* x, double* out) {
-        if (err == hipSuccess) err = vpt::train_grad_rows(nr, z.p, y.p, c, solver, gz.p, D.p, st);
+        if (ok()) err = vpt::train_grad_rows(nr, z.p, y.p, c, solver, gz.p, D.p, st);
         add_xtv(x, gz.p, out);
     }
-    void hv(const double* v, double* out) {
-        if (err == hipSuccess) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, v, m->nd, zt.p, st);
-        if (err == hipSuccess) err = vpt::train_scale_rows(nr, D.p, zt.p, st);
-        add_xtv(v, zt.p, out);
-    }
-    int trcg(double delta) {
-        if (err == hipSuccess) err = hipMemsetAsync(s.p, 0, n * 8, st);
-        if (err == hipSuccess) err = hipMemsetAsync(r.p, 0, n * 8, st);
-        axpy(-1.0, g.p, r.p);
-        if (err == hipSuccess) err = hipMemcpyAsync(d.p, r.p, n * 8, hipMemcpyDeviceToDevice, st);
-        const double cgtol = 0.1 * nrm2(g.p);
-        int cg_iter = 0;
-        double rTr = dot(r.p, r.p, n);
-        while (err == hipSuccess) {
-            if (nrm2(r.p) <= cgtol) break;
-            cg_iter++;
-            hv(d.p, Hd.p);
-            double alpha = rTr / dot(d.p, Hd.p, n);
-            axpy(alpha, d.p, s.p);
-            if (nrm2(s.p) > delta) {
-                alpha = -alpha;
-                axpy(alpha, d.p, s.p);
-                const double std_ = dot(s.p, d.p, n), sts = dot(s.p, s.p, n), dtd = dot(d.p, d.p, n), dsq = delta * delta;
-                const double rad = std::sqrt(std_ * std_ + dtd * (dsq - sts));
-                alpha = std_ >= 0 ? (dsq - sts) / (std_ + rad) : (rad - std_) / dtd;
-                axpy(alpha, d.p, s.p);
-                alpha = -alpha;
-                axpy(alpha, Hd.p, r.p);
-                break;
-            }
-            alpha = -alpha;
-            axpy(alpha, Hd.p, r.p);
-            const double rnew = dot(r.p, r.p, n);
-            const double beta = rnew / rTr;
-            if (err == hipSuccess) err = vpt::train_xpby(n, r.p, beta, d.p, st);
-            rTr = rnew;
-        }
-        return cg_iter;
-    }
-    void run(double eps, vpt_train_stats* stats) {
-        const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sigma1 = 0.25, sigma2 = 0.5, sigma3 = 4;
-        const int max_iter = 1000;
-        if (err == hipSuccess) err = hipMemsetAsync(w.p, 0, n * 8, st);
-        double f = fun(w.p);
-        grad(w.p, g.p);
-        double delta = nrm2(g.p);
-        const double gnorm1 = delta;
-        double gnorm = gnorm1;
-        bool search = !(gnorm <= eps * gnorm1);
-        int iter = 1, cg_total = 0;
-        while (iter <= max_iter && search && err == hipSuccess) {
-            const int cg_iter = trcg(delta);
-            cg_total += cg_iter;
-            if (err == hipSuccess) err = hipMemcpyAsync(w_new.p, w.p, n * 8, hipMemcpyDeviceToDevice, st);
-            axpy(1.0, s.p, w_new.p);
-            const double gs = dot(g.p, s.p, n);
-            const double prered = -0.5 * (gs - dot(s.p, r.p, n));
-            const double fnew = fun(w_new.p);
-            const double actred = f - fnew;
-            const double snorm = nrm2(s.p);
-            if (iter == 1) delta = std::min(delta, snorm);
-            const double alpha = (fnew - f - gs <= 0) ? sigma3 : std::max(sigma1, -0.5 * (gs / (fnew - f - gs)));
-            if (actred < eta0 * prered) delta = std::min(std::max(alpha, sigma1) * snorm, sigma2 * delta);
-            else if (actred < eta1 * prered) delta = std::max(sigma1 * delta, std::min(alpha * snorm, sigma2 * delta));
-            else if (actred < eta2 * prered) delta = std::max(sigma1 * delta, std::min(alpha * snorm, sigma3 * delta));
-            else delta = std::max(delta, std::min(alpha * snorm, sigma3 * delta));
-            if (actred > eta0 * prered) {
-                iter++;
-                if (err == hipSuccess) err = hipMemcpyAsync(w.p, w_new.p, n * 8, hipMemcpyDeviceToDevice, st);
-                f = fnew;
-                grad(w.p, g.p);
-                gnorm = nrm2(g.p);
-                if (gnorm <= eps * gnorm1) break;
-            }
-            if (f < -1.0e+32) break;
-            if (std::fabs(actred) <= 0 && prered <= 0) break;
-            if (std::fabs(actred) <= 1.0e-12 * std::fabs(f) && std::fabs(prered) <= 1.0e-12 * std::fabs(f)) break;
-        }
-        stats->iterations = uint32_t(iter - 1);
-        stats->cg_steps = uint32_t(cg_total);
-        stats->gnorm0 = gnorm1;
-        stats->gnorm = gnorm;
-        stats->objective = f;
+    void hv(const double* x, double* out) {
+        if (ok()) err = vpt::train_xv(m->csr_ptr.p, m->cols.p, m->vals.p, nr, x, m->nd, zt.p, st);
+        if (ok()) err = vpt::train_scale_rows(nr, D.p, zt.p, st);
+        add_xtv(x, zt.p, out);
     }
 };
 
@@ -855,25 +786,22 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         const double t0 = now_s();
         DBuf<vpt::TagSolveDesc> d_desc;
         DBuf<double> d_w;
-        DBuf<vpt::TagClassStats> d_stats;
+        DBuf<vpt_train_stats> d_stats;
         VPT_HIP(d_desc.resize(descs.size())); VPT_HIP(d_w.resize(n_w)); VPT_HIP(d_stats.resize(n_stats));
         VPT_HIP(hipMemcpyAsync(d_desc.p, descs.data(), descs.size() * sizeof(vpt::TagSolveDesc), hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemsetAsync(d_w.p, 0, n_w * 8, st));
-        VPT_HIP(hipMemsetAsync(d_stats.p, 0, n_stats * sizeof(vpt::TagClassStats), st));
+        VPT_HIP(hipMemsetAsync(d_stats.p, 0, n_stats * sizeof(vpt_train_stats), st));
         VPT_HIP(vpt::train_tag_solve(d_desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, eps, cost, solver, d_w.p,
                                      d_stats.p, st));
         std::vector<double> w(n_w);
-        std::vector<vpt::TagClassStats> stats(n_stats);
+        std::vector<vpt_train_stats> stats(n_stats);
         VPT_HIP(hipMemcpyAsync(w.data(), d_w.p, n_w * 8, hipMemcpyDeviceToHost, st));
-        VPT_HIP(hipMemcpyAsync(stats.data(), d_stats.p, n_stats * sizeof(vpt::TagClassStats), hipMemcpyDeviceToHost, st));
+        VPT_HIP(hipMemcpyAsync(stats.data(), d_stats.p, n_stats * sizeof(vpt_train_stats), hipMemcpyDeviceToHost, st));
         VPT_HIP(hipStreamSynchronize(st));
         for (size_t q = 0; q < small.size(); ++q) {
             TagProblem& Pb = t->tag_problems[small[q]];
             std::copy(w.begin() + descs[q].w, w.begin() + descs[q].w + Pb.w.size(), Pb.w.begin());
-            for (size_t c = 0; c < Pb.stats.size(); ++c) {
-                const vpt::TagClassStats& S = stats[descs[q].stats + c];
-                Pb.stats[c] = vpt_train_stats{S.iterations, S.cg_steps, S.gnorm0, S.gnorm, S.objective};
-            }
+            std::copy(stats.begin() + descs[q].stats, stats.begin() + descs[q].stats + Pb.stats.size(), Pb.stats.begin());
         }
         t->tag_summary.problems_in_kernel = descs.size();
         t->tag_summary.seconds_in_kernel = now_s() - t0;

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/vaporetto_hip.h"
 #include "layout.h"
 #include "tables.hpp"
 
@@ -457,12 +458,8 @@ struct TagSolveDesc {
     uint64_t rp, cols, cp, y, w, stats;   // where the problem's row pointers, nonzeros (CSR and CSC alike), column pointers, labels, weights and stats start
     uint32_t nf, l, k, pad;               // features (the bias is one more), rows, classes
 };
-struct TagClassStats {
-    uint32_t iterations, cg_steps;
-    double gnorm0, gnorm, objective;
-};
 bool train_tag_fits(uint64_t rows, uint64_t features);
 hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
-                           const uint32_t* y, double eps, double cost, int solver, double* w, TagClassStats* stats, hipStream_t st);
+                           const uint32_t* y, double eps, double cost, int solver, double* w, vpt_train_stats* stats, hipStream_t st);
 
 }  // namespace vpt

@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "device_common.h"
+#include "tron.h"
 
 namespace vpt {
 namespace {
@@ -373,26 +374,15 @@ __global__ __launch_bounds__(kTrainThreads) void scale_rows_kernel(uint64_t n, c
 __global__ __launch_bounds__(kTrainThreads) void loss_kernel(uint64_t n, const double* z, const double* y, double c, int solver, double* loss) {
     const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
     if (i >= n) return;
-    const double yz = y[i] * z[i];
-    if (solver == 0) loss[i] = yz >= 0 ? c * log(1 + exp(-yz)) : c * (-yz + log(1 + exp(yz)));
-    else { const double d = 1 - yz; loss[i] = d > 0 ? c * d * d : 0.0; }
+    loss[i] = tron_loss(y[i] * z[i], c, solver);
 }
 // ::grad: gz (the vector Xᵀ is applied to) and D (Hv's diagonal), from the same z
 __global__ __launch_bounds__(kTrainThreads) void grad_rows_kernel(uint64_t n, const double* z, const double* y, double c, int solver, double* gz, double* D) {
     const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
     if (i >= n) return;
-    const double yz = y[i] * z[i];
-    if (solver == 0) {
-        const double s = 1 / (1 + exp(-yz));
-        D[i] = c * s * (1 - s);
-        gz[i] = c * (s - 1) * y[i];
-    } else if (yz < 1) {
-        D[i] = 2 * c;
-        gz[i] = 2 * c * y[i] * (yz - 1);
-    } else {
-        D[i] = 0;
-        gz[i] = 0;
-    }
+    const TronRow t = tron_grad_row(y[i], y[i] * z[i], c, solver);
+    D[i] = t.D;
+    gz[i] = t.gz;
 }
 
 uint64_t tiles(uint64_t n) { return (n + kTile - 1) / kTile; }

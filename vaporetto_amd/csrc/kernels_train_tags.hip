@@ -7,17 +7,18 @@
 //   kind << 120 | c0 << 99 | .. | c4 << 15 | (n + 1) << 5 | (rel + 16)      (kernels_train.hip's TrainKey; left context, then right)
 // One pass counts, a scan places, one pass writes the example records (sentence, start, end, features) and the keys.
 //
-// The solver: a workgroup per (surface, slot) problem runs liblinear's TRON (tron.cpp as scikit-learn bundles it: CG without a
-// preconditioner, eps_cg = 0.1, from w = 0) for solvers 0 and 2 entirely inside the kernel, one class after another over the same
-// matrix (one solve for two classes).  The fp64 vectors live in LDS; the 0/1 matrix is read as CSR (Xv: a thread per row) and CSC
-// (Xᵀv: a thread per column) indices from global memory.  Every sum has a fixed shape: a thread adds its strided elements in order,
-// sixteen threads add sixteen partial sums each in order, and every thread adds those sixteen in order -- no float atomics, and the
-// scalars that steer the loop are the same bits in every thread.
+// The solver: a workgroup per (surface, slot) problem runs liblinear's TRON for solvers 0 and 2 entirely inside the kernel, one class
+// after another over the same matrix (one solve for two classes).  The algorithm is tron.h's, the same text the host driver of
+// capi_train.cpp runs; TagProb below is its backend here.  The fp64 vectors live in LDS; the 0/1 matrix is read as CSR (Xv: a thread
+// per row) and CSC (Xᵀv: a thread per column) indices from global memory.  Every sum has a fixed shape: a thread adds its strided
+// elements in order, sixteen threads add sixteen partial sums each in order, and every thread adds those sixteen in order -- no float
+// atomics, and the scalars that steer the loop are the same bits in every thread.
 #include "kernels.hpp"
 
 #include <cmath>
 
 #include "device_common.h"
+#include "tron.h"
 
 namespace vpt {
 namespace {
@@ -124,171 +125,104 @@ __device__ __forceinline__ double blk_dot(const double* a, const double* b, uint
     return blk_sum(s, red);
 }
 
+// the in-kernel backend of tron.h: one class of a problem, the workgroup's threads over vectors in LDS
 struct TagProb {
     const uint32_t *rp, *cols, *cp, *crow, *y;
-    uint32_t nf, l;
+    uint32_t nf, l, n, cls;
+    double c;
+    int solver;
     double *z, *D, *tmp, *red;
-};
+    TronVectors v;
 
-// z = Xv (the bias column last)
-__device__ __forceinline__ void tag_xv(const TagProb& Q, const double* v, double* out) {
-    for (uint32_t r = threadIdx.x; r < Q.l; r += kTagThreads) {
-        double s = 0;
-        for (uint32_t k = Q.rp[r]; k < Q.rp[r + 1]; ++k) s += v[Q.cols[k]];
-        out[r] = s + v[Q.nf];
-    }
-    __syncthreads();
-}
-// out = a + Xᵀu
-__device__ __forceinline__ void tag_add_xtv(const TagProb& Q, const double* a, const double* u, double* out) {
-    double b = 0;
-    for (uint32_t r = threadIdx.x; r < Q.l; r += kTagThreads) b += u[r];
-    b = blk_sum(b, Q.red);
-    for (uint32_t j = threadIdx.x; j < Q.nf; j += kTagThreads) {
-        double s = 0;
-        for (uint32_t k = Q.cp[j]; k < Q.cp[j + 1]; ++k) s += u[Q.crow[k]];
-        out[j] = a[j] + s;
-    }
-    if (threadIdx.x == 0) out[Q.nf] = a[Q.nf] + b;
-    __syncthreads();
-}
-__device__ __forceinline__ double tag_y(const TagProb& Q, uint32_t r, uint32_t cls) { return Q.y[r] == cls ? 1.0 : -1.0; }
-// l2r_lr_fun / l2r_l2_svc_fun::fun (liblinear linear.cpp); leaves z = Xx
-__device__ double tag_fun(const TagProb& Q, const double* x, uint32_t cls, double c, int solver) {
-    tag_xv(Q, x, Q.z);
-    double s = 0;
-    for (uint32_t r = threadIdx.x; r < Q.l; r += kTagThreads) {
-        const double yz = tag_y(Q, r, cls) * Q.z[r];
-        if (solver == 0) s += yz >= 0 ? c * log(1 + exp(-yz)) : c * (-yz + log(1 + exp(yz)));
-        else { const double d = 1 - yz; s += d > 0 ? c * d * d : 0.0; }
-    }
-    const double loss = blk_sum(s, Q.red);
-    return blk_dot(x, x, Q.nf + 1, Q.red) / 2.0 + loss;
-}
-// ::grad from the z of the last fun; keeps D for Hv
-__device__ void tag_grad(const TagProb& Q, const double* x, double* out, uint32_t cls, double c, int solver) {
-    for (uint32_t r = threadIdx.x; r < Q.l; r += kTagThreads) {
-        const double y = tag_y(Q, r, cls), yz = y * Q.z[r];
-        if (solver == 0) {
-            const double s = 1 / (1 + exp(-yz));
-            Q.D[r] = c * s * (1 - s);
-            Q.tmp[r] = c * (s - 1) * y;
-        } else if (yz < 1) {
-            Q.D[r] = 2 * c;
-            Q.tmp[r] = 2 * c * y * (yz - 1);
-        } else {
-            Q.D[r] = 0;
-            Q.tmp[r] = 0;
+    // out = Xx (the bias column last)
+    __device__ __forceinline__ void xv(const double* x, double* out) const {
+        for (uint32_t r = threadIdx.x; r < l; r += kTagThreads) {
+            double s = 0;
+            for (uint32_t k = rp[r]; k < rp[r + 1]; ++k) s += x[cols[k]];
+            out[r] = s + x[nf];
         }
+        __syncthreads();
     }
-    __syncthreads();
-    tag_add_xtv(Q, x, Q.tmp, out);
-}
-__device__ void tag_hv(const TagProb& Q, const double* v, double* out) {
-    tag_xv(Q, v, Q.tmp);
-    for (uint32_t r = threadIdx.x; r < Q.l; r += kTagThreads) Q.tmp[r] *= Q.D[r];
-    __syncthreads();
-    tag_add_xtv(Q, v, Q.tmp, out);
-}
+    // out = a + Xᵀu
+    __device__ __forceinline__ void add_xtv(const double* a, const double* u, double* out) const {
+        double b = 0;
+        for (uint32_t r = threadIdx.x; r < l; r += kTagThreads) b += u[r];
+        b = blk_sum(b, red);
+        for (uint32_t j = threadIdx.x; j < nf; j += kTagThreads) {
+            double s = 0;
+            for (uint32_t k = cp[j]; k < cp[j + 1]; ++k) s += u[crow[k]];
+            out[j] = a[j] + s;
+        }
+        if (threadIdx.x == 0) out[nf] = a[nf] + b;
+        __syncthreads();
+    }
+    __device__ __forceinline__ double target(uint32_t r) const { return y[r] == cls ? 1.0 : -1.0; }
+    __device__ double fun(const double* x) const {
+        xv(x, z);
+        double s = 0;
+        for (uint32_t r = threadIdx.x; r < l; r += kTagThreads) s += tron_loss(target(r) * z[r], c, solver);
+        const double loss = blk_sum(s, red);
+        return blk_dot(x, x, n, red) / 2.0 + loss;
+    }
+    __device__ void grad(const double* x, double* out) const {
+        for (uint32_t r = threadIdx.x; r < l; r += kTagThreads) {
+            const double yr = target(r);
+            const TronRow t = tron_grad_row(yr, yr * z[r], c, solver);
+            D[r] = t.D;
+            tmp[r] = t.gz;
+        }
+        __syncthreads();
+        add_xtv(x, tmp, out);
+    }
+    __device__ void hv(const double* x, double* out) const {
+        xv(x, tmp);
+        for (uint32_t r = threadIdx.x; r < l; r += kTagThreads) tmp[r] *= D[r];
+        __syncthreads();
+        add_xtv(x, tmp, out);
+    }
+    __device__ __forceinline__ double dot(const double* a, const double* b) const { return blk_dot(a, b, n, red); }
+    // the vector loops: a thread its strided elements, then the workgroup meets
+    template <typename F>
+    __device__ __forceinline__ void each(F f) const {
+        for (uint32_t i = threadIdx.x; i < n; i += kTagThreads) f(i);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void zero(double* x) const { each([=](uint32_t i) { x[i] = 0; }); }
+    __device__ __forceinline__ void copy(const double* x, double* out) const { each([=](uint32_t i) { out[i] = x[i]; }); }
+    __device__ __forceinline__ void add(const double* a, const double* b, double* out) const { each([=](uint32_t i) { out[i] = a[i] + b[i]; }); }
+    __device__ __forceinline__ void axpy(double a, const double* x, double* y_) const { each([=](uint32_t i) { y_[i] += a * x[i]; }); }
+    __device__ __forceinline__ void xpby(const double* x, double b, double* y_) const { each([=](uint32_t i) { y_[i] = b * y_[i] + x[i]; }); }
+    __device__ __forceinline__ void cg_start() const { each([=](uint32_t i) { v.s[i] = 0; v.r[i] = -v.g[i]; v.d[i] = -v.g[i]; }); }
+    __device__ __forceinline__ void cg_boundary(double a) const { each([=](uint32_t i) { v.s[i] += a * v.d[i]; v.r[i] += -a * v.Hd[i]; }); }
+    // exact CG ends within n steps; the cap only keeps a non-finite problem from spinning on the device
+    __device__ __forceinline__ bool cg_more(int k) const { return uint32_t(k) < 16 * n + 64; }
+    __device__ __forceinline__ bool ok() const { return true; }
+};
 
 __global__ __launch_bounds__(kTagThreads) void tag_solve_kernel(const TagSolveDesc* descs, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp,
                                                                   const uint32_t* crow, const uint32_t* y, double eps, double c, int solver,
-                                                                  double* w_out, TagClassStats* stats) {
+                                                                  double* w_out, vpt_train_stats* stats) {
     __shared__ double lds[kTagLdsDoubles + kTagThreads + 16];
     const TagSolveDesc P = descs[blockIdx.x];
     const uint32_t n = P.nf + 1, l = P.l, t = threadIdx.x;
     if (7ull * n + 3ull * l > kTagLdsDoubles) return;   // the host sends such a problem down the other path
     TagProb Q;
     Q.rp = rp + P.rp; Q.cols = cols + P.cols; Q.cp = cp + P.cp; Q.crow = crow + P.cols; Q.y = y + P.y;
-    Q.nf = P.nf; Q.l = l;
-    double *w = lds, *wn = w + n, *g = wn + n, *s = g + n, *r = s + n, *d = r + n, *Hd = d + n;
-    Q.z = Hd + n; Q.D = Q.z + l; Q.tmp = Q.D + l; Q.red = lds + kTagLdsDoubles;
-    const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sigma1 = 0.25, sigma2 = 0.5, sigma3 = 4;
-    const int max_iter = 1000;
+    Q.nf = P.nf; Q.l = l; Q.n = n; Q.c = c; Q.solver = solver;
+    double* const w = lds;
+    Q.v = TronVectors{w, w + n, w + 2 * n, w + 3 * n, w + 4 * n, w + 5 * n, w + 6 * n};
+    Q.z = w + 7 * n; Q.D = Q.z + l; Q.tmp = Q.D + l; Q.red = lds + kTagLdsDoubles;
     const uint32_t n_solve = P.k == 2 ? 1 : P.k;
     for (uint32_t cls = 0; cls < n_solve; ++cls) {
+        Q.cls = cls;
         double pc = 0;
         for (uint32_t i = t; i < l; i += kTagThreads) pc += Q.y[i] == cls ? 1.0 : 0.0;
-        const double pos = blk_sum(pc, Q.red), neg = double(l) - pos;
-        // liblinear's primal tolerance (linear.cpp train_one): eps * max(min(pos, neg), 1) / l
-        const double tol = eps * fmax(fmin(pos, neg), 1.0) / double(l);
-        for (uint32_t i = t; i < n; i += kTagThreads) w[i] = 0;
-        __syncthreads();
-        double f = tag_fun(Q, w, cls, c, solver);
-        tag_grad(Q, w, g, cls, c, solver);
-        double delta = sqrt(blk_dot(g, g, n, Q.red));
-        const double gnorm1 = delta;
-        double gnorm = gnorm1;
-        const bool search = !(gnorm <= tol * gnorm1);
-        int iter = 1, cg_total = 0;
-        while (iter <= max_iter && search) {
-            // trcg
-            for (uint32_t i = t; i < n; i += kTagThreads) { s[i] = 0; r[i] = -g[i]; d[i] = -g[i]; }
-            __syncthreads();
-            const double cgtol = 0.1 * sqrt(blk_dot(g, g, n, Q.red));
-            double rTr = blk_dot(r, r, n, Q.red);
-            // exact CG ends within n steps; the cap only keeps a non-finite problem from spinning on the device
-            for (uint32_t cg = 0; cg < 16 * n + 64; ++cg) {
-                // tron.cpp takes dnrm2(r) anew here although rTr holds the same product: kept, so that the bits are liblinear's
-                if (sqrt(blk_dot(r, r, n, Q.red)) <= cgtol) break;
-                cg_total++;
-                tag_hv(Q, d, Hd);
-                double alpha = rTr / blk_dot(d, Hd, n, Q.red);
-                for (uint32_t i = t; i < n; i += kTagThreads) s[i] += alpha * d[i];
-                __syncthreads();
-                if (sqrt(blk_dot(s, s, n, Q.red)) > delta) {
-                    alpha = -alpha;
-                    for (uint32_t i = t; i < n; i += kTagThreads) s[i] += alpha * d[i];
-                    __syncthreads();
-                    const double std_ = blk_dot(s, d, n, Q.red), sts = blk_dot(s, s, n, Q.red), dtd = blk_dot(d, d, n, Q.red), dsq = delta * delta;
-                    const double rad = sqrt(std_ * std_ + dtd * (dsq - sts));
-                    alpha = std_ >= 0 ? (dsq - sts) / (std_ + rad) : (rad - std_) / dtd;
-                    for (uint32_t i = t; i < n; i += kTagThreads) { s[i] += alpha * d[i]; r[i] += -alpha * Hd[i]; }
-                    __syncthreads();
-                    break;
-                }
-                alpha = -alpha;
-                for (uint32_t i = t; i < n; i += kTagThreads) r[i] += alpha * Hd[i];
-                __syncthreads();
-                const double rnew = blk_dot(r, r, n, Q.red);
-                const double beta = rnew / rTr;
-                for (uint32_t i = t; i < n; i += kTagThreads) d[i] = beta * d[i] + r[i];
-                __syncthreads();
-                rTr = rnew;
-            }
-            for (uint32_t i = t; i < n; i += kTagThreads) wn[i] = w[i] + s[i];
-            __syncthreads();
-            const double gs = blk_dot(g, s, n, Q.red);
-            const double prered = -0.5 * (gs - blk_dot(s, r, n, Q.red));
-            const double fnew = tag_fun(Q, wn, cls, c, solver);
-            const double actred = f - fnew;
-            const double snorm = sqrt(blk_dot(s, s, n, Q.red));
-            if (iter == 1) delta = fmin(delta, snorm);
-            const double alpha = (fnew - f - gs <= 0) ? sigma3 : fmax(sigma1, -0.5 * (gs / (fnew - f - gs)));
-            if (actred < eta0 * prered) delta = fmin(fmax(alpha, sigma1) * snorm, sigma2 * delta);
-            else if (actred < eta1 * prered) delta = fmax(sigma1 * delta, fmin(alpha * snorm, sigma2 * delta));
-            else if (actred < eta2 * prered) delta = fmax(sigma1 * delta, fmin(alpha * snorm, sigma3 * delta));
-            else delta = fmax(delta, fmin(alpha * snorm, sigma3 * delta));
-            if (actred > eta0 * prered) {
-                iter++;
-                for (uint32_t i = t; i < n; i += kTagThreads) w[i] = wn[i];
-                __syncthreads();
-                f = fnew;
-                tag_grad(Q, w, g, cls, c, solver);
-                gnorm = sqrt(blk_dot(g, g, n, Q.red));
-                if (gnorm <= tol * gnorm1) break;
-            }
-            if (f < -1.0e+32) break;
-            if (fabs(actred) <= 0 && prered <= 0) break;
-            if (fabs(actred) <= 1.0e-12 * fabs(f) && fabs(prered) <= 1.0e-12 * fabs(f)) break;
-        }
+        const vpt_train_stats st = tron(Q, tron_tolerance(eps, blk_sum(pc, Q.red), double(l)));
         for (uint32_t i = t; i < n; i += kTagThreads) {
             w_out[P.w + uint64_t(cls) * n + i] = w[i];
             if (P.k == 2) w_out[P.w + n + i] = -w[i];   // feature_coefficient(f, 1) = -feature_coefficient(f, 0)
         }
         if (t == 0) {
-            TagClassStats st;
-            st.iterations = uint32_t(iter - 1); st.cg_steps = uint32_t(cg_total); st.gnorm0 = gnorm1; st.gnorm = gnorm; st.objective = f;
             stats[P.stats + cls] = st;
             if (P.k == 2) stats[P.stats + 1] = st;
         }
@@ -457,7 +391,7 @@ hipError_t train_tag_flags(const uint32_t* occ, const uint32_t* order, uint64_t 
 }
 bool train_tag_fits(uint64_t rows, uint64_t features) { return 7 * (features + 1) + 3 * rows <= kTagLdsDoubles; }
 hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
-                           const uint32_t* y, double eps, double cost, int solver, double* w, TagClassStats* stats, hipStream_t st) {
+                           const uint32_t* y, double eps, double cost, int solver, double* w, vpt_train_stats* stats, hipStream_t st) {
     if (n_prob == 0) return hipSuccess;
     hipLaunchKernelGGL(tag_solve_kernel, dim3(n_prob), dim3(kTagThreads), 0, st, descs, rp, cols, cp, crow, y, eps, cost, solver, w, stats);
     return hipGetLastError();
