@@ -51,13 +51,14 @@ fn check(st: c_int) -> Result<()> {
 }
 
 /// `KyteaFullwidthFilter` before scoring, `KyteaWsConstFilter(t)` / `SplitLinebreaksFilter` on the labels (predict/src/main.rs:126-134).
-/// `ConcatGraphemeClustersFilter` (`--wsconst G`, predict/src/main.rs:101-104) has no flag: it segments by UAX #29 and only edits labels, so
-/// it stays on the host -- after `predict_batch` run `vaporetto_rules`' own filter over the sentences (their boundaries are the device's
-/// labels by then), then `fill_tags` / `write_tokenized_text` as the CLI does; `tokenize_lines` cannot take it.
+/// `ConcatGraphemeClustersFilter` (`--wsconst G`, predict/src/main.rs:101-104) is `FLAG_CONCAT_GRAPHEMES`: a launch behind the scoring
+/// launch that always runs after the other label filters; `concat_graphemes` applies it to labels of the caller's for any other order.
 pub const FLAG_KYTEA_FULLWIDTH: u32 = 1;
 pub const FLAG_SPLIT_LINEBREAKS: u32 = 1 << 7;
 /// With `FLAG_SPLIT_LINEBREAKS`: that filter runs before the wsconst ones (the order of vaporetto_tantivy's post-filters).
 pub const FLAG_LINEBREAKS_FIRST: u32 = 1 << 8;
+/// `ConcatGraphemeClustersFilter` on the device, after every other label filter (also a bit of `token_stream_batch`'s `wsconst_flags`: the adapter's G).
+pub const FLAG_CONCAT_GRAPHEMES: u32 = 1 << 9;
 pub const fn flag_wsconst(char_type: u8) -> u32 {
     1 << char_type
 }
@@ -127,7 +128,7 @@ impl HipPredictor {
     }
 
     /// `VaporettoTokenizer::token_stream` (vaporetto_tantivy/src/lib.rs:160-192) for a batch of documents: `utf8[boff[i] .. boff[i + 1]]` is document i
-    /// (empty ones are allowed), `wsconst_flags` the `flag_wsconst` bits of the adapter's D R H T K O.  Returns `(token_offsets, token_ends)`: document i
+    /// (empty ones are allowed), `wsconst_flags` the `flag_wsconst` bits of the adapter's D R H T K O and `FLAG_CONCAT_GRAPHEMES` for its G.  Returns `(token_offsets, token_ends)`: document i
     /// owns `token_ends[token_offsets[i] .. token_offsets[i + 1]]`, the byte offset behind every one of its tokens from its first byte (the adapter's
     /// `boundary_pos`).  The C side trusts the sizes, so they are checked here.
     pub fn token_stream_batch(&self, utf8: &[u8], boff: &[u64], wsconst_flags: u32) -> Result<(Vec<u64>, Vec<u32>)> {
@@ -144,6 +145,20 @@ impl HipPredictor {
         })?;
         ends.truncate(offsets[n] as usize);
         Ok((offsets, ends))
+    }
+
+    /// `ConcatGraphemeClustersFilter` on labels of the caller's (`labels[ooff[i] + b]`: boundary b of sentence i, `ooff` from
+    /// `vpt_count_boundaries`), in place, on the device; `fullwidth`: the clusters of the `KyteaFullwidthFilter` image.  The sizes are checked here.
+    pub fn concat_graphemes(&self, utf8: &[u8], boff: &[u64], ooff: &[u64], fullwidth: bool, labels: &mut [u8]) -> Result<()> {
+        let bad = |what: &str| Err(HipError::InvalidArgument(format!("InvalidArgumentError: {}", what)));
+        if boff.is_empty() || ooff.len() != boff.len() { return bad("offsets: n + 1 entries each"); }
+        let n = boff.len() - 1;
+        if boff.windows(2).any(|w| w[1] < w[0]) || ooff.windows(2).any(|w| w[1] < w[0]) { return bad("offsets: must not decrease"); }
+        if (utf8.len() as u64) < boff[n] { return bad("utf8: shorter than byte_offsets[n]"); }
+        if (labels.len() as u64) < ooff[n] { return bad("labels: shorter than out_offsets[n]"); }
+        check(unsafe {
+            ffi::vpt_concat_graphemes_batch(self.raw, utf8.as_ptr(), boff.as_ptr(), n, ooff.as_ptr(), if fullwidth { FLAG_KYTEA_FULLWIDTH } else { 0 }, labels.as_mut_ptr())
+        })
     }
 
     /// `Predictor::serialize_to_vec` / `deserialize_from_slice_unchecked` (predictor.rs:640-664), in this library's own format

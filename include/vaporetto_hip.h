@@ -54,6 +54,19 @@ enum { VPT_FLAG_SPLIT_LINEBREAKS = 1 << 7, VPT_FLAG_ALL = 0xFF };
  * shows where a linebreak stands next to a char of its own type under its wsconst flag ('\n', '\r' and ' ' are Other): "a\n\nb" with
  * VPT_FLAG_WSCONST(6) gives a | \n\n | b with this bit, a | \n | \n | b without.  Not part of VPT_FLAG_ALL. */
 enum { VPT_FLAG_LINEBREAKS_FIRST = 1 << 8 };
+/* VPT_FLAG_CONCAT_GRAPHEMES: ConcatGraphemeClustersFilter (vaporetto_rules/src/sentence_filters/concat_grapheme_clusters.rs:10-36; the `G` of
+ * --wsconst and of the tantivy adapter) -- every label inside an extended grapheme cluster (UAX #29) of the text as it was scored (the
+ * KyteaFullwidthFilter image under VPT_FLAG_KYTEA_FULLWIDTH) becomes NotWordBoundary, Unknown labels included.  A launch of its own behind the
+ * scoring launch, position-parallel (vaporetto_amd/csrc/kernels_graphemes.hip).  It and the VPT_FLAG_WSCONST filters only clear labels and
+ * commute; SplitLinebreaksFilter sets them, so the order matters there, and on the device this filter always runs LAST:
+ *   with VPT_FLAG_LINEBREAKS_FIRST   split, wsconst, graphemes -- the tantivy adapter's result for any place of `G` in its string
+ *                                    (vaporetto_tantivy/src/lib.rs:69-86): "\r\n" stays joined;
+ *   without it                       wsconst, split, graphemes.
+ * A caller that wants another order runs vpt_concat_graphemes_batch[_device] (below) between calls of its own.  Accepted wherever the label
+ * post-filter flags are (vpt_predict_batch_flags, vpt_batch_set_flags, vpt_tokenize_batch, vpt_predict_listing_batch, vpt_evaluate_batch,
+ * vpt_predict_batch_sharded, and as a bit of vpt_token_stream_batch's wsconst_flags).  Not part of VPT_FLAG_ALL.  The classes are those of
+ * include/vaporetto_grapheme_tables.inc. */
+enum { VPT_FLAG_CONCAT_GRAPHEMES = 1 << 9 };
 
 typedef struct vpt_predictor vpt_predictor;
 typedef struct vpt_batch vpt_batch;
@@ -419,8 +432,8 @@ vpt_status vpt_predict_listing_batch_device(const vpt_predictor *p, vpt_batch *b
  *   any other bit is VPT_INVALID_ARGUMENT "Could not parse a wsconst value"), the spans counted on the caller's bytes.  Only the text crosses
  *   PCIe on the way in and 8 (n + 1) + 4 x tokens bytes on the way out: char counting, scoring, filters and spans run on the device, large batches
  *   as chunks of whole documents through vpt_tokenize_batch's pipeline.  A NUL in a document (Sentence::from_raw(..).unwrap() panics there,
- *   lib.rs:173) is VPT_INVALID_ARGUMENT "text: must not contain NULL".  ("G", ConcatGraphemeClustersFilter, is a host filter: predict with
- *   VPT_FLAG_LINEBREAKS_FIRST, the filter, vpt_token_spans_batch -- as include/vaporetto_hip.hpp and vaporetto_amd/api.py do.) */
+ *   lib.rs:173) is VPT_INVALID_ARGUMENT "text: must not contain NULL".  "G" is VPT_FLAG_CONCAT_GRAPHEMES in wsconst_flags: the filter runs last,
+ *   which is the adapter's result wherever "G" stands in its string. */
 vpt_status vpt_token_spans_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
                                         const uint64_t *d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t *d_labels,
                                         uint64_t *d_token_offsets, uint32_t *d_token_ends, uint64_t capacity, void *hip_stream);
@@ -429,6 +442,21 @@ vpt_status vpt_token_spans_batch(const vpt_predictor *p, const uint8_t *utf8, co
                                  uint64_t capacity);
 vpt_status vpt_token_stream_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
                                   unsigned wsconst_flags, uint64_t *token_offsets_out, uint32_t *token_ends_out, uint64_t capacity);
+
+/* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
+ * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
+ * other label is written.  out_offsets from vpt_count_boundaries.
+ * vpt_concat_graphemes_batch: host buffers; flags: 0 or VPT_FLAG_KYTEA_FULLWIDTH (the clusters of the KyteaFullwidthFilter image -- what a
+ *   predict call with that flag scored); anything else is VPT_INVALID_ARGUMENT "flags: unknown bit".
+ * vpt_concat_graphemes_batch_device: device pointers, asynchronous on hip_stream, VPT_FLAG_KYTEA_FULLWIDTH from vpt_batch_set_flags, the verdict
+ *   (empty sentences, NUL, offsets that do not match the text) at vpt_batch_sync.
+ * vpt_concat_graphemes_tile: the chars of a tile of the kernel (the tests place clusters across its edges). */
+vpt_status vpt_concat_graphemes_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
+                                      const uint64_t *out_offsets, unsigned flags, uint8_t *labels);
+vpt_status vpt_concat_graphemes_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                             const uint64_t *d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint8_t *d_labels,
+                                             void *hip_stream);
+vpt_status vpt_concat_graphemes_tile(uint32_t *n_chars);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Sentence::from_tokenized over a batch                                                  (sentence.rs:285-514)

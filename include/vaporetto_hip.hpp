@@ -303,10 +303,9 @@ private:
 // vaporetto_tantivy's VaporettoTokenizer (vaporetto_tantivy/src/lib.rs:62-229) for callers that are not Rust: KyteaFullwidthFilter always,
 // Predictor::new(model, false), SplitLinebreaksFilter first, then one filter per char of `wsconst` -- D R H T K O: KyteaWsConstFilter of that type,
 // G: ConcatGraphemeClustersFilter; anything else throws "Could not parse a wsconst value" (lib.rs:69-86).  A Token is tantivy's as
-// VaporettoTokenStream fills it (lib.rs:204-219): byte offsets into the caller's text.  Without G a batch is ONE call (vpt_token_stream_batch: the
-// text goes to the device, the spans come back); with G three: predict with VPT_FLAG_LINEBREAKS_FIRST, the grapheme filter on the host
-// (vaporetto_grapheme.hpp), vpt_token_spans_batch.  (The reference runs that filter on the normalised text; the fullwidth map sends chars without a
-// grapheme-break property to chars without one, so the caller's text has the same clusters.)
+// VaporettoTokenStream fills it (lib.rs:204-219): byte offsets into the caller's text.  A batch is ONE call (vpt_token_stream_batch: the text
+// goes to the device, the spans come back), G included: VPT_FLAG_CONCAT_GRAPHEMES runs last on the device, which is the adapter's result for any
+// place of G in the string.
 struct Token {
     std::string text;
     size_t offset_from, offset_to, position, position_length;
@@ -316,7 +315,7 @@ public:
     VaporettoTokenizer(const Model& model, const std::string& wsconst, int device_id = 0) : predictor_(model, false, device_id) {
         for (char c : wsconst) {
             const char* at = std::char_traits<char>::find("DRHTKO", 6, c);
-            if (c == 'G') graphemes_ = true;
+            if (c == 'G') flags_ |= VPT_FLAG_CONCAT_GRAPHEMES;
             else if (at) flags_ |= VPT_FLAG_WSCONST(unsigned(at - "DRHTKO") + 1);
             else throw VaporettoError(VaporettoError::InvalidArgument, "Could not parse a wsconst value");
         }
@@ -339,23 +338,7 @@ public:
         const uint8_t* utf8 = reinterpret_cast<const uint8_t*>(text.data());
         std::vector<uint64_t> toff(doc.size() + 1);
         std::vector<uint32_t> ends(text.size());
-        if (!graphemes_) {
-            detail::check(vpt_token_stream_batch(predictor_.raw(), utf8, boff.data(), doc.size(), flags_, toff.data(), ends.data(), ends.size()));
-        } else {
-            std::vector<uint64_t> ooff(doc.size() + 1);
-            detail::check(vpt_count_boundaries(utf8, boff.data(), doc.size(), ooff.data()));
-            std::vector<uint8_t> labels(size_t(ooff.back()) + 1);
-            detail::check(vpt_predict_batch_flags(predictor_.raw(), utf8, boff.data(), doc.size(), nullptr, labels.data(), ooff.data(),
-                                                  VPT_FLAG_KYTEA_FULLWIDTH | VPT_FLAG_SPLIT_LINEBREAKS | VPT_FLAG_LINEBREAKS_FIRST | flags_));
-            for (size_t k = 0; k < doc.size(); ++k) {
-                size_t at = size_t(ooff[k]);
-                for (uint32_t n : grapheme_cluster_lengths(texts[doc[k]])) {
-                    for (uint32_t j = 0; j + 1 < n; ++j) labels[at + j] = VPT_NOT_WORD_BOUNDARY;
-                    at += n;
-                }
-            }
-            detail::check(vpt_token_spans_batch(predictor_.raw(), utf8, boff.data(), doc.size(), ooff.data(), labels.data(), toff.data(), ends.data(), ends.size()));
-        }
+        detail::check(vpt_token_stream_batch(predictor_.raw(), utf8, boff.data(), doc.size(), flags_, toff.data(), ends.data(), ends.size()));
         for (size_t k = 0; k < doc.size(); ++k) {
             const std::string& t = texts[doc[k]];
             const size_t n = size_t(toff[k + 1] - toff[k]);
@@ -373,7 +356,6 @@ public:
 private:
     Predictor predictor_;
     unsigned flags_ = 0;
-    bool graphemes_ = false;
 };
 
 inline void Sentence::fill_tags() {

@@ -15,6 +15,7 @@ VPT_OK, VPT_INVALID_MODEL, VPT_INVALID_ARGUMENT, VPT_RUNTIME_ERROR = 0, 1, 2, 3
 VPT_FLAG_KYTEA_FULLWIDTH = 1
 VPT_FLAG_SPLIT_LINEBREAKS = 1 << 7
 VPT_FLAG_LINEBREAKS_FIRST = 1 << 8
+VPT_FLAG_CONCAT_GRAPHEMES = 1 << 9
 VPT_LISTING_SCORES, VPT_LISTING_TAG_SCORES, VPT_LISTING_TAGGED, VPT_LISTING_NO_NORM_ORDER = 1, 2, 4, 8
 VPT_EVAL_TAGS_NONE, VPT_EVAL_TAGS_GOLD, VPT_EVAL_TAGS_PREDICTED = 0, 1, 2
 
@@ -105,6 +106,9 @@ SIGNATURES = {
     "vpt_token_spans_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, C.c_uint64, _P]),
     "vpt_token_spans_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_uint64]),
     "vpt_token_stream_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, C.c_uint64]),
+    "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
+    "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
+    "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
     "vpt_predictor_max_tag_listing": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vpt_predict_listing_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, C.c_uint, _P, _P, _P, C.c_uint64, _P]),
     "vpt_predict_listing_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, C.c_uint, _P, C.c_uint64, _P, _P]),

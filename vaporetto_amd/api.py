@@ -96,14 +96,17 @@ class KyteaFullwidthFilter:
 
 class ConcatGraphemeClustersFilter:
     """vaporetto_rules/src/sentence_filters/concat_grapheme_clusters.rs:10-36 (the CLI's `--wsconst G`, predict/src/main.rs:101-104): a
-    sentence filter that runs on the HOST between predict and fill_tags -- every boundary inside an extended grapheme cluster (UAX #29)
-    becomes NotWordBoundary, so a ZWJ sequence or a base + modifier is never cut.  The reference segments with the `unicode-segmentation`
+    sentence filter between predict and fill_tags -- every boundary inside an extended grapheme cluster (UAX #29) becomes
+    NotWordBoundary, so a ZWJ sequence or a base + modifier is never cut.  THIS class is the host form (the oracle of the device filter's
+    tests, and for callers that want another order); `wsconst=("G", ..)` everywhere in this module is VPT_FLAG_CONCAT_GRAPHEMES, the
+    same filter as a launch on the device behind the scoring launch (Predictor.concat_graphemes_packed: on the caller's labels).  The reference segments with the `unicode-segmentation`
     crate (1.12.0); here the clusters come from the `regex` module's \\X, whichever Unicode version that module carries (the crate's and
     the module's rules agree on everything the reference's tests hold: concat_grapheme_clusters.rs:43-88).  It only CLEARS boundaries, so it
     commutes with KyteaWsConstFilter (which clears too) -- but not with SplitLinebreaksFilter, which SETS the boundary between "\r" and "\n"
     while CR LF is one cluster: the reference applies its filters in the caller's order (predict/src/main.rs:130-134);
-    `Predictor.tokenize(wsconst=("G", ..), split_linebreaks=True)` has ONE fixed order -- the device's label flags (wsconst types, then
-    split_linebreaks), then "G" on the host -- so "\r\n" stays joined there.  A caller that wants the other order runs this filter itself
+    on the device "G" always runs LAST -- wsconst types, split_linebreaks, "G" (`Predictor.tokenize(wsconst=("G", ..),
+    split_linebreaks=True)`), or with linebreaks_first split_linebreaks, wsconst types, "G" (the tantivy adapter's result for any place of
+    "G" in its string) -- so "\r\n" stays joined.  A caller that wants the other order runs this filter (or concat_graphemes_packed) itself
     between `predict_packed(.., wsconst=.., split_linebreaks=False)` and its own SplitLinebreaksFilter pass."""
 
     _X = None
@@ -682,28 +685,14 @@ class Predictor:
                               fullwidth: bool = True, wsconst: Sequence = (), no_norm_order: bool = False, split_linebreaks: bool = False):
         """The `predict` CLI's output for these lines (predict/src/main.rs:122-176) as the device made it: (uint8 arena, uint64 [S+1] offsets
         of the lines in it).  Per line T, the --scores block and the --tag-scores block, in the normalising loop's order or (no_norm_order)
-        the --no-norm loop's.  `wsconst` as for tokenize: "G" takes the three-call path (predict, ConcatGraphemeClustersFilter on the host,
-        the listing of the filtered labels)."""
+        the --no-norm loop's.  `wsconst` as for tokenize ("G": VPT_FLAG_CONCAT_GRAPHEMES, in the same one call)."""
         if not texts:
             return np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64)
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
         listing = ((_lib.VPT_LISTING_SCORES if scores else 0) | (_lib.VPT_LISTING_TAG_SCORES if tag_scores else 0) |
                    (_lib.VPT_LISTING_TAGGED if tagged else 0) | (_lib.VPT_LISTING_NO_NORM_ORDER if no_norm_order else 0))
-        graphemes = any(isinstance(t, str) and t == "G" for t in wsconst)
-        types = [int(t) for t in wsconst if not (isinstance(t, str) and t == "G")]
-        if graphemes:
-            sc, labels, ooff = self.predict_packed(utf8, boff, fullwidth=fullwidth, wsconst=tuple(types), split_linebreaks=split_linebreaks)
-            norm = KyteaFullwidthFilter()
-            ConcatGraphemeClustersFilter().filter_packed([norm.filter(t) for t in texts] if fullwidth else texts, ooff, labels)
-            out, offs = self.predict_listing_packed(utf8, boff, listing, flags=_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, scores=sc, labels=labels)
-        else:
-            flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0
-            for t in types:
-                flags |= _lib.VPT_FLAG_WSCONST(t)
-            if split_linebreaks:
-                flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
-            out, offs = self.predict_listing_packed(utf8, boff, listing, flags=flags)
-        return out, offs
+        flags = (_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0) | _label_flags(wsconst, split_linebreaks)
+        return self.predict_listing_packed(utf8, boff, listing, flags=flags)
 
     def tokenize_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, tagged: bool = False, flags: int = 0,
                         text_out: Optional[np.ndarray] = None, offsets_out: Optional[np.ndarray] = None):
@@ -728,26 +717,14 @@ class Predictor:
                  split_linebreaks: bool = False) -> List[str]:
         """Lines in, tokenized lines out (vpt_tokenize_batch): the CLI's loop (predict/src/main.rs:122-176) for a batch,
         with char counting, scoring, post-filters, tagging and the writer on the device.  `wsconst`: CharacterType values (the
-        KyteaWsConstFilter of that type, on the device) and / or "G" (ConcatGraphemeClustersFilter, predict/src/main.rs:101-104: on the
-        host -- the batch then takes three calls, predict / the filter on the labels / fill_tags + writer, instead of one)."""
+        KyteaWsConstFilter of that type) and / or "G" (ConcatGraphemeClustersFilter, predict/src/main.rs:101-104: VPT_FLAG_CONCAT_GRAPHEMES, a
+        launch behind the scoring launch that runs after the other label filters) -- one call either way."""
         if not texts:
             return []
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
         S = len(texts)
-        graphemes = any(isinstance(t, str) and t == "G" for t in wsconst)
-        types = [int(t) for t in wsconst if not (isinstance(t, str) and t == "G")]
-        if graphemes:
-            _, labels, ooff = self.predict_packed(utf8, boff, fullwidth=fullwidth, wsconst=tuple(types), split_linebreaks=split_linebreaks)
-            norm = KyteaFullwidthFilter()
-            ConcatGraphemeClustersFilter().filter_packed([norm.filter(t) for t in texts] if fullwidth else texts, ooff, labels)
-            text, toff = self.write_tokenized_packed(utf8, boff, ooff, labels, tagged=tagged, fullwidth=fullwidth)
-        else:
-            flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0
-            for t in types:
-                flags |= _lib.VPT_FLAG_WSCONST(t)
-            if split_linebreaks:
-                flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
-            text, toff = self.tokenize_packed(utf8, boff, tagged=tagged, flags=flags)
+        flags = (_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0) | _label_flags(wsconst, split_linebreaks)
+        text, toff = self.tokenize_packed(utf8, boff, tagged=tagged, flags=flags)
         raw = bytes(text)
         return [raw[int(toff[i]):int(toff[i + 1])].decode("utf-8") for i in range(S)]
 
@@ -861,18 +838,13 @@ class Predictor:
                 start, valid = e + 1, True
 
     def predict_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, fullwidth: bool = False,
-                       wsconst: Sequence[int] = (), split_linebreaks: bool = False, linebreaks_first: bool = False):
+                       wsconst: Sequence = (), split_linebreaks: bool = False, linebreaks_first: bool = False):
         """utf8: uint8[total bytes]; byte_offsets: uint64[S+1].  Returns (scores, labels, out_offsets).
         fullwidth: score the text as KyteaFullwidthFilter would rewrite it (the CLI's default normalisation).
-        wsconst: CharacterTypes for KyteaWsConstFilter; split_linebreaks: SplitLinebreaksFilter (labels only), after the wsconst filters
-        unless linebreaks_first (VPT_FLAG_LINEBREAKS_FIRST: the order of vaporetto_tantivy's post-filters)."""
-        flags = _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0
-        for t in wsconst:
-            flags |= _lib.VPT_FLAG_WSCONST(int(t))
-        if split_linebreaks:
-            flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
-        if linebreaks_first:
-            flags |= _lib.VPT_FLAG_LINEBREAKS_FIRST
+        wsconst: CharacterTypes for KyteaWsConstFilter and / or "G" (ConcatGraphemeClustersFilter: VPT_FLAG_CONCAT_GRAPHEMES, always the last
+        filter); split_linebreaks: SplitLinebreaksFilter (labels only), after the wsconst filters unless linebreaks_first
+        (VPT_FLAG_LINEBREAKS_FIRST: the order of vaporetto_tantivy's post-filters)."""
+        flags = (_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0) | _label_flags(wsconst, split_linebreaks, linebreaks_first)
         L = _lib.load()
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
@@ -889,6 +861,21 @@ class Predictor:
         if st != _lib.VPT_OK:
             _raise(st)
         return scores[:nb], labels[:nb], ooff
+
+    def concat_graphemes_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
+                                fullwidth: bool = False) -> np.ndarray:
+        """vpt_concat_graphemes_batch: ConcatGraphemeClustersFilter on the CALLER'S labels (uint8 per boundary, 0 / 1 / 2), on the device -- a
+        copy with every label inside an extended grapheme cluster cleared; fullwidth: the clusters of the KyteaFullwidthFilter image."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        out_offsets = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        out = np.array(labels, dtype=np.uint8, copy=True)
+        lab = out if len(out) else np.zeros(1, dtype=np.uint8)
+        st = _lib.load().vpt_concat_graphemes_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, len(byte_offsets) - 1, out_offsets.ctypes.data,
+                                                    _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, lab.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return out
 
     def token_spans_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray):
         """vpt_token_spans_batch: the token spans (vaporetto_tantivy/src/lib.rs:183-192) of a packed batch for the CALLER'S labels, on the
@@ -914,10 +901,10 @@ class Predictor:
                             offsets_out: Optional[np.ndarray] = None):
         """vpt_token_stream_batch: VaporettoTokenizer::token_stream (vaporetto_tantivy/src/lib.rs:160-192) for a packed batch of documents
         (empty ones allowed) -- KyteaFullwidthFilter, predict, SplitLinebreaksFilter, the wsconst filters, the spans, all on the device.
-        `wsconst`: chars of "DRHTKO" ("G" is a host filter: VaporettoTokenizer takes that path).  Returns (token_offsets, token_ends) as
+        `wsconst`: chars of "DRHTKOG" ("G": ConcatGraphemeClustersFilter, the last filter wherever it stands).  Returns (token_offsets, token_ends) as
         token_spans_packed; `ends_out` / `offsets_out` may be preallocated (pinned) arrays, ends_out of one uint32 per text byte."""
         L = _lib.load()
-        flags = wsconst_flags(wsconst)
+        flags = wsconst_flags(wsconst, allow_graphemes=True)
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
         S = len(byte_offsets) - 1
@@ -966,8 +953,8 @@ class Predictor:
     def evaluate(self, lines: Sequence[str], predict_tags: bool = False, wsconst: Sequence = (), no_norm: bool = False) -> dict:
         """The `evaluate` CLI (evaluate/src/main.rs:91-193) over tokenized lines: empty lines are skipped, every other line must parse.
         wsconst: CharacterType values and / or "G".  The "(line N)" of a parse error counts the given lines, empty ones included.  Returns the counters (tp, tn, fp, fn, n_sys, n_ref, n_cor, n_sentences) and the
-        P / R / F1 of both metrics (char_*, word_*; NaN for 0 / 0).  Without "G" the whole pipeline is one call (vpt_evaluate_batch);
-        with "G" the grapheme filter runs on the host between the device's predict and its fill_tags + compare."""
+        P / R / F1 of both metrics (char_*, word_*; NaN for 0 / 0).  The whole pipeline is one call (vpt_evaluate_batch), "G"
+        (VPT_FLAG_CONCAT_GRAPHEMES) included: the filter's launch sits between a chunk's scoring and its fill_tags + compare."""
         if predict_tags and not self._predict_tags:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: this predictor is created with predict_tags = false")
         index = [k for k, ln in enumerate(lines) if ln]   # the input line of every line evaluated (errors name the input's line)
@@ -981,63 +968,14 @@ class Predictor:
             raise VaporettoError(e.kind, str(e)[:m.start()] + " (line %d)" % index[int(m.group(1))]) from None
 
     def _evaluate(self, lines, predict_tags, wsconst, no_norm) -> dict:
-        graphemes = any(isinstance(t, str) and t == "G" for t in wsconst)
-        types = [int(t) for t in wsconst if not (isinstance(t, str) and t == "G")]
-        flags = 0 if no_norm else _lib.VPT_FLAG_KYTEA_FULLWIDTH
-        for t in types:
-            flags |= _lib.VPT_FLAG_WSCONST(t)
+        flags = (0 if no_norm else _lib.VPT_FLAG_KYTEA_FULLWIDTH) | _label_flags(wsconst)
         utf8, boff = pack_texts([ln.encode("utf-8") for ln in lines])
         counts = np.zeros(8, dtype=np.uint64)
-        if not graphemes or not lines:
-            st = _lib.load().vpt_evaluate_batch(self._h, utf8.ctypes.data, boff.ctypes.data, len(lines), flags, int(bool(predict_tags)),
-                                                counts.ctypes.data)
-            if st != _lib.VPT_OK:
-                _raise(st)
-        else:
-            counts = self._evaluate_graphemes(lines, utf8, boff, flags, types, predict_tags, no_norm)
+        st = _lib.load().vpt_evaluate_batch(self._h, utf8.ctypes.data, boff.ctypes.data, len(lines), flags, int(bool(predict_tags)),
+                                            counts.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
         return evaluation_result(counts)
-
-    def _evaluate_graphemes(self, lines, utf8, boff, flags, types, predict_tags, no_norm) -> np.ndarray:
-        import torch
-        dev = torch.device("cuda", self.device)
-        S, B = len(lines), len(utf8)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-
-        def d(n, dt):
-            return torch.zeros(max(n, 1), dtype=dt, device=dev)
-        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(1, np.uint8)])).to(dev)
-        d_boff = torch.from_numpy(boff.view(np.int64)).to(dev)
-        raw, roff, ooff, gold = d(B, torch.uint8), d(S + 1, torch.int64), d(S + 1, torch.int64), d(B, torch.uint8)
-        ntags, tidx, soff, tbytes = d(S, torch.int32), d(B + 1, torch.int64), d(B + 1, torch.int64), d(B, torch.uint8)
-        batch = DeviceBatch(self)
-        L = _lib.load()
-        st = L.vpt_parse_tokenized_batch_device(self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, raw.data_ptr(), roff.data_ptr(),
-                                                ooff.data_ptr(), gold.data_ptr(), ntags.data_ptr(), tidx.data_ptr(), soff.data_ptr(),
-                                                tbytes.data_ptr(), stream)
-        if st != _lib.VPT_OK:
-            _raise(st)
-        batch.sync()
-        h_roff = roff[:S + 1].cpu().numpy().view(np.uint64)
-        h_raw = raw[:int(h_roff[S])].cpu().numpy()
-        texts = [bytes(h_raw[int(h_roff[i]):int(h_roff[i + 1])]).decode("utf-8") for i in range(S)]
-        fullwidth = not no_norm
-        _, labels, h_ooff = self.predict_packed(h_raw, h_roff, fullwidth=fullwidth, wsconst=tuple(types))
-        norm = KyteaFullwidthFilter()
-        ConcatGraphemeClustersFilter().filter_packed([norm.filter(t) for t in texts] if fullwidth else texts, h_ooff, labels)
-        nb = int(h_ooff[S])
-        sys_l = torch.from_numpy(np.concatenate([labels[:nb], np.zeros(1, np.uint8)])).to(dev)
-        mode = _lib.VPT_EVAL_TAGS_NONE if fullwidth else _lib.VPT_EVAL_TAGS_GOLD
-        if predict_tags and self.n_tags():
-            mode = _lib.VPT_EVAL_TAGS_PREDICTED
-            batch.set_flags(_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
-            batch.fill_tags(raw.data_ptr(), roff.data_ptr(), ooff.data_ptr(), S, nb, sys_l.data_ptr(), 0, stream)
-        counts = torch.zeros(8, dtype=torch.int64, device=dev)
-        st = L.vpt_evaluate_labels_batch_device(self._h, batch._h, ooff.data_ptr(), S, gold.data_ptr(), ntags.data_ptr(), tidx.data_ptr(),
-                                                soff.data_ptr(), tbytes.data_ptr(), sys_l.data_ptr(), mode, counts.data_ptr(), stream)
-        if st != _lib.VPT_OK:
-            _raise(st)
-        batch.sync()
-        return counts.cpu().numpy().view(np.uint64)
 
     def char_types_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, fullwidth: bool = False) -> np.ndarray:
         """Sentence::char_types for a packed batch, from the device: uint8 per char (char c of sentence i at out_offsets[i] + i + c)."""
@@ -1181,6 +1119,14 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def concat_graphemes(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, stream: int = 0) -> None:
+        """Device-resident ConcatGraphemeClustersFilter on the labels at d_labels, in place (vpt_concat_graphemes_batch_device; the clusters of
+        the KyteaFullwidthFilter image when set_flags / set_fullwidth say so); enqueues and returns."""
+        st = _lib.load().vpt_concat_graphemes_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_sentences, total_boundaries,
+                                                           d_labels or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def predict_listing(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, text_bytes: int, d_scores: int,
                         d_labels: int, listing: int, d_out: int, capacity: int, d_listing_offsets: int, stream: int = 0) -> None:
         """The predict CLI's listing of the batch from the scores and labels on the device (vpt_predict_listing_batch_device); enqueues and
@@ -1218,7 +1164,7 @@ class DeviceBatch:
 
     def set_flags(self, flags: int) -> None:
         """VPT_FLAG_* for the calls that follow on this workspace (vpt_batch_set_flags): KyteaFullwidthFilter on the text, KyteaWsConstFilter /
-        SplitLinebreaksFilter on the labels."""
+        SplitLinebreaksFilter / ConcatGraphemeClustersFilter (VPT_FLAG_CONCAT_GRAPHEMES, always the last) on the labels."""
         st = _lib.load().vpt_batch_set_flags(self._h, int(flags))
         if st != _lib.VPT_OK:
             _raise(st)
@@ -1321,11 +1267,25 @@ def evaluation_result(counts) -> dict:
 _WSCONST_TYPES = {"D": 1, "R": 2, "H": 3, "T": 4, "K": 5, "O": 6}
 
 
+def _label_flags(wsconst: Sequence, split_linebreaks: bool = False, linebreaks_first: bool = False) -> int:
+    """The VPT_FLAG_* label post-filter bits of a `wsconst` sequence of CharacterType values and / or "G" (VPT_FLAG_CONCAT_GRAPHEMES)."""
+    flags = 0
+    for t in wsconst:
+        flags |= _lib.VPT_FLAG_CONCAT_GRAPHEMES if (isinstance(t, str) and t == "G") else _lib.VPT_FLAG_WSCONST(int(t))
+    if split_linebreaks:
+        flags |= _lib.VPT_FLAG_SPLIT_LINEBREAKS
+    if linebreaks_first:
+        flags |= _lib.VPT_FLAG_LINEBREAKS_FIRST
+    return flags
+
+
 def wsconst_flags(wsconst: str, allow_graphemes: bool = False) -> int:
-    """The VPT_FLAG_WSCONST bits of a wsconst string of vaporetto_tantivy (D R H T K O; vaporetto_tantivy/src/lib.rs:69-86)."""
+    """The VPT_FLAG_WSCONST bits of a wsconst string of vaporetto_tantivy (D R H T K O; vaporetto_tantivy/src/lib.rs:69-86); with
+    allow_graphemes "G" is VPT_FLAG_CONCAT_GRAPHEMES (the device applies it last, which is the adapter's result for any place of "G")."""
     flags = 0
     for c in wsconst:
         if c == "G" and allow_graphemes:
+            flags |= _lib.VPT_FLAG_CONCAT_GRAPHEMES
             continue
         if c not in _WSCONST_TYPES:
             raise VaporettoError("InvalidArgument", "Could not parse a wsconst value")   # lib.rs:82
@@ -1353,13 +1313,12 @@ class TantivyToken:
 class VaporettoTokenizer:
     """vaporetto_tantivy's VaporettoTokenizer (vaporetto_tantivy/src/lib.rs:62-229) over the C ABI: KyteaFullwidthFilter always, Predictor::new(model,
     false), SplitLinebreaksFilter first, then one filter per char of `wsconst` (D R H T K O: KyteaWsConstFilter; G: ConcatGraphemeClustersFilter).
-    Without "G" a batch is ONE call (vpt_token_stream_batch: only the text goes to the device, the spans come back); with it three -- predict with
-    the linebreaks-first flag, the grapheme filter on the host over the normalised text, vpt_token_spans_batch -- as Predictor.tokenize does."""
+    A batch is ONE call (vpt_token_stream_batch: only the text goes to the device, the spans come back), "G" included: the device applies it
+    last, which is the adapter's result for any place of "G" in the string."""
 
     def __init__(self, model: Model, wsconst: str = "", device: int = 0, _predictor: Optional[Predictor] = None):
         self._flags = wsconst_flags(wsconst, allow_graphemes=True)
-        self._wsconst = "".join(c for c in wsconst if c != "G")
-        self._graphemes = "G" in wsconst
+        self._wsconst = wsconst
         self._predictor = _predictor if _predictor is not None else Predictor(model, False, device=device)
 
     @classmethod
@@ -1376,22 +1335,7 @@ class VaporettoTokenizer:
         """(utf8, byte_offsets, token_offsets, token_ends) of a batch of documents."""
         raws = [t.encode("utf-8") for t in texts]
         utf8, boff = pack_texts(raws)
-        if not self._graphemes:
-            toff, ends = self._predictor.token_stream_packed(utf8, boff, self._wsconst)
-            return utf8, boff, toff, ends
-        keep = [i for i, r in enumerate(raws) if r]   # an empty document has no tokens and is no sentence
-        toff = np.zeros(len(texts) + 1, dtype=np.uint64)
-        if not keep:
-            return utf8, boff, toff, np.zeros(0, dtype=np.uint32)
-        k_utf8, k_boff = pack_texts([raws[i] for i in keep])
-        types = [t for t in range(1, 7) if self._flags & _lib.VPT_FLAG_WSCONST(t)]
-        _, labels, ooff = self._predictor.predict_packed(k_utf8, k_boff, fullwidth=True, wsconst=types, split_linebreaks=True, linebreaks_first=True)
-        norm = KyteaFullwidthFilter()
-        ConcatGraphemeClustersFilter().filter_packed([norm.filter(texts[i]) for i in keep], ooff, labels)
-        k_toff, ends = self._predictor.token_spans_packed(k_utf8, k_boff, ooff, labels)
-        counts = np.zeros(len(texts), dtype=np.uint64)
-        counts[keep] = np.diff(k_toff)
-        toff[1:] = np.cumsum(counts)
+        toff, ends = self._predictor.token_stream_packed(utf8, boff, self._wsconst)
         return utf8, boff, toff, ends
 
     def token_stream_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:

@@ -475,7 +475,7 @@ vpt_status vpt_batch_set_max_sentence_chars(vpt_batch* b, uint64_t max_sentence_
 
 vpt_status vpt_batch_set_flags(vpt_batch* b, unsigned flags) {
     if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST | VPT_FLAG_CONCAT_GRAPHEMES)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     b->flags = flags;
     return VPT_OK;
 }

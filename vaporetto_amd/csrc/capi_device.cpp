@@ -154,9 +154,77 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     if (b->timing) { VPT_HIP(hipEventRecord(b->ev[2 * slot + 1], stream)); ++b->ev_calls; }
     b->last_tiles = n_tiles; b->last_stream = stream; b->pending = true;
     b->last_tile_flat = uint32_t(tile_flat); b->last_plan = !fast ? 0u : cut_tiles ? 2u : 1u;
+    // ConcatGraphemeClustersFilter: behind the scoring launch (whose epilogue applied the other label filters) on its stream, in front of
+    // whatever the caller enqueues on the labels
+    if ((b->flags & VPT_FLAG_CONCAT_GRAPHEMES) && d_labels)
+        return concat_graphemes_impl(p, b, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, P.cps_out != nullptr, stream);
+    return VPT_OK;
+}
+
+namespace {
+// the class table on `device`: uploaded by the first call that asks for it there (model-independent: no predictor owns it, none frees it)
+vpt_status grapheme_table_on(int device, const uint8_t** out) {
+    constexpr int kMaxDevices = 64;
+    static std::mutex mu;
+    static const uint8_t* tables[kMaxDevices] = {};
+    if (device < 0 || device >= kMaxDevices) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: device_id: no such HIP device");
+    std::lock_guard<std::mutex> g(mu);
+    if (!tables[device]) {
+        const std::vector<uint8_t>& h = vpt::grapheme_table_host();
+        uint8_t* d = nullptr;
+        VPT_HIP(hipMalloc(reinterpret_cast<void**>(&d), h.size() + kTablePadBytes));
+        const hipError_t e = hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e)); }
+        tables[device] = d;
+    }
+    *out = tables[device];
+    return VPT_OK;
+}
+}  // namespace
+
+vpt_status concat_graphemes_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                 const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint8_t* d_labels, bool have_cps,
+                                 hipStream_t stream) {
+    if (n_sentences == 0 || total_boundaries == 0) return VPT_OK;   // no boundary, no label
+    const uint64_t total_c = total_boundaries + n_sentences;
+    const uint64_t n_tiles = (total_c + vpt::kGraphemeTile - 1) / vpt::kGraphemeTile;
+    if (n_tiles >= 0x7FFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch too large for one call");
+    vpt::GraphemeParams G{};
+    vpt_status st;
+    if ((st = grapheme_table_on(p->device, &G.table)) != VPT_OK) return st;
+    if ((st = grow(&b->d_gcls, &b->gcls_cap, size_t(n_tiles) * vpt::kGraphemeTile)) != VPT_OK) return st;
+    if ((st = grow(&b->d_gsum, &b->gsum_cap, 2 * size_t(n_tiles))) != VPT_OK) return st;
+    if (!have_cps) {
+        const bool fw = (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
+        if ((st = grow(&b->d_cps, &b->cps_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        b->cps_text = nullptr;
+        VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_c, p->d_cinfo + (fw ? 65536 : 0), b->d_cps, nullptr, b->d_ctrl, stream, fw));
+    }
+    G.cps = b->d_cps; G.boff = d_byte_offsets; G.ooff = d_out_offsets; G.n_sent = n_sentences; G.total_chars = total_c; G.total_boundaries = total_boundaries;
+    G.cls = b->d_gcls; G.summ = b->d_gsum; G.first = b->d_gsum + n_tiles; G.labels = d_labels; G.status = b->d_ctrl; G.n_tiles = uint32_t(n_tiles);
+    VPT_HIP(vpt::launch_concat_graphemes(G, stream));
+    b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
 }  // namespace vptc
+
+vpt_status vpt_concat_graphemes_tile(uint32_t* n_chars) {
+    if (!n_chars) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_chars = vpt::kGraphemeTile;
+    return VPT_OK;
+}
+
+// ConcatGraphemeClustersFilter on the caller's labels, device buffers: the classes are those of the text under the workspace's VPT_FLAG_KYTEA_FULLWIDTH
+vpt_status vpt_concat_graphemes_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                             const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint8_t* d_labels,
+                                             void* hip_stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (n_sentences == 0) return VPT_OK;
+    if (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_sentences >= 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_sentences: at most 2^32-2 per call");
+    VPT_HIP(hipSetDevice(p->device));
+    return concat_graphemes_impl(p, b, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, false, static_cast<hipStream_t>(hip_stream));
+}
 
 vpt_status vpt_predict_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                     const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,

@@ -193,7 +193,7 @@ vpt_status vpt_predict_batch(const vpt_predictor* p, const uint8_t* utf8, const 
 
 vpt_status vpt_predict_batch_flags(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
                                    int32_t* scores_out, uint8_t* labels_out, const uint64_t* out_offsets, unsigned flags) {
-    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST | VPT_FLAG_CONCAT_GRAPHEMES)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (n_sentences == 0) return VPT_OK;
     if (!utf8 || !byte_offsets || !out_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -492,7 +492,7 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
                               int tagged, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!text_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (flags & ~unsigned(VPT_FLAG_ALL)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_CONCAT_GRAPHEMES)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (tagged && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     text_offsets_out[0] = 0;
     if (n_sentences == 0) return VPT_OK;
@@ -640,7 +640,7 @@ vpt_status vpt_predict_listing_batch(const vpt_predictor* p, const uint8_t* utf8
                                      unsigned listing, const int32_t* scores, const uint8_t* labels, uint8_t* out, uint64_t capacity,
                                      uint64_t* listing_offsets_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
-    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_LINEBREAKS_FIRST | VPT_FLAG_CONCAT_GRAPHEMES)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (listing & ~unsigned(VPT_LISTING_ALL)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: listing: unknown bit");
     if ((listing & (VPT_LISTING_TAG_SCORES | VPT_LISTING_TAGGED)) && !p->predict_tags)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
@@ -715,12 +715,38 @@ vpt_status vpt_token_spans_batch(const vpt_predictor* p, const uint8_t* utf8, co
     return VPT_OK;
 }
 
+// ConcatGraphemeClustersFilter on the caller's labels, host buffers
+vpt_status vpt_concat_graphemes_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
+                                      const uint64_t* out_offsets, unsigned flags, uint8_t* labels) {
+    if (flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (n_sentences == 0) return VPT_OK;
+    if (!utf8 || !byte_offsets || !out_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (out_offsets[n_sentences] != out_offsets[0] && !labels) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: must not be NULL");
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st = acquire(p, &w);
+    if (st != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    uint64_t total_b = 0;
+    if ((st = stage(b, utf8, byte_offsets, out_offsets, n_sentences, labels, &total_b, nullptr, nullptr)) != VPT_OK) return st;
+    b->flags = flags;
+    if (total_b == 0) {   // no label to clear: the text's own checks (Sentence::from_raw's) all the same
+        std::vector<uint64_t> ooff(n_sentences + 1);
+        return vpt_count_boundaries(utf8, byte_offsets, n_sentences, ooff.data());
+    }
+    st = vpt_concat_graphemes_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, b->d_labels, b->own_stream);
+    if (st != VPT_OK) return st;
+    VPT_HIP(hipMemcpyAsync(labels + out_offsets[0], b->d_labels, size_t(total_b), hipMemcpyDeviceToHost, b->own_stream));
+    return vpt_batch_sync(b);
+}
+
 // VaporettoTokenizer::token_stream (vaporetto_tantivy/src/lib.rs:160-192) for a batch of documents: only the text goes in, the spans come back.
 vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
                                   unsigned wsconst_flags, uint64_t* token_offsets_out, uint32_t* token_ends_out, uint64_t capacity) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (wsconst_flags & ~0x7Eu) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
+    if (wsconst_flags & ~(0x7Eu | unsigned(VPT_FLAG_CONCAT_GRAPHEMES))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
     token_offsets_out[0] = 0;
     if (n_documents == 0) return VPT_OK;
     if (!utf8 || !byte_offsets || (capacity && !token_ends_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");

@@ -307,6 +307,9 @@ struct vpt_batch {
     uint64_t* d_lst_pos = nullptr; size_t lst_pos_cap = 0;
     uint8_t* d_lst_out = nullptr; size_t lst_out_cap = 0;
     uint64_t* d_lst_off = nullptr; size_t lst_off_cap = 0;
+    // VPT_FLAG_CONCAT_GRAPHEMES (kernels_graphemes.hip): the class bytes and, in one array, the tiles' summaries and first sentences
+    uint8_t* d_gcls = nullptr; size_t gcls_cap = 0;
+    uint32_t* d_gsum = nullptr; size_t gsum_cap = 0;
 };
 
 struct DeviceTags {   // views into the arena
@@ -372,6 +375,7 @@ void batch_release(vpt_batch* b) {
     (void)hipFree(b->d_types);
     (void)hipFree(b->d_parse_tmp); (void)hipFree(b->d_eval);
     (void)hipFree(b->d_lst_pos); (void)hipFree(b->d_lst_out); (void)hipFree(b->d_lst_off);
+    (void)hipFree(b->d_gcls); (void)hipFree(b->d_gsum);
     for (auto& ps : b->pipe) {
         (void)hipFree(ps.text); (void)hipFree(ps.off); (void)hipFree(ps.scores); (void)hipFree(ps.labels);
         if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
@@ -549,5 +553,10 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);
 vpt_status count_boundaries_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                  size_t n_sentences, uint64_t* d_out_offsets, void* hip_stream, uint64_t text_bytes_hint);
+// ConcatGraphemeClustersFilter on d_labels (kernels_graphemes.hip), the classes those of the text under b->flags' VPT_FLAG_KYTEA_FULLWIDTH; have_cps:
+// b->d_cps holds this batch's chars already (the scoring launch in front left them there), else they are decoded here
+vpt_status concat_graphemes_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                 const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, uint8_t* d_labels, bool have_cps,
+                                 hipStream_t stream);
 }  // namespace vptc
 using namespace vptc;

@@ -186,7 +186,7 @@ vpt_status vpt_evaluate_labels_batch_device(const vpt_predictor* p, vpt_batch* b
 vpt_status vpt_evaluate_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
                               int predict_tags, uint64_t* counts_out) {
     if (!p || !byte_offsets || !counts_out || (n_sentences && !utf8)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if ((flags & ~unsigned(VPT_FLAG_ALL)) != 0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bits");
+    if ((flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_CONCAT_GRAPHEMES)) != 0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bits");
     if (predict_tags && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     for (size_t i = 0; i < n_sentences; ++i)
         if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");

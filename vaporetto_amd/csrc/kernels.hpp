@@ -223,6 +223,26 @@ struct SpanParams {
     uint32_t* status;
 };
 hipError_t launch_token_spans(const SpanParams& P, const EmitFuse& F, hipStream_t stream);
+// ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
+// grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
+constexpr uint32_t kGraphemeTile = 1024;
+struct GraphemeParams {
+    const uint32_t* cps;        // decode_chars' words of the batch (or the scoring kernel's ScoreParams::cps_out): the chars as they were scored
+    const uint64_t* boff;       // [S+1]
+    const uint64_t* ooff;       // [S+1]
+    uint64_t n_sent;
+    uint64_t total_chars;       // what cps holds: total boundaries + S, or an upper bound of it (the offsets say how many there are)
+    uint64_t total_boundaries;  // what labels holds (or an upper bound)
+    const uint8_t* table;       // tables.hpp, grapheme_class
+    uint8_t* cls;               // workspace [n_tiles * kGraphemeTile]: class byte | 0x80 at a sentence's first char
+    uint32_t* summ;             // workspace [n_tiles]: the tiles' summaries
+    uint32_t* first;            // workspace [n_tiles]: sentences that start in front of the tile
+    uint8_t* labels;            // [total boundaries], edited in place
+    uint32_t* status;
+    uint32_t n_tiles;           // ceil(total_chars / kGraphemeTile)
+};
+hipError_t launch_concat_graphemes(const GraphemeParams& P, hipStream_t stream);
+
 // the predict CLI's listings (kernels_listing.hip): per line T, the scores block and the tag block in one arena (predict/src/main.rs:66-93, 122-176)
 constexpr uint32_t kListingScores = 1u, kListingTagScores = 2u, kListingTagged = 4u, kListingNoNormOrder = 8u;   // VPT_LISTING_*
 struct ListingParams {

@@ -6,10 +6,12 @@
 // See layout.h for why all-matches tables give the same sums as the reference's merged automaton.
 #include "tables.hpp"
 #include "patset.hpp"
+#include "../../include/vaporetto_grapheme.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <exception>
 #include <string>
@@ -1074,6 +1076,27 @@ CompiledModel compile_model(const ModelData& m, bool predict_tags) {
     c.pad = std::max(1, std::max(c.chars.present ? c.chars.window : 0, c.type_kind != kTypeNone ? wt : 0));   // (the window the rows are laid out for)
     if (tags_on) c.tags = build_tag_tables(m, c.chars.present, c.type_kind != kTypeNone);
     return c;
+}
+
+const std::vector<uint8_t>& grapheme_table_host() {
+    static const std::vector<uint8_t> table = [] {
+        size_t n = 0;
+        const vaporetto_hip::grapheme_detail::Range* r = vaporetto_hip::grapheme_detail::ranges(&n);
+        std::vector<uint8_t> flat(size_t(kGraphemeStage1) << 8, 0);
+        for (size_t k = 0; k < n; ++k)
+            for (uint32_t cp = r[k].first; cp <= r[k].last && cp < flat.size(); ++cp) flat[cp] = r[k].cls;
+        std::vector<uint8_t> out(kGraphemeBlocksAt, 0);
+        uint32_t n_blocks = 0;
+        for (uint32_t b = 0; b < kGraphemeStage1; ++b) {
+            const uint8_t* src = flat.data() + (size_t(b) << 8);
+            uint32_t at = 0;
+            while (at < n_blocks && std::memcmp(out.data() + kGraphemeBlocksAt + (size_t(at) << 8), src, 256) != 0) ++at;
+            if (at == n_blocks) { out.insert(out.end(), src, src + 256); ++n_blocks; }
+            out[2 * b] = uint8_t(at & 0xFFu); out[2 * b + 1] = uint8_t(at >> 8);   // little-endian u16
+        }
+        return out;
+    }();
+    return table;
 }
 
 }  // namespace vpt

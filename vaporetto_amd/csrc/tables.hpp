@@ -113,6 +113,21 @@ uint32_t kytea_fullwidth_host(uint32_t c);
 // CharacterType::get_type (sentence.rs:50-67) on the host; used to build the device's BMP class table.
 uint8_t char_type_host(uint32_t c);
 
+// ConcatGraphemeClustersFilter's class table for the device (kernels_graphemes.hip): the class byte of every scalar value 0 .. 0x10FFFF as
+// grapheme_detail::class_of gives it (include/vaporetto_grapheme.hpp: GCB in the low 4 bits, ExtPict = 16, InCB in bits 5 - 6), built from the
+// ranges of include/vaporetto_grapheme_tables.inc -- the one source -- as a two-stage table: stage1[cp >> 8] names a block of 256 class
+// bytes, identical blocks shared.  ONE buffer: kGraphemeStage1 u16 entries, then the blocks.  Hangul syllables are not in it: LV / LVT are
+// arithmetic, as in the header.  Model-independent: built once per process, uploaded once per device, never part of a predictor blob.
+constexpr uint32_t kGraphemeStage1 = 0x1100;                   // (0x10FFFF >> 8) + 1
+constexpr uint32_t kGraphemeBlocksAt = 2 * kGraphemeStage1;   // byte offset of block 0 (a multiple of 256)
+const std::vector<uint8_t>& grapheme_table_host();
+VPT_HD uint32_t grapheme_class(const uint8_t* __restrict__ table, uint32_t cp) {
+    if (cp - 0xAC00u <= 0xD7A3u - 0xAC00u) return (cp - 0xAC00u) % 28u == 0 ? 12u : 13u;   // Hangul syllables: LV / LVT
+    if (cp > 0x10FFFFu) return 0u;
+    const uint32_t blk = reinterpret_cast<const uint16_t*>(table)[cp >> 8];
+    return table[kGraphemeBlocksAt + (blk << 8) + (cp & 0xFFu)];
+}
+
 // Throws ModelError with the reference's message where it defines one.
 CompiledModel compile_model(const ModelData& m, bool predict_tags);
 

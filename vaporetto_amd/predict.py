@@ -4,7 +4,7 @@ Lines on stdin, tokenized lines on stdout, byte for byte what the reference prin
 line is followed by "{i}:{c}{c'} {score}" per boundary and an empty line, with --tag-scores by every token's surface and "\\ttag:score,..."
 per tag slot and an empty line.  Scoring, the post-filters, fill_tags, the tokenized text and BOTH listings are made on the device
 (Predictor.predict_listing_arena -> vpt_predict_listing_batch); the host cuts stdin into chunks of lines and writes the arena of each chunk as
-it came from the device, with one write and no per-line work on the output path.  "G" (ConcatGraphemeClustersFilter) runs on the host between predict and the listing.
+it came from the device, with one write and no per-line work on the output path.  "G" (ConcatGraphemeClustersFilter) is a flag of the same call.
 
 Order of the pieces of a line, as in the reference: normalising (default) `T "\\n" [scores] [tag scores]` (main.rs:154-176); with --no-norm
 `T [scores] "\\n" [tag scores]` (main.rs:129-144) -- the first score line follows T without a newline between them.  That is the reference's
