@@ -194,6 +194,106 @@ impl Drop for HipPredictor {
     }
 }
 
+/// `vaporetto_rules::sentence_filters::PatternMatchTagger` (pattern_match_tagger.rs:10-41) on the device: `rules[surface]` fills the tag slots
+/// `fill_tags` left `None` -- never one that is `Some`; entries past the predictor's `n_tags` are ignored; `None` stays `None`, `Some("")` is a
+/// tag.  The table is built on the host and uploaded once, for ONE predictor (its device, its `n_tags`), which it borrows: the predictor
+/// outlives the tagger.  `HipPredictor::tokenize_lines_rules` runs it behind `fill_tags` in the same one call.
+pub struct PatternMatchTagger<'p> {
+    raw: *mut std::ffi::c_void,
+    predictor: &'p HipPredictor,
+}
+// immutable after creation, like the predictor it belongs to
+unsafe impl Send for PatternMatchTagger<'_> {}
+unsafe impl Sync for PatternMatchTagger<'_> {}
+
+impl<'p> PatternMatchTagger<'p> {
+    /// `PatternMatchTagger::new(rules)` (pattern_match_tagger.rs:15-19) for `predictor`; the rules as (surface, tags) pairs -- a `HashMap`'s
+    /// `iter()` will do; of a surface given twice the last pair is kept.  Errors name the rule: a surface that is empty or holds a NUL, a tag
+    /// that holds a NUL.
+    pub fn new<'a, I>(predictor: &'p HipPredictor, rules: I) -> Result<Self>
+    where
+        I: IntoIterator<Item = (&'a String, &'a Vec<Option<String>>)>,
+    {
+        let (mut surfaces, mut tags) = (Vec::<u8>::new(), Vec::<u8>::new());
+        let (mut offsets, mut tag_offsets) = (vec![0u64], vec![0u64]);
+        let (mut slot_counts, mut present) = (Vec::<u32>::new(), Vec::<u8>::new());
+        for (surface, list) in rules {
+            surfaces.extend_from_slice(surface.as_bytes());
+            offsets.push(surfaces.len() as u64);
+            slot_counts.push(list.len() as u32);
+            for tag in list {
+                present.push(tag.is_some() as u8);
+                if let Some(t) = tag {
+                    tags.extend_from_slice(t.as_bytes());
+                }
+                tag_offsets.push(tags.len() as u64);
+            }
+        }
+        let n_rules = slot_counts.len();
+        // (no dangling pointer of an empty Vec is handed over)
+        surfaces.push(0);
+        tags.push(0);
+        slot_counts.push(0);
+        present.push(0);
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            ffi::vpt_pattern_tagger_create(predictor.raw, surfaces.as_ptr(), offsets.as_ptr(), n_rules, slot_counts.as_ptr(), present.as_ptr(), tags.as_ptr(),
+                                           tag_offsets.as_ptr(), &mut raw)
+        })?;
+        Ok(Self { raw, predictor })
+    }
+
+    /// The distinct tag strings of the rules: a rule tag is `-(2 + id)`, `id < n_tags()`, wherever the C ABI hands out tag indices.
+    pub fn n_tags(&self) -> Result<u32> {
+        let mut n = 0u32;
+        check(unsafe { ffi::vpt_pattern_tagger_n_tags(self.raw, &mut n) })?;
+        Ok(n)
+    }
+
+    /// The string of rule tag `id`.
+    pub fn tag(&self, id: u32) -> Result<String> {
+        let (mut bytes, mut len) = (std::ptr::null::<u8>(), 0usize);
+        check(unsafe { ffi::vpt_pattern_tagger_tag(self.raw, id, &mut bytes, &mut len) })?;
+        let slice = if len == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(bytes, len) } };
+        Ok(String::from_utf8_lossy(slice).into_owned())
+    }
+
+    /// The most bytes one rule's tags take in the tokenized text (added to the predictor's bound while the tagger is used).
+    pub fn max_tag_suffix(&self) -> Result<u32> {
+        let mut n = 0u32;
+        check(unsafe { ffi::vpt_pattern_tagger_max_tag_suffix(self.raw, &mut n) })?;
+        Ok(n)
+    }
+}
+
+impl Drop for PatternMatchTagger<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::vpt_pattern_tagger_destroy(self.raw) }
+    }
+}
+
+impl HipPredictor {
+    /// `tokenize_lines(.., tagged = true)` with `tagger.filter(&mut sentence)` behind every `fill_tags` (pattern_match_tagger.rs:21-41), in the
+    /// same one call: the rule tags are printed with the tag models'.  The tagger must have been made for this predictor.
+    pub fn tokenize_lines_rules<'a, I: IntoIterator<Item = &'a str>>(&self, lines: I, flags: u32, tagger: &PatternMatchTagger<'_>) -> Result<Vec<String>> {
+        if !std::ptr::eq(tagger.predictor, self) {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: tagger: does not belong to this predictor".to_string()));
+        }
+        let (utf8, boff) = pack(lines.into_iter());
+        let n = boff.len() - 1;
+        let mut suffix = 0u32;
+        check(unsafe { ffi::vpt_predictor_max_tag_suffix(self.raw, &mut suffix) })?;
+        let suffix = suffix as usize + tagger.max_tag_suffix()? as usize;
+        let cap = 3 * utf8.len() + 64 + utf8.len() * suffix;
+        let mut text = vec![0u8; cap];
+        let mut toff = vec![0u64; n + 1];
+        check(unsafe {
+            ffi::vpt_tokenize_batch_rules(self.raw, utf8.as_ptr(), boff.as_ptr(), n, flags, 1, text.as_mut_ptr(), cap as u64, toff.as_mut_ptr(), tagger.raw)
+        })?;
+        Ok((0..n).map(|i| String::from_utf8_lossy(&text[toff[i] as usize..toff[i + 1] as usize]).into_owned()).collect())
+    }
+}
+
 /// One batch over the GPUs of a node: `preds[r]` scores the r-th character-balanced range of the sentences (no data-path collective).
 /// `boff` / `ooff`: the n + 1 byte / boundary offsets of the n sentences (`vpt_count_boundaries` makes the latter); `scores` and `labels` take
 /// `ooff[n]` entries.  The C side trusts these sizes, so they are checked here: a safe function must not let a short slice become a write past it.

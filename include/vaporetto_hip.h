@@ -515,6 +515,63 @@ vpt_status vpt_evaluate_labels_batch_device(const vpt_predictor *p, vpt_batch *b
 vpt_status vpt_evaluate_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
                               unsigned flags, int predict_tags, uint64_t *counts_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * PatternMatchTagger: rule tags for the slots fill_tags leaves None      (vaporetto_rules/src/sentence_filters/pattern_match_tagger.rs:10-41)
+ *
+ * The filter callers put behind Sentence::fill_tags: a table surface -> tags (HashMap<String, Vec<Option<String>>>).  Per sentence, with
+ * n_tags = vpt_predictor_n_tags: for every token and every slot j < n_tags that is None, if the token's WHOLE surface is a key of the table the
+ * slot becomes rules[surface].get(j) -- possibly None itself (a None entry, or a list shorter than j + 1).  Slots that are Some are never
+ * touched; rule entries at j >= n_tags are ignored; Some("") is not None (as a last slot it prints a trailing '/').  A predictor whose model has
+ * no tag models has n_tags == 0 and the filter changes NOTHING, as in the reference (its loop runs over the token's n_tags slots): a tagged
+ * writer then writes what the untagged one writes.  The surfaces are those of the text fill_tags sees (the KyteaFullwidthFilter image under
+ * VPT_FLAG_KYTEA_FULLWIDTH, as predict/src/main.rs tags the normalised sentence; the bytes printed are the caller's); rule surfaces are taken as
+ * they are.  A token that touches VPT_BOUNDARY_UNKNOWN gets no rule tags (the rule stated for fill_tags above).
+ *
+ * The handle is an opaque `void *` (a `const void *` where it is only read): immutable after creation, tied to the predictor it was created
+ * for (its device, its n_tags, its tag strings), shareable by any number of that predictor's workspaces and host threads; destroy it after them.
+ * vpt_pattern_tagger_create: surfaces / offsets [n_rules + 1]: the rules' surfaces as packed UTF-8; slot_counts [n_rules]: the length of each
+ *   rule's list; present [sum of slot_counts] and tag_offsets [that + 1]: per (rule, slot), in order, present != 0: Some(tag_bytes[tag_offsets[k] ..
+ *   tag_offsets[k + 1])), else None.  A duplicate surface keeps the LAST rule (HashMap::insert).  The table -- open addressing over (code
+ *   points, length), at most half full, the whole surface kept for verification -- is built on the host and uploaded once.
+ *   Errors, VPT_INVALID_ARGUMENT "InvalidArgumentError: rules: <reason> (rule i)" for the first failing rule: a surface is not valid UTF-8 | a
+ *   surface must contain at least one character | a surface must not contain NULL | a tag must not contain NULL.
+ * Encoding: a rule tag is -(2 + id) wherever a tag index is an int32 (the dense arrays of the fill_tags calls and of
+ *   vpt_expand_tags_batch_device); -1 stays None and values >= 0 stay candidates of the token's tag model.  id < vpt_pattern_tagger_n_tags
+ *   indexes the tagger's distinct tag strings in the order the rules name them first; vpt_pattern_tagger_tag gives the bytes of one (owned by the
+ *   tagger).
+ * vpt_batch_set_pattern_tagger(b, tagger or NULL): while one is set, vpt_fill_tags_batch_device, vpt_fill_tags_scores_batch_device and the
+ *   fill_tags inside vpt_predict_listing_batch_device apply the rules behind fill_tags on the same stream (kernels_pattern.hip), and
+ *   vpt_expand_tags_batch_device / vpt_write_tagged_batch_device / the listing's T read the result.  Order guarantee: the workspace's records
+ *   stay sorted by position -- the rule tags are merged by a count, a prefix sum and a scatter, no sort and no atomics -- so two runs give the
+ *   same bytes.  Setting or clearing a tagger drops the records on the workspace: call fill_tags again.  With none set every call makes
+ *   exactly the launches it made before this section existed.  vpt_evaluate_labels_batch_device (VPT_EVAL_TAGS_PREDICTED) keeps reading what
+ *   fill_tags itself left, never the rule tags: the evaluate CLI runs no PatternMatchTagger.  In the listing a token the rules tagged without a tag model has no line of
+ *   candidates in the tag block (Token::tag_candidates knows model candidates only).
+ * Capacity: wherever a bound above says vpt_predictor_max_tag_suffix, add vpt_pattern_tagger_max_tag_suffix (the most bytes one rule's tags
+ *   take, escapes included) while a tagger is used.
+ * vpt_fill_tags_batch_rules / vpt_write_tagged_batch_rules / vpt_tokenize_batch_rules: vpt_fill_tags_batch_flags / vpt_write_tagged_batch /
+ *   vpt_tokenize_batch with the tagger applied behind their fill_tags (NULL: exactly those calls).
+ * vpt_pattern_tagger_info: keys (distinct surfaces), slots of the table, the longest surface in chars (any pointer may be NULL).
+ * vpt_pattern_tagger_tile: the chars a workgroup of the kernel takes at a time (the tests place tokens across its edges). */
+vpt_status vpt_pattern_tagger_create(const vpt_predictor *p, const uint8_t *surfaces, const uint64_t *offsets, size_t n_rules,
+                                     const uint32_t *slot_counts, const uint8_t *present, const uint8_t *tag_bytes, const uint64_t *tag_offsets,
+                                     void **out);
+void vpt_pattern_tagger_destroy(void *tagger);
+vpt_status vpt_pattern_tagger_n_tags(const void *tagger, uint32_t *n_tags);
+vpt_status vpt_pattern_tagger_tag(const void *tagger, uint32_t id, const uint8_t **bytes, size_t *len);
+vpt_status vpt_pattern_tagger_max_tag_suffix(const void *tagger, uint32_t *n_bytes);
+vpt_status vpt_pattern_tagger_info(const void *tagger, uint32_t *n_keys, uint32_t *n_slots, uint32_t *max_surface_chars);
+vpt_status vpt_pattern_tagger_tile(uint32_t *n_chars);
+vpt_status vpt_batch_set_pattern_tagger(vpt_batch *b, const void *tagger);
+vpt_status vpt_fill_tags_batch_rules(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
+                                     const uint64_t *out_offsets, const uint8_t *labels, int32_t *tags_out, unsigned flags, const void *tagger);
+vpt_status vpt_write_tagged_batch_rules(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
+                                        const uint64_t *out_offsets, const uint8_t *labels, unsigned flags, uint8_t *text_out,
+                                        uint64_t text_capacity, uint64_t *text_offsets_out, const void *tagger);
+vpt_status vpt_tokenize_batch_rules(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences,
+                                    unsigned flags, int tagged, uint8_t *text_out, uint64_t text_capacity, uint64_t *text_offsets_out,
+                                    const void *tagger);
+
 /* Diagnostics: when the environment variable VPT_PROFILE_PHASES is set at vpt_batch_create, the specialised
  * kernel accumulates, per workgroup (wave 0), the shader cycles spent in 0 text scan, 1 per-char decode,
  * 2 pattern lookups, 3 barrier wait, 4 boundary output.  Reads the sums (after a device sync) and resets them;

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -92,6 +93,7 @@ private:
 };
 
 class Predictor;
+class PatternMatchTagger;
 
 // sentence.rs:85-101, raw-text path: the text, its character types, and after `predict` the boundary scores and labels.
 class Sentence {
@@ -129,8 +131,10 @@ public:
         need_scores();
         return std::vector<int32_t>(tag_scores_.begin() + c * score_stride_, tag_scores_.begin() + (c + 1) * score_stride_);
     }
-    inline void fill_tags();                                                         // sentence.rs:1144-1148
-    inline std::string write_tokenized_text() const;                                 // sentence.rs:850-886
+    // tagger: a PatternMatchTagger whose rules fill the slots fill_tags leaves None, on the device behind it (a rule tag is -(2 + id) in
+    // tag_indices(); PatternMatchTagger::tag gives its string); the writer prints them when it is given the same tagger
+    inline void fill_tags(const PatternMatchTagger* tagger = nullptr);               // sentence.rs:1144-1148
+    inline std::string write_tokenized_text(const PatternMatchTagger* tagger = nullptr) const;   // sentence.rs:850-886
 
     // TokenIterator (sentence.rs:1265-1309), surfaces only: tokens next to an Unknown boundary are skipped.
     std::vector<std::string> iter_tokens() const {
@@ -253,21 +257,9 @@ public:
     }
 
     // Lines in, tokenized lines out: the CLI's loop (predict/src/main.rs:122-176) for a batch, everything on the device.
-    std::vector<std::string> tokenize(const std::vector<std::string>& lines, bool tagged = false, unsigned flags = 0) const {
-        std::vector<std::string> out;
-        if (lines.empty()) return out;
-        std::string text;
-        std::vector<uint64_t> boff(1, 0);
-        for (const std::string& l : lines) { text += l; boff.push_back(text.size()); }
-        uint32_t sfx = 0;
-        if (tagged) detail::check(vpt_predictor_max_tag_suffix(raw_->raw, &sfx));
-        std::vector<uint8_t> buf(3 * text.size() + text.size() * sfx + 16);
-        std::vector<uint64_t> toff(lines.size() + 1);
-        detail::check(vpt_tokenize_batch(raw_->raw, reinterpret_cast<const uint8_t*>(text.data()), boff.data(), lines.size(), flags, tagged ? 1 : 0, buf.data(),
-                                         buf.size(), toff.data()));
-        for (size_t i = 0; i < lines.size(); ++i) out.emplace_back(buf.begin() + toff[i], buf.begin() + toff[i + 1]);
-        return out;
-    }
+    // tagger (with tagged): PatternMatchTagger behind fill_tags, in the same one call (vpt_tokenize_batch_rules).
+    inline std::vector<std::string> tokenize(const std::vector<std::string>& lines, bool tagged = false, unsigned flags = 0,
+                                             const PatternMatchTagger* tagger = nullptr) const;
 
     // The `predict` CLI's stdout per line with --scores / --tag-scores (predict/src/main.rs:66-93, 122-176), formatted on the device:
     // listing = VPT_LISTING_* bits, flags = VPT_FLAG_* (vpt_predict_listing_batch).
@@ -296,9 +288,76 @@ public:
 
 private:
     friend class Sentence;
+    friend class PatternMatchTagger;
     std::shared_ptr<detail::Shared> raw_;
     bool predict_tags_;
 };
+
+// vaporetto_rules' PatternMatchTagger (sentence_filters/pattern_match_tagger.rs:10-41) on the device: rules[surface] fills the tag slots
+// fill_tags left None (never one that is Some; entries past the predictor's n_tags are ignored; nullopt stays None, "" is a tag).  The table
+// is built and uploaded once, for ONE predictor (its device, its n_tags); a repeated surface keeps the last rule, like HashMap::insert.
+// Pass it to Sentence::fill_tags / write_tokenized_text or Predictor::tokenize.  Keeps the predictor's handle alive.
+class PatternMatchTagger {
+public:
+    using Rules = std::vector<std::pair<std::string, std::vector<std::optional<std::string>>>>;
+    PatternMatchTagger(const Predictor& predictor, const Rules& rules) : predictor_(predictor.raw_) {   // PatternMatchTagger::new
+        std::string surf, tags;
+        std::vector<uint64_t> off(1, 0), toff(1, 0);
+        std::vector<uint32_t> counts;
+        std::vector<uint8_t> present;
+        for (const auto& r : rules) {
+            surf += r.first;
+            off.push_back(surf.size());
+            counts.push_back(uint32_t(r.second.size()));
+            for (const auto& t : r.second) {
+                present.push_back(t ? 1 : 0);
+                if (t) tags += *t;
+                toff.push_back(tags.size());
+            }
+        }
+        surf.push_back('\0'); tags.push_back('\0'); counts.push_back(0); present.push_back(0);   // (no empty array's data() is handed over)
+        detail::check(vpt_pattern_tagger_create(predictor_->raw, reinterpret_cast<const uint8_t*>(surf.data()), off.data(), rules.size(), counts.data(),
+                                                present.data(), reinterpret_cast<const uint8_t*>(tags.data()), toff.data(), &raw_));
+    }
+    ~PatternMatchTagger() { vpt_pattern_tagger_destroy(raw_); }
+    PatternMatchTagger(const PatternMatchTagger&) = delete;
+    PatternMatchTagger& operator=(const PatternMatchTagger&) = delete;
+
+    const void* raw() const { return raw_; }
+    uint32_t n_tags() const { uint32_t n = 0; detail::check(vpt_pattern_tagger_n_tags(raw_, &n)); return n; }   // the distinct tag strings: the ids
+    std::string tag(uint32_t id) const {                                                                          // the string of rule tag -(2 + id)
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        detail::check(vpt_pattern_tagger_tag(raw_, id, &p, &n));
+        return std::string(reinterpret_cast<const char*>(p), n);
+    }
+    uint32_t max_tag_suffix() const { uint32_t n = 0; detail::check(vpt_pattern_tagger_max_tag_suffix(raw_, &n)); return n; }
+
+private:
+    std::shared_ptr<detail::Shared> predictor_;
+    void* raw_ = nullptr;
+};
+
+inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
+    std::vector<std::string> out;
+    if (lines.empty()) return out;
+    std::string text;
+    std::vector<uint64_t> boff(1, 0);
+    for (const std::string& l : lines) { text += l; boff.push_back(text.size()); }
+    uint32_t sfx = 0;
+    if (tagged) detail::check(vpt_predictor_max_tag_suffix(raw_->raw, &sfx));
+    if (tagged && tagger) sfx += tagger->max_tag_suffix();
+    std::vector<uint8_t> buf(3 * text.size() + text.size() * sfx + 16);
+    std::vector<uint64_t> toff(lines.size() + 1);
+    if (tagger)
+        detail::check(vpt_tokenize_batch_rules(raw_->raw, reinterpret_cast<const uint8_t*>(text.data()), boff.data(), lines.size(), flags, tagged ? 1 : 0,
+                                               buf.data(), buf.size(), toff.data(), tagger->raw()));
+    else
+        detail::check(vpt_tokenize_batch(raw_->raw, reinterpret_cast<const uint8_t*>(text.data()), boff.data(), lines.size(), flags, tagged ? 1 : 0, buf.data(),
+                                         buf.size(), toff.data()));
+    for (size_t i = 0; i < lines.size(); ++i) out.emplace_back(buf.begin() + toff[i], buf.begin() + toff[i + 1]);
+    return out;
+}
 
 // vaporetto_tantivy's VaporettoTokenizer (vaporetto_tantivy/src/lib.rs:62-229) for callers that are not Rust: KyteaFullwidthFilter always,
 // Predictor::new(model, false), SplitLinebreaksFilter first, then one filter per char of `wsconst` -- D R H T K O: KyteaWsConstFilter of that type,
@@ -358,14 +417,19 @@ private:
     unsigned flags_ = 0;
 };
 
-inline void Sentence::fill_tags() {
+inline void Sentence::fill_tags(const PatternMatchTagger* tagger) {
     if (!predictor_) throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: sentence: predict() has not been called");
     const uint64_t boff[2] = {0, text_.size()}, ooff[2] = {0, len() - 1};
     uint32_t nt = 0, stride = 0;
     detail::check(vpt_predictor_n_tags(predictor_->raw, &nt));
     std::vector<int32_t> tags(len() * size_t(nt) + 1);
     tag_scores_.clear(); tag_models_.clear();
-    if (predictor_->store_tag_scores && nt != 0) {   // predictor.rs:563-566
+    if (tagger && predictor_->store_tag_scores)
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: tagger: not with store_tag_scores (rule tags have no scores)");
+    if (tagger) {
+        detail::check(vpt_fill_tags_batch_rules(predictor_->raw, reinterpret_cast<const uint8_t*>(text_.data()), boff, 1, ooff, boundaries_.data(), tags.data(),
+                                                0u, tagger->raw()));
+    } else if (predictor_->store_tag_scores && nt != 0) {   // predictor.rs:563-566
         detail::check(vpt_predictor_tag_score_stride(predictor_->raw, &stride));
         std::vector<int32_t> sc(len() * size_t(stride) + 1), md(len(), -1);
         detail::check(vpt_fill_tags_scores_batch(predictor_->raw, reinterpret_cast<const uint8_t*>(text_.data()), boff, 1, ooff, boundaries_.data(), 0u,
@@ -380,7 +444,7 @@ inline void Sentence::fill_tags() {
     n_tags_ = nt;
 }
 
-inline std::string Sentence::write_tokenized_text() const {
+inline std::string Sentence::write_tokenized_text(const PatternMatchTagger* tagger) const {
     // The writer is the device's (the same bytes Sentence::write_tokenized_text produces): with tags when fill_tags has been
     // called, which is when the reference's Sentence holds any.
     const uint64_t boff[2] = {0, text_.size()}, ooff[2] = {0, len() - 1};
@@ -388,8 +452,12 @@ inline std::string Sentence::write_tokenized_text() const {
     const bool tagged = n_tags_ != 0 && predictor_ != nullptr;
     uint32_t sfx = 0;
     if (tagged) detail::check(vpt_predictor_max_tag_suffix(predictor_->raw, &sfx));
+    if (tagged && tagger) sfx += tagger->max_tag_suffix();
     std::vector<uint8_t> buf(3 * text_.size() + text_.size() * sfx + 16);
-    if (tagged) {
+    if (tagged && tagger) {
+        detail::check(vpt_write_tagged_batch_rules(predictor_->raw, reinterpret_cast<const uint8_t*>(text_.data()), boff, 1, ooff, boundaries_.data(), 0u,
+                                                   buf.data(), buf.size(), toff, tagger->raw()));
+    } else if (tagged) {
         detail::check(vpt_write_tagged_batch(predictor_->raw, reinterpret_cast<const uint8_t*>(text_.data()), boff, 1, ooff, boundaries_.data(), 0u,
                                              buf.data(), buf.size(), toff));
     } else {

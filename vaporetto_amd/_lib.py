@@ -109,6 +109,17 @@ SIGNATURES = {
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "vpt_pattern_tagger_create": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.POINTER(_P)]),
+    "vpt_pattern_tagger_destroy": (None, [_P]),
+    "vpt_pattern_tagger_n_tags": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vpt_pattern_tagger_tag": (C.c_int, [_P, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vpt_pattern_tagger_max_tag_suffix": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vpt_pattern_tagger_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "vpt_pattern_tagger_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "vpt_batch_set_pattern_tagger": (C.c_int, [_P, _P]),
+    "vpt_fill_tags_batch_rules": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, C.c_uint, _P]),
+    "vpt_write_tagged_batch_rules": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_uint, _P, C.c_uint64, _P, _P]),
+    "vpt_tokenize_batch_rules": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, C.c_int, _P, C.c_uint64, _P, _P]),
     "vpt_predictor_max_tag_listing": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vpt_predict_listing_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, C.c_uint, _P, _P, _P, C.c_uint64, _P]),
     "vpt_predict_listing_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, C.c_uint, _P, C.c_uint64, _P, _P]),

@@ -142,6 +142,104 @@ class ConcatGraphemeClustersFilter:
                 start += n
 
 
+class PatternMatchTagger:
+    """vaporetto_rules/src/sentence_filters/pattern_match_tagger.rs:10-41: a table surface -> tags that fills the tag slots fill_tags left
+    None.  `rules`: {surface: [tag or None, ...]} (or a sequence of such pairs: a repeated surface keeps the last, like HashMap::insert).
+    `filter` is the host form, a plain restatement of the Rust (the oracle of the device form, and for callers who order their filters
+    differently); the `tagger=` keyword of Predictor.fill_tags_batch / write_tokenized_batch / tokenize and DeviceBatch.set_pattern_tagger
+    run it on the device behind fill_tags (vpt_pattern_tagger_*, kernels_pattern.hip)."""
+
+    def __init__(self, rules):
+        pairs = list(rules.items()) if hasattr(rules, "items") else list(rules)
+        self._pairs = [(str(k), [None if t is None else str(t) for t in v]) for k, v in pairs]
+        self.rules = dict(self._pairs)
+        self._handles = {}   # id(predictor) -> (handle, predictor): the table lives on the predictor's device, with its n_tags
+
+    def filter(self, sentence: "Sentence") -> None:  # pattern_match_tagger.rs:22-40
+        n_tags = sentence.n_tags()
+        queue = []
+        for token in sentence.tokens():
+            for j, tag in enumerate(token.tags()):
+                if tag is None:
+                    tags = self.rules.get(token.surface())
+                    if tags is not None:
+                        queue.append((token.end() - 1, j, tags[j] if j < len(tags) else None))
+        for i, j, tag in queue:
+            sentence._tags[i * n_tags + j] = tag
+
+    def _packed(self):
+        surf = [k.encode("utf-8", "surrogatepass") if isinstance(k, str) else bytes(k) for k, _ in self._pairs]
+        utf8, off = pack_texts(surf) if surf else (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+        counts = np.array([len(v) for _, v in self._pairs], dtype=np.uint32)
+        present, tags = [], []
+        for _, v in self._pairs:
+            for t in v:
+                present.append(0 if t is None else 1)
+                tags.append(b"" if t is None else t.encode("utf-8"))
+        tb, toff = pack_texts(tags) if tags else (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+        return utf8, off, counts, np.array(present, dtype=np.uint8), tb, toff
+
+    def handle(self, predictor: "Predictor"):
+        """The device table for `predictor` (vpt_pattern_tagger_create), built on first use and kept."""
+        got = self._handles.get(id(predictor))
+        if got is not None:
+            return got[0]
+        utf8, off, counts, present, tb, toff = self._packed()
+        h = C.c_void_p()
+        keep = [a if len(a) else np.zeros(1, a.dtype) for a in (utf8, counts, present, tb)]
+        st = _lib.load().vpt_pattern_tagger_create(predictor.handle, keep[0].ctypes.data, off.ctypes.data, len(self._pairs), keep[1].ctypes.data,
+                                                   keep[2].ctypes.data, keep[3].ctypes.data, toff.ctypes.data, C.byref(h))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self._handles[id(predictor)] = (h, predictor)
+        return h
+
+    def __del__(self):
+        for h, _ in getattr(self, "_handles", {}).values():
+            try:
+                _lib.load().vpt_pattern_tagger_destroy(h)
+            except Exception:
+                pass
+        self._handles = {}
+
+    def n_tags(self, predictor: "Predictor") -> int:
+        """vpt_pattern_tagger_n_tags: the distinct tag strings of the rules (the ids of the -(2 + id) encoding)."""
+        v = C.c_uint32()
+        st = _lib.load().vpt_pattern_tagger_n_tags(self.handle(predictor), C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
+    def tag(self, predictor: "Predictor", tag_id: int) -> str:
+        ptr, n = C.c_void_p(), C.c_size_t()
+        st = _lib.load().vpt_pattern_tagger_tag(self.handle(predictor), int(tag_id), C.byref(ptr), C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return C.string_at(ptr.value, n.value).decode("utf-8") if n.value else ""
+
+    def max_tag_suffix(self, predictor: "Predictor") -> int:
+        v = C.c_uint32()
+        st = _lib.load().vpt_pattern_tagger_max_tag_suffix(self.handle(predictor), C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
+    def info(self, predictor: "Predictor") -> dict:
+        k, n, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        st = _lib.load().vpt_pattern_tagger_info(self.handle(predictor), C.byref(k), C.byref(n), C.byref(m))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return {"n_keys": int(k.value), "n_slots": int(n.value), "max_surface_chars": int(m.value)}
+
+    @staticmethod
+    def tile() -> int:
+        v = C.c_uint32()
+        st = _lib.load().vpt_pattern_tagger_tile(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
+
 class Model:
     """model.rs:55-169."""
 
@@ -605,9 +703,10 @@ class Predictor:
         return v.value
 
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
-                         fullwidth: bool = False) -> np.ndarray:
+                         fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
         """Predictor::predict_tags over a packed batch (predictor.rs:546-637).  labels: uint8 per boundary (0/1/2).
-        Returns int32 [total chars, n_tags]: candidate index per slot, -1 = None."""
+        Returns int32 [total chars, n_tags]: candidate index per slot, -1 = None; with `tagger` its rules run behind fill_tags on the
+        device and a rule tag is -(2 + id) (PatternMatchTagger.tag)."""
         L = _lib.load()
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
@@ -618,8 +717,12 @@ class Predictor:
         total_c = int(out_offsets[S]) + S
         tags = np.full((total_c, max(nt, 1)), -1, dtype=np.int32)
         lab = labels if len(labels) else np.zeros(1, dtype=np.uint8)
-        st = L.vpt_fill_tags_batch_flags(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data,
-                                         lab.ctypes.data, tags.ctypes.data, _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
+        if tagger is not None:
+            st = L.vpt_fill_tags_batch_rules(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data, lab.ctypes.data,
+                                             tags.ctypes.data, _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, tagger.handle(self))
+        else:
+            st = L.vpt_fill_tags_batch_flags(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data,
+                                             lab.ctypes.data, tags.ctypes.data, _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0)
         if st != _lib.VPT_OK:
             _raise(st)
         return tags[:, :nt]
@@ -695,26 +798,31 @@ class Predictor:
         return self.predict_listing_packed(utf8, boff, listing, flags=flags)
 
     def tokenize_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, tagged: bool = False, flags: int = 0,
-                        text_out: Optional[np.ndarray] = None, offsets_out: Optional[np.ndarray] = None):
-        """vpt_tokenize_batch over a packed batch: (uint8 tokenized text, uint64 [S+1] offsets).  `text_out` / `offsets_out` may be
+                        text_out: Optional[np.ndarray] = None, offsets_out: Optional[np.ndarray] = None,
+                        tagger: Optional["PatternMatchTagger"] = None):
+        """vpt_tokenize_batch (with `tagger`: vpt_tokenize_batch_rules, its suffix bound added to the capacity) over a packed batch: (uint8 tokenized text, uint64 [S+1] offsets).  `text_out` / `offsets_out` may be
         preallocated (pinned) arrays; text_out needs 3 x the text bytes (+ text bytes x max_tag_suffix() when tagged)."""
         L = _lib.load()
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
         S = len(byte_offsets) - 1
-        cap = 3 * len(utf8) + (len(utf8) * self.max_tag_suffix() if tagged else 0)
+        cap = 3 * len(utf8) + (len(utf8) * (self.max_tag_suffix() + (tagger.max_tag_suffix(self) if tagger is not None else 0)) if tagged else 0)
         if text_out is None:
             text_out = np.zeros(max(cap, 1), dtype=np.uint8)
         if offsets_out is None:
             offsets_out = np.zeros(S + 1, dtype=np.uint64)
-        st = L.vpt_tokenize_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, flags, int(tagged), text_out.ctypes.data,
-                                  min(cap, text_out.nbytes), offsets_out.ctypes.data)
+        if tagger is not None:
+            st = L.vpt_tokenize_batch_rules(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, flags, int(tagged), text_out.ctypes.data,
+                                            min(cap, text_out.nbytes), offsets_out.ctypes.data, tagger.handle(self))
+        else:
+            st = L.vpt_tokenize_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, flags, int(tagged), text_out.ctypes.data,
+                                      min(cap, text_out.nbytes), offsets_out.ctypes.data)
         if st != _lib.VPT_OK:
             _raise(st)
         return text_out[:int(offsets_out[S])], offsets_out
 
     def tokenize(self, texts: Sequence[str], tagged: bool = False, fullwidth: bool = False, wsconst: Sequence = (),
-                 split_linebreaks: bool = False) -> List[str]:
+                 split_linebreaks: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> List[str]:
         """Lines in, tokenized lines out (vpt_tokenize_batch): the CLI's loop (predict/src/main.rs:122-176) for a batch,
         with char counting, scoring, post-filters, tagging and the writer on the device.  `wsconst`: CharacterType values (the
         KyteaWsConstFilter of that type) and / or "G" (ConcatGraphemeClustersFilter, predict/src/main.rs:101-104: VPT_FLAG_CONCAT_GRAPHEMES, a
@@ -724,12 +832,13 @@ class Predictor:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
         S = len(texts)
         flags = (_lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0) | _label_flags(wsconst, split_linebreaks)
-        text, toff = self.tokenize_packed(utf8, boff, tagged=tagged, flags=flags)
+        text, toff = self.tokenize_packed(utf8, boff, tagged=tagged, flags=flags, tagger=tagger)
         raw = bytes(text)
         return [raw[int(toff[i]):int(toff[i + 1])].decode("utf-8") for i in range(S)]
 
     def write_tokenized_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray,
-                               labels: np.ndarray, tagged: bool = False, fullwidth: bool = False):
+                               labels: np.ndarray, tagged: bool = False, fullwidth: bool = False,
+                               tagger: Optional["PatternMatchTagger"] = None):
         """Sentence::write_tokenized_text (sentence.rs:850-886) over a packed batch on the device; with `tagged`
         (predictors created with predict_tags) fill_tags runs first and every token gets its "/tag" suffixes.
         Returns (uint8 text, uint64 [S+1] offsets): sentence i is text[offsets[i]:offsets[i+1]]."""
@@ -746,11 +855,15 @@ class Predictor:
             sfx = C.c_uint32(0)
             if L.vpt_predictor_max_tag_suffix(self._h, C.byref(sfx)) != _lib.VPT_OK:
                 _raise(_lib.VPT_INVALID_ARGUMENT)
-            cap += nchars * int(sfx.value)
+            cap += nchars * (int(sfx.value) + (tagger.max_tag_suffix(self) if tagger is not None else 0))
         text = np.zeros(max(cap, 1), dtype=np.uint8)
         toff = np.zeros(S + 1, dtype=np.uint64)
         lab = labels if len(labels) else np.zeros(1, dtype=np.uint8)
-        if tagged:
+        if tagged and tagger is not None:
+            st = L.vpt_write_tagged_batch_rules(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data, lab.ctypes.data,
+                                                _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, text.ctypes.data, cap, toff.ctypes.data,
+                                                tagger.handle(self))
+        elif tagged:
             st = L.vpt_write_tagged_batch(self._h, utf8.ctypes.data, byte_offsets.ctypes.data, S, out_offsets.ctypes.data, lab.ctypes.data,
                                           _lib.VPT_FLAG_KYTEA_FULLWIDTH if fullwidth else 0, text.ctypes.data, cap, toff.ctypes.data)
         else:
@@ -760,7 +873,8 @@ class Predictor:
             _raise(st)
         return text[:int(toff[S])], toff
 
-    def write_tokenized_batch(self, sentences: Sequence["Sentence"], tagged: bool = False) -> List[str]:
+    def write_tokenized_batch(self, sentences: Sequence["Sentence"], tagged: bool = False,
+                              tagger: Optional["PatternMatchTagger"] = None) -> List[str]:
         """write_tokenized_text for many sentences in one launch.  tagged: fill_tags + "/tag" suffixes on the device
         (the sentences' own tags are not touched); otherwise sentences that carry tags take the host writer."""
         if not sentences:
@@ -770,7 +884,7 @@ class Predictor:
             ooff = np.zeros(len(sentences) + 1, dtype=np.uint64)
             ooff[1:] = np.cumsum([len(s) - 1 for s in sentences])
             labels = np.concatenate([np.asarray(s._boundaries, dtype=np.uint8) for s in sentences]) if int(ooff[-1]) else np.zeros(0, np.uint8)
-            text, toff = self.write_tokenized_packed(utf8, boff, ooff, labels, tagged=True)
+            text, toff = self.write_tokenized_packed(utf8, boff, ooff, labels, tagged=True, tagger=tagger)
             raw = bytes(text)
             return [raw[int(toff[i]):int(toff[i + 1])].decode("utf-8") for i in range(len(sentences))]
         utf8, boff = pack_texts([s._utf8 for s in sentences])
@@ -787,9 +901,12 @@ class Predictor:
             out.append(t)
         return out
 
-    def fill_tags_batch(self, sentences: Sequence["Sentence"]) -> None:
+    def fill_tags_batch(self, sentences: Sequence["Sentence"], tagger: Optional["PatternMatchTagger"] = None) -> None:
         """Sentence::fill_tags for many sentences in one launch; candidate indices are mapped to the tag strings of
-        the tag model whose token equals the token's surface (the LAST one of a repeated token, predictor.rs:466-478)."""
+        the tag model whose token equals the token's surface (the LAST one of a repeated token, predictor.rs:466-478).
+        `tagger`: a PatternMatchTagger applied behind fill_tags on the device; its tags come back through PatternMatchTagger.tag.  Not
+        together with store_tag_scores(True) in this mirror (VaporettoError): rule tags have no scores, and the host pipeline that returns
+        scores takes no tagger -- a caller that wants both binds the tagger to a DeviceBatch and calls fill_tags_scores there."""
         if not sentences:
             return
         utf8, boff = pack_texts([s._utf8 for s in sentences])
@@ -797,11 +914,14 @@ class Predictor:
         ooff[1:] = np.cumsum([len(s) - 1 for s in sentences])
         labels = np.concatenate([np.asarray(s._boundaries, dtype=np.uint8) for s in sentences]) if int(ooff[-1]) else np.zeros(0, np.uint8)
         scores = models = None
+        if self._store_tag_scores and tagger is not None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: tagger: not with store_tag_scores (rule tags have no scores)")
         if self._store_tag_scores:
             tags, scores, models = self.fill_tags_scores_packed(utf8, boff, ooff, labels)
         else:
-            tags = self.fill_tags_packed(utf8, boff, ooff, labels)
+            tags = self.fill_tags_packed(utf8, boff, ooff, labels, tagger=tagger)
         nt = tags.shape[1]
+        rule_tags = {}   # -(2 + id) -> the tagger's string
         tag_model_list = self._model.tag_models() if scores is not None else None
         if self._tag_models is None:
             self._tag_models = {tm.token: tm for tm in self._model.tag_models()}
@@ -829,6 +949,12 @@ class Predictor:
                 if b != CharacterBoundary.WordBoundary:
                     continue
                 if valid:
+                    for j in range(nt if tagger is not None else 0):   # rule tags: -(2 + id), resolved through the tagger
+                        idx = int(tags[g0 + e, j])
+                        if idx <= -2:
+                            if idx not in rule_tags:
+                                rule_tags[idx] = tagger.tag(self, -2 - idx)
+                            s._tags[e * nt + j] = rule_tags[idx]
                     tm = self._tag_models.get(s._text[start:e + 1])
                     if tm is not None:
                         for j in range(min(nt, len(tm.tags))):
@@ -1153,6 +1279,13 @@ class DeviceBatch:
         (vpt_write_tagged_batch_device; d_tags is not read any more and may be 0); enqueues and returns."""
         st = _lib.load().vpt_write_tagged_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_sentences, total_boundaries,
                                                        d_labels, d_tags or None, d_text_out, text_capacity, d_text_offsets, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def set_pattern_tagger(self, tagger: Optional["PatternMatchTagger"]) -> None:
+        """vpt_batch_set_pattern_tagger: the rules applied behind every fill_tags on this workspace (None: none)."""
+        self._tagger = tagger   # (keeps the table alive while it is bound)
+        st = _lib.load().vpt_batch_set_pattern_tagger(self._h, tagger.handle(self._p) if tagger is not None else None)
         if st != _lib.VPT_OK:
             _raise(st)
 

@@ -349,7 +349,27 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     T.n_runs = n_runs; T.run_sent = run_sent;
     T.summary = b->d_tag_summary;
     VPT_HIP(vpt::launch_tag_tokens(T, stream));
-    b->d_run_pref = T.run_pref; b->tag_chars = total_c; b->tag_sentences = n_sentences; b->tag_runs = n_runs; b->tag_run_sent = run_sent;
+    b->d_run_pref = T.run_pref; b->d_fill_run_pref = T.run_pref; b->tag_runs = n_runs; b->tag_run_sent = run_sent;
+    b->rv_records = b->d_tag_records; b->rv_rec_tags = b->d_rec_tags; b->rv_rec_str = b->d_rec_str; b->rv_str_bytes = p->dtag.str_bytes;
+    if (const vpt_pattern_tagger* t = b->tagger) {   // PatternMatchTagger: the rules' tags merged into records of their own (kernels_pattern.hip)
+        const size_t pm_words = n_state + size_t(n_runs) + 2;
+        if ((st = grow(&b->d_pm_records, &b->pm_records_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = grow(&b->d_pm_rec_tags, &b->pm_rec_tags_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+        if ((st = grow(&b->d_pm_rec_str, &b->pm_rec_str_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+        if ((st = grow(&b->d_pm_hits, &b->pm_hits_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = grow(&b->d_pm_ctl, &b->pm_ctl_cap, pm_words)) != VPT_OK) return st;
+        VPT_HIP(hipMemsetAsync(b->d_pm_ctl, 0, pm_words * sizeof(uint64_t), stream));
+        vpt::PatternParams R{};
+        R.slots = t->slots; R.surf = t->surf; R.rule_tags = t->rule_tags; R.id_str = t->id_str; R.bits = t->bits; R.max_len = t->max_len; R.n_tags = p->n_tags;
+        R.cps = b->d_cps; R.ooff = d_out_offsets; R.labels = d_labels; R.n_sent = n_sentences; R.total_chars = total_c;
+        R.records = b->d_tag_records; R.rec_tags = b->d_rec_tags; R.rec_str = b->d_rec_str; R.run_pref = T.run_pref; R.n_runs = n_runs; R.run_sent = run_sent;
+        R.hits = b->d_pm_hits; R.out_records = b->d_pm_records; R.out_rec_tags = b->d_pm_rec_tags; R.out_rec_str = b->d_pm_rec_str;
+        R.scan_state = b->d_pm_ctl; R.out_run_pref = b->d_pm_ctl + n_state; R.tags = d_tags_out; R.n_cus = p->n_cus;
+        VPT_HIP(vpt::launch_pattern_tagger(R, stream));
+        b->d_run_pref = R.out_run_pref;
+        b->rv_records = b->d_pm_records; b->rv_rec_tags = b->d_pm_rec_tags; b->rv_rec_str = b->d_pm_rec_str; b->rv_str_bytes = t->arena;
+    }
+    b->tag_chars = total_c; b->tag_sentences = n_sentences;
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
@@ -363,7 +383,7 @@ vpt_status vpt_expand_tags_batch_device(const vpt_predictor* p, vpt_batch* b, si
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
     VPT_HIP(hipSetDevice(p->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    VPT_HIP(vpt::launch_expand_tags(b->d_tag_records, b->d_rec_tags, b->d_run_pref + b->tag_runs, p->n_tags, b->tag_chars, d_tags_out, p->n_cus, stream));
+    VPT_HIP(vpt::launch_expand_tags(b->rv_records, b->rv_rec_tags, b->d_run_pref + b->tag_runs, p->n_tags, b->tag_chars, d_tags_out, p->n_cus, stream));
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
@@ -431,8 +451,8 @@ vpt_status emit_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_ut
         if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
         if (b->tag_chars != total_boundaries + n_sentences || b->tag_sentences != n_sentences || !b->d_tag_records)
             return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
-        E.records = b->d_tag_records; E.rec_str = b->d_rec_str; E.run_pref = b->d_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;
-        E.n_tags = p->n_tags; E.str_bytes = p->dtag.str_bytes;
+        E.records = b->rv_records; E.rec_str = b->rv_rec_str; E.run_pref = b->d_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;
+        E.n_tags = p->n_tags; E.str_bytes = b->rv_str_bytes;
     }
     vpt::EmitFuse F{};
     {
@@ -545,7 +565,7 @@ vpt_status vpt_predict_listing_batch_device(const vpt_predictor* p, vpt_batch* b
         VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, ooff, n_sentences, total_c, p->d_cinfo + (fw ? 65536 : 0), b->d_cps, nullptr, b->d_ctrl, stream, fw));
     }
     const bool tagged = (listing & VPT_LISTING_TAGGED) && p->n_tags > 0;
-    const uint64_t t_cap = 3 * text_bytes + (tagged ? total_c * p->max_tag_suffix : 0) + 16;
+    const uint64_t t_cap = 3 * text_bytes + (tagged ? total_c * (uint64_t(p->max_tag_suffix) + (b->tagger ? b->tagger->max_suffix : 0u)) : 0) + 16;
     if ((st = grow(&b->d_tok, &b->tok_cap, size_t(t_cap) + 16)) != VPT_OK) return st;
     if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 1)) != VPT_OK) return st;
     st = emit_device(p, b, d_utf8, d_byte_offsets, ooff, n_sentences, total_boundaries, d_labels, tagged, b->d_tok, t_cap, b->d_toff, stream);
@@ -631,5 +651,113 @@ vpt_status vpt_char_types_batch_device(const vpt_predictor* p, vpt_batch* b, con
     VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries + n_sentences, cinfo, nullptr, d_types_out,
                                      b->d_ctrl, stream, (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0));
     b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+    return VPT_OK;
+}
+
+// ---- PatternMatchTagger (vaporetto_rules/src/sentence_filters/pattern_match_tagger.rs): the rule table on the predictor's device
+vpt_status vpt_pattern_tagger_create(const vpt_predictor* p, const uint8_t* surfaces, const uint64_t* offsets, size_t n_rules, const uint32_t* slot_counts,
+                                     const uint8_t* present, const uint8_t* tag_bytes, const uint64_t* tag_offsets, void** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_rules && (!surfaces || !offsets || !slot_counts)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    size_t n_entries = 0;
+    for (size_t r = 0; r < n_rules; ++r) n_entries += slot_counts[r];
+    if (n_entries && (!present || !tag_offsets)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    vpt::HostRuleTable H;
+    try {
+        static const uint8_t none = 0;
+        H = vpt::build_rule_table(surfaces, offsets, n_rules, slot_counts, present, tag_bytes ? tag_bytes : &none, tag_offsets, p->n_tags);
+    } catch (const vpt::RuleError& e) {
+        return fail(VPT_INVALID_ARGUMENT, e.what());
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory while building the rule table");
+    }
+    VPT_HIP(hipSetDevice(p->device));
+    vpt_pattern_tagger* t = new (std::nothrow) vpt_pattern_tagger();
+    if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
+    t->pred = p; t->device = p->device;
+    t->bits = H.bits; t->max_len = H.max_len; t->n_tags = p->n_tags; t->n_ids = H.n_ids; t->max_suffix = H.max_suffix; t->n_keys = H.n_keys;
+    t->raw_off = std::move(H.raw_off); t->raw_bytes = std::move(H.raw_bytes);
+    // one allocation, 256-byte sections: slots | surfaces' code points | rule_tags | id_str | the arena (the predictor's tag strings, then the rules')
+    const size_t pred_bytes = p->has_tags ? size_t(p->meta.sec_bytes[kSecTagStrBytes]) : 0;
+    if (uint64_t(pred_bytes) + H.str_bytes.size() >= 0xFFFFFFFFull) { delete t; return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: rules: the tags take 4 GB or more"); }
+    std::vector<uint32_t> id_str(2 * size_t(H.n_ids));
+    for (uint32_t k = 0; k < H.n_ids; ++k) { id_str[2 * k] = uint32_t(pred_bytes) + H.str_off[k]; id_str[2 * k + 1] = H.str_off[k + 1] - H.str_off[k]; }
+    auto pad = [](size_t n) { return (n + kTablePadBytes + 255) & ~size_t(255); };
+    const size_t o_slots = 0, o_surf = o_slots + pad(4 * H.slots.size()), o_rt = o_surf + pad(4 * H.cps.size()), o_ids = o_rt + pad(4 * H.rule_tags.size()),
+                 o_arena = o_ids + pad(4 * id_str.size()), total = o_arena + pad(pred_bytes + H.str_bytes.size());
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->mem), total);
+    if (e == hipSuccess) e = hipMemset(t->mem, 0, total);
+    auto up = [&](size_t at, const void* src, size_t n) { if (e == hipSuccess && n) e = hipMemcpy(t->mem + at, src, n, hipMemcpyHostToDevice); };
+    up(o_slots, H.slots.data(), 4 * H.slots.size());
+    up(o_surf, H.cps.data(), 4 * H.cps.size());
+    up(o_rt, H.rule_tags.data(), 4 * H.rule_tags.size());
+    up(o_ids, id_str.data(), 4 * id_str.size());
+    if (e == hipSuccess && pred_bytes) e = hipMemcpy(t->mem + o_arena, p->dtag.str_bytes, pred_bytes, hipMemcpyDeviceToDevice);
+    up(o_arena + pred_bytes, H.str_bytes.data(), H.str_bytes.size());
+    if (e != hipSuccess) {
+        (void)hipFree(t->mem);
+        delete t;
+        return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    t->slots = reinterpret_cast<const uint4*>(t->mem + o_slots); t->surf = reinterpret_cast<const uint32_t*>(t->mem + o_surf);
+    t->rule_tags = reinterpret_cast<const int32_t*>(t->mem + o_rt); t->id_str = reinterpret_cast<const uint2*>(t->mem + o_ids);
+    t->arena = t->mem + o_arena;
+    *out = t;
+    return VPT_OK;
+}
+
+void vpt_pattern_tagger_destroy(void* tagger) {
+    vpt_pattern_tagger* t = static_cast<vpt_pattern_tagger*>(tagger);
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    (void)hipFree(t->mem);
+    delete t;
+}
+
+vpt_status vpt_pattern_tagger_n_tags(const void* tagger, uint32_t* n_tags) {
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (!t || !n_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_tags = t->n_ids;
+    return VPT_OK;
+}
+
+vpt_status vpt_pattern_tagger_tag(const void* tagger, uint32_t id, const uint8_t** bytes, size_t* len) {
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (!t || !bytes || !len) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (id >= t->n_ids) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: id: no such rule tag");
+    *bytes = t->raw_bytes.data() + t->raw_off[id];
+    *len = size_t(t->raw_off[id + 1] - t->raw_off[id]);
+    return VPT_OK;
+}
+
+vpt_status vpt_pattern_tagger_max_tag_suffix(const void* tagger, uint32_t* n_bytes) {
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (!t || !n_bytes) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_bytes = t->max_suffix;
+    return VPT_OK;
+}
+
+vpt_status vpt_pattern_tagger_info(const void* tagger, uint32_t* n_keys, uint32_t* n_slots, uint32_t* max_surface_chars) {
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (!t) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_keys) *n_keys = t->n_keys;
+    if (n_slots) *n_slots = 1u << t->bits;
+    if (max_surface_chars) *max_surface_chars = t->max_len;
+    return VPT_OK;
+}
+
+vpt_status vpt_pattern_tagger_tile(uint32_t* n_chars) {
+    if (!n_chars) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_chars = vpt::kPatternStep;
+    return VPT_OK;
+}
+
+vpt_status vpt_batch_set_pattern_tagger(vpt_batch* b, const void* tagger) {
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (t && t->pred != b->pred) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this workspace's predictor");
+    b->tagger = t;
+    b->tag_chars = 0;   // the records on the workspace were made under the other setting
     return VPT_OK;
 }

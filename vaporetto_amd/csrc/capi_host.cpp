@@ -230,12 +230,14 @@ vpt_status vpt_fill_tags_batch_flags(const vpt_predictor* p, const uint8_t* utf8
     return vpt_fill_tags_scores_batch(p, utf8, byte_offsets, n_sentences, out_offsets, labels, flags, tags_out, nullptr, nullptr);
 }
 
-vpt_status vpt_fill_tags_scores_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
-                                      const uint64_t* out_offsets, const uint8_t* labels, unsigned flags, int32_t* tags_out,
-                                      int32_t* tag_scores_out, int32_t* tag_models_out) {
+// (t: the PatternMatchTagger whose rules fill the slots left None, or nullptr)
+static vpt_status fill_tags_host(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
+                                 const uint64_t* out_offsets, const uint8_t* labels, unsigned flags, int32_t* tags_out,
+                                 int32_t* tag_scores_out, int32_t* tag_models_out, const vpt_pattern_tagger* t) {
     if (flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
     if (n_sentences == 0 || p->n_tags == 0) return VPT_OK;   // predictor.rs:553-555
     if (!utf8 || !byte_offsets || !out_offsets || !tags_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (out_offsets[n_sentences] != out_offsets[0] && !labels) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: must not be NULL");
@@ -253,6 +255,7 @@ vpt_status vpt_fill_tags_scores_batch(const vpt_predictor* p, const uint8_t* utf
     // rows that end no token with a tag model are not written by the kernel: they read 0 (the reference holds None there)
     if (tag_scores_out && n_score_words) VPT_HIP(hipMemsetAsync(b->d_tag_scores, 0, n_score_words * sizeof(int32_t), b->own_stream));
     b->flags = flags;
+    b->tagger = t;
     st = vpt_fill_tags_scores_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, b->d_labels, b->d_tags,
                                            tag_scores_out ? b->d_tag_scores : nullptr, tag_models_out ? b->d_tag_models : nullptr, b->own_stream);
     if (st != VPT_OK) return st;
@@ -264,13 +267,26 @@ vpt_status vpt_fill_tags_scores_batch(const vpt_predictor* p, const uint8_t* utf
     return VPT_OK;
 }
 
+vpt_status vpt_fill_tags_scores_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
+                                      const uint64_t* out_offsets, const uint8_t* labels, unsigned flags, int32_t* tags_out,
+                                      int32_t* tag_scores_out, int32_t* tag_models_out) {
+    return fill_tags_host(p, utf8, byte_offsets, n_sentences, out_offsets, labels, flags, tags_out, tag_scores_out, tag_models_out, nullptr);
+}
+
+vpt_status vpt_fill_tags_batch_rules(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
+                                     const uint64_t* out_offsets, const uint8_t* labels, int32_t* tags_out, unsigned flags,
+                                     const void* tagger) {
+    return fill_tags_host(p, utf8, byte_offsets, n_sentences, out_offsets, labels, flags, tags_out, nullptr, nullptr, static_cast<const vpt_pattern_tagger*>(tagger));
+}
+
 static vpt_status emit_host(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
                             const uint64_t* out_offsets, const uint8_t* labels, bool tagged, unsigned flags, uint8_t* text_out,
-                            uint64_t text_capacity, uint64_t* text_offsets_out) {
+                            uint64_t text_capacity, uint64_t* text_offsets_out, const vpt_pattern_tagger* t = nullptr) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!text_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (tagged && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
     text_offsets_out[0] = 0;
     if (n_sentences == 0) return VPT_OK;
     if (!utf8 || !byte_offsets || !out_offsets || (text_capacity && !text_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -287,6 +303,7 @@ static vpt_status emit_host(const vpt_predictor* p, const uint8_t* utf8, const u
     const bool with_tags = tagged && p->n_tags > 0;
     if (with_tags) {   // Sentence::fill_tags, then the writer, as the CLI does (predict/src/main.rs:156-176); no dense array: the records are the tags
         b->flags = flags;
+        b->tagger = t;
         st = vpt_fill_tags_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, b->d_labels, nullptr, b->own_stream);
         if (st != VPT_OK) return st;
     }
@@ -310,6 +327,12 @@ vpt_status vpt_write_tagged_batch(const vpt_predictor* p, const uint8_t* utf8, c
                                   const uint64_t* out_offsets, const uint8_t* labels, unsigned flags, uint8_t* text_out,
                                   uint64_t text_capacity, uint64_t* text_offsets_out) {
     return emit_host(p, utf8, byte_offsets, n_sentences, out_offsets, labels, true, flags, text_out, text_capacity, text_offsets_out);
+}
+
+vpt_status vpt_write_tagged_batch_rules(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
+                                        const uint64_t* out_offsets, const uint8_t* labels, unsigned flags, uint8_t* text_out,
+                                        uint64_t text_capacity, uint64_t* text_offsets_out, const void* tagger) {
+    return emit_host(p, utf8, byte_offsets, n_sentences, out_offsets, labels, true, flags, text_out, text_capacity, text_offsets_out, static_cast<const vpt_pattern_tagger*>(tagger));
 }
 
 namespace {
@@ -488,12 +511,13 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
 // Lines in, tokenized lines out: Sentence::from_raw -> [KyteaFullwidthFilter] -> Predictor::predict -> [post-filters]
 // -> [fill_tags] -> write_tokenized_text for a whole batch (the loop of predict/src/main.rs:122-176), with only the
 // text crossing PCIe: char counting, scoring, tagging and the writer all run on the device.
-vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
-                              int tagged, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out) {
+static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
+                                int tagged, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out, const vpt_pattern_tagger* t) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!text_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (flags & ~unsigned(VPT_FLAG_ALL | VPT_FLAG_CONCAT_GRAPHEMES)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     if (tagged && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
     text_offsets_out[0] = 0;
     if (n_sentences == 0) return VPT_OK;
     if (!utf8 || !byte_offsets || (text_capacity && !text_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -525,7 +549,7 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
     // overrides; the tests use it).
     constexpr int kMaxLanes = 4;
     const uint64_t chunk_bytes = p->knobs.tokenize_chunk_bytes;
-    const uint64_t per_byte = 3 + (with_tags ? uint64_t(p->max_tag_suffix) : 0);   // tokenized bytes per text byte, at most
+    const uint64_t per_byte = 3 + (with_tags ? uint64_t(p->max_tag_suffix) + (t ? t->max_suffix : 0u) : 0);   // tokenized bytes per text byte, at most
     const size_t max_chunks = std::min<size_t>(n_sentences, size_t(nbytes / chunk_bytes) + 2);
     const int n_lanes = int(std::min<size_t>(kMaxLanes, max_chunks));
     Workspace extra[kMaxLanes - 1];
@@ -585,6 +609,7 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
         if (st != VPT_OK) return st;
         if (with_tags) {   // (no dense array: the writer takes the records)
             bb->flags = flags & VPT_FLAG_KYTEA_FULLWIDTH;
+            bb->tagger = t;
             st = vpt_fill_tags_batch_device(p, bb, b->d_text, d_boff_k, d_ooff_k, n, tb_bound, d_labels_k, nullptr, s);
             if (st != VPT_OK) return st;
         }
@@ -632,6 +657,17 @@ vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const
     for (size_t k = 1; k < chunks.size(); ++k)
         for (size_t j = 1; j <= chunks[k].n; ++j) text_offsets_out[chunks[k].a + j] += base[k];
     return VPT_OK;
+}
+
+vpt_status vpt_tokenize_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
+                              int tagged, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out) {
+    return tokenize_host(p, utf8, byte_offsets, n_sentences, flags, tagged, text_out, text_capacity, text_offsets_out, nullptr);
+}
+
+vpt_status vpt_tokenize_batch_rules(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
+                                    int tagged, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out,
+                                    const void* tagger) {
+    return tokenize_host(p, utf8, byte_offsets, n_sentences, flags, tagged, text_out, text_capacity, text_offsets_out, static_cast<const vpt_pattern_tagger*>(tagger));
 }
 
 // predict/src/main.rs:122-176 with --scores / --tag-scores for a batch in host buffers: the bytes the CLI writes for these lines.  labels == NULL:

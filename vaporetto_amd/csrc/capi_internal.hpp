@@ -18,6 +18,7 @@
 
 #include "kernels.hpp"
 #include "model.hpp"
+#include "pattern_tagger.hpp"
 #include "tables.hpp"
 
 extern thread_local std::string vpt_g_last_error;   // (capi.cpp) the calling thread's message: vpt_last_error
@@ -231,6 +232,20 @@ void fill_info(const vpt::CompiledModel& c, vpt_model_info* info) {
 
 }  // namespace
 
+// PatternMatchTagger's rule table on the predictor's device (pattern_tagger.hpp; kernels_pattern.hip): immutable, shared by any number of workspaces
+// of ITS predictor.  One allocation; `arena` = the predictor's tag strings followed by the rules' (escaped), so that the writer copies either kind
+// from one base: a record's strings are {start, length} in it (the predictor's keep their places at its front).
+struct vpt_pattern_tagger {
+    const vpt_predictor* pred = nullptr;
+    int device = 0;
+    unsigned char* mem = nullptr;
+    const uint4* slots = nullptr; const uint32_t* surf = nullptr; const int32_t* rule_tags = nullptr; const uint2* id_str = nullptr;
+    const uint8_t* arena = nullptr;
+    uint32_t bits = 4, max_len = 0, n_tags = 0, n_ids = 0, max_suffix = 0, n_keys = 0;
+    std::vector<uint32_t> raw_off;     // vpt_pattern_tagger_tag: the tags as the caller gave them
+    std::vector<uint8_t> raw_bytes;
+};
+
 struct vpt_batch {
     const vpt_predictor* pred = nullptr;
     int device = 0;
@@ -275,12 +290,22 @@ struct vpt_batch {
     uint4* d_tag_records = nullptr; size_t tag_records_cap = 0;
     int32_t* d_rec_tags = nullptr; size_t rec_tags_cap = 0;
     uint64_t* d_tag_ctl = nullptr; size_t tag_ctl_cap = 0;          // the scan's state, run_pref [n_runs + 1]: zeroed as one range per call
-    uint64_t* d_run_pref = nullptr;                                 // (inside d_tag_ctl)
+    uint64_t* d_run_pref = nullptr;                                 // (inside d_tag_ctl, or d_pm_ctl: the run_pref of the records the readers take)
+    uint64_t* d_fill_run_pref = nullptr;                            // (inside d_tag_ctl: fill_tags' own, what vpt_evaluate_* reads)
     uint2* d_rec_str = nullptr; size_t rec_str_cap = 0;
     uint4* d_tag_cands = nullptr; size_t tag_cands_cap = 0;
     uint32_t* d_tag_summary = nullptr;
     uint64_t tag_chars = 0, tag_sentences = 0, tag_runs = 0;        // the batch those records belong to (0 chars: none)
     uint32_t tag_run_sent = 0;
+    // vpt_batch_set_pattern_tagger: the rules applied behind every fill_tags on this workspace (nullptr: none), and what they are merged into.
+    // rv_*: the records the readers take (the writer, expand_tags; not evaluate: it keeps to fill_tags' own) -- fill_tags' own, or the merged ones; d_run_pref goes with them.
+    const vpt_pattern_tagger* tagger = nullptr;
+    uint4* d_pm_records = nullptr; size_t pm_records_cap = 0;
+    int32_t* d_pm_rec_tags = nullptr; size_t pm_rec_tags_cap = 0;
+    uint2* d_pm_rec_str = nullptr; size_t pm_rec_str_cap = 0;
+    uint2* d_pm_hits = nullptr; size_t pm_hits_cap = 0;
+    uint64_t* d_pm_ctl = nullptr; size_t pm_ctl_cap = 0;
+    const uint4* rv_records = nullptr; const int32_t* rv_rec_tags = nullptr; const uint2* rv_rec_str = nullptr; const uint8_t* rv_str_bytes = nullptr;
     std::vector<uint64_t> h_boff, h_ooff;                           // rebased offsets of the call in flight (copied asynchronously)
     uint8_t* d_types = nullptr; size_t types_cap = 0;               // vpt_char_types_batch
     uint64_t* d_scan_part = nullptr; size_t scan_part_cap = 0;      // per-workgroup partials of the prefix sums (kernels_emit.hip)
@@ -376,6 +401,7 @@ void batch_release(vpt_batch* b) {
     (void)hipFree(b->d_parse_tmp); (void)hipFree(b->d_eval);
     (void)hipFree(b->d_lst_pos); (void)hipFree(b->d_lst_out); (void)hipFree(b->d_lst_off);
     (void)hipFree(b->d_gcls); (void)hipFree(b->d_gsum);
+    (void)hipFree(b->d_pm_records); (void)hipFree(b->d_pm_rec_tags); (void)hipFree(b->d_pm_rec_str); (void)hipFree(b->d_pm_hits); (void)hipFree(b->d_pm_ctl);
     for (auto& ps : b->pipe) {
         (void)hipFree(ps.text); (void)hipFree(ps.off); (void)hipFree(ps.scores); (void)hipFree(ps.labels);
         if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
@@ -445,6 +471,7 @@ struct Workspace {
         if (b->s_tok_in) (void)hipStreamSynchronize(b->s_tok_in);
         if (b->s_tok_out) (void)hipStreamSynchronize(b->s_tok_out);
         if (b->s_out) (void)hipStreamSynchronize(b->s_out);
+        b->tagger = nullptr;   // (the *_rules pipelines bind one for their call)
         std::lock_guard<std::mutex> g(p->pool_mu);
         p->pool.push_back(b);
     }

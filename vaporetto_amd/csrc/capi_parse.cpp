@@ -110,7 +110,7 @@ vpt_status evaluate_device_impl(const vpt_predictor* p, vpt_batch* b, const uint
     if (sys_tags == VPT_EVAL_TAGS_PREDICTED) {
         E.sys_n_tags = p->n_tags;
         if (p->n_tags) {
-            E.records = b->d_tag_records; E.rec_tags = b->d_rec_tags; E.rec_str = b->d_rec_str; E.run_pref = b->d_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;
+            E.records = b->d_tag_records; E.rec_tags = b->d_rec_tags; E.rec_str = b->d_rec_str; E.run_pref = b->d_fill_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;   // (fill_tags' own: the evaluate CLI runs no PatternMatchTagger)
             E.str_bytes = p->dtag.str_bytes;
         } else {
             E.mode = vpt::kEvalTagsNone;   // predict_tags returns early without tag models (predictor.rs:553-555): every vector empty

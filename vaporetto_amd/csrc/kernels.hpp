@@ -243,6 +243,30 @@ struct GraphemeParams {
 };
 hipError_t launch_concat_graphemes(const GraphemeParams& P, hipStream_t stream);
 
+// PatternMatchTagger behind fill_tags (kernels_pattern.hip; the table: pattern_tagger.hpp): every token whose whole surface is a rule's key gets the
+// rule's tags in the slots fill_tags left None.  A rule tag is -(2 + id) in rec_tags and in the dense array (-1 stays None, >= 0 a candidate of the
+// tag model); a record the rules made for a token without a tag model carries kTokModelMask where a model's records carry model + 1.
+// The merged records go to arrays of their own, sorted by position like fill_tags' -- a count per run, a scan, a scatter; no sort, no atomics.
+constexpr uint32_t kPatternStep = 256;   // chars a workgroup takes at a time (vpt_pattern_tagger_tile)
+struct PatternParams {
+    const uint4* slots; const uint32_t* surf; const int32_t* rule_tags; const uint2* id_str;   // the table; id_str: a tag's escaped bytes {start, length} in the writer's arena
+    uint32_t bits, max_len, n_tags;
+    const uint32_t* cps;        // decode_chars' words of the batch
+    const uint64_t* ooff;       // [S+1]
+    const uint8_t* labels;      // [total boundaries]
+    uint64_t n_sent, total_chars;
+    const uint4* records; const int32_t* rec_tags; const uint2* rec_str; const uint64_t* run_pref;   // what fill_tags left (TagParams)
+    uint64_t n_runs;
+    uint32_t run_sent;
+    uint2* hits;                // workspace [total_chars]: {rule + 1 | a new record << 31, new records of the run in front of the char}
+    uint4* out_records; int32_t* out_rec_tags; uint2* out_rec_str;
+    uint64_t* out_run_pref;     // [n_runs + 1], zero in front of the launches
+    uint64_t* scan_state;       // scan_part_entries(n_runs) zero words
+    int32_t* tags;              // the dense array of the C ABI, or nullptr
+    uint32_t n_cus;
+};
+hipError_t launch_pattern_tagger(const PatternParams& P, hipStream_t stream);
+
 // the predict CLI's listings (kernels_listing.hip): per line T, the scores block and the tag block in one arena (predict/src/main.rs:66-93, 122-176)
 constexpr uint32_t kListingScores = 1u, kListingTagScores = 2u, kListingTagged = 4u, kListingNoNormOrder = 8u;   // VPT_LISTING_*
 struct ListingParams {
