@@ -1938,6 +1938,41 @@ def test_pipelined_host_path_matches_oracle(chunk_chars, pinned, lanes, monkeypa
     assert "NULL" in str(e.value)
 
 
+def test_host_schedules_agree_on_cuts_and_errors(monkeypatch):
+    """One batch through the three ways vpt_predict_batch takes it -- in one piece, chunks over lanes, chunks through the event pipeline (the two
+    chunked ones share one cutter, vaporetto_amd/csrc/host_chunks.hpp): a first sentence longer than three chunks, a sentence that ends exactly
+    where a chunk is full (and where the batch's chars reach a multiple of the chunk size).  The oracle's scores, labels and offsets each way;
+    offsets that do not match the text, and an empty sentence, are refused in the same words each way wherever they fall in a chunk."""
+    m = randmodel.rand_model(777, alphabet="kana", wc=3, wt=3, n_char=200, n_dict=200, max_word=8)
+    raw = encode_model(m)
+    orc = cbind.OraclePredictor(raw, False)
+    rng = np.random.default_rng(50)
+    mixed = randmodel.ALPHABETS["kana"][:12] + list("漢字A9、")
+    lengths = [170, 20, 10, 20] + [int(n) for n in rng.integers(1, 31, 36)]      # chunks of 50 chars: {0}, {1, 2, 3} = 50 exactly (220 in all), ...
+    texts = ["".join(rng.choice(mixed, size=n)) for n in lengths]
+    assert len(texts) == 40
+    utf8, boff = api.pack_texts([t.encode("utf-8") for t in texts])
+    o_scores, o_labels, o_ooff, _ = orc.predict_batch(utf8, boff)
+    bad_ooff = o_ooff.copy()
+    bad_ooff[31] += 1000                     # sentence 30 claims more chars than it has bytes
+    empty_boff = boff.copy()
+    empty_boff[31] = empty_boff[30]          # sentence 30 has no bytes
+    for lanes in ("0", "3", None):
+        if lanes is None:
+            monkeypatch.delenv("VPT_CHUNK_CHARS")
+            monkeypatch.delenv("VPT_PIPE_LANES")
+        else:
+            monkeypatch.setenv("VPT_CHUNK_CHARS", "50")
+            monkeypatch.setenv("VPT_PIPE_LANES", lanes)
+        pred = api.Predictor(api.Model.read_slice(raw)[0], False)      # the library reads its knobs when a predictor is made
+        scores, labels, ooff = api.predict_packed_sharded([pred], utf8, boff)
+        assert np.array_equal(ooff, o_ooff) and np.array_equal(scores, o_scores) and np.array_equal(labels, o_labels), lanes
+        with pytest.raises(api.VaporettoError, match="out_offsets: do not match"):
+            api.predict_packed_sharded([pred], utf8, boff, out_offsets=bad_ooff)
+        with pytest.raises(api.VaporettoError, match="must contain at least one character"):
+            api.predict_packed_sharded([pred], utf8, empty_boff, out_offsets=o_ooff)
+
+
 def test_tokenize_with_the_grapheme_cluster_filter():
     """`--wsconst G` of the CLI (predict/src/main.rs:101-104): Predictor.tokenize(.., wsconst=("G", ..)) = predict, ConcatGraphemeClustersFilter on
     the host, [fill_tags,] writer -- line for line what the per-sentence mirror gives, with and without the char-type filter, tags and

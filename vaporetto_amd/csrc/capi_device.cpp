@@ -89,19 +89,13 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     uint32_t slow_blocks = 0, scratch_cap = 0;
     uint64_t slab = 0;
     if (fast && cut_tiles) {
-        if ((st = grow(&b->d_tiles, &b->tiles_cap, size_t(n_tiles) + 1)) != VPT_OK) return st;
+        if ((st = b->d_tiles.grow(size_t(n_tiles) + 1)) != VPT_OK) return st;
         size_t n_local = 0, n_super = 0;
         vpt::cut_index_entries(total_chars, &n_local, &n_super);
-        if ((st = grow(&b->d_cut_local, &b->cut_local_cap, n_local + 16)) != VPT_OK) return st;
-        if ((st = grow(&b->d_cut_super, &b->cut_super_cap, n_super + 16)) != VPT_OK) return st;
+        if ((st = b->d_cut_local.grow(n_local + 16)) != VPT_OK) return st;
+        if ((st = b->d_cut_super.grow(n_super + 16)) != VPT_OK) return st;
     } else {
-        if (size_t(n_tiles) + 1 > b->tile_cap || !b->d_tile_first) {
-            (void)hipFree(b->d_slow_list); b->d_slow_list = nullptr;
-            size_t tcap = b->tile_cap;
-            if ((st = grow(&b->d_tile_first, &tcap, size_t(n_tiles) + 1)) != VPT_OK) return st;
-            b->tile_cap = tcap;
-            VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_slow_list), tcap * sizeof(uint32_t) + 64));
-        }
+        if ((st = grow_pair(b->d_tile_first, b->d_slow_list, size_t(n_tiles) + 1)) != VPT_OK) return st;
         // long-sentence scratch of the general kernels (only when a sentence might not fit the LDS tile)
         need_slow = !fast && max_chars + 2 * uint64_t(p->pad) + tile_flat > cap;
         if (need_slow) {
@@ -111,14 +105,10 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
             slab = (uint64_t(scratch_cap) * 9 + 255) & ~255ull;
             slow_blocks = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(64, (8ull << 30) / slab)));
             const size_t need = size_t(slab) * slow_blocks;
-            if (need > b->scratch_bytes) {
-                (void)hipFree(b->d_scratch); b->d_scratch = nullptr; b->scratch_bytes = 0;
-                VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_scratch), need));
-                b->scratch_bytes = need;
-            }
+            if (need > b->d_scratch.cap && (st = b->d_scratch.alloc(need)) != VPT_OK) return st;
         }
     }
-    P.text = d_utf8; P.boff = d_byte_offsets; P.ooff = d_out_offsets; P.tile_first = b->d_tile_first; P.tiles = (fast && cut_tiles) ? b->d_tiles : nullptr;
+    P.text = d_utf8; P.boff = d_byte_offsets; P.ooff = d_out_offsets; P.tile_first = b->d_tile_first; P.tiles = (fast && cut_tiles) ? b->d_tiles.p : nullptr;
     P.scores = d_scores; P.labels = d_labels; P.status = b->d_ctrl; P.slow_list = b->d_slow_list; P.slow_count = b->d_ctrl + 1;
     P.scratch = b->d_scratch; P.scratch_stride = slab; P.scratch_cap = scratch_cap;
     P.prof = b->d_prof;
@@ -128,7 +118,7 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     // predictor.rs:542) skips its own decode pass.
     b->cps_text = nullptr;
     if (p->has_tags && p->predict_tags && fast) {
-        vpt_status st2 = grow(&b->d_cps, &b->cps_cap, size_t(total_chars) + 16);
+        vpt_status st2 = b->d_cps.grow(size_t(total_chars) + 16);
         if (st2 != VPT_OK) return st2;
         P.cps_out = b->d_cps;
         b->cps_text = d_utf8; b->cps_ooff = d_out_offsets; b->cps_sentences = n_sentences; b->cps_boundaries = total_boundaries;
@@ -192,11 +182,11 @@ vpt_status concat_graphemes_impl(const vpt_predictor* p, vpt_batch* b, const uin
     vpt::GraphemeParams G{};
     vpt_status st;
     if ((st = grapheme_table_on(p->device, &G.table)) != VPT_OK) return st;
-    if ((st = grow(&b->d_gcls, &b->gcls_cap, size_t(n_tiles) * vpt::kGraphemeTile)) != VPT_OK) return st;
-    if ((st = grow(&b->d_gsum, &b->gsum_cap, 2 * size_t(n_tiles))) != VPT_OK) return st;
+    if ((st = b->d_gcls.grow(size_t(n_tiles) * vpt::kGraphemeTile)) != VPT_OK) return st;
+    if ((st = b->d_gsum.grow(2 * size_t(n_tiles))) != VPT_OK) return st;
     if (!have_cps) {
         const bool fw = (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
-        if ((st = grow(&b->d_cps, &b->cps_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = b->d_cps.grow(size_t(total_c) + 16)) != VPT_OK) return st;
         b->cps_text = nullptr;
         VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_c, p->d_cinfo + (fw ? 65536 : 0), b->d_cps, nullptr, b->d_ctrl, stream, fw));
     }
@@ -250,7 +240,7 @@ vpt_status vpt_predict_write_batch_device(const vpt_predictor* p, vpt_batch* b, 
     if (!d_utf8 || !d_byte_offsets || !d_out_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
     uint8_t* labels = d_labels;
     if (!labels) {
-        const vpt_status st = grow(&b->d_tlab, &b->tlab_cap, size_t(total_boundaries) + 16);
+        const vpt_status st = b->d_tlab.grow(size_t(total_boundaries) + 16);
         if (st != VPT_OK) return st;
         labels = b->d_tlab;
     }
@@ -308,7 +298,7 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     const uint64_t total_c = total_boundaries + n_sentences;
     // record numbers and queue places are 32-bit (one per char at most)
     if (total_c >= 0xFFFFFF00ull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: fill_tags takes fewer than 2^32 - 256 chars per call");
-    vpt_status st = grow(&b->d_cps, &b->cps_cap, size_t(total_c) + 16);
+    vpt_status st = b->d_cps.grow(size_t(total_c) + 16);
     if (st != VPT_OK) return st;
     b->tag_chars = 0;   // (until the launches are enqueued: a failure below leaves no records behind)
     // What the call leaves is ONE RECORD PER TOKEN THAT HAS A TAG MODEL (kernels.hpp, TagParams): the reference holds None for every other
@@ -318,12 +308,12 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     const uint32_t run_sent = vpt::tag_run_sentences(n_sentences, total_c);
     const uint64_t n_runs = (uint64_t(n_sentences) + run_sent - 1) / run_sent;
     const size_t n_state = vpt::scan_part_entries(n_runs), ctl_words = n_state + size_t(n_runs) + 2;
-    if ((st = grow(&b->d_tag_records, &b->tag_records_cap, size_t(total_c) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_rec_tags, &b->rec_tags_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_rec_str, &b->rec_str_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_tag_cands, &b->tag_cands_cap, size_t(total_c) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_tag_ctl, &b->tag_ctl_cap, ctl_words)) != VPT_OK) return st;
-    if (!b->d_tag_summary) VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_tag_summary), vpt::tag_summary_words() * sizeof(uint32_t)));
+    if ((st = b->d_tag_records.grow(size_t(total_c) + 16)) != VPT_OK) return st;
+    if ((st = b->d_rec_tags.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+    if ((st = b->d_rec_str.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+    if ((st = b->d_tag_cands.grow(size_t(total_c) + 16)) != VPT_OK) return st;
+    if ((st = b->d_tag_ctl.grow(ctl_words)) != VPT_OK) return st;
+    if (!b->d_tag_summary && (st = b->d_tag_summary.alloc(vpt::tag_summary_words() * sizeof(uint32_t))) != VPT_OK) return st;
     VPT_HIP(hipMemsetAsync(b->d_tag_ctl, 0, ctl_words * sizeof(uint64_t), stream));   // the scan's state, the runs' counts
     // the dense arrays of the C ABI, for the callers that want them: None everywhere (what `resize(n_tags * len, None)` leaves, predictor.rs:556-557);
     // the passes write the entries of the tokens that have a model
@@ -353,11 +343,11 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     b->rv_records = b->d_tag_records; b->rv_rec_tags = b->d_rec_tags; b->rv_rec_str = b->d_rec_str; b->rv_str_bytes = p->dtag.str_bytes;
     if (const vpt_pattern_tagger* t = b->tagger) {   // PatternMatchTagger: the rules' tags merged into records of their own (kernels_pattern.hip)
         const size_t pm_words = n_state + size_t(n_runs) + 2;
-        if ((st = grow(&b->d_pm_records, &b->pm_records_cap, size_t(total_c) + 16)) != VPT_OK) return st;
-        if ((st = grow(&b->d_pm_rec_tags, &b->pm_rec_tags_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
-        if ((st = grow(&b->d_pm_rec_str, &b->pm_rec_str_cap, size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
-        if ((st = grow(&b->d_pm_hits, &b->pm_hits_cap, size_t(total_c) + 16)) != VPT_OK) return st;
-        if ((st = grow(&b->d_pm_ctl, &b->pm_ctl_cap, pm_words)) != VPT_OK) return st;
+        if ((st = b->d_pm_records.grow(size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = b->d_pm_rec_tags.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+        if ((st = b->d_pm_rec_str.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
+        if ((st = b->d_pm_hits.grow(size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = b->d_pm_ctl.grow(pm_words)) != VPT_OK) return st;
         VPT_HIP(hipMemsetAsync(b->d_pm_ctl, 0, pm_words * sizeof(uint64_t), stream));
         vpt::PatternParams R{};
         R.slots = t->slots; R.surf = t->surf; R.rule_tags = t->rule_tags; R.id_str = t->id_str; R.bits = t->bits; R.max_len = t->max_len; R.n_tags = p->n_tags;
@@ -411,9 +401,8 @@ vpt_status plan_runs(const vpt_predictor* p, vpt_batch* b, size_t n_sentences, u
     const size_t words = size_t(F.n_blocks) + 1;
     if (words > b->emit_state_cap) {
         const size_t cap = std::max(words + words / 2, size_t(4096));
-        (void)hipFree(b->d_emit_state);   // (waits for the device)
-        b->d_emit_state = nullptr; b->emit_state_cap = 0;
-        VPT_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_emit_state), 2 * cap * sizeof(uint64_t)));
+        b->emit_state_cap = 0;
+        if (const vpt_status st = b->d_emit_state.alloc(2 * cap * sizeof(uint64_t)); st != VPT_OK) return st;   // (freeing the old one waits for the device)
         VPT_HIP(hipMemsetAsync(b->d_emit_state, 0, 2 * cap * sizeof(uint64_t), stream));   // (in front of the kernel on ITS stream: a plain hipMemset is not ordered with a non-blocking stream)
         b->emit_state_cap = cap; b->emit_dirty[0] = b->emit_dirty[1] = 0; b->emit_flip = 0;
     }
@@ -547,33 +536,33 @@ vpt_status vpt_predict_listing_batch_device(const vpt_predictor* p, vpt_batch* b
     vpt::ListingParams L{};
     L.n_elem = 2 * total_c + n_sentences;
     const size_t n_part = vpt::scan_part_entries(L.n_elem), n_pos = size_t(L.n_elem) + 2;
-    if ((st = grow(&b->d_lst_pos, &b->lst_pos_cap, n_pos + n_part + 2 + n_sentences + 1)) != VPT_OK) return st;
+    if ((st = b->d_lst_pos.grow(n_pos + n_part + 2 + n_sentences + 1)) != VPT_OK) return st;
     VPT_HIP(hipMemsetAsync(b->d_lst_pos + n_pos, 0, (n_part + 2) * sizeof(uint64_t), stream));
     uint64_t* const ooff = b->d_lst_pos + n_pos + n_part + 2;
     VPT_HIP(vpt::launch_listing_offsets(d_out_offsets, n_sentences, total_boundaries, ooff, reinterpret_cast<uint32_t*>(b->d_lst_pos + n_pos + n_part), b->d_ctrl, stream));
     if (with_tags) {   // Sentence::fill_tags with store_tag_scores (main.rs:113-115, 132-134): leaves the chars in d_cps, the records for the writer
         if (tag_block) {
-            if ((st = grow(&b->d_tag_scores, &b->tag_scores_cap, size_t(total_c) * p->max_tag_scores + 16)) != VPT_OK) return st;
-            if ((st = grow(&b->d_tag_models, &b->tag_models_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+            if ((st = b->d_tag_scores.grow(size_t(total_c) * p->max_tag_scores + 16)) != VPT_OK) return st;
+            if ((st = b->d_tag_models.grow(size_t(total_c) + 16)) != VPT_OK) return st;
         }
         st = vpt_fill_tags_scores_batch_device(p, b, d_utf8, d_byte_offsets, ooff, n_sentences, total_boundaries, d_labels, nullptr,
-                                               tag_block ? b->d_tag_scores : nullptr, tag_block ? b->d_tag_models : nullptr, hip_stream);
+                                               tag_block ? b->d_tag_scores.p : nullptr, tag_block ? b->d_tag_models.p : nullptr, hip_stream);
         if (st != VPT_OK) return st;
     } else if (listing & (VPT_LISTING_SCORES | VPT_LISTING_TAG_SCORES)) {
-        if ((st = grow(&b->d_cps, &b->cps_cap, size_t(total_c) + 16)) != VPT_OK) return st;
+        if ((st = b->d_cps.grow(size_t(total_c) + 16)) != VPT_OK) return st;
         const bool fw = (b->flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
         VPT_HIP(vpt::launch_decode_chars(d_utf8, d_byte_offsets, ooff, n_sentences, total_c, p->d_cinfo + (fw ? 65536 : 0), b->d_cps, nullptr, b->d_ctrl, stream, fw));
     }
     const bool tagged = (listing & VPT_LISTING_TAGGED) && p->n_tags > 0;
     const uint64_t t_cap = 3 * text_bytes + (tagged ? total_c * (uint64_t(p->max_tag_suffix) + (b->tagger ? b->tagger->max_suffix : 0u)) : 0) + 16;
-    if ((st = grow(&b->d_tok, &b->tok_cap, size_t(t_cap) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 1)) != VPT_OK) return st;
+    if ((st = b->d_tok.grow(size_t(t_cap) + 16)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(n_sentences + 1)) != VPT_OK) return st;
     st = emit_device(p, b, d_utf8, d_byte_offsets, ooff, n_sentences, total_boundaries, d_labels, tagged, b->d_tok, t_cap, b->d_toff, stream);
     if (st != VPT_OK) return st;
     L.cps = b->d_cps; L.ooff = ooff; L.scores = d_scores; L.labels = d_labels; L.n_sent = n_sentences; L.total_boundaries = total_boundaries;
     L.t_text = b->d_tok; L.t_off = b->d_toff; L.t_cap = t_cap;
     if (tag_block) {
-        L.tag_models = b->d_tag_models; L.tag_scores = p->max_tag_scores ? b->d_tag_scores : nullptr; L.score_stride = p->max_tag_scores;
+        L.tag_models = b->d_tag_models; L.tag_scores = p->max_tag_scores ? b->d_tag_scores.p : nullptr; L.score_stride = p->max_tag_scores;
         L.n_models = p->dtag.n_models; L.n_strings = p->dtag.n_strings;
         L.models = p->dtag.models; L.slots = p->dtag.slots; L.slot_str = p->dtag.slot_str; L.str_off = p->dtag.str_off; L.str_bytes = p->dtag.str_bytes;
     }
@@ -622,7 +611,7 @@ vpt_status count_boundaries_impl(const vpt_predictor* p, vpt_batch* b, const uin
     VPT_HIP(hipSetDevice(p->device));
     if (n_sentences == 0) VPT_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), stream));
     else {
-        const vpt_status st = grow(&b->d_scan_part, &b->scan_part_cap, vpt::scan_part_entries(n_sentences));
+        const vpt_status st = b->d_scan_part.grow(vpt::scan_part_entries(n_sentences));
         if (st != VPT_OK) return st;
         VPT_HIP(vpt::launch_count_boundaries(d_utf8, d_byte_offsets, n_sentences, d_out_offsets, b->d_scan_part, b->d_ctrl, nullptr /* nobody reads the longest sentence: no launch to clear it */, text_bytes_hint, stream));
     }

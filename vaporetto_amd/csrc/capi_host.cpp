@@ -23,6 +23,76 @@ PipePlan pipeline_plan(const PredictorKnobs& knobs, uint64_t total_chars) {
     return plan;
 }
 
+// A few workspaces that take a call's chunks in turn, each on its own stream: lane 0 is the call's, the others are taken from the pool here and
+// go back to it when the guard dies -- declared behind lane 0's Workspace, so before it does.
+struct Lanes {
+    static constexpr int kMax = 8;
+    Workspace extra[kMax - 1];
+    vpt_batch* lane[kMax] = {};
+    int n = 1;
+    vpt_status init(const vpt_predictor* p, vpt_batch* b, int n_lanes) {
+        n = std::max(1, std::min(n_lanes, kMax));
+        lane[0] = b;
+        for (int l = 1; l < n; ++l) {
+            const vpt_status st = acquire(p, &extra[l - 1]);
+            if (st != VPT_OK) return st;
+            lane[l] = extra[l - 1].b;
+            lane[l]->flags = b->flags;
+        }
+        return VPT_OK;
+    }
+    vpt_batch* operator[](size_t k) const { return lane[k % size_t(n)]; }
+    // The device's verdict over every chunk (a lane's status word accumulates), folded into `st`: the lanes' words are fetched together, one
+    // round trip for all of them instead of one each.
+    vpt_status verdict(vpt_status st = VPT_OK) {
+        uint32_t ctrl[kMax][2] = {};
+        for (int l = 0; l < n; ++l)
+            if (lane[l]->pending) VPT_HIP(hipMemcpyAsync(ctrl[l], lane[l]->d_ctrl, sizeof(ctrl[l]), hipMemcpyDeviceToHost, lane[l]->last_stream));
+        for (int l = 0; l < n; ++l) {
+            if (!lane[l]->pending) continue;
+            VPT_HIP(hipStreamSynchronize(lane[l]->last_stream));
+            lane[l]->pending = false;
+            if (ctrl[l][0]) {
+                VPT_HIP(hipMemset(lane[l]->d_ctrl, 0, sizeof(uint32_t)));
+                if (st == VPT_OK) st = status_from_bits(ctrl[l][0]);
+            }
+        }
+        return st;
+    }
+};
+
+// b->chunk_ev holds n events
+vpt_status chunk_events(vpt_batch* b, size_t n) {
+    while (b->chunk_ev.size() < n) {
+        hipEvent_t e;
+        VPT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        b->chunk_ev.push_back(e);
+    }
+    return VPT_OK;
+}
+
+// What a call left on the device for the caller, after its sync: the n + 1 offsets, then as many elements as the last of them says -- or none of
+// them, and `too_small`, where the caller's buffer holds fewer.
+template <typename T>
+vpt_status download_sized(uint64_t* offsets_out, const uint64_t* d_offsets, size_t n, T* out, const T* d_out, uint64_t capacity, const char* too_small) {
+    VPT_HIP(hipMemcpy(offsets_out, d_offsets, 8 * (n + 1), hipMemcpyDeviceToHost));
+    const uint64_t total = offsets_out[n];
+    if (total > capacity) return fail(VPT_INVALID_ARGUMENT, too_small);
+    if (total) VPT_HIP(hipMemcpy(out, d_out, sizeof(T) * size_t(total), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+const char* const kTextTooSmall = "InvalidArgumentError: text_capacity: smaller than the tokenized text";
+const char* const kTokensTooSmall = "InvalidArgumentError: capacity: smaller than the number of tokens";
+
+// The cutter of a vpt_predict_batch call over b's pinned staging (both schedules).
+vpt_status predict_cutter(vpt_batch* b, const uint64_t* byte_offsets, const uint64_t* out_offsets, size_t n_sentences, uint64_t chunk_chars, vptcut::PredictCutter* out) {
+    const uint64_t total_chars = out_offsets[n_sentences] - out_offsets[0] + n_sentences;
+    const size_t max_chunks = vptcut::predict_max_chunks(n_sentences, total_chars, chunk_chars);
+    const vpt_status st = pinned_words(b, vptcut::predict_pinned_words(n_sentences, max_chunks));
+    *out = vptcut::PredictCutter{byte_offsets, out_offsets, n_sentences, chunk_chars, max_chunks, b->h_off};
+    return st;
+}
+
 // vpt_predict_batch for a LARGE batch: the copy in of chunk k + 1, the kernels of chunk k and the copy out of chunk k - 1 run at
 // the same time on three streams over two sets of device buffers, so that a caller with PINNED buffers (vpt_host_alloc) gets
 // both directions of the PCIe link busy at once instead of a copy-launch-copy sequence; pageable buffers go through the
@@ -42,52 +112,29 @@ vpt_status predict_pipelined(const vpt_predictor* p, vpt_batch* b, const uint8_t
             VPT_HIP(hipEventCreateWithFlags(&ps.ev_out, hipEventDisableTiming));
         }
     }
-    const uint64_t total_chars = out_offsets[n_sentences] - out_offsets[0] + n_sentences;
-    const size_t max_chunks = std::min<size_t>(n_sentences, size_t(total_chars / chunk_chars) + 2);   // every chunk holds a sentence
-    const size_t need_off = 2 * (n_sentences + max_chunks);   // a chunk of n sentences stages 2 (n + 1) offsets
-    if (need_off > b->h_off_cap) {
-        if (b->h_off) (void)hipHostFree(b->h_off);
-        b->h_off = nullptr; b->h_off_cap = 0;
-        VPT_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_off), (need_off + need_off / 2) * sizeof(uint64_t), hipHostMallocDefault));
-        b->h_off_cap = need_off + need_off / 2;
-    }
+    vptcut::PredictCutter cutter{};
     vpt_status st;
-    size_t i = 0, staged = 0;
-    for (size_t k = 0; i < n_sentences; ++k) {
+    if ((st = predict_cutter(b, byte_offsets, out_offsets, n_sentences, chunk_chars, &cutter)) != VPT_OK) return st;
+    for (size_t k = 0; !cutter.done(); ++k) {
         vpt_batch::PipeSet& ps = b->pipe[k & 1];
         // ---- walk the chunk's sentences: validate, rebase, cut
-        const size_t a = i;
-        const uint64_t t0 = byte_offsets[a], o0 = out_offsets[a];
-        uint64_t* hb = b->h_off + staged;             // n + 1 byte offsets, then n + 1 boundary offsets, filled below
-        uint64_t chars = 0, max_bytes = 0, max_chars = 0;
-        while (i < n_sentences && chars < chunk_chars) {
-            if (byte_offsets[i + 1] <= byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: must contain at least one character");
-            const uint64_t nby = byte_offsets[i + 1] - byte_offsets[i];
-            if (out_offsets[i + 1] < out_offsets[i] || out_offsets[i + 1] - out_offsets[i] + 1 > nby)
-                return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out_offsets: do not match the text (or the text is not valid UTF-8)");
-            const uint64_t nch = out_offsets[i + 1] - out_offsets[i] + 1;
-            max_bytes = std::max(max_bytes, nby); max_chars = std::max(max_chars, nch);
-            chars += nch;
-            ++i;
-        }
-        const size_t n = i - a;
-        uint64_t* ho = hb + (n + 1);
-        for (size_t j = 0; j <= n; ++j) { hb[j] = byte_offsets[a + j] - t0; ho[j] = out_offsets[a + j] - o0; }
-        staged += 2 * (n + 1);
-        const uint64_t nbytes = byte_offsets[i] - t0, nb = out_offsets[i] - o0;
+        const vptcut::PredictChunk c = cutter.next();
+        if (c.error != vptcut::CutError::kNone) return cut_fail(c.error);
+        const size_t n = c.n;
+        const uint64_t t0 = byte_offsets[c.a], o0 = out_offsets[c.a], nbytes = c.off[n], nb = c.off[2 * n + 1];
         // ---- this set's buffers are free once chunk k - 2 has been scored (inputs) and copied out (outputs)
         if (k >= 2) { VPT_HIP(hipEventSynchronize(ps.ev_out)); }   // also bounds how far the host runs ahead; growing a buffer below is then safe
-        if ((st = grow(&ps.text, &ps.text_cap, size_t(nbytes) + 32)) != VPT_OK) return st;
-        if ((st = grow(&ps.off, &ps.off_cap, 2 * (n + 1))) != VPT_OK) return st;
-        if (scores_out && (st = grow(&ps.scores, &ps.scores_cap, size_t(nb) + 1)) != VPT_OK) return st;
-        if (labels_out && (st = grow(&ps.labels, &ps.labels_cap, size_t(nb) + 1)) != VPT_OK) return st;
+        if ((st = ps.text.grow(size_t(nbytes) + 32)) != VPT_OK) return st;
+        if ((st = ps.off.grow(2 * (n + 1))) != VPT_OK) return st;
+        if (scores_out && (st = ps.scores.grow(size_t(nb) + 1)) != VPT_OK) return st;
+        if (labels_out && (st = ps.labels.grow(size_t(nb) + 1)) != VPT_OK) return st;
         VPT_HIP(hipMemcpyAsync(ps.text, utf8 + t0, size_t(nbytes), hipMemcpyHostToDevice, b->s_in));
-        VPT_HIP(hipMemcpyAsync(ps.off, hb, 16 * (n + 1), hipMemcpyHostToDevice, b->s_in));
+        VPT_HIP(hipMemcpyAsync(ps.off, c.off, 16 * (n + 1), hipMemcpyHostToDevice, b->s_in));
         VPT_HIP(hipEventRecord(ps.ev_in, b->s_in));
         VPT_HIP(hipStreamWaitEvent(b->own_stream, ps.ev_in, 0));
-        b->max_chars = max_chars;
-        st = vpt_predict_batch_device(p, b, ps.text, ps.off, ps.off + (n + 1), n, nb, max_bytes, scores_out ? ps.scores : nullptr,
-                                      labels_out ? ps.labels : nullptr, b->own_stream);
+        b->max_chars = c.max_chars;
+        st = vpt_predict_batch_device(p, b, ps.text, ps.off, ps.off + (n + 1), n, nb, c.max_bytes, scores_out ? ps.scores.p : nullptr,
+                                      labels_out ? ps.labels.p : nullptr, b->own_stream);
         if (st != VPT_OK) return st;
         VPT_HIP(hipEventRecord(ps.ev_k, b->own_stream));
         VPT_HIP(hipStreamWaitEvent(b->s_out, ps.ev_k, 0));
@@ -106,82 +153,37 @@ vpt_status predict_pipelined(const vpt_predictor* p, vpt_batch* b, const uint8_t
 // no host synchronisation before the end (a set's reuse is ordered by its own stream), and the copies out go through SDMA.
 vpt_status predict_lanes(const vpt_predictor* p, vpt_batch* b, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
                          int32_t* scores_out, uint8_t* labels_out, const uint64_t* out_offsets, uint64_t chunk_chars, int n_lanes) {
-    constexpr int kMaxLanes = 8;
-    n_lanes = std::max(1, std::min(n_lanes, kMaxLanes));
-    Workspace extra[kMaxLanes - 1];
-    vpt_batch* lane[kMaxLanes] = {b};
+    Lanes lanes;
     vpt_status st;
-    for (int l = 1; l < n_lanes; ++l) {
-        if ((st = acquire(p, &extra[l - 1])) != VPT_OK) return st;
-        lane[l] = extra[l - 1].b;
-        lane[l]->flags = b->flags;
-    }
-    const uint64_t total_chars = out_offsets[n_sentences] - out_offsets[0] + n_sentences;
-    const size_t max_chunks = std::min<size_t>(n_sentences, size_t(total_chars / chunk_chars) + 2);
-    const size_t need_off = 2 * (n_sentences + max_chunks);   // a chunk of n sentences stages 2 (n + 1) offsets
-    if (need_off > b->h_off_cap) {
-        if (b->h_off) (void)hipHostFree(b->h_off);
-        b->h_off = nullptr; b->h_off_cap = 0;
-        VPT_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_off), (need_off + need_off / 2) * sizeof(uint64_t), hipHostMallocDefault));
-        b->h_off_cap = need_off + need_off / 2;
-    }
-    size_t i = 0, staged = 0;
-    for (size_t k = 0; i < n_sentences; ++k) {
-        vpt_batch* bb = lane[k % size_t(n_lanes)];
+    if ((st = lanes.init(p, b, n_lanes)) != VPT_OK) return st;
+    vptcut::PredictCutter cutter{};
+    if ((st = predict_cutter(b, byte_offsets, out_offsets, n_sentences, chunk_chars, &cutter)) != VPT_OK) return st;
+    for (size_t k = 0; !cutter.done(); ++k) {
+        vpt_batch* bb = lanes[k];
         vpt_batch::PipeSet& ps = bb->pipe[0];
         hipStream_t s = bb->own_stream;
-        const size_t a = i;
-        const uint64_t t0 = byte_offsets[a], o0 = out_offsets[a];
-        uint64_t* hb = b->h_off + staged;
-        uint64_t chars = 0, max_bytes = 0, max_chars = 0;
-        while (i < n_sentences && chars < chunk_chars) {
-            if (byte_offsets[i + 1] <= byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: must contain at least one character");
-            const uint64_t nby = byte_offsets[i + 1] - byte_offsets[i];
-            if (out_offsets[i + 1] < out_offsets[i] || out_offsets[i + 1] - out_offsets[i] + 1 > nby)
-                return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out_offsets: do not match the text (or the text is not valid UTF-8)");
-            const uint64_t nch = out_offsets[i + 1] - out_offsets[i] + 1;
-            max_bytes = std::max(max_bytes, nby); max_chars = std::max(max_chars, nch);
-            chars += nch;
-            ++i;
-        }
-        const size_t n = i - a;
-        uint64_t* ho = hb + (n + 1);
-        for (size_t j = 0; j <= n; ++j) { hb[j] = byte_offsets[a + j] - t0; ho[j] = out_offsets[a + j] - o0; }
-        staged += 2 * (n + 1);
-        const uint64_t nbytes = byte_offsets[i] - t0, nb = out_offsets[i] - o0;
+        const vptcut::PredictChunk c = cutter.next();
+        if (c.error != vptcut::CutError::kNone) return cut_fail(c.error);
+        const size_t n = c.n;
+        const uint64_t t0 = byte_offsets[c.a], o0 = out_offsets[c.a], nbytes = c.off[n], nb = c.off[2 * n + 1];
         // a buffer that has to grow may still be read or written by the lane's earlier chunk
-        if (size_t(nbytes) + 32 > ps.text_cap || 2 * (n + 1) > ps.off_cap || (scores_out && size_t(nb) + 1 > ps.scores_cap) ||
-            (labels_out && size_t(nb) + 1 > ps.labels_cap))
+        if (size_t(nbytes) + 32 > ps.text.cap || 2 * (n + 1) > ps.off.cap || (scores_out && size_t(nb) + 1 > ps.scores.cap) ||
+            (labels_out && size_t(nb) + 1 > ps.labels.cap))
             VPT_HIP(hipStreamSynchronize(s));
-        if ((st = grow(&ps.text, &ps.text_cap, size_t(nbytes) + 32)) != VPT_OK) return st;
-        if ((st = grow(&ps.off, &ps.off_cap, 2 * (n + 1))) != VPT_OK) return st;
-        if (scores_out && (st = grow(&ps.scores, &ps.scores_cap, size_t(nb) + 1)) != VPT_OK) return st;
-        if (labels_out && (st = grow(&ps.labels, &ps.labels_cap, size_t(nb) + 1)) != VPT_OK) return st;
+        if ((st = ps.text.grow(size_t(nbytes) + 32)) != VPT_OK) return st;
+        if ((st = ps.off.grow(2 * (n + 1))) != VPT_OK) return st;
+        if (scores_out && (st = ps.scores.grow(size_t(nb) + 1)) != VPT_OK) return st;
+        if (labels_out && (st = ps.labels.grow(size_t(nb) + 1)) != VPT_OK) return st;
         VPT_HIP(hipMemcpyAsync(ps.text, utf8 + t0, size_t(nbytes), hipMemcpyHostToDevice, s));
-        VPT_HIP(hipMemcpyAsync(ps.off, hb, 16 * (n + 1), hipMemcpyHostToDevice, s));
-        bb->max_chars = max_chars;
-        st = vpt_predict_batch_device(p, bb, ps.text, ps.off, ps.off + (n + 1), n, nb, max_bytes, scores_out ? ps.scores : nullptr,
-                                      labels_out ? ps.labels : nullptr, s);
+        VPT_HIP(hipMemcpyAsync(ps.off, c.off, 16 * (n + 1), hipMemcpyHostToDevice, s));
+        bb->max_chars = c.max_chars;
+        st = vpt_predict_batch_device(p, bb, ps.text, ps.off, ps.off + (n + 1), n, nb, c.max_bytes, scores_out ? ps.scores.p : nullptr,
+                                      labels_out ? ps.labels.p : nullptr, s);
         if (st != VPT_OK) return st;
         if (scores_out && nb) VPT_HIP(hipMemcpyAsync(scores_out + o0, ps.scores, 4 * size_t(nb), hipMemcpyDeviceToHost, s));
         if (labels_out && nb) VPT_HIP(hipMemcpyAsync(labels_out + o0, ps.labels, size_t(nb), hipMemcpyDeviceToHost, s));
     }
-    // the device's verdict over every chunk (a lane's status word accumulates): the lanes' words are fetched together, one
-    // round trip for all of them instead of one each
-    uint32_t ctrl[kMaxLanes][2] = {};
-    for (int l = 0; l < n_lanes; ++l)
-        if (lane[l]->pending) VPT_HIP(hipMemcpyAsync(ctrl[l], lane[l]->d_ctrl, sizeof(ctrl[l]), hipMemcpyDeviceToHost, lane[l]->last_stream));
-    st = VPT_OK;
-    for (int l = 0; l < n_lanes; ++l) {
-        if (!lane[l]->pending) continue;
-        VPT_HIP(hipStreamSynchronize(lane[l]->last_stream));
-        lane[l]->pending = false;
-        if (ctrl[l][0]) {
-            VPT_HIP(hipMemset(lane[l]->d_ctrl, 0, sizeof(uint32_t)));
-            if (st == VPT_OK) st = status_from_bits(ctrl[l][0]);
-        }
-    }
-    return st;
+    return lanes.verdict();
 }
 
 }  // namespace
@@ -213,7 +215,7 @@ vpt_status vpt_predict_batch_flags(const vpt_predictor* p, const uint8_t* utf8, 
     b->max_chars = max_chars;
     hipStream_t s = b->own_stream;
     st = vpt_predict_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, max_bytes,
-                                  scores_out ? b->d_scores : nullptr, labels_out ? b->d_labels : nullptr, s);
+                                  scores_out ? b->d_scores.p : nullptr, labels_out ? b->d_labels.p : nullptr, s);
     if (st != VPT_OK) return st;
     if (scores_out && total_b) VPT_HIP(hipMemcpyAsync(scores_out + out_offsets[0], b->d_scores, 4 * total_b, hipMemcpyDeviceToHost, s));
     if (labels_out && total_b) VPT_HIP(hipMemcpyAsync(labels_out + out_offsets[0], b->d_labels, total_b, hipMemcpyDeviceToHost, s));
@@ -249,15 +251,15 @@ static vpt_status fill_tags_host(const vpt_predictor* p, const uint8_t* utf8, co
     uint64_t total_b = 0;
     if ((st = stage(b, utf8, byte_offsets, out_offsets, n_sentences, labels, &total_b, nullptr, nullptr)) != VPT_OK) return st;
     const size_t n_rows = size_t(total_b + n_sentences), n_tag_words = n_rows * p->n_tags, n_score_words = n_rows * p->max_tag_scores;
-    if ((st = grow(&b->d_tags, &b->tags_cap, n_tag_words + 16)) != VPT_OK) return st;
-    if (tag_scores_out && (st = grow(&b->d_tag_scores, &b->tag_scores_cap, n_score_words + 16)) != VPT_OK) return st;
-    if (tag_models_out && (st = grow(&b->d_tag_models, &b->tag_models_cap, n_rows + 16)) != VPT_OK) return st;
+    if ((st = b->d_tags.grow(n_tag_words + 16)) != VPT_OK) return st;
+    if (tag_scores_out && (st = b->d_tag_scores.grow(n_score_words + 16)) != VPT_OK) return st;
+    if (tag_models_out && (st = b->d_tag_models.grow(n_rows + 16)) != VPT_OK) return st;
     // rows that end no token with a tag model are not written by the kernel: they read 0 (the reference holds None there)
     if (tag_scores_out && n_score_words) VPT_HIP(hipMemsetAsync(b->d_tag_scores, 0, n_score_words * sizeof(int32_t), b->own_stream));
     b->flags = flags;
     b->tagger = t;
     st = vpt_fill_tags_scores_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, b->d_labels, b->d_tags,
-                                           tag_scores_out ? b->d_tag_scores : nullptr, tag_models_out ? b->d_tag_models : nullptr, b->own_stream);
+                                           tag_scores_out ? b->d_tag_scores.p : nullptr, tag_models_out ? b->d_tag_models.p : nullptr, b->own_stream);
     if (st != VPT_OK) return st;
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
     const size_t row0 = size_t(out_offsets[0]);   // (the caller's rows start at out_offsets[0] + 0)
@@ -298,8 +300,8 @@ static vpt_status emit_host(const vpt_predictor* p, const uint8_t* utf8, const u
     vpt_batch* b = w.b;
     uint64_t total_b = 0;
     if ((st = stage(b, utf8, byte_offsets, out_offsets, n_sentences, labels, &total_b, nullptr, nullptr)) != VPT_OK) return st;
-    if ((st = grow(&b->d_tok, &b->tok_cap, size_t(text_capacity) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 1)) != VPT_OK) return st;
+    if ((st = b->d_tok.grow(size_t(text_capacity) + 16)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(n_sentences + 1)) != VPT_OK) return st;
     const bool with_tags = tagged && p->n_tags > 0;
     if (with_tags) {   // Sentence::fill_tags, then the writer, as the CLI does (predict/src/main.rs:156-176); no dense array: the records are the tags
         b->flags = flags;
@@ -311,10 +313,7 @@ static vpt_status emit_host(const vpt_predictor* p, const uint8_t* utf8, const u
                      text_capacity, b->d_toff, b->own_stream);
     if (st != VPT_OK) return st;
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    VPT_HIP(hipMemcpy(text_offsets_out, b->d_toff, 8 * (n_sentences + 1), hipMemcpyDeviceToHost));
-    const uint64_t total = text_offsets_out[n_sentences];
-    if (total) VPT_HIP(hipMemcpy(text_out, b->d_tok, size_t(total), hipMemcpyDeviceToHost));
-    return VPT_OK;
+    return download_sized<uint8_t>(text_offsets_out, b->d_toff, n_sentences, text_out, b->d_tok, text_capacity, kTextTooSmall);
 }
 
 vpt_status vpt_write_tokenized_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences,
@@ -358,16 +357,12 @@ namespace {
 // ends_out (vpt_token_stream_batch): the same pipeline with the span kernel in the writer's place -- the chunks write ONE array of token end-points
 // (four bytes each; text_capacity counts them) and the documents' ranges in it instead of text and text offsets.
 vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t* text, const uint64_t* byte_offsets, size_t n_sentences, unsigned flags,
-                          uint64_t max_bytes, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out, uint32_t* ends_out = nullptr) {
-    (void)max_bytes;
-    const uint64_t t0 = byte_offsets[0];
-    const size_t nbytes = size_t(byte_offsets[n_sentences] - t0);
+                          uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out, uint32_t* ends_out = nullptr) {
+    const size_t nbytes = size_t(byte_offsets[n_sentences] - byte_offsets[0]);
     // 1/6 of the batch, at least 2 MB (a scoring launch costs 50 us + 1.3 us per 1000 lines) and at most 8 (1 M lines: 5.8 ms in 8 MB chunks, 6.4 in 32)
     const uint64_t chunk_bytes = p->knobs.tokenize_chunk_bytes_set ? std::max<uint64_t>(p->knobs.tokenize_chunk_bytes, 1)
                                                                    : std::min<uint64_t>(uint64_t(8) << 20, std::max<uint64_t>(uint64_t(2) << 20, (uint64_t(nbytes) + 5) / 6));
-    const size_t n_cuts = size_t((uint64_t(nbytes) + chunk_bytes - 1) / chunk_bytes);   // chunks, unless sentences longer than one swallow some
-    const size_t max_chunks = std::min<size_t>(n_sentences, n_cuts) + 1;
-    auto cut_end = [&](size_t k) -> uint64_t { return std::min<uint64_t>(uint64_t(nbytes), (k + 1) * chunk_bytes); };   // where chunk k of n_cuts should end
+    const size_t max_chunks = vptcut::stream_max_chunks(n_sentences, nbytes, chunk_bytes);
     vpt_status st;
     Workspace second;   // the scratch (tiles, partial sums, the writer's words, labels, status) of every other chunk
     if ((st = acquire(p, &second)) != VPT_OK) return st;
@@ -376,42 +371,22 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
     // behind it is destroyed in front of it), or another host thread could take and clear what a chunk in flight still reads
     struct DrainFirst {
         vpt_batch* b;
-        ~DrainFirst() {
-            (void)hipStreamSynchronize(b->own_stream);
-            if (b->s_tok_in) (void)hipStreamSynchronize(b->s_tok_in);
-            if (b->s_tok_out) (void)hipStreamSynchronize(b->s_tok_out);
-        }
+        ~DrainFirst() { drain(b); }
     } drain_first{b};
     vpt_batch* const ws[2] = {b, second.b};
     if (!b->s_tok_in) VPT_HIP(hipStreamCreateWithFlags(&b->s_tok_in, hipStreamNonBlocking));
     if (!b->s_tok_out) VPT_HIP(hipStreamCreateWithFlags(&b->s_tok_out, hipStreamNonBlocking));
-    while (b->chunk_ev.size() < 3 * max_chunks) {   // per chunk: copied in, tiles found, scored
-        hipEvent_t e;
-        VPT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        b->chunk_ev.push_back(e);
-    }
-    if ((st = grow(&b->d_text, &b->text_cap, nbytes + 32)) != VPT_OK) return st;
-    {
-        size_t cap = b->off_cap;
-        if ((st = grow(&b->d_boff, &cap, n_sentences + max_chunks + 1)) != VPT_OK) return st;
-        size_t cap2 = b->off_cap;
-        if ((st = grow(&b->d_ooff, &cap2, n_sentences + max_chunks + 1)) != VPT_OK) return st;
-        b->off_cap = std::min(cap, cap2);
-    }
-    if ((st = grow(&b->d_chain, &b->chain_cap, max_chunks + 2)) != VPT_OK) return st;
+    if ((st = chunk_events(b, 3 * max_chunks)) != VPT_OK) return st;   // per chunk: copied in, tiles found, scored
+    if ((st = b->d_text.grow(nbytes + 32)) != VPT_OK) return st;
+    if ((st = grow_pair(b->d_boff, b->d_ooff, vptcut::offset_slots(n_sentences, max_chunks))) != VPT_OK) return st;
+    if ((st = b->d_chain.grow(max_chunks + 2)) != VPT_OK) return st;
     const uint64_t out_cap = ends_out ? uint64_t(nbytes) : uint64_t(nbytes) * 3 + 16;   // (an end-point per char at most, a char per byte at most)
-    if (ends_out) { if ((st = grow(&b->d_tends, &b->tends_cap, size_t(out_cap) + 16)) != VPT_OK) return st; }
-    else if ((st = grow(&b->d_tok, &b->tok_cap, size_t(out_cap) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + 2)) != VPT_OK) return st;
+    if (ends_out) { if ((st = b->d_tends.grow(size_t(out_cap) + 16)) != VPT_OK) return st; }
+    else if ((st = b->d_tok.grow(size_t(out_cap) + 16)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(n_sentences + 2)) != VPT_OK) return st;
     uint8_t* const d_out = b->d_tok;
     uint64_t* const d_off_out = b->d_toff;
-    const size_t need_off = n_sentences + 1 + max_chunks + 1 + 2;   // pinned: the offsets relative to the batch's text, where every chunk's text ends, the workspaces' status words
-    if (need_off > b->h_off_cap) {
-        if (b->h_off) (void)hipHostFree(b->h_off);
-        b->h_off = nullptr; b->h_off_cap = 0;
-        VPT_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_off), (need_off + need_off / 2) * sizeof(uint64_t), hipHostMallocDefault));
-        b->h_off_cap = need_off + need_off / 2;
-    }
+    if ((st = pinned_words(b, vptcut::stream_pinned_words(n_sentences, max_chunks))) != VPT_OK) return st;
     uint64_t* const h_boff = b->h_off;
     uint64_t* const h_end = b->h_off + n_sentences + 1;
     uint64_t* const h_ctrl = h_end + max_chunks + 1;
@@ -422,30 +397,18 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         w->max_chars = 0;   // unknown on the host (no round trip for it): the scoring kernel takes the geometry that fits any sentence
     }
     VPT_HIP(hipMemsetAsync(b->d_chain, 0, sizeof(uint64_t), s));
-    struct Chunk { size_t a, n; uint64_t tb, nby, mb; };
+    using Chunk = vptcut::TokenizeChunk;
     std::vector<Chunk> chunks;
     chunks.reserve(max_chunks);
-    size_t cut_at = 0, cut_k = 0;
-    h_boff[0] = 0;
+    vptcut::StreamCutter cutter(byte_offsets, n_sentences, chunk_bytes, h_boff);
     auto copy_in_next = [&]() -> vpt_status {   // the next chunk of lines: offsets rebased into pinned memory, text and offsets on their way
-        if (cut_at >= n_sentences) return VPT_OK;
-        const size_t a = cut_at, k = chunks.size();
-        uint64_t want = cut_end(cut_k++);
-        while (want <= h_boff[a] && cut_k < n_cuts) want = cut_end(cut_k++);   // (a sentence longer than a chunk took these)
-        size_t i = a;
-        uint64_t mb = 0;
-        do {
-            h_boff[i + 1] = byte_offsets[i + 1] - t0;
-            mb = std::max<uint64_t>(mb, h_boff[i + 1] - h_boff[i]);
-            ++i;
-        } while (i < n_sentences && (h_boff[i] < want || chunks.size() + 1 >= max_chunks));
-        const size_t n = i - a;
-        const uint64_t tb = h_boff[a], nby = h_boff[i] - tb;
-        VPT_HIP(hipMemcpyAsync(b->d_text + tb, text + tb, size_t(nby), hipMemcpyHostToDevice, s_in));
-        VPT_HIP(hipMemcpyAsync(b->d_boff + a + k, h_boff + a, 8 * (n + 1), hipMemcpyHostToDevice, s_in));   // n + 1 entries per chunk; offsets into the WHOLE text: no rebasing
+        if (cutter.done()) return VPT_OK;
+        const size_t k = chunks.size();
+        const Chunk c = cutter.next();
+        VPT_HIP(hipMemcpyAsync(b->d_text + c.tb, text + c.tb, size_t(c.nby), hipMemcpyHostToDevice, s_in));
+        VPT_HIP(hipMemcpyAsync(b->d_boff + c.a + k, h_boff + c.a, 8 * (c.n + 1), hipMemcpyHostToDevice, s_in));   // n + 1 entries per chunk; offsets into the WHOLE text: no rebasing
         VPT_HIP(hipEventRecord(b->chunk_ev[3 * k], s_in));
-        chunks.push_back({a, n, tb, nby, mb});
-        cut_at = i;
+        chunks.push_back(c);
         return VPT_OK;
     };
     uint64_t at = 0;
@@ -471,7 +434,7 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         if (k >= 2) VPT_HIP(hipStreamWaitEvent(s_prep, b->chunk_ev[3 * (k - 2) + 2], 0));   // this workspace's scratch: the chunk before the last is through with it
         if ((st = count_boundaries_impl(p, w, b->d_text, d_boff_k, c.n, d_ooff_k, s_prep, c.nby)) != VPT_OK) return st;
         h_end[k] = ~uint64_t(0);
-        if ((st = grow(&w->d_tlab, &w->tlab_cap, size_t(c.nby) + 16)) != VPT_OK) return st;
+        if ((st = w->d_tlab.grow(size_t(c.nby) + 16)) != VPT_OK) return st;
         w->split_stream = s; w->split_event = b->chunk_ev[3 * k + 1];   // the scoring launch: on the scoring stream, behind the tile search
         st = predict_device_impl(p, w, b->d_text, d_boff_k, d_ooff_k, c.n, c.nby - c.n /* boundaries of the chunk, at most */, c.mb, nullptr, w->d_tlab, s_prep);
         w->split_stream = nullptr; w->split_event = nullptr;
@@ -502,7 +465,7 @@ vpt_status tokenize_chunked(const vpt_predictor* p, vpt_batch* b, const uint8_t*
         for (vpt_batch* w : ws) VPT_HIP(hipMemset(w->d_ctrl, 0, sizeof(uint32_t)));
         return status_from_bits(bits);
     }
-    if (too_small) return fail(VPT_INVALID_ARGUMENT, ends_out ? "InvalidArgumentError: capacity: smaller than the number of tokens" : "InvalidArgumentError: text_capacity: smaller than the tokenized text");
+    if (too_small) return fail(VPT_INVALID_ARGUMENT, ends_out ? kTokensTooSmall : kTextTooSmall);
     if (out_of_range || h_end[chunks.size() - 1] > out_cap) return fail(VPT_RUNTIME_ERROR, "vpt_tokenize_batch: the output size is out of range");
     return VPT_OK;
 }
@@ -523,12 +486,8 @@ static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, con
     if (!utf8 || !byte_offsets || (text_capacity && !text_out)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     const uint64_t t0 = byte_offsets[0], t1 = byte_offsets[n_sentences];
     if (t1 < t0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
-    uint64_t max_bytes = 0;
-    for (size_t i = 0; i < n_sentences; ++i) {
-        if (byte_offsets[i + 1] <= byte_offsets[i])
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: must contain at least one character");
-        max_bytes = std::max<uint64_t>(max_bytes, byte_offsets[i + 1] - byte_offsets[i]);
-    }
+    for (size_t i = 0; i < n_sentences; ++i)
+        if (byte_offsets[i + 1] <= byte_offsets[i]) return cut_fail(vptcut::CutError::kEmptySentence);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     vpt_status st = acquire(p, &w);
@@ -536,7 +495,7 @@ static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, con
     vpt_batch* b = w.b;
     const size_t nbytes = size_t(t1 - t0);
     const bool with_tags = tagged && p->n_tags > 0;
-    if (!with_tags) return tokenize_chunked(p, b, utf8 + t0, byte_offsets, n_sentences, flags, max_bytes, text_out, text_capacity, text_offsets_out);
+    if (!with_tags) return tokenize_chunked(p, b, utf8 + t0, byte_offsets, n_sentences, flags, text_out, text_capacity, text_offsets_out);
     // NOTHING on the way needs a number from the device: the device buffers hold the whole batch and a slice of an output starts
     // where an upper bound puts it (a char is at least one byte: boundaries and chars in front of a slice <= text bytes in front
     // of it; tokenized text <= 3 bytes per text byte + the longest tag suffix per char), so copy in, char count, scoring, tagging
@@ -550,51 +509,29 @@ static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, con
     constexpr int kMaxLanes = 4;
     const uint64_t chunk_bytes = p->knobs.tokenize_chunk_bytes;
     const uint64_t per_byte = 3 + (with_tags ? uint64_t(p->max_tag_suffix) + (t ? t->max_suffix : 0u) : 0);   // tokenized bytes per text byte, at most
-    const size_t max_chunks = std::min<size_t>(n_sentences, size_t(nbytes / chunk_bytes) + 2);
-    const int n_lanes = int(std::min<size_t>(kMaxLanes, max_chunks));
-    Workspace extra[kMaxLanes - 1];
-    vpt_batch* lane[kMaxLanes] = {b};
-    for (int l = 1; l < n_lanes; ++l) {
-        if ((st = acquire(p, &extra[l - 1])) != VPT_OK) return st;
-        lane[l] = extra[l - 1].b;
-    }
+    const size_t max_chunks = vptcut::tagged_max_chunks(n_sentences, nbytes, chunk_bytes);
+    Lanes lanes;
+    if ((st = lanes.init(p, b, int(std::min<size_t>(kMaxLanes, max_chunks)))) != VPT_OK) return st;
     if (!b->s_out) VPT_HIP(hipStreamCreateWithFlags(&b->s_out, hipStreamNonBlocking));
-    while (b->chunk_ev.size() < max_chunks) {
-        hipEvent_t e;
-        VPT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        b->chunk_ev.push_back(e);
-    }
+    if ((st = chunk_events(b, max_chunks)) != VPT_OK) return st;
     // whole-batch device buffers (lane 0's workspace owns them); the other lanes only lend their scratch
-    if ((st = grow(&b->d_text, &b->text_cap, nbytes + 32)) != VPT_OK) return st;
-    {
-        size_t cap = b->off_cap;
-        if ((st = grow(&b->d_boff, &cap, n_sentences + max_chunks + 1)) != VPT_OK) return st;
-        size_t cap2 = b->off_cap;
-        if ((st = grow(&b->d_ooff, &cap2, n_sentences + max_chunks + 1)) != VPT_OK) return st;
-        b->off_cap = std::min(cap, cap2);
-    }
-    if ((st = grow(&b->d_tlab, &b->tlab_cap, nbytes + 1)) != VPT_OK) return st;
-    if ((st = grow(&b->d_tok, &b->tok_cap, size_t(nbytes * per_byte) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_toff, &b->toff_cap, n_sentences + max_chunks + 1)) != VPT_OK) return st;
-    const size_t need_off = n_sentences + 1 + max_chunks;   // pinned: the offsets relative to the batch's text, then one total per chunk
-    if (need_off > b->h_off_cap) {
-        if (b->h_off) (void)hipHostFree(b->h_off);
-        b->h_off = nullptr; b->h_off_cap = 0;
-        VPT_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_off), (need_off + need_off / 2) * sizeof(uint64_t), hipHostMallocDefault));
-        b->h_off_cap = need_off + need_off / 2;
-    }
+    if ((st = b->d_text.grow(nbytes + 32)) != VPT_OK) return st;
+    if ((st = grow_pair(b->d_boff, b->d_ooff, vptcut::offset_slots(n_sentences, max_chunks))) != VPT_OK) return st;
+    if ((st = b->d_tlab.grow(nbytes + 1)) != VPT_OK) return st;
+    if ((st = b->d_tok.grow(size_t(nbytes * per_byte) + 16)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(vptcut::offset_slots(n_sentences, max_chunks))) != VPT_OK) return st;
+    if ((st = pinned_words(b, vptcut::tagged_pinned_words(n_sentences, max_chunks))) != VPT_OK) return st;
     uint64_t* const h_boff = b->h_off;
     uint64_t* const h_total = b->h_off + n_sentences + 1;
     for (size_t i = 0; i <= n_sentences; ++i) h_boff[i] = byte_offsets[i] - t0;
-    struct Chunk { size_t a, n; uint64_t tb; };   // first sentence, sentences, first text byte (relative to the batch's)
+    using Chunk = vptcut::TokenizeChunk;
     std::vector<Chunk> chunks;
     for (size_t i = 0; i < n_sentences;) {
-        const size_t a = i;
-        uint64_t mb = 0;
-        while (i < n_sentences && h_boff[i] - h_boff[a] < chunk_bytes) { mb = std::max<uint64_t>(mb, h_boff[i + 1] - h_boff[i]); ++i; }
-        const size_t k = chunks.size(), n = i - a;
-        const uint64_t tb = h_boff[a], nby = h_boff[i] - tb;
-        vpt_batch* bb = lane[k % size_t(n_lanes)];
+        const Chunk c = vptcut::tagged_chunk(h_boff, n_sentences, i, chunk_bytes);
+        i += c.n;
+        const size_t a = c.a, n = c.n, k = chunks.size();
+        const uint64_t tb = c.tb, nby = c.nby, mb = c.mb;
+        vpt_batch* bb = lanes[k];
         hipStream_t s = bb->own_stream;
         bb->flags = flags;
         bb->max_chars = 0;   // unknown on the host (no round trip for it): the scoring kernel takes the geometry that fits any sentence
@@ -618,7 +555,7 @@ static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, con
                          b->d_toff + a + k, s, h_total + k);
         if (st != VPT_OK) return st;
         VPT_HIP(hipEventRecord(b->chunk_ev[k], s));
-        chunks.push_back({a, n, tb});
+        chunks.push_back(c);
     }
     // ---- collect: chunk by chunk, in order
     uint64_t at = 0;   // tokenized bytes in front of the chunk
@@ -630,26 +567,14 @@ static vpt_status tokenize_host(const vpt_predictor* p, const uint8_t* utf8, con
         VPT_HIP(hipEventSynchronize(b->chunk_ev[k]));
         const uint64_t total = h_total[k];
         if (total > (h_boff[c.a + c.n] - c.tb) * per_byte) { incomplete = true; break; }   // the device found the inputs inconsistent and says so below
-        if (total > text_capacity || at > text_capacity - total) { st = fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text"); break; }
+        if (total > text_capacity || at > text_capacity - total) { st = fail(VPT_INVALID_ARGUMENT, kTextTooSmall); break; }
         base[k] = at;
         if (total) VPT_HIP(hipMemcpyAsync(text_out + at, b->d_tok + c.tb * per_byte, size_t(total), hipMemcpyDeviceToHost, b->s_out));
         VPT_HIP(hipMemcpyAsync(text_offsets_out + c.a + 1, b->d_toff + c.a + k + 1, 8 * c.n, hipMemcpyDeviceToHost, b->s_out));
         at += total;
     }
     VPT_HIP(hipStreamSynchronize(b->s_out));
-    // the device's verdict over every chunk (a lane's status word accumulates), fetched together
-    uint32_t ctrl[kMaxLanes][2] = {};
-    for (int l = 0; l < n_lanes; ++l)
-        if (lane[l]->pending) VPT_HIP(hipMemcpyAsync(ctrl[l], lane[l]->d_ctrl, sizeof(ctrl[l]), hipMemcpyDeviceToHost, lane[l]->last_stream));
-    for (int l = 0; l < n_lanes; ++l) {
-        if (!lane[l]->pending) continue;
-        VPT_HIP(hipStreamSynchronize(lane[l]->last_stream));
-        lane[l]->pending = false;
-        if (ctrl[l][0]) {
-            VPT_HIP(hipMemset(lane[l]->d_ctrl, 0, sizeof(uint32_t)));
-            if (st == VPT_OK) st = status_from_bits(ctrl[l][0]);
-        }
-    }
+    st = lanes.verdict(st);
     if (st != VPT_OK) return st;
     if (incomplete) return fail(VPT_RUNTIME_ERROR, "vpt_tokenize_batch: a chunk's output size is out of range");
     // the offsets came back relative to their chunk's text
@@ -703,17 +628,13 @@ vpt_status vpt_predict_listing_batch(const vpt_predictor* p, const uint8_t* utf8
         b->max_chars = max_chars;
         if ((st = vpt_predict_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, max_bytes, b->d_scores, b->d_labels, s)) != VPT_OK) return st;
     }
-    if ((st = grow(&b->d_lst_out, &b->lst_out_cap, size_t(capacity) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_lst_off, &b->lst_off_cap, n_sentences + 1)) != VPT_OK) return st;
+    if ((st = b->d_lst_out.grow(size_t(capacity) + 16)) != VPT_OK) return st;
+    if ((st = b->d_lst_off.grow(n_sentences + 1)) != VPT_OK) return st;
     st = vpt_predict_listing_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, byte_offsets[n_sentences] - byte_offsets[0], b->d_scores,
                                           b->d_labels, listing, b->d_lst_out, capacity, b->d_lst_off, s);
     if (st != VPT_OK) return st;
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    VPT_HIP(hipMemcpy(listing_offsets_out, b->d_lst_off, 8 * (n_sentences + 1), hipMemcpyDeviceToHost));
-    const uint64_t total = listing_offsets_out[n_sentences];
-    if (total > capacity) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the listing");
-    if (total) VPT_HIP(hipMemcpy(out, b->d_lst_out, size_t(total), hipMemcpyDeviceToHost));
-    return VPT_OK;
+    return download_sized<uint8_t>(listing_offsets_out, b->d_lst_off, n_sentences, out, b->d_lst_out, capacity, "InvalidArgumentError: text_capacity: smaller than the listing");
 }
 
 // vaporetto_tantivy/src/lib.rs:183-192 for a batch in host buffers, on the caller's labels
@@ -739,16 +660,12 @@ vpt_status vpt_token_spans_batch(const vpt_predictor* p, const uint8_t* utf8, co
     // the device buffer holds every end-point there can be (one per char), so a capacity that is too small is found here and nothing is
     // copied past it
     const uint64_t d_cap = total_b + n_documents;
-    if ((st = grow(&b->d_tends, &b->tends_cap, size_t(d_cap) + 16)) != VPT_OK) return st;
-    if ((st = grow(&b->d_toff, &b->toff_cap, n_documents + 1)) != VPT_OK) return st;
+    if ((st = b->d_tends.grow(size_t(d_cap) + 16)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(n_documents + 1)) != VPT_OK) return st;
     st = spans_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_documents, total_b, b->d_labels, b->d_toff, b->d_tends, d_cap, b->own_stream, nullptr, nullptr, nullptr);
     if (st != VPT_OK) return st;
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    VPT_HIP(hipMemcpy(token_offsets_out, b->d_toff, 8 * (n_documents + 1), hipMemcpyDeviceToHost));
-    const uint64_t total = token_offsets_out[n_documents];
-    if (total > capacity) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: smaller than the number of tokens");
-    if (total) VPT_HIP(hipMemcpy(token_ends_out, b->d_tends, 4 * size_t(total), hipMemcpyDeviceToHost));
-    return VPT_OK;
+    return download_sized<uint32_t>(token_offsets_out, b->d_toff, n_documents, token_ends_out, b->d_tends, capacity, kTokensTooSmall);
 }
 
 // ConcatGraphemeClustersFilter on the caller's labels, host buffers
@@ -800,7 +717,7 @@ vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, c
     if (max_bytes > 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: a document must be shorter than 2^32 bytes");
     const size_t n = docs.size() - 1;
     if (n == 0) { std::fill(token_offsets_out, token_offsets_out + n_documents + 1, uint64_t(0)); return VPT_OK; }
-    if (capacity < n) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: smaller than the number of tokens");   // (a token per document at least)
+    if (capacity < n) return fail(VPT_INVALID_ARGUMENT, kTokensTooSmall);   // (a token per document at least)
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     vpt_status st = acquire(p, &w);
@@ -809,7 +726,7 @@ vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, c
     std::vector<uint64_t> packed;   // (only with empty documents: the ranges of the others)
     uint64_t* const offs = n == n_documents ? token_offsets_out : (packed.resize(n + 1), packed.data());
     offs[0] = 0;
-    st = tokenize_chunked(p, w.b, utf8 + docs[0], docs.data(), n, flags, max_bytes, nullptr, capacity, offs, token_ends_out);
+    st = tokenize_chunked(p, w.b, utf8 + docs[0], docs.data(), n, flags, nullptr, capacity, offs, token_ends_out);
     if (st != VPT_OK) return st;
     if (n != n_documents) {
         size_t k = 0;
@@ -900,7 +817,7 @@ vpt_status vpt_char_types_batch(const vpt_predictor* p, const uint8_t* utf8, con
     uint64_t total_b = 0;
     if ((st = stage(b, utf8, byte_offsets, out_offsets, n_sentences, nullptr, &total_b, nullptr, nullptr)) != VPT_OK) return st;
     const size_t total_c = size_t(total_b) + n_sentences;
-    if ((st = grow(&b->d_types, &b->types_cap, total_c + 16)) != VPT_OK) return st;
+    if ((st = b->d_types.grow(total_c + 16)) != VPT_OK) return st;
     b->flags = flags;
     if ((st = vpt_char_types_batch_device(p, b, b->d_text, b->d_boff, b->d_ooff, n_sentences, total_b, b->d_types, b->own_stream)) != VPT_OK) return st;
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
@@ -910,7 +827,7 @@ vpt_status vpt_char_types_batch(const vpt_predictor* p, const uint8_t* utf8, con
 
 vpt_status vpt_predict_one(const vpt_predictor* p, const uint8_t* utf8, size_t len, int32_t* scores, uint8_t* labels, size_t* n_boundaries) {
     uint64_t boff[2] = {0, uint64_t(len)}, ooff[2] = {0, 0};
-    if (len == 0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: must contain at least one character");
+    if (len == 0) return cut_fail(vptcut::CutError::kEmptySentence);
     vpt_status st = vpt_count_boundaries(utf8, boff, 1, ooff);
     if (st != VPT_OK) return st;
     if (n_boundaries) *n_boundaries = size_t(ooff[1]);

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "host_chunks.hpp"
 #include "kernels.hpp"
 #include "model.hpp"
 #include "pattern_tagger.hpp"
@@ -46,7 +47,7 @@ struct PredictorKnobs {
     bool force_window_table = false;    // VPT_FORCE_WINDOW_TABLE: the 8^(2W) type table instead of the type rows
     int pipe_lanes = -1;                // VPT_PIPE_LANES (-1: the size rule)
     uint64_t chunk_chars = 0;           // VPT_CHUNK_CHARS (0: the size rule)
-    uint64_t tokenize_chunk_bytes = uint64_t(256) << 20;   // VPT_TOKENIZE_CHUNK_BYTES (the tagged pipeline's default; the fused one: an eighth of the batch, at least 4 MB)
+    uint64_t tokenize_chunk_bytes = uint64_t(256) << 20;   // VPT_TOKENIZE_CHUNK_BYTES (the tagged pipeline's default; the untagged one: a sixth of the batch, 2 .. 8 MB)
     bool tokenize_chunk_bytes_set = false;
     uint64_t eval_chunk_bytes = uint64_t(64) << 20;        // VPT_EVAL_CHUNK_BYTES: vpt_evaluate_batch's chunks of tokenized text (~22 device bytes per byte)
 };
@@ -246,20 +247,53 @@ struct vpt_pattern_tagger {
     std::vector<uint8_t> raw_bytes;
 };
 
+// A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    operator T*() const { return p; }
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+    vpt_status alloc(size_t bytes) {   // exactly `bytes`; the contents are gone
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+        if (e != hipSuccess) { vpt_g_last_error = std::string("HIP error: ") + hipGetErrorString(e) + " at hipMalloc"; return VPT_RUNTIME_ERROR; }
+        cap = bytes / sizeof(T);
+        return VPT_OK;
+    }
+    vpt_status grow(size_t need) {     // room for `need` elements: by half as much again at least; the contents are gone
+        if (need <= cap && p) return VPT_OK;
+        const size_t ncap = std::max<size_t>(std::max<size_t>(need, cap + cap / 2), 64);
+        const vpt_status st = alloc(ncap * sizeof(T) + 64);
+        if (st == VPT_OK) cap = ncap;
+        return st;
+    }
+};
+// Two buffers indexed alike (grown by the same needs, they have the same capacity); each knows its own, so a failure between the two leaves
+// nothing behind that a later call could overrun.
+template <typename A, typename B>
+vpt_status grow_pair(DevBuf<A>& a, DevBuf<B>& b, size_t need) {
+    const vpt_status st = a.grow(need);
+    return st != VPT_OK ? st : b.grow(need);
+}
+
 struct vpt_batch {
     const vpt_predictor* pred = nullptr;
     int device = 0;
     BatchKnobs knobs;                  // read once, when the workspace was made
     // per-call device tables
-    uint32_t* d_tile_first = nullptr; size_t tile_cap = 0;
-    vpt::TileDesc* d_tiles = nullptr; size_t tiles_cap = 0;          // the specialised kernel's tiles
-    uint32_t* d_cut_local = nullptr; size_t cut_local_cap = 0;       // ... and, for cut tiles, the lead-byte index of the text
-    uint64_t* d_cut_super = nullptr; size_t cut_super_cap = 0;
-    uint32_t* d_slow_list = nullptr;
-    uint32_t* d_ctrl = nullptr;        // [0] status bits, [1] slow tile count
-    uint64_t* d_prof = nullptr;        // 8 per-phase cycle counters + 8 node-read counters (only with VPT_PROFILE_PHASES set)
-    unsigned char* d_scratch = nullptr; size_t scratch_bytes = 0;
-    uint32_t* d_cps = nullptr; size_t cps_cap = 0;   // decoded scalar values for vpt_fill_tags_batch_device
+    DevBuf<uint32_t> d_tile_first, d_slow_list;   // (one capacity: grow_pair)
+    DevBuf<vpt::TileDesc> d_tiles;     // the specialised kernel's tiles
+    DevBuf<uint32_t> d_cut_local;      // ... and, for cut tiles, the lead-byte index of the text
+    DevBuf<uint64_t> d_cut_super;
+    DevBuf<uint32_t> d_ctrl;           // [0] status bits, [1] slow tile count
+    DevBuf<uint64_t> d_prof;           // 8 per-phase cycle counters + 8 node-read counters (only with VPT_PROFILE_PHASES set)
+    DevBuf<unsigned char> d_scratch;
+    DevBuf<uint32_t> d_cps;            // decoded scalar values for vpt_fill_tags_batch_device
     // the batch whose chars d_cps holds because the scoring kernel of a predict call on this workspace wrote them (all 0: none)
     const void* cps_text = nullptr; const void* cps_ooff = nullptr; size_t cps_sentences = 0; uint64_t cps_boundaries = 0; unsigned cps_flags = 0;
     uint64_t max_chars = 0;            // caller's bound on chars per sentence (0 = unknown)
@@ -275,66 +309,64 @@ struct vpt_batch {
     hipStream_t last_stream = nullptr; bool pending = false;
     // staging for the host-buffer entry points
     hipStream_t own_stream = nullptr;
-    uint8_t* d_text = nullptr; size_t text_cap = 0;
-    uint64_t *d_boff = nullptr, *d_ooff = nullptr; size_t off_cap = 0;
-    int32_t* d_scores = nullptr; uint8_t* d_labels = nullptr; size_t out_cap = 0;
-    int32_t* d_tags = nullptr; size_t tags_cap = 0;                 // vpt_fill_tags_batch
-    int32_t* d_tag_scores = nullptr; size_t tag_scores_cap = 0;     // vpt_fill_tags_scores_batch
-    int32_t* d_tag_models = nullptr; size_t tag_models_cap = 0;
-    uint8_t* d_tok = nullptr; size_t tok_cap = 0;                   // vpt_write_tokenized_batch
-    uint8_t* d_tlab = nullptr; size_t tlab_cap = 0;                 // vpt_tokenize_batch: the labels of the whole batch (no scores are kept)
-    uint64_t* d_toff = nullptr; size_t toff_cap = 0;
-    uint32_t* d_tends = nullptr; size_t tends_cap = 0;             // vpt_token_spans_batch / vpt_token_stream_batch: the tokens' end-points
-    uint64_t* d_chain = nullptr; size_t chain_cap = 0;             // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
+    DevBuf<uint8_t> d_text;
+    DevBuf<uint64_t> d_boff, d_ooff;                                // (one capacity: grow_pair)
+    DevBuf<int32_t> d_scores; DevBuf<uint8_t> d_labels;             // (one capacity: grow_pair)
+    DevBuf<int32_t> d_tags;                                         // vpt_fill_tags_batch
+    DevBuf<int32_t> d_tag_scores, d_tag_models;                     // vpt_fill_tags_scores_batch
+    DevBuf<uint8_t> d_tok;                                          // vpt_write_tokenized_batch
+    DevBuf<uint8_t> d_tlab;                                         // vpt_tokenize_batch: the labels of the whole batch (no scores are kept)
+    DevBuf<uint64_t> d_toff;
+    DevBuf<uint32_t> d_tends;                                       // vpt_token_spans_batch / vpt_token_stream_batch: the tokens' end-points
+    DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
-    uint4* d_tag_records = nullptr; size_t tag_records_cap = 0;
-    int32_t* d_rec_tags = nullptr; size_t rec_tags_cap = 0;
-    uint64_t* d_tag_ctl = nullptr; size_t tag_ctl_cap = 0;          // the scan's state, run_pref [n_runs + 1]: zeroed as one range per call
+    DevBuf<uint4> d_tag_records;
+    DevBuf<int32_t> d_rec_tags;
+    DevBuf<uint64_t> d_tag_ctl;                                     // the scan's state, run_pref [n_runs + 1]: zeroed as one range per call
     uint64_t* d_run_pref = nullptr;                                 // (inside d_tag_ctl, or d_pm_ctl: the run_pref of the records the readers take)
     uint64_t* d_fill_run_pref = nullptr;                            // (inside d_tag_ctl: fill_tags' own, what vpt_evaluate_* reads)
-    uint2* d_rec_str = nullptr; size_t rec_str_cap = 0;
-    uint4* d_tag_cands = nullptr; size_t tag_cands_cap = 0;
-    uint32_t* d_tag_summary = nullptr;
+    DevBuf<uint2> d_rec_str;
+    DevBuf<uint4> d_tag_cands;
+    DevBuf<uint32_t> d_tag_summary;
     uint64_t tag_chars = 0, tag_sentences = 0, tag_runs = 0;        // the batch those records belong to (0 chars: none)
     uint32_t tag_run_sent = 0;
     // vpt_batch_set_pattern_tagger: the rules applied behind every fill_tags on this workspace (nullptr: none), and what they are merged into.
     // rv_*: the records the readers take (the writer, expand_tags; not evaluate: it keeps to fill_tags' own) -- fill_tags' own, or the merged ones; d_run_pref goes with them.
     const vpt_pattern_tagger* tagger = nullptr;
-    uint4* d_pm_records = nullptr; size_t pm_records_cap = 0;
-    int32_t* d_pm_rec_tags = nullptr; size_t pm_rec_tags_cap = 0;
-    uint2* d_pm_rec_str = nullptr; size_t pm_rec_str_cap = 0;
-    uint2* d_pm_hits = nullptr; size_t pm_hits_cap = 0;
-    uint64_t* d_pm_ctl = nullptr; size_t pm_ctl_cap = 0;
+    DevBuf<uint4> d_pm_records;
+    DevBuf<int32_t> d_pm_rec_tags;
+    DevBuf<uint2> d_pm_rec_str, d_pm_hits;
+    DevBuf<uint64_t> d_pm_ctl;
     const uint4* rv_records = nullptr; const int32_t* rv_rec_tags = nullptr; const uint2* rv_rec_str = nullptr; const uint8_t* rv_str_bytes = nullptr;
     std::vector<uint64_t> h_boff, h_ooff;                           // rebased offsets of the call in flight (copied asynchronously)
-    uint8_t* d_types = nullptr; size_t types_cap = 0;               // vpt_char_types_batch
-    uint64_t* d_scan_part = nullptr; size_t scan_part_cap = 0;      // per-workgroup partials of the prefix sums (kernels_emit.hip)
-    // the writer's state words (EmitFuse): two arrays of emit_state_cap words, used in turn; a call zeroes what the call before it
-    // left in the other one (emit_dirty = how many words that is)
-    uint64_t* d_emit_state = nullptr; size_t emit_state_cap = 0; size_t emit_dirty[2] = {0, 0}; int emit_flip = 0;
+    DevBuf<uint8_t> d_types;                                        // vpt_char_types_batch
+    DevBuf<uint64_t> d_scan_part;                                   // per-workgroup partials of the prefix sums (kernels_emit.hip)
+    // the writer's state words (EmitFuse): two arrays of emit_state_cap words in one allocation, used in turn; a call zeroes what the call
+    // before it left in the other one (emit_dirty = how many words that is)
+    DevBuf<uint64_t> d_emit_state; size_t emit_state_cap = 0; size_t emit_dirty[2] = {0, 0}; int emit_flip = 0;
     // the pipelined host-buffer path (predict_pipelined): two sets of device buffers, copy streams, pinned offset staging
     struct PipeSet {
-        uint8_t* text = nullptr; size_t text_cap = 0;
-        uint64_t* off = nullptr; size_t off_cap = 0;      // byte offsets, then boundary offsets: one copy
-        int32_t* scores = nullptr; uint8_t* labels = nullptr; size_t scores_cap = 0, labels_cap = 0;
+        DevBuf<uint8_t> text;
+        DevBuf<uint64_t> off;                             // byte offsets, then boundary offsets: one copy
+        DevBuf<int32_t> scores; DevBuf<uint8_t> labels;
         hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;   // chunk copied in / scored / copied out
     } pipe[2];   // (four sets, i.e. the host running further ahead, measured no faster at 2 M-char chunks and slower at 1 M: profiles/r02_c7_e2e.txt)
     // ONE copy stream per direction: a single hipMemcpyAsync stream moves 56 GB/s each way and 84 GB/s both ways at once on
     // this link; two streams per direction were slower (profiles/r02_c6_pcie_microbench.txt)
     hipStream_t s_in = nullptr, s_out = nullptr;
-    hipStream_t s_tok_in = nullptr, s_tok_out = nullptr;            // vpt_tokenize_batch's copy streams (the fused path)
-    uint64_t* h_off = nullptr; size_t h_off_cap = 0;                // pinned: the rebased offsets of every chunk of the call in flight
+    hipStream_t s_tok_in = nullptr, s_tok_out = nullptr;            // tokenize_chunked's copy streams, in and out
+    uint64_t* h_off = nullptr; size_t h_off_cap = 0;                // pinned (pinned_words): the offsets and totals of every chunk of the call in flight
     // vpt_parse_tokenized_batch_device's per-line tag counts (ParseParams::tag_off / tb_off) and vpt_evaluate_batch's buffers (one allocation)
-    uint64_t* d_parse_tmp = nullptr; size_t parse_tmp_cap = 0;
-    unsigned char* d_eval = nullptr; size_t eval_cap = 0;
-    std::vector<hipEvent_t> chunk_ev;                               // vpt_tokenize_batch: one per chunk in flight
+    DevBuf<uint64_t> d_parse_tmp;
+    DevBuf<unsigned char> d_eval;
+    std::vector<hipEvent_t> chunk_ev;                               // vpt_tokenize_batch: one per chunk in flight (chunk_events)
     // vpt_predict_listing_batch[_device]: the elements' sizes / positions and the scan's state (kernels_listing.hip); the host variant's output
-    uint64_t* d_lst_pos = nullptr; size_t lst_pos_cap = 0;
-    uint8_t* d_lst_out = nullptr; size_t lst_out_cap = 0;
-    uint64_t* d_lst_off = nullptr; size_t lst_off_cap = 0;
+    DevBuf<uint64_t> d_lst_pos;
+    DevBuf<uint8_t> d_lst_out;
+    DevBuf<uint64_t> d_lst_off;
     // VPT_FLAG_CONCAT_GRAPHEMES (kernels_graphemes.hip): the class bytes and, in one array, the tiles' summaries and first sentences
-    uint8_t* d_gcls = nullptr; size_t gcls_cap = 0;
-    uint32_t* d_gsum = nullptr; size_t gsum_cap = 0;
+    DevBuf<uint8_t> d_gcls;
+    DevBuf<uint32_t> d_gsum;
 };
 
 struct DeviceTags {   // views into the arena
@@ -386,49 +418,20 @@ vpt_status compile(const uint8_t* bytes, size_t len, int predict_tags, vpt::Comp
     return VPT_OK;
 }
 
+// (the device buffers free themselves: DevBuf)
 void batch_release(vpt_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    (void)hipFree(b->d_scan_part);
-    (void)hipFree(b->d_emit_state);
-    (void)hipFree(b->d_chain);
-    (void)hipFree(b->d_tiles); (void)hipFree(b->d_cut_local); (void)hipFree(b->d_cut_super);
-    (void)hipFree(b->d_tile_first); (void)hipFree(b->d_slow_list); (void)hipFree(b->d_ctrl); (void)hipFree(b->d_scratch);
-    (void)hipFree(b->d_prof); (void)hipFree(b->d_cps);
-    (void)hipFree(b->d_text); (void)hipFree(b->d_boff); (void)hipFree(b->d_ooff); (void)hipFree(b->d_scores); (void)hipFree(b->d_labels);
-    (void)hipFree(b->d_tags); (void)hipFree(b->d_tag_scores); (void)hipFree(b->d_tag_models); (void)hipFree(b->d_tok); (void)hipFree(b->d_tlab); (void)hipFree(b->d_toff); (void)hipFree(b->d_tends); (void)hipFree(b->d_tag_records); (void)hipFree(b->d_rec_tags); (void)hipFree(b->d_tag_ctl); (void)hipFree(b->d_rec_str); (void)hipFree(b->d_tag_cands); (void)hipFree(b->d_tag_summary);
-    (void)hipFree(b->d_types);
-    (void)hipFree(b->d_parse_tmp); (void)hipFree(b->d_eval);
-    (void)hipFree(b->d_lst_pos); (void)hipFree(b->d_lst_out); (void)hipFree(b->d_lst_off);
-    (void)hipFree(b->d_gcls); (void)hipFree(b->d_gsum);
-    (void)hipFree(b->d_pm_records); (void)hipFree(b->d_pm_rec_tags); (void)hipFree(b->d_pm_rec_str); (void)hipFree(b->d_pm_hits); (void)hipFree(b->d_pm_ctl);
-    for (auto& ps : b->pipe) {
-        (void)hipFree(ps.text); (void)hipFree(ps.off); (void)hipFree(ps.scores); (void)hipFree(ps.labels);
-        if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
-        if (ps.ev_k) (void)hipEventDestroy(ps.ev_k);
-        if (ps.ev_out) (void)hipEventDestroy(ps.ev_out);
-    }
+    for (auto& ps : b->pipe)
+        for (hipEvent_t e : {ps.ev_in, ps.ev_k, ps.ev_out})
+            if (e) (void)hipEventDestroy(e);
     if (b->h_off) (void)hipHostFree(b->h_off);
     for (hipEvent_t e : b->chunk_ev) (void)hipEventDestroy(e);
-    if (b->s_in) (void)hipStreamDestroy(b->s_in);
-    if (b->s_tok_in) (void)hipStreamDestroy(b->s_tok_in);
-    if (b->s_tok_out) (void)hipStreamDestroy(b->s_tok_out);
-    if (b->s_out) (void)hipStreamDestroy(b->s_out);
+    for (hipStream_t s : {b->s_in, b->s_tok_in, b->s_tok_out, b->s_out})
+        if (s) (void)hipStreamDestroy(s);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
-}
-
-template <typename T>
-vpt_status grow(T** ptr, size_t* cap, size_t need) {
-    if (need <= *cap && *ptr) return VPT_OK;
-    size_t ncap = std::max<size_t>(need, *cap + *cap / 2);
-    ncap = std::max<size_t>(ncap, 64);
-    (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    VPT_HIP(hipMalloc(reinterpret_cast<void**>(ptr), ncap * sizeof(T) + 64));
-    *cap = ncap;
-    return VPT_OK;
 }
 
 vpt_status status_from_bits(uint32_t bits) {
@@ -443,6 +446,11 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrOutputTooSmall)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text");
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
+}
+
+// what a cutter of host_chunks.hpp refused, in the words the device has for the same finding
+vpt_status cut_fail(vptcut::CutError e) {
+    return status_from_bits(e == vptcut::CutError::kEmptySentence ? vpt::kErrEmptySentence : vpt::kErrBadOffsets);
 }
 
 // The device's verdict on tokenized text (kErrParse): the smallest failing line over the reason words (kernels.hpp), named with
@@ -461,16 +469,18 @@ vpt_status parse_status(const uint32_t* ctrl, uint64_t line_base) {
 
 // An idle workspace of the predictor's pool for one host-buffer call (created, with a stream of its own, when the
 // pool is empty); goes back to the pool when the guard dies.
+// Every stream a host-buffer call may have used on this workspace has run dry.
+void drain(vpt_batch* b) {
+    (void)hipStreamSynchronize(b->own_stream);
+    for (hipStream_t s : {b->s_in, b->s_tok_in, b->s_tok_out, b->s_out})
+        if (s) (void)hipStreamSynchronize(s);
+}
 struct Workspace {
     const vpt_predictor* p = nullptr;
     vpt_batch* b = nullptr;
     ~Workspace() {
         if (!b) return;
-        (void)hipStreamSynchronize(b->own_stream);   // an error return may leave copies from the caller's buffers in flight
-        if (b->s_in) (void)hipStreamSynchronize(b->s_in);
-        if (b->s_tok_in) (void)hipStreamSynchronize(b->s_tok_in);
-        if (b->s_tok_out) (void)hipStreamSynchronize(b->s_tok_out);
-        if (b->s_out) (void)hipStreamSynchronize(b->s_out);
+        drain(b);              // an error return may leave copies from the caller's buffers in flight
         b->tagger = nullptr;   // (the *_rules pipelines bind one for their call)
         std::lock_guard<std::mutex> g(p->pool_mu);
         p->pool.push_back(b);
@@ -483,13 +493,12 @@ vpt_status batch_create_with(const vpt_predictor* p, const BatchKnobs& knobs, vp
     if (!b) return fail(VPT_RUNTIME_ERROR, "out of host memory");
     b->pred = p; b->device = p->device;
     b->knobs = knobs;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->d_ctrl), 64);
-    if (e == hipSuccess) e = hipMemset(b->d_ctrl, 0, 64);
-    if (e == hipSuccess && b->knobs.profile_phases) {
-        e = hipMalloc(reinterpret_cast<void**>(&b->d_prof), 128);
-        if (e == hipSuccess) e = hipMemset(b->d_prof, 0, 128);
-    }
-    if (e != hipSuccess) { batch_release(b); return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e)); }
+    hipError_t e = hipSuccess;
+    vpt_status st = b->d_ctrl.alloc(64);
+    if (st == VPT_OK) e = hipMemset(b->d_ctrl, 0, 64);
+    if (st == VPT_OK && e == hipSuccess && b->knobs.profile_phases && (st = b->d_prof.alloc(128)) == VPT_OK) e = hipMemset(b->d_prof, 0, 128);
+    if (e != hipSuccess) st = fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    if (st != VPT_OK) { batch_release(b); return st; }
     *out = b;
     return VPT_OK;
 }
@@ -512,6 +521,16 @@ vpt_status acquire(const vpt_predictor* p, Workspace* w) {
     return VPT_OK;
 }
 
+// b->h_off holds `need` pinned words (by half as much again when it has to be made anew: its contents are then gone).
+vpt_status pinned_words(vpt_batch* b, size_t need) {
+    if (need <= b->h_off_cap) return VPT_OK;
+    if (b->h_off) (void)hipHostFree(b->h_off);
+    b->h_off = nullptr; b->h_off_cap = 0;
+    VPT_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_off), (need + need / 2) * sizeof(uint64_t), hipHostMallocDefault));
+    b->h_off_cap = need + need / 2;
+    return VPT_OK;
+}
+
 // The caller's batch -> the workspace's staging buffers, on its stream: text, offsets rebased so that the device sees
 // text and outputs starting at 0, and (when given) the labels.  `max_bytes` / `max_chars`: the longest sentence.
 vpt_status stage(vpt_batch* b, const uint8_t* utf8, const uint64_t* byte_offsets, const uint64_t* out_offsets, size_t n_sentences,
@@ -522,33 +541,17 @@ vpt_status stage(vpt_batch* b, const uint8_t* utf8, const uint64_t* byte_offsets
     const size_t nbytes = size_t(t1 - t0);
     const uint64_t total_b = out_offsets[n_sentences] - out_offsets[0];
     uint64_t max_bytes = 0, max_chars = 0;
-    for (size_t i = 0; i < n_sentences; ++i) {
-        if (byte_offsets[i + 1] <= byte_offsets[i])
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: must contain at least one character");
-        const uint64_t nb = byte_offsets[i + 1] - byte_offsets[i];
-        // n chars take between n and 4n bytes: anything else cannot have come from vpt_count_boundaries (checked
-        // before any buffer is sized from these numbers)
-        if (out_offsets[i + 1] < out_offsets[i] || out_offsets[i + 1] - out_offsets[i] + 1 > nb)
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out_offsets: do not match the text (or the text is not valid UTF-8)");
-        max_bytes = std::max<uint64_t>(max_bytes, nb);
-        max_chars = std::max<uint64_t>(max_chars, out_offsets[i + 1] - out_offsets[i] + 1);
+    for (size_t i = 0; i < n_sentences; ++i) {   // (checked before any buffer is sized from these numbers)
+        uint64_t nb = 0, nc = 0;
+        const vptcut::CutError bad = vptcut::check_sentence(byte_offsets, out_offsets, i, &nb, &nc);
+        if (bad != vptcut::CutError::kNone) return cut_fail(bad);
+        max_bytes = std::max(max_bytes, nb);
+        max_chars = std::max(max_chars, nc);
     }
     vpt_status st;
-    if ((st = grow(&b->d_text, &b->text_cap, nbytes + 32)) != VPT_OK) return st;
-    {
-        size_t cap = b->off_cap;
-        if ((st = grow(&b->d_boff, &cap, n_sentences + 1)) != VPT_OK) return st;
-        size_t cap2 = b->off_cap;
-        if ((st = grow(&b->d_ooff, &cap2, n_sentences + 1)) != VPT_OK) return st;
-        b->off_cap = std::min(cap, cap2);
-    }
-    {
-        size_t cap = b->out_cap;
-        if ((st = grow(&b->d_scores, &cap, size_t(total_b) + 1)) != VPT_OK) return st;
-        size_t cap2 = b->out_cap;
-        if ((st = grow(&b->d_labels, &cap2, size_t(total_b) + 1)) != VPT_OK) return st;
-        b->out_cap = std::min(cap, cap2);
-    }
+    if ((st = b->d_text.grow(nbytes + 32)) != VPT_OK) return st;
+    if ((st = grow_pair(b->d_boff, b->d_ooff, n_sentences + 1)) != VPT_OK) return st;
+    if ((st = grow_pair(b->d_scores, b->d_labels, size_t(total_b) + 1)) != VPT_OK) return st;
     std::vector<uint64_t>&boff = b->h_boff, &ooff = b->h_ooff;   // they outlive the asynchronous copies: the call ends with a sync
     boff.resize(n_sentences + 1); ooff.resize(n_sentences + 1);
     for (size_t i = 0; i <= n_sentences; ++i) { boff[i] = byte_offsets[i] - t0; ooff[i] = out_offsets[i] - out_offsets[0]; }

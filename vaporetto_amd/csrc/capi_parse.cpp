@@ -72,8 +72,8 @@ vpt_status parse_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t
         return VPT_OK;
     }
     vpt_status st;
-    if ((st = grow(&b->d_parse_tmp, &b->parse_tmp_cap, 2 * (n_sentences + 1))) != VPT_OK) return st;
-    if ((st = grow(&b->d_scan_part, &b->scan_part_cap, vpt::scan_part_entries(n_sentences))) != VPT_OK) return st;
+    if ((st = b->d_parse_tmp.grow(2 * (n_sentences + 1))) != VPT_OK) return st;
+    if ((st = b->d_scan_part.grow(vpt::scan_part_entries(n_sentences))) != VPT_OK) return st;
     vpt::ParseParams P{};
     P.text = d_utf8; P.boff = d_byte_offsets; P.n_sent = n_sentences;
     P.raw = d_raw_out; P.raw_cap = capacity; P.raw_off = d_raw_offsets_out; P.ooff = d_out_offsets_out;
@@ -220,7 +220,7 @@ vpt_status vpt_evaluate_batch(const vpt_predictor* p, const uint8_t* utf8, const
         i0 = i1;
     }
     EvalLayout L{};
-    if ((st = grow(&b->d_eval, &b->eval_cap, eval_layout(nullptr, max_bytes, max_lines, &L))) != VPT_OK) return st;
+    if ((st = b->d_eval.grow(eval_layout(nullptr, max_bytes, max_lines, &L))) != VPT_OK) return st;
     eval_layout(b->d_eval, max_bytes, max_lines, &L);
     VPT_HIP(hipMemsetAsync(L.counts, 0, 8 * vpt::kEvalCounts, s));
     std::vector<uint64_t>& boff = b->h_boff;
