@@ -487,6 +487,48 @@ vpt_status vpt_parse_tokenized_batch_device(const vpt_predictor *p, vpt_batch *b
                                             uint64_t *d_span_offsets_out, uint8_t *d_tag_bytes_out, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Sentence::from_partial_annotation / write_partial_annotation_text over a batch          (sentence.rs:516-769, 907-944)
+ *
+ * Line i is utf8[byte_offsets[i] .. byte_offsets[i+1]): chars alternating with boundary marks -- '-' NotWordBoundary (0), '|' WordBoundary (1),
+ * ' ' Unknown (2) -- and "/tag" suffixes behind any char, '\\' escaping the next code point of an annotation.  Signatures, output arrays,
+ * bounds, the capacity rule and error delivery are those of vpt_parse_tokenized_batch[_device] above; what differs:
+ *   labels_out       0 / 1 / 2;
+ *   tag_index_out    EVERY char may carry tags, not only a token's last one; an empty tag is None but counts towards n_tags.
+ * The reference's rules, quirks included.  A char is a lead byte and the continuation bytes behind it.
+ *   - The code point behind a mark (or at the line's start) is a char WHATEVER it is: ' ', '-', '|', '/' and '\\' can all be chars
+ *     ("a||-b" is the raw text "a|b" with labels 1, 0).
+ *   - '\\' escapes only inside the annotation.  An escaped or ordinary code point outside a tag is the error
+ *     "contains an invalid boundary character: 'c'" -- c is that code point, not the backslash.
+ *   - A dangling escape at the line's end is accepted ("a\\" is the one char a; "a/x\\" has the tag x).
+ *   - NUL is "must not contain NULL" only where a char is expected; inside a tag it is a tag byte.
+ *   - A line that ends right behind a mark is "invalid annotation"; an empty line is "must contain at least one character".
+ * Errors: VPT_INVALID_ARGUMENT "InvalidArgumentError: partial_annotation_text: <reason> (line i)" for the smallest failing line and that
+ * line's first error in reading order.  (The message is a C string: a NUL named by the invalid-boundary-character reason ends it.)  The
+ * device returns the line, the reason and the offending code point's bytes in its status words; the host formats them at vpt_batch_sync. */
+vpt_status vpt_parse_partial_batch(const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, uint8_t *raw_out,
+                                   uint64_t *raw_offsets_out, uint64_t *out_offsets_out, uint8_t *labels_out, uint32_t *n_tags_out,
+                                   uint64_t *tag_index_out, uint64_t *span_offsets_out, uint8_t *tag_bytes_out);
+vpt_status vpt_parse_partial_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                          size_t n_sentences, uint64_t capacity, uint8_t *d_raw_out, uint64_t *d_raw_offsets_out,
+                                          uint64_t *d_out_offsets_out, uint8_t *d_labels_out, uint32_t *d_n_tags_out, uint64_t *d_tag_index_out,
+                                          uint64_t *d_span_offsets_out, uint8_t *d_tag_bytes_out, void *hip_stream);
+/* The other direction, from what the two parsers write: the raw text and its byte offsets, out_offsets, labels 0 / 1 / 2 and the tag arrays
+ * (n_tags == NULL: no tags, the three tag arrays are not read).  text_out: the lines back to back, byte for byte write_partial_annotation_text --
+ * the first char as it is; before every later char its boundary's '-' / '|' / ' '; behind a char its tags up to the last non-empty one, each
+ * preceded by '/', an empty one among them an empty field (a char whose tags are all empty prints no '/').  Tags are NOT escaped (the reference
+ * does not escape them), so only tags without ' ', '-', '|', '/' and '\\' parse back to themselves.  text_offsets_out [S+1]: the lines' ranges.
+ * Errors (VPT_INVALID_ARGUMENT): a label above 2, an empty line, out_offsets that do not match the text, and an output larger than
+ * text_capacity (nothing is written past it; raw bytes + chars + tags + tag bytes always suffices).  The host variant runs on the host; the
+ * *_device variant is asynchronous on hip_stream with its errors at vpt_batch_sync. */
+vpt_status vpt_write_partial_batch(const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_sentences, const uint64_t *out_offsets,
+                                   const uint8_t *labels, const uint32_t *n_tags, const uint64_t *tag_index, const uint64_t *span_offsets,
+                                   const uint8_t *tag_bytes, uint8_t *text_out, uint64_t text_capacity, uint64_t *text_offsets_out);
+vpt_status vpt_write_partial_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                          size_t n_sentences, const uint64_t *d_out_offsets, const uint8_t *d_labels, const uint32_t *d_n_tags,
+                                          const uint64_t *d_tag_index, const uint64_t *d_span_offsets, const uint8_t *d_tag_bytes,
+                                          uint8_t *d_text_out, uint64_t text_capacity, uint64_t *d_text_offsets_out, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The `evaluate` CLI's counters                                                          (evaluate/src/main.rs:91-193)
  *
  * counts: eight uint64_t, indexed by VPT_EVAL_*: the char metric's TP / TN / FP / FN over the boundaries, Nagata's word metric's

@@ -125,6 +125,10 @@ SIGNATURES = {
     "vpt_predict_listing_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, C.c_uint, _P, C.c_uint64, _P, _P]),
     "vpt_parse_tokenized_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vpt_parse_tokenized_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_parse_partial_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_parse_partial_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vpt_write_partial_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, _P]),
+    "vpt_write_partial_batch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, _P, _P]),
     "vpt_evaluate_labels_batch_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "vpt_evaluate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, C.c_int, _P]),
     "vpt_batch_create": (C.c_int, [_P, C.POINTER(_P)]),

@@ -544,6 +544,20 @@ class Sentence:
             out.append("/".join(parts))
         return " ".join(out)
 
+    def write_partial_annotation_text(self) -> str:  # sentence.rs:907-944: tags are written as they are, not escaped
+        marks = {int(CharacterBoundary.NotWordBoundary): "-", int(CharacterBoundary.WordBoundary): "|", int(CharacterBoundary.Unknown): " "}
+        out = []
+        for c, ch in enumerate(self._text):
+            if c:
+                out.append(marks[int(self._boundaries[c - 1])])
+            out.append(ch)
+            if self._n_tags:
+                row = list(self._tags[c * self._n_tags:(c + 1) * self._n_tags])
+                while row and row[-1] is None:   # up to the last Some (sentence.rs:914, 927)
+                    row.pop()
+                out += ["/" + (t if t is not None else "") for t in row]
+        return "".join(out)
+
 
 class Predictor:
     """predictor.rs:433-665 (boundary prediction)."""
@@ -1076,6 +1090,68 @@ class Predictor:
         h["n_tags"] = h["n_tags"].view(np.uint32)[:S]
         return _trim_parsed(h, S)
 
+    def parse_partial_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, capacity: Optional[int] = None) -> dict:
+        """Sentence::from_partial_annotation for a packed batch of partially annotated lines, on the device (vpt_parse_partial_batch_device).
+        Returns the arrays of parse_partial_host.  capacity: what the output buffers hold (default: the input's bytes)."""
+        import torch
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S = len(byte_offsets) - 1
+        B = len(utf8) if capacity is None else int(capacity)
+        dev = torch.device("cuda", self.device)
+
+        def d(n, dt):
+            return torch.zeros(max(n, 1), dtype=dt, device=dev)
+        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(1, np.uint8)])).to(dev)
+        d_boff = torch.from_numpy(byte_offsets.view(np.int64)).to(dev)
+        o = {"raw": d(B, torch.uint8), "raw_offsets": d(S + 1, torch.int64), "out_offsets": d(S + 1, torch.int64), "labels": d(B, torch.uint8),
+             "n_tags": d(S, torch.int32), "tag_index": d(B + 1, torch.int64), "span_offsets": d(B + 1, torch.int64), "tag_bytes": d(B, torch.uint8)}
+        batch = DeviceBatch(self)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.load().vpt_parse_partial_batch_device(
+            self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, o["raw"].data_ptr(), o["raw_offsets"].data_ptr(),
+            o["out_offsets"].data_ptr(), o["labels"].data_ptr(), o["n_tags"].data_ptr(), o["tag_index"].data_ptr(),
+            o["span_offsets"].data_ptr(), o["tag_bytes"].data_ptr(), stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        batch.sync()
+        h = {k: v.cpu().numpy() for k, v in o.items()}
+        for k in ("raw_offsets", "out_offsets", "tag_index", "span_offsets"):
+            h[k] = h[k].view(np.uint64)
+        h["n_tags"] = h["n_tags"].view(np.uint32)[:S]
+        return _trim_parsed(h, S)
+
+    def write_partial_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
+                             n_tags: Optional[np.ndarray] = None, tag_index: Optional[np.ndarray] = None,
+                             span_offsets: Optional[np.ndarray] = None, tag_bytes: Optional[np.ndarray] = None, capacity: Optional[int] = None):
+        """Sentence::write_partial_annotation_text (sentence.rs:907-944) over a packed batch on the device (vpt_write_partial_batch_device), from
+        the arrays the parsers return; n_tags None: no tags.  Returns (uint8 text, uint64 [S+1] offsets)."""
+        import torch
+        a = _partial_writer_args(utf8, byte_offsets, out_offsets, labels, n_tags, tag_index, span_offsets, tag_bytes)
+        S, cap = a["S"], a["cap"] if capacity is None else int(capacity)
+        dev = torch.device("cuda", self.device)
+
+        def up(x):
+            x = x if len(x) else np.zeros(1, x.dtype)
+            signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}.get(x.dtype)
+            return torch.from_numpy(x.view(signed) if signed else x).to(dev)
+        dv = {k: up(a[k]) for k in ("utf8", "boff", "ooff", "labels")}
+        if a["n_tags"] is not None:
+            dv.update({k: up(a[k]) for k in ("n_tags", "tag_index", "span_offsets", "tag_bytes")})
+        ptr = lambda k: dv[k].data_ptr() if k in dv else None
+        d_text = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+        d_toff = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+        batch = DeviceBatch(self)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.load().vpt_write_partial_batch_device(self._h, batch._h, ptr("utf8"), ptr("boff"), S, ptr("ooff"), ptr("labels"), ptr("n_tags"),
+                                                        ptr("tag_index"), ptr("span_offsets"), ptr("tag_bytes"), d_text.data_ptr(), cap,
+                                                        d_toff.data_ptr(), stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        batch.sync()
+        toff = d_toff.cpu().numpy().view(np.uint64)
+        return d_text.cpu().numpy()[:int(toff[S])], toff
+
     def evaluate(self, lines: Sequence[str], predict_tags: bool = False, wsconst: Sequence = (), no_norm: bool = False) -> dict:
         """The `evaluate` CLI (evaluate/src/main.rs:91-193) over tokenized lines: empty lines are skipped, every other line must parse.
         wsconst: CharacterType values and / or "G".  The "(line N)" of a parse error counts the given lines, empty ones included.  Returns the counters (tp, tn, fp, fn, n_sys, n_ref, n_cor, n_sentences) and the
@@ -1379,6 +1455,56 @@ def parse_tokenized_host(lines: Sequence[bytes]) -> dict:
     if st != _lib.VPT_OK:
         _raise(st)
     return _trim_parsed(h, S)
+
+
+def parse_partial_host(lines: Sequence[bytes]) -> dict:
+    """vpt_parse_partial_batch (host): partially annotated lines -> the arrays of parse_tokenized_host, labels 0 / 1 / 2 and tags on any char."""
+    utf8, boff = pack_texts(list(lines))
+    S, B = len(lines), len(utf8)
+    h = {"raw": np.zeros(max(B, 1), np.uint8), "raw_offsets": np.zeros(S + 1, np.uint64), "out_offsets": np.zeros(S + 1, np.uint64),
+         "labels": np.zeros(max(B, 1), np.uint8), "n_tags": np.zeros(max(S, 1), np.uint32), "tag_index": np.zeros(B + 1, np.uint64),
+         "span_offsets": np.zeros(B + 1, np.uint64), "tag_bytes": np.zeros(max(B, 1), np.uint8)}
+    u = utf8 if B else np.zeros(1, np.uint8)
+    st = _lib.load().vpt_parse_partial_batch(u.ctypes.data, boff.ctypes.data, S, *[h[k].ctypes.data for k in
+                                             ("raw", "raw_offsets", "out_offsets", "labels", "n_tags", "tag_index", "span_offsets", "tag_bytes")])
+    if st != _lib.VPT_OK:
+        _raise(st)
+    return _trim_parsed(h, S)
+
+
+def _partial_writer_args(utf8, byte_offsets, out_offsets, labels, n_tags, tag_index, span_offsets, tag_bytes) -> dict:
+    a = {"utf8": np.ascontiguousarray(utf8, dtype=np.uint8), "boff": np.ascontiguousarray(byte_offsets, dtype=np.uint64),
+         "ooff": np.ascontiguousarray(out_offsets, dtype=np.uint64), "labels": np.ascontiguousarray(labels, dtype=np.uint8), "n_tags": None}
+    a["S"] = len(a["boff"]) - 1
+    a["cap"] = len(a["utf8"]) + len(a["labels"])
+    if n_tags is not None:
+        a["n_tags"] = np.ascontiguousarray(n_tags, dtype=np.uint32)
+        a["tag_index"] = np.ascontiguousarray(tag_index, dtype=np.uint64)
+        a["span_offsets"] = np.ascontiguousarray(span_offsets, dtype=np.uint64)
+        a["tag_bytes"] = np.ascontiguousarray(tag_bytes, dtype=np.uint8)
+        a["cap"] += len(a["span_offsets"]) + len(a["tag_bytes"])
+    return a
+
+
+def write_partial_host(utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray, n_tags: Optional[np.ndarray] = None,
+                       tag_index: Optional[np.ndarray] = None, span_offsets: Optional[np.ndarray] = None, tag_bytes: Optional[np.ndarray] = None,
+                       capacity: Optional[int] = None):
+    """vpt_write_partial_batch (host): Sentence::write_partial_annotation_text over a packed batch, from the arrays the parsers return;
+    n_tags None: no tags.  Returns (uint8 text, uint64 [S+1] offsets)."""
+    a = _partial_writer_args(utf8, byte_offsets, out_offsets, labels, n_tags, tag_index, span_offsets, tag_bytes)
+    S, cap = a["S"], a["cap"] if capacity is None else int(capacity)
+    text = np.zeros(max(cap, 1), np.uint8)
+    toff = np.zeros(S + 1, np.uint64)
+    keep = [x if len(x) else np.zeros(1, x.dtype) for x in (a["utf8"], a["labels"])]
+    tags = [None] * 4
+    if a["n_tags"] is not None:
+        keep += [x if len(x) else np.zeros(1, x.dtype) for x in (a["n_tags"], a["tag_index"], a["span_offsets"], a["tag_bytes"])]
+        tags = [x.ctypes.data for x in keep[2:]]
+    st = _lib.load().vpt_write_partial_batch(keep[0].ctypes.data, a["boff"].ctypes.data, S, a["ooff"].ctypes.data, keep[1].ctypes.data, *tags,
+                                             text.ctypes.data, cap, toff.ctypes.data)
+    if st != _lib.VPT_OK:
+        _raise(st)
+    return text[:int(toff[S])], toff
 
 
 def evaluation_result(counts) -> dict:

@@ -274,6 +274,10 @@ vpt_status vpt_batch_sync(vpt_batch* b) {
         VPT_HIP(hipMemset(b->d_ctrl + vpt::kParseErrWord, 0, 8 * sizeof(uint32_t)));
         return parse_status(ctrl, 0);
     }
+    if (ctrl[0] & vpt::kErrParsePartial) {   // partially annotated text (vpt_parse_partial_batch_device): its reason words and the offender's bytes
+        VPT_HIP(hipMemset(b->d_ctrl + vpt::kPartialErrWord + 1, 0, 6 * sizeof(uint32_t)));
+        return partial_status(ctrl, 0);
+    }
     return status_from_bits(ctrl[0]);
 }
 

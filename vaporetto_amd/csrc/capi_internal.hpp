@@ -445,6 +445,8 @@ vpt_status status_from_bits(uint32_t bits) {
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: only NotWordBoundary (0) and WordBoundary (1) can be written as tokenized text");
     if (bits & vpt::kErrOutputTooSmall)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text");
+    if (bits & vpt::kErrBadLabel)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: not a CharacterBoundary (0, 1 or 2)");
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
 
@@ -465,6 +467,30 @@ vpt_status parse_status(const uint32_t* ctrl, uint64_t line_base) {
     if (!reason) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tokenized_text: rejected");
     return fail(VPT_INVALID_ARGUMENT, std::string("InvalidArgumentError: tokenized_text: ") + msg[reason] + " (line " +
                                           std::to_string(line_base + (0xFFFFFFFFu - best)) + ")");
+}
+
+// A line that parse_partial_annotation rejects (sentence.rs:516-631): the reference's message and the batch's line.  offender: the code point of
+// kPartialErrChar (the message is a C string: a NUL offender ends it).
+vpt_status partial_fail(uint32_t reason, const std::string& offender, uint64_t line) {
+    static const char* const msg[5] = {"rejected", "must contain at least one character", "must not contain NULL",
+                                       "contains an invalid boundary character: '", "invalid annotation"};
+    std::string m = std::string("InvalidArgumentError: partial_annotation_text: ") + msg[reason <= 4 ? reason : 0];
+    if (reason == vpt::kPartialErrChar) m += offender + "'";
+    return fail(VPT_INVALID_ARGUMENT, m + " (line " + std::to_string(line) + ")");
+}
+// The device's verdict on partially annotated text (kErrParsePartial): the smallest failing line over the reason words, and for the
+// invalid-boundary-character reason the offender's bytes (kernels.hpp).
+vpt_status partial_status(const uint32_t* ctrl, uint64_t line_base) {
+    uint32_t best = 0, reason = 0;
+    for (uint32_t r = 1; r <= 4; ++r)
+        if (ctrl[vpt::kPartialErrWord + r] > best) { best = ctrl[vpt::kPartialErrWord + r]; reason = r; }
+    std::string offender;
+    if (reason == vpt::kPartialErrChar) {
+        const uint32_t w = ctrl[vpt::kPartialErrBytesWord];
+        offender.push_back(char(w & 0xFFu));
+        for (int k = 1; k < 4 && ((w >> (8 * k)) & 0xC0u) == 0x80u; ++k) offender.push_back(char((w >> (8 * k)) & 0xFFu));
+    }
+    return partial_fail(reason, offender, line_base + (0xFFFFFFFFu - best));
 }
 
 // An idle workspace of the predictor's pool for one host-buffer call (created, with a stream of its own, when the

@@ -1,4 +1,5 @@
-// C ABI of libvaporetto_hip.so, tokenized text: Sentence::from_tokenized for a batch (sentence.rs:285-400) on the host and on the device, and the
+// C ABI of libvaporetto_hip.so, annotated text: Sentence::from_tokenized for a batch (sentence.rs:285-400) on the host and on the device,
+// Sentence::from_partial_annotation and write_partial_annotation_text likewise (sentence.rs:516-631, 907-944), and the
 // counters of the `evaluate` CLI (evaluate/src/main.rs:91-193) -- the compare kernel alone, and the whole pipeline over host lines.
 #include "capi_internal.hpp"
 
@@ -54,10 +55,90 @@ uint32_t parse_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32
     return 0;
 }
 
+// One line of parse_partial_annotation (sentence.rs:516-631), code point by code point (a lead byte and the continuation bytes behind it); appends
+// to the outputs.  Returns 0 or the kPartialErr* reason; *offender: the code point an invalid-boundary-character error names.
+uint32_t parse_partial_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32_t* n_tags_out, std::string* offender) {
+    if (len == 0) return vpt::kPartialErrNoChar;
+    bool escape = false, is_char = true, in_tag = false;
+    uint64_t chars = 0;
+    uint32_t slot = 0, n_tags = 0;
+    for (uint64_t k = 0; k < len;) {
+        const uint64_t k0 = k++;
+        while (k < len && (t[k] & 0xC0u) == 0x80u) ++k;
+        const uint8_t c = t[k0];
+        if (is_char) {
+            if (c == 0) return vpt::kPartialErrNul;
+            if (chars) ++o.n_labels;   // (its label was stored by the mark in front of it)
+            o.tag_index[o.n_chars++] = o.n_tags;
+            ++chars;
+            slot = 0;
+            for (uint64_t q = k0; q < k; ++q) o.raw[o.n_raw++] = t[q];
+            is_char = false;
+            continue;
+        }
+        if (!escape && c == '\\') { escape = true; continue; }
+        if (!escape && (c == ' ' || c == '-' || c == '|')) {
+            o.labels[o.n_labels] = c == '-' ? VPT_NOT_WORD_BOUNDARY : c == '|' ? VPT_WORD_BOUNDARY : VPT_BOUNDARY_UNKNOWN;
+            in_tag = false;
+            is_char = true;
+            continue;
+        }
+        if (!escape && c == '/') {
+            in_tag = true;
+            o.span_off[o.n_tags++] = o.n_tb;
+            n_tags = std::max(n_tags, ++slot);
+            continue;
+        }
+        escape = false;
+        if (!in_tag) {
+            offender->assign(reinterpret_cast<const char*>(t + k0), size_t(k - k0));
+            return vpt::kPartialErrChar;
+        }
+        for (uint64_t q = k0; q < k; ++q) o.tag_bytes[o.n_tb++] = t[q];
+    }
+    if (is_char) return vpt::kPartialErrEnd;
+    *n_tags_out = n_tags;
+    return 0;
+}
+
+// One line of write_partial_annotation_text (sentence.rs:907-944); returns the bytes it takes, written to out (when given) up to `cap`.
+struct HostPartialIn {
+    const uint8_t *text, *labels, *tag_bytes;
+    const uint64_t *tag_index, *span_off;
+};
+uint64_t write_partial_line_host(const HostPartialIn& in, uint64_t t0, uint64_t t1, uint64_t b0, uint64_t g0, uint8_t* out, uint64_t at, uint64_t cap) {
+    uint64_t k = at, ci = 0;
+    auto put = [&](uint8_t c) { if (out && k < cap) out[k] = c; ++k; };
+    auto suffix = [&](uint64_t g) {
+        if (!in.tag_index) return;
+        const uint64_t a = in.tag_index[g];
+        uint64_t e = in.tag_index[g + 1];
+        while (e > a && in.span_off[e] == in.span_off[e - 1]) --e;   // up to the last Some
+        for (uint64_t t = a; t < e; ++t) {
+            put('/');
+            for (uint64_t q = in.span_off[t]; q < in.span_off[t + 1]; ++q) put(in.tag_bytes[q]);
+        }
+    };
+    for (uint64_t q = t0; q < t1; ++q) {
+        const uint8_t c = in.text[q];
+        if ((c & 0xC0u) != 0x80u) {
+            if (ci) {
+                suffix(g0 + ci - 1);
+                const uint8_t lab = in.labels[b0 + ci - 1];
+                put(lab == VPT_NOT_WORD_BOUNDARY ? '-' : lab == VPT_WORD_BOUNDARY ? '|' : ' ');
+            }
+            ++ci;
+        }
+        put(c);
+    }
+    suffix(g0 + ci - 1);
+    return k - at;
+}
+
 vpt_status parse_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets, size_t n_sentences,
                              uint64_t capacity, uint8_t* d_raw_out, uint64_t* d_raw_offsets_out, uint64_t* d_out_offsets_out, uint8_t* d_labels_out,
                              uint32_t* d_n_tags_out, uint64_t* d_tag_index_out, uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out,
-                             hipStream_t stream) {
+                             hipStream_t stream, bool partial = false) {
     if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
     if (n_sentences >= 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_sentences: at most 2^32-2 per call");
     if (!d_raw_offsets_out || !d_out_offsets_out || !d_tag_index_out || !d_span_offsets_out ||
@@ -82,7 +163,7 @@ vpt_status parse_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t
     P.tag_bytes = d_tag_bytes_out; P.tb_cap = capacity;
     P.tag_off = b->d_parse_tmp; P.tb_off = b->d_parse_tmp + n_sentences + 1;
     P.status = b->d_ctrl;
-    VPT_HIP(vpt::launch_parse_tokenized(P, b->d_scan_part, stream));
+    VPT_HIP(partial ? vpt::launch_parse_partial(P, b->d_scan_part, stream) : vpt::launch_parse_tokenized(P, b->d_scan_part, stream));
     b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
     return VPT_OK;
 }
@@ -173,6 +254,85 @@ vpt_status vpt_parse_tokenized_batch_device(const vpt_predictor* p, vpt_batch* b
                                             uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out, void* hip_stream) {
     return parse_device_impl(p, b, d_utf8, d_byte_offsets, n_sentences, capacity, d_raw_out, d_raw_offsets_out, d_out_offsets_out, d_labels_out,
                              d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream));
+}
+
+vpt_status vpt_parse_partial_batch(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, uint8_t* raw_out,
+                                   uint64_t* raw_offsets_out, uint64_t* out_offsets_out, uint8_t* labels_out, uint32_t* n_tags_out,
+                                   uint64_t* tag_index_out, uint64_t* span_offsets_out, uint8_t* tag_bytes_out) {
+    if (!byte_offsets || !raw_offsets_out || !out_offsets_out || !tag_index_out || !span_offsets_out ||
+        (n_sentences && (!utf8 || !raw_out || !labels_out || !n_tags_out || !tag_bytes_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    HostParseOut o{raw_out, labels_out, tag_bytes_out, tag_index_out, span_offsets_out};
+    raw_offsets_out[0] = 0; out_offsets_out[0] = 0;
+    std::string offender;
+    for (size_t i = 0; i < n_sentences; ++i) {
+        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+        const uint32_t r = parse_partial_line_host(utf8 + byte_offsets[i], byte_offsets[i + 1] - byte_offsets[i], o, n_tags_out + i, &offender);
+        if (r) return partial_fail(r, offender, i);
+        raw_offsets_out[i + 1] = o.n_raw;
+        out_offsets_out[i + 1] = o.n_labels;
+    }
+    tag_index_out[o.n_chars] = o.n_tags;
+    span_offsets_out[o.n_tags] = o.n_tb;
+    return VPT_OK;
+}
+
+vpt_status vpt_parse_partial_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                          size_t n_sentences, uint64_t capacity, uint8_t* d_raw_out, uint64_t* d_raw_offsets_out,
+                                          uint64_t* d_out_offsets_out, uint8_t* d_labels_out, uint32_t* d_n_tags_out, uint64_t* d_tag_index_out,
+                                          uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out, void* hip_stream) {
+    return parse_device_impl(p, b, d_utf8, d_byte_offsets, n_sentences, capacity, d_raw_out, d_raw_offsets_out, d_out_offsets_out, d_labels_out,
+                             d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream), true);
+}
+
+vpt_status vpt_write_partial_batch(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint64_t* out_offsets,
+                                   const uint8_t* labels, const uint32_t* n_tags, const uint64_t* tag_index, const uint64_t* span_offsets,
+                                   const uint8_t* tag_bytes, uint8_t* text_out, uint64_t text_capacity, uint64_t* text_offsets_out) {
+    if (!byte_offsets || !out_offsets || !text_offsets_out || (n_sentences && (!utf8 || !text_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_tags && (!tag_index || !span_offsets)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_tags without the tag arrays");
+    const HostPartialIn in{utf8, labels, tag_bytes, n_tags ? tag_index : nullptr, span_offsets};
+    text_offsets_out[0] = 0;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n_sentences; ++i) {
+        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+        if (byte_offsets[i + 1] == byte_offsets[i]) return status_from_bits(vpt::kErrEmptySentence);
+        uint64_t chars = 0;
+        for (uint64_t q = byte_offsets[i]; q < byte_offsets[i + 1]; ++q) chars += (utf8[q] & 0xC0u) != 0x80u;
+        if (out_offsets[i + 1] < out_offsets[i] || chars != out_offsets[i + 1] - out_offsets[i] + 1) return status_from_bits(vpt::kErrBadOffsets);
+        if (chars > 1 && !labels) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+        for (uint64_t q = out_offsets[i]; q < out_offsets[i + 1]; ++q)
+            if (labels[q] > VPT_BOUNDARY_UNKNOWN) return status_from_bits(vpt::kErrBadLabel);
+        at += write_partial_line_host(in, byte_offsets[i], byte_offsets[i + 1], out_offsets[i], out_offsets[i] + i, text_out, at, text_capacity);
+        text_offsets_out[i + 1] = at;
+    }
+    return at > text_capacity ? status_from_bits(vpt::kErrOutputTooSmall) : VPT_OK;
+}
+
+vpt_status vpt_write_partial_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                          size_t n_sentences, const uint64_t* d_out_offsets, const uint8_t* d_labels, const uint32_t* d_n_tags,
+                                          const uint64_t* d_tag_index, const uint64_t* d_span_offsets, const uint8_t* d_tag_bytes,
+                                          uint8_t* d_text_out, uint64_t text_capacity, uint64_t* d_text_offsets_out, void* hip_stream) {
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (n_sentences >= 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_sentences: at most 2^32-2 per call");
+    if (!d_text_offsets_out || (n_sentences && (!d_utf8 || !d_byte_offsets || !d_out_offsets || !d_labels || !d_text_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (d_n_tags && (!d_tag_index || !d_span_offsets || !d_tag_bytes)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_tags without the tag arrays");
+    VPT_HIP(hipSetDevice(p->device));
+    if (n_sentences == 0) {
+        VPT_HIP(hipMemsetAsync(d_text_offsets_out, 0, sizeof(uint64_t), stream));
+        return VPT_OK;
+    }
+    vpt_status st;
+    if ((st = b->d_scan_part.grow(vpt::scan_part_entries(n_sentences))) != VPT_OK) return st;
+    vpt::WritePartialParams W{};
+    W.text = d_utf8; W.boff = d_byte_offsets; W.ooff = d_out_offsets; W.n_sent = n_sentences; W.labels = d_labels;
+    W.tag_index = d_n_tags ? d_tag_index : nullptr; W.span_off = d_span_offsets; W.tag_bytes = d_tag_bytes;
+    W.out = d_text_out; W.capacity = text_capacity; W.out_off = d_text_offsets_out; W.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_write_partial(W, b->d_scan_part, stream));
+    b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+    return VPT_OK;
 }
 
 vpt_status vpt_evaluate_labels_batch_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_out_offsets, size_t n_sentences,

@@ -60,6 +60,11 @@ constexpr uint32_t kErrParse = 64u;           // tokenized text that parse_token
 // the reasons (sentence.rs:285-400), each with the smallest failing line as 0xFFFFFFFF - line (atomicMax) in status word kParseErrWord + reason
 constexpr uint32_t kParseErrNoChar = 1u, kParseErrStartSpace = 2u, kParseErrDoubleSpace = 3u, kParseErrEndSpace = 4u, kParseErrSlash = 5u,
                    kParseErrNul = 6u, kParseErrWord = 8u;
+constexpr uint32_t kErrParsePartial = 128u;   // partially annotated text that parse_partial_annotation rejects (sentence.rs:516-631)
+// its reasons, each with the smallest failing line as 0xFFFFFFFF - line (atomicMax) in status word kPartialErrWord + reason; for kPartialErrChar the
+// offending code point's bytes (little-endian, lead first) of THAT line in status word kPartialErrBytesWord, stored by the write pass
+constexpr uint32_t kPartialErrNoChar = 1u, kPartialErrNul = 2u, kPartialErrChar = 3u, kPartialErrEnd = 4u, kPartialErrWord = 1u, kPartialErrBytesWord = 7u;
+constexpr uint32_t kErrBadLabel = 256u;       // the partial-annotation writer: a label that is no CharacterBoundary (above 2)
 
 
 struct ScoreParams {
@@ -321,6 +326,25 @@ struct ParseParams {
     uint32_t* status;           // the workspace's status words (kErrParse + the reason words)
 };
 hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
+// partially annotated text -> the same arrays (Sentence::from_partial_annotation, sentence.rs:516-631): labels 0 / 1 / 2, tags on any char.
+// The same two passes and four scans; a byte's role comes from a scan of state-transition maps over the window (kernels_parse.hip).
+hipError_t launch_parse_partial(const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
+// Sentence::write_partial_annotation_text for a batch (sentence.rs:907-944) from what the parsers write: a count pass (out_off[line + 1] = the
+// line's bytes), the chained scan, a write pass.  tag_index == nullptr: no tags.
+struct WritePartialParams {
+    const uint8_t* text;        // raw text
+    const uint64_t* boff;       // [S+1]
+    const uint64_t* ooff;       // [S+1]
+    uint64_t n_sent;
+    const uint8_t* labels;      // 0 / 1 / 2 per boundary
+    const uint64_t* tag_index;  // the parsers' tag CSR, or nullptr
+    const uint64_t* span_off;
+    const uint8_t* tag_bytes;
+    uint8_t* out; uint64_t capacity;
+    uint64_t* out_off;          // [S+1]
+    uint32_t* status;
+};
+hipError_t launch_write_partial(const WritePartialParams& P, uint64_t* scan_part, hipStream_t stream);
 // the counters of evaluate/src/main.rs:124-191, ADDED to counts[kEvalCounts]: tp, tn, fp, fn, n_sys, n_ref, n_cor, n_sentences
 constexpr uint32_t kEvalCounts = 8;
 constexpr uint32_t kEvalTagsNone = 0, kEvalTagsGold = 1, kEvalTagsPredicted = 2;

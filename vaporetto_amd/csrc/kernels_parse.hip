@@ -12,6 +12,9 @@
 // counts (surface bytes, chars, tags, tag bytes, the largest slot count) and reports the first error of the line; a chained scan of each
 // count (kernels_emit.hip) places the lines; kWrite == true walks the line again and writes what it counted where the scans put it.
 //
+// parse_partial_kernel / write_partial_kernel: partially annotated text both ways (Sentence::from_partial_annotation, write_partial_annotation_text;
+// sentence.rs:516-631, 907-944), described where they stand.
+//
 // evaluate_kernel: a wave per sentence over its boundaries, 64 a window.  The char metric is four popcounts.  Nagata's word metric
 // (evaluate/src/main.rs:149-191) carries `matched` from boundary to boundary; here it is a segmented scan: at an agreed WordBoundary b the
 // flag is "the last disagreement before b lies before the last agreed WordBoundary before b" -- two highest-bit searches per lane.
@@ -152,6 +155,241 @@ __global__ __launch_bounds__(kParseThreads) void parse_tokenized_kernel(const Pa
     }
 }
 
+// ---- partial annotation
+//
+// parse_partial_kernel<kWrite>: Sentence::from_partial_annotation (sentence.rs:516-631) in the frame of parse_tokenized_kernel.  What a byte IS depends
+// on the whole prefix here -- the code point behind a mark is a char whatever it is -- so the window step is a prefix scan of the transition maps of a
+// six-state machine over five input classes:
+//   states   E expect-char, A annotation, AE annotation behind a '\\', T tag, TE tag behind a '\\', X error (absorbing)
+//   classes  '\\', mark (' ' '-' '|'), '/', NUL, other
+// A map is 6 states x 3 bits in one word; a lead-byte lane holds the map of its class, a continuation byte the identity; composing two maps is six
+// extracts, the inclusive scan six DPP steps.  The carried entry state applied to a lane's map is its state behind its byte; the lane below (or the
+// entry state) gives the state in front of it, and (state in front, class) is the byte's role.  Continuation bytes take the role of their lead.
+constexpr uint32_t kStE = 0, kStA = 1, kStAE = 2, kStT = 3, kStTE = 4, kStX = 5;
+constexpr uint32_t pmap(uint32_t e, uint32_t a, uint32_t ae, uint32_t t, uint32_t te) {
+    return e | (a << 3) | (ae << 6) | (t << 9) | (te << 12) | (kStX << 15);
+}
+constexpr uint32_t kMapId = pmap(kStE, kStA, kStAE, kStT, kStTE);
+constexpr uint32_t kMapBackslash = pmap(kStA, kStAE, kStX, kStTE, kStT);
+constexpr uint32_t kMapMark = pmap(kStA, kStE, kStX, kStE, kStT);
+constexpr uint32_t kMapSlash = pmap(kStA, kStT, kStX, kStT, kStT);
+constexpr uint32_t kMapNul = pmap(kStX, kStX, kStX, kStT, kStT);
+constexpr uint32_t kMapOther = pmap(kStA, kStX, kStX, kStT, kStT);
+// first f, then g
+__device__ __forceinline__ uint32_t map_then(uint32_t f, uint32_t g) {
+    uint32_t h = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 6; ++s) h |= ((g >> (3u * ((f >> (3u * s)) & 7u))) & 7u) << (3u * s);
+    return h;
+}
+// inclusive scan of the maps over the wave, lane 0 first (the steps of wave_inclusive_scan; a lane without a source composes with the identity)
+__device__ __forceinline__ uint32_t wave_map_scan(uint32_t x) {
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x111, 0xF, 0xF, false)), x);  // row_shr:1
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x112, 0xF, 0xF, false)), x);  // row_shr:2
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x114, 0xF, 0xF, false)), x);  // row_shr:4
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x118, 0xF, 0xF, false)), x);  // row_shr:8
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x142, 0xA, 0xF, false)), x);  // row_bcast:15 -> rows 1, 3
+    x = map_then(uint32_t(__builtin_amdgcn_update_dpp(int(kMapId), int(x), 0x143, 0xC, 0xF, false)), x);  // row_bcast:31 -> rows 2, 3
+    return x;
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(kParseThreads) void parse_partial_kernel(const ParseParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
+    for (uint64_t line = uint64_t(blockIdx.x) * (kParseThreads / 64) + (threadIdx.x >> 6); line < P.n_sent; line += n_waves) {
+        const uint64_t start = P.boff[line], end = P.boff[line + 1];
+        const int64_t len = end > start ? int64_t(end - start) : 0;
+        uint64_t raw_at = 0, lab_at = 0, char_at = 0, tag_at = 0, tb_at = 0;
+        if (kWrite) {
+            raw_at = P.raw_off[line];
+            lab_at = P.ooff[line];
+            char_at = P.ooff[line] + line;
+            tag_at = P.tag_off[line];
+            tb_at = P.tb_off[line];
+        }
+        // carried from window to window: the state, the role of the last lead byte (0 none, 1 char, 2 tag), the openers since the last char, the counters
+        uint32_t state = kStE, open_role = 0, open_since_char = 0, n_tags = 0;
+        uint64_t raw = 0, chars = 0, tags = 0, tbytes = 0;
+        uint32_t err = 0, err_bytes = 0;   // first error of the line: kPartialErr* reason, and the offender's bytes
+        for (int64_t w0 = 0; w0 < len; w0 += 64) {
+            const bool valid = w0 + int64_t(lane) < len;
+            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : 0x80u;
+            // (a continuation byte that opens the line has no lead to belong to: it is one)
+            const bool lead = valid && ((c & 0xC0u) != 0x80u || w0 + int64_t(lane) == 0);
+            const bool is_bs = c == '\\', is_mark = c == ' ' || c == '-' || c == '|', is_sl = c == '/';
+            const uint32_t own = !lead ? kMapId : is_bs ? kMapBackslash : is_mark ? kMapMark : is_sl ? kMapSlash : c == 0u ? kMapNul : kMapOther;
+            const uint32_t incl = wave_map_scan(own);
+            const uint32_t after = (incl >> (3u * state)) & 7u;
+            const uint32_t up = __shfl_up(after, 1u);
+            const uint32_t before = lane == 0 ? state : up;
+            const bool annot = before == kStA || before == kStT;   // where '\\', marks and '/' mean something
+            const bool char_lead = lead && before == kStE && c != 0u;
+            const bool mark = lead && annot && is_mark, opener = lead && annot && is_sl;
+            const bool tag_lead = lead && (before == kStTE || (before == kStT && !is_bs && !is_mark && !is_sl));
+            const uint64_t leadm = __ballot(lead), clm = __ballot(char_lead), tlm = __ballot(tag_lead), openm = __ballot(opener);
+            const uint64_t below = lanes_below(lane);
+            // a continuation byte: the role of the last lead below it
+            const int jl = hi_lane(leadm & below);
+            const uint32_t role = lead ? (char_lead ? 1u : tag_lead ? 2u : 0u) : !valid ? 0u : jl >= 0 ? uint32_t((clm >> jl) & 1u) + 2u * uint32_t((tlm >> jl) & 1u) : open_role;
+            const uint64_t cbm = __ballot(role == 1u), tbm = __ballot(role == 2u);
+            // the first lane that enters the error state: NUL where a char is expected, else a code point that is no annotation
+            const uint64_t errm = __ballot(lead && before != kStX && after == kStX);
+            if (errm && !err) {
+                const uint32_t f = uint32_t(__builtin_ctzll(errm));
+                err = uint32_t(__shfl(int(before), int(f))) == kStE ? kPartialErrNul : kPartialErrChar;
+                if (kWrite && err == kPartialErrChar) {   // its bytes: the lead and the continuation bytes behind it (they may lie in the next window)
+                    const int64_t at = w0 + int64_t(f);
+                    err_bytes = P.text[start + uint64_t(at)];
+                    for (int64_t k = 1; k < 4 && at + k < len; ++k) {
+                        const uint32_t b = P.text[start + uint64_t(at + k)];
+                        if ((b & 0xC0u) != 0x80u) break;
+                        err_bytes |= b << (8 * k);
+                    }
+                }
+            }
+            // the slot of a '/': the openers between the char's lead and this one
+            const int jc = hi_lane(clm & below);
+            const uint32_t slot = jc >= 0 ? popc(openm & below & ~lanes_upto(uint32_t(jc))) : open_since_char + popc(openm & below);
+            if (!kWrite) {
+                n_tags = opener && slot + 1u > n_tags ? slot + 1u : n_tags;
+            } else {
+                if (role == 1u) {
+                    const uint64_t k = raw_at + raw + popc(cbm & below);
+                    if (k < P.raw_cap) P.raw[k] = uint8_t(c);
+                }
+                if (char_lead) {
+                    const uint64_t ci = chars + popc(clm & below);
+                    if (char_at + ci < P.index_cap) P.tag_index[char_at + ci] = tag_at + tags + popc(openm & below);
+                }
+                if (mark) {   // the boundary behind char ci - 1 (a mark only follows a char)
+                    const uint64_t ci = chars + popc(clm & below);
+                    if (lab_at + ci - 1 < P.label_cap) P.labels[lab_at + ci - 1] = c == '-' ? 0u : c == '|' ? 1u : 2u;
+                }
+                if (opener) {
+                    const uint64_t k = tag_at + tags + popc(openm & below);
+                    if (k < P.span_cap) P.span_off[k] = tb_at + tbytes + popc(tbm & below);
+                }
+                if (role == 2u) {
+                    const uint64_t k = tb_at + tbytes + popc(tbm & below);
+                    if (k < P.tb_cap) P.tag_bytes[k] = uint8_t(c);
+                }
+            }
+            // carried to the next window
+            state = uint32_t(__shfl(int(after), 63));
+            if (leadm) {
+                const int h = hi_lane(leadm);
+                open_role = uint32_t((clm >> h) & 1u) + 2u * uint32_t((tlm >> h) & 1u);
+            }
+            if (clm) open_since_char = popc(openm & ~lanes_upto(uint32_t(hi_lane(clm))));
+            else open_since_char += popc(openm);
+            raw += popc(cbm);
+            chars += popc(clm);
+            tags += popc(openm);
+            tbytes += popc(tbm);
+        }
+        if (!err) {
+            if (len == 0) err = kPartialErrNoChar;
+            else if (state == kStE) err = kPartialErrEnd;
+        }
+        if (!kWrite) {
+            const uint32_t nt = wave_max(n_tags);
+            if (lane == 0) {
+                P.raw_off[line + 1] = raw;
+                P.ooff[line + 1] = chars ? chars - 1 : 0;
+                P.tag_off[line + 1] = tags;
+                P.tb_off[line + 1] = tbytes;
+                P.n_tags[line] = nt;
+                if (err) {
+                    atomicOr(P.status, kErrParsePartial);
+                    atomicMax(P.status + kPartialErrWord + err, 0xFFFFFFFFu - uint32_t(line));
+                }
+            }
+        } else if (lane == 0) {
+            // the count pass has settled which line each reason names: the one kPartialErrChar names leaves its offender's bytes
+            if (err == kPartialErrChar && P.status[kPartialErrWord + kPartialErrChar] == 0xFFFFFFFFu - uint32_t(line)) P.status[kPartialErrBytesWord] = err_bytes;
+            if (line + 1 == P.n_sent) {   // the CSR arrays' last entries
+                if (char_at + chars < P.index_cap) P.tag_index[char_at + chars] = tag_at + tags;
+                if (tag_at + tags < P.span_cap) P.span_off[tag_at + tags] = tb_at + tbytes;
+            }
+        }
+    }
+}
+
+// write_partial_kernel<kWrite>: Sentence::write_partial_annotation_text (sentence.rs:907-944), a wave per line over windows of 64 raw bytes.  A char's
+// lead byte brings along what stands in front of it: the tags of the char before it ("/tag" up to the last non-empty one) and its boundary's mark;
+// the line's last char leaves its tags at the line's end.  A window's sizes are one prefix sum.
+__device__ __forceinline__ uint64_t partial_suffix(const WritePartialParams& P, uint64_t g, uint8_t* dst, uint64_t at) {
+    if (!P.tag_index) return 0;
+    const uint64_t t0 = P.tag_index[g];
+    uint64_t t1 = P.tag_index[g + 1];
+    while (t1 > t0 && P.span_off[t1] == P.span_off[t1 - 1]) --t1;   // up to the last Some
+    if (t1 <= t0) return 0;
+    const uint64_t b0 = P.span_off[t0], n = (t1 - t0) + (P.span_off[t1] - b0);
+    if (dst) {
+        uint64_t k = at;
+        for (uint64_t t = t0; t < t1; ++t) {
+            if (k < P.capacity) dst[k] = uint8_t('/');
+            ++k;
+            for (uint64_t q = P.span_off[t]; q < P.span_off[t + 1]; ++q, ++k)
+                if (k < P.capacity) dst[k] = P.tag_bytes[q];
+        }
+    }
+    return n;
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(kParseThreads) void write_partial_kernel(const WritePartialParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
+    for (uint64_t line = uint64_t(blockIdx.x) * (kParseThreads / 64) + (threadIdx.x >> 6); line < P.n_sent; line += n_waves) {
+        const uint64_t start = P.boff[line], end = P.boff[line + 1];
+        const int64_t len = end > start ? int64_t(end - start) : 0;
+        const uint64_t b0 = P.ooff[line], nb = P.ooff[line + 1] >= b0 ? P.ooff[line + 1] - b0 : 0, g0 = b0 + line;
+        const uint64_t out_at = kWrite ? P.out_off[line] : 0;
+        uint64_t chars = 0, bytes = 0;
+        uint32_t bad = len == 0 ? kErrEmptySentence : 0u;
+        for (int64_t w0 = 0; w0 < len; w0 += 64) {
+            const bool valid = w0 + int64_t(lane) < len;
+            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : 0x80u;
+            const bool lead = valid && (c & 0xC0u) != 0x80u;
+            const uint64_t leadm = __ballot(lead);
+            const uint64_t ci = chars + popc(leadm & lanes_below(lane));   // the lead's char of the line
+            // a char past what out_offsets promise reads no label and no tags (the line is reported: the offsets do not match the text)
+            const bool front = lead && ci > 0 && ci <= nb;
+            uint32_t lab = 0;
+            uint64_t sfx = 0;
+            if (front) {
+                lab = P.labels[b0 + ci - 1];
+                sfx = partial_suffix(P, g0 + ci - 1, nullptr, 0);
+            }
+            if (__ballot(lab > 2u)) bad |= kErrBadLabel;
+            const uint32_t mine = valid ? 1u + (front ? 1u + uint32_t(sfx) : 0u) : 0u;
+            const uint32_t incl = wave_inclusive_scan(mine);
+            if (kWrite && valid) {
+                uint64_t k = out_at + bytes + (incl - mine);
+                if (front) {
+                    partial_suffix(P, g0 + ci - 1, P.out, k);
+                    k += sfx;
+                    if (k < P.capacity) P.out[k] = uint8_t(lab == 0u ? '-' : lab == 1u ? '|' : ' ');
+                    ++k;
+                }
+                if (k < P.capacity) P.out[k] = uint8_t(c);
+            }
+            bytes += uint32_t(__shfl(int(incl), 63));
+            chars += popc(leadm);
+        }
+        if (len > 0 && chars != nb + 1) bad |= kErrBadOffsets;
+        if (lane == 0) {
+            if (!bad) bytes += partial_suffix(P, g0 + nb, kWrite ? P.out : nullptr, out_at + bytes);   // the last char's tags
+            if (!kWrite) {
+                P.out_off[line + 1] = bytes;
+                if (bad) atomicOr(P.status, bad);
+            }
+        }
+    }
+}
+
 // ---- evaluate
 
 // the record fill_tags left for flat char g (kernels.hpp, TagParams::records), or ~0; [lo, hi): the records of the run of sentences
@@ -264,6 +502,31 @@ hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hip
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(parse_tokenized_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_parse_partial(const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
+    hipLaunchKernelGGL(parse_partial_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    hipError_t e = hipGetLastError();
+    uint64_t* const counts[4] = {P.raw_off, P.ooff, P.tag_off, P.tb_off};
+    const uint64_t caps[4] = {P.raw_cap, P.label_cap, P.span_cap - 1, P.tb_cap};
+    const size_t part_bytes = scan_part_entries(P.n_sent) * sizeof(uint64_t);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
+        e = hipMemsetAsync(scan_part, 0, part_bytes, stream);
+        if (e == hipSuccess) e = launch_scan(counts[k], P.n_sent, scan_part, caps[k], P.status, nullptr, stream);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(parse_partial_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_write_partial(const WritePartialParams& P, uint64_t* scan_part, hipStream_t stream) {
+    hipLaunchKernelGGL(write_partial_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemsetAsync(scan_part, 0, scan_part_entries(P.n_sent) * sizeof(uint64_t), stream);
+    if (e == hipSuccess) e = launch_scan(P.out_off, P.n_sent, scan_part, P.capacity, P.status, nullptr, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(write_partial_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 Reads tokenized (--tok) and partially annotated (--part) corpora and word dictionaries (--dict), normalises them with
 KyteaFullwidthFilter unless --no-norm, trains the boundary model on the device (api.Trainer: features, ids and the TRON solver all
 run there) and writes the model un-compressed (the `evaluate` CLI reads it as it is; the reference writes zstd).  Progress goes to
-stderr as the reference prints it.  Tokenized lines are parsed by the library's parser (vpt_parse_tokenized_batch) in chunks.
+stderr as the reference prints it.  Tokenized and partially annotated lines are parsed by the library's batch parsers
+(vpt_parse_tokenized_batch, vpt_parse_partial_batch) in chunks.
 
 With --train-tags (ours) the tags of the corpora are kept and the tag models are trained on the device too (api.Trainer(train_tags=True):
 the parser's arrays go straight into add_packed_tagged), the dictionary lines become the tag dictionary (main.rs:131-157), and the
@@ -33,13 +34,14 @@ def _lines(path):
             raise CorpusError("%s: stream did not contain valid UTF-8" % path) from None
 
 
-def _parse_tokenized(path, lines, ignore_tags):
-    """Chunks of vpt_parse_tokenized_batch: yields (raw utf8, raw byte offsets, labels) per chunk; errors name the file and line."""
+def _parse_chunks(path, lines, ignore_tags, parse):
+    """Chunks of the library's batch parser `parse`: yields (raw utf8, raw byte offsets, labels, the parser's arrays) per chunk; errors name the
+    file and line."""
     from . import api
     for c0 in range(0, len(lines), _CHUNK_LINES):
         chunk = [ln.encode("utf-8") for ln in lines[c0:c0 + _CHUNK_LINES]]
         try:
-            p = api.parse_tokenized_host(chunk)
+            p = parse(chunk)
         except api.VaporettoError as e:
             msg = str(e)
             k = msg.rfind(" (line ")
@@ -63,18 +65,16 @@ def _parse_tokenized(path, lines, ignore_tags):
         yield p["raw"], p["raw_offsets"], p["labels"], p
 
 
-def _parse_partial(path, lines, ignore_tags):
+def _parse_tokenized(path, lines, ignore_tags):
+    """vpt_parse_tokenized_batch in chunks"""
     from . import api
-    sents = []
-    for i, ln in enumerate(lines):
-        try:
-            s = api.Sentence.from_partial_annotation(ln)
-        except api.VaporettoError as e:
-            raise CorpusError("%s:%d: %s" % (path, i + 1, e)) from None
-        if not ignore_tags and any(t is not None for t in s.tags()):
-            raise CorpusError("%s:%d: carries tags; tag models are not trained (--ignore-tags drops them, --train-tags trains them)" % (path, i + 1))
-        sents.append(s)
-    return sents
+    return _parse_chunks(path, lines, ignore_tags, api.parse_tokenized_host)
+
+
+def _parse_partial(path, lines, ignore_tags):
+    """vpt_parse_partial_batch in chunks: the same arrays, labels 0 / 1 / 2 and tags on any char"""
+    from . import api
+    return _parse_chunks(path, lines, ignore_tags, api.parse_partial_host)
 
 
 def main(argv=None) -> int:
@@ -116,13 +116,10 @@ def main(argv=None) -> int:
             print("# of sentences: %d" % n_sent, file=sys.stderr)
         for path in args.part:
             print("Loading %r ..." % path, file=sys.stderr)
-            sents = _parse_partial(path, _lines(path), skip_tags)
-            if sents and args.train_tags:
-                batches.append((sents, None, None, None))
-            elif sents:
-                utf8, boff = api.pack_texts([s.as_raw_text().encode("utf-8") for s in sents])
-                batches.append((utf8, boff, np.concatenate([np.asarray(s.boundaries(), np.uint8) for s in sents]), None))
-            n_sent += len(sents)
+            lines = _lines(path)
+            for raw, roff, labels, p in _parse_partial(path, lines, skip_tags):
+                batches.append((raw, roff, labels, p if args.train_tags else None))
+            n_sent += len(lines)
             print("# of sentences: %d" % n_sent, file=sys.stderr)
         words, tag_dictionary = set(), []
         for path in args.dict:
@@ -150,9 +147,7 @@ def main(argv=None) -> int:
         trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags,
                               train_tags=args.train_tags, tag_dictionary=tag_dictionary)
         for utf8, boff, labels, p in batches:
-            if boff is None:
-                trainer.add_examples(utf8, fullwidth=not args.no_norm)
-            elif p is not None:
+            if p is not None:
                 trainer.add_packed_tagged(utf8, boff, labels, p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"],
                                           fullwidth=not args.no_norm)
             else:
