@@ -176,8 +176,9 @@ def parse_buffers(S, cap, fill=0):
     return sizes, {k: devmem.put(np.full(sizes[k] + GUARD, fill, DTYPES[k])) for k in KEYS}
 
 
-def device_parse(ctx, lines, capacity=None, bufs=None, expect_error=None):
-    """-> the trimmed arrays, or None when the expected error came; the guard elements behind every buffer must be untouched"""
+def device_parse(ctx, lines, capacity=None, bufs=None, expect_error=None, kind="partial"):
+    """-> the trimmed arrays, or None when the expected error came; the guard elements behind every buffer must be untouched.  kind: "partial" or
+    "tokenized", the device parser that reads the lines"""
     lib, pred, batch = ctx
     utf8, boff = pack(lines)
     S, cap = len(lines), len(utf8) if capacity is None else capacity
@@ -185,7 +186,7 @@ def device_parse(ctx, lines, capacity=None, bufs=None, expect_error=None):
     sizes, own = parse_buffers(S, cap, fill)
     bufs = bufs or own
     d_text, d_boff = devmem.put(np.concatenate([utf8, np.zeros(16, np.uint8)])), devmem.put(boff)
-    st = lib.vpt_parse_partial_batch_device(pred, batch, d_text.ptr, d_boff.ptr, S, cap, *[bufs[k].ptr for k in KEYS], devmem.stream())
+    st = getattr(lib, "vpt_parse_%s_batch_device" % kind)(pred, batch, d_text.ptr, d_boff.ptr, S, cap, *[bufs[k].ptr for k in KEYS], devmem.stream())
     assert st == 0, lib.vpt_last_error()
     st = lib.vpt_batch_sync(batch)
     h = {k: bufs[k].get() for k in KEYS}

@@ -1,4 +1,4 @@
-"""Partial annotation on the CPU emulator (tests/native/hipemu): parse_partial_kernel / write_partial_kernel (kernels_parse.hip) and their host
+"""Partial annotation on the CPU emulator (tests/native/hipemu): parse_lines_kernel<PartialSyntax> / write_partial_kernel (kernels_parse.hip) and their host
 pipelines against the restatement -- the checks of tests/partialsuite.py."""
 import ctypes as C
 import gc

@@ -1,4 +1,4 @@
-"""Partial annotation on the MI355X: parse_partial_kernel / write_partial_kernel (kernels_parse.hip) through the C ABI and through
+"""Partial annotation on the MI355X: parse_lines_kernel<PartialSyntax> / write_partial_kernel (kernels_parse.hip) through the C ABI and through
 api.Predictor -- the checks of tests/partialsuite.py."""
 import numpy as np
 import pytest

@@ -1059,40 +1059,8 @@ class Predictor:
             _raise(st)
         return offsets_out, ends_out[:int(offsets_out[S])]
 
-    def parse_tokenized_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray) -> dict:
-        """Sentence::from_tokenized for a packed batch of tokenized lines, on the device (vpt_parse_tokenized_batch_device).  Returns
-        the arrays of parse_tokenized_host."""
-        import torch
-        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
-        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
-        S = len(byte_offsets) - 1
-        B = len(utf8)
-        dev = torch.device("cuda", self.device)
-
-        def d(n, dt):
-            return torch.zeros(max(n, 1), dtype=dt, device=dev)
-        d_text = torch.from_numpy(np.concatenate([utf8, np.zeros(1, np.uint8)])).to(dev)
-        d_boff = torch.from_numpy(byte_offsets.view(np.int64)).to(dev)
-        o = {"raw": d(B, torch.uint8), "raw_offsets": d(S + 1, torch.int64), "out_offsets": d(S + 1, torch.int64), "labels": d(B, torch.uint8),
-             "n_tags": d(S, torch.int32), "tag_index": d(B + 1, torch.int64), "span_offsets": d(B + 1, torch.int64), "tag_bytes": d(B, torch.uint8)}
-        batch = DeviceBatch(self)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        st = _lib.load().vpt_parse_tokenized_batch_device(
-            self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, o["raw"].data_ptr(), o["raw_offsets"].data_ptr(),
-            o["out_offsets"].data_ptr(), o["labels"].data_ptr(), o["n_tags"].data_ptr(), o["tag_index"].data_ptr(),
-            o["span_offsets"].data_ptr(), o["tag_bytes"].data_ptr(), stream)
-        if st != _lib.VPT_OK:
-            _raise(st)
-        batch.sync()
-        h = {k: v.cpu().numpy() for k, v in o.items()}
-        for k in ("raw_offsets", "out_offsets", "tag_index", "span_offsets"):
-            h[k] = h[k].view(np.uint64)
-        h["n_tags"] = h["n_tags"].view(np.uint32)[:S]
-        return _trim_parsed(h, S)
-
-    def parse_partial_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, capacity: Optional[int] = None) -> dict:
-        """Sentence::from_partial_annotation for a packed batch of partially annotated lines, on the device (vpt_parse_partial_batch_device).
-        Returns the arrays of parse_partial_host.  capacity: what the output buffers hold (default: the input's bytes)."""
+    def _parse_packed(self, entry, utf8: np.ndarray, byte_offsets: np.ndarray, capacity: Optional[int]) -> dict:
+        """One of the device parsers (`entry`: its C entry point) over a packed batch; capacity: what the output buffers hold."""
         import torch
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
@@ -1108,10 +1076,7 @@ class Predictor:
              "n_tags": d(S, torch.int32), "tag_index": d(B + 1, torch.int64), "span_offsets": d(B + 1, torch.int64), "tag_bytes": d(B, torch.uint8)}
         batch = DeviceBatch(self)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        st = _lib.load().vpt_parse_partial_batch_device(
-            self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, o["raw"].data_ptr(), o["raw_offsets"].data_ptr(),
-            o["out_offsets"].data_ptr(), o["labels"].data_ptr(), o["n_tags"].data_ptr(), o["tag_index"].data_ptr(),
-            o["span_offsets"].data_ptr(), o["tag_bytes"].data_ptr(), stream)
+        st = entry(self._h, batch._h, d_text.data_ptr(), d_boff.data_ptr(), S, B, *[o[k].data_ptr() for k in _PARSED_KEYS], stream)
         if st != _lib.VPT_OK:
             _raise(st)
         batch.sync()
@@ -1120,6 +1085,16 @@ class Predictor:
             h[k] = h[k].view(np.uint64)
         h["n_tags"] = h["n_tags"].view(np.uint32)[:S]
         return _trim_parsed(h, S)
+
+    def parse_tokenized_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray) -> dict:
+        """Sentence::from_tokenized for a packed batch of tokenized lines, on the device (vpt_parse_tokenized_batch_device).  Returns
+        the arrays of parse_tokenized_host."""
+        return self._parse_packed(_lib.load().vpt_parse_tokenized_batch_device, utf8, byte_offsets, None)
+
+    def parse_partial_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, capacity: Optional[int] = None) -> dict:
+        """Sentence::from_partial_annotation for a packed batch of partially annotated lines, on the device (vpt_parse_partial_batch_device).
+        Returns the arrays of parse_partial_host.  capacity: what the output buffers hold (default: the input's bytes)."""
+        return self._parse_packed(_lib.load().vpt_parse_partial_batch_device, utf8, byte_offsets, capacity)
 
     def write_partial_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                              n_tags: Optional[np.ndarray] = None, tag_index: Optional[np.ndarray] = None,
@@ -1441,35 +1416,32 @@ def _trim_parsed(h: dict, S: int) -> dict:
             "n_tags": h["n_tags"][:S], "tag_index": ti, "span_offsets": so, "tag_bytes": h["tag_bytes"][:int(so[n_t]) if S else 0]}
 
 
-def parse_tokenized_host(lines: Sequence[bytes]) -> dict:
-    """vpt_parse_tokenized_batch (host): tokenized lines -> {raw, raw_offsets, out_offsets, labels, n_tags, tag_index, span_offsets,
-    tag_bytes} as include/vaporetto_hip.h describes them."""
+_PARSED_KEYS = ("raw", "raw_offsets", "out_offsets", "labels", "n_tags", "tag_index", "span_offsets", "tag_bytes")
+
+
+def _parse_host(entry, lines: Sequence[bytes]) -> dict:
+    """One of the host parsers (`entry`: its C entry point) over lines."""
     utf8, boff = pack_texts(list(lines))
     S, B = len(lines), len(utf8)
     h = {"raw": np.zeros(max(B, 1), np.uint8), "raw_offsets": np.zeros(S + 1, np.uint64), "out_offsets": np.zeros(S + 1, np.uint64),
          "labels": np.zeros(max(B, 1), np.uint8), "n_tags": np.zeros(max(S, 1), np.uint32), "tag_index": np.zeros(B + 1, np.uint64),
          "span_offsets": np.zeros(B + 1, np.uint64), "tag_bytes": np.zeros(max(B, 1), np.uint8)}
     u = utf8 if B else np.zeros(1, np.uint8)
-    st = _lib.load().vpt_parse_tokenized_batch(u.ctypes.data, boff.ctypes.data, S, *[h[k].ctypes.data for k in
-                                               ("raw", "raw_offsets", "out_offsets", "labels", "n_tags", "tag_index", "span_offsets", "tag_bytes")])
+    st = entry(u.ctypes.data, boff.ctypes.data, S, *[h[k].ctypes.data for k in _PARSED_KEYS])
     if st != _lib.VPT_OK:
         _raise(st)
     return _trim_parsed(h, S)
+
+
+def parse_tokenized_host(lines: Sequence[bytes]) -> dict:
+    """vpt_parse_tokenized_batch (host): tokenized lines -> {raw, raw_offsets, out_offsets, labels, n_tags, tag_index, span_offsets,
+    tag_bytes} as include/vaporetto_hip.h describes them."""
+    return _parse_host(_lib.load().vpt_parse_tokenized_batch, lines)
 
 
 def parse_partial_host(lines: Sequence[bytes]) -> dict:
     """vpt_parse_partial_batch (host): partially annotated lines -> the arrays of parse_tokenized_host, labels 0 / 1 / 2 and tags on any char."""
-    utf8, boff = pack_texts(list(lines))
-    S, B = len(lines), len(utf8)
-    h = {"raw": np.zeros(max(B, 1), np.uint8), "raw_offsets": np.zeros(S + 1, np.uint64), "out_offsets": np.zeros(S + 1, np.uint64),
-         "labels": np.zeros(max(B, 1), np.uint8), "n_tags": np.zeros(max(S, 1), np.uint32), "tag_index": np.zeros(B + 1, np.uint64),
-         "span_offsets": np.zeros(B + 1, np.uint64), "tag_bytes": np.zeros(max(B, 1), np.uint8)}
-    u = utf8 if B else np.zeros(1, np.uint8)
-    st = _lib.load().vpt_parse_partial_batch(u.ctypes.data, boff.ctypes.data, S, *[h[k].ctypes.data for k in
-                                             ("raw", "raw_offsets", "out_offsets", "labels", "n_tags", "tag_index", "span_offsets", "tag_bytes")])
-    if st != _lib.VPT_OK:
-        _raise(st)
-    return _trim_parsed(h, S)
+    return _parse_host(_lib.load().vpt_parse_partial_batch, lines)
 
 
 def _partial_writer_args(utf8, byte_offsets, out_offsets, labels, n_tags, tag_index, span_offsets, tag_bytes) -> dict:

@@ -455,18 +455,18 @@ vpt_status cut_fail(vptcut::CutError e) {
     return status_from_bits(e == vptcut::CutError::kEmptySentence ? vpt::kErrEmptySentence : vpt::kErrBadOffsets);
 }
 
-// The device's verdict on tokenized text (kErrParse): the smallest failing line over the reason words (kernels.hpp), named with
-// parse_tokenized's message (sentence.rs:285-400); line_base: the first line of the call's batch.
+// A line that parse_tokenized rejects (sentence.rs:285-400): the reference's message for the kParseErr* reason and the batch's line.
+vpt_status parse_fail(uint32_t reason, uint64_t line) {
+    static const char* const msg[7] = {"", "must contain at least one character", "must not start with a whitespace", "must not contain consecutive whitespaces", "must not end with a whitespace", "a slash must follow a character", "must not contain NULL"};
+    return fail(VPT_INVALID_ARGUMENT, std::string("InvalidArgumentError: tokenized_text: ") + msg[reason] + " (line " + std::to_string(line) + ")");
+}
+// The device's verdict on tokenized text (kErrParse): the smallest failing line over the reason words (kernels.hpp); line_base: the first line of the call's batch.
 vpt_status parse_status(const uint32_t* ctrl, uint64_t line_base) {
-    static const char* const msg[7] = {"", "must contain at least one character", "must not start with a whitespace",
-                                       "must not contain consecutive whitespaces", "must not end with a whitespace",
-                                       "a slash must follow a character", "must not contain NULL"};
     uint32_t best = 0, reason = 0;
     for (uint32_t r = 1; r <= 6; ++r)
         if (ctrl[vpt::kParseErrWord + r] > best) { best = ctrl[vpt::kParseErrWord + r]; reason = r; }
     if (!reason) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tokenized_text: rejected");
-    return fail(VPT_INVALID_ARGUMENT, std::string("InvalidArgumentError: tokenized_text: ") + msg[reason] + " (line " +
-                                          std::to_string(line_base + (0xFFFFFFFFu - best)) + ")");
+    return parse_fail(reason, line_base + (0xFFFFFFFFu - best));
 }
 
 // A line that parse_partial_annotation rejects (sentence.rs:516-631): the reference's message and the batch's line.  offender: the code point of

@@ -5,15 +5,12 @@
 
 namespace {
 
-constexpr const char* kParseMsg[7] = {"", "must contain at least one character", "must not start with a whitespace",
-                                      "must not contain consecutive whitespaces", "must not end with a whitespace",
-                                      "a slash must follow a character", "must not contain NULL"};
-
 // One line of parse_tokenized (sentence.rs:285-400), byte by byte; appends to the outputs.  Returns 0 or the kParseErr* reason.
 struct HostParseOut {
     uint8_t *raw, *labels, *tag_bytes;
     uint64_t *tag_index, *span_off;
     uint64_t n_raw = 0, n_labels = 0, n_chars = 0, n_tags = 0, n_tb = 0;
+    std::string offender;   // parse_partial_line_host: the code point an invalid-boundary-character error names
 };
 uint32_t parse_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32_t* n_tags_out) {
     if (len == 0) return vpt::kParseErrNoChar;
@@ -56,8 +53,8 @@ uint32_t parse_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32
 }
 
 // One line of parse_partial_annotation (sentence.rs:516-631), code point by code point (a lead byte and the continuation bytes behind it); appends
-// to the outputs.  Returns 0 or the kPartialErr* reason; *offender: the code point an invalid-boundary-character error names.
-uint32_t parse_partial_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32_t* n_tags_out, std::string* offender) {
+// to the outputs.  Returns 0 or the kPartialErr* reason.
+uint32_t parse_partial_line_host(const uint8_t* t, uint64_t len, HostParseOut& o, uint32_t* n_tags_out) {
     if (len == 0) return vpt::kPartialErrNoChar;
     bool escape = false, is_char = true, in_tag = false;
     uint64_t chars = 0;
@@ -91,7 +88,7 @@ uint32_t parse_partial_line_host(const uint8_t* t, uint64_t len, HostParseOut& o
         }
         escape = false;
         if (!in_tag) {
-            offender->assign(reinterpret_cast<const char*>(t + k0), size_t(k - k0));
+            o.offender.assign(reinterpret_cast<const char*>(t + k0), size_t(k - k0));
             return vpt::kPartialErrChar;
         }
         for (uint64_t q = k0; q < k; ++q) o.tag_bytes[o.n_tb++] = t[q];
@@ -135,10 +132,33 @@ uint64_t write_partial_line_host(const HostPartialIn& in, uint64_t t0, uint64_t 
     return k - at;
 }
 
+// The host parsers' batch: the argument checks, the lines one after the other, the CSR arrays' last entries.  parse_line: one of the two above;
+// fail_line(reason, outputs, line): the reason it returned as the call's status and message.
+template <class ParseLine, class FailLine>
+vpt_status parse_batch_host(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, uint8_t* raw_out, uint64_t* raw_offsets_out,
+                            uint64_t* out_offsets_out, uint8_t* labels_out, uint32_t* n_tags_out, uint64_t* tag_index_out,
+                            uint64_t* span_offsets_out, uint8_t* tag_bytes_out, ParseLine parse_line, FailLine fail_line) {
+    if (!byte_offsets || !raw_offsets_out || !out_offsets_out || !tag_index_out || !span_offsets_out ||
+        (n_sentences && (!utf8 || !raw_out || !labels_out || !n_tags_out || !tag_bytes_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    HostParseOut o{raw_out, labels_out, tag_bytes_out, tag_index_out, span_offsets_out};
+    raw_offsets_out[0] = 0; out_offsets_out[0] = 0;
+    for (size_t i = 0; i < n_sentences; ++i) {
+        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+        const uint32_t r = parse_line(utf8 + byte_offsets[i], byte_offsets[i + 1] - byte_offsets[i], o, n_tags_out + i);
+        if (r) return fail_line(r, o, i);
+        raw_offsets_out[i + 1] = o.n_raw;
+        out_offsets_out[i + 1] = o.n_labels;
+    }
+    tag_index_out[o.n_chars] = o.n_tags;
+    span_offsets_out[o.n_tags] = o.n_tb;
+    return VPT_OK;
+}
+
 vpt_status parse_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets, size_t n_sentences,
                              uint64_t capacity, uint8_t* d_raw_out, uint64_t* d_raw_offsets_out, uint64_t* d_out_offsets_out, uint8_t* d_labels_out,
                              uint32_t* d_n_tags_out, uint64_t* d_tag_index_out, uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out,
-                             hipStream_t stream, bool partial = false) {
+                             hipStream_t stream, vpt::ParseKind kind) {
     if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
     if (n_sentences >= 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_sentences: at most 2^32-2 per call");
     if (!d_raw_offsets_out || !d_out_offsets_out || !d_tag_index_out || !d_span_offsets_out ||
@@ -163,7 +183,7 @@ vpt_status parse_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t
     P.tag_bytes = d_tag_bytes_out; P.tb_cap = capacity;
     P.tag_off = b->d_parse_tmp; P.tb_off = b->d_parse_tmp + n_sentences + 1;
     P.status = b->d_ctrl;
-    VPT_HIP(partial ? vpt::launch_parse_partial(P, b->d_scan_part, stream) : vpt::launch_parse_tokenized(P, b->d_scan_part, stream));
+    VPT_HIP(vpt::launch_parse(kind, P, b->d_scan_part, stream));
     b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
     return VPT_OK;
 }
@@ -231,21 +251,9 @@ size_t eval_layout(unsigned char* base, uint64_t bytes, uint64_t n, EvalLayout* 
 vpt_status vpt_parse_tokenized_batch(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, uint8_t* raw_out,
                                      uint64_t* raw_offsets_out, uint64_t* out_offsets_out, uint8_t* labels_out, uint32_t* n_tags_out,
                                      uint64_t* tag_index_out, uint64_t* span_offsets_out, uint8_t* tag_bytes_out) {
-    if (!byte_offsets || !raw_offsets_out || !out_offsets_out || !tag_index_out || !span_offsets_out ||
-        (n_sentences && (!utf8 || !raw_out || !labels_out || !n_tags_out || !tag_bytes_out)))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    HostParseOut o{raw_out, labels_out, tag_bytes_out, tag_index_out, span_offsets_out};
-    raw_offsets_out[0] = 0; out_offsets_out[0] = 0;
-    for (size_t i = 0; i < n_sentences; ++i) {
-        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
-        const uint32_t r = parse_line_host(utf8 + byte_offsets[i], byte_offsets[i + 1] - byte_offsets[i], o, n_tags_out + i);
-        if (r) return fail(VPT_INVALID_ARGUMENT, std::string("InvalidArgumentError: tokenized_text: ") + kParseMsg[r] + " (line " + std::to_string(i) + ")");
-        raw_offsets_out[i + 1] = o.n_raw;
-        out_offsets_out[i + 1] = o.n_labels;
-    }
-    tag_index_out[o.n_chars] = o.n_tags;
-    span_offsets_out[o.n_tags] = o.n_tb;
-    return VPT_OK;
+    return parse_batch_host(utf8, byte_offsets, n_sentences, raw_out, raw_offsets_out, out_offsets_out, labels_out, n_tags_out, tag_index_out,
+                            span_offsets_out, tag_bytes_out, parse_line_host,
+                            [](uint32_t reason, const HostParseOut&, uint64_t line) { return parse_fail(reason, line); });
 }
 
 vpt_status vpt_parse_tokenized_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
@@ -253,28 +261,16 @@ vpt_status vpt_parse_tokenized_batch_device(const vpt_predictor* p, vpt_batch* b
                                             uint64_t* d_out_offsets_out, uint8_t* d_labels_out, uint32_t* d_n_tags_out, uint64_t* d_tag_index_out,
                                             uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out, void* hip_stream) {
     return parse_device_impl(p, b, d_utf8, d_byte_offsets, n_sentences, capacity, d_raw_out, d_raw_offsets_out, d_out_offsets_out, d_labels_out,
-                             d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream));
+                             d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream),
+                             vpt::ParseKind::kTokenized);
 }
 
 vpt_status vpt_parse_partial_batch(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, uint8_t* raw_out,
                                    uint64_t* raw_offsets_out, uint64_t* out_offsets_out, uint8_t* labels_out, uint32_t* n_tags_out,
                                    uint64_t* tag_index_out, uint64_t* span_offsets_out, uint8_t* tag_bytes_out) {
-    if (!byte_offsets || !raw_offsets_out || !out_offsets_out || !tag_index_out || !span_offsets_out ||
-        (n_sentences && (!utf8 || !raw_out || !labels_out || !n_tags_out || !tag_bytes_out)))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    HostParseOut o{raw_out, labels_out, tag_bytes_out, tag_index_out, span_offsets_out};
-    raw_offsets_out[0] = 0; out_offsets_out[0] = 0;
-    std::string offender;
-    for (size_t i = 0; i < n_sentences; ++i) {
-        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
-        const uint32_t r = parse_partial_line_host(utf8 + byte_offsets[i], byte_offsets[i + 1] - byte_offsets[i], o, n_tags_out + i, &offender);
-        if (r) return partial_fail(r, offender, i);
-        raw_offsets_out[i + 1] = o.n_raw;
-        out_offsets_out[i + 1] = o.n_labels;
-    }
-    tag_index_out[o.n_chars] = o.n_tags;
-    span_offsets_out[o.n_tags] = o.n_tb;
-    return VPT_OK;
+    return parse_batch_host(utf8, byte_offsets, n_sentences, raw_out, raw_offsets_out, out_offsets_out, labels_out, n_tags_out, tag_index_out,
+                            span_offsets_out, tag_bytes_out, parse_partial_line_host,
+                            [](uint32_t reason, const HostParseOut& o, uint64_t line) { return partial_fail(reason, o.offender, line); });
 }
 
 vpt_status vpt_parse_partial_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
@@ -282,7 +278,8 @@ vpt_status vpt_parse_partial_batch_device(const vpt_predictor* p, vpt_batch* b, 
                                           uint64_t* d_out_offsets_out, uint8_t* d_labels_out, uint32_t* d_n_tags_out, uint64_t* d_tag_index_out,
                                           uint64_t* d_span_offsets_out, uint8_t* d_tag_bytes_out, void* hip_stream) {
     return parse_device_impl(p, b, d_utf8, d_byte_offsets, n_sentences, capacity, d_raw_out, d_raw_offsets_out, d_out_offsets_out, d_labels_out,
-                             d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream), true);
+                             d_n_tags_out, d_tag_index_out, d_span_offsets_out, d_tag_bytes_out, static_cast<hipStream_t>(hip_stream),
+                             vpt::ParseKind::kPartial);
 }
 
 vpt_status vpt_write_partial_batch(const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint64_t* out_offsets,
@@ -398,7 +395,7 @@ vpt_status vpt_evaluate_batch(const vpt_predictor* p, const uint8_t* utf8, const
         VPT_HIP(hipMemcpyAsync(L.text, utf8 + t0, size_t(nbytes), hipMemcpyHostToDevice, s));
         VPT_HIP(hipMemcpyAsync(L.boff, boff.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
         if ((st = parse_device_impl(p, b, L.text, L.boff, n, nbytes, L.raw, L.raw_off, L.ooff, L.gold, L.n_tags, L.tag_index, L.span_off,
-                                    L.tag_bytes, s)) != VPT_OK)
+                                    L.tag_bytes, s, vpt::ParseKind::kTokenized)) != VPT_OK)
             return st;
         // the parse's verdict before anything runs on what it wrote (a rejected line leaves no text to score), and the boundary total
         uint32_t ctrl[16] = {};

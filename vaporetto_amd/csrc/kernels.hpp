@@ -305,10 +305,13 @@ hipError_t launch_listing_offsets(const uint64_t* ooff, uint64_t n_sent, uint64_
 hipError_t launch_count_boundaries(const uint8_t* text, const uint64_t* boff, uint64_t n_sent, uint64_t* ooff_out, uint64_t* scan_part, uint32_t* status,
                                    uint32_t* max_chars, uint64_t text_bytes_hint, hipStream_t stream);
 
-// tokenized text -> raw text + gold labels + gold tags (kernels_parse.hip): Sentence::from_tokenized for a batch (sentence.rs:285-400).
+// annotated text -> raw text + labels + tags (kernels_parse.hip), one frame for two syntaxes:
+//   kTokenized  Sentence::from_tokenized (sentence.rs:285-400): labels 0 / 1, tags on a token's last char;
+//   kPartial    Sentence::from_partial_annotation (sentence.rs:516-631): labels 0 / 1 / 2, tags on any char.
 // Count pass: raw_off / ooff / tag_off / tb_off [line + 1] = the line's surface bytes / boundaries / tags / tag bytes, n_tags[line]; four
 // chained scans turn them into offsets; the write pass fills raw, labels, tag_index (first tag of every char, [chars + 1]), span_off
 // (first byte of every tag in tag_bytes, [tags + 1]) and tag_bytes (escapes removed).  *_cap: what the caller's buffers hold.
+enum class ParseKind { kTokenized, kPartial };
 struct ParseParams {
     const uint8_t* text;
     const uint64_t* boff;       // [S+1]
@@ -323,12 +326,9 @@ struct ParseParams {
     uint8_t* tag_bytes; uint64_t tb_cap;
     uint64_t* tag_off;          // [S+1] workspace: tags in front of every line
     uint64_t* tb_off;           // [S+1] workspace: tag bytes in front of every line
-    uint32_t* status;           // the workspace's status words (kErrParse + the reason words)
+    uint32_t* status;           // the workspace's status words (kErrParse / kErrParsePartial + the syntax's reason words)
 };
-hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
-// partially annotated text -> the same arrays (Sentence::from_partial_annotation, sentence.rs:516-631): labels 0 / 1 / 2, tags on any char.
-// The same two passes and four scans; a byte's role comes from a scan of state-transition maps over the window (kernels_parse.hip).
-hipError_t launch_parse_partial(const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
+hipError_t launch_parse(ParseKind kind, const ParseParams& P, uint64_t* scan_part, hipStream_t stream);
 // Sentence::write_partial_annotation_text for a batch (sentence.rs:907-944) from what the parsers write: a count pass (out_off[line + 1] = the
 // line's bytes), the chained scan, a write pass.  tag_index == nullptr: no tags.
 struct WritePartialParams {

@@ -1,18 +1,22 @@
-// Tokenized text in, gold labels out: Sentence::from_tokenized / parse_tokenized for a batch (sentence.rs:285-400), and the counters of the
-// `evaluate` CLI (evaluate/src/main.rs:91-193) over gold and system labels.
+// Annotated text in, labels and tags out: Sentence::from_tokenized / parse_tokenized (sentence.rs:285-400) and Sentence::from_partial_annotation
+// (sentence.rs:516-631) for a batch, the partial-annotation writer, and the counters of the `evaluate` CLI (evaluate/src/main.rs:91-193).
 //
-// parse_tokenized_kernel<kWrite>: a WAVE per line, the line walked in windows of 64 bytes, one byte a lane.  Every byte's part in the line
-// is a function of masks over the window (ballots) and of four positions carried from the windows before it:
+// parse_lines_kernel<Syntax, kWrite>: the frame of both parsers.  A WAVE per line, the line walked in windows of 64 bytes, one byte a lane.  A syntax
+// turns a window into each lane's roles (LaneRoles) and carries its own state from window to window; the frame owns the line loop, the counters
+// (surface bytes, chars, tags, tag bytes, the largest slot count), the stores and the error report.  kWrite == false counts and reports the first
+// error of the line; a chained scan of each count (kernels_emit.hip) places the lines; kWrite == true walks the line again and writes what it counted
+// where the scans put it.
+//
+// TokenizedSyntax: every byte's part in the line is a function of masks over the window (ballots) and of four positions carried from the windows
+// before it:
 //   escaped      the previous byte is an unescaped '\\' -- the parity of the run of '\\' in front of the byte: the highest non-'\\' lane
 //                below it, or the carried escape state when the run reaches the window's start;
 //   tag mode     the last unescaped '/' before the byte lies after the last unescaped ' ' (a tag runs to the next unescaped '/' or ' ');
 //   WordBoundary the last unescaped ' ' before a surface char lies after the last surface byte before it;
-//   slot         the unescaped '/' between a char's last surface byte and the '/' in question.
-// The ' ', '/' and '\\' bytes never occur inside a multi-byte UTF-8 sequence, so the byte-level formulation is exact.  kWrite == false
-// counts (surface bytes, chars, tags, tag bytes, the largest slot count) and reports the first error of the line; a chained scan of each
-// count (kernels_emit.hip) places the lines; kWrite == true walks the line again and writes what it counted where the scans put it.
+//   slot         the unescaped '/' between a char's last surface byte and the '/' in question (the frame counts them from the syntax's anchor mask).
+// The ' ', '/' and '\\' bytes never occur inside a multi-byte UTF-8 sequence, so the byte-level formulation is exact.
 //
-// parse_partial_kernel / write_partial_kernel: partially annotated text both ways (Sentence::from_partial_annotation, write_partial_annotation_text;
+// PartialSyntax / write_partial_kernel: partially annotated text both ways (Sentence::from_partial_annotation, write_partial_annotation_text;
 // sentence.rs:516-631, 907-944), described where they stand.
 //
 // evaluate_kernel: a wave per sentence over its boundaries, 64 a window.  The char metric is four popcounts.  Nagata's word metric
@@ -44,122 +48,63 @@ __device__ __forceinline__ int64_t last_in(uint64_t m, int64_t w0, int64_t carry
     return j >= 0 ? w0 + j : carry;
 }
 
-template <bool kWrite>
-__global__ __launch_bounds__(kParseThreads) void parse_tokenized_kernel(const ParseParams P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
-    for (uint64_t line = uint64_t(blockIdx.x) * (kParseThreads / 64) + (threadIdx.x >> 6); line < P.n_sent; line += n_waves) {
-        const uint64_t start = P.boff[line], end = P.boff[line + 1];
-        const int64_t len = end > start ? int64_t(end - start) : 0;
-        // bases of the line in the outputs (the write pass; the count pass leaves them at 0)
-        uint64_t raw_at = 0, lab_at = 0, char_at = 0, tag_at = 0, tb_at = 0;
-        if (kWrite) {
-            raw_at = P.raw_off[line];
-            lab_at = P.ooff[line];
-            char_at = P.ooff[line] + line;
-            tag_at = P.tag_off[line];
-            tb_at = P.tb_off[line];
-        }
-        int64_t last_sp = -1, last_sl = -1, last_surf = -1;
-        uint32_t esc_carry = 0, sl_since_surf = 0, n_tags = 0;
-        uint64_t raw = 0, chars = 0, tags = 0, tbytes = 0;
-        uint32_t err = 0;   // first error of the line: kParseErr* reason
-        for (int64_t w0 = 0; w0 < len; w0 += 64) {
-            const bool valid = w0 + int64_t(lane) < len;
-            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : 0x41u;
-            const uint64_t bs = __ballot(valid && c == '\\');
-            // escaped: the run of '\\' right in front of the lane is odd (through the window's start: the carried state)
-            const int jn = hi_lane(~bs & lanes_below(lane));
-            const uint32_t esc = jn >= 0 ? uint32_t(lane - 1u - uint32_t(jn)) & 1u : (lane & 1u) ^ esc_carry;
-            const bool is_sp = valid && c == ' ' && !esc, is_sl = valid && c == '/' && !esc, drop = valid && c == '\\' && !esc;
-            const bool content = valid && !is_sp && !is_sl && !drop;
-            const uint64_t spm = __ballot(is_sp), slm = __ballot(is_sl);
-            const int64_t lsp = last_below(spm, lane, w0, last_sp), lsl = last_below(slm, lane, w0, last_sl);
-            const bool in_tag = lsl > lsp;
-            const bool surf = content && !in_tag, tagb = content && in_tag;
-            const bool lead = surf && (c & 0xC0u) != 0x80u;
-            const uint64_t surfm = __ballot(surf), leadm = __ballot(lead), tagm = __ballot(tagb);
-            const int64_t lsurf = last_below(surfm, lane, w0, last_surf);
-            const bool has_surf = lsurf >= 0, prev_boundary = has_surf && lsp > lsurf;
-            // the slot of a '/': the '/' between the char's last surface byte and this one
-            const int js = hi_lane(surfm & lanes_below(lane));
-            const uint32_t slot = js >= 0 ? popc(slm & lanes_below(lane) & ~lanes_upto(uint32_t(js))) : sl_since_surf + popc(slm & lanes_below(lane));
-            // errors in the order parse_tokenized meets them (sentence.rs:308-354)
-            uint32_t e = 0;
-            if (valid && c == 0u) e = kParseErrNul;
-            else if (is_sp && !has_surf) e = kParseErrStartSpace;
-            else if (is_sp && prev_boundary) e = kParseErrDoubleSpace;
-            else if (is_sl && (!has_surf || prev_boundary)) e = kParseErrSlash;
-            const uint64_t errm = __ballot(e != 0);
-            if (errm && !err) err = uint32_t(__shfl(int(e), __builtin_ctzll(errm)));
-            if (!kWrite) {
-                n_tags = is_sl && slot + 1u > n_tags ? slot + 1u : n_tags;
-            } else {
-                const uint64_t below = lanes_below(lane);
-                if (surf) {
-                    const uint64_t k = raw_at + raw + popc(surfm & below);
-                    if (k < P.raw_cap) P.raw[k] = uint8_t(c);
-                }
-                if (lead) {
-                    const uint64_t ci = chars + popc(leadm & below);   // char of the line
-                    if (ci > 0 && lab_at + ci - 1 < P.label_cap) P.labels[lab_at + ci - 1] = prev_boundary ? 1u : 0u;
-                    if (char_at + ci < P.index_cap) P.tag_index[char_at + ci] = tag_at + tags + popc(slm & below);
-                }
-                if (is_sl) {
-                    const uint64_t k = tag_at + tags + popc(slm & below);
-                    if (k < P.span_cap) P.span_off[k] = tb_at + tbytes + popc(tagm & below);
-                }
-                if (tagb) {
-                    const uint64_t k = tb_at + tbytes + popc(tagm & below);
-                    if (k < P.tb_cap) P.tag_bytes[k] = uint8_t(c);
-                }
-            }
-            // carried to the next window
-            const uint32_t last_drop = uint32_t(__shfl(int(drop ? 1 : 0), 63));
-            esc_carry = last_drop;
-            if (surfm) {
-                const int h = hi_lane(surfm);
-                sl_since_surf = popc(slm & ~lanes_upto(uint32_t(h)));
-            } else {
-                sl_since_surf += popc(slm);
-            }
-            last_sp = last_in(spm, w0, last_sp);
-            last_sl = last_in(slm, w0, last_sl);
-            last_surf = last_in(surfm, w0, last_surf);
-            raw += popc(surfm);
-            chars += popc(leadm);
-            tags += popc(slm);
-            tbytes += popc(tagm);
-        }
-        if (!err) {
-            if (last_surf >= 0 && last_sp > last_surf) err = kParseErrEndSpace;
-            else if (chars == 0) err = kParseErrNoChar;
-        }
-        if (!kWrite) {
-            const uint32_t nt = wave_max(n_tags);
-            if (lane == 0) {
-                P.raw_off[line + 1] = raw;
-                P.ooff[line + 1] = chars ? chars - 1 : 0;
-                P.tag_off[line + 1] = tags;
-                P.tb_off[line + 1] = tbytes;
-                P.n_tags[line] = nt;
-                if (err) {
-                    atomicOr(P.status, kErrParse);
-                    atomicMax(P.status + kParseErrWord + err, 0xFFFFFFFFu - uint32_t(line));
-                }
-            }
-        } else if (lane == 0 && line + 1 == P.n_sent) {   // the CSR arrays' last entries
-            if (char_at + chars < P.index_cap) P.tag_index[char_at + chars] = tag_at + tags;
-            if (tag_at + tags < P.span_cap) P.span_off[tag_at + tags] = tb_at + tbytes;
-        }
+// What a syntax's window step says of its lane.  The masks the frame needs are ballots of these.
+struct LaneRoles {
+    bool raw, lead, opener, tagb;   // a surface byte, the lead byte of a surface char, a '/' that opens a tag, a tag byte
+    bool label;                     // stores the label of the boundary in front of char (chars + leads below): labels[ci - 1]
+    uint32_t label_value;
+    uint64_t anchorm;               // (the same in every lane) the lanes a '/' counts its slot from: the openers since the highest one below it
+    uint32_t err;                   // the reason this lane rejects the line for, or 0
+};
+
+// Tokenized text (sentence.rs:285-400): ballots and four carried positions, as the header describes.
+struct TokenizedSyntax {
+    static constexpr uint32_t kPad = 0x41u, kStatusBit = kErrParse, kErrWord = kParseErrWord;
+    struct Carry {
+        int64_t last_sp = -1, last_sl = -1, last_surf = -1;   // the last unescaped ' ', unescaped '/' and surface byte
+        uint32_t esc = 0;                                     // the window's last byte is an unescaped '\\'
+    };
+    // the lane's roles; leaves `carry` as the next window finds it
+    static __device__ __forceinline__ LaneRoles step(uint32_t c, bool valid, uint32_t lane, int64_t w0, Carry& carry) {
+        const uint64_t bs = __ballot(valid && c == '\\');
+        // escaped: the run of '\\' right in front of the lane is odd (through the window's start: the carried state)
+        const int jn = hi_lane(~bs & lanes_below(lane));
+        const uint32_t esc = jn >= 0 ? uint32_t(lane - 1u - uint32_t(jn)) & 1u : (lane & 1u) ^ carry.esc;
+        const bool is_sp = valid && c == ' ' && !esc, is_sl = valid && c == '/' && !esc, drop = valid && c == '\\' && !esc;
+        const bool content = valid && !is_sp && !is_sl && !drop;
+        const uint64_t spm = __ballot(is_sp), slm = __ballot(is_sl);
+        const int64_t lsp = last_below(spm, lane, w0, carry.last_sp), lsl = last_below(slm, lane, w0, carry.last_sl);
+        const bool in_tag = lsl > lsp;
+        const bool surf = content && !in_tag;
+        const uint64_t surfm = __ballot(surf);
+        const int64_t lsurf = last_below(surfm, lane, w0, carry.last_surf);
+        const bool has_surf = lsurf >= 0, prev_boundary = has_surf && lsp > lsurf;
+        LaneRoles r;
+        r.raw = surf; r.lead = surf && (c & 0xC0u) != 0x80u; r.opener = is_sl; r.tagb = content && in_tag;
+        r.label = r.lead; r.label_value = prev_boundary ? 1u : 0u;   // at a char's lead, for the boundary in front of it
+        r.anchorm = surfm;                                           // a tag's slot: the '/' since the char's last surface BYTE
+        // errors in the order parse_tokenized meets them (sentence.rs:308-354)
+        r.err = 0;
+        if (valid && c == 0u) r.err = kParseErrNul;
+        else if (is_sp && !has_surf) r.err = kParseErrStartSpace;
+        else if (is_sp && prev_boundary) r.err = kParseErrDoubleSpace;
+        else if (is_sl && (!has_surf || prev_boundary)) r.err = kParseErrSlash;
+        carry.esc = uint32_t(__shfl(int(drop ? 1 : 0), 63));
+        carry.last_sp = last_in(spm, w0, carry.last_sp);
+        carry.last_sl = last_in(slm, w0, carry.last_sl);
+        carry.last_surf = last_in(surfm, w0, carry.last_surf);
+        return r;
     }
-}
+    static __device__ __forceinline__ uint32_t end_error(const Carry& carry, int64_t, uint64_t chars) {
+        return carry.last_surf >= 0 && carry.last_sp > carry.last_surf ? kParseErrEndSpace : chars == 0 ? kParseErrNoChar : 0u;
+    }
+    static __device__ __forceinline__ void first_error(const ParseParams&, uint64_t, uint64_t, int64_t, int64_t, uint32_t, uint32_t) {}
+};
 
 // ---- partial annotation
 //
-// parse_partial_kernel<kWrite>: Sentence::from_partial_annotation (sentence.rs:516-631) in the frame of parse_tokenized_kernel.  What a byte IS depends
-// on the whole prefix here -- the code point behind a mark is a char whatever it is -- so the window step is a prefix scan of the transition maps of a
-// six-state machine over five input classes:
+// PartialSyntax: Sentence::from_partial_annotation (sentence.rs:516-631).  What a byte IS depends on the whole prefix here -- the code point behind a
+// mark is a char whatever it is -- so the window step is a prefix scan of the transition maps of a six-state machine over five input classes:
 //   states   E expect-char, A annotation, AE annotation behind a '\\', T tag, TE tag behind a '\\', X error (absorbing)
 //   classes  '\\', mark (' ' '-' '|'), '/', NUL, other
 // A map is 6 states x 3 bits in one word; a lead-byte lane holds the map of its class, a continuation byte the identity; composing two maps is six
@@ -193,13 +138,67 @@ __device__ __forceinline__ uint32_t wave_map_scan(uint32_t x) {
     return x;
 }
 
-template <bool kWrite>
-__global__ __launch_bounds__(kParseThreads) void parse_partial_kernel(const ParseParams P) {
+struct PartialSyntax {
+    static constexpr uint32_t kPad = 0x80u, kStatusBit = kErrParsePartial, kErrWord = kPartialErrWord;
+    struct Carry {
+        uint32_t state = kStE, open_role = 0;   // the state behind the window, the role of its last lead byte (0 none, 1 char, 2 tag)
+    };
+    static __device__ __forceinline__ LaneRoles step(uint32_t c, bool valid, uint32_t lane, int64_t w0, Carry& carry) {
+        // (a continuation byte that opens the line has no lead to belong to: it is one)
+        const bool lead = valid && ((c & 0xC0u) != 0x80u || w0 + int64_t(lane) == 0);
+        const bool is_bs = c == '\\', is_mark = c == ' ' || c == '-' || c == '|', is_sl = c == '/';
+        const uint32_t own = !lead ? kMapId : is_bs ? kMapBackslash : is_mark ? kMapMark : is_sl ? kMapSlash : c == 0u ? kMapNul : kMapOther;
+        const uint32_t incl = wave_map_scan(own);
+        const uint32_t after = (incl >> (3u * carry.state)) & 7u;
+        const uint32_t up = __shfl_up(after, 1u);
+        const uint32_t before = lane == 0 ? carry.state : up;
+        const bool annot = before == kStA || before == kStT;   // where '\\', marks and '/' mean something
+        const bool char_lead = lead && before == kStE && c != 0u;
+        const bool tag_lead = lead && (before == kStTE || (before == kStT && !is_bs && !is_mark && !is_sl));
+        const uint64_t leadm = __ballot(lead), clm = __ballot(char_lead), tlm = __ballot(tag_lead);
+        // a continuation byte: the role of the last lead below it
+        const int jl = hi_lane(leadm & lanes_below(lane));
+        const uint32_t role = lead ? (char_lead ? 1u : tag_lead ? 2u : 0u) : !valid ? 0u : jl >= 0 ? uint32_t((clm >> jl) & 1u) + 2u * uint32_t((tlm >> jl) & 1u) : carry.open_role;
+        LaneRoles r;
+        r.raw = role == 1u; r.lead = char_lead; r.opener = lead && annot && is_sl; r.tagb = role == 2u;
+        r.label = lead && annot && is_mark; r.label_value = c == '-' ? 0u : c == '|' ? 1u : 2u;   // at the mark, for the boundary behind the char in front of it
+        r.anchorm = clm;                                                                           // a tag's slot: the openers since the char's LEAD
+        // the lane that enters the error state: NUL where a char is expected, else a code point that is no annotation
+        r.err = lead && before != kStX && after == kStX ? (before == kStE ? kPartialErrNul : kPartialErrChar) : 0u;
+        carry.state = uint32_t(__shfl(int(after), 63));
+        if (leadm) {
+            const int h = hi_lane(leadm);
+            carry.open_role = uint32_t((clm >> h) & 1u) + 2u * uint32_t((tlm >> h) & 1u);
+        }
+        return r;
+    }
+    static __device__ __forceinline__ uint32_t end_error(const Carry& carry, int64_t len, uint64_t) {
+        return len == 0 ? kPartialErrNoChar : carry.state == kStE ? kPartialErrEnd : 0u;
+    }
+    // The write pass meets the line's first error at byte `at`.  The count pass has settled which line each reason names: the one kPartialErrChar names
+    // leaves its offender's bytes, the lead and the continuation bytes behind it (they may lie in the next window).
+    static __device__ __forceinline__ void first_error(const ParseParams& P, uint64_t line, uint64_t start, int64_t len, int64_t at, uint32_t err, uint32_t lane) {
+        if (err != kPartialErrChar || P.status[kPartialErrWord + kPartialErrChar] != 0xFFFFFFFFu - uint32_t(line)) return;
+        uint32_t bytes = P.text[start + uint64_t(at)];
+        for (int64_t k = 1; k < 4 && at + k < len; ++k) {
+            const uint32_t b = P.text[start + uint64_t(at + k)];
+            if ((b & 0xC0u) != 0x80u) break;
+            bytes |= b << (8 * k);
+        }
+        if (lane == 0) P.status[kPartialErrBytesWord] = bytes;
+    }
+};
+
+// The frame of both parsers: a wave per line, the line in windows of 64 bytes.  The syntax says what each byte is; the frame counts, places and stores.
+template <class Syntax, bool kWrite>
+__global__ __launch_bounds__(kParseThreads) void parse_lines_kernel(const ParseParams P) {
     const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = lanes_below(lane);
     const uint64_t n_waves = uint64_t(gridDim.x) * (kParseThreads / 64);
     for (uint64_t line = uint64_t(blockIdx.x) * (kParseThreads / 64) + (threadIdx.x >> 6); line < P.n_sent; line += n_waves) {
         const uint64_t start = P.boff[line], end = P.boff[line + 1];
         const int64_t len = end > start ? int64_t(end - start) : 0;
+        // bases of the line in the outputs (the write pass; the count pass leaves them at 0)
         uint64_t raw_at = 0, lab_at = 0, char_at = 0, tag_at = 0, tb_at = 0;
         if (kWrite) {
             raw_at = P.raw_off[line];
@@ -208,90 +207,52 @@ __global__ __launch_bounds__(kParseThreads) void parse_partial_kernel(const Pars
             tag_at = P.tag_off[line];
             tb_at = P.tb_off[line];
         }
-        // carried from window to window: the state, the role of the last lead byte (0 none, 1 char, 2 tag), the openers since the last char, the counters
-        uint32_t state = kStE, open_role = 0, open_since_char = 0, n_tags = 0;
+        typename Syntax::Carry carry;
+        uint32_t open_since_anchor = 0, n_tags = 0;   // the openers behind the last anchor lane; the line's largest slot count
         uint64_t raw = 0, chars = 0, tags = 0, tbytes = 0;
-        uint32_t err = 0, err_bytes = 0;   // first error of the line: kPartialErr* reason, and the offender's bytes
+        uint32_t err = 0;   // first error of the line: the syntax's reason
         for (int64_t w0 = 0; w0 < len; w0 += 64) {
             const bool valid = w0 + int64_t(lane) < len;
-            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : 0x80u;
-            // (a continuation byte that opens the line has no lead to belong to: it is one)
-            const bool lead = valid && ((c & 0xC0u) != 0x80u || w0 + int64_t(lane) == 0);
-            const bool is_bs = c == '\\', is_mark = c == ' ' || c == '-' || c == '|', is_sl = c == '/';
-            const uint32_t own = !lead ? kMapId : is_bs ? kMapBackslash : is_mark ? kMapMark : is_sl ? kMapSlash : c == 0u ? kMapNul : kMapOther;
-            const uint32_t incl = wave_map_scan(own);
-            const uint32_t after = (incl >> (3u * state)) & 7u;
-            const uint32_t up = __shfl_up(after, 1u);
-            const uint32_t before = lane == 0 ? state : up;
-            const bool annot = before == kStA || before == kStT;   // where '\\', marks and '/' mean something
-            const bool char_lead = lead && before == kStE && c != 0u;
-            const bool mark = lead && annot && is_mark, opener = lead && annot && is_sl;
-            const bool tag_lead = lead && (before == kStTE || (before == kStT && !is_bs && !is_mark && !is_sl));
-            const uint64_t leadm = __ballot(lead), clm = __ballot(char_lead), tlm = __ballot(tag_lead), openm = __ballot(opener);
-            const uint64_t below = lanes_below(lane);
-            // a continuation byte: the role of the last lead below it
-            const int jl = hi_lane(leadm & below);
-            const uint32_t role = lead ? (char_lead ? 1u : tag_lead ? 2u : 0u) : !valid ? 0u : jl >= 0 ? uint32_t((clm >> jl) & 1u) + 2u * uint32_t((tlm >> jl) & 1u) : open_role;
-            const uint64_t cbm = __ballot(role == 1u), tbm = __ballot(role == 2u);
-            // the first lane that enters the error state: NUL where a char is expected, else a code point that is no annotation
-            const uint64_t errm = __ballot(lead && before != kStX && after == kStX);
+            const uint32_t c = valid ? P.text[start + uint64_t(w0) + lane] : Syntax::kPad;
+            const LaneRoles r = Syntax::step(c, valid, lane, w0, carry);
+            const uint64_t rawm = __ballot(r.raw), leadm = __ballot(r.lead), openm = __ballot(r.opener), tagm = __ballot(r.tagb);
+            const uint64_t errm = __ballot(r.err != 0);
             if (errm && !err) {
                 const uint32_t f = uint32_t(__builtin_ctzll(errm));
-                err = uint32_t(__shfl(int(before), int(f))) == kStE ? kPartialErrNul : kPartialErrChar;
-                if (kWrite && err == kPartialErrChar) {   // its bytes: the lead and the continuation bytes behind it (they may lie in the next window)
-                    const int64_t at = w0 + int64_t(f);
-                    err_bytes = P.text[start + uint64_t(at)];
-                    for (int64_t k = 1; k < 4 && at + k < len; ++k) {
-                        const uint32_t b = P.text[start + uint64_t(at + k)];
-                        if ((b & 0xC0u) != 0x80u) break;
-                        err_bytes |= b << (8 * k);
-                    }
-                }
+                err = uint32_t(__shfl(int(r.err), int(f)));
+                if (kWrite) Syntax::first_error(P, line, start, len, w0 + int64_t(f), err, lane);
             }
-            // the slot of a '/': the openers between the char's lead and this one
-            const int jc = hi_lane(clm & below);
-            const uint32_t slot = jc >= 0 ? popc(openm & below & ~lanes_upto(uint32_t(jc))) : open_since_char + popc(openm & below);
             if (!kWrite) {
-                n_tags = opener && slot + 1u > n_tags ? slot + 1u : n_tags;
+                // the slot of a '/': the openers between the anchor below it and this one
+                const int ja = hi_lane(r.anchorm & below);
+                const uint32_t slot = ja >= 0 ? popc(openm & below & ~lanes_upto(uint32_t(ja))) : open_since_anchor + popc(openm & below);
+                n_tags = r.opener && slot + 1u > n_tags ? slot + 1u : n_tags;
             } else {
-                if (role == 1u) {
-                    const uint64_t k = raw_at + raw + popc(cbm & below);
+                const uint64_t ci = chars + popc(leadm & below);   // char of the line
+                if (r.raw) {
+                    const uint64_t k = raw_at + raw + popc(rawm & below);
                     if (k < P.raw_cap) P.raw[k] = uint8_t(c);
                 }
-                if (char_lead) {
-                    const uint64_t ci = chars + popc(clm & below);
-                    if (char_at + ci < P.index_cap) P.tag_index[char_at + ci] = tag_at + tags + popc(openm & below);
-                }
-                if (mark) {   // the boundary behind char ci - 1 (a mark only follows a char)
-                    const uint64_t ci = chars + popc(clm & below);
-                    if (lab_at + ci - 1 < P.label_cap) P.labels[lab_at + ci - 1] = c == '-' ? 0u : c == '|' ? 1u : 2u;
-                }
-                if (opener) {
+                if (r.lead && char_at + ci < P.index_cap) P.tag_index[char_at + ci] = tag_at + tags + popc(openm & below);
+                if (r.label && ci > 0 && lab_at + ci - 1 < P.label_cap) P.labels[lab_at + ci - 1] = uint8_t(r.label_value);
+                if (r.opener) {
                     const uint64_t k = tag_at + tags + popc(openm & below);
-                    if (k < P.span_cap) P.span_off[k] = tb_at + tbytes + popc(tbm & below);
+                    if (k < P.span_cap) P.span_off[k] = tb_at + tbytes + popc(tagm & below);
                 }
-                if (role == 2u) {
-                    const uint64_t k = tb_at + tbytes + popc(tbm & below);
+                if (r.tagb) {
+                    const uint64_t k = tb_at + tbytes + popc(tagm & below);
                     if (k < P.tb_cap) P.tag_bytes[k] = uint8_t(c);
                 }
             }
             // carried to the next window
-            state = uint32_t(__shfl(int(after), 63));
-            if (leadm) {
-                const int h = hi_lane(leadm);
-                open_role = uint32_t((clm >> h) & 1u) + 2u * uint32_t((tlm >> h) & 1u);
-            }
-            if (clm) open_since_char = popc(openm & ~lanes_upto(uint32_t(hi_lane(clm))));
-            else open_since_char += popc(openm);
-            raw += popc(cbm);
-            chars += popc(clm);
+            if (r.anchorm) open_since_anchor = popc(openm & ~lanes_upto(uint32_t(hi_lane(r.anchorm))));
+            else open_since_anchor += popc(openm);
+            raw += popc(rawm);
+            chars += popc(leadm);
             tags += popc(openm);
-            tbytes += popc(tbm);
+            tbytes += popc(tagm);
         }
-        if (!err) {
-            if (len == 0) err = kPartialErrNoChar;
-            else if (state == kStE) err = kPartialErrEnd;
-        }
+        if (!err) err = Syntax::end_error(carry, len, chars);   // what only the line's end tells
         if (!kWrite) {
             const uint32_t nt = wave_max(n_tags);
             if (lane == 0) {
@@ -301,17 +262,13 @@ __global__ __launch_bounds__(kParseThreads) void parse_partial_kernel(const Pars
                 P.tb_off[line + 1] = tbytes;
                 P.n_tags[line] = nt;
                 if (err) {
-                    atomicOr(P.status, kErrParsePartial);
-                    atomicMax(P.status + kPartialErrWord + err, 0xFFFFFFFFu - uint32_t(line));
+                    atomicOr(P.status, Syntax::kStatusBit);
+                    atomicMax(P.status + Syntax::kErrWord + err, 0xFFFFFFFFu - uint32_t(line));
                 }
             }
-        } else if (lane == 0) {
-            // the count pass has settled which line each reason names: the one kPartialErrChar names leaves its offender's bytes
-            if (err == kPartialErrChar && P.status[kPartialErrWord + kPartialErrChar] == 0xFFFFFFFFu - uint32_t(line)) P.status[kPartialErrBytesWord] = err_bytes;
-            if (line + 1 == P.n_sent) {   // the CSR arrays' last entries
-                if (char_at + chars < P.index_cap) P.tag_index[char_at + chars] = tag_at + tags;
-                if (tag_at + tags < P.span_cap) P.span_off[tag_at + tags] = tb_at + tbytes;
-            }
+        } else if (lane == 0 && line + 1 == P.n_sent) {   // the CSR arrays' last entries
+            if (char_at + chars < P.index_cap) P.tag_index[char_at + chars] = tag_at + tags;
+            if (tag_at + tags < P.span_cap) P.span_off[tag_at + tags] = tb_at + tbytes;
         }
     }
 }
@@ -487,44 +444,35 @@ uint32_t grid_for(uint64_t n) {
     return uint32_t(blocks < kParseMaxBlocks ? (blocks ? blocks : 1) : kParseMaxBlocks);
 }
 
-}  // namespace
+// zeroes the scan's partials, then the chained scan of counts[0 .. n] in place; a total above `cap` is kErrOutputTooSmall
+hipError_t scan_counts(uint64_t* counts, uint64_t n, uint64_t* scan_part, uint64_t cap, uint32_t* status, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(scan_part, 0, scan_part_entries(n) * sizeof(uint64_t), stream);
+    return e != hipSuccess ? e : launch_scan(counts, n, scan_part, cap, status, nullptr, stream);
+}
 
-hipError_t launch_parse_tokenized(const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
-    hipLaunchKernelGGL(parse_tokenized_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+template <class Syntax>
+hipError_t parse_with(const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
+    hipLaunchKernelGGL((parse_lines_kernel<Syntax, false>), dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
     hipError_t e = hipGetLastError();
     uint64_t* const counts[4] = {P.raw_off, P.ooff, P.tag_off, P.tb_off};
-    const size_t part_bytes = scan_part_entries(P.n_sent) * sizeof(uint64_t);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-        e = hipMemsetAsync(scan_part, 0, part_bytes, stream);
-        // the totals against what the caller's buffers hold: an output larger than them is kErrOutputTooSmall (the write pass stores nothing past them)
-        if (e == hipSuccess) e = launch_scan(counts[k], P.n_sent, scan_part, k == 1 ? P.label_cap : k == 0 ? P.raw_cap : k == 2 ? P.span_cap - 1 : P.tb_cap,
-                                             P.status, nullptr, stream);
-    }
+    // the totals against what the caller's buffers hold: an output larger than them is kErrOutputTooSmall (the write pass stores nothing past them)
+    const uint64_t caps[4] = {P.raw_cap, P.label_cap, P.span_cap - 1, P.tb_cap};
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = scan_counts(counts[k], P.n_sent, scan_part, caps[k], P.status, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(parse_tokenized_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
+    hipLaunchKernelGGL((parse_lines_kernel<Syntax, true>), dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
     return hipGetLastError();
 }
 
-hipError_t launch_parse_partial(const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
-    hipLaunchKernelGGL(parse_partial_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
-    hipError_t e = hipGetLastError();
-    uint64_t* const counts[4] = {P.raw_off, P.ooff, P.tag_off, P.tb_off};
-    const uint64_t caps[4] = {P.raw_cap, P.label_cap, P.span_cap - 1, P.tb_cap};
-    const size_t part_bytes = scan_part_entries(P.n_sent) * sizeof(uint64_t);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-        e = hipMemsetAsync(scan_part, 0, part_bytes, stream);
-        if (e == hipSuccess) e = launch_scan(counts[k], P.n_sent, scan_part, caps[k], P.status, nullptr, stream);
-    }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(parse_partial_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
-    return hipGetLastError();
+}  // namespace
+
+hipError_t launch_parse(ParseKind kind, const ParseParams& P, uint64_t* scan_part, hipStream_t stream) {
+    return kind == ParseKind::kPartial ? parse_with<PartialSyntax>(P, scan_part, stream) : parse_with<TokenizedSyntax>(P, scan_part, stream);
 }
 
 hipError_t launch_write_partial(const WritePartialParams& P, uint64_t* scan_part, hipStream_t stream) {
     hipLaunchKernelGGL(write_partial_kernel<false>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemsetAsync(scan_part, 0, scan_part_entries(P.n_sent) * sizeof(uint64_t), stream);
-    if (e == hipSuccess) e = launch_scan(P.out_off, P.n_sent, scan_part, P.capacity, P.status, nullptr, stream);
+    if (e == hipSuccess) e = scan_counts(P.out_off, P.n_sent, scan_part, P.capacity, P.status, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(write_partial_kernel<true>, dim3(grid_for(P.n_sent)), dim3(kParseThreads), 0, stream, P);
     return hipGetLastError();
