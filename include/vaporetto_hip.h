@@ -664,6 +664,14 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * Solvers: 0 (L2R_LR) and 2 (L2R_L2LOSS_SVC), the primal TRON solvers of liblinear as scikit-learn bundles it (CG without a
  * preconditioner): the reference's newer liblinear preconditions its CG, so weights agree with it to the stopping tolerance, not bit
  * for bit.  Sums run in a fixed order: the same examples and arguments give byte-identical models on every run.
+ * Solver 5 (L1R_L2LOSS_SVC, the one the reference's README trains with) is opt-in: a trainer created with VPT_TRAIN_L1R in
+ * params->flags also accepts solver == 5 and then runs liblinear's coordinate descent (solve_l1r_l2_svc) on the device, a launch per
+ * group of columns that share no row (the columns of one template (kind, n-gram length, rel_position); every dictionary column and the
+ * bias alone), the groups in a new seeded order every sweep, without shrinking, stopping by liblinear's rule (the sweep's violation sum
+ * <= eps * max(min(pos, neg), 1) / rows * the first sweep's) or after 1000 sweeps.  Weights that end at exactly 0 are not written, so
+ * the model is sparse.  Without the flag solver 5 is refused as below; with it solvers 0 and 2 train exactly as without it, solvers 1,
+ * 3, 4, 6, 7 are VPT_INVALID_ARGUMENT "solver: only 0, 2 and 5 are implemented", and solver 5 together with VPT_TRAIN_TAGS is
+ * VPT_INVALID_ARGUMENT "solver 5: tag models are trained with solvers 0 and 2 only".
  * Divergences: tag models are trained only by a trainer created with VPT_TRAIN_TAGS (below), without it the caller rejects or drops tags
  * (the train CLI's --ignore-tags); solvers 1, 3-7 are
  * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
@@ -680,7 +688,7 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * are assigned, about 52 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
- *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0 or VPT_TRAIN_TAGS (any other bit is
+ *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0, VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both (any other bit is
  *   VPT_INVALID_ARGUMENT "flags: ...").
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
@@ -695,12 +703,15 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * vpt_trainer_weights: after train, the fp64 weights of the features in key order, the bias, and the keys (two words each, low first:
  *   kind << 120 | c0 << 99 | c1 << 78 | c2 << 57 | c3 << 36 | c4 << 15 | length << 5 | (rel_position + 16), kind 0 char, 1 type
  *   (c = CharacterType values), 2 dictionary (c0 = min(length, dictn), c1 = 0 Left / 1 Inside / 2 Right, no length or position)).
- * vpt_trainer_last_stats: TRON iterations, CG steps, the gradient norms at w = 0 and at the result, and the objective. */
+ * vpt_trainer_last_stats: TRON iterations, CG steps, the gradient norms at w = 0 and at the result, and the objective.  After solver 5
+ *   the same layout holds: iterations = sweeps, cg_steps = line-search halvings (each follows a pass over the column's data; a step
+ *   that the data-free test accepts costs none), gnorm0 / gnorm = the first and the last sweep's violation sums, objective =
+ *   |w|_1 + C sum max(0, 1 - y w.x)^2, the bias inside the norm as liblinear has it. */
 typedef struct vpt_train_params {
     uint32_t charw, charn, typew, typen, dictn;
-    uint32_t flags; /* 0 or VPT_TRAIN_TAGS */
+    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R */
 } vpt_train_params;
-enum { VPT_TRAIN_TAGS = 1 };
+enum { VPT_TRAIN_TAGS = 1, VPT_TRAIN_L1R = 4 /* bit 1 stays an unknown flag */ };
 typedef struct vpt_train_stats {
     uint32_t iterations;
     uint32_t cg_steps;

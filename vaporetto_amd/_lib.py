@@ -49,6 +49,7 @@ class TrainStats(C.Structure):
 
 
 VPT_TRAIN_TAGS = 1
+VPT_TRAIN_L1R = 4
 
 
 class TagProblemInfo(C.Structure):

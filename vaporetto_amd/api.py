@@ -1613,7 +1613,7 @@ def model_inspect(model_bytes: bytes, predict_tags: bool = False) -> dict:
     return mi.as_dict()
 
 
-class SolverType(enum.IntEnum):  # trainer.rs:20-45; only the primal TRON solvers 0 and 2 are implemented
+class SolverType(enum.IntEnum):  # trainer.rs:20-45; the primal TRON solvers 0 and 2 and, on a Trainer(l1r=True), solver 5 are implemented
     L2RegularizedLogistic = 0
     L2RegularizedL2LossSVCDual = 1
     L2RegularizedL2LossSVC = 2
@@ -1629,10 +1629,12 @@ class Trainer:
     carries a tag is an error unless `ignore_tags` is set, which drops the tags (the train CLI's --ignore-tags) and writes a model
     without tag models.  With `train_tags=True` the tags are kept and the tag models are trained too (tag_trainer.rs);
     `tag_dictionary` is then the reference's tag dictionary: tagged Sentences, or (surface, tags) pairs, whose first occurrence of a
-    surface gives the tags of a surface the corpus does not contain."""
+    surface gives the tags of a surface the corpus does not contain.  With `l1r=True` (VPT_TRAIN_L1R) train also accepts
+    SolverType.L1RegularizedL2LossSVC, the solver the reference's README trains with: most weights end at exactly 0 and are not written.
+    Solvers 0 and 2 train as without it; tag models are not trained with solver 5."""
 
     def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
-                 ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = ()):
+                 ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = (), l1r: bool = False):
         if ignore_tags and train_tags:
             raise ValueError("ignore_tags and train_tags exclude each other")
         if tag_dictionary and not train_tags:
@@ -1643,7 +1645,8 @@ class Trainer:
         self._h = C.c_void_p()
         self._charw, self._typew = charw, typew
         self.dict_words = list(dict_words)
-        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, _lib.VPT_TRAIN_TAGS if train_tags else 0)
+        self.l1r = bool(l1r)
+        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, (_lib.VPT_TRAIN_TAGS if train_tags else 0) | (_lib.VPT_TRAIN_L1R if l1r else 0))
         utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
         st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
         if st != _lib.VPT_OK:

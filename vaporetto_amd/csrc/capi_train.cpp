@@ -1,4 +1,5 @@
-// C ABI of libvaporetto_hip.so, boundary-model training: Trainer (vaporetto/src/trainer.rs) with the liblinear TRON solvers 0 and 2.
+// C ABI of libvaporetto_hip.so, boundary-model training: Trainer (vaporetto/src/trainer.rs) with the liblinear TRON solvers 0 and 2 and,
+// on a trainer created with VPT_TRAIN_L1R, the coordinate descent of solver 5 by column groups (solve_l1r, l1r.h).
 //
 // The vpt_trainer handle keeps every example's feature keys and label on the device (kernels_train.hip); feature ids, the CSR and CSC
 // copies of the design matrix are made when they are first needed after an add, and the TRON / CG loop runs here, on the host, over
@@ -7,6 +8,7 @@
 // preconditions its CG and reaches the same optimum by another path, so weights agree with it only to the stopping tolerance.
 // Quantisation and the model layout are trainer.rs:352-487; the encoder mirrors vaporetto_amd/modelfmt.encode_model (model.rs:99-104).
 #include "capi_internal.hpp"
+#include "l1r.h"
 #include "tron.h"
 
 #include <chrono>
@@ -418,6 +420,119 @@ struct Tron {
         add_xtv(x, zt.p, out);
     }
 };
+
+// ---------------------------------------------------------------------------------------------------- solver 5 (l1r.h)
+// The column groups of a sweep: the char and type columns by template (kind, n-gram length, rel_position) in that order -- a boundary
+// has exactly one n-gram of a template, with count 1, so the columns of a template share no row --, then every dictionary column and
+// the bias (column nd) alone: those can share rows.  A group's columns stand by length class, as train_l1r_group takes them.
+struct L1rGroups {
+    std::vector<uint32_t> cols;
+    std::vector<uint64_t> ptr{0};
+    std::vector<uint32_t> n_lane, n_wave;
+    size_t size() const { return n_lane.size(); }
+};
+L1rGroups l1r_groups(const std::vector<uint64_t>& keys, const std::vector<uint64_t>& cptr, uint64_t nd) {
+    std::map<uint32_t, std::vector<uint32_t>> tpl;
+    std::vector<uint32_t> alone;
+    for (uint64_t j = 0; j < nd; ++j) {
+        const vpt::TrainKey k = vpt::train_key(keys[2 * j], keys[2 * j + 1]);
+        if (k.kind == 2) alone.push_back(uint32_t(j));
+        else tpl[(k.kind << 16) | (k.len << 8) | uint32_t(k.rel + 16)].push_back(uint32_t(j));
+    }
+    alone.push_back(uint32_t(nd));
+    L1rGroups G;
+    auto push = [&](const std::vector<uint32_t>& g) {
+        auto len = [&](uint32_t j) { return j == nd ? ~uint64_t(0) : cptr[j + 1] - cptr[j]; };
+        uint32_t cnt[2] = {0, 0};
+        for (int cls = 0; cls < 3; ++cls)
+            for (uint32_t j : g) {
+                const uint64_t n = len(j);
+                if ((n <= vpt::kL1rLaneMax ? 0 : n <= vpt::kL1rWaveMax ? 1 : 2) != cls) continue;
+                G.cols.push_back(j);
+                if (cls < 2) ++cnt[cls];
+            }
+        G.ptr.push_back(G.cols.size());
+        G.n_lane.push_back(cnt[0]);
+        G.n_wave.push_back(cnt[1]);
+    };
+    for (auto& kv : tpl) push(kv.second);
+    for (uint32_t j : alone) push({j});
+    return G;
+}
+
+// solve_l1r_l2_svc from w = 0 by groups: a launch per group, the groups permuted anew per sweep (l1r.h), the columns' violations summed
+// in a fixed order and read back once per sweep: the only readback of a sweep.  The weights come back into t->w, the stats into t->stats:
+// sweeps, halvings, the first and last sweep's violation sums, and |w|_1 + C sum max(0, b)^2 with b recomputed from w.
+vpt_status solve_l1r(vpt_trainer* t, const std::vector<double>& y, uint64_t pos, const std::vector<uint64_t>& keys, double eps, double cost) {
+    const Matrix& M = t->m;
+    hipStream_t st = t->st;
+    const uint64_t nd = M.nd, nr = t->nrows, n = nd + 1;
+    std::vector<uint64_t> cptr(nd + 1);
+    VPT_HIP(hipMemcpy(cptr.data(), M.cptr.p, (nd + 1) * 8, hipMemcpyDeviceToHost));
+    const L1rGroups G = l1r_groups(keys, cptr, nd);
+#if defined(VPT_HIPEMU) || defined(VPT_DEBUG)
+    {   // what the launches rest on: no row twice in a group
+        std::vector<uint32_t> crow(M.nnz), seen(nr, ~uint32_t(0));
+        if (M.nnz) VPT_HIP(hipMemcpy(crow.data(), M.crow.p, M.nnz * 4, hipMemcpyDeviceToHost));
+        for (size_t g = 0; g < G.size(); ++g)
+            for (uint64_t q = G.ptr[g]; q < G.ptr[g + 1]; ++q) {
+                const uint32_t j = G.cols[q];
+                if (j == nd) continue;   // the bias is alone
+                for (uint64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
+                    if (seen[crow[k]] == uint32_t(g)) return fail(VPT_RUNTIME_ERROR, "solver 5: a row occurs twice in a column group");
+                    seen[crow[k]] = uint32_t(g);
+                }
+            }
+    }
+#endif
+    Tron T;   // its vectors and its reductions: w, y, b (in gz), xj_sq (in s), the violations (in g)
+    VPT_TRY(T.init(M, st, nr, 2, cost));
+    DBuf<uint32_t> d_cols, d_halv;
+    DBuf<vpt::L1rPair> tile0, tile1;
+    VPT_HIP(d_cols.resize(G.cols.size())); VPT_HIP(d_halv.resize(1));
+    VPT_HIP(tile0.resize(vpt::train_l1r_scratch(M.nnz, nr, nd, 0))); VPT_HIP(tile1.resize(vpt::train_l1r_scratch(M.nnz, nr, nd, 1)));
+    const std::vector<double> ones(nr, 1.0);
+    VPT_HIP(hipMemcpy(T.y.p, y.data(), nr * 8, hipMemcpyHostToDevice));
+    VPT_HIP(hipMemcpy(T.gz.p, ones.data(), nr * 8, hipMemcpyHostToDevice));
+    VPT_HIP(hipMemcpy(d_cols.p, G.cols.data(), G.cols.size() * 4, hipMemcpyHostToDevice));
+    VPT_HIP(hipMemsetAsync(T.w.p, 0, n * 8, st));
+    VPT_HIP(hipMemsetAsync(d_halv.p, 0, 4, st));
+    vpt::L1rParams P{};
+    P.cptr = M.cptr.p; P.crow = M.crow.p; P.cval = M.cval.p; P.nd = nd; P.nr = nr; P.nnz = M.nnz;
+    P.y = T.y.p; P.b = T.gz.p; P.w = T.w.p; P.xj_sq = T.s.p; P.viol = T.g.p; P.halvings = d_halv.p; P.tile0 = tile0.p; P.tile1 = tile1.p; P.c = cost;
+    auto launch = [&](size_t g, bool init) {
+        const uint32_t total = uint32_t(G.ptr[g + 1] - G.ptr[g]);
+        return vpt::train_l1r_group(P, init, d_cols.p + G.ptr[g], G.n_lane[g], G.n_wave[g], total - G.n_lane[g] - G.n_wave[g], st);
+    };
+    for (size_t g = 0; g < G.size(); ++g) VPT_HIP(launch(g, true));
+    const double tol = vpt::tron_tolerance(eps, double(pos), double(nr));
+    std::vector<uint32_t> order(G.size());
+    for (size_t g = 0; g < G.size(); ++g) order[g] = uint32_t(g);
+    uint64_t rng = vpt::kL1rSeed;
+    double v0 = 0, v = 0;
+    uint32_t sweeps = 0;
+    while (sweeps < uint32_t(vpt::kL1rMaxSweeps)) {
+        vpt::l1r_shuffle(order.data(), uint32_t(order.size()), &rng);
+        for (uint32_t g : order) VPT_HIP(launch(g, false));
+        v = T.dot(T.g.p, nullptr, n);
+        VPT_HIP(T.err);
+        if (sweeps++ == 0) v0 = v;
+        if (v <= tol * v0) break;
+    }
+    uint32_t halvings = 0;
+    t->w.resize(n);
+    VPT_HIP(hipMemcpyAsync(&halvings, d_halv.p, 4, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(t->w.data(), T.w.p, n * 8, hipMemcpyDeviceToHost, st));
+    // the loss at the weights themselves, not at the b the sweeps carried along
+    VPT_HIP(vpt::train_xv(M.csr_ptr.p, M.cols.p, M.vals.p, nr, T.w.p, nd, T.z.p, st));
+    VPT_HIP(vpt::train_loss(nr, T.z.p, T.y.p, cost, 2, T.loss.p, st));
+    const double loss = T.dot(T.loss.p, nullptr, nr);
+    VPT_HIP(T.err);
+    double norm1 = 0;
+    for (double x : t->w) norm1 += std::fabs(x);
+    t->stats = vpt_train_stats{sweeps, halvings, v0, v, norm1 + loss};
+    return VPT_OK;
+}
 
 void encode_tag_models(vpt_trainer* t, Enc& e);
 
@@ -1028,7 +1143,7 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     if (p.charw > 16) return fail_arg("charw: must be at most 16");
     if (p.typew > 16) return fail_arg("typew: must be at most 16");
     if (p.typew > p.charw) return fail_arg("typew: must not exceed charw (type weights use the char window)");
-    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS)) != 0) return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS");
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R)) != 0) return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
     if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail_arg("dictn: must be at least 1 with a dictionary");
     std::unique_ptr<vpt_trainer> t(new (std::nothrow) vpt_trainer());
     if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
@@ -1144,7 +1259,10 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     double ec[2];
     std::memcpy(ec, eps_cost, sizeof ec);
     const double eps = ec[0], cost = ec[1];
-    if (solver != 0 && solver != 2) return fail_arg("solver: only 0 and 2 are implemented");
+    const bool l1r = (t->prm.flags & VPT_TRAIN_L1R) != 0;
+    if (!l1r && solver != 0 && solver != 2) return fail_arg("solver: only 0 and 2 are implemented");
+    if (l1r && solver != 0 && solver != 2 && solver != 5) return fail_arg("solver: only 0, 2 and 5 are implemented");
+    if (solver == 5 && (t->prm.flags & VPT_TRAIN_TAGS)) return fail_arg("solver 5: tag models are trained with solvers 0 and 2 only");
     if (!(eps > 0) || !(cost > 0)) return fail_arg("eps and cost: must be positive");
     VPT_HIP(hipSetDevice(t->device));
     t->trained = false;
@@ -1161,12 +1279,16 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     }
     if (pos == 0 || pos == nr)
         return fail_arg("examples: need both WordBoundary and other boundaries");
-    Tron T;
-    VPT_TRY(T.init(t->m, t->st, nr, solver, cost));
-    t->w.resize(T.n);
-    VPT_TRY(T.solve(y, pos, eps, &t->stats, t->w.data()));
     std::vector<uint64_t> keys(2 * nd);
     if (nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
+    if (solver == 5) {
+        VPT_TRY(solve_l1r(t, y, pos, keys, eps, cost));
+    } else {
+        Tron T;
+        VPT_TRY(T.init(t->m, t->st, nr, solver, cost));
+        t->w.resize(T.n);
+        VPT_TRY(T.solve(y, pos, eps, &t->stats, t->w.data()));
+    }
     if (t->prm.flags & VPT_TRAIN_TAGS) {
         VPT_TRY(build_tags(t));
         VPT_TRY(solve_tags(t, eps, cost, solver));

@@ -474,6 +474,28 @@ hipError_t train_scale_rows(uint64_t n, const double* d, double* t, hipStream_t 
 hipError_t train_loss(uint64_t n, const double* z, const double* y, double c, int solver, double* loss, hipStream_t st);
 hipError_t train_grad_rows(uint64_t n, const double* z, const double* y, double c, int solver, double* gz, double* D, hipStream_t st);
 
+// solver 5 (kernels_train_l1.hip): coordinate descent over a group of columns that share no row, one launch a group
+constexpr uint32_t kL1rLaneMax = 64;     // nonzeros of a column a lane takes; a wave takes one of at most kL1rWaveMax, a workgroup a longer one
+constexpr uint32_t kL1rWaveMax = 1024;   // (picked, not measured)
+struct L1rPair;
+struct L1rParams {
+    const uint64_t* cptr;       // the CSC copy of the design matrix; column nd is the bias: every row, value 1
+    const uint32_t* crow;
+    const uint16_t* cval;
+    uint64_t nd, nr, nnz;
+    const double* y;            // [nr] +1 / -1
+    double* b;                  // [nr] 1 - y w.x
+    double* w;                  // [nd + 1]
+    double* xj_sq;              // [nd + 1] C sum x^2 (written by the init launch)
+    double* viol;               // [nd + 1] the columns' violations of this sweep
+    uint32_t* halvings;         // one counter over the training
+    L1rPair *tile0, *tile1;     // the workgroups' level sums: train_l1r_scratch(.., 0) and (.., 1) elements
+    double c;
+};
+uint64_t train_l1r_scratch(uint64_t nnz, uint64_t nr, uint64_t nd, int level);
+// cols[0 .. n_lane + n_wave + n_block): the group's columns in that order of length class; init: xj_sq alone
+hipError_t train_l1r_group(const L1rParams& P, bool init, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block, hipStream_t st);
+
 // tag-model training (kernels_train_tags.hip)
 struct TagFeatParams {
     const uint32_t* cps;        // decode_chars' words: sentence i's char c at ooff[i] + i + c
