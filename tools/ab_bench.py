@@ -28,6 +28,68 @@ def lib_path(name):
     return os.path.join(ROOT, "tools", "prebuilt", "libvaporetto_%s.so" % name)
 
 
+def interleaved(args, by_lib, raw, name, S, nb, max_bytes, ooff, d_text, d_boff, d_ooff, stream, o_scores, o_labels, dev):
+    import gc
+    import torch
+    from vaporetto_amd import _lib, api
+    for k in KNOBS:
+        os.environ.pop(k, None)
+    d_scores = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+    d_labels = torch.zeros(nb + 1, dtype=torch.uint8, device=dev)
+    libs = {}
+    for libname, envs in by_lib.items():
+        path = lib_path(libname)
+        if not os.path.exists(path) or any(env for _, env in envs):
+            print(json.dumps({"variant": libname, "error": "missing " + path if not os.path.exists(path) else "--interleave takes no knobs"}), flush=True)
+            continue
+        L = C.CDLL(path)
+        for fn_name, (res, argt) in _lib.SIGNATURES.items():
+            if hasattr(L, fn_name):
+                fn = getattr(L, fn_name)
+                fn.restype = res
+                fn.argtypes = argt
+        _lib._lib = L   # every handle of a library is made, used and destroyed with that library in place
+        pred = api.Predictor(api.Model.read_slice(raw)[0], False, device=0)
+        batch = api.DeviceBatch(pred, timing=True)
+        batch.set_max_sentence_chars(int(np.max(np.diff(ooff.astype(np.int64)))) + 1)
+        libs[libname] = [L, pred, batch]
+    results = {}
+    for rnd in range(args.rounds):
+        for libname, (L, pred, batch) in libs.items():
+            _lib._lib = L
+
+            def step():
+                batch.predict(d_text.data_ptr(), d_boff.data_ptr(), d_ooff.data_ptr(), S, nb, max_bytes, d_scores.data_ptr(), d_labels.data_ptr(), stream)
+            if rnd == 0:
+                d_scores.zero_()
+                d_labels.zero_()
+            for _ in range(args.warmup):
+                step()
+            batch.sync()
+            batch.kernel_ms()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            ms = 1e3 * (time.perf_counter() - t) / args.steps
+            batch.sync()
+            kernel_ms, tiles = batch.kernel_ms()
+            r = results.setdefault(libname, {"variant": libname, "model": name, "ms_per_step": [], "kernel_ms": [], "tiles": tiles, "sentences": S, "len": [args.min_len, args.max_len]})
+            if rnd == 0:
+                r["parity"] = bool(np.array_equal(d_scores[:nb].cpu().numpy(), o_scores) and np.array_equal(d_labels[:nb].cpu().numpy(), o_labels))
+            r["ms_per_step"].append(round(ms, 4))
+            r["kernel_ms"].append(round(kernel_ms, 4))
+    for libname, r in results.items():
+        r["kernel_ms_median"] = round(float(np.median(r["kernel_ms"])), 4)
+        print(json.dumps(r), flush=True)
+    for libname in list(libs):
+        _lib._lib = libs[libname][0]
+        libs[libname][1:] = [None, None]
+        pred = batch = None
+        gc.collect()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variants", default="new,new:VPT_INLINE_ASSIGN=1")
@@ -40,6 +102,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--interleave", action="store_true", help="every library is loaded first and a round visits them all in turn (libraries that take no knobs: "
+                    "drift of the card then shows as spread within a variant, not as a difference between two); the outputs are compared in the first round")
     ap.add_argument("--phases", action="store_true", help="VPT_PROFILE_PHASES: wave 0's shader cycles per phase and tile (slows the kernel)")
     args = ap.parse_args()
     import torch
@@ -65,6 +129,8 @@ def main():
         parts = v.split(":")
         by_lib.setdefault(parts[0], []).append((v, dict(p.split("=", 1) for p in parts[1:])))
     results = {}
+    if args.interleave:
+        return interleaved(args, by_lib, raw, name, S, nb, max_bytes, ooff, d_text, d_boff, d_ooff, stream, o_scores, o_labels, dev)
     for libname, envs in by_lib.items():
         path = lib_path(libname)
         if not os.path.exists(path):

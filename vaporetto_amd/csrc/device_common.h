@@ -63,6 +63,50 @@ namespace vpt {
 __device__ __forceinline__ uint32_t wave_uniform(uint32_t x) { return uint32_t(__builtin_amdgcn_readfirstlane(int(x))); }
 __device__ __forceinline__ uint64_t wave_uniform64(uint64_t x) { return uint64_t(wave_uniform(uint32_t(x))) | (uint64_t(wave_uniform(uint32_t(x >> 32))) << 32); }
 
+// Which caches a global load or store may occupy (gfx950: the CU's 32 KB vector L1, the XCD's 4 MiB L2):
+//   kPlain        global_load / global_store: the line is kept in both
+//   kNonTemporal  ... nt: a load is served by the L2 and bypasses the L1; a store keeps its line in the L2
+//   kAgent        ... sc1 (a relaxed atomic of agent scope, at most 8 bytes): a load bypasses the L1; a store writes through and drops its line from the L2
+// A kernel names one constant per CLASS of its accesses and goes through these two functions, so that a policy is one word to change and to
+// measure.  The CPU emulator has no caches: every policy is the plain access there.
+enum class MemPolicy { kPlain = 0, kNonTemporal = 1, kAgent = 2 };
+#ifdef VPT_HIPEMU
+template <MemPolicy P, typename T>
+__device__ __forceinline__ T ld_pol(const T* p) { return *p; }
+template <MemPolicy P, typename T>
+__device__ __forceinline__ void st_pol(T* p, T v) { *p = v; }
+#else
+template <MemPolicy P, typename T>
+__device__ __forceinline__ T ld_pol(const T* p) {
+    if constexpr (P == MemPolicy::kPlain) {
+        return *p;
+    } else if constexpr (P == MemPolicy::kAgent) {
+        static_assert(sizeof(T) <= 8, "an agent-scope load is an atomic: 8 bytes at most (two of them for a node are two requests)");
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if constexpr (sizeof(T) == 16) {   // uint4 is a struct to the builtin: as the vector it is
+        typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+        const V4 v = __builtin_nontemporal_load(reinterpret_cast<const V4*>(p));
+        T r;
+        __builtin_memcpy(&r, &v, 16);
+        return r;
+    } else {
+        return __builtin_nontemporal_load(p);
+    }
+}
+template <MemPolicy P, typename T>
+__device__ __forceinline__ void st_pol(T* p, T v) {
+    if constexpr (P == MemPolicy::kPlain) {
+        *p = v;
+    } else if constexpr (P == MemPolicy::kAgent) {
+        static_assert(sizeof(T) <= 8, "an agent-scope store is an atomic: 8 bytes at most");
+        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        static_assert(sizeof(T) <= 8, "scalar types only");
+        __builtin_nontemporal_store(v, p);
+    }
+}
+#endif
+
 // First sentence i in [0, n_sent] whose flat start F(i) = ooff[i] + i * (1 + pad) is >= target (F is non-decreasing and
 // F(n_sent) is the total).  Sentences of similar length make F nearly linear: start from the interpolated position
 // and gallop outwards (two or three dependent loads instead of log2(n_sent)), then bisect.

@@ -39,6 +39,55 @@ namespace {
 #ifndef VPT_FAST_PAIR_BI
 #define VPT_FAST_PAIR_BI 1                   // the bigram node's halves fetched by lane pairs (A/B builds: -DVPT_FAST_PAIR_BI=0)
 #endif
+// Cache policy of every class of global access of the scoring kernel (device_common.h, MemPolicy).  A/B builds (tools/build_variants.sh) name
+// another with -DVPT_POL_<CLASS>=0|1|2: plain, non-temporal, agent scope.  Measured on MI355X (profiles/cache_policy_*): the outputs
+// -- 3.1 GB a launch on configs[2], never read back by the kernel -- stored non-temporal make the kernel 2.7 % faster there and 0.6-0.7 % on
+// 100 K sentences; agent-scope stores cost 6.6 %; every gather wants its L1 hits (a class that bypasses the L1 costs 20-30 % each); non-temporal
+// text is 1.9 % faster on 10 M sentences and 2 % slower on 100 K, whose text the chip's caches still hold from the step before: it stays plain.
+#ifndef VPT_POL_TEXT
+#define VPT_POL_TEXT 0
+#endif
+#ifndef VPT_POL_OFFSETS
+#define VPT_POL_OFFSETS 0
+#endif
+#ifndef VPT_POL_CID
+#define VPT_POL_CID 0
+#endif
+#ifndef VPT_POL_UNI
+#define VPT_POL_UNI 0
+#endif
+#ifndef VPT_POL_BI
+#define VPT_POL_BI 0
+#endif
+#ifndef VPT_POL_TRI
+#define VPT_POL_TRI 0
+#endif
+#ifndef VPT_POL_DEEP
+#define VPT_POL_DEEP 0
+#endif
+#ifndef VPT_POL_DEEPROW
+#define VPT_POL_DEEPROW 0
+#endif
+#ifndef VPT_POL_TYPE
+#define VPT_POL_TYPE 0
+#endif
+#ifndef VPT_POL_SCORE
+#define VPT_POL_SCORE 1
+#endif
+#ifndef VPT_POL_LABEL
+#define VPT_POL_LABEL 1
+#endif
+constexpr MemPolicy kPolText = MemPolicy(VPT_POL_TEXT);         // the tile's text, staged into LDS: read once (and once more by a neighbouring cut tile)
+constexpr MemPolicy kPolOffsets = MemPolicy(VPT_POL_OFFSETS);   // boff / ooff of the tile's sentences
+constexpr MemPolicy kPolCid = MemPolicy(VPT_POL_CID);           // a char's word of the 256 KB char table, and the probes of `xcid`
+constexpr MemPolicy kPolUni = MemPolicy(VPT_POL_UNI);           // unigram nodes
+constexpr MemPolicy kPolBi = MemPolicy(VPT_POL_BI);             // bigram nodes (both lanes of a pair, both halves)
+constexpr MemPolicy kPolTri = MemPolicy(VPT_POL_TRI);           // trigram nodes
+constexpr MemPolicy kPolDeep = MemPolicy(VPT_POL_DEEP);         // deep entries (the searched symbol, the symbols that must follow)
+constexpr MemPolicy kPolDeepRow = MemPolicy(VPT_POL_DEEPROW);   // deep rows and `xrows`
+constexpr MemPolicy kPolType = MemPolicy(VPT_POL_TYPE);         // type rows (staged into LDS, or global) and the window table
+constexpr MemPolicy kPolScore = MemPolicy(VPT_POL_SCORE);       // the scores out
+constexpr MemPolicy kPolLabel = MemPolicy(VPT_POL_LABEL);       // the labels out
 constexpr int kQCap = 128;                   // W items per wave
 constexpr uint32_t kQHigh = kQCap - 64;      // replay until one more round of pushes (<= 64) fits
 constexpr int kMCap = 64;                    // M items per wave: one round of pushes (<= 64) always fits an empty stack
@@ -108,8 +157,9 @@ __device__ __forceinline__ void count_reads(uint64_t* prof, int slot, bool pred,
 }
 
 // 16 bytes at base + byte offset (32-bit): one scalar base for all packed arrays
+template <MemPolicy POL>
 __device__ __forceinline__ uint4 ld16(const unsigned char* base, uint32_t byte_off) {
-    return *reinterpret_cast<const uint4*>(base + byte_off);
+    return ld_pol<POL>(reinterpret_cast<const uint4*>(base + byte_off));
 }
 // branch-free UTF-8 -> scalar value; b4 = the lead byte and the three bytes after it, little-endian
 __device__ __forceinline__ uint32_t utf8_scalar_bf(uint32_t b4) {
@@ -201,7 +251,7 @@ __device__ __forceinline__ void replay_w(VPT_KARG(ScoreParams) P, const DeepView
     const uint32_t tab = K.off_deep + ((it.y >> 5) << 6);   // byte offset of the mini-table (64-byte entries)
     const uint32_t last = (1u << (it.y & 31u)) - 1u;
     const uint32_t i0 = packed_mini_slot(c, it.y), i1 = (i0 + 1) & last;
-    const uint4 ea = ld16(K.base, tab + (i0 << 6)), eb = ld16(K.base, tab + (i1 << 6));
+    const uint4 ea = ld16<kPolDeep>(K.base, tab + (i0 << 6)), eb = ld16<kPolDeep>(K.base, tab + (i1 << 6));
     count_reads(prof, 3, have, 2);
     const bool ma = c != 0 && (ea.x & 0xFFFFu) == c;
     const bool mb = c != 0 && !ma && ea.x != 0 && (eb.x & 0xFFFFu) == c;   // last == 0: eb is ea again, no match
@@ -213,7 +263,7 @@ __device__ __forceinline__ void replay_w(VPT_KARG(ScoreParams) P, const DeepView
         uint32_t i = (i1 + 1) & last, n = 2;
         while (__ballot(open) != 0) {
             if (open) {
-                e = ld16(K.base, tab + (i << 6));
+                e = ld16<kPolDeep>(K.base, tab + (i << 6));
                 found = (e.x & 0xFFFFu) == c;
                 idx = i;
                 open = !found && e.x != 0 && n < last;
@@ -227,7 +277,7 @@ __device__ __forceinline__ void replay_w(VPT_KARG(ScoreParams) P, const DeepView
     const uint32_t nskip = found ? (e.x >> 24) & 15u : 0u;
     if (__ballot(nskip != 0) != 0) {
         uint4 e1 = make_uint4(0, 0, 0, 0);
-        if (__ballot(nskip > 2) != 0) { if (nskip > 2) e1 = ld16(K.base, ent + 16); }
+        if (__ballot(nskip > 2) != 0) { if (nskip > 2) e1 = ld16<kPolDeep>(K.base, ent + 16); }
         const uint32_t sk[4] = {e.z, e.w, e1.x, e1.y};
 #pragma unroll
         for (uint32_t j = 0; j < kPackedMaxSkip; ++j) {
@@ -246,9 +296,9 @@ __device__ __forceinline__ void replay_w(VPT_KARG(ScoreParams) P, const DeepView
     const bool row = found && (e.x & (kPkHasRow << 16));
     if (__ballot(row) != 0) {
         uint4 f0 = make_uint4(0, 0, 0, 0), f1 = make_uint4(0, 0, 0, 0);
-        if (row) f0 = ld16(K.base, ent + 32);   // (loading the home entry's row speculatively with the entry: no faster, profiles/r02_c5_ab*.jsonl)
+        if (row) f0 = ld16<kPolDeepRow>(K.base, ent + 32);   // (loading the home entry's row speculatively with the entry: no faster, profiles/r02_c5_ab*.jsonl)
         count_reads(prof, 4, row);
-        if (__ballot(row && rlen > 8) != 0) { if (row && rlen > 8) f1 = ld16(K.base, ent + 48); }
+        if (__ballot(row && rlen > 8) != 0) { if (row && rlen > 8) f1 = ld16<kPolDeepRow>(K.base, ent + 48); }
         if (row) {
             atomicAdd(dst, lo16(f0.x)); atomicAdd(dst + 1, hi16(f0.x)); atomicAdd(dst + 2, lo16(f0.y)); atomicAdd(dst + 3, hi16(f0.y));
             atomicAdd(dst + 4, lo16(f0.z)); atomicAdd(dst + 5, hi16(f0.z)); atomicAdd(dst + 6, lo16(f0.w)); atomicAdd(dst + 7, hi16(f0.w));
@@ -264,8 +314,8 @@ __device__ __forceinline__ void replay_w(VPT_KARG(ScoreParams) P, const DeepView
         if (found && (e.x & (kPkExtRow << 16))) {
             VPT_KARG(ScoreParams) R = P;
             VPT_KARG_FENCE(R);   // (asked for here, not kept over the pattern phase)
-            const int32_t* w32 = reinterpret_cast<const int32_t*>(K.base + R->pk.off_xrows) + ld16(K.base, ent + 32).x;
-            for (uint32_t j = 0; j < rlen; ++j) atomicAdd(dst + j, w32[j]);
+            const int32_t* w32 = reinterpret_cast<const int32_t*>(K.base + R->pk.off_xrows) + ld16<kPolDeepRow>(K.base, ent + 32).x;
+            for (uint32_t j = 0; j < rlen; ++j) atomicAdd(dst + j, ld_pol<kPolDeepRow>(w32 + j));
         }
     }
     Q.push_w(found && e.y != 0, s | (m << 11), e.y);
@@ -395,7 +445,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
         i0 = P->tile_first[tile];
         const uint64_t i1 = P->tile_first[tile + 1];
         if (i0 >= i1) return;      // no sentence starts in this tile's range
-        const uint64_t O0 = p_ooff[i0], O1 = p_ooff[i1], B0 = p_boff[i0], B1 = p_boff[i1];
+        const uint64_t O0 = ld_pol<kPolOffsets>(&p_ooff[i0]), O1 = ld_pol<kPolOffsets>(&p_ooff[i1]), B0 = ld_pol<kPolOffsets>(&p_boff[i0]), B1 = ld_pol<kPolOffsets>(&p_boff[i1]);
         const uint64_t fl = uint64_t(kPad) + (O1 + i1 * (kPad + 1)) - (O0 + i0 * (kPad + 1));
         if (O1 < O0 || B1 <= B0 || fl > uint64_t(kFastCap) || B1 - B0 > uint64_t(kFastCap) * 4 + 15 || i1 - i0 > 1023) {
             if (tid == 0) atomicOr(P->status, kErrScratchTooSmall);   // a sentence longer than the caller's bound (or offsets that are no offsets)
@@ -428,13 +478,13 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
     // offsets are asked for NOW, together with the text and the tables -- one trip to memory instead of three on the tile's
     // critical path -- and used after the barriers
     uint64_t my_b = 0, my_bn = 1, my_oa = 0, my_ob = 0;
-    if (uint32_t(tid) < nsent) { my_b = p_boff[i0 + tid]; my_bn = p_boff[i0 + tid + 1]; my_oa = p_ooff[i0 + tid]; my_ob = p_ooff[i0 + tid + 1]; }
+    if (uint32_t(tid) < nsent) { my_b = ld_pol<kPolOffsets>(&p_boff[i0 + tid]); my_bn = ld_pol<kPolOffsets>(&p_boff[i0 + tid + 1]); my_oa = ld_pol<kPolOffsets>(&p_ooff[i0 + tid]); my_ob = ld_pol<kPolOffsets>(&p_ooff[i0 + tid + 1]); }
     for (uint32_t i = tid; i < ((nbytes_al + 31) >> 5) + 1; i += kThreads) bitmap[i] = 0;
     for (uint32_t i = tid; i < (span + 3) / 4; i += kThreads) reinterpret_cast<uint4*>(L.sym)[i] = make_uint4(0, 0, 0, 0);
     if (TM != kTypeRows) {
         for (uint32_t i = tid; i < (span + 3) / 4; i += kThreads) reinterpret_cast<uint32_t*>(M.typ)[i] = 0;
     }
-    for (uint32_t c = tid; c < nchunks; c += kThreads) reinterpret_cast<uint4*>(raw)[c] = reinterpret_cast<const uint4*>(a0)[c];   // (non-temporal loads / stores here measured 1-2 % slower: profiles/r02_c1_ab.jsonl, r02_c3_ab.jsonl)
+    for (uint32_t c = tid; c < nchunks; c += kThreads) reinterpret_cast<uint4*>(raw)[c] = ld_pol<kPolText>(reinterpret_cast<const uint4*>(a0) + c);
     if (tid == 0) {
         raw[nchunks * 4] = 0;  // the dword after the staged text is read (as padding) by the last char
         // what phase C needs of the tile: read back there, so that it does not wait in scalar registers over the pattern phase
@@ -444,12 +494,12 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
     // the LDS-resident type rows (coalesced 16-byte loads from the predictor's arena)
     if (trow_lds) {
         const unsigned char* const tb = P->pk.base + P->pk.off_trow;
-        for (uint32_t i = tid; i < uint32_t(kTrowCount * G::kTrowQ); i += kThreads) M.trow[i] = *reinterpret_cast<const uint4*>(tb + (i << 4));
+        for (uint32_t i = tid; i < uint32_t(kTrowCount * G::kTrowQ); i += kThreads) M.trow[i] = ld_pol<kPolType>(reinterpret_cast<const uint4*>(tb + (i << 4)));
     }
     __syncthreads();
     tmark = phase_mark(prof, 0, tmark);   // zeroing, staging, table loads
     for (uint32_t j = tid; j < nsent; j += kThreads) {
-        const uint64_t b = j == uint32_t(tid) ? my_b : p_boff[i0 + j], bn = j == uint32_t(tid) ? my_bn : p_boff[i0 + j + 1];
+        const uint64_t b = j == uint32_t(tid) ? my_b : ld_pol<kPolOffsets>(&p_boff[i0 + j]), bn = j == uint32_t(tid) ? my_bn : ld_pol<kPolOffsets>(&p_boff[i0 + j + 1]);
         if (bn <= b) err |= kErrEmptySentence;
         if (b >= byte0 && b - byte0 < nbytes) {   // (sentence i0 of a cut tile may have started before the staged text)
             const uint32_t pos = head + uint32_t(b - byte0);
@@ -553,7 +603,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
             // id of the char it is scored as | CharacterType << 16 | linebreak << 29: one word of a 256 KB table (plain, or -- with
             // VPT_FLAG_KYTEA_FULLWIDTH -- the one that looks through KyteaFullwidthFilter); a separator or a char outside the BMP asks for nothing
             const uint32_t cp = xs[k] & 0x1FFFFFu;
-            if (uint32_t(cp - 1u) < 0xFFFFu) info[k] = cid[cp];
+            if (uint32_t(cp - 1u) < 0xFFFFu) info[k] = ld_pol<kPolCid>(cid + cp);
         }
         uint32_t outside = 0;   // this lane's chars outside the BMP (bit k), for the pass below
 #pragma unroll
@@ -574,7 +624,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
                 if (!((outside >> k) & 1u)) continue;
                 const uint32_t pos = uint32_t(tid) + uint32_t(k) * kThreads;
                 const uint32_t x = L.sym[pos], cp = x & 0x1FFFFFu, si = x >> 21;
-                const uint32_t id = ox ? xcid_find(xt, cp) : kNoId;
+                const uint32_t id = ox ? xcid_find_with(xt, cp, [](const uint32_t* p) { return ld_pol<kPolCid>(p); }) : kNoId;
                 placed(pos, cp, si, id | (char_type(cp) << 16) | (si << 19));
             }
         }
@@ -584,7 +634,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
     // e = c_off + (its first char's global number - g0) + kPad * j and is followed by a separator -- checked wherever e or its end
     // falls into the tile's window.  (A sentence longer or shorter than stated moves everything behind it.)
     for (uint32_t j = tid; j < nsent; j += kThreads) {
-        const uint64_t oa = j == uint32_t(tid) ? my_oa : p_ooff[i0 + j], ob = j == uint32_t(tid) ? my_ob : p_ooff[i0 + j + 1];
+        const uint64_t oa = j == uint32_t(tid) ? my_oa : ld_pol<kPolOffsets>(&p_ooff[i0 + j]), ob = j == uint32_t(tid) ? my_ob : ld_pol<kPolOffsets>(&p_ooff[i0 + j + 1]);
         const int64_t e = int64_t(c_off) + int64_t(oa + i0 + j - g0) + int64_t(kPad) * int64_t(j);
         const int64_t end = e + int64_t(ob - oa) + 1;
         if (ob < oa) err |= kErrBadOffsets;
@@ -635,7 +685,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
             if (t_slot != ~0u) {
                 const uint32_t a = off_tri + (((dbg & 1u) ? 0u : t_slot) * uint32_t(4 * pk_tri_dw(WL)));
 #pragma unroll
-                for (int q = 0; q < G::kTriQ; ++q) tn[q] = ld16(kbase, a + 16u * uint32_t(q));
+                for (int q = 0; q < G::kTriQ; ++q) tn[q] = ld16<kPolTri>(kbase, a + 16u * uint32_t(q));
             }
         }
         if (do_b) {
@@ -651,12 +701,12 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
                 const uint32_t slot_a = odd ? p_slot : b_slot, slot_b = odd ? b_slot : p_slot;
                 const bool on_a = odd ? p_on : b_key != 0, on_b = odd ? b_key != 0 : p_on;
                 const uint32_t half = odd ? 16u : 0u;
-                if (on_a) pa = ld16(kbase, (off_bi + (((dbg & 1u) ? 0u : slot_a) * uint32_t(4 * pk_bi_dw(WL)))) | half);
-                if (on_b) pb = ld16(kbase, (off_bi + (((dbg & 1u) ? 0u : slot_b) * uint32_t(4 * pk_bi_dw(WL)))) | half);
+                if (on_a) pa = ld16<kPolBi>(kbase, (off_bi + (((dbg & 1u) ? 0u : slot_a) * uint32_t(4 * pk_bi_dw(WL)))) | half);
+                if (on_b) pb = ld16<kPolBi>(kbase, (off_bi + (((dbg & 1u) ? 0u : slot_b) * uint32_t(4 * pk_bi_dw(WL)))) | half);
             } else if (b_key != 0) {
                 const uint32_t a = off_bi + (((dbg & 1u) ? 0u : b_slot) * uint32_t(4 * pk_bi_dw(WL)));
 #pragma unroll
-                for (int q = 0; q < G::kBiQ; ++q) nn[q] = ld16(kbase, a | (16u * uint32_t(q)));
+                for (int q = 0; q < G::kBiQ; ++q) nn[q] = ld16<kPolBi>(kbase, a | (16u * uint32_t(q)));
             }
         }
         bool live = false;
@@ -670,7 +720,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
                 if (want) {
                     const uint32_t a = ((dbg & 4u) ? 0u : id1) * uint32_t(4 * pk_uni_dw(WL));
 #pragma unroll
-                    for (int q = 0; q < G::kUniQ; ++q) un[q] = ld16(kbase, a + 16u * uint32_t(q));
+                    for (int q = 0; q < G::kUniQ; ++q) un[q] = ld16<kPolUni>(kbase, a + 16u * uint32_t(q));
                 }
             }
         }
@@ -758,7 +808,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
                         const uint32_t ra = P->pk.off_trow + idx * uint32_t(4 * pk_trow_global_dw(WL));
                         uint4 tr[pk_trow_global_dw(WL) / 4];
 #pragma unroll
-                        for (int q = 0; q < pk_trow_global_dw(WL) / 4; ++q) tr[q] = ld16(kbase, ra + 16u * uint32_t(q));
+                        for (int q = 0; q < pk_trow_global_dw(WL) / 4; ++q) tr[q] = ld16<kPolType>(kbase, ra + 16u * uint32_t(q));
                         uint32_t rd[pk_trow_global_dw(WL) + 1];
                         unpack4(tr, rd);
 #pragma unroll
@@ -816,11 +866,11 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
             uint32_t id = 0;  // window t[b-W+1 .. b+W], 3 bits each (boundary_scorer_cache.rs:59-81)
 #pragma unroll
             for (int i = 1 - TM; i <= TM; ++i) id = (id << 3) | (M.typ[int(p) + i] & 7u);
-            y += P->type_table[id];
+            y += ld_pol<kPolType>(P->type_table + id);
         }
         const uint32_t o = uint32_t(int32_t(p) - c_off_c) - (kPad + 1) * ((x >> 19) & 1023u);
         if (o >= o_lim) { err |= kErrBadOffsets; continue; }  // only with offsets that do not match the text
-        if (sc) sc[o] = y;
+        if (sc) st_pol<kPolScore>(sc + o, y);
         uint32_t label = y > 0 ? 1u : 0u;
         if (lb) {
             if (post) {   // wave-uniform: KyteaWsConstFilter / SplitLinebreaksFilter on the label
@@ -829,7 +879,7 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
                 if (same) label = 0;
                 if ((post & 0x80u) && ((x | x2) & kSymLinebreak) && !(same && (post & 0x100u))) label = 1;   // (bit 8, VPT_FLAG_LINEBREAKS_FIRST: the wsconst filters have the last word)
             }
-            lb[o] = uint8_t(label);
+            st_pol<kPolLabel>(lb + o, uint8_t(label));
         }
     }
     tmark = phase_mark(prof, 6, tmark);           // boundaries out

@@ -182,15 +182,20 @@ VPT_HD uint32_t packed_kid_filter_bit(uint32_t sym) { return (mul_u16(sym & 0xFF
 VPT_HD uint32_t tri_kid_filter(uint32_t dword0, uint32_t kids_word) { return (kids_word >> 27) | (((dword0 >> 28) & 7u) << 5); }
 // the alphabet outside the BMP (header comment, "xcid"): `tab` = the section's first dword
 VPT_HD uint32_t xcid_slot(uint32_t cp, uint32_t bits) { return (cp * kHashMulLo) >> (32u - bits); }   // bits in 1..31
-VPT_HD uint32_t xcid_find(const uint32_t* tab, uint32_t cp) {
-    const uint32_t bits = tab[0], mask = (1u << bits) - 1u;
+// (`ld`: how a word of the table is read -- the scoring kernel reads through its cache policy)
+template <typename LD>
+VPT_HD uint32_t xcid_find_with(const uint32_t* tab, uint32_t cp, LD ld) {
+    const uint32_t bits = ld(tab), mask = (1u << bits) - 1u;
     const uint32_t* const e = tab + 2;
     for (uint32_t i = xcid_slot(cp, bits), n = 0; n <= mask; i = (i + 1u) & mask, ++n) {
-        const uint32_t k = e[2u * i];
-        if (k == cp) return e[2u * i + 1u];
+        const uint32_t k = ld(e + 2u * i);
+        if (k == cp) return ld(e + 2u * i + 1u);
         if (k == 0u) break;
     }
     return 0xFFFFu;   // kNoId
+}
+VPT_HD uint32_t xcid_find(const uint32_t* tab, uint32_t cp) {
+    return xcid_find_with(tab, cp, [](const uint32_t* p) { return *p; });
 }
 
 // Tag token table (HostTagTables::tok_tab): a surface is hashed from its length and the low 16 bits of its first four chars
