@@ -228,6 +228,9 @@ vpt_status vpt_batch_sync(vpt_batch *b);
  * positions (chars + separators) a tile covers, and the kind -- 1 whole-sentence tiles, 2 tiles cut at any position with a halo
  * (batches with sentences too long for a tile), 0 the general kernels (models outside the packed shape). */
 vpt_status vpt_batch_last_plan(const vpt_batch *b, uint32_t *n_tiles, uint32_t *tile_flat, uint32_t *kind);
+/* How the last vpt_fill_tags_batch_device call on this workspace cut its batch (diagnostics): the number of front-end runs and the
+ * sentences of a run (the last run may hold fewer); both 0 before the first call.  Either pointer may be NULL. */
+vpt_status vpt_batch_tag_plan(const vpt_batch *b, uint64_t *n_runs, uint32_t *run_sentences);
 vpt_status vpt_batch_set_timing(vpt_batch *b, int enabled);
 vpt_status vpt_batch_kernel_ms(vpt_batch *b, float *score_kernel_ms, uint32_t *n_tiles);
 /* The individual durations (ms, oldest first) of the timed calls since the previous vpt_batch_kernel_ms, at most `capacity`
@@ -270,14 +273,17 @@ vpt_status vpt_fill_tags_batch_flags(const vpt_predictor *p, const uint8_t *utf8
  * (as Sentence::fill_tags follows Predictor::predict on the same sentence, predictor.rs:542), the chars that call decoded are
  * taken over and the decode kernel is skipped: do not rewrite d_utf8 in place between those two calls.  The chars are good
  * for that one call only, and only while no vpt_batch_sync lies between the two (a caller that waited for the device may have
- * rewritten its buffers): any other fill_tags call decodes the text it is given. */
+ * rewritten its buffers): any other fill_tags call decodes the text it is given.
+ * d_out_offsets that do not describe the text (out of order, past total_boundaries, not the chars the text holds) are an error reported
+ * by vpt_batch_sync and never a write outside d_tags_out, the other arrays of the call or the workspace; the records such a call leaves are empty. */
 vpt_status vpt_fill_tags_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8,
                                       const uint64_t *d_byte_offsets, const uint64_t *d_out_offsets,
                                       size_t n_sentences, uint64_t total_boundaries, const uint8_t *d_labels,
                                       int32_t *d_tags_out, void *hip_stream);
 /* Sentence::tags() of the batch of the last vpt_fill_tags_batch_device call on this workspace (same n_sentences and
  * total_boundaries): d_tags_out, (total_boundaries + n_sentences) * n_tags int32, receives the dense array -- None (-1)
- * for every char but the last one of a token that has a tag model (predictor.rs:556-598). */
+ * for every char but the last one of a token that has a tag model (predictor.rs:556-598).  Whatever offsets the fill_tags call was given,
+ * nothing outside those (total_boundaries + n_sentences) * n_tags entries is written. */
 vpt_status vpt_expand_tags_batch_device(const vpt_predictor *p, vpt_batch *b, size_t n_sentences, uint64_t total_boundaries,
                                         int32_t *d_tags_out, void *hip_stream);
 
@@ -346,7 +352,8 @@ vpt_status vpt_predict_write_batch_device(const vpt_predictor *p, vpt_batch *b, 
  * LABELS (one per token that call found a tag model for: the model, the chosen candidates, the bytes they take; labels
  * changed in between are reported as offsets that do not match -- Sentence::fill_tags and write_tokenized_text see the
  * same boundaries too, sentence.rs:1144-1148, 850-886).  d_tags: not read (until round 6 the dense array of that
- * fill_tags call); NULL is fine. */
+ * fill_tags call); NULL is fine.  Offsets that do not describe the text -- those of this call, or those the fill_tags call was given -- are
+ * an error reported by vpt_batch_sync and never a write outside d_text_out[0, text_capacity) and d_text_offsets_out[0, n_sentences]. */
 vpt_status vpt_write_tokenized_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8,
                                             const uint64_t *d_byte_offsets, const uint64_t *d_out_offsets,
                                             size_t n_sentences, uint64_t total_boundaries, const uint8_t *d_labels,

@@ -1378,7 +1378,13 @@ class DeviceBatch:
         st = _lib.load().vpt_batch_last_plan(self._h, C.byref(n), C.byref(tf), C.byref(kind))
         if st != _lib.VPT_OK:
             _raise(st)
-        return {"tiles": n.value, "tile_flat": tf.value, "kind": ("general kernels", "whole-sentence tiles", "cut tiles")[min(kind.value, 2)]}
+        runs, run_sent = C.c_uint64(), C.c_uint32()
+        st = _lib.load().vpt_batch_tag_plan(self._h, C.byref(runs), C.byref(run_sent))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        # tag_runs / tag_run_sent: the front-end runs of the last fill_tags call and the sentences of a run (vpt_batch_tag_plan)
+        return {"tiles": n.value, "tile_flat": tf.value, "kind": ("general kernels", "whole-sentence tiles", "cut tiles")[min(kind.value, 2)],
+                "tag_runs": runs.value, "tag_run_sent": run_sent.value}
 
     def kernel_times(self) -> np.ndarray:
         """Durations (ms) of the timed scoring-kernel launches since the last kernel_ms(), oldest first (at most 256)."""

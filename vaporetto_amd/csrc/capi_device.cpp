@@ -258,6 +258,13 @@ vpt_status vpt_batch_last_plan(const vpt_batch* b, uint32_t* n_tiles, uint32_t* 
     return VPT_OK;
 }
 
+vpt_status vpt_batch_tag_plan(const vpt_batch* b, uint64_t* n_runs, uint32_t* run_sentences) {
+    if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_runs) *n_runs = b->tag_runs;
+    if (run_sentences) *run_sentences = b->tag_run_sent;
+    return VPT_OK;
+}
+
 vpt_status vpt_batch_sync(vpt_batch* b) {
     if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     // A caller that waits for the device may rewrite its buffers afterwards: the chars a predict call left decoded for the fill_tags
@@ -341,7 +348,7 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     T.records = b->d_tag_records; T.rec_tags = b->d_rec_tags; T.rec_str = b->d_rec_str; T.cands = b->d_tag_cands;
     T.scan_state = b->d_tag_ctl; T.run_pref = b->d_tag_ctl + n_state;
     T.n_runs = n_runs; T.run_sent = run_sent;
-    T.summary = b->d_tag_summary;
+    T.summary = b->d_tag_summary; T.status = b->d_ctrl;
     VPT_HIP(vpt::launch_tag_tokens(T, stream));
     b->d_run_pref = T.run_pref; b->d_fill_run_pref = T.run_pref; b->tag_runs = n_runs; b->tag_run_sent = run_sent;
     b->rv_records = b->d_tag_records; b->rv_rec_tags = b->d_rec_tags; b->rv_rec_str = b->d_rec_str; b->rv_str_bytes = p->dtag.str_bytes;
@@ -358,7 +365,7 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
         R.cps = b->d_cps; R.ooff = d_out_offsets; R.labels = d_labels; R.n_sent = n_sentences; R.total_chars = total_c;
         R.records = b->d_tag_records; R.rec_tags = b->d_rec_tags; R.rec_str = b->d_rec_str; R.run_pref = T.run_pref; R.n_runs = n_runs; R.run_sent = run_sent;
         R.hits = b->d_pm_hits; R.out_records = b->d_pm_records; R.out_rec_tags = b->d_pm_rec_tags; R.out_rec_str = b->d_pm_rec_str;
-        R.scan_state = b->d_pm_ctl; R.out_run_pref = b->d_pm_ctl + n_state; R.tags = d_tags_out; R.n_cus = p->n_cus;
+        R.scan_state = b->d_pm_ctl; R.out_run_pref = b->d_pm_ctl + n_state; R.tags = d_tags_out; R.n_cus = p->n_cus; R.status = b->d_ctrl;
         VPT_HIP(vpt::launch_pattern_tagger(R, stream));
         b->d_run_pref = R.out_run_pref;
         b->rv_records = b->d_pm_records; b->rv_rec_tags = b->d_pm_rec_tags; b->rv_rec_str = b->d_pm_rec_str; b->rv_str_bytes = t->arena;

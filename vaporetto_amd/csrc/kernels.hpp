@@ -165,6 +165,15 @@ struct TagParams {
     uint32_t score_stride;
     uint32_t n_cus;             // the device's CUs: the grids are what it holds at a time
     const uint32_t* summary;    // 2^(kTagSumLog2 - 5) words for the summary of the token filter (tag_filter_summary_kernel writes it, the front end reads it)
+    // The batch's control word.  THE RUNS' BOUND: the records are numbered by a scan over the runs' candidate counts and every array they index
+    // holds total_chars entries, so the runs the front end accepts may never cover more than total_chars chars.  Offsets that go down and up again
+    // make runs that overlap (each of them inside the batch on its own), so three things hold whatever the offsets say:
+    //   * decode_chars_kernel / the scoring kernel in front of these launches have raised kErrBadOffsets in this word for such offsets: the front
+    //     end then accepts no run at all (no candidates, no records);
+    //   * the scan has total_chars as its capacity and raises kErrBadOffsets past it;
+    //   * every reader of run_pref clamps what it reads to total_chars, and a record's char is checked against total_chars before it indexes
+    //     cps, tags, model_out or scores_out (tag_resolve_kernel, tag_pass_kernel, expand_tags_kernel, the writer, the pattern tagger's merge).
+    uint32_t* status;
 };
 // sentences of a front-end run for a batch of this shape (about VPT_TAG_RUN_CHARS chars, at most 256 sentences); words of TagParams::summary
 uint32_t tag_run_sentences(uint64_t n_sent, uint64_t total_chars);
@@ -210,7 +219,9 @@ struct EmitFuse {
     uint64_t* chain_out;
 };
 // inclusive prefix sum over offsets[1 .. n] in place, offsets[0] = 0 (a chained scan, one launch; part: scan_part_entries(n) zero words)
-hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t capacity, uint32_t* status, uint64_t* total_out, hipStream_t stream);
+// (a total above `capacity` raises `overflow_err` in *status, when there is one)
+hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t capacity, uint32_t* status, uint64_t* total_out, hipStream_t stream,
+                       uint32_t overflow_err = kErrOutputTooSmall);
 // vpt_expand_tags_batch_device: the dense tags array from the records (None everywhere else)
 hipError_t launch_expand_tags(const uint4* records, const int32_t* rec_tags, const uint64_t* n_records, uint32_t n_tags, uint64_t total_chars, int32_t* tags,
                               uint32_t n_cus, hipStream_t stream);
@@ -269,6 +280,7 @@ struct PatternParams {
     uint64_t* scan_state;       // scan_part_entries(n_runs) zero words
     int32_t* tags;              // the dense array of the C ABI, or nullptr
     uint32_t n_cus;
+    uint32_t* status;           // the batch's control word: with kErrBadOffsets in it no run is looked at (TagParams::status)
 };
 hipError_t launch_pattern_tagger(const PatternParams& P, hipStream_t stream);
 

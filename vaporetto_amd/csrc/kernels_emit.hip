@@ -97,7 +97,8 @@ __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t* lds, uint64_t
 // total_out (optional): where the grand total is left as well -- host memory the device can write (hipHostMalloc), so that a
 // caller waiting on an event of the stream reads the size of the output without a copy of its own
 __global__ __launch_bounds__(kScanThreads) void scan_chained_kernel(uint64_t* __restrict__ offsets, uint64_t n, uint64_t* __restrict__ state, uint64_t n_part,
-                                                                    uint64_t capacity, uint32_t* __restrict__ status, uint64_t* __restrict__ total_out) {
+                                                                    uint64_t capacity, uint32_t* __restrict__ status, uint64_t* __restrict__ total_out,
+                                                                    uint32_t overflow_err) {
     __shared__ uint64_t lds[kScanThreads];
     __shared__ uint64_t bcast[2];
     const uint32_t tid = threadIdx.x;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_chained_kernel(uint64_t* __
         bcast[1] = base;
         if (blk == 0) offsets[0] = 0;
         if (blk == n_part - 1) {
-            if (base + total > capacity && status) atomicOr(status, kErrOutputTooSmall);
+            if (base + total > capacity && status) atomicOr(status, overflow_err);
             if (total_out) *total_out = base + total;
         }
     }
@@ -144,9 +145,10 @@ __global__ __launch_bounds__(kScanThreads) void scan_chained_kernel(uint64_t* __
 }
 
 }  // namespace
-hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t capacity, uint32_t* status, uint64_t* total_out, hipStream_t stream) {
+hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t capacity, uint32_t* status, uint64_t* total_out, hipStream_t stream,
+                       uint32_t overflow_err) {
     const uint64_t n_part = (n + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(scan_chained_kernel, dim3(uint32_t(n_part)), dim3(kScanThreads), 0, stream, offsets, n, part, n_part, capacity, status, total_out);
+    hipLaunchKernelGGL(scan_chained_kernel, dim3(uint32_t(n_part)), dim3(kScanThreads), 0, stream, offsets, n, part, n_part, capacity, status, total_out, overflow_err);
     return hipGetLastError();
 }
 namespace {
@@ -278,8 +280,12 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
     uint64_t r_lo = 0, r_hi = 0;
     if (kTags && sane) {
         const uint64_t ra = i0 / P.run_sent, rb = (i0 + ns + P.run_sent - 1) / P.run_sent;
+        // (never a record past the arrays, whatever the counts say: they hold a record per char of the batch -- TagParams::status)
+        const uint64_t r_cap = P.total_boundaries + P.n_sent;
         r_lo = wave_uniform64(P.run_pref[ra < P.n_runs ? ra : P.n_runs]);
         r_hi = wave_uniform64(P.run_pref[rb < P.n_runs ? rb : P.n_runs]);
+        r_lo = r_lo < r_cap ? r_lo : r_cap;
+        r_hi = r_hi < r_cap ? r_hi : r_cap;
         if (r_hi < r_lo) r_hi = r_lo;
         if (i0 != ra * P.run_sent) {   // (the same in every thread) a run that starts inside a front-end run: its records begin further on
             for (;;) {

@@ -47,7 +47,8 @@ __device__ __forceinline__ uint64_t records_before(const uint4* __restrict__ rec
 }
 
 // what both kernels know of a run: its sentences, its chars [run0, run0 + n), its records [r_lo, r_hi); ok == false: offsets or counts that do not
-// fit the batch (reported by decode_chars_kernel / the scoring kernel) -- the run keeps its records and gets no rule tags
+// fit the batch (reported by decode_chars_kernel / the scoring kernel in the batch's control word, which is looked at here: runs of such offsets can
+// overlap, TagParams::status) -- the run keeps its records and gets no rule tags
 struct PmRun {
     uint64_t i_a, run0, r_lo, r_hi;
     uint32_t ns, n;
@@ -63,7 +64,12 @@ __device__ __forceinline__ PmRun pm_run(const PatternParams& P, uint64_t run) {
     R.r_lo = P.run_pref[run]; R.r_hi = P.run_pref[run + 1];
     const bool recs = R.r_hi >= R.r_lo && R.r_hi <= P.total_chars;
     if (!recs) { R.r_lo = 0; R.r_hi = 0; }
-    R.ok = recs && run1 >= R.run0 && run1 <= P.total_chars && run1 - R.run0 < 0x7FFFFF00ull && R.ns <= kPmMaxRunSent;
+#ifdef VPT_TAG_NO_OFFSETS_GATE   // (test builds, kernels_tags.hip)
+    const bool gate = false;
+#else
+    const bool gate = (*P.status & kErrBadOffsets) != 0;
+#endif
+    R.ok = recs && !gate && run1 >= R.run0 && run1 <= P.total_chars && run1 - R.run0 < 0x7FFFFF00ull && R.ns <= kPmMaxRunSent;
     R.n = R.ok ? uint32_t(run1 - R.run0) : 0u;
     return R;
 }
@@ -227,7 +233,7 @@ hipError_t launch_pattern_tagger(const PatternParams& P, hipStream_t stream) {
     hipLaunchKernelGGL(pattern_match_kernel, grid, block, 0, stream, P);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = launch_scan(P.out_run_pref, P.n_runs, P.scan_state, ~uint64_t(0), nullptr, nullptr, stream);
+    e = launch_scan(P.out_run_pref, P.n_runs, P.scan_state, P.total_chars, P.status, nullptr, stream, kErrBadOffsets);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pattern_merge_kernel, grid, block, 0, stream, P);
     return hipGetLastError();

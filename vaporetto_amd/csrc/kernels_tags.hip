@@ -532,7 +532,8 @@ __global__ __launch_bounds__(kTagThreads) void tag_resolve_kernel(const TagParam
         const uint32_t nr = uint32_t(P.n_runs - r_first < kResolveRuns ? P.n_runs - r_first : kResolveRuns);
         __builtin_amdgcn_wave_barrier();
         // the runs' first records (= their candidates' numbers: candidate c IS record c) and first chars, one trip for all of them
-        if (uint32_t(lane) <= nr) PREF[wid][lane] = P.run_pref[r_first + uint32_t(lane)];
+        // (clamped: the records' arrays hold total_chars entries -- TagParams::status)
+        if (uint32_t(lane) <= nr) { const uint64_t f = P.run_pref[r_first + uint32_t(lane)]; PREF[wid][lane] = f < P.total_chars ? f : P.total_chars; }
         if (uint32_t(lane) < nr) { const uint64_t i_a = (r_first + uint32_t(lane)) * P.run_sent; RUN0[wid][lane] = P.ooff[i_a] + i_a; }
         __builtin_amdgcn_wave_barrier();
         const uint64_t c_lo = PREF[wid][0], c_hi = PREF[wid][nr];
@@ -543,14 +544,23 @@ __global__ __launch_bounds__(kTagThreads) void tag_resolve_kernel(const TagParam
 #pragma unroll
             for (uint32_t q = 1; q < kResolveRuns; ++q) j += (q < nr && PREF[wid][q] <= c) ? 1u : 0u;
             const uint64_t run0 = RUN0[wid][j];
-            const uint4 e = have ? P.cands[run0 + (c - PREF[wid][j])] : make_uint4(0, 1, 0, 0);
+            const uint64_t at = run0 + (c - PREF[wid][j]);
+            uint4 e = (have && at < P.total_chars) ? P.cands[at] : make_uint4(0, 1, 0, 0);
             const uint64_t gp = run0 + e.x;
+            // Runs that overlap (offsets that go down and up again) share their places in cands: an entry may be another run's.  A token that does
+            // not lie inside the batch's chars is no token -- an empty record at char 0 --, and no context reaches past the batch's ends.
+            const bool inside = have && at < P.total_chars && gp < P.total_chars && e.y >= 1u && uint64_t(e.y) <= gp + 1;
+            if (inside) {
+                const uint32_t back = e.z & 0xFFu, fwd = e.z >> 8;
+                const uint64_t room = P.total_chars - 1 - gp;
+                e.z = uint32_t(back < gp ? back : gp) | (uint32_t(fwd < room ? fwd : room) << 8);
+            }
             bool fast = false;
-            const uint32_t model = have ? find_tag_model(P, P.cps + (gp + 1 - e.y), e.y, &fast) : 0u;
+            const uint32_t model = inside ? find_tag_model(P, P.cps + (gp + 1 - e.y), e.y, &fast) : 0u;
             // the record, for now: {last char, context clip, tag model + 1 | record form << 31, 0}; the passes make it the token's record.
             // No tag model: that IS the (empty) record.  (A queue of the tokens that have one, filled with an atomic per 64 candidates,
             // stood here first: 44 K atomics on one word took most of the launch's 0.48 ms, profiles/r06_e_*.)
-            if (have) P.records[c] = make_uint4(uint32_t(gp), model ? e.z : 0u, model | (fast ? 0x80000000u : 0u), 0u);
+            if (have) P.records[c] = make_uint4(inside ? uint32_t(gp) : 0u, model ? e.z : 0u, model | (fast ? 0x80000000u : 0u), 0u);
         }
     }
 }
@@ -566,7 +576,8 @@ __global__ __launch_bounds__(kTagThreads, kTagPairOcc) void tag_pass_kernel(cons
     TagWaveLds& L = LDS[wid];
     const uint64_t below_me = (uint64_t(1) << lane) - 1;
     const uint64_t wave = uint64_t(blockIdx.x) * kTagWaves + wid, n_waves = uint64_t(gridDim.x) * kTagWaves;
-    const uint64_t n_rec = wave_uniform64(P.run_pref[P.n_runs]);
+    const uint64_t n_all = wave_uniform64(P.run_pref[P.n_runs]);
+    const uint64_t n_rec = n_all < P.total_chars ? n_all : P.total_chars;   // (clamped: TagParams::status)
     uint32_t nq = 0;
     for (uint64_t c0 = wave * 64; c0 < n_rec; c0 += n_waves * 64) {
         const uint64_t c = c0 + uint32_t(lane);
@@ -602,9 +613,15 @@ __global__ __launch_bounds__(kTagThreads, kTagPairOcc) void tag_pass_kernel(cons
                 if (P.ooff[mid] + mid <= gk) lo = mid; else hi = mid;
             }
             const uint64_t g0 = P.ooff[lo] + lo;
+            const uint64_t sn = P.ooff[lo + 1] - P.ooff[lo] + 1;
+            // (offsets that do not match the text: a sentence that does not hold the char, or does not lie inside the batch's chars, is none -- an empty record)
+            if (g0 > gk || sn > P.total_chars - g0 || gk - g0 >= sn) {
+                if (lane == 0) P.records[c0 + uint32_t(k)] = make_uint4(uint32_t(gk), 0u, 0u, 0u);
+                continue;
+            }
             // (the routine's scratch is the union's other member: the queue's rows stay as they are only while it is empty -- so run the waiting pass first)
             if (nq != 0) { tag_pass(P, L, nq, lane); nq = 0; }
-            tag_token_by_wave(P, P.cps + g0, int64_t(P.ooff[lo + 1] - P.ooff[lo]) + 1, int64_t(gk - g0), g0, mk, VPT_TO_LDS_PTR(volatile int32_t, L.z), lane, c0 + uint32_t(k));
+            tag_token_by_wave(P, P.cps + g0, int64_t(sn), int64_t(gk - g0), g0, mk, VPT_TO_LDS_PTR(volatile int32_t, L.z), lane, c0 + uint32_t(k));
         }
     }
     if (nq != 0) tag_pass(P, L, nq, lane);
@@ -712,7 +729,13 @@ __global__ __launch_bounds__(kFlatThreads, VPT_TAG_FLAT_OCC) void tag_front_flat
     const uint64_t below_me = (uint64_t(1) << lane) - 1;
     const uint64_t total_b = P->total_chars - P->n_sent;   // labels of the batch
     const uint32_t per = P->run_sent;
+    // offsets the launch in front of this one has found not to match the text: no run is accepted (TagParams::status)
+    // (-DVPT_TAG_NO_OFFSETS_GATE, test builds: the control word is not looked at, here and in the pattern tagger, so that the clamps alone are what holds)
+#ifdef VPT_TAG_NO_OFFSETS_GATE
     const uint64_t n_runs = P->n_runs;
+#else
+    const uint64_t n_runs = (wave_uniform(*P->status) & kErrBadOffsets) ? 0 : P->n_runs;
+#endif
     VPT_TP_DECL;
     for (uint64_t run = wave; run < n_runs; run += n_waves) {
         VPT_TP(0);
@@ -985,7 +1008,7 @@ hipError_t launch_tag_tokens(const TagParams& P, hipStream_t stream) {
     const uint64_t want_w = (P.n_runs + kFlatWaves - 1) / kFlatWaves, cap_w = uint64_t(cus) * (VPT_TAG_FLAT_OCC / 2);
     const dim3 grid(uint32_t(want_w < 1 ? 1 : want_w > cap_w ? cap_w : want_w)), block(kFlatThreads);
     hipLaunchKernelGGL((tag_front_flat_kernel<sum>), grid, block, 0, stream, P, sum_log2);
-    hipError_t e = launch_scan(P.run_pref, P.n_runs, P.scan_state, ~uint64_t(0), nullptr, nullptr, stream);
+    hipError_t e = launch_scan(P.run_pref, P.n_runs, P.scan_state, P.total_chars, P.status, nullptr, stream, kErrBadOffsets);
     if (e != hipSuccess) return e;
     // the lookups and the passes: what the device holds (8 workgroups of 4 waves per CU), never more waves than there are runs / than a
     // wave per 16 chars of the batch would need
@@ -1001,7 +1024,7 @@ hipError_t launch_tag_tokens(const TagParams& P, hipStream_t stream) {
 // `resize(n_tags * len, None)`, predictor.rs:556-557), then the records' tags at their tokens' last chars
 __global__ __launch_bounds__(256) void expand_tags_kernel(const uint4* __restrict__ records, const int32_t* __restrict__ rec_tags, const uint64_t* __restrict__ n_records,
                                                           const uint32_t n_tags, const uint64_t total_chars, int32_t* __restrict__ tags) {
-    const uint64_t n = *n_records, n_items = n * n_tags;
+    const uint64_t n_all = *n_records, n = n_all < total_chars ? n_all : total_chars, n_items = n * n_tags;   // (clamped: TagParams::status)
     for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n_items; i += uint64_t(gridDim.x) * 256u) {
         const uint64_t k = i / n_tags, j = i - k * n_tags;
         const uint4 r = records[k];
