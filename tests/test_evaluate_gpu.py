@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 from oracle import cbind
-from tests import evalref, kat
+from tests import devmem, evalref, kat
 from tests.test_evaluate_cli import KAT_GOLD, MODES, _expected
 from tests.test_tokenized_parse import _expect, check_parsed, random_line
-from vaporetto_amd import api, build
+from vaporetto_amd import _lib, api, build
 from vaporetto_amd.modelfmt import encode_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +129,39 @@ def test_evaluate_matches_restatement(wsconst, predict_tags, no_norm):
         want = evalref.evaluate(lines, _oracle_system(raw, pred._model.tag_models(), types, "G" in wsconst, predict_tags),
                                 predict_tags=predict_tags, no_norm=no_norm)
         assert {k: got[k] for k in want} == want, name
+
+
+def test_evaluate_over_several_front_end_runs():
+    """fill_tags numbers its records run by run of at most 256 sentences and the compare finds a sentence's records through its run: 720 lines
+    are three runs at least, so sentences of run 1 and 2 are compared -- the one call, and the compare alone on a workspace of the test's own
+    (which says how fill_tags cut the batch), both against the restatement over the oracle's system side."""
+    keys = ("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences")
+    texts = ["まぁ社長は火星猫だ", "まぁ良いだろう", "この人は地球人だ", "火星猫", "Ｒｕｓｔで良いプログラミング体験を！", "ab 12 cd"] * 120
+    for name, raw in (("model.bin", open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()), ("kat", encode_model(kat.predictor_test_model()))):
+        pred = _predictor(raw)
+        lines = _corpus(pred, texts)
+        want = evalref.evaluate(lines, _oracle_system(raw, pred._model.tag_models(), [], False, True), predict_tags=True)
+        assert want["n_cor"] > 0 and want["n_cor"] < want["n_ref"]
+        got = pred.evaluate(lines, predict_tags=True)
+        assert {k: got[k] for k in want} == want, name
+        # call by call: parse, predict, fill_tags (the records stay on the workspace), the compare
+        h = api.parse_tokenized_host([ln.encode("utf-8") for ln in lines])
+        _, sys_l, ooff = pred.predict_packed(h["raw"], h["raw_offsets"], fullwidth=True)
+        assert np.array_equal(ooff, h["out_offsets"])
+        S, nb = len(lines), int(ooff[-1])
+        pad = lambda a: np.concatenate([a, np.zeros(32, a.dtype)])
+        d = {k: devmem.put(pad(v)) for k, v in h.items()}
+        d_sys, d_counts = devmem.put(pad(sys_l)), devmem.zeros(8, np.uint64)
+        batch = api.DeviceBatch(pred)
+        batch.set_flags(_lib.VPT_FLAG_KYTEA_FULLWIDTH)
+        batch.fill_tags(d["raw"].ptr, d["raw_offsets"].ptr, d["out_offsets"].ptr, S, nb, d_sys.ptr, 0, devmem.stream())
+        st = _lib.load().vpt_evaluate_labels_batch_device(pred.handle, batch._h, d["out_offsets"].ptr, S, d["labels"].ptr, d["n_tags"].ptr, d["tag_index"].ptr,
+                                                          d["span_offsets"].ptr, d["tag_bytes"].ptr, d_sys.ptr, _lib.VPT_EVAL_TAGS_PREDICTED, d_counts.ptr,
+                                                          devmem.stream())
+        assert st == _lib.VPT_OK, _lib.last_error()
+        batch.sync()
+        assert batch.last_plan()["tag_runs"] >= 3, name
+        assert dict(zip(keys, (int(c) for c in d_counts.get()))) == {k: want[k] for k in keys}, name
 
 
 def test_chunked_path_gives_the_same_counts():

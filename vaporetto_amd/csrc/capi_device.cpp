@@ -260,8 +260,8 @@ vpt_status vpt_batch_last_plan(const vpt_batch* b, uint32_t* n_tiles, uint32_t* 
 
 vpt_status vpt_batch_tag_plan(const vpt_batch* b, uint64_t* n_runs, uint32_t* run_sentences) {
     if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (n_runs) *n_runs = b->tag_runs;
-    if (run_sentences) *run_sentences = b->tag_run_sent;
+    if (n_runs) *n_runs = b->tag_out.own.n_runs;
+    if (run_sentences) *run_sentences = b->tag_out.own.run_sent;
     return VPT_OK;
 }
 
@@ -311,7 +311,7 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     if (total_c >= 0xFFFFFF00ull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: fill_tags takes fewer than 2^32 - 256 chars per call");
     vpt_status st = b->d_cps.grow(size_t(total_c) + 16);
     if (st != VPT_OK) return st;
-    b->tag_chars = 0;   // (until the launches are enqueued: a failure below leaves no records behind)
+    b->tag_out.chars = 0;   // (until the launches are enqueued: a failure below leaves no records behind)
     // What the call leaves is ONE RECORD PER TOKEN THAT HAS A TAG MODEL (kernels.hpp, TagParams): the reference holds None for every other
     // char (predictor.rs:558-573).  Everything is sized for the worst case -- a tagged token per char, which a real tag model comes close
     // to (most tokens of real text have one; the synthetic M3's one token in thirty-five is the other end) -- so nothing can overflow and
@@ -350,27 +350,25 @@ vpt_status vpt_fill_tags_scores_batch_device(const vpt_predictor* p, vpt_batch* 
     T.n_runs = n_runs; T.run_sent = run_sent;
     T.summary = b->d_tag_summary; T.status = b->d_ctrl;
     VPT_HIP(vpt::launch_tag_tokens(T, stream));
-    b->d_run_pref = T.run_pref; b->d_fill_run_pref = T.run_pref; b->tag_runs = n_runs; b->tag_run_sent = run_sent;
-    b->rv_records = b->d_tag_records; b->rv_rec_tags = b->d_rec_tags; b->rv_rec_str = b->d_rec_str; b->rv_str_bytes = p->dtag.str_bytes;
+    vpt::TagRecordsView own = vpt::records_view(T, p->dtag.str_bytes), merged = own;
+    b->tag_out.own = own;
     if (const vpt_pattern_tagger* t = b->tagger) {   // PatternMatchTagger: the rules' tags merged into records of their own (kernels_pattern.hip)
-        const size_t pm_words = n_state + size_t(n_runs) + 2;
         if ((st = b->d_pm_records.grow(size_t(total_c) + 16)) != VPT_OK) return st;
         if ((st = b->d_pm_rec_tags.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
         if ((st = b->d_pm_rec_str.grow(size_t(total_c) * p->n_tags + 16)) != VPT_OK) return st;
         if ((st = b->d_pm_hits.grow(size_t(total_c) + 16)) != VPT_OK) return st;
-        if ((st = b->d_pm_ctl.grow(pm_words)) != VPT_OK) return st;
-        VPT_HIP(hipMemsetAsync(b->d_pm_ctl, 0, pm_words * sizeof(uint64_t), stream));
+        if ((st = b->d_pm_ctl.grow(ctl_words)) != VPT_OK) return st;   // (its own scan state and run_pref)
+        VPT_HIP(hipMemsetAsync(b->d_pm_ctl, 0, ctl_words * sizeof(uint64_t), stream));
         vpt::PatternParams R{};
         R.slots = t->slots; R.surf = t->surf; R.rule_tags = t->rule_tags; R.id_str = t->id_str; R.bits = t->bits; R.max_len = t->max_len; R.n_tags = p->n_tags;
         R.cps = b->d_cps; R.ooff = d_out_offsets; R.labels = d_labels; R.n_sent = n_sentences; R.total_chars = total_c;
-        R.records = b->d_tag_records; R.rec_tags = b->d_rec_tags; R.rec_str = b->d_rec_str; R.run_pref = T.run_pref; R.n_runs = n_runs; R.run_sent = run_sent;
+        R.in = own;
         R.hits = b->d_pm_hits; R.out_records = b->d_pm_records; R.out_rec_tags = b->d_pm_rec_tags; R.out_rec_str = b->d_pm_rec_str;
         R.scan_state = b->d_pm_ctl; R.out_run_pref = b->d_pm_ctl + n_state; R.tags = d_tags_out; R.n_cus = p->n_cus; R.status = b->d_ctrl;
         VPT_HIP(vpt::launch_pattern_tagger(R, stream));
-        b->d_run_pref = R.out_run_pref;
-        b->rv_records = b->d_pm_records; b->rv_rec_tags = b->d_pm_rec_tags; b->rv_rec_str = b->d_pm_rec_str; b->rv_str_bytes = t->arena;
+        merged.records = R.out_records; merged.rec_tags = R.out_rec_tags; merged.rec_str = R.out_rec_str; merged.run_pref = R.out_run_pref; merged.str_bytes = t->arena;
     }
-    b->tag_chars = total_c; b->tag_sentences = n_sentences;
+    b->tag_out.merged = merged; b->tag_out.chars = total_c; b->tag_out.sentences = n_sentences;
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
@@ -380,11 +378,11 @@ vpt_status vpt_expand_tags_batch_device(const vpt_predictor* p, vpt_batch* b, si
     if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     if (n_sentences == 0 || p->n_tags == 0) return VPT_OK;
     if (!d_tags_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (b->tag_chars != total_boundaries + n_sentences || b->tag_sentences != n_sentences || !b->d_tag_records)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
+    vpt::TagRecordsView V;
+    if (const vpt_status st = tag_records_for(b, n_sentences, total_boundaries, true, &V); st != VPT_OK) return st;
     VPT_HIP(hipSetDevice(p->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    VPT_HIP(vpt::launch_expand_tags(b->rv_records, b->rv_rec_tags, b->d_run_pref + b->tag_runs, p->n_tags, b->tag_chars, d_tags_out, p->n_cus, stream));
+    VPT_HIP(vpt::launch_expand_tags(V, d_tags_out, p->n_cus, stream));
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
@@ -449,14 +447,11 @@ vpt_status emit_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_ut
     E.status = b->d_ctrl;
     if (tagged && p->n_tags > 0) {   // "/tag" suffixes: from the records the fill_tags call on this workspace left for this batch
         if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
-        if (b->tag_chars != total_boundaries + n_sentences || b->tag_sentences != n_sentences || !b->d_tag_records)
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
-        E.records = b->rv_records; E.rec_str = b->rv_rec_str; E.run_pref = b->d_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;
-        E.n_tags = p->n_tags; E.str_bytes = b->rv_str_bytes;
+        if (const vpt_status st = tag_records_for(b, n_sentences, total_boundaries, true, &E.tag); st != VPT_OK) return st;
     }
     vpt::EmitFuse F{};
     {
-        const vpt_status st = plan_runs(p, b, n_sentences, total_boundaries, E.records != nullptr, E.run_sent, total_out, chain_in, chain_out, stream, &F);
+        const vpt_status st = plan_runs(p, b, n_sentences, total_boundaries, E.tag.records != nullptr, E.tag.run_sent, total_out, chain_in, chain_out, stream, &F);
         if (st != VPT_OK) return st;
     }
     VPT_HIP(vpt::launch_emit_tokenized(E, F, stream));
@@ -758,6 +753,6 @@ vpt_status vpt_batch_set_pattern_tagger(vpt_batch* b, const void* tagger) {
     if (!b) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (t && t->pred != b->pred) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this workspace's predictor");
     b->tagger = t;
-    b->tag_chars = 0;   // the records on the workspace were made under the other setting
+    b->tag_out.chars = 0;   // the records on the workspace were made under the other setting
     return VPT_OK;
 }

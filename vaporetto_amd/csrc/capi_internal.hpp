@@ -323,21 +323,21 @@ struct vpt_batch {
     DevBuf<uint4> d_tag_records;
     DevBuf<int32_t> d_rec_tags;
     DevBuf<uint64_t> d_tag_ctl;                                     // the scan's state, run_pref [n_runs + 1]: zeroed as one range per call
-    uint64_t* d_run_pref = nullptr;                                 // (inside d_tag_ctl, or d_pm_ctl: the run_pref of the records the readers take)
-    uint64_t* d_fill_run_pref = nullptr;                            // (inside d_tag_ctl: fill_tags' own, what vpt_evaluate_* reads)
     DevBuf<uint2> d_rec_str;
     DevBuf<uint4> d_tag_cands;
     DevBuf<uint32_t> d_tag_summary;
-    uint64_t tag_chars = 0, tag_sentences = 0, tag_runs = 0;        // the batch those records belong to (0 chars: none)
-    uint32_t tag_run_sent = 0;
+    // What that call hands to the readers of its records (tag_records.h; tag_records_for).  own: fill_tags' (what evaluate takes: its CLI runs no
+    // PatternMatchTagger); merged: the pattern tagger's merge when the workspace has one, else own again (the writer, expand_tags)
+    struct TagHandOver {
+        vpt::TagRecordsView own{}, merged{};
+        uint64_t chars = 0, sentences = 0;                          // the batch they belong to (0 chars: none)
+    } tag_out;
     // vpt_batch_set_pattern_tagger: the rules applied behind every fill_tags on this workspace (nullptr: none), and what they are merged into.
-    // rv_*: the records the readers take (the writer, expand_tags; not evaluate: it keeps to fill_tags' own) -- fill_tags' own, or the merged ones; d_run_pref goes with them.
     const vpt_pattern_tagger* tagger = nullptr;
     DevBuf<uint4> d_pm_records;
     DevBuf<int32_t> d_pm_rec_tags;
     DevBuf<uint2> d_pm_rec_str, d_pm_hits;
     DevBuf<uint64_t> d_pm_ctl;
-    const uint4* rv_records = nullptr; const int32_t* rv_rec_tags = nullptr; const uint2* rv_rec_str = nullptr; const uint8_t* rv_str_bytes = nullptr;
     std::vector<uint64_t> h_boff, h_ooff;                           // rebased offsets of the call in flight (copied asynchronously)
     DevBuf<uint8_t> d_types;                                        // vpt_char_types_batch
     DevBuf<uint64_t> d_scan_part;                                   // per-workgroup partials of the prefix sums (kernels_emit.hip)
@@ -589,6 +589,17 @@ vpt_status stage(vpt_batch* b, const uint8_t* utf8, const uint64_t* byte_offsets
     *total_b_out = total_b;
     if (max_bytes_out) *max_bytes_out = max_bytes;
     if (max_chars_out) *max_chars_out = max_chars;
+    return VPT_OK;
+}
+
+// The records the fill_tags call on this workspace left for THIS batch -- n_sentences and, where the caller knows them, total_boundaries
+// (kBoundariesUnknown: any batch of that many sentences) -- merged with the pattern tagger's or fill_tags' own; an error when there are none.
+constexpr uint64_t kBoundariesUnknown = ~uint64_t(0);
+vpt_status tag_records_for(const vpt_batch* b, size_t n_sentences, uint64_t total_boundaries, bool merged, vpt::TagRecordsView* out) {
+    const vpt_batch::TagHandOver& h = b->tag_out;
+    if (h.sentences != n_sentences || (total_boundaries == kBoundariesUnknown ? h.chars == 0 : h.chars != total_boundaries + n_sentences))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
+    *out = merged ? h.merged : h.own;
     return VPT_OK;
 }
 

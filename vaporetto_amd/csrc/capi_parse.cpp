@@ -197,11 +197,8 @@ vpt_status evaluate_device_impl(const vpt_predictor* p, vpt_batch* b, const uint
     if (!d_out_offsets || !d_gold_labels || !d_sys_labels || !d_counts || (sys_tags != VPT_EVAL_TAGS_GOLD && !d_n_tags) ||
         (sys_tags == VPT_EVAL_TAGS_PREDICTED && (!d_tag_index || !d_span_offsets || !d_tag_bytes)))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (sys_tags == VPT_EVAL_TAGS_PREDICTED) {
-        if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
-        if (p->n_tags && (b->tag_sentences != n_sentences || !b->tag_chars || !b->d_tag_records))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: call vpt_fill_tags_batch_device on this workspace for this batch first");
-    }
+    if (sys_tags == VPT_EVAL_TAGS_PREDICTED && !p->predict_tags)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     VPT_HIP(hipSetDevice(p->device));
     vpt::EvalParams E{};
     E.gold = d_gold_labels; E.sys = d_sys_labels; E.ooff = d_out_offsets; E.n_sent = n_sentences;
@@ -209,13 +206,9 @@ vpt_status evaluate_device_impl(const vpt_predictor* p, vpt_batch* b, const uint
     E.mode = uint32_t(sys_tags);
     E.counts = d_counts;
     if (sys_tags == VPT_EVAL_TAGS_PREDICTED) {
-        E.sys_n_tags = p->n_tags;
-        if (p->n_tags) {
-            E.records = b->d_tag_records; E.rec_tags = b->d_rec_tags; E.rec_str = b->d_rec_str; E.run_pref = b->d_fill_run_pref; E.n_runs = b->tag_runs; E.run_sent = b->tag_run_sent;   // (fill_tags' own: the evaluate CLI runs no PatternMatchTagger)
-            E.str_bytes = p->dtag.str_bytes;
-        } else {
-            E.mode = vpt::kEvalTagsNone;   // predict_tags returns early without tag models (predictor.rs:553-555): every vector empty
-        }
+        // fill_tags' own records (the evaluate CLI runs no PatternMatchTagger), of a batch of as many sentences: the boundaries are not known here
+        if (!p->n_tags) E.mode = vpt::kEvalTagsNone;   // predict_tags returns early without tag models (predictor.rs:553-555): every vector empty
+        else if (const vpt_status st = tag_records_for(b, n_sentences, kBoundariesUnknown, false, &E.sys_tags); st != VPT_OK) return st;
     }
     VPT_HIP(vpt::launch_evaluate(E, stream));
     b->last_stream = stream; b->pending = true;

@@ -8,6 +8,7 @@
 #include "../../include/vaporetto_hip.h"
 #include "layout.h"
 #include "tables.hpp"
+#include "tag_records.h"
 
 namespace vpt {
 
@@ -133,7 +134,7 @@ struct TagParams {
     const uint64_t* ooff;       // [S+1]
     const uint8_t* labels;      // [total boundaries] CharacterBoundary values (0, 1, 2 = Unknown)
     uint64_t n_sent;
-    uint64_t total_chars;       // total boundaries + S: what `cps` holds (below 2^32 - 256: capi.cpp)
+    uint64_t total_chars;       // total boundaries + S: what `cps` holds (below 2^32 - 256: capi_device.cpp)
     const uint32_t *slot_str, *str_off;   // the tag strings' lengths (HostTagTables): what a token's tags take in the tokenized text
     uint32_t n_strings;
     // What fill_tags LEAVES (round 6): one RECORD per token that can have a tag model -- the reference holds None for every other char
@@ -165,16 +166,10 @@ struct TagParams {
     uint32_t score_stride;
     uint32_t n_cus;             // the device's CUs: the grids are what it holds at a time
     const uint32_t* summary;    // 2^(kTagSumLog2 - 5) words for the summary of the token filter (tag_filter_summary_kernel writes it, the front end reads it)
-    // The batch's control word.  THE RUNS' BOUND: the records are numbered by a scan over the runs' candidate counts and every array they index
-    // holds total_chars entries, so the runs the front end accepts may never cover more than total_chars chars.  Offsets that go down and up again
-    // make runs that overlap (each of them inside the batch on its own), so three things hold whatever the offsets say:
-    //   * decode_chars_kernel / the scoring kernel in front of these launches have raised kErrBadOffsets in this word for such offsets: the front
-    //     end then accepts no run at all (no candidates, no records);
-    //   * the scan has total_chars as its capacity and raises kErrBadOffsets past it;
-    //   * every reader of run_pref clamps what it reads to total_chars, and a record's char is checked against total_chars before it indexes
-    //     cps, tags, model_out or scores_out (tag_resolve_kernel, tag_pass_kernel, expand_tags_kernel, the writer, the pattern tagger's merge).
-    uint32_t* status;
+    uint32_t* status;           // the batch's control word; with kErrBadOffsets in it the front end accepts no run (THE RUNS' BOUND, tag_records.h)
 };
+// the records of P as their readers take them (the passes of fill_tags itself among them); str_bytes: the arena of the strings rec_str points into
+VPT_HD TagRecordsView records_view(const TagParams& P, const uint8_t* str_bytes = nullptr) { return {P.records, P.rec_tags, P.rec_str, P.run_pref, str_bytes, P.n_runs, P.total_chars, P.run_sent, P.n_tags}; }
 // sentences of a front-end run for a batch of this shape (about VPT_TAG_RUN_CHARS chars, at most 256 sentences); words of TagParams::summary
 uint32_t tag_run_sentences(uint64_t n_sent, uint64_t total_chars);
 size_t tag_summary_words();
@@ -194,14 +189,7 @@ struct EmitParams {
     uint64_t* out_offsets;      // [S+1] byte range of every sentence's tokenized text in out_text
     uint64_t capacity;
     uint32_t* status;
-    // "/tag" suffixes (sentence.rs:866-881), from the records the fill_tags call on this workspace left (TagParams); records == nullptr: none
-    const uint4* records;
-    const uint2* rec_str;       // [records * n_tags]: the strings of a record's suffix
-    const uint64_t* run_pref;   // [n_runs + 1]: records in front of run r of `run_sent` sentences
-    uint64_t n_runs;
-    uint32_t run_sent;
-    uint32_t n_tags;
-    const uint8_t* str_bytes;
+    TagRecordsView tag;         // "/tag" suffixes (sentence.rs:866-881), from the records the fill_tags call on this workspace left; records == nullptr: none
 };
 // scan_part: workspace of scan_part_entries(n_sent) uint64 (the prefix sum's per-workgroup partials)
 size_t scan_part_entries(uint64_t n);
@@ -223,8 +211,7 @@ struct EmitFuse {
 hipError_t launch_scan(uint64_t* offsets, uint64_t n, uint64_t* part, uint64_t capacity, uint32_t* status, uint64_t* total_out, hipStream_t stream,
                        uint32_t overflow_err = kErrOutputTooSmall);
 // vpt_expand_tags_batch_device: the dense tags array from the records (None everywhere else)
-hipError_t launch_expand_tags(const uint4* records, const int32_t* rec_tags, const uint64_t* n_records, uint32_t n_tags, uint64_t total_chars, int32_t* tags,
-                              uint32_t n_cus, hipStream_t stream);
+hipError_t launch_expand_tags(const TagRecordsView& V, int32_t* tags, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_emit_tokenized(const EmitParams& P, const EmitFuse& F, hipStream_t stream);
 // token spans (kernels_tokens.hip): vaporetto_tantivy's boundary_pos per document (vaporetto_tantivy/src/lib.rs:183-192), the writer's runs
 struct SpanParams {
@@ -271,13 +258,11 @@ struct PatternParams {
     const uint64_t* ooff;       // [S+1]
     const uint8_t* labels;      // [total boundaries]
     uint64_t n_sent, total_chars;
-    const uint4* records; const int32_t* rec_tags; const uint2* rec_str; const uint64_t* run_pref;   // what fill_tags left (TagParams)
-    uint64_t n_runs;
-    uint32_t run_sent;
+    TagRecordsView in;          // what fill_tags left (capacity = total_chars, n_tags = n_tags)
     uint2* hits;                // workspace [total_chars]: {rule + 1 | a new record << 31, new records of the run in front of the char}
     uint4* out_records; int32_t* out_rec_tags; uint2* out_rec_str;
-    uint64_t* out_run_pref;     // [n_runs + 1], zero in front of the launches
-    uint64_t* scan_state;       // scan_part_entries(n_runs) zero words
+    uint64_t* out_run_pref;     // [in.n_runs + 1], zero in front of the launches
+    uint64_t* scan_state;       // scan_part_entries(in.n_runs) zero words
     int32_t* tags;              // the dense array of the C ABI, or nullptr
     uint32_t n_cus;
     uint32_t* status;           // the batch's control word: with kErrBadOffsets in it no run is looked at (TagParams::status)
@@ -371,14 +356,7 @@ struct EvalParams {
     const uint64_t* span_off;
     const uint8_t* tag_bytes;
     uint32_t mode;              // kEvalTags*: the system's tag vectors are empty / the gold ones / fill_tags' records
-    uint32_t sys_n_tags;        // kEvalTagsPredicted: the predictor's n_tags
-    const uint4* records;       // ... the records fill_tags left on the workspace (TagParams)
-    const int32_t* rec_tags;
-    const uint2* rec_str;
-    const uint64_t* run_pref;   // [n_runs + 1]: the records of run r of `run_sent` sentences are [run_pref[r], run_pref[r + 1])
-    uint64_t n_runs;
-    uint32_t run_sent;
-    const uint8_t* str_bytes;
+    TagRecordsView sys_tags;    // kEvalTagsPredicted: the records fill_tags left on the workspace (n_tags: the predictor's)
     uint64_t* counts;
 };
 hipError_t launch_evaluate(const EvalParams& P, hipStream_t stream);

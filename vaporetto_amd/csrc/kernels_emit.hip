@@ -61,7 +61,7 @@ __device__ __forceinline__ uint32_t tag_suffix_bytes(const TagStrings P, uint64_
 }
 __device__ __noinline__ uint32_t tag_suffix(const TagStrings P, uint64_t ri, uint8_t* dst, uint32_t limit = 0xFFFFFFFFu) {   // (the rare paths: everything from HBM)
     const uint4 rec = P.records[ri];
-    return (rec.z & kTokModelMask) == 0 ? 0u : tag_suffix_write(P, ri, rec.w, nullptr, dst, limit);
+    return rec_has_model(rec) ? tag_suffix_write(P, ri, rec.w, nullptr, dst, limit) : 0u;
 }
 
 // the scan's state, zeroed by the kernel in front of it: workgroup b of that kernel clears word b (its grid is at least as large)
@@ -164,7 +164,7 @@ namespace {
 // prefix sums and barriers where a wave did them alone for 1 KB, and a workgroup looks back once where four waves did.)
 // kTags: "/tag" suffixes from the records of fill_tags (round 6).  The records are sorted by position and the front end's runs are runs of
 // sentences like this kernel's: the records of a workgroup's chars are ONE contiguous slice (run_pref of its first and last front-end run;
-// capi.cpp makes this kernel's runs whole multiples of those, anything else costs the slice's ends a compare).  Its suffix bytes are a
+// capi_device.cpp makes this kernel's runs whole multiples of those, anything else costs the slice's ends a compare).  Its suffix bytes are a
 // reduction over the slice; per piece the records whose chars lie in it are MARKED in LDS (a u16 per char: which record) with a coalesced
 // read, and a thread asks the marks of its chars -- where rounds 4 - 5 read a dense token word per char from HBM, twice, for one
 // token in thirty-five that had tags.
@@ -224,7 +224,7 @@ template <bool kTags>
 __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_OCC) void emit_flat_kernel(const EmitParams P, const EmitFuse F) {
     __shared__ FlatLds L;
     __shared__ FlatMarks MK[1];   // (with tags; the instance without never touches it and the compiler drops it)
-    const TagStrings TS{P.records, P.rec_str, P.str_bytes, P.n_tags};
+    const TagStrings TS{P.tag.records, P.tag.rec_str, P.tag.str_bytes, P.tag.n_tags};
     // the other array of state words, for the call after this one
     for (uint64_t k = uint64_t(blockIdx.x) * kEmitThreads + threadIdx.x; k < F.clear_n; k += uint64_t(gridDim.x) * kEmitThreads) F.clear[k] = 0;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
@@ -279,18 +279,13 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
     const uint64_t g0 = O0 + i0, g1 = O1 + i0 + ns;
     uint64_t r_lo = 0, r_hi = 0;
     if (kTags && sane) {
-        const uint64_t ra = i0 / P.run_sent, rb = (i0 + ns + P.run_sent - 1) / P.run_sent;
-        // (never a record past the arrays, whatever the counts say: they hold a record per char of the batch -- TagParams::status)
-        const uint64_t r_cap = P.total_boundaries + P.n_sent;
-        r_lo = wave_uniform64(P.run_pref[ra < P.n_runs ? ra : P.n_runs]);
-        r_hi = wave_uniform64(P.run_pref[rb < P.n_runs ? rb : P.n_runs]);
-        r_lo = r_lo < r_cap ? r_lo : r_cap;
-        r_hi = r_hi < r_cap ? r_hi : r_cap;
-        if (r_hi < r_lo) r_hi = r_lo;
-        if (i0 != ra * P.run_sent) {   // (the same in every thread) a run that starts inside a front-end run: its records begin further on
+        const uint64_t ra = i0 / P.tag.run_sent, rb = (i0 + ns + P.tag.run_sent - 1) / P.tag.run_sent;
+        records_of_runs(P.tag, ra, rb, &r_lo, &r_hi);   // (never a record past the arrays, whatever the counts say: tag_records.h)
+        r_lo = wave_uniform64(r_lo); r_hi = wave_uniform64(r_hi);
+        if (i0 != ra * P.tag.run_sent) {   // (the same in every thread) a run that starts inside a front-end run: its records begin further on
             for (;;) {
                 bool below = false;
-                if (r_lo + tid < r_hi) { const uint4 rec = P.records[r_lo + tid]; below = (uint64_t(rec.x) | (uint64_t(rec.y) << 32)) < g0; }
+                if (r_lo + tid < r_hi) below = rec_pos(P.tag.records[r_lo + tid]) < g0;
                 uint32_t n_below;
                 flat_block_scan(below ? 1u : 0u, L.wtot, lane, wave, &n_below);
                 r_lo += n_below;
@@ -324,8 +319,8 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
         }
         if (kTags) {   // the bytes of the run's tag suffixes: fill_tags left them in the records' token words (layout.h)
             for (uint64_t r = r_lo + tid; r < r_hi; r += kEmitThreads) {
-                const uint4 rec = P.records[r];
-                const uint64_t pos = uint64_t(rec.x) | (uint64_t(rec.y) << 32);
+                const uint4 rec = P.tag.records[r];
+                const uint64_t pos = rec_pos(rec);
                 if (pos >= g0 && pos < g1 && !(VPT_EMIT_ABLATE & 6)) added += tag_suffix_bytes(TS, r, rec.z, rec.w);
             }
         }
@@ -453,11 +448,11 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
                 const uint64_t r = rp + n_rec + tid;
                 bool in = false;
                 if (tid < width && r < r_hi) {
-                    const uint4 rec = P.records[r];
+                    const uint4 rec = P.tag.records[r];
                     const uint32_t si = n_rec + tid;
                     uint2 s0 = make_uint2(0u, 0u), s1 = s0;
-                    if (si < kStash) { s0 = P.rec_str[r * P.n_tags]; if (P.n_tags > 1) s1 = P.rec_str[r * P.n_tags + 1]; }
-                    const uint64_t pos = uint64_t(rec.x) | (uint64_t(rec.y) << 32);
+                    if (si < kStash) { s0 = P.tag.rec_str[r * P.tag.n_tags]; if (P.tag.n_tags > 1) s1 = P.tag.rec_str[r * P.tag.n_tags + 1]; }
+                    const uint64_t pos = rec_pos(rec);
                     in = pos < p_hi;
                     if (in && pos >= p_lo) {
                         marks[uint32_t(pos - p_lo) + 1u] = uint16_t(si + 1u);
@@ -488,7 +483,7 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
                     if (ri == ~uint64_t(0)) continue;
                     uint32_t word, last;
                     if (si != ~0u) { word = SK.word[si]; last = SK.last[si]; }
-                    else { const uint4 rec = P.records[ri]; word = rec.z; last = rec.w; }
+                    else { const uint4 rec = P.tag.records[ri]; word = rec.z; last = rec.w; }
                     const uint32_t len = tag_suffix_bytes(TS, ri, word, last);   // (carried from fill_tags)
                     if (!len) continue;
                     if (tk1 == 16) { tk1 = k; tl1 = len; tr1 = ri; ts1 = si; }
@@ -623,9 +618,9 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
                 if (next_si != kStash) {
                     if (next_si != ~0u) { SK.word[kStash] = SK.word[next_si]; SK.last[kStash] = SK.last[next_si]; SK.str[kStash][0] = SK.str[next_si][0]; SK.str[kStash][1] = SK.str[next_si][1]; }
                     else {
-                        const uint4 rec = P.records[carry_rec];
+                        const uint4 rec = P.tag.records[carry_rec];
                         SK.word[kStash] = rec.z; SK.last[kStash] = rec.w;
-                        SK.str[kStash][0] = P.rec_str[carry_rec * P.n_tags]; SK.str[kStash][1] = P.n_tags > 1 ? P.rec_str[carry_rec * P.n_tags + 1] : make_uint2(0u, 0u);
+                        SK.str[kStash][0] = P.tag.rec_str[carry_rec * P.tag.n_tags]; SK.str[kStash][1] = P.tag.n_tags > 1 ? P.tag.rec_str[carry_rec * P.tag.n_tags + 1] : make_uint2(0u, 0u);
                     }
                 }
             }
@@ -649,8 +644,8 @@ __global__ __launch_bounds__(kEmitThreads, kTags ? VPT_EMIT_TAG_OCC : VPT_EMIT_O
         sb += tot >> 16;
     }
     if (kTags && fits && carry_rec != ~uint64_t(0) && !(VPT_EMIT_ABLATE & 6)) {   // the tags of the run's last token: the record, if any, of its last char
-        const uint4 rec = P.records[carry_rec];
-        const uint32_t sl = (uint64_t(rec.x) | (uint64_t(rec.y) << 32)) == g1 - 1 ? tag_suffix(TS, carry_rec, nullptr) : 0u;   // (every thread computes the same)
+        const uint4 rec = P.tag.records[carry_rec];
+        const uint32_t sl = rec_pos(rec) == g1 - 1 ? tag_suffix(TS, carry_rec, nullptr) : 0u;   // (every thread computes the same)
         if (sl && store_ok && at_out + sl <= end && tid == 0) tag_suffix(TS, carry_rec, P.out_text + at_out);
         at_out += sl;
     }
@@ -772,7 +767,7 @@ hipError_t launch_count_boundaries(const uint8_t* text, const uint64_t* boff, ui
 }
 
 hipError_t launch_emit_tokenized(const EmitParams& P, const EmitFuse& F, hipStream_t stream) {   // a workgroup per run of sentences
-    if (P.records) hipLaunchKernelGGL(emit_flat_kernel<true>, dim3(uint32_t(F.n_blocks)), dim3(kEmitThreads), 0, stream, P, F);
+    if (P.tag.records) hipLaunchKernelGGL(emit_flat_kernel<true>, dim3(uint32_t(F.n_blocks)), dim3(kEmitThreads), 0, stream, P, F);
     else hipLaunchKernelGGL(emit_flat_kernel<false>, dim3(uint32_t(F.n_blocks)), dim3(kEmitThreads), 0, stream, P, F);
     return hipGetLastError();
 }

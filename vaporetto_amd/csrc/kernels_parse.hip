@@ -349,17 +349,10 @@ __global__ __launch_bounds__(kParseThreads) void write_partial_kernel(const Writ
 
 // ---- evaluate
 
-// the record fill_tags left for flat char g (kernels.hpp, TagParams::records), or ~0; [lo, hi): the records of the run of sentences
-// that holds g (run_pref: fill_tags numbers a run's records contiguously, in order)
+// the record fill_tags left for flat char g, or ~0; [lo, hi): the records of the run of sentences that holds g (tag_records.h)
 __device__ uint64_t find_record(const EvalParams& P, uint64_t lo, uint64_t hi, uint64_t g) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const uint4 r = P.records[mid];
-        const uint64_t at = uint64_t(r.x) | (uint64_t(r.y) << 32);
-        if (at == g) return (r.z & kTokModelMask) ? mid : ~uint64_t(0);
-        if (at < g) lo = mid + 1; else hi = mid;
-    }
-    return ~uint64_t(0);
+    const uint64_t k = records_lower_bound(P.sys_tags.records, lo, hi, g);
+    return k < hi && rec_pos(P.sys_tags.records[k]) == g && rec_has_model(P.sys_tags.records[k]) ? k : ~uint64_t(0);
 }
 
 // the tag vector of char g (sentence i) of the gold side equals that of the system side (evaluate/src/main.rs:111-122, 163, 181)
@@ -367,23 +360,23 @@ __device__ bool tags_equal(const EvalParams& P, uint64_t rec_lo, uint64_t rec_hi
     if (P.mode == kEvalTagsGold) return true;
     const uint32_t nt = P.gold_n_tags[i];
     if (P.mode == kEvalTagsNone) return nt == 0;
-    if (nt != P.sys_n_tags) return false;
+    if (nt != P.sys_tags.n_tags) return false;
     const uint64_t t0 = P.tag_index[g], own = P.tag_index[g + 1] - t0;
     const uint64_t rec = find_record(P, rec_lo, rec_hi, g);
     for (uint32_t j = 0; j < nt; ++j) {
         uint64_t gs = 0, gl = 0;   // gold: bytes of tag j (empty: None)
         if (j < own) { gs = P.span_off[t0 + j]; gl = P.span_off[t0 + j + 1] - gs; }
-        const int32_t t = rec != ~uint64_t(0) ? P.rec_tags[rec * P.sys_n_tags + j] : -1;
+        const int32_t t = rec != ~uint64_t(0) ? P.sys_tags.rec_tags[rec * P.sys_tags.n_tags + j] : -1;
         if (t < 0 || gl == 0) {
             if ((t < 0) != (gl == 0)) return false;
             continue;
         }
         // the candidate string is stored escaped as write_tokenized_text writes it (tables.hpp, str_bytes): compare it unescaped
-        const uint2 s = P.rec_str[rec * P.sys_n_tags + j];
+        const uint2 s = P.sys_tags.rec_str[rec * P.sys_tags.n_tags + j];
         uint64_t k = 0;
         for (uint32_t q = 0; q < s.y; ++q) {
-            uint8_t ch = P.str_bytes[s.x + q];
-            if (ch == '\\' && q + 1 < s.y) ch = P.str_bytes[s.x + ++q];
+            uint8_t ch = P.sys_tags.str_bytes[s.x + q];
+            if (ch == '\\' && q + 1 < s.y) ch = P.sys_tags.str_bytes[s.x + ++q];
             if (k >= gl || P.tag_bytes[gs + k] != ch) return false;
             ++k;
         }
@@ -401,11 +394,7 @@ __global__ __launch_bounds__(kParseThreads) void evaluate_kernel(const EvalParam
         const uint64_t b0 = P.ooff[i], nb = P.ooff[i + 1] - b0, g0 = b0 + i;
         int64_t last_a = -1, last_d = -2;
         uint64_t rec_lo = 0, rec_hi = 0;
-        if (P.mode == kEvalTagsPredicted) {
-            const uint64_t run = i / P.run_sent;
-            rec_lo = P.run_pref[run];
-            rec_hi = P.run_pref[run + 1];
-        }
+        if (P.mode == kEvalTagsPredicted) { const uint64_t run = i / P.sys_tags.run_sent; records_of_runs(P.sys_tags, run, run + 1, &rec_lo, &rec_hi); }
         for (uint64_t w0 = 0; w0 < nb; w0 += 64) {
             const bool valid = w0 + lane < nb;
             const uint32_t r = valid ? P.gold[b0 + w0 + lane] : 0u, s = valid ? P.sys[b0 + w0 + lane] : 0u;

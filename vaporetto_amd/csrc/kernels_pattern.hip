@@ -35,20 +35,9 @@ constexpr uint32_t kPmCharMask = 0x1FFFFFu;   // a cps word: scored scalar value
 constexpr uint32_t kPmNew = 0x80000000u;
 constexpr uint32_t kPmMaxRunSent = 256;       // sentences of a front-end run, at most (tag_run_sentences); sst holds their starts and the run's end
 
-__device__ __forceinline__ uint64_t rec_pos(const uint4& r) { return uint64_t(r.x) | (uint64_t(r.y) << 32); }
-// records of the slice [lo, hi) in front of position gp (they are sorted by position)
-__device__ __forceinline__ uint64_t records_before(const uint4* __restrict__ records, uint64_t lo, uint64_t hi, uint64_t gp) {
-    const uint64_t lo0 = lo;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (rec_pos(records[mid]) < gp) lo = mid + 1; else hi = mid;
-    }
-    return lo - lo0;
-}
-
 // what both kernels know of a run: its sentences, its chars [run0, run0 + n), its records [r_lo, r_hi); ok == false: offsets or counts that do not
 // fit the batch (reported by decode_chars_kernel / the scoring kernel in the batch's control word, which is looked at here: runs of such offsets can
-// overlap, TagParams::status) -- the run keeps its records and gets no rule tags
+// overlap, tag_records.h) -- the run keeps its records and gets no rule tags; records that do not fit the arrays are dropped, not clamped
 struct PmRun {
     uint64_t i_a, run0, r_lo, r_hi;
     uint32_t ns, n;
@@ -56,13 +45,12 @@ struct PmRun {
 };
 __device__ __forceinline__ PmRun pm_run(const PatternParams& P, uint64_t run) {
     PmRun R;
-    R.i_a = run * P.run_sent;
-    const uint64_t i_b = R.i_a + P.run_sent < P.n_sent ? R.i_a + P.run_sent : P.n_sent;
+    R.i_a = run * P.in.run_sent;
+    const uint64_t i_b = R.i_a + P.in.run_sent < P.n_sent ? R.i_a + P.in.run_sent : P.n_sent;
     R.ns = uint32_t(i_b - R.i_a);
     R.run0 = P.ooff[R.i_a] + R.i_a;
     const uint64_t run1 = P.ooff[i_b] + i_b;
-    R.r_lo = P.run_pref[run]; R.r_hi = P.run_pref[run + 1];
-    const bool recs = R.r_hi >= R.r_lo && R.r_hi <= P.total_chars;
+    const bool recs = records_of_runs(P.in, run, run + 1, &R.r_lo, &R.r_hi);
     if (!recs) { R.r_lo = 0; R.r_hi = 0; }
 #ifdef VPT_TAG_NO_OFFSETS_GATE   // (test builds, kernels_tags.hip)
     const bool gate = false;
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(kPmThreads) void pattern_match_kernel(const Pattern
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
     const uint64_t total_b = P.total_chars - P.n_sent;
     const uint32_t mask = (1u << P.bits) - 1u;
-    for (uint64_t run = blockIdx.x; run < P.n_runs; run += gridDim.x) {
+    for (uint64_t run = blockIdx.x; run < P.in.n_runs; run += gridDim.x) {
         const PmRun R = pm_run(P, run);
         __syncthreads();   // (the run before is done with sst / wtot / bad)
         if (tid == 0) bad = 0;
@@ -136,8 +124,8 @@ __global__ __launch_bounds__(kPmThreads) void pattern_match_kernel(const Pattern
                     }
                 }
                 if (hit) {   // has the token a record already?
-                    const uint64_t gp = R.run0 + q, k = R.r_lo + records_before(P.records, R.r_lo, R.r_hi, gp);
-                    is_new = !(k < R.r_hi && rec_pos(P.records[k]) == gp);
+                    const uint64_t gp = R.run0 + q, k = records_lower_bound(P.in.records, R.r_lo, R.r_hi, gp);
+                    is_new = !(k < R.r_hi && rec_pos(P.in.records[k]) == gp);
                 }
             }
             // the new records in front of the char: a prefix sum over the workgroup, carried from step to step
@@ -168,16 +156,17 @@ __device__ __forceinline__ void rule_slot(const PatternParams& P, uint32_t rule,
 
 __global__ __launch_bounds__(kPmThreads) void pattern_merge_kernel(const PatternParams P) {
     const uint32_t tid = threadIdx.x, nt = P.n_tags;
-    for (uint64_t run = blockIdx.x; run < P.n_runs; run += gridDim.x) {
+    for (uint64_t run = blockIdx.x; run < P.in.n_runs; run += gridDim.x) {
         const PmRun R = pm_run(P, run);
-        const uint64_t o_lo = P.out_run_pref[run];
+        TagRecordsView out = P.in; out.run_pref = P.out_run_pref;   // (the merged records: their runs' first records come through the same accessor)
+        const uint64_t o_lo = run_first_record(out, run);
         const bool have_hits = R.n != 0;   // (the first kernel left an entry per char of the run)
         // ---- the new records
         for (uint32_t q = tid; have_hits && q < R.n; q += uint32_t(kPmThreads)) {
             const uint64_t gp = R.run0 + q;
             const uint2 h = P.hits[gp];
             if (!(h.x & kPmNew)) continue;
-            const uint64_t k = o_lo + records_before(P.records, R.r_lo, R.r_hi, gp) + h.y;
+            const uint64_t k = o_lo + (records_lower_bound(P.in.records, R.r_lo, R.r_hi, gp) - R.r_lo) + h.y;
             if (k >= P.total_chars) continue;   // (cannot be: a record per char at most)
             const uint32_t rule = (h.x & ~kPmNew) - 1u;
             uint32_t bytes = 0, last = 0;
@@ -195,7 +184,7 @@ __global__ __launch_bounds__(kPmThreads) void pattern_merge_kernel(const Pattern
         }
         // ---- fill_tags' records, moved up by the new ones in front of them; the None slots of a token the rules name are filled
         for (uint64_t r = R.r_lo + tid; r < R.r_hi; r += uint32_t(kPmThreads)) {
-            const uint4 rec = P.records[r];
+            const uint4 rec = P.in.records[r];
             const uint64_t gp = rec_pos(rec);
             uint2 h = make_uint2(0u, 0u);
             if (have_hits && gp >= R.run0 && gp - R.run0 < R.n) h = P.hits[gp];
@@ -205,8 +194,8 @@ __global__ __launch_bounds__(kPmThreads) void pattern_merge_kernel(const Pattern
             bool changed = false;
             uint32_t bytes = 0, last = 0;
             for (uint32_t j = 0; j < nt; ++j) {
-                int32_t tag = model ? P.rec_tags[r * nt + j] : -1;   // (an empty record: the passes wrote nothing for it)
-                uint2 str = model ? P.rec_str[r * nt + j] : make_uint2(0u, 0u);
+                int32_t tag = model ? P.in.rec_tags[r * nt + j] : -1;   // (an empty record: the passes wrote nothing for it)
+                uint2 str = model ? P.in.rec_str[r * nt + j] : make_uint2(0u, 0u);
                 if (tag == -1 && hit) {
                     rule_slot(P, hit - 1u, j, &tag, &str);
                     if (tag != -1) { changed = true; if (P.tags) P.tags[gp * nt + j] = tag; }
@@ -226,14 +215,14 @@ __global__ __launch_bounds__(kPmThreads) void pattern_merge_kernel(const Pattern
 }  // namespace
 
 hipError_t launch_pattern_tagger(const PatternParams& P, hipStream_t stream) {
-    if (P.n_runs == 0) return hipSuccess;
+    if (P.in.n_runs == 0) return hipSuccess;
     // a workgroup per run, as many as the device holds at a time (8 of 4 waves per CU), striding over the runs
     const uint64_t cap = uint64_t(P.n_cus ? P.n_cus : 256u) * 8u;
-    const dim3 grid(uint32_t(P.n_runs < cap ? P.n_runs : cap)), block(kPmThreads);
+    const dim3 grid(uint32_t(P.in.n_runs < cap ? P.in.n_runs : cap)), block(kPmThreads);
     hipLaunchKernelGGL(pattern_match_kernel, grid, block, 0, stream, P);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = launch_scan(P.out_run_pref, P.n_runs, P.scan_state, P.total_chars, P.status, nullptr, stream, kErrBadOffsets);
+    e = launch_scan(P.out_run_pref, P.in.n_runs, P.scan_state, P.total_chars, P.status, nullptr, stream, kErrBadOffsets);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pattern_merge_kernel, grid, block, 0, stream, P);
     return hipGetLastError();

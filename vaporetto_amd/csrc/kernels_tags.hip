@@ -531,9 +531,8 @@ __global__ __launch_bounds__(kTagThreads) void tag_resolve_kernel(const TagParam
     for (uint64_t r_first = wave * kResolveRuns; r_first < P.n_runs; r_first += n_waves * kResolveRuns) {
         const uint32_t nr = uint32_t(P.n_runs - r_first < kResolveRuns ? P.n_runs - r_first : kResolveRuns);
         __builtin_amdgcn_wave_barrier();
-        // the runs' first records (= their candidates' numbers: candidate c IS record c) and first chars, one trip for all of them
-        // (clamped: the records' arrays hold total_chars entries -- TagParams::status)
-        if (uint32_t(lane) <= nr) { const uint64_t f = P.run_pref[r_first + uint32_t(lane)]; PREF[wid][lane] = f < P.total_chars ? f : P.total_chars; }
+        // the runs' first records (= their candidates' numbers: candidate c IS record c; never past the arrays: tag_records.h) and first chars, one trip for all of them
+        if (uint32_t(lane) <= nr) PREF[wid][lane] = run_first_record(records_view(P), r_first + uint32_t(lane));
         if (uint32_t(lane) < nr) { const uint64_t i_a = (r_first + uint32_t(lane)) * P.run_sent; RUN0[wid][lane] = P.ooff[i_a] + i_a; }
         __builtin_amdgcn_wave_barrier();
         const uint64_t c_lo = PREF[wid][0], c_hi = PREF[wid][nr];
@@ -576,8 +575,7 @@ __global__ __launch_bounds__(kTagThreads, kTagPairOcc) void tag_pass_kernel(cons
     TagWaveLds& L = LDS[wid];
     const uint64_t below_me = (uint64_t(1) << lane) - 1;
     const uint64_t wave = uint64_t(blockIdx.x) * kTagWaves + wid, n_waves = uint64_t(gridDim.x) * kTagWaves;
-    const uint64_t n_all = wave_uniform64(P.run_pref[P.n_runs]);
-    const uint64_t n_rec = n_all < P.total_chars ? n_all : P.total_chars;   // (clamped: TagParams::status)
+    const uint64_t n_rec = wave_uniform64(records_count(records_view(P)));
     uint32_t nq = 0;
     for (uint64_t c0 = wave * 64; c0 < n_rec; c0 += n_waves * 64) {
         const uint64_t c = c0 + uint32_t(lane);
@@ -1022,21 +1020,19 @@ hipError_t launch_tag_tokens(const TagParams& P, hipStream_t stream) {
 
 // vpt_expand_tags_batch_device: the dense array of the C ABI from the records -- None everywhere (the reference's Vec<Option<..>> after
 // `resize(n_tags * len, None)`, predictor.rs:556-557), then the records' tags at their tokens' last chars
-__global__ __launch_bounds__(256) void expand_tags_kernel(const uint4* __restrict__ records, const int32_t* __restrict__ rec_tags, const uint64_t* __restrict__ n_records,
-                                                          const uint32_t n_tags, const uint64_t total_chars, int32_t* __restrict__ tags) {
-    const uint64_t n_all = *n_records, n = n_all < total_chars ? n_all : total_chars, n_items = n * n_tags;   // (clamped: TagParams::status)
+__global__ __launch_bounds__(256) void expand_tags_kernel(const TagRecordsView V, int32_t* __restrict__ tags) {
+    const uint64_t n_tags = V.n_tags, n_items = records_count(V) * n_tags;
     for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n_items; i += uint64_t(gridDim.x) * 256u) {
         const uint64_t k = i / n_tags, j = i - k * n_tags;
-        const uint4 r = records[k];
-        const uint64_t gp = uint64_t(r.x) | (uint64_t(r.y) << 32);
-        if (gp < total_chars && (r.z & kTokModelMask) != 0) tags[gp * n_tags + j] = rec_tags[i];   // (an empty record: a candidate without a tag model)
+        const uint4 r = V.records[k];
+        const uint64_t gp = rec_pos(r);
+        if (gp < V.capacity && rec_has_model(r)) tags[gp * n_tags + j] = V.rec_tags[i];   // (an empty record: a candidate without a tag model)
     }
 }
-hipError_t launch_expand_tags(const uint4* records, const int32_t* rec_tags, const uint64_t* n_records, uint32_t n_tags, uint64_t total_chars, int32_t* tags,
-                              uint32_t n_cus, hipStream_t stream) {
-    const hipError_t e = hipMemsetAsync(tags, 0xFF, size_t(total_chars) * n_tags * sizeof(int32_t), stream);
+hipError_t launch_expand_tags(const TagRecordsView& V, int32_t* tags, uint32_t n_cus, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(tags, 0xFF, size_t(V.capacity) * V.n_tags * sizeof(int32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(expand_tags_kernel, dim3((n_cus ? n_cus : 256u) * 8u), dim3(256), 0, stream, records, rec_tags, n_records, n_tags, total_chars, tags);
+    hipLaunchKernelGGL(expand_tags_kernel, dim3((n_cus ? n_cus : 256u) * 8u), dim3(256), 0, stream, V, tags);
     return hipGetLastError();
 }
 
