@@ -228,6 +228,14 @@ vpt_status vpt_batch_sync(vpt_batch *b);
  * positions (chars + separators) a tile covers, and the kind -- 1 whole-sentence tiles, 2 tiles cut at any position with a halo
  * (batches with sentences too long for a tile), 0 the general kernels (models outside the packed shape). */
 vpt_status vpt_batch_last_plan(const vpt_batch *b, uint32_t *n_tiles, uint32_t *tile_flat, uint32_t *kind);
+/* The cache policy under which the last vpt_predict_batch_device call on this workspace loaded its text (diagnostics): 0 plain, 1 non-temporal.
+ * The library chooses per launch from the bytes the launch streams (vpt_text_policy_for); the general kernels always load it plain. */
+vpt_status vpt_batch_last_text_policy(const vpt_batch *b, uint32_t *policy);
+/* The rule itself (a pure function of the host; diagnostics and tests): the policy of a launch that scores `text_bytes` of text with
+ * `total_boundaries` boundaries and writes scores (4 bytes each) and / or labels (1 byte each), and the threshold the rule compares their
+ * sum with.  Either pointer may be NULL. */
+vpt_status vpt_text_policy_for(uint64_t text_bytes, uint64_t total_boundaries, int want_scores, int want_labels, uint32_t *policy,
+                               uint64_t *threshold_bytes);
 /* How the last vpt_fill_tags_batch_device call on this workspace cut its batch (diagnostics): the number of front-end runs and the
  * sentences of a run (the last run may hold fewer); both 0 before the first call.  Either pointer may be NULL. */
 vpt_status vpt_batch_tag_plan(const vpt_batch *b, uint64_t *n_runs, uint32_t *run_sentences);

@@ -3,6 +3,7 @@
 #   tools/build_variants.sh name:"-DVPT_FAST_CC=1024 -DVPT_FAST_WG=7" ...
 # and of the cache policy of a class of its accesses (kernels_fast.hip, kPol*: 0 plain, 1 non-temporal, 2 agent scope):
 #   tools/build_variants.sh nt_text:"-DVPT_POL_TEXT=1" sc1_out:"-DVPT_POL_SCORE=2 -DVPT_POL_LABEL=2" ...
+# (the text's policy is the launch's choice unless a variant fixes it: -DVPT_POL_TEXT=0 plain, =1 non-temporal)
 # A variant whose definitions are all VPT_POL_* differs in kernels_fast.hip only: the other sources (vaporetto_amd/build.py, SOURCES) are compiled
 # once and shared by those.  Any other definition may reach every source (VPT_FAST_CAP is the host's too): such a variant is compiled whole.
 set -e

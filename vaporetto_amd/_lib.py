@@ -89,6 +89,8 @@ SIGNATURES = {
     "vpt_predictor_n_tags": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vpt_fill_tags_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
     "vpt_batch_last_plan": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "vpt_batch_last_text_policy": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vpt_text_policy_for": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "vpt_batch_tag_plan": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "vpt_predictor_tag_score_stride": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vpt_fill_tags_scores_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_uint, _P, _P, _P]),

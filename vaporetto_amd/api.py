@@ -1382,9 +1382,14 @@ class DeviceBatch:
         st = _lib.load().vpt_batch_tag_plan(self._h, C.byref(runs), C.byref(run_sent))
         if st != _lib.VPT_OK:
             _raise(st)
-        # tag_runs / tag_run_sent: the front-end runs of the last fill_tags call and the sentences of a run (vpt_batch_tag_plan)
+        pol = C.c_uint32()
+        st = _lib.load().vpt_batch_last_text_policy(self._h, C.byref(pol))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        # tag_runs / tag_run_sent: the front-end runs of the last fill_tags call and the sentences of a run (vpt_batch_tag_plan);
+        # text_policy: how the scoring launch loaded its text (vpt_batch_last_text_policy)
         return {"tiles": n.value, "tile_flat": tf.value, "kind": ("general kernels", "whole-sentence tiles", "cut tiles")[min(kind.value, 2)],
-                "tag_runs": runs.value, "tag_run_sent": run_sent.value}
+                "tag_runs": runs.value, "tag_run_sent": run_sent.value, "text_policy": ("plain", "nt")[min(pol.value, 1)]}
 
     def kernel_times(self) -> np.ndarray:
         """Durations (ms) of the timed scoring-kernel launches since the last kernel_ms(), oldest first (at most 256)."""

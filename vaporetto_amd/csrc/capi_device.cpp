@@ -127,6 +127,13 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     if (b->knobs.debug_ablate) { P.debug = b->knobs.debug_ablate; P.ct.debug = P.debug; P.tt.debug = P.debug; }
 
     P.n_sent = n_sentences; P.tile_flat = uint32_t(tile_flat); P.n_tiles = n_tiles;
+    // The text's cache policy (capi_internal.hpp, text_policy_for).  The offsets are on the device: the text's bytes are bounded from what
+    // the caller says of the batch -- at most 4 a char and max_sentence_bytes a sentence (exact for sentences of one length).
+    if (fast) {
+        const uint64_t text_bytes = std::min<uint64_t>(total_chars * 4, uint64_t(n_sentences) * max_sentence_bytes);
+        P.text_nt = b->knobs.text_policy >= 0 ? uint32_t(b->knobs.text_policy)
+                                              : text_policy_for(text_bytes, launch_output_bytes(total_boundaries, d_scores != nullptr, d_labels != nullptr));
+    }
     // the tiles (a kernel of its own: finding them at the head of every workgroup measured slower, profiles/r02_c1_ab.jsonl); for
     // cut tiles preceded by the lead-byte index of the text
     if (fast && cut_tiles) VPT_HIP(vpt::launch_assign_tiles_cut(P, cut, n_tiles, total_chars, b->d_cut_local, b->d_cut_super, b->d_tiles, b->d_ctrl, stream));
@@ -144,6 +151,7 @@ vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8
     if (b->timing) { VPT_HIP(hipEventRecord(b->ev[2 * slot + 1], stream)); ++b->ev_calls; }
     b->last_tiles = n_tiles; b->last_stream = stream; b->pending = true;
     b->last_tile_flat = uint32_t(tile_flat); b->last_plan = !fast ? 0u : cut_tiles ? 2u : 1u;
+    b->last_text_policy = P.text_nt;
     // ConcatGraphemeClustersFilter: behind the scoring launch (whose epilogue applied the other label filters) on its stream, in front of
     // whatever the caller enqueues on the labels
     if ((b->flags & VPT_FLAG_CONCAT_GRAPHEMES) && d_labels)
@@ -255,6 +263,18 @@ vpt_status vpt_batch_last_plan(const vpt_batch* b, uint32_t* n_tiles, uint32_t* 
     if (n_tiles) *n_tiles = b->last_tiles;
     if (tile_flat) *tile_flat = b->last_tile_flat;
     if (kind) *kind = b->last_plan;
+    return VPT_OK;
+}
+
+vpt_status vpt_batch_last_text_policy(const vpt_batch* b, uint32_t* policy) {
+    if (!b || !policy) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *policy = b->last_text_policy;
+    return VPT_OK;
+}
+
+vpt_status vpt_text_policy_for(uint64_t text_bytes, uint64_t total_boundaries, int want_scores, int want_labels, uint32_t* policy, uint64_t* threshold_bytes) {
+    if (policy) *policy = text_policy_for(text_bytes, launch_output_bytes(total_boundaries, want_scores != 0, want_labels != 0));
+    if (threshold_bytes) *threshold_bytes = kTextNtMinStreamBytes;
     return VPT_OK;
 }
 

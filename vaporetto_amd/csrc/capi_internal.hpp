@@ -58,6 +58,7 @@ struct BatchKnobs {
     uint32_t debug_ablate = 0;          // VPT_DEBUG_ABLATE
     bool profile_phases = false;        // VPT_PROFILE_PHASES
     uint32_t emit_per_block = 0;        // VPT_EMIT_PER_BLOCK: sentences a workgroup of the writer takes (1..512; 0: from the mean sentence length) -- tests: runs of any size
+    int text_policy = -1;               // VPT_TEXT_POLICY=plain|nt: how the specialised kernel loads the text, 0 / 1 (-1, unset: text_policy_for decides per launch)
 };
 PredictorKnobs read_predictor_knobs() {
     PredictorKnobs k;
@@ -76,8 +77,23 @@ BatchKnobs read_batch_knobs() {
     if (const char* v = std::getenv("VPT_EMIT_PER_BLOCK")) k.emit_per_block = uint32_t(std::min(512, std::max(0, std::atoi(v))));
     if (const char* v = std::getenv("VPT_DEBUG_ABLATE")) k.debug_ablate = uint32_t(std::atoi(v));
     k.profile_phases = std::getenv("VPT_PROFILE_PHASES") != nullptr;
+    if (const char* v = std::getenv("VPT_TEXT_POLICY")) k.text_policy = std::strcmp(v, "nt") == 0 ? 1 : std::strcmp(v, "plain") == 0 ? 0 : -1;
     return k;
 }
+
+// How the specialised scoring kernel loads a launch's text (ScoreParams::text_nt): plain, or non-temporal -- around the vector L1, and marked
+// in the L2 as the line to give up first.  What decides is how much the launch streams through the L2 and the Infinity Cache beside the table
+// gathers that need them: its text and its outputs (4 bytes of score and 1 of label a boundary).  A launch that streams less than the caches
+// hold gains nothing from sparing them and, scored again on the same buffers, finds its text still there; one that streams far more evicts
+// table lines with text it reads once.  Measured on MI355X over 100 K .. 10 M sentences of 64 chars, configs[3]'s model and whole documents
+// (profiles/text_policy_sweep.jsonl): the threshold lies between the largest batch on which plain was not slower (300 K
+// sentences: 58 MB + 95 MB, plain 2.9 % faster) and the smallest on which `nt` won by more than the rounds' spread (1 M: 192 MB + 315 MB,
+// `nt` 3.2 % faster) -- at the size of the Infinity Cache, 256 MiB.
+constexpr uint64_t kTextNtMinStreamBytes = uint64_t(256) << 20;
+inline uint64_t launch_output_bytes(uint64_t total_boundaries, bool want_scores, bool want_labels) {
+    return total_boundaries * ((want_scores ? 4u : 0u) + (want_labels ? 1u : 0u));
+}
+inline uint32_t text_policy_for(uint64_t text_bytes, uint64_t output_bytes) { return text_bytes + output_bytes > kTextNtMinStreamBytes ? 1u : 0u; }
 
 constexpr size_t kTimingRing = 256;     // timed launches remembered per vpt_batch
 constexpr size_t kTablePadBytes = 256;  // probes read whole 16-byte chunks; keep the tail of every table readable
@@ -306,6 +322,7 @@ struct vpt_batch {
     std::vector<hipEvent_t> ev;        // ring of (start, stop) pairs around the scoring kernel
     size_t ev_calls = 0;               // timed calls since the last vpt_batch_kernel_ms
     uint32_t last_tiles = 0, last_tile_flat = 0, last_plan = 0;   // last_plan: 0 general kernels, 1 whole-sentence tiles, 2 cut tiles
+    uint32_t last_text_policy = 0;     // the text's cache policy in the last scoring launch: 0 plain (the general kernels: always), 1 non-temporal
     hipStream_t last_stream = nullptr; bool pending = false;
     // staging for the host-buffer entry points
     hipStream_t own_stream = nullptr;

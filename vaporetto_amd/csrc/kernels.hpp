@@ -103,6 +103,7 @@ struct ScoreParams {
     uint32_t post;              // label post-filters: bits 1..6 KyteaWsConstFilter per CharacterType, bit 7 SplitLinebreaksFilter, bit 8: that one FIRST
     uint32_t force_window_table;// experiment knob (read when the predictor is made): the 8^(2W) type table although type rows exist
     uint32_t debug;             // profiling ablation bits (VPT_DEBUG_ABLATE env, 0 in production)
+    uint32_t text_nt;           // specialised kernel: the text is loaded non-temporal (1) or plain (0) -- the launch's choice (capi_internal.hpp, text_policy_for)
     uint64_t* prof;             // per-phase shader-cycle counters (VPT_PROFILE_PHASES env), else nullptr
 };
 
@@ -123,6 +124,7 @@ struct TileDesc {
     uint32_t rsv0, rsv1;
 };
 static_assert(sizeof(TileDesc) == 64, "four 16-byte scalar loads");
+static_assert(sizeof(ScoreParams) == 488, "the scoring kernels' parameter block (DESIGN.md 4.1; text_nt sits in what was padding in front of `prof`)");
 
 // tag prediction (kernels_tags.hip); table layouts: HostTagTables in tables.hpp
 struct TagParams {

@@ -42,11 +42,14 @@ namespace {
 // Cache policy of every class of global access of the scoring kernel (device_common.h, MemPolicy).  A/B builds (tools/build_variants.sh) name
 // another with -DVPT_POL_<CLASS>=0|1|2: plain, non-temporal, agent scope.  Measured on MI355X (profiles/cache_policy_*): the outputs
 // -- 3.1 GB a launch on configs[2], never read back by the kernel -- stored non-temporal make the kernel 2.7 % faster there and 0.6-0.7 % on
-// 100 K sentences; agent-scope stores cost 6.6 %; every gather wants its L1 hits (a class that bypasses the L1 costs 20-30 % each); non-temporal
-// text is 1.9 % faster on 10 M sentences and 2 % slower on 100 K, whose text the chip's caches still hold from the step before: it stays plain.
+// 100 K sentences; agent-scope stores cost 6.6 %; every gather wants its L1 hits (a class that bypasses the L1 costs 20-30 % each).  The TEXT is the
+// one class whose best policy depends on the batch (non-temporal wins on batches that stream far more than the chip's caches hold, plain on small
+// ones scored again and again: profiles/text_policy_sweep.jsonl), so it is a parameter of the launch (ScoreParams::text_nt, set by the host's rule:
+// capi_internal.hpp, text_policy_for) unless a build fixes it with -DVPT_POL_TEXT=0|1.
 #ifndef VPT_POL_TEXT
-#define VPT_POL_TEXT 0
+#define VPT_POL_TEXT -1
 #endif
+static_assert(VPT_POL_TEXT >= -1 && VPT_POL_TEXT <= 1, "the text: -1 the launch decides, 0 plain, 1 non-temporal (a 16-byte load has no agent-scope form)");
 #ifndef VPT_POL_OFFSETS
 #define VPT_POL_OFFSETS 0
 #endif
@@ -77,7 +80,7 @@ namespace {
 #ifndef VPT_POL_LABEL
 #define VPT_POL_LABEL 1
 #endif
-constexpr MemPolicy kPolText = MemPolicy(VPT_POL_TEXT);         // the tile's text, staged into LDS: read once (and once more by a neighbouring cut tile)
+constexpr int kPolTextFixed = VPT_POL_TEXT;                     // the tile's text, staged into LDS: read once (and once more by a neighbouring cut tile)
 constexpr MemPolicy kPolOffsets = MemPolicy(VPT_POL_OFFSETS);   // boff / ooff of the tile's sentences
 constexpr MemPolicy kPolCid = MemPolicy(VPT_POL_CID);           // a char's word of the 256 KB char table, and the probes of `xcid`
 constexpr MemPolicy kPolUni = MemPolicy(VPT_POL_UNI);           // unigram nodes
@@ -484,7 +487,12 @@ __global__ __launch_bounds__(kThreads, fast_wg(WL)) void score_tiles_fast_kernel
     if (TM != kTypeRows) {
         for (uint32_t i = tid; i < (span + 3) / 4; i += kThreads) reinterpret_cast<uint32_t*>(M.typ)[i] = 0;
     }
-    for (uint32_t c = tid; c < nchunks; c += kThreads) reinterpret_cast<uint4*>(raw)[c] = ld_pol<kPolText>(reinterpret_cast<const uint4*>(a0) + c);
+    // the text under the launch's policy: a kernel argument, so one scalar branch around two copies of the short loop
+    if (kPolTextFixed < 0 ? P->text_nt != 0 : kPolTextFixed == 1) {
+        for (uint32_t c = tid; c < nchunks; c += kThreads) reinterpret_cast<uint4*>(raw)[c] = ld_pol<MemPolicy::kNonTemporal>(reinterpret_cast<const uint4*>(a0) + c);
+    } else {
+        for (uint32_t c = tid; c < nchunks; c += kThreads) reinterpret_cast<uint4*>(raw)[c] = ld_pol<MemPolicy::kPlain>(reinterpret_cast<const uint4*>(a0) + c);
+    }
     if (tid == 0) {
         raw[nchunks * 4] = 0;  // the dword after the staged text is read (as padding) by the last char
         // what phase C needs of the tile: read back there, so that it does not wait in scalar registers over the pattern phase
