@@ -686,7 +686,15 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * <= eps * max(min(pos, neg), 1) / rows * the first sweep's) or after 1000 sweeps.  Weights that end at exactly 0 are not written, so
  * the model is sparse.  Without the flag solver 5 is refused as below; with it solvers 0 and 2 train exactly as without it, solvers 1,
  * 3, 4, 6, 7 are VPT_INVALID_ARGUMENT "solver: only 0, 2 and 5 are implemented", and solver 5 together with VPT_TRAIN_TAGS is
- * VPT_INVALID_ARGUMENT "solver 5: tag models are trained with solvers 0 and 2 only".
+ * VPT_INVALID_ARGUMENT "solver 5: tag models are trained with solvers 0 and 2 only".  That last sentence holds for a trainer without
+ * VPT_TRAIN_TAGS_L1R.  A trainer created with all three of VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R (the third without
+ * both others is VPT_INVALID_ARGUMENT "flags: ...") trains, under solver 5, the boundary model as above and every tag problem by the
+ * same coordinate descent, one-vs-rest over the problem's 0/1 matrix (one mirrored solve for two candidates), every class from w = 0
+ * and the same seed; the groups are the templates (kind, number of context symbols, rel_position) of the problem's features -- a tag
+ * example has at most one feature of a template -- and the bias alone.  A problem with (features + 1) + rows <= 7256 doubles is solved
+ * by one workgroup of one launch with w and b in LDS (path 1), a larger one, or every one after vpt_trainer_set_tag_path(1), by the
+ * group launches of the boundary solver, a class at a time (path 2); both use one summation rule.  vpt_trainer_tag_weights' stats then
+ * have solver 5's meanings (below).  With the third flag solvers 0 and 2 give the bytes they give without it.
  * Divergences: tag models are trained only by a trainer created with VPT_TRAIN_TAGS (below), without it the caller rejects or drops tags
  * (the train CLI's --ignore-tags); solvers 1, 3-7 are
  * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
@@ -703,8 +711,8 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * are assigned, about 52 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
- *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0, VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both (any other bit is
- *   VPT_INVALID_ARGUMENT "flags: ...").
+ *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0, VPT_TRAIN_TAGS, VPT_TRAIN_L1R, both, or both with
+ *   VPT_TRAIN_TAGS_L1R (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ...").
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
  * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's raw text, offsets and labels): the
@@ -724,9 +732,9 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  *   |w|_1 + C sum max(0, 1 - y w.x)^2, the bias inside the norm as liblinear has it. */
 typedef struct vpt_train_params {
     uint32_t charw, charn, typew, typen, dictn;
-    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R */
+    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R */
 } vpt_train_params;
-enum { VPT_TRAIN_TAGS = 1, VPT_TRAIN_L1R = 4 /* bit 1 stays an unknown flag */ };
+enum { VPT_TRAIN_TAGS = 1, VPT_TRAIN_L1R = 4, VPT_TRAIN_TAGS_L1R = 8 /* needs both others; bit 1 stays an unknown flag */ };
 typedef struct vpt_train_stats {
     uint32_t iterations;
     uint32_t cg_steps;
@@ -767,7 +775,8 @@ vpt_status vpt_trainer_last_stats(const void *t, void *stats);
  * order) from a device hash table and radix sort, the examples are sorted by (surface, corpus order), and the keys of all problems are
  * deduplicated, numbered and written as CSR and CSC in a few launches over concatenated arrays.  The host interns the tag strings and, from
  * 8 bytes of ids an example, picks each problem's candidates, rows and y.  Every problem with 7 * (features + 1) + 3 * rows <= 7424 doubles is solved by one workgroup of one kernel
- * launch (TRON with its vectors in LDS), a larger one by the global-memory TRON of the boundary model, a class at a time.
+ * launch (TRON with its vectors in LDS), a larger one by the global-memory TRON of the boundary model, a class at a time.  (Solver 5 on a
+ * trainer with VPT_TRAIN_TAGS_L1R: see the Trainer section; its in-kernel rule is (features + 1) + rows <= 7256.)
  * Divergences: the in-kernel CG loop stops after 16 * (features + 1) + 64 steps (exact CG needs at most features + 1; liblinear's loop and the
  * global-memory solver have no cap), so that a non-finite problem cannot spin on the device.  A HIP error (not an argument error) after the
  * boundary examples of a batch were added leaves them added without the batch's tag examples: destroy the trainer then.

@@ -1,0 +1,55 @@
+"""Solver 5 for tag models (Trainer(l1r=True, train_tags=True, l1r_tags=True)) on the CPU emulator (tests/native/hipemu) against the
+restatement of tests/tagl1ref.py: the in-kernel solver of vaporetto_amd/csrc/kernels_train_tags_l1.hip and the group launches of
+solve_l1r over a tag problem's own matrix (the emulated build also verifies that no row occurs twice in a group), the stats, the model's
+bytes, determinism, the shapes at which the kernel takes another path, and the errors."""
+import pytest
+
+from tests import emu, tagl1suite
+from vaporetto_amd import _lib
+
+
+@pytest.fixture(scope="module", autouse=True)
+def emulated():
+    saved = _lib._lib
+    _lib._lib = emu.load()
+    tagl1suite.trained.cache_clear()   # a trainer belongs to the library that made it
+    yield
+    tagl1suite.trained.cache_clear()
+    _lib._lib = saved
+
+
+CASES = [(name, path) for name in sorted(tagl1suite.CASES) for path in (0, 1)]
+
+
+@pytest.mark.parametrize("name,path", CASES)
+def test_objective_violation_counts_and_mirror(name, path):
+    stats = tagl1suite.check_solution(name, path)
+    assert {p["path"] for p in stats["problems"]} == ({1} if path == 0 else {2})
+
+
+@pytest.mark.parametrize("name,path", CASES)
+def test_library_stats(name, path):
+    tagl1suite.check_library_stats(name, path)
+
+
+@pytest.mark.parametrize("name", sorted(tagl1suite.CASES))
+def test_paths_agree(name):
+    tagl1suite.check_paths_agree(name)
+
+
+@pytest.mark.parametrize("name,path", CASES)
+def test_model_bytes_determinism_and_sparsity(name, path):
+    tagl1suite.check_model(name, path)
+
+
+def test_solvers_0_and_2_unchanged_by_the_flags():
+    tagl1suite.check_tron_unchanged("small")
+
+
+@pytest.mark.parametrize("name", sorted(tagl1suite.SHAPES))
+def test_shapes(name):
+    tagl1suite.check_shape(name)
+
+
+def test_flag_and_errors():
+    tagl1suite.check_errors()

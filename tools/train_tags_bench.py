@@ -41,17 +41,48 @@ def corpus(n_sent, n_surf, seed):
     return lines
 
 
+def l1_leg(arrays, res, out):
+    """--solver 5: a Trainer(l1r=True, train_tags=True, l1r_tags=True) trains the corpus with solver 5 and then with solver 2, each once
+    untimed and once timed, by size; the tag solvers' seconds, problems per path, sweeps, halvings and the share of exactly-zero weights
+    go to `out` with solver 2's numbers of the same run beside them."""
+    import numpy as np
+    t = api.Trainer(2, 2, 2, 2, train_tags=True, l1r=True, l1r_tags=True)
+    t.add_packed_tagged(*arrays)
+    for solver in (5, 2):
+        t.train_bytes(0.01, 1.0, solver)   # warm-up
+        t0 = time.perf_counter()
+        model = t.train_bytes(0.01, 1.0, solver)
+        t1 = time.perf_counter()
+        st = t.tag_stats()
+        sm = st["summary"]
+        w = np.concatenate([t.tag_weights(i).ravel() for i in range(len(st["problems"]))])
+        res["solver_%d" % solver] = {
+            "train_total_s": t1 - t0, "seconds_in_kernel": sm["seconds_in_kernel"], "seconds_large": sm["seconds_large"],
+            "seconds_large_solve": sm["seconds_large_solve"], "problems_in_kernel": sm["problems_in_kernel"], "problems_large": sm["problems_large"],
+            "iterations": int(sum(c["iterations"] for q in st["problems"] for c in q["classes"])),
+            "cg_steps_or_halvings": int(sum(c["cg_steps"] for q in st["problems"] for c in q["classes"])),
+            "classes_at_max_iterations": int(sum(c["iterations"] >= 1000 for q in st["problems"] for c in q["classes"])),
+            "zero_weight_share": float((w == 0.0).mean()), "model_bytes": len(model)}
+    print(json.dumps(res))
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sentences", type=int, default=4000)
     ap.add_argument("--surfaces", type=int, default=300)
     ap.add_argument("--solver", type=int, default=2)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--out", default="profiles/train_tags_l1_bench.json", help="where --solver 5 writes its result")
     args = ap.parse_args()
     p = api.parse_tokenized_host(corpus(args.sentences, args.surfaces, args.seed))
     arrays = (p["raw"], p["raw_offsets"], p["labels"], p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"])
     res = {"sentences": args.sentences, "surfaces": args.surfaces, "solver": args.solver, "chars": int(len(p["tag_index"]) - 1),
            "charn": 2, "typen": 2}
+    if args.solver == 5:
+        return l1_leg(arrays, res, args.out)
     # warm-up: one whole run by size (the device, the allocator and the code objects), not timed
     w = api.Trainer(2, 2, 2, 2, train_tags=True)
     w.add_packed_tagged(*arrays)

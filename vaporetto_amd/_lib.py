@@ -50,6 +50,7 @@ class TrainStats(C.Structure):
 
 VPT_TRAIN_TAGS = 1
 VPT_TRAIN_L1R = 4
+VPT_TRAIN_TAGS_L1R = 8
 
 
 class TagProblemInfo(C.Structure):

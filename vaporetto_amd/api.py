@@ -1642,10 +1642,15 @@ class Trainer:
     `tag_dictionary` is then the reference's tag dictionary: tagged Sentences, or (surface, tags) pairs, whose first occurrence of a
     surface gives the tags of a surface the corpus does not contain.  With `l1r=True` (VPT_TRAIN_L1R) train also accepts
     SolverType.L1RegularizedL2LossSVC, the solver the reference's README trains with: most weights end at exactly 0 and are not written.
-    Solvers 0 and 2 train as without it; tag models are not trained with solver 5."""
+    Solvers 0 and 2 train as without it; tag models are not trained with solver 5 unless `l1r_tags=True` (VPT_TRAIN_TAGS_L1R, which
+    needs both `l1r` and `train_tags`): then solver 5 trains every tag problem by the same coordinate descent, one-vs-rest, and the tag
+    models are sparse too; tag_stats() then carries sweeps and halvings as last_stats() does."""
 
     def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
-                 ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = (), l1r: bool = False):
+                 ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = (), l1r: bool = False,
+                 l1r_tags: bool = False):
+        if l1r_tags and not (l1r and train_tags):
+            raise ValueError("l1r_tags needs l1r=True and train_tags=True")
         if ignore_tags and train_tags:
             raise ValueError("ignore_tags and train_tags exclude each other")
         if tag_dictionary and not train_tags:
@@ -1657,7 +1662,9 @@ class Trainer:
         self._charw, self._typew = charw, typew
         self.dict_words = list(dict_words)
         self.l1r = bool(l1r)
-        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, (_lib.VPT_TRAIN_TAGS if train_tags else 0) | (_lib.VPT_TRAIN_L1R if l1r else 0))
+        self.l1r_tags = bool(l1r_tags)
+        prm = _lib.TrainParams(charw, charn, typew, typen, dictn, (_lib.VPT_TRAIN_TAGS if train_tags else 0) | (_lib.VPT_TRAIN_L1R if l1r else 0) |
+                               (_lib.VPT_TRAIN_TAGS_L1R if l1r_tags else 0))
         utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
         st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
         if st != _lib.VPT_OK:

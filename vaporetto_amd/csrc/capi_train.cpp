@@ -1,5 +1,6 @@
 // C ABI of libvaporetto_hip.so, boundary-model training: Trainer (vaporetto/src/trainer.rs) with the liblinear TRON solvers 0 and 2 and,
-// on a trainer created with VPT_TRAIN_L1R, the coordinate descent of solver 5 by column groups (solve_l1r, l1r.h).
+// on a trainer created with VPT_TRAIN_L1R, the coordinate descent of solver 5 by column groups (solve_l1r, l1r.h); with
+// VPT_TRAIN_TAGS_L1R beside it solver 5 trains the tag models too (kernels_train_tags_l1.hip in LDS, solve_l1r for what does not fit).
 //
 // The vpt_trainer handle keeps every example's feature keys and label on the device (kernels_train.hip); feature ids, the CSR and CSC
 // copies of the design matrix are made when they are first needed after an add, and the TRON / CG loop runs here, on the host, over
@@ -110,7 +111,7 @@ struct TagProblem {
     uint64_t nnz = 0;
     bool fetched = false;
     std::vector<uint32_t> rp, cols;       // the 0/1 CSR, read back from the device when asked for (fetch_rows)
-    uint32_t path = 0;                    // 1 solved inside the kernel, 2 by the global-memory TRON
+    uint32_t path = 0;                    // 1 solved inside the kernel, 2 by the global-memory solver (TRON, or solver 5's group launches)
     double seconds_setup = 0, seconds_solve = 0;   // path 2: uploading the matrix and building its CSC; the solves of its classes
     std::vector<double> w;                // [classes][features + 1]
     std::vector<vpt_train_stats> stats;   // per class
@@ -431,7 +432,8 @@ struct L1rGroups {
     std::vector<uint32_t> n_lane, n_wave;
     size_t size() const { return n_lane.size(); }
 };
-L1rGroups l1r_groups(const std::vector<uint64_t>& keys, const std::vector<uint64_t>& cptr, uint64_t nd) {
+template <typename Ptr>
+L1rGroups l1r_groups(const std::vector<uint64_t>& keys, const Ptr* cptr, uint64_t nd) {
     std::map<uint32_t, std::vector<uint32_t>> tpl;
     std::vector<uint32_t> alone;
     for (uint64_t j = 0; j < nd; ++j) {
@@ -442,7 +444,7 @@ L1rGroups l1r_groups(const std::vector<uint64_t>& keys, const std::vector<uint64
     alone.push_back(uint32_t(nd));
     L1rGroups G;
     auto push = [&](const std::vector<uint32_t>& g) {
-        auto len = [&](uint32_t j) { return j == nd ? ~uint64_t(0) : cptr[j + 1] - cptr[j]; };
+        auto len = [&](uint32_t j) { return j == nd ? ~uint64_t(0) : uint64_t(cptr[j + 1] - cptr[j]); };
         uint32_t cnt[2] = {0, 0};
         for (int cls = 0; cls < 3; ++cls)
             for (uint32_t j : g) {
@@ -460,31 +462,47 @@ L1rGroups l1r_groups(const std::vector<uint64_t>& keys, const std::vector<uint64
     return G;
 }
 
-// solve_l1r_l2_svc from w = 0 by groups: a launch per group, the groups permuted anew per sweep (l1r.h), the columns' violations summed
-// in a fixed order and read back once per sweep: the only readback of a sweep.  The weights come back into t->w, the stats into t->stats:
-// sweeps, halvings, the first and last sweep's violation sums, and |w|_1 + C sum max(0, b)^2 with b recomputed from w.
-vpt_status solve_l1r(vpt_trainer* t, const std::vector<double>& y, uint64_t pos, const std::vector<uint64_t>& keys, double eps, double cost) {
-    const Matrix& M = t->m;
-    hipStream_t st = t->st;
-    const uint64_t nd = M.nd, nr = t->nrows, n = nd + 1;
+// what the launches of a group (and the in-kernel solver's groups) rest on: no row twice in a group.  Checked by the emulated build and
+// by -DVPT_DEBUG once per matrix; crow, cptr: the CSC on the host
+template <typename Ptr>
+vpt_status l1r_check_groups(const L1rGroups& G, const uint32_t* crow, const Ptr* cptr, uint64_t nr, uint64_t nd) {
+#if defined(VPT_HIPEMU) || defined(VPT_DEBUG)
+    std::vector<uint32_t> seen(nr, ~uint32_t(0));
+    for (size_t g = 0; g < G.size(); ++g)
+        for (uint64_t q = G.ptr[g]; q < G.ptr[g + 1]; ++q) {
+            const uint32_t j = G.cols[q];
+            if (j == nd) continue;   // the bias is alone
+            for (uint64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
+                if (seen[crow[k]] == uint32_t(g)) return fail(VPT_RUNTIME_ERROR, "solver 5: a row occurs twice in a column group");
+                seen[crow[k]] = uint32_t(g);
+            }
+        }
+#endif
+    return VPT_OK;
+}
+// the groups of M's columns, whose keys are `keys`, checked as above
+vpt_status l1r_matrix_groups(const Matrix& M, uint64_t nr, const std::vector<uint64_t>& keys, L1rGroups& G) {
+    const uint64_t nd = M.nd;
     std::vector<uint64_t> cptr(nd + 1);
     VPT_HIP(hipMemcpy(cptr.data(), M.cptr.p, (nd + 1) * 8, hipMemcpyDeviceToHost));
-    const L1rGroups G = l1r_groups(keys, cptr, nd);
+    G = l1r_groups(keys, cptr.data(), nd);
 #if defined(VPT_HIPEMU) || defined(VPT_DEBUG)
-    {   // what the launches rest on: no row twice in a group
-        std::vector<uint32_t> crow(M.nnz), seen(nr, ~uint32_t(0));
-        if (M.nnz) VPT_HIP(hipMemcpy(crow.data(), M.crow.p, M.nnz * 4, hipMemcpyDeviceToHost));
-        for (size_t g = 0; g < G.size(); ++g)
-            for (uint64_t q = G.ptr[g]; q < G.ptr[g + 1]; ++q) {
-                const uint32_t j = G.cols[q];
-                if (j == nd) continue;   // the bias is alone
-                for (uint64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
-                    if (seen[crow[k]] == uint32_t(g)) return fail(VPT_RUNTIME_ERROR, "solver 5: a row occurs twice in a column group");
-                    seen[crow[k]] = uint32_t(g);
-                }
-            }
-    }
+    std::vector<uint32_t> crow(M.nnz);
+    if (M.nnz) VPT_HIP(hipMemcpy(crow.data(), M.crow.p, M.nnz * 4, hipMemcpyDeviceToHost));
+    VPT_TRY(l1r_check_groups(G, crow.data(), cptr.data(), nr, nd));
 #endif
+    return VPT_OK;
+}
+
+// solve_l1r_l2_svc from w = 0 by groups over the matrix M of nr rows with the targets y (`pos` of them +1): a launch per group, the
+// groups G permuted anew per sweep (l1r.h), the columns' violations summed in a fixed order and read back once per sweep: the only
+// readback of a sweep.  The boundary model and a class of a tag problem that does not fit its kernel are solved here.  Out come the
+// weights and the stats: sweeps, halvings, the first and last sweep's violation sums, and |w|_1 + C sum max(0, b)^2 with b recomputed
+// from w.
+vpt_status solve_l1r(vpt_trainer* t, const Matrix& M, uint64_t nr, const std::vector<double>& y, uint64_t pos, const L1rGroups& G, double eps, double cost,
+                     double* w_out, vpt_train_stats* stats) {
+    hipStream_t st = t->st;
+    const uint64_t nd = M.nd, n = nd + 1;
     Tron T;   // its vectors and its reductions: w, y, b (in gz), xj_sq (in s), the violations (in g)
     VPT_TRY(T.init(M, st, nr, 2, cost));
     DBuf<uint32_t> d_cols, d_halv;
@@ -520,17 +538,16 @@ vpt_status solve_l1r(vpt_trainer* t, const std::vector<double>& y, uint64_t pos,
         if (v <= tol * v0) break;
     }
     uint32_t halvings = 0;
-    t->w.resize(n);
     VPT_HIP(hipMemcpyAsync(&halvings, d_halv.p, 4, hipMemcpyDeviceToHost, st));
-    VPT_HIP(hipMemcpyAsync(t->w.data(), T.w.p, n * 8, hipMemcpyDeviceToHost, st));
+    VPT_HIP(hipMemcpyAsync(w_out, T.w.p, n * 8, hipMemcpyDeviceToHost, st));
     // the loss at the weights themselves, not at the b the sweeps carried along
     VPT_HIP(vpt::train_xv(M.csr_ptr.p, M.cols.p, M.vals.p, nr, T.w.p, nd, T.z.p, st));
     VPT_HIP(vpt::train_loss(nr, T.z.p, T.y.p, cost, 2, T.loss.p, st));
     const double loss = T.dot(T.loss.p, nullptr, nr);
     VPT_HIP(T.err);
     double norm1 = 0;
-    for (double x : t->w) norm1 += std::fabs(x);
-    t->stats = vpt_train_stats{sweeps, halvings, v0, v, norm1 + loss};
+    for (uint64_t j = 0; j < n; ++j) norm1 += std::fabs(w_out[j]);
+    *stats = vpt_train_stats{sweeps, halvings, v0, v, norm1 + loss};
     return VPT_OK;
 }
 
@@ -819,6 +836,13 @@ vpt_status build_tags(vpt_trainer* t) {
     return VPT_OK;
 }
 
+// a problem's keys as the two words a key that vpt::train_key and l1r_groups take
+std::vector<uint64_t> tag_key_words(const TagProblem& Pb) {
+    std::vector<uint64_t> out(2 * Pb.keys.size());
+    for (size_t j = 0; j < Pb.keys.size(); ++j) { out[2 * j] = uint64_t(Pb.keys[j]); out[2 * j + 1] = uint64_t(Pb.keys[j] >> 64); }
+    return out;
+}
+
 // a problem's CSR on the host, for the inspection calls and the global-memory path
 vpt_status fetch_rows(vpt_trainer* t, TagProblem& Pb) {
     if (Pb.fetched) return VPT_OK;
@@ -831,7 +855,7 @@ vpt_status fetch_rows(vpt_trainer* t, TagProblem& Pb) {
     return VPT_OK;
 }
 
-// one problem through the global-memory TRON, a class at a time
+// one problem through the global-memory solver, a class at a time: TRON, or for solver 5 the group launches of solve_l1r
 vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double cost, int solver) {
     hipStream_t st = t->st;
     const double t_setup = now_s();
@@ -853,9 +877,11 @@ vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double co
     }
     VPT_TRY(csc_levels(t, M, d_rows.p, nz, nf));
     Tron T;
-    VPT_TRY(T.init(M, st, l, solver, cost));
+    L1rGroups G;
+    if (solver == 5) VPT_TRY(l1r_matrix_groups(M, l, tag_key_words(Pb), G));
+    else VPT_TRY(T.init(M, st, l, solver, cost));
     std::vector<double> y(l);
-    const uint64_t n_solve = k == 2 ? 1 : k;
+    const uint64_t n_solve = k == 2 ? 1 : k, n = nf + 1;
     VPT_HIP(hipStreamSynchronize(st));
     Pb.seconds_setup = now_s() - t_setup;
     Pb.seconds_solve = 0;
@@ -863,11 +889,12 @@ vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double co
         uint64_t pos = 0;
         for (uint64_t r = 0; r < l; ++r) { y[r] = Pb.y[r] == c ? 1.0 : -1.0; pos += Pb.y[r] == c; }
         const double t_run = now_s();
-        VPT_TRY(T.solve(y, pos, eps, &Pb.stats[c], Pb.w.data() + c * T.n));
+        if (solver == 5) VPT_TRY(solve_l1r(t, M, l, y, pos, G, eps, cost, Pb.w.data() + c * n, &Pb.stats[c]));
+        else VPT_TRY(T.solve(y, pos, eps, &Pb.stats[c], Pb.w.data() + c * n));
         Pb.seconds_solve += now_s() - t_run;
     }
     if (k == 2) {
-        for (uint64_t i = 0; i < T.n; ++i) Pb.w[T.n + i] = -Pb.w[i];
+        for (uint64_t i = 0; i < n; ++i) Pb.w[n + i] = -Pb.w[i];
         Pb.stats[1] = Pb.stats[0];
     }
     Pb.path = 2;
@@ -880,12 +907,27 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
     std::vector<vpt::TagSolveDesc> descs;
     std::vector<uint32_t> small;
     uint64_t n_w = 0, n_stats = 0;
+    // solver 5: the in-kernel problems' columns by group (l1r_groups over a problem's keys: a tag example has at most one feature per
+    // template, tag_trainer.rs:79-100) beside their descriptors
+    const bool l1 = solver == 5;
+    std::vector<vpt::TagL1Desc> l1descs;
+    std::vector<vpt::TagL1Group> l1groups;
+    std::vector<uint32_t> gcols, h_cp, h_crow;
+    uint64_t n_viol = 0;
+    if (l1 && t->tag_path_mode == 0 && !t->tag_problems.empty()) {
+        h_cp.resize(t->h_key_ptr.back() + t->tag_problems.size());
+        VPT_HIP(hipMemcpy(h_cp.data(), t->b_cp.p, h_cp.size() * 4, hipMemcpyDeviceToHost));
+#if defined(VPT_HIPEMU) || defined(VPT_DEBUG)
+        h_crow.resize(t->h_prob_occ0.back());
+        if (!h_crow.empty()) VPT_HIP(hipMemcpy(h_crow.data(), t->b_crow.p, h_crow.size() * 4, hipMemcpyDeviceToHost));
+#endif
+    }
     for (size_t i = 0; i < t->tag_problems.size(); ++i) {
         TagProblem& Pb = t->tag_problems[i];
         const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), k = Pb.cands.size();
         Pb.w.assign(k * (nf + 1), 0.0);
         Pb.stats.assign(k, vpt_train_stats{});
-        Pb.path = (t->tag_path_mode == 0 && vpt::train_tag_fits(l, nf)) ? 1 : 2;
+        Pb.path = (t->tag_path_mode == 0 && (l1 ? vpt::train_tag_l1_fits(l, nf) : vpt::train_tag_fits(l, nf))) ? 1 : 2;
         Pb.seconds_setup = Pb.seconds_solve = 0;
         if (Pb.path != 1) continue;
         // the problem where build_tags left it on the device
@@ -896,6 +938,18 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         n_stats += k;
         descs.push_back(D);
         small.push_back(uint32_t(i));
+        if (!l1) continue;
+        const uint32_t* cp = h_cp.data() + D.cp;
+        const L1rGroups G = l1r_groups(tag_key_words(Pb), cp, nf);
+        VPT_TRY(l1r_check_groups(G, h_crow.empty() ? nullptr : h_crow.data() + D.cols, cp, l, nf));
+        if (G.size() > vpt::kTagL1MaxGroups) return fail(VPT_RUNTIME_ERROR, "solver 5: a tag problem with more column groups than its kernel holds");
+        vpt::TagL1Desc E{};
+        E.gcols = gcols.size(); E.groups = l1groups.size(); E.viol = n_viol; E.n_groups = uint32_t(G.size());
+        for (size_t g = 0; g < G.size(); ++g)
+            l1groups.push_back(vpt::TagL1Group{uint32_t(G.ptr[g]), G.n_lane[g], G.n_wave[g], uint32_t(G.ptr[g + 1] - G.ptr[g])});
+        gcols.insert(gcols.end(), G.cols.begin(), G.cols.end());
+        n_viol += nf + 1;
+        l1descs.push_back(E);
     }
     if (!descs.empty()) {
         const double t0 = now_s();
@@ -906,8 +960,22 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         VPT_HIP(hipMemcpyAsync(d_desc.p, descs.data(), descs.size() * sizeof(vpt::TagSolveDesc), hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemsetAsync(d_w.p, 0, n_w * 8, st));
         VPT_HIP(hipMemsetAsync(d_stats.p, 0, n_stats * sizeof(vpt_train_stats), st));
-        VPT_HIP(vpt::train_tag_solve(d_desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, eps, cost, solver, d_w.p,
-                                     d_stats.p, st));
+        DBuf<vpt::TagL1Desc> d_l1desc;   // solver 5's
+        DBuf<vpt::TagL1Group> d_groups;
+        DBuf<uint32_t> d_gcols;
+        DBuf<double> d_viol;
+        if (l1) {
+            VPT_HIP(d_l1desc.resize(l1descs.size())); VPT_HIP(d_groups.resize(l1groups.size())); VPT_HIP(d_gcols.resize(gcols.size())); VPT_HIP(d_viol.resize(n_viol));
+            VPT_HIP(hipMemcpyAsync(d_l1desc.p, l1descs.data(), l1descs.size() * sizeof(vpt::TagL1Desc), hipMemcpyHostToDevice, st));
+            VPT_HIP(hipMemcpyAsync(d_groups.p, l1groups.data(), l1groups.size() * sizeof(vpt::TagL1Group), hipMemcpyHostToDevice, st));
+            VPT_HIP(hipMemcpyAsync(d_gcols.p, gcols.data(), gcols.size() * 4, hipMemcpyHostToDevice, st));
+            VPT_HIP(hipMemsetAsync(d_viol.p, 0, n_viol * 8, st));
+            VPT_HIP(vpt::train_tag_l1_solve(d_desc.p, d_l1desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, d_gcols.p,
+                                            d_groups.p, eps, cost, d_viol.p, d_w.p, d_stats.p, st));
+        } else {
+            VPT_HIP(vpt::train_tag_solve(d_desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, eps, cost, solver, d_w.p,
+                                         d_stats.p, st));
+        }
         std::vector<double> w(n_w);
         std::vector<vpt_train_stats> stats(n_stats);
         VPT_HIP(hipMemcpyAsync(w.data(), d_w.p, n_w * 8, hipMemcpyDeviceToHost, st));
@@ -1143,7 +1211,10 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     if (p.charw > 16) return fail_arg("charw: must be at most 16");
     if (p.typew > 16) return fail_arg("typew: must be at most 16");
     if (p.typew > p.charw) return fail_arg("typew: must not exceed charw (type weights use the char window)");
-    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R)) != 0) return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R)) != 0)
+        return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
+    if ((p.flags & VPT_TRAIN_TAGS_L1R) && (p.flags & (VPT_TRAIN_TAGS | VPT_TRAIN_L1R)) != (VPT_TRAIN_TAGS | VPT_TRAIN_L1R))
+        return fail_arg("flags: VPT_TRAIN_TAGS_L1R needs both VPT_TRAIN_TAGS and VPT_TRAIN_L1R");
     if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail_arg("dictn: must be at least 1 with a dictionary");
     std::unique_ptr<vpt_trainer> t(new (std::nothrow) vpt_trainer());
     if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
@@ -1262,7 +1333,7 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     const bool l1r = (t->prm.flags & VPT_TRAIN_L1R) != 0;
     if (!l1r && solver != 0 && solver != 2) return fail_arg("solver: only 0 and 2 are implemented");
     if (l1r && solver != 0 && solver != 2 && solver != 5) return fail_arg("solver: only 0, 2 and 5 are implemented");
-    if (solver == 5 && (t->prm.flags & VPT_TRAIN_TAGS)) return fail_arg("solver 5: tag models are trained with solvers 0 and 2 only");
+    if (solver == 5 && (t->prm.flags & VPT_TRAIN_TAGS) && !(t->prm.flags & VPT_TRAIN_TAGS_L1R)) return fail_arg("solver 5: tag models are trained with solvers 0 and 2 only");
     if (!(eps > 0) || !(cost > 0)) return fail_arg("eps and cost: must be positive");
     VPT_HIP(hipSetDevice(t->device));
     t->trained = false;
@@ -1282,7 +1353,10 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     std::vector<uint64_t> keys(2 * nd);
     if (nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
     if (solver == 5) {
-        VPT_TRY(solve_l1r(t, y, pos, keys, eps, cost));
+        L1rGroups G;
+        VPT_TRY(l1r_matrix_groups(t->m, nr, keys, G));
+        t->w.resize(nd + 1);
+        VPT_TRY(solve_l1r(t, t->m, nr, y, pos, G, eps, cost, t->w.data(), &t->stats));
     } else {
         Tron T;
         VPT_TRY(T.init(t->m, t->st, nr, solver, cost));

@@ -544,4 +544,21 @@ bool train_tag_fits(uint64_t rows, uint64_t features);
 hipError_t train_tag_solve(const TagSolveDesc* descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols, const uint32_t* cp, const uint32_t* crow,
                            const uint32_t* y, double eps, double cost, int solver, double* w, vpt_train_stats* stats, hipStream_t st);
 
+// solver 5 for tag problems (kernels_train_tags_l1.hip): the in-kernel solver keeps w (features + 1) and b (rows) in LDS and nothing
+// else of the problem's size, so a problem fits iff (features + 1) + rows <= kTagL1LdsDoubles; the rest of tag_solve_kernel's 61568
+// bytes holds the level sums of the summation rule, the groups' order and the halvings
+constexpr uint32_t kTagL1LdsDoubles = 7256;
+constexpr uint32_t kTagL1MaxGroups = 64;   // templates of a kind: 20 with n-grams of up to 5 symbols; two kinds and the bias: 41
+struct TagL1Group {
+    uint32_t at, n_lane, n_wave, n;        // the group's columns gcols[at .. at + n): those a lane takes, then a wave's, then the workgroup's
+};
+struct TagL1Desc {                         // beside a problem's TagSolveDesc
+    uint64_t gcols, groups, viol;          // where its columns by group, its groups and its features + 1 violations start
+    uint32_t n_groups, pad;
+};
+bool train_tag_l1_fits(uint64_t rows, uint64_t features);
+hipError_t train_tag_l1_solve(const TagSolveDesc* descs, const TagL1Desc* l1descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols,
+                              const uint32_t* cp, const uint32_t* crow, const uint32_t* y, const uint32_t* gcols, const TagL1Group* groups, double eps,
+                              double cost, double* viol, double* w, vpt_train_stats* stats, hipStream_t st);
+
 }  // namespace vpt

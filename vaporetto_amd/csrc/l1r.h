@@ -1,6 +1,7 @@
 // liblinear's coordinate descent for L1-regularised L2-loss SVC (linear.cpp: solve_l1r_l2_svc, solver 5), one column's step and the
-// order of a sweep, host and device code: the one transcript that the device kernel (kernels_train_l1.hip), the host driver
-// (capi_train.cpp, solve_l1r) and the native check (tests/native/l1r_test.cpp) share.
+// order of a sweep, host and device code: the one transcript that the device kernels (kernels_train_l1.hip over global memory,
+// kernels_train_tags_l1.hip a tag problem in LDS), the host driver (capi_train.cpp, solve_l1r) and the native check
+// (tests/native/l1r_test.cpp) share.
 //
 //   min_w  |w|_1 + C sum_i max(0, b_i)^2,   b_i = 1 - y_i w.x_i,   the bias a column of ones inside the norm, as liblinear has it.
 //
@@ -42,7 +43,7 @@ VPT_HD uint64_t l1r_next(uint64_t* state) {
     return z ^ (z >> 31);
 }
 // the order of the next sweep: order[0 .. n) permuted in place
-inline void l1r_shuffle(uint32_t* order, uint32_t n, uint64_t* state) {
+VPT_HD void l1r_shuffle(uint32_t* order, uint32_t n, uint64_t* state) {
     for (uint32_t i = n; i-- > 1;) {
         const uint32_t j = uint32_t(l1r_next(state) % (uint64_t(i) + 1));
         const uint32_t t = order[i];
