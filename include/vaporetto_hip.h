@@ -715,8 +715,12 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  *   VPT_TRAIN_TAGS_L1R (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ...").
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
- * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's raw text, offsets and labels): the
- *   examples are appended after hip_stream's work so far; returns when they are.
+ * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's or vpt_parse_partial_batch_device's raw
+ *   text, offsets and labels): the examples are appended after hip_stream's work so far; returns when they are.  The text may start
+ *   anywhere in a larger buffer, at any alignment.  total_boundaries is EXACT here, not an upper bound as in the predictor's device
+ *   calls.  Checked once hip_stream's work is done and before a kernel follows an offset, each VPT_INVALID_ARGUMENT with nothing added:
+ *   d_out_offsets[0] != 0 "out_offsets: must start at 0"; d_out_offsets[n_sentences] != total_boundaries "total_boundaries: must
+ *   equal out_offsets[n_sentences]"; a label above 2 "labels: must be 0, 1 or 2" (vpt_trainer_add_batch's message).
  * vpt_trainer_n_features: the distinct features of the examples so far (Trainer::n_features).
  * vpt_trainer_csr: the design matrix: row_ptr[n_rows + 1], per nonzero its column (features in key order) and count; NULL outputs ask
  *   for the sizes only.
@@ -790,7 +794,10 @@ vpt_status vpt_trainer_last_stats(const void *t, void *stats);
  * vpt_trainer_add_tagged_batch[_device]: vpt_trainer_add_batch[_device]'s arguments plus the gold tags as vpt_parse_tokenized_batch[_device]
  *   writes them: n_tags[S], tag_index[chars + 1], span_offsets[n_spans + 1], tag_bytes[n_tag_bytes] (an empty span is None).  The CSR is
  *   checked on the device before an offset is followed: VPT_INVALID_ARGUMENT "tag_index: ..." / "span_offsets: ...", nothing added.  The
- *   boundary examples are added exactly as the untagged call adds them.
+ *   boundary examples are added exactly as the untagged call adds them, behind the call's last refusal.
+ *   vpt_trainer_add_tagged_batch_device holds its batch to vpt_trainer_add_batch_device's three rules first, with the same messages and
+ *   nothing added: d_out_offsets[0] == 0, total_boundaries == d_out_offsets[n_sentences] exactly (no upper bound, unlike the predictor's
+ *   device calls), and no label above 2.
  * vpt_trainer_set_tag_dictionary: replaces the tag dictionary: surface i is surfaces_utf8[surface_offsets[i] .. [i+1]) with n_tags[i] slots,
  *   whose tags are the next n_tags[i] spans of span_offsets into tag_bytes (empty: None); the first occurrence of a surface wins.  A surface
  *   with a tag and no example gets a model of fixed tags.  Host only.

@@ -1727,6 +1727,27 @@ class Trainer:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def add_device(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, flags: int = 0,
+                   stream: int = 0) -> None:
+        """Device-resident add_packed (vpt_trainer_add_batch_device): all pointers are raw device addresses, e.g. the raw text, raw offsets,
+        out_offsets and labels vpt_parse_tokenized_batch_device wrote; the examples are appended after `stream`'s work so far.
+        total_boundaries is exact, out_offsets[n_sentences]; d_labels may be 0 (NULL) when it is 0."""
+        st = self._L.vpt_trainer_add_batch_device(self._h, d_utf8 or None, d_boff or None, d_ooff or None, n_sentences, total_boundaries,
+                                                  d_labels or None, flags, stream or None)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def add_tagged_device(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, d_n_tags: int,
+                          d_tag_index: int, d_span_offsets: int, d_tag_bytes: int, n_spans: int, n_tag_bytes: int, flags: int = 0,
+                          stream: int = 0) -> None:
+        """Device-resident add_packed_tagged (vpt_trainer_add_tagged_batch_device) on the arrays either device parser wrote; needs
+        train_tags=True."""
+        st = self._L.vpt_trainer_add_tagged_batch_device(self._h, d_utf8 or None, d_boff or None, d_ooff or None, n_sentences, total_boundaries,
+                                                         d_labels or None, d_n_tags or None, d_tag_index or None, d_span_offsets or None,
+                                                         d_tag_bytes or None, n_spans, n_tag_bytes, flags, stream or None)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def add_examples(self, sentences: Sequence["Sentence"], fullwidth: bool = False) -> None:
         if not sentences:
             return

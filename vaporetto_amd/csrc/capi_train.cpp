@@ -610,14 +610,27 @@ vpt_status make_model(vpt_trainer* t, const std::vector<uint64_t>& keys) {
     return VPT_OK;
 }
 
+// A device caller's totals, once its stream has been synchronised and before a kernel follows an offset: the features' kernels index
+// the boundaries from 0 and run a thread for each of total_b, so both ends of out_offsets are held to exactly that.
+vpt_status check_totals(const uint64_t* d_ooff, size_t n, uint64_t total_b) {
+    uint64_t first = 0, last = 0;
+    VPT_HIP(hipMemcpy(&first, d_ooff, 8, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(&last, d_ooff + n, 8, hipMemcpyDeviceToHost));
+    if (first != 0) return fail_arg("out_offsets: must start at 0");
+    if (last != total_b) return fail_arg("total_boundaries: must equal out_offsets[n_sentences]");
+    return VPT_OK;
+}
+
+// `checked`: the caller has looked at the totals and the labels already (stage_batch on the host, add_tagged_device on the device)
 vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_boff, const uint64_t* d_ooff, size_t n, uint64_t total_b,
-                      const uint8_t* d_labels, unsigned flags, hipStream_t st) {
+                      const uint8_t* d_labels, unsigned flags, hipStream_t st, bool checked) {
     if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail_arg("flags: only VPT_FLAG_KYTEA_FULLWIDTH");
     if (n == 0) return VPT_OK;
     VPT_HIP(hipSetDevice(t->device));
     // the caller's stream, then ours: the examples are appended in call order
     VPT_HIP(hipStreamSynchronize(st));
     st = t->st;
+    if (!checked) VPT_TRY(check_totals(d_ooff, n, total_b));
     const uint64_t total_chars = total_b + n;
     DBuf<uint32_t> cps, status, counts;
     DBuf<uint64_t> off;
@@ -625,10 +638,12 @@ vpt_status add_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_b
     VPT_HIP(hipMemsetAsync(status.p, 0, 4, st));
     const bool fw = (flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
     VPT_HIP(vpt::launch_decode_chars(d_utf8, d_boff, d_ooff, n, total_chars, fw ? t->d_cinfo.p : nullptr, cps.p, nullptr, status.p, st, fw));
+    if (!checked) VPT_HIP(vpt::train_check_labels(d_labels, total_b, status.p, st));
     uint32_t bad = 0;
     VPT_HIP(hipMemcpyAsync(&bad, status.p, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad) return fail_arg("out_offsets: do not match the text");
+    if (bad & ~vpt::kErrBadLabel) return fail_arg("out_offsets: do not match the text");
+    if (bad) return fail_arg("labels: must be 0, 1 or 2");
     vpt::TrainFeatParams P{};
     P.cps = cps.p; P.ooff = d_ooff; P.n_sent = n; P.total_b = total_b;
     P.charw = t->prm.charw; P.charn = t->prm.charn; P.typew = t->prm.typew; P.typen = t->prm.typen; P.dictn = t->prm.dictn;
@@ -1062,12 +1077,13 @@ void encode_tag_models(vpt_trainer* t, Enc& e) {
 
 vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64_t* d_boff, const uint64_t* d_ooff, size_t n, uint64_t total_b,
                              const uint8_t* d_labels, const uint32_t* d_n_tags, const uint64_t* d_tag_index, const uint64_t* d_span_off,
-                             const uint8_t* d_tag_bytes, uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, hipStream_t caller) {
+                             const uint8_t* d_tag_bytes, uint64_t n_spans, uint64_t n_tag_bytes, unsigned flags, hipStream_t caller, bool checked) {
     if ((flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) != 0) return fail_arg("flags: only VPT_FLAG_KYTEA_FULLWIDTH");
     if (n == 0) return VPT_OK;
     VPT_HIP(hipSetDevice(t->device));
     VPT_HIP(hipStreamSynchronize(caller));
     hipStream_t st = t->st;
+    if (!checked) VPT_TRY(check_totals(d_ooff, n, total_b));
     const uint64_t total_chars = total_b + n;
     if (total_chars >= (uint64_t(1) << 32)) return fail_arg("examples: at most 2^32 - 1 chars in a batch");
     DBuf<uint32_t> cps, status, counts, is_ex;
@@ -1075,10 +1091,12 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
     VPT_HIP(hipMemsetAsync(status.p, 0, 8, st));
     const bool fw = (flags & VPT_FLAG_KYTEA_FULLWIDTH) != 0;
     VPT_HIP(vpt::launch_decode_chars(d_utf8, d_boff, d_ooff, n, total_chars, fw ? t->d_cinfo.p : nullptr, cps.p, nullptr, status.p, st, fw));
+    if (!checked) VPT_HIP(vpt::train_check_labels(d_labels, total_b, status.p, st));
     uint32_t bad[2] = {0, 0};
     VPT_HIP(hipMemcpyAsync(bad, status.p, 4, hipMemcpyDeviceToHost, st));
     VPT_HIP(hipStreamSynchronize(st));
-    if (bad[0]) return fail_arg("out_offsets: do not match the text");
+    if (bad[0] & ~vpt::kErrBadLabel) return fail_arg("out_offsets: do not match the text");
+    if (bad[0]) return fail_arg("labels: must be 0, 1 or 2");
     // the tags' CSR is checked on the device before anything follows one of its offsets
     VPT_HIP(vpt::train_tag_validate(d_n_tags, d_ooff, n, total_chars, d_tag_index, d_span_off, n_spans, n_tag_bytes, status.p + 1, st));
     VPT_HIP(hipMemcpyAsync(bad + 1, status.p + 1, 4, hipMemcpyDeviceToHost, st));
@@ -1109,8 +1127,6 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
             }
         }
     }
-    // the boundary examples, exactly as the untagged call adds them
-    VPT_TRY(add_device(t, d_utf8, d_boff, d_ooff, n, total_b, d_labels, flags, st));
     // the tag examples: count, place, write
     DBuf<uint64_t> ex_off, key_off;
     VPT_HIP(counts.resize(total_chars)); VPT_HIP(is_ex.resize(total_chars)); VPT_HIP(ex_off.resize(total_chars + 1)); VPT_HIP(key_off.resize(total_chars + 1));
@@ -1123,6 +1139,8 @@ vpt_status add_tagged_device(vpt_trainer* t, const uint8_t* d_utf8, const uint64
     VPT_TRY(scan_total(t, counts.p, total_chars, key_off.p, &n_keys));
     if (t->n_tag_cps + total_chars >= (uint64_t(1) << 32) || t->n_tag_keys + n_keys >= (uint64_t(1) << 32) || t->n_tag_ex + n_ex >= (uint64_t(1) << 32))
         return fail_arg("examples: at most 2^32 - 1 chars, tagged tokens and tag feature occurrences");
+    // the boundary examples, exactly as the untagged call adds them: behind the last refusal, so that a refused batch adds nothing
+    VPT_TRY(add_device(t, d_utf8, d_boff, d_ooff, n, total_b, d_labels, flags, st, true));
     // the examples stay on the device: the batch's chars, the records and the keys are appended to the trainer's arrays
     DBuf<uint32_t> recs;
     VPT_HIP(recs.resize(4 * n_ex));
@@ -1282,7 +1300,7 @@ vpt_status vpt_trainer_add_batch_device(void* th, const uint8_t* d_utf8, const u
     vpt_trainer* t = static_cast<vpt_trainer*>(th);
     if (!t || (n_sentences && (!d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels))))
         return fail_arg("NULL argument");
-    return add_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, flags, static_cast<hipStream_t>(hip_stream));
+    return add_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, flags, static_cast<hipStream_t>(hip_stream), false);
 }
 
 vpt_status vpt_trainer_add_batch(void* th, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint8_t* labels,
@@ -1292,7 +1310,7 @@ vpt_status vpt_trainer_add_batch(void* th, const uint8_t* utf8, const uint64_t* 
     if (n_sentences == 0) return VPT_OK;
     StagedBatch B;
     VPT_TRY(stage_batch(t, utf8, byte_offsets, n_sentences, labels, B));
-    return add_device(t, B.d_text.p, B.d_boff.p, B.d_ooff.p, n_sentences, B.total_b, B.d_labels.p, flags, t->st);
+    return add_device(t, B.d_text.p, B.d_boff.p, B.d_ooff.p, n_sentences, B.total_b, B.d_labels.p, flags, t->st, true);
 }
 
 vpt_status vpt_trainer_n_features(void* th, size_t* out) {
@@ -1409,7 +1427,7 @@ vpt_status vpt_trainer_add_tagged_batch_device(void* th, const uint8_t* d_utf8, 
                                                       d_tag_index && d_span_offsets && (!n_tag_bytes || d_tag_bytes)));
     if (!t) return VPT_INVALID_ARGUMENT;
     return add_tagged_device(t, d_utf8, d_byte_offsets, d_out_offsets, n_sentences, total_boundaries, d_labels, d_n_tags, d_tag_index, d_span_offsets,
-                             d_tag_bytes, n_spans, n_tag_bytes, flags, static_cast<hipStream_t>(hip_stream));
+                             d_tag_bytes, n_spans, n_tag_bytes, flags, static_cast<hipStream_t>(hip_stream), false);
 }
 
 vpt_status vpt_trainer_add_tagged_batch(void* th, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_sentences, const uint8_t* labels,
@@ -1430,7 +1448,7 @@ vpt_status vpt_trainer_add_tagged_batch(void* th, const uint8_t* utf8, const uin
     VPT_HIP(hipMemcpyAsync(d_so.p, span_offsets, (n_spans + 1) * 8, hipMemcpyHostToDevice, t->st));
     if (n_tag_bytes) VPT_HIP(hipMemcpyAsync(d_tb.p, tag_bytes, n_tag_bytes, hipMemcpyHostToDevice, t->st));
     return add_tagged_device(t, B.d_text.p, B.d_boff.p, B.d_ooff.p, n_sentences, B.total_b, B.d_labels.p, d_nt.p, d_ti.p, d_so.p, d_tb.p, n_spans,
-                             n_tag_bytes, flags, t->st);
+                             n_tag_bytes, flags, t->st, true);
 }
 
 vpt_status vpt_trainer_set_tag_dictionary(void* th, const uint8_t* surfaces_utf8, const uint64_t* surface_offsets, size_t n_surfaces,

@@ -431,6 +431,7 @@ struct TrainFeatParams {
     uint64_t* keys;             // emit pass: two words per key (low, high)
 };
 hipError_t train_features(const TrainFeatParams& P, bool emit, hipStream_t st);
+hipError_t train_check_labels(const uint8_t* labels, uint64_t n, uint32_t* status, hipStream_t st);   // ORs kErrBadLabel for a label above 2
 uint64_t train_scan_scratch(uint64_t n);
 hipError_t train_scan(const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);   // out[n + 1], exclusive
 hipError_t train_scan(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* scratch, hipStream_t st);

@@ -96,6 +96,12 @@ __global__ __launch_bounds__(kTrainThreads) void features_kernel(TrainFeatParams
     else P.counts[b] = boundary_features<false>(P, chars, n, p, 0);
 }
 
+// The labels of a device caller, which no host loop has seen: one above 2 (no CharacterBoundary) raises kErrBadLabel.
+__global__ __launch_bounds__(kTrainThreads) void check_labels_kernel(const uint8_t* labels, uint64_t n, uint32_t* status) {
+    const uint64_t i = uint64_t(blockIdx.x) * kTrainThreads + threadIdx.x;
+    if (i < n && labels[i] > 2) atomicOr(status, kErrBadLabel);
+}
+
 // ---------------------------------------------------------------------------------------------------- exclusive scan (u32 / u64 -> u64)
 __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* lds, uint64_t* total) {
     const uint32_t t = threadIdx.x;
@@ -395,6 +401,9 @@ hipError_t train_features(const TrainFeatParams& P, bool emit, hipStream_t st) {
     if (emit) hipLaunchKernelGGL(features_kernel<true>, g, dim3(kTrainThreads), 0, st, P);
     else hipLaunchKernelGGL(features_kernel<false>, g, dim3(kTrainThreads), 0, st, P);
     return hipGetLastError();
+}
+hipError_t train_check_labels(const uint8_t* labels, uint64_t n, uint32_t* status, hipStream_t st) {
+    return launch1(check_labels_kernel, n, st, labels, n, status);
 }
 uint64_t train_scan_scratch(uint64_t n) { return tiles(n) + 1; }
 template <typename T>
