@@ -695,6 +695,19 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * by one workgroup of one launch with w and b in LDS (path 1), a larger one, or every one after vpt_trainer_set_tag_path(1), by the
  * group launches of the boundary solver, a class at a time (path 2); both use one summation rule.  vpt_trainer_tag_weights' stats then
  * have solver 5's meanings (below).  With the third flag solvers 0 and 2 give the bytes they give without it.
+ * Solver 6 (L1R_LR, L1-regularised logistic regression) is opt-in too: a trainer created with VPT_TRAIN_L1R_LR in params->flags -- alone
+ * or beside any accepted combination of the flags above -- also accepts solver == 6 and then runs liblinear's newGLMNET (solve_l1r_lr)
+ * on the device for  |w|_1 + C sum log(1 + exp(-y w.x)),  the bias inside the norm: per Newton iteration one launch over all columns
+ * for the model's diagonal, the gradient and the violations at w; coordinate descent over the quadratic model by the same column
+ * groups, a launch per group, the groups in a new seeded order every inner sweep, until a sweep's violation sum is <= inner_eps * the
+ * first outer one (inner_eps 1, times 0.25 after an iteration of one sweep; at most 1000 sweeps); then a line search over all rows
+ * that halves the step at most 20 times.  It stops by liblinear's rule (the violation sum at w <= eps * max(min(pos, neg), 1) / rows *
+ * the first one) or after 100 Newton iterations.  Divergences from liblinear: no shrinking at either level; after 20 refused trials
+ * the trial weights are put back to w; sums run in the fixed order of solver 5's kernels, so the same examples and arguments give
+ * byte-identical models on every run.  Without the flag every message and every byte of every model is as above.  With it solvers 0
+ * and 2 (and 5, with VPT_TRAIN_L1R) train exactly as without it; the other solvers are VPT_INVALID_ARGUMENT "solver: only 0, 2 and 6
+ * are implemented" ("only 0, 2, 5 and 6" with VPT_TRAIN_L1R); solver 6 on a trainer with VPT_TRAIN_TAGS is VPT_INVALID_ARGUMENT
+ * "solver 6: tag models are trained with solvers 0, 2 and 5 only".
  * Divergences: tag models are trained only by a trainer created with VPT_TRAIN_TAGS (below), without it the caller rejects or drops tags
  * (the train CLI's --ignore-tags); solvers 1, 3-7 are
  * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
@@ -707,12 +720,15 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * nonzero (CSR and CSC copies: 4-byte index + 2-byte count each), 16 bytes (sorted key) + 8 bytes (CSC column pointer) per feature,
  * and the column segments of Xᵀv: per level 8 bytes per feature (pointers) and 12 bytes per segment (column + partial sum), with at
  * least one segment per feature per level and ceil(log64(longest column)) levels -- about 100 bytes per feature when one column
- * holds tens of millions of nonzeros.  Training adds 48 bytes per boundary and 56 per feature for the fp64 vectors.  While the ids
+ * holds tens of millions of nonzeros.  Training adds 48 bytes per boundary and 56 per feature for the fp64 vectors: solver 6's five
+ * vectors per boundary (exp(w.x), tau, D, xTd, the terms of a sum) and six per feature (trial weights, diagonal, gradient, negative-row
+ * sums, violations, the terms of a sum) are TRON's own, so it adds none; like solver 5 it adds 16 bytes per 64 nonzeros and per
+ * feature for the long columns' partial sums, and 4 bytes per feature twice for the column lists.  While the ids
  * are assigned, about 52 bytes per feature occurrence are in use for the table, the sort and the per-occurrence ids.
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
  *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0, VPT_TRAIN_TAGS, VPT_TRAIN_L1R, both, or both with
- *   VPT_TRAIN_TAGS_L1R (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ...").
+ *   VPT_TRAIN_TAGS_L1R, each with or without VPT_TRAIN_L1R_LR (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ...").
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
  * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's or vpt_parse_partial_batch_device's raw
@@ -733,12 +749,19 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * vpt_trainer_last_stats: TRON iterations, CG steps, the gradient norms at w = 0 and at the result, and the objective.  After solver 5
  *   the same layout holds: iterations = sweeps, cg_steps = line-search halvings (each follows a pass over the column's data; a step
  *   that the data-free test accepts costs none), gnorm0 / gnorm = the first and the last sweep's violation sums, objective =
- *   |w|_1 + C sum max(0, 1 - y w.x)^2, the bias inside the norm as liblinear has it. */
+ *   |w|_1 + C sum max(0, 1 - y w.x)^2, the bias inside the norm as liblinear has it.  After solver 6: iterations = Newton iterations,
+ *   cg_steps = inner sweeps over all of them, gnorm0 / gnorm = the first and the last violation sum at w, objective =
+ *   |w|_1 + C sum log(1 + exp(-y w.x)) recomputed from the returned weights. */
 typedef struct vpt_train_params {
     uint32_t charw, charn, typew, typen, dictn;
-    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R */
+    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR */
 } vpt_train_params;
-enum { VPT_TRAIN_TAGS = 1, VPT_TRAIN_L1R = 4, VPT_TRAIN_TAGS_L1R = 8 /* needs both others; bit 1 stays an unknown flag */ };
+enum {
+    VPT_TRAIN_TAGS = 1,
+    VPT_TRAIN_L1R = 4,
+    VPT_TRAIN_TAGS_L1R = 8, /* needs both others; bit 1 stays an unknown flag */
+    VPT_TRAIN_L1R_LR = 16   /* solver 6; alone or beside any accepted combination of the others */
+};
 typedef struct vpt_train_stats {
     uint32_t iterations;
     uint32_t cg_steps;

@@ -1,11 +1,13 @@
 """The trainer on a synthetic corpus: random text labelled by the golden model's predictions, then api.Trainer with --solver 2 (the
-default) or 5 (a Trainer(l1r=True); the option may be given more than once: the solvers then train one after the other on the same
-trainer and matrix, a line each).
+default), 5 (a Trainer(l1r=True)) or 6 (a Trainer(l1r_lr=True)); the option may be given more than once: the solvers then train one
+after the other on the same trainer and matrix, a line each.
 
 Reports one JSON line per solver: feature extraction (vpt_trainer_add_batch) and id assignment / design matrix (the first vpt_trainer_n_features)
 with keys per second, the TRON iterations and CG steps, the training time and the mean time per CG step (one Xw, one Xᵀv and the
 reductions).  Xw and Xᵀv are not timed on their own.  For solver 5 the line holds the sweeps, the seconds per sweep, the line-search
-halvings and the first and last violation sums instead; every line ends with the nonzero weights and the model's bytes.  A CPU
+halvings and the first and last violation sums instead, for solver 6 the Newton iterations, the inner sweeps, the seconds per inner
+sweep (the whole training over the sweeps: the launches over all columns and the line searches are in it) and the two violation sums;
+every line ends with the nonzero weights and the model's bytes.  A CPU
 comparison with sklearn's liblinear is not part of it yet."""
 import argparse
 import json
@@ -26,7 +28,7 @@ def main():
     ap.add_argument("--sentences", type=int, default=1_000_000)
     ap.add_argument("--chars", type=int, default=64)
     ap.add_argument("--batch", type=int, default=250_000)
-    ap.add_argument("--solver", type=int, action="append", choices=(2, 5))
+    ap.add_argument("--solver", type=int, action="append", choices=(2, 5, 6))
     a = ap.parse_args()
     solvers = a.solver or [2]
     from vaporetto_amd import api
@@ -34,7 +36,7 @@ def main():
     labeler = api.Predictor(api.Model.read_slice(raw)[0], False, device=0)
     rng = np.random.default_rng(0)
     alpha = np.array([c.encode() for c in ALPHABET], dtype=object)
-    t = api.Trainer(3, 3, 3, 3, l1r=5 in solvers)
+    t = api.Trainer(3, 3, 3, 3, l1r=5 in solvers, l1r_lr=6 in solvers)
     t_add, n_b = 0.0, 0
     for s0 in range(0, a.sentences, a.batch):
         n = min(a.batch, a.sentences - s0)
@@ -63,6 +65,9 @@ def main():
         out = dict(base, solver=solver, train_s=round(t_train, 3))
         if solver == 5:
             out.update(sweeps=st["iterations"], s_per_sweep=round(t_train / max(st["iterations"], 1), 4), halvings=st["cg_steps"],
+                       violation0=st["gnorm0"], violation=st["gnorm"])
+        elif solver == 6:
+            out.update(newton_iterations=st["iterations"], inner_sweeps=st["cg_steps"], s_per_inner_sweep=round(t_train / max(st["cg_steps"], 1), 4),
                        violation0=st["gnorm0"], violation=st["gnorm"])
         else:
             out.update(tron_iterations=st["iterations"], cg_steps=st["cg_steps"], ms_per_cg_step=round(1e3 * t_train / max(st["cg_steps"], 1), 3),

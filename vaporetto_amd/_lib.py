@@ -51,6 +51,7 @@ class TrainStats(C.Structure):
 VPT_TRAIN_TAGS = 1
 VPT_TRAIN_L1R = 4
 VPT_TRAIN_TAGS_L1R = 8
+VPT_TRAIN_L1R_LR = 16
 
 
 class TagProblemInfo(C.Structure):

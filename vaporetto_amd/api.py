@@ -1624,7 +1624,7 @@ def model_inspect(model_bytes: bytes, predict_tags: bool = False) -> dict:
     return mi.as_dict()
 
 
-class SolverType(enum.IntEnum):  # trainer.rs:20-45; the primal TRON solvers 0 and 2 and, on a Trainer(l1r=True), solver 5 are implemented
+class SolverType(enum.IntEnum):  # trainer.rs:20-45; the primal TRON solvers 0 and 2 and, on a Trainer(l1r=True), solver 5, on a Trainer(l1r_lr=True), solver 6 are implemented
     L2RegularizedLogistic = 0
     L2RegularizedL2LossSVCDual = 1
     L2RegularizedL2LossSVC = 2
@@ -1644,11 +1644,14 @@ class Trainer:
     SolverType.L1RegularizedL2LossSVC, the solver the reference's README trains with: most weights end at exactly 0 and are not written.
     Solvers 0 and 2 train as without it; tag models are not trained with solver 5 unless `l1r_tags=True` (VPT_TRAIN_TAGS_L1R, which
     needs both `l1r` and `train_tags`): then solver 5 trains every tag problem by the same coordinate descent, one-vs-rest, and the tag
-    models are sparse too; tag_stats() then carries sweeps and halvings as last_stats() does."""
+    models are sparse too; tag_stats() then carries sweeps and halvings as last_stats() does.  With `l1r_lr=True` (VPT_TRAIN_L1R_LR,
+    alone or beside any of the above) train also accepts SolverType.L1RegularizedLogistic: liblinear's newGLMNET on the device, a sparse
+    boundary model with the logistic loss; last_stats() then carries Newton iterations and inner sweeps.  Tag models are not trained
+    with solver 6: with `train_tags` it is refused."""
 
     def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
                  ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = (), l1r: bool = False,
-                 l1r_tags: bool = False):
+                 l1r_tags: bool = False, l1r_lr: bool = False):
         if l1r_tags and not (l1r and train_tags):
             raise ValueError("l1r_tags needs l1r=True and train_tags=True")
         if ignore_tags and train_tags:
@@ -1663,8 +1666,9 @@ class Trainer:
         self.dict_words = list(dict_words)
         self.l1r = bool(l1r)
         self.l1r_tags = bool(l1r_tags)
+        self.l1r_lr = bool(l1r_lr)
         prm = _lib.TrainParams(charw, charn, typew, typen, dictn, (_lib.VPT_TRAIN_TAGS if train_tags else 0) | (_lib.VPT_TRAIN_L1R if l1r else 0) |
-                               (_lib.VPT_TRAIN_TAGS_L1R if l1r_tags else 0))
+                               (_lib.VPT_TRAIN_TAGS_L1R if l1r_tags else 0) | (_lib.VPT_TRAIN_L1R_LR if l1r_lr else 0))
         utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
         st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
         if st != _lib.VPT_OK:

@@ -1,6 +1,7 @@
 // C ABI of libvaporetto_hip.so, boundary-model training: Trainer (vaporetto/src/trainer.rs) with the liblinear TRON solvers 0 and 2 and,
 // on a trainer created with VPT_TRAIN_L1R, the coordinate descent of solver 5 by column groups (solve_l1r, l1r.h); with
 // VPT_TRAIN_TAGS_L1R beside it solver 5 trains the tag models too (kernels_train_tags_l1.hip in LDS, solve_l1r for what does not fit).
+// On a trainer created with VPT_TRAIN_L1R_LR solver 6 trains the boundary model by newGLMNET over the same groups (solve_l1r_lr, l1r_lr.h).
 //
 // The vpt_trainer handle keeps every example's feature keys and label on the device (kernels_train.hip); feature ids, the CSR and CSC
 // copies of the design matrix are made when they are first needed after an add, and the TRON / CG loop runs here, on the host, over
@@ -10,6 +11,7 @@
 // Quantisation and the model layout are trainer.rs:352-487; the encoder mirrors vaporetto_amd/modelfmt.encode_model (model.rs:99-104).
 #include "capi_internal.hpp"
 #include "l1r.h"
+#include "l1r_lr.h"
 #include "tron.h"
 
 #include <chrono>
@@ -548,6 +550,118 @@ vpt_status solve_l1r(vpt_trainer* t, const Matrix& M, uint64_t nr, const std::ve
     double norm1 = 0;
     for (uint64_t j = 0; j < n; ++j) norm1 += std::fabs(w_out[j]);
     *stats = vpt_train_stats{sweeps, halvings, v0, v, norm1 + loss};
+    return VPT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- solver 6 (l1r_lr.h)
+// The host backend of l1r_lr.h: a step is a launch, a sum is Tron's fixed-shape reduction read back.  Every vector is one of Tron's:
+// per feature w, wpd (w_new), Grad (g), Hdiag (s), xjneg_sum (r), the violations (d) and the terms of a sum (Hd); per row y, e (z),
+// tau (zt), D, xTd (gz) and the terms of a sum (loss).
+struct L1lr {
+    Tron T;
+    const L1rGroups* G;
+    vpt::L1lrParams P{};
+    DBuf<uint32_t> d_cols, d_all;   // the groups' columns; every column by length class, for the launch over all of them
+    DBuf<vpt::L1rPair> tile0, tile1;
+    DBuf<double> pack;              // three sums, read back in one copy
+    uint32_t all_lane = 0, all_wave = 0, all_block = 0;
+    hipStream_t st;
+    uint64_t n;
+
+    vpt_status init(vpt_trainer* t, const Matrix& M, uint64_t nr, const std::vector<double>& y, const L1rGroups& G_, double cost) {
+        st = t->st; G = &G_; n = M.nd + 1;
+        VPT_TRY(T.init(M, st, nr, 0, cost));
+        std::vector<uint32_t> all;
+        for (int cls = 0; cls < 3; ++cls)
+            for (size_t g = 0; g < G_.size(); ++g) {
+                const uint64_t a = G_.ptr[g], lane = a + G_.n_lane[g], wave = lane + G_.n_wave[g];
+                const uint64_t lo = cls == 0 ? a : cls == 1 ? lane : wave, hi = cls == 0 ? lane : cls == 1 ? wave : G_.ptr[g + 1];
+                all.insert(all.end(), G_.cols.begin() + lo, G_.cols.begin() + hi);
+                (cls == 0 ? all_lane : cls == 1 ? all_wave : all_block) += uint32_t(hi - lo);
+            }
+        VPT_HIP(d_cols.resize(G_.cols.size())); VPT_HIP(d_all.resize(all.size())); VPT_HIP(pack.resize(3));
+        VPT_HIP(tile0.resize(vpt::train_l1r_scratch(M.nnz, nr, M.nd, 0))); VPT_HIP(tile1.resize(vpt::train_l1r_scratch(M.nnz, nr, M.nd, 1)));
+        VPT_HIP(hipMemcpy(T.y.p, y.data(), nr * 8, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(d_cols.p, G_.cols.data(), G_.cols.size() * 4, hipMemcpyHostToDevice));
+        VPT_HIP(hipMemcpy(d_all.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        P.cptr = M.cptr.p; P.crow = M.crow.p; P.cval = M.cval.p; P.nd = M.nd; P.nr = nr; P.nnz = M.nnz;
+        P.y = T.y.p; P.e = T.z.p; P.tau = T.zt.p; P.D = T.D.p; P.xTd = T.gz.p;
+        P.w = T.w.p; P.wpd = T.w_new.p; P.grad = T.g.p; P.hdiag = T.s.p; P.xjneg = T.r.p; P.viol = T.d.p;
+        P.tile0 = tile0.p; P.tile1 = tile1.p; P.c = cost;
+        return VPT_OK;
+    }
+    bool ok() const { return T.ok(); }
+    void run(hipError_t e) { if (ok()) T.err = e; }
+    void setup() {
+        T.zero(P.w); T.zero(P.wpd);
+        if (ok()) run(vpt::train_l1lr_start(P, true, st));
+        if (ok()) run(vpt::train_l1lr_accept(P, st));   // xTd = 0: e stays 1
+        if (ok()) run(vpt::train_l1lr_grad(P, true, d_all.p, all_lane, all_wave, all_block, st));
+    }
+    double grad() {
+        if (ok()) run(vpt::train_l1lr_grad(P, false, d_all.p, all_lane, all_wave, all_block, st));
+        return T.dot(P.viol, nullptr, n);
+    }
+    void qp_start() { if (ok()) run(vpt::train_l1lr_start(P, false, st)); }
+    void cd_group(uint32_t g) {
+        const uint32_t total = uint32_t(G->ptr[g + 1] - G->ptr[g]);
+        if (ok()) run(vpt::train_l1lr_cd_group(P, d_cols.p + G->ptr[g], G->n_lane[g], G->n_wave[g], total - G->n_lane[g] - G->n_wave[g], st));
+    }
+    double qp_violation() { return T.dot(P.viol, nullptr, n); }
+    void keep(const double* sum, int k) { if (ok()) run(hipMemcpyAsync(pack.p + k, sum, 8, hipMemcpyDeviceToDevice, st)); }
+    vpt::L1lrSums direction_sums() {
+        if (ok()) run(vpt::train_l1lr_feat_terms(P, T.Hd.p, P.viol, st));
+        keep(T.reduce_dev(T.Hd.p, nullptr, n), 0);
+        keep(T.reduce_dev(P.viol, nullptr, n), 1);
+        if (ok()) run(vpt::train_l1lr_neg_terms(P, T.loss.p, st));
+        keep(T.reduce_dev(T.loss.p, nullptr, P.nr), 2);
+        double s[3] = {0, 0, 0};
+        if (ok()) run(hipMemcpyAsync(s, pack.p, sizeof s, hipMemcpyDeviceToHost, st));
+        if (ok()) run(hipStreamSynchronize(st));
+        return {s[0], s[1], s[2]};
+    }
+    double linesearch_loss() {
+        if (ok()) run(vpt::train_l1lr_ls_terms(P, T.loss.p, st));
+        return T.dot(T.loss.p, nullptr, P.nr);
+    }
+    void accept() {
+        T.copy(P.wpd, P.w);
+        if (ok()) run(vpt::train_l1lr_accept(P, st));
+    }
+    double halve() {
+        if (ok()) run(vpt::train_l1lr_halve(P, st));
+        if (ok()) run(vpt::train_l1lr_feat_terms(P, nullptr, P.viol, st));
+        return T.dot(P.viol, nullptr, n);
+    }
+    void recompute() {
+        if (ok()) run(vpt::train_xv(T.m->csr_ptr.p, T.m->cols.p, T.m->vals.p, P.nr, P.w, P.nd, P.e, st));
+        if (ok()) run(vpt::train_l1lr_exp(P.nr, P.e, st));
+        T.copy(P.w, P.wpd);
+    }
+};
+
+// solve_l1r_lr from w = 0 over the matrix M of nr rows with the targets y (`pos` of them +1) and the groups G, as solve_l1r takes them.
+// Readbacks: one per inner sweep, one per line-search trial, and per Newton iteration the violations' sum and the three sums of the
+// direction in one copy.  Out come the weights and the stats: Newton iterations, inner sweeps, the first and last violation sums at w,
+// and |w|_1 + C sum log(1 + exp(-y w.x)) recomputed from w by solver 0's loss.
+vpt_status solve_l1r_lr(vpt_trainer* t, const Matrix& M, uint64_t nr, const std::vector<double>& y, uint64_t pos, const L1rGroups& G, double eps, double cost,
+                        double* w_out, vpt_train_stats* stats) {
+    L1lr S;
+    VPT_TRY(S.init(t, M, nr, y, G, cost));
+    std::vector<uint32_t> order(G.size());
+    for (size_t g = 0; g < G.size(); ++g) order[g] = uint32_t(g);
+    const vpt::L1lrResult r = vpt::l1r_lr(S, vpt::tron_tolerance(eps, double(pos), double(nr)), order.data(), uint32_t(order.size()));
+    VPT_HIP(S.T.err);
+    Tron& T = S.T;
+    VPT_HIP(hipMemcpyAsync(w_out, T.w.p, S.n * 8, hipMemcpyDeviceToHost, t->st));
+    // the loss at the weights themselves, not at the e the iterations carried along
+    VPT_HIP(vpt::train_xv(M.csr_ptr.p, M.cols.p, M.vals.p, nr, T.w.p, M.nd, T.z.p, t->st));
+    VPT_HIP(vpt::train_loss(nr, T.z.p, T.y.p, cost, 0, T.loss.p, t->st));
+    const double loss = T.dot(T.loss.p, nullptr, nr);
+    VPT_HIP(T.err);
+    double norm1 = 0;
+    for (uint64_t j = 0; j < S.n; ++j) norm1 += std::fabs(w_out[j]);
+    *stats = vpt_train_stats{r.newton, r.sweeps, r.gnorm0, r.gnorm, norm1 + loss};
     return VPT_OK;
 }
 
@@ -1229,8 +1343,9 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     if (p.charw > 16) return fail_arg("charw: must be at most 16");
     if (p.typew > 16) return fail_arg("typew: must be at most 16");
     if (p.typew > p.charw) return fail_arg("typew: must not exceed charw (type weights use the char window)");
-    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R)) != 0)
-        return fail_arg("flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR)) != 0)
+        return fail_arg((p.flags & VPT_TRAIN_L1R_LR) ? "flags: unknown bit beside VPT_TRAIN_L1R_LR (the others: VPT_TRAIN_TAGS, VPT_TRAIN_L1R, VPT_TRAIN_TAGS_L1R)"
+                                                     : "flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
     if ((p.flags & VPT_TRAIN_TAGS_L1R) && (p.flags & (VPT_TRAIN_TAGS | VPT_TRAIN_L1R)) != (VPT_TRAIN_TAGS | VPT_TRAIN_L1R))
         return fail_arg("flags: VPT_TRAIN_TAGS_L1R needs both VPT_TRAIN_TAGS and VPT_TRAIN_L1R");
     if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail_arg("dictn: must be at least 1 with a dictionary");
@@ -1348,10 +1463,12 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
     double ec[2];
     std::memcpy(ec, eps_cost, sizeof ec);
     const double eps = ec[0], cost = ec[1];
-    const bool l1r = (t->prm.flags & VPT_TRAIN_L1R) != 0;
-    if (!l1r && solver != 0 && solver != 2) return fail_arg("solver: only 0 and 2 are implemented");
-    if (l1r && solver != 0 && solver != 2 && solver != 5) return fail_arg("solver: only 0, 2 and 5 are implemented");
+    const bool l1r = (t->prm.flags & VPT_TRAIN_L1R) != 0, l1lr = (t->prm.flags & VPT_TRAIN_L1R_LR) != 0;
+    if (solver != 0 && solver != 2 && !(l1r && solver == 5) && !(l1lr && solver == 6))
+        return fail_arg(l1lr ? (l1r ? "solver: only 0, 2, 5 and 6 are implemented" : "solver: only 0, 2 and 6 are implemented")
+                             : (l1r ? "solver: only 0, 2 and 5 are implemented" : "solver: only 0 and 2 are implemented"));
     if (solver == 5 && (t->prm.flags & VPT_TRAIN_TAGS) && !(t->prm.flags & VPT_TRAIN_TAGS_L1R)) return fail_arg("solver 5: tag models are trained with solvers 0 and 2 only");
+    if (solver == 6 && (t->prm.flags & VPT_TRAIN_TAGS)) return fail_arg("solver 6: tag models are trained with solvers 0, 2 and 5 only");
     if (!(eps > 0) || !(cost > 0)) return fail_arg("eps and cost: must be positive");
     VPT_HIP(hipSetDevice(t->device));
     t->trained = false;
@@ -1370,11 +1487,11 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
         return fail_arg("examples: need both WordBoundary and other boundaries");
     std::vector<uint64_t> keys(2 * nd);
     if (nd) VPT_HIP(hipMemcpy(keys.data(), t->sorted_keys.p, keys.size() * 8, hipMemcpyDeviceToHost));
-    if (solver == 5) {
+    if (solver == 5 || solver == 6) {
         L1rGroups G;
         VPT_TRY(l1r_matrix_groups(t->m, nr, keys, G));
         t->w.resize(nd + 1);
-        VPT_TRY(solve_l1r(t, t->m, nr, y, pos, G, eps, cost, t->w.data(), &t->stats));
+        VPT_TRY((solver == 5 ? solve_l1r : solve_l1r_lr)(t, t->m, nr, y, pos, G, eps, cost, t->w.data(), &t->stats));
     } else {
         Tron T;
         VPT_TRY(T.init(t->m, t->st, nr, solver, cost));

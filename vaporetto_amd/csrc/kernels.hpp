@@ -489,6 +489,35 @@ uint64_t train_l1r_scratch(uint64_t nnz, uint64_t nr, uint64_t nd, int level);
 // cols[0 .. n_lane + n_wave + n_block): the group's columns in that order of length class; init: xj_sq alone
 hipError_t train_l1r_group(const L1rParams& P, bool init, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block, hipStream_t st);
 
+// solver 6 (kernels_train_l1lr.hip): the device backend of l1r_lr.h; columns by length class as train_l1r_group takes them, the
+// workgroups' level sums in tile0 / tile1 of train_l1r_scratch's sizes
+struct L1lrParams {
+    const uint64_t* cptr;       // the CSC copy of the design matrix; column nd is the bias: every row, value 1
+    const uint32_t* crow;
+    const uint16_t* cval;
+    uint64_t nd, nr, nnz;
+    const double* y;            // [nr] +1 / -1
+    double *e, *tau, *D, *xTd;  // [nr] exp(w.x), C / (1 + e), C e / (1 + e)^2, x.(wpd - w)
+    double *w, *wpd;            // [nd + 1]
+    double *hdiag, *grad;       // [nd + 1] of this Newton iteration
+    double* xjneg;              // [nd + 1] C sum_{y = -1} x
+    double* viol;               // [nd + 1] the columns' violations of the last grad launch or sweep
+    L1rPair *tile0, *tile1;
+    double c;
+};
+// all columns in one launch: xjneg (neg_sum) or hdiag, grad and viol at w
+hipError_t train_l1lr_grad(const L1lrParams& P, bool neg_sum, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block, hipStream_t st);
+// a group's columns of an inner sweep: wpd, xTd and viol
+hipError_t train_l1lr_cd_group(const L1lrParams& P, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block, hipStream_t st);
+hipError_t train_l1lr_start(const L1lrParams& P, bool setup, hipStream_t st);   // xTd = 0; setup: e = 1 too
+hipError_t train_l1lr_accept(const L1lrParams& P, hipStream_t st);              // e *= exp(xTd), tau and D from it
+hipError_t train_l1lr_ls_terms(const L1lrParams& P, double* out, hipStream_t st);    // [nr] the line search's row terms
+hipError_t train_l1lr_neg_terms(const L1lrParams& P, double* out, hipStream_t st);   // [nr] C xTd where y = -1
+hipError_t train_l1lr_exp(uint64_t n, double* z, hipStream_t st);               // z = exp(z)
+// [nd + 1] Grad_j (wpd_j - w_j) (delta NULL: skipped) and |wpd_j|
+hipError_t train_l1lr_feat_terms(const L1lrParams& P, double* delta, double* norm1, hipStream_t st);
+hipError_t train_l1lr_halve(const L1lrParams& P, hipStream_t st);               // wpd = (w + wpd) / 2, xTd /= 2
+
 // tag-model training (kernels_train_tags.hip)
 struct TagFeatParams {
     const uint32_t* cps;        // decode_chars' words: sentence i's char c at ooff[i] + i + c

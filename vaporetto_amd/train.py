@@ -12,12 +12,14 @@ reference's `Tags: n/n` line is printed once, at the end.
 
 With --l1r (ours) the trainer is made with l1r=True and --solver 5 (L1-regularised L2-loss SVC, the reference README's solver) trains by
 coordinate descent over column groups on the device; most weights end at exactly 0, so the model is small.  With --l1r-tags (ours)
-beside --l1r and --train-tags, --solver 5 trains the tag models too, by the same coordinate descent.
+beside --l1r and --train-tags, --solver 5 trains the tag models too, by the same coordinate descent.  With --l1r-lr (ours) the trainer
+is made with l1r_lr=True and --solver 6 (L1-regularised logistic regression) trains the boundary model by liblinear's newGLMNET on the
+device: a sparse model again, with the logistic loss.
 
 Divergences: without --train-tags tag models are not trained, so a corpus or dictionary line that carries a tag is an error naming the
 file and line unless --ignore-tags (ours) drops the tags; only solvers 0 and 2 are implemented, and solver 5 only with --l1r (ours: without
-it --solver 5 is refused like the others; with it and --train-tags it is refused too unless --l1r-tags is given); --zstd-workers does not
-exist."""
+it --solver 5 is refused like the others; with it and --train-tags it is refused too unless --l1r-tags is given), and solver 6 only with
+--l1r-lr (ours; refused together with --train-tags); --zstd-workers does not exist."""
 import argparse
 import sys
 
@@ -97,12 +99,13 @@ def main(argv=None) -> int:
     ap.add_argument("--eps", type=float, default=0.01, help="The epsilon stopping criterion for classifier training")
     ap.add_argument("--cost", type=float, default=1.0, help="The cost hyperparameter for classifier training")
     ap.add_argument("--solver", type=int, required=True, choices=range(8), metavar="{0..7}",
-                    help="The solver. {0, 1, 2, 3, 4, 5, 6, 7} (only 0 and 2 are implemented here, and 5 with --l1r)")
+                    help="The solver. {0, 1, 2, 3, 4, 5, 6, 7} (only 0 and 2 are implemented here, 5 with --l1r and 6 with --l1r-lr)")
     ap.add_argument("--no-norm", action="store_true", help="Do not normalize training data.")
     ap.add_argument("--ignore-tags", action="store_true", help="Drop tags of the corpora and dictionaries (no tag models are trained).")
     ap.add_argument("--train-tags", action="store_true", help="Keep the tags of the corpora and dictionaries and train the tag models.")
     ap.add_argument("--l1r", action="store_true", help="Make the trainer accept --solver 5 (L1-regularised L2-loss SVC).")
     ap.add_argument("--l1r-tags", action="store_true", help="With --l1r and --train-tags: --solver 5 trains the tag models too.")
+    ap.add_argument("--l1r-lr", action="store_true", help="Make the trainer accept --solver 6 (L1-regularised logistic regression).")
     args = ap.parse_args(argv)
     if not args.tok and not args.part:
         ap.error("one of --tok or --part is required")
@@ -156,7 +159,7 @@ def main(argv=None) -> int:
 
         print("Extracting into features...", file=sys.stderr)
         trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags,
-                              train_tags=args.train_tags, tag_dictionary=tag_dictionary, l1r=args.l1r, l1r_tags=args.l1r_tags)
+                              train_tags=args.train_tags, tag_dictionary=tag_dictionary, l1r=args.l1r, l1r_tags=args.l1r_tags, l1r_lr=args.l1r_lr)
         for utf8, boff, labels, p in batches:
             if p is not None:
                 trainer.add_packed_tagged(utf8, boff, labels, p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"],
