@@ -63,6 +63,14 @@ pub const fn flag_wsconst(char_type: u8) -> u32 {
     1 << char_type
 }
 
+/// `vpt_train_params.flags` for `ffi::vpt_trainer_create` (include/vaporetto_hip.h, Trainer): tag models; solver 5; solver 5 for the tag
+/// models (needs the two before it); solver 6; solver 6 for the tag models (needs `TRAIN_TAGS` and `TRAIN_L1R_LR`).
+pub const TRAIN_TAGS: u32 = 1;
+pub const TRAIN_L1R: u32 = 4;
+pub const TRAIN_TAGS_L1R: u32 = 8;
+pub const TRAIN_L1R_LR: u32 = 16;
+pub const TRAIN_TAGS_L1R_LR: u32 = 32;
+
 /// `vaporetto::Predictor` for batches, on one GPU.
 pub struct HipPredictor {
     raw: *mut ffi::vpt_predictor,

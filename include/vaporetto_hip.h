@@ -707,7 +707,17 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  * byte-identical models on every run.  Without the flag every message and every byte of every model is as above.  With it solvers 0
  * and 2 (and 5, with VPT_TRAIN_L1R) train exactly as without it; the other solvers are VPT_INVALID_ARGUMENT "solver: only 0, 2 and 6
  * are implemented" ("only 0, 2, 5 and 6" with VPT_TRAIN_L1R); solver 6 on a trainer with VPT_TRAIN_TAGS is VPT_INVALID_ARGUMENT
- * "solver 6: tag models are trained with solvers 0, 2 and 5 only".
+ * "solver 6: tag models are trained with solvers 0, 2 and 5 only".  That last sentence holds for a trainer without
+ * VPT_TRAIN_TAGS_L1R_LR.  A trainer created with VPT_TRAIN_TAGS | VPT_TRAIN_L1R_LR | VPT_TRAIN_TAGS_L1R_LR (the third without both
+ * others is VPT_INVALID_ARGUMENT "flags: ..."; VPT_TRAIN_L1R and VPT_TRAIN_TAGS_L1R may stand beside them) trains, under solver 6, the
+ * boundary model as above and every tag problem by the same newGLMNET, one-vs-rest over the problem's 0/1 matrix (one mirrored solve
+ * for two candidates), every class from w = 0 and the same seed, over solver 5's groups of a tag problem.  A problem with
+ * 3 * rows + (features + 1) <= 7256 doubles is solved by one workgroup of one launch (path 1): tau, D and xTd per row and the trial
+ * weights per feature in LDS, the weights, Grad, Hdiag, the negative-row sums and the violations per feature and exp(w.x) per row in
+ * global memory (5 * (features + 1) + rows doubles a problem); a larger one, or every one after vpt_trainer_set_tag_path(1), by the
+ * launches of the boundary solver, a class at a time (path 2); both use one summation rule.  In the kernel a sum that is not finite
+ * ends the solve.  vpt_trainer_tag_weights' stats then have solver 6's meanings (below).  With the flag solvers 0 and 2 (and 5, where
+ * the trainer accepts it) give the bytes they give without it.
  * Divergences: tag models are trained only by a trainer created with VPT_TRAIN_TAGS (below), without it the caller rejects or drops tags
  * (the train CLI's --ignore-tags); solvers 1, 3-7 are
  * VPT_INVALID_ARGUMENT "solver: only 0 and 2 are implemented"; a corpus without WordBoundary, or with nothing else, is
@@ -728,7 +738,8 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  *
  * vpt_trainer_create: dictionary words utf8[offsets[i] .. offsets[i+1]), distinct and non-empty, in the order the model lists them
  *   (the CLI passes the BTreeSet's, main.rs:132-161); params->flags must be 0, VPT_TRAIN_TAGS, VPT_TRAIN_L1R, both, or both with
- *   VPT_TRAIN_TAGS_L1R, each with or without VPT_TRAIN_L1R_LR (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ...").
+ *   VPT_TRAIN_TAGS_L1R, each with or without VPT_TRAIN_L1R_LR (any other bit or combination is VPT_INVALID_ARGUMENT "flags: ..."),
+ *   or a combination with VPT_TRAIN_TAGS and VPT_TRAIN_L1R_LR in it beside VPT_TRAIN_TAGS_L1R_LR.
  * vpt_trainer_add_batch: sentences as vpt_count_boundaries takes them, labels (0 / 1 / 2) laid out as it lays them out; flags:
  *   VPT_FLAG_KYTEA_FULLWIDTH extracts the features from the KyteaFullwidthFilter image of the text (the CLI without --no-norm).
  * vpt_trainer_add_batch_device: the same from device buffers (vpt_parse_tokenized_batch_device's or vpt_parse_partial_batch_device's raw
@@ -754,13 +765,14 @@ vpt_status vpt_predictor_info(const vpt_predictor *p, vpt_model_info *info);
  *   |w|_1 + C sum log(1 + exp(-y w.x)) recomputed from the returned weights. */
 typedef struct vpt_train_params {
     uint32_t charw, charn, typew, typen, dictn;
-    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR */
+    uint32_t flags; /* 0 or VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR | VPT_TRAIN_TAGS_L1R_LR */
 } vpt_train_params;
 enum {
     VPT_TRAIN_TAGS = 1,
     VPT_TRAIN_L1R = 4,
     VPT_TRAIN_TAGS_L1R = 8, /* needs both others; bit 1 stays an unknown flag */
-    VPT_TRAIN_L1R_LR = 16   /* solver 6; alone or beside any accepted combination of the others */
+    VPT_TRAIN_L1R_LR = 16,  /* solver 6; alone or beside any accepted combination of the others */
+    VPT_TRAIN_TAGS_L1R_LR = 32 /* solver 6 for the tag models; needs both VPT_TRAIN_TAGS and VPT_TRAIN_L1R_LR */
 };
 typedef struct vpt_train_stats {
     uint32_t iterations;
@@ -803,7 +815,8 @@ vpt_status vpt_trainer_last_stats(const void *t, void *stats);
  * deduplicated, numbered and written as CSR and CSC in a few launches over concatenated arrays.  The host interns the tag strings and, from
  * 8 bytes of ids an example, picks each problem's candidates, rows and y.  Every problem with 7 * (features + 1) + 3 * rows <= 7424 doubles is solved by one workgroup of one kernel
  * launch (TRON with its vectors in LDS), a larger one by the global-memory TRON of the boundary model, a class at a time.  (Solver 5 on a
- * trainer with VPT_TRAIN_TAGS_L1R: see the Trainer section; its in-kernel rule is (features + 1) + rows <= 7256.)
+ * trainer with VPT_TRAIN_TAGS_L1R: see the Trainer section; its in-kernel rule is (features + 1) + rows <= 7256.  Solver 6 on a trainer
+ * with VPT_TRAIN_TAGS_L1R_LR: see there too; its in-kernel rule is 3 * rows + (features + 1) <= 7256.)
  * Divergences: the in-kernel CG loop stops after 16 * (features + 1) + 64 steps (exact CG needs at most features + 1; liblinear's loop and the
  * global-memory solver have no cap), so that a non-finite problem cannot spin on the device.  A HIP error (not an argument error) after the
  * boundary examples of a batch were added leaves them added without the batch's tag examples: destroy the trainer then.

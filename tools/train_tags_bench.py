@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times tag-model training on a synthetic tagged corpus: extraction (add), problem construction, and the solver -- the batched
 in-kernel TRON against the same problems pushed one by one through the global-memory TRON (Trainer.set_tag_path(1)), in one process,
-after an untimed warm-up run.  The ratio is taken over the problems the kernel solved, the one-by-one side counting its TRON runs only.
+after an untimed warm-up run (--solver 5 and --solver 6: the L1 solvers' legs instead, below).  The ratio is taken over the problems the kernel solved, the one-by-one side counting its TRON runs only.
 
 Corpus: `--surfaces` random surfaces of 1-3 kana with Zipf-like weights 1 / rank, one tag slot, 2-8 candidates per surface, the tag
 decided by the char behind the token; `--sentences` sentences of 4-16 tokens.  Prints one JSON line with the sizes and the seconds."""
@@ -69,13 +69,41 @@ def l1_leg(arrays, res, out):
         fh.write("\n")
 
 
+def l1lr_leg(arrays, res, out):
+    """--solver 6: one Trainer with every flag (train_tags, l1r, l1r_tags, l1r_lr, l1r_lr_tags) trains the corpus with solvers 6, 5 and
+    2, each once untimed and once timed, by size; per solver the tag solvers' seconds, problems per path, iterations (Newton iterations,
+    sweeps or TRON iterations), inner steps (sweeps, halvings or CG steps), the share of exactly-zero weights, the model's size and its
+    SHA-256 go to `out`."""
+    import hashlib
+    t = api.Trainer(2, 2, 2, 2, train_tags=True, l1r=True, l1r_tags=True, l1r_lr=True, l1r_lr_tags=True)
+    t.add_packed_tagged(*arrays)
+    for solver in (6, 5, 2):
+        t.train_bytes(0.01, 1.0, solver)   # warm-up
+        t0 = time.perf_counter()
+        model = t.train_bytes(0.01, 1.0, solver)
+        t1 = time.perf_counter()
+        st = t.tag_stats()
+        sm = st["summary"]
+        w = np.concatenate([t.tag_weights(i).ravel() for i in range(len(st["problems"]))])
+        res["solver_%d" % solver] = {
+            "train_total_s": t1 - t0, "seconds_in_kernel": sm["seconds_in_kernel"], "seconds_large": sm["seconds_large"],
+            "seconds_large_solve": sm["seconds_large_solve"], "problems_in_kernel": sm["problems_in_kernel"], "problems_large": sm["problems_large"],
+            "iterations": int(sum(c["iterations"] for q in st["problems"] for c in q["classes"])),
+            "inner_steps": int(sum(c["cg_steps"] for q in st["problems"] for c in q["classes"])),
+            "zero_weight_share": float((w == 0.0).mean()), "model_bytes": len(model), "model_sha256": hashlib.sha256(model).hexdigest()}
+    print(json.dumps(res))
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sentences", type=int, default=4000)
     ap.add_argument("--surfaces", type=int, default=300)
     ap.add_argument("--solver", type=int, default=2)
     ap.add_argument("--seed", type=int, default=5)
-    ap.add_argument("--out", default="profiles/train_tags_l1_bench.json", help="where --solver 5 writes its result")
+    ap.add_argument("--out", default="profiles/train_tags_l1_bench.json", help="where --solver 5 writes its result; --solver 6 writes to it too (profiles/train_tags_l1lr_bench.json is its run's)")
     args = ap.parse_args()
     p = api.parse_tokenized_host(corpus(args.sentences, args.surfaces, args.seed))
     arrays = (p["raw"], p["raw_offsets"], p["labels"], p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"])
@@ -83,6 +111,8 @@ def main():
            "charn": 2, "typen": 2}
     if args.solver == 5:
         return l1_leg(arrays, res, args.out)
+    if args.solver == 6:
+        return l1lr_leg(arrays, res, args.out)
     # warm-up: one whole run by size (the device, the allocator and the code objects), not timed
     w = api.Trainer(2, 2, 2, 2, train_tags=True)
     w.add_packed_tagged(*arrays)

@@ -52,6 +52,7 @@ VPT_TRAIN_TAGS = 1
 VPT_TRAIN_L1R = 4
 VPT_TRAIN_TAGS_L1R = 8
 VPT_TRAIN_L1R_LR = 16
+VPT_TRAIN_TAGS_L1R_LR = 32
 
 
 class TagProblemInfo(C.Structure):

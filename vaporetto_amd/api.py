@@ -1647,13 +1647,17 @@ class Trainer:
     models are sparse too; tag_stats() then carries sweeps and halvings as last_stats() does.  With `l1r_lr=True` (VPT_TRAIN_L1R_LR,
     alone or beside any of the above) train also accepts SolverType.L1RegularizedLogistic: liblinear's newGLMNET on the device, a sparse
     boundary model with the logistic loss; last_stats() then carries Newton iterations and inner sweeps.  Tag models are not trained
-    with solver 6: with `train_tags` it is refused."""
+    with solver 6 -- with `train_tags` it is refused -- unless `l1r_lr_tags=True` (VPT_TRAIN_TAGS_L1R_LR, which needs both `l1r_lr` and
+    `train_tags`): then solver 6 trains every tag problem by the same newGLMNET, one-vs-rest, the tag models are sparse and their
+    scores are log-odds; tag_stats() then carries Newton iterations and inner sweeps."""
 
     def __init__(self, charw: int, charn: int, typew: int, typen: int, dict_words: Sequence[str] = (), dictn: int = 0, device: int = 0,
                  ignore_tags: bool = False, train_tags: bool = False, tag_dictionary: Sequence = (), l1r: bool = False,
-                 l1r_tags: bool = False, l1r_lr: bool = False):
+                 l1r_tags: bool = False, l1r_lr: bool = False, l1r_lr_tags: bool = False):
         if l1r_tags and not (l1r and train_tags):
             raise ValueError("l1r_tags needs l1r=True and train_tags=True")
+        if l1r_lr_tags and not (l1r_lr and train_tags):
+            raise ValueError("l1r_lr_tags needs l1r_lr=True and train_tags=True")
         if ignore_tags and train_tags:
             raise ValueError("ignore_tags and train_tags exclude each other")
         if tag_dictionary and not train_tags:
@@ -1667,8 +1671,10 @@ class Trainer:
         self.l1r = bool(l1r)
         self.l1r_tags = bool(l1r_tags)
         self.l1r_lr = bool(l1r_lr)
+        self.l1r_lr_tags = bool(l1r_lr_tags)
         prm = _lib.TrainParams(charw, charn, typew, typen, dictn, (_lib.VPT_TRAIN_TAGS if train_tags else 0) | (_lib.VPT_TRAIN_L1R if l1r else 0) |
-                               (_lib.VPT_TRAIN_TAGS_L1R if l1r_tags else 0) | (_lib.VPT_TRAIN_L1R_LR if l1r_lr else 0))
+                               (_lib.VPT_TRAIN_TAGS_L1R if l1r_tags else 0) | (_lib.VPT_TRAIN_L1R_LR if l1r_lr else 0) |
+                               (_lib.VPT_TRAIN_TAGS_L1R_LR if l1r_lr_tags else 0))
         utf8, off = pack_texts([w.encode("utf-8") for w in self.dict_words])
         st = self._L.vpt_trainer_create(C.addressof(prm), utf8.ctypes.data, off.ctypes.data, len(self.dict_words), device, C.byref(self._h))
         if st != _lib.VPT_OK:

@@ -1,7 +1,9 @@
 // C ABI of libvaporetto_hip.so, boundary-model training: Trainer (vaporetto/src/trainer.rs) with the liblinear TRON solvers 0 and 2 and,
 // on a trainer created with VPT_TRAIN_L1R, the coordinate descent of solver 5 by column groups (solve_l1r, l1r.h); with
 // VPT_TRAIN_TAGS_L1R beside it solver 5 trains the tag models too (kernels_train_tags_l1.hip in LDS, solve_l1r for what does not fit).
-// On a trainer created with VPT_TRAIN_L1R_LR solver 6 trains the boundary model by newGLMNET over the same groups (solve_l1r_lr, l1r_lr.h).
+// On a trainer created with VPT_TRAIN_L1R_LR solver 6 trains the boundary model by newGLMNET over the same groups (solve_l1r_lr, l1r_lr.h);
+// with VPT_TRAIN_TAGS_L1R_LR beside it and VPT_TRAIN_TAGS solver 6 trains the tag models too (kernels_train_tags_l1lr.hip in LDS,
+// solve_l1r_lr for what does not fit).
 //
 // The vpt_trainer handle keeps every example's feature keys and label on the device (kernels_train.hip); feature ids, the CSR and CSC
 // copies of the design matrix are made when they are first needed after an add, and the TRON / CG loop runs here, on the host, over
@@ -984,7 +986,8 @@ vpt_status fetch_rows(vpt_trainer* t, TagProblem& Pb) {
     return VPT_OK;
 }
 
-// one problem through the global-memory solver, a class at a time: TRON, or for solver 5 the group launches of solve_l1r
+// one problem through the global-memory solver, a class at a time: TRON, or for solvers 5 and 6 the group launches of solve_l1r and
+// solve_l1r_lr
 vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double cost, int solver) {
     hipStream_t st = t->st;
     const double t_setup = now_s();
@@ -1007,7 +1010,7 @@ vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double co
     VPT_TRY(csc_levels(t, M, d_rows.p, nz, nf));
     Tron T;
     L1rGroups G;
-    if (solver == 5) VPT_TRY(l1r_matrix_groups(M, l, tag_key_words(Pb), G));
+    if (solver == 5 || solver == 6) VPT_TRY(l1r_matrix_groups(M, l, tag_key_words(Pb), G));
     else VPT_TRY(T.init(M, st, l, solver, cost));
     std::vector<double> y(l);
     const uint64_t n_solve = k == 2 ? 1 : k, n = nf + 1;
@@ -1019,6 +1022,7 @@ vpt_status solve_tag_large(vpt_trainer* t, TagProblem& Pb, double eps, double co
         for (uint64_t r = 0; r < l; ++r) { y[r] = Pb.y[r] == c ? 1.0 : -1.0; pos += Pb.y[r] == c; }
         const double t_run = now_s();
         if (solver == 5) VPT_TRY(solve_l1r(t, M, l, y, pos, G, eps, cost, Pb.w.data() + c * n, &Pb.stats[c]));
+        else if (solver == 6) VPT_TRY(solve_l1r_lr(t, M, l, y, pos, G, eps, cost, Pb.w.data() + c * n, &Pb.stats[c]));
         else VPT_TRY(T.solve(y, pos, eps, &Pb.stats[c], Pb.w.data() + c * n));
         Pb.seconds_solve += now_s() - t_run;
     }
@@ -1036,9 +1040,9 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
     std::vector<vpt::TagSolveDesc> descs;
     std::vector<uint32_t> small;
     uint64_t n_w = 0, n_stats = 0;
-    // solver 5: the in-kernel problems' columns by group (l1r_groups over a problem's keys: a tag example has at most one feature per
-    // template, tag_trainer.rs:79-100) beside their descriptors
-    const bool l1 = solver == 5;
+    // solvers 5 and 6: the in-kernel problems' columns by group (l1r_groups over a problem's keys: a tag example has at most one feature
+    // per template, tag_trainer.rs:79-100) beside their descriptors; n_viol counts solver 5's violations or solver 6's scratch
+    const bool l1lr = solver == 6, l1 = solver == 5 || l1lr;
     std::vector<vpt::TagL1Desc> l1descs;
     std::vector<vpt::TagL1Group> l1groups;
     std::vector<uint32_t> gcols, h_cp, h_crow;
@@ -1056,7 +1060,7 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         const uint64_t l = Pb.y.size(), nf = Pb.keys.size(), k = Pb.cands.size();
         Pb.w.assign(k * (nf + 1), 0.0);
         Pb.stats.assign(k, vpt_train_stats{});
-        Pb.path = (t->tag_path_mode == 0 && (l1 ? vpt::train_tag_l1_fits(l, nf) : vpt::train_tag_fits(l, nf))) ? 1 : 2;
+        Pb.path = (t->tag_path_mode == 0 && (l1lr ? vpt::train_tag_l1lr_fits(l, nf) : l1 ? vpt::train_tag_l1_fits(l, nf) : vpt::train_tag_fits(l, nf))) ? 1 : 2;
         Pb.seconds_setup = Pb.seconds_solve = 0;
         if (Pb.path != 1) continue;
         // the problem where build_tags left it on the device
@@ -1071,13 +1075,13 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         const uint32_t* cp = h_cp.data() + D.cp;
         const L1rGroups G = l1r_groups(tag_key_words(Pb), cp, nf);
         VPT_TRY(l1r_check_groups(G, h_crow.empty() ? nullptr : h_crow.data() + D.cols, cp, l, nf));
-        if (G.size() > vpt::kTagL1MaxGroups) return fail(VPT_RUNTIME_ERROR, "solver 5: a tag problem with more column groups than its kernel holds");
+        if (G.size() > vpt::kTagL1MaxGroups) return fail(VPT_RUNTIME_ERROR, "solvers 5 and 6: a tag problem with more column groups than its kernel holds");
         vpt::TagL1Desc E{};
         E.gcols = gcols.size(); E.groups = l1groups.size(); E.viol = n_viol; E.n_groups = uint32_t(G.size());
         for (size_t g = 0; g < G.size(); ++g)
             l1groups.push_back(vpt::TagL1Group{uint32_t(G.ptr[g]), G.n_lane[g], G.n_wave[g], uint32_t(G.ptr[g + 1] - G.ptr[g])});
         gcols.insert(gcols.end(), G.cols.begin(), G.cols.end());
-        n_viol += nf + 1;
+        n_viol += l1lr ? vpt::train_tag_l1lr_scratch(l, nf) : nf + 1;
         l1descs.push_back(E);
     }
     if (!descs.empty()) {
@@ -1089,7 +1093,7 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
         VPT_HIP(hipMemcpyAsync(d_desc.p, descs.data(), descs.size() * sizeof(vpt::TagSolveDesc), hipMemcpyHostToDevice, st));
         VPT_HIP(hipMemsetAsync(d_w.p, 0, n_w * 8, st));
         VPT_HIP(hipMemsetAsync(d_stats.p, 0, n_stats * sizeof(vpt_train_stats), st));
-        DBuf<vpt::TagL1Desc> d_l1desc;   // solver 5's
+        DBuf<vpt::TagL1Desc> d_l1desc;   // solvers 5 and 6
         DBuf<vpt::TagL1Group> d_groups;
         DBuf<uint32_t> d_gcols;
         DBuf<double> d_viol;
@@ -1099,8 +1103,9 @@ vpt_status solve_tags(vpt_trainer* t, double eps, double cost, int solver) {
             VPT_HIP(hipMemcpyAsync(d_groups.p, l1groups.data(), l1groups.size() * sizeof(vpt::TagL1Group), hipMemcpyHostToDevice, st));
             VPT_HIP(hipMemcpyAsync(d_gcols.p, gcols.data(), gcols.size() * 4, hipMemcpyHostToDevice, st));
             VPT_HIP(hipMemsetAsync(d_viol.p, 0, n_viol * 8, st));
-            VPT_HIP(vpt::train_tag_l1_solve(d_desc.p, d_l1desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, d_gcols.p,
-                                            d_groups.p, eps, cost, d_viol.p, d_w.p, d_stats.p, st));
+            VPT_HIP((l1lr ? vpt::train_tag_l1lr_solve : vpt::train_tag_l1_solve)(d_desc.p, d_l1desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p,
+                                                                                 t->b_crow.p, t->b_y.p, d_gcols.p, d_groups.p, eps, cost, d_viol.p, d_w.p,
+                                                                                 d_stats.p, st));
         } else {
             VPT_HIP(vpt::train_tag_solve(d_desc.p, uint32_t(descs.size()), t->b_rp.p, t->b_cols.p, t->b_cp.p, t->b_crow.p, t->b_y.p, eps, cost, solver, d_w.p,
                                          d_stats.p, st));
@@ -1343,11 +1348,13 @@ vpt_status vpt_trainer_create(const uint32_t* params_words, const uint8_t* dict_
     if (p.charw > 16) return fail_arg("charw: must be at most 16");
     if (p.typew > 16) return fail_arg("typew: must be at most 16");
     if (p.typew > p.charw) return fail_arg("typew: must not exceed charw (type weights use the char window)");
-    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR)) != 0)
-        return fail_arg((p.flags & VPT_TRAIN_L1R_LR) ? "flags: unknown bit beside VPT_TRAIN_L1R_LR (the others: VPT_TRAIN_TAGS, VPT_TRAIN_L1R, VPT_TRAIN_TAGS_L1R)"
+    if ((p.flags & ~uint32_t(VPT_TRAIN_TAGS | VPT_TRAIN_L1R | VPT_TRAIN_TAGS_L1R | VPT_TRAIN_L1R_LR | VPT_TRAIN_TAGS_L1R_LR)) != 0)
+        return fail_arg((p.flags & VPT_TRAIN_L1R_LR) ? "flags: unknown bit beside VPT_TRAIN_L1R_LR (the others: VPT_TRAIN_TAGS, VPT_TRAIN_L1R, VPT_TRAIN_TAGS_L1R, VPT_TRAIN_TAGS_L1R_LR)"
                                                      : "flags: must be 0 or VPT_TRAIN_TAGS, VPT_TRAIN_L1R or both");
     if ((p.flags & VPT_TRAIN_TAGS_L1R) && (p.flags & (VPT_TRAIN_TAGS | VPT_TRAIN_L1R)) != (VPT_TRAIN_TAGS | VPT_TRAIN_L1R))
         return fail_arg("flags: VPT_TRAIN_TAGS_L1R needs both VPT_TRAIN_TAGS and VPT_TRAIN_L1R");
+    if ((p.flags & VPT_TRAIN_TAGS_L1R_LR) && (p.flags & (VPT_TRAIN_TAGS | VPT_TRAIN_L1R_LR)) != (VPT_TRAIN_TAGS | VPT_TRAIN_L1R_LR))
+        return fail_arg("flags: VPT_TRAIN_TAGS_L1R_LR needs both VPT_TRAIN_TAGS and VPT_TRAIN_L1R_LR");
     if (n_dict_words && (p.dictn < 1 || p.dictn > 0x1FFFFF)) return fail_arg("dictn: must be at least 1 with a dictionary");
     std::unique_ptr<vpt_trainer> t(new (std::nothrow) vpt_trainer());
     if (!t) return fail(VPT_RUNTIME_ERROR, "out of host memory");
@@ -1468,7 +1475,7 @@ vpt_status vpt_trainer_train(void* th, const void* eps_cost, int solver, uint8_t
         return fail_arg(l1lr ? (l1r ? "solver: only 0, 2, 5 and 6 are implemented" : "solver: only 0, 2 and 6 are implemented")
                              : (l1r ? "solver: only 0, 2 and 5 are implemented" : "solver: only 0 and 2 are implemented"));
     if (solver == 5 && (t->prm.flags & VPT_TRAIN_TAGS) && !(t->prm.flags & VPT_TRAIN_TAGS_L1R)) return fail_arg("solver 5: tag models are trained with solvers 0 and 2 only");
-    if (solver == 6 && (t->prm.flags & VPT_TRAIN_TAGS)) return fail_arg("solver 6: tag models are trained with solvers 0, 2 and 5 only");
+    if (solver == 6 && (t->prm.flags & VPT_TRAIN_TAGS) && !(t->prm.flags & VPT_TRAIN_TAGS_L1R_LR)) return fail_arg("solver 6: tag models are trained with solvers 0, 2 and 5 only");
     if (!(eps > 0) || !(cost > 0)) return fail_arg("eps and cost: must be positive");
     VPT_HIP(hipSetDevice(t->device));
     t->trained = false;

@@ -591,4 +591,15 @@ hipError_t train_tag_l1_solve(const TagSolveDesc* descs, const TagL1Desc* l1desc
                               const uint32_t* cp, const uint32_t* crow, const uint32_t* y, const uint32_t* gcols, const TagL1Group* groups, double eps,
                               double cost, double* viol, double* w, vpt_train_stats* stats, hipStream_t st);
 
+// solver 6 for tag problems (kernels_train_tags_l1lr.hip): the in-kernel newGLMNET keeps in LDS what a sweep gathers or scatters per
+// nonzero and the feature vector it writes -- tau, D and xTd (rows each) and wpd (features + 1) -- so a problem fits iff
+// 3 rows + (features + 1) <= kTagL1LdsDoubles; w is the output itself, and Grad, Hdiag, xjneg_sum, the violations (features + 1 each)
+// and e (rows) are train_tag_l1lr_scratch doubles of global memory per problem, which start at its TagL1Desc's `viol`.  Groups and
+// descriptors are solver 5's.
+bool train_tag_l1lr_fits(uint64_t rows, uint64_t features);
+uint64_t train_tag_l1lr_scratch(uint64_t rows, uint64_t features);
+hipError_t train_tag_l1lr_solve(const TagSolveDesc* descs, const TagL1Desc* l1descs, uint32_t n_prob, const uint32_t* rp, const uint32_t* cols,
+                                const uint32_t* cp, const uint32_t* crow, const uint32_t* y, const uint32_t* gcols, const TagL1Group* groups, double eps,
+                                double cost, double* scratch, double* w, vpt_train_stats* stats, hipStream_t st);
+
 }  // namespace vpt

@@ -14,12 +14,13 @@ With --l1r (ours) the trainer is made with l1r=True and --solver 5 (L1-regularis
 coordinate descent over column groups on the device; most weights end at exactly 0, so the model is small.  With --l1r-tags (ours)
 beside --l1r and --train-tags, --solver 5 trains the tag models too, by the same coordinate descent.  With --l1r-lr (ours) the trainer
 is made with l1r_lr=True and --solver 6 (L1-regularised logistic regression) trains the boundary model by liblinear's newGLMNET on the
-device: a sparse model again, with the logistic loss.
+device: a sparse model again, with the logistic loss.  With --l1r-lr-tags (ours) beside --l1r-lr and --train-tags, --solver 6 trains the
+tag models too, by the same newGLMNET: sparse tag models whose --tag-scores are log-odds.
 
 Divergences: without --train-tags tag models are not trained, so a corpus or dictionary line that carries a tag is an error naming the
 file and line unless --ignore-tags (ours) drops the tags; only solvers 0 and 2 are implemented, and solver 5 only with --l1r (ours: without
 it --solver 5 is refused like the others; with it and --train-tags it is refused too unless --l1r-tags is given), and solver 6 only with
---l1r-lr (ours; refused together with --train-tags); --zstd-workers does not exist."""
+--l1r-lr (ours; refused together with --train-tags unless --l1r-lr-tags is given); --zstd-workers does not exist."""
 import argparse
 import sys
 
@@ -106,6 +107,7 @@ def main(argv=None) -> int:
     ap.add_argument("--l1r", action="store_true", help="Make the trainer accept --solver 5 (L1-regularised L2-loss SVC).")
     ap.add_argument("--l1r-tags", action="store_true", help="With --l1r and --train-tags: --solver 5 trains the tag models too.")
     ap.add_argument("--l1r-lr", action="store_true", help="Make the trainer accept --solver 6 (L1-regularised logistic regression).")
+    ap.add_argument("--l1r-lr-tags", action="store_true", help="With --l1r-lr and --train-tags: --solver 6 trains the tag models too.")
     args = ap.parse_args(argv)
     if not args.tok and not args.part:
         ap.error("one of --tok or --part is required")
@@ -113,6 +115,9 @@ def main(argv=None) -> int:
         ap.error("--train-tags and --ignore-tags exclude each other")
     if args.l1r_tags and not (args.l1r and args.train_tags):
         print("Error: --l1r-tags needs both --l1r and --train-tags", file=sys.stderr)
+        return 1
+    if args.l1r_lr_tags and not (args.l1r_lr and args.train_tags):
+        print("Error: --l1r-lr-tags needs both --l1r-lr and --train-tags", file=sys.stderr)
         return 1
     skip_tags = args.ignore_tags or args.train_tags   # either way a tag is no error
 
@@ -159,7 +164,8 @@ def main(argv=None) -> int:
 
         print("Extracting into features...", file=sys.stderr)
         trainer = api.Trainer(args.charw, args.charn, args.typew, args.typen, dictionary, args.dictn, ignore_tags=args.ignore_tags,
-                              train_tags=args.train_tags, tag_dictionary=tag_dictionary, l1r=args.l1r, l1r_tags=args.l1r_tags, l1r_lr=args.l1r_lr)
+                              train_tags=args.train_tags, tag_dictionary=tag_dictionary, l1r=args.l1r, l1r_tags=args.l1r_tags, l1r_lr=args.l1r_lr,
+                              l1r_lr_tags=args.l1r_lr_tags)
         for utf8, boff, labels, p in batches:
             if p is not None:
                 trainer.add_packed_tagged(utf8, boff, labels, p["n_tags"], p["tag_index"], p["span_offsets"], p["tag_bytes"],
