@@ -302,6 +302,114 @@ impl HipPredictor {
     }
 }
 
+/// A stop set for the tagged token stream (`vpt_tag_stop_create`): (slot, tag string) pairs.  A token is dropped when, for some pair, its slot's
+/// tag equals the pair's string -- a tag model's or, with `tagger`, a rule's; `None` never matches; a string in neither vocabulary matches
+/// nothing.  Immutable; borrows its predictor (and the tagger whose ids it resolved), which outlive it.
+pub struct TagStopFilter<'p> {
+    raw: *mut std::ffi::c_void,
+    predictor: &'p HipPredictor,
+}
+unsafe impl Send for TagStopFilter<'_> {}
+unsafe impl Sync for TagStopFilter<'_> {}
+
+impl<'p> TagStopFilter<'p> {
+    /// Errors name the entry: a slot that is not below the predictor's `n_tags`, a tag that holds a NUL; a tagger of another predictor.
+    pub fn new<'a, I>(predictor: &'p HipPredictor, pairs: I, tagger: Option<&'p PatternMatchTagger<'p>>) -> Result<Self>
+    where
+        I: IntoIterator<Item = (u32, &'a str)>,
+    {
+        if let Some(t) = tagger {
+            if !std::ptr::eq(t.predictor, predictor) {
+                return Err(HipError::InvalidArgument("InvalidArgumentError: tagger: does not belong to this predictor".to_string()));
+            }
+        }
+        let (mut slots, mut tags, mut tag_offsets) = (Vec::<u32>::new(), Vec::<u8>::new(), vec![0u64]);
+        for (slot, tag) in pairs {
+            slots.push(slot);
+            tags.extend_from_slice(tag.as_bytes());
+            tag_offsets.push(tags.len() as u64);
+        }
+        let n = slots.len();
+        // (no dangling pointer of an empty Vec is handed over)
+        slots.push(0);
+        tags.push(0);
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            ffi::vpt_tag_stop_create(predictor.raw, tagger.map_or(std::ptr::null(), |t| t.raw as *const std::ffi::c_void), slots.as_ptr(), tags.as_ptr(),
+                                     tag_offsets.as_ptr(), n, &mut raw)
+        })?;
+        Ok(Self { raw, predictor })
+    }
+}
+
+impl Drop for TagStopFilter<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::vpt_tag_stop_destroy(self.raw) }
+    }
+}
+
+/// What `HipPredictor::token_stream_tagged_batch` returns, over the KEPT tokens: document i owns entries `offsets[i] .. offsets[i + 1]`;
+/// `starts` / `ends` are a token's `offset_from` / `offset_to` from its document's first byte, `positions` its index in the document BEFORE
+/// filtering, `tags[token * n_tags + slot]` an id of `tag_strings()` (>= 0), -1 (`None`) or -(2 + id) (a rule tag of the tagger).
+pub struct TaggedTokens {
+    pub offsets: Vec<u64>,
+    pub starts: Vec<u32>,
+    pub ends: Vec<u32>,
+    pub positions: Vec<u32>,
+    pub tags: Vec<i32>,
+    pub n_tags: usize,
+}
+
+impl HipPredictor {
+    /// The predictor's tag vocabulary (`vpt_predictor_n_tag_strings` / `vpt_predictor_tag_string`): the distinct raw tag strings of its tag
+    /// models in order of first appearance over tag models, slots, candidates.  Empty without `predict_tags`.
+    pub fn tag_strings(&self) -> Result<Vec<String>> {
+        let mut n = 0u32;
+        check(unsafe { ffi::vpt_predictor_n_tag_strings(self.raw, &mut n) })?;
+        let mut out = Vec::with_capacity(n as usize);
+        for id in 0..n {
+            let (mut bytes, mut len) = (std::ptr::null::<u8>(), 0usize);
+            check(unsafe { ffi::vpt_predictor_tag_string(self.raw, id, &mut bytes, &mut len) })?;
+            let slice = if len == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(bytes, len) } };
+            out.push(String::from_utf8_lossy(slice).into_owned());
+        }
+        Ok(out)
+    }
+
+    /// `token_stream_batch` with every token's tags and, with `stop`, without the stopped tokens (`vpt_token_stream_tagged_batch`): one call,
+    /// everything behind the copy in on the device.  The predictor must have been made with `predict_tags`; `tagger` and `stop` for it.  The C
+    /// side trusts the sizes, so they are checked here.
+    pub fn token_stream_tagged_batch(&self, utf8: &[u8], boff: &[u64], wsconst_flags: u32, tagger: Option<&PatternMatchTagger<'_>>,
+                                     stop: Option<&TagStopFilter<'_>>) -> Result<TaggedTokens> {
+        let bad = |what: &str| Err(HipError::InvalidArgument(format!("InvalidArgumentError: {}", what)));
+        if boff.is_empty() { return bad("byte_offsets: n + 1 entries"); }
+        let n = boff.len() - 1;
+        if boff.windows(2).any(|w| w[1] < w[0]) { return bad("offsets: must not decrease"); }
+        if (utf8.len() as u64) < boff[n] { return bad("utf8: shorter than byte_offsets[n]"); }
+        if tagger.map_or(false, |t| !std::ptr::eq(t.predictor, self)) { return bad("tagger: does not belong to this predictor"); }
+        if stop.map_or(false, |s| !std::ptr::eq(s.predictor, self)) { return bad("stop: does not belong to this predictor"); }
+        let mut nt = 0u32;
+        check(unsafe { ffi::vpt_predictor_n_tags(self.raw, &mut nt) })?;
+        let n_tags = nt as usize;
+        let capacity = ((boff[n] - boff[0]) as usize).max(1);   // a token per char at most, a char per byte at most
+        let mut offsets = vec![0u64; n + 1];
+        let (mut starts, mut ends, mut positions) = (vec![0u32; capacity], vec![0u32; capacity], vec![0u32; capacity]);
+        let mut tags = vec![0i32; capacity * n_tags.max(1)];
+        check(unsafe {
+            ffi::vpt_token_stream_tagged_batch(self.raw, utf8.as_ptr(), boff.as_ptr(), n, wsconst_flags,
+                                               tagger.map_or(std::ptr::null(), |t| t.raw as *const std::ffi::c_void),
+                                               stop.map_or(std::ptr::null(), |s| s.raw as *const std::ffi::c_void), offsets.as_mut_ptr(),
+                                               starts.as_mut_ptr(), ends.as_mut_ptr(), positions.as_mut_ptr(), tags.as_mut_ptr(), capacity as u64)
+        })?;
+        let kept = offsets[n] as usize;
+        starts.truncate(kept);
+        ends.truncate(kept);
+        positions.truncate(kept);
+        tags.truncate(kept * n_tags);
+        Ok(TaggedTokens { offsets, starts, ends, positions, tags, n_tags })
+    }
+}
+
 /// One batch over the GPUs of a node: `preds[r]` scores the r-th character-balanced range of the sentences (no data-path collective).
 /// `boff` / `ooff`: the n + 1 byte / boundary offsets of the n sentences (`vpt_count_boundaries` makes the latter); `scores` and `labels` take
 /// `ooff[n]` entries.  The C side trusts these sizes, so they are checked here: a safe function must not let a short slice become a write past it.

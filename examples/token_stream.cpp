@@ -2,6 +2,11 @@
 //   g++ -O2 -std=c++17 -Iinclude -o token_stream examples/token_stream.cpp -Lvaporetto_amd/lib -lvaporetto_hip -Wl,-rpath,'$ORIGIN/vaporetto_amd/lib'
 //   ./token_stream model.bin [wsconst] < documents.txt       (one document per line; wsconst: chars of DRHTKOG, vaporetto_tantivy/src/lib.rs:69-86)
 // One line per token: doc <TAB> position <TAB> offset_from <TAB> offset_to <TAB> text   (byte offsets into the document, as tantivy's Token holds them)
+//   ./token_stream model.bin wsconst --tags [slot:tag ...] < documents.txt
+// With --tags (beyond the adapter): the predictor predicts tags, every line continues with position_length and one field per tag slot ("*": None),
+// and the tokens whose slot carries one of the listed tags are dropped -- position and position_length stay those before filtering.
+#include <cstdlib>
+#include <cstring>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -16,6 +21,25 @@ int main(int argc, char** argv) {
     std::ifstream f(argv[1], std::ios::binary);
     const std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     try {
+        if (argc > 3 && std::strcmp(argv[3], "--tags") == 0) {
+            vaporetto_hip::TagStopFilter::Pairs stop;
+            for (int a = 4; a < argc; ++a) {
+                const char* colon = std::strchr(argv[a], ':');
+                if (!colon) { std::fprintf(stderr, "a stop tag is slot:tag\n"); return 2; }
+                stop.emplace_back(uint32_t(std::strtoul(argv[a], nullptr, 10)), std::string(colon + 1));
+            }
+            vaporetto_hip::VaporettoTokenizer tagged(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argv[2], 0, true, {}, stop);
+            std::vector<std::string> docs;
+            for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
+            const auto streams = tagged.token_stream_batch(docs);
+            for (size_t d = 0; d < streams.size(); ++d)
+                for (const vaporetto_hip::Token& t : streams[d]) {
+                    std::printf("%zu\t%zu\t%zu\t%zu\t%s\t%zu", d, t.position, t.offset_from, t.offset_to, t.text.c_str(), t.position_length);
+                    for (const auto& tag : t.tags) std::printf("\t%s", tag ? tag->c_str() : "*");
+                    std::printf("\n");
+                }
+            return 0;
+        }
         vaporetto_hip::VaporettoTokenizer tokenizer(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argc > 2 ? argv[2] : "");
         std::vector<std::string> docs;
         for (std::string l; std::getline(std::cin, l);) docs.push_back(l);

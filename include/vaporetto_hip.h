@@ -458,6 +458,65 @@ vpt_status vpt_token_spans_batch(const vpt_predictor *p, const uint8_t *utf8, co
 vpt_status vpt_token_stream_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
                                   unsigned wsconst_flags, uint64_t *token_offsets_out, uint32_t *token_ends_out, uint64_t capacity);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The token spans with every token's tags                                     (an indexer's part-of-speech filter; no item of the adapter)
+ *
+ * The tag vocabulary: a predictor created with predict_tags != 0 holds the distinct RAW (unescaped) tag strings of its tag models, numbered in
+ *   order of first appearance over Model::tag_models, then slots, then candidates.  vpt_predictor_n_tag_strings: their number (0 without tag
+ *   models or without predict_tags); vpt_predictor_tag_string: the bytes of `id`, owned by the predictor (an id that is none: VPT_INVALID_ARGUMENT).
+ *   Built from the compiled tables, so vpt_predictor_load / _adopt_device / _clone_to_device give the same vocabulary, id for id: with
+ *   predict_tags and tag models every such call reads five small table sections back from the device once (synchronous copies).  A HIP
+ *   error there does not fail the creation -- every other call is what it was --; the calls of this section then return it (VPT_RUNTIME_ERROR).
+ * vpt_token_tags_batch_device: vpt_token_spans_batch_device plus
+ *   token_tags [capacity * n_tags]   n_tags int32 per token at token_tags[token * n_tags + slot], `token` its index in token_ends:
+ *                           >= 0 an id of the tag vocabulary; -1 None (a token without a tag model, an empty candidate list, a slot the model
+ *                           left None); -(2 + id) a rule tag of the pattern tagger set on the workspace (vpt_pattern_tagger_tag).
+ *   The tags are the RECORDS the vpt_fill_tags_batch_device call on THIS workspace left (the tagged writer's contract): call it first, for the same
+ *   batch and the same labels (else VPT_INVALID_ARGUMENT "call vpt_fill_tags_batch_device ..."); labels changed in between are reported at
+ *   vpt_batch_sync as offsets that do not match.  One launch (kernels_tokens.hip, the tagged instance), asynchronous; errors as for
+ *   vpt_token_spans_batch_device, and nothing is written past `capacity` tokens or capacity * n_tags tags.  A predictor whose model has no tag
+ *   models (n_tags == 0) writes what vpt_token_spans_batch_device writes and touches no tag entry; one created with predict_tags == 0 is
+ *   VPT_INVALID_ARGUMENT "this predictor is created with predict_tags = false". */
+vpt_status vpt_predictor_n_tag_strings(const vpt_predictor *p, uint32_t *n);
+vpt_status vpt_predictor_tag_string(const vpt_predictor *p, uint32_t id, const uint8_t **bytes, size_t *len);
+vpt_status vpt_token_tags_batch_device(const vpt_predictor *p, vpt_batch *b, const uint8_t *d_utf8, const uint64_t *d_byte_offsets,
+                                       const uint64_t *d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t *d_labels,
+                                       uint64_t *d_token_offsets, uint32_t *d_token_ends, int32_t *d_token_tags, uint64_t capacity,
+                                       void *hip_stream);
+
+/* The tag stop filter: the token stream without the tokens an indexer drops (particles, auxiliaries, symbols), positions kept.
+ *
+ * vpt_tag_stop_create: a stop set from n_entries (slot, tag string) pairs -- slots[e], tag_bytes[tag_offsets[e] .. tag_offsets[e + 1]).  A token
+ *   is STOPPED when, for some pair, its slot's tag string equals the pair's string, whether a tag model or a rule of `tagger` (or NULL) gave the
+ *   tag; None never matches; a string that neither the predictor's vocabulary nor the tagger's holds matches nothing and is no error.  The host
+ *   resolves the strings once into one bitmap per slot over the vocabulary ids (and one over the tagger's ids).  VPT_INVALID_ARGUMENT
+ *   "stop tags: ... (entry e)": a slot >= n_tags, a tag that contains NUL; "tagger: does not belong to this predictor".  The handle is immutable,
+ *   tied to its predictor (and to the tagger's ids), shareable between workspaces and host threads; vpt_tag_stop_destroy frees it.
+ * vpt_token_filter_batch_device: a pass of its own over a finished CSR (token_offsets [n + 1], token_ends, token_tags as
+ *   vpt_token_tags_batch_device writes them; capacity_in: what the two arrays hold, the tokens are token_offsets[n] or fewer) -- a keep-flag count
+ *   per block of vpt_token_filter_tile tokens, a prefix sum, a scatter; no sort, no atomics on what decides an order: two runs give identical
+ *   bytes.  Out, for the kept tokens: offsets_out [n + 1]; starts_out / ends_out (u32: offset_from, offset_to); positions_out (u32: the token's
+ *   index in its document BEFORE filtering -- what position increments need); tags_out.  A document may keep no token.  stop == NULL keeps
+ *   every token (starts: the entry before or 0; positions: the index).  Asynchronous; more kept tokens than `capacity` is reported at
+ *   vpt_batch_sync (VPT_INVALID_ARGUMENT "text_capacity: ...") and nothing is written past `capacity`, whatever the offsets say.
+ * vpt_token_stream_tagged_batch: vpt_token_stream_batch's steps (empty documents, the 2^32 limit, the NUL message and the wsconst parsing are
+ *   its) with, per chunk of whole documents, Sentence::fill_tags (on the normalised text, `tagger`'s rules behind it when not NULL) between the
+ *   label filters and the spans, the tagged span instance, and the filter pass (`stop` or NULL) -- everything after the copy in on the device.
+ *   The five arrays as above, `capacity` entries each (capacity * n_tags tags); one per text byte always suffices.  The result does not depend
+ *   on how the batch is cut into chunks.  A predictor with predict_tags == 0: VPT_INVALID_ARGUMENT. */
+vpt_status vpt_tag_stop_create(const vpt_predictor *p, const void *tagger, const uint32_t *slots, const uint8_t *tag_bytes,
+                               const uint64_t *tag_offsets, size_t n_entries, void **out);
+void vpt_tag_stop_destroy(void *stop);
+vpt_status vpt_token_filter_tile(uint32_t *n_tokens);
+vpt_status vpt_token_filter_batch_device(const vpt_predictor *p, vpt_batch *b, const void *stop, const uint64_t *d_token_offsets,
+                                         const uint32_t *d_token_ends, const int32_t *d_token_tags, size_t n_documents, uint64_t capacity_in,
+                                         uint64_t *d_offsets_out, uint32_t *d_starts_out, uint32_t *d_ends_out, uint32_t *d_positions_out,
+                                         int32_t *d_tags_out, uint64_t capacity, void *hip_stream);
+vpt_status vpt_token_stream_tagged_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                         unsigned wsconst_flags, const void *tagger, const void *stop, uint64_t *token_offsets_out,
+                                         uint32_t *token_starts_out, uint32_t *token_ends_out, uint32_t *token_positions_out,
+                                         int32_t *token_tags_out, uint64_t capacity);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

@@ -286,9 +286,25 @@ public:
         return out;
     }
 
+    // The tag vocabulary (vpt_predictor_n_tag_strings / vpt_predictor_tag_string): the distinct raw tag strings of the tag models in order of
+    // first appearance over tag models, slots, candidates -- what the ids >= 0 of the tagged token stream name.  Empty without predict_tags.
+    std::vector<std::string> tag_strings() const {
+        uint32_t n = 0;
+        detail::check(vpt_predictor_n_tag_strings(raw_->raw, &n));
+        std::vector<std::string> out;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint8_t* p = nullptr;
+            size_t len = 0;
+            detail::check(vpt_predictor_tag_string(raw_->raw, k, &p, &len));
+            out.emplace_back(reinterpret_cast<const char*>(p), len);
+        }
+        return out;
+    }
+
 private:
     friend class Sentence;
     friend class PatternMatchTagger;
+    friend class TagStopFilter;
     std::shared_ptr<detail::Shared> raw_;
     bool predict_tags_;
 };
@@ -338,6 +354,35 @@ private:
     void* raw_ = nullptr;
 };
 
+// A stop set for the tagged token stream (vpt_tag_stop_create): (slot, tag string) pairs -- a token is dropped when, for some pair, its slot's tag
+// equals the pair's string, a tag model's or (with `tagger`) a rule's; None never matches; a string in neither vocabulary matches nothing.
+// Tied to ONE predictor (and the tagger's ids); immutable.  Keeps the predictor's handle alive.
+class TagStopFilter {
+public:
+    using Pairs = std::vector<std::pair<uint32_t, std::string>>;
+    TagStopFilter(const Predictor& predictor, const Pairs& pairs, const PatternMatchTagger* tagger = nullptr) : predictor_(predictor.raw_) {
+        std::string tags;
+        std::vector<uint64_t> toff(1, 0);
+        std::vector<uint32_t> slots;
+        for (const auto& p : pairs) {
+            slots.push_back(p.first);
+            tags += p.second;
+            toff.push_back(tags.size());
+        }
+        slots.push_back(0);   // (no empty array's data() is handed over; std::string::data() is never null)
+        detail::check(vpt_tag_stop_create(predictor_->raw, tagger ? tagger->raw() : nullptr, slots.data(), reinterpret_cast<const uint8_t*>(tags.data()),
+                                          toff.data(), pairs.size(), &raw_));
+    }
+    ~TagStopFilter() { vpt_tag_stop_destroy(raw_); }
+    TagStopFilter(const TagStopFilter&) = delete;
+    TagStopFilter& operator=(const TagStopFilter&) = delete;
+    const void* raw() const { return raw_; }
+
+private:
+    std::shared_ptr<detail::Shared> predictor_;
+    void* raw_ = nullptr;
+};
+
 inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
     std::vector<std::string> out;
     if (lines.empty()) return out;
@@ -365,19 +410,31 @@ inline std::vector<std::string> Predictor::tokenize(const std::vector<std::strin
 // VaporettoTokenStream fills it (lib.rs:204-219): byte offsets into the caller's text.  A batch is ONE call (vpt_token_stream_batch: the text
 // goes to the device, the spans come back), G included: VPT_FLAG_CONCAT_GRAPHEMES runs last on the device, which is the adapter's result for any
 // place of G in the string.
+// Beyond the adapter (which predicts no tags): with predict_tags a Token carries `tags`, one entry per slot (nullopt: None) -- the tag models'
+// and, behind them, the rules' of `rules` (PatternMatchTagger) --, and the tokens of `stop_tags` ((slot, tag string) pairs, TagStopFilter) are
+// dropped: a kept token's `position` is then its index BEFORE filtering and `position_length` the count before filtering (what position
+// increments need).  ONE call per batch (vpt_token_stream_tagged_batch); under a stop filter a second, untagged one (vpt_token_stream_batch:
+// scoring and spans again, no tags) gives the counts before filtering.  Without predict_tags the class is the adapter's, token for token.
 struct Token {
     std::string text;
     size_t offset_from, offset_to, position, position_length;
+    std::vector<std::optional<std::string>> tags;
 };
 class VaporettoTokenizer {
 public:
-    VaporettoTokenizer(const Model& model, const std::string& wsconst, int device_id = 0) : predictor_(model, false, device_id) {
+    VaporettoTokenizer(const Model& model, const std::string& wsconst, int device_id = 0, bool predict_tags = false,
+                       const PatternMatchTagger::Rules& rules = {}, const TagStopFilter::Pairs& stop_tags = {})
+        : predictor_(model, predict_tags, device_id), tagged_(predict_tags) {
         for (char c : wsconst) {
             const char* at = std::char_traits<char>::find("DRHTKO", 6, c);
             if (c == 'G') flags_ |= VPT_FLAG_CONCAT_GRAPHEMES;
             else if (at) flags_ |= VPT_FLAG_WSCONST(unsigned(at - "DRHTKO") + 1);
             else throw VaporettoError(VaporettoError::InvalidArgument, "Could not parse a wsconst value");
         }
+        if (!predict_tags && (!rules.empty() || !stop_tags.empty()))
+            throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: rules / stop_tags: need predict_tags = true");
+        if (!rules.empty()) tagger_ = std::make_unique<PatternMatchTagger>(predictor_, rules);
+        if (!stop_tags.empty()) stop_ = std::make_unique<TagStopFilter>(predictor_, stop_tags, tagger_.get());
     }
     const Predictor& predictor() const { return predictor_; }
 
@@ -397,6 +454,35 @@ public:
         const uint8_t* utf8 = reinterpret_cast<const uint8_t*>(text.data());
         std::vector<uint64_t> toff(doc.size() + 1);
         std::vector<uint32_t> ends(text.size());
+        if (tagged_) {
+            uint32_t nt = 0;
+            detail::check(vpt_predictor_n_tags(predictor_.raw(), &nt));
+            std::vector<uint32_t> starts(text.size()), pos(text.size());
+            std::vector<int32_t> tags(text.size() * size_t(nt) + 1);
+            detail::check(vpt_token_stream_tagged_batch(predictor_.raw(), utf8, boff.data(), doc.size(), flags_, tagger_ ? tagger_->raw() : nullptr,
+                                                        stop_ ? stop_->raw() : nullptr, toff.data(), starts.data(), ends.data(), pos.data(), tags.data(),
+                                                        ends.size()));
+            std::vector<uint64_t> full(toff);   // the documents' tokens before filtering
+            if (stop_) {
+                std::vector<uint32_t> all_ends(text.size());
+                detail::check(vpt_token_stream_batch(predictor_.raw(), utf8, boff.data(), doc.size(), flags_, full.data(), all_ends.data(), all_ends.size()));
+            }
+            const std::vector<std::string> vocab = predictor_.tag_strings();
+            for (size_t k = 0; k < doc.size(); ++k) {
+                const std::string& t = texts[doc[k]];
+                for (size_t j = size_t(toff[k]); j < size_t(toff[k + 1]); ++j) {
+                    Token tok{t.substr(starts[j], ends[j] - starts[j]), starts[j], ends[j], pos[j], size_t(full[k + 1] - full[k]), {}};
+                    for (uint32_t q = 0; q < nt; ++q) {
+                        const int32_t v = tags[j * nt + q];
+                        if (v >= 0) tok.tags.emplace_back(vocab.at(size_t(v)));
+                        else if (v <= -2 && tagger_) tok.tags.emplace_back(tagger_->tag(uint32_t(-2 - v)));
+                        else tok.tags.emplace_back(std::nullopt);
+                    }
+                    out[doc[k]].push_back(std::move(tok));
+                }
+            }
+            return out;
+        }
         detail::check(vpt_token_stream_batch(predictor_.raw(), utf8, boff.data(), doc.size(), flags_, toff.data(), ends.data(), ends.size()));
         for (size_t k = 0; k < doc.size(); ++k) {
             const std::string& t = texts[doc[k]];
@@ -404,7 +490,7 @@ public:
             size_t from = 0;
             for (size_t j = 0; j < n; ++j) {
                 const size_t to = ends[size_t(toff[k]) + j];
-                out[doc[k]].push_back(Token{t.substr(from, to - from), from, to, j, n});
+                out[doc[k]].push_back(Token{t.substr(from, to - from), from, to, j, n, {}});
                 from = to;
             }
         }
@@ -415,6 +501,9 @@ public:
 private:
     Predictor predictor_;
     unsigned flags_ = 0;
+    bool tagged_ = false;
+    std::unique_ptr<PatternMatchTagger> tagger_;
+    std::unique_ptr<TagStopFilter> stop_;
 };
 
 inline void Sentence::fill_tags(const PatternMatchTagger* tagger) {

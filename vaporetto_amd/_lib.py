@@ -113,6 +113,14 @@ SIGNATURES = {
     "vpt_token_spans_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, C.c_uint64, _P]),
     "vpt_token_spans_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_uint64]),
     "vpt_token_stream_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, C.c_uint64]),
+    "vpt_predictor_n_tag_strings": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vpt_predictor_tag_string": (C.c_int, [_P, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vpt_token_tags_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, C.c_uint64, _P]),
+    "vpt_tag_stop_create": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.POINTER(_P)]),
+    "vpt_tag_stop_destroy": (None, [_P]),
+    "vpt_token_filter_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "vpt_token_filter_batch_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint64, _P]),
+    "vpt_token_stream_tagged_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),

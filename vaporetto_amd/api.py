@@ -716,6 +716,48 @@ class Predictor:
             _raise(st)
         return v.value
 
+    def tag_strings(self) -> List[str]:
+        """The predictor's tag vocabulary (vpt_predictor_n_tag_strings / vpt_predictor_tag_string): the distinct raw tag strings of its tag
+        models in order of first appearance over tag models, slots, candidates -- what the ids >= 0 of DeviceBatch.token_tags name.  Empty
+        without predict_tags or without tag models."""
+        L = _lib.load()
+        n = C.c_uint32()
+        st = L.vpt_predictor_n_tag_strings(self._h, C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        out = []
+        for k in range(n.value):
+            ptr, ln = C.c_void_p(), C.c_size_t()
+            st = L.vpt_predictor_tag_string(self._h, k, C.byref(ptr), C.byref(ln))
+            if st != _lib.VPT_OK:
+                _raise(st)
+            out.append(C.string_at(ptr.value, ln.value).decode("utf-8") if ln.value else "")
+        return out
+
+    def token_stream_tagged_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, wsconst: str = "", tagger: Optional["PatternMatchTagger"] = None,
+                                   stop: Optional["TagStopFilter"] = None):
+        """vpt_token_stream_tagged_batch: token_stream_packed with every token's tags and, with `stop`, without the stopped tokens ->
+        (token_offsets uint64 [n + 1], token_starts, token_ends, token_positions uint32, token_tags int32 [tokens, n_tags]): a token's
+        offset_from / offset_to, its index in its document BEFORE filtering, and per slot an id of tag_strings(), -1 (None) or
+        -(2 + id) (a rule tag of `tagger`)."""
+        flags = wsconst_flags(wsconst, allow_graphemes=True)
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S, nt = len(byte_offsets) - 1, self.n_tags() if self._predict_tags else 0
+        cap = max(int(byte_offsets[-1] - byte_offsets[0]), 1) if S else 1
+        toff = np.zeros(S + 1, np.uint64)
+        starts, ends, pos = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        tags = np.zeros(cap * max(nt, 1), np.int32)
+        src = utf8 if len(utf8) else np.zeros(1, np.uint8)
+        st = _lib.load().vpt_token_stream_tagged_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags,
+                                                       tagger.handle(self) if tagger is not None else None,
+                                                       stop.handle if stop is not None else None, toff.ctypes.data, starts.ctypes.data,
+                                                       ends.ctypes.data, pos.ctypes.data, tags.ctypes.data, cap)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        n = int(toff[S])
+        return toff, starts[:n].copy(), ends[:n].copy(), pos[:n].copy(), tags[:n * nt].reshape(n, nt).copy()
+
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                          fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
         """Predictor::predict_tags over a packed batch (predictor.rs:546-637).  labels: uint8 per boundary (0/1/2).
@@ -1296,6 +1338,26 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def token_tags(self, d_utf8: int, d_boff: int, d_ooff: int, n_documents: int, total_boundaries: int, d_labels: int,
+                   d_token_offsets: int, d_token_ends: int, d_token_tags: int, capacity: int, stream: int = 0) -> None:
+        """Device-resident token spans with n_tags int32 per token at d_token_tags (vpt_token_tags_batch_device): >= 0 an id of
+        Predictor.tag_strings(), -1 None, -(2 + id) a rule tag of the pattern tagger set on this workspace.  After fill_tags on this
+        workspace for the same batch and labels; enqueues and returns."""
+        st = _lib.load().vpt_token_tags_batch_device(self._p.handle, self._h, d_utf8, d_boff, d_ooff, n_documents, total_boundaries,
+                                                     d_labels or None, d_token_offsets, d_token_ends or None, d_token_tags or None, capacity, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def token_filter(self, stop, d_token_offsets: int, d_token_ends: int, d_token_tags: int, n_documents: int, capacity_in: int, d_offsets_out: int,
+                     d_starts_out: int, d_ends_out: int, d_positions_out: int, d_tags_out: int, capacity: int, stream: int = 0) -> None:
+        """Device-resident stop filter over a finished CSR (vpt_token_filter_batch_device; stop: a TagStopFilter or None); enqueues and returns."""
+        st = _lib.load().vpt_token_filter_batch_device(self._p.handle, self._h, stop.handle if stop is not None else None, d_token_offsets,
+                                                       d_token_ends or None, d_token_tags or None, n_documents, capacity_in, d_offsets_out,
+                                                       d_starts_out or None, d_ends_out or None, d_positions_out or None, d_tags_out or None,
+                                                       capacity, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def concat_graphemes(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, stream: int = 0) -> None:
         """Device-resident ConcatGraphemeClustersFilter on the labels at d_labels, in place (vpt_concat_graphemes_batch_device; the clusters of
         the KyteaFullwidthFilter image when set_flags / set_fullwidth say so); enqueues and returns."""
@@ -1552,22 +1614,75 @@ class TantivyToken:
         return "Token(text=%r, offset_from=%d, offset_to=%d, position=%d, position_length=%d)" % self._key()
 
 
+class TagStopFilter:
+    """vpt_tag_stop_create: a stop set for the tagged token stream from (slot, tag string) pairs -- a token is dropped when, for some pair, its
+    slot's tag equals the pair's string (a tag model's or, with `tagger`, a rule's; None never matches; an unknown string matches nothing).
+    Tied to `predictor` (and `tagger`); immutable."""
+
+    def __init__(self, predictor: "Predictor", pairs, tagger: Optional["PatternMatchTagger"] = None):
+        pairs = list(pairs)
+        slots = np.array([int(s) for s, _ in pairs] or [0], np.uint32)
+        raws = [t.encode("utf-8") for _, t in pairs]
+        tb, toff = pack_texts(raws)
+        tb = tb if len(tb) else np.zeros(1, np.uint8)
+        h = C.c_void_p()
+        self._keep = (predictor, tagger)
+        st = _lib.load().vpt_tag_stop_create(predictor.handle, tagger.handle(predictor) if tagger is not None else None, slots.ctypes.data,
+                                             tb.ctypes.data, toff.ctypes.data, len(pairs), C.byref(h))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None:
+            try:
+                _lib.load().vpt_tag_stop_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+class TaggedToken(TantivyToken):
+    """A token of the tagged stream: TantivyToken plus `tags`, a tuple of Optional[str] per slot.  Under a stop filter `position` is the index
+    before filtering and `position_length` the count before filtering."""
+
+    def __init__(self, text, offset_from, offset_to, position, position_length, tags):
+        super().__init__(text, offset_from, offset_to, position, position_length)
+        self.tags = tuple(tags)
+
+    def __eq__(self, other):
+        return isinstance(other, TaggedToken) and self._key() == other._key() and self.tags == other.tags
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + ", tags=%r)" % (self.tags,)
+
+
 class VaporettoTokenizer:
     """vaporetto_tantivy's VaporettoTokenizer (vaporetto_tantivy/src/lib.rs:62-229) over the C ABI: KyteaFullwidthFilter always, Predictor::new(model,
     false), SplitLinebreaksFilter first, then one filter per char of `wsconst` (D R H T K O: KyteaWsConstFilter; G: ConcatGraphemeClustersFilter).
     A batch is ONE call (vpt_token_stream_batch: only the text goes to the device, the spans come back), "G" included: the device applies it
     last, which is the adapter's result for any place of "G" in the string."""
 
-    def __init__(self, model: Model, wsconst: str = "", device: int = 0, _predictor: Optional[Predictor] = None):
+    def __init__(self, model: Model, wsconst: str = "", device: int = 0, _predictor: Optional[Predictor] = None, predict_tags: bool = False,
+                 tagger: Optional["PatternMatchTagger"] = None, stop_tags=None):
+        """predict_tags (beyond the adapter, which predicts none): the tokens are TaggedToken, with `tagger`'s rule tags behind the tag models'
+        and without the tokens of `stop_tags` ((slot, tag string) pairs).  Without it the class is the adapter's."""
         self._flags = wsconst_flags(wsconst, allow_graphemes=True)
         self._wsconst = wsconst
-        self._predictor = _predictor if _predictor is not None else Predictor(model, False, device=device)
+        self._predictor = _predictor if _predictor is not None else Predictor(model, bool(predict_tags), device=device)
+        if (tagger is not None or stop_tags is not None) and not predict_tags:
+            raise VaporettoError("InvalidArgumentError: tagger / stop_tags: need predict_tags = True")
+        self._tagged, self._tagger = bool(predict_tags), tagger
+        self._stop = TagStopFilter(self._predictor, stop_tags, tagger) if stop_tags is not None else None
 
     @classmethod
-    def deserialize(cls, blob, wsconst: str = "", device: int = 0) -> "VaporettoTokenizer":
-        """lib.rs:121-146, from Predictor.save_compiled's bytes (vpt_predictor_load)."""
+    def deserialize(cls, blob, wsconst: str = "", device: int = 0, predict_tags: bool = False, tagger: Optional["PatternMatchTagger"] = None,
+                    stop_tags=None) -> "VaporettoTokenizer":
+        """lib.rs:121-146, from Predictor.save_compiled's bytes (vpt_predictor_load); predict_tags needs bytes of a predictor made with it."""
         wsconst_flags(wsconst, allow_graphemes=True)
-        return cls(None, wsconst, device, _predictor=Predictor.load_compiled(blob, device=device))
+        return cls(None, wsconst, device, _predictor=Predictor.load_compiled(blob, device=device), predict_tags=predict_tags, tagger=tagger,
+                   stop_tags=stop_tags)
 
     @property
     def predictor(self) -> Predictor:
@@ -1583,6 +1698,8 @@ class VaporettoTokenizer:
     def token_stream_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         if not texts:
             return []
+        if self._tagged:
+            return self._tagged_batch(texts)
         utf8, boff, toff, ends = self.token_spans(texts)
         out = []
         for i, _ in enumerate(texts):
@@ -1593,6 +1710,25 @@ class VaporettoTokenizer:
                 toks.append(TantivyToken(raw[start:end].decode("utf-8"), start, end, k, len(e)))
                 start = end
             out.append(toks)
+        return out
+
+    def _tagged_batch(self, texts: Sequence[str]) -> List[List["TaggedToken"]]:
+        p = self._predictor
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        toff, starts, ends, pos, tags = p.token_stream_tagged_packed(utf8, boff, self._wsconst, self._tagger, self._stop)
+        # position_length is the count before filtering, which the filtered arrays no longer hold: under a stop filter the UNTAGGED stream
+        # (vpt_token_stream_batch: scoring and spans a second time, no fill_tags, no tags) gives it.  Callers that do not need
+        # position_length take token_stream_tagged_packed, which is one pass.
+        full = toff if self._stop is None else p.token_stream_packed(utf8, boff, self._wsconst)[0]
+        vocab = p.tag_strings()
+        rule = [self._tagger.tag(p, k) for k in range(self._tagger.n_tags(p))] if self._tagger is not None and tags.shape[1] else []
+        out = []
+        for i, _ in enumerate(texts):
+            raw = bytes(utf8[int(boff[i]):int(boff[i + 1])])
+            n = int(full[i + 1]) - int(full[i])
+            out.append([TaggedToken(raw[int(starts[k]):int(ends[k])].decode("utf-8"), int(starts[k]), int(ends[k]), int(pos[k]), n,
+                                    [None if v == -1 else vocab[v] if v >= 0 else rule[-2 - v] for v in (int(x) for x in tags[k])])
+                        for k in range(int(toff[i]), int(toff[i + 1]))])
         return out
 
     def token_stream(self, text: str) -> List[TantivyToken]:

@@ -85,6 +85,34 @@ void bind_predictor(vpt_predictor* p) {
         p->dtag.str_bytes = at(kSecTagStrBytes);
         p->dtag.n_models = m.n_tag_models; p->dtag.n_strings = m.n_tag_strings;
     }
+    if (m.has_tags && m.predict_tags && m.n_tags) {   // the tag vocabulary (tag_vocab.hpp), from the tables as they lie in the arena
+        std::vector<uint32_t> models(size_t(m.sec_bytes[kSecTagModels] / 4)), slots(size_t(m.sec_bytes[kSecTagSlots] / 4)),
+            slot_str(size_t(m.sec_bytes[kSecTagSlotStr] / 4)), str_off(size_t(m.sec_bytes[kSecTagStrOff] / 4));
+        std::vector<uint8_t> str_bytes(size_t(m.sec_bytes[kSecTagStrBytes]));
+        hipError_t e = hipSuccess;
+        auto down = [&](void* dst, const void* src, size_t n) { if (e == hipSuccess && n) e = hipMemcpy(dst, src, n, hipMemcpyDeviceToHost); };
+        down(models.data(), p->dtag.models, models.size() * 4); down(slots.data(), p->dtag.slots, slots.size() * 4);
+        down(slot_str.data(), p->dtag.slot_str, slot_str.size() * 4); down(str_off.data(), p->dtag.str_off, str_off.size() * 4);
+        down(str_bytes.data(), p->dtag.str_bytes, str_bytes.size());
+        const size_t n_models = std::min<size_t>(m.n_tag_models, models.size() / 12), n_str_off = std::min<size_t>(size_t(m.n_tag_strings) + 1, str_off.size());
+        if (e == hipSuccess) {
+            p->vocab = vpt::build_tag_vocab(models.data(), n_models, slots.data(), slots.size(), slot_str.data(), slot_str.size(), str_off.data(), n_str_off,
+                                            str_bytes.data(), str_bytes.size(), m.n_tags);
+            const size_t slot_bytes = (p->vocab.slot.size() * 4 + 255) & ~size_t(255), id_bytes = p->vocab.ids.size() * 4;
+            e = hipMalloc(reinterpret_cast<void**>(&p->vocab_mem), slot_bytes + id_bytes + 256);
+            if (e == hipSuccess) e = hipMemset(p->vocab_mem, 0, slot_bytes + id_bytes + 256);
+            if (e == hipSuccess && !p->vocab.slot.empty()) e = hipMemcpy(p->vocab_mem, p->vocab.slot.data(), p->vocab.slot.size() * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess && id_bytes) e = hipMemcpy(p->vocab_mem + slot_bytes, p->vocab.ids.data(), id_bytes, hipMemcpyHostToDevice);
+            p->d_vocab_slot = reinterpret_cast<const uint2*>(p->vocab_mem);
+            p->d_vocab_ids = reinterpret_cast<const uint32_t*>(p->vocab_mem + slot_bytes);
+        }
+        if (e != hipSuccess) {   // (the calls that need it say so; every other call is what it was)
+            p->vocab_error = std::string("HIP error while making the tag vocabulary: ") + hipGetErrorString(e);
+            p->vocab = vpt::TagVocab{};
+            (void)hipFree(p->vocab_mem);
+            p->vocab_mem = nullptr; p->d_vocab_slot = nullptr; p->d_vocab_ids = nullptr;
+        }
+    }
     p->info = m.info;
     p->bias = m.bias; p->pad = m.pad; p->type_kind = m.type_kind; p->type_window = m.type_window; p->chunks = m.chunks;
     p->tile_slots = 0;
@@ -246,7 +274,27 @@ void vpt_predictor_destroy(vpt_predictor* p) {
     (void)hipSetDevice(p->device);
     for (vpt_batch* b : p->pool) batch_release(b);
     (void)hipFree(p->arena);
+    (void)hipFree(p->vocab_mem);
     delete p;
+}
+
+// The tag vocabulary of a predictor with predict_tags (tag_vocab.hpp): what the ids of vpt_token_tags_batch_device name.
+vpt_status vpt_predictor_n_tag_strings(const vpt_predictor* p, uint32_t* n) {
+    if (!p || !n) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n = 0;
+    if (!p->vocab_error.empty()) return fail(VPT_RUNTIME_ERROR, p->vocab_error);
+    *n = p->vocab.size();
+    return VPT_OK;
+}
+
+vpt_status vpt_predictor_tag_string(const vpt_predictor* p, uint32_t id, const uint8_t** bytes, size_t* len) {
+    if (!p || !bytes || !len) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (!p->vocab_error.empty()) return fail(VPT_RUNTIME_ERROR, p->vocab_error);
+    if (id >= p->vocab.size()) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: id: no such tag string");
+    static const uint8_t none = 0;
+    *bytes = p->vocab.raw_bytes.empty() ? &none : p->vocab.raw_bytes.data() + p->vocab.raw_off[id];
+    *len = size_t(p->vocab.raw_off[id + 1] - p->vocab.raw_off[id]);
+    return VPT_OK;
 }
 
 // ---- the compiled form: PredictorMeta + the arena's bytes

@@ -515,6 +515,143 @@ vpt_status vpt_token_spans_batch_device(const vpt_predictor* p, vpt_batch* b, co
                         static_cast<hipStream_t>(hip_stream), nullptr, nullptr, nullptr);
 }
 
+// ... with every token's tags beside its end-point (token_spans_kernel<true>), from the records the fill_tags call on this workspace left for this
+// batch and these labels -- the tagged writer's contract; on the tagged writer's runs (whole multiples of fill_tags')
+namespace vptc {
+vpt_status token_tags_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                             const uint64_t* d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t* d_labels,
+                             uint64_t* d_token_offsets, uint32_t* d_token_ends, int32_t* d_token_tags, uint64_t capacity, hipStream_t stream,
+                             uint64_t* total_out) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (p->n_tags == 0 || n_documents == 0)   // no tag models: what the untagged call writes, and no tag entry is touched
+        return spans_device(p, b, d_utf8, d_byte_offsets, d_out_offsets, n_documents, total_boundaries, d_labels, d_token_offsets, d_token_ends, capacity,
+                            stream, total_out, nullptr, nullptr);
+    if (!p->vocab_error.empty()) return fail(VPT_RUNTIME_ERROR, p->vocab_error);
+    if (!d_token_offsets || !d_utf8 || !d_byte_offsets || !d_out_offsets || (total_boundaries && !d_labels) || (capacity && (!d_token_ends || !d_token_tags)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    vpt::SpanTags T{};
+    if (const vpt_status st = tag_records_for(b, n_documents, total_boundaries, true, &T.tag); st != VPT_OK) return st;
+    VPT_HIP(hipSetDevice(p->device));
+    T.token_tags = d_token_tags; T.vocab_slot = p->d_vocab_slot; T.vocab_ids = p->d_vocab_ids;
+    T.n_models = uint32_t(p->vocab.slot.size() / (2 * size_t(p->n_tags))); T.n_strings = uint32_t(p->vocab.ids.size());
+    vpt::SpanParams S{};
+    S.text = d_utf8; S.boff = d_byte_offsets; S.ooff = d_out_offsets; S.labels = d_labels; S.n_sent = n_documents;
+    S.total_boundaries = total_boundaries; S.token_ends = d_token_ends; S.token_offsets = d_token_offsets; S.capacity = capacity;
+    S.status = b->d_ctrl;
+    vpt::EmitFuse F{};
+    if (const vpt_status st = plan_runs(p, b, n_documents, total_boundaries, true, T.tag.run_sent, total_out, nullptr, nullptr, stream, &F); st != VPT_OK) return st;
+    VPT_HIP(vpt::launch_token_tags(S, T, F, stream));
+    b->last_stream = stream; b->pending = true; b->cps_text = nullptr;
+    return VPT_OK;
+}
+
+// The stop filter over a finished CSR (kernels_token_filter.hip): count, scan, scatter.  The number of tokens is on the device; capacity_in bounds it.
+vpt_status token_filter_device(const vpt_predictor* p, vpt_batch* b, const vpt_tag_stop* stop, const uint64_t* d_token_offsets,
+                               const uint32_t* d_token_ends, const int32_t* d_token_tags, size_t n_documents, uint64_t capacity_in,
+                               uint64_t* d_offsets_out, uint32_t* d_starts_out, uint32_t* d_ends_out, uint32_t* d_positions_out, int32_t* d_tags_out,
+                               uint64_t capacity, hipStream_t stream, uint64_t* total_out) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (stop && stop->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: stop: does not belong to this predictor");
+    if (!d_token_offsets || !d_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    const uint32_t nt = p->predict_tags ? p->n_tags : 0u;
+    if ((capacity_in && (!d_token_ends || (nt && !d_token_tags))) || (capacity && (!d_starts_out || !d_ends_out || !d_positions_out || (nt && !d_tags_out))))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    VPT_HIP(hipSetDevice(p->device));
+    vpt::TokenFilterParams P{};
+    P.token_offsets = d_token_offsets; P.token_ends = d_token_ends; P.token_tags = d_token_tags; P.n_docs = n_documents; P.capacity_in = capacity_in;
+    P.n_tags = nt;
+    if (stop && nt) {
+        P.model_bits = stop->model_bits; P.rule_bits = stop->rule_bits; P.model_words = stop->model_words; P.rule_words = stop->rule_words;
+        P.n_vocab = stop->n_vocab; P.n_rule = stop->n_rule;
+    }
+    P.out_offsets = d_offsets_out; P.out_starts = d_starts_out; P.out_ends = d_ends_out; P.out_positions = d_positions_out; P.out_tags = d_tags_out;
+    P.capacity_out = capacity;
+    P.n_blocks = std::max<uint64_t>((capacity_in + vpt::kTokenFilterBlock - 1) / vpt::kTokenFilterBlock, 1);
+    if (P.n_blocks > 0x7FFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the filter takes fewer than 2^39 tokens per call");
+    const size_t n_counts = size_t(P.n_blocks) + 1, n_part = vpt::scan_part_entries(P.n_blocks);
+    if (const vpt_status st = b->d_filt.grow(n_counts + n_part); st != VPT_OK) return st;
+    VPT_HIP(hipMemsetAsync(b->d_filt, 0, (n_counts + n_part) * sizeof(uint64_t), stream));
+    P.counts = b->d_filt; P.total_out = total_out; P.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_token_filter(P, b->d_filt + n_counts, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_token_tags_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                       const uint64_t* d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t* d_labels,
+                                       uint64_t* d_token_offsets, uint32_t* d_token_ends, int32_t* d_token_tags, uint64_t capacity, void* hip_stream) {
+    return token_tags_device(p, b, d_utf8, d_byte_offsets, d_out_offsets, n_documents, total_boundaries, d_labels, d_token_offsets, d_token_ends,
+                             d_token_tags, capacity, static_cast<hipStream_t>(hip_stream), nullptr);
+}
+
+vpt_status vpt_token_filter_batch_device(const vpt_predictor* p, vpt_batch* b, const void* stop, const uint64_t* d_token_offsets,
+                                         const uint32_t* d_token_ends, const int32_t* d_token_tags, size_t n_documents, uint64_t capacity_in,
+                                         uint64_t* d_offsets_out, uint32_t* d_starts_out, uint32_t* d_ends_out, uint32_t* d_positions_out,
+                                         int32_t* d_tags_out, uint64_t capacity, void* hip_stream) {
+    return token_filter_device(p, b, static_cast<const vpt_tag_stop*>(stop), d_token_offsets, d_token_ends, d_token_tags, n_documents, capacity_in,
+                               d_offsets_out, d_starts_out, d_ends_out, d_positions_out, d_tags_out, capacity, static_cast<hipStream_t>(hip_stream), nullptr);
+}
+
+vpt_status vpt_token_filter_tile(uint32_t* n_tokens) {
+    if (!n_tokens) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_tokens = vpt::kTokenFilterBlock;
+    return VPT_OK;
+}
+
+// ---- the tag stop set (tag_stop.hpp): (slot, tag string) pairs resolved into bitmaps over the predictor's vocabulary and the tagger's
+vpt_status vpt_tag_stop_create(const vpt_predictor* p, const void* tagger, const uint32_t* slots, const uint8_t* tag_bytes, const uint64_t* tag_offsets,
+                               size_t n_entries, void** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_entries && (!slots || !tag_offsets)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
+    if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (!p->vocab_error.empty()) return fail(VPT_RUNTIME_ERROR, p->vocab_error);
+    vpt::StopBitmap M, R;
+    static const uint8_t none = 0;
+    static const uint32_t zero_off = 0;
+    try {
+        M = vpt::build_stop_bitmap(slots, tag_bytes ? tag_bytes : &none, tag_offsets, n_entries, p->n_tags, p->vocab.raw_off.data(),
+                                   p->vocab.raw_bytes.empty() ? &none : p->vocab.raw_bytes.data(), p->vocab.size());
+        if (t) R = vpt::build_stop_bitmap(slots, tag_bytes ? tag_bytes : &none, tag_offsets, n_entries, p->n_tags, t->n_ids ? t->raw_off.data() : &zero_off,
+                                          t->raw_bytes.empty() ? &none : t->raw_bytes.data(), t->n_ids);
+    } catch (const vpt::StopError& e) {
+        return fail(VPT_INVALID_ARGUMENT, e.what());
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory while building the stop set");
+    }
+    VPT_HIP(hipSetDevice(p->device));
+    vpt_tag_stop* s = new (std::nothrow) vpt_tag_stop();
+    if (!s) return fail(VPT_RUNTIME_ERROR, "out of host memory");
+    s->pred = p; s->tagger = t; s->device = p->device;
+    s->model_words = M.words; s->rule_words = R.words; s->n_vocab = p->vocab.size(); s->n_rule = t ? t->n_ids : 0u;
+    const size_t mb = (M.bits.size() * 4 + 255) & ~size_t(255), rb = R.bits.size() * 4, total = mb + rb + 256;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->mem), total);
+    if (e == hipSuccess) e = hipMemset(s->mem, 0, total);
+    if (e == hipSuccess && !M.bits.empty()) e = hipMemcpy(s->mem, M.bits.data(), M.bits.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && rb) e = hipMemcpy(s->mem + mb, R.bits.data(), rb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(s->mem);
+        delete s;
+        return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    s->model_bits = M.bits.empty() ? nullptr : reinterpret_cast<const uint32_t*>(s->mem);
+    s->rule_bits = rb ? reinterpret_cast<const uint32_t*>(s->mem + mb) : nullptr;
+    *out = s;
+    return VPT_OK;
+}
+
+void vpt_tag_stop_destroy(void* stop) {
+    vpt_tag_stop* s = static_cast<vpt_tag_stop*>(stop);
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipFree(s->mem);
+    delete s;
+}
+
 vpt_status vpt_write_tokenized_batch_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                             const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                             const uint8_t* d_labels, uint8_t* d_text_out, uint64_t text_capacity,

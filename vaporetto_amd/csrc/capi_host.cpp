@@ -739,6 +739,139 @@ vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, c
     return VPT_OK;
 }
 
+// vpt_token_stream_batch with every token's tags and, when asked, without the tokens of a stop set: per chunk of whole documents (the tagged
+// pipeline's chunks and lanes, tokenize_host) copy in, char count, scoring with the adapter's filters, fill_tags (fullwidth flag only, the
+// tagger on the lane's workspace), the tagged span instance, the filter pass (without a stop set it keeps every token and writes the trivial
+// starts and positions) -- enqueued back to back, nothing on the way needs a number from the device.  A chunk's arrays start where an upper
+// bound puts them (a token per byte at most); the host collects the chunks in order and rebases their offsets: the filter runs per chunk, and
+// a chunk holds whole documents, so the arrays do not depend on the cut.
+vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                         unsigned wsconst_flags, const void* tagger, const void* stop, uint64_t* token_offsets_out,
+                                         uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out, int32_t* token_tags_out,
+                                         uint64_t capacity) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (wsconst_flags & ~(0x7Eu | unsigned(VPT_FLAG_CONCAT_GRAPHEMES))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
+    if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
+    const vpt_tag_stop* sp = static_cast<const vpt_tag_stop*>(stop);
+    if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
+    if (sp && sp->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: stop: does not belong to this predictor");
+    token_offsets_out[0] = 0;
+    if (n_documents == 0) return VPT_OK;
+    const uint32_t nt = p->n_tags;
+    if (!utf8 || !byte_offsets || (capacity && (!token_starts_out || !token_ends_out || !token_positions_out || (nt && !token_tags_out))))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    std::vector<uint64_t> docs;   // an empty document has no tokens and never reaches the device (vpt_token_stream_batch)
+    docs.reserve(n_documents + 1);
+    docs.push_back(byte_offsets[0]);
+    uint64_t max_bytes = 0;
+    for (size_t i = 0; i < n_documents; ++i) {
+        if (byte_offsets[i + 1] < byte_offsets[i]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+        if (byte_offsets[i + 1] == byte_offsets[i]) continue;
+        max_bytes = std::max<uint64_t>(max_bytes, byte_offsets[i + 1] - byte_offsets[i]);
+        docs.push_back(byte_offsets[i + 1]);
+    }
+    if (max_bytes > 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: a document must be shorter than 2^32 bytes");
+    const size_t n = docs.size() - 1;
+    if (n == 0) { std::fill(token_offsets_out, token_offsets_out + n_documents + 1, uint64_t(0)); return VPT_OK; }
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st = acquire(p, &w);
+    if (st != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    const unsigned flags = VPT_FLAG_KYTEA_FULLWIDTH | VPT_FLAG_SPLIT_LINEBREAKS | VPT_FLAG_LINEBREAKS_FIRST | wsconst_flags;
+    const uint64_t t0 = docs[0];
+    const size_t nbytes = size_t(docs[n] - t0);
+    constexpr int kMaxLanes = 4;
+    const uint64_t chunk_bytes = p->knobs.tokenize_chunk_bytes;
+    const size_t max_chunks = vptcut::tagged_max_chunks(n, nbytes, chunk_bytes);
+    Lanes lanes;
+    if ((st = lanes.init(p, b, int(std::min<size_t>(kMaxLanes, max_chunks)))) != VPT_OK) return st;
+    if (!b->s_out) VPT_HIP(hipStreamCreateWithFlags(&b->s_out, hipStreamNonBlocking));
+    if ((st = chunk_events(b, max_chunks)) != VPT_OK) return st;
+    const size_t slots = vptcut::offset_slots(n, max_chunks), tag_words = size_t(nbytes) * std::max<uint32_t>(nt, 1) + 16;
+    if ((st = b->d_text.grow(nbytes + 32)) != VPT_OK) return st;
+    if ((st = grow_pair(b->d_boff, b->d_ooff, slots)) != VPT_OK) return st;
+    if ((st = b->d_tlab.grow(nbytes + 1)) != VPT_OK) return st;
+    if ((st = b->d_toff.grow(slots)) != VPT_OK || (st = b->d_ftoff.grow(slots)) != VPT_OK) return st;
+    if ((st = b->d_tends.grow(nbytes + 16)) != VPT_OK || (st = b->d_ttags.grow(tag_words)) != VPT_OK) return st;
+    if ((st = b->d_fstarts.grow(nbytes + 16)) != VPT_OK || (st = b->d_fends.grow(nbytes + 16)) != VPT_OK || (st = b->d_fpos.grow(nbytes + 16)) != VPT_OK ||
+        (st = b->d_ftags.grow(tag_words)) != VPT_OK)
+        return st;
+    if ((st = pinned_words(b, vptcut::tagged_pinned_words(n, max_chunks))) != VPT_OK) return st;
+    uint64_t* const h_boff = b->h_off;
+    uint64_t* const h_total = b->h_off + n + 1;
+    for (size_t i = 0; i <= n; ++i) h_boff[i] = docs[i] - t0;
+    using Chunk = vptcut::TokenizeChunk;
+    std::vector<Chunk> chunks;
+    for (size_t i = 0; i < n;) {
+        const Chunk c = vptcut::tagged_chunk(h_boff, n, i, chunk_bytes);
+        i += c.n;
+        const size_t a = c.a, cn = c.n, k = chunks.size();
+        const uint64_t tb = c.tb, nby = c.nby;
+        vpt_batch* bb = lanes[k];
+        hipStream_t s = bb->own_stream;
+        bb->flags = flags;
+        bb->max_chars = 0;
+        uint64_t* d_boff_k = b->d_boff + a + k;
+        uint64_t* d_ooff_k = b->d_ooff + a + k;
+        uint8_t* d_labels_k = b->d_tlab + tb;
+        VPT_HIP(hipMemcpyAsync(b->d_text + tb, utf8 + t0 + tb, size_t(nby), hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(d_boff_k, h_boff + a, 8 * (cn + 1), hipMemcpyHostToDevice, s));
+        if ((st = count_boundaries_impl(p, bb, b->d_text, d_boff_k, cn, d_ooff_k, s, nby)) != VPT_OK) return st;
+        const uint64_t tb_bound = nby - cn;   // boundaries of the chunk, at most
+        if ((st = vpt_predict_batch_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, c.mb, nullptr, d_labels_k, s)) != VPT_OK) return st;
+        if (nt) {
+            bb->flags = flags & VPT_FLAG_KYTEA_FULLWIDTH;
+            bb->tagger = t;
+            if ((st = vpt_fill_tags_batch_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, nullptr, s)) != VPT_OK) return st;
+        }
+        st = token_tags_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, b->d_toff + a + k, b->d_tends + tb, b->d_ttags + tb * nt, nby, s, nullptr);
+        if (st != VPT_OK) return st;
+        h_total[k] = 0;
+        st = token_filter_device(p, bb, sp, b->d_toff + a + k, b->d_tends + tb, b->d_ttags + tb * nt, cn, nby, b->d_ftoff + a + k, b->d_fstarts + tb,
+                                 b->d_fends + tb, b->d_fpos + tb, b->d_ftags + tb * nt, nby, s, h_total + k);
+        if (st != VPT_OK) return st;
+        VPT_HIP(hipEventRecord(b->chunk_ev[k], s));
+        chunks.push_back(c);
+    }
+    // ---- collect: chunk by chunk, in order
+    std::vector<uint64_t> packed(n + 1, 0), base(chunks.size());
+    uint64_t at = 0;
+    bool incomplete = false;
+    st = VPT_OK;
+    for (size_t k = 0; k < chunks.size() && st == VPT_OK; ++k) {
+        const Chunk& c = chunks[k];
+        VPT_HIP(hipEventSynchronize(b->chunk_ev[k]));
+        const uint64_t total = h_total[k];
+        if (total > c.nby) { incomplete = true; break; }   // the device found the inputs inconsistent and says so below
+        if (total > capacity || at > capacity - total) { st = fail(VPT_INVALID_ARGUMENT, kTokensTooSmall); break; }
+        base[k] = at;
+        if (total) {
+            VPT_HIP(hipMemcpyAsync(token_starts_out + at, b->d_fstarts + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
+            VPT_HIP(hipMemcpyAsync(token_ends_out + at, b->d_fends + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
+            VPT_HIP(hipMemcpyAsync(token_positions_out + at, b->d_fpos + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
+            if (nt) VPT_HIP(hipMemcpyAsync(token_tags_out + at * nt, b->d_ftags + c.tb * nt, 4 * size_t(total) * nt, hipMemcpyDeviceToHost, b->s_out));
+        }
+        VPT_HIP(hipMemcpyAsync(packed.data() + c.a + 1, b->d_ftoff + c.a + k + 1, 8 * c.n, hipMemcpyDeviceToHost, b->s_out));
+        at += total;
+    }
+    VPT_HIP(hipStreamSynchronize(b->s_out));
+    st = lanes.verdict(st);
+    if (st != VPT_OK) return st;
+    if (incomplete) return fail(VPT_RUNTIME_ERROR, "vpt_token_stream_tagged_batch: a chunk's output size is out of range");
+    for (size_t k = 1; k < chunks.size(); ++k)
+        for (size_t j = 1; j <= chunks[k].n; ++j) packed[chunks[k].a + j] += base[k];
+    size_t k = 0;
+    for (size_t i = 0; i < n_documents; ++i) {
+        token_offsets_out[i] = packed[k];
+        if (byte_offsets[i + 1] != byte_offsets[i]) ++k;
+    }
+    token_offsets_out[n_documents] = packed[n];
+    return VPT_OK;
+}
+
 // ---- pinned host memory for callers that want the PCIe link at full rate
 vpt_status vpt_host_alloc(size_t bytes, void** out) {
     if (!out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out: must not be NULL");

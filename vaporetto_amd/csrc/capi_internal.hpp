@@ -21,6 +21,8 @@
 #include "model.hpp"
 #include "pattern_tagger.hpp"
 #include "tables.hpp"
+#include "tag_stop.hpp"
+#include "tag_vocab.hpp"
 
 extern thread_local std::string vpt_g_last_error;   // (capi.cpp) the calling thread's message: vpt_last_error
 
@@ -263,6 +265,17 @@ struct vpt_pattern_tagger {
     std::vector<uint8_t> raw_bytes;
 };
 
+// A tag stop set on the predictor's device (tag_stop.hpp; kernels_token_filter.hip): one bitmap per slot over the predictor's vocabulary ids and,
+// when it was made with a tagger, one over the tagger's ids.  Immutable, tied to its predictor, shared by workspaces and host threads.
+struct vpt_tag_stop {
+    const vpt_predictor* pred = nullptr;
+    const vpt_pattern_tagger* tagger = nullptr;
+    int device = 0;
+    unsigned char* mem = nullptr;
+    const uint32_t *model_bits = nullptr, *rule_bits = nullptr;
+    uint32_t model_words = 0, rule_words = 0, n_vocab = 0, n_rule = 0;
+};
+
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
 struct DevBuf {
@@ -335,6 +348,10 @@ struct vpt_batch {
     DevBuf<uint8_t> d_tlab;                                         // vpt_tokenize_batch: the labels of the whole batch (no scores are kept)
     DevBuf<uint64_t> d_toff;
     DevBuf<uint32_t> d_tends;                                       // vpt_token_spans_batch / vpt_token_stream_batch: the tokens' end-points
+    // vpt_token_stream_tagged_batch: the unfiltered tags beside d_tends, the filter's five arrays, and its counts + scan state (vpt_token_filter_batch_device)
+    DevBuf<int32_t> d_ttags, d_ftags;
+    DevBuf<uint32_t> d_fstarts, d_fends, d_fpos;
+    DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -418,6 +435,14 @@ struct vpt_predictor {
     mutable std::mutex pool_mu;
     mutable std::vector<vpt_batch*> pool;  // idle workspaces for the host-buffer entry points
     mutable std::atomic<int64_t> max_tag_listing{-1};  // vpt_predictor_max_tag_listing: a constant of the tables, computed by the first call
+    // The tag vocabulary (bind_predictor, from the tables the predictor holds; only with predict_tags and tag models): the distinct raw tag strings
+    // in order of first appearance over tag models, slots, candidates -- vpt_predictor_tag_string -- and, on the device in one allocation of its
+    // own, what token_spans_kernel<true> turns a record's candidate into an id with (SpanTags, kernels.hpp).
+    vpt::TagVocab vocab;
+    std::string vocab_error;           // why there is none although there should be one (a HIP error while it was made)
+    unsigned char* vocab_mem = nullptr;
+    const uint2* d_vocab_slot = nullptr;
+    const uint32_t* d_vocab_ids = nullptr;
 };
 
 namespace {
@@ -632,6 +657,16 @@ vpt_status spans_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_u
                         const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries, const uint8_t* d_labels,
                         uint64_t* d_token_offsets, uint32_t* d_token_ends, uint64_t capacity, hipStream_t stream, uint64_t* total_out,
                         const uint64_t* chain_in, uint64_t* chain_out);
+// ... with the tokens' tags (vpt_token_tags_batch_device), and the stop filter behind them (vpt_token_filter_batch_device; stop: or nullptr --
+// every token is kept); total_out: an optional device-writable host word for the number of tokens written
+vpt_status token_tags_device(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                             const uint64_t* d_out_offsets, size_t n_documents, uint64_t total_boundaries, const uint8_t* d_labels,
+                             uint64_t* d_token_offsets, uint32_t* d_token_ends, int32_t* d_token_tags, uint64_t capacity, hipStream_t stream,
+                             uint64_t* total_out);
+vpt_status token_filter_device(const vpt_predictor* p, vpt_batch* b, const vpt_tag_stop* stop, const uint64_t* d_token_offsets,
+                               const uint32_t* d_token_ends, const int32_t* d_token_tags, size_t n_documents, uint64_t capacity_in,
+                               uint64_t* d_offsets_out, uint32_t* d_starts_out, uint32_t* d_ends_out, uint32_t* d_positions_out, int32_t* d_tags_out,
+                               uint64_t capacity, hipStream_t stream, uint64_t* total_out);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

@@ -228,6 +228,40 @@ struct SpanParams {
     uint32_t* status;
 };
 hipError_t launch_token_spans(const SpanParams& P, const EmitFuse& F, hipStream_t stream);
+// ... with every token's tags (token_spans_kernel<true>): n_tags int32 per token at token_tags[token * n_tags + slot] -- >= 0 an id of the
+// predictor's tag vocabulary, -1 None (no record, an empty record, a slot left None), -(2 + id) a rule tag of the pattern tagger, as in the records.
+// The records are those the fill_tags call on the workspace left for the same batch and labels (a slice per run, through tag_records.h).
+struct SpanTags {
+    TagRecordsView tag;
+    int32_t* token_tags;          // [capacity * tag.n_tags]
+    const uint2* vocab_slot;      // [n_models * tag.n_tags] {the slot's first string (HostTagTables::slot_str), its candidates}
+    const uint32_t* vocab_ids;    // [n_strings] candidate string -> vocabulary id
+    uint32_t n_models, n_strings;
+};
+hipError_t launch_token_tags(const SpanParams& P, const SpanTags& T, const EmitFuse& F, hipStream_t stream);
+// The tag stop filter behind them (kernels_token_filter.hip): the kept tokens of the CSR, with starts and positions.  A count per workgroup of
+// kTokenFilterBlock tokens, the chained scan, a scatter.  model_bits / rule_bits: one bitmap per slot over the predictor's vocabulary ids / the
+// tagger's ids (nullptr: nothing of that kind is stopped; both nullptr: every token is kept).
+constexpr uint32_t kTokenFilterBlock = 256;   // tokens a workgroup takes (vpt_token_filter_tile)
+struct TokenFilterParams {
+    const uint64_t* token_offsets;  // [n_docs + 1]
+    const uint32_t* token_ends;     // [capacity_in]
+    const int32_t* token_tags;      // [capacity_in * n_tags]
+    uint64_t n_docs, capacity_in;
+    uint32_t n_tags;
+    const uint32_t *model_bits, *rule_bits;   // [n_tags * model_words], [n_tags * rule_words]
+    uint32_t model_words, rule_words, n_vocab, n_rule;
+    uint64_t* out_offsets;          // [n_docs + 1]
+    uint32_t *out_starts, *out_ends, *out_positions;   // [capacity_out]
+    int32_t* out_tags;              // [capacity_out * n_tags]
+    uint64_t capacity_out;
+    uint64_t* counts;               // workspace [n_blocks + 1], zero in front of the launches
+    uint64_t n_blocks;              // ceil(bound of the tokens / kTokenFilterBlock), at least 1
+    uint64_t* total_out;            // optional device-writable host address: the kept tokens
+    uint32_t* status;
+};
+// scan_part: scan_part_entries(n_blocks) zero words
+hipError_t launch_token_filter(const TokenFilterParams& P, uint64_t* scan_part, hipStream_t stream);
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
