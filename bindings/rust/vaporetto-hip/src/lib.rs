@@ -348,6 +348,65 @@ impl Drop for TagStopFilter<'_> {
     }
 }
 
+/// A vocabulary for the token stream's ids (`vpt_vocab_create`): entry k of `surfaces` gets id k, a token that is no entry `unk_id`.  Tied to
+/// ONE predictor (it borrows it); immutable.  An empty surface, a NUL and a repeated surface are errors that name the entry.
+pub struct Vocabulary<'p> {
+    raw: *mut std::ffi::c_void,
+    predictor: &'p HipPredictor,
+    pub unk_id: i32,
+}
+unsafe impl Send for Vocabulary<'_> {}
+unsafe impl Sync for Vocabulary<'_> {}
+
+impl<'p> Vocabulary<'p> {
+    pub fn new<'a, I>(predictor: &'p HipPredictor, surfaces: I, unk_id: i32) -> Result<Self>
+    where
+        I: IntoIterator<Item = &'a str>,
+    {
+        let (mut bytes, mut offsets) = (Vec::<u8>::new(), vec![0u64]);
+        for s in surfaces {
+            bytes.extend_from_slice(s.as_bytes());
+            offsets.push(bytes.len() as u64);
+        }
+        let n = offsets.len() - 1;
+        bytes.push(0);   // (no dangling pointer of an empty Vec is handed over)
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ffi::vpt_vocab_create(predictor.raw, bytes.as_ptr(), offsets.as_ptr(), n, unk_id, &mut raw) })?;
+        Ok(Self { raw, predictor, unk_id })
+    }
+
+    /// The surface of `id` (`vpt_vocab_surface`).
+    pub fn surface(&self, id: u32) -> Result<String> {
+        let (mut bytes, mut len) = (std::ptr::null::<u8>(), 0usize);
+        check(unsafe { ffi::vpt_vocab_surface(self.raw as *const std::ffi::c_void, id, &mut bytes, &mut len) })?;
+        let slice = if len == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(bytes, len) } };
+        Ok(String::from_utf8_lossy(slice).into_owned())
+    }
+
+    /// (token_offsets [n + 1], ids) of a packed batch of documents through the untagged stream's steps (`vpt_token_stream_ids_batch`):
+    /// `normalize` looks the KyteaFullwidthFilter image of a token up, else the caller's bytes.
+    pub fn encode_batch(&self, utf8: &[u8], byte_offsets: &[u64], wsconst_flags: u32, normalize: bool) -> Result<(Vec<u64>, Vec<i32>)> {
+        let n = byte_offsets.len().saturating_sub(1);
+        let cap = utf8.len() + 1;
+        let mut offsets = vec![0u64; n + 1];
+        let (mut starts, mut ends, mut positions, mut ids) = (vec![0u32; cap], vec![0u32; cap], vec![0u32; cap], vec![0i32; cap]);
+        let text = if utf8.is_empty() { &[0u8][..] } else { utf8 };
+        check(unsafe {
+            ffi::vpt_token_stream_ids_batch(self.predictor.raw, text.as_ptr(), byte_offsets.as_ptr(), n, wsconst_flags, std::ptr::null(), std::ptr::null(),
+                                            self.raw as *const std::ffi::c_void, if normalize { 1 } else { 0 }, offsets.as_mut_ptr(), starts.as_mut_ptr(),
+                                            ends.as_mut_ptr(), positions.as_mut_ptr(), std::ptr::null_mut(), ids.as_mut_ptr(), cap as u64)
+        })?;
+        ids.truncate(offsets[n] as usize);
+        Ok((offsets, ids))
+    }
+}
+
+impl Drop for Vocabulary<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::vpt_vocab_destroy(self.raw) }
+    }
+}
+
 /// What `HipPredictor::token_stream_tagged_batch` returns, over the KEPT tokens: document i owns entries `offsets[i] .. offsets[i + 1]`;
 /// `starts` / `ends` are a token's `offset_from` / `offset_to` from its document's first byte, `positions` its index in the document BEFORE
 /// filtering, `tags[token * n_tags + slot]` an id of `tag_strings()` (>= 0), -1 (`None`) or -(2 + id) (a rule tag of the tagger).

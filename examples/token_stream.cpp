@@ -5,6 +5,9 @@
 //   ./token_stream model.bin wsconst --tags [slot:tag ...] < documents.txt
 // With --tags (beyond the adapter): the predictor predicts tags, every line continues with position_length and one field per tag slot ("*": None),
 // and the tokens whose slot carries one of the listed tags are dropped -- position and position_length stay those before filtering.
+//   ./token_stream model.bin wsconst --vocab vocab.txt < documents.txt
+// With --vocab (beyond the adapter): vocab.txt holds one surface per line, line k is id k; one line per token: doc <TAB> index <TAB> id, the id of
+// the token's surface (of the text as it was scored: through KyteaFullwidthFilter) or -1 -- looked up on the device, no token text comes back.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -38,6 +41,20 @@ int main(int argc, char** argv) {
                     for (const auto& tag : t.tags) std::printf("\t%s", tag ? tag->c_str() : "*");
                     std::printf("\n");
                 }
+            return 0;
+        }
+        if (argc > 4 && std::strcmp(argv[3], "--vocab") == 0) {
+            std::ifstream vf(argv[4]);
+            std::vector<std::string> surfaces;
+            for (std::string l; std::getline(vf, l);) surfaces.push_back(l);
+            vaporetto_hip::VaporettoTokenizer plain(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argv[2]);
+            const vaporetto_hip::Vocabulary vocab(plain.predictor(), surfaces);
+            std::vector<std::string> docs;
+            for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
+            const auto enc = plain.encode(docs, vocab);
+            for (size_t d = 0; d < docs.size(); ++d)
+                for (uint64_t k = enc.first[d]; k < enc.first[d + 1]; ++k)
+                    std::printf("%zu\t%zu\t%d\n", d, size_t(k - enc.first[d]), int(enc.second[size_t(k)]));
             return 0;
         }
         vaporetto_hip::VaporettoTokenizer tokenizer(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argc > 2 ? argv[2] : "");

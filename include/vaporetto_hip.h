@@ -517,6 +517,48 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor *p, const uint8_t *
                                          uint32_t *token_starts_out, uint32_t *token_ends_out, uint32_t *token_positions_out,
                                          int32_t *token_tags_out, uint64_t capacity);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Vocabulary ids in the token stream                  (no item of the adapter: what the consumer of its Token::text, vaporetto_tantivy/src/lib.rs:204-219,
+ *                                                      does with a term dictionary or a model's vocabulary -- here without the strings leaving the device)
+ *
+ * vpt_vocab_create: a vocabulary of n_entries surfaces -- entry k is surfaces[offsets[k] .. offsets[k + 1]) and gets id k; unk_id (any int32) is
+ *   the id of a token that is no entry.  The host builds a hashed table laid out like the pattern tagger's (open addressing, 16-byte slots {id + 1,
+ *   chars, fingerprint, first code point}, load factor in (1/4, 1/2], the surfaces' code points back to back) and puts it on the predictor's device.
+ *   Up to 2^24 entries.  VPT_INVALID_ARGUMENT "InvalidArgumentError: vocab: <reason> (entry k)" for the first failing entry: not valid UTF-8, an
+ *   empty surface, a NUL, a surface an earlier entry has (an id names one string: no last-wins here).  The handle is immutable, tied to its
+ *   predictor's device, shareable between workspaces and host threads; vpt_vocab_destroy frees it.
+ * vpt_vocab_info: keys, slots and the longest surface in chars; vpt_vocab_surface: the bytes of `id`, owned by the handle (an id that is none:
+ *   VPT_INVALID_ARGUMENT); vpt_vocab_tile: the tokens a workgroup of the id pass takes (the tests place tokens across its edges).
+ * vpt_token_ids_batch_device: a pass of its own over a FINISHED span CSR (one launch, kernels_vocab.hip), asynchronous on hip_stream, errors at
+ *   vpt_batch_sync.  d_token_offsets [n + 1] and d_token_ends as vpt_token_spans_batch_device / vpt_token_tags_batch_device write them with
+ *   d_token_starts == NULL (a token starts where the one before it in its document ends, or at 0), or d_offsets_out / d_starts_out / d_ends_out of
+ *   vpt_token_filter_batch_device (a document may own no token).  capacity_in: what the arrays hold; the tokens are token_offsets[n].
+ *   d_token_ids [capacity_in]: per token the id of its surface, or unk_id.  The surface is the token's bytes IN THE CALLER'S TEXT; with
+ *   flags == VPT_FLAG_KYTEA_FULLWIDTH it is the KyteaFullwidthFilter image of those chars -- the text as it was scored, the convention of the rule
+ *   surfaces of vpt_pattern_tagger_create.  The vocabulary's surfaces are taken as they are.  Any other flag bit: VPT_INVALID_ARGUMENT.  A token of
+ *   more bytes than 4 * max_surface_chars is unk_id and its surface is not read.  No atomics on anything that decides a value: two runs give
+ *   identical bytes.  Whatever the device arrays hold, nothing is read outside [byte_offsets[0], byte_offsets[n]) of the text and nothing is written
+ *   outside d_token_ids[0 .. capacity_in); token_offsets that decrease or exceed capacity_in, a span with start > end or end past its document, and
+ *   a start or an end inside a char are VPT_INVALID_ARGUMENT at the sync (the ids of such tokens are unspecified).
+ * vpt_token_stream_ids_batch: host buffers in, the stream with ids out.  With tagger == stop == token_tags_out == NULL: vpt_token_stream_batch's
+ *   steps (starts and positions are written all the same); otherwise vpt_token_stream_tagged_batch's, which need predict_tags.  The id pass runs
+ *   last, on every chunk's finished CSR, on the device; vocab_flags as `flags` above.  token_ids_out [capacity].  The result does not depend on how
+ *   the batch is cut into chunks. */
+vpt_status vpt_vocab_create(const vpt_predictor *p, const uint8_t *surfaces, const uint64_t *offsets, size_t n_entries, int32_t unk_id,
+                            void **out);
+void vpt_vocab_destroy(void *vocab);
+vpt_status vpt_vocab_info(const void *vocab, uint32_t *n_keys, uint32_t *n_slots, uint32_t *max_surface_chars);
+vpt_status vpt_vocab_surface(const void *vocab, uint32_t id, const uint8_t **bytes, size_t *len);
+vpt_status vpt_vocab_tile(uint32_t *n_tokens);
+vpt_status vpt_token_ids_batch_device(const vpt_predictor *p, vpt_batch *b, const void *vocab, const uint8_t *d_utf8,
+                                      const uint64_t *d_byte_offsets, size_t n_documents, const uint64_t *d_token_offsets,
+                                      const uint32_t *d_token_starts, const uint32_t *d_token_ends, uint64_t capacity_in, unsigned flags,
+                                      int32_t *d_token_ids, void *hip_stream);
+vpt_status vpt_token_stream_ids_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                      unsigned wsconst_flags, const void *tagger, const void *stop, const void *vocab, unsigned vocab_flags,
+                                      uint64_t *token_offsets_out, uint32_t *token_starts_out, uint32_t *token_ends_out,
+                                      uint32_t *token_positions_out, int32_t *token_tags_out, int32_t *token_ids_out, uint64_t capacity);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

@@ -305,6 +305,7 @@ private:
     friend class Sentence;
     friend class PatternMatchTagger;
     friend class TagStopFilter;
+    friend class Vocabulary;
     std::shared_ptr<detail::Shared> raw_;
     bool predict_tags_;
 };
@@ -381,6 +382,35 @@ public:
 private:
     std::shared_ptr<detail::Shared> predictor_;
     void* raw_ = nullptr;
+};
+
+// A vocabulary for the token stream's ids (vpt_vocab_create): entry k of `surfaces` gets id k, a token that is no entry unk_id.  An empty surface,
+// a NUL, invalid UTF-8 and a repeated surface throw, naming the entry.  Tied to ONE predictor; immutable.  Keeps the predictor's handle alive.
+class Vocabulary {
+public:
+    Vocabulary(const Predictor& predictor, const std::vector<std::string>& surfaces, int32_t unk_id = -1) : predictor_(predictor.raw_), unk_id_(unk_id) {
+        std::string bytes;
+        std::vector<uint64_t> off(1, 0);
+        for (const std::string& s : surfaces) { bytes += s; off.push_back(bytes.size()); }
+        detail::check(vpt_vocab_create(predictor_->raw, reinterpret_cast<const uint8_t*>(bytes.data()), off.data(), surfaces.size(), unk_id, &raw_));
+    }
+    ~Vocabulary() { vpt_vocab_destroy(raw_); }
+    Vocabulary(const Vocabulary&) = delete;
+    Vocabulary& operator=(const Vocabulary&) = delete;
+    const void* raw() const { return raw_; }
+    int32_t unk_id() const { return unk_id_; }
+    size_t size() const { uint32_t n = 0; detail::check(vpt_vocab_info(raw_, &n, nullptr, nullptr)); return n; }
+    std::string surface(uint32_t id) const {
+        const uint8_t* b = nullptr;
+        size_t n = 0;
+        detail::check(vpt_vocab_surface(raw_, id, &b, &n));
+        return std::string(reinterpret_cast<const char*>(b), n);
+    }
+
+private:
+    std::shared_ptr<detail::Shared> predictor_;
+    void* raw_ = nullptr;
+    int32_t unk_id_;
 };
 
 inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
@@ -497,6 +527,31 @@ public:
         return out;
     }
     std::vector<Token> token_stream(const std::string& text) const { return token_stream_batch({text})[0]; }
+
+    // The stream's vocabulary ids and nothing else (vpt_token_stream_ids_batch; beyond the adapter): {token_offsets [n + 1], ids} -- document i
+    // owns ids[token_offsets[i] .. token_offsets[i + 1]), the tokens this tokenizer streams (tags and stop set included), each the id of its
+    // surface in `vocab` (made for predictor()) or vocab.unk_id().  normalize: the surface looked up is the KyteaFullwidthFilter image of the
+    // token -- the text as it was scored --, else the caller's bytes.  No token string is built on the way.
+    std::pair<std::vector<uint64_t>, std::vector<int32_t>> encode(const std::vector<std::string>& texts, const Vocabulary& vocab, bool normalize = true) const {
+        std::string text;
+        std::vector<uint64_t> boff(1, 0);
+        for (const std::string& t : texts) { text += t; boff.push_back(text.size()); }
+        std::vector<uint64_t> toff(texts.size() + 1, 0);
+        const size_t cap = text.size() + 1;
+        std::vector<uint32_t> starts(cap), ends(cap), pos(cap);
+        std::vector<int32_t> ids(cap), tags;
+        if (tagged_) {
+            uint32_t nt = 0;
+            detail::check(vpt_predictor_n_tags(predictor_.raw(), &nt));
+            tags.resize(cap * size_t(nt) + 1);
+        }
+        detail::check(vpt_token_stream_ids_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
+                                                 tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, vocab.raw(),
+                                                 normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u, toff.data(), starts.data(), ends.data(), pos.data(),
+                                                 tagged_ ? tags.data() : nullptr, ids.data(), cap));
+        ids.resize(size_t(toff[texts.size()]));
+        return {std::move(toff), std::move(ids)};
+    }
 
 private:
     Predictor predictor_;

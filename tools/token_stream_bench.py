@@ -1,6 +1,6 @@
 """Token streams on the GPU box: the span kernel beside the untagged writer, and vpt_token_stream_batch end to end beside the two routes a caller
 had to the same arrays before it.
-    python tools/token_stream_bench.py [--configs 2,5] [--sentences N] [--steps 15] [--rounds 3] [--out profiles/token_stream_bench.json]
+    python tools/token_stream_bench.py [--configs 2,5] [--sentences N] [--steps 15] [--rounds 3] [--ids] [--out profiles/token_stream_bench.json]
 Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and its documents workload):
   (a) kernels, by device events on the labels a predict call left on the device, in ONE process, alternating, `--rounds` rounds of `--steps` calls:
       token_spans_kernel and the untagged emit_flat_kernel (same text and labels in; the writer stores the tokens' text, the span kernel 4 bytes a
@@ -11,6 +11,9 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       text     vpt_tokenize_batch + numpy parsing of the tokenized text to the CSR (same flags without the linebreak ones: the synthetic text has none)
       and the host share of the two older routes on its own.
   (c) bytes over PCIe each way for the three.
+  --ids: the vocabulary id pass (kernels_vocab.hip) on the span kernel's CSR by device events -- the vocabulary every other distinct surface of the
+      first --vocab-docs documents -- as ms and ms per 100 K documents, and vpt_token_stream_ids_batch end to end (untagged route; its outputs are
+      fresh pageable numpy arrays, the stream route's pinned) beside vpt_token_stream_batch; its ids must equal the device call's.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
 on the first --parity-docs documents."""
 import argparse
@@ -84,6 +87,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--parity-docs", type=int, default=2000)
     ap.add_argument("--wsconst", default="")
+    ap.add_argument("--ids", action="store_true", help="also time the vocabulary id pass and vpt_token_stream_ids_batch")
+    ap.add_argument("--vocab-docs", type=int, default=20000)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -155,6 +160,36 @@ def main():
         row["kernels"] = k
         dev_off = d_soff.cpu().numpy().astype(np.uint64)
         dev_ends = d_ends[:n_tokens].cpu().numpy().view(np.uint32)
+        vocab = dev_ids = None
+        if args.ids:
+            surf = set()
+            for i in range(min(S, args.vocab_docs)):
+                doc, a = bytes(utf8[int(boff[i]):int(boff[i + 1])]), 0
+                for t in range(int(dev_off[i]), int(dev_off[i + 1])):
+                    surf.add(doc[a:int(dev_ends[t])])
+                    a = int(dev_ends[t])
+            keys = sorted(surf)[::2]
+            vocab = api.Vocabulary(pred, keys)
+            d_ids = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
+
+            def ids():
+                batch.token_ids(vocab, d_text.data_ptr(), d_boff.data_ptr(), S, d_soff.data_ptr(), 0, d_ends.data_ptr(), cap_ends, d_ids.data_ptr(), 0, stream)
+            for _ in range(3):
+                ids()
+            batch.sync()
+            r = []
+            for _ in range(args.rounds):
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); ids(); b.record()
+                torch.cuda.synchronize()
+                r.append(med([a.elapsed_time(b) for a, b in ev]))
+            batch.sync()
+            dev_ids = d_ids[:n_tokens].cpu().numpy()
+            row["ids"] = {"vocab_keys": len(keys), "vocab": vocab.info(), "ids_ms": round(med(r), 4), "ids_rounds_ms": [round(x, 4) for x in r],
+                          "ids_spread": round((max(r) - min(r)) / min(r), 4), "ids_ms_per_100k_docs": round(med(r) * 1e5 / S, 4),
+                          "known_share": round(float(np.mean(dev_ids != vocab.unk_id)), 4), "ids_over_spans": round(med(r) / k["spans_ms"], 3)}
+            del d_ids
         del d_out, d_toff, d_ends, d_soff, d_labels, d_text, batch
         # ---- (b) end to end, pinned buffers
         p_text = api.PinnedArray(nbytes, np.uint8); p_text.array[:] = utf8
@@ -200,6 +235,12 @@ def main():
         e["text_route_ms"] = round(med(t_txt_dev) + med(t_txt_host), 3)
         e["text_route_device_ms"], e["text_route_host_ms"] = round(med(t_txt_dev), 3), round(med(t_txt_host), 3)
         e["host_scan"] = "numpy, one thread: the conversion a caller of the older routes runs after the call returns"
+        if args.ids:
+            t_ids = timed(lambda: pred.token_ids_packed(u, bo, vocab, args.wsconst, False), args.steps)
+            i_out = pred.token_ids_packed(u, bo, vocab, args.wsconst, False)
+            e["ids_stream_ms"] = round(med(t_ids), 3)
+            e["ids_stream_over_stream"] = round(med(t_ids) / med(t_stream), 3)
+            row["ids"]["stream_ids_equal_device_call"] = bool(np.array_equal(i_out[0], s_off) and np.array_equal(i_out[2], s_ends) and np.array_equal(i_out[5], dev_ids))
         row["end_to_end"] = e
         # ---- (c) PCIe bytes
         row["pcie"] = {"stream": {"h2d": nbytes + 8 * (S + 1), "d2h": 8 * (S + 1) + 4 * len(s_ends)},
@@ -225,6 +266,8 @@ def main():
             json.dump({"tool": "tools/token_stream_bench.py", "args": vars(args), "rows": rows}, fh, indent=1)
     if not all(all(v for kk, v in r["parity"].items() if kk != "tokenref_docs") for r in rows):
         raise SystemExit("parity FAILED")
+    if args.ids and not all(r["ids"]["stream_ids_equal_device_call"] for r in rows):
+        raise SystemExit("ids parity FAILED")
 
 
 if __name__ == "__main__":

@@ -758,6 +758,34 @@ class Predictor:
         n = int(toff[S])
         return toff, starts[:n].copy(), ends[:n].copy(), pos[:n].copy(), tags[:n * nt].reshape(n, nt).copy()
 
+    def token_ids_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, vocab: "Vocabulary", wsconst: str = "", normalize: bool = True,
+                         tagger: Optional["PatternMatchTagger"] = None, stop: Optional["TagStopFilter"] = None, tags: bool = False):
+        """vpt_token_stream_ids_batch: the token stream with every token's id in `vocab` -> (token_offsets uint64 [n + 1], token_starts,
+        token_ends, token_positions uint32, token_tags int32 [tokens, n_tags] or None, token_ids int32).  normalize: the surface looked up is
+        the KyteaFullwidthFilter image of the token (the text as it was scored), else the caller's bytes.  Without tagger, stop and tags the
+        untagged stream's steps run (no predict_tags needed) and token_tags is None."""
+        flags = wsconst_flags(wsconst, allow_graphemes=True)
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        tagged = bool(tags) or tagger is not None or stop is not None
+        S, nt = len(byte_offsets) - 1, self.n_tags() if (tagged and self._predict_tags) else 0
+        cap = max(int(byte_offsets[-1] - byte_offsets[0]), 1) if S else 1
+        toff = np.zeros(S + 1, np.uint64)
+        starts, ends, pos = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        tag_arr = np.zeros(cap * max(nt, 1), np.int32) if tagged else None
+        ids = np.zeros(cap, np.int32)
+        src = utf8 if len(utf8) else np.zeros(1, np.uint8)
+        st = _lib.load().vpt_token_stream_ids_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags,
+                                                    tagger.handle(self) if tagger is not None else None, stop.handle if stop is not None else None,
+                                                    vocab.handle if vocab is not None else None, _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0,
+                                                    toff.ctypes.data, starts.ctypes.data, ends.ctypes.data, pos.ctypes.data,
+                                                    tag_arr.ctypes.data if tagged else None, ids.ctypes.data, cap)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        n = int(toff[S])
+        return (toff, starts[:n].copy(), ends[:n].copy(), pos[:n].copy(), tag_arr[:n * nt].reshape(n, nt).copy() if tagged else None,
+                ids[:n].copy())
+
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                          fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
         """Predictor::predict_tags over a packed batch (predictor.rs:546-637).  labels: uint8 per boundary (0/1/2).
@@ -1358,6 +1386,17 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def token_ids(self, vocab: "Vocabulary", d_utf8: int, d_boff: int, n_documents: int, d_token_offsets: int, d_token_starts: int, d_token_ends: int,
+                  capacity_in: int, d_token_ids: int, flags: int = 0, stream: int = 0) -> None:
+        """Device-resident vocabulary ids of a finished CSR (vpt_token_ids_batch_device): int32 per token at d_token_ids, vocab.unk_id for a token
+        that is no entry.  d_token_starts 0: the spans of token_spans / token_tags; else the filter's starts.  flags: 0 or VPT_FLAG_KYTEA_FULLWIDTH.
+        Enqueues and returns."""
+        st = _lib.load().vpt_token_ids_batch_device(self._p.handle, self._h, vocab.handle if vocab is not None else None, d_utf8, d_boff, n_documents,
+                                                    d_token_offsets, d_token_starts or None, d_token_ends or None, capacity_in, flags,
+                                                    d_token_ids or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def concat_graphemes(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, stream: int = 0) -> None:
         """Device-resident ConcatGraphemeClustersFilter on the labels at d_labels, in place (vpt_concat_graphemes_batch_device; the clusters of
         the KyteaFullwidthFilter image when set_flags / set_fullwidth say so); enqueues and returns."""
@@ -1599,7 +1638,7 @@ def wsconst_flags(wsconst: str, allow_graphemes: bool = False) -> int:
 
 class TantivyToken:
     """tantivy's Token as VaporettoTokenStream fills it (vaporetto_tantivy/src/lib.rs:204-219): byte offsets into the caller's text."""
-    __slots__ = ("text", "offset_from", "offset_to", "position", "position_length")
+    __slots__ = ("text", "offset_from", "offset_to", "position", "position_length", "id")   # id: only under VaporettoTokenizer(vocab=...)
 
     def __init__(self, text: str, offset_from: int, offset_to: int, position: int, position_length: int):
         self.text, self.offset_from, self.offset_to, self.position, self.position_length = text, offset_from, offset_to, position, position_length
@@ -1643,6 +1682,55 @@ class TagStopFilter:
             self.handle = None
 
 
+class Vocabulary:
+    """vpt_vocab_create: token surface -> int32 id on the predictor's device.  `surfaces`: a sequence of str (or bytes); entry k gets id k, a
+    token that is no entry `unk_id`.  An empty surface, a NUL, invalid UTF-8 and a repeated surface are errors that name the entry.  Tied to
+    `predictor`; immutable."""
+
+    def __init__(self, predictor: "Predictor", surfaces, unk_id: int = -1):
+        raws = [s.encode("utf-8", "surrogatepass") if isinstance(s, str) else bytes(s) for s in surfaces]
+        sb, off = pack_texts(raws)
+        sb = sb if len(sb) else np.zeros(1, np.uint8)
+        h = C.c_void_p()
+        self._keep = predictor
+        self.unk_id = int(unk_id)
+        st = _lib.load().vpt_vocab_create(predictor.handle, sb.ctypes.data, off.ctypes.data, len(raws), self.unk_id, C.byref(h))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None:
+            try:
+                _lib.load().vpt_vocab_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def info(self) -> dict:
+        k, n, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        st = _lib.load().vpt_vocab_info(self.handle, C.byref(k), C.byref(n), C.byref(m))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return {"n_keys": int(k.value), "n_slots": int(n.value), "max_surface_chars": int(m.value)}
+
+    def surface(self, entry_id: int) -> str:
+        ptr, n = C.c_void_p(), C.c_size_t()
+        st = _lib.load().vpt_vocab_surface(self.handle, int(entry_id), C.byref(ptr), C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return C.string_at(ptr.value, n.value).decode("utf-8") if n.value else ""
+
+    @staticmethod
+    def tile() -> int:
+        v = C.c_uint32()
+        st = _lib.load().vpt_vocab_tile(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
+
 class TaggedToken(TantivyToken):
     """A token of the tagged stream: TantivyToken plus `tags`, a tuple of Optional[str] per slot.  Under a stop filter `position` is the index
     before filtering and `position_length` the count before filtering."""
@@ -1665,9 +1753,12 @@ class VaporettoTokenizer:
     last, which is the adapter's result for any place of "G" in the string."""
 
     def __init__(self, model: Model, wsconst: str = "", device: int = 0, _predictor: Optional[Predictor] = None, predict_tags: bool = False,
-                 tagger: Optional["PatternMatchTagger"] = None, stop_tags=None):
+                 tagger: Optional["PatternMatchTagger"] = None, stop_tags=None, vocab=None, vocab_normalize: bool = True):
         """predict_tags (beyond the adapter, which predicts none): the tokens are TaggedToken, with `tagger`'s rule tags behind the tag models'
-        and without the tokens of `stop_tags` ((slot, tag string) pairs).  Without it the class is the adapter's."""
+        and without the tokens of `stop_tags` ((slot, tag string) pairs).  Without it the class is the adapter's.
+        vocab (a Vocabulary of this tokenizer's predictor, or a sequence of surfaces; also beyond the adapter): every token carries `.id`, its
+        entry in the vocabulary or the vocabulary's unk_id, looked up on the device -- with vocab_normalize on the KyteaFullwidthFilter image of
+        the token (the text as it was scored), else on the caller's bytes; encode_batch returns the ids alone."""
         self._flags = wsconst_flags(wsconst, allow_graphemes=True)
         self._wsconst = wsconst
         self._predictor = _predictor if _predictor is not None else Predictor(model, bool(predict_tags), device=device)
@@ -1675,14 +1766,16 @@ class VaporettoTokenizer:
             raise VaporettoError("InvalidArgumentError: tagger / stop_tags: need predict_tags = True")
         self._tagged, self._tagger = bool(predict_tags), tagger
         self._stop = TagStopFilter(self._predictor, stop_tags, tagger) if stop_tags is not None else None
+        self._vocab = vocab if vocab is None or isinstance(vocab, Vocabulary) else Vocabulary(self._predictor, vocab)
+        self._vocab_normalize = bool(vocab_normalize)
 
     @classmethod
     def deserialize(cls, blob, wsconst: str = "", device: int = 0, predict_tags: bool = False, tagger: Optional["PatternMatchTagger"] = None,
-                    stop_tags=None) -> "VaporettoTokenizer":
+                    stop_tags=None, vocab=None, vocab_normalize: bool = True) -> "VaporettoTokenizer":
         """lib.rs:121-146, from Predictor.save_compiled's bytes (vpt_predictor_load); predict_tags needs bytes of a predictor made with it."""
         wsconst_flags(wsconst, allow_graphemes=True)
         return cls(None, wsconst, device, _predictor=Predictor.load_compiled(blob, device=device), predict_tags=predict_tags, tagger=tagger,
-                   stop_tags=stop_tags)
+                   stop_tags=stop_tags, vocab=vocab, vocab_normalize=vocab_normalize)
 
     @property
     def predictor(self) -> Predictor:
@@ -1700,6 +1793,8 @@ class VaporettoTokenizer:
             return []
         if self._tagged:
             return self._tagged_batch(texts)
+        if self._vocab is not None:
+            return self._ids_batch(texts)
         utf8, boff, toff, ends = self.token_spans(texts)
         out = []
         for i, _ in enumerate(texts):
@@ -1712,10 +1807,42 @@ class VaporettoTokenizer:
             out.append(toks)
         return out
 
+    def _stream_ids(self, utf8, boff):
+        return self._predictor.token_ids_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop,
+                                                tags=self._tagged)
+
+    def encode_batch(self, texts: Sequence[str]):
+        """(token_offsets uint64 [n + 1], ids int32) of a batch of documents: the stream's vocabulary ids and nothing else -- no token string is
+        built on the way (vpt_token_stream_ids_batch).  Needs vocab=."""
+        if self._vocab is None:
+            raise VaporettoError("InvalidArgumentError: encode_batch: the tokenizer has no vocab")
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        out = self._stream_ids(utf8, boff)
+        return out[0], out[5]
+
+    def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        toff, starts, ends, pos, _, ids = self._stream_ids(utf8, boff)
+        out = []
+        for i, _t in enumerate(texts):
+            raw = bytes(utf8[int(boff[i]):int(boff[i + 1])])
+            a, b = int(toff[i]), int(toff[i + 1])
+            toks = []
+            for k in range(a, b):
+                tok = TantivyToken(raw[int(starts[k]):int(ends[k])].decode("utf-8"), int(starts[k]), int(ends[k]), int(pos[k]), b - a)
+                tok.id = int(ids[k])
+                toks.append(tok)
+            out.append(toks)
+        return out
+
     def _tagged_batch(self, texts: Sequence[str]) -> List[List["TaggedToken"]]:
         p = self._predictor
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
-        toff, starts, ends, pos, tags = p.token_stream_tagged_packed(utf8, boff, self._wsconst, self._tagger, self._stop)
+        ids = None
+        if self._vocab is not None:
+            toff, starts, ends, pos, tags, ids = self._stream_ids(utf8, boff)
+        else:
+            toff, starts, ends, pos, tags = p.token_stream_tagged_packed(utf8, boff, self._wsconst, self._tagger, self._stop)
         # position_length is the count before filtering, which the filtered arrays no longer hold: under a stop filter the UNTAGGED stream
         # (vpt_token_stream_batch: scoring and spans a second time, no fill_tags, no tags) gives it.  Callers that do not need
         # position_length take token_stream_tagged_packed, which is one pass.
@@ -1729,6 +1856,9 @@ class VaporettoTokenizer:
             out.append([TaggedToken(raw[int(starts[k]):int(ends[k])].decode("utf-8"), int(starts[k]), int(ends[k]), int(pos[k]), n,
                                     [None if v == -1 else vocab[v] if v >= 0 else rule[-2 - v] for v in (int(x) for x in tags[k])])
                         for k in range(int(toff[i]), int(toff[i + 1]))])
+            if ids is not None:
+                for tok, k in zip(out[-1], range(int(toff[i]), int(toff[i + 1]))):
+                    tok.id = int(ids[k])
         return out
 
     def token_stream(self, text: str) -> List[TantivyToken]:

@@ -1,6 +1,7 @@
 // C ABI of libvaporetto_hip.so, the device-resident entry points: Predictor::predict (tile planning + the scoring launch), Sentence::fill_tags (the tag
 // records), write_tokenized_text (the flat writer), the char count, Sentence::char_types -- all on device buffers, asynchronous on the caller's stream.
 #include "capi_internal.hpp"
+#include "vocab_table.hpp"
 
 // (the entry points have C linkage from their declarations in include/vaporetto_hip.h)
 
@@ -550,11 +551,11 @@ vpt_status token_tags_device(const vpt_predictor* p, vpt_batch* b, const uint8_t
 vpt_status token_filter_device(const vpt_predictor* p, vpt_batch* b, const vpt_tag_stop* stop, const uint64_t* d_token_offsets,
                                const uint32_t* d_token_ends, const int32_t* d_token_tags, size_t n_documents, uint64_t capacity_in,
                                uint64_t* d_offsets_out, uint32_t* d_starts_out, uint32_t* d_ends_out, uint32_t* d_positions_out, int32_t* d_tags_out,
-                               uint64_t capacity, hipStream_t stream, uint64_t* total_out) {
+                               uint64_t capacity, hipStream_t stream, uint64_t* total_out, bool with_tags) {
     if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
     if (stop && stop->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: stop: does not belong to this predictor");
     if (!d_token_offsets || !d_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    const uint32_t nt = p->predict_tags ? p->n_tags : 0u;
+    const uint32_t nt = (with_tags && p->predict_tags) ? p->n_tags : 0u;   // (without tags: the untagged stream's starts and positions)
     if ((capacity_in && (!d_token_ends || (nt && !d_token_tags))) || (capacity && (!d_starts_out || !d_ends_out || !d_positions_out || (nt && !d_tags_out))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
     VPT_HIP(hipSetDevice(p->device));
@@ -912,4 +913,104 @@ vpt_status vpt_batch_set_pattern_tagger(vpt_batch* b, const void* tagger) {
     b->tagger = t;
     b->tag_out.chars = 0;   // the records on the workspace were made under the other setting
     return VPT_OK;
+}
+
+// ---- the vocabulary of the id pass (vocab_table.hpp): the hashed surface table on the predictor's device
+vpt_status vpt_vocab_create(const vpt_predictor* p, const uint8_t* surfaces, const uint64_t* offsets, size_t n_entries, int32_t unk_id, void** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_entries && (!surfaces || !offsets)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    vpt::HostVocabTable H;
+    try {
+        H = vpt::build_vocab_table(surfaces, offsets, n_entries);
+    } catch (const vpt::VocabError& e) {
+        return fail(VPT_INVALID_ARGUMENT, e.what());
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory while building the vocabulary");
+    }
+    VPT_HIP(hipSetDevice(p->device));
+    vpt_vocab* v = new (std::nothrow) vpt_vocab();
+    if (!v) return fail(VPT_RUNTIME_ERROR, "out of host memory");
+    v->pred = p; v->device = p->device; v->bits = H.bits; v->max_len = H.max_len; v->n_keys = H.n_keys; v->unk_id = unk_id;
+    v->off = std::move(H.off); v->bytes = std::move(H.bytes);
+    // one allocation, 256-byte sections: slots | the surfaces' code points
+    auto pad = [](size_t n) { return (n + kTablePadBytes + 255) & ~size_t(255); };
+    const size_t o_slots = 0, o_surf = o_slots + pad(4 * H.slots.size()), total = o_surf + pad(4 * H.cps.size());
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&v->mem), total);
+    if (e == hipSuccess) e = hipMemset(v->mem, 0, total);
+    if (e == hipSuccess) e = hipMemcpy(v->mem + o_slots, H.slots.data(), 4 * H.slots.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !H.cps.empty()) e = hipMemcpy(v->mem + o_surf, H.cps.data(), 4 * H.cps.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(v->mem);
+        delete v;
+        return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    v->slots = reinterpret_cast<const uint4*>(v->mem + o_slots); v->surf = reinterpret_cast<const uint32_t*>(v->mem + o_surf);
+    *out = v;
+    return VPT_OK;
+}
+
+void vpt_vocab_destroy(void* vocab) {
+    vpt_vocab* v = static_cast<vpt_vocab*>(vocab);
+    if (!v) return;
+    (void)hipSetDevice(v->device);
+    (void)hipFree(v->mem);
+    delete v;
+}
+
+vpt_status vpt_vocab_info(const void* vocab, uint32_t* n_keys, uint32_t* n_slots, uint32_t* max_surface_chars) {
+    const vpt_vocab* v = static_cast<const vpt_vocab*>(vocab);
+    if (!v) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_keys) *n_keys = v->n_keys;
+    if (n_slots) *n_slots = 1u << v->bits;
+    if (max_surface_chars) *max_surface_chars = v->max_len;
+    return VPT_OK;
+}
+
+vpt_status vpt_vocab_surface(const void* vocab, uint32_t id, const uint8_t** bytes, size_t* len) {
+    const vpt_vocab* v = static_cast<const vpt_vocab*>(vocab);
+    if (!v || !bytes || !len) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (id >= v->n_keys) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: id: no such vocabulary entry");
+    *bytes = v->bytes.data() + v->off[id];
+    *len = size_t(v->off[id + 1] - v->off[id]);
+    return VPT_OK;
+}
+
+vpt_status vpt_vocab_tile(uint32_t* n_tokens) {
+    if (!n_tokens) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *n_tokens = vpt::kVocabTile;
+    return VPT_OK;
+}
+
+// The id pass over a finished CSR (kernels_vocab.hip): one launch.  The number of tokens is on the device; capacity_in bounds it and sizes the grid.
+namespace vptc {
+vpt_status token_ids_device(const vpt_predictor* p, vpt_batch* b, const vpt_vocab* vocab, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                            size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
+                            uint64_t capacity_in, unsigned flags, int32_t* d_token_ids, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!vocab) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: must not be NULL");
+    if (vocab->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: does not belong to this predictor");
+    if (flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (n_documents == 0) return VPT_OK;   // no document owns a token: nothing is enqueued
+    if (!d_utf8 || !d_byte_offsets || !d_token_offsets || (capacity_in && (!d_token_ends || !d_token_ids)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if ((capacity_in + vpt::kVocabTile - 1) / vpt::kVocabTile > 0x7FFFFFFFull)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the id pass takes fewer than 2^39 tokens per call");
+    VPT_HIP(hipSetDevice(p->device));
+    vpt::VocabParams P{};
+    P.text = d_utf8; P.boff = d_byte_offsets; P.n_docs = n_documents; P.token_offsets = d_token_offsets; P.token_starts = d_token_starts;
+    P.token_ends = d_token_ends; P.capacity_in = capacity_in; P.slots = vocab->slots; P.surf = vocab->surf;
+    P.cinfo = (flags & VPT_FLAG_KYTEA_FULLWIDTH) ? p->d_cinfo + 65536 : nullptr;
+    P.bits = vocab->bits; P.max_len = vocab->max_len; P.unk_id = vocab->unk_id; P.ids = d_token_ids; P.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_token_ids(P, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_token_ids_batch_device(const vpt_predictor* p, vpt_batch* b, const void* vocab, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                      size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
+                                      uint64_t capacity_in, unsigned flags, int32_t* d_token_ids, void* hip_stream) {
+    return token_ids_device(p, b, static_cast<const vpt_vocab*>(vocab), d_utf8, d_byte_offsets, n_documents, d_token_offsets, d_token_starts,
+                            d_token_ends, capacity_in, flags, d_token_ids, static_cast<hipStream_t>(hip_stream));
 }

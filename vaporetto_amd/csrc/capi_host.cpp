@@ -745,22 +745,29 @@ vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, c
 // starts and positions) -- enqueued back to back, nothing on the way needs a number from the device.  A chunk's arrays start where an upper
 // bound puts them (a token per byte at most); the host collects the chunks in order and rebases their offsets: the filter runs per chunk, and
 // a chunk holds whole documents, so the arrays do not depend on the cut.
-vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
-                                         unsigned wsconst_flags, const void* tagger, const void* stop, uint64_t* token_offsets_out,
-                                         uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out, int32_t* token_tags_out,
-                                         uint64_t capacity) {
+// `tagged` == false (vpt_token_stream_ids_batch without tagger, stop set and tags): no fill_tags, the untagged span instance, and the filter
+// pass without tags -- vpt_token_stream_batch's steps with starts and positions.  `vocab` != NULL: the id pass (kernels_vocab.hip) runs last
+// on every chunk's finished CSR, one launch more per chunk; with NULL the launches are what they were.
+namespace {
+vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents, unsigned wsconst_flags,
+                               bool tagged, const void* tagger, const void* stop, const vpt_vocab* vocab, unsigned vocab_flags,
+                               uint64_t* token_offsets_out, uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out,
+                               int32_t* token_tags_out, int32_t* token_ids_out, uint64_t capacity) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (wsconst_flags & ~(0x7Eu | unsigned(VPT_FLAG_CONCAT_GRAPHEMES))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
-    if (!p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
+    if (tagged && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
     const vpt_tag_stop* sp = static_cast<const vpt_tag_stop*>(stop);
     if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
     if (sp && sp->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: stop: does not belong to this predictor");
+    if (vocab && vocab->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: does not belong to this predictor");
+    if (vocab && (vocab_flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
     token_offsets_out[0] = 0;
     if (n_documents == 0) return VPT_OK;
-    const uint32_t nt = p->n_tags;
-    if (!utf8 || !byte_offsets || (capacity && (!token_starts_out || !token_ends_out || !token_positions_out || (nt && !token_tags_out))))
+    const uint32_t nt = tagged ? p->n_tags : 0u;
+    if (!utf8 || !byte_offsets ||
+        (capacity && (!token_starts_out || !token_ends_out || !token_positions_out || (nt && !token_tags_out) || (vocab && !token_ids_out))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     std::vector<uint64_t> docs;   // an empty document has no tokens and never reaches the device (vpt_token_stream_batch)
     docs.reserve(n_documents + 1);
@@ -795,10 +802,11 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* 
     if ((st = grow_pair(b->d_boff, b->d_ooff, slots)) != VPT_OK) return st;
     if ((st = b->d_tlab.grow(nbytes + 1)) != VPT_OK) return st;
     if ((st = b->d_toff.grow(slots)) != VPT_OK || (st = b->d_ftoff.grow(slots)) != VPT_OK) return st;
-    if ((st = b->d_tends.grow(nbytes + 16)) != VPT_OK || (st = b->d_ttags.grow(tag_words)) != VPT_OK) return st;
+    if ((st = b->d_tends.grow(nbytes + 16)) != VPT_OK || (tagged && (st = b->d_ttags.grow(tag_words)) != VPT_OK)) return st;
     if ((st = b->d_fstarts.grow(nbytes + 16)) != VPT_OK || (st = b->d_fends.grow(nbytes + 16)) != VPT_OK || (st = b->d_fpos.grow(nbytes + 16)) != VPT_OK ||
-        (st = b->d_ftags.grow(tag_words)) != VPT_OK)
+        (tagged && (st = b->d_ftags.grow(tag_words)) != VPT_OK))
         return st;
+    if (vocab && (st = b->d_fids.grow(nbytes + 16)) != VPT_OK) return st;
     if ((st = pinned_words(b, vptcut::tagged_pinned_words(n, max_chunks))) != VPT_OK) return st;
     uint64_t* const h_boff = b->h_off;
     uint64_t* const h_total = b->h_off + n + 1;
@@ -827,12 +835,22 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* 
             bb->tagger = t;
             if ((st = vpt_fill_tags_batch_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, nullptr, s)) != VPT_OK) return st;
         }
-        st = token_tags_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, b->d_toff + a + k, b->d_tends + tb, b->d_ttags + tb * nt, nby, s, nullptr);
+        int32_t* const d_ttags_k = nt ? b->d_ttags + tb * nt : nullptr;
+        int32_t* const d_ftags_k = nt ? b->d_ftags + tb * nt : nullptr;
+        if (tagged)
+            st = token_tags_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, b->d_toff + a + k, b->d_tends + tb, d_ttags_k, nby, s, nullptr);
+        else
+            st = spans_device(p, bb, b->d_text, d_boff_k, d_ooff_k, cn, tb_bound, d_labels_k, b->d_toff + a + k, b->d_tends + tb, nby, s, nullptr, nullptr, nullptr);
         if (st != VPT_OK) return st;
         h_total[k] = 0;
-        st = token_filter_device(p, bb, sp, b->d_toff + a + k, b->d_tends + tb, b->d_ttags + tb * nt, cn, nby, b->d_ftoff + a + k, b->d_fstarts + tb,
-                                 b->d_fends + tb, b->d_fpos + tb, b->d_ftags + tb * nt, nby, s, h_total + k);
+        st = token_filter_device(p, bb, sp, b->d_toff + a + k, b->d_tends + tb, d_ttags_k, cn, nby, b->d_ftoff + a + k, b->d_fstarts + tb,
+                                 b->d_fends + tb, b->d_fpos + tb, d_ftags_k, nby, s, h_total + k, tagged);
         if (st != VPT_OK) return st;
+        if (vocab) {   // the ids of the chunk's finished CSR, in the caller's text or its KyteaFullwidthFilter image
+            st = token_ids_device(p, bb, vocab, b->d_text, d_boff_k, cn, b->d_ftoff + a + k, b->d_fstarts + tb, b->d_fends + tb, nby, vocab_flags,
+                                  b->d_fids + tb, s);
+            if (st != VPT_OK) return st;
+        }
         VPT_HIP(hipEventRecord(b->chunk_ev[k], s));
         chunks.push_back(c);
     }
@@ -853,6 +871,7 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* 
             VPT_HIP(hipMemcpyAsync(token_ends_out + at, b->d_fends + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
             VPT_HIP(hipMemcpyAsync(token_positions_out + at, b->d_fpos + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
             if (nt) VPT_HIP(hipMemcpyAsync(token_tags_out + at * nt, b->d_ftags + c.tb * nt, 4 * size_t(total) * nt, hipMemcpyDeviceToHost, b->s_out));
+            if (vocab) VPT_HIP(hipMemcpyAsync(token_ids_out + at, b->d_fids + c.tb, 4 * size_t(total), hipMemcpyDeviceToHost, b->s_out));
         }
         VPT_HIP(hipMemcpyAsync(packed.data() + c.a + 1, b->d_ftoff + c.a + k + 1, 8 * c.n, hipMemcpyDeviceToHost, b->s_out));
         at += total;
@@ -870,6 +889,26 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* 
     }
     token_offsets_out[n_documents] = packed[n];
     return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                         unsigned wsconst_flags, const void* tagger, const void* stop, uint64_t* token_offsets_out,
+                                         uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out, int32_t* token_tags_out,
+                                         uint64_t capacity) {
+    return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, true, tagger, stop, nullptr, 0, token_offsets_out, token_starts_out,
+                               token_ends_out, token_positions_out, token_tags_out, nullptr, capacity);
+}
+
+// The token stream with every token's vocabulary id: the untagged steps when neither tagger, stop set nor tags are asked for, else the tagged ones
+vpt_status vpt_token_stream_ids_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                      unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab, unsigned vocab_flags,
+                                      uint64_t* token_offsets_out, uint32_t* token_starts_out, uint32_t* token_ends_out,
+                                      uint32_t* token_positions_out, int32_t* token_tags_out, int32_t* token_ids_out, uint64_t capacity) {
+    if (!vocab) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: must not be NULL");
+    const bool tagged = tagger || stop || token_tags_out;
+    return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, tagged, tagger, stop, static_cast<const vpt_vocab*>(vocab), vocab_flags,
+                               token_offsets_out, token_starts_out, token_ends_out, token_positions_out, token_tags_out, token_ids_out, capacity);
 }
 
 // ---- pinned host memory for callers that want the PCIe link at full rate

@@ -276,6 +276,19 @@ struct vpt_tag_stop {
     uint32_t model_words = 0, rule_words = 0, n_vocab = 0, n_rule = 0;
 };
 
+// A vocabulary on the predictor's device (vocab_table.hpp; kernels_vocab.hip): the hashed surface table and the surfaces' code points in one
+// allocation; the surfaces' bytes stay on the host (vpt_vocab_surface).  Immutable, tied to its predictor's device, shared by workspaces and host threads.
+struct vpt_vocab {
+    const vpt_predictor* pred = nullptr;
+    int device = 0;
+    unsigned char* mem = nullptr;
+    const uint4* slots = nullptr; const uint32_t* surf = nullptr;
+    uint32_t bits = 1, max_len = 0, n_keys = 0;
+    int32_t unk_id = -1;
+    std::vector<uint64_t> off;         // [n_keys + 1]
+    std::vector<uint8_t> bytes;
+};
+
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
 struct DevBuf {
@@ -352,6 +365,7 @@ struct vpt_batch {
     DevBuf<int32_t> d_ttags, d_ftags;
     DevBuf<uint32_t> d_fstarts, d_fends, d_fpos;
     DevBuf<uint64_t> d_ftoff, d_filt;
+    DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -489,6 +503,8 @@ vpt_status status_from_bits(uint32_t bits) {
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text_capacity: smaller than the tokenized text");
     if (bits & vpt::kErrBadLabel)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: not a CharacterBoundary (0, 1 or 2)");
+    if (bits & vpt::kErrBadTokenCsr)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: token_offsets / token_starts / token_ends: do not describe the documents' tokens");
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
 
@@ -666,7 +682,11 @@ vpt_status token_tags_device(const vpt_predictor* p, vpt_batch* b, const uint8_t
 vpt_status token_filter_device(const vpt_predictor* p, vpt_batch* b, const vpt_tag_stop* stop, const uint64_t* d_token_offsets,
                                const uint32_t* d_token_ends, const int32_t* d_token_tags, size_t n_documents, uint64_t capacity_in,
                                uint64_t* d_offsets_out, uint32_t* d_starts_out, uint32_t* d_ends_out, uint32_t* d_positions_out, int32_t* d_tags_out,
-                               uint64_t capacity, hipStream_t stream, uint64_t* total_out);
+                               uint64_t capacity, hipStream_t stream, uint64_t* total_out, bool with_tags = true);
+// The id pass over a finished CSR (vpt_token_ids_batch_device; kernels_vocab.hip)
+vpt_status token_ids_device(const vpt_predictor* p, vpt_batch* b, const vpt_vocab* vocab, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                            size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
+                            uint64_t capacity_in, unsigned flags, int32_t* d_token_ids, hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

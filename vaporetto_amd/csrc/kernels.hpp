@@ -66,6 +66,7 @@ constexpr uint32_t kErrParsePartial = 128u;   // partially annotated text that p
 // offending code point's bytes (little-endian, lead first) of THAT line in status word kPartialErrBytesWord, stored by the write pass
 constexpr uint32_t kPartialErrNoChar = 1u, kPartialErrNul = 2u, kPartialErrChar = 3u, kPartialErrEnd = 4u, kPartialErrWord = 1u, kPartialErrBytesWord = 7u;
 constexpr uint32_t kErrBadLabel = 256u;       // the partial-annotation writer: a label that is no CharacterBoundary (above 2)
+constexpr uint32_t kErrBadTokenCsr = 512u;    // the id pass: token_offsets / starts / ends that do not describe the documents (kernels_vocab.hip)
 
 
 struct ScoreParams {
@@ -262,6 +263,29 @@ struct TokenFilterParams {
 };
 // scan_part: scan_part_entries(n_blocks) zero words
 hipError_t launch_token_filter(const TokenFilterParams& P, uint64_t* scan_part, hipStream_t stream);
+// Vocabulary ids of a finished span CSR (kernels_vocab.hip): one int32 per token, the id of its surface in the table of vocab_table.hpp or unk_id.
+// A workgroup takes kVocabTile consecutive tokens, a lane per token.  starts == nullptr: a token's start is the entry before it in its
+// document, or 0 (what the span kernels write); else starts / ends are the filter's.  cinfo: nullptr, or the KyteaFullwidthFilter image of the
+// BMP (decode_chars_kernel's table): the surface looked up is then that of the text as it was scored.
+constexpr uint32_t kVocabTile = 256;       // tokens a workgroup takes (vpt_vocab_tile)
+constexpr uint32_t kVocabLdsOffsets = 512; // token_offsets entries of a tile's documents kept in LDS; a tile that spans more bisects in global memory
+struct VocabParams {
+    const uint8_t* text;
+    const uint64_t* boff;           // [n_docs + 1]
+    uint64_t n_docs;
+    const uint64_t* token_offsets;  // [n_docs + 1]
+    const uint32_t* token_starts;   // [capacity_in] or nullptr
+    const uint32_t* token_ends;     // [capacity_in]
+    uint64_t capacity_in;
+    const uint4* slots;             // 2^bits slots {id + 1, chars, fingerprint, first code point in surf}
+    const uint32_t* surf;
+    const uint32_t* cinfo;
+    uint32_t bits, max_len;
+    int32_t unk_id;
+    int32_t* ids;                   // [capacity_in]
+    uint32_t* status;
+};
+hipError_t launch_token_ids(const VocabParams& P, hipStream_t stream);
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
