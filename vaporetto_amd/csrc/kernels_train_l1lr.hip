@@ -12,83 +12,37 @@
 // the accept and halving steps would have to keep it current.  Which of the two moves fewer bytes depends on the share of columns that
 // move in a sweep; nobody has measured it.
 //
-// Who takes a column and the summation rule are those of kernels_train_l1.hip: a lane a column of at most kL1rLaneMax nonzeros, a wave
-// one of at most kL1rWaveMax, the workgroup a longer one and the bias; a column's sum is taken over tiles of 64 nonzeros, each summed
-// in index order by one thread, the tile sums 64 at a time in index order, level by level.  The shape of that tree depends on the
-// column's length alone, so every column sum has the same bits on every path and for every launch geometry.
+// Who takes a column, the summation rule of its sums and the dealing of a launch's columns are l1r_team.h's.
 #include "kernels.hpp"
 
 #include "device_common.h"
 #include "l1r_lr.h"
+#include "l1r_team.h"
 
 namespace vpt {
 namespace {
 
-constexpr uint32_t kTileNz = 64;                           // nonzeros (partial sums) a thread adds up in order
-constexpr uint32_t kWaveTiles = kL1rWaveMax / kTileNz;     // tile sums a wave keeps in LDS
-static_assert(kL1rLaneMax == kTileNz && kWaveTiles >= 1 && kWaveTiles <= 64, "a lane takes one tile, a wave's second level is one sum");
-
-// the lanes of a wave meet: what they wrote to LDS before is what they read after
-__device__ __forceinline__ void wave_rendezvous() {
-#ifndef VPT_HIPEMU
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-    __builtin_amdgcn_wave_barrier();
-}
-
-// a team of kT threads (1: a lane, 64: a wave, 256: the workgroup) over one column: its sums and its write of xTd
+// a team of kT threads over one column: its sums and its write of xTd
 template <uint32_t kT>
 struct Team {
     const L1lrParams& P;
-    uint64_t a, n;      // the column's nonzeros: a .. a + n of the CSC (the bias: rows 0 .. n, value 1)
+    uint64_t a;         // the column's nonzeros: a .. a + n of the CSC (the bias: rows 0 .. n, value 1)
     bool bias;
-    uint32_t t;         // this thread in the team
-    L1rPair *s0, *s1;   // the levels' sums, written in turn
+    L1rTeam<kT, uint64_t> tm;
 
-    __device__ __forceinline__ void sync() const {
-        if constexpr (kT == 64) wave_rendezvous();
-        else if constexpr (kT > 64) __syncthreads();
-    }
-    // the tile that starts at nonzero k0, in index order; f(row, x)
+    __device__ __forceinline__ uint64_t row(uint64_t k) const { return bias ? k : P.crow[a + k]; }
+    __device__ __forceinline__ double x(uint64_t k) const { return bias ? 1.0 : double(P.cval[a + k]); }
+    // f(row, x) over the column's nonzeros
     template <typename F>
-    __device__ __forceinline__ L1rPair tile(uint64_t k0, F f) const {
-        const uint64_t k1 = k0 + kTileNz < n ? k0 + kTileNz : n;
-        L1rPair acc{0.0, 0.0};
-        for (uint64_t k = k0; k < k1; ++k) {
-            const uint64_t row = bias ? k : P.crow[a + k];
-            acc = l1r_add(acc, f(row, bias ? 1.0 : double(P.cval[a + k])));
-        }
-        return acc;
-    }
-    template <typename F>
-    __device__ L1rPair sums(F f) const {
-        if constexpr (kT == 1) return tile(0, f);
-        uint64_t m = (n + kTileNz - 1) / kTileNz;
-        for (uint64_t i = t; i < m; i += kT) s0[i] = tile(i * kTileNz, f);
-        sync();
-        L1rPair *src = s0, *dst = s1;
-        while (m > 1) {
-            const uint64_t g = (m + kTileNz - 1) / kTileNz;
-            for (uint64_t i = t; i < g; i += kT) {
-                const uint64_t q1 = (i + 1) * kTileNz < m ? (i + 1) * kTileNz : m;
-                L1rPair acc{0.0, 0.0};
-                for (uint64_t q = i * kTileNz; q < q1; ++q) acc = l1r_add(acc, src[q]);
-                dst[i] = acc;
-            }
-            sync();
-            L1rPair* tmp = src; src = dst; dst = tmp;
-            m = g;
-        }
-        const L1rPair r = src[0];
-        sync();   // the next pass writes the buffers again
-        return r;
+    __device__ __forceinline__ L1rPair sums(F f) const {
+        return tm.sums([this, f](uint64_t k) { return f(row(k), x(k)); });
     }
     // xTd_i += z x_ij over the column: its rows are distinct, and no other column of the launch has them
     __device__ void add_xTd(double z) const {
-        for (uint64_t k = t; k < n; k += kT) {
-            const uint64_t row = bias ? k : P.crow[a + k];
-            P.xTd[row] = P.xTd[row] + z * (bias ? 1.0 : double(P.cval[a + k]));
-        }
+        tm.each([this, z](uint64_t k) {
+            const uint64_t r = row(k);
+            P.xTd[r] = P.xTd[r] + z * x(k);
+        });
     }
 };
 
@@ -99,7 +53,7 @@ template <uint32_t kT, int kMode>
 __device__ void column(const L1lrParams& P, uint32_t j, uint32_t t, L1rPair* s0, L1rPair* s1) {
     const bool bias = j == P.nd;
     const uint64_t a = bias ? 0 : P.cptr[j], n = bias ? P.nr : P.cptr[j + 1] - a;
-    const Team<kT> be{P, a, n, bias, t, s0, s1};
+    const Team<kT> be{P, a, bias, {n, t, s0, s1}};
     if constexpr (kMode == kNeg) {
         const double c = P.c;
         const double* y = P.y;
@@ -127,38 +81,19 @@ __device__ void column(const L1lrParams& P, uint32_t j, uint32_t t, L1rPair* s0,
     }
 }
 
-// cols: the launch's columns, those a lane takes first, then a wave's, then a workgroup's
 template <int kMode>
 __device__ __forceinline__ void columns(const L1lrParams& P, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block,
-                                        L1rPair (*lds)[kWaveTiles + 1]) {
-    constexpr uint32_t kWaves = kTrainThreads / 64;
-    const uint32_t lane_blocks = (n_lane + kTrainThreads - 1) / kTrainThreads, wave_blocks = (n_wave + kWaves - 1) / kWaves;
-    uint32_t bx = blockIdx.x;
-    if (bx < lane_blocks) {
-        const uint32_t i = bx * kTrainThreads + threadIdx.x;
-        if (i < n_lane) column<1, kMode>(P, cols[i], 0, nullptr, nullptr);
-        return;
-    }
-    bx -= lane_blocks;
-    if (bx < wave_blocks) {
-        const uint32_t wave = threadIdx.x >> 6, i = bx * kWaves + wave;
-        if (i < n_wave) column<64, kMode>(P, cols[n_lane + i], threadIdx.x & 63u, lds[wave], lds[wave] + kWaveTiles);
-        return;
-    }
-    bx -= wave_blocks;
-    if (bx >= n_block) return;
-    const uint32_t j = cols[n_lane + n_wave + bx];
-    const uint64_t start = j == P.nd ? P.nnz : P.cptr[j];   // the bias behind every column
-    column<kTrainThreads, kMode>(P, j, threadIdx.x, P.tile0 + (start >> 6) + j, P.tile1 + (start >> 12) + j);
+                                        L1rPair (*lds)[kL1rWaveTiles + 1]) {
+    l1r_deal_launch(cols, n_lane, n_wave, n_block, lds, P.nd, P.nnz, P.cptr, P.tile0, P.tile1,
+                    [&P](auto kT, uint32_t j, uint32_t t, L1rPair* s0, L1rPair* s1) { column<kT, kMode>(P, j, t, s0, s1); });
 }
-
 template <bool kNegSum>
 __global__ __launch_bounds__(kTrainThreads) void l1lr_grad_kernel(L1lrParams P, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block) {
-    __shared__ L1rPair lds[kTrainThreads / 64][kWaveTiles + 1];
+    __shared__ L1rPair lds[kL1rWaves][kL1rWaveTiles + 1];
     columns<kNegSum ? kNeg : kGrad>(P, cols, n_lane, n_wave, n_block, lds);
 }
 __global__ __launch_bounds__(kTrainThreads) void l1lr_cd_group_kernel(L1lrParams P, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block) {
-    __shared__ L1rPair lds[kTrainThreads / 64][kWaveTiles + 1];
+    __shared__ L1rPair lds[kL1rWaves][kL1rWaveTiles + 1];
     columns<kCd>(P, cols, n_lane, n_wave, n_block, lds);
 }
 
@@ -208,7 +143,7 @@ __global__ __launch_bounds__(kTrainThreads) void l1lr_halve_kernel(uint64_t n, u
 }
 
 hipError_t launch_cols(int mode, const L1lrParams& P, const uint32_t* cols, uint32_t n_lane, uint32_t n_wave, uint32_t n_block, hipStream_t st) {
-    const uint32_t blocks = (n_lane + kTrainThreads - 1) / kTrainThreads + (n_wave + kTrainThreads / 64 - 1) / (kTrainThreads / 64) + n_block;
+    const uint32_t blocks = l1r_launch_blocks(n_lane, n_wave, n_block);
     if (blocks == 0) return hipSuccess;
     if (mode == kNeg) hipLaunchKernelGGL(l1lr_grad_kernel<true>, dim3(blocks), dim3(kTrainThreads), 0, st, P, cols, n_lane, n_wave, n_block);
     else if (mode == kGrad) hipLaunchKernelGGL(l1lr_grad_kernel<false>, dim3(blocks), dim3(kTrainThreads), 0, st, P, cols, n_lane, n_wave, n_block);

@@ -6,72 +6,30 @@
 // (tag_rows_kernel: a row's columns are distinct), so v = y_i and xj_sq = C * the column's length.
 //
 // A sweep: the problem's groups (capi_train.cpp, l1r_groups over the problem's keys: a template's columns share no row, the bias alone
-// and last) in a new Fisher-Yates order (thread 0 draws it, LDS hands it on), and for each group its columns dealt by length: a lane
-// takes the columns of at most kL1rLaneMax nonzeros, a wave those of at most kL1rWaveMax, the workgroup the longer ones and the bias;
-// then the workgroup meets.  No column of a group reads a b[i] that another one writes, and there is no atomic on a double anywhere.
+// and last) in a new Fisher-Yates order (thread 0 draws it, LDS hands it on), and for each group its columns dealt by length
+// (l1r_team.h, tag_l1_deal); then the workgroup meets.  No column of a group reads a b[i] that another one writes, and there is no
+// atomic on a double anywhere.
 //
-// Summation rule: kernels_train_l1.hip's -- tiles of 64 nonzeros in index order, tile sums 64 at a time, level by level -- so a
-// column's sums have the bits the group launches give them.  The sweep's violation sum has the shape of the host driver's (dot_kernel
-// of kernels_train.hip: tiles of 4096, a thread its sixteen strided values in order, a halving tree over the 256), so both paths stop
-// at the same sweep.
+// The column team and its summation rule, the LDS behind w and b and the sums over a vector are l1r_team.h's: a column's sums have the
+// bits the group launches give them, and the sweep's violation sum has the shape of the host driver's, so both paths stop at the same
+// sweep.
 #include "kernels.hpp"
 
 #include <cmath>
 
 #include "device_common.h"
 #include "l1r.h"
+#include "l1r_team.h"
 #include "tron.h"
 
 namespace vpt {
 namespace {
 
 constexpr uint32_t kT = kTrainThreads;
-constexpr uint32_t kWaves = kT / 64;
-constexpr uint32_t kTileNz = 64;                            // the summation rule's tile
-constexpr uint32_t kWaveTiles = kL1rWaveMax / kTileNz;      // tile sums of a wave's column
-// the LDS behind w and b, in doubles: [0, kRedDoubles) the workgroup's level sums (a column has at most kTagL1LdsDoubles rows) or the
-// tree of the sums over a vector; then the waves' tile sums; then the groups' order and the halvings
-constexpr uint32_t kBlkTiles0 = (kTagL1LdsDoubles + kTileNz - 1) / kTileNz, kBlkTiles1 = (kBlkTiles0 + kTileNz - 1) / kTileNz;
-constexpr uint32_t kRedDoubles = 264;
-constexpr uint32_t kWaveDoubles = 2 * kWaves * (kWaveTiles + 1);
-constexpr uint32_t kOrderDoubles = kTagL1MaxGroups / 2 + 8;
-constexpr uint32_t kLdsDoubles = kTagL1LdsDoubles + kRedDoubles + kWaveDoubles + kOrderDoubles;
-static_assert(kT == 256 && kL1rLaneMax == kTileNz && kWaveTiles <= 64, "a lane takes one tile, a wave's second level is one sum");
-static_assert(2 * (kBlkTiles0 + kBlkTiles1) <= kRedDoubles && kT + 2 <= kRedDoubles && kBlkTiles1 <= kTileNz, "the level sums and the tree share a place");
-static_assert(kTagL1LdsDoubles <= 2 * 16 * kT, "a vector is at most two tiles of the tree");
-static_assert(kLdsDoubles * 8 <= 61568, "the static LDS array of tag_solve_kernel is the budget");
 
-__device__ __forceinline__ void wave_rendezvous() {
-#ifndef VPT_HIPEMU
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-    __builtin_amdgcn_wave_barrier();
-}
-
-// the sum of f(0) .. f(n - 1) in the shape of dot_kernel and its second level; the same bits in every thread.  red: kT + 2 doubles
+// solver 5's sums over a vector: their terms are not rounded first (l1r_team.h)
 template <typename F>
-__device__ double vec_sum(uint32_t n, F f, double* red) {
-    const uint32_t t = threadIdx.x, m = (n + 16 * kT - 1) / (16 * kT);
-    for (uint32_t tile = 0; tile < m; ++tile) {
-        double s = 0;
-        for (uint32_t k = 0; k < 16; ++k) {
-            const uint32_t i = tile * 16 * kT + k * kT + t;
-            if (i < n) s += f(i);
-        }
-        red[t] = s;
-        __syncthreads();
-        for (uint32_t h = kT / 2; h > 0; h >>= 1) {
-            if (t < h) red[t] += red[t + h];
-            __syncthreads();
-        }
-        if (t == 0) red[kT + tile] = red[0];
-        __syncthreads();
-    }
-    // the partials are a tile of their own: the zeros beside them add nothing
-    const double r = m > 1 ? red[kT] + red[kT + 1] : red[kT];
-    __syncthreads();   // the next sum writes red again
-    return r;
-}
+__device__ double vec_sum(uint32_t n, F f, double* red) { return tag_l1_vec_sum<false>(n, f, red); }
 
 struct Prob {
     const uint32_t *rp, *cols, *cp, *crow, *y;
@@ -81,52 +39,22 @@ struct Prob {
     __device__ __forceinline__ double target(uint32_t r) const { return y[r] == cls ? 1.0 : -1.0; }
 };
 
-// l1r.h's backend for a team of kN threads (1: a lane, 64: a wave, 256: the workgroup) over one column: nonzeros a .. a + n of the
-// CSC, or rows 0 .. n for the bias
+// l1r.h's backend for a team of kN threads over one column: nonzeros a .. a + n of the CSC, or rows 0 .. n for the bias
 template <uint32_t kN>
 struct Team {
     const Prob& P;
-    uint32_t a, n;
+    uint32_t a;
     bool bias;
-    uint32_t t;
-    L1rPair *s0, *s1;
+    L1rTeam<kN, uint32_t> tm;
 
-    __device__ __forceinline__ void sync() const {
-        if constexpr (kN == 64) wave_rendezvous();
-        else if constexpr (kN > 64) __syncthreads();
-    }
+    __device__ __forceinline__ uint32_t row(uint32_t k) const { return bias ? k : P.crow[a + k]; }
+    // f(b, v) over the column's nonzeros
     template <typename F>
-    __device__ __forceinline__ L1rPair tile(uint32_t k0, F f) const {
-        const uint32_t k1 = k0 + kTileNz < n ? k0 + kTileNz : n;
-        L1rPair acc{0.0, 0.0};
-        for (uint32_t k = k0; k < k1; ++k) {
-            const uint32_t row = bias ? k : P.crow[a + k];
-            acc = l1r_add(acc, f(P.b[row], P.target(row)));
-        }
-        return acc;
-    }
-    template <typename F>
-    __device__ L1rPair sums(F f) const {
-        if constexpr (kN == 1) return tile(0, f);
-        uint32_t m = (n + kTileNz - 1) / kTileNz;
-        for (uint32_t i = t; i < m; i += kN) s0[i] = tile(i * kTileNz, f);
-        sync();
-        L1rPair *src = s0, *dst = s1;
-        while (m > 1) {
-            const uint32_t g = (m + kTileNz - 1) / kTileNz;
-            for (uint32_t i = t; i < g; i += kN) {
-                const uint32_t q1 = (i + 1) * kTileNz < m ? (i + 1) * kTileNz : m;
-                L1rPair acc{0.0, 0.0};
-                for (uint32_t q = i * kTileNz; q < q1; ++q) acc = l1r_add(acc, src[q]);
-                dst[i] = acc;
-            }
-            sync();
-            L1rPair* tmp = src; src = dst; dst = tmp;
-            m = g;
-        }
-        const L1rPair r = src[0];
-        sync();   // the next pass writes the buffers again
-        return r;
+    __device__ __forceinline__ L1rPair sums(F f) const {
+        return tm.sums([this, f](uint32_t k) {
+            const uint32_t r = row(k);
+            return f(P.b[r], P.target(r));
+        });
     }
     __device__ L1rPair grad_sums() const {
         const double c = P.c;
@@ -137,10 +65,10 @@ struct Team {
         return sums([c, d](double b, double v) { return l1r_loss_term(b, v, c, d); });
     }
     __device__ void commit(double d) const {
-        for (uint32_t k = t; k < n; k += kN) {
-            const uint32_t row = bias ? k : P.crow[a + k];
-            P.b[row] = P.b[row] - d * P.target(row);
-        }
+        tm.each([this, d](uint32_t k) {
+            const uint32_t r = row(k);
+            P.b[r] = P.b[r] - d * P.target(r);
+        });
     }
 };
 
@@ -149,7 +77,7 @@ template <uint32_t kN>
 __device__ void column(const Prob& P, uint32_t j, uint32_t t, L1rPair* s0, L1rPair* s1, double* viol, uint32_t* halvings) {
     const bool bias = j == P.nf;
     const uint32_t a = bias ? 0 : P.cp[j], n = bias ? P.l : P.cp[j + 1] - a;
-    const Team<kN> be{P, a, n, bias, t, s0, s1};
+    const Team<kN> be{P, a, bias, {n, t, s0, s1}};
     const double w = P.w[j];
     const L1rStep s = l1r_column(be, w, P.c * double(n));
     if (t != 0) return;
@@ -162,19 +90,17 @@ __global__ __launch_bounds__(kT) void tag_l1_solve_kernel(const TagSolveDesc* de
                                                           const uint32_t* cp, const uint32_t* crow, const uint32_t* y, const uint32_t* gcols,
                                                           const TagL1Group* groups, double eps, double c, double* viol_all, double* w_out,
                                                           vpt_train_stats* stats) {
-    __shared__ double lds[kLdsDoubles];
+    __shared__ double lds[kTagL1Doubles];
     const TagSolveDesc D = descs[blockIdx.x];
     const TagL1Desc E = l1descs[blockIdx.x];
-    const uint32_t n = D.nf + 1, l = D.l, t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t n = D.nf + 1, l = D.l, t = threadIdx.x;
     if (uint64_t(n) + l > kTagL1LdsDoubles || E.n_groups > kTagL1MaxGroups) return;   // the host sends such a problem down the other path
     Prob P;
     P.rp = rp + D.rp; P.cols = cols + D.cols; P.cp = cp + D.cp; P.crow = crow + D.cols; P.y = y + D.y;
     P.nf = D.nf; P.l = l; P.c = c; P.w = lds; P.b = lds + n;
-    double* const red = lds + kTagL1LdsDoubles;
-    L1rPair* const blk0 = reinterpret_cast<L1rPair*>(red);
-    L1rPair* const blk1 = blk0 + kBlkTiles0;
-    L1rPair* const wv0 = reinterpret_cast<L1rPair*>(red + kRedDoubles) + wave * (kWaveTiles + 1);
-    uint32_t* const order = reinterpret_cast<uint32_t*>(red + kRedDoubles + kWaveDoubles);
+    const TagL1Lds L = tag_l1_lds(lds);
+    double* const red = L.red;
+    uint32_t* const order = L.order;
     uint32_t* const halvings = order + kTagL1MaxGroups;
     const uint32_t* const gc = gcols + E.gcols;
     const TagL1Group* const gr = groups + E.groups;
@@ -196,10 +122,7 @@ __global__ __launch_bounds__(kT) void tag_l1_solve_kernel(const TagSolveDesc* de
             __syncthreads();
             for (uint32_t q = 0; q < E.n_groups; ++q) {
                 const TagL1Group G = gr[order[q]];
-                const uint32_t* const cj = gc + G.at;
-                for (uint32_t i = t; i < G.n_lane; i += kT) column<1>(P, cj[i], 0, nullptr, nullptr, viol, halvings);
-                for (uint32_t i = wave; i < G.n_wave; i += kWaves) column<64>(P, cj[G.n_lane + i], lane, wv0, wv0 + kWaveTiles, viol, halvings);
-                for (uint32_t i = G.n_lane + G.n_wave; i < G.n; ++i) column<kT>(P, cj[i], t, blk0, blk1, viol, halvings);
+                tag_l1_deal(G, gc + G.at, L, [&](auto kN, uint32_t j, uint32_t tt, L1rPair* s0, L1rPair* s1) { column<kN>(P, j, tt, s0, s1, viol, halvings); });
                 __syncthreads();
             }
             v = vec_sum(n, [&](uint32_t i) { return viol[i]; }, red);

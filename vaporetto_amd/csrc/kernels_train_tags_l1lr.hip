@@ -12,17 +12,15 @@
 // (tag_rows_kernel: a row's columns are distinct) and y comes from the tag id.
 //
 // A sweep (cd_group): the problem's groups (capi_train.cpp, l1r_groups over the problem's keys: a template's columns share no row, the
-// bias alone and last) in a new order, and for each group its columns dealt by length: a lane takes the columns of at most
-// kL1rLaneMax nonzeros, a wave those of at most kL1rWaveMax, the workgroup the longer ones and the bias; then the workgroup meets.  The
-// header would have every thread permute the order; here it is handed one group -- the whole sweep -- which it cannot permute and for
-// which it draws nothing, and thread 0 alone runs l1r_shuffle over the real groups in LDS from the backend's own state, kL1rSeed at
+// bias alone and last) in a new order, and for each group its columns dealt by length (l1r_team.h, tag_l1_deal); then the workgroup
+// meets.  The header would have every thread permute the order; here it is handed one group -- the whole sweep -- which it cannot
+// permute and for which it draws nothing, and thread 0 alone runs l1r_shuffle over the real groups in LDS from the backend's own state, kL1rSeed at
 // setup and carried across sweeps and Newton iterations: the draws and the orders are those the global-memory driver gets.  grad() and
 // setup()'s xjneg_sum deal all columns at once, as the one launch over all columns does: they write nothing that a column reads.
 //
-// Summation rule: kernels_train_l1.hip's -- tiles of 64 nonzeros in index order, tile sums 64 at a time, level by level -- so a
-// column's sums have the bits the group launches give them.  Sums over rows or features have the shape of the host driver's
-// (dot_kernel of kernels_train.hip and its second level: tiles of 4096, a thread its sixteen strided values in order, a halving tree
-// over the 256); their terms are rounded before they are added, as the driver's term kernels store them.  No atomic on a double.
+// The column team and its summation rule, the LDS behind the problem's vectors and the sums over rows or features are l1r_team.h's: a
+// column's sums have the bits the group launches give them, and a sum over a vector has the shape of the host driver's; its terms are
+// rounded before they are added, as the driver's term kernels store them.  No atomic on a double.
 // A sum that is not finite clears `fine`, and ok() ends every loop of the header.
 #include "kernels.hpp"
 
@@ -30,66 +28,17 @@
 
 #include "device_common.h"
 #include "l1r_lr.h"
+#include "l1r_team.h"
 #include "tron.h"
 
 namespace vpt {
 namespace {
 
 constexpr uint32_t kT = kTrainThreads;
-constexpr uint32_t kWaves = kT / 64;
-constexpr uint32_t kTileNz = 64;                            // the summation rule's tile
-constexpr uint32_t kWaveTiles = kL1rWaveMax / kTileNz;      // tile sums of a wave's column
-// the LDS behind the problem's vectors, in doubles, as kernels_train_tags_l1.hip lays it out: [0, kRedDoubles) the workgroup's level
-// sums (a column has fewer than kTagL1LdsDoubles rows) or the tree of the sums over a vector; then the waves' tile sums; then the
-// groups' order
-constexpr uint32_t kBlkTiles0 = (kTagL1LdsDoubles + kTileNz - 1) / kTileNz, kBlkTiles1 = (kBlkTiles0 + kTileNz - 1) / kTileNz;
-constexpr uint32_t kRedDoubles = 264;
-constexpr uint32_t kWaveDoubles = 2 * kWaves * (kWaveTiles + 1);
-constexpr uint32_t kOrderDoubles = kTagL1MaxGroups / 2 + 8;
-constexpr uint32_t kLdsDoubles = kTagL1LdsDoubles + kRedDoubles + kWaveDoubles + kOrderDoubles;
-static_assert(kT == 256 && kL1rLaneMax == kTileNz && kWaveTiles <= 64, "a lane takes one tile, a wave's second level is one sum");
-static_assert(2 * (kBlkTiles0 + kBlkTiles1) <= kRedDoubles && kT + 2 <= kRedDoubles && kBlkTiles1 <= kTileNz, "the level sums and the tree share a place");
-static_assert(kTagL1LdsDoubles <= 2 * 16 * kT, "a vector is at most two tiles of the tree");
-static_assert(kLdsDoubles * 8 <= 61568, "the static LDS array of tag_solve_kernel is the budget");
 
-__device__ __forceinline__ void wave_rendezvous() {
-#ifndef VPT_HIPEMU
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-    __builtin_amdgcn_wave_barrier();
-}
-
-// s + v with v rounded first: never fused with the product that made v
-__device__ __forceinline__ double add_rounded(double s, double v) {
-#pragma clang fp contract(off)
-    return s + v;
-}
-
-// the sum of f(0) .. f(n - 1) in the shape of dot_kernel and its second level; the same bits in every thread.  red: kT + 2 doubles.
-// The caller has met since f's inputs were written.
+// solver 6's sums over a vector: a term is rounded before it is added, as the host driver's term kernels store it (l1r_team.h)
 template <typename F>
-__device__ double vec_sum(uint32_t n, F f, double* red) {
-    const uint32_t t = threadIdx.x, m = (n + 16 * kT - 1) / (16 * kT);
-    for (uint32_t tile = 0; tile < m; ++tile) {
-        double s = 0;
-        for (uint32_t k = 0; k < 16; ++k) {
-            const uint32_t i = tile * 16 * kT + k * kT + t;
-            if (i < n) s = add_rounded(s, f(i));
-        }
-        red[t] = s;
-        __syncthreads();
-        for (uint32_t h = kT / 2; h > 0; h >>= 1) {
-            if (t < h) red[t] += red[t + h];
-            __syncthreads();
-        }
-        if (t == 0) red[kT + tile] = red[0];
-        __syncthreads();
-    }
-    // the partials are a tile of their own: the zeros beside them add nothing
-    const double r = m > 1 ? red[kT] + red[kT + 1] : red[kT];
-    __syncthreads();   // the next sum writes red again
-    return r;
-}
+__device__ double vec_sum(uint32_t n, F f, double* red) { return tag_l1_vec_sum<true>(n, f, red); }
 
 struct Prob {
     const uint32_t *rp, *cols, *cp, *crow, *y;
@@ -100,56 +49,26 @@ struct Prob {
     __device__ __forceinline__ double target(uint32_t r) const { return y[r] == cls ? 1.0 : -1.0; }
 };
 
-// a team of kN threads (1: a lane, 64: a wave, 256: the workgroup) over one column: nonzeros a .. a + n of the CSC, or rows 0 .. n for
-// the bias
+// a team of kN threads over one column: nonzeros a .. a + n of the CSC, or rows 0 .. n for the bias
 template <uint32_t kN>
 struct Team {
     const Prob& P;
-    uint32_t a, n;
+    uint32_t a;
     bool bias;
-    uint32_t t;
-    L1rPair *s0, *s1;
+    L1rTeam<kN, uint32_t> tm;
 
-    __device__ __forceinline__ void sync() const {
-        if constexpr (kN == 64) wave_rendezvous();
-        else if constexpr (kN > 64) __syncthreads();
-    }
+    __device__ __forceinline__ uint32_t row(uint32_t k) const { return bias ? k : P.crow[a + k]; }
+    // f(row) over the column's nonzeros
     template <typename F>
-    __device__ __forceinline__ L1rPair tile(uint32_t k0, F f) const {
-        const uint32_t k1 = k0 + kTileNz < n ? k0 + kTileNz : n;
-        L1rPair acc{0.0, 0.0};
-        for (uint32_t k = k0; k < k1; ++k) acc = l1r_add(acc, f(bias ? k : P.crow[a + k]));
-        return acc;
-    }
-    template <typename F>
-    __device__ L1rPair sums(F f) const {
-        if constexpr (kN == 1) return tile(0, f);
-        uint32_t m = (n + kTileNz - 1) / kTileNz;
-        for (uint32_t i = t; i < m; i += kN) s0[i] = tile(i * kTileNz, f);
-        sync();
-        L1rPair *src = s0, *dst = s1;
-        while (m > 1) {
-            const uint32_t g = (m + kTileNz - 1) / kTileNz;
-            for (uint32_t i = t; i < g; i += kN) {
-                const uint32_t q1 = (i + 1) * kTileNz < m ? (i + 1) * kTileNz : m;
-                L1rPair acc{0.0, 0.0};
-                for (uint32_t q = i * kTileNz; q < q1; ++q) acc = l1r_add(acc, src[q]);
-                dst[i] = acc;
-            }
-            sync();
-            L1rPair* tmp = src; src = dst; dst = tmp;
-            m = g;
-        }
-        const L1rPair r = src[0];
-        sync();   // the next pass writes the buffers again
-        return r;
+    __device__ __forceinline__ L1rPair sums(F f) const {
+        return tm.sums([this, f](uint32_t k) { return f(row(k)); });
     }
     // xTd_i += z over the column: its rows are distinct, and no other column of the group has them
     __device__ void add_xTd(double z) const {
-        for (uint32_t k = t; k < n; k += kN) {
-            const uint32_t row = bias ? k : P.crow[a + k];
-            P.xTd[row] = P.xTd[row] + z * 1.0;
-        }
+        tm.each([this, z](uint32_t k) {
+            const uint32_t r = row(k);
+            P.xTd[r] = P.xTd[r] + z * 1.0;
+        });
     }
 };
 
@@ -161,7 +80,7 @@ template <uint32_t kN, int kMode>
 __device__ void column(const Prob& P, uint32_t j, uint32_t t, L1rPair* s0, L1rPair* s1) {
     const bool bias = j == P.nf;
     const uint32_t a = bias ? 0 : P.cp[j], n = bias ? P.l : P.cp[j + 1] - a;
-    const Team<kN> be{P, a, n, bias, t, s0, s1};
+    const Team<kN> be{P, a, bias, {n, t, s0, s1}};
     if constexpr (kMode == kNeg) {
         const L1rPair s = be.sums([&P](uint32_t row) { return l1lr_neg_term(1.0, P.target(row), P.c); });
         if (t == 0) P.xjneg[j] = s.a;
@@ -191,20 +110,13 @@ struct Solver {
     const TagL1Group* gr;      // the problem's groups and their columns
     const uint32_t* gc;
     uint32_t n_groups, n, t;   // n = features + 1
-    double* red;
-    L1rPair *blk0, *blk1, *wv0;
-    uint32_t* order;           // LDS: the groups' order, permuted by thread 0
+    TagL1Lds L;                // L.order: the groups' order, permuted by thread 0
     uint64_t rng;
     bool fine;
 
-    // a group's columns by length class; every thread comes through every workgroup column
     template <int kMode>
     __device__ __forceinline__ void deal(const TagL1Group& G) {
-        const uint32_t wave = t >> 6, lane = t & 63u;
-        const uint32_t* const cj = gc + G.at;
-        for (uint32_t i = t; i < G.n_lane; i += kT) column<1, kMode>(P, cj[i], 0, nullptr, nullptr);
-        for (uint32_t i = wave; i < G.n_wave; i += kWaves) column<64, kMode>(P, cj[G.n_lane + i], lane, wv0, wv0 + kWaveTiles);
-        for (uint32_t i = G.n_lane + G.n_wave; i < G.n; ++i) column<kT, kMode>(P, cj[i], t, blk0, blk1);
+        tag_l1_deal(G, gc + G.at, L, [this](auto kN, uint32_t j, uint32_t tt, L1rPair* s0, L1rPair* s1) { column<kN, kMode>(P, j, tt, s0, s1); });
     }
     template <int kMode>
     __device__ void all_columns() {
@@ -221,7 +133,7 @@ struct Solver {
         const L1lrRow r = l1lr_accept_row(1.0, 0.0, P.c);
         for (uint32_t j = t; j < n; j += kT) { P.w[j] = 0; P.wpd[j] = 0; }
         for (uint32_t i = t; i < P.l; i += kT) { P.xTd[i] = 0; P.e[i] = r.e; P.tau[i] = r.tau; P.D[i] = r.D; }
-        if (t < n_groups) order[t] = t;
+        if (t < n_groups) L.order[t] = t;
         rng = kL1rSeed;
         fine = true;
         __syncthreads();
@@ -229,7 +141,7 @@ struct Solver {
     }
     __device__ double grad() {
         all_columns<kGrad>();
-        return seen(vec_sum(n, [this](uint32_t j) { return P.viol[j]; }, red));
+        return seen(vec_sum(n, [this](uint32_t j) { return P.viol[j]; }, L.red));
     }
     __device__ void qp_start() {
         for (uint32_t i = t; i < P.l; i += kT) P.xTd[i] = 0;
@@ -237,24 +149,24 @@ struct Solver {
     }
     // the one group the header knows is the whole sweep
     __device__ void cd_group(uint32_t) {
-        if (t == 0) l1r_shuffle(order, n_groups, &rng);
+        if (t == 0) l1r_shuffle(L.order, n_groups, &rng);
         __syncthreads();
         for (uint32_t q = 0; q < n_groups; ++q) {
-            deal<kCd>(gr[order[q]]);
+            deal<kCd>(gr[L.order[q]]);
             __syncthreads();
         }
     }
     __device__ double qp_violation() {
-        return seen(vec_sum(n, [this](uint32_t j) { return P.viol[j]; }, red));
+        return seen(vec_sum(n, [this](uint32_t j) { return P.viol[j]; }, L.red));
     }
     __device__ L1lrSums direction_sums() {
-        const double delta = vec_sum(n, [this](uint32_t j) { return P.grad[j] * (P.wpd[j] - P.w[j]); }, red);
-        const double norm1 = vec_sum(n, [this](uint32_t j) { return fabs(P.wpd[j]); }, red);
-        const double neg = vec_sum(P.l, [this](uint32_t i) { return P.target(i) < 0 ? P.c * P.xTd[i] : 0.0; }, red);
+        const double delta = vec_sum(n, [this](uint32_t j) { return P.grad[j] * (P.wpd[j] - P.w[j]); }, L.red);
+        const double norm1 = vec_sum(n, [this](uint32_t j) { return fabs(P.wpd[j]); }, L.red);
+        const double neg = vec_sum(P.l, [this](uint32_t i) { return P.target(i) < 0 ? P.c * P.xTd[i] : 0.0; }, L.red);
         return {seen(delta), seen(norm1), seen(neg)};
     }
     __device__ double linesearch_loss() {
-        return seen(vec_sum(P.l, [this](uint32_t i) { return l1lr_ls_term(P.e[i], P.xTd[i], P.c); }, red));
+        return seen(vec_sum(P.l, [this](uint32_t i) { return l1lr_ls_term(P.e[i], P.xTd[i], P.c); }, L.red));
     }
     __device__ void accept() {
         for (uint32_t j = t; j < n; j += kT) P.w[j] = P.wpd[j];
@@ -268,7 +180,7 @@ struct Solver {
         for (uint32_t j = t; j < n; j += kT) P.wpd[j] = (P.w[j] + P.wpd[j]) * 0.5;
         for (uint32_t i = t; i < P.l; i += kT) P.xTd[i] = P.xTd[i] * 0.5;
         __syncthreads();
-        return seen(vec_sum(n, [this](uint32_t j) { return fabs(P.wpd[j]); }, red));
+        return seen(vec_sum(n, [this](uint32_t j) { return fabs(P.wpd[j]); }, L.red));
     }
     // w.x of row r through the CSR, the bias last: train_xv's order
     __device__ __forceinline__ double wx(uint32_t r) const {
@@ -287,12 +199,11 @@ __global__ __launch_bounds__(kT) void tag_l1lr_solve_kernel(const TagSolveDesc* 
                                                             const uint32_t* cp, const uint32_t* crow, const uint32_t* y, const uint32_t* gcols,
                                                             const TagL1Group* groups, double eps, double c, double* scratch, double* w_out,
                                                             vpt_train_stats* stats) {
-    __shared__ double lds[kLdsDoubles];
+    __shared__ double lds[kTagL1Doubles];
     const TagSolveDesc D = descs[blockIdx.x];
     const TagL1Desc E = l1descs[blockIdx.x];
     const uint32_t n = D.nf + 1, l = D.l, t = threadIdx.x;
     if (3 * uint64_t(l) + n > kTagL1LdsDoubles || E.n_groups > kTagL1MaxGroups) return;   // the host sends such a problem down the other path
-    double* const red = lds + kTagL1LdsDoubles;
     double* const scr = scratch + E.viol;
     Solver S;
     Prob& P = S.P;
@@ -301,11 +212,8 @@ __global__ __launch_bounds__(kT) void tag_l1lr_solve_kernel(const TagSolveDesc* 
     P.wpd = lds; P.tau = lds + n; P.D = P.tau + l; P.xTd = P.D + l;
     P.viol = scr; P.grad = scr + n; P.hdiag = scr + 2 * uint64_t(n); P.xjneg = scr + 3 * uint64_t(n); P.e = scr + 4 * uint64_t(n);
     S.gr = groups + E.groups; S.gc = gcols + E.gcols; S.n_groups = E.n_groups; S.n = n; S.t = t;
-    S.red = red;
-    S.blk0 = reinterpret_cast<L1rPair*>(red);
-    S.blk1 = S.blk0 + kBlkTiles0;
-    S.wv0 = reinterpret_cast<L1rPair*>(red + kRedDoubles) + (t >> 6) * (kWaveTiles + 1);
-    S.order = reinterpret_cast<uint32_t*>(red + kRedDoubles + kWaveDoubles);
+    S.L = tag_l1_lds(lds);
+    double* const red = S.L.red;
     const uint32_t n_solve = D.k == 2 ? 1 : D.k;
     for (uint32_t cls = 0; cls < n_solve; ++cls) {
         P.cls = cls;
