@@ -407,6 +407,95 @@ impl Drop for Vocabulary<'_> {
     }
 }
 
+/// A vocabulary counter (`vpt_vocab_counter_create`): token surface -> count, accumulated on the predictor's device; `finish` is what
+/// `Vocabulary::new` takes.  Tied to ONE predictor (it borrows it).  The handle is mutable and takes one call at a time: the methods that
+/// count take `&mut self`, and the type is `Send` but not `Sync`.
+pub struct VocabularyCounter<'p> {
+    raw: *mut std::ffi::c_void,
+    predictor: &'p HipPredictor,
+}
+unsafe impl Send for VocabularyCounter<'_> {}
+
+/// `vpt_vocab_counter_info`.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct VocabularyCounterInfo {
+    pub n_keys: u64,
+    pub n_counted: u64,
+    pub n_skipped: u64,
+    pub n_slots: u32,
+    pub full: bool,
+}
+
+impl<'p> VocabularyCounter<'p> {
+    /// `max_keys`: 1 ..= 2^24 distinct surfaces; `max_surface_chars`: 1 ..= 2^24, a longer token is skipped; `arena_chars`: the code points
+    /// kept over all keys, 0 = 8 * max_keys, below 2^32.  Checked here before anything is handed to C.
+    pub fn new(predictor: &'p HipPredictor, max_keys: u64, max_surface_chars: u64, arena_chars: u64) -> Result<Self> {
+        if max_keys < 1 || max_keys > 1 << 24 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: max_keys: must be between 1 and 2^24".into()));
+        }
+        if max_surface_chars < 1 || max_surface_chars > 1 << 24 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: max_surface_chars: must be between 1 and 2^24".into()));
+        }
+        if arena_chars > 0xFFFF_FFF0 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: arena_chars: must be below 2^32".into()));
+        }
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ffi::vpt_vocab_counter_create(predictor.raw, max_keys, max_surface_chars, arena_chars, &mut raw) })?;
+        Ok(Self { raw, predictor })
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { ffi::vpt_vocab_counter_reset(self.raw) })
+    }
+
+    pub fn info(&mut self) -> Result<VocabularyCounterInfo> {
+        let (mut k, mut c, mut s, mut n, mut f) = (0u64, 0u64, 0u64, 0u32, 0u32);
+        check(unsafe { ffi::vpt_vocab_counter_info(self.raw, &mut k, &mut c, &mut s, &mut n, &mut f) })?;
+        Ok(VocabularyCounterInfo { n_keys: k, n_counted: c, n_skipped: s, n_slots: n, full: f != 0 })
+    }
+
+    /// Every token of a packed batch of documents through the untagged stream's steps into the counter (`vpt_token_stream_count_batch`);
+    /// `normalize` counts the KyteaFullwidthFilter image of a token, else the caller's bytes.  `byte_offsets` must be non-decreasing, start
+    /// inside `utf8` and end at most at its length: checked here.
+    pub fn count_batch(&mut self, utf8: &[u8], byte_offsets: &[u64], wsconst_flags: u32, normalize: bool) -> Result<()> {
+        let n = byte_offsets.len().saturating_sub(1);
+        if n == 0 {
+            return Ok(());
+        }
+        if byte_offsets.windows(2).any(|w| w[0] > w[1]) || byte_offsets[n] > utf8.len() as u64 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: byte_offsets: must be non-decreasing and inside the text".into()));
+        }
+        let text = if utf8.is_empty() { &[0u8][..] } else { utf8 };
+        check(unsafe {
+            ffi::vpt_token_stream_count_batch(self.predictor.raw, text.as_ptr(), byte_offsets.as_ptr(), n, wsconst_flags, std::ptr::null(),
+                                              std::ptr::null(), self.raw, if normalize { 1 } else { 0 })
+        })
+    }
+
+    /// A snapshot (`vpt_vocab_counter_finish`): (surface, count) of the keys of count >= `min_count`, by count descending, then by code
+    /// points ascending; the first `max_entries` of them (0: all).
+    pub fn finish(&mut self, min_count: u64, max_entries: u64) -> Result<Vec<(String, u64)>> {
+        let (mut s, mut off, mut cnt, mut n) = (std::ptr::null::<u8>(), std::ptr::null::<u64>(), std::ptr::null::<u64>(), 0usize);
+        check(unsafe { ffi::vpt_vocab_counter_finish(self.raw, min_count, max_entries, &mut s, &mut off, &mut cnt, &mut n) })?;
+        let mut out = Vec::with_capacity(n);
+        if n == 0 {
+            return Ok(out);
+        }
+        let (off, cnt) = unsafe { (std::slice::from_raw_parts(off, n + 1), std::slice::from_raw_parts(cnt, n)) };
+        let bytes = unsafe { std::slice::from_raw_parts(s, off[n] as usize) };
+        for k in 0..n {
+            out.push((String::from_utf8_lossy(&bytes[off[k] as usize..off[k + 1] as usize]).into_owned(), cnt[k]));
+        }
+        Ok(out)
+    }
+}
+
+impl Drop for VocabularyCounter<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::vpt_vocab_counter_destroy(self.raw) }
+    }
+}
+
 /// What `HipPredictor::token_stream_tagged_batch` returns, over the KEPT tokens: document i owns entries `offsets[i] .. offsets[i + 1]`;
 /// `starts` / `ends` are a token's `offset_from` / `offset_to` from its document's first byte, `positions` its index in the document BEFORE
 /// filtering, `tags[token * n_tags + slot]` an id of `tag_strings()` (>= 0), -1 (`None`) or -(2 + id) (a rule tag of the tagger).

@@ -8,6 +8,9 @@
 //   ./token_stream model.bin wsconst --vocab vocab.txt < documents.txt
 // With --vocab (beyond the adapter): vocab.txt holds one surface per line, line k is id k; one line per token: doc <TAB> index <TAB> id, the id of
 // the token's surface (of the text as it was scored: through KyteaFullwidthFilter) or -1 -- looked up on the device, no token text comes back.
+//   ./token_stream model.bin wsconst --build-vocab [min_count] < documents.txt
+// With --build-vocab (beyond the adapter): the documents' token surfaces (of the text as it was scored) are counted on the device; one line per
+// surface of count >= min_count: count <TAB> surface, most frequent first -- the second column is a vocab.txt for --vocab.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -55,6 +58,16 @@ int main(int argc, char** argv) {
             for (size_t d = 0; d < docs.size(); ++d)
                 for (uint64_t k = enc.first[d]; k < enc.first[d + 1]; ++k)
                     std::printf("%zu\t%zu\t%d\n", d, size_t(k - enc.first[d]), int(enc.second[size_t(k)]));
+            return 0;
+        }
+        if (argc > 3 && std::strcmp(argv[3], "--build-vocab") == 0) {
+            vaporetto_hip::VaporettoTokenizer plain(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argv[2]);
+            vaporetto_hip::VocabularyCounter counter(plain.predictor(), uint64_t(1) << 20);
+            std::vector<std::string> docs;
+            for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
+            plain.count(docs, counter);
+            for (const auto& e : counter.entries(argc > 4 ? std::strtoull(argv[4], nullptr, 10) : 1))
+                std::printf("%llu\t%s\n", static_cast<unsigned long long>(e.second), e.first.c_str());
             return 0;
         }
         vaporetto_hip::VaporettoTokenizer tokenizer(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argc > 2 ? argv[2] : "");

@@ -559,6 +559,50 @@ vpt_status vpt_token_stream_ids_batch(const vpt_predictor *p, const uint8_t *utf
                                       uint64_t *token_offsets_out, uint32_t *token_starts_out, uint32_t *token_ends_out,
                                       uint32_t *token_positions_out, int32_t *token_tags_out, int32_t *token_ids_out, uint64_t capacity);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Build a vocabulary on the device: count token surfaces over a corpus          (no item of the adapter: the dict over Token::text that a caller
+ *                                                      fills on the host before it can make the vocabulary above -- here the strings stay on the device)
+ *
+ * vpt_vocab_counter_create: an accumulating table token surface -> 64-bit count on the predictor's device, tied to that predictor.  max_keys
+ *   (1 .. 2^24): the distinct surfaces it can hold; it has n_slots = the smallest power of two >= 2 * max_keys slots.  max_surface_chars (>= 1):
+ *   a longer token is skipped.  arena_chars: the code points it can keep over all keys, 0 = 8 * max_keys.  One device allocation.
+ *   THE HANDLE IS MUTABLE, unlike a vocabulary: only one call may be in flight on it at a time, in stream order -- a count call on another
+ *   stream, or a host call below, while one is running is the caller's error.  vpt_vocab_counter_destroy frees it (after the stream of the last
+ *   count call is through); vpt_vocab_counter_reset empties it.
+ * vpt_vocab_counter_info: distinct keys, tokens counted, tokens skipped, slots, and whether it is full.  Synchronises the last count call's stream.
+ * vpt_vocab_count_batch_device: counts the tokens of a FINISHED span CSR -- the arrays, conventions and flags of vpt_token_ids_batch_device
+ *   (d_token_starts == NULL or the filter's starts, documents that own no token, capacity_in; flags 0 or VPT_FLAG_KYTEA_FULLWIDTH, any other bit
+ *   VPT_INVALID_ARGUMENT) and its definition of a surface: a vocabulary built with a flag and looked up with the same flag agrees token for token.
+ *   Three launches (kernels_vocab_count.hip), asynchronous on hip_stream, errors at vpt_batch_sync; two uint4 per token of the batch's workspace.
+ *   Not counted, and one more in n_skipped: an empty token, a token that is not strict UTF-8 inside its span, a token of more than
+ *   max_surface_chars chars (one of more than 4 * max_surface_chars bytes is not read).  Every other token adds 1 to its key's count and to
+ *   n_counted.  Counts are integer atomics: the result does not depend on the order of the lanes.  Whatever the device arrays hold, nothing is read
+ *   outside [byte_offsets[0], byte_offsets[n]) of the text and nothing is written outside the counter and the batch's scratch; the id pass's
+ *   conditions are the same VPT_INVALID_ARGUMENT at the sync -- the counter's contents are then unspecified and reset makes it usable again.
+ *   FULL: more than max_keys distinct keys, more than arena_chars code points, or a probe that has seen every slot: a sticky bit, and the sync
+ *   returns VPT_INVALID_ARGUMENT "InvalidArgumentError: vocab counter: full (max_keys / arena_chars)"; later count calls (at the call or at
+ *   their sync) and finish refuse with the same message until reset.  No kernel waits for another lane: every loop is bounded.
+ * vpt_vocab_counter_finish: a snapshot (counting may go on): the keys of count >= min_count, by count descending, then by code points ascending
+ *   -- a total order: two runs give identical bytes --, the first max_entries of them (0: all).  surfaces: UTF-8 (the KyteaFullwidthFilter
+ *   image under that flag, else the caller's chars), entry k at surfaces[offsets[k] .. offsets[k + 1]); offsets [n + 1]; counts [n].  Owned by
+ *   the handle until the next finish, reset or destroy.  Synchronises the last count call's stream.  surfaces, offsets and *n_entries are what
+ *   vpt_vocab_create takes.
+ * vpt_token_stream_count_batch: host buffers in, nothing out: vpt_token_stream_batch's steps when tagger == stop == NULL, else
+ *   vpt_token_stream_tagged_batch's (which need predict_tags); the count call runs on every chunk's finished CSR, on the device, one chunk after
+ *   the other; vocab_flags as `flags` above.  The result does not depend on how the batch is cut into chunks.  Returns when the device is through. */
+vpt_status vpt_vocab_counter_create(const vpt_predictor *p, uint64_t max_keys, uint64_t max_surface_chars, uint64_t arena_chars, void **out);
+void vpt_vocab_counter_destroy(void *counter);
+vpt_status vpt_vocab_counter_reset(void *counter);
+vpt_status vpt_vocab_counter_info(void *counter, uint64_t *n_keys, uint64_t *n_counted, uint64_t *n_skipped, uint32_t *n_slots, uint32_t *full);
+vpt_status vpt_vocab_count_batch_device(const vpt_predictor *p, vpt_batch *b, void *counter, const uint8_t *d_utf8,
+                                        const uint64_t *d_byte_offsets, size_t n_documents, const uint64_t *d_token_offsets,
+                                        const uint32_t *d_token_starts, const uint32_t *d_token_ends, uint64_t capacity_in, unsigned flags,
+                                        void *hip_stream);
+vpt_status vpt_vocab_counter_finish(void *counter, uint64_t min_count, uint64_t max_entries, const uint8_t **surfaces, const uint64_t **offsets,
+                                    const uint64_t **counts, size_t *n_entries);
+vpt_status vpt_token_stream_count_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                        unsigned wsconst_flags, const void *tagger, const void *stop, void *counter, unsigned vocab_flags);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

@@ -306,6 +306,7 @@ private:
     friend class PatternMatchTagger;
     friend class TagStopFilter;
     friend class Vocabulary;
+    friend class VocabularyCounter;
     std::shared_ptr<detail::Shared> raw_;
     bool predict_tags_;
 };
@@ -411,6 +412,46 @@ private:
     std::shared_ptr<detail::Shared> predictor_;
     void* raw_ = nullptr;
     int32_t unk_id_;
+};
+
+// A vocabulary counter (vpt_vocab_counter_create): token surface -> count, accumulated on the predictor's device; entries() is what Vocabulary
+// takes.  max_keys distinct surfaces (1 .. 2^24), tokens of more than max_surface_chars chars are skipped, arena_chars code points over all keys
+// (0: 8 * max_keys).  Tied to ONE predictor, whose handle it keeps alive.  MUTABLE: one call at a time, in stream order.  A counter that has
+// become full throws "vocab counter: full" from count calls and entries() until reset().
+class VocabularyCounter {
+public:
+    struct Info { uint64_t n_keys, n_counted, n_skipped; uint32_t n_slots; bool full; };
+    VocabularyCounter(const Predictor& predictor, uint64_t max_keys, uint64_t max_surface_chars = 64, uint64_t arena_chars = 0) : predictor_(predictor.raw_) {
+        detail::check(vpt_vocab_counter_create(predictor_->raw, max_keys, max_surface_chars, arena_chars, &raw_));
+    }
+    ~VocabularyCounter() { vpt_vocab_counter_destroy(raw_); }
+    VocabularyCounter(const VocabularyCounter&) = delete;
+    VocabularyCounter& operator=(const VocabularyCounter&) = delete;
+    void* raw() const { return raw_; }
+    void reset() { detail::check(vpt_vocab_counter_reset(raw_)); }
+    Info info() const {
+        Info i{};
+        uint32_t full = 0;
+        detail::check(vpt_vocab_counter_info(raw_, &i.n_keys, &i.n_counted, &i.n_skipped, &i.n_slots, &full));
+        i.full = full != 0;
+        return i;
+    }
+    // A snapshot: {surface, count} of the keys of count >= min_count, by count descending, then by code points ascending; the first
+    // max_entries of them (0: all).  Copies of the handle's arrays.
+    std::vector<std::pair<std::string, uint64_t>> entries(uint64_t min_count = 1, uint64_t max_entries = 0) const {
+        const uint8_t* s = nullptr;
+        const uint64_t *off = nullptr, *cnt = nullptr;
+        size_t n = 0;
+        detail::check(vpt_vocab_counter_finish(raw_, min_count, max_entries, &s, &off, &cnt, &n));
+        std::vector<std::pair<std::string, uint64_t>> out;
+        out.reserve(n);
+        for (size_t k = 0; k < n; ++k) out.emplace_back(std::string(reinterpret_cast<const char*>(s) + off[k], size_t(off[k + 1] - off[k])), cnt[k]);
+        return out;
+    }
+
+private:
+    std::shared_ptr<detail::Shared> predictor_;
+    void* raw_ = nullptr;
 };
 
 inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
@@ -551,6 +592,17 @@ public:
                                                  tagged_ ? tags.data() : nullptr, ids.data(), cap));
         ids.resize(size_t(toff[texts.size()]));
         return {std::move(toff), std::move(ids)};
+    }
+
+    // Every token this tokenizer streams for `texts` (tagger and stop set included) into `counter` (made for predictor()), on the device
+    // (vpt_token_stream_count_batch); normalize as in encode.  Nothing comes back.
+    void count(const std::vector<std::string>& texts, VocabularyCounter& counter, bool normalize = true) const {
+        std::string text;
+        std::vector<uint64_t> boff(1, 0);
+        for (const std::string& t : texts) { text += t; boff.push_back(text.size()); }
+        detail::check(vpt_token_stream_count_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
+                                                   tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, counter.raw(),
+                                                   normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u));
     }
 
 private:

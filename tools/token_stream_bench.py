@@ -14,6 +14,8 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
   --ids: the vocabulary id pass (kernels_vocab.hip) on the span kernel's CSR by device events -- the vocabulary every other distinct surface of the
       first --vocab-docs documents -- as ms and ms per 100 K documents, and vpt_token_stream_ids_batch end to end (untagged route; its outputs are
       fresh pageable numpy arrays, the stream route's pinned) beside vpt_token_stream_batch; its ids must equal the device call's.
+  --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
+      --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
 on the first --parity-docs documents."""
 import argparse
@@ -89,6 +91,8 @@ def main():
     ap.add_argument("--wsconst", default="")
     ap.add_argument("--ids", action="store_true", help="also time the vocabulary id pass and vpt_token_stream_ids_batch")
     ap.add_argument("--vocab-docs", type=int, default=20000)
+    ap.add_argument("--count", action="store_true", help="also time the vocabulary counter's count call (three launches) and finish once")
+    ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -190,6 +194,40 @@ def main():
                           "ids_spread": round((max(r) - min(r)) / min(r), 4), "ids_ms_per_100k_docs": round(med(r) * 1e5 / S, 4),
                           "known_share": round(float(np.mean(dev_ids != vocab.unk_id)), 4), "ids_over_spans": round(med(r) / k["spans_ms"], 3)}
             del d_ids
+        if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run
+            counter = api.VocabularyCounter(pred, args.count_keys)
+
+            def count():
+                batch.count_tokens(counter, d_text.data_ptr(), d_boff.data_ptr(), S, d_soff.data_ptr(), 0, d_ends.data_ptr(), cap_ends, 0, stream)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); count(); b.record()   # the first call: every surface is inserted and committed
+            torch.cuda.synchronize()
+            try:
+                batch.sync()
+            except api.VaporettoError as e:   # more distinct surfaces than --count-keys: nothing below would measure counting
+                raise SystemExit("--count: %s (distinct surfaces exceed --count-keys %d)" % (e, args.count_keys))
+            first_ms = a.elapsed_time(b)
+            r = []
+            for _ in range(args.rounds):   # the calls behind it: every surface is a committed key
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); count(); b.record()
+                torch.cuda.synchronize()
+                r.append(med([a.elapsed_time(b) for a, b in ev]))
+            batch.sync()
+            t0 = time.perf_counter()
+            surfaces, counts = counter.finish()
+            finish_ms = (time.perf_counter() - t0) * 1e3
+            info = counter.info()
+            calls = 1 + args.rounds * args.steps
+            row["count"] = {"counter": info, "first_call_ms": round(first_ms, 4), "count_ms": round(med(r), 4), "count_rounds_ms": [round(x, 4) for x in r],
+                            "count_spread": round((max(r) - min(r)) / min(r), 4), "count_ms_per_100k_docs": round(med(r) * 1e5 / S, 4),
+                            "finish_wall_ms": round(finish_ms, 3), "distinct": len(surfaces), "top": [[s, int(c) // calls] for s, c in zip(surfaces[:5], counts[:5])],
+                            "top_share": round(float(counts[0]) / max(float(counts.sum()), 1.0), 4) if len(counts) else 0.0,
+                            "tokens_equal_counted_plus_skipped": bool((info["n_counted"] + info["n_skipped"]) == calls * n_tokens)}
+            if args.ids:
+                row["count"]["count_over_ids"] = round(med(r) / row["ids"]["ids_ms"], 3)
+            del counter
         del d_out, d_toff, d_ends, d_soff, d_labels, d_text, batch
         # ---- (b) end to end, pinned buffers
         p_text = api.PinnedArray(nbytes, np.uint8); p_text.array[:] = utf8

@@ -786,6 +786,21 @@ class Predictor:
         return (toff, starts[:n].copy(), ends[:n].copy(), pos[:n].copy(), tag_arr[:n * nt].reshape(n, nt).copy() if tagged else None,
                 ids[:n].copy())
 
+    def count_tokens_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, counter: "VocabularyCounter", wsconst: str = "", normalize: bool = True,
+                            tagger: Optional["PatternMatchTagger"] = None, stop: Optional["TagStopFilter"] = None) -> None:
+        """vpt_token_stream_count_batch: every token of the stream into `counter`, on the device; nothing comes back.  normalize: the surface
+        counted is the KyteaFullwidthFilter image of the token (the text as it was scored), else the caller's bytes.  Without tagger and stop
+        the untagged stream's steps run (no predict_tags needed)."""
+        flags = wsconst_flags(wsconst, allow_graphemes=True)
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        src = utf8 if len(utf8) else np.zeros(1, np.uint8)
+        st = _lib.load().vpt_token_stream_count_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, len(byte_offsets) - 1, flags,
+                                                      tagger.handle(self) if tagger is not None else None, stop.handle if stop is not None else None,
+                                                      counter.handle if counter is not None else None, _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                          fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
         """Predictor::predict_tags over a packed batch (predictor.rs:546-637).  labels: uint8 per boundary (0/1/2).
@@ -1397,6 +1412,16 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def count_tokens(self, counter: "VocabularyCounter", d_utf8: int, d_boff: int, n_documents: int, d_token_offsets: int, d_token_starts: int,
+                     d_token_ends: int, capacity_in: int, flags: int = 0, stream: int = 0) -> None:
+        """Device-resident count of a finished CSR's token surfaces into `counter` (vpt_vocab_count_batch_device): the arrays and flags of
+        token_ids.  One call at a time on a counter, in stream order.  Enqueues and returns; errors (a hostile CSR, a full counter) at sync()."""
+        st = _lib.load().vpt_vocab_count_batch_device(self._p.handle, self._h, counter.handle if counter is not None else None, d_utf8, d_boff,
+                                                      n_documents, d_token_offsets, d_token_starts or None, d_token_ends or None, capacity_in, flags,
+                                                      stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     def concat_graphemes(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, stream: int = 0) -> None:
         """Device-resident ConcatGraphemeClustersFilter on the labels at d_labels, in place (vpt_concat_graphemes_batch_device; the clusters of
         the KyteaFullwidthFilter image when set_flags / set_fullwidth say so); enqueues and returns."""
@@ -1731,6 +1756,66 @@ class Vocabulary:
         return int(v.value)
 
 
+class VocabularyCounter:
+    """vpt_vocab_counter_create: an accumulating table token surface -> count on the predictor's device; what it counted goes to Vocabulary.
+    max_keys: the distinct surfaces it can hold (1 .. 2^24); a token of more than max_surface_chars chars is skipped; arena_chars: the code
+    points it can keep, 0 = 8 * max_keys.  Tied to `predictor`.  MUTABLE: one call at a time, in stream order.  A counter that has become full
+    raises "vocab counter: full" at the sync, at later count calls and at finish(), until reset()."""
+
+    def __init__(self, predictor: "Predictor", max_keys: int, max_surface_chars: int = 64, arena_chars: int = 0):
+        for name, v in (("max_keys", max_keys), ("max_surface_chars", max_surface_chars), ("arena_chars", arena_chars)):
+            if not 0 <= int(v) < 1 << 64:
+                raise VaporettoError("InvalidArgumentError: %s: out of range" % name)
+        h = C.c_void_p()
+        self._keep = predictor
+        st = _lib.load().vpt_vocab_counter_create(predictor.handle, int(max_keys), int(max_surface_chars), int(arena_chars), C.byref(h))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None:
+            try:
+                _lib.load().vpt_vocab_counter_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def info(self) -> dict:
+        k, c, s, n, f = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        st = _lib.load().vpt_vocab_counter_info(self.handle, C.byref(k), C.byref(c), C.byref(s), C.byref(n), C.byref(f))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return {"n_keys": int(k.value), "n_counted": int(c.value), "n_skipped": int(s.value), "n_slots": int(n.value), "full": bool(f.value)}
+
+    def reset(self) -> None:
+        st = _lib.load().vpt_vocab_counter_reset(self.handle)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def finish_raw(self, min_count: int = 1, max_entries: Optional[int] = None):
+        """vpt_vocab_counter_finish as it is: (surfaces uint8, offsets uint64 [n + 1], counts uint64 [n]), copies of the handle's arrays --
+        what vpt_vocab_create takes."""
+        sp, op, cp, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        st = _lib.load().vpt_vocab_counter_finish(self.handle, int(min_count), int(max_entries or 0), C.byref(sp), C.byref(op), C.byref(cp), C.byref(n))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        k = n.value
+        offsets = np.frombuffer(C.string_at(op.value, 8 * (k + 1)), np.uint64).copy()
+        counts = np.frombuffer(C.string_at(cp.value, 8 * k), np.uint64).copy() if k else np.zeros(0, np.uint64)
+        nb = int(offsets[k])
+        surfaces = np.frombuffer(C.string_at(sp.value, nb), np.uint8).copy() if nb else np.zeros(0, np.uint8)
+        return surfaces, offsets, counts
+
+    def finish(self, min_count: int = 1, max_entries: Optional[int] = None):
+        """A snapshot (counting may go on): (surfaces list[str], counts uint64) of the keys of count >= min_count, by count descending, then by
+        code points ascending; the first max_entries of them (None or 0: all)."""
+        surfaces, offsets, counts = self.finish_raw(min_count, max_entries)
+        raw = surfaces.tobytes()
+        return [raw[int(offsets[k]):int(offsets[k + 1])].decode("utf-8") for k in range(len(counts))], counts
+
+
 class TaggedToken(TantivyToken):
     """A token of the tagged stream: TantivyToken plus `tags`, a tuple of Optional[str] per slot.  Under a stop filter `position` is the index
     before filtering and `position_length` the count before filtering."""
@@ -1819,6 +1904,30 @@ class VaporettoTokenizer:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
         out = self._stream_ids(utf8, boff)
         return out[0], out[5]
+
+    def set_vocab(self, vocab: Optional["Vocabulary"]) -> None:
+        """The vocabulary of `.id` and encode_batch from here on (one of this tokenizer's predictor, as build_vocab returns), or None."""
+        self._vocab = vocab
+
+    def count_batch(self, texts: Sequence[str], counter: "VocabularyCounter") -> None:
+        """Every token this tokenizer streams for `texts` (tagger and stop set included) into `counter`, on the device
+        (vpt_token_stream_count_batch); the surface is the one encode_batch looks up (vocab_normalize).  No token string is built."""
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        self._predictor.count_tokens_packed(utf8, boff, counter, self._wsconst, self._vocab_normalize, self._tagger, self._stop)
+
+    def build_vocab(self, batches, min_count: int = 1, max_size: Optional[int] = None, specials=(), unk_id: int = -1,
+                    max_keys: int = 1 << 20) -> "Vocabulary":
+        """corpus -> Vocabulary without a token string leaving the device before the vocabulary itself is read out.  batches: an iterable of
+        lists of str, each counted with count_batch into one VocabularyCounter(max_keys).  The specials get ids 0.. in the order given (and
+        leave the counted list if they occur in it); the ids behind them follow the counter's finish order -- count descending, then code
+        points ascending -- over the surfaces of count >= min_count, at most max_size of them (None: all)."""
+        counter = VocabularyCounter(self._predictor, max_keys)
+        for texts in batches:
+            self.count_batch(list(texts), counter)
+        surfaces, _counts = counter.finish(min_count, max_size)
+        specials = list(specials)
+        taken = set(specials)
+        return Vocabulary(self._predictor, specials + [s for s in surfaces if s not in taken], unk_id)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

@@ -1,6 +1,7 @@
 // C ABI of libvaporetto_hip.so, the device-resident entry points: Predictor::predict (tile planning + the scoring launch), Sentence::fill_tags (the tag
 // records), write_tokenized_text (the flat writer), the char count, Sentence::char_types -- all on device buffers, asynchronous on the caller's stream.
 #include "capi_internal.hpp"
+#include "vocab_count.hpp"
 #include "vocab_table.hpp"
 
 // (the entry points have C linkage from their declarations in include/vaporetto_hip.h)
@@ -1013,4 +1014,158 @@ vpt_status vpt_token_ids_batch_device(const vpt_predictor* p, vpt_batch* b, cons
                                       uint64_t capacity_in, unsigned flags, int32_t* d_token_ids, void* hip_stream) {
     return token_ids_device(p, b, static_cast<const vpt_vocab*>(vocab), d_utf8, d_byte_offsets, n_documents, d_token_offsets, d_token_starts,
                             d_token_ends, capacity_in, flags, d_token_ids, static_cast<hipStream_t>(hip_stream));
+}
+
+// ---- the vocabulary counter (vocab_count.hpp; kernels_vocab_count.hip): an accumulating table of token surfaces on the predictor's device
+namespace {
+// everything enqueued on the counter is through: the host may read and rewrite it
+vpt_status vocab_counter_quiesce(vpt_vocab_counter* c) {
+    VPT_HIP(hipSetDevice(c->device));
+    if (c->in_flight) VPT_HIP(hipStreamSynchronize(c->last_stream));
+    c->in_flight = false;
+    c->last_stream = nullptr;
+    return VPT_OK;
+}
+vpt_status vocab_counter_ctrl(vpt_vocab_counter* c, uint64_t* ctrl) {
+    if (const vpt_status st = vocab_counter_quiesce(c); st != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(ctrl, c->view.ctrl, 8 * vpt::kVcCtrlWords, hipMemcpyDeviceToHost));
+    if (uint32_t(ctrl[vpt::kVcFull])) c->known_full = true;
+    return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_vocab_counter_create(const vpt_predictor* p, uint64_t max_keys, uint64_t max_surface_chars, uint64_t arena_chars, void** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (max_keys < 1 || max_keys > vpt::kVocabCounterMaxKeys) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_keys: must be between 1 and 2^24");
+    if (max_surface_chars < 1 || max_surface_chars > vpt::kVocabCounterMaxSurfaceChars)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_surface_chars: must be between 1 and 2^24");
+    const uint64_t arena = vpt::vocab_counter_arena_chars(max_keys, arena_chars);
+    if (arena > vpt::kVocabCounterMaxArenaChars) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: arena_chars: must be below 2^32");
+    VPT_HIP(hipSetDevice(p->device));
+    vpt_vocab_counter* c = new (std::nothrow) vpt_vocab_counter();
+    if (!c) return fail(VPT_RUNTIME_ERROR, "out of host memory");
+    c->pred = p; c->device = p->device;
+    const uint32_t n_slots = vpt::vocab_counter_slots(max_keys);
+    // one allocation, 256-byte sections: control words | slots | counts | key records | arena | finish's entries
+    auto pad = [](size_t n) { return (n + 255) & ~size_t(255); };
+    const size_t o_ctrl = 0, o_slots = o_ctrl + pad(8 * vpt::kVcCtrlWords), o_counts = o_slots + pad(8 * size_t(n_slots)),
+                 o_keys = o_counts + pad(8 * size_t(n_slots)), o_arena = o_keys + pad(16 * size_t(max_keys)), o_out = o_arena + pad(4 * size_t(arena)),
+                 total = o_out + pad(16 * size_t(max_keys));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->mem), total);
+    if (e == hipSuccess) e = hipMemset(c->mem, 0, total);
+    if (e != hipSuccess) {
+        (void)hipFree(c->mem);
+        delete c;
+        return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    c->state_bytes = o_keys;
+    vpt::VocabCounterView& V = c->view;
+    V.ctrl = reinterpret_cast<uint64_t*>(c->mem + o_ctrl); V.slots = reinterpret_cast<uint64_t*>(c->mem + o_slots);
+    V.counts = reinterpret_cast<uint64_t*>(c->mem + o_counts); V.keys = reinterpret_cast<uint4*>(c->mem + o_keys);
+    V.arena = reinterpret_cast<uint32_t*>(c->mem + o_arena); V.out = reinterpret_cast<uint4*>(c->mem + o_out);
+    V.arena_chars = arena; V.n_slots = n_slots; V.max_keys = uint32_t(max_keys); V.max_chars = uint32_t(max_surface_chars);
+    c->offsets.assign(1, 0);
+    *out = c;
+    return VPT_OK;
+}
+
+void vpt_vocab_counter_destroy(void* counter) {
+    vpt_vocab_counter* c = static_cast<vpt_vocab_counter*>(counter);
+    if (!c) return;
+    (void)vocab_counter_quiesce(c);
+    (void)hipFree(c->mem);
+    delete c;
+}
+
+vpt_status vpt_vocab_counter_reset(void* counter) {
+    vpt_vocab_counter* c = static_cast<vpt_vocab_counter*>(counter);
+    if (!c) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: must not be NULL");
+    if (const vpt_status st = vocab_counter_quiesce(c); st != VPT_OK) return st;
+    VPT_HIP(hipMemset(c->mem, 0, c->state_bytes));
+    c->known_full = false;
+    c->surfaces.clear(); c->counts.clear(); c->offsets.assign(1, 0);
+    return VPT_OK;
+}
+
+vpt_status vpt_vocab_counter_info(void* counter, uint64_t* n_keys, uint64_t* n_counted, uint64_t* n_skipped, uint32_t* n_slots, uint32_t* full) {
+    vpt_vocab_counter* c = static_cast<vpt_vocab_counter*>(counter);
+    if (!c) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: must not be NULL");
+    uint64_t ctrl[vpt::kVcCtrlWords] = {};
+    if (const vpt_status st = vocab_counter_ctrl(c, ctrl); st != VPT_OK) return st;
+    if (n_keys) *n_keys = std::min<uint64_t>(ctrl[vpt::kVcKeys], c->view.max_keys);
+    if (n_counted) *n_counted = ctrl[vpt::kVcCounted];
+    if (n_skipped) *n_skipped = ctrl[vpt::kVcSkipped];
+    if (n_slots) *n_slots = c->view.n_slots;
+    if (full) *full = uint32_t(ctrl[vpt::kVcFull]) ? 1u : 0u;
+    return VPT_OK;
+}
+
+namespace vptc {
+vpt_status vocab_count_device(const vpt_predictor* p, vpt_batch* b, vpt_vocab_counter* c, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                              size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
+                              uint64_t capacity_in, unsigned flags, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!c) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: must not be NULL");
+    if (c->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: does not belong to this predictor");
+    if (flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (c->known_full) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    if (n_documents == 0) return VPT_OK;   // no document owns a token: nothing is enqueued
+    if (!d_utf8 || !d_byte_offsets || !d_token_offsets || (capacity_in && !d_token_ends))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if ((capacity_in + vpt::kVocabTile - 1) / vpt::kVocabTile > 0x7FFFFFFFull)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: a count call takes fewer than 2^39 tokens");
+    VPT_HIP(hipSetDevice(p->device));
+    if (const vpt_status st = b->d_vrec.grow(2 * size_t(capacity_in) + 2); st != VPT_OK) return st;
+    vpt::VocabCountParams P{};
+    P.text = d_utf8; P.boff = d_byte_offsets; P.n_docs = n_documents; P.token_offsets = d_token_offsets; P.token_starts = d_token_starts;
+    P.token_ends = d_token_ends; P.capacity_in = capacity_in;
+    P.cinfo = (flags & VPT_FLAG_KYTEA_FULLWIDTH) ? p->d_cinfo + 65536 : nullptr;
+    P.C = c->view; P.rec = b->d_vrec; P.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_vocab_count(P, stream));
+    c->last_stream = stream; c->in_flight = true;
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_vocab_count_batch_device(const vpt_predictor* p, vpt_batch* b, void* counter, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                                        size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts,
+                                        const uint32_t* d_token_ends, uint64_t capacity_in, unsigned flags, void* hip_stream) {
+    return vocab_count_device(p, b, static_cast<vpt_vocab_counter*>(counter), d_utf8, d_byte_offsets, n_documents, d_token_offsets, d_token_starts,
+                              d_token_ends, capacity_in, flags, static_cast<hipStream_t>(hip_stream));
+}
+
+// A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them
+// (vocab_count.hpp).  Counting may go on afterwards.
+vpt_status vpt_vocab_counter_finish(void* counter, uint64_t min_count, uint64_t max_entries, const uint8_t** surfaces, const uint64_t** offsets,
+                                    const uint64_t** counts, size_t* n_entries) {
+    vpt_vocab_counter* c = static_cast<vpt_vocab_counter*>(counter);
+    if (!c) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: must not be NULL");
+    if (!surfaces || !offsets || !counts || !n_entries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    uint64_t ctrl[vpt::kVcCtrlWords] = {};
+    if (const vpt_status st = vocab_counter_ctrl(c, ctrl); st != VPT_OK) return st;
+    if (c->known_full) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    VPT_HIP(hipMemset(c->view.ctrl + vpt::kVcOut, 0, 8));
+    VPT_HIP(vpt::launch_vocab_count_finish(c->view, min_count, nullptr));
+    uint64_t n_out = 0;
+    VPT_HIP(hipMemcpy(&n_out, c->view.ctrl + vpt::kVcOut, 8, hipMemcpyDeviceToHost));
+    n_out = std::min<uint64_t>(n_out, c->view.max_keys);
+    const uint64_t n_arena = std::min<uint64_t>(ctrl[vpt::kVcArena], c->view.arena_chars);
+    try {
+        std::vector<uint4> raw(size_t(n_out) + 1);
+        std::vector<uint32_t> arena(size_t(n_arena) + 1);
+        if (n_out) VPT_HIP(hipMemcpy(raw.data(), c->view.out, 16 * size_t(n_out), hipMemcpyDeviceToHost));
+        if (n_arena) VPT_HIP(hipMemcpy(arena.data(), c->view.arena, 4 * size_t(n_arena), hipMemcpyDeviceToHost));
+        std::vector<vpt::VocabCountEntry> entries(size_t(n_out) + 1);
+        for (size_t k = 0; k < n_out; ++k) entries[k] = {uint64_t(raw[k].x) | (uint64_t(raw[k].y) << 32), raw[k].z, raw[k].w};
+        vpt::VocabCountResult R = vpt::finish_vocab_count(entries.data(), size_t(n_out), arena.data(), size_t(n_arena), min_count, max_entries);
+        c->surfaces = std::move(R.surfaces); c->offsets = std::move(R.offsets); c->counts = std::move(R.counts);
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory while ordering the counted surfaces");
+    }
+    c->surfaces.reserve(1); c->counts.reserve(1);   // (data() of an empty result is still a pointer)
+    *surfaces = c->surfaces.data(); *offsets = c->offsets.data(); *counts = c->counts.data();
+    *n_entries = c->counts.size();
+    return VPT_OK;
 }

@@ -748,13 +748,16 @@ vpt_status vpt_token_stream_batch(const vpt_predictor* p, const uint8_t* utf8, c
 // `tagged` == false (vpt_token_stream_ids_batch without tagger, stop set and tags): no fill_tags, the untagged span instance, and the filter
 // pass without tags -- vpt_token_stream_batch's steps with starts and positions.  `vocab` != NULL: the id pass (kernels_vocab.hip) runs last
 // on every chunk's finished CSR, one launch more per chunk; with NULL the launches are what they were.
+// `counter` != NULL (vpt_token_stream_count_batch): the count call (kernels_vocab_count.hip, three launches) runs last on every chunk's finished
+// CSR instead, and nothing is copied out: the output pointers are NULL.  A counter takes one call at a time, so a chunk's count call waits for the
+// chunk before it (on another lane's stream) to be through; everything in front of it overlaps as before.  With NULL nothing changes.
 namespace {
 vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents, unsigned wsconst_flags,
                                bool tagged, const void* tagger, const void* stop, const vpt_vocab* vocab, unsigned vocab_flags,
-                               uint64_t* token_offsets_out, uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out,
+                               vpt_vocab_counter* counter, uint64_t* token_offsets_out, uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out,
                                int32_t* token_tags_out, int32_t* token_ids_out, uint64_t capacity) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
-    if (!token_offsets_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (!token_offsets_out && !counter) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (wsconst_flags & ~(0x7Eu | unsigned(VPT_FLAG_CONCAT_GRAPHEMES))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: Could not parse a wsconst value");   // lib.rs:82
     if (tagged && !p->predict_tags) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: this predictor is created with predict_tags = false");
     const vpt_pattern_tagger* t = static_cast<const vpt_pattern_tagger*>(tagger);
@@ -762,12 +765,14 @@ vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, cons
     if (t && t->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tagger: does not belong to this predictor");
     if (sp && sp->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: stop: does not belong to this predictor");
     if (vocab && vocab->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: does not belong to this predictor");
-    if (vocab && (vocab_flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
-    token_offsets_out[0] = 0;
+    if (counter && counter->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: does not belong to this predictor");
+    if ((vocab || counter) && (vocab_flags & ~unsigned(VPT_FLAG_KYTEA_FULLWIDTH))) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (counter && counter->known_full) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    if (token_offsets_out) token_offsets_out[0] = 0;
     if (n_documents == 0) return VPT_OK;
     const uint32_t nt = tagged ? p->n_tags : 0u;
     if (!utf8 || !byte_offsets ||
-        (capacity && (!token_starts_out || !token_ends_out || !token_positions_out || (nt && !token_tags_out) || (vocab && !token_ids_out))))
+        (capacity && !counter && (!token_starts_out || !token_ends_out || !token_positions_out || (nt && !token_tags_out) || (vocab && !token_ids_out))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     std::vector<uint64_t> docs;   // an empty document has no tokens and never reaches the device (vpt_token_stream_batch)
     docs.reserve(n_documents + 1);
@@ -781,7 +786,10 @@ vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, cons
     }
     if (max_bytes > 0xFFFFFFFFull) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: text: a document must be shorter than 2^32 bytes");
     const size_t n = docs.size() - 1;
-    if (n == 0) { std::fill(token_offsets_out, token_offsets_out + n_documents + 1, uint64_t(0)); return VPT_OK; }
+    if (n == 0) {
+        if (token_offsets_out) std::fill(token_offsets_out, token_offsets_out + n_documents + 1, uint64_t(0));
+        return VPT_OK;
+    }
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     vpt_status st = acquire(p, &w);
@@ -851,6 +859,11 @@ vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, cons
                                   b->d_fids + tb, s);
             if (st != VPT_OK) return st;
         }
+        if (counter) {   // the chunk's tokens into the counter, behind the count call of the chunk before
+            if (k) VPT_HIP(hipStreamWaitEvent(s, b->chunk_ev[k - 1], 0));
+            st = vocab_count_device(p, bb, counter, b->d_text, d_boff_k, cn, b->d_ftoff + a + k, b->d_fstarts + tb, b->d_fends + tb, nby, vocab_flags, s);
+            if (st != VPT_OK) return st;
+        }
         VPT_HIP(hipEventRecord(b->chunk_ev[k], s));
         chunks.push_back(c);
     }
@@ -859,7 +872,7 @@ vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, cons
     uint64_t at = 0;
     bool incomplete = false;
     st = VPT_OK;
-    for (size_t k = 0; k < chunks.size() && st == VPT_OK; ++k) {
+    for (size_t k = 0; k < chunks.size() && st == VPT_OK && !counter; ++k) {
         const Chunk& c = chunks[k];
         VPT_HIP(hipEventSynchronize(b->chunk_ev[k]));
         const uint64_t total = h_total[k];
@@ -878,6 +891,11 @@ vpt_status token_stream_chunks(const vpt_predictor* p, const uint8_t* utf8, cons
     }
     VPT_HIP(hipStreamSynchronize(b->s_out));
     st = lanes.verdict(st);
+    if (counter) {   // every lane is through: so is the counter
+        counter->in_flight = false;
+        counter->last_stream = nullptr;
+        return st;
+    }
     if (st != VPT_OK) return st;
     if (incomplete) return fail(VPT_RUNTIME_ERROR, "vpt_token_stream_tagged_batch: a chunk's output size is out of range");
     for (size_t k = 1; k < chunks.size(); ++k)
@@ -896,7 +914,7 @@ vpt_status vpt_token_stream_tagged_batch(const vpt_predictor* p, const uint8_t* 
                                          unsigned wsconst_flags, const void* tagger, const void* stop, uint64_t* token_offsets_out,
                                          uint32_t* token_starts_out, uint32_t* token_ends_out, uint32_t* token_positions_out, int32_t* token_tags_out,
                                          uint64_t capacity) {
-    return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, true, tagger, stop, nullptr, 0, token_offsets_out, token_starts_out,
+    return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, true, tagger, stop, nullptr, 0, nullptr, token_offsets_out, token_starts_out,
                                token_ends_out, token_positions_out, token_tags_out, nullptr, capacity);
 }
 
@@ -908,7 +926,16 @@ vpt_status vpt_token_stream_ids_batch(const vpt_predictor* p, const uint8_t* utf
     if (!vocab) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: must not be NULL");
     const bool tagged = tagger || stop || token_tags_out;
     return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, tagged, tagger, stop, static_cast<const vpt_vocab*>(vocab), vocab_flags,
-                               token_offsets_out, token_starts_out, token_ends_out, token_positions_out, token_tags_out, token_ids_out, capacity);
+                               nullptr, token_offsets_out, token_starts_out, token_ends_out, token_positions_out, token_tags_out, token_ids_out, capacity);
+}
+
+// Every token of the stream into a vocabulary counter; nothing comes back: the untagged steps without tagger and stop set, else the tagged ones
+vpt_status vpt_token_stream_count_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                        unsigned wsconst_flags, const void* tagger, const void* stop, void* counter, unsigned vocab_flags) {
+    if (!counter) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: counter: must not be NULL");
+    const bool tagged = tagger || stop;
+    return token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, tagged, tagger, stop, nullptr, vocab_flags, static_cast<vpt_vocab_counter*>(counter),
+                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- pinned host memory for callers that want the PCIe link at full rate

@@ -289,6 +289,23 @@ struct vpt_vocab {
     std::vector<uint8_t> bytes;
 };
 
+// A vocabulary counter on the predictor's device (vocab_count.hpp; kernels_vocab_count.hip): control words, slots, counts, key records, the
+// arena and finish's output in ONE allocation.  MUTABLE, unlike a vocabulary: one call on it at a time, in stream order.  What the last finish
+// handed out lives here until the next finish, reset or destroy.
+struct vpt_vocab_counter {
+    const vpt_predictor* pred = nullptr;
+    int device = 0;
+    unsigned char* mem = nullptr;
+    size_t state_bytes = 0;            // control words, slots and counts: what reset clears
+    vpt::VocabCounterView view{};
+    hipStream_t last_stream = nullptr; // of the last count call that may still be running
+    bool in_flight = false;
+    bool known_full = false;           // the host has seen the full word (info / finish): count calls refuse at once
+    std::vector<uint8_t> surfaces;
+    std::vector<uint64_t> offsets, counts;
+};
+constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: full (max_keys / arena_chars)";
+
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
 struct DevBuf {
@@ -366,6 +383,7 @@ struct vpt_batch {
     DevBuf<uint32_t> d_fstarts, d_fends, d_fpos;
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
+    DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -505,6 +523,7 @@ vpt_status status_from_bits(uint32_t bits) {
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: labels: not a CharacterBoundary (0, 1 or 2)");
     if (bits & vpt::kErrBadTokenCsr)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: token_offsets / token_starts / token_ends: do not describe the documents' tokens");
+    if (bits & vpt::kErrVocabCounterFull) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
 
@@ -687,6 +706,10 @@ vpt_status token_filter_device(const vpt_predictor* p, vpt_batch* b, const vpt_t
 vpt_status token_ids_device(const vpt_predictor* p, vpt_batch* b, const vpt_vocab* vocab, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                             size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
                             uint64_t capacity_in, unsigned flags, int32_t* d_token_ids, hipStream_t stream);
+// A count call over a finished CSR (vpt_vocab_count_batch_device; kernels_vocab_count.hip)
+vpt_status vocab_count_device(const vpt_predictor* p, vpt_batch* b, vpt_vocab_counter* counter, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
+                              size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
+                              uint64_t capacity_in, unsigned flags, hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

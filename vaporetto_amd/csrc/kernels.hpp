@@ -67,6 +67,7 @@ constexpr uint32_t kErrParsePartial = 128u;   // partially annotated text that p
 constexpr uint32_t kPartialErrNoChar = 1u, kPartialErrNul = 2u, kPartialErrChar = 3u, kPartialErrEnd = 4u, kPartialErrWord = 1u, kPartialErrBytesWord = 7u;
 constexpr uint32_t kErrBadLabel = 256u;       // the partial-annotation writer: a label that is no CharacterBoundary (above 2)
 constexpr uint32_t kErrBadTokenCsr = 512u;    // the id pass: token_offsets / starts / ends that do not describe the documents (kernels_vocab.hip)
+constexpr uint32_t kErrVocabCounterFull = 1024u;   // the vocabulary counter: more keys or chars than it was made for (kernels_vocab_count.hip)
 
 
 struct ScoreParams {
@@ -286,6 +287,46 @@ struct VocabParams {
     uint32_t* status;
 };
 hipError_t launch_token_ids(const VocabParams& P, hipStream_t stream);
+// The vocabulary counter (kernels_vocab_count.hip; vocab_count.hpp): an accumulating table token surface -> 64-bit count in ONE device allocation.
+//   ctrl     kVc* words below
+//   slots    [n_slots], n_slots a power of two: 0 empty; bit 63 set: a committed key, the low bits its index in `keys`; else token index + 1 of
+//            the representative of the count call that is running
+//   counts   [n_slots]: the count of the slot's key
+//   keys     [max_keys] {first code point in arena, chars, fingerprint (high 32 bits of the surface's hash), 0}
+//   arena    [arena_chars]: the keys' code points
+//   out      [max_keys] {count low, count high, first code point in arena, chars}: what finish leaves for the host
+constexpr uint32_t kVcKeys = 0, kVcArena = 1, kVcCounted = 2, kVcSkipped = 3, kVcFull = 4, kVcOut = 5, kVcCtrlWords = 32;
+constexpr uint32_t kVcNoSlot = 0xFFFFFFFFu;
+constexpr uint64_t kVcCommitted = 1ull << 63;
+struct VocabCounterView {
+    uint64_t* ctrl;
+    uint64_t* slots;
+    uint64_t* counts;
+    uint4* keys;
+    uint32_t* arena;
+    uint4* out;
+    uint64_t arena_chars;
+    uint32_t n_slots, max_keys, max_chars;
+};
+// A count call over a finished span CSR (the id pass's conventions): three launches over the batch's tokens, a lane per token in tiles of
+// kVocabTile.  rec: two uint4 per token, [2 * capacity_in], scratch of the batch: {hash low, hash high, first byte in the text low, high},
+// {bytes, chars (0: skipped), the slot this token won or kVcNoSlot, 0}.
+struct VocabCountParams {
+    const uint8_t* text;
+    const uint64_t* boff;           // [n_docs + 1]
+    uint64_t n_docs;
+    const uint64_t* token_offsets;  // [n_docs + 1]
+    const uint32_t* token_starts;   // [capacity_in] or nullptr
+    const uint32_t* token_ends;     // [capacity_in]
+    uint64_t capacity_in;
+    const uint32_t* cinfo;
+    VocabCounterView C;
+    uint4* rec;
+    uint32_t* status;
+};
+hipError_t launch_vocab_count(const VocabCountParams& P, hipStream_t stream);
+// one launch, a lane per slot: out[0 .. ctrl[kVcOut]) for every committed key of count >= min_count (ctrl[kVcOut] zero before)
+hipError_t launch_vocab_count_finish(const VocabCounterView& C, uint64_t min_count, hipStream_t stream);
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
