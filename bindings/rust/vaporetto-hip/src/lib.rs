@@ -399,6 +399,63 @@ impl<'p> Vocabulary<'p> {
         ids.truncate(offsets[n] as usize);
         Ok((offsets, ids))
     }
+
+    /// The number of entries (`vpt_vocab_info`): the `n_terms` of the postings over this vocabulary.
+    pub fn len(&self) -> Result<u32> {
+        let mut n = 0u32;
+        check(unsafe { ffi::vpt_vocab_info(self.raw as *const std::ffi::c_void, &mut n, std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        Ok(n)
+    }
+
+    /// The postings of a packed batch of documents (a segment) through the untagged stream's steps (`vpt_token_stream_postings_batch`):
+    /// term = this vocabulary's id, document = `doc_base` + the document's index (empty documents included), tf = the term's tokens in it.
+    /// `byte_offsets` must be non-decreasing and inside `utf8`, `doc_base` + the documents at most 2^32: checked here.
+    pub fn index_batch(&self, utf8: &[u8], byte_offsets: &[u64], wsconst_flags: u32, normalize: bool, doc_base: u64) -> Result<Postings> {
+        let n = byte_offsets.len().saturating_sub(1);
+        if byte_offsets.windows(2).any(|w| w[0] > w[1]) || (n > 0 && byte_offsets[n] > utf8.len() as u64) {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: byte_offsets: must be non-decreasing and inside the text".into()));
+        }
+        if doc_base > 1 << 32 || n as u64 > (1u64 << 32) - doc_base {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32".into()));
+        }
+        let cap = utf8.len() + 1;   // (a token has a byte at least, a posting a token)
+        let mut term_offsets = vec![0u64; self.len()? as usize + 1];
+        let (mut docs, mut tfs) = (vec![0u32; cap], vec![0u32; cap]);
+        let (mut n_postings, mut n_dropped) = (0u64, 0u64);
+        let text = if utf8.is_empty() { &[0u8][..] } else { utf8 };
+        let offsets = if byte_offsets.is_empty() { &[0u64][..] } else { byte_offsets };
+        check(unsafe {
+            ffi::vpt_token_stream_postings_batch(self.predictor.raw, text.as_ptr(), offsets.as_ptr(), n, wsconst_flags, std::ptr::null(), std::ptr::null(),
+                                                 self.raw as *const std::ffi::c_void, if normalize { 1 } else { 0 }, doc_base, term_offsets.as_mut_ptr(),
+                                                 docs.as_mut_ptr(), tfs.as_mut_ptr(), cap as u64, &mut n_postings, &mut n_dropped)
+        })?;
+        docs.truncate(n_postings as usize);
+        tfs.truncate(n_postings as usize);
+        Ok(Postings { term_offsets, docs, tfs, n_dropped })
+    }
+}
+
+/// The postings of one batch of documents (a segment), term-major: term k's postings are `term_offsets[k] .. term_offsets[k + 1]` of `docs`
+/// (`doc_base` + the document's index, ascending within a term) and `tfs`.  `n_dropped`: the tokens whose id was no term.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct Postings {
+    pub term_offsets: Vec<u64>,
+    pub docs: Vec<u32>,
+    pub tfs: Vec<u32>,
+    pub n_dropped: u64,
+}
+
+impl Postings {
+    /// The document frequency of `term`.
+    pub fn df(&self, term: usize) -> u64 {
+        self.term_offsets[term + 1] - self.term_offsets[term]
+    }
+
+    /// (docs, tfs) of `term`.
+    pub fn postings(&self, term: usize) -> (&[u32], &[u32]) {
+        let (a, b) = (self.term_offsets[term] as usize, self.term_offsets[term + 1] as usize);
+        (&self.docs[a..b], &self.tfs[a..b])
+    }
 }
 
 impl Drop for Vocabulary<'_> {

@@ -11,6 +11,9 @@
 //   ./token_stream model.bin wsconst --build-vocab [min_count] < documents.txt
 // With --build-vocab (beyond the adapter): the documents' token surfaces (of the text as it was scored) are counted on the device; one line per
 // surface of count >= min_count: count <TAB> surface, most frequent first -- the second column is a vocab.txt for --vocab.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] < documents.txt
+// With --postings (beyond the adapter): the documents are one segment; one line per posting, by term, then by document:
+// term <TAB> document <TAB> tf, the document being doc_base + the line's index; then one line "dropped <TAB> n" for the tokens that are no entry.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -58,6 +61,21 @@ int main(int argc, char** argv) {
             for (size_t d = 0; d < docs.size(); ++d)
                 for (uint64_t k = enc.first[d]; k < enc.first[d + 1]; ++k)
                     std::printf("%zu\t%zu\t%d\n", d, size_t(k - enc.first[d]), int(enc.second[size_t(k)]));
+            return 0;
+        }
+        if (argc > 4 && std::strcmp(argv[3], "--postings") == 0) {
+            std::ifstream vf(argv[4]);
+            std::vector<std::string> surfaces;
+            for (std::string l; std::getline(vf, l);) surfaces.push_back(l);
+            vaporetto_hip::VaporettoTokenizer plain(vaporetto_hip::Model::read_slice(bytes.data(), bytes.size()).first, argv[2]);
+            const vaporetto_hip::Vocabulary vocab(plain.predictor(), surfaces);
+            std::vector<std::string> docs;
+            for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
+            const vaporetto_hip::Postings post = plain.index(docs, vocab, argc > 5 ? std::strtoull(argv[5], nullptr, 10) : 0);
+            for (size_t k = 0; k < post.n_terms(); ++k)
+                for (uint64_t q = post.term_offsets[k]; q < post.term_offsets[k + 1]; ++q)
+                    std::printf("%zu\t%u\t%u\n", k, unsigned(post.docs[size_t(q)]), unsigned(post.tfs[size_t(q)]));
+            std::printf("dropped\t%llu\n", static_cast<unsigned long long>(post.n_dropped));
             return 0;
         }
         if (argc > 3 && std::strcmp(argv[3], "--build-vocab") == 0) {

@@ -603,6 +603,48 @@ vpt_status vpt_vocab_counter_finish(void *counter, uint64_t min_count, uint64_t 
 vpt_status vpt_token_stream_count_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
                                         unsigned wsconst_flags, const void *tagger, const void *stop, void *counter, unsigned vocab_flags);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Postings on the device: term -> (document, tf) lists from token ids           (no item of the adapter: what the index writer behind its token
+ *                                                      stream does first -- here one int32 per token never has to reach the host to be grouped)
+ *
+ * vpt_postings_batch_device: the postings of one batch (a SEGMENT: doc_base makes its document numbers global, merging segments is the caller's
+ *   job) from a FINISHED span CSR -- d_token_offsets [n_documents + 1] and capacity_in as vpt_token_ids_batch_device takes them, a document may own
+ *   no token, the tokens are min(token_offsets[n], capacity_in) -- and d_token_ids [capacity_in], what that call wrote.  It reads those two arrays
+ *   and nothing else.  Token t of document d is INDEXED when 0 <= ids[t] < n_terms; every other token (negative, >= n_terms) adds 1 to
+ *   d_counts[1] and appears nowhere else.  THE PASS SEES IDS ONLY: a vocabulary's unk_id chosen inside [0, n_terms) is a term like any other.
+ *   A posting is a (term, document) pair with at least one indexed token; postings are ordered by term, then by document.  Posting q:
+ *   d_post_docs[q] = doc_base + d, d_post_tfs[q] = the number of such tokens.  Term k's postings are [d_term_offsets[k], d_term_offsets[k + 1]),
+ *   its document frequency their difference; d_term_offsets[0] = 0, d_term_offsets[n_terms] = d_counts[0] = the postings.
+ *   The optional pair (both NULL or neither): d_token_order[0 .. sum of tfs) = the indexed tokens' indices sorted by (term, token index);
+ *   d_post_first[q] = posting q's first place in it, d_post_first[d_counts[0]] = the indexed tokens: posting q's tokens are
+ *   d_token_order[d_post_first[q] .. d_post_first[q + 1]), ascending -- with token_positions, a positional index by one gather.
+ *   Four launches with the trainer's stable radix sort (ceil(bit_width(n_terms) / 8) passes) and scan in between (kernels_postings.hip);
+ *   asynchronous on hip_stream, errors at vpt_batch_sync.  No atomic decides a value: two runs give identical bytes.  The workspace keeps
+ *   28 bytes per token of capacity_in (key, document, two index words, a flag, a scan word) and 16 bytes per 16 tokens of histograms.
+ *   At the call, VPT_INVALID_ARGUMENT: a NULL pointer other than the optional pair, only one of the pair, n_terms == 0 or > 2^24,
+ *   capacity_in >= 2^32, doc_base + n_documents > 2^32, a workspace of another predictor.
+ *   At the sync, VPT_INVALID_ARGUMENT: the id pass's message when token_offsets decrease, exceed capacity_in or leave a token below
+ *   token_offsets[n] that no document owns (the outputs are then unspecified); "InvalidArgumentError: capacity: smaller than the number of
+ *   postings" when there are more than capacity_out -- d_counts[0] then holds the number needed, the postings below capacity_out are written and
+ *   nothing behind it.  capacity_out >= the tokens always suffices.  Whatever the arrays hold, nothing is read outside token_offsets[0 .. n] and
+ *   token_ids[0 .. capacity_in), and nothing is written outside term_offsets [n_terms + 1], post_docs / post_tfs [capacity_out], post_first
+ *   [capacity_out + 1], token_order [capacity_in], counts [2] and the workspace.
+ * vpt_postings_tile: the tokens a workgroup of the sort takes (the tests' edges; the key pass's tile is vpt_vocab_tile).
+ * vpt_token_stream_postings_batch: host buffers in, the segment's postings out: vpt_token_stream_ids_batch's steps into buffers of the call,
+ *   then the whole batch's offsets and ids on the device and the pass once; n_terms = the vocabulary's keys, term_offsets_out [n_keys + 1].  A
+ *   document's index is the caller's, empty documents included.  The result does not depend on how the stream is cut into chunks.  More than
+ *   `capacity` postings: VPT_INVALID_ARGUMENT with the message above, *n_postings_out = the number needed, nothing else written but
+ *   *n_dropped_out.  Returns when the device is through. */
+vpt_status vpt_postings_batch_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_token_offsets, size_t n_documents,
+                                     const int32_t *d_token_ids, uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base,
+                                     uint64_t *d_term_offsets, uint32_t *d_post_docs, uint32_t *d_post_tfs, uint64_t capacity_out,
+                                     uint64_t *d_post_first, uint32_t *d_token_order, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_tile(uint32_t *n_tokens);
+vpt_status vpt_token_stream_postings_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets, size_t n_documents,
+                                           unsigned wsconst_flags, const void *tagger, const void *stop, const void *vocab, unsigned vocab_flags,
+                                           uint64_t doc_base, uint64_t *term_offsets_out, uint32_t *post_docs_out, uint32_t *post_tfs_out,
+                                           uint64_t capacity, uint64_t *n_postings_out, uint64_t *n_dropped_out);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

@@ -454,6 +454,17 @@ private:
     void* raw_ = nullptr;
 };
 
+// The postings of one batch of documents (a segment), term-major (vpt_token_stream_postings_batch): term k's postings are
+// [term_offsets[k], term_offsets[k + 1]) of docs (doc_base + the document's index, ascending within a term) and tfs; its document frequency is
+// the difference of the two offsets.  n_dropped: the tokens whose id was no term.
+struct Postings {
+    std::vector<uint64_t> term_offsets;   // [n_terms + 1]
+    std::vector<uint32_t> docs, tfs;
+    uint64_t n_dropped = 0;
+    size_t n_terms() const { return term_offsets.size() - 1; }
+    uint64_t df(size_t term) const { return term_offsets[term + 1] - term_offsets[term]; }
+};
+
 inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
     std::vector<std::string> out;
     if (lines.empty()) return out;
@@ -603,6 +614,27 @@ public:
         detail::check(vpt_token_stream_count_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
                                                    tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, counter.raw(),
                                                    normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u));
+    }
+
+    // The postings of `texts` (a segment) over `vocab` (made for predictor()): term = vocabulary id, document = doc_base + the text's index,
+    // empty texts included, tf = the term's tokens among those this tokenizer streams (vpt_token_stream_postings_batch); normalize as in encode.
+    Postings index(const std::vector<std::string>& texts, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true) const {
+        std::string text;
+        std::vector<uint64_t> boff(1, 0);
+        for (const std::string& t : texts) { text += t; boff.push_back(text.size()); }
+        Postings out;
+        out.term_offsets.assign(vocab.size() + 1, 0);
+        const size_t cap = text.size() + 1;   // (a token has a byte at least, a posting a token)
+        out.docs.resize(cap);
+        out.tfs.resize(cap);
+        uint64_t n_postings = 0;
+        detail::check(vpt_token_stream_postings_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
+                                                      tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, vocab.raw(),
+                                                      normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u, doc_base, out.term_offsets.data(),
+                                                      out.docs.data(), out.tfs.data(), cap, &n_postings, &out.n_dropped));
+        out.docs.resize(size_t(n_postings));
+        out.tfs.resize(size_t(n_postings));
+        return out;
     }
 
 private:

@@ -1,0 +1,58 @@
+"""include/vaporetto_hip.hpp's Postings and VaporettoTokenizer::index through the --postings block of examples/token_stream.cpp against the Python
+mirror (VaporettoTokenizer.index_batch), which tests/postingssuite.py holds to the definition: compiled against the emulated build of the kernel
+sources on the CPU, against the product with -m gpu."""
+import gc
+import os
+import subprocess
+
+import pytest
+
+from tests import devmem, patterntagsuite
+from vaporetto_amd import _lib, api
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _check(lib_path, tmp_path):
+    d, name = os.path.dirname(lib_path), os.path.basename(lib_path)
+    exe = str(tmp_path / "token_stream")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                           os.path.join(ROOT, "examples", "token_stream.cpp"), "-L" + d, "-l:" + name, "-Wl,-rpath," + d])
+    raw = api.Model(patterntagsuite.tagged_model(31)).to_vec()
+    model = str(tmp_path / "model.bin")
+    open(model, "wb").write(raw)
+    texts = patterntagsuite.docs(5, 80, lo=1, hi=40) + ["う", "", "AB０９", "漢字う"]
+    plain = api.VaporettoTokenizer(api.Model.read_slice(raw)[0], "DR")
+    surfaces = sorted({api.KyteaFullwidthFilter().filter(t.text) for doc in plain.token_stream_batch(texts) for t in doc})
+    keys = surfaces[::2]
+    vocab_file = str(tmp_path / "vocab.txt")
+    open(vocab_file, "w", encoding="utf-8").write("".join(k + "\n" for k in keys))
+    tok = api.VaporettoTokenizer(api.Model.read_slice(raw)[0], "DR", vocab=keys)
+    for doc_base in (0, 70000):
+        post = tok.index_batch(texts, doc_base)
+        want = "".join("%d\t%d\t%d\n" % (k, int(post.docs[q]), int(post.tfs[q])) for k in range(len(keys))
+                       for q in range(int(post.term_offsets[k]), int(post.term_offsets[k + 1]))) + "dropped\t%d\n" % post.n_dropped
+        out = subprocess.run([exe, model, "DR", "--postings", vocab_file] + ([str(doc_base)] if doc_base else []),
+                             input=("\n".join(texts) + "\n").encode("utf-8"), stdout=subprocess.PIPE, check=True, timeout=600).stdout.decode("utf-8")
+        assert out == want
+        assert len(post) >= 40 and post.n_dropped > 0 and len(out.splitlines()) == len(post) + 1
+    bad = subprocess.run([exe, model, "DR", "--postings", vocab_file, str(1 << 32)], input=b"a\n", stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert bad.returncode == 1 and b"doc_base + n_documents must not exceed 2^32" in bad.stderr
+
+
+def test_cpp_postings_and_index_on_the_emulated_sources(tmp_path):
+    from tests import emu
+    saved = _lib._lib
+    _lib._lib = emu.load()
+    devmem.EMULATED = True
+    try:
+        _check(emu.build_emulated(), tmp_path)
+    finally:
+        gc.collect()
+        devmem.EMULATED = False
+        _lib._lib = saved
+
+
+@pytest.mark.gpu
+def test_cpp_postings_and_index_on_the_gpu(tmp_path):
+    _check(_lib.LIB_PATH, tmp_path)

@@ -14,6 +14,7 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
   --ids: the vocabulary id pass (kernels_vocab.hip) on the span kernel's CSR by device events -- the vocabulary every other distinct surface of the
       first --vocab-docs documents -- as ms and ms per 100 K documents, and vpt_token_stream_ids_batch end to end (untagged route; its outputs are
       fresh pageable numpy arrays, the stream route's pinned) beside vpt_token_stream_batch; its ids must equal the device call's.
+  --postings: the postings pass (kernels_postings.hip: four launches, the sort and the scan) over the ids of --ids by device events, in the same run.
   --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
       --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
@@ -92,6 +93,7 @@ def main():
     ap.add_argument("--ids", action="store_true", help="also time the vocabulary id pass and vpt_token_stream_ids_batch")
     ap.add_argument("--vocab-docs", type=int, default=20000)
     ap.add_argument("--count", action="store_true", help="also time the vocabulary counter's count call (three launches) and finish once")
+    ap.add_argument("--postings", action="store_true", help="also time the postings pass over the id pass's ids (needs --ids)")
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -193,7 +195,40 @@ def main():
             row["ids"] = {"vocab_keys": len(keys), "vocab": vocab.info(), "ids_ms": round(med(r), 4), "ids_rounds_ms": [round(x, 4) for x in r],
                           "ids_spread": round((max(r) - min(r)) / min(r), 4), "ids_ms_per_100k_docs": round(med(r) * 1e5 / S, 4),
                           "known_share": round(float(np.mean(dev_ids != vocab.unk_id)), 4), "ids_over_spans": round(med(r) / k["spans_ms"], 3)}
-            del d_ids
+            if not args.postings:
+                del d_ids
+        if args.postings:   # the postings pass over the ids the id pass left, beside that id pass (the same run)
+            if not args.ids:
+                raise SystemExit("--postings needs --ids (the ids it groups, and the yardstick)")
+            n_terms = len(keys)
+            d_term = torch.empty(n_terms + 1, dtype=torch.int64, device=dev)
+            d_pdocs, d_ptfs = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev), torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
+            d_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+
+            def postings():
+                batch.postings(d_soff.data_ptr(), S, d_ids.data_ptr(), cap_ends, n_terms, 0, d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), cap_ends,
+                               0, 0, d_cnt.data_ptr(), stream)
+            for _ in range(2):
+                postings()
+            batch.sync()
+            r = []
+            for _ in range(args.rounds):
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); postings(); b.record()
+                torch.cuda.synchronize()
+                r.append(med([a.elapsed_time(b) for a, b in ev]))
+            batch.sync()
+            cnt = d_cnt.cpu().numpy()
+            term = d_term.cpu().numpy()
+            tf_sum = int(d_ptfs[:int(cnt[0])].to(torch.int64).sum().item())
+            row["postings"] = {"n_terms": n_terms, "postings": int(cnt[0]), "dropped": int(cnt[1]), "sort_passes": (n_terms.bit_length() + 7) // 8,
+                               "postings_ms": round(med(r), 4), "postings_rounds_ms": [round(x, 4) for x in r],
+                               "postings_spread": round((max(r) - min(r)) / min(r), 4), "postings_ms_per_100k_docs": round(med(r) * 1e5 / S, 4),
+                               "postings_over_ids": round(med(r) / row["ids"]["ids_ms"], 3),
+                               "tfs_plus_dropped_equal_tokens": bool(tf_sum + int(cnt[1]) == n_tokens),
+                               "term_offsets_end_equal_postings": bool(int(term[n_terms]) == int(cnt[0]) and int(term[0]) == 0)}
+            del d_ids, d_term, d_pdocs, d_ptfs, d_cnt
         if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run
             counter = api.VocabularyCounter(pred, args.count_keys)
 

@@ -135,6 +135,10 @@ SIGNATURES = {
     "vpt_vocab_count_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint, _P]),
     "vpt_vocab_counter_finish": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "vpt_token_stream_count_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, _P, C.c_uint]),
+    "vpt_postings_batch_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, _P, _P]),
+    "vpt_postings_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "vpt_token_stream_postings_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, _P, C.c_uint, C.c_uint64, _P, _P, _P, C.c_uint64,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),

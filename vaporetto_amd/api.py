@@ -801,6 +801,64 @@ class Predictor:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def postings_packed(self, token_offsets: np.ndarray, token_ids: np.ndarray, n_terms: int, doc_base: int = 0, positions: bool = False) -> "Postings":
+        """vpt_postings_batch_device over host arrays: token_offsets uint64 [n + 1] and token_ids int32 (what token_ids_packed / encode_batch
+        return) go to the device, the pass runs once, the segment's Postings come back.  positions: with `first` and `order` (the tokens of
+        every posting)."""
+        import torch
+        toff = np.ascontiguousarray(token_offsets, dtype=np.uint64)
+        ids = np.ascontiguousarray(token_ids, dtype=np.int32)
+        n_docs, n_tok, n_terms = len(toff) - 1, len(ids), int(n_terms)
+        if not 0 <= n_terms <= 1 << 24:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: n_terms: must be between 1 and 2^24")
+        dev = torch.device("cuda", self.device)
+
+        def d(n, dt):
+            return torch.zeros(max(n, 1), dtype=dt, device=dev)
+        d_toff = torch.from_numpy(toff.view(np.int64)).to(dev)
+        d_ids = torch.from_numpy(ids if n_tok else np.zeros(1, np.int32)).to(dev)
+        d_term, d_docs, d_tfs, d_cnt = d(n_terms + 1, torch.int64), d(n_tok, torch.int32), d(n_tok, torch.int32), d(2, torch.int64)
+        d_first, d_order = (d(n_tok + 1, torch.int64), d(n_tok, torch.int32)) if positions else (None, None)
+        batch = DeviceBatch(self)
+        batch.postings(d_toff.data_ptr(), n_docs, d_ids.data_ptr(), n_tok, n_terms, doc_base, d_term.data_ptr(), d_docs.data_ptr(), d_tfs.data_ptr(), n_tok,
+                       d_first.data_ptr() if positions else 0, d_order.data_ptr() if positions else 0, d_cnt.data_ptr(),
+                       torch.cuda.current_stream(dev).cuda_stream)
+        batch.sync()
+        cnt = d_cnt.cpu().numpy().view(np.uint64)
+        n_post = int(cnt[0])
+        first = d_first.cpu().numpy().view(np.uint64)[:n_post + 1].copy() if positions else None
+        return Postings(d_term.cpu().numpy().view(np.uint64)[:n_terms + 1].copy(), d_docs.cpu().numpy().view(np.uint32)[:n_post].copy(),
+                        d_tfs.cpu().numpy().view(np.uint32)[:n_post].copy(), first,
+                        d_order.cpu().numpy().view(np.uint32)[:int(first[n_post])].copy() if positions else None, int(cnt[1]))
+
+    def token_postings_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, vocab: "Vocabulary", wsconst: str = "", normalize: bool = True,
+                              tagger: Optional["PatternMatchTagger"] = None, stop: Optional["TagStopFilter"] = None, doc_base: int = 0,
+                              capacity: Optional[int] = None) -> "Postings":
+        """vpt_token_stream_postings_batch: documents in, the segment's Postings out (no `first` / `order`); n_terms is the vocabulary's key
+        count.  capacity: what the posting arrays hold (default: the text's bytes, which always suffices)."""
+        flags = wsconst_flags(wsconst, allow_graphemes=True)
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
+        S = len(byte_offsets) - 1
+        cap = (max(int(byte_offsets[-1] - byte_offsets[0]), 1) if S else 1) if capacity is None else int(capacity)
+        n_terms = vocab.info()["n_keys"] if vocab is not None else 0
+        term = np.zeros(n_terms + 1, np.uint64)
+        docs, tfs = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        n_post, n_drop = C.c_uint64(), C.c_uint64()
+        src = utf8 if len(utf8) else np.zeros(1, np.uint8)
+        st = _lib.load().vpt_token_stream_postings_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags,
+                                                         tagger.handle(self) if tagger is not None else None, stop.handle if stop is not None else None,
+                                                         vocab.handle if vocab is not None else None, _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0,
+                                                         int(doc_base), term.ctypes.data, docs.ctypes.data, tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_drop))
+        if st != _lib.VPT_OK:
+            try:
+                _raise(st)
+            except VaporettoError as e:
+                e.n_postings = int(n_post.value)   # (too small a capacity: the number needed)
+                raise
+        n = int(n_post.value)
+        return Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, int(n_drop.value))
+
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                          fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
         """Predictor::predict_tags over a packed batch (predictor.rs:546-637).  labels: uint8 per boundary (0/1/2).
@@ -1422,6 +1480,29 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def postings(self, d_token_offsets: int, n_documents: int, d_token_ids: int, capacity_in: int, n_terms: int, doc_base: int, d_term_offsets: int,
+                 d_post_docs: int, d_post_tfs: int, capacity_out: int, d_post_first: int = 0, d_token_order: int = 0, d_counts: int = 0,
+                 stream: int = 0) -> None:
+        """Device-resident postings of a finished CSR's ids (vpt_postings_batch_device): term -> (document, tf), term-major; d_post_first and
+        d_token_order both 0 (NULL) or neither.  Enqueues and returns; errors (a hostile CSR, more postings than capacity_out) at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("doc_base", doc_base, 1 << 64), ("capacity_in", capacity_in, 1 << 64),
+                             ("capacity_out", capacity_out, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_batch_device(self._p.handle, self._h, d_token_offsets or None, n_documents, d_token_ids or None, int(capacity_in),
+                                                   int(n_terms), int(doc_base), d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
+                                                   int(capacity_out), d_post_first or None, d_token_order or None, d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    @staticmethod
+    def postings_tile() -> int:
+        v = C.c_uint32()
+        st = _lib.load().vpt_postings_tile(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
     def concat_graphemes(self, d_utf8: int, d_boff: int, d_ooff: int, n_sentences: int, total_boundaries: int, d_labels: int, stream: int = 0) -> None:
         """Device-resident ConcatGraphemeClustersFilter on the labels at d_labels, in place (vpt_concat_graphemes_batch_device; the clusters of
         the KyteaFullwidthFilter image when set_flags / set_fullwidth say so); enqueues and returns."""
@@ -1816,6 +1897,35 @@ class VocabularyCounter:
         return [raw[int(offsets[k]):int(offsets[k + 1])].decode("utf-8") for k in range(len(counts))], counts
 
 
+class Postings:
+    """The postings of one batch (a segment), term-major (vpt_postings_batch_device): term k's postings are [term_offsets[k], term_offsets[k + 1])
+    of `docs` (doc_base + the document's index, ascending within a term) and `tfs`.  With positions: posting q's tokens are
+    order[first[q] : first[q + 1]], ascending token indices of the batch; else `first` and `order` are None.  n_dropped: the tokens whose id
+    was no term (negative or >= n_terms)."""
+
+    def __init__(self, term_offsets: np.ndarray, docs: np.ndarray, tfs: np.ndarray, first: Optional[np.ndarray], order: Optional[np.ndarray],
+                 n_dropped: int):
+        self.term_offsets, self.docs, self.tfs, self.first, self.order, self.n_dropped = term_offsets, docs, tfs, first, order, int(n_dropped)
+
+    def __len__(self) -> int:
+        return len(self.docs)
+
+    def df(self) -> np.ndarray:
+        """the document frequency of every term: uint64 [n_terms]"""
+        return np.diff(self.term_offsets)
+
+    def postings(self, term: int):
+        """(docs, tfs) of one term"""
+        a, b = int(self.term_offsets[term]), int(self.term_offsets[term + 1])
+        return self.docs[a:b], self.tfs[a:b]
+
+    def tokens(self, q: int) -> np.ndarray:
+        """the token indices of posting q, ascending (needs positions)"""
+        if self.first is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: tokens: the postings were made without positions")
+        return self.order[int(self.first[q]):int(self.first[q + 1])]
+
+
 class TaggedToken(TantivyToken):
     """A token of the tagged stream: TantivyToken plus `tags`, a tuple of Optional[str] per slot.  Under a stop filter `position` is the index
     before filtering and `position_length` the count before filtering."""
@@ -1928,6 +2038,15 @@ class VaporettoTokenizer:
         specials = list(specials)
         taken = set(specials)
         return Vocabulary(self._predictor, specials + [s for s in surfaces if s not in taken], unk_id)
+
+    def index_batch(self, texts: Sequence[str], doc_base: int = 0) -> "Postings":
+        """The postings of a batch of documents (a segment) over this tokenizer's vocabulary: term = vocabulary id, document = doc_base + the
+        text's index, tf = the term's tokens in it (vpt_token_stream_postings_batch; tagger and stop set included).  A token whose id is no
+        entry (unk_id outside the vocabulary) is counted in n_dropped.  Needs vocab=."""
+        if self._vocab is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: index_batch: the tokenizer has no vocab")
+        utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
+        return self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

@@ -1136,6 +1136,74 @@ vpt_status vpt_vocab_count_batch_device(const vpt_predictor* p, vpt_batch* b, vo
                               d_token_ends, capacity_in, flags, static_cast<hipStream_t>(hip_stream));
 }
 
+// ---- postings of a finished CSR's ids (kernels_postings.hip): keys, the trainer's sort, heads, the trainer's scan, emit and terms
+vpt_status vpt_postings_tile(uint32_t* n_tokens) {
+    if (!n_tokens) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    // (the constant is the sort's tile: one tile of histograms up to it, two behind it)
+    if (vpt::train_radix_scratch(vpt::kPostingsSortTile) != 256 || vpt::train_radix_scratch(uint64_t(vpt::kPostingsSortTile) + 1) != 512)
+        return fail(VPT_RUNTIME_ERROR, "vpt_postings_tile: kPostingsSortTile is not the sort's tile");
+    *n_tokens = vpt::kPostingsSortTile;
+    return VPT_OK;
+}
+
+namespace vptc {
+vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, const int32_t* d_token_ids,
+                           uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base, uint64_t* d_term_offsets, uint32_t* d_post_docs, uint32_t* d_post_tfs,
+                           uint64_t capacity_out, uint64_t* d_post_first, uint32_t* d_token_order, uint64_t* d_counts, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!d_token_offsets || !d_token_ids || !d_term_offsets || !d_post_docs || !d_post_tfs || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if ((d_post_first == nullptr) != (d_token_order == nullptr))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: post_first / token_order: both or neither");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (capacity_in >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+    if (doc_base > (1ull << 32) || uint64_t(n_documents) > (1ull << 32) - doc_base)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    VPT_HIP(hipSetDevice(p->device));
+    VPT_HIP(hipMemsetAsync(d_counts, 0, 16, stream));
+    if (n_documents == 0) {   // no document owns a token: no posting
+        VPT_HIP(hipMemsetAsync(d_term_offsets, 0, 8 * (size_t(n_terms) + 1), stream));
+        if (d_post_first) VPT_HIP(hipMemsetAsync(d_post_first, 0, 8, stream));
+        b->last_stream = stream; b->pending = true;
+        return VPT_OK;
+    }
+    // the scratch in 256-byte sections: keydoc | order | skey | flags | scan | hist | hist_scan | the scans' partials
+    const uint64_t n = capacity_in, nh = vpt::train_radix_scratch(n);
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_keydoc = 0, o_order = o_keydoc + pad(8 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
+                 o_scan = o_flags + pad(4 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
+                 o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
+                 total = o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
+    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    unsigned char* m = b->d_post;
+    vpt::PostingsParams P{};
+    P.token_offsets = d_token_offsets; P.n_docs = n_documents; P.ids = d_token_ids; P.capacity_in = capacity_in; P.n_terms = n_terms; P.doc_base = doc_base;
+    P.keydoc = reinterpret_cast<uint32_t*>(m + o_keydoc); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
+    P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+    P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.capacity_out = capacity_out; P.post_first = d_post_first;
+    P.token_order = d_token_order; P.counts = d_counts; P.status = b->d_ctrl;
+    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
+    uint32_t passes[4], n_passes = 0;   // the bytes of the values 0 .. n_terms, least significant first
+    for (uint32_t v = n_terms; v; v >>= 8, ++n_passes) passes[n_passes] = 8 * n_passes;
+    VPT_HIP(vpt::launch_postings_keys(P, stream));
+    VPT_HIP(vpt::train_radix_sort(P.keydoc, 2, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
+                                  reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
+    VPT_HIP(vpt::launch_postings_heads(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_emit(P, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_postings_batch_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents,
+                                     const int32_t* d_token_ids, uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base, uint64_t* d_term_offsets,
+                                     uint32_t* d_post_docs, uint32_t* d_post_tfs, uint64_t capacity_out, uint64_t* d_post_first, uint32_t* d_token_order,
+                                     uint64_t* d_counts, void* hip_stream) {
+    return postings_device(p, b, d_token_offsets, n_documents, d_token_ids, capacity_in, n_terms, doc_base, d_term_offsets, d_post_docs, d_post_tfs,
+                           capacity_out, d_post_first, d_token_order, d_counts, static_cast<hipStream_t>(hip_stream));
+}
+
 // A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them
 // (vocab_count.hpp).  Counting may go on afterwards.
 vpt_status vpt_vocab_counter_finish(void* counter, uint64_t min_count, uint64_t max_entries, const uint8_t** surfaces, const uint64_t** offsets,

@@ -938,6 +938,80 @@ vpt_status vpt_token_stream_count_batch(const vpt_predictor* p, const uint8_t* u
                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
+// Documents in, the segment's postings out: the id stream's steps into buffers of this call (a token has a byte at least, so the text's bytes
+// bound the tokens), then the WHOLE batch's token_offsets and ids to the device and the postings pass once over them -- the ids make one trip to
+// the host and back, and the result cannot depend on how the stream was cut into chunks.
+vpt_status vpt_token_stream_postings_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                           unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab, unsigned vocab_flags,
+                                           uint64_t doc_base, uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out,
+                                           uint64_t capacity, uint64_t* n_postings_out, uint64_t* n_dropped_out) {
+    if (n_postings_out) *n_postings_out = 0;
+    if (n_dropped_out) *n_dropped_out = 0;
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    const vpt_vocab* v = static_cast<const vpt_vocab*>(vocab);
+    if (!v) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: must not be NULL");
+    if (v->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: does not belong to this predictor");
+    if (!term_offsets_out || !n_postings_out || !n_dropped_out || (capacity && (!post_docs_out || !post_tfs_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (v->n_keys == 0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (doc_base > (1ull << 32) || uint64_t(n_documents) > (1ull << 32) - doc_base)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    const uint32_t n_terms = v->n_keys;
+    std::fill(term_offsets_out, term_offsets_out + size_t(n_terms) + 1, uint64_t(0));
+    if (n_documents == 0) return VPT_OK;
+    if (!utf8 || !byte_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (byte_offsets[n_documents] < byte_offsets[0]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
+    const uint64_t cap_tok = byte_offsets[n_documents] - byte_offsets[0];
+    if (cap_tok >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+    const bool tagged = tagger || stop;
+    const uint32_t nt = tagged ? p->n_tags : 0u;
+    std::vector<uint64_t> toff;
+    std::vector<uint32_t> starts, ends, pos;
+    std::vector<int32_t> tags, ids;
+    try {
+        toff.resize(n_documents + 1);
+        starts.resize(size_t(cap_tok) + 1); ends.resize(size_t(cap_tok) + 1); pos.resize(size_t(cap_tok) + 1); ids.resize(size_t(cap_tok) + 1);
+        tags.resize(size_t(cap_tok) * nt + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory");
+    }
+    vpt_status st = token_stream_chunks(p, utf8, byte_offsets, n_documents, wsconst_flags, tagged, tagger, stop, v, vocab_flags, nullptr, toff.data(),
+                                        starts.data(), ends.data(), pos.data(), tags.data(), ids.data(), cap_tok);
+    if (st != VPT_OK) return st;
+    const uint64_t n_tok = toff[n_documents];
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    // one allocation of this call, 256-byte sections: token_offsets | ids | term_offsets | docs | tfs | counts
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_toff = 0, o_ids = o_toff + pad(8 * (n_documents + 1)), o_term = o_ids + pad(4 * size_t(n_tok) + 4),
+                 o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_tok) + 4), o_cnt = o_tfs + pad(4 * size_t(n_tok) + 4),
+                 total = o_cnt + 256;
+    DevBuf<unsigned char> mem;
+    if ((st = mem.alloc(total)) != VPT_OK) return st;
+    unsigned char* m = mem;
+    VPT_HIP(hipMemcpyAsync(m + o_toff, toff.data(), 8 * (n_documents + 1), hipMemcpyHostToDevice, s));
+    if (n_tok) VPT_HIP(hipMemcpyAsync(m + o_ids, ids.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
+    st = postings_device(p, b, reinterpret_cast<const uint64_t*>(m + o_toff), n_documents, reinterpret_cast<const int32_t*>(m + o_ids), n_tok, n_terms, doc_base,
+                         reinterpret_cast<uint64_t*>(m + o_term), reinterpret_cast<uint32_t*>(m + o_docs), reinterpret_cast<uint32_t*>(m + o_tfs), n_tok,
+                         nullptr, nullptr, reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    uint64_t counts[2] = {0, 0};
+    VPT_HIP(hipMemcpy(counts, m + o_cnt, 16, hipMemcpyDeviceToHost));
+    *n_postings_out = counts[0];
+    *n_dropped_out = counts[1];
+    if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
+    VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms) + 1), hipMemcpyDeviceToHost));
+    if (counts[0]) {
+        VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+    }
+    return VPT_OK;
+}
+
 // ---- pinned host memory for callers that want the PCIe link at full rate
 vpt_status vpt_host_alloc(size_t bytes, void** out) {
     if (!out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out: must not be NULL");

@@ -305,6 +305,7 @@ struct vpt_vocab_counter {
     std::vector<uint64_t> offsets, counts;
 };
 constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: full (max_keys / arena_chars)";
+constexpr const char* kPostingsTooSmall = "InvalidArgumentError: capacity: smaller than the number of postings";
 
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
@@ -384,6 +385,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
+    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams)
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -524,6 +526,7 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrBadTokenCsr)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: token_offsets / token_starts / token_ends: do not describe the documents' tokens");
     if (bits & vpt::kErrVocabCounterFull) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    if (bits & vpt::kErrPostingsTooSmall) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
 
@@ -710,6 +713,10 @@ vpt_status token_ids_device(const vpt_predictor* p, vpt_batch* b, const vpt_voca
 vpt_status vocab_count_device(const vpt_predictor* p, vpt_batch* b, vpt_vocab_counter* counter, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                               size_t n_documents, const uint64_t* d_token_offsets, const uint32_t* d_token_starts, const uint32_t* d_token_ends,
                               uint64_t capacity_in, unsigned flags, hipStream_t stream);
+// The postings pass over a finished CSR's ids (vpt_postings_batch_device; kernels_postings.hip)
+vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, const int32_t* d_token_ids,
+                           uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base, uint64_t* d_term_offsets, uint32_t* d_post_docs, uint32_t* d_post_tfs,
+                           uint64_t capacity_out, uint64_t* d_post_first, uint32_t* d_token_order, uint64_t* d_counts, hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

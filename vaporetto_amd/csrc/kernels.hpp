@@ -68,6 +68,7 @@ constexpr uint32_t kPartialErrNoChar = 1u, kPartialErrNul = 2u, kPartialErrChar 
 constexpr uint32_t kErrBadLabel = 256u;       // the partial-annotation writer: a label that is no CharacterBoundary (above 2)
 constexpr uint32_t kErrBadTokenCsr = 512u;    // the id pass: token_offsets / starts / ends that do not describe the documents (kernels_vocab.hip)
 constexpr uint32_t kErrVocabCounterFull = 1024u;   // the vocabulary counter: more keys or chars than it was made for (kernels_vocab_count.hip)
+constexpr uint32_t kErrPostingsTooSmall = 2048u;   // the postings pass: more postings than capacity_out (kernels_postings.hip)
 
 
 struct ScoreParams {
@@ -327,6 +328,37 @@ struct VocabCountParams {
 hipError_t launch_vocab_count(const VocabCountParams& P, hipStream_t stream);
 // one launch, a lane per slot: out[0 .. ctrl[kVcOut]) for every committed key of count >= min_count (ctrl[kVcOut] zero before)
 hipError_t launch_vocab_count_finish(const VocabCounterView& C, uint64_t min_count, hipStream_t stream);
+// Postings of a finished span CSR's ids (kernels_postings.hip): term -> (document, tf), term-major, by one stable sort of the capacity_in places
+// by key (the id, or the sentinel n_terms for a dropped token and for a place behind the tokens) and a run-length pass.  Scratch of the batch,
+// 28 bytes a place and the sort's histograms (16 bytes per 16 places): keydoc [2 * capacity_in] {key, document}; order, skey, flags
+// [capacity_in]; scan [capacity_in + 1].  The caller runs train_radix_sort (keydoc, stride 2 -> order; skey is its second index array) between
+// keys and heads, and train_scan (flags -> scan) between heads and emit.
+constexpr uint32_t kPostingsSortTile = 4096;   // the tile of train_radix_sort and train_scan (vpt_postings_tile checks it against them)
+constexpr uint32_t kPostingsMaxTerms = 1u << 24;
+struct PostingsParams {
+    const uint64_t* token_offsets;  // [n_docs + 1]
+    uint64_t n_docs;
+    const int32_t* ids;             // [capacity_in]
+    uint64_t capacity_in;
+    uint32_t n_terms;
+    uint64_t doc_base;
+    uint32_t* keydoc;
+    uint32_t* order;
+    uint32_t* skey;
+    uint32_t* flags;
+    uint64_t* scan;
+    uint64_t* term_offsets;         // [n_terms + 1]
+    uint32_t* post_docs;            // [capacity_out]
+    uint32_t* post_tfs;             // [capacity_out]
+    uint64_t capacity_out;
+    uint64_t* post_first;           // [capacity_out + 1] or nullptr
+    uint32_t* token_order;          // [capacity_in] or nullptr
+    uint64_t* counts;               // [2]: postings (written), dropped tokens (added to: zero before the launches)
+    uint32_t* status;
+};
+hipError_t launch_postings_keys(const PostingsParams& P, hipStream_t stream);
+hipError_t launch_postings_heads(const PostingsParams& P, hipStream_t stream);
+hipError_t launch_postings_emit(const PostingsParams& P, hipStream_t stream);   // emit, then the terms
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
