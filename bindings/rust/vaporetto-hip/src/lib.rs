@@ -431,7 +431,7 @@ impl<'p> Vocabulary<'p> {
         })?;
         docs.truncate(n_postings as usize);
         tfs.truncate(n_postings as usize);
-        Ok(Postings { term_offsets, docs, tfs, n_dropped })
+        Ok(Postings { term_offsets, docs, tfs, n_dropped, n_combined: 0 })
     }
 }
 
@@ -443,9 +443,49 @@ pub struct Postings {
     pub docs: Vec<u32>,
     pub tfs: Vec<u32>,
     pub n_dropped: u64,
+    /// After `merge`: the input postings that were combined into another.
+    pub n_combined: u64,
+}
+
+/// `vpt_postings_segment` of include/vaporetto_hip.h, field by field (host pointers for `vpt_postings_merge`).
+#[repr(C)]
+struct PostingsSegment {
+    term_offsets: *const u64,
+    docs: *const u32,
+    tfs: *const u32,
+    n_terms: u32,
+    capacity: u64,
 }
 
 impl Postings {
+    /// The merge of segments that share a term id space (`vpt_postings_merge`): per term the union of their lists by document, a document
+    /// that stands in several of them one posting whose tf is the sum; `n_dropped` the segments' sum.  `ordered`: the promise that every
+    /// segment's documents are above those of the one before -- checked on the device, no sort.  `n_terms`: the merged term count, at least
+    /// every segment's.  The segments' arrays must belong together: checked here.
+    pub fn merge(predictor: &Predictor, segments: &[Postings], ordered: bool, n_terms: u32) -> Result<Postings> {
+        let mut segs = Vec::with_capacity(segments.len());
+        let mut cap = 0usize;
+        for s in segments {
+            let n = s.term_offsets.len();
+            if n == 0 || n - 1 > n_terms as usize || s.docs.len() != s.tfs.len() || s.term_offsets[n - 1] > s.docs.len() as u64 {
+                return Err(HipError::InvalidArgument("InvalidArgumentError: merge: a segment's arrays do not belong together".into()));
+            }
+            segs.push(PostingsSegment { term_offsets: s.term_offsets.as_ptr(), docs: s.docs.as_ptr(), tfs: s.tfs.as_ptr(), n_terms: (n - 1) as u32,
+                                        capacity: s.docs.len() as u64 });
+            cap += s.docs.len();
+        }
+        let mut term_offsets = vec![0u64; n_terms as usize + 1];
+        let (mut docs, mut tfs) = (vec![0u32; cap + 1], vec![0u32; cap + 1]);
+        let (mut n_postings, mut n_combined) = (0u64, 0u64);
+        check(unsafe {
+            ffi::vpt_postings_merge(predictor.raw, segs.as_ptr() as *const std::ffi::c_void, segs.len(), n_terms, if ordered { 1 } else { 0 },
+                                    term_offsets.as_mut_ptr(), docs.as_mut_ptr(), tfs.as_mut_ptr(), cap as u64, &mut n_postings, &mut n_combined)
+        })?;
+        docs.truncate(n_postings as usize);
+        tfs.truncate(n_postings as usize);
+        Ok(Postings { term_offsets, docs, tfs, n_dropped: segments.iter().map(|s| s.n_dropped).sum(), n_combined })
+    }
+
     /// The document frequency of `term`.
     pub fn df(&self, term: usize) -> u64 {
         self.term_offsets[term + 1] - self.term_offsets[term]

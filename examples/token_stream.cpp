@@ -14,6 +14,8 @@
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] < documents.txt
 // With --postings (beyond the adapter): the documents are one segment; one line per posting, by term, then by document:
 // term <TAB> document <TAB> tf, the document being doc_base + the line's index; then one line "dropped <TAB> n" for the tokens that are no entry.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] --segment-docs N < documents.txt
+// With --segment-docs N: N documents are indexed a segment, and the segments are merged on the device; the output is the same.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -71,7 +73,19 @@ int main(int argc, char** argv) {
             const vaporetto_hip::Vocabulary vocab(plain.predictor(), surfaces);
             std::vector<std::string> docs;
             for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
-            const vaporetto_hip::Postings post = plain.index(docs, vocab, argc > 5 ? std::strtoull(argv[5], nullptr, 10) : 0);
+            size_t segment_docs = 0;
+            int n_args = argc;
+            if (argc > 6 && std::strcmp(argv[argc - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[argc - 1], nullptr, 10); n_args = argc - 2; }
+            const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
+            vaporetto_hip::Postings post;
+            if (segment_docs) {
+                std::vector<std::vector<std::string>> batches;
+                for (size_t a = 0; a < docs.size(); a += segment_docs)
+                    batches.emplace_back(docs.begin() + a, docs.begin() + std::min(docs.size(), a + segment_docs));
+                post = plain.index(batches, vocab, doc_base);
+            } else {
+                post = plain.index(docs, vocab, doc_base);
+            }
             for (size_t k = 0; k < post.n_terms(); ++k)
                 for (uint64_t q = post.term_offsets[k]; q < post.term_offsets[k + 1]; ++q)
                     std::printf("%zu\t%u\t%u\n", k, unsigned(post.docs[size_t(q)]), unsigned(post.tfs[size_t(q)]));

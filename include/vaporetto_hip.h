@@ -607,8 +607,8 @@ vpt_status vpt_token_stream_count_batch(const vpt_predictor *p, const uint8_t *u
  * Postings on the device: term -> (document, tf) lists from token ids           (no item of the adapter: what the index writer behind its token
  *                                                      stream does first -- here one int32 per token never has to reach the host to be grouped)
  *
- * vpt_postings_batch_device: the postings of one batch (a SEGMENT: doc_base makes its document numbers global, merging segments is the caller's
- *   job) from a FINISHED span CSR -- d_token_offsets [n_documents + 1] and capacity_in as vpt_token_ids_batch_device takes them, a document may own
+ * vpt_postings_batch_device: the postings of one batch (a SEGMENT: doc_base makes its document numbers global, vpt_postings_merge_device below
+ *   merges segments) from a FINISHED span CSR -- d_token_offsets [n_documents + 1] and capacity_in as vpt_token_ids_batch_device takes them, a document may own
  *   no token, the tokens are min(token_offsets[n], capacity_in) -- and d_token_ids [capacity_in], what that call wrote.  It reads those two arrays
  *   and nothing else.  Token t of document d is INDEXED when 0 <= ids[t] < n_terms; every other token (negative, >= n_terms) adds 1 to
  *   d_counts[1] and appears nowhere else.  THE PASS SEES IDS ONLY: a vocabulary's unk_id chosen inside [0, n_terms) is a term like any other.
@@ -644,6 +644,65 @@ vpt_status vpt_token_stream_postings_batch(const vpt_predictor *p, const uint8_t
                                            unsigned wsconst_flags, const void *tagger, const void *stop, const void *vocab, unsigned vocab_flags,
                                            uint64_t doc_base, uint64_t *term_offsets_out, uint32_t *post_docs_out, uint32_t *post_tfs_out,
                                            uint64_t capacity, uint64_t *n_postings_out, uint64_t *n_dropped_out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Merging postings segments on the device                       (no item of the adapter: a corpus indexed in batches ends in ONE index that never
+ *                                                                left the device -- the 28 bytes per token of the postings pass bound a batch)
+ *
+ * vpt_postings_segment: a segment as vpt_postings_batch_device (or this call) left it.  The number of its postings stays on the device --
+ *   d_term_offsets[n_terms], read there -- so K postings calls and the merge behind them need no sync in between; `capacity` bounds it. */
+typedef struct vpt_postings_segment {
+    const uint64_t *d_term_offsets;   /* [n_terms + 1]                                                         */
+    const uint32_t *d_post_docs;      /* [capacity], global document numbers                                   */
+    const uint32_t *d_post_tfs;       /* [capacity]                                                            */
+    uint32_t        n_terms;          /* <= n_terms_out; terms at or above it have no postings here            */
+    uint64_t        capacity;         /* the size of the two arrays; the postings: d_term_offsets[n_terms]     */
+} vpt_postings_segment;
+/* VPT_POSTINGS_MERGE_ORDERED: the caller's promise that every document of segment s is below every document of the next segment that has
+ *   postings (what ascending doc_bases give).  The device CHECKS it. */
+enum { VPT_POSTINGS_MERGE_ORDERED = 1 };
+/* vpt_postings_merge_device: `segments` is a HOST array of n_segments vpt_postings_segment structs -- 1 .. 1024, vpt_postings_merge_limits; read during the
+ *   call, it may go afterwards -- whose pointers are device pointers; the segments share the term id space [0, n_terms_out).  One segment comes
+ *   out, in the three arrays and with the guarantees of vpt_postings_batch_device: for every term k the merged list is the union of the
+ *   segments' lists of k, ordered by document; a document that stands in several segments' lists of k is ONE posting whose tf is the sum.
+ *   d_term_offsets_out[0] = 0, d_term_offsets_out[n_terms_out] = d_counts[0] = the merged postings; d_counts[1] = the input postings that were
+ *   combined into another (input minus output postings; 0 when no document repeats).  So: however a batch's indexed tokens are dealt out to
+ *   segments, the merge of the segments' postings is, byte for byte, what the one-pass call over the whole batch writes.  The optional token
+ *   lists (post_first / token_order) are not merged: token indices are local to a segment.
+ *   flags = VPT_POSTINGS_MERGE_ORDERED: no sort; the merged list of a term is the segments' lists one after another.  Three launches over the
+ *   scratch: a lane per term bound sums the K term_offsets columns and leaves every segment's base inside the term (a K x (n_terms_out + 1)
+ *   table of 8-byte words, read and written coalesced across terms); a lane per input place (the sum of the capacities) finds its segment and
+ *   its term by bisection and copies its posting; the segments' smallest and largest documents (integer atomic min / max) are compared.  A
+ *   broken promise: "InvalidArgumentError: segments: document ranges overlap or descend" at the sync, the outputs unspecified.
+ *   flags = 0: any document numbers, repeats combined.  A {term, document, tf} record per input place, the trainer's stable radix sort over
+ *   the document word (4 passes) and the term word (ceil(bit_width(n_terms_out) / 8) passes), heads, the trainer's scan, emit (the tf a sum
+ *   over the run) and terms, as in the postings pass.
+ *   Both: asynchronous on hip_stream, errors at vpt_batch_sync; launch sizes come from the capacities; no atomic decides a value and two runs
+ *   give identical bytes.  THE OUTPUTS MUST NOT ALIAS THE INPUTS.  Scratch of the workspace: 48 bytes per segment, and ordered 8 bytes per
+ *   segment and 8 bytes per (segment, term bound) -- 8 * n_segments * (n_terms_out + 1) --, general 32 bytes per input place (three record
+ *   words, two index words, a flag, a scan word) and 16 bytes per 16 places of histograms.
+ *   At the call, VPT_INVALID_ARGUMENT: a NULL pointer (a segment's three included, whatever its capacity), n_segments == 0 or > 1024,
+ *   n_terms_out == 0 or > 2^24, a segment's n_terms > n_terms_out, a sum of capacities >= 2^32, an unknown flag bit, a workspace of another
+ *   predictor.
+ *   At the sync, VPT_INVALID_ARGUMENT: "InvalidArgumentError: segment: term_offsets or postings are not a segment's" -- a segment's
+ *   term_offsets do not start at 0, decrease or end above its capacity, or inside one term's list documents do not strictly ascend or a tf
+ *   is 0; "InvalidArgumentError: tf: sum exceeds 32 bits"; "InvalidArgumentError: capacity: smaller than the number of postings" when there are
+ *   more than capacity_out merged postings -- d_counts[0] then holds the number needed, the postings below capacity_out are written and
+ *   nothing behind them.  capacity_out >= the sum of the capacities always suffices.  Whatever the arrays hold, nothing is read outside
+ *   term_offsets[0 .. n_terms] and [0, capacity) of each segment, and nothing is written outside d_term_offsets_out [n_terms_out + 1],
+ *   d_post_docs_out / d_post_tfs_out [capacity_out], d_counts [2] and the workspace.
+ * vpt_postings_merge_limits: the most segments a call takes.
+ * vpt_postings_merge: the same over HOST arrays: `segments` with host pointers, each segment's postings term_offsets[n_terms] (at most its
+ *   capacity) read here; host arrays out.  More than `capacity` merged postings: VPT_INVALID_ARGUMENT with the message above,
+ *   *n_postings_out = the number needed, nothing else written.  Returns when the device is through.
+ * (`segments` is declared const void * as the other struct arguments of this header are; pass a const vpt_postings_segment *.) */
+vpt_status vpt_postings_merge_device(const vpt_predictor *p, vpt_batch *b, const void *segments, size_t n_segments, uint32_t n_terms_out,
+                                     unsigned flags, uint64_t *d_term_offsets_out, uint32_t *d_post_docs_out, uint32_t *d_post_tfs_out,
+                                     uint64_t capacity_out, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_merge_limits(uint32_t *max_segments);
+vpt_status vpt_postings_merge(const vpt_predictor *p, const void *segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                              uint64_t *term_offsets_out, uint32_t *post_docs_out, uint32_t *post_tfs_out, uint64_t capacity,
+                              uint64_t *n_postings_out, uint64_t *n_combined_out);
 
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no

@@ -18,6 +18,7 @@
 #ifndef VAPORETTO_HIP_HPP
 #define VAPORETTO_HIP_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <optional>
@@ -463,7 +464,37 @@ struct Postings {
     uint64_t n_dropped = 0;
     size_t n_terms() const { return term_offsets.size() - 1; }
     uint64_t df(size_t term) const { return term_offsets[term + 1] - term_offsets[term]; }
+    uint64_t n_combined = 0;   // merge: the input postings that were combined into another
+    // The merge of segments that share a term id space (vpt_postings_merge): per term the union of their lists by document, a document that
+    // stands in several of them one posting whose tf is the sum; n_dropped the segments' sum.  ordered: the promise that every segment's
+    // documents are above those of the one before -- checked on the device, no sort.  n_terms: the merged term count (0: the largest of the
+    // segments').  No token lists: token indices are local to a segment.
+    static Postings merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered = false, size_t n_terms = 0);
 };
+
+inline Postings Postings::merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered, size_t n_terms) {
+    std::vector<vpt_postings_segment> segs(segments.size());
+    size_t cap = 0;
+    Postings out;
+    for (size_t k = 0; k < segments.size(); ++k) {
+        const Postings& s = segments[k];
+        if (s.term_offsets.empty() || s.docs.size() != s.tfs.size())
+            throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: merge: a segment's arrays do not belong together");
+        segs[k] = vpt_postings_segment{s.term_offsets.data(), s.docs.data(), s.tfs.data(), uint32_t(s.n_terms()), uint64_t(s.docs.size())};
+        n_terms = std::max(n_terms, s.n_terms());
+        cap += s.docs.size();
+        out.n_dropped += s.n_dropped;
+    }
+    out.term_offsets.assign(n_terms + 1, 0);
+    out.docs.resize(cap + 1);
+    out.tfs.resize(cap + 1);
+    uint64_t n_postings = 0;
+    detail::check(vpt_postings_merge(predictor.raw(), segs.data(), segs.size(), uint32_t(n_terms), ordered ? unsigned(VPT_POSTINGS_MERGE_ORDERED) : 0u,
+                                     out.term_offsets.data(), out.docs.data(), out.tfs.data(), cap, &n_postings, &out.n_combined));
+    out.docs.resize(size_t(n_postings));
+    out.tfs.resize(size_t(n_postings));
+    return out;
+}
 
 inline std::vector<std::string> Predictor::tokenize(const std::vector<std::string>& lines, bool tagged, unsigned flags, const PatternMatchTagger* tagger) const {
     std::vector<std::string> out;
@@ -635,6 +666,18 @@ public:
         out.docs.resize(size_t(n_postings));
         out.tfs.resize(size_t(n_postings));
         return out;
+    }
+
+    // The postings of a corpus given as batches of texts: every batch a segment (index above) with a running doc_base, the segments merged on
+    // the device by the ordered route (Postings::merge).  Equal to index of the concatenation.
+    Postings index(const std::vector<std::vector<std::string>>& batches, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true) const {
+        std::vector<Postings> segments;
+        for (const std::vector<std::string>& texts : batches) {
+            segments.push_back(index(texts, vocab, doc_base, normalize));
+            doc_base += texts.size();
+        }
+        if (segments.empty()) return index(std::vector<std::string>(), vocab, doc_base, normalize);
+        return Postings::merge(predictor_, segments, true, vocab.size());
     }
 
 private:

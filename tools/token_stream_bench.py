@@ -15,6 +15,9 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       first --vocab-docs documents -- as ms and ms per 100 K documents, and vpt_token_stream_ids_batch end to end (untagged route; its outputs are
       fresh pageable numpy arrays, the stream route's pinned) beside vpt_token_stream_batch; its ids must equal the device call's.
   --postings: the postings pass (kernels_postings.hip: four launches, the sort and the scan) over the ids of --ids by device events, in the same run.
+  --merge K[,K..]: with --postings, the batch's documents as K equal ranges: the K segment calls, the ordered and the general merge
+      (kernels_postings_merge.hip) and a device-to-device copy of the bytes the ordered merge must move, each the median of --rounds rounds of
+      --steps calls by device events, beside the one-pass call of the same run (profiles/postings_merge_bench.json).
   --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
       --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
@@ -82,6 +85,70 @@ def med(xs):
     return float(np.median(xs))
 
 
+def merge_rows(torch, batch, stream, dev, args, K, S, n_terms, dev_off, d_soff, d_ids, d_term, d_pdocs, d_ptfs, n_post, one_pass_ms):
+    """--merge K: the batch's documents in K equal ranges, each a segment of the postings call (its token_offsets rebased to 0, its ids and its
+    posting arrays slices of the batch's, doc_base its first document); by device events: the K segment calls together, the ordered merge, the
+    general merge, and device-to-device copies of as many bytes as the ordered merge must move (8 bytes a posting in and out, the K
+    term_offsets arrays in -- a copy of B bytes moves B in and B out, so 8 * postings and 4 * K * (n_terms + 1) bytes are copied).  The ordered
+    merge's three arrays must be the one-pass call's bytes."""
+    cuts = [S * s // K for s in range(K + 1)]
+    tok = [int(dev_off[c]) for c in cuts]
+    seg_off = [(d_soff[a:b + 1] - d_soff[a]).contiguous() for a, b in zip(cuts, cuts[1:])]
+    seg_term = torch.empty(K * (n_terms + 1), dtype=torch.int64, device=dev)
+    seg_docs, seg_tfs = torch.empty(tok[-1] + 1, dtype=torch.int32, device=dev), torch.empty(tok[-1] + 1, dtype=torch.int32, device=dev)
+    seg_cnt = torch.zeros(2 * K, dtype=torch.int64, device=dev)
+    out_term = torch.empty(n_terms + 1, dtype=torch.int64, device=dev)
+    out_docs, out_tfs = torch.empty(tok[-1] + 1, dtype=torch.int32, device=dev), torch.empty(tok[-1] + 1, dtype=torch.int32, device=dev)
+    out_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    descr = [(seg_term.data_ptr() + 8 * s * (n_terms + 1), seg_docs.data_ptr() + 4 * tok[s], seg_tfs.data_ptr() + 4 * tok[s], n_terms, tok[s + 1] - tok[s])
+             for s in range(K)]
+
+    def segments():
+        for s in range(K):
+            batch.postings(seg_off[s].data_ptr(), cuts[s + 1] - cuts[s], d_ids.data_ptr() + 4 * tok[s], tok[s + 1] - tok[s], n_terms, cuts[s], descr[s][0],
+                           descr[s][1], descr[s][2], tok[s + 1] - tok[s], 0, 0, seg_cnt.data_ptr() + 16 * s, stream)
+
+    def merge(ordered):
+        batch.merge_postings(descr, n_terms, out_term.data_ptr(), out_docs.data_ptr(), out_tfs.data_ptr(), tok[-1], out_cnt.data_ptr(), ordered, stream)
+    a_post, b_post = torch.empty(2 * n_post + 2, dtype=torch.int32, device=dev), torch.empty(2 * n_post + 2, dtype=torch.int32, device=dev)
+    a_term, b_term = torch.empty(K * (n_terms + 1) // 2 + 1, dtype=torch.int64, device=dev), torch.empty(K * (n_terms + 1) // 2 + 1, dtype=torch.int64, device=dev)
+
+    def floor():
+        b_post.copy_(a_post)
+        b_term.copy_(a_term)
+    segments()
+    batch.sync()
+    out = {"K": K, "n_terms": n_terms, "input_places": tok[-1], "postings": n_post, "table_bytes": 8 * K * (n_terms + 1),
+           "floor_bytes_copied": 8 * n_post + 4 * K * (n_terms + 1), "one_pass_ms": one_pass_ms}
+    for name, fn in (("segments", segments), ("ordered", lambda: merge(True)), ("general", lambda: merge(False)), ("floor", floor)):
+        fn()
+        batch.sync()
+        if name == "ordered":
+            n = int(out_cnt[0].item())
+            out["ordered_equals_one_pass"] = bool(n == n_post and int(out_cnt[1].item()) == 0 and torch.equal(out_term, d_term)
+                                                  and torch.equal(out_docs[:n], d_pdocs[:n]) and torch.equal(out_tfs[:n], d_ptfs[:n]))
+        if name == "general":
+            n = int(out_cnt[0].item())
+            out["general_equals_one_pass"] = bool(n == n_post and int(out_cnt[1].item()) == 0 and torch.equal(out_term, d_term)
+                                                  and torch.equal(out_docs[:n], d_pdocs[:n]) and torch.equal(out_tfs[:n], d_ptfs[:n]))
+        r = []
+        for _ in range(args.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in ev:
+                a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            r.append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        out[name + "_ms"] = round(med(r), 4)
+        out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+    for name in ("ordered", "general"):
+        out[name + "_over_floor"] = round(out[name + "_ms"] / out["floor_ms"], 2)
+        out[name + "_over_one_pass"] = round(out[name + "_ms"] / one_pass_ms, 3)
+    out["segments_plus_ordered_over_one_pass"] = round((out["segments_ms"] + out["ordered_ms"]) / one_pass_ms, 3)
+    out["segments_over_one_pass"] = round(out["segments_ms"] / one_pass_ms, 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="2,5")
@@ -94,6 +161,7 @@ def main():
     ap.add_argument("--vocab-docs", type=int, default=20000)
     ap.add_argument("--count", action="store_true", help="also time the vocabulary counter's count call (three launches) and finish once")
     ap.add_argument("--postings", action="store_true", help="also time the postings pass over the id pass's ids (needs --ids)")
+    ap.add_argument("--merge", default="", help="with --postings: K[,K..] equal document ranges as segments, then the ordered and the general merge")
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -228,6 +296,9 @@ def main():
                                "postings_over_ids": round(med(r) / row["ids"]["ids_ms"], 3),
                                "tfs_plus_dropped_equal_tokens": bool(tf_sum + int(cnt[1]) == n_tokens),
                                "term_offsets_end_equal_postings": bool(int(term[n_terms]) == int(cnt[0]) and int(term[0]) == 0)}
+            if args.merge:   # K equal document ranges as segments, then the two merges, beside the one-pass call above
+                row["merge"] = [merge_rows(torch, batch, stream, dev, args, int(K), S, n_terms, dev_off, d_soff, d_ids, d_term, d_pdocs, d_ptfs,
+                                           int(cnt[0]), row["postings"]["postings_ms"]) for K in args.merge.split(",")]
             del d_ids, d_term, d_pdocs, d_ptfs, d_cnt
         if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run
             counter = api.VocabularyCounter(pred, args.count_keys)

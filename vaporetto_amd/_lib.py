@@ -53,6 +53,13 @@ VPT_TRAIN_L1R = 4
 VPT_TRAIN_TAGS_L1R = 8
 VPT_TRAIN_L1R_LR = 16
 VPT_TRAIN_TAGS_L1R_LR = 32
+VPT_POSTINGS_MERGE_ORDERED = 1
+
+
+class PostingsSegment(C.Structure):
+    """vpt_postings_segment: the pointers are device pointers for vpt_postings_merge_device, host pointers for vpt_postings_merge"""
+    _fields_ = [("d_term_offsets", C.c_void_p), ("d_post_docs", C.c_void_p), ("d_post_tfs", C.c_void_p), ("n_terms", C.c_uint32),
+                ("capacity", C.c_uint64)]
 
 
 class TagProblemInfo(C.Structure):
@@ -139,6 +146,9 @@ SIGNATURES = {
     "vpt_postings_tile": (C.c_int, [C.POINTER(C.c_uint32)]),
     "vpt_token_stream_postings_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, _P, C.c_uint, C.c_uint64, _P, _P, _P, C.c_uint64,
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vpt_postings_merge_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, C.c_uint64, _P, _P]),
+    "vpt_postings_merge_limits": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "vpt_postings_merge": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),

@@ -857,7 +857,9 @@ class Predictor:
                 e.n_postings = int(n_post.value)   # (too small a capacity: the number needed)
                 raise
         n = int(n_post.value)
-        return Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, int(n_drop.value))
+        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, int(n_drop.value))
+        out._predictor = self
+        return out
 
     def fill_tags_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, out_offsets: np.ndarray, labels: np.ndarray,
                          fullwidth: bool = False, tagger: Optional["PatternMatchTagger"] = None) -> np.ndarray:
@@ -1495,6 +1497,36 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def merge_postings(self, segments: Sequence[Tuple[int, int, int, int, int]], n_terms_out: int, d_term_offsets: int, d_post_docs: int,
+                       d_post_tfs: int, capacity_out: int, d_counts: int, ordered: bool = False, stream: int = 0, flags: Optional[int] = None) -> None:
+        """Device-resident merge of postings segments (vpt_postings_merge_device).  segments: (d_term_offsets, d_post_docs, d_post_tfs, n_terms,
+        capacity) each, raw device pointers; the outputs must not alias them.  ordered: the promise VPT_POSTINGS_MERGE_ORDERED (flags, when
+        given, is passed as it is).  Enqueues and returns; errors (a hostile segment, a broken promise, a tf above 32 bits, more postings
+        than capacity_out) at sync()."""
+        segs = (_lib.PostingsSegment * max(len(segments), 1))()
+        for k, (toff, docs, tfs, n_terms, cap) in enumerate(segments):
+            for name, v, top in (("segment n_terms", n_terms, 1 << 32), ("segment capacity", cap, 1 << 64)):
+                if not 0 <= int(v) < top:
+                    raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+            segs[k] = _lib.PostingsSegment(toff or None, docs or None, tfs or None, int(n_terms), int(cap))
+        for name, v, top in (("n_terms_out", n_terms_out, 1 << 32), ("capacity_out", capacity_out, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        f = (_lib.VPT_POSTINGS_MERGE_ORDERED if ordered else 0) if flags is None else int(flags)
+        st = _lib.load().vpt_postings_merge_device(self._p.handle, self._h, C.addressof(segs), len(segments), int(n_terms_out), f, d_term_offsets or None,
+                                                   d_post_docs or None, d_post_tfs or None, int(capacity_out), d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    @staticmethod
+    def postings_merge_limit() -> int:
+        """the most segments one merge takes (vpt_postings_merge_limits)"""
+        v = C.c_uint32()
+        st = _lib.load().vpt_postings_merge_limits(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
     @staticmethod
     def postings_tile() -> int:
         v = C.c_uint32()
@@ -1906,6 +1938,8 @@ class Postings:
     def __init__(self, term_offsets: np.ndarray, docs: np.ndarray, tfs: np.ndarray, first: Optional[np.ndarray], order: Optional[np.ndarray],
                  n_dropped: int):
         self.term_offsets, self.docs, self.tfs, self.first, self.order, self.n_dropped = term_offsets, docs, tfs, first, order, int(n_dropped)
+        self.n_combined = 0      # merge: the input postings that were combined into another
+        self._predictor = None   # who made it (merge's default device)
 
     def __len__(self) -> int:
         return len(self.docs)
@@ -1918,6 +1952,47 @@ class Postings:
         """(docs, tfs) of one term"""
         a, b = int(self.term_offsets[term]), int(self.term_offsets[term + 1])
         return self.docs[a:b], self.tfs[a:b]
+
+    @staticmethod
+    def merge(segments: Sequence["Postings"], ordered: bool = False, predictor: Optional["Predictor"] = None, n_terms: Optional[int] = None,
+              capacity: Optional[int] = None) -> "Postings":
+        """The merge of segments that share a term id space (vpt_postings_merge): per term the union of their lists by document, a document
+        that stands in several of them one posting whose tf is the sum; n_dropped the segments' sum, n_combined the postings that went into
+        another.  ordered: the promise that every segment's documents are above those of the one before (checked on the device; no sort).
+        n_terms: the merged term count (default: the largest of the segments').  predictor: whose device (default: the one that made the
+        first segment).  No `first` / `order`: token indices are local to a segment."""
+        segments = list(segments)
+        pred = predictor or next((s._predictor for s in segments if getattr(s, "_predictor", None) is not None), None)
+        if pred is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: no predictor (pass predictor=)")
+        keep = [(np.ascontiguousarray(s.term_offsets, dtype=np.uint64), np.ascontiguousarray(s.docs, dtype=np.uint32),
+                 np.ascontiguousarray(s.tfs, dtype=np.uint32)) for s in segments]
+        for t, d, f in keep:
+            if len(t) == 0 or len(d) != len(f):
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: a segment's arrays do not belong together")
+        n_out = max([len(t) - 1 for t, _, _ in keep] + [0]) if n_terms is None else int(n_terms)
+        segs = (_lib.PostingsSegment * max(len(keep), 1))()
+        for k, (t, d, f) in enumerate(keep):
+            segs[k] = _lib.PostingsSegment(t.ctypes.data, d.ctypes.data if len(d) else None, f.ctypes.data if len(f) else None, len(t) - 1, len(d))
+        cap = sum(len(d) for _, d, _ in keep) if capacity is None else int(capacity)
+        term = np.zeros(max(n_out, 0) + 1, np.uint64)
+        docs, tfs = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        n_post, n_comb = C.c_uint64(), C.c_uint64()
+        if not 0 <= n_out < 1 << 32:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: n_terms: must be between 1 and 2^24")
+        st = _lib.load().vpt_postings_merge(pred.handle, C.addressof(segs), len(keep), n_out, _lib.VPT_POSTINGS_MERGE_ORDERED if ordered else 0,
+                                            term.ctypes.data, docs.ctypes.data, tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_comb))
+        if st != _lib.VPT_OK:
+            try:
+                _raise(st)
+            except VaporettoError as e:
+                e.n_postings = int(n_post.value)   # (too small a capacity: the number needed)
+                raise
+        n = int(n_post.value)
+        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, sum(s.n_dropped for s in segments))
+        out.n_combined = int(n_comb.value)
+        out._predictor = pred
+        return out
 
     def tokens(self, q: int) -> np.ndarray:
         """the token indices of posting q, ascending (needs positions)"""
@@ -2047,6 +2122,19 @@ class VaporettoTokenizer:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: index_batch: the tokenizer has no vocab")
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
         return self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base)
+
+    def index_batches(self, batches: Iterable[Sequence[str]], doc_base: int = 0, ordered: bool = True) -> "Postings":
+        """The postings of a corpus given as batches of documents: every batch is indexed as a segment (index_batch) with a running doc_base,
+        and the segments are merged on the device (Postings.merge; ordered: the running doc_bases keep the promise of the ordered route).
+        Equal to index_batch of the concatenation.  No batch: the empty postings over the vocabulary."""
+        segments, base = [], int(doc_base)
+        for texts in batches:
+            texts = list(texts)
+            segments.append(self.index_batch(texts, base))
+            base += len(texts)
+        if not segments:
+            return self.index_batch([], base)
+        return Postings.merge(segments, ordered=ordered, predictor=self._predictor)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

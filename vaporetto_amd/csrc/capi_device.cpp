@@ -1204,6 +1204,91 @@ vpt_status vpt_postings_batch_device(const vpt_predictor* p, vpt_batch* b, const
                            capacity_out, d_post_first, d_token_order, d_counts, static_cast<hipStream_t>(hip_stream));
 }
 
+// ---- merge of postings segments (kernels_postings_merge.hip).  Ordered: load, offsets (the table), copy, check.  General: load, offsets,
+// records, the trainer's sort over the document and the term word, heads, the trainer's scan, emit and terms.
+vpt_status vpt_postings_merge_limits(uint32_t* max_segments) {
+    if (!max_segments) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *max_segments = vpt::kPostingsMergeMaxSegments;
+    return VPT_OK;
+}
+
+namespace vptc {
+vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
+                                 unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
+                                 uint64_t* d_counts, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!segments || !d_term_offsets_out || !d_post_docs_out || !d_post_tfs_out || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
+    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (flags & ~unsigned(VPT_POSTINGS_MERGE_ORDERED)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    const uint32_t K = uint32_t(n_segments);
+    std::vector<vpt::PostingsMergeSegment> segs(K);
+    uint64_t n = 0;
+    for (uint32_t s = 0; s < K; ++s) {
+        const vpt_postings_segment& in = segments[s];
+        if (!in.d_term_offsets || !in.d_post_docs || !in.d_post_tfs) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+        if (in.n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
+        if (in.capacity >= (1ull << 32) || n + in.capacity >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
+        segs[s] = vpt::PostingsMergeSegment{in.d_term_offsets, in.d_post_docs, in.d_post_tfs, in.capacity, n, in.n_terms, 0u};
+        n += in.capacity;
+    }
+    VPT_HIP(hipSetDevice(p->device));
+    const bool ordered = (flags & VPT_POSTINGS_MERGE_ORDERED) != 0;
+    // the scratch in 256-byte sections: segs | range | table (ordered)   or   segs | rec | order | skey | flags | scan | hist | hist_scan | partials
+    const uint64_t nh = vpt::train_radix_scratch(n), row = uint64_t(n_terms_out) + 1;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_segs = 0, o_a = pad(sizeof(vpt::PostingsMergeSegment) * K);
+    const size_t o_table = o_a + pad(8 * size_t(K));
+    const size_t o_order = o_a + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
+                 o_scan = o_flags + pad(4 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
+                 o_part = o_hscan + pad(8 * (size_t(nh) + 1));
+    const size_t total = ordered ? o_table + pad(8 * size_t(K) * size_t(row))
+                                 : o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
+    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    unsigned char* m = b->d_post;
+    vpt::PostingsMergeParams P{};
+    P.segs = reinterpret_cast<vpt::PostingsMergeSegment*>(m + o_segs); P.n_segs = K; P.n_terms = n_terms_out; P.n_places = n;
+    P.term_offsets = d_term_offsets_out; P.post_docs = d_post_docs_out; P.post_tfs = d_post_tfs_out; P.capacity_out = capacity_out;
+    P.counts = d_counts; P.status = b->d_ctrl;
+    if (ordered) {
+        P.range = reinterpret_cast<uint32_t*>(m + o_a); P.table = reinterpret_cast<uint64_t*>(m + o_table);
+        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_ordered(P, stream));
+    } else {
+        P.rec = reinterpret_cast<uint32_t*>(m + o_a); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
+        P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+        uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
+        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_records(P, stream));
+        if (n == 0) {   // no place: no posting (the offsets were still checked)
+            VPT_HIP(hipMemsetAsync(d_term_offsets_out, 0, 8 * size_t(row), stream));
+            VPT_HIP(hipMemsetAsync(d_counts, 0, 16, stream));
+        } else {
+            uint32_t passes[8], n_passes = 0;   // the document word's four bytes, then the bytes of the values 0 .. n_terms_out of the term word
+            for (uint32_t k = 0; k < 4; ++k) passes[n_passes++] = (1u << 8) | (8 * k);
+            for (uint32_t v = n_terms_out, k = 0; v; v >>= 8, ++k) passes[n_passes++] = 8 * k;
+            VPT_HIP(vpt::train_radix_sort(P.rec, 3, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
+                                          reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
+            VPT_HIP(vpt::launch_postings_merge_heads(P, stream));
+            VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+            VPT_HIP(vpt::launch_postings_merge_emit(P, stream));
+        }
+    }
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_postings_merge_device(const vpt_predictor* p, vpt_batch* b, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                                     uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
+                                     uint64_t* d_counts, void* hip_stream) {
+    return postings_merge_device(p, b, static_cast<const vpt_postings_segment*>(segments), n_segments, n_terms_out, flags, d_term_offsets_out,
+                                 d_post_docs_out, d_post_tfs_out, capacity_out, d_counts, static_cast<hipStream_t>(hip_stream));
+}
+
 // A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them
 // (vocab_count.hpp).  Counting may go on afterwards.
 vpt_status vpt_vocab_counter_finish(void* counter, uint64_t min_count, uint64_t max_entries, const uint8_t** surfaces, const uint64_t** offsets,

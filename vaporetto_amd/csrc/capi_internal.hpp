@@ -385,7 +385,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
-    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams)
+    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -526,6 +526,11 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrBadTokenCsr)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: token_offsets / token_starts / token_ends: do not describe the documents' tokens");
     if (bits & vpt::kErrVocabCounterFull) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    if (bits & vpt::kErrBadSegment)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: term_offsets or postings are not a segment's");
+    if (bits & vpt::kErrSegmentsOverlap)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segments: document ranges overlap or descend");
+    if (bits & vpt::kErrTfOverflow) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tf: sum exceeds 32 bits");
     if (bits & vpt::kErrPostingsTooSmall) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
@@ -717,6 +722,10 @@ vpt_status vocab_count_device(const vpt_predictor* p, vpt_batch* b, vpt_vocab_co
 vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, const int32_t* d_token_ids,
                            uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base, uint64_t* d_term_offsets, uint32_t* d_post_docs, uint32_t* d_post_tfs,
                            uint64_t capacity_out, uint64_t* d_post_first, uint32_t* d_token_order, uint64_t* d_counts, hipStream_t stream);
+// The merge of postings segments (vpt_postings_merge_device; kernels_postings_merge.hip)
+vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
+                                 unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
+                                 uint64_t* d_counts, hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

@@ -69,6 +69,9 @@ constexpr uint32_t kErrBadLabel = 256u;       // the partial-annotation writer: 
 constexpr uint32_t kErrBadTokenCsr = 512u;    // the id pass: token_offsets / starts / ends that do not describe the documents (kernels_vocab.hip)
 constexpr uint32_t kErrVocabCounterFull = 1024u;   // the vocabulary counter: more keys or chars than it was made for (kernels_vocab_count.hip)
 constexpr uint32_t kErrPostingsTooSmall = 2048u;   // the postings pass: more postings than capacity_out (kernels_postings.hip)
+constexpr uint32_t kErrBadSegment = 4096u;         // the postings merge: term_offsets or postings that are not a segment's (kernels_postings_merge.hip)
+constexpr uint32_t kErrSegmentsOverlap = 8192u;    // the postings merge, ordered: the segments' document ranges overlap or descend
+constexpr uint32_t kErrTfOverflow = 16384u;        // the postings merge: a combined tf above 32 bits
 
 
 struct ScoreParams {
@@ -359,6 +362,52 @@ struct PostingsParams {
 hipError_t launch_postings_keys(const PostingsParams& P, hipStream_t stream);
 hipError_t launch_postings_heads(const PostingsParams& P, hipStream_t stream);
 hipError_t launch_postings_emit(const PostingsParams& P, hipStream_t stream);   // emit, then the terms
+// Merge of K postings segments that share a term id space (kernels_postings_merge.hip).  The segments' descriptors live in the batch's scratch
+// (segs [n_segs], loaded by launch_postings_merge_load from kernel arguments, kPostingsMergeLoad a launch); every launch is over the n_places =
+// the sum of the capacities, over the n_terms + 1 term bounds, or over the segments.  A place p belongs to the segment s with
+// place_base[s] <= p < place_base[s + 1]; it holds a posting when p - place_base[s] < min(term_offsets_s[n_terms_s], capacity_s).
+// Ordered route: table [n_segs * (n_terms + 1)], table[s * (n_terms + 1) + k] = where segment s's list of term k starts in the output; range
+// [2 * n_segs] the segments' smallest and largest document.  General route: rec [3 * n_places] {term or the sentinel n_terms, document, tf};
+// order, skey, flags [n_places]; scan [n_places + 1]; the caller runs train_radix_sort (rec, stride 3: the document word, then the term word)
+// between records and heads, and train_scan (flags -> scan) between heads and emit.
+constexpr uint32_t kPostingsMergeMaxSegments = 1024;
+constexpr uint32_t kPostingsMergeLoad = 64;   // descriptors a load launch carries in its arguments
+struct PostingsMergeSegment {
+    const uint64_t* term_offsets;   // [n_terms + 1]
+    const uint32_t* docs;           // [capacity]
+    const uint32_t* tfs;            // [capacity]
+    uint64_t capacity;
+    uint64_t place_base;            // the capacities in front
+    uint32_t n_terms;
+    uint32_t pad;
+};
+struct PostingsMergeLoadArgs {
+    PostingsMergeSegment seg[kPostingsMergeLoad];
+};
+struct PostingsMergeParams {
+    PostingsMergeSegment* segs;     // [n_segs], scratch
+    uint32_t n_segs;
+    uint32_t n_terms;               // n_terms_out
+    uint64_t n_places;              // the sum of the capacities, < 2^32
+    uint64_t* table;                // ordered
+    uint32_t* range;                // ordered
+    uint32_t* rec;                  // general
+    uint32_t* order;
+    uint32_t* skey;
+    uint32_t* flags;
+    uint64_t* scan;
+    uint64_t* term_offsets;         // [n_terms + 1]
+    uint32_t* post_docs;            // [capacity_out]
+    uint32_t* post_tfs;             // [capacity_out]
+    uint64_t capacity_out;
+    uint64_t* counts;               // [2]: merged postings, input postings combined into another
+    uint32_t* status;
+};
+hipError_t launch_postings_merge_load(const PostingsMergeParams& P, const PostingsMergeSegment* host_segs, hipStream_t stream);
+hipError_t launch_postings_merge_ordered(const PostingsMergeParams& P, hipStream_t stream);   // table, copy, check
+hipError_t launch_postings_merge_records(const PostingsMergeParams& P, hipStream_t stream);   // the offsets' check, then the records
+hipError_t launch_postings_merge_heads(const PostingsMergeParams& P, hipStream_t stream);
+hipError_t launch_postings_merge_emit(const PostingsMergeParams& P, hipStream_t stream);      // emit, then the terms
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
