@@ -486,6 +486,50 @@ impl Postings {
         Ok(Postings { term_offsets, docs, tfs, n_dropped: segments.iter().map(|s| s.n_dropped).sum(), n_combined })
     }
 
+    /// BM25 top-k of every query over this segment (`vpt_postings_search`; the definition is in include/vaporetto_hip.h).  `queries`: term ids, a
+    /// slot per id, ids outside the vocabulary score nothing, each weighted with `vpt_okapi_idf(n_documents, df)`.  `doc_lens[i]`: the length of
+    /// document `doc_base + i`; avgdl = their mean, computed in f64 and rounded to f32.  Returns per query at most `k` (document, score) pairs by
+    /// score descending, then document ascending, and the queries' match counts.
+    pub fn search(&self, predictor: &Predictor, queries: &[Vec<i32>], doc_lens: &[u32], doc_base: u64, k: u32, k1: f32, b: f32)
+                  -> Result<(Vec<Vec<(u32, f32)>>, Vec<u64>)> {
+        if queries.is_empty() {
+            return Ok((Vec::new(), Vec::new()));
+        }
+        let n = self.term_offsets.len();
+        if n == 0 || doc_lens.is_empty() || self.docs.len() != self.tfs.len() || self.term_offsets[n - 1] > self.docs.len() as u64 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: search: the arrays do not belong together".into()));
+        }
+        let avgdl = (doc_lens.iter().map(|&l| l as f64).sum::<f64>() / doc_lens.len() as f64) as f32;
+        let mut offsets = vec![0u64];
+        let (mut terms, mut weights) = (Vec::new(), Vec::new());
+        for q in queries {
+            for &t in q {
+                let mut w = 0f32;
+                if t >= 0 && (t as usize) < n - 1 {
+                    check(unsafe { ffi::vpt_okapi_idf(doc_lens.len() as u64, self.df(t as usize), &mut w) })?;
+                }
+                terms.push(t);
+                weights.push(w);
+            }
+            offsets.push(terms.len() as u64);
+        }
+        terms.push(0);
+        weights.push(0f32);
+        let n_out = queries.len() * k as usize + 1;
+        let (mut hit_docs, mut hit_scores) = (vec![0u32; n_out], vec![0f32; n_out]);
+        let (mut hit_counts, mut match_counts, mut counts) = (vec![0u32; queries.len()], vec![0u64; queries.len()], [0u64; 3]);
+        check(unsafe {
+            ffi::vpt_postings_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(), (n - 1) as u32, doc_base,
+                                     doc_lens.len() as u64, doc_lens.as_ptr(), offsets.as_ptr(), terms.as_ptr(), weights.as_ptr(), queries.len() as u32,
+                                     k1, b, avgdl, k, hit_docs.as_mut_ptr(), hit_scores.as_mut_ptr(), hit_counts.as_mut_ptr(), match_counts.as_mut_ptr(),
+                                     counts.as_mut_ptr())
+        })?;
+        let hits = (0..queries.len())
+            .map(|q| (0..hit_counts[q] as usize).map(|j| (hit_docs[q * k as usize + j], hit_scores[q * k as usize + j])).collect())
+            .collect();
+        Ok((hits, match_counts))
+    }
+
     /// The document frequency of `term`.
     pub fn df(&self, term: usize) -> u64 {
         self.term_offsets[term + 1] - self.term_offsets[term]

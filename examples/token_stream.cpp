@@ -16,6 +16,9 @@
 // term <TAB> document <TAB> tf, the document being doc_base + the line's index; then one line "dropped <TAB> n" for the tokens that are no entry.
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] --segment-docs N < documents.txt
 // With --segment-docs N: N documents are indexed a segment, and the segments are merged on the device; the output is the same.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --search "QUERY" [--top K] < documents.txt
+// With --search: the query text is tokenised as a document is, its tokens are weighted with BM25's idf and the K (default 10) best documents of
+// the index are found on the device; one line per hit, best first: document <TAB> the score's bits in hex <TAB> the score.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -75,7 +78,11 @@ int main(int argc, char** argv) {
             for (std::string l; std::getline(std::cin, l);) docs.push_back(l);
             size_t segment_docs = 0;
             int n_args = argc;
-            if (argc > 6 && std::strcmp(argv[argc - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[argc - 1], nullptr, 10); n_args = argc - 2; }
+            const char* query = nullptr;
+            uint32_t top = 10;
+            if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
+            if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
+            if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }
             const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
             vaporetto_hip::Postings post;
             if (segment_docs) {
@@ -85,6 +92,15 @@ int main(int argc, char** argv) {
                 post = plain.index(batches, vocab, doc_base);
             } else {
                 post = plain.index(docs, vocab, doc_base);
+            }
+            if (query) {
+                const auto found = plain.search(post, vocab, {std::string(query)}, plain.doc_lens(docs, vocab), doc_base, top);
+                for (const vaporetto_hip::Postings::Hit& h : found.hits[0]) {
+                    uint32_t bits;
+                    std::memcpy(&bits, &h.score, 4);
+                    std::printf("%u\t%08x\t%.9g\n", unsigned(h.document), unsigned(bits), double(h.score));
+                }
+                return 0;
             }
             for (size_t k = 0; k < post.n_terms(); ++k)
                 for (uint64_t q = post.term_offsets[k]; q < post.term_offsets[k + 1]; ++q)

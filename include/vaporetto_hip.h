@@ -704,6 +704,68 @@ vpt_status vpt_postings_merge(const vpt_predictor *p, const void *segments, size
                               uint64_t *term_offsets_out, uint32_t *post_docs_out, uint32_t *post_tfs_out, uint64_t capacity,
                               uint64_t *n_postings_out, uint64_t *n_combined_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * BM25 top-k search over a postings segment on the device     (no item of the adapter: the ranking tantivy applies behind its token stream --
+ *                                                                here the index that never left the device is also READ there)
+ *
+ * vpt_postings_search_device: a batch of queries against ONE segment, as vpt_postings_batch_device or vpt_postings_merge_device left it.
+ *   Segment: d_term_offsets [n_terms + 1], d_post_docs / d_post_tfs [capacity_postings]; the postings are d_term_offsets[n_terms], read on the
+ *   device, so indexing, merging and searching need no sync in between.
+ *   Documents: doc_base, n_documents, d_doc_lens uint32 [n_documents] = the length of document doc_base + i (the wrappers pass its token count,
+ *   token_offsets[i + 1] - token_offsets[i], dropped tokens included, as tantivy's field norm counts every token).
+ *   Queries, a CSR: d_query_offsets [n_queries + 1], d_query_terms int32 / d_query_weights float [capacity_slots]; the slots are
+ *   min(query_offsets[n_queries], capacity_slots).  A slot whose term is outside [0, n_terms) scores nothing and adds 1 to d_counts[2] (an unk_id
+ *   of -1 is such a term).  A term repeated in a query is scored once per slot.  The weight is the caller's -- idf for BM25, vpt_okapi_idf; the
+ *   device never takes a logarithm.
+ *   Score, all in IEEE binary32, round to nearest, no contraction, in exactly this order: for a slot with weight w and a posting (d, tf) of its
+ *   term
+ *       r = float(dl[d - doc_base]) / avgdl;  K = k1 * ((1.0f - b) + b * r);  f = float(tf);  c = w * ((f * (k1 + 1.0f)) / (f + K))
+ *   A document MATCHES a query when at least one slot has a posting for it; its score is the sum of its c values in slot order, left to right,
+ *   starting from the first c.
+ *   Output, per query q: d_match_counts[q] = the matching documents; d_hit_counts[q] = min(k, matches); d_hit_docs[q * k + j] /
+ *   d_hit_scores[q * k + j] for j below the hit count = the matches by score descending, then document ascending; entries at or behind the hit
+ *   count are not written.  d_counts[0] = the candidates (the sum over in-range slots of the term's df), d_counts[1] = the matches of all
+ *   queries, d_counts[2] = the skipped slots.  Two runs, on one workspace or on two, give identical bytes.
+ *   Launches (kernels_postings_search.hip), each sized from capacity_slots, capacity_candidates, n_queries or n_queries * k, none from a value
+ *   read back: slots (df, checks), the trainer's scan (candidate bases), expand (a {document, query, c} record per candidate place), the
+ *   trainer's stable radix sort over the document word (ceil(bit_width(n_documents) / 8) passes, at most 4) and the query word
+ *   (ceil(bit_width(n_queries) / 8) passes), heads, the trainer's scan, sum (a head adds its run in slot order) and ranges, the trainer's sort
+ *   over ~bits(score) (4 passes) and the query word, take.  Asynchronous on hip_stream, errors at vpt_batch_sync; no atomic decides a value.
+ *   Scratch of the workspace: 20 bytes per slot of capacity_slots, 44 bytes per place of capacity_candidates (two records of three words, two
+ *   index words, a flag, a scan word), 8 bytes per query and 16 bytes per 16 places of histograms.
+ *   At the call, VPT_INVALID_ARGUMENT: a NULL pointer, n_terms == 0 or > 2^24, n_queries == 0 or > 2^24, k == 0 or n_queries * k >= 2^32,
+ *   capacity_slots or capacity_candidates >= 2^32, doc_base + n_documents > 2^32, k1 outside [0, 65536], b outside [0, 1], avgdl outside
+ *   [2^-32, 2^32] (with these and tf >= 1 every denominator is >= 1 and no NaN arises from finite non-negative weights; a sum may reach +inf,
+ *   which sorts first, ties by document), a workspace of another predictor.
+ *   At the sync, VPT_INVALID_ARGUMENT: "InvalidArgumentError: query_offsets: do not describe the queries' slots" (they decrease, exceed
+ *   capacity_slots or leave a slot unowned); "InvalidArgumentError: segment: term_offsets or postings are not a segment's" (a scored term's two
+ *   bounds descend or end above capacity_postings, a tf of 0, a document outside [doc_base, doc_base + n_documents) or not above the one before
+ *   it in its list); "InvalidArgumentError: weights: negative or not finite" (bits above 0x7F7FFFFF); "InvalidArgumentError: query: more than
+ *   1024 slots" (vpt_postings_search_limits); "InvalidArgumentError: capacity_candidates: smaller than the number of candidates" -- d_counts[0]
+ *   then holds the number needed.  After any of these the four outputs are as they were before the call (so are they while an error of this
+ *   list from an earlier call on the workspace waits for its sync).  Whatever the arrays hold, nothing is read outside
+ *   term_offsets[0 .. n_terms], [0, capacity_postings), doc_lens[0 .. n_documents) and the query arrays' stated sizes, and nothing is written
+ *   outside d_hit_docs / d_hit_scores [n_queries * k], d_hit_counts / d_match_counts [n_queries], d_counts [3] and the workspace.
+ * vpt_postings_search_limits: the most slots a query may have.
+ * vpt_postings_search: the same over HOST arrays: what the segment holds (term_offsets[n_terms] postings) is uploaded, the candidates are
+ *   counted from the host's term_offsets, the device call runs once, the four outputs and counts_out [3] come back (hit entries at or behind a
+ *   query's hit count come back 0).  Returns when the device is through.
+ * vpt_okapi_idf: (float)log(1 + (N - df + 0.5) / (df + 0.5)) evaluated in double -- tantivy's idf; df > N is VPT_INVALID_ARGUMENT.  The one
+ *   implementation every binding calls, so all agree on the weights' bits. */
+vpt_status vpt_postings_search_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets, const uint32_t *d_post_docs,
+                                      const uint32_t *d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t *d_doc_lens, const uint64_t *d_query_offsets,
+                                      const int32_t *d_query_terms, const float *d_query_weights, uint32_t n_queries, uint64_t capacity_slots,
+                                      float k1, float b_param, float avgdl, uint32_t k, uint64_t capacity_candidates, uint32_t *d_hit_docs,
+                                      float *d_hit_scores, uint32_t *d_hit_counts, uint64_t *d_match_counts, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_search_limits(uint32_t *max_query_slots);
+vpt_status vpt_postings_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs, const uint32_t *post_tfs,
+                               uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint32_t *doc_lens, const uint64_t *query_offsets,
+                               const int32_t *query_terms, const float *query_weights, uint32_t n_queries, float k1, float b_param, float avgdl,
+                               uint32_t k, uint32_t *hit_docs_out, float *hit_scores_out, uint32_t *hit_counts_out, uint64_t *match_counts_out,
+                               uint64_t *counts_out);
+vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float *idf_out);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

@@ -470,7 +470,58 @@ struct Postings {
     // documents are above those of the one before -- checked on the device, no sort.  n_terms: the merged term count (0: the largest of the
     // segments').  No token lists: token indices are local to a segment.
     static Postings merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered = false, size_t n_terms = 0);
+    // BM25 top-k of every query over this segment (vpt_postings_search; the definition is in vaporetto_hip.h).  queries: term ids, a slot per
+    // id, ids outside [0, n_terms) score nothing.  doc_lens[i]: the length of document doc_base + i (VaporettoTokenizer::doc_lens).  weights:
+    // shaped as queries, or nullptr for vpt_okapi_idf(n_documents, df(term)) per slot.  avgdl = float(sum(doc_lens) / n_documents), in double.
+    struct Hit { uint32_t document; float score; };
+    struct SearchResult {
+        std::vector<std::vector<Hit>> hits;   // per query at most k, by score descending, then document ascending
+        std::vector<uint64_t> match_counts;   // per query
+        uint64_t counts[3] = {0, 0, 0};       // candidates, matches, skipped slots
+    };
+    SearchResult search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& queries, const std::vector<uint32_t>& doc_lens,
+                        uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
+                        const std::vector<std::vector<float>>* weights = nullptr) const;
 };
+
+inline Postings::SearchResult Postings::search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& queries, const std::vector<uint32_t>& doc_lens,
+                                               uint64_t doc_base, uint32_t k, float k1, float b, const std::vector<std::vector<float>>* weights) const {
+    SearchResult out;
+    if (queries.empty()) return out;
+    if (term_offsets.empty() || doc_lens.empty() || (weights && weights->size() != queries.size()))
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: search: the arrays do not belong together");
+    double total = 0;
+    for (uint32_t l : doc_lens) total += double(l);
+    const float avgdl = float(total / double(doc_lens.size()));
+    std::vector<uint64_t> qoff(1, 0);
+    std::vector<int32_t> terms;
+    std::vector<float> w;
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (weights && (*weights)[q].size() != queries[q].size())
+            throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: weights: not shaped as the queries");
+        for (size_t j = 0; j < queries[q].size(); ++j) {
+            const int32_t t = queries[q][j];
+            float x = 0.0f;
+            if (weights) x = (*weights)[q][j];
+            else if (t >= 0 && size_t(t) < n_terms()) detail::check(vpt_okapi_idf(doc_lens.size(), df(size_t(t)), &x));
+            terms.push_back(t);
+            w.push_back(x);
+        }
+        qoff.push_back(terms.size());
+    }
+    terms.push_back(0); w.push_back(0.0f);   // (data() of an empty vector may be NULL)
+    const size_t n_out = queries.size() * size_t(k) + 1;
+    std::vector<uint32_t> hd(n_out), hc(queries.size());
+    std::vector<float> hs(n_out);
+    out.match_counts.assign(queries.size(), 0);
+    detail::check(vpt_postings_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), uint32_t(n_terms()), doc_base, doc_lens.size(),
+                                      doc_lens.data(), qoff.data(), terms.data(), w.data(), uint32_t(queries.size()), k1, b, avgdl, k, hd.data(), hs.data(),
+                                      hc.data(), out.match_counts.data(), out.counts));
+    out.hits.resize(queries.size());
+    for (size_t q = 0; q < queries.size(); ++q)
+        for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(Hit{hd[q * size_t(k) + j], hs[q * size_t(k) + j]});
+    return out;
+}
 
 inline Postings Postings::merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered, size_t n_terms) {
     std::vector<vpt_postings_segment> segs(segments.size());
@@ -678,6 +729,25 @@ public:
         }
         if (segments.empty()) return index(std::vector<std::string>(), vocab, doc_base, normalize);
         return Postings::merge(predictor_, segments, true, vocab.size());
+    }
+
+    // The lengths Postings::search takes: the tokens this tokenizer streams per text (those without a vocabulary entry included).
+    std::vector<uint32_t> doc_lens(const std::vector<std::string>& texts, const Vocabulary& vocab, bool normalize = true) const {
+        const auto enc = encode(texts, vocab, normalize);
+        std::vector<uint32_t> out(texts.size());
+        for (size_t i = 0; i < texts.size(); ++i) out[i] = uint32_t(enc.first[i + 1] - enc.first[i]);
+        return out;
+    }
+
+    // BM25 top-k of query TEXTS over `postings` (of this tokenizer and `vocab`): the texts are tokenised and encoded as documents are, every
+    // token a slot -- nothing is dropped, a token without a vocabulary entry scores nothing -- then Postings::search with the idf weights.
+    Postings::SearchResult search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
+                                  const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
+                                  bool normalize = true) const {
+        const auto enc = encode(texts, vocab, normalize);
+        std::vector<std::vector<int32_t>> queries(texts.size());
+        for (size_t i = 0; i < texts.size(); ++i) queries[i].assign(enc.second.begin() + enc.first[i], enc.second.begin() + enc.first[i + 1]);
+        return postings.search(predictor_, queries, doc_lens, doc_base, k, k1, b);
     }
 
 private:

@@ -1,0 +1,65 @@
+"""The BM25 top-k search on the MI355X through the C ABI: the launches of kernels_postings_search.hip with the trainer's sort and scan between
+them, the host call, Postings.search and VaporettoTokenizer.search against the definition of tests/searchref.py -- the checks of
+tests/searchsuite.py.  (The hostile inputs run here in the form that has run on the emulator, tests/test_postings_search_emu.py: every kernel
+loop is bounded, every index is clamped before use, nothing waits.)"""
+import pytest
+
+from tests import searchsuite, vocabsuite
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def fresh_predictor():
+    vocabsuite._PRED.clear()
+    yield
+    vocabsuite._PRED.clear()
+
+
+def test_random_queries_over_a_postings_pass_segment_and_the_addition_order():
+    searchsuite.check_random()
+
+
+def test_equal_documents_tie_by_ascending_document_and_k_cuts_a_tie_group():
+    searchsuite.check_ties()
+
+
+def test_slots_repeated_df0_out_of_range_empty_queries_and_the_slot_limit():
+    searchsuite.check_slots()
+
+
+@pytest.mark.parametrize("n", ["T-1", "T", "T+1", "3T+1"])
+def test_candidates_and_matches_on_the_tile_edges(n):
+    searchsuite.check_candidates(searchsuite.postingssuite.token_count(n))
+
+
+def test_merged_segment_searched_equals_one_pass_segment_searched():
+    searchsuite.check_merged_segment()
+
+
+def test_zero_weights_k1_zero_b_zero_b_one_and_a_document_of_length_zero():
+    searchsuite.check_weights_and_parameters()
+
+
+def test_bm25_idf_is_the_definition():
+    searchsuite.check_idf()
+
+
+def test_capacity_too_small_is_an_error_at_sync_with_the_number_needed():
+    searchsuite.check_capacity()
+
+
+def test_errors_at_the_call():
+    searchsuite.check_errors()
+
+
+def test_hostile_input_is_an_error_at_sync_and_touches_nothing_outside():
+    assert searchsuite.run_hostile() == searchsuite.N_HOSTILE
+
+
+def test_two_runs_and_a_second_workspace_give_identical_bytes():
+    searchsuite.check_determinism()
+
+
+def test_host_call_and_postings_search():
+    searchsuite.check_host_call()

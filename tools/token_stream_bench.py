@@ -18,6 +18,10 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
   --merge K[,K..]: with --postings, the batch's documents as K equal ranges: the K segment calls, the ordered and the general merge
       (kernels_postings_merge.hip) and a device-to-device copy of the bytes the ordered merge must move, each the median of --rounds rounds of
       --steps calls by device events, beside the one-pass call of the same run (profiles/postings_merge_bench.json).
+  --search Q,L,K: with --postings, Q queries of L terms drawn from the vocabulary by count (a term's tokens in the batch), top K, over the one-pass
+      segment (kernels_postings_search.hip) by device events, beside two yardsticks of the same run: the general merge over one segment of as
+      many input places as the search has candidates, and a device-to-device copy of half of 8 bytes a candidate plus 8 bytes a hit (a copy of
+      B bytes moves B in and B out).  Q is halved until the candidates are at most --search-max-candidates (profiles/postings_search_bench.json).
   --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
       --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
@@ -149,6 +153,82 @@ def merge_rows(torch, batch, stream, dev, args, K, S, n_terms, dev_off, d_soff, 
     return out
 
 
+def search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_term, d_pdocs, d_ptfs, n_post):
+    """--search Q,L,K over the one-pass segment; see the module's docstring"""
+    from vaporetto_amd import api
+    Q, L, K = (int(x) for x in spec.split(","))
+    term = d_term.cpu().numpy().astype(np.int64)
+    df = np.diff(term)
+    tfs = d_ptfs[:n_post].cpu().numpy().astype(np.int64)
+    count = np.add.reduceat(np.concatenate([tfs, [0]]), np.minimum(term[:-1], n_post)) * (df > 0)
+    rng = np.random.default_rng(7)
+    while True:
+        terms = rng.choice(n_terms, size=Q * L, p=count / count.sum()).astype(np.int32)
+        n_cand = int(df[terms].sum())
+        if n_cand <= args.search_max_candidates or Q == 1:
+            break
+        Q //= 2
+    if n_cand >= 1 << 32:
+        raise SystemExit("--search: %d candidates" % n_cand)
+    idf = {int(t): float(api.bm25_idf(S, int(df[t]))) for t in set(terms.tolist())}
+    dl = np.diff(dev_off.astype(np.int64))
+    avgdl = float(np.float32(float(dl.sum()) / S))
+    d_dl = torch.from_numpy(dl.astype(np.int32)).to(dev)
+    d_qoff = torch.from_numpy(np.arange(0, Q * L + 1, L, dtype=np.int64)).to(dev)
+    d_qt = torch.from_numpy(terms).to(dev)
+    d_qw = torch.from_numpy(np.array([idf[int(t)] for t in terms], np.float32)).to(dev)
+    d_hd, d_hs = torch.zeros(Q * K, dtype=torch.int32, device=dev), torch.zeros(Q * K, dtype=torch.float32, device=dev)
+    d_hc, d_mc, d_cnt = torch.zeros(Q, dtype=torch.int32, device=dev), torch.zeros(Q, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev)
+
+    def search():
+        batch.search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, 0, S, d_dl.data_ptr(), d_qoff.data_ptr(), d_qt.data_ptr(),
+                              d_qw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K, n_cand, d_hd.data_ptr(), d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(),
+                              d_cnt.data_ptr(), stream)
+    search()
+    batch.sync()
+    cnt = d_cnt.cpu().numpy()
+    matches = int(cnt[1])
+    # the yardsticks: one segment of n_cand input places (the batch's postings in front, its term bounds cut there) through the general merge
+    y_term = torch.clamp(d_term, max=n_cand).contiguous()
+    y_docs, y_tfs = torch.zeros(n_cand + 1, dtype=torch.int32, device=dev), torch.zeros(n_cand + 1, dtype=torch.int32, device=dev)
+    m = min(n_cand, n_post)
+    y_docs[:m].copy_(d_pdocs[:m]); y_tfs[:m].copy_(d_ptfs[:m])
+    o_term = torch.empty(n_terms + 1, dtype=torch.int64, device=dev)
+    o_docs, o_tfs = torch.empty(n_cand + 1, dtype=torch.int32, device=dev), torch.empty(n_cand + 1, dtype=torch.int32, device=dev)
+    o_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def merge():
+        batch.merge_postings([(y_term.data_ptr(), y_docs.data_ptr(), y_tfs.data_ptr(), n_terms, n_cand)], n_terms, o_term.data_ptr(), o_docs.data_ptr(),
+                             o_tfs.data_ptr(), n_cand, o_cnt.data_ptr(), False, stream)
+    copy_bytes = (8 * n_cand + 8 * matches) // 2
+    a_buf, b_buf = torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev), torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev)
+
+    def floor():
+        b_buf.copy_(a_buf)
+    out = {"spec": spec, "queries": Q, "slots_per_query": L, "k": K, "n_terms": n_terms, "documents": S, "postings": n_post, "candidates": int(cnt[0]),
+           "matches": matches, "skipped": int(cnt[2]), "candidates_equal_host_count": bool(int(cnt[0]) == n_cand), "copy_bytes": copy_bytes,
+           "sort_passes": {"group": min((S.bit_length() + 7) // 8, 4) + (Q.bit_length() + 7) // 8, "rank": 4 + (Q.bit_length() + 7) // 8,
+                           "merge": 4 + (n_terms.bit_length() + 7) // 8}}
+    for name, fn in (("search", search), ("merge", merge), ("floor", floor)):
+        fn()
+        batch.sync()
+        r = []
+        for _ in range(args.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in ev:
+                a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            r.append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        out[name + "_ms"] = round(med(r), 4)
+        out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+    out["hit_counts_sum"] = int(d_hc.to(torch.int64).sum().item())
+    out["candidates_per_s"] = round(int(cnt[0]) / out["search_ms"] * 1e3, 1)
+    out["search_over_merge"] = round(out["search_ms"] / out["merge_ms"], 3)
+    out["search_over_floor"] = round(out["search_ms"] / out["floor_ms"], 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="2,5")
@@ -162,6 +242,8 @@ def main():
     ap.add_argument("--count", action="store_true", help="also time the vocabulary counter's count call (three launches) and finish once")
     ap.add_argument("--postings", action="store_true", help="also time the postings pass over the id pass's ids (needs --ids)")
     ap.add_argument("--merge", default="", help="with --postings: K[,K..] equal document ranges as segments, then the ordered and the general merge")
+    ap.add_argument("--search", action="append", default=[], help="with --postings: Q,L,K -- Q queries of L terms by count, top K (may be repeated)")
+    ap.add_argument("--search-max-candidates", type=int, default=1 << 26)
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -299,6 +381,9 @@ def main():
             if args.merge:   # K equal document ranges as segments, then the two merges, beside the one-pass call above
                 row["merge"] = [merge_rows(torch, batch, stream, dev, args, int(K), S, n_terms, dev_off, d_soff, d_ids, d_term, d_pdocs, d_ptfs,
                                            int(cnt[0]), row["postings"]["postings_ms"]) for K in args.merge.split(",")]
+            if args.search:   # BM25 top-k over the segment the one-pass call left, beside the general merge and a copy
+                row["search"] = [search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_term, d_pdocs, d_ptfs, int(cnt[0]))
+                                 for spec in args.search]
             del d_ids, d_term, d_pdocs, d_ptfs, d_cnt
         if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run
             counter = api.VocabularyCounter(pred, args.count_keys)

@@ -1527,6 +1527,35 @@ class DeviceBatch:
             _raise(st)
         return int(v.value)
 
+    def search_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, n_terms: int, capacity_postings: int, doc_base: int,
+                        n_documents: int, d_doc_lens: int, d_query_offsets: int, d_query_terms: int, d_query_weights: int, n_queries: int,
+                        capacity_slots: int, k1: float, b: float, avgdl: float, k: int, capacity_candidates: int, d_hit_docs: int, d_hit_scores: int,
+                        d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0) -> None:
+        """Device-resident BM25 top-k search of a batch of queries over one segment (vpt_postings_search_device), raw device pointers.
+        Enqueues and returns; errors (a hostile segment or query CSR, a bad weight, a query above the slot limit, more candidates than
+        capacity_candidates) at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_queries", n_queries, 1 << 32), ("k", k, 1 << 32), ("doc_base", doc_base, 1 << 64),
+                             ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
+                             ("capacity_slots", capacity_slots, 1 << 64), ("capacity_candidates", capacity_candidates, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_search_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None, int(n_terms),
+                                                    int(capacity_postings), int(doc_base), int(n_documents), d_doc_lens or None, d_query_offsets or None,
+                                                    d_query_terms or None, d_query_weights or None, int(n_queries), int(capacity_slots), float(k1), float(b),
+                                                    float(avgdl), int(k), int(capacity_candidates), d_hit_docs or None, d_hit_scores or None,
+                                                    d_hit_counts or None, d_match_counts or None, d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    @staticmethod
+    def postings_search_limit() -> int:
+        """the most slots a query of a search may have (vpt_postings_search_limits)"""
+        v = C.c_uint32()
+        st = _lib.load().vpt_postings_search_limits(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
     @staticmethod
     def postings_tile() -> int:
         v = C.c_uint32()
@@ -1929,6 +1958,17 @@ class VocabularyCounter:
         return [raw[int(offsets[k]):int(offsets[k + 1])].decode("utf-8") for k in range(len(counts))], counts
 
 
+def bm25_idf(n_documents: int, df: int) -> np.float32:
+    """tantivy's BM25 idf, float32(log(1 + (N - df + 0.5) / (df + 0.5))) evaluated in double (vpt_okapi_idf: the one implementation of every binding)"""
+    v = C.c_float()
+    if not (0 <= int(n_documents) < 1 << 64 and 0 <= int(df) < 1 << 64):
+        raise VaporettoError("InvalidArgument", "InvalidArgumentError: df: above n_documents")
+    st = _lib.load().vpt_okapi_idf(int(n_documents), int(df), C.byref(v))
+    if st != _lib.VPT_OK:
+        _raise(st)
+    return np.float32(v.value)
+
+
 class Postings:
     """The postings of one batch (a segment), term-major (vpt_postings_batch_device): term k's postings are [term_offsets[k], term_offsets[k + 1])
     of `docs` (doc_base + the document's index, ascending within a term) and `tfs`.  With positions: posting q's tokens are
@@ -1940,6 +1980,8 @@ class Postings:
         self.term_offsets, self.docs, self.tfs, self.first, self.order, self.n_dropped = term_offsets, docs, tfs, first, order, int(n_dropped)
         self.n_combined = 0      # merge: the input postings that were combined into another
         self._predictor = None   # who made it (merge's default device)
+        self.doc_lens = None     # search: uint32, the token count of document doc_base + i (index_batch / index_batches attach both)
+        self.doc_base = None
 
     def __len__(self) -> int:
         return len(self.docs)
@@ -1993,6 +2035,60 @@ class Postings:
         out.n_combined = int(n_comb.value)
         out._predictor = pred
         return out
+
+    def search(self, queries: Sequence[Sequence[int]], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2, b: float = 0.75,
+               weights=None, predictor: Optional["Predictor"] = None):
+        """BM25 top-k of every query over this segment (vpt_postings_search; the definition is in include/vaporetto_hip.h).  queries: a sequence
+        of term-id sequences, a slot per id, ids outside the vocabulary score nothing.  doc_lens / doc_base: the documents' lengths (default:
+        what index_batch / index_batches attached).  weights: a sequence of float sequences shaped as queries (default: bm25_idf(n_documents,
+        df[term]) per slot).  avgdl = float32(sum(doc_lens) / n_documents), in double.  Returns (hits, match_counts): hits[q] the list of
+        (document, score float32) pairs, at most k, by score descending, then document ascending; match_counts uint64 [n_queries]."""
+        pred = predictor or self._predictor
+        if pred is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: search: no predictor (pass predictor=)")
+        doc_lens = self.doc_lens if doc_lens is None else doc_lens
+        doc_base = self.doc_base if doc_base is None else doc_base
+        if doc_lens is None or doc_base is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: search: the postings carry no doc_lens / doc_base (pass them)")
+        dl = np.ascontiguousarray(doc_lens, dtype=np.uint32)
+        n_docs, n_terms, n_q = len(dl), len(self.term_offsets) - 1, len(queries)
+        if n_q == 0:
+            return [], np.zeros(0, np.uint64)
+        if n_docs == 0:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32")
+        avgdl = np.float32(float(int(dl.sum(dtype=np.uint64))) / float(n_docs))
+        qoff = np.zeros(n_q + 1, np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        n_slots = int(qoff[-1])
+        terms = np.array([t for q in queries for t in q] + [0], np.int64).astype(np.int32)
+        if weights is None:
+            df, idf = self.df(), {}
+            w = np.zeros(n_slots + 1, np.float32)
+            for s in range(n_slots):
+                t = int(terms[s])
+                if 0 <= t < n_terms:
+                    if t not in idf:
+                        idf[t] = bm25_idf(n_docs, int(df[t]))
+                    w[s] = idf[t]
+        else:
+            w = np.array([x for q in weights for x in q] + [0], np.float32)
+            if len(w) != n_slots + 1 or any(len(a) != len(c) for a, c in zip(weights, queries)):
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: weights: not shaped as the queries")
+        if not (0 <= int(k) < 1 << 32 and 0 <= n_terms < 1 << 32 and 0 <= n_q < 1 << 32 and 0 <= int(doc_base) < 1 << 64):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32")
+        term = np.ascontiguousarray(self.term_offsets, dtype=np.uint64)
+        docs, tfs = np.ascontiguousarray(self.docs, dtype=np.uint32), np.ascontiguousarray(self.tfs, dtype=np.uint32)
+        n_out = max(n_q * int(k), 1)
+        hd, hs, hc, mc, cnt = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
+        st = _lib.load().vpt_postings_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None, tfs.ctypes.data if len(tfs) else None,
+                                             n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data, n_q,
+                                             float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data,
+                                             cnt.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.last_search_counts = cnt   # candidates, matches, skipped slots
+        k = int(k)
+        return [[(int(hd[q * k + j]), hs[q * k + j]) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
     def tokens(self, q: int) -> np.ndarray:
         """the token indices of posting q, ascending (needs positions)"""
@@ -2121,7 +2217,11 @@ class VaporettoTokenizer:
         if self._vocab is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: index_batch: the tokenizer has no vocab")
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
-        return self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base)
+        out = self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base)
+        # what Postings.search needs of the documents: their token counts (the stream's tokens, those without a vocabulary entry included)
+        out.doc_lens = np.diff(self._stream_ids(utf8, boff)[0]).astype(np.uint32) if len(texts) else np.zeros(0, np.uint32)
+        out.doc_base = int(doc_base)
+        return out
 
     def index_batches(self, batches: Iterable[Sequence[str]], doc_base: int = 0, ordered: bool = True) -> "Postings":
         """The postings of a corpus given as batches of documents: every batch is indexed as a segment (index_batch) with a running doc_base,
@@ -2134,7 +2234,17 @@ class VaporettoTokenizer:
             base += len(texts)
         if not segments:
             return self.index_batch([], base)
-        return Postings.merge(segments, ordered=ordered, predictor=self._predictor)
+        out = Postings.merge(segments, ordered=ordered, predictor=self._predictor)
+        out.doc_lens, out.doc_base = np.concatenate([s.doc_lens for s in segments]), int(doc_base)   # (the running doc_bases are contiguous)
+        return out
+
+    def search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
+               b: float = 0.75, weights=None):
+        """BM25 top-k of query TEXTS over `postings`: the texts are tokenised and encoded as documents are (encode_batch), every token a slot --
+        nothing is dropped, a token without a vocabulary entry is a slot that scores nothing -- then Postings.search.  Needs vocab=."""
+        toff, ids = self.encode_batch(list(texts))
+        queries = [ids[int(toff[i]):int(toff[i + 1])].tolist() for i in range(len(toff) - 1)]
+        return postings.search(queries, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

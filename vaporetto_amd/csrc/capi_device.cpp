@@ -1289,6 +1289,96 @@ vpt_status vpt_postings_merge_device(const vpt_predictor* p, vpt_batch* b, const
                                  d_post_docs_out, d_post_tfs_out, capacity_out, d_counts, static_cast<hipStream_t>(hip_stream));
 }
 
+// ---- BM25 top-k search over a segment (kernels_postings_search.hip): slots, the trainer's scan, expand, the trainer's sort over the document
+// and the query word, heads, the trainer's scan, sum and ranges, the trainer's sort over the score and the query word, take.
+vpt_status vpt_postings_search_limits(uint32_t* max_query_slots) {
+    if (!max_query_slots) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *max_query_slots = vpt::kSearchMaxQuerySlots;
+    return VPT_OK;
+}
+
+namespace vptc {
+vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
+                                  uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
+                                  const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, uint32_t n_queries,
+                                  uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
+                                  uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
+                                  hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_doc_lens || !d_query_offsets || !d_query_terms || !d_query_weights || !d_hit_docs ||
+        !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
+    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    if (capacity_slots >= (1ull << 32) || capacity_candidates >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+    if (doc_base > (1ull << 32) || n_documents > (1ull << 32) - doc_base)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    if (!(k1 >= 0.0f && k1 <= 65536.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k1: must be between 0 and 65536");
+    if (!(bm_b >= 0.0f && bm_b <= 1.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: b: must be between 0 and 1");
+    if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
+    VPT_HIP(hipSetDevice(p->device));
+    VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
+    // the scratch in 256-byte sections: slot_df | base | slot_query | rec | hit | order | skey | flags | scan | qstart | hist | hist_scan | partials
+    const uint64_t n = capacity_candidates, ns = capacity_slots, nh = vpt::train_radix_scratch(n);
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_df = 0, o_base = o_df + pad(8 * size_t(ns)), o_sq = o_base + pad(8 * (size_t(ns) + 1)), o_rec = o_sq + pad(4 * size_t(ns)),
+                 o_hit = o_rec + pad(12 * size_t(n)), o_order = o_hit + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)),
+                 o_flags = o_skey + pad(4 * size_t(n)), o_scan = o_flags + pad(4 * size_t(n)), o_qstart = o_scan + pad(8 * (size_t(n) + 1)),
+                 o_hist = o_qstart + pad(8 * (size_t(n_queries) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)), o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
+                 total = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(ns)})) + 1));
+    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    unsigned char* m = b->d_post;
+    vpt::PostingsSearchParams P{};
+    P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.capacity_postings = capacity_postings; P.n_terms = n_terms;
+    P.doc_base = doc_base; P.n_docs = n_documents; P.doc_lens = d_doc_lens;
+    P.query_offsets = d_query_offsets; P.query_terms = d_query_terms; P.query_weights = d_query_weights; P.n_queries = n_queries; P.capacity_slots = ns;
+    P.n_places = n; P.k1 = k1; P.b = bm_b; P.avgdl = avgdl; P.k = k;
+    P.slot_df = reinterpret_cast<uint64_t*>(m + o_df); P.base = reinterpret_cast<uint64_t*>(m + o_base); P.slot_query = reinterpret_cast<uint32_t*>(m + o_sq);
+    P.rec = reinterpret_cast<uint32_t*>(m + o_rec); P.hit = reinterpret_cast<uint32_t*>(m + o_hit); P.order = reinterpret_cast<uint32_t*>(m + o_order);
+    P.skey = reinterpret_cast<uint32_t*>(m + o_skey); P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+    P.qstart = reinterpret_cast<uint64_t*>(m + o_qstart);
+    P.hit_docs = d_hit_docs; P.hit_scores = d_hit_scores; P.hit_counts = d_hit_counts; P.match_counts = d_match_counts; P.counts = d_counts;
+    P.status = b->d_ctrl;
+    uint64_t* hist = reinterpret_cast<uint64_t*>(m + o_hist);
+    uint64_t* hscan = reinterpret_cast<uint64_t*>(m + o_hscan);
+    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
+    // the bytes of the values 0 .. n_documents (at most four: the key is relative to doc_base) and 0 .. n_queries, least significant first
+    uint32_t doc_passes = 0, query_passes = 0;
+    for (uint64_t v = n_documents; v && doc_passes < 4; v >>= 8) ++doc_passes;
+    for (uint32_t v = n_queries; v; v >>= 8) ++query_passes;
+    uint32_t group[8], rank[8], n_group = 0, n_rank = 0;
+    for (uint32_t i = 0; i < doc_passes; ++i) group[n_group++] = (0u << 8) | (8 * i);
+    for (uint32_t i = 0; i < query_passes; ++i) group[n_group++] = (1u << 8) | (8 * i);
+    for (uint32_t i = 0; i < 4; ++i) rank[n_rank++] = (2u << 8) | (8 * i);
+    for (uint32_t i = 0; i < query_passes; ++i) rank[n_rank++] = (0u << 8) | (8 * i);
+    VPT_HIP(vpt::launch_postings_search_slots(P, stream));
+    VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
+    VPT_HIP(vpt::launch_postings_search_expand(P, stream));
+    VPT_HIP(vpt::train_radix_sort(P.rec, 3, group, n_group, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::launch_postings_search_heads(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_search_sum(P, stream));
+    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank, n_rank, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::launch_postings_search_take(P, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                      const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents,
+                                      const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
+                                      const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float b_param, float avgdl,
+                                      uint32_t k, uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts,
+                                      uint64_t* d_match_counts, uint64_t* d_counts, void* hip_stream) {
+    return postings_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens,
+                                  d_query_offsets, d_query_terms, d_query_weights, n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_candidates,
+                                  d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
+}
+
 // A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them
 // (vocab_count.hpp).  Counting may go on afterwards.
 vpt_status vpt_vocab_counter_finish(void* counter, uint64_t min_count, uint64_t max_entries, const uint8_t** surfaces, const uint64_t** offsets,

@@ -2,6 +2,8 @@
 // (vpt_predict_batch: chunks over lanes or three streams; vpt_tokenize_batch: lines in, tokenized lines out), the sharded call, single sentences.
 #include "capi_internal.hpp"
 
+#include <cmath>
+
 // (the entry points have C linkage from their declarations in include/vaporetto_hip.h)
 
 namespace {
@@ -1080,6 +1082,87 @@ vpt_status vpt_postings_merge(const vpt_predictor* p, const void* segments, size
         VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
         VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
     }
+    return VPT_OK;
+}
+
+// The BM25 weight of a term of document frequency df among n_documents, as tantivy's Bm25Weight computes it: one implementation for every binding.
+vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float* idf_out) {
+    if (!idf_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (df > n_documents) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: df: above n_documents");
+    const double x = (double(n_documents - df) + 0.5) / (double(df) + 0.5);
+    *idf_out = float(std::log(1.0 + x));
+    return VPT_OK;
+}
+
+// A host segment, host documents' lengths and host queries in, the hits out: what the segment holds (term_offsets[n_terms] postings) goes to one
+// allocation of this call, the candidates are counted from the host's term_offsets, the device search runs once, the four outputs come back.
+vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs, uint32_t n_terms,
+                               uint64_t doc_base, uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                               const int32_t* query_terms, const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl,
+                               uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_counts_out, uint64_t* match_counts_out,
+                               uint64_t* counts_out) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!term_offsets || !query_offsets || !hit_docs_out || !hit_scores_out || !hit_counts_out || !match_counts_out || !counts_out)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
+    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    const uint64_t n_post = term_offsets[n_terms], n_slots = query_offsets[n_queries];
+    if (n_post >= (1ull << 32) || n_slots >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+    if ((n_post && (!post_docs || !post_tfs)) || (n_documents && !doc_lens) || (n_slots && (!query_terms || !query_weights)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    uint64_t n_cand = 0;   // (bounds that do not ascend: the device reports them)
+    for (uint64_t s = 0; s < n_slots; ++s) {
+        const int32_t t = query_terms[s];
+        if (t < 0 || uint32_t(t) >= n_terms) continue;
+        const uint64_t a = term_offsets[t], e = term_offsets[uint32_t(t) + 1];
+        if (e > a && e <= n_post) n_cand += e - a;
+        if (n_cand >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+    }
+    if (n_documents > (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t n_out = size_t(n_queries) * k;
+    const size_t o_term = 0, o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_post) + 4), o_dl = o_tfs + pad(4 * size_t(n_post) + 4),
+                 o_qoff = o_dl + pad(4 * size_t(n_documents) + 4), o_qt = o_qoff + pad(8 * (size_t(n_queries) + 1)), o_qw = o_qt + pad(4 * size_t(n_slots) + 4),
+                 o_hd = o_qw + pad(4 * size_t(n_slots) + 4), o_hs = o_hd + pad(4 * n_out), o_hc = o_hs + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
+                 o_cnt = o_mc + pad(8 * size_t(n_queries));
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st;
+    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    DevBuf<unsigned char> mem;
+    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    unsigned char* m = mem;
+    VPT_HIP(hipMemcpyAsync(m + o_term, term_offsets, 8 * (size_t(n_terms) + 1), hipMemcpyHostToDevice, s));
+    if (n_post) {
+        VPT_HIP(hipMemcpyAsync(m + o_docs, post_docs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(m + o_tfs, post_tfs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
+    }
+    if (n_documents) VPT_HIP(hipMemcpyAsync(m + o_dl, doc_lens, 4 * size_t(n_documents), hipMemcpyHostToDevice, s));
+    VPT_HIP(hipMemcpyAsync(m + o_qoff, query_offsets, 8 * (size_t(n_queries) + 1), hipMemcpyHostToDevice, s));
+    if (n_slots) {
+        VPT_HIP(hipMemcpyAsync(m + o_qt, query_terms, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(m + o_qw, query_weights, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
+    }
+    VPT_HIP(hipMemsetAsync(m + o_hd, 0, o_hc - o_hd, s));   // an entry at or behind a query's hit count is not written on the device: zeros come back
+    st = postings_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
+                                reinterpret_cast<const uint32_t*>(m + o_tfs), n_terms, n_post, doc_base, n_documents, reinterpret_cast<const uint32_t*>(m + o_dl),
+                                reinterpret_cast<const uint64_t*>(m + o_qoff), reinterpret_cast<const int32_t*>(m + o_qt),
+                                reinterpret_cast<const float*>(m + o_qw), n_queries, n_slots, k1, b_param, avgdl, k, n_cand,
+                                reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs), reinterpret_cast<uint32_t*>(m + o_hc),
+                                reinterpret_cast<uint64_t*>(m + o_mc), reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(counts_out, m + o_cnt, 24, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_counts_out, m + o_hc, 4 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(match_counts_out, m + o_mc, 8 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 

@@ -306,6 +306,7 @@ struct vpt_vocab_counter {
 };
 constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: full (max_keys / arena_chars)";
 constexpr const char* kPostingsTooSmall = "InvalidArgumentError: capacity: smaller than the number of postings";
+constexpr const char* kCandidatesTooSmall = "InvalidArgumentError: capacity_candidates: smaller than the number of candidates";
 
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
@@ -385,7 +386,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
-    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams
+    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_search_device: PostingsSearchParams
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -526,8 +527,13 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrBadTokenCsr)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: token_offsets / token_starts / token_ends: do not describe the documents' tokens");
     if (bits & vpt::kErrVocabCounterFull) return fail(VPT_INVALID_ARGUMENT, kVocabCounterFull);
+    if (bits & vpt::kErrBadQueryCsr)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query_offsets: do not describe the queries' slots");
     if (bits & vpt::kErrBadSegment)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: term_offsets or postings are not a segment's");
+    if (bits & vpt::kErrBadWeights) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: weights: negative or not finite");
+    if (bits & vpt::kErrQueryTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: more than 1024 slots");
+    if (bits & vpt::kErrCandidatesTooSmall) return fail(VPT_INVALID_ARGUMENT, kCandidatesTooSmall);
     if (bits & vpt::kErrSegmentsOverlap)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segments: document ranges overlap or descend");
     if (bits & vpt::kErrTfOverflow) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tf: sum exceeds 32 bits");
@@ -726,6 +732,13 @@ vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t*
 vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
                                  unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
                                  uint64_t* d_counts, hipStream_t stream);
+// The BM25 top-k search over a segment (vpt_postings_search_device; kernels_postings_search.hip)
+vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
+                                  uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
+                                  const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, uint32_t n_queries,
+                                  uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
+                                  uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
+                                  hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

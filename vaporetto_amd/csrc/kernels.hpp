@@ -72,6 +72,10 @@ constexpr uint32_t kErrPostingsTooSmall = 2048u;   // the postings pass: more po
 constexpr uint32_t kErrBadSegment = 4096u;         // the postings merge: term_offsets or postings that are not a segment's (kernels_postings_merge.hip)
 constexpr uint32_t kErrSegmentsOverlap = 8192u;    // the postings merge, ordered: the segments' document ranges overlap or descend
 constexpr uint32_t kErrTfOverflow = 16384u;        // the postings merge: a combined tf above 32 bits
+constexpr uint32_t kErrBadQueryCsr = 32768u;          // the postings search: query_offsets that decrease, exceed capacity_slots or leave a slot unowned
+constexpr uint32_t kErrBadWeights = 65536u;           // the postings search: a weight that is negative or not finite
+constexpr uint32_t kErrQueryTooLong = 131072u;        // the postings search: a query of more than kSearchMaxQuerySlots slots
+constexpr uint32_t kErrCandidatesTooSmall = 262144u;  // the postings search: more candidates than capacity_candidates
 
 
 struct ScoreParams {
@@ -408,6 +412,56 @@ hipError_t launch_postings_merge_ordered(const PostingsMergeParams& P, hipStream
 hipError_t launch_postings_merge_records(const PostingsMergeParams& P, hipStream_t stream);   // the offsets' check, then the records
 hipError_t launch_postings_merge_heads(const PostingsMergeParams& P, hipStream_t stream);
 hipError_t launch_postings_merge_emit(const PostingsMergeParams& P, hipStream_t stream);      // emit, then the terms
+// BM25 top-k search of a batch of queries over one postings segment (kernels_postings_search.hip).  A CANDIDATE is a (slot, posting of the slot's
+// term) pair; the slots' dfs are scanned into candidate bases, and every launch is over the capacity_slots slots, the capacity_candidates PLACES,
+// the n_queries + 1 query bounds or the n_queries * k outputs.  Scratch of the batch: per slot slot_df (u64), base (u64, [capacity_slots + 1]) and
+// slot_query (u32); per place rec [3] {document - doc_base, query or the sentinel n_queries, bits of c}, hit [3] {query or the sentinel,
+// document - doc_base, ~bits of the score}, order, skey, flags (u32) and scan (u64, [places + 1]); qstart [n_queries + 1] (u64).  The caller runs
+// train_scan (slot_df -> base) between slots and expand, train_radix_sort (rec, stride 3: the document word, then the query word) between expand
+// and heads, train_scan (flags -> scan) between heads and sum, train_radix_sort (hit, stride 3: the score word, then the query word) between
+// sum and take.  A launch behind expand that finds one of kSearchErrors in the status leaves the four outputs alone.
+constexpr uint32_t kSearchMaxQuerySlots = 1024;
+constexpr uint32_t kSearchMaxQueries = 1u << 24;
+constexpr uint32_t kSearchErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrQueryTooLong | kErrCandidatesTooSmall;
+struct PostingsSearchParams {
+    const uint64_t* term_offsets;   // [n_terms + 1]
+    const uint32_t* post_docs;      // [capacity_postings]
+    const uint32_t* post_tfs;       // [capacity_postings]
+    uint64_t capacity_postings;
+    uint32_t n_terms;
+    uint64_t doc_base;
+    uint64_t n_docs;
+    const uint32_t* doc_lens;       // [n_docs]
+    const uint64_t* query_offsets;  // [n_queries + 1]
+    const int32_t* query_terms;     // [capacity_slots]
+    const float* query_weights;     // [capacity_slots]
+    uint32_t n_queries;
+    uint64_t capacity_slots;        // < 2^32
+    uint64_t n_places;              // capacity_candidates, < 2^32
+    float k1, b, avgdl;
+    uint32_t k;
+    uint64_t* slot_df;
+    uint64_t* base;
+    uint32_t* slot_query;
+    uint32_t* rec;
+    uint32_t* hit;
+    uint32_t* order;
+    uint32_t* skey;
+    uint32_t* flags;
+    uint64_t* scan;
+    uint64_t* qstart;
+    uint32_t* hit_docs;             // [n_queries * k]
+    float* hit_scores;              // [n_queries * k]
+    uint32_t* hit_counts;           // [n_queries]
+    uint64_t* match_counts;         // [n_queries]
+    uint64_t* counts;               // [3]: candidates, matches (written), skipped slots (added to: zero before the launches)
+    uint32_t* status;
+};
+hipError_t launch_postings_search_slots(const PostingsSearchParams& P, hipStream_t stream);
+hipError_t launch_postings_search_expand(const PostingsSearchParams& P, hipStream_t stream);
+hipError_t launch_postings_search_heads(const PostingsSearchParams& P, hipStream_t stream);
+hipError_t launch_postings_search_sum(const PostingsSearchParams& P, hipStream_t stream);    // sum, then the queries' ranges
+hipError_t launch_postings_search_take(const PostingsSearchParams& P, hipStream_t stream);
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
