@@ -530,6 +530,56 @@ impl Postings {
         Ok((hits, match_counts))
     }
 
+    /// Exact-phrase BM25 top-k of every phrase over this segment and its position lists (`vpt_postings_phrase_search`; the definition is in
+    /// include/vaporetto_hip.h).  `first` [postings + 1] and `positions` [indexed tokens]: posting q's positions are
+    /// `positions[first[q] .. first[q + 1]]`, strictly ascending (what `vpt_token_stream_positional_postings_batch` returns).  `phrases`: term
+    /// ids, each ONE phrase, its ids at consecutive positions in order; an id outside the vocabulary makes it match nothing.  The weight of a
+    /// phrase is tantivy's: the f32 sum, in slot order, of `vpt_okapi_idf` over its slots.  Returns per phrase at most `k`
+    /// (document, score, frequency) by score descending, then document ascending, and the match counts.
+    pub fn phrase_search(&self, predictor: &Predictor, first: &[u64], positions: &[u32], phrases: &[Vec<i32>], doc_lens: &[u32], doc_base: u64,
+                         k: u32, k1: f32, b: f32) -> Result<(Vec<Vec<(u32, f32, u32)>>, Vec<u64>)> {
+        if phrases.is_empty() {
+            return Ok((Vec::new(), Vec::new()));
+        }
+        let n = self.term_offsets.len();
+        if n == 0 || doc_lens.is_empty() || self.docs.len() != self.tfs.len() || self.term_offsets[n - 1] != self.docs.len() as u64
+            || first.len() != self.docs.len() + 1 || first[first.len() - 1] != positions.len() as u64 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: phrase_search: the arrays do not belong together".into()));
+        }
+        let avgdl = (doc_lens.iter().map(|&l| l as f64).sum::<f64>() / doc_lens.len() as f64) as f32;
+        let mut offsets = vec![0u64];
+        let (mut terms, mut weights) = (Vec::new(), Vec::new());
+        for q in phrases {
+            let mut sum: Option<f32> = None;
+            for &t in q {
+                if t >= 0 && (t as usize) < n - 1 {
+                    let mut w = 0f32;
+                    check(unsafe { ffi::vpt_okapi_idf(doc_lens.len() as u64, self.df(t as usize), &mut w) })?;
+                    sum = Some(match sum { Some(s) => s + w, None => w });
+                }
+                terms.push(t);
+            }
+            weights.push(sum.unwrap_or(0f32));
+            offsets.push(terms.len() as u64);
+        }
+        terms.push(0);
+        let mut pos = positions.to_vec();
+        pos.push(0);
+        let n_out = phrases.len() * k as usize + 1;
+        let (mut hit_docs, mut hit_scores, mut hit_freqs) = (vec![0u32; n_out], vec![0f32; n_out], vec![0u32; n_out]);
+        let (mut hit_counts, mut match_counts, mut counts) = (vec![0u32; phrases.len()], vec![0u64; phrases.len()], [0u64; 3]);
+        check(unsafe {
+            ffi::vpt_postings_phrase_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(), first.as_ptr(), pos.as_ptr(),
+                                            (n - 1) as u32, doc_base, doc_lens.len() as u64, doc_lens.as_ptr(), offsets.as_ptr(), terms.as_ptr(),
+                                            weights.as_ptr(), phrases.len() as u32, k1, b, avgdl, k, hit_docs.as_mut_ptr(), hit_scores.as_mut_ptr(),
+                                            hit_freqs.as_mut_ptr(), hit_counts.as_mut_ptr(), match_counts.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        let hits = (0..phrases.len())
+            .map(|q| (0..hit_counts[q] as usize).map(|j| { let at = q * k as usize + j; (hit_docs[at], hit_scores[at], hit_freqs[at]) }).collect())
+            .collect();
+        Ok((hits, match_counts))
+    }
+
     /// The document frequency of `term`.
     pub fn df(&self, term: usize) -> u64 {
         self.term_offsets[term + 1] - self.term_offsets[term]

@@ -19,6 +19,9 @@
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --search "QUERY" [--top K] < documents.txt
 // With --search: the query text is tokenised as a document is, its tokens are weighted with BM25's idf and the K (default 10) best documents of
 // the index are found on the device; one line per hit, best first: document <TAB> the score's bits in hex <TAB> the score.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] --phrase "QUERY" [--top K] < documents.txt
+// With --phrase: the documents are indexed with positions, the query text is ONE phrase -- its tokens at consecutive positions, in order -- and
+// the K best documents that hold it are found on the device; the lines of --search, plus <TAB> the phrase's occurrences in the document.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -79,12 +82,24 @@ int main(int argc, char** argv) {
             size_t segment_docs = 0;
             int n_args = argc;
             const char* query = nullptr;
+            const char* phrase = nullptr;
             uint32_t top = 10;
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
+            else if (n_args > 6 && std::strcmp(argv[n_args - 2], "--phrase") == 0) { phrase = argv[n_args - 1]; n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }
             const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
             vaporetto_hip::Postings post;
+            if (phrase) {   // (a merge does not carry position lists: one segment)
+                post = plain.index(docs, vocab, doc_base, true, true);
+                const auto found = plain.phrase_search(post, vocab, {std::string(phrase)}, plain.doc_lens(docs, vocab), doc_base, top);
+                for (const vaporetto_hip::Postings::PhraseHit& h : found.hits[0]) {
+                    uint32_t bits;
+                    std::memcpy(&bits, &h.score, 4);
+                    std::printf("%u\t%08x\t%.9g\t%u\n", unsigned(h.document), unsigned(bits), double(h.score), unsigned(h.freq));
+                }
+                return 0;
+            }
             if (segment_docs) {
                 std::vector<std::vector<std::string>> batches;
                 for (size_t a = 0; a < docs.size(); a += segment_docs)

@@ -766,6 +766,100 @@ vpt_status vpt_postings_search(const vpt_predictor *p, const uint64_t *term_offs
                                uint64_t *counts_out);
 vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float *idf_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Phrase queries on the device: the positions of a segment, exact-phrase BM25 top-k      (the adapter indexes WithFreqsAndPositions, and positions
+ *                                                 serve phrase queries: what tantivy's query parser makes of a query text of several tokens)
+ *
+ * vpt_postings_positions_device: the position lists of a segment, behind a vpt_postings_batch_device call that was given the optional pair.
+ *   d_token_offsets [n_documents + 1], capacity_in: as that call took them.  d_token_positions uint32 [capacity_in] or NULL: NULL makes the
+ *   position of token t of document d t - token_offsets[d]; else it is the array the stream calls write (a stop filter leaves gaps).
+ *   d_term_offsets [n_terms + 1]: the postings are min(d_term_offsets[n_terms], capacity_postings), read on the device.  d_post_first
+ *   [capacity_postings + 1], d_token_order [capacity_in]: what the postings call wrote.  Out: d_post_positions uint32 [capacity_in]; for every
+ *   i below the indexed tokens post_first[postings], d_post_positions[i] = the position of token d_token_order[i]; nothing is written at or
+ *   behind the indexed tokens.  One launch, a lane per place of capacity_in, the owner document by the id pass's bisection; asynchronous on
+ *   hip_stream.  At the call, VPT_INVALID_ARGUMENT: a NULL pointer other than d_token_positions, n_terms == 0 or > 2^24, capacity_in >= 2^32,
+ *   a workspace of another predictor.  At vpt_batch_sync, VPT_INVALID_ARGUMENT: the id pass's message when token_offsets decrease, exceed
+ *   capacity_in or leave a token no document owns (a token_order entry at or above the tokens included); "InvalidArgumentError: positions: do
+ *   not strictly ascend inside a document's list" when inside one posting a position is not above the one before it (checked against the
+ *   neighbour in the same posting; the search's bisection relies on it).  Whatever the arrays hold, a token index is below
+ *   min(token_offsets[n], capacity_in) before anything is read through it and a place below capacity_in before it is written.
+ *
+ * A POSITIONAL SEGMENT is a segment's three arrays plus post_first [postings + 1] and post_positions [indexed tokens]: posting q's positions are
+ *   post_positions[post_first[q] .. post_first[q + 1]), strictly ascending, post_tfs[q] of them.
+ *
+ * vpt_postings_phrase_search_device: a batch of exact-phrase queries against ONE positional segment.
+ *   Segment: d_term_offsets [n_terms + 1], d_post_docs / d_post_tfs [capacity_postings], d_post_first [capacity_postings + 1],
+ *   d_post_positions [capacity_positions].  Documents: doc_base, n_documents, d_doc_lens as in vpt_postings_search_device.
+ *   Queries, a CSR: d_query_offsets [n_queries + 1], d_query_terms int32 [capacity_slots]; query q is ONE phrase, its slots in order.
+ *   d_query_weights float [n_queries]: one weight per query, the caller's (the wrappers pass tantivy's phrase weight: the binary32 sum, in slot
+ *   order, of vpt_okapi_idf of every slot's term); the device never takes a logarithm.
+ *   Occurrence: phrase q of L >= 1 slots occurs in document d at start s when for every j in [0, L) the positions of posting (term_j, d)
+ *   contain s + j (64-bit arithmetic; a repeated term is two distinct places).  pf(q, d) = the number of distinct starts; d MATCHES q when
+ *   pf >= 1.  A query with a slot outside [0, n_terms) matches nothing and adds 1 to d_counts[2]; an empty query and a query with a term of
+ *   df 0 match nothing.  Slop is 0; nothing is reordered.
+ *   Score, in IEEE binary32, round to nearest, no contraction, in exactly the order of vpt_postings_search_device's c, with the query's weight
+ *   w and f = float(pf):
+ *       r = float(dl[d - doc_base]) / avgdl;  K = k1 * ((1.0f - b) + b * r);  f = float(pf);  score = w * ((f * (k1 + 1.0f)) / (f + K))
+ *   one c, no sum: a phrase of one slot has the bits vpt_postings_search_device gives a one-slot query of the same weight.
+ *   Output, per query q: d_match_counts[q] = the matching documents; d_hit_counts[q] = min(k, matches); d_hit_docs[q * k + j] /
+ *   d_hit_scores[q * k + j] / d_hit_freqs[q * k + j] (uint32, the hit's pf; d_hit_freqs may be NULL) for j below the hit count = the matches by
+ *   score descending, then document ascending; entries at or behind the hit count are not written.  d_counts [3] = the probes (below), the
+ *   matches of all queries, the skipped queries.  Two runs, on one workspace or on two, give identical bytes.
+ *   Launches (kernels_postings_phrase.hip), each sized from n_queries, capacity_probes or n_queries * k, none from a value read back.  A
+ *   query's ANCHOR is the slot whose term has the fewest indexed tokens, post_first[term_offsets[t + 1]] - post_first[term_offsets[t]], the
+ *   first such slot; its PROBES are the anchor term's positions, one contiguous run of post_positions (0 when the query cannot match);
+ *   capacity_probes bounds the sum over the queries.  queries (a lane per query: checks, anchor, probe count), the trainer's scan (probe
+ *   bases), probe (a lane per probe place: its posting by bisection over post_first, start = position - anchor slot, every other slot's
+ *   posting of that document by bisection over post_docs and start + j by bisection over its positions), the trainer's scan, heads (pf = the
+ *   scan's difference over a posting), the trainer's scan, emit (hits are born in (query, document) order) and ranges, the trainer's stable
+ *   radix sort over ~bits(score) (4 passes) and the query word, take.  Asynchronous on hip_stream, errors at vpt_batch_sync; no atomic decides a
+ *   value.  Scratch of the workspace: 36 bytes per query, nothing per slot, 48 bytes per place of capacity_probes (a hit of three words, a scan
+ *   word, seven index and flag words) and 16 bytes per 16 places of histograms.
+ *   At the call, VPT_INVALID_ARGUMENT: vpt_postings_search_device's list, with d_post_first / d_post_positions among the pointers,
+ *   capacity_probes for capacity_candidates and d_hit_freqs the one pointer that may be NULL.
+ *   At the sync, VPT_INVALID_ARGUMENT: the query_offsets, segment and weights messages of vpt_postings_search_device (segment: a slot's term
+ *   bounds descend or end above capacity_postings; post_first of a term's two bounds or of a probed posting descend or exceed
+ *   capacity_positions, or their difference is not the posting's tf; a probed posting's document outside [doc_base, doc_base + n_documents) or
+ *   not above the one before it -- all seen before doc_lens is touched); "InvalidArgumentError: query: a phrase of more than 64 terms"
+ *   (vpt_postings_phrase_limits); "InvalidArgumentError: capacity_probes: smaller than the number of probes" -- d_counts[0] then holds the
+ *   number needed.  After any of these the five outputs are as they were before the call; d_counts[0] is the probes (the need), d_counts[1] and
+ *   d_counts[2] are written and unspecified.  Positions that do not ascend inside a posting are
+ *   NOT seen here (vpt_postings_positions_device reports them): the result is then unspecified.  Whatever the arrays hold, nothing is read
+ *   outside the stated sizes and nothing is written outside the five outputs' stated sizes, d_counts [3] and the workspace.
+ * vpt_postings_phrase_limits: the most slots a phrase may have.
+ * vpt_postings_phrase_search: the same over HOST arrays (post_first[term_offsets[n_terms]] positions); the probes are counted on the host as
+ *   the device counts them, the device call runs once, the five outputs and counts_out [3] come back (hit entries at or behind a query's hit
+ *   count come back 0).  Returns when the device is through.
+ * vpt_token_stream_positional_postings_batch: vpt_token_stream_postings_batch's steps, also returning post_first_out [capacity + 1] and
+ *   post_positions_out [capacity_positions], the latter from the stream's token_positions; *n_positions_out = the indexed tokens.  More than
+ *   capacity_positions of them: VPT_INVALID_ARGUMENT "InvalidArgumentError: capacity_positions: smaller than the number of indexed tokens",
+ *   *n_positions_out = the number needed. */
+vpt_status vpt_postings_positions_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_token_offsets, size_t n_documents,
+                                         uint64_t capacity_in, const uint32_t *d_token_positions, const uint64_t *d_term_offsets,
+                                         uint32_t n_terms, const uint64_t *d_post_first, uint64_t capacity_postings,
+                                         const uint32_t *d_token_order, uint32_t *d_post_positions, void *hip_stream);
+vpt_status vpt_postings_phrase_search_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets, const uint32_t *d_post_docs,
+                                             const uint32_t *d_post_tfs, const uint64_t *d_post_first, const uint32_t *d_post_positions,
+                                             uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                             uint64_t n_documents, const uint32_t *d_doc_lens, const uint64_t *d_query_offsets,
+                                             const int32_t *d_query_terms, const float *d_query_weights, uint32_t n_queries,
+                                             uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k, uint64_t capacity_probes,
+                                             uint32_t *d_hit_docs, float *d_hit_scores, uint32_t *d_hit_freqs, uint32_t *d_hit_counts,
+                                             uint64_t *d_match_counts, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_phrase_limits(uint32_t *max_phrase_terms);
+vpt_status vpt_postings_phrase_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs, const uint32_t *post_tfs,
+                                      const uint64_t *post_first, const uint32_t *post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t *doc_lens, const uint64_t *query_offsets, const int32_t *query_terms,
+                                      const float *query_weights, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                      uint32_t *hit_docs_out, float *hit_scores_out, uint32_t *hit_freqs_out, uint32_t *hit_counts_out,
+                                      uint64_t *match_counts_out, uint64_t *counts_out);
+vpt_status vpt_token_stream_positional_postings_batch(const vpt_predictor *p, const uint8_t *utf8, const uint64_t *byte_offsets,
+                                                      size_t n_documents, unsigned wsconst_flags, const void *tagger, const void *stop,
+                                                      const void *vocab, unsigned vocab_flags, uint64_t doc_base, uint64_t *term_offsets_out,
+                                                      uint32_t *post_docs_out, uint32_t *post_tfs_out, uint64_t *post_first_out,
+                                                      uint64_t capacity, uint32_t *post_positions_out, uint64_t capacity_positions,
+                                                      uint64_t *n_postings_out, uint64_t *n_dropped_out, uint64_t *n_positions_out);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

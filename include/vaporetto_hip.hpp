@@ -461,6 +461,10 @@ private:
 struct Postings {
     std::vector<uint64_t> term_offsets;   // [n_terms + 1]
     std::vector<uint32_t> docs, tfs;
+    // A positional segment (VaporettoTokenizer::index with positions) also has first [postings + 1] and positions [indexed tokens]: posting q's
+    // positions are positions[first[q] .. first[q + 1]), strictly ascending; both empty otherwise.
+    std::vector<uint64_t> first;
+    std::vector<uint32_t> positions;
     uint64_t n_dropped = 0;
     size_t n_terms() const { return term_offsets.size() - 1; }
     uint64_t df(size_t term) const { return term_offsets[term + 1] - term_offsets[term]; }
@@ -482,7 +486,65 @@ struct Postings {
     SearchResult search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& queries, const std::vector<uint32_t>& doc_lens,
                         uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
                         const std::vector<std::vector<float>>* weights = nullptr) const;
+    // Exact-phrase BM25 top-k of every phrase over this POSITIONAL segment (vpt_postings_phrase_search; the definition is in vaporetto_hip.h).
+    // phrases: term ids, each vector ONE phrase, its ids at consecutive positions in order; an id outside [0, n_terms) makes it match nothing.
+    // weights: one per phrase, or nullptr for tantivy's phrase weight (the float sum, in slot order, of vpt_okapi_idf over the slots).
+    struct PhraseHit { uint32_t document; float score; uint32_t freq; };
+    struct PhraseResult {
+        std::vector<std::vector<PhraseHit>> hits;   // per phrase at most k, by score descending, then document ascending
+        std::vector<uint64_t> match_counts;         // per phrase
+        uint64_t counts[3] = {0, 0, 0};             // probes, matches, skipped phrases
+    };
+    PhraseResult phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases, const std::vector<uint32_t>& doc_lens,
+                               uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
+                               const std::vector<float>* weights = nullptr) const;
 };
+
+inline Postings::PhraseResult Postings::phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases,
+                                                      const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
+                                                      const std::vector<float>* weights) const {
+    PhraseResult out;
+    if (phrases.empty()) return out;
+    if (first.size() != docs.size() + 1)
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: phrase_search: the postings were made without positions");
+    if (term_offsets.empty() || doc_lens.empty() || (weights && weights->size() != phrases.size()) || docs.size() != tfs.size() ||
+        term_offsets.back() != docs.size() || first.back() != positions.size())
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: phrase_search: the arrays do not belong together");
+    double total = 0;
+    for (uint32_t l : doc_lens) total += double(l);
+    const float avgdl = float(total / double(doc_lens.size()));
+    std::vector<uint64_t> qoff(1, 0);
+    std::vector<int32_t> terms;
+    std::vector<float> w;
+    for (size_t q = 0; q < phrases.size(); ++q) {
+        float sum = 0.0f;
+        bool any = false;
+        for (const int32_t t : phrases[q]) {
+            terms.push_back(t);
+            if (weights || t < 0 || size_t(t) >= n_terms()) continue;
+            float x = 0.0f;
+            detail::check(vpt_okapi_idf(doc_lens.size(), df(size_t(t)), &x));
+            sum = any ? sum + x : x;
+            any = true;
+        }
+        w.push_back(weights ? (*weights)[q] : sum);
+        qoff.push_back(terms.size());
+    }
+    terms.push_back(0);   // (data() of an empty vector may be NULL)
+    std::vector<uint32_t> pos(positions);
+    pos.push_back(0);
+    const size_t n_out = phrases.size() * size_t(k) + 1;
+    std::vector<uint32_t> hd(n_out), hf(n_out), hc(phrases.size());
+    std::vector<float> hs(n_out);
+    out.match_counts.assign(phrases.size(), 0);
+    detail::check(vpt_postings_phrase_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(), uint32_t(n_terms()),
+                                             doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), terms.data(), w.data(), uint32_t(phrases.size()), k1, b,
+                                             avgdl, k, hd.data(), hs.data(), hf.data(), hc.data(), out.match_counts.data(), out.counts));
+    out.hits.resize(phrases.size());
+    for (size_t q = 0; q < phrases.size(); ++q)
+        for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(PhraseHit{hd[q * size_t(k) + j], hs[q * size_t(k) + j], hf[q * size_t(k) + j]});
+    return out;
+}
 
 inline Postings::SearchResult Postings::search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& queries, const std::vector<uint32_t>& doc_lens,
                                                uint64_t doc_base, uint32_t k, float k1, float b, const std::vector<std::vector<float>>* weights) const {
@@ -700,7 +762,9 @@ public:
 
     // The postings of `texts` (a segment) over `vocab` (made for predictor()): term = vocabulary id, document = doc_base + the text's index,
     // empty texts included, tf = the term's tokens among those this tokenizer streams (vpt_token_stream_postings_batch); normalize as in encode.
-    Postings index(const std::vector<std::string>& texts, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true) const {
+    // positions: a positional segment (first, positions: the stream's token positions; vpt_token_stream_positional_postings_batch).
+    Postings index(const std::vector<std::string>& texts, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true,
+                   bool positions = false) const {
         std::string text;
         std::vector<uint64_t> boff(1, 0);
         for (const std::string& t : texts) { text += t; boff.push_back(text.size()); }
@@ -710,10 +774,22 @@ public:
         out.docs.resize(cap);
         out.tfs.resize(cap);
         uint64_t n_postings = 0;
-        detail::check(vpt_token_stream_postings_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
-                                                      tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, vocab.raw(),
-                                                      normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u, doc_base, out.term_offsets.data(),
-                                                      out.docs.data(), out.tfs.data(), cap, &n_postings, &out.n_dropped));
+        if (positions) {
+            uint64_t n_positions = 0;
+            out.first.resize(cap + 1);
+            out.positions.resize(cap);
+            detail::check(vpt_token_stream_positional_postings_batch(
+                predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_, tagger_ ? tagger_->raw() : nullptr,
+                stop_ ? stop_->raw() : nullptr, vocab.raw(), normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u, doc_base, out.term_offsets.data(),
+                out.docs.data(), out.tfs.data(), out.first.data(), cap, out.positions.data(), cap, &n_postings, &out.n_dropped, &n_positions));
+            out.first.resize(size_t(n_postings) + 1);
+            out.positions.resize(size_t(n_positions));
+        } else {
+            detail::check(vpt_token_stream_postings_batch(predictor_.raw(), reinterpret_cast<const uint8_t*>(text.data()), boff.data(), texts.size(), flags_,
+                                                          tagger_ ? tagger_->raw() : nullptr, stop_ ? stop_->raw() : nullptr, vocab.raw(),
+                                                          normalize ? unsigned(VPT_FLAG_KYTEA_FULLWIDTH) : 0u, doc_base, out.term_offsets.data(),
+                                                          out.docs.data(), out.tfs.data(), cap, &n_postings, &out.n_dropped));
+        }
         out.docs.resize(size_t(n_postings));
         out.tfs.resize(size_t(n_postings));
         return out;
@@ -748,6 +824,17 @@ public:
         std::vector<std::vector<int32_t>> queries(texts.size());
         for (size_t i = 0; i < texts.size(); ++i) queries[i].assign(enc.second.begin() + enc.first[i], enc.second.begin() + enc.first[i + 1]);
         return postings.search(predictor_, queries, doc_lens, doc_base, k, k1, b);
+    }
+
+    // Exact-phrase BM25 top-k of query TEXTS over a positional `postings` (index with positions): each text is tokenised and encoded as
+    // documents are and is ONE phrase -- a token without a vocabulary entry makes it match nothing -- then Postings::phrase_search.
+    Postings::PhraseResult phrase_search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
+                                         const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f,
+                                         float b = 0.75f, bool normalize = true) const {
+        const auto enc = encode(texts, vocab, normalize);
+        std::vector<std::vector<int32_t>> phrases(texts.size());
+        for (size_t i = 0; i < texts.size(); ++i) phrases[i].assign(enc.second.begin() + enc.first[i], enc.second.begin() + enc.first[i + 1]);
+        return postings.phrase_search(predictor_, phrases, doc_lens, doc_base, k, k1, b);
     }
 
 private:

@@ -22,6 +22,12 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       segment (kernels_postings_search.hip) by device events, beside two yardsticks of the same run: the general merge over one segment of as
       many input places as the search has candidates, and a device-to-device copy of half of 8 bytes a candidate plus 8 bytes a hit (a copy of
       B bytes moves B in and B out).  Q is halved until the candidates are at most --search-max-candidates (profiles/postings_search_bench.json).
+  --phrase Q,L,K: with --postings, Q phrases of L consecutive tokens of random documents (windows whose tokens all have a vocabulary entry, so
+      every phrase occurs at least once), top K, over the one-pass segment with its position lists (kernels_postings_phrase.hip) by device
+      events, beside yardsticks of the same process: the OR search of --search (the parent's kernels) over the same queries, every token a slot
+      with its idf; the phrase search over every phrase's anchor slot alone (the same probes, scans and sort, none of the other slots'
+      bisections: the difference is what those bisections cost); and a device-to-device copy of half of 4 bytes a probe plus 12 bytes a hit.
+      Q is halved until the probes and the OR search's candidates are at most --search-max-candidates (profiles/postings_phrase_bench.json).
   --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
       --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
@@ -229,6 +235,116 @@ def search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_te
     return out
 
 
+def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs, d_ptfs, n_post, seg):
+    """--phrase Q,L,K over the one-pass segment and its position lists (seg: post_first, post_positions, the indexed tokens); see the module's
+    docstring"""
+    from vaporetto_amd import api
+    Q, L, K = (int(x) for x in spec.split(","))
+    d_first, d_ppos, n_idx = seg
+    term = d_term.cpu().numpy().astype(np.int64)
+    df = np.diff(term)
+    tfs = d_ptfs[:n_post].cpu().numpy().astype(np.int64)
+    count = np.add.reduceat(np.concatenate([tfs, [0]]), np.minimum(term[:-1], n_post)) * (df > 0)
+    toff = dev_off.astype(np.int64)
+    dl = np.diff(toff)
+    known = (host_ids >= 0) & (host_ids < n_terms)
+    run = np.concatenate([[0], np.cumsum(~known)])   # a window [a, a + L) is all known when run[a + L] == run[a]
+    long_docs = np.flatnonzero(dl >= L)
+    rng = np.random.default_rng(7)
+    phrases = []
+    for _ in range(64 * Q):
+        if len(phrases) == Q or len(long_docs) == 0:
+            break
+        d = int(long_docs[rng.integers(len(long_docs))])
+        a = int(toff[d]) + int(rng.integers(int(dl[d]) - L + 1))
+        if run[a + L] == run[a]:
+            phrases.append(host_ids[a:a + L].astype(np.int32))
+    if not phrases:
+        raise SystemExit("--phrase: no window of %d tokens with vocabulary entries" % L)
+    while True:
+        terms = np.concatenate(phrases)
+        n_probes = int(sum(int(count[ph].min()) for ph in phrases))
+        n_cand = int(df[terms].sum())
+        if max(n_probes, n_cand) <= args.search_max_candidates or len(phrases) == 1:
+            break
+        phrases = phrases[:len(phrases) // 2]
+    Q = len(phrases)
+    if max(n_probes, n_cand) >= 1 << 32:
+        raise SystemExit("--phrase: %d probes, %d candidates" % (n_probes, n_cand))
+    idf = {int(t): api.bm25_idf(S, int(df[t])) for t in set(terms.tolist())}
+    weights = []
+    for ph in phrases:   # tantivy's phrase weight: the float32 sum in slot order
+        w = idf[int(ph[0])]
+        for t in ph[1:]:
+            w = np.float32(w + idf[int(t)])
+        weights.append(w)
+    anchors = np.array([ph[int(np.argmin(count[ph]))] for ph in phrases], np.int32)
+    avgdl = float(np.float32(float(dl.sum()) / S))
+    d_dl = torch.from_numpy(dl.astype(np.int32)).to(dev)
+    d_qoff = torch.from_numpy(np.arange(0, Q * L + 1, L, dtype=np.int64)).to(dev)
+    d_qt = torch.from_numpy(terms).to(dev)
+    d_qw = torch.from_numpy(np.array(weights, np.float32)).to(dev)
+    d_sw = torch.from_numpy(np.array([idf[int(t)] for t in terms], np.float32)).to(dev)
+    d_aoff = torch.from_numpy(np.arange(0, Q + 1, dtype=np.int64)).to(dev)
+    d_at = torch.from_numpy(anchors).to(dev)
+    d_hd, d_hs, d_hf = (torch.zeros(Q * K, dtype=dt, device=dev) for dt in (torch.int32, torch.float32, torch.int32))
+    d_hc, d_mc, d_cnt = torch.zeros(Q, dtype=torch.int32, device=dev), torch.zeros(Q, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev)
+
+    def phrase():
+        batch.phrase_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), d_first.data_ptr(), d_ppos.data_ptr(), n_terms, n_post, n_idx,
+                                     0, S, d_dl.data_ptr(), d_qoff.data_ptr(), d_qt.data_ptr(), d_qw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K, n_probes,
+                                     d_hd.data_ptr(), d_hs.data_ptr(), d_hf.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+
+    def anchor_only():
+        batch.phrase_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), d_first.data_ptr(), d_ppos.data_ptr(), n_terms, n_post, n_idx,
+                                     0, S, d_dl.data_ptr(), d_aoff.data_ptr(), d_at.data_ptr(), d_qw.data_ptr(), Q, Q, 1.2, 0.75, avgdl, K, n_probes,
+                                     d_hd.data_ptr(), d_hs.data_ptr(), d_hf.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+
+    def or_search():
+        batch.search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, 0, S, d_dl.data_ptr(), d_qoff.data_ptr(), d_qt.data_ptr(),
+                              d_sw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K, n_cand, d_hd.data_ptr(), d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(),
+                              d_cnt.data_ptr(), stream)
+    out = {"spec": spec, "queries": Q, "slots_per_query": L, "k": K, "n_terms": n_terms, "documents": S, "postings": n_post, "positions": n_idx}
+    or_search()
+    batch.sync()
+    cnt = d_cnt.cpu().numpy()
+    out.update({"or_candidates": int(cnt[0]), "or_matches": int(cnt[1])})
+    anchor_only()
+    batch.sync()
+    out["anchor_only_matches"] = int(d_cnt.cpu().numpy()[1])
+    phrase()
+    batch.sync()
+    cnt = d_cnt.cpu().numpy()
+    matches = int(cnt[1])
+    out.update({"probes": int(cnt[0]), "matches": matches, "skipped": int(cnt[2]), "probes_equal_host_count": bool(int(cnt[0]) == n_probes),
+                "every_phrase_matches": bool(int(d_mc.min().item()) >= 1), "hit_counts_sum": int(d_hc.to(torch.int64).sum().item()),
+                "occurrences_in_hits": int(d_hf.to(torch.int64).sum().item())})
+    copy_bytes = (4 * n_probes + 12 * matches) // 2
+    a_buf, b_buf = torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev), torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev)
+    out["copy_bytes"] = copy_bytes
+
+    def floor():
+        b_buf.copy_(a_buf)
+    for name, fn in (("phrase", phrase), ("anchor_only", anchor_only), ("or_search", or_search), ("floor", floor)):
+        fn()
+        batch.sync()
+        r = []
+        for _ in range(args.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in ev:
+                a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            r.append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        out[name + "_ms"] = round(med(r), 4)
+        out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+    out["probes_per_s"] = round(n_probes / out["phrase_ms"] * 1e3, 1)
+    out["phrase_over_or_search"] = round(out["phrase_ms"] / out["or_search_ms"], 3)
+    out["phrase_over_floor"] = round(out["phrase_ms"] / out["floor_ms"], 2)
+    out["other_slots_share"] = round((out["phrase_ms"] - out["anchor_only_ms"]) / out["phrase_ms"], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="2,5")
@@ -243,6 +359,7 @@ def main():
     ap.add_argument("--postings", action="store_true", help="also time the postings pass over the id pass's ids (needs --ids)")
     ap.add_argument("--merge", default="", help="with --postings: K[,K..] equal document ranges as segments, then the ordered and the general merge")
     ap.add_argument("--search", action="append", default=[], help="with --postings: Q,L,K -- Q queries of L terms by count, top K (may be repeated)")
+    ap.add_argument("--phrase", action="append", default=[], help="with --postings: Q,L,K -- Q phrases of L consecutive tokens of random documents, top K (may be repeated)")
     ap.add_argument("--search-max-candidates", type=int, default=1 << 26)
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
@@ -384,6 +501,33 @@ def main():
             if args.search:   # BM25 top-k over the segment the one-pass call left, beside the general merge and a copy
                 row["search"] = [search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_term, d_pdocs, d_ptfs, int(cnt[0]))
                                  for spec in args.search]
+            if args.phrase:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
+                n_post = int(cnt[0])
+                d_first, d_order = torch.empty(cap_ends + 2, dtype=torch.int64, device=dev), torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
+                d_ppos = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
+                batch.postings(d_soff.data_ptr(), S, d_ids.data_ptr(), cap_ends, n_terms, 0, d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), cap_ends,
+                               d_first.data_ptr(), d_order.data_ptr(), d_cnt.data_ptr(), stream)
+
+                def positions():
+                    batch.postings_positions(d_soff.data_ptr(), S, cap_ends, 0, d_term.data_ptr(), n_terms, d_first.data_ptr(), cap_ends, d_order.data_ptr(),
+                                             d_ppos.data_ptr(), stream)
+                positions()
+                batch.sync()
+                r = []
+                for _ in range(args.rounds):
+                    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                    for a, b in ev:
+                        a.record(); positions(); b.record()
+                    torch.cuda.synchronize()
+                    r.append(med([a.elapsed_time(b) for a, b in ev]))
+                batch.sync()
+                n_idx = int(d_first[n_post].item())
+                row["positions"] = {"indexed_tokens": n_idx, "positions_ms": round(med(r), 4), "positions_rounds_ms": [round(x, 4) for x in r],
+                                    "positions_over_postings": round(med(r) / row["postings"]["postings_ms"], 3),
+                                    "indexed_plus_dropped_equal_tokens": bool(n_idx + int(cnt[1]) == n_tokens)}
+                row["phrase"] = [phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs,
+                                             d_ptfs, n_post, (d_first, d_ppos, n_idx)) for spec in args.phrase]
+                del d_first, d_order, d_ppos
             del d_ids, d_term, d_pdocs, d_ptfs, d_cnt
         if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run
             counter = api.VocabularyCounter(pred, args.count_keys)

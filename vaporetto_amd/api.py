@@ -801,10 +801,12 @@ class Predictor:
         if st != _lib.VPT_OK:
             _raise(st)
 
-    def postings_packed(self, token_offsets: np.ndarray, token_ids: np.ndarray, n_terms: int, doc_base: int = 0, positions: bool = False) -> "Postings":
+    def postings_packed(self, token_offsets: np.ndarray, token_ids: np.ndarray, n_terms: int, doc_base: int = 0, positions: bool = False,
+                        token_positions: Optional[np.ndarray] = None) -> "Postings":
         """vpt_postings_batch_device over host arrays: token_offsets uint64 [n + 1] and token_ids int32 (what token_ids_packed / encode_batch
         return) go to the device, the pass runs once, the segment's Postings come back.  positions: with `first` and `order` (the tokens of
-        every posting)."""
+        every posting) and `positions` (vpt_postings_positions_device: every posting's position list; token_positions uint32 per token, what
+        the stream calls return, default the token's index inside its document)."""
         import torch
         toff = np.ascontiguousarray(token_offsets, dtype=np.uint64)
         ids = np.ascontiguousarray(token_ids, dtype=np.int32)
@@ -823,19 +825,35 @@ class Predictor:
         batch.postings(d_toff.data_ptr(), n_docs, d_ids.data_ptr(), n_tok, n_terms, doc_base, d_term.data_ptr(), d_docs.data_ptr(), d_tfs.data_ptr(), n_tok,
                        d_first.data_ptr() if positions else 0, d_order.data_ptr() if positions else 0, d_cnt.data_ptr(),
                        torch.cuda.current_stream(dev).cuda_stream)
+        d_ppos = None
+        if positions:
+            d_ppos = d(n_tok, torch.int32)
+            d_tpos = None
+            if token_positions is not None:
+                tpos = np.ascontiguousarray(token_positions, dtype=np.uint32)
+                if len(tpos) != n_tok:
+                    raise VaporettoError("InvalidArgument", "InvalidArgumentError: token_positions: one per token")
+                d_tpos = torch.from_numpy((tpos if n_tok else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
+            batch.postings_positions(d_toff.data_ptr(), n_docs, n_tok, d_tpos.data_ptr() if d_tpos is not None else 0, d_term.data_ptr(), n_terms,
+                                     d_first.data_ptr(), n_tok, d_order.data_ptr(), d_ppos.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         batch.sync()
         cnt = d_cnt.cpu().numpy().view(np.uint64)
         n_post = int(cnt[0])
         first = d_first.cpu().numpy().view(np.uint64)[:n_post + 1].copy() if positions else None
-        return Postings(d_term.cpu().numpy().view(np.uint64)[:n_terms + 1].copy(), d_docs.cpu().numpy().view(np.uint32)[:n_post].copy(),
-                        d_tfs.cpu().numpy().view(np.uint32)[:n_post].copy(), first,
-                        d_order.cpu().numpy().view(np.uint32)[:int(first[n_post])].copy() if positions else None, int(cnt[1]))
+        out = Postings(d_term.cpu().numpy().view(np.uint64)[:n_terms + 1].copy(), d_docs.cpu().numpy().view(np.uint32)[:n_post].copy(),
+                       d_tfs.cpu().numpy().view(np.uint32)[:n_post].copy(), first,
+                       d_order.cpu().numpy().view(np.uint32)[:int(first[n_post])].copy() if positions else None, int(cnt[1]))
+        if positions:
+            out.positions = d_ppos.cpu().numpy().view(np.uint32)[:int(first[n_post])].copy()
+        return out
 
     def token_postings_packed(self, utf8: np.ndarray, byte_offsets: np.ndarray, vocab: "Vocabulary", wsconst: str = "", normalize: bool = True,
                               tagger: Optional["PatternMatchTagger"] = None, stop: Optional["TagStopFilter"] = None, doc_base: int = 0,
-                              capacity: Optional[int] = None) -> "Postings":
+                              capacity: Optional[int] = None, positions: bool = False) -> "Postings":
         """vpt_token_stream_postings_batch: documents in, the segment's Postings out (no `first` / `order`); n_terms is the vocabulary's key
-        count.  capacity: what the posting arrays hold (default: the text's bytes, which always suffices)."""
+        count.  capacity: what the posting arrays hold (default: the text's bytes, which always suffices).  positions:
+        vpt_token_stream_positional_postings_batch -- with `first` and `positions`, every posting's position list from the stream's
+        token positions (no `order`: the token indices stay in the call)."""
         flags = wsconst_flags(wsconst, allow_graphemes=True)
         utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
         byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.uint64)
@@ -846,10 +864,19 @@ class Predictor:
         docs, tfs = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
         n_post, n_drop = C.c_uint64(), C.c_uint64()
         src = utf8 if len(utf8) else np.zeros(1, np.uint8)
-        st = _lib.load().vpt_token_stream_postings_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags,
-                                                         tagger.handle(self) if tagger is not None else None, stop.handle if stop is not None else None,
-                                                         vocab.handle if vocab is not None else None, _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0,
-                                                         int(doc_base), term.ctypes.data, docs.ctypes.data, tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_drop))
+        if positions:
+            cap_pos = max(int(byte_offsets[-1] - byte_offsets[0]), 1) if S else 1
+            first, ppos, n_pos = np.zeros(max(cap, 1) + 1, np.uint64), np.zeros(cap_pos, np.uint32), C.c_uint64()
+            st = _lib.load().vpt_token_stream_positional_postings_batch(
+                self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags, tagger.handle(self) if tagger is not None else None,
+                stop.handle if stop is not None else None, vocab.handle if vocab is not None else None,
+                _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0, int(doc_base), term.ctypes.data, docs.ctypes.data, tfs.ctypes.data,
+                first.ctypes.data, cap, ppos.ctypes.data, cap_pos, C.byref(n_post), C.byref(n_drop), C.byref(n_pos))
+        else:
+            st = _lib.load().vpt_token_stream_postings_batch(self._h, src.ctypes.data, byte_offsets.ctypes.data, S, flags,
+                                                             tagger.handle(self) if tagger is not None else None, stop.handle if stop is not None else None,
+                                                             vocab.handle if vocab is not None else None, _lib.VPT_FLAG_KYTEA_FULLWIDTH if normalize else 0,
+                                                             int(doc_base), term.ctypes.data, docs.ctypes.data, tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_drop))
         if st != _lib.VPT_OK:
             try:
                 _raise(st)
@@ -857,7 +884,9 @@ class Predictor:
                 e.n_postings = int(n_post.value)   # (too small a capacity: the number needed)
                 raise
         n = int(n_post.value)
-        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, int(n_drop.value))
+        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), first[:n + 1].copy() if positions else None, None, int(n_drop.value))
+        if positions:
+            out.positions = ppos[:int(n_pos.value)].copy()
         out._predictor = self
         return out
 
@@ -1556,6 +1585,52 @@ class DeviceBatch:
             _raise(st)
         return int(v.value)
 
+    def postings_positions(self, d_token_offsets: int, n_documents: int, capacity_in: int, d_token_positions: int, d_term_offsets: int, n_terms: int,
+                           d_post_first: int, capacity_postings: int, d_token_order: int, d_post_positions: int, stream: int = 0) -> None:
+        """Device-resident position lists of a segment (vpt_postings_positions_device), behind postings() with the optional pair;
+        d_token_positions 0 (NULL): a token's index inside its document.  Enqueues and returns; errors (a hostile CSR, positions that do not
+        strictly ascend inside a posting) at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("capacity_in", capacity_in, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_positions_device(self._p.handle, self._h, d_token_offsets or None, n_documents, int(capacity_in),
+                                                       d_token_positions or None, d_term_offsets or None, int(n_terms), d_post_first or None,
+                                                       int(capacity_postings), d_token_order or None, d_post_positions or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def phrase_search_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, d_post_first: int, d_post_positions: int, n_terms: int,
+                               capacity_postings: int, capacity_positions: int, doc_base: int, n_documents: int, d_doc_lens: int,
+                               d_query_offsets: int, d_query_terms: int, d_query_weights: int, n_queries: int, capacity_slots: int, k1: float,
+                               b: float, avgdl: float, k: int, capacity_probes: int, d_hit_docs: int, d_hit_scores: int, d_hit_freqs: int,
+                               d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0) -> None:
+        """Device-resident exact-phrase BM25 top-k search over one positional segment (vpt_postings_phrase_search_device), raw device
+        pointers; a query is one phrase with one weight; d_hit_freqs may be 0 (NULL).  Enqueues and returns; errors at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_queries", n_queries, 1 << 32), ("k", k, 1 << 32), ("doc_base", doc_base, 1 << 64),
+                             ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
+                             ("capacity_positions", capacity_positions, 1 << 64), ("capacity_slots", capacity_slots, 1 << 64),
+                             ("capacity_probes", capacity_probes, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_phrase_search_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
+                                                           d_post_first or None, d_post_positions or None, int(n_terms), int(capacity_postings),
+                                                           int(capacity_positions), int(doc_base), int(n_documents), d_doc_lens or None,
+                                                           d_query_offsets or None, d_query_terms or None, d_query_weights or None, int(n_queries),
+                                                           int(capacity_slots), float(k1), float(b), float(avgdl), int(k), int(capacity_probes),
+                                                           d_hit_docs or None, d_hit_scores or None, d_hit_freqs or None, d_hit_counts or None,
+                                                           d_match_counts or None, d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    @staticmethod
+    def postings_phrase_limit() -> int:
+        """the most slots a phrase may have (vpt_postings_phrase_limits)"""
+        v = C.c_uint32()
+        st = _lib.load().vpt_postings_phrase_limits(C.byref(v))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value)
+
     @staticmethod
     def postings_tile() -> int:
         v = C.c_uint32()
@@ -1972,12 +2047,14 @@ def bm25_idf(n_documents: int, df: int) -> np.float32:
 class Postings:
     """The postings of one batch (a segment), term-major (vpt_postings_batch_device): term k's postings are [term_offsets[k], term_offsets[k + 1])
     of `docs` (doc_base + the document's index, ascending within a term) and `tfs`.  With positions: posting q's tokens are
-    order[first[q] : first[q + 1]], ascending token indices of the batch; else `first` and `order` are None.  n_dropped: the tokens whose id
-    was no term (negative or >= n_terms)."""
+    order[first[q] : first[q + 1]], ascending token indices of the batch; else `first` and `order` are None.  `positions`: an array, or None --
+    posting q's position list is positions[first[q] : first[q + 1]], strictly ascending (vpt_postings_positions_device); with it the postings
+    are a positional segment and phrase_search runs.  n_dropped: the tokens whose id was no term (negative or >= n_terms)."""
 
     def __init__(self, term_offsets: np.ndarray, docs: np.ndarray, tfs: np.ndarray, first: Optional[np.ndarray], order: Optional[np.ndarray],
                  n_dropped: int):
         self.term_offsets, self.docs, self.tfs, self.first, self.order, self.n_dropped = term_offsets, docs, tfs, first, order, int(n_dropped)
+        self.positions = None    # uint32 [indexed tokens]: every posting's position list (postings_packed / index_batch with positions=True)
         self.n_combined = 0      # merge: the input postings that were combined into another
         self._predictor = None   # who made it (merge's default device)
         self.doc_lens = None     # search: uint32, the token count of document doc_base + i (index_batch / index_batches attach both)
@@ -2089,6 +2166,71 @@ class Postings:
         self.last_search_counts = cnt   # candidates, matches, skipped slots
         k = int(k)
         return [[(int(hd[q * k + j]), hs[q * k + j]) for j in range(int(hc[q]))] for q in range(n_q)], mc
+
+    def phrase_search(self, phrases: Sequence[Sequence[int]], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
+                      b: float = 0.75, weights=None, predictor: Optional["Predictor"] = None):
+        """Exact-phrase BM25 top-k of every phrase over this positional segment (vpt_postings_phrase_search; the definition is in
+        include/vaporetto_hip.h).  phrases: a sequence of term-id sequences, each ONE phrase: its ids at consecutive positions, in order; an id
+        outside the vocabulary makes the phrase match nothing.  weights: one float per phrase (default: tantivy's phrase weight, the float32
+        sum in slot order of bm25_idf(n_documents, df[term]) over the slots).  doc_lens / doc_base / avgdl as in search.  Returns (hits,
+        match_counts): hits[q] the list of (document, score float32, freq) triples, at most k, by score descending, then document
+        ascending; freq the phrase's occurrences in the document."""
+        if self.first is None or self.positions is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: the postings were made without positions")
+        pred = predictor or self._predictor
+        if pred is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: no predictor (pass predictor=)")
+        doc_lens = self.doc_lens if doc_lens is None else doc_lens
+        doc_base = self.doc_base if doc_base is None else doc_base
+        if doc_lens is None or doc_base is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: the postings carry no doc_lens / doc_base (pass them)")
+        dl = np.ascontiguousarray(doc_lens, dtype=np.uint32)
+        n_docs, n_terms, n_q = len(dl), len(self.term_offsets) - 1, len(phrases)
+        if n_q == 0:
+            return [], np.zeros(0, np.uint64)
+        if n_docs == 0:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32")
+        avgdl = np.float32(float(int(dl.sum(dtype=np.uint64))) / float(n_docs))
+        qoff = np.zeros(n_q + 1, np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in phrases], dtype=np.uint64)
+        terms = np.array([t for q in phrases for t in q] + [0], np.int64).astype(np.int32)
+        if weights is None:
+            df, idf = self.df(), {}
+            w = np.zeros(n_q, np.float32)
+            for i, q in enumerate(phrases):
+                total = None
+                for t in q:
+                    t = int(t)
+                    if not 0 <= t < n_terms:
+                        continue
+                    if t not in idf:
+                        idf[t] = bm25_idf(n_docs, int(df[t]))
+                    total = idf[t] if total is None else np.float32(total + idf[t])
+                w[i] = np.float32(0) if total is None else total
+        else:
+            w = np.array(list(weights), np.float32)
+            if len(w) != n_q:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: weights: one per phrase")
+        if not (0 <= int(k) < 1 << 32 and 0 <= n_terms < 1 << 32 and 0 <= n_q < 1 << 32 and 0 <= int(doc_base) < 1 << 64):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32")
+        term = np.ascontiguousarray(self.term_offsets, dtype=np.uint64)
+        docs, tfs = np.ascontiguousarray(self.docs, dtype=np.uint32), np.ascontiguousarray(self.tfs, dtype=np.uint32)
+        first, ppos = np.ascontiguousarray(self.first, dtype=np.uint64), np.ascontiguousarray(self.positions, dtype=np.uint32)
+        if len(docs) != len(tfs) or len(first) != len(docs) + 1 or int(term[-1]) != len(docs) or int(first[-1]) != len(ppos):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: the postings' arrays do not belong together")
+        n_out = max(n_q * int(k), 1)
+        hd, hs, hf = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_out, np.uint32)
+        hc, mc, cnt = np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
+        st = _lib.load().vpt_postings_phrase_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None,
+                                                    tfs.ctypes.data if len(tfs) else None, first.ctypes.data, ppos.ctypes.data if len(ppos) else None,
+                                                    n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data,
+                                                    n_q, float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hf.ctypes.data,
+                                                    hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.last_search_counts = cnt   # probes, matches, skipped queries
+        k = int(k)
+        return [[(int(hd[q * k + j]), hs[q * k + j], int(hf[q * k + j])) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
     def tokens(self, q: int) -> np.ndarray:
         """the token indices of posting q, ascending (needs positions)"""
@@ -2210,14 +2352,16 @@ class VaporettoTokenizer:
         taken = set(specials)
         return Vocabulary(self._predictor, specials + [s for s in surfaces if s not in taken], unk_id)
 
-    def index_batch(self, texts: Sequence[str], doc_base: int = 0) -> "Postings":
+    def index_batch(self, texts: Sequence[str], doc_base: int = 0, positions: bool = False) -> "Postings":
         """The postings of a batch of documents (a segment) over this tokenizer's vocabulary: term = vocabulary id, document = doc_base + the
         text's index, tf = the term's tokens in it (vpt_token_stream_postings_batch; tagger and stop set included).  A token whose id is no
-        entry (unk_id outside the vocabulary) is counted in n_dropped.  Needs vocab=."""
+        entry (unk_id outside the vocabulary) is counted in n_dropped.  positions: a positional segment (`first`, `positions`: the stream's
+        token positions, with the gaps a stop set leaves), what phrase_search reads.  Needs vocab=."""
         if self._vocab is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: index_batch: the tokenizer has no vocab")
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])
-        out = self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base)
+        out = self._predictor.token_postings_packed(utf8, boff, self._vocab, self._wsconst, self._vocab_normalize, self._tagger, self._stop, doc_base,
+                                                    positions=positions)
         # what Postings.search needs of the documents: their token counts (the stream's tokens, those without a vocabulary entry included)
         out.doc_lens = np.diff(self._stream_ids(utf8, boff)[0]).astype(np.uint32) if len(texts) else np.zeros(0, np.uint32)
         out.doc_base = int(doc_base)
@@ -2245,6 +2389,15 @@ class VaporettoTokenizer:
         toff, ids = self.encode_batch(list(texts))
         queries = [ids[int(toff[i]):int(toff[i + 1])].tolist() for i in range(len(toff) - 1)]
         return postings.search(queries, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
+
+    def phrase_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
+                      b: float = 0.75, weights=None):
+        """Exact-phrase BM25 top-k of query TEXTS over `postings` (index_batch(positions=True)): each text is tokenised and encoded as documents
+        are and is ONE phrase, every token a slot -- a token without a vocabulary entry makes it match nothing -- then Postings.phrase_search.
+        Needs vocab=."""
+        toff, ids = self.encode_batch(list(texts))
+        phrases = [ids[int(toff[i]):int(toff[i + 1])].tolist() for i in range(len(toff) - 1)]
+        return postings.phrase_search(phrases, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

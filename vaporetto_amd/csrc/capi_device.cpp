@@ -1379,6 +1379,127 @@ vpt_status vpt_postings_search_device(const vpt_predictor* p, vpt_batch* b, cons
                                   d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
 }
 
+// ---- the position lists of a segment and the exact-phrase search over them (kernels_postings_phrase.hip).  Positions: one launch.  Search:
+// queries, the trainer's scan (probe bases), probe, the trainer's scan, heads, the trainer's scan, emit and ranges, the trainer's sort over the
+// score and the query word, take.
+vpt_status vpt_postings_phrase_limits(uint32_t* max_phrase_terms) {
+    if (!max_phrase_terms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *max_phrase_terms = vpt::kPhraseMaxTerms;
+    return VPT_OK;
+}
+
+namespace vptc {
+vpt_status postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
+                                     const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms, const uint64_t* d_post_first,
+                                     uint64_t capacity_postings, const uint32_t* d_token_order, uint32_t* d_post_positions, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!d_token_offsets || !d_term_offsets || !d_post_first || !d_token_order || !d_post_positions)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (capacity_in >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+    VPT_HIP(hipSetDevice(p->device));
+    vpt::PostingsPositionsParams P{};
+    P.token_offsets = d_token_offsets; P.n_docs = n_documents; P.capacity_in = capacity_in; P.positions = d_token_positions;
+    P.term_offsets = d_term_offsets; P.n_terms = n_terms; P.post_first = d_post_first; P.capacity_postings = capacity_postings;
+    P.token_order = d_token_order; P.post_positions = d_post_positions; P.status = b->d_ctrl;
+    VPT_HIP(vpt::launch_postings_positions(P, stream));   // (no document or no place: no token is indexed, nothing to write)
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+
+vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                         const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions, uint32_t n_terms,
+                                         uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                         const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
+                                         const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
+                                         uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
+                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_post_first || !d_post_positions || !d_doc_lens || !d_query_offsets || !d_query_terms ||
+        !d_query_weights || !d_hit_docs || !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
+    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    if (capacity_slots >= (1ull << 32) || capacity_probes >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    if (doc_base > (1ull << 32) || n_documents > (1ull << 32) - doc_base)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    if (!(k1 >= 0.0f && k1 <= 65536.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k1: must be between 0 and 65536");
+    if (!(bm_b >= 0.0f && bm_b <= 1.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: b: must be between 0 and 1");
+    if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
+    VPT_HIP(hipSetDevice(p->device));
+    VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
+    // the scratch in 256-byte sections: q_anchor | q_run | q_probes | base | qstart | flags | plen | pdoc | pq | hpf | order | skey | hit | scan |
+    // hist | hist_scan | partials
+    const uint64_t n = capacity_probes, nq = n_queries, nh = vpt::train_radix_scratch(n);
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_anchor = 0, o_run = o_anchor + pad(4 * size_t(nq)), o_probes = o_run + pad(8 * size_t(nq)), o_base = o_probes + pad(8 * size_t(nq)),
+                 o_qstart = o_base + pad(8 * (size_t(nq) + 1)), o_flags = o_qstart + pad(8 * (size_t(nq) + 1)), o_plen = o_flags + pad(4 * size_t(n)),
+                 o_pdoc = o_plen + pad(4 * size_t(n)), o_pq = o_pdoc + pad(4 * size_t(n)), o_hpf = o_pq + pad(4 * size_t(n)),
+                 o_order = o_hpf + pad(4 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_hit = o_skey + pad(4 * size_t(n)),
+                 o_scan = o_hit + pad(12 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
+                 o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
+                 total = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(nq)})) + 1));
+    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    unsigned char* m = b->d_post;
+    vpt::PostingsPhraseParams P{};
+    P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.post_first = d_post_first; P.post_positions = d_post_positions;
+    P.capacity_postings = capacity_postings; P.capacity_positions = capacity_positions; P.n_terms = n_terms;
+    P.doc_base = doc_base; P.n_docs = n_documents; P.doc_lens = d_doc_lens;
+    P.query_offsets = d_query_offsets; P.query_terms = d_query_terms; P.query_weights = d_query_weights; P.n_queries = n_queries;
+    P.capacity_slots = capacity_slots; P.n_places = n; P.k1 = k1; P.b = bm_b; P.avgdl = avgdl; P.k = k;
+    P.q_anchor = reinterpret_cast<uint32_t*>(m + o_anchor); P.q_run = reinterpret_cast<uint64_t*>(m + o_run);
+    P.q_probes = reinterpret_cast<uint64_t*>(m + o_probes); P.base = reinterpret_cast<uint64_t*>(m + o_base);
+    P.qstart = reinterpret_cast<uint64_t*>(m + o_qstart); P.flags = reinterpret_cast<uint32_t*>(m + o_flags);
+    P.plen = reinterpret_cast<uint32_t*>(m + o_plen); P.pdoc = reinterpret_cast<uint32_t*>(m + o_pdoc); P.pq = reinterpret_cast<uint32_t*>(m + o_pq);
+    P.hpf = reinterpret_cast<uint32_t*>(m + o_hpf); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
+    P.hit = reinterpret_cast<uint32_t*>(m + o_hit); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+    P.hit_docs = d_hit_docs; P.hit_scores = d_hit_scores; P.hit_freqs = d_hit_freqs; P.hit_counts = d_hit_counts; P.match_counts = d_match_counts;
+    P.counts = d_counts; P.status = b->d_ctrl;
+    uint64_t* hist = reinterpret_cast<uint64_t*>(m + o_hist);
+    uint64_t* hscan = reinterpret_cast<uint64_t*>(m + o_hscan);
+    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
+    uint32_t rank[8], n_rank = 0;   // the four bytes of ~bits(score), then the bytes of the values 0 .. n_queries, least significant first
+    for (uint32_t i = 0; i < 4; ++i) rank[n_rank++] = (2u << 8) | (8 * i);
+    for (uint32_t v = n_queries, i = 0; v; v >>= 8, ++i) rank[n_rank++] = (0u << 8) | (8 * i);
+    VPT_HIP(vpt::launch_postings_phrase_queries(P, stream));
+    VPT_HIP(vpt::train_scan(P.q_probes, nq, P.base, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_probe(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_heads(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_emit(P, stream));
+    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank, n_rank, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_take(P, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
+}  // namespace vptc
+
+vpt_status vpt_postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
+                                         const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms,
+                                         const uint64_t* d_post_first, uint64_t capacity_postings, const uint32_t* d_token_order,
+                                         uint32_t* d_post_positions, void* hip_stream) {
+    return postings_positions_device(p, b, d_token_offsets, n_documents, capacity_in, d_token_positions, d_term_offsets, n_terms, d_post_first,
+                                     capacity_postings, d_token_order, d_post_positions, static_cast<hipStream_t>(hip_stream));
+}
+
+vpt_status vpt_postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                             const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions,
+                                             uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                             uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                             const int32_t* d_query_terms, const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots,
+                                             float k1, float b_param, float avgdl, uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs,
+                                             float* d_hit_scores, uint32_t* d_hit_freqs, uint32_t* d_hit_counts, uint64_t* d_match_counts,
+                                             uint64_t* d_counts, void* hip_stream) {
+    return postings_phrase_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
+                                         capacity_positions, doc_base, n_documents, d_doc_lens, d_query_offsets, d_query_terms, d_query_weights,
+                                         n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_probes, d_hit_docs, d_hit_scores, d_hit_freqs,
+                                         d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
+}
+
 // A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them
 // (vocab_count.hpp).  Counting may go on afterwards.
 vpt_status vpt_vocab_counter_finish(void* counter, uint64_t min_count, uint64_t max_entries, const uint8_t** surfaces, const uint64_t** offsets,

@@ -943,12 +943,19 @@ vpt_status vpt_token_stream_count_batch(const vpt_predictor* p, const uint8_t* u
 // Documents in, the segment's postings out: the id stream's steps into buffers of this call (a token has a byte at least, so the text's bytes
 // bound the tokens), then the WHOLE batch's token_offsets and ids to the device and the postings pass once over them -- the ids make one trip to
 // the host and back, and the result cannot depend on how the stream was cut into chunks.
-vpt_status vpt_token_stream_postings_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
-                                           unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab, unsigned vocab_flags,
-                                           uint64_t doc_base, uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out,
-                                           uint64_t capacity, uint64_t* n_postings_out, uint64_t* n_dropped_out) {
+// (positional: also post_first [capacity + 1] and post_positions [capacity_positions], the latter from the stream's token_positions by
+// postings_positions_device behind the pass)
+namespace {
+vpt_status token_stream_postings(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                 unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab, unsigned vocab_flags,
+                                 uint64_t doc_base, uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out,
+                                 uint64_t capacity, uint64_t* n_postings_out, uint64_t* n_dropped_out, bool positional, uint64_t* post_first_out,
+                                 uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_positions_out) {
     if (n_postings_out) *n_postings_out = 0;
     if (n_dropped_out) *n_dropped_out = 0;
+    if (n_positions_out) *n_positions_out = 0;
+    if (positional && (!post_first_out || !n_positions_out || (capacity_positions && !post_positions_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     const vpt_vocab* v = static_cast<const vpt_vocab*>(vocab);
     if (!v) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: vocab: must not be NULL");
@@ -960,6 +967,7 @@ vpt_status vpt_token_stream_postings_batch(const vpt_predictor* p, const uint8_t
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
     const uint32_t n_terms = v->n_keys;
     std::fill(term_offsets_out, term_offsets_out + size_t(n_terms) + 1, uint64_t(0));
+    if (positional) post_first_out[0] = 0;
     if (n_documents == 0) return VPT_OK;
     if (!utf8 || !byte_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (byte_offsets[n_documents] < byte_offsets[0]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
@@ -986,32 +994,70 @@ vpt_status vpt_token_stream_postings_batch(const vpt_predictor* p, const uint8_t
     if ((st = acquire(p, &w)) != VPT_OK) return st;
     vpt_batch* b = w.b;
     hipStream_t s = b->own_stream;
-    // one allocation of this call, 256-byte sections: token_offsets | ids | term_offsets | docs | tfs | counts
+    // one allocation of this call, 256-byte sections: token_offsets | ids | term_offsets | docs | tfs | counts, and positional: first | order |
+    // the stream's positions | the segment's positions
     auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t o_toff = 0, o_ids = o_toff + pad(8 * (n_documents + 1)), o_term = o_ids + pad(4 * size_t(n_tok) + 4),
                  o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_tok) + 4), o_cnt = o_tfs + pad(4 * size_t(n_tok) + 4),
-                 total = o_cnt + 256;
+                 o_first = o_cnt + 256, o_order = o_first + (positional ? pad(8 * (size_t(n_tok) + 1)) : 0),
+                 o_pos = o_order + (positional ? pad(4 * size_t(n_tok) + 4) : 0), o_ppos = o_pos + (positional ? pad(4 * size_t(n_tok) + 4) : 0),
+                 total = o_ppos + (positional ? pad(4 * size_t(n_tok) + 4) : 0);
     DevBuf<unsigned char> mem;
     if ((st = mem.alloc(total)) != VPT_OK) return st;
     unsigned char* m = mem;
     VPT_HIP(hipMemcpyAsync(m + o_toff, toff.data(), 8 * (n_documents + 1), hipMemcpyHostToDevice, s));
     if (n_tok) VPT_HIP(hipMemcpyAsync(m + o_ids, ids.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
+    if (positional && n_tok) VPT_HIP(hipMemcpyAsync(m + o_pos, pos.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
     st = postings_device(p, b, reinterpret_cast<const uint64_t*>(m + o_toff), n_documents, reinterpret_cast<const int32_t*>(m + o_ids), n_tok, n_terms, doc_base,
                          reinterpret_cast<uint64_t*>(m + o_term), reinterpret_cast<uint32_t*>(m + o_docs), reinterpret_cast<uint32_t*>(m + o_tfs), n_tok,
-                         nullptr, nullptr, reinterpret_cast<uint64_t*>(m + o_cnt), s);
+                         positional ? reinterpret_cast<uint64_t*>(m + o_first) : nullptr, positional ? reinterpret_cast<uint32_t*>(m + o_order) : nullptr,
+                         reinterpret_cast<uint64_t*>(m + o_cnt), s);
     if (st != VPT_OK) return st;
+    if (positional) {
+        st = postings_positions_device(p, b, reinterpret_cast<const uint64_t*>(m + o_toff), n_documents, n_tok, reinterpret_cast<const uint32_t*>(m + o_pos),
+                                       reinterpret_cast<const uint64_t*>(m + o_term), n_terms, reinterpret_cast<const uint64_t*>(m + o_first), n_tok,
+                                       reinterpret_cast<const uint32_t*>(m + o_order), reinterpret_cast<uint32_t*>(m + o_ppos), s);
+        if (st != VPT_OK) return st;
+    }
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
     uint64_t counts[2] = {0, 0};
     VPT_HIP(hipMemcpy(counts, m + o_cnt, 16, hipMemcpyDeviceToHost));
     *n_postings_out = counts[0];
     *n_dropped_out = counts[1];
+    if (positional) *n_positions_out = n_tok - counts[1];   // the indexed tokens
     if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
+    if (positional && *n_positions_out > capacity_positions)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: smaller than the number of indexed tokens");
     VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms) + 1), hipMemcpyDeviceToHost));
     if (counts[0]) {
         VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
         VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
     }
+    if (positional) {
+        VPT_HIP(hipMemcpy(post_first_out, m + o_first, 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
+        if (*n_positions_out) VPT_HIP(hipMemcpy(post_positions_out, m + o_ppos, 4 * size_t(*n_positions_out), hipMemcpyDeviceToHost));
+    }
     return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_token_stream_postings_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                           unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab, unsigned vocab_flags,
+                                           uint64_t doc_base, uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out,
+                                           uint64_t capacity, uint64_t* n_postings_out, uint64_t* n_dropped_out) {
+    return token_stream_postings(p, utf8, byte_offsets, n_documents, wsconst_flags, tagger, stop, vocab, vocab_flags, doc_base, term_offsets_out,
+                                 post_docs_out, post_tfs_out, capacity, n_postings_out, n_dropped_out, false, nullptr, nullptr, 0, nullptr);
+}
+
+vpt_status vpt_token_stream_positional_postings_batch(const vpt_predictor* p, const uint8_t* utf8, const uint64_t* byte_offsets, size_t n_documents,
+                                                      unsigned wsconst_flags, const void* tagger, const void* stop, const void* vocab,
+                                                      unsigned vocab_flags, uint64_t doc_base, uint64_t* term_offsets_out, uint32_t* post_docs_out,
+                                                      uint32_t* post_tfs_out, uint64_t* post_first_out, uint64_t capacity,
+                                                      uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_postings_out,
+                                                      uint64_t* n_dropped_out, uint64_t* n_positions_out) {
+    return token_stream_postings(p, utf8, byte_offsets, n_documents, wsconst_flags, tagger, stop, vocab, vocab_flags, doc_base, term_offsets_out,
+                                 post_docs_out, post_tfs_out, capacity, n_postings_out, n_dropped_out, true, post_first_out, post_positions_out,
+                                 capacity_positions, n_positions_out);
 }
 
 // Host segments in, the merged segment out: every segment's term_offsets and its postings (term_offsets[n_terms] of them, at most its capacity)
@@ -1163,6 +1209,94 @@ vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offs
     VPT_HIP(hipMemcpy(match_counts_out, m + o_mc, 8 * size_t(n_queries), hipMemcpyDeviceToHost));
     VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
     VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
+// A host positional segment, host documents' lengths and host phrases in, the hits out: what the segment holds goes to one allocation of this
+// call, the probes are counted from the host's arrays as the device counts them, the device search runs once, the five outputs come back.
+vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const int32_t* query_terms,
+                                      const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                      uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_freqs_out, uint32_t* hit_counts_out,
+                                      uint64_t* match_counts_out, uint64_t* counts_out) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!term_offsets || !post_first || !query_offsets || !query_weights || !hit_docs_out || !hit_scores_out || !hit_freqs_out || !hit_counts_out ||
+        !match_counts_out || !counts_out)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
+    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    const uint64_t n_post = term_offsets[n_terms], n_slots = query_offsets[n_queries];
+    if (n_post >= (1ull << 32) || n_slots >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    const uint64_t n_pos = post_first[n_post];
+    if (n_pos >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    if ((n_post && (!post_docs || !post_tfs)) || (n_pos && !post_positions) || (n_documents && !doc_lens) || (n_slots && !query_terms))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    uint64_t n_probes = 0;   // (arrays that are no segment's or no CSR: the device reports them; a query is then counted as 0)
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const uint64_t a = query_offsets[q], e = query_offsets[q + 1];
+        if (a >= e || e > n_slots || e - a > vpt::kPhraseMaxTerms) continue;
+        uint64_t best = ~uint64_t(0);
+        for (uint64_t s = a; s < e && best; ++s) {
+            const int32_t t = query_terms[s];
+            if (t < 0 || uint32_t(t) >= n_terms) { best = 0; break; }
+            const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
+            if (ta >= tb || tb > n_post || post_first[ta] > post_first[tb] || post_first[tb] > n_pos) { best = 0; break; }
+            best = std::min(best, post_first[tb] - post_first[ta]);
+        }
+        n_probes += best;
+        if (n_probes >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    }
+    if (n_documents > (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t n_out = size_t(n_queries) * k;
+    const size_t o_term = 0, o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_post) + 4), o_first = o_tfs + pad(4 * size_t(n_post) + 4),
+                 o_pos = o_first + pad(8 * (size_t(n_post) + 1)), o_dl = o_pos + pad(4 * size_t(n_pos) + 4), o_qoff = o_dl + pad(4 * size_t(n_documents) + 4),
+                 o_qt = o_qoff + pad(8 * (size_t(n_queries) + 1)), o_qw = o_qt + pad(4 * size_t(n_slots) + 4), o_hd = o_qw + pad(4 * size_t(n_queries)),
+                 o_hs = o_hd + pad(4 * n_out), o_hf = o_hs + pad(4 * n_out), o_hc = o_hf + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
+                 o_cnt = o_mc + pad(8 * size_t(n_queries));
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st;
+    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    DevBuf<unsigned char> mem;
+    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    unsigned char* m = mem;
+    VPT_HIP(hipMemcpyAsync(m + o_term, term_offsets, 8 * (size_t(n_terms) + 1), hipMemcpyHostToDevice, s));
+    if (n_post) {
+        VPT_HIP(hipMemcpyAsync(m + o_docs, post_docs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(m + o_tfs, post_tfs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
+    }
+    VPT_HIP(hipMemcpyAsync(m + o_first, post_first, 8 * (size_t(n_post) + 1), hipMemcpyHostToDevice, s));
+    if (n_pos) VPT_HIP(hipMemcpyAsync(m + o_pos, post_positions, 4 * size_t(n_pos), hipMemcpyHostToDevice, s));
+    if (n_documents) VPT_HIP(hipMemcpyAsync(m + o_dl, doc_lens, 4 * size_t(n_documents), hipMemcpyHostToDevice, s));
+    VPT_HIP(hipMemcpyAsync(m + o_qoff, query_offsets, 8 * (size_t(n_queries) + 1), hipMemcpyHostToDevice, s));
+    if (n_slots) VPT_HIP(hipMemcpyAsync(m + o_qt, query_terms, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
+    VPT_HIP(hipMemcpyAsync(m + o_qw, query_weights, 4 * size_t(n_queries), hipMemcpyHostToDevice, s));
+    VPT_HIP(hipMemsetAsync(m + o_hd, 0, o_hc - o_hd, s));   // an entry at or behind a query's hit count is not written on the device: zeros come back
+    st = postings_phrase_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
+                                       reinterpret_cast<const uint32_t*>(m + o_tfs), reinterpret_cast<const uint64_t*>(m + o_first),
+                                       reinterpret_cast<const uint32_t*>(m + o_pos), n_terms, n_post, n_pos, doc_base, n_documents,
+                                       reinterpret_cast<const uint32_t*>(m + o_dl), reinterpret_cast<const uint64_t*>(m + o_qoff),
+                                       reinterpret_cast<const int32_t*>(m + o_qt), reinterpret_cast<const float*>(m + o_qw), n_queries, n_slots, k1, b_param,
+                                       avgdl, k, n_probes, reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs),
+                                       reinterpret_cast<uint32_t*>(m + o_hf), reinterpret_cast<uint32_t*>(m + o_hc), reinterpret_cast<uint64_t*>(m + o_mc),
+                                       reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(counts_out, m + o_cnt, 24, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_counts_out, m + o_hc, 4 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(match_counts_out, m + o_mc, 8 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_freqs_out, m + o_hf, 4 * n_out, hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 

@@ -307,6 +307,7 @@ struct vpt_vocab_counter {
 constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: full (max_keys / arena_chars)";
 constexpr const char* kPostingsTooSmall = "InvalidArgumentError: capacity: smaller than the number of postings";
 constexpr const char* kCandidatesTooSmall = "InvalidArgumentError: capacity_candidates: smaller than the number of candidates";
+constexpr const char* kProbesTooSmall = "InvalidArgumentError: capacity_probes: smaller than the number of probes";
 
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
@@ -386,7 +387,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
-    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_search_device: PostingsSearchParams
+    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_search_device: PostingsSearchParams; vpt_postings_phrase_search_device: PostingsPhraseParams (36 bytes a query, 48 bytes a probe place, the histograms)
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -534,6 +535,10 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrBadWeights) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: weights: negative or not finite");
     if (bits & vpt::kErrQueryTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: more than 1024 slots");
     if (bits & vpt::kErrCandidatesTooSmall) return fail(VPT_INVALID_ARGUMENT, kCandidatesTooSmall);
+    if (bits & vpt::kErrPhraseTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: a phrase of more than 64 terms");
+    if (bits & vpt::kErrProbesTooSmall) return fail(VPT_INVALID_ARGUMENT, kProbesTooSmall);
+    if (bits & vpt::kErrBadPositions)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: positions: do not strictly ascend inside a document's list");
     if (bits & vpt::kErrSegmentsOverlap)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segments: document ranges overlap or descend");
     if (bits & vpt::kErrTfOverflow) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tf: sum exceeds 32 bits");
@@ -739,6 +744,18 @@ vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const ui
                                   uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
                                   uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
                                   hipStream_t stream);
+// The position lists of a segment and the exact-phrase search over them (vpt_postings_positions_device, vpt_postings_phrase_search_device;
+// kernels_postings_phrase.hip)
+vpt_status postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
+                                     const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms, const uint64_t* d_post_first,
+                                     uint64_t capacity_postings, const uint32_t* d_token_order, uint32_t* d_post_positions, hipStream_t stream);
+vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                         const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions, uint32_t n_terms,
+                                         uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                         const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
+                                         const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
+                                         uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
+                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

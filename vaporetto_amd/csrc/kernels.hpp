@@ -76,6 +76,9 @@ constexpr uint32_t kErrBadQueryCsr = 32768u;          // the postings search: qu
 constexpr uint32_t kErrBadWeights = 65536u;           // the postings search: a weight that is negative or not finite
 constexpr uint32_t kErrQueryTooLong = 131072u;        // the postings search: a query of more than kSearchMaxQuerySlots slots
 constexpr uint32_t kErrCandidatesTooSmall = 262144u;  // the postings search: more candidates than capacity_candidates
+constexpr uint32_t kErrBadPositions = 524288u;        // the positions of a segment: a posting's positions do not strictly ascend (kernels_postings_phrase.hip)
+constexpr uint32_t kErrPhraseTooLong = 1048576u;      // the phrase search: a phrase of more than kPhraseMaxTerms slots
+constexpr uint32_t kErrProbesTooSmall = 2097152u;     // the phrase search: more probes than capacity_probes
 
 
 struct ScoreParams {
@@ -462,6 +465,80 @@ hipError_t launch_postings_search_expand(const PostingsSearchParams& P, hipStrea
 hipError_t launch_postings_search_heads(const PostingsSearchParams& P, hipStream_t stream);
 hipError_t launch_postings_search_sum(const PostingsSearchParams& P, hipStream_t stream);    // sum, then the queries' ranges
 hipError_t launch_postings_search_take(const PostingsSearchParams& P, hipStream_t stream);
+// The position lists of a segment (kernels_postings_phrase.hip): one launch, a lane per place of capacity_in, behind the postings pass that wrote
+// post_first / token_order.  post_positions[i] = the position of token token_order[i] for every i below the indexed tokens.
+struct PostingsPositionsParams {
+    const uint64_t* token_offsets;  // [n_docs + 1]
+    uint64_t n_docs;                // >= 1
+    uint64_t capacity_in;
+    const uint32_t* positions;      // [capacity_in] or nullptr: the token's index inside its document
+    const uint64_t* term_offsets;   // [n_terms + 1]
+    uint32_t n_terms;
+    const uint64_t* post_first;     // [capacity_postings + 1]
+    uint64_t capacity_postings;
+    const uint32_t* token_order;    // [capacity_in]
+    uint32_t* post_positions;       // [capacity_in]
+    uint32_t* status;
+};
+hipError_t launch_postings_positions(const PostingsPositionsParams& P, hipStream_t stream);
+// Exact-phrase BM25 top-k search over a POSITIONAL segment (kernels_postings_phrase.hip).  A query is one phrase; its ANCHOR is the slot whose
+// term has the fewest indexed tokens (the first such slot), and its PROBES are the anchor term's positions, one contiguous run of
+// post_positions.  The probe counts are scanned into probe bases, and every launch is over the n_queries + 1 query bounds, the capacity_probes
+// PLACES or the n_queries * k outputs.  Scratch of the batch: per query q_anchor (u32), q_run, q_probes, base [n_queries + 1] and qstart
+// [n_queries + 1] (u64): 36 bytes; per slot nothing; per place flags, plen, pdoc, pq, hpf, order, skey (u32), hit [3] {query or the sentinel
+// n_queries, document - doc_base, ~bits of the score} and scan (u64, [places + 1]): 48 bytes.  The caller runs train_scan (q_probes -> base)
+// between queries and probe, train_scan (flags -> scan) between probe and heads and again between heads and emit, and train_radix_sort (hit,
+// stride 3: the score word, then the query word) between emit and take.  A launch behind probe that finds one of kPhraseErrors in the status
+// leaves the five outputs alone.
+constexpr uint32_t kPhraseMaxTerms = 64;
+constexpr uint32_t kPhraseErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrPhraseTooLong | kErrProbesTooSmall;
+struct PostingsPhraseParams {
+    const uint64_t* term_offsets;   // [n_terms + 1]
+    const uint32_t* post_docs;      // [capacity_postings]
+    const uint32_t* post_tfs;       // [capacity_postings]
+    const uint64_t* post_first;     // [capacity_postings + 1]
+    const uint32_t* post_positions; // [capacity_positions]
+    uint64_t capacity_postings;
+    uint64_t capacity_positions;
+    uint32_t n_terms;
+    uint64_t doc_base;
+    uint64_t n_docs;
+    const uint32_t* doc_lens;       // [n_docs]
+    const uint64_t* query_offsets;  // [n_queries + 1]
+    const int32_t* query_terms;     // [capacity_slots]
+    const float* query_weights;     // [n_queries]
+    uint32_t n_queries;
+    uint64_t capacity_slots;        // < 2^32
+    uint64_t n_places;              // capacity_probes, < 2^32
+    float k1, b, avgdl;
+    uint32_t k;
+    uint32_t* q_anchor;             // [n_queries]: the anchor's slot inside the query
+    uint64_t* q_run;                // [n_queries]: the anchor run's first place in post_positions
+    uint64_t* q_probes;             // [n_queries]: the run's length, 0 when the query cannot match
+    uint64_t* base;                 // [n_queries + 1]
+    uint64_t* qstart;               // [n_queries + 1]
+    uint32_t* flags;                // probe: 1 at an occurrence; heads: 1 at a head
+    uint64_t* scan;                 // of the occurrences, then of the heads
+    uint32_t* plen;                 // probe: the posting's tf at its first place, else 0; heads: pf at a head
+    uint32_t* pdoc;                 // document - doc_base
+    uint32_t* pq;                   // the place's query, or n_queries
+    uint32_t* hit;
+    uint32_t* hpf;
+    uint32_t* order;
+    uint32_t* skey;
+    uint32_t* hit_docs;             // [n_queries * k]
+    float* hit_scores;              // [n_queries * k]
+    uint32_t* hit_freqs;            // [n_queries * k] or nullptr
+    uint32_t* hit_counts;           // [n_queries]
+    uint64_t* match_counts;         // [n_queries]
+    uint64_t* counts;               // [3]: probes, matches (written), skipped queries (added to: zero before the launches)
+    uint32_t* status;
+};
+hipError_t launch_postings_phrase_queries(const PostingsPhraseParams& P, hipStream_t stream);
+hipError_t launch_postings_phrase_probe(const PostingsPhraseParams& P, hipStream_t stream);
+hipError_t launch_postings_phrase_heads(const PostingsPhraseParams& P, hipStream_t stream);
+hipError_t launch_postings_phrase_emit(const PostingsPhraseParams& P, hipStream_t stream);    // emit, then the queries' ranges
+hipError_t launch_postings_phrase_take(const PostingsPhraseParams& P, hipStream_t stream);
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;
