@@ -457,6 +457,19 @@ struct PostingsSegment {
     capacity: u64,
 }
 
+/// `vpt_postings_positional_segment` of include/vaporetto_hip.h, field by field (host pointers for `vpt_postings_merge_positional`).
+#[repr(C)]
+struct PostingsPositionalSegment {
+    term_offsets: *const u64,
+    docs: *const u32,
+    tfs: *const u32,
+    first: *const u64,
+    positions: *const u32,
+    n_terms: u32,
+    capacity: u64,
+    capacity_positions: u64,
+}
+
 impl Postings {
     /// The merge of segments that share a term id space (`vpt_postings_merge`): per term the union of their lists by document, a document
     /// that stands in several of them one posting whose tf is the sum; `n_dropped` the segments' sum.  `ordered`: the promise that every
@@ -484,6 +497,41 @@ impl Postings {
         docs.truncate(n_postings as usize);
         tfs.truncate(n_postings as usize);
         Ok(Postings { term_offsets, docs, tfs, n_dropped: segments.iter().map(|s| s.n_dropped).sum(), n_combined })
+    }
+
+    /// The merge of POSITIONAL segments (`vpt_postings_merge_positional`): `merge`, with the position lists carried along.  A segment is its
+    /// postings, its `first` (`docs.len() + 1` entries) and its `positions` (`first[docs.len()]` of them), as
+    /// `vpt_token_stream_positional_postings_batch` returns them.  Returns the merged postings with their `first` and `positions`: a merged
+    /// posting's list is the ascending union of its inputs' lists (an equal position in two of them is an error), what `phrase_search` takes.
+    pub fn merge_positional(predictor: &Predictor, segments: &[(&Postings, &[u64], &[u32])], ordered: bool, n_terms: u32)
+                            -> Result<(Postings, Vec<u64>, Vec<u32>)> {
+        let mut segs = Vec::with_capacity(segments.len());
+        let (mut cap, mut cap_pos) = (0usize, 0usize);
+        for (s, first, positions) in segments {
+            let n = s.term_offsets.len();
+            if n == 0 || n - 1 > n_terms as usize || s.docs.len() != s.tfs.len() || s.term_offsets[n - 1] > s.docs.len() as u64
+                || first.len() != s.docs.len() + 1 || first[s.docs.len()] > positions.len() as u64 {
+                return Err(HipError::InvalidArgument("InvalidArgumentError: merge: a segment's arrays do not belong together".into()));
+            }
+            segs.push(PostingsPositionalSegment { term_offsets: s.term_offsets.as_ptr(), docs: s.docs.as_ptr(), tfs: s.tfs.as_ptr(), first: first.as_ptr(),
+                                                  positions: positions.as_ptr(), n_terms: (n - 1) as u32, capacity: s.docs.len() as u64,
+                                                  capacity_positions: positions.len() as u64 });
+            cap += s.docs.len();
+            cap_pos += positions.len();
+        }
+        let mut term_offsets = vec![0u64; n_terms as usize + 1];
+        let (mut docs, mut tfs, mut first, mut positions) = (vec![0u32; cap + 1], vec![0u32; cap + 1], vec![0u64; cap + 1], vec![0u32; cap_pos + 1]);
+        let (mut n_postings, mut n_combined, mut n_positions) = (0u64, 0u64, 0u64);
+        check(unsafe {
+            ffi::vpt_postings_merge_positional(predictor.raw, segs.as_ptr() as *const std::ffi::c_void, segs.len(), n_terms, if ordered { 1 } else { 0 },
+                                               term_offsets.as_mut_ptr(), docs.as_mut_ptr(), tfs.as_mut_ptr(), first.as_mut_ptr(), cap as u64,
+                                               positions.as_mut_ptr(), cap_pos as u64, &mut n_postings, &mut n_combined, &mut n_positions)
+        })?;
+        docs.truncate(n_postings as usize);
+        tfs.truncate(n_postings as usize);
+        first.truncate(n_postings as usize + 1);
+        positions.truncate(n_positions as usize);
+        Ok((Postings { term_offsets, docs, tfs, n_dropped: segments.iter().map(|(s, _, _)| s.n_dropped).sum(), n_combined }, first, positions))
     }
 
     /// BM25 top-k of every query over this segment (`vpt_postings_search`; the definition is in include/vaporetto_hip.h).  `queries`: term ids, a

@@ -19,9 +19,11 @@
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --search "QUERY" [--top K] < documents.txt
 // With --search: the query text is tokenised as a document is, its tokens are weighted with BM25's idf and the K (default 10) best documents of
 // the index are found on the device; one line per hit, best first: document <TAB> the score's bits in hex <TAB> the score.
-//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] --phrase "QUERY" [--top K] < documents.txt
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --phrase "QUERY" [--top K] < documents.txt
 // With --phrase: the documents are indexed with positions, the query text is ONE phrase -- its tokens at consecutive positions, in order -- and
 // the K best documents that hold it are found on the device; the lines of --search, plus <TAB> the phrase's occurrences in the document.
+// With --segment-docs N the positional segments of N documents each are merged on the device with their position lists (the same lines come
+// out; stderr tells "segments <TAB> n <TAB> postings <TAB> n <TAB> positions <TAB> n").
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -85,13 +87,22 @@ int main(int argc, char** argv) {
             const char* phrase = nullptr;
             uint32_t top = 10;
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
+            if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }   // (behind the query, too)
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
             else if (n_args > 6 && std::strcmp(argv[n_args - 2], "--phrase") == 0) { phrase = argv[n_args - 1]; n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }
             const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
             vaporetto_hip::Postings post;
-            if (phrase) {   // (a merge does not carry position lists: one segment)
-                post = plain.index(docs, vocab, doc_base, true, true);
+            if (phrase) {
+                if (segment_docs) {
+                    std::vector<std::vector<std::string>> batches;
+                    for (size_t a = 0; a < docs.size(); a += segment_docs)
+                        batches.emplace_back(docs.begin() + a, docs.begin() + std::min(docs.size(), a + segment_docs));
+                    post = plain.index(batches, vocab, doc_base, true, true);
+                    std::fprintf(stderr, "segments\t%zu\tpostings\t%zu\tpositions\t%zu\n", batches.size(), post.docs.size(), post.positions.size());
+                } else {
+                    post = plain.index(docs, vocab, doc_base, true, true);
+                }
                 const auto found = plain.phrase_search(post, vocab, {std::string(phrase)}, plain.doc_lens(docs, vocab), doc_base, top);
                 for (const vaporetto_hip::Postings::PhraseHit& h : found.hits[0]) {
                     uint32_t bits;

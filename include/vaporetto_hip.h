@@ -860,6 +860,74 @@ vpt_status vpt_token_stream_positional_postings_batch(const vpt_predictor *p, co
                                                       uint64_t capacity, uint32_t *post_positions_out, uint64_t capacity_positions,
                                                       uint64_t *n_postings_out, uint64_t *n_dropped_out, uint64_t *n_positions_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Merging POSITIONAL segments on the device: phrase search over a corpus indexed in batches          (no item of the adapter: the merge above
+ *                                                                         with the position lists carried along, so the merged index serves phrases)
+ *
+ * vpt_postings_positional_segment: a positional segment as vpt_postings_batch_device with the optional pair and vpt_postings_positions_device
+ *   (or this call) left it.  Its postings are d_term_offsets[n_terms], its positions d_post_first[postings]; both are read on the device, so K
+ *   postings calls, K positions calls and the merge behind them need no sync in between; the two capacities bound them. */
+typedef struct vpt_postings_positional_segment {
+    const uint64_t *d_term_offsets;   /* [n_terms + 1]                                                         */
+    const uint32_t *d_post_docs;      /* [capacity], global document numbers                                   */
+    const uint32_t *d_post_tfs;       /* [capacity]                                                            */
+    const uint64_t *d_post_first;     /* [capacity + 1]                                                        */
+    const uint32_t *d_post_positions; /* [capacity_positions]                                                  */
+    uint32_t        n_terms;          /* <= n_terms_out; terms at or above it have no postings here            */
+    uint64_t        capacity;         /* the postings: d_term_offsets[n_terms]                                 */
+    uint64_t        capacity_positions; /* the positions: d_post_first[postings]                               */
+} vpt_postings_positional_segment;
+/* vpt_postings_merge_positional_device: `segments` is a HOST array of n_segments (1 .. 1024, vpt_postings_merge_limits)
+ *   vpt_postings_positional_segment structs whose pointers are device pointers; flags as vpt_postings_merge_device takes them.  ONE positional
+ *   segment comes out: d_term_offsets_out [n_terms_out + 1], d_post_docs_out / d_post_tfs_out [capacity_out] are exactly what
+ *   vpt_postings_merge_device writes for the same segments and flags; d_post_first_out [capacity_out + 1]: post_first_out[0] = 0,
+ *   post_first_out[q + 1] - post_first_out[q] = post_tfs_out[q], post_first_out[merged postings] = d_counts[2]; d_post_positions_out
+ *   [capacity_positions_out]: the position list of the merged posting (term k, document d) is the ascending union of the position lists of every
+ *   input posting (k, d).  d_counts [3] = the merged postings, the input postings combined into another, the merged positions.  Nothing is
+ *   written at or behind the merged postings + 1 entries of post_first_out or behind d_counts[2] positions.  The result is what
+ *   vpt_postings_phrase_search_device takes as it is.  So: however a batch's indexed tokens are dealt out to segments -- token_positions given to
+ *   the positions call so that every token keeps its position in its document --, the merge with flags 0 is, array for array, the one-pass
+ *   positional segment of the whole batch.  THE OUTPUTS MUST NOT ALIAS THE INPUTS.
+ *   Launches (kernels_postings_merge.hip), sized from the places of the posting arrays (the sum of the capacities), the POSITION PLACES (the
+ *   segments' capacity_positions laid end to end), the term bounds or the segments, none from a value read back.
+ *   VPT_POSTINGS_MERGE_ORDERED: the table applied to post_first.  The positions of segment s in front of term k are
+ *   post_first_s[term_offsets_s[k]], so a lane per term bound sums them over the segments -- the merged position offset of the term, no scan --
+ *   and leaves where every segment's positions of the term start in the output (a SECOND K x (n_terms_out + 1) table of 8-byte words); the copy
+ *   of a posting also writes its post_first; a lane per position place finds its segment, its posting (over post_first) and its term (over
+ *   term_offsets) by bisection and copies its position.
+ *   flags = 0: behind the merge's records, sort and heads, the tf of every sorted input posting is scanned (post_first of a merged posting is
+ *   the scan at its head) and the inverse of the sort order is scattered; a lane per position place finds its segment and posting by
+ *   bisection, the posting's run of at most n_segments input postings of one (term, document), and adds to its rank in its own posting the
+ *   positions below its own in every other member of the run, one bisection each.  No second sort.
+ *   Both: asynchronous on hip_stream, errors at vpt_batch_sync; no atomic decides a value, every loop is bounded by n_segments or 64 bisection
+ *   steps, two runs give identical bytes.  Scratch of the workspace: what vpt_postings_merge_device keeps, and 32 bytes more per segment;
+ *   ordered a second 8 * n_segments * (n_terms_out + 1) bytes; general 16 bytes more per input place (48 in all: a tf word, an inverse index
+ *   word, a second scan word).
+ *   At the call, VPT_INVALID_ARGUMENT: what vpt_postings_merge_device refuses, with d_post_first / d_post_positions of every segment and
+ *   d_post_first_out / d_post_positions_out among the pointers that must not be NULL; a sum of capacity_positions >= 2^32;
+ *   capacity_positions_out >= 2^32.
+ *   At the sync, VPT_INVALID_ARGUMENT: the merge's messages -- the segment message also when a segment's post_first[0] != 0, post_first
+ *   descends or ends above capacity_positions, or post_first[i + 1] - post_first[i] != post_tfs[i] --; "InvalidArgumentError: positions: do not
+ *   strictly ascend inside a document's list" when positions do not strictly ascend inside an input posting or two input postings of one
+ *   (term, document) hold an equal position (the outputs are then unspecified); "InvalidArgumentError: capacity_positions: smaller than the
+ *   number of indexed tokens" when there are more than capacity_positions_out merged positions -- d_counts[2] then holds the number needed and
+ *   what fits is written; the capacity message of the merge as there.  capacity_positions_out >= the sum of the capacity_positions always
+ *   suffices.  Whatever the arrays hold, every index is clamped or bounded before use: nothing is read outside the segments' stated sizes and
+ *   nothing is written outside the five outputs' stated sizes, d_counts [3] and the workspace.
+ * vpt_postings_merge_positional: the same over HOST arrays: each segment's term_offsets[n_terms] postings and post_first[postings] positions
+ *   are uploaded; five arrays come back with *n_postings_out, *n_combined_out and *n_positions_out.  Too small a `capacity` or
+ *   `capacity_positions`: VPT_INVALID_ARGUMENT with the message above, the three numbers as needed, nothing else written.
+ * (`segments` is declared const void *; pass a const vpt_postings_positional_segment *.) */
+vpt_status vpt_postings_merge_positional_device(const vpt_predictor *p, vpt_batch *b, const void *segments, size_t n_segments,
+                                                uint32_t n_terms_out, unsigned flags, uint64_t *d_term_offsets_out, uint32_t *d_post_docs_out,
+                                                uint32_t *d_post_tfs_out, uint64_t *d_post_first_out, uint64_t capacity_out,
+                                                uint32_t *d_post_positions_out, uint64_t capacity_positions_out, uint64_t *d_counts,
+                                                void *hip_stream);
+vpt_status vpt_postings_merge_positional(const vpt_predictor *p, const void *segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                                         uint64_t *term_offsets_out, uint32_t *post_docs_out, uint32_t *post_tfs_out, uint64_t *post_first_out,
+                                         uint64_t capacity, uint32_t *post_positions_out, uint64_t capacity_positions,
+                                         uint64_t *n_postings_out, uint64_t *n_combined_out, uint64_t *n_positions_out);
+
 /* ConcatGraphemeClustersFilter on the CALLER'S labels (for callers that want it at another place among their filters than
  * VPT_FLAG_CONCAT_GRAPHEMES puts it): labels[out_offsets[i] + b] = 0 for every boundary b of sentence i inside an extended grapheme cluster; no
  * other label is written.  out_offsets from vpt_count_boundaries.

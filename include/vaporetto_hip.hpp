@@ -472,8 +472,11 @@ struct Postings {
     // The merge of segments that share a term id space (vpt_postings_merge): per term the union of their lists by document, a document that
     // stands in several of them one posting whose tf is the sum; n_dropped the segments' sum.  ordered: the promise that every segment's
     // documents are above those of the one before -- checked on the device, no sort.  n_terms: the merged term count (0: the largest of the
-    // segments').  No token lists: token indices are local to a segment.
-    static Postings merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered = false, size_t n_terms = 0);
+    // segments').  No token lists: token indices are local to a segment.  positions: the position lists are merged too
+    // (vpt_postings_merge_positional; every segment must be positional): the result has first and positions, a merged posting's list the
+    // ascending union of its inputs', and phrase_search runs on it; without it both stay empty.
+    static Postings merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered = false, size_t n_terms = 0,
+                          bool positions = false);
     // BM25 top-k of every query over this segment (vpt_postings_search; the definition is in vaporetto_hip.h).  queries: term ids, a slot per
     // id, ids outside [0, n_terms) score nothing.  doc_lens[i]: the length of document doc_base + i (VaporettoTokenizer::doc_lens).  weights:
     // shaped as queries, or nullptr for vpt_okapi_idf(n_documents, df(term)) per slot.  avgdl = float(sum(doc_lens) / n_documents), in double.
@@ -585,15 +588,25 @@ inline Postings::SearchResult Postings::search(const Predictor& predictor, const
     return out;
 }
 
-inline Postings Postings::merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered, size_t n_terms) {
+inline Postings Postings::merge(const Predictor& predictor, const std::vector<Postings>& segments, bool ordered, size_t n_terms, bool positions) {
     std::vector<vpt_postings_segment> segs(segments.size());
-    size_t cap = 0;
+    std::vector<vpt_postings_positional_segment> psegs(positions ? segments.size() : 0);
+    size_t cap = 0, cap_pos = 0;
     Postings out;
     for (size_t k = 0; k < segments.size(); ++k) {
         const Postings& s = segments[k];
         if (s.term_offsets.empty() || s.docs.size() != s.tfs.size())
             throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: merge: a segment's arrays do not belong together");
         segs[k] = vpt_postings_segment{s.term_offsets.data(), s.docs.data(), s.tfs.data(), uint32_t(s.n_terms()), uint64_t(s.docs.size())};
+        if (positions) {
+            if (s.first.empty())
+                throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: merge: a segment was made without positions");
+            if (s.first.size() != s.docs.size() + 1)
+                throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: merge: a segment's arrays do not belong together");
+            psegs[k] = vpt_postings_positional_segment{s.term_offsets.data(), s.docs.data(), s.tfs.data(), s.first.data(), s.positions.data(),
+                                                       uint32_t(s.n_terms()), uint64_t(s.docs.size()), uint64_t(s.positions.size())};
+            cap_pos += s.positions.size();
+        }
         n_terms = std::max(n_terms, s.n_terms());
         cap += s.docs.size();
         out.n_dropped += s.n_dropped;
@@ -602,8 +615,20 @@ inline Postings Postings::merge(const Predictor& predictor, const std::vector<Po
     out.docs.resize(cap + 1);
     out.tfs.resize(cap + 1);
     uint64_t n_postings = 0;
-    detail::check(vpt_postings_merge(predictor.raw(), segs.data(), segs.size(), uint32_t(n_terms), ordered ? unsigned(VPT_POSTINGS_MERGE_ORDERED) : 0u,
-                                     out.term_offsets.data(), out.docs.data(), out.tfs.data(), cap, &n_postings, &out.n_combined));
+    const unsigned flags = ordered ? unsigned(VPT_POSTINGS_MERGE_ORDERED) : 0u;
+    if (positions) {
+        uint64_t n_positions = 0;
+        out.first.resize(cap + 1);
+        out.positions.resize(cap_pos + 1);
+        detail::check(vpt_postings_merge_positional(predictor.raw(), psegs.data(), psegs.size(), uint32_t(n_terms), flags, out.term_offsets.data(),
+                                                    out.docs.data(), out.tfs.data(), out.first.data(), cap, out.positions.data(), cap_pos, &n_postings,
+                                                    &out.n_combined, &n_positions));
+        out.first.resize(size_t(n_postings) + 1);
+        out.positions.resize(size_t(n_positions));
+    } else {
+        detail::check(vpt_postings_merge(predictor.raw(), segs.data(), segs.size(), uint32_t(n_terms), flags, out.term_offsets.data(), out.docs.data(),
+                                         out.tfs.data(), cap, &n_postings, &out.n_combined));
+    }
     out.docs.resize(size_t(n_postings));
     out.tfs.resize(size_t(n_postings));
     return out;
@@ -796,15 +821,17 @@ public:
     }
 
     // The postings of a corpus given as batches of texts: every batch a segment (index above) with a running doc_base, the segments merged on
-    // the device by the ordered route (Postings::merge).  Equal to index of the concatenation.
-    Postings index(const std::vector<std::vector<std::string>>& batches, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true) const {
+    // the device by the ordered route (Postings::merge).  Equal to index of the concatenation.  positions: positional segments, merged with
+    // their position lists -- equal to index of the concatenation with positions; phrase_search runs on it.
+    Postings index(const std::vector<std::vector<std::string>>& batches, const Vocabulary& vocab, uint64_t doc_base = 0, bool normalize = true,
+                   bool positions = false) const {
         std::vector<Postings> segments;
         for (const std::vector<std::string>& texts : batches) {
-            segments.push_back(index(texts, vocab, doc_base, normalize));
+            segments.push_back(index(texts, vocab, doc_base, normalize, positions));
             doc_base += texts.size();
         }
-        if (segments.empty()) return index(std::vector<std::string>(), vocab, doc_base, normalize);
-        return Postings::merge(predictor_, segments, true, vocab.size());
+        if (segments.empty()) return index(std::vector<std::string>(), vocab, doc_base, normalize, positions);
+        return Postings::merge(predictor_, segments, true, vocab.size(), positions);
     }
 
     // The lengths Postings::search takes: the tokens this tokenizer streams per text (those without a vocabulary entry included).

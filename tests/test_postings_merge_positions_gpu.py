@@ -1,0 +1,70 @@
+"""The merge of positional segments on the MI355X through the C ABI: the ordered route's tables, copy and pcopy, the general route's ranks,
+scans, first and pcopy behind the merge's own launches, the host call, Postings.merge(positions=True) and the tokenizer's
+index_batches(positions=True) against the definitions of tests/positionsmergeref.py and tests/phraseref.py -- the checks of
+tests/positionsmergesuite.py.  (The hostile segments run here after they have run on the emulator,
+tests/test_postings_merge_positions_emu.py: every kernel loop is bounded, every index is bounded before it is used, nothing waits.)"""
+import pytest
+
+from tests import positionsmergesuite, vocabsuite
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def fresh_predictor():
+    vocabsuite._PRED.clear()
+    yield
+    vocabsuite._PRED.clear()
+
+
+def test_ordered_merge_of_device_made_ranges_equals_one_pass_on_both_routes():
+    positionsmergesuite.check_ordered_equals_one_pass()
+
+
+def test_general_merge_of_tokens_dealt_at_random_equals_one_pass():
+    positionsmergesuite.check_general()
+
+
+def test_position_places_on_the_workgroup_edges_and_a_segment_boundary_inside_a_wave():
+    positionsmergesuite.check_position_places()
+
+
+@pytest.mark.parametrize("n", ["T-1", "T", "T+1", "3T+1"])
+def test_positions_on_the_scan_tile_edges(n):
+    positionsmergesuite.check_positions_on_the_scan_tile(positionsmergesuite.postingssuite.token_count(n))
+
+
+def test_edges_one_posting_last_segment_term_spare_capacity_and_one_segment():
+    positionsmergesuite.check_edges()
+
+
+def test_phrase_search_over_the_merged_segment_has_the_definitions_score_bits():
+    positionsmergesuite.check_phrase_search_over_the_merge()
+
+
+def test_capacities_too_small_are_errors_at_sync_with_the_numbers_needed():
+    positionsmergesuite.check_capacity()
+
+
+def test_errors_at_the_call():
+    positionsmergesuite.check_errors()
+
+
+def test_positions_that_do_not_ascend_or_repeat_across_segments():
+    positionsmergesuite.check_bad_positions()
+
+
+def test_hostile_segment_is_an_error_at_sync_and_touches_nothing_outside():
+    assert positionsmergesuite.run_hostile() == positionsmergesuite.N_HOSTILE
+
+
+def test_two_runs_and_a_second_workspace_give_identical_bytes():
+    positionsmergesuite.check_determinism()
+
+
+def test_host_call_and_postings_merge_with_positions():
+    positionsmergesuite.check_host_call()
+
+
+def test_index_batches_with_positions_equals_index_batch_of_the_concatenation():
+    positionsmergesuite.check_index_batches()

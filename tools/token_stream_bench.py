@@ -18,6 +18,9 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
   --merge K[,K..]: with --postings, the batch's documents as K equal ranges: the K segment calls, the ordered and the general merge
       (kernels_postings_merge.hip) and a device-to-device copy of the bytes the ordered merge must move, each the median of --rounds rounds of
       --steps calls by device events, beside the one-pass call of the same run (profiles/postings_merge_bench.json).
+      Its `positional` row: the same ranges as positional segments (each with its positions call), the ordered and the general positional merge
+      beside the merges without positions over the same segments and a copy of the bytes the ordered positional merge must move
+      (profiles/postings_merge_positions_bench.json).
   --search Q,L,K: with --postings, Q queries of L terms drawn from the vocabulary by count (a term's tokens in the batch), top K, over the one-pass
       segment (kernels_postings_search.hip) by device events, beside two yardsticks of the same run: the general merge over one segment of as
       many input places as the search has candidates, and a device-to-device copy of half of 8 bytes a candidate plus 8 bytes a hit (a copy of
@@ -156,6 +159,79 @@ def merge_rows(torch, batch, stream, dev, args, K, S, n_terms, dev_off, d_soff, 
         out[name + "_over_one_pass"] = round(out[name + "_ms"] / one_pass_ms, 3)
     out["segments_plus_ordered_over_one_pass"] = round((out["segments_ms"] + out["ordered_ms"]) / one_pass_ms, 3)
     out["segments_over_one_pass"] = round(out["segments_ms"] / one_pass_ms, 3)
+    out["positional"] = positional_merge_row(torch, batch, stream, dev, args, K, S, n_terms, cuts, tok, seg_off, descr, seg_cnt, d_soff, d_ids, n_post,
+                                             out["ordered_ms"], out["general_ms"])
+    return out
+
+
+def positional_merge_row(torch, batch, stream, dev, args, K, S, n_terms, cuts, tok, seg_off, descr, seg_cnt, d_soff, d_ids, n_post, ordered_ms, general_ms):
+    """The positional row of --merge K: the same K document ranges, each a POSITIONAL segment (its postings call with the
+    optional pair and its positions call, NULL token_positions); by device events: the K pairs of calls together, the ordered and the general
+    positional merge, and device-to-device copies of as many bytes as the ordered positional merge must move (8 bytes a posting, 8 bytes a
+    post_first entry and 4 bytes a position in and out, the K term_offsets arrays in).  The yardsticks of the same process: the merges without
+    positions over the same segments (ordered_ms, general_ms of the row above) and that copy.  Both routes' five arrays must be the bytes of
+    the one-pass positional segment of the whole batch."""
+    T = tok[-1]
+    i64, i32 = torch.int64, torch.int32
+    w_term, w_first, w_cnt = torch.empty(n_terms + 1, dtype=i64, device=dev), torch.empty(T + 2, dtype=i64, device=dev), torch.zeros(2, dtype=i64, device=dev)
+    w_docs, w_tfs, w_order, w_ppos = (torch.empty(T + 1, dtype=i32, device=dev) for _ in range(4))
+    batch.postings(d_soff.data_ptr(), S, d_ids.data_ptr(), T, n_terms, 0, w_term.data_ptr(), w_docs.data_ptr(), w_tfs.data_ptr(), T, w_first.data_ptr(),
+                   w_order.data_ptr(), w_cnt.data_ptr(), stream)
+    batch.postings_positions(d_soff.data_ptr(), S, T, 0, w_term.data_ptr(), n_terms, w_first.data_ptr(), T, w_order.data_ptr(), w_ppos.data_ptr(), stream)
+    batch.sync()
+    assert int(w_cnt[0].item()) == n_post
+    n_idx = int(w_first[n_post].item())
+    seg_first = torch.empty(T + K + 1, dtype=i64, device=dev)                     # segment s: tok[s] + s .. tok[s + 1] + s + 1
+    seg_order, seg_ppos = torch.empty(T + 1, dtype=i32, device=dev), torch.empty(T + 1, dtype=i32, device=dev)
+    first_at = [seg_first.data_ptr() + 8 * (tok[s] + s) for s in range(K)]
+    order_at = [seg_order.data_ptr() + 4 * tok[s] for s in range(K)]
+    ppos_at = [seg_ppos.data_ptr() + 4 * tok[s] for s in range(K)]
+    pdescr = [(descr[s][0], descr[s][1], descr[s][2], first_at[s], ppos_at[s], n_terms, tok[s + 1] - tok[s], tok[s + 1] - tok[s]) for s in range(K)]
+    o_term, o_first, o_cnt = torch.empty(n_terms + 1, dtype=i64, device=dev), torch.empty(T + 2, dtype=i64, device=dev), torch.zeros(3, dtype=i64, device=dev)
+    o_docs, o_tfs, o_ppos = (torch.empty(T + 1, dtype=i32, device=dev) for _ in range(3))
+
+    def segments():
+        for s in range(K):
+            n_s, docs_s = tok[s + 1] - tok[s], cuts[s + 1] - cuts[s]
+            batch.postings(seg_off[s].data_ptr(), docs_s, d_ids.data_ptr() + 4 * tok[s], n_s, n_terms, cuts[s], descr[s][0], descr[s][1], descr[s][2], n_s,
+                           first_at[s], order_at[s], seg_cnt.data_ptr() + 16 * s, stream)
+            batch.postings_positions(seg_off[s].data_ptr(), docs_s, n_s, 0, descr[s][0], n_terms, first_at[s], n_s, order_at[s], ppos_at[s], stream)
+
+    def merge(ordered):
+        batch.merge_positional_postings(pdescr, n_terms, o_term.data_ptr(), o_docs.data_ptr(), o_tfs.data_ptr(), o_first.data_ptr(), T, o_ppos.data_ptr(), T,
+                                        o_cnt.data_ptr(), ordered, stream)
+    half = lambda n_bytes, dt, size: (torch.empty(n_bytes // (2 * size) + 1, dtype=dt, device=dev), torch.empty(n_bytes // (2 * size) + 1, dtype=dt, device=dev))
+    copies = [half(2 * 8 * n_post, i32, 4), half(2 * 8 * (n_post + 1), i64, 8), half(2 * 4 * n_idx, i32, 4), half(8 * K * (n_terms + 1), i64, 8)]
+
+    def floor():
+        for a, b in copies:
+            b.copy_(a)
+    segments()
+    batch.sync()
+    out = {"K": K, "input_places": T, "position_places": T, "postings": n_post, "positions": n_idx, "table_bytes": 2 * 8 * K * (n_terms + 1),
+           "floor_bytes_copied": 8 * n_post + 8 * (n_post + 1) + 4 * n_idx + 4 * K * (n_terms + 1),
+           "ordered_without_positions_ms": ordered_ms, "general_without_positions_ms": general_ms}
+    for name, fn in (("segments", segments), ("ordered", lambda: merge(True)), ("general", lambda: merge(False)), ("floor", floor)):
+        fn()
+        batch.sync()
+        if name in ("ordered", "general"):
+            n, m = int(o_cnt[0].item()), int(o_cnt[2].item())
+            out[name + "_equals_one_pass"] = bool(n == n_post and m == n_idx and int(o_cnt[1].item()) == 0 and torch.equal(o_term, w_term)
+                                                  and torch.equal(o_docs[:n], w_docs[:n]) and torch.equal(o_tfs[:n], w_tfs[:n])
+                                                  and torch.equal(o_first[:n + 1], w_first[:n + 1]) and torch.equal(o_ppos[:m], w_ppos[:m]))
+        r = []
+        for _ in range(args.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in ev:
+                a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            r.append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        out[name + "_ms"] = round(med(r), 4)
+        out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+    for name, plain in (("ordered", ordered_ms), ("general", general_ms)):
+        out[name + "_over_floor"] = round(out[name + "_ms"] / out["floor_ms"], 2)
+        out[name + "_over_without_positions"] = round(out[name + "_ms"] / plain, 3)
     return out
 
 

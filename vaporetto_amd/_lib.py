@@ -62,6 +62,12 @@ class PostingsSegment(C.Structure):
                 ("capacity", C.c_uint64)]
 
 
+class PostingsPositionalSegment(C.Structure):
+    """vpt_postings_positional_segment: device pointers for vpt_postings_merge_positional_device, host pointers for vpt_postings_merge_positional"""
+    _fields_ = [("d_term_offsets", C.c_void_p), ("d_post_docs", C.c_void_p), ("d_post_tfs", C.c_void_p), ("d_post_first", C.c_void_p),
+                ("d_post_positions", C.c_void_p), ("n_terms", C.c_uint32), ("capacity", C.c_uint64), ("capacity_positions", C.c_uint64)]
+
+
 class TagProblemInfo(C.Structure):
     _fields_ = [("slot", C.c_uint32), ("n_classes", C.c_uint32), ("path", C.c_uint32), ("model", C.c_uint32), ("n_rows", C.c_uint64),
                 ("n_features", C.c_uint64), ("nnz", C.c_uint64), ("surface_bytes", C.c_uint64), ("cand_bytes", C.c_uint64),
@@ -149,6 +155,9 @@ SIGNATURES = {
     "vpt_postings_merge_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, C.c_uint64, _P, _P]),
     "vpt_postings_merge_limits": (C.c_int, [C.POINTER(C.c_uint32)]),
     "vpt_postings_merge": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vpt_postings_merge_positional_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
+    "vpt_postings_merge_positional": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vpt_postings_search_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_uint32, C.c_uint64,
                                              C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P]),
     "vpt_postings_search_limits": (C.c_int, [C.POINTER(C.c_uint32)]),

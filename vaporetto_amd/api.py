@@ -1547,6 +1547,32 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def merge_positional_postings(self, segments: Sequence[Tuple[int, int, int, int, int, int, int, int]], n_terms_out: int, d_term_offsets: int,
+                                  d_post_docs: int, d_post_tfs: int, d_post_first: int, capacity_out: int, d_post_positions: int,
+                                  capacity_positions_out: int, d_counts: int, ordered: bool = False, stream: int = 0,
+                                  flags: Optional[int] = None) -> None:
+        """Device-resident merge of POSITIONAL segments (vpt_postings_merge_positional_device).  segments: (d_term_offsets, d_post_docs,
+        d_post_tfs, d_post_first, d_post_positions, n_terms, capacity, capacity_positions) each, raw device pointers; the outputs must not alias
+        them.  d_counts: uint64 [3] = merged postings, combined postings, merged positions.  Enqueues and returns; errors (merge_postings' list,
+        post_first that is no segment's, positions that do not ascend or repeat, more positions than capacity_positions_out) at sync()."""
+        segs = (_lib.PostingsPositionalSegment * max(len(segments), 1))()
+        for k, (toff, docs, tfs, first, ppos, n_terms, cap, cap_pos) in enumerate(segments):
+            for name, v, top in (("segment n_terms", n_terms, 1 << 32), ("segment capacity", cap, 1 << 64), ("segment capacity_positions", cap_pos, 1 << 64)):
+                if not 0 <= int(v) < top:
+                    raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+            segs[k] = _lib.PostingsPositionalSegment(toff or None, docs or None, tfs or None, first or None, ppos or None, int(n_terms), int(cap), int(cap_pos))
+        for name, v, top in (("n_terms_out", n_terms_out, 1 << 32), ("capacity_out", capacity_out, 1 << 64),
+                             ("capacity_positions_out", capacity_positions_out, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        f = (_lib.VPT_POSTINGS_MERGE_ORDERED if ordered else 0) if flags is None else int(flags)
+        st = _lib.load().vpt_postings_merge_positional_device(self._p.handle, self._h, C.addressof(segs), len(segments), int(n_terms_out), f,
+                                                              d_term_offsets or None, d_post_docs or None, d_post_tfs or None, d_post_first or None,
+                                                              int(capacity_out), d_post_positions or None, int(capacity_positions_out),
+                                                              d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     @staticmethod
     def postings_merge_limit() -> int:
         """the most segments one merge takes (vpt_postings_merge_limits)"""
@@ -2074,41 +2100,64 @@ class Postings:
 
     @staticmethod
     def merge(segments: Sequence["Postings"], ordered: bool = False, predictor: Optional["Predictor"] = None, n_terms: Optional[int] = None,
-              capacity: Optional[int] = None) -> "Postings":
+              capacity: Optional[int] = None, positions: bool = False, capacity_positions: Optional[int] = None) -> "Postings":
         """The merge of segments that share a term id space (vpt_postings_merge): per term the union of their lists by document, a document
         that stands in several of them one posting whose tf is the sum; n_dropped the segments' sum, n_combined the postings that went into
         another.  ordered: the promise that every segment's documents are above those of the one before (checked on the device; no sort).
         n_terms: the merged term count (default: the largest of the segments').  predictor: whose device (default: the one that made the
-        first segment).  No `first` / `order`: token indices are local to a segment."""
+        first segment).  No `order`: token indices are local to a segment.  positions: the position lists are merged too
+        (vpt_postings_merge_positional; every segment must carry `first` and `positions`): the result has `first` and `positions`, a merged
+        posting's list the ascending union of its inputs', and phrase_search runs on it; without it `first` and `positions` are None."""
         segments = list(segments)
         pred = predictor or next((s._predictor for s in segments if getattr(s, "_predictor", None) is not None), None)
         if pred is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: no predictor (pass predictor=)")
+        if positions and any(s.first is None or s.positions is None for s in segments):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: a segment was made without positions")
         keep = [(np.ascontiguousarray(s.term_offsets, dtype=np.uint64), np.ascontiguousarray(s.docs, dtype=np.uint32),
                  np.ascontiguousarray(s.tfs, dtype=np.uint32)) for s in segments]
         for t, d, f in keep:
             if len(t) == 0 or len(d) != len(f):
                 raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: a segment's arrays do not belong together")
         n_out = max([len(t) - 1 for t, _, _ in keep] + [0]) if n_terms is None else int(n_terms)
-        segs = (_lib.PostingsSegment * max(len(keep), 1))()
-        for k, (t, d, f) in enumerate(keep):
-            segs[k] = _lib.PostingsSegment(t.ctypes.data, d.ctypes.data if len(d) else None, f.ctypes.data if len(f) else None, len(t) - 1, len(d))
         cap = sum(len(d) for _, d, _ in keep) if capacity is None else int(capacity)
         term = np.zeros(max(n_out, 0) + 1, np.uint64)
         docs, tfs = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
-        n_post, n_comb = C.c_uint64(), C.c_uint64()
+        n_post, n_comb, n_pos = C.c_uint64(), C.c_uint64(), C.c_uint64()
         if not 0 <= n_out < 1 << 32:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: n_terms: must be between 1 and 2^24")
-        st = _lib.load().vpt_postings_merge(pred.handle, C.addressof(segs), len(keep), n_out, _lib.VPT_POSTINGS_MERGE_ORDERED if ordered else 0,
-                                            term.ctypes.data, docs.ctypes.data, tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_comb))
+        flags = _lib.VPT_POSTINGS_MERGE_ORDERED if ordered else 0
+        if positions:
+            pkeep = [(np.ascontiguousarray(s.first, dtype=np.uint64), np.ascontiguousarray(s.positions, dtype=np.uint32)) for s in segments]
+            for (_, d, _), (fi, _) in zip(keep, pkeep):
+                if len(fi) != len(d) + 1:
+                    raise VaporettoError("InvalidArgument", "InvalidArgumentError: merge: a segment's arrays do not belong together")
+            segs = (_lib.PostingsPositionalSegment * max(len(keep), 1))()
+            for k, ((t, d, f), (fi, pp)) in enumerate(zip(keep, pkeep)):
+                segs[k] = _lib.PostingsPositionalSegment(t.ctypes.data, d.ctypes.data if len(d) else None, f.ctypes.data if len(f) else None, fi.ctypes.data,
+                                                         pp.ctypes.data if len(pp) else None, len(t) - 1, len(d), len(pp))
+            cap_pos = sum(len(pp) for _, pp in pkeep) if capacity_positions is None else int(capacity_positions)
+            first, ppos = np.zeros(max(cap, 0) + 1, np.uint64), np.zeros(max(cap_pos, 1), np.uint32)
+            st = _lib.load().vpt_postings_merge_positional(pred.handle, C.addressof(segs), len(keep), n_out, flags, term.ctypes.data, docs.ctypes.data,
+                                                           tfs.ctypes.data, first.ctypes.data, cap, ppos.ctypes.data, cap_pos, C.byref(n_post),
+                                                           C.byref(n_comb), C.byref(n_pos))
+        else:
+            segs = (_lib.PostingsSegment * max(len(keep), 1))()
+            for k, (t, d, f) in enumerate(keep):
+                segs[k] = _lib.PostingsSegment(t.ctypes.data, d.ctypes.data if len(d) else None, f.ctypes.data if len(f) else None, len(t) - 1, len(d))
+            st = _lib.load().vpt_postings_merge(pred.handle, C.addressof(segs), len(keep), n_out, flags, term.ctypes.data, docs.ctypes.data,
+                                                tfs.ctypes.data, cap, C.byref(n_post), C.byref(n_comb))
         if st != _lib.VPT_OK:
             try:
                 _raise(st)
             except VaporettoError as e:
-                e.n_postings = int(n_post.value)   # (too small a capacity: the number needed)
+                e.n_postings = int(n_post.value)   # (too small a capacity: the numbers needed)
+                e.n_positions = int(n_pos.value)
                 raise
         n = int(n_post.value)
-        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), None, None, sum(s.n_dropped for s in segments))
+        out = Postings(term, docs[:n].copy(), tfs[:n].copy(), first[:n + 1].copy() if positions else None, None, sum(s.n_dropped for s in segments))
+        if positions:
+            out.positions = ppos[:int(n_pos.value)].copy()
         out.n_combined = int(n_comb.value)
         out._predictor = pred
         return out
@@ -2367,18 +2416,19 @@ class VaporettoTokenizer:
         out.doc_base = int(doc_base)
         return out
 
-    def index_batches(self, batches: Iterable[Sequence[str]], doc_base: int = 0, ordered: bool = True) -> "Postings":
+    def index_batches(self, batches: Iterable[Sequence[str]], doc_base: int = 0, ordered: bool = True, positions: bool = False) -> "Postings":
         """The postings of a corpus given as batches of documents: every batch is indexed as a segment (index_batch) with a running doc_base,
         and the segments are merged on the device (Postings.merge; ordered: the running doc_bases keep the promise of the ordered route).
-        Equal to index_batch of the concatenation.  No batch: the empty postings over the vocabulary."""
+        Equal to index_batch of the concatenation.  positions: positional segments, merged with their position lists -- equal to
+        index_batch(concatenation, positions=True), and phrase_search runs on it.  No batch: the empty postings over the vocabulary."""
         segments, base = [], int(doc_base)
         for texts in batches:
             texts = list(texts)
-            segments.append(self.index_batch(texts, base))
+            segments.append(self.index_batch(texts, base, positions=positions))
             base += len(texts)
         if not segments:
-            return self.index_batch([], base)
-        out = Postings.merge(segments, ordered=ordered, predictor=self._predictor)
+            return self.index_batch([], base, positions=positions)
+        out = Postings.merge(segments, ordered=ordered, predictor=self._predictor, positions=positions)
         out.doc_lens, out.doc_base = np.concatenate([s.doc_lens for s in segments]), int(doc_base)   # (the running doc_bases are contiguous)
         return out
 

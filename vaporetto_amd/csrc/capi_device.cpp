@@ -1280,7 +1280,109 @@ vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
+
+// The merge of positional segments.  Ordered: load, offsets and the position offsets (the two tables), copy with post_first, check, pcopy.
+// General: load, offsets, records, the sort, heads, ranks (the tfs in sorted order, the inverse of the order), the scan of the heads, emit and
+// terms, the scan of the tfs, first, pcopy.
+vpt_status postings_merge_positional_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_positional_segment* segments, size_t n_segments,
+                                            uint32_t n_terms_out, unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out,
+                                            uint32_t* d_post_tfs_out, uint64_t* d_post_first_out, uint64_t capacity_out, uint32_t* d_post_positions_out,
+                                            uint64_t capacity_positions_out, uint64_t* d_counts, hipStream_t stream) {
+    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    if (!segments || !d_term_offsets_out || !d_post_docs_out || !d_post_tfs_out || !d_post_first_out || !d_post_positions_out || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
+    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    if (flags & ~unsigned(VPT_POSTINGS_MERGE_ORDERED)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (capacity_positions_out >= (1ull << 32))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+    const uint32_t K = uint32_t(n_segments);
+    std::vector<vpt::PostingsMergeSegment> segs(K);
+    std::vector<vpt::PostingsMergePosSegment> psegs(K);
+    uint64_t n = 0, np = 0;
+    for (uint32_t s = 0; s < K; ++s) {
+        const vpt_postings_positional_segment& in = segments[s];
+        if (!in.d_term_offsets || !in.d_post_docs || !in.d_post_tfs || !in.d_post_first || !in.d_post_positions)
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+        if (in.n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
+        if (in.capacity >= (1ull << 32) || n + in.capacity >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
+        if (in.capacity_positions >= (1ull << 32) || np + in.capacity_positions >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+        segs[s] = vpt::PostingsMergeSegment{in.d_term_offsets, in.d_post_docs, in.d_post_tfs, in.capacity, n, in.n_terms, 0u};
+        psegs[s] = vpt::PostingsMergePosSegment{in.d_post_first, in.d_post_positions, in.capacity_positions, np};
+        n += in.capacity;
+        np += in.capacity_positions;
+    }
+    VPT_HIP(hipSetDevice(p->device));
+    const bool ordered = (flags & VPT_POSTINGS_MERGE_ORDERED) != 0;
+    // the scratch in 256-byte sections: segs | psegs | range | table | ptable (ordered)   or
+    // segs | psegs | rec | order | skey | flags | scan | ptf | inv | pscan | hist | hist_scan | partials
+    const uint64_t nh = vpt::train_radix_scratch(n), row = uint64_t(n_terms_out) + 1;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_segs = 0, o_psegs = pad(sizeof(vpt::PostingsMergeSegment) * K), o_a = o_psegs + pad(sizeof(vpt::PostingsMergePosSegment) * K);
+    const size_t o_table = o_a + pad(8 * size_t(K)), o_ptable = o_table + pad(8 * size_t(K) * size_t(row));
+    const size_t o_order = o_a + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
+                 o_scan = o_flags + pad(4 * size_t(n)), o_ptf = o_scan + pad(8 * (size_t(n) + 1)), o_inv = o_ptf + pad(4 * size_t(n)),
+                 o_pscan = o_inv + pad(4 * size_t(n)), o_hist = o_pscan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
+                 o_part = o_hscan + pad(8 * (size_t(nh) + 1));
+    const size_t total = ordered ? o_ptable + pad(8 * size_t(K) * size_t(row))
+                                 : o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
+    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    unsigned char* m = b->d_post;
+    vpt::PostingsMergePosParams Q{};
+    vpt::PostingsMergeParams& P = Q.M;
+    P.segs = reinterpret_cast<vpt::PostingsMergeSegment*>(m + o_segs); P.n_segs = K; P.n_terms = n_terms_out; P.n_places = n;
+    P.term_offsets = d_term_offsets_out; P.post_docs = d_post_docs_out; P.post_tfs = d_post_tfs_out; P.capacity_out = capacity_out;
+    P.counts = d_counts; P.status = b->d_ctrl;
+    Q.psegs = reinterpret_cast<vpt::PostingsMergePosSegment*>(m + o_psegs); Q.n_pplaces = np;
+    Q.post_first = d_post_first_out; Q.post_positions = d_post_positions_out; Q.capacity_positions_out = capacity_positions_out;
+    if (ordered) {
+        P.range = reinterpret_cast<uint32_t*>(m + o_a); P.table = reinterpret_cast<uint64_t*>(m + o_table);
+        Q.ptable = reinterpret_cast<uint64_t*>(m + o_ptable);
+        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_positions_load(Q, psegs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_positions_ordered(Q, stream));
+    } else {
+        P.rec = reinterpret_cast<uint32_t*>(m + o_a); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
+        P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+        Q.ptf = reinterpret_cast<uint32_t*>(m + o_ptf); Q.inv = reinterpret_cast<uint32_t*>(m + o_inv); Q.pscan = reinterpret_cast<uint64_t*>(m + o_pscan);
+        uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
+        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_positions_load(Q, psegs.data(), stream));
+        VPT_HIP(vpt::launch_postings_merge_records(P, stream));
+        if (n == 0) {   // no place: no posting, no position (the offsets were still checked)
+            VPT_HIP(hipMemsetAsync(d_term_offsets_out, 0, 8 * size_t(row), stream));
+            VPT_HIP(hipMemsetAsync(d_post_first_out, 0, 8, stream));
+            VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
+        } else {
+            uint32_t passes[8], n_passes = 0;   // the document word's four bytes, then the bytes of the values 0 .. n_terms_out of the term word
+            for (uint32_t k = 0; k < 4; ++k) passes[n_passes++] = (1u << 8) | (8 * k);
+            for (uint32_t v = n_terms_out, k = 0; v; v >>= 8, ++k) passes[n_passes++] = 8 * k;
+            VPT_HIP(vpt::train_radix_sort(P.rec, 3, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
+                                          reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
+            VPT_HIP(vpt::launch_postings_merge_heads(P, stream));
+            VPT_HIP(vpt::launch_postings_merge_positions_ranks(Q, stream));
+            VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+            VPT_HIP(vpt::launch_postings_merge_emit(P, stream));
+            VPT_HIP(vpt::train_scan(Q.ptf, n, Q.pscan, part, stream));
+            VPT_HIP(vpt::launch_postings_merge_positions_general(Q, stream));
+        }
+    }
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
 }  // namespace vptc
+
+vpt_status vpt_postings_merge_positional_device(const vpt_predictor* p, vpt_batch* b, const void* segments, size_t n_segments, uint32_t n_terms_out,
+                                                unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out,
+                                                uint64_t* d_post_first_out, uint64_t capacity_out, uint32_t* d_post_positions_out,
+                                                uint64_t capacity_positions_out, uint64_t* d_counts, void* hip_stream) {
+    return postings_merge_positional_device(p, b, static_cast<const vpt_postings_positional_segment*>(segments), n_segments, n_terms_out, flags,
+                                            d_term_offsets_out, d_post_docs_out, d_post_tfs_out, d_post_first_out, capacity_out, d_post_positions_out,
+                                            capacity_positions_out, d_counts, static_cast<hipStream_t>(hip_stream));
+}
 
 vpt_status vpt_postings_merge_device(const vpt_predictor* p, vpt_batch* b, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
                                      uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,

@@ -1027,7 +1027,7 @@ vpt_status token_stream_postings(const vpt_predictor* p, const uint8_t* utf8, co
     if (positional) *n_positions_out = n_tok - counts[1];   // the indexed tokens
     if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
     if (positional && *n_positions_out > capacity_positions)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: smaller than the number of indexed tokens");
+        return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
     VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms) + 1), hipMemcpyDeviceToHost));
     if (counts[0]) {
         VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
@@ -1128,6 +1128,97 @@ vpt_status vpt_postings_merge(const vpt_predictor* p, const void* segments, size
         VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
         VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
     }
+    return VPT_OK;
+}
+
+// Host positional segments in, the merged positional segment out: vpt_postings_merge's steps with every segment's post_first (postings + 1
+// entries) and positions (post_first[postings] of them, at most its capacity_positions) beside its three arrays.
+vpt_status vpt_postings_merge_positional(const vpt_predictor* p, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                                         uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t* post_first_out,
+                                         uint64_t capacity, uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_postings_out,
+                                         uint64_t* n_combined_out, uint64_t* n_positions_out) {
+    if (n_postings_out) *n_postings_out = 0;
+    if (n_combined_out) *n_combined_out = 0;
+    if (n_positions_out) *n_positions_out = 0;
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    const vpt_postings_positional_segment* in = static_cast<const vpt_postings_positional_segment*>(segments);
+    if (!in || !term_offsets_out || !post_first_out || !n_postings_out || !n_combined_out || !n_positions_out ||
+        (capacity && (!post_docs_out || !post_tfs_out)) || (capacity_positions && !post_positions_out))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
+    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    std::vector<vpt_postings_positional_segment> dev(n_segments);
+    std::vector<size_t> at(n_segments);   // where the segment's five arrays start in the allocation
+    size_t total = 0;
+    uint64_t n_in = 0, np_in = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        if (!in[s].d_term_offsets || !in[s].d_post_first || (in[s].capacity && (!in[s].d_post_docs || !in[s].d_post_tfs)) ||
+            (in[s].capacity_positions && !in[s].d_post_positions))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+        if (in[s].n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
+        const uint64_t n = std::min(in[s].d_term_offsets[in[s].n_terms], in[s].capacity);   // (an end above the capacity: the device reports it)
+        const uint64_t np = std::min(in[s].d_post_first[n], in[s].capacity_positions);
+        if (n >= (1ull << 32) || n_in + n >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
+        if (np >= (1ull << 32) || np_in + np >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+        dev[s].n_terms = in[s].n_terms;
+        dev[s].capacity = n;
+        dev[s].capacity_positions = np;
+        at[s] = total;
+        total += pad(8 * (size_t(in[s].n_terms) + 1)) + 2 * pad(4 * size_t(n) + 4) + pad(8 * (size_t(n) + 1)) + pad(4 * size_t(np) + 4);
+        n_in += n;
+        np_in += np;
+    }
+    const size_t o_term = total, o_docs = o_term + pad(8 * (size_t(n_terms_out) + 1)), o_tfs = o_docs + pad(4 * size_t(n_in) + 4),
+                 o_first = o_tfs + pad(4 * size_t(n_in) + 4), o_ppos = o_first + pad(8 * (size_t(n_in) + 1)), o_cnt = o_ppos + pad(4 * size_t(np_in) + 4);
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    vpt_status st;
+    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    DevBuf<unsigned char> mem;
+    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    unsigned char* m = mem;
+    for (size_t k = 0; k < n_segments; ++k) {
+        const size_t n = size_t(dev[k].capacity), np = size_t(dev[k].capacity_positions), o_d = at[k] + pad(8 * (size_t(in[k].n_terms) + 1)),
+                     o_t = o_d + pad(4 * n + 4), o_f = o_t + pad(4 * n + 4), o_p = o_f + pad(8 * (n + 1));
+        VPT_HIP(hipMemcpyAsync(m + at[k], in[k].d_term_offsets, 8 * (size_t(in[k].n_terms) + 1), hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(m + o_f, in[k].d_post_first, 8 * (n + 1), hipMemcpyHostToDevice, s));
+        if (n) {
+            VPT_HIP(hipMemcpyAsync(m + o_d, in[k].d_post_docs, 4 * n, hipMemcpyHostToDevice, s));
+            VPT_HIP(hipMemcpyAsync(m + o_t, in[k].d_post_tfs, 4 * n, hipMemcpyHostToDevice, s));
+        }
+        if (np) VPT_HIP(hipMemcpyAsync(m + o_p, in[k].d_post_positions, 4 * np, hipMemcpyHostToDevice, s));
+        dev[k].d_term_offsets = reinterpret_cast<const uint64_t*>(m + at[k]);
+        dev[k].d_post_docs = reinterpret_cast<const uint32_t*>(m + o_d);
+        dev[k].d_post_tfs = reinterpret_cast<const uint32_t*>(m + o_t);
+        dev[k].d_post_first = reinterpret_cast<const uint64_t*>(m + o_f);
+        dev[k].d_post_positions = reinterpret_cast<const uint32_t*>(m + o_p);
+    }
+    st = postings_merge_positional_device(p, b, dev.data(), n_segments, n_terms_out, flags, reinterpret_cast<uint64_t*>(m + o_term),
+                                          reinterpret_cast<uint32_t*>(m + o_docs), reinterpret_cast<uint32_t*>(m + o_tfs),
+                                          reinterpret_cast<uint64_t*>(m + o_first), n_in, reinterpret_cast<uint32_t*>(m + o_ppos), np_in,
+                                          reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    if (st != VPT_OK) return st;
+    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    uint64_t counts[3] = {0, 0, 0};
+    VPT_HIP(hipMemcpy(counts, m + o_cnt, 24, hipMemcpyDeviceToHost));
+    *n_postings_out = counts[0];
+    *n_combined_out = counts[1];
+    *n_positions_out = counts[2];
+    if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
+    if (counts[2] > capacity_positions) return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
+    VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms_out) + 1), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(post_first_out, m + o_first, 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
+    if (counts[0]) {
+        VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+    }
+    if (counts[2]) VPT_HIP(hipMemcpy(post_positions_out, m + o_ppos, 4 * size_t(counts[2]), hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 

@@ -308,6 +308,7 @@ constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: 
 constexpr const char* kPostingsTooSmall = "InvalidArgumentError: capacity: smaller than the number of postings";
 constexpr const char* kCandidatesTooSmall = "InvalidArgumentError: capacity_candidates: smaller than the number of candidates";
 constexpr const char* kProbesTooSmall = "InvalidArgumentError: capacity_probes: smaller than the number of probes";
+constexpr const char* kPositionsTooSmall = "InvalidArgumentError: capacity_positions: smaller than the number of indexed tokens";
 
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
 template <typename T>
@@ -387,7 +388,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
-    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_search_device: PostingsSearchParams; vpt_postings_phrase_search_device: PostingsPhraseParams (36 bytes a query, 48 bytes a probe place, the histograms)
+    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_merge_positional_device: PostingsMergePosParams (32 bytes more a segment; ordered a second table, general 16 bytes more a place); vpt_postings_search_device: PostingsSearchParams; vpt_postings_phrase_search_device: PostingsPhraseParams (36 bytes a query, 48 bytes a probe place, the histograms)
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -543,6 +544,7 @@ vpt_status status_from_bits(uint32_t bits) {
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segments: document ranges overlap or descend");
     if (bits & vpt::kErrTfOverflow) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: tf: sum exceeds 32 bits");
     if (bits & vpt::kErrPostingsTooSmall) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
+    if (bits & vpt::kErrPositionsTooSmall) return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
     return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: max_sentence_bytes / max_sentence_chars: smaller than the longest sentence");
 }
 
@@ -737,6 +739,11 @@ vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t*
 vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
                                  unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
                                  uint64_t* d_counts, hipStream_t stream);
+// The merge of positional segments (vpt_postings_merge_positional_device; kernels_postings_merge.hip)
+vpt_status postings_merge_positional_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_positional_segment* segments, size_t n_segments,
+                                            uint32_t n_terms_out, unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out,
+                                            uint32_t* d_post_tfs_out, uint64_t* d_post_first_out, uint64_t capacity_out, uint32_t* d_post_positions_out,
+                                            uint64_t capacity_positions_out, uint64_t* d_counts, hipStream_t stream);
 // The BM25 top-k search over a segment (vpt_postings_search_device; kernels_postings_search.hip)
 vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
                                   uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,

@@ -79,6 +79,7 @@ constexpr uint32_t kErrCandidatesTooSmall = 262144u;  // the postings search: mo
 constexpr uint32_t kErrBadPositions = 524288u;        // the positions of a segment: a posting's positions do not strictly ascend (kernels_postings_phrase.hip)
 constexpr uint32_t kErrPhraseTooLong = 1048576u;      // the phrase search: a phrase of more than kPhraseMaxTerms slots
 constexpr uint32_t kErrProbesTooSmall = 2097152u;     // the phrase search: more probes than capacity_probes
+constexpr uint32_t kErrPositionsTooSmall = 4194304u;  // the positional merge: more merged positions than capacity_positions_out
 
 
 struct ScoreParams {
@@ -415,6 +416,42 @@ hipError_t launch_postings_merge_ordered(const PostingsMergeParams& P, hipStream
 hipError_t launch_postings_merge_records(const PostingsMergeParams& P, hipStream_t stream);   // the offsets' check, then the records
 hipError_t launch_postings_merge_heads(const PostingsMergeParams& P, hipStream_t stream);
 hipError_t launch_postings_merge_emit(const PostingsMergeParams& P, hipStream_t stream);      // emit, then the terms
+// The merge of POSITIONAL segments: the launches above write the three arrays as they do without positions, the launches below add post_first
+// and post_positions.  psegs [n_segs] lies beside segs (loaded by launch_postings_merge_positions_load); a POSITION PLACE pp belongs to the
+// segment s with pplace_base[s] <= pp < pplace_base[s + 1] (the capacity_positions laid end to end, n_pplaces their sum) and holds a position
+// when pp - pplace_base[s] < min(post_first_s[postings_s], capacity_positions_s).
+// Ordered route: ptable [n_segs * (n_terms + 1)], ptable[s * (n_terms + 1) + k] = where segment s's positions of term k start in the output =
+// the sum over the segments of post_first_t[term_offsets_t[k]] plus the positions of term k in the segments in front of s.  launch_..._ordered
+// runs offsets (M's table and ptable), copy (M's copy and post_first), check and pcopy in place of launch_postings_merge_ordered.
+// General route, behind launch_postings_merge_heads: ptf [n_places] = the tf of the input posting at sorted place j, inv [n_places] = the sorted
+// place of input place p (launch_..._ranks); the caller runs train_scan (flags -> scan), launch_postings_merge_emit and train_scan (ptf ->
+// pscan [n_places + 1]); then launch_..._general: first (post_first of a head = pscan at it) and pcopy (a position's rank inside its merged
+// posting = its rank in its own posting + the positions below it in the other members of its run, at most n_segs - 1 bisections).
+struct PostingsMergePosSegment {
+    const uint64_t* first;          // [capacity + 1]
+    const uint32_t* positions;      // [capacity_positions]
+    uint64_t capacity_positions;
+    uint64_t pplace_base;           // the capacity_positions in front
+};
+struct PostingsMergePosLoadArgs {
+    PostingsMergePosSegment seg[kPostingsMergeLoad];
+};
+struct PostingsMergePosParams {
+    PostingsMergeParams M;          // M.counts: [3], the third the merged positions
+    PostingsMergePosSegment* psegs; // [n_segs], scratch
+    uint64_t n_pplaces;             // the sum of the capacity_positions, < 2^32
+    uint64_t* ptable;               // ordered
+    uint32_t* ptf;                  // general
+    uint32_t* inv;
+    uint64_t* pscan;
+    uint64_t* post_first;           // [capacity_out + 1]
+    uint32_t* post_positions;       // [capacity_positions_out]
+    uint64_t capacity_positions_out;
+};
+hipError_t launch_postings_merge_positions_load(const PostingsMergePosParams& Q, const PostingsMergePosSegment* host_psegs, hipStream_t stream);
+hipError_t launch_postings_merge_positions_ordered(const PostingsMergePosParams& Q, hipStream_t stream);
+hipError_t launch_postings_merge_positions_ranks(const PostingsMergePosParams& Q, hipStream_t stream);
+hipError_t launch_postings_merge_positions_general(const PostingsMergePosParams& Q, hipStream_t stream);   // first, then pcopy
 // BM25 top-k search of a batch of queries over one postings segment (kernels_postings_search.hip).  A CANDIDATE is a (slot, posting of the slot's
 // term) pair; the slots' dfs are scanned into candidate bases, and every launch is over the capacity_slots slots, the capacity_candidates PLACES,
 // the n_queries + 1 query bounds or the n_queries * k outputs.  Scratch of the batch: per slot slot_df (u64), base (u64, [capacity_slots + 1]) and
