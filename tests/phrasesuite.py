@@ -8,7 +8,14 @@ by tests/test_postings_phrase_gpu.py; every comparison of documents, counts, fre
 
 Every array handed to a device call has exactly the size the call is told and guard words on both sides, checked after the sync with the
 inputs unwritten; the outputs are filled with SENTINEL first (the scores are handed over as their uint32 bits), so an entry the call must not
-write is seen to be left alone.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 probes."""
+write is seen to be left alone.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 probes.
+
+    python -m tests.phrasesuite --emu-hostile-high     the hostile postings at the top of the document range, in the same way
+
+check_high_documents runs the random and the ties corpus at the two bases of postingssuite.HIGH_BASES (documents on both sides of 2^31, the
+last document 0xFFFFFFFF) with two hostile postings at the upper one; check_tile_edge_ties cuts a group of n equal scores (n = T, T + 1,
+2 T + 1 probes, the largest it uses and inside the cap above) with k on both sides of T and puts a phrase's last probe on records T - 2, T - 1
+and T."""
 import random
 import sys
 
@@ -671,6 +678,111 @@ def check_host_call(seed=5):
         assert np.array_equal(packed.positions, pseg_of(docs, 4, 100, gaps).postings().positions)
 
 
+# ---- 16
+def hits_of(ref):
+    return {d for h in ref.hits for d, _, _ in h}
+
+
+def check_high_documents(name, hostile=True):
+    """the corpora of check_random and check_topk at a doc_base of postingssuite.HIGH_BASES: documents on both sides of 2^31, or the last
+    document 0xFFFFFFFF; at the upper base the two hostile postings too (hostile=False where they run in a process of their own)"""
+    batch = api.DeviceBatch(predictor())
+    docs = random_docs(7)
+    rng = random.Random(8)
+    phrases = [[rng.randrange(3) for _ in range(rng.randint(1, 5))] for _ in range(20)] + [[0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2], [2, 2, 2, 2, 2, 2, 2, 2]]
+    doc_base = postingssuite.high_base(name, len(docs))
+    last = doc_base + len(docs) - 1
+    for k in (1, 3, 50):
+        ref = check(docs, 3, doc_base, phrases, k, batch=batch, extra=3)
+    assert max(ref.match_counts) < 50 and {doc_base, last} <= hits_of(ref) and last >= 1 << 31   # (k = 50: every match is a hit)
+    assert (doc_base < 1 << 31) == (name == "2^31-3") and (last == 0xFFFFFFFF) == (name == "2^32-n")
+    same = [1, 2, 2, 0]
+    docs = [[3, 3], same, [0], same, same, [1, 2, 1, 2], same, same, [2]]
+    doc_base = postingssuite.high_base(name, len(docs))
+    for k in (2, 5):   # 2: inside the group of five equal scores, which stands on both sides of 2^31 at the lower base
+        ref = check(docs, 4, doc_base, [[1, 2], [2, 2, 0], [3, 3, 3]], k, batch=batch)
+        group = [doc_base + d for d in (1, 3, 4, 6, 7)]
+        assert [d for d, _, _ in ref.hits[1]] == group[:k] and len({bits(s) for _, s, _ in ref.hits[1]}) == 1
+        assert ref.match_counts == [6, 5, 0] and ref.hits[0][0][0] == doc_base + 5 and ref.hits[0][0][2] == 2
+    assert group[-1] >= 1 << 31 and (group[0] < 1 << 31) == (name == "2^31-3")
+    if hostile and name == "2^32-n":
+        assert run_hostile_high(batch) == N_HOSTILE_HIGH
+
+
+N_HOSTILE_HIGH = 2
+
+
+def run_hostile_high(batch=None):
+    """HOSTILE_DOCS as the documents 2^32 - 5 .. 2^32 - 1, and one posting outside them: the first of term 0's list, the anchor of the phrase
+    [0, 3], so the list's own order is sound and only the range check can see it"""
+    B = (1 << 32) - len(HOSTILE_DOCS)
+    w = [F(1.25), F(1), F(0.5), F(2)]
+    dl = [len(d) for d in HOSTILE_DOCS]
+    sound = pseg_of(HOSTILE_DOCS, 4, B, extra=2)
+    assert sound.docs[:6].tolist() == [B, B + 2, B + 1, B, B + 2, B + 4] and B + 4 == 0xFFFFFFFF
+    ref = phraseref.PhraseRef(HOSTILE_DOCS, 4, B, HOSTILE_PHRASES, w, 3)
+    assert ref.match_counts == [2, 0, 1, 2] and 0xFFFFFFFF in hits_of(ref)
+    cases = {"document_below_doc_base": B - 1, "document_at_the_end_wrapped_to_zero": (B + len(HOSTILE_DOCS) - 1 + 1) & 0xFFFFFFFF}
+    assert len(cases) == N_HOSTILE_HIGH and cases["document_at_the_end_wrapped_to_zero"] == 0
+    batch = batch or api.DeviceBatch(predictor())
+    ran = 0
+    for name, d in cases.items():
+        seg = pseg_of(HOSTILE_DOCS, 4, B, extra=2)
+        seg.docs[0] = d
+        r = run(seg, B, dl, HOSTILE_PHRASES, w, 3, cap_probes=16, batch=batch)
+        assert r.error is not None and SEG_ERROR in r.error, (name, r.error)
+        assert r.untouched(), name
+        same_as(run(sound, B, dl, HOSTILE_PHRASES, w, 3, batch=batch), ref)   # the sound ones on the same workspace
+        ran += 1
+    return ran
+
+
+# ---- 17
+def check_tile_edge_ties(n):
+    """n documents of six tokens that all hold the phrase [0, 1] once: n probes and n equal scores, a tie group over the records 0 .. n - 1 that
+    k cuts at 1, T - 1, T and n; seven of the documents hold [2, 3] twice, another score.  Then two phrases over corpora in which term 1, the
+    anchor of [0, 1], has T - 1, T and T + 1 tokens: the probes of [2, 3] start on record T - 1, T and T + 1.  (2 T + 1 probes: inside the
+    suite's cap of 3 T + 1 for a case, so no size is dropped.)"""
+    T = tile()
+    assert T <= n <= 3 * T + 1
+    batch = api.DeviceBatch(predictor())
+    doc_base = 5
+    seven = [(j * (n - 1)) // 6 for j in range(7)]   # the first and the last document among them
+    plain, twice = [0, 1, 4, 4, 4, 4], [0, 1, 2, 3, 2, 3]
+    docs = [twice if d in seven else plain for d in range(n)]
+    weights = [F(1.25), F(0.75)]
+    # what the input has to be, by the definition alone and before any device call
+    whole = phraseref.PhraseRef(docs, 5, doc_base, [[0, 1]], weights[:1], n)
+    other = phraseref.PhraseRef(docs, 5, doc_base, [[2, 3]], weights[1:], n)
+    assert len(set(seven)) == 7 and whole.counts == [n, n, 0] and other.counts == [14, 7, 0]
+    assert len({bits(s) for _, s, _ in whole.hits[0]}) == 1 and {f for _, _, f in whole.hits[0]} == {1} and {f for _, _, f in other.hits[0]} == {2}
+    assert not {bits(s) for _, s, _ in whole.hits[0]} & {bits(s) for _, s, _ in other.hits[0]}
+    pairs = []
+    for c in (T - 1, T, T + 1):
+        m = min(c, n)   # the documents that hold [0, 1]; a probe more than there are documents: the second one holds it twice
+        cdocs = [([0, 1, 0, 1, 4, 4] if d == 1 and c > n else [0, 1, 4, 4, 4, 4]) if d < m else [0, 4, 4, 4, 4, 4] for d in range(n)]
+        assert 1 not in seven
+        for d in seven:
+            cdocs[d] = cdocs[d][:2] + [2, 3, 2, 3]
+        seg = pseg_of(cdocs, 5, doc_base)
+        assert probes_of(seg, [[0, 1]]) == c and probes_of(seg, [[0, 1], [2, 3]]) == c + 14 and sum(d.count(1) for d in cdocs) == c   # the phrase changes on record c
+        pairs.append((c, cdocs, seg))
+    seg = pseg_of(docs, 5, doc_base, extra=1)
+    dl = [6] * n
+    for k in (1, T - 1, T, n):
+        r = run(seg, doc_base, dl, [[0, 1]], weights[:1], k, batch=batch)
+        same_as(r, searchsuite.cut(whole, k))   # (the reference is computed once)
+        m = min(k, n)
+        assert r.hd[:m].tolist() == list(range(doc_base, doc_base + m)) and len(set(r.hs[:m].tolist())) == 1 and set(r.hf[:m].tolist()) == {1}
+        assert r.mc.tolist() == [n] and r.counts.tolist() == [n, n, 0]
+    for c, cdocs, cseg in pairs:
+        ref = phraseref.PhraseRef(cdocs, 5, doc_base, [[0, 1], [2, 3]], weights, 9)
+        r = run(cseg, doc_base, dl, [[0, 1], [2, 3]], weights, 9, batch=batch)
+        same_as(r, ref)
+        assert int(r.counts[0]) == c + 14 and r.mc.tolist() == [min(c, n), 7] and r.hd[9:16].tolist() == [doc_base + d for d in seven]
+        assert len(set(r.hs[9:16].tolist())) == 1 and sorted(r.hd[:9].tolist()) == list(range(doc_base, doc_base + 9))
+
+
 PHRASE_TEXTS = ["火星猫", "東京特許許可局", "", "火星猫は東京だ", "まぁ良いだろう", "だだだ", "猫は東京", "１２３４５６円"]
 
 
@@ -712,12 +824,12 @@ def example_lines(docs, n_terms, doc_base, phrase, weight, k):
 
 
 def main(argv):
-    assert argv == ["--emu-hostile"], "usage: python -m tests.phrasesuite --emu-hostile"
+    assert argv in (["--emu-hostile"], ["--emu-hostile-high"]), "usage: python -m tests.phrasesuite --emu-hostile | --emu-hostile-high"
     import gc
     from tests import emu
     _lib._lib = emu.load()
     devmem.EMULATED = True
-    ran = run_hostile()
+    ran = run_hostile() if argv == ["--emu-hostile"] else run_hostile_high()
     vocabsuite._PRED.clear()
     gc.collect()   # batch and predictor destroyed: hipemu has checked the red zones of every allocation it freed
     print("ran %d cases" % ran, flush=True)

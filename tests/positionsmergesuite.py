@@ -8,7 +8,9 @@ with the plain-Python definitions, never with the device's own one-pass call.
 
 Every array handed to the call has exactly the size the call is told and guard words on both sides, checked after the sync with the inputs
 unwritten; outputs are filled with SENTINEL first, so a write behind what the call had to write is seen.  T = vpt_postings_tile (4096); no
-case has more than 3 T + 1 positions."""
+case has more than 3 T + 1 positions.  check_high_documents merges three contiguous positional segments at the two bases of
+postingssuite.HIGH_BASES (documents on both sides of 2^31, the last document 0xFFFFFFFF) on both routes, a few hundred positions, swaps two of
+them under the ordered route and runs a phrase search over the merged arrays."""
 import random
 import sys
 
@@ -336,6 +338,45 @@ def check_phrase_search_over_the_merge(seed=11):
         n = int(r.counts[0])
         merged = phrasesuite.PSeg(r.term, r.docs[:n], r.tfs[:n], r.first[:n + 1], r.ppos[:int(r.counts[2])])
         phrasesuite.same_as(phrasesuite.run(merged, 0, dl, phrases, weights, 4, batch=batch), ref)
+
+
+# ---- 4b
+def check_high_documents(name):
+    """postingsmergesuite.check_high_documents with positions: segments over [base, base + 12), [base + 12, base + 13), [base + 13, base + 37),
+    the ordered merge and the general merge of the segments in reverse against the definition (and the one pass), two segments swapped under
+    the ordered route, and the phrase search over the merged arrays against phraseref on the 37 documents"""
+    batch = api.DeviceBatch(predictor())
+    cuts = postingsmergesuite.HIGH_CUTS
+    n_terms = 4
+    docs = phrasesuite.random_docs(29, cuts[-1], n_terms, 16)
+    docs[2], docs[3] = [0, 1, 0, 1], [1, 0, 1]
+    docs[11], docs[12], docs[13] = [0, 1, 2], [1, 0, 1, 0], [0, 1, 3, 3]
+    docs[36] = [2, 0, 1]
+    base = postingssuite.high_base(name, len(docs))
+    segs = [pseg_of(docs[lo:hi], n_terms, base + lo, extra=e, extra_pos=ep) for (lo, hi), e, ep in zip(zip(cuts, cuts[1:]), (0, 2, 1), (3, 0, 5))]
+    whole = Ref.of_documents(docs, n_terms, base)
+    ref = Ref.of_segments([s.five() for s in segs], n_terms)
+    assert all(np.array_equal(a, b) for a, b in zip(ref.arrays(), whole.arrays())) and ref.n_combined == 0 and len(ref.arrays()[4]) > 200
+    zero = ref.terms[0]
+    assert {base + d for d in (2, 3, 11, 12, 13, 36)} <= set(zero) and max(zero) >= 1 << 31
+    assert (min(zero) < 1 << 31) == (name == "2^31-3") and (max(zero) == 0xFFFFFFFF) == (name == "2^32-n")
+    phrases = [[0, 1], [1, 0, 1], [3, 3], [2, 0, 1], [1], [0, 1, 2, 3]]
+    weights = phrasesuite.weights_of(docs, n_terms, phrases)
+    dl = [len(d) for d in docs]
+    pref = phraseref.PhraseRef(docs, n_terms, base, phrases, weights, 40)
+    assert {base + 2, base + 3, base + 36} <= set(pref.pf[0]) and base + 36 in pref.pf[3] and max(pref.match_counts) < 40
+    for these, ordered in ((segs, True), (segs[::-1], False), (segs, False)):
+        r = run(these, n_terms, ordered, batch=batch)
+        same_as(r, ref)
+        n = int(r.counts[0])
+        merged = phrasesuite.PSeg(r.term, r.docs[:n], r.tfs[:n], r.first[:n + 1], r.ppos[:int(r.counts[2])], extra=1)
+        for k in (3, 40):
+            phrasesuite.same_as(phrasesuite.run(merged, base, dl, phrases, weights, k, batch=batch),
+                                pref if k == 40 else phraseref.PhraseRef(docs, n_terms, base, phrases, weights, k))
+    for swapped in ([segs[1], segs[0], segs[2]], [segs[0], segs[2], segs[1]], segs[::-1]):
+        r = run(swapped, n_terms, True, batch=batch)
+        assert r.error is not None and OVERLAP_ERROR in r.error, r.error
+    same_as(run(segs, n_terms, True, batch=batch), ref)   # on the workspace that reported
 
 
 # ---- 5

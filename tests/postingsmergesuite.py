@@ -6,7 +6,9 @@ tests/test_postings_merge_gpu.py; every comparison is exact integer equality, ne
                                                          zones when the workspace goes)
 
 Every array handed to the call has exactly the size the call is told and guard words on both sides, checked after the sync with the inputs
-unwritten; outputs are filled with SENTINEL first.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 input postings."""
+unwritten; outputs are filled with SENTINEL first.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 input postings.
+check_high_documents merges three contiguous device-made segments at the two bases of postingssuite.HIGH_BASES (documents on both sides of
+2^31, the last document 0xFFFFFFFF) on both routes, a few hundred postings, and swaps two of them under the ordered route."""
 import random
 import sys
 
@@ -171,6 +173,43 @@ def check_general(seed):
         ref = postingsmergeref.MergeRef([s.triple() for s in segs], n_terms)
         assert all(np.array_equal(x, y) for x, y in zip(ref.arrays(), (term, wdocs, wtfs))) and ref.n_combined > 0
         same_as(run(segs, n_terms, False, batch=batch), term, wdocs, wtfs, ref.n_combined)
+
+
+# ---- 2b
+HIGH_CUTS = (0, 12, 13, 37)
+
+
+def high_docs(seed=33):
+    """37 documents over 7 terms; the documents on both sides of every cut of HIGH_CUTS, the two on both sides of 2^31 at the lower base and the
+    last one share terms, so neighbours in a term's merged list come from two segments and from both sides of the sign bit"""
+    docs = random_docs(random.Random(seed), 7, True, 37)
+    docs[2], docs[3] = [0, 1, 0], [1, 0]
+    docs[11], docs[12], docs[13] = [0, 2], [1, 0, 1], [0, 3, 3]
+    docs[36] = [2, 0]
+    return docs
+
+
+def check_high_documents(name):
+    """segments over [base, base + 12), [base + 12, base + 13), [base + 13, base + 37): the ordered merge, and the general merge of the same
+    segments handed over in reverse, are the definition's (and the one pass over the 37 documents); two segments swapped are the ordered
+    route's error"""
+    batch = api.DeviceBatch(predictor())
+    docs = high_docs()
+    base = postingssuite.high_base(name, len(docs))
+    segs = [device_segment(*csr(docs[lo:hi]), 7, base + lo, batch) for lo, hi in zip(HIGH_CUTS, HIGH_CUTS[1:])]
+    ref = postingsmergeref.MergeRef([s.triple() for s in segs], 7)
+    term, wdocs, wtfs, _f, _o = postingsref.Ref(*csr(docs), 7, base).arrays()
+    assert all(np.array_equal(x, y) for x, y in zip(ref.arrays(), (term, wdocs, wtfs))) and ref.n_combined == 0 and len(wdocs) > 100
+    zero = ref.terms[0]
+    assert {base + d for d in (2, 3, 11, 12, 13, 36)} <= set(zero) and max(zero) >= 1 << 31 and all(int(s.term[-1]) > 0 for s in segs)
+    assert (min(zero) < 1 << 31) == (name == "2^31-3") and (max(zero) == 0xFFFFFFFF) == (name == "2^32-n")
+    same_as(run(segs, 7, True, batch=batch), term, wdocs, wtfs, 0)
+    same_as(run(segs[::-1], 7, False, batch=batch), term, wdocs, wtfs, 0)
+    same_as(run(segs, 7, False, batch=batch), term, wdocs, wtfs, 0)
+    for swapped in ([segs[1], segs[0], segs[2]], [segs[0], segs[2], segs[1]], segs[::-1]):   # (at both bases)
+        r = run(swapped, 7, True, batch=batch)
+        assert r.error is not None and OVERLAP_ERROR in r.error, r.error
+    same_as(run(segs, 7, True, batch=batch), term, wdocs, wtfs, 0)   # on the workspace that reported
 
 
 # ---- 3

@@ -7,7 +7,8 @@ comparison is exact integer equality.
 
 Every array handed to the device call has exactly the size the call is told and guard words on both sides, checked after the sync; outputs
 are filled with SENTINEL first, so an entry the call must not write is seen to be left alone.  The sort's tile is T = vpt_postings_tile
-(4096), the key pass's vpt_vocab_tile (256); no case has more than 3 T + 1 tokens."""
+(4096), the key pass's vpt_vocab_tile (256); no case has more than 3 T + 1 tokens.  check_doc_base runs the pass at the two HIGH_BASES too: a
+batch that straddles document 2^31 and one whose last document is 0xFFFFFFFF (high_base; the search, phrase and merge suites use the same two)."""
 import os
 import random
 import re
@@ -28,6 +29,14 @@ INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
 
 def tile():
     return api.DeviceBatch.postings_tile()
+
+
+HIGH_BASES = ("2^31-3", "2^32-n")   # the names the parametrised tests carry
+
+
+def high_base(name, n_docs):
+    """the doc_base of n_docs documents that straddle the sign bit of the document word / whose last document is 0xFFFFFFFF"""
+    return {"2^31-3": (1 << 31) - 3, "2^32-n": (1 << 32) - n_docs}[name]
 
 
 class Result:
@@ -256,7 +265,7 @@ def check_doc_base():
     n = len(docs)
     base = run(toff, ids, 3)
     same_as_ref(base, postingsref.Ref(toff, ids, 3))
-    for doc_base in (7, (1 << 32) - n):
+    for doc_base in (7, high_base("2^31-3", n), (1 << 32) - n):
         r = run(toff, ids, 3, doc_base)
         same_as_ref(r, postingsref.Ref(toff, ids, 3, doc_base))
         k = int(r.counts[0])

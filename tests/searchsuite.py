@@ -8,7 +8,13 @@ device call.
 
 Every array handed to the device call has exactly the size the call is told and guard words on both sides, checked after the sync with the
 inputs unwritten; the outputs are filled with SENTINEL first (the scores are handed over as their uint32 bits), so an entry the call must not
-write is seen to be left alone.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 candidates."""
+write is seen to be left alone.  T = vpt_postings_tile (4096); no case has more than 3 T + 1 candidates.
+
+    python -m tests.searchsuite --emu-hostile-high     the hostile postings at the top of the document range, in the same way
+
+check_high_documents runs the random and the ties corpus at the two bases of postingssuite.HIGH_BASES (documents on both sides of 2^31, the
+last document 0xFFFFFFFF) with two hostile postings at the upper one; check_tile_edge_ties cuts a group of n equal scores (n = T, T + 1,
+2 T + 1 candidates, the largest it uses) with k on both sides of T and puts a query's last candidate on records T - 2, T - 1 and T."""
 import math
 import random
 import sys
@@ -439,6 +445,140 @@ def check_host_call(seed=5):
     assert post.search([], 4, dl, 100, predictor=pred)[0] == []
 
 
+# ---- 14
+def hits_of(ref):
+    return {d for h in ref.hits for d, _ in h}
+
+
+def check_high_documents(name, hostile=True):
+    """the random input and the ties corpus at a doc_base of postingssuite.HIGH_BASES: documents on both sides of 2^31, or the last document
+    0xFFFFFFFF; at the upper base the two hostile postings too (hostile=False where they run in a process of their own)"""
+    batch = api.DeviceBatch(predictor())
+    doc_base = postingssuite.high_base(name, 37)
+    seg, dl, queries = random_input(3, doc_base, batch)
+    last = doc_base + 36
+    for k in (1, 3, 64):
+        ref = check(seg, doc_base, dl, queries, k, batch=batch)
+    assert max(ref.match_counts) < 64 and {doc_base, last} <= hits_of(ref) and last >= 1 << 31   # (k = 64: every match is a hit)
+    assert (doc_base < 1 << 31) == (name == "2^31-3") and (last == 0xFFFFFFFF) == (name == "2^32-n")
+    same = [1, 2, 2, 5]
+    docs = [[3, 3], same, [0], same, same, [1, 1, 1, 1], same, same, [2]]
+    toff, ids = csr(docs)
+    doc_base = postingssuite.high_base(name, len(docs))
+    tseg = postingsmergesuite.device_segment(toff, ids, 6, doc_base, batch)
+    tdl = np.diff(toff.astype(np.int64)).astype(np.uint32)
+    tqueries = with_idf(tseg, len(docs), [[1, 2], [5], [2, 1, 5]])
+    for k in (2, 5):   # 2: inside the group of five equal scores, which stands on both sides of 2^31 at the lower base
+        ref = check(tseg, doc_base, tdl, tqueries, k, batch=batch)
+        group = [doc_base + d for d in (1, 3, 4, 6, 7)]
+        assert [d for d, _ in ref.hits[1]] == group[:k] and len({searchref.bits(s) for _, s in ref.hits[1]}) == 1 and ref.match_counts[1] == 5
+    # (k = 5: the whole group is hits; the last document matches and is below the best five)
+    assert group[-1] in hits_of(ref) and group[-1] >= 1 << 31 and (group[0] < 1 << 31) == (name == "2^31-3") and doc_base + 8 in ref.scores[0]
+    if hostile and name == "2^32-n":
+        assert run_hostile_high(batch) == N_HOSTILE_HIGH
+
+
+HIGH_HOSTILE_BASE = (1 << 32) - 5
+
+
+def high_hostile_cases():
+    """hostile_cases' segment on the documents 2^32 - 5 .. 2^32 - 1; name -> the segment with one posting outside them"""
+    B = HIGH_HOSTILE_BASE
+
+    def base():
+        return seg_of({0: {B + 1: 1, B + 3: 2}, 1: {B + 2: 1}, 3: {B: 1, B + 1: 1, B + 4: 4}}, 4, extra=2)   # term 0 2 3 3 6; cap 8
+    cases = {}
+
+    def seg_case(name, fn):
+        s = base()
+        fn(s)
+        cases[name] = s
+    # both are the first posting of term 0's list, so the list's own order is sound: only the range check can see them
+    seg_case("document_below_doc_base", lambda s: s.docs.__setitem__(0, B - 1))
+    seg_case("document_at_the_end_wrapped_to_zero", lambda s: s.docs.__setitem__(0, (B + 5 - 1 + 1) & 0xFFFFFFFF))
+    return base(), cases
+
+
+N_HOSTILE_HIGH = 2
+
+
+def run_hostile_high(batch=None):
+    B = HIGH_HOSTILE_BASE
+    sound_seg, cases = high_hostile_cases()
+    assert len(cases) == N_HOSTILE_HIGH and cases["document_at_the_end_wrapped_to_zero"].docs[0] == 0
+    _s, sound, _c = hostile_cases()
+    dl = [3, 5, 2, 9, 4]
+    batch = batch or api.DeviceBatch(predictor())
+    ran = 0
+    for name, seg in cases.items():
+        r = run(seg, B, dl, sound, 3, cap_cand=16, batch=batch)
+        assert r.error is not None and SEG_ERROR in r.error, (name, r.error)
+        assert r.untouched(), name
+        ref = check(sound_seg, B, dl, sound, 3, batch=batch)   # the sound ones on the same workspace
+        assert 0xFFFFFFFF in hits_of(ref)
+        ran += 1
+    return ran
+
+
+# ---- 15
+def cut(ref, k):
+    """the definition for a smaller k: the same ranking, its first k of every query (the reference is computed once and left as it is)"""
+    import copy
+    out = copy.copy(ref)
+    out.k, out.hits = k, [h[:k] for h in ref.hits]
+    return out
+
+
+def candidate_records(seg, queries):
+    """the candidates in the order the first sort leaves them, by the definition alone: (query, document, slot)"""
+    out = []
+    for q, query in enumerate(queries):
+        for s, (t, _w) in enumerate(query):
+            if 0 <= t < seg.n_terms:
+                out += [(q, int(seg.docs[at]), s) for at in range(int(seg.term[t]), int(seg.term[t + 1]))]
+    return sorted(out)
+
+
+def check_tile_edge_ties(n):
+    """n documents of one length that all hold term 0 once: one query of that slot has n equal scores, a tie group over the records 0 .. n - 1
+    that k cuts at 1, T - 1, T and n.  Then two queries: the first has T - 1, T and T + 1 candidates (terms 2, 3 and 4 add up to them), so the
+    second one's group of 7 equal scores (term 1, another tf) starts on record T - 1, T and T + 1."""
+    T = tile()
+    assert n >= T
+    batch = api.DeviceBatch(predictor())
+    doc_base = 5
+    seven = [doc_base + (j * (n - 1)) // 6 for j in range(7)]   # the first and the last document among them
+    terms = {0: {doc_base + d: 1 for d in range(n)}, 1: {d: 3 for d in seven}, 2: {doc_base + d: 1 for d in range(T - 1)}, 3: {doc_base + T - 1: 1},
+             4: {doc_base: 1}}
+    seg = seg_of(terms, 5, extra=1)
+    dl = [4] * n
+    w = [idf_of(n, len(terms[t])) for t in range(5)]
+    # what the input has to be, by the definition alone and before any device call
+    whole = searchref.SearchRef(seg.term, seg.docs, seg.tfs, doc_base, dl, [[(0, w[0])]], n)
+    assert whole.match_counts == [n] and len(whole.hits[0]) == n and len({searchref.bits(s) for _, s in whole.hits[0]}) == 1
+    assert len(set(seven)) == 7 and len({searchref.bits(searchref.contribution(w[0], tf, 4, 1.2, 0.75, whole.avgdl)) for tf in (1, 3)}) == 2
+    pairs = []
+    for c, slots in ((T - 1, [2]), (T, [2, 3]), (T + 1, [2, 3, 4])):
+        queries = [[(t, w[2]) for t in slots], [(1, w[1])]]   # (one weight for the three terms: their documents tie)
+        records = candidate_records(seg, queries)
+        assert [r[0] for r in records] == [0] * c + [1] * 7, c   # the query changes on record c
+        pairs.append((c, queries))
+    for k in (1, T - 1, T, n):
+        r = run(seg, doc_base, dl, [[(0, w[0])]], k, batch=batch)
+        same_as(r, cut(whole, k))
+        m = min(k, n)
+        assert r.hd[:m].tolist() == list(range(doc_base, doc_base + m)) and len(set(r.hs[:m].tolist())) == 1
+        assert r.mc.tolist() == [n] and r.counts.tolist() == [n, n, 0]
+    for c, queries in pairs:
+        ref = searchref.SearchRef(seg.term, seg.docs, seg.tfs, doc_base, dl, queries, 9)
+        r = run(seg, doc_base, dl, queries, 9, batch=batch)
+        same_as(r, ref)
+        assert int(r.counts[0]) == c + 7 and r.mc.tolist() == [min(c, T), 7] and r.hd[9:16].tolist() == seven
+        # (T + 1 candidates: the first document holds two of them, so it leads with a score of its own)
+        assert len(set(r.hs[:9].tolist())) == (2 if c == T + 1 else 1) and len(set(r.hs[1:9].tolist())) == 1 and len(set(r.hs[9:16].tolist())) == 1
+        assert r.hd[:9].tolist() == list(range(doc_base, doc_base + 9))
+
+
 def example_lines(post, dl, doc_base, queries, k):
     """the lines examples/token_stream.cpp --postings --search prints for these hits"""
     ref = searchref.SearchRef(post.term_offsets, post.docs, post.tfs, doc_base, dl, queries, k)
@@ -446,12 +586,12 @@ def example_lines(post, dl, doc_base, queries, k):
 
 
 def main(argv):
-    assert argv == ["--emu-hostile"], "usage: python -m tests.searchsuite --emu-hostile"
+    assert argv in (["--emu-hostile"], ["--emu-hostile-high"]), "usage: python -m tests.searchsuite --emu-hostile | --emu-hostile-high"
     import gc
     from tests import emu
     _lib._lib = emu.load()
     devmem.EMULATED = True
-    ran = run_hostile()
+    ran = run_hostile() if argv == ["--emu-hostile"] else run_hostile_high()
     vocabsuite._PRED.clear()
     gc.collect()   # batch and predictor destroyed: hipemu has checked the red zones of every allocation it freed
     print("ran %d cases" % ran, flush=True)

@@ -36,6 +36,11 @@ def test_general_merge_of_documents_and_of_tokens_dealt_at_random():
     postingsmergesuite.check_general(21)
 
 
+@pytest.mark.parametrize("base", postingsmergesuite.postingssuite.HIGH_BASES)
+def test_segments_on_both_sides_of_2_31_and_up_to_the_last_document_word_on_both_routes(base):
+    postingsmergesuite.check_high_documents(base)
+
+
 def test_broken_promise_is_an_error_at_sync_and_touching_ranges_are_not():
     postingsmergesuite.check_broken_promise()
 

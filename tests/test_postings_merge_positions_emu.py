@@ -37,6 +37,11 @@ def test_general_merge_of_tokens_dealt_at_random_equals_one_pass():
     positionsmergesuite.check_general()
 
 
+@pytest.mark.parametrize("base", positionsmergesuite.postingssuite.HIGH_BASES)
+def test_segments_on_both_sides_of_2_31_and_up_to_the_last_document_word_merged_and_searched(base):
+    positionsmergesuite.check_high_documents(base)
+
+
 def test_position_places_on_the_workgroup_edges_and_a_segment_boundary_inside_a_wave():
     positionsmergesuite.check_position_places()
 

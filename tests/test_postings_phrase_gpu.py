@@ -73,6 +73,16 @@ def test_hostile_input_is_an_error_at_sync_and_touches_nothing_outside():
     assert phrasesuite.run_hostile() == phrasesuite.N_HOSTILE
 
 
+@pytest.mark.parametrize("base", phrasesuite.postingssuite.HIGH_BASES)
+def test_documents_on_both_sides_of_2_31_and_up_to_the_last_document_word(base):
+    phrasesuite.check_high_documents(base)   # (at the upper base with the two hostile postings, which have run on the emulator)
+
+
+@pytest.mark.parametrize("n", ["T", "T+1", "2T+1"])
+def test_k_cuts_a_tie_group_on_the_tile_edges_and_a_phrase_ends_on_them(n):
+    phrasesuite.check_tile_edge_ties(phrasesuite.postingssuite.token_count(n))
+
+
 def test_two_runs_and_a_second_workspace_give_identical_bytes():
     phrasesuite.check_determinism()
 

@@ -65,13 +65,30 @@ def test_errors_at_the_call():
     searchsuite.check_errors()
 
 
-def test_hostile_input_is_an_error_at_sync_and_touches_nothing_outside():
-    r = subprocess.run([sys.executable, "-m", "tests.searchsuite", "--emu-hostile"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600)
+def hostile_child(flag, n_cases):
+    r = subprocess.run([sys.executable, "-m", "tests.searchsuite", flag], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     out = r.stdout.decode()
     print(out, r.stderr.decode()[-3000:])
     assert r.returncode == 0, (out[-500:], r.stderr.decode()[-2000:])
-    assert out.strip().endswith("ran %d cases" % searchsuite.N_HOSTILE)
+    assert out.strip().endswith("ran %d cases" % n_cases)
+
+
+def test_hostile_input_is_an_error_at_sync_and_touches_nothing_outside():
+    hostile_child("--emu-hostile", searchsuite.N_HOSTILE)
+
+
+@pytest.mark.parametrize("base", searchsuite.postingssuite.HIGH_BASES)
+def test_documents_on_both_sides_of_2_31_and_up_to_the_last_document_word(base):
+    searchsuite.check_high_documents(base, hostile=False)
+
+
+def test_hostile_postings_outside_a_range_that_ends_at_the_last_document_word():
+    hostile_child("--emu-hostile-high", searchsuite.N_HOSTILE_HIGH)
+
+
+@pytest.mark.parametrize("n", ["T", "T+1", "2T+1"])
+def test_k_cuts_a_tie_group_on_the_tile_edges_and_a_query_ends_on_them(n):
+    searchsuite.check_tile_edge_ties(searchsuite.postingssuite.token_count(n))
 
 
 def test_two_runs_and_a_second_workspace_give_identical_bytes():
