@@ -22,6 +22,9 @@
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --phrase "QUERY" [--top K] < documents.txt
 // With --phrase: the documents are indexed with positions, the query text is ONE phrase -- its tokens at consecutive positions, in order -- and
 // the K best documents that hold it are found on the device; the lines of --search, plus <TAB> the phrase's occurrences in the document.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --boolean "QUERY" [--top K] < documents.txt
+// With --boolean: the query text is split on spaces into clauses, +clause is required, -clause is forbidden, any other is wanted; every token
+// of a clause takes the clause's occur (a clause of several tokens is not a phrase); the lines of --search.
 // With --segment-docs N the positional segments of N documents each are merged on the device with their position lists (the same lines come
 // out; stderr tells "segments <TAB> n <TAB> postings <TAB> n <TAB> positions <TAB> n").
 #include <cstdlib>
@@ -85,11 +88,13 @@ int main(int argc, char** argv) {
             int n_args = argc;
             const char* query = nullptr;
             const char* phrase = nullptr;
+            const char* boolean = nullptr;
             uint32_t top = 10;
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }   // (behind the query, too)
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
             else if (n_args > 6 && std::strcmp(argv[n_args - 2], "--phrase") == 0) { phrase = argv[n_args - 1]; n_args -= 2; }
+            else if (n_args > 6 && std::strcmp(argv[n_args - 2], "--boolean") == 0) { boolean = argv[n_args - 1]; n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }
             const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
             vaporetto_hip::Postings post;
@@ -119,8 +124,9 @@ int main(int argc, char** argv) {
             } else {
                 post = plain.index(docs, vocab, doc_base);
             }
-            if (query) {
-                const auto found = plain.search(post, vocab, {std::string(query)}, plain.doc_lens(docs, vocab), doc_base, top);
+            if (query || boolean) {
+                const auto found = query ? plain.search(post, vocab, {std::string(query)}, plain.doc_lens(docs, vocab), doc_base, top)
+                                         : plain.boolean_search(post, vocab, {std::string(boolean)}, plain.doc_lens(docs, vocab), doc_base, top);
                 for (const vaporetto_hip::Postings::Hit& h : found.hits[0]) {
                     uint32_t bits;
                     std::memcpy(&bits, &h.score, 4);

@@ -767,6 +767,60 @@ vpt_status vpt_postings_search(const vpt_predictor *p, const uint64_t *term_offs
 vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float *idf_out);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Boolean queries on the device: MUST / SHOULD / MUST_NOT slots in the BM25 search      (tantivy's BooleanQuery of Occur::{Must, Should, MustNot}
+ *                                                                                          clauses over term queries: what `+a -b c` parses to)
+ *
+ * vpt_postings_boolean_search_device: every argument of vpt_postings_search_device with the same meaning, and d_query_occurs uint8
+ *   [capacity_slots] behind d_query_weights: VPT_OCCUR_SHOULD, VPT_OCCUR_MUST or VPT_OCCUR_MUST_NOT per slot.
+ *   A slot HAS a document when its term is inside [0, n_terms) and the term's list holds a posting for it.  A document MATCHES query q when
+ *   every MUST slot of q has it, no MUST_NOT slot of q has it and, if q has no MUST slot, at least one SHOULD slot has it.  So: a query with
+ *   no slots matches nothing; a query with only MUST_NOT slots matches nothing (as in tantivy); a MUST slot whose term is out of range or has
+ *   df 0 leaves the query with no match; an out-of-range SHOULD or MUST_NOT slot is ignored; every out-of-range slot adds 1 to d_counts[2].  A
+ *   repeated term is one slot per repetition: the same term as MUST and as MUST_NOT matches nothing, a term twice as MUST is scored twice.
+ *   Score: c is vpt_postings_search_device's, computed for every MUST or SHOULD slot that has the document; the c values are added in slot
+ *   order, left to right, starting from the first c, each add rounded to binary32.  MUST_NOT slots contribute nothing; their weights are
+ *   checked like the rest.  A call whose slots are all SHOULD gives the documents, counts and score bits of vpt_postings_search_device.
+ *   Outputs, their order (score descending, then document ascending), k, "entries at or behind the hit count are not written" and
+ *   determinism: as in vpt_postings_search_device.  d_counts[1] = the matches of all queries, d_counts[2] = the skipped slots.
+ *   PLACES: a query's ANCHOR is its first MUST slot of the smallest df.  A query with an anchor needs the anchor's df places; a query without a
+ *   MUST slot needs the sum of the dfs of its in-range SHOULD slots; a query with a MUST slot out of range or of df 0 needs none.
+ *   d_counts[0] = the places of all queries; capacity_candidates bounds them ("InvalidArgumentError: capacity_candidates: smaller than the
+ *   number of candidates" at the sync, d_counts[0] then holds the number needed).  The sum of the dfs of all in-range slots always suffices.
+ *   Launches (kernels_postings_boolean.hip), none sized from a value read back: queries (a lane per query: the occurs, the anchor, whether a
+ *   MUST_NOT slot is there), slots (the OR search's checks; a slot's places), the trainer's scan, expand (a lane per place: its posting with
+ *   the OR search's checks; in an anchored query every other in-range slot of the query is bisected in its list -- at most 64 steps inside
+ *   the term's two bounds, which are clamped to capacity_postings -- for the anchor's document: a MUST slot without it or a MUST_NOT slot
+ *   with it drops the place, the others add their c in slot order; in a query without an anchor only its MUST_NOT slots are bisected, and
+ *   none when it has none); from the first sort on, the launches of vpt_postings_search_device as they stand.  No atomic decides a value;
+ *   every loop is bounded by 1024 slots or 64 halvings.
+ *   Scratch of the workspace: the OR search's (20 bytes per slot of capacity_slots, 44 bytes per place of capacity_candidates, 8 bytes per
+ *   query, the histograms) and 12 bytes more per query (the anchor, a flag word).
+ *   At the call, VPT_INVALID_ARGUMENT: vpt_postings_search_device's list, d_query_occurs NULL included.
+ *   At the sync, VPT_INVALID_ARGUMENT: vpt_postings_search_device's list and "InvalidArgumentError: occurs: a value above 2"; after any of
+ *   these the four outputs are as they were before the call.  Only a list that deals out places (the anchor's, or a SHOULD slot's in a query
+ *   without an anchor) is checked for ascent, tf and document range posting by posting; of a bisected list the two bounds are checked
+ *   (every in-range slot's, as in the OR search), and a posting found there with tf 0 is "segment: term_offsets or postings are not a
+ *   segment's".  A bisected list that does not ascend is not reported: the bisection ends inside the list's bounds on some posting, and the
+ *   answer is that posting's.  Whatever the arrays hold, nothing is read outside term_offsets[0 .. n_terms], [0, capacity_postings),
+ *   doc_lens[0 .. n_documents) and the query arrays' stated sizes, and nothing is written outside the four outputs' stated sizes, d_counts [3]
+ *   and the workspace.
+ * vpt_postings_boolean_search: the same over HOST arrays, as vpt_postings_search is; the places are counted on the host by the rule above. */
+enum { VPT_OCCUR_SHOULD = 0, VPT_OCCUR_MUST = 1, VPT_OCCUR_MUST_NOT = 2 };
+vpt_status vpt_postings_boolean_search_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets, const uint32_t *d_post_docs,
+                                              const uint32_t *d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base,
+                                              uint64_t n_documents, const uint32_t *d_doc_lens, const uint64_t *d_query_offsets,
+                                              const int32_t *d_query_terms, const float *d_query_weights, const uint8_t *d_query_occurs,
+                                              uint32_t n_queries, uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                              uint64_t capacity_candidates, uint32_t *d_hit_docs, float *d_hit_scores, uint32_t *d_hit_counts,
+                                              uint64_t *d_match_counts, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_boolean_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs, const uint32_t *post_tfs,
+                                       uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint32_t *doc_lens,
+                                       const uint64_t *query_offsets, const int32_t *query_terms, const float *query_weights,
+                                       const uint8_t *query_occurs, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                       uint32_t *hit_docs_out, float *hit_scores_out, uint32_t *hit_counts_out, uint64_t *match_counts_out,
+                                       uint64_t *counts_out);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Phrase queries on the device: the positions of a segment, exact-phrase BM25 top-k      (the adapter indexes WithFreqsAndPositions, and positions
  *                                                 serve phrase queries: what tantivy's query parser makes of a query text of several tokens)
  *

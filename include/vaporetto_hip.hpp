@@ -489,6 +489,14 @@ struct Postings {
     SearchResult search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& queries, const std::vector<uint32_t>& doc_lens,
                         uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
                         const std::vector<std::vector<float>>* weights = nullptr) const;
+    // BM25 top-k of every boolean query over this segment (vpt_postings_boolean_search; the definition is in vaporetto_hip.h).  A slot is a
+    // term and an occur (VPT_OCCUR_SHOULD / VPT_OCCUR_MUST / VPT_OCCUR_MUST_NOT): a document matches when every MUST slot has it, no MUST_NOT
+    // slot has it and, without a MUST slot, some SHOULD slot has it.  weights: shaped as queries, or nullptr for vpt_okapi_idf(n_documents,
+    // df(term)) per MUST / SHOULD slot and 0 per MUST_NOT slot.  counts[0] of the result: the places.
+    struct Clause { int32_t term; uint8_t occur; };
+    SearchResult boolean_search(const Predictor& predictor, const std::vector<std::vector<Clause>>& queries, const std::vector<uint32_t>& doc_lens,
+                                uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
+                                const std::vector<std::vector<float>>* weights = nullptr) const;
     // Exact-phrase BM25 top-k of every phrase over this POSITIONAL segment (vpt_postings_phrase_search; the definition is in vaporetto_hip.h).
     // phrases: term ids, each vector ONE phrase, its ids at consecutive positions in order; an id outside [0, n_terms) makes it match nothing.
     // weights: one per phrase, or nullptr for tantivy's phrase weight (the float sum, in slot order, of vpt_okapi_idf over the slots).
@@ -582,6 +590,49 @@ inline Postings::SearchResult Postings::search(const Predictor& predictor, const
     detail::check(vpt_postings_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), uint32_t(n_terms()), doc_base, doc_lens.size(),
                                       doc_lens.data(), qoff.data(), terms.data(), w.data(), uint32_t(queries.size()), k1, b, avgdl, k, hd.data(), hs.data(),
                                       hc.data(), out.match_counts.data(), out.counts));
+    out.hits.resize(queries.size());
+    for (size_t q = 0; q < queries.size(); ++q)
+        for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(Hit{hd[q * size_t(k) + j], hs[q * size_t(k) + j]});
+    return out;
+}
+
+inline Postings::SearchResult Postings::boolean_search(const Predictor& predictor, const std::vector<std::vector<Clause>>& queries,
+                                                       const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
+                                                       const std::vector<std::vector<float>>* weights) const {
+    SearchResult out;
+    if (queries.empty()) return out;
+    if (term_offsets.empty() || doc_lens.empty() || (weights && weights->size() != queries.size()))
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: boolean_search: the arrays do not belong together");
+    double total = 0;
+    for (uint32_t l : doc_lens) total += double(l);
+    const float avgdl = float(total / double(doc_lens.size()));
+    std::vector<uint64_t> qoff(1, 0);
+    std::vector<int32_t> terms;
+    std::vector<float> w;
+    std::vector<uint8_t> occurs;
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (weights && (*weights)[q].size() != queries[q].size())
+            throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: weights: not shaped as the queries");
+        for (size_t j = 0; j < queries[q].size(); ++j) {
+            const int32_t t = queries[q][j].term;
+            float x = 0.0f;
+            if (weights) x = (*weights)[q][j];
+            else if (queries[q][j].occur != VPT_OCCUR_MUST_NOT && t >= 0 && size_t(t) < n_terms())
+                detail::check(vpt_okapi_idf(doc_lens.size(), df(size_t(t)), &x));
+            terms.push_back(t);
+            w.push_back(x);
+            occurs.push_back(queries[q][j].occur);
+        }
+        qoff.push_back(terms.size());
+    }
+    terms.push_back(0); w.push_back(0.0f); occurs.push_back(0);   // (data() of an empty vector may be NULL)
+    const size_t n_out = queries.size() * size_t(k) + 1;
+    std::vector<uint32_t> hd(n_out), hc(queries.size());
+    std::vector<float> hs(n_out);
+    out.match_counts.assign(queries.size(), 0);
+    detail::check(vpt_postings_boolean_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), uint32_t(n_terms()), doc_base, doc_lens.size(),
+                                              doc_lens.data(), qoff.data(), terms.data(), w.data(), occurs.data(), uint32_t(queries.size()), k1, b, avgdl, k,
+                                              hd.data(), hs.data(), hc.data(), out.match_counts.data(), out.counts));
     out.hits.resize(queries.size());
     for (size_t q = 0; q < queries.size(); ++q)
         for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(Hit{hd[q * size_t(k) + j], hs[q * size_t(k) + j]});
@@ -851,6 +902,38 @@ public:
         std::vector<std::vector<int32_t>> queries(texts.size());
         for (size_t i = 0; i < texts.size(); ++i) queries[i].assign(enc.second.begin() + enc.first[i], enc.second.begin() + enc.first[i + 1]);
         return postings.search(predictor_, queries, doc_lens, doc_base, k, k1, b);
+    }
+
+    // BM25 top-k of boolean query TEXTS over `postings`.  A text is split on ASCII spaces into clauses: one that starts with `+` is MUST, one
+    // that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are, and every token
+    // of it is a slot of the clause's occur; an empty clause adds nothing.  A clause of several tokens is NOT made a phrase here (unlike
+    // tantivy's query parser).  Then Postings::boolean_search with the idf weights.
+    Postings::SearchResult boolean_search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
+                                          const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f,
+                                          float b = 0.75f, bool normalize = true) const {
+        std::vector<std::string> clauses;
+        std::vector<std::pair<size_t, uint8_t>> owner;
+        for (size_t i = 0; i < texts.size(); ++i) {
+            const std::string& text = texts[i];
+            for (size_t a = 0; a <= text.size();) {
+                size_t e = text.find(' ', a);
+                if (e == std::string::npos) e = text.size();
+                uint8_t occur = VPT_OCCUR_SHOULD;
+                if (a < e && (text[a] == '+' || text[a] == '-')) occur = text[a++] == '+' ? VPT_OCCUR_MUST : VPT_OCCUR_MUST_NOT;
+                if (a < e) {
+                    clauses.push_back(text.substr(a, e - a));
+                    owner.emplace_back(i, occur);
+                }
+                a = e + 1;
+            }
+        }
+        std::vector<std::vector<Postings::Clause>> queries(texts.size());
+        if (!clauses.empty()) {
+            const auto enc = encode(clauses, vocab, normalize);
+            for (size_t c = 0; c < clauses.size(); ++c)
+                for (uint64_t t = enc.first[c]; t < enc.first[c + 1]; ++t) queries[owner[c].first].push_back(Postings::Clause{enc.second[t], owner[c].second});
+        }
+        return postings.boolean_search(predictor_, queries, doc_lens, doc_base, k, k1, b);
     }
 
     // Exact-phrase BM25 top-k of query TEXTS over a positional `postings` (index with positions): each text is tokenised and encoded as

@@ -25,6 +25,11 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       segment (kernels_postings_search.hip) by device events, beside two yardsticks of the same run: the general merge over one segment of as
       many input places as the search has candidates, and a device-to-device copy of half of 8 bytes a candidate plus 8 bytes a hit (a copy of
       B bytes moves B in and B out).  Q is halved until the candidates are at most --search-max-candidates (profiles/postings_search_bench.json).
+  --boolean Q,L,K: with --postings, three settings over the one-pass segment (kernels_postings_boolean.hip) by device events, each beside the OR
+      search of the same run over the same slots and a device-to-device copy of half of 8 bytes a place plus 8 bytes a hit: (a) Q queries of L
+      terms drawn by count as --search draws them, all MUST; (b) Q all-MUST queries of L consecutive tokens of a random document as --phrase
+      draws them, so each matches at least once (every_query_matches); (c) the queries of (a) as all-SHOULD (equals_or_search: the OR search's
+      bytes).  Places against candidates, matches, times and ratios (profiles/postings_boolean_bench.json).
   --phrase Q,L,K: with --postings, Q phrases of L consecutive tokens of random documents (windows whose tokens all have a vocabulary entry, so
       every phrase occurs at least once), top K, over the one-pass segment with its position lists (kernels_postings_phrase.hip) by device
       events, beside yardsticks of the same process: the OR search of --search (the parent's kernels) over the same queries, every token a slot
@@ -421,6 +426,106 @@ def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host
     return out
 
 
+def boolean_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_term, d_pdocs, d_ptfs, n_post):
+    """--boolean Q,L,K over the one-pass segment; see the module's docstring"""
+    from vaporetto_amd import api
+    Q, L, K = (int(x) for x in spec.split(","))
+    term = d_term.cpu().numpy().astype(np.int64)
+    df = np.diff(term)
+    tfs = d_ptfs[:n_post].cpu().numpy().astype(np.int64)
+    count = np.add.reduceat(np.concatenate([tfs, [0]]), np.minimum(term[:-1], n_post)) * (df > 0)
+    toff = dev_off.astype(np.int64)
+    dl = np.diff(toff)
+    rng = np.random.default_rng(7)
+    while True:   # (a), (c): the terms --search draws
+        drawn = rng.choice(n_terms, size=Q * L, p=count / count.sum()).astype(np.int32)
+        if int(df[drawn].sum()) <= args.search_max_candidates or Q == 1:
+            break
+        Q //= 2
+    known = (host_ids >= 0) & (host_ids < n_terms)
+    run = np.concatenate([[0], np.cumsum(~known)])   # a window [a, a + L) is all known when run[a + L] == run[a]
+    long_docs = np.flatnonzero(dl >= L)
+    windows = []
+    for _ in range(64 * Q):   # (b): the windows --phrase draws
+        if len(windows) == Q or len(long_docs) == 0:
+            break
+        d = int(long_docs[rng.integers(len(long_docs))])
+        a = int(toff[d]) + int(rng.integers(int(dl[d]) - L + 1))
+        if run[a + L] == run[a]:
+            windows.append(host_ids[a:a + L].astype(np.int32))
+    while windows and int(df[np.concatenate(windows)].sum()) > args.search_max_candidates and len(windows) > 1:
+        windows = windows[:len(windows) // 2]
+    avgdl = float(np.float32(float(dl.sum()) / S))
+    d_dl = torch.from_numpy(dl.astype(np.int32)).to(dev)
+    rows = []
+    settings = [("a_must_by_count", drawn, Q, 1), ("c_should_by_count", drawn, Q, 0)]
+    if windows:
+        settings.insert(1, ("b_must_windows", np.concatenate(windows), len(windows), 1))
+    for name, terms, n_q, occur in settings:
+        n_cand = int(df[terms].sum())
+        per_q = df[terms].reshape(n_q, L)
+        n_places = int(per_q.min(axis=1).sum()) if occur else n_cand
+        if max(n_cand, n_places) >= 1 << 32:
+            raise SystemExit("--boolean: %d candidates" % n_cand)
+        idf = {int(t): float(api.bm25_idf(S, int(df[t]))) for t in set(terms.tolist())}
+        d_qoff = torch.from_numpy(np.arange(0, n_q * L + 1, L, dtype=np.int64)).to(dev)
+        d_qt = torch.from_numpy(terms).to(dev)
+        d_qw = torch.from_numpy(np.array([idf[int(t)] for t in terms], np.float32)).to(dev)
+        d_qo = torch.full((n_q * L,), occur, dtype=torch.uint8, device=dev)
+        d_hd, d_hs = torch.zeros(n_q * K, dtype=torch.int32, device=dev), torch.zeros(n_q * K, dtype=torch.float32, device=dev)
+        d_hc, d_mc, d_cnt = torch.zeros(n_q, dtype=torch.int32, device=dev), torch.zeros(n_q, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev)
+
+        def boolean():
+            batch.boolean_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, 0, S, d_dl.data_ptr(), d_qoff.data_ptr(),
+                                          d_qt.data_ptr(), d_qw.data_ptr(), d_qo.data_ptr(), n_q, n_q * L, 1.2, 0.75, avgdl, K, n_places, d_hd.data_ptr(),
+                                          d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+
+        def or_search():
+            batch.search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, 0, S, d_dl.data_ptr(), d_qoff.data_ptr(), d_qt.data_ptr(),
+                                  d_qw.data_ptr(), n_q, n_q * L, 1.2, 0.75, avgdl, K, n_cand, d_hd.data_ptr(), d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(),
+                                  d_cnt.data_ptr(), stream)
+        out = {"setting": name, "spec": spec, "queries": n_q, "slots_per_query": L, "k": K, "n_terms": n_terms, "documents": S, "postings": n_post}
+        or_search()
+        batch.sync()
+        cnt = d_cnt.cpu().numpy()
+        or_hits = (d_hd.clone(), d_hs.clone(), d_hc.clone(), d_mc.clone())
+        out.update({"or_candidates": int(cnt[0]), "or_matches": int(cnt[1])})
+        boolean()
+        batch.sync()
+        cnt = d_cnt.cpu().numpy()
+        matches = int(cnt[1])
+        out.update({"places": int(cnt[0]), "matches": matches, "skipped": int(cnt[2]), "places_equal_host_count": bool(int(cnt[0]) == n_places),
+                    "places_over_candidates": round(int(cnt[0]) / max(n_cand, 1), 5), "hit_counts_sum": int(d_hc.to(torch.int64).sum().item())})
+        if name == "b_must_windows":
+            out["every_query_matches"] = bool(int(d_mc.min().item()) >= 1)
+        if occur == 0:   # all SHOULD: the OR search's bytes
+            out["equals_or_search"] = bool(all(torch.equal(x, y) for x, y in zip(or_hits, (d_hd, d_hs, d_hc, d_mc))))
+        copy_bytes = (8 * int(cnt[0]) + 8 * matches) // 2
+        a_buf, b_buf = torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev), torch.empty(copy_bytes + 8, dtype=torch.uint8, device=dev)
+        out["copy_bytes"] = copy_bytes
+
+        def floor():
+            b_buf.copy_(a_buf)
+        for fname, fn in (("boolean", boolean), ("or_search", or_search), ("floor", floor)):
+            fn()
+            batch.sync()
+            r = []
+            for _ in range(args.rounds):
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                r.append(med([a.elapsed_time(b) for a, b in ev]))
+            batch.sync()
+            out[fname + "_ms"] = round(med(r), 4)
+            out[fname + "_rounds_ms"] = [round(x, 4) for x in r]
+        out["places_per_s"] = round(int(cnt[0]) / out["boolean_ms"] * 1e3, 1)
+        out["boolean_over_or_search"] = round(out["boolean_ms"] / out["or_search_ms"], 3)
+        out["boolean_over_floor"] = round(out["boolean_ms"] / out["floor_ms"], 2)
+        rows.append(out)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="2,5")
@@ -436,6 +541,7 @@ def main():
     ap.add_argument("--merge", default="", help="with --postings: K[,K..] equal document ranges as segments, then the ordered and the general merge")
     ap.add_argument("--search", action="append", default=[], help="with --postings: Q,L,K -- Q queries of L terms by count, top K (may be repeated)")
     ap.add_argument("--phrase", action="append", default=[], help="with --postings: Q,L,K -- Q phrases of L consecutive tokens of random documents, top K (may be repeated)")
+    ap.add_argument("--boolean", action="append", default=[], help="with --postings: Q,L,K -- Q all-MUST queries of L terms by count, Q all-MUST windows of L tokens, the first as all-SHOULD (may be repeated)")
     ap.add_argument("--search-max-candidates", type=int, default=1 << 26)
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
     ap.add_argument("--out", default="")
@@ -577,6 +683,9 @@ def main():
             if args.search:   # BM25 top-k over the segment the one-pass call left, beside the general merge and a copy
                 row["search"] = [search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_term, d_pdocs, d_ptfs, int(cnt[0]))
                                  for spec in args.search]
+            if args.boolean:   # MUST / SHOULD / MUST_NOT slots over the same segment, beside the OR search over the same slots and a copy
+                row["boolean"] = [boolean_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_term, d_pdocs, d_ptfs, int(cnt[0]))
+                                  for spec in args.boolean]
             if args.phrase:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
                 n_post = int(cnt[0])
                 d_first, d_order = torch.empty(cap_ends + 2, dtype=torch.int64, device=dev), torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)

@@ -164,6 +164,10 @@ SIGNATURES = {
     "vpt_postings_search": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                       C.c_uint32, _P, _P, _P, _P, _P]),
     "vpt_okapi_idf": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_float)]),
+    "vpt_postings_boolean_search_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32,
+                                                     C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P]),
+    "vpt_postings_boolean_search": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32, C.c_float, C.c_float,
+                                              C.c_float, C.c_uint32, _P, _P, _P, _P, _P]),
     "vpt_postings_positions_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint64, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     "vpt_postings_phrase_search_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, _P,
                                                     C.c_uint32, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P,

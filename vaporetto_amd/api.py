@@ -1602,6 +1602,27 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def boolean_search_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, n_terms: int, capacity_postings: int, doc_base: int,
+                                n_documents: int, d_doc_lens: int, d_query_offsets: int, d_query_terms: int, d_query_weights: int, d_query_occurs: int,
+                                n_queries: int, capacity_slots: int, k1: float, b: float, avgdl: float, k: int, capacity_candidates: int,
+                                d_hit_docs: int, d_hit_scores: int, d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0) -> None:
+        """Device-resident BM25 top-k search with MUST / SHOULD / MUST_NOT slots (vpt_postings_boolean_search_device), raw device pointers:
+        search_postings' arguments and d_query_occurs (uint8 per slot, Occur) behind the weights; capacity_candidates bounds the PLACES.
+        Enqueues and returns; errors (search_postings' and an occur above 2) at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_queries", n_queries, 1 << 32), ("k", k, 1 << 32), ("doc_base", doc_base, 1 << 64),
+                             ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
+                             ("capacity_slots", capacity_slots, 1 << 64), ("capacity_candidates", capacity_candidates, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_boolean_search_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
+                                                            int(n_terms), int(capacity_postings), int(doc_base), int(n_documents), d_doc_lens or None,
+                                                            d_query_offsets or None, d_query_terms or None, d_query_weights or None,
+                                                            d_query_occurs or None, int(n_queries), int(capacity_slots), float(k1), float(b),
+                                                            float(avgdl), int(k), int(capacity_candidates), d_hit_docs or None, d_hit_scores or None,
+                                                            d_hit_counts or None, d_match_counts or None, d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     @staticmethod
     def postings_search_limit() -> int:
         """the most slots a query of a search may have (vpt_postings_search_limits)"""
@@ -2070,6 +2091,12 @@ def bm25_idf(n_documents: int, df: int) -> np.float32:
     return np.float32(v.value)
 
 
+class Occur(enum.IntEnum):  # VPT_OCCUR_*: tantivy's Occur of a BooleanQuery's clause
+    SHOULD = 0
+    MUST = 1
+    MUST_NOT = 2
+
+
 class Postings:
     """The postings of one batch (a segment), term-major (vpt_postings_batch_device): term k's postings are [term_offsets[k], term_offsets[k + 1])
     of `docs` (doc_base + the document's index, ascending within a term) and `tfs`.  With positions: posting q's tokens are
@@ -2169,13 +2196,33 @@ class Postings:
         what index_batch / index_batches attached).  weights: a sequence of float sequences shaped as queries (default: bm25_idf(n_documents,
         df[term]) per slot).  avgdl = float32(sum(doc_lens) / n_documents), in double.  Returns (hits, match_counts): hits[q] the list of
         (document, score float32) pairs, at most k, by score descending, then document ascending; match_counts uint64 [n_queries]."""
+        return self._search("search", queries, None, k, doc_lens, doc_base, k1, b, weights, predictor)
+
+    def boolean_search(self, queries, k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2, b: float = 0.75,
+                       predictor: Optional["Predictor"] = None):
+        """BM25 top-k of every boolean query over this segment (vpt_postings_boolean_search; the definition is in include/vaporetto_hip.h).
+        queries: a sequence of sequences of (term, occur) or (term, occur, weight), a slot each, occur an Occur.  A document matches when every
+        MUST slot has it, no MUST_NOT slot has it and, without a MUST slot, some SHOULD slot has it; MUST and SHOULD slots that have it add to
+        its score.  A slot without a weight gets bm25_idf(n_documents, df[term]), a MUST_NOT slot 0.0.  doc_lens / doc_base / avgdl / the
+        return value: as in search.  last_search_counts: places, matches, skipped slots."""
+        queries = [[tuple(x) for x in q] for q in queries]
+        if any(len(x) not in (2, 3) for q in queries for x in q):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: boolean_search: a slot is (term, occur) or (term, occur, weight)")
+        occurs = [[int(x[1]) for x in q] for q in queries]
+        if any(not 0 <= o <= 255 for q in occurs for o in q):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: occurs: a value above 2")
+        weights = [[(np.float32(0.0) if int(x[1]) == Occur.MUST_NOT else None) if len(x) == 2 else x[2] for x in q] for q in queries]
+        return self._search("boolean_search", [[x[0] for x in q] for q in queries], occurs, k, doc_lens, doc_base, k1, b, weights, predictor)
+
+    def _search(self, name, queries, occurs, k, doc_lens, doc_base, k1, b, weights, predictor):
+        """search (occurs None) and boolean_search: the host call over this segment's arrays.  A weight of None: the slot's bm25_idf."""
         pred = predictor or self._predictor
         if pred is None:
-            raise VaporettoError("InvalidArgument", "InvalidArgumentError: search: no predictor (pass predictor=)")
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: no predictor (pass predictor=)" % name)
         doc_lens = self.doc_lens if doc_lens is None else doc_lens
         doc_base = self.doc_base if doc_base is None else doc_base
         if doc_lens is None or doc_base is None:
-            raise VaporettoError("InvalidArgument", "InvalidArgumentError: search: the postings carry no doc_lens / doc_base (pass them)")
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: the postings carry no doc_lens / doc_base (pass them)" % name)
         dl = np.ascontiguousarray(doc_lens, dtype=np.uint32)
         n_docs, n_terms, n_q = len(dl), len(self.term_offsets) - 1, len(queries)
         if n_q == 0:
@@ -2197,22 +2244,35 @@ class Postings:
                         idf[t] = bm25_idf(n_docs, int(df[t]))
                     w[s] = idf[t]
         else:
-            w = np.array([x for q in weights for x in q] + [0], np.float32)
-            if len(w) != n_slots + 1 or any(len(a) != len(c) for a, c in zip(weights, queries)):
+            flat = [x for q in weights for x in q] + [0]
+            if len(flat) != n_slots + 1 or any(len(a) != len(c) for a, c in zip(weights, queries)):
                 raise VaporettoError("InvalidArgument", "InvalidArgumentError: weights: not shaped as the queries")
+            if any(x is None for x in flat):
+                df, idf = self.df(), {}
+                for s, x in enumerate(flat):
+                    if x is None:
+                        t = int(terms[s])
+                        if 0 <= t < n_terms and t not in idf:
+                            idf[t] = bm25_idf(n_docs, int(df[t]))
+                        flat[s] = idf.get(t, 0.0)
+            w = np.array(flat, np.float32)
         if not (0 <= int(k) < 1 << 32 and 0 <= n_terms < 1 << 32 and 0 <= n_q < 1 << 32 and 0 <= int(doc_base) < 1 << 64):
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32")
         term = np.ascontiguousarray(self.term_offsets, dtype=np.uint64)
         docs, tfs = np.ascontiguousarray(self.docs, dtype=np.uint32), np.ascontiguousarray(self.tfs, dtype=np.uint32)
         n_out = max(n_q * int(k), 1)
         hd, hs, hc, mc, cnt = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
-        st = _lib.load().vpt_postings_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None, tfs.ctypes.data if len(tfs) else None,
-                                             n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data, n_q,
-                                             float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data,
-                                             cnt.ctypes.data)
+        head = (pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None, tfs.ctypes.data if len(tfs) else None, n_terms, int(doc_base),
+                n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data)
+        tail = (n_q, float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        if occurs is None:
+            st = _lib.load().vpt_postings_search(*(head + tail))
+        else:
+            occ = np.array([o for q in occurs for o in q] + [0], np.uint8)
+            st = _lib.load().vpt_postings_boolean_search(*(head + (occ.ctypes.data,) + tail))
         if st != _lib.VPT_OK:
             _raise(st)
-        self.last_search_counts = cnt   # candidates, matches, skipped slots
+        self.last_search_counts = cnt   # candidates (boolean_search: places), matches, skipped slots
         k = int(k)
         return [[(int(hd[q * k + j]), hs[q * k + j]) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
@@ -2439,6 +2499,27 @@ class VaporettoTokenizer:
         toff, ids = self.encode_batch(list(texts))
         queries = [ids[int(toff[i]):int(toff[i + 1])].tolist() for i in range(len(toff) - 1)]
         return postings.search(queries, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
+
+    def boolean_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
+                       b: float = 0.75):
+        """BM25 top-k of boolean query TEXTS over `postings`.  A text is split on ASCII spaces into CLAUSES: one that starts with `+` is MUST,
+        one that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are, and every
+        token of it is a slot of the clause's occur; an empty clause adds nothing.  A clause of several tokens is NOT made a phrase here (unlike
+        tantivy's query parser): `+東京都` requires each of its tokens somewhere in the document.  Then Postings.boolean_search.  Needs vocab=."""
+        clauses, owner = [], []
+        for i, text in enumerate(texts):
+            for clause in text.split(" "):
+                occur = Occur.MUST if clause[:1] == "+" else Occur.MUST_NOT if clause[:1] == "-" else Occur.SHOULD
+                body = clause[1:] if occur != Occur.SHOULD else clause
+                if body:
+                    clauses.append(body)
+                    owner.append((i, occur))
+        queries = [[] for _ in texts]
+        if clauses:
+            toff, ids = self.encode_batch(clauses)
+            for c, (i, occur) in enumerate(owner):
+                queries[i] += [(int(t), occur) for t in ids[int(toff[c]):int(toff[c + 1])]]
+        return postings.boolean_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor)
 
     def phrase_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
                       b: float = 0.75, weights=None):

@@ -1392,23 +1392,26 @@ vpt_status vpt_postings_merge_device(const vpt_predictor* p, vpt_batch* b, const
 }
 
 // ---- BM25 top-k search over a segment (kernels_postings_search.hip): slots, the trainer's scan, expand, the trainer's sort over the document
-// and the query word, heads, the trainer's scan, sum and ranges, the trainer's sort over the score and the query word, take.
+// and the query word, heads, the trainer's scan, sum and ranges, the trainer's sort over the score and the query word, take.  The boolean search
+// (kernels_postings_boolean.hip) puts queries, slots and expand of its own in front of the same sort.
 vpt_status vpt_postings_search_limits(uint32_t* max_query_slots) {
     if (!max_query_slots) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     *max_query_slots = vpt::kSearchMaxQuerySlots;
     return VPT_OK;
 }
 
-namespace vptc {
-vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
-                                  uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
-                                  const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, uint32_t n_queries,
-                                  uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
-                                  uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
-                                  hipStream_t stream) {
+namespace {
+// The OR search (boolean false: d_query_occurs is not looked at) and the boolean search (kernels_postings_boolean.hip: queries, slots and expand
+// of its own, then the OR search's launches as they stand) over one block of arguments, checks and scratch.
+vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
+                              uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
+                              const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, bool boolean,
+                              const uint8_t* d_query_occurs, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k,
+                              uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts,
+                              uint64_t* d_counts, hipStream_t stream) {
     if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_doc_lens || !d_query_offsets || !d_query_terms || !d_query_weights || !d_hit_docs ||
-        !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts)
+        !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts || (boolean && !d_query_occurs))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
     if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
     if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
@@ -1423,14 +1426,16 @@ vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const ui
     if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
     VPT_HIP(hipSetDevice(p->device));
     VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
-    // the scratch in 256-byte sections: slot_df | base | slot_query | rec | hit | order | skey | flags | scan | qstart | hist | hist_scan | partials
-    const uint64_t n = capacity_candidates, ns = capacity_slots, nh = vpt::train_radix_scratch(n);
+    // the scratch in 256-byte sections: slot_df | base | slot_query | rec | hit | order | skey | flags | scan | qstart | hist | hist_scan | partials |
+    // the boolean search's q_anchor | q_flags
+    const uint64_t n = capacity_candidates, ns = capacity_slots, nh = vpt::train_radix_scratch(n), nb = boolean ? n_queries : 0;
     auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t o_df = 0, o_base = o_df + pad(8 * size_t(ns)), o_sq = o_base + pad(8 * (size_t(ns) + 1)), o_rec = o_sq + pad(4 * size_t(ns)),
                  o_hit = o_rec + pad(12 * size_t(n)), o_order = o_hit + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)),
                  o_flags = o_skey + pad(4 * size_t(n)), o_scan = o_flags + pad(4 * size_t(n)), o_qstart = o_scan + pad(8 * (size_t(n) + 1)),
                  o_hist = o_qstart + pad(8 * (size_t(n_queries) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)), o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
-                 total = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(ns)})) + 1));
+                 o_anchor = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(ns)})) + 1)),
+                 o_qflags = o_anchor + pad(8 * size_t(nb)), total = o_qflags + pad(4 * size_t(nb));
     if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
     unsigned char* m = b->d_post;
     vpt::PostingsSearchParams P{};
@@ -1456,9 +1461,18 @@ vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const ui
     for (uint32_t i = 0; i < query_passes; ++i) group[n_group++] = (1u << 8) | (8 * i);
     for (uint32_t i = 0; i < 4; ++i) rank[n_rank++] = (2u << 8) | (8 * i);
     for (uint32_t i = 0; i < query_passes; ++i) rank[n_rank++] = (0u << 8) | (8 * i);
-    VPT_HIP(vpt::launch_postings_search_slots(P, stream));
-    VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
-    VPT_HIP(vpt::launch_postings_search_expand(P, stream));
+    if (boolean) {
+        vpt::PostingsBooleanParams B{};
+        B.S = P; B.occurs = d_query_occurs; B.q_anchor = reinterpret_cast<uint64_t*>(m + o_anchor); B.q_flags = reinterpret_cast<uint32_t*>(m + o_qflags);
+        VPT_HIP(vpt::launch_postings_boolean_queries(B, stream));
+        VPT_HIP(vpt::launch_postings_boolean_slots(B, stream));
+        VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
+        VPT_HIP(vpt::launch_postings_boolean_expand(B, stream));
+    } else {
+        VPT_HIP(vpt::launch_postings_search_slots(P, stream));
+        VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
+        VPT_HIP(vpt::launch_postings_search_expand(P, stream));
+    }
     VPT_HIP(vpt::train_radix_sort(P.rec, 3, group, n_group, n, P.order, P.skey, hist, hscan, part, stream));
     VPT_HIP(vpt::launch_postings_search_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
@@ -1467,6 +1481,30 @@ vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const ui
     VPT_HIP(vpt::launch_postings_search_take(P, stream));
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
+}
+}  // namespace
+
+namespace vptc {
+vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
+                                  uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
+                                  const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, uint32_t n_queries,
+                                  uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
+                                  uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
+                                  hipStream_t stream) {
+    return search_device_impl(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens, d_query_offsets,
+                              d_query_terms, d_query_weights, false, nullptr, n_queries, capacity_slots, k1, bm_b, avgdl, k, capacity_candidates, d_hit_docs,
+                              d_hit_scores, d_hit_counts, d_match_counts, d_counts, stream);
+}
+
+vpt_status postings_boolean_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                          const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents,
+                                          const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
+                                          const float* d_query_weights, const uint8_t* d_query_occurs, uint32_t n_queries, uint64_t capacity_slots, float k1,
+                                          float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores,
+                                          uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream) {
+    return search_device_impl(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens, d_query_offsets,
+                              d_query_terms, d_query_weights, true, d_query_occurs, n_queries, capacity_slots, k1, bm_b, avgdl, k, capacity_candidates,
+                              d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, stream);
 }
 }  // namespace vptc
 
@@ -1479,6 +1517,19 @@ vpt_status vpt_postings_search_device(const vpt_predictor* p, vpt_batch* b, cons
     return postings_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens,
                                   d_query_offsets, d_query_terms, d_query_weights, n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_candidates,
                                   d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
+}
+
+vpt_status vpt_postings_boolean_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                              const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base,
+                                              uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                              const int32_t* d_query_terms, const float* d_query_weights, const uint8_t* d_query_occurs,
+                                              uint32_t n_queries, uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                              uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts,
+                                              uint64_t* d_match_counts, uint64_t* d_counts, void* hip_stream) {
+    return postings_boolean_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens,
+                                          d_query_offsets, d_query_terms, d_query_weights, d_query_occurs, n_queries, capacity_slots, k1, b_param, avgdl, k,
+                                          capacity_candidates, d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts,
+                                          static_cast<hipStream_t>(hip_stream));
 }
 
 // ---- the position lists of a segment and the exact-phrase search over them (kernels_postings_phrase.hip).  Positions: one launch.  Search:

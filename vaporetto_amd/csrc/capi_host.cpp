@@ -1231,13 +1231,46 @@ vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float* idf_out) {
     return VPT_OK;
 }
 
+namespace {
+// The places of the boolean search as the device counts them (kernels_postings_boolean.hip): per query the df of its first MUST slot of the
+// smallest df, or, without a MUST slot, the dfs of its SHOULD slots; nothing for a query with a MUST slot out of range or of df 0.  (Arrays
+// that are no segment's or no CSR: the device reports them; such a query or list counts 0.)
+uint64_t boolean_places(const uint64_t* term_offsets, uint32_t n_terms, uint64_t n_post, const uint64_t* query_offsets, const int32_t* query_terms,
+                        const uint8_t* query_occurs, uint32_t n_queries, uint64_t n_slots) {
+    uint64_t places = 0;
+    for (uint32_t q = 0; q < n_queries && places < (1ull << 32); ++q) {
+        const uint64_t a = query_offsets[q], e = query_offsets[q + 1];
+        if (a > e || e > n_slots || e - a > vpt::kSearchMaxQuerySlots) continue;
+        uint64_t best = ~uint64_t(0), should = 0;
+        bool must = false, dead = false;
+        for (uint64_t s = a; s < e; ++s) {
+            const int32_t t = query_terms[s];
+            uint64_t df = 0;
+            if (t >= 0 && uint32_t(t) < n_terms) {
+                const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
+                if (ta <= tb && tb <= n_post) df = tb - ta;
+            }
+            if (query_occurs[s] == VPT_OCCUR_MUST) {
+                must = true;
+                if (df == 0) dead = true;
+                best = std::min(best, df);
+            } else if (query_occurs[s] == VPT_OCCUR_SHOULD) {
+                should += df;
+            }
+        }
+        if (!dead) places += must ? best : should;
+    }
+    return places;
+}
+
 // A host segment, host documents' lengths and host queries in, the hits out: what the segment holds (term_offsets[n_terms] postings) goes to one
-// allocation of this call, the candidates are counted from the host's term_offsets, the device search runs once, the four outputs come back.
-vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs, uint32_t n_terms,
-                               uint64_t doc_base, uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
-                               const int32_t* query_terms, const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl,
-                               uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_counts_out, uint64_t* match_counts_out,
-                               uint64_t* counts_out) {
+// allocation of this call, the candidates (boolean false: the OR search) or the places (the boolean search) are counted from the host's arrays,
+// the device search runs once, the four outputs come back.
+vpt_status postings_search_host(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs, uint32_t n_terms,
+                                uint64_t doc_base, uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                                const int32_t* query_terms, const float* query_weights, bool boolean, const uint8_t* query_occurs, uint32_t n_queries,
+                                float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
+                                uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!term_offsets || !query_offsets || !hit_docs_out || !hit_scores_out || !hit_counts_out || !match_counts_out || !counts_out)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -1248,10 +1281,15 @@ vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offs
     const uint64_t n_post = term_offsets[n_terms], n_slots = query_offsets[n_queries];
     if (n_post >= (1ull << 32) || n_slots >= (1ull << 32))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
-    if ((n_post && (!post_docs || !post_tfs)) || (n_documents && !doc_lens) || (n_slots && (!query_terms || !query_weights)))
+    if ((n_post && (!post_docs || !post_tfs)) || (n_documents && !doc_lens) || (n_slots && (!query_terms || !query_weights || (boolean && !query_occurs))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     uint64_t n_cand = 0;   // (bounds that do not ascend: the device reports them)
-    for (uint64_t s = 0; s < n_slots; ++s) {
+    if (boolean) {
+        n_cand = boolean_places(term_offsets, n_terms, n_post, query_offsets, query_terms, query_occurs, n_queries, n_slots);
+        if (n_cand >= (1ull << 32))
+            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+    }
+    for (uint64_t s = 0; s < n_slots && !boolean; ++s) {
         const int32_t t = query_terms[s];
         if (t < 0 || uint32_t(t) >= n_terms) continue;
         const uint64_t a = term_offsets[t], e = term_offsets[uint32_t(t) + 1];
@@ -1264,7 +1302,8 @@ vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offs
     const size_t n_out = size_t(n_queries) * k;
     const size_t o_term = 0, o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_post) + 4), o_dl = o_tfs + pad(4 * size_t(n_post) + 4),
                  o_qoff = o_dl + pad(4 * size_t(n_documents) + 4), o_qt = o_qoff + pad(8 * (size_t(n_queries) + 1)), o_qw = o_qt + pad(4 * size_t(n_slots) + 4),
-                 o_hd = o_qw + pad(4 * size_t(n_slots) + 4), o_hs = o_hd + pad(4 * n_out), o_hc = o_hs + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
+                 o_qo = o_qw + pad(4 * size_t(n_slots) + 4),
+                 o_hd = o_qo + pad(boolean ? size_t(n_slots) + 4 : 0), o_hs = o_hd + pad(4 * n_out), o_hc = o_hs + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
                  o_cnt = o_mc + pad(8 * size_t(n_queries));
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
@@ -1285,12 +1324,21 @@ vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offs
     if (n_slots) {
         VPT_HIP(hipMemcpyAsync(m + o_qt, query_terms, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
         VPT_HIP(hipMemcpyAsync(m + o_qw, query_weights, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
+        if (boolean) VPT_HIP(hipMemcpyAsync(m + o_qo, query_occurs, size_t(n_slots), hipMemcpyHostToDevice, s));
     }
     VPT_HIP(hipMemsetAsync(m + o_hd, 0, o_hc - o_hd, s));   // an entry at or behind a query's hit count is not written on the device: zeros come back
-    st = postings_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
+    if (!boolean)
+        st = postings_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
                                 reinterpret_cast<const uint32_t*>(m + o_tfs), n_terms, n_post, doc_base, n_documents, reinterpret_cast<const uint32_t*>(m + o_dl),
                                 reinterpret_cast<const uint64_t*>(m + o_qoff), reinterpret_cast<const int32_t*>(m + o_qt),
                                 reinterpret_cast<const float*>(m + o_qw), n_queries, n_slots, k1, b_param, avgdl, k, n_cand,
+                                reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs), reinterpret_cast<uint32_t*>(m + o_hc),
+                                reinterpret_cast<uint64_t*>(m + o_mc), reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    else
+        st = postings_boolean_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
+                                reinterpret_cast<const uint32_t*>(m + o_tfs), n_terms, n_post, doc_base, n_documents, reinterpret_cast<const uint32_t*>(m + o_dl),
+                                reinterpret_cast<const uint64_t*>(m + o_qoff), reinterpret_cast<const int32_t*>(m + o_qt),
+                                reinterpret_cast<const float*>(m + o_qw), m + o_qo, n_queries, n_slots, k1, b_param, avgdl, k, n_cand,
                                 reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs), reinterpret_cast<uint32_t*>(m + o_hc),
                                 reinterpret_cast<uint64_t*>(m + o_mc), reinterpret_cast<uint64_t*>(m + o_cnt), s);
     if (st != VPT_OK) return st;
@@ -1301,6 +1349,28 @@ vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offs
     VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
     VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
     return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_postings_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs, uint32_t n_terms,
+                               uint64_t doc_base, uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                               const int32_t* query_terms, const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl,
+                               uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_counts_out, uint64_t* match_counts_out,
+                               uint64_t* counts_out) {
+    return postings_search_host(p, term_offsets, post_docs, post_tfs, n_terms, doc_base, n_documents, doc_lens, query_offsets, query_terms, query_weights,
+                                false, nullptr, n_queries, k1, b_param, avgdl, k, hit_docs_out, hit_scores_out, hit_counts_out, match_counts_out,
+                                counts_out);
+}
+
+// The boolean search over host arrays: vpt_postings_search's route with the occurs beside the weights and the places counted as the device does.
+vpt_status vpt_postings_boolean_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                       uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                                       const int32_t* query_terms, const float* query_weights, const uint8_t* query_occurs, uint32_t n_queries, float k1,
+                                       float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_counts_out,
+                                       uint64_t* match_counts_out, uint64_t* counts_out) {
+    return postings_search_host(p, term_offsets, post_docs, post_tfs, n_terms, doc_base, n_documents, doc_lens, query_offsets, query_terms, query_weights,
+                                true, query_occurs, n_queries, k1, b_param, avgdl, k, hit_docs_out, hit_scores_out, hit_counts_out, match_counts_out,
+                                counts_out);
 }
 
 // A host positional segment, host documents' lengths and host phrases in, the hits out: what the segment holds goes to one allocation of this

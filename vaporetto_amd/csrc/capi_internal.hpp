@@ -535,6 +535,7 @@ vpt_status status_from_bits(uint32_t bits) {
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: term_offsets or postings are not a segment's");
     if (bits & vpt::kErrBadWeights) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: weights: negative or not finite");
     if (bits & vpt::kErrQueryTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: more than 1024 slots");
+    if (bits & vpt::kErrBadOccur) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: occurs: a value above 2");
     if (bits & vpt::kErrCandidatesTooSmall) return fail(VPT_INVALID_ARGUMENT, kCandidatesTooSmall);
     if (bits & vpt::kErrPhraseTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: a phrase of more than 64 terms");
     if (bits & vpt::kErrProbesTooSmall) return fail(VPT_INVALID_ARGUMENT, kProbesTooSmall);
@@ -751,6 +752,13 @@ vpt_status postings_search_device(const vpt_predictor* p, vpt_batch* b, const ui
                                   uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
                                   uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
                                   hipStream_t stream);
+// The BM25 top-k search with MUST / SHOULD / MUST_NOT slots (vpt_postings_boolean_search_device; kernels_postings_boolean.hip)
+vpt_status postings_boolean_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                          const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents,
+                                          const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
+                                          const float* d_query_weights, const uint8_t* d_query_occurs, uint32_t n_queries, uint64_t capacity_slots, float k1,
+                                          float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores,
+                                          uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream);
 // The position lists of a segment and the exact-phrase search over them (vpt_postings_positions_device, vpt_postings_phrase_search_device;
 // kernels_postings_phrase.hip)
 vpt_status postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,

@@ -80,6 +80,7 @@ constexpr uint32_t kErrBadPositions = 524288u;        // the positions of a segm
 constexpr uint32_t kErrPhraseTooLong = 1048576u;      // the phrase search: a phrase of more than kPhraseMaxTerms slots
 constexpr uint32_t kErrProbesTooSmall = 2097152u;     // the phrase search: more probes than capacity_probes
 constexpr uint32_t kErrPositionsTooSmall = 4194304u;  // the positional merge: more merged positions than capacity_positions_out
+constexpr uint32_t kErrBadOccur = 8388608u;           // the boolean search: an occur value above 2 (kernels_postings_boolean.hip)
 
 
 struct ScoreParams {
@@ -462,7 +463,7 @@ hipError_t launch_postings_merge_positions_general(const PostingsMergePosParams&
 // sum and take.  A launch behind expand that finds one of kSearchErrors in the status leaves the four outputs alone.
 constexpr uint32_t kSearchMaxQuerySlots = 1024;
 constexpr uint32_t kSearchMaxQueries = 1u << 24;
-constexpr uint32_t kSearchErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrQueryTooLong | kErrCandidatesTooSmall;
+constexpr uint32_t kSearchErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrQueryTooLong | kErrCandidatesTooSmall | kErrBadOccur;
 struct PostingsSearchParams {
     const uint64_t* term_offsets;   // [n_terms + 1]
     const uint32_t* post_docs;      // [capacity_postings]
@@ -502,6 +503,24 @@ hipError_t launch_postings_search_expand(const PostingsSearchParams& P, hipStrea
 hipError_t launch_postings_search_heads(const PostingsSearchParams& P, hipStream_t stream);
 hipError_t launch_postings_search_sum(const PostingsSearchParams& P, hipStream_t stream);    // sum, then the queries' ranges
 hipError_t launch_postings_search_take(const PostingsSearchParams& P, hipStream_t stream);
+// BM25 top-k search with MUST / SHOULD / MUST_NOT slots (kernels_postings_boolean.hip).  S is the OR search's block: the same inputs, scratch and
+// outputs, and heads, sum, ranges and take are the OR search's launches over S as they stand.  A query's ANCHOR is its first MUST slot of the
+// smallest df.  A PLACE is a posting of the anchor, or, in a query without a MUST slot, a posting of a SHOULD slot (a candidate of the OR
+// search); S.slot_df holds a slot's places, S.n_places bounds their sum.  Scratch beside S's: q_anchor (u64) and q_flags (u32) per query.  The
+// caller runs queries, slots, train_scan (S.slot_df -> S.base), expand, then the OR search's launches from the first sort on.
+constexpr uint32_t kOccurShould = 0, kOccurMust = 1, kOccurMustNot = 2;
+constexpr uint64_t kBoolNoAnchor = ~uint64_t(0);      // q_anchor: the query has no MUST slot
+constexpr uint64_t kBoolDead = ~uint64_t(0) - 1;      // q_anchor: no document can match (a MUST slot of df 0 or out of range, a query that is none)
+constexpr uint32_t kBoolHasNot = 1u;                  // q_flags: the query has a MUST_NOT slot
+struct PostingsBooleanParams {
+    PostingsSearchParams S;
+    const uint8_t* occurs;          // [capacity_slots]
+    uint64_t* q_anchor;             // [n_queries]
+    uint32_t* q_flags;              // [n_queries]
+};
+hipError_t launch_postings_boolean_queries(const PostingsBooleanParams& P, hipStream_t stream);
+hipError_t launch_postings_boolean_slots(const PostingsBooleanParams& P, hipStream_t stream);
+hipError_t launch_postings_boolean_expand(const PostingsBooleanParams& P, hipStream_t stream);
 // The position lists of a segment (kernels_postings_phrase.hip): one launch, a lane per place of capacity_in, behind the postings pass that wrote
 // post_first / token_order.  post_positions[i] = the position of token token_order[i] for every i below the indexed tokens.
 struct PostingsPositionsParams {

@@ -1,5 +1,6 @@
-// What the searches over a postings segment share (kernels_postings_search.hip: the OR search; kernels_postings_phrase.hip: the phrase search):
-// the bounded bisection, the bits of a binary32 and the score of one posting.  One copy, so both searches give a posting the same bits.
+// What the searches over a postings segment share (kernels_postings_search.hip: the OR search; kernels_postings_phrase.hip: the phrase search;
+// kernels_postings_boolean.hip: the boolean search): the bounded bisection, the bits of a binary32 and the score of one posting.  One copy, so
+// every search gives a posting the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
