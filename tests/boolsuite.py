@@ -523,6 +523,41 @@ def check_determinism(seed=12):
     same_as(a, ref)
 
 
+def check_scratch_reuse(seed=17):
+    """one workspace through the five drivers that lay out its postings scratch, each in a layout of its own over the same bytes -- a postings
+    pass with positions, a positional general merge of two segments, a phrase search with 2 T + 1 probes, an OR search with T + 1 candidates
+    and a boolean search with a MUST, a SHOULD and a MUST_NOT slot and T - 1 places, in this order: every result is, byte for byte, that of
+    the same call on a workspace of its own"""
+    from tests import phrasesuite, positionsmergesuite
+    rng = random.Random(seed)
+    T = tile()
+    pred = predictor()
+    docs = positionsmergesuite.random_docs(rng, 30, 6)
+    toff, ids = csr(docs)
+    owner = [[rng.randrange(2) for _ in d] for d in docs]
+    segs = [positionsmergesuite.pseg_of(d, 6, 0, p) for d, p in positionsmergesuite.deal(docs, None, owner, 2)]
+    n = 2 * T + 1
+    phrase_docs = [[0, 1, 2] * min(3, n - a) for a in range(0, n, 3)]   # 2 T + 1 tokens of each term
+    phrase_seg = phrasesuite.pseg_of(phrase_docs, 3)
+    wide = seg_of({0: {d: 1 + d % 3 for d in range(T + 1)}, 1: {d: 2 for d in range(0, T - 1, 2)}, 2: {d: 1 for d in range(T - 1)},
+                   3: {d: 1 for d in range(5, T - 1, 7)}}, 4, extra=2)
+    dl = [1 + (7 * d) % 50 for d in range(T + 1)]
+    steps = [
+        ("postings", None, lambda b: postingssuite.run(toff, ids, 6, batch=b)),
+        ("merge", None, lambda b: positionsmergesuite.run(segs, 6, False, batch=b)),
+        ("phrase", n, lambda b: phrasesuite.run(phrase_seg, 0, [len(d) for d in phrase_docs], [[0, 1]], [F(1.5)], 7, batch=b)),
+        ("search", T + 1, lambda b: searchsuite.run(wide, 0, dl, [[(0, F(0.75))]], 7, batch=b)),
+        ("boolean", T - 1, lambda b: run(wide, 0, dl, [[(2, M, F(1.25)), (1, S, F(0.5)), (3, N, F(0))]], 7, batch=b)),
+    ]
+    shared = api.DeviceBatch(pred)
+    for name, places, step in steps:
+        got, want = step(shared), step(api.DeviceBatch(pred))
+        assert got.error is None and want.error is None, (name, got.error, want.error)
+        assert got.same_bytes(want), name
+        assert places is None or int(got.counts[0]) == places, (name, got.counts.tolist())
+    assert int(got.mc[0]) == len([d for d in range(T - 1) if (d - 5) % 7])   # (the last step: the MUST list without the forbidden documents)
+
+
 # ---- 9
 def check_host_call(seed=5):
     """vpt_postings_boolean_search through Postings.boolean_search: host arrays in and out, the default weights and the caller's"""

@@ -94,5 +94,9 @@ def test_two_runs_and_a_second_workspace_give_identical_bytes():
     boolsuite.check_determinism()
 
 
+def test_one_workspace_through_the_five_scratch_layouts_gives_the_bytes_of_fresh_ones():
+    boolsuite.check_scratch_reuse()
+
+
 def test_host_call_and_postings_boolean_search():
     boolsuite.check_host_call()

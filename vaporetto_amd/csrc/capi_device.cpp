@@ -1146,19 +1146,19 @@ vpt_status vpt_postings_tile(uint32_t* n_tokens) {
     return VPT_OK;
 }
 
+// (every driver below lays its scratch out in b->d_post through a struct of scratch_carve.hpp: S.x.at(m) is section x of the layout)
 namespace vptc {
 vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, const int32_t* d_token_ids,
                            uint64_t capacity_in, uint32_t n_terms, uint64_t doc_base, uint64_t* d_term_offsets, uint32_t* d_post_docs, uint32_t* d_post_tfs,
                            uint64_t capacity_out, uint64_t* d_post_first, uint32_t* d_token_order, uint64_t* d_counts, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    VPT_TRY(check_batch(p, b));
     if (!d_token_offsets || !d_token_ids || !d_term_offsets || !d_post_docs || !d_post_tfs || !d_counts)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
     if ((d_post_first == nullptr) != (d_token_order == nullptr))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: post_first / token_order: both or neither");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (capacity_in >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
-    if (doc_base > (1ull << 32) || uint64_t(n_documents) > (1ull << 32) - doc_base)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(check_pass_tokens(capacity_in));
+    VPT_TRY(check_doc_range(doc_base, n_documents));
     VPT_HIP(hipSetDevice(p->device));
     VPT_HIP(hipMemsetAsync(d_counts, 0, 16, stream));
     if (n_documents == 0) {   // no document owns a token: no posting
@@ -1167,27 +1167,20 @@ vpt_status postings_device(const vpt_predictor* p, vpt_batch* b, const uint64_t*
         b->last_stream = stream; b->pending = true;
         return VPT_OK;
     }
-    // the scratch in 256-byte sections: keydoc | order | skey | flags | scan | hist | hist_scan | the scans' partials
-    const uint64_t n = capacity_in, nh = vpt::train_radix_scratch(n);
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_keydoc = 0, o_order = o_keydoc + pad(8 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
-                 o_scan = o_flags + pad(4 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
-                 o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
-                 total = o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
-    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    const uint64_t n = capacity_in;
+    const vptcarve::PostingsScratch S(n);
+    VPT_TRY(b->d_post.grow(S.bytes()));
     unsigned char* m = b->d_post;
     vpt::PostingsParams P{};
     P.token_offsets = d_token_offsets; P.n_docs = n_documents; P.ids = d_token_ids; P.capacity_in = capacity_in; P.n_terms = n_terms; P.doc_base = doc_base;
-    P.keydoc = reinterpret_cast<uint32_t*>(m + o_keydoc); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
-    P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+    P.keydoc = S.keydoc.at(m); P.order = S.order.at(m); P.skey = S.skey.at(m); P.flags = S.flags.at(m); P.scan = S.scan.at(m);
     P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.capacity_out = capacity_out; P.post_first = d_post_first;
     P.token_order = d_token_order; P.counts = d_counts; P.status = b->d_ctrl;
-    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
-    uint32_t passes[4], n_passes = 0;   // the bytes of the values 0 .. n_terms, least significant first
-    for (uint32_t v = n_terms; v; v >>= 8, ++n_passes) passes[n_passes] = 8 * n_passes;
+    uint64_t* part = S.tail.partials.at(m);
+    vptcarve::PassList passes;
+    passes.add(0, n_terms);
     VPT_HIP(vpt::launch_postings_keys(P, stream));
-    VPT_HIP(vpt::train_radix_sort(P.keydoc, 2, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
-                                  reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
+    VPT_HIP(vpt::train_radix_sort(P.keydoc, 2, passes.v, passes.n, n, P.order, P.skey, S.tail.hist.at(m), S.tail.hist_scan.at(m), part, stream));
     VPT_HIP(vpt::launch_postings_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
     VPT_HIP(vpt::launch_postings_emit(P, stream));
@@ -1206,172 +1199,113 @@ vpt_status vpt_postings_batch_device(const vpt_predictor* p, vpt_batch* b, const
 
 // ---- merge of postings segments (kernels_postings_merge.hip).  Ordered: load, offsets (the table), copy, check.  General: load, offsets,
 // records, the trainer's sort over the document and the term word, heads, the trainer's scan, emit and terms.
+// Of positional segments.  Ordered: load, offsets and the position offsets (the two tables), copy with post_first, check, pcopy.  General:
+// load, offsets, records, the sort, heads, ranks (the tfs in sorted order, the inverse of the order), the scan of the heads, emit and terms,
+// the scan of the tfs, first, pcopy.
 vpt_status vpt_postings_merge_limits(uint32_t* max_segments) {
     if (!max_segments) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     *max_segments = vpt::kPostingsMergeMaxSegments;
     return VPT_OK;
 }
 
-namespace vptc {
-vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
-                                 unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
-                                 uint64_t* d_counts, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
-    if (!segments || !d_term_offsets_out || !d_post_docs_out || !d_post_tfs_out || !d_counts)
+namespace {
+// The plain merge (segments: vpt_postings_segment; the position arguments are not looked at) and the positional merge (segments:
+// vpt_postings_positional_segment) over one block of arguments, checks and scratch: the plain one is the positional one without position
+// arrays -- what only those need is a section of count 0 and a launch that is left out.
+vpt_status merge_device_impl(const vpt_predictor* p, vpt_batch* b, const void* segments, bool positional, size_t n_segments, uint32_t n_terms_out,
+                             unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t* d_post_first_out,
+                             uint64_t capacity_out, uint32_t* d_post_positions_out, uint64_t capacity_positions_out, uint64_t* d_counts,
+                             hipStream_t stream) {
+    VPT_TRY(check_batch(p, b));
+    if (!segments || !d_term_offsets_out || !d_post_docs_out || !d_post_tfs_out || !d_counts || (positional && (!d_post_first_out || !d_post_positions_out)))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
-    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+    VPT_TRY(check_n_segments(n_segments));
+    VPT_TRY(check_n_terms(n_terms_out));
     if (flags & ~unsigned(VPT_POSTINGS_MERGE_ORDERED)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
+    if (positional) VPT_TRY(check_merge_positions(0, capacity_positions_out));
     const uint32_t K = uint32_t(n_segments);
     std::vector<vpt::PostingsMergeSegment> segs(K);
-    uint64_t n = 0;
-    for (uint32_t s = 0; s < K; ++s) {
-        const vpt_postings_segment& in = segments[s];
-        if (!in.d_term_offsets || !in.d_post_docs || !in.d_post_tfs) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-        if (in.n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
-        if (in.capacity >= (1ull << 32) || n + in.capacity >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
-        segs[s] = vpt::PostingsMergeSegment{in.d_term_offsets, in.d_post_docs, in.d_post_tfs, in.capacity, n, in.n_terms, 0u};
-        n += in.capacity;
-    }
-    VPT_HIP(hipSetDevice(p->device));
-    const bool ordered = (flags & VPT_POSTINGS_MERGE_ORDERED) != 0;
-    // the scratch in 256-byte sections: segs | range | table (ordered)   or   segs | rec | order | skey | flags | scan | hist | hist_scan | partials
-    const uint64_t nh = vpt::train_radix_scratch(n), row = uint64_t(n_terms_out) + 1;
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_segs = 0, o_a = pad(sizeof(vpt::PostingsMergeSegment) * K);
-    const size_t o_table = o_a + pad(8 * size_t(K));
-    const size_t o_order = o_a + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
-                 o_scan = o_flags + pad(4 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
-                 o_part = o_hscan + pad(8 * (size_t(nh) + 1));
-    const size_t total = ordered ? o_table + pad(8 * size_t(K) * size_t(row))
-                                 : o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
-    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
-    unsigned char* m = b->d_post;
-    vpt::PostingsMergeParams P{};
-    P.segs = reinterpret_cast<vpt::PostingsMergeSegment*>(m + o_segs); P.n_segs = K; P.n_terms = n_terms_out; P.n_places = n;
-    P.term_offsets = d_term_offsets_out; P.post_docs = d_post_docs_out; P.post_tfs = d_post_tfs_out; P.capacity_out = capacity_out;
-    P.counts = d_counts; P.status = b->d_ctrl;
-    if (ordered) {
-        P.range = reinterpret_cast<uint32_t*>(m + o_a); P.table = reinterpret_cast<uint64_t*>(m + o_table);
-        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
-        VPT_HIP(vpt::launch_postings_merge_ordered(P, stream));
-    } else {
-        P.rec = reinterpret_cast<uint32_t*>(m + o_a); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
-        P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
-        uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
-        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
-        VPT_HIP(vpt::launch_postings_merge_records(P, stream));
-        if (n == 0) {   // no place: no posting (the offsets were still checked)
-            VPT_HIP(hipMemsetAsync(d_term_offsets_out, 0, 8 * size_t(row), stream));
-            VPT_HIP(hipMemsetAsync(d_counts, 0, 16, stream));
-        } else {
-            uint32_t passes[8], n_passes = 0;   // the document word's four bytes, then the bytes of the values 0 .. n_terms_out of the term word
-            for (uint32_t k = 0; k < 4; ++k) passes[n_passes++] = (1u << 8) | (8 * k);
-            for (uint32_t v = n_terms_out, k = 0; v; v >>= 8, ++k) passes[n_passes++] = 8 * k;
-            VPT_HIP(vpt::train_radix_sort(P.rec, 3, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
-                                          reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
-            VPT_HIP(vpt::launch_postings_merge_heads(P, stream));
-            VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
-            VPT_HIP(vpt::launch_postings_merge_emit(P, stream));
-        }
-    }
-    b->last_stream = stream; b->pending = true;
-    return VPT_OK;
-}
-
-// The merge of positional segments.  Ordered: load, offsets and the position offsets (the two tables), copy with post_first, check, pcopy.
-// General: load, offsets, records, the sort, heads, ranks (the tfs in sorted order, the inverse of the order), the scan of the heads, emit and
-// terms, the scan of the tfs, first, pcopy.
-vpt_status postings_merge_positional_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_positional_segment* segments, size_t n_segments,
-                                            uint32_t n_terms_out, unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out,
-                                            uint32_t* d_post_tfs_out, uint64_t* d_post_first_out, uint64_t capacity_out, uint32_t* d_post_positions_out,
-                                            uint64_t capacity_positions_out, uint64_t* d_counts, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
-    if (!segments || !d_term_offsets_out || !d_post_docs_out || !d_post_tfs_out || !d_post_first_out || !d_post_positions_out || !d_counts)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
-    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (flags & ~unsigned(VPT_POSTINGS_MERGE_ORDERED)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: flags: unknown bit");
-    if (capacity_positions_out >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
-    const uint32_t K = uint32_t(n_segments);
-    std::vector<vpt::PostingsMergeSegment> segs(K);
-    std::vector<vpt::PostingsMergePosSegment> psegs(K);
+    std::vector<vpt::PostingsMergePosSegment> psegs(positional ? K : 0);
     uint64_t n = 0, np = 0;
     for (uint32_t s = 0; s < K; ++s) {
-        const vpt_postings_positional_segment& in = segments[s];
-        if (!in.d_term_offsets || !in.d_post_docs || !in.d_post_tfs || !in.d_post_first || !in.d_post_positions)
+        const vpt_postings_positional_segment in = merge_segment(segments, positional, s);
+        if (!in.d_term_offsets || !in.d_post_docs || !in.d_post_tfs || (positional && (!in.d_post_first || !in.d_post_positions)))
             return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
         if (in.n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
-        if (in.capacity >= (1ull << 32) || n + in.capacity >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
-        if (in.capacity_positions >= (1ull << 32) || np + in.capacity_positions >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+        VPT_TRY(check_merge_places(n, in.capacity));
+        VPT_TRY(check_merge_positions(np, in.capacity_positions));
         segs[s] = vpt::PostingsMergeSegment{in.d_term_offsets, in.d_post_docs, in.d_post_tfs, in.capacity, n, in.n_terms, 0u};
-        psegs[s] = vpt::PostingsMergePosSegment{in.d_post_first, in.d_post_positions, in.capacity_positions, np};
+        if (positional) psegs[s] = vpt::PostingsMergePosSegment{in.d_post_first, in.d_post_positions, in.capacity_positions, np};
         n += in.capacity;
         np += in.capacity_positions;
     }
     VPT_HIP(hipSetDevice(p->device));
     const bool ordered = (flags & VPT_POSTINGS_MERGE_ORDERED) != 0;
-    // the scratch in 256-byte sections: segs | psegs | range | table | ptable (ordered)   or
-    // segs | psegs | rec | order | skey | flags | scan | ptf | inv | pscan | hist | hist_scan | partials
-    const uint64_t nh = vpt::train_radix_scratch(n), row = uint64_t(n_terms_out) + 1;
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_segs = 0, o_psegs = pad(sizeof(vpt::PostingsMergeSegment) * K), o_a = o_psegs + pad(sizeof(vpt::PostingsMergePosSegment) * K);
-    const size_t o_table = o_a + pad(8 * size_t(K)), o_ptable = o_table + pad(8 * size_t(K) * size_t(row));
-    const size_t o_order = o_a + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_flags = o_skey + pad(4 * size_t(n)),
-                 o_scan = o_flags + pad(4 * size_t(n)), o_ptf = o_scan + pad(8 * (size_t(n) + 1)), o_inv = o_ptf + pad(4 * size_t(n)),
-                 o_pscan = o_inv + pad(4 * size_t(n)), o_hist = o_pscan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
-                 o_part = o_hscan + pad(8 * (size_t(nh) + 1));
-    const size_t total = ordered ? o_ptable + pad(8 * size_t(K) * size_t(row))
-                                 : o_part + pad(8 * (size_t(std::max(vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n))) + 1));
-    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    const uint64_t row = uint64_t(n_terms_out) + 1;
+    const vptcarve::MergeScratch<vpt::PostingsMergeSegment, vpt::PostingsMergePosSegment> S(K, n, row, positional);
+    VPT_TRY(b->d_post.grow(S.bytes(ordered)));
     unsigned char* m = b->d_post;
     vpt::PostingsMergePosParams Q{};
     vpt::PostingsMergeParams& P = Q.M;
-    P.segs = reinterpret_cast<vpt::PostingsMergeSegment*>(m + o_segs); P.n_segs = K; P.n_terms = n_terms_out; P.n_places = n;
+    P.segs = S.segs.at(m); P.n_segs = K; P.n_terms = n_terms_out; P.n_places = n;
     P.term_offsets = d_term_offsets_out; P.post_docs = d_post_docs_out; P.post_tfs = d_post_tfs_out; P.capacity_out = capacity_out;
     P.counts = d_counts; P.status = b->d_ctrl;
-    Q.psegs = reinterpret_cast<vpt::PostingsMergePosSegment*>(m + o_psegs); Q.n_pplaces = np;
-    Q.post_first = d_post_first_out; Q.post_positions = d_post_positions_out; Q.capacity_positions_out = capacity_positions_out;
+    if (positional) {
+        Q.psegs = S.psegs.at(m); Q.n_pplaces = np;
+        Q.post_first = d_post_first_out; Q.post_positions = d_post_positions_out; Q.capacity_positions_out = capacity_positions_out;
+    }
     if (ordered) {
-        P.range = reinterpret_cast<uint32_t*>(m + o_a); P.table = reinterpret_cast<uint64_t*>(m + o_table);
-        Q.ptable = reinterpret_cast<uint64_t*>(m + o_ptable);
-        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
-        VPT_HIP(vpt::launch_postings_merge_positions_load(Q, psegs.data(), stream));
-        VPT_HIP(vpt::launch_postings_merge_positions_ordered(Q, stream));
+        P.range = S.range.at(m); P.table = S.table.at(m);
+        if (positional) Q.ptable = S.ptable.at(m);
     } else {
-        P.rec = reinterpret_cast<uint32_t*>(m + o_a); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
-        P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
-        Q.ptf = reinterpret_cast<uint32_t*>(m + o_ptf); Q.inv = reinterpret_cast<uint32_t*>(m + o_inv); Q.pscan = reinterpret_cast<uint64_t*>(m + o_pscan);
-        uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
-        VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
-        VPT_HIP(vpt::launch_postings_merge_positions_load(Q, psegs.data(), stream));
+        P.rec = S.rec.at(m); P.order = S.order.at(m); P.skey = S.skey.at(m); P.flags = S.flags.at(m); P.scan = S.scan.at(m);
+        if (positional) { Q.ptf = S.ptf.at(m); Q.inv = S.inv.at(m); Q.pscan = S.pscan.at(m); }
+    }
+    VPT_HIP(vpt::launch_postings_merge_load(P, segs.data(), stream));
+    if (positional) VPT_HIP(vpt::launch_postings_merge_positions_load(Q, psegs.data(), stream));
+    if (ordered) {
+        VPT_HIP(positional ? vpt::launch_postings_merge_positions_ordered(Q, stream) : vpt::launch_postings_merge_ordered(P, stream));
+    } else {
+        uint64_t* part = S.tail.partials.at(m);
         VPT_HIP(vpt::launch_postings_merge_records(P, stream));
         if (n == 0) {   // no place: no posting, no position (the offsets were still checked)
             VPT_HIP(hipMemsetAsync(d_term_offsets_out, 0, 8 * size_t(row), stream));
-            VPT_HIP(hipMemsetAsync(d_post_first_out, 0, 8, stream));
-            VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
+            if (positional) VPT_HIP(hipMemsetAsync(d_post_first_out, 0, 8, stream));
+            VPT_HIP(hipMemsetAsync(d_counts, 0, positional ? 24 : 16, stream));
         } else {
-            uint32_t passes[8], n_passes = 0;   // the document word's four bytes, then the bytes of the values 0 .. n_terms_out of the term word
-            for (uint32_t k = 0; k < 4; ++k) passes[n_passes++] = (1u << 8) | (8 * k);
-            for (uint32_t v = n_terms_out, k = 0; v; v >>= 8, ++k) passes[n_passes++] = 8 * k;
-            VPT_HIP(vpt::train_radix_sort(P.rec, 3, passes, n_passes, n, P.order, P.skey, reinterpret_cast<uint64_t*>(m + o_hist),
-                                          reinterpret_cast<uint64_t*>(m + o_hscan), part, stream));
+            vptcarve::PassList passes;   // the document word's four bytes, then the term word's for the values 0 .. n_terms_out
+            passes.add(1, 0xFFFFFFFFu);
+            passes.add(0, n_terms_out);
+            VPT_HIP(vpt::train_radix_sort(P.rec, 3, passes.v, passes.n, n, P.order, P.skey, S.tail.hist.at(m), S.tail.hist_scan.at(m), part, stream));
             VPT_HIP(vpt::launch_postings_merge_heads(P, stream));
-            VPT_HIP(vpt::launch_postings_merge_positions_ranks(Q, stream));
+            if (positional) VPT_HIP(vpt::launch_postings_merge_positions_ranks(Q, stream));
             VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
             VPT_HIP(vpt::launch_postings_merge_emit(P, stream));
-            VPT_HIP(vpt::train_scan(Q.ptf, n, Q.pscan, part, stream));
-            VPT_HIP(vpt::launch_postings_merge_positions_general(Q, stream));
+            if (positional) {
+                VPT_HIP(vpt::train_scan(Q.ptf, n, Q.pscan, part, stream));
+                VPT_HIP(vpt::launch_postings_merge_positions_general(Q, stream));
+            }
         }
     }
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
+}
+}  // namespace
+
+namespace vptc {
+vpt_status postings_merge_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_segment* segments, size_t n_segments, uint32_t n_terms_out,
+                                 unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out, uint32_t* d_post_tfs_out, uint64_t capacity_out,
+                                 uint64_t* d_counts, hipStream_t stream) {
+    return merge_device_impl(p, b, segments, false, n_segments, n_terms_out, flags, d_term_offsets_out, d_post_docs_out, d_post_tfs_out, nullptr,
+                             capacity_out, nullptr, 0, d_counts, stream);
+}
+
+vpt_status postings_merge_positional_device(const vpt_predictor* p, vpt_batch* b, const vpt_postings_positional_segment* segments, size_t n_segments,
+                                            uint32_t n_terms_out, unsigned flags, uint64_t* d_term_offsets_out, uint32_t* d_post_docs_out,
+                                            uint32_t* d_post_tfs_out, uint64_t* d_post_first_out, uint64_t capacity_out, uint32_t* d_post_positions_out,
+                                            uint64_t capacity_positions_out, uint64_t* d_counts, hipStream_t stream) {
+    return merge_device_impl(p, b, segments, true, n_segments, n_terms_out, flags, d_term_offsets_out, d_post_docs_out, d_post_tfs_out, d_post_first_out,
+                             capacity_out, d_post_positions_out, capacity_positions_out, d_counts, stream);
 }
 }  // namespace vptc
 
@@ -1401,6 +1335,20 @@ vpt_status vpt_postings_search_limits(uint32_t* max_query_slots) {
 }
 
 namespace {
+// What the three searches check behind their pointers, in this order.  phrase: the phrase search's words for its sizes.
+vpt_status check_search_arguments(bool phrase, uint32_t n_terms, uint32_t n_queries, uint32_t k, uint64_t capacity_slots, uint64_t capacity_places,
+                                  uint64_t doc_base, uint64_t n_documents, float k1, float bm_b, float avgdl) {
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(check_n_queries(n_queries));
+    VPT_TRY(check_top_k(n_queries, k));
+    VPT_TRY(check_search_sizes(phrase, capacity_slots, capacity_places));
+    VPT_TRY(check_doc_range(doc_base, n_documents));
+    if (!(k1 >= 0.0f && k1 <= 65536.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k1: must be between 0 and 65536");
+    if (!(bm_b >= 0.0f && bm_b <= 1.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: b: must be between 0 and 1");
+    if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
+    return VPT_OK;
+}
+
 // The OR search (boolean false: d_query_occurs is not looked at) and the boolean search (kernels_postings_boolean.hip: queries, slots and expand
 // of its own, then the OR search's launches as they stand) over one block of arguments, checks and scratch.
 vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
@@ -1409,61 +1357,35 @@ vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64
                               const uint8_t* d_query_occurs, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k,
                               uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts,
                               uint64_t* d_counts, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    VPT_TRY(check_batch(p, b));
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_doc_lens || !d_query_offsets || !d_query_terms || !d_query_weights || !d_hit_docs ||
         !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts || (boolean && !d_query_occurs))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
-    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
-    if (capacity_slots >= (1ull << 32) || capacity_candidates >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
-    if (doc_base > (1ull << 32) || n_documents > (1ull << 32) - doc_base)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
-    if (!(k1 >= 0.0f && k1 <= 65536.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k1: must be between 0 and 65536");
-    if (!(bm_b >= 0.0f && bm_b <= 1.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: b: must be between 0 and 1");
-    if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
+    VPT_TRY(check_search_arguments(false, n_terms, n_queries, k, capacity_slots, capacity_candidates, doc_base, n_documents, k1, bm_b, avgdl));
     VPT_HIP(hipSetDevice(p->device));
     VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
-    // the scratch in 256-byte sections: slot_df | base | slot_query | rec | hit | order | skey | flags | scan | qstart | hist | hist_scan | partials |
-    // the boolean search's q_anchor | q_flags
-    const uint64_t n = capacity_candidates, ns = capacity_slots, nh = vpt::train_radix_scratch(n), nb = boolean ? n_queries : 0;
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_df = 0, o_base = o_df + pad(8 * size_t(ns)), o_sq = o_base + pad(8 * (size_t(ns) + 1)), o_rec = o_sq + pad(4 * size_t(ns)),
-                 o_hit = o_rec + pad(12 * size_t(n)), o_order = o_hit + pad(12 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)),
-                 o_flags = o_skey + pad(4 * size_t(n)), o_scan = o_flags + pad(4 * size_t(n)), o_qstart = o_scan + pad(8 * (size_t(n) + 1)),
-                 o_hist = o_qstart + pad(8 * (size_t(n_queries) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)), o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
-                 o_anchor = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(ns)})) + 1)),
-                 o_qflags = o_anchor + pad(8 * size_t(nb)), total = o_qflags + pad(4 * size_t(nb));
-    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    const uint64_t n = capacity_candidates, ns = capacity_slots;
+    const vptcarve::SearchScratch S(n, ns, n_queries, boolean);
+    VPT_TRY(b->d_post.grow(S.bytes()));
     unsigned char* m = b->d_post;
     vpt::PostingsSearchParams P{};
     P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.capacity_postings = capacity_postings; P.n_terms = n_terms;
     P.doc_base = doc_base; P.n_docs = n_documents; P.doc_lens = d_doc_lens;
     P.query_offsets = d_query_offsets; P.query_terms = d_query_terms; P.query_weights = d_query_weights; P.n_queries = n_queries; P.capacity_slots = ns;
     P.n_places = n; P.k1 = k1; P.b = bm_b; P.avgdl = avgdl; P.k = k;
-    P.slot_df = reinterpret_cast<uint64_t*>(m + o_df); P.base = reinterpret_cast<uint64_t*>(m + o_base); P.slot_query = reinterpret_cast<uint32_t*>(m + o_sq);
-    P.rec = reinterpret_cast<uint32_t*>(m + o_rec); P.hit = reinterpret_cast<uint32_t*>(m + o_hit); P.order = reinterpret_cast<uint32_t*>(m + o_order);
-    P.skey = reinterpret_cast<uint32_t*>(m + o_skey); P.flags = reinterpret_cast<uint32_t*>(m + o_flags); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
-    P.qstart = reinterpret_cast<uint64_t*>(m + o_qstart);
+    P.slot_df = S.slot_df.at(m); P.base = S.base.at(m); P.slot_query = S.slot_query.at(m); P.rec = S.rec.at(m); P.hit = S.hit.at(m);
+    P.order = S.order.at(m); P.skey = S.skey.at(m); P.flags = S.flags.at(m); P.scan = S.scan.at(m); P.qstart = S.qstart.at(m);
     P.hit_docs = d_hit_docs; P.hit_scores = d_hit_scores; P.hit_counts = d_hit_counts; P.match_counts = d_match_counts; P.counts = d_counts;
     P.status = b->d_ctrl;
-    uint64_t* hist = reinterpret_cast<uint64_t*>(m + o_hist);
-    uint64_t* hscan = reinterpret_cast<uint64_t*>(m + o_hscan);
-    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
-    // the bytes of the values 0 .. n_documents (at most four: the key is relative to doc_base) and 0 .. n_queries, least significant first
-    uint32_t doc_passes = 0, query_passes = 0;
-    for (uint64_t v = n_documents; v && doc_passes < 4; v >>= 8) ++doc_passes;
-    for (uint32_t v = n_queries; v; v >>= 8) ++query_passes;
-    uint32_t group[8], rank[8], n_group = 0, n_rank = 0;
-    for (uint32_t i = 0; i < doc_passes; ++i) group[n_group++] = (0u << 8) | (8 * i);
-    for (uint32_t i = 0; i < query_passes; ++i) group[n_group++] = (1u << 8) | (8 * i);
-    for (uint32_t i = 0; i < 4; ++i) rank[n_rank++] = (2u << 8) | (8 * i);
-    for (uint32_t i = 0; i < query_passes; ++i) rank[n_rank++] = (0u << 8) | (8 * i);
+    uint64_t *hist = S.tail.hist.at(m), *hscan = S.tail.hist_scan.at(m), *part = S.tail.partials.at(m);
+    vptcarve::PassList group, rank;
+    group.add(0, n_documents);   // (at most four bytes: the key is relative to doc_base)
+    group.add(1, n_queries);
+    rank.add(2, 0xFFFFFFFFu);    // the four bytes of ~bits(score)
+    rank.add(0, n_queries);
     if (boolean) {
         vpt::PostingsBooleanParams B{};
-        B.S = P; B.occurs = d_query_occurs; B.q_anchor = reinterpret_cast<uint64_t*>(m + o_anchor); B.q_flags = reinterpret_cast<uint32_t*>(m + o_qflags);
+        B.S = P; B.occurs = d_query_occurs; B.q_anchor = S.q_anchor.at(m); B.q_flags = S.q_flags.at(m);
         VPT_HIP(vpt::launch_postings_boolean_queries(B, stream));
         VPT_HIP(vpt::launch_postings_boolean_slots(B, stream));
         VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
@@ -1473,11 +1395,11 @@ vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64
         VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
         VPT_HIP(vpt::launch_postings_search_expand(P, stream));
     }
-    VPT_HIP(vpt::train_radix_sort(P.rec, 3, group, n_group, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::train_radix_sort(P.rec, 3, group.v, group.n, n, P.order, P.skey, hist, hscan, part, stream));
     VPT_HIP(vpt::launch_postings_search_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
     VPT_HIP(vpt::launch_postings_search_sum(P, stream));
-    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank, n_rank, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank.v, rank.n, n, P.order, P.skey, hist, hscan, part, stream));
     VPT_HIP(vpt::launch_postings_search_take(P, stream));
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
@@ -1545,11 +1467,11 @@ namespace vptc {
 vpt_status postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
                                      const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms, const uint64_t* d_post_first,
                                      uint64_t capacity_postings, const uint32_t* d_token_order, uint32_t* d_post_positions, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    VPT_TRY(check_batch(p, b));
     if (!d_token_offsets || !d_term_offsets || !d_post_first || !d_token_order || !d_post_positions)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (capacity_in >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(check_pass_tokens(capacity_in));
     VPT_HIP(hipSetDevice(p->device));
     vpt::PostingsPositionsParams P{};
     P.token_offsets = d_token_offsets; P.n_docs = n_documents; P.capacity_in = capacity_in; P.positions = d_token_positions;
@@ -1567,35 +1489,16 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
                                          const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
                                          uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
                                          uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream) {
-    if (!p || !b || b->pred != p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: batch: does not belong to this predictor");
+    VPT_TRY(check_batch(p, b));
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_post_first || !d_post_positions || !d_doc_lens || !d_query_offsets || !d_query_terms ||
         !d_query_weights || !d_hit_docs || !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
-    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
-    if (capacity_slots >= (1ull << 32) || capacity_probes >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
-    if (doc_base > (1ull << 32) || n_documents > (1ull << 32) - doc_base)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
-    if (!(k1 >= 0.0f && k1 <= 65536.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k1: must be between 0 and 65536");
-    if (!(bm_b >= 0.0f && bm_b <= 1.0f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: b: must be between 0 and 1");
-    if (!(avgdl >= 0x1p-32f && avgdl <= 0x1p32f)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32");
+    VPT_TRY(check_search_arguments(true, n_terms, n_queries, k, capacity_slots, capacity_probes, doc_base, n_documents, k1, bm_b, avgdl));
     VPT_HIP(hipSetDevice(p->device));
     VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
-    // the scratch in 256-byte sections: q_anchor | q_run | q_probes | base | qstart | flags | plen | pdoc | pq | hpf | order | skey | hit | scan |
-    // hist | hist_scan | partials
-    const uint64_t n = capacity_probes, nq = n_queries, nh = vpt::train_radix_scratch(n);
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_anchor = 0, o_run = o_anchor + pad(4 * size_t(nq)), o_probes = o_run + pad(8 * size_t(nq)), o_base = o_probes + pad(8 * size_t(nq)),
-                 o_qstart = o_base + pad(8 * (size_t(nq) + 1)), o_flags = o_qstart + pad(8 * (size_t(nq) + 1)), o_plen = o_flags + pad(4 * size_t(n)),
-                 o_pdoc = o_plen + pad(4 * size_t(n)), o_pq = o_pdoc + pad(4 * size_t(n)), o_hpf = o_pq + pad(4 * size_t(n)),
-                 o_order = o_hpf + pad(4 * size_t(n)), o_skey = o_order + pad(4 * size_t(n)), o_hit = o_skey + pad(4 * size_t(n)),
-                 o_scan = o_hit + pad(12 * size_t(n)), o_hist = o_scan + pad(8 * (size_t(n) + 1)), o_hscan = o_hist + pad(8 * size_t(nh)),
-                 o_part = o_hscan + pad(8 * (size_t(nh) + 1)),
-                 total = o_part + pad(8 * (size_t(std::max({vpt::train_scan_scratch(nh), vpt::train_scan_scratch(n), vpt::train_scan_scratch(nq)})) + 1));
-    if (const vpt_status st = b->d_post.grow(total); st != VPT_OK) return st;
+    const uint64_t n = capacity_probes, nq = n_queries;
+    const vptcarve::PhraseScratch S(n, n_queries);
+    VPT_TRY(b->d_post.grow(S.bytes()));
     unsigned char* m = b->d_post;
     vpt::PostingsPhraseParams P{};
     P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.post_first = d_post_first; P.post_positions = d_post_positions;
@@ -1603,20 +1506,15 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
     P.doc_base = doc_base; P.n_docs = n_documents; P.doc_lens = d_doc_lens;
     P.query_offsets = d_query_offsets; P.query_terms = d_query_terms; P.query_weights = d_query_weights; P.n_queries = n_queries;
     P.capacity_slots = capacity_slots; P.n_places = n; P.k1 = k1; P.b = bm_b; P.avgdl = avgdl; P.k = k;
-    P.q_anchor = reinterpret_cast<uint32_t*>(m + o_anchor); P.q_run = reinterpret_cast<uint64_t*>(m + o_run);
-    P.q_probes = reinterpret_cast<uint64_t*>(m + o_probes); P.base = reinterpret_cast<uint64_t*>(m + o_base);
-    P.qstart = reinterpret_cast<uint64_t*>(m + o_qstart); P.flags = reinterpret_cast<uint32_t*>(m + o_flags);
-    P.plen = reinterpret_cast<uint32_t*>(m + o_plen); P.pdoc = reinterpret_cast<uint32_t*>(m + o_pdoc); P.pq = reinterpret_cast<uint32_t*>(m + o_pq);
-    P.hpf = reinterpret_cast<uint32_t*>(m + o_hpf); P.order = reinterpret_cast<uint32_t*>(m + o_order); P.skey = reinterpret_cast<uint32_t*>(m + o_skey);
-    P.hit = reinterpret_cast<uint32_t*>(m + o_hit); P.scan = reinterpret_cast<uint64_t*>(m + o_scan);
+    P.q_anchor = S.q_anchor.at(m); P.q_run = S.q_run.at(m); P.q_probes = S.q_probes.at(m); P.base = S.base.at(m); P.qstart = S.qstart.at(m);
+    P.flags = S.flags.at(m); P.plen = S.plen.at(m); P.pdoc = S.pdoc.at(m); P.pq = S.pq.at(m); P.hpf = S.hpf.at(m); P.order = S.order.at(m);
+    P.skey = S.skey.at(m); P.hit = S.hit.at(m); P.scan = S.scan.at(m);
     P.hit_docs = d_hit_docs; P.hit_scores = d_hit_scores; P.hit_freqs = d_hit_freqs; P.hit_counts = d_hit_counts; P.match_counts = d_match_counts;
     P.counts = d_counts; P.status = b->d_ctrl;
-    uint64_t* hist = reinterpret_cast<uint64_t*>(m + o_hist);
-    uint64_t* hscan = reinterpret_cast<uint64_t*>(m + o_hscan);
-    uint64_t* part = reinterpret_cast<uint64_t*>(m + o_part);
-    uint32_t rank[8], n_rank = 0;   // the four bytes of ~bits(score), then the bytes of the values 0 .. n_queries, least significant first
-    for (uint32_t i = 0; i < 4; ++i) rank[n_rank++] = (2u << 8) | (8 * i);
-    for (uint32_t v = n_queries, i = 0; v; v >>= 8, ++i) rank[n_rank++] = (0u << 8) | (8 * i);
+    uint64_t* part = S.tail.partials.at(m);
+    vptcarve::PassList rank;
+    rank.add(2, 0xFFFFFFFFu);   // the four bytes of ~bits(score)
+    rank.add(0, n_queries);
     VPT_HIP(vpt::launch_postings_phrase_queries(P, stream));
     VPT_HIP(vpt::train_scan(P.q_probes, nq, P.base, part, stream));
     VPT_HIP(vpt::launch_postings_phrase_probe(P, stream));
@@ -1624,7 +1522,7 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
     VPT_HIP(vpt::launch_postings_phrase_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
     VPT_HIP(vpt::launch_postings_phrase_emit(P, stream));
-    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank, n_rank, n, P.order, P.skey, hist, hscan, part, stream));
+    VPT_HIP(vpt::train_radix_sort(P.hit, 3, rank.v, rank.n, n, P.order, P.skey, S.tail.hist.at(m), S.tail.hist_scan.at(m), part, stream));
     VPT_HIP(vpt::launch_postings_phrase_take(P, stream));
     b->last_stream = stream; b->pending = true;
     return VPT_OK;

@@ -963,8 +963,7 @@ vpt_status token_stream_postings(const vpt_predictor* p, const uint8_t* utf8, co
     if (!term_offsets_out || !n_postings_out || !n_dropped_out || (capacity && (!post_docs_out || !post_tfs_out)))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (v->n_keys == 0) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (doc_base > (1ull << 32) || uint64_t(n_documents) > (1ull << 32) - doc_base)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+    VPT_TRY(check_doc_range(doc_base, n_documents));
     const uint32_t n_terms = v->n_keys;
     std::fill(term_offsets_out, term_offsets_out + size_t(n_terms) + 1, uint64_t(0));
     if (positional) post_first_out[0] = 0;
@@ -972,7 +971,7 @@ vpt_status token_stream_postings(const vpt_predictor* p, const uint8_t* utf8, co
     if (!utf8 || !byte_offsets) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     if (byte_offsets[n_documents] < byte_offsets[0]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: byte_offsets: must be non-decreasing");
     const uint64_t cap_tok = byte_offsets[n_documents] - byte_offsets[0];
-    if (cap_tok >= (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+    VPT_TRY(check_pass_tokens(cap_tok));
     const bool tagged = tagger || stop;
     const uint32_t nt = tagged ? p->n_tags : 0u;
     std::vector<uint64_t> toff;
@@ -996,46 +995,49 @@ vpt_status token_stream_postings(const vpt_predictor* p, const uint8_t* utf8, co
     hipStream_t s = b->own_stream;
     // one allocation of this call, 256-byte sections: token_offsets | ids | term_offsets | docs | tfs | counts, and positional: first | order |
     // the stream's positions | the segment's positions
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_toff = 0, o_ids = o_toff + pad(8 * (n_documents + 1)), o_term = o_ids + pad(4 * size_t(n_tok) + 4),
-                 o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_tok) + 4), o_cnt = o_tfs + pad(4 * size_t(n_tok) + 4),
-                 o_first = o_cnt + 256, o_order = o_first + (positional ? pad(8 * (size_t(n_tok) + 1)) : 0),
-                 o_pos = o_order + (positional ? pad(4 * size_t(n_tok) + 4) : 0), o_ppos = o_pos + (positional ? pad(4 * size_t(n_tok) + 4) : 0),
-                 total = o_ppos + (positional ? pad(4 * size_t(n_tok) + 4) : 0);
+    vptcarve::Carver c;
+    const size_t nt1 = size_t(n_tok) + 1, np1 = positional ? nt1 : 0;   // (a word of slack an array)
+    const auto m_toff = c.take<uint64_t>(n_documents + 1);
+    const auto m_ids = c.take<int32_t>(nt1);
+    const auto m_term = c.take<uint64_t>(size_t(n_terms) + 1);
+    const auto m_docs = c.take<uint32_t>(nt1);
+    const auto m_tfs = c.take<uint32_t>(nt1);
+    const auto m_cnt = c.take<uint64_t>(2);
+    const auto m_first = c.take<uint64_t>(np1);
+    const auto m_order = c.take<uint32_t>(np1);
+    const auto m_pos = c.take<uint32_t>(np1);
+    const auto m_ppos = c.take<uint32_t>(np1);
     DevBuf<unsigned char> mem;
-    if ((st = mem.alloc(total)) != VPT_OK) return st;
+    if ((st = mem.alloc(c.bytes())) != VPT_OK) return st;
     unsigned char* m = mem;
-    VPT_HIP(hipMemcpyAsync(m + o_toff, toff.data(), 8 * (n_documents + 1), hipMemcpyHostToDevice, s));
-    if (n_tok) VPT_HIP(hipMemcpyAsync(m + o_ids, ids.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
-    if (positional && n_tok) VPT_HIP(hipMemcpyAsync(m + o_pos, pos.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
-    st = postings_device(p, b, reinterpret_cast<const uint64_t*>(m + o_toff), n_documents, reinterpret_cast<const int32_t*>(m + o_ids), n_tok, n_terms, doc_base,
-                         reinterpret_cast<uint64_t*>(m + o_term), reinterpret_cast<uint32_t*>(m + o_docs), reinterpret_cast<uint32_t*>(m + o_tfs), n_tok,
-                         positional ? reinterpret_cast<uint64_t*>(m + o_first) : nullptr, positional ? reinterpret_cast<uint32_t*>(m + o_order) : nullptr,
-                         reinterpret_cast<uint64_t*>(m + o_cnt), s);
+    VPT_HIP(hipMemcpyAsync(m_toff.at(m), toff.data(), 8 * (n_documents + 1), hipMemcpyHostToDevice, s));
+    if (n_tok) VPT_HIP(hipMemcpyAsync(m_ids.at(m), ids.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
+    if (positional && n_tok) VPT_HIP(hipMemcpyAsync(m_pos.at(m), pos.data(), 4 * size_t(n_tok), hipMemcpyHostToDevice, s));
+    st = postings_device(p, b, m_toff.at(m), n_documents, m_ids.at(m), n_tok, n_terms, doc_base, m_term.at(m), m_docs.at(m), m_tfs.at(m), n_tok,
+                         positional ? m_first.at(m) : nullptr, positional ? m_order.at(m) : nullptr, m_cnt.at(m), s);
     if (st != VPT_OK) return st;
     if (positional) {
-        st = postings_positions_device(p, b, reinterpret_cast<const uint64_t*>(m + o_toff), n_documents, n_tok, reinterpret_cast<const uint32_t*>(m + o_pos),
-                                       reinterpret_cast<const uint64_t*>(m + o_term), n_terms, reinterpret_cast<const uint64_t*>(m + o_first), n_tok,
-                                       reinterpret_cast<const uint32_t*>(m + o_order), reinterpret_cast<uint32_t*>(m + o_ppos), s);
+        st = postings_positions_device(p, b, m_toff.at(m), n_documents, n_tok, m_pos.at(m), m_term.at(m), n_terms, m_first.at(m), n_tok, m_order.at(m),
+                                       m_ppos.at(m), s);
         if (st != VPT_OK) return st;
     }
     if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
     uint64_t counts[2] = {0, 0};
-    VPT_HIP(hipMemcpy(counts, m + o_cnt, 16, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(counts, m_cnt.at(m), 16, hipMemcpyDeviceToHost));
     *n_postings_out = counts[0];
     *n_dropped_out = counts[1];
     if (positional) *n_positions_out = n_tok - counts[1];   // the indexed tokens
     if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
     if (positional && *n_positions_out > capacity_positions)
         return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
-    VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms) + 1), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(term_offsets_out, m_term.at(m), 8 * (size_t(n_terms) + 1), hipMemcpyDeviceToHost));
     if (counts[0]) {
-        VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
-        VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_docs_out, m_docs.at(m), 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_tfs_out, m_tfs.at(m), 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
     }
     if (positional) {
-        VPT_HIP(hipMemcpy(post_first_out, m + o_first, 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
-        if (*n_positions_out) VPT_HIP(hipMemcpy(post_positions_out, m + o_ppos, 4 * size_t(*n_positions_out), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_first_out, m_first.at(m), 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
+        if (*n_positions_out) VPT_HIP(hipMemcpy(post_positions_out, m_ppos.at(m), 4 * size_t(*n_positions_out), hipMemcpyDeviceToHost));
     }
     return VPT_OK;
 }
@@ -1060,166 +1062,120 @@ vpt_status vpt_token_stream_positional_postings_batch(const vpt_predictor* p, co
                                  capacity_positions, n_positions_out);
 }
 
-// Host segments in, the merged segment out: every segment's term_offsets and its postings (term_offsets[n_terms] of them, at most its capacity)
-// go to one allocation of this call, the device merge runs once over them, and the merged arrays come back.
-vpt_status vpt_postings_merge(const vpt_predictor* p, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
-                              uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t capacity, uint64_t* n_postings_out,
-                              uint64_t* n_combined_out) {
-    if (n_postings_out) *n_postings_out = 0;
-    if (n_combined_out) *n_combined_out = 0;
-    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
-    const vpt_postings_segment* in = static_cast<const vpt_postings_segment*>(segments);
-    if (!in || !term_offsets_out || !n_postings_out || !n_combined_out || (capacity && (!post_docs_out || !post_tfs_out)))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
-    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    std::vector<vpt_postings_segment> dev(n_segments);
-    std::vector<size_t> at(n_segments);   // where the segment's three arrays start in the allocation
-    size_t total = 0;
-    uint64_t n_in = 0;
-    for (size_t s = 0; s < n_segments; ++s) {
-        if (!in[s].d_term_offsets || (in[s].capacity && (!in[s].d_post_docs || !in[s].d_post_tfs)))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-        if (in[s].n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
-        const uint64_t n = std::min(in[s].d_term_offsets[in[s].n_terms], in[s].capacity);   // (an end above the capacity: the device reports it)
-        if (n >= (1ull << 32) || n_in + n >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
-        dev[s].n_terms = in[s].n_terms;
-        dev[s].capacity = n;
-        at[s] = total;
-        total += pad(8 * (size_t(in[s].n_terms) + 1)) + 2 * pad(4 * size_t(n) + 4);
-        n_in += n;
-    }
-    const size_t o_term = total, o_docs = o_term + pad(8 * (size_t(n_terms_out) + 1)), o_tfs = o_docs + pad(4 * size_t(n_in) + 4),
-                 o_cnt = o_tfs + pad(4 * size_t(n_in) + 4);
-    VPT_HIP(hipSetDevice(p->device));
-    Workspace w;
-    vpt_status st;
-    if ((st = acquire(p, &w)) != VPT_OK) return st;
-    vpt_batch* b = w.b;
-    hipStream_t s = b->own_stream;
-    DevBuf<unsigned char> mem;
-    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
-    unsigned char* m = mem;
-    for (size_t k = 0; k < n_segments; ++k) {
-        const size_t n = size_t(dev[k].capacity), o_d = at[k] + pad(8 * (size_t(in[k].n_terms) + 1)), o_t = o_d + pad(4 * n + 4);
-        VPT_HIP(hipMemcpyAsync(m + at[k], in[k].d_term_offsets, 8 * (size_t(in[k].n_terms) + 1), hipMemcpyHostToDevice, s));
-        if (n) {
-            VPT_HIP(hipMemcpyAsync(m + o_d, in[k].d_post_docs, 4 * n, hipMemcpyHostToDevice, s));
-            VPT_HIP(hipMemcpyAsync(m + o_t, in[k].d_post_tfs, 4 * n, hipMemcpyHostToDevice, s));
-        }
-        dev[k].d_term_offsets = reinterpret_cast<const uint64_t*>(m + at[k]);
-        dev[k].d_post_docs = reinterpret_cast<const uint32_t*>(m + o_d);
-        dev[k].d_post_tfs = reinterpret_cast<const uint32_t*>(m + o_t);
-    }
-    st = postings_merge_device(p, b, dev.data(), n_segments, n_terms_out, flags, reinterpret_cast<uint64_t*>(m + o_term), reinterpret_cast<uint32_t*>(m + o_docs),
-                               reinterpret_cast<uint32_t*>(m + o_tfs), n_in, reinterpret_cast<uint64_t*>(m + o_cnt), s);
-    if (st != VPT_OK) return st;
-    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    uint64_t counts[2] = {0, 0};
-    VPT_HIP(hipMemcpy(counts, m + o_cnt, 16, hipMemcpyDeviceToHost));
-    *n_postings_out = counts[0];
-    *n_combined_out = counts[1];
-    if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
-    VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms_out) + 1), hipMemcpyDeviceToHost));
-    if (counts[0]) {
-        VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
-        VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
-    }
-    return VPT_OK;
-}
+namespace {
+// a segment's arrays in an allocation of a host call, each with a word of slack; first and ppos: a positional segment's, else of count 0
+struct SegmentMem {
+    vptcarve::Section<uint64_t> term;
+    vptcarve::Section<uint32_t> docs, tfs;
+    vptcarve::Section<uint64_t> first;
+    vptcarve::Section<uint32_t> ppos;
+    SegmentMem(vptcarve::Carver& c, size_t n_terms, size_t n, size_t np, bool positional)
+        : term(c, n_terms + 1), docs(c, n + 1), tfs(c, n + 1), first(c, positional ? n + 1 : 0), ppos(c, positional ? np + 1 : 0) {}
+};
 
-// Host positional segments in, the merged positional segment out: vpt_postings_merge's steps with every segment's post_first (postings + 1
-// entries) and positions (post_first[postings] of them, at most its capacity_positions) beside its three arrays.
-vpt_status vpt_postings_merge_positional(const vpt_predictor* p, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
-                                         uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t* post_first_out,
-                                         uint64_t capacity, uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_postings_out,
-                                         uint64_t* n_combined_out, uint64_t* n_positions_out) {
+// Host segments in, the merged segment out: every segment's term_offsets and its postings (term_offsets[n_terms] of them, at most its capacity)
+// go to one allocation of this call, the device merge runs once over them, and the merged arrays come back.  positional (segments:
+// vpt_postings_positional_segment): with every segment's post_first (postings + 1 entries) and positions (post_first[postings] of them, at
+// most its capacity_positions) beside its three arrays; else (segments: vpt_postings_segment) the position arguments are not looked at.
+vpt_status postings_merge_host(const vpt_predictor* p, const void* segments, bool positional, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                               uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t* post_first_out, uint64_t capacity,
+                               uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_postings_out, uint64_t* n_combined_out,
+                               uint64_t* n_positions_out) {
     if (n_postings_out) *n_postings_out = 0;
     if (n_combined_out) *n_combined_out = 0;
     if (n_positions_out) *n_positions_out = 0;
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
-    const vpt_postings_positional_segment* in = static_cast<const vpt_postings_positional_segment*>(segments);
-    if (!in || !term_offsets_out || !post_first_out || !n_postings_out || !n_combined_out || !n_positions_out ||
-        (capacity && (!post_docs_out || !post_tfs_out)) || (capacity_positions && !post_positions_out))
+    if (!segments || !term_offsets_out || !n_postings_out || !n_combined_out || (capacity && (!post_docs_out || !post_tfs_out)) ||
+        (positional && (!post_first_out || !n_positions_out || (capacity_positions && !post_positions_out))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments)
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_segments: must be between 1 and 1024");
-    if (n_terms_out == 0 || n_terms_out > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    std::vector<vpt_postings_positional_segment> dev(n_segments);
-    std::vector<size_t> at(n_segments);   // where the segment's five arrays start in the allocation
-    size_t total = 0;
+    VPT_TRY(check_n_segments(n_segments));
+    VPT_TRY(check_n_terms(n_terms_out));
+    vptcarve::Carver c;
+    std::vector<vpt_postings_positional_segment> in(n_segments), dev(n_segments);
+    std::vector<SegmentMem> at;   // where the segment's arrays are in the allocation
+    at.reserve(n_segments);
     uint64_t n_in = 0, np_in = 0;
     for (size_t s = 0; s < n_segments; ++s) {
-        if (!in[s].d_term_offsets || !in[s].d_post_first || (in[s].capacity && (!in[s].d_post_docs || !in[s].d_post_tfs)) ||
+        in[s] = merge_segment(segments, positional, s);
+        if (!in[s].d_term_offsets || (positional && !in[s].d_post_first) || (in[s].capacity && (!in[s].d_post_docs || !in[s].d_post_tfs)) ||
             (in[s].capacity_positions && !in[s].d_post_positions))
             return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
         if (in[s].n_terms > n_terms_out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: segment: n_terms above n_terms_out");
         const uint64_t n = std::min(in[s].d_term_offsets[in[s].n_terms], in[s].capacity);   // (an end above the capacity: the device reports it)
-        const uint64_t np = std::min(in[s].d_post_first[n], in[s].capacity_positions);
-        if (n >= (1ull << 32) || n_in + n >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
-        if (np >= (1ull << 32) || np_in + np >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+        const uint64_t np = positional ? std::min(in[s].d_post_first[n], in[s].capacity_positions) : 0;
+        VPT_TRY(check_merge_places(n_in, n));
+        VPT_TRY(check_merge_positions(np_in, np));
         dev[s].n_terms = in[s].n_terms;
         dev[s].capacity = n;
         dev[s].capacity_positions = np;
-        at[s] = total;
-        total += pad(8 * (size_t(in[s].n_terms) + 1)) + 2 * pad(4 * size_t(n) + 4) + pad(8 * (size_t(n) + 1)) + pad(4 * size_t(np) + 4);
+        at.emplace_back(c, in[s].n_terms, size_t(n), size_t(np), positional);
         n_in += n;
         np_in += np;
     }
-    const size_t o_term = total, o_docs = o_term + pad(8 * (size_t(n_terms_out) + 1)), o_tfs = o_docs + pad(4 * size_t(n_in) + 4),
-                 o_first = o_tfs + pad(4 * size_t(n_in) + 4), o_ppos = o_first + pad(8 * (size_t(n_in) + 1)), o_cnt = o_ppos + pad(4 * size_t(np_in) + 4);
+    const SegmentMem out(c, n_terms_out, size_t(n_in), size_t(np_in), positional);
+    const auto cnt = c.take<uint64_t>(3);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
-    vpt_status st;
-    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    VPT_TRY(acquire(p, &w));
     vpt_batch* b = w.b;
     hipStream_t s = b->own_stream;
     DevBuf<unsigned char> mem;
-    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    VPT_TRY(mem.alloc(c.bytes()));
     unsigned char* m = mem;
     for (size_t k = 0; k < n_segments; ++k) {
-        const size_t n = size_t(dev[k].capacity), np = size_t(dev[k].capacity_positions), o_d = at[k] + pad(8 * (size_t(in[k].n_terms) + 1)),
-                     o_t = o_d + pad(4 * n + 4), o_f = o_t + pad(4 * n + 4), o_p = o_f + pad(8 * (n + 1));
-        VPT_HIP(hipMemcpyAsync(m + at[k], in[k].d_term_offsets, 8 * (size_t(in[k].n_terms) + 1), hipMemcpyHostToDevice, s));
-        VPT_HIP(hipMemcpyAsync(m + o_f, in[k].d_post_first, 8 * (n + 1), hipMemcpyHostToDevice, s));
+        const size_t n = size_t(dev[k].capacity), np = size_t(dev[k].capacity_positions);
+        const SegmentMem& a = at[k];
+        VPT_HIP(hipMemcpyAsync(a.term.at(m), in[k].d_term_offsets, 8 * (size_t(in[k].n_terms) + 1), hipMemcpyHostToDevice, s));
+        if (positional) VPT_HIP(hipMemcpyAsync(a.first.at(m), in[k].d_post_first, 8 * (n + 1), hipMemcpyHostToDevice, s));
         if (n) {
-            VPT_HIP(hipMemcpyAsync(m + o_d, in[k].d_post_docs, 4 * n, hipMemcpyHostToDevice, s));
-            VPT_HIP(hipMemcpyAsync(m + o_t, in[k].d_post_tfs, 4 * n, hipMemcpyHostToDevice, s));
+            VPT_HIP(hipMemcpyAsync(a.docs.at(m), in[k].d_post_docs, 4 * n, hipMemcpyHostToDevice, s));
+            VPT_HIP(hipMemcpyAsync(a.tfs.at(m), in[k].d_post_tfs, 4 * n, hipMemcpyHostToDevice, s));
         }
-        if (np) VPT_HIP(hipMemcpyAsync(m + o_p, in[k].d_post_positions, 4 * np, hipMemcpyHostToDevice, s));
-        dev[k].d_term_offsets = reinterpret_cast<const uint64_t*>(m + at[k]);
-        dev[k].d_post_docs = reinterpret_cast<const uint32_t*>(m + o_d);
-        dev[k].d_post_tfs = reinterpret_cast<const uint32_t*>(m + o_t);
-        dev[k].d_post_first = reinterpret_cast<const uint64_t*>(m + o_f);
-        dev[k].d_post_positions = reinterpret_cast<const uint32_t*>(m + o_p);
+        if (np) VPT_HIP(hipMemcpyAsync(a.ppos.at(m), in[k].d_post_positions, 4 * np, hipMemcpyHostToDevice, s));
+        dev[k].d_term_offsets = a.term.at(m); dev[k].d_post_docs = a.docs.at(m); dev[k].d_post_tfs = a.tfs.at(m);
+        dev[k].d_post_first = a.first.at(m); dev[k].d_post_positions = a.ppos.at(m);
     }
-    st = postings_merge_positional_device(p, b, dev.data(), n_segments, n_terms_out, flags, reinterpret_cast<uint64_t*>(m + o_term),
-                                          reinterpret_cast<uint32_t*>(m + o_docs), reinterpret_cast<uint32_t*>(m + o_tfs),
-                                          reinterpret_cast<uint64_t*>(m + o_first), n_in, reinterpret_cast<uint32_t*>(m + o_ppos), np_in,
-                                          reinterpret_cast<uint64_t*>(m + o_cnt), s);
-    if (st != VPT_OK) return st;
-    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
+    if (positional) {
+        VPT_TRY(postings_merge_positional_device(p, b, dev.data(), n_segments, n_terms_out, flags, out.term.at(m), out.docs.at(m), out.tfs.at(m),
+                                                 out.first.at(m), n_in, out.ppos.at(m), np_in, cnt.at(m), s));
+    } else {
+        std::vector<vpt_postings_segment> plain(n_segments);
+        for (size_t k = 0; k < n_segments; ++k)
+            plain[k] = vpt_postings_segment{dev[k].d_term_offsets, dev[k].d_post_docs, dev[k].d_post_tfs, dev[k].n_terms, dev[k].capacity};
+        VPT_TRY(postings_merge_device(p, b, plain.data(), n_segments, n_terms_out, flags, out.term.at(m), out.docs.at(m), out.tfs.at(m), n_in, cnt.at(m), s));
+    }
+    VPT_TRY(vpt_batch_sync(b));
     uint64_t counts[3] = {0, 0, 0};
-    VPT_HIP(hipMemcpy(counts, m + o_cnt, 24, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(counts, cnt.at(m), positional ? 24 : 16, hipMemcpyDeviceToHost));
     *n_postings_out = counts[0];
     *n_combined_out = counts[1];
-    *n_positions_out = counts[2];
+    if (positional) *n_positions_out = counts[2];
     if (counts[0] > capacity) return fail(VPT_INVALID_ARGUMENT, kPostingsTooSmall);
-    if (counts[2] > capacity_positions) return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
-    VPT_HIP(hipMemcpy(term_offsets_out, m + o_term, 8 * (size_t(n_terms_out) + 1), hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(post_first_out, m + o_first, 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
+    if (positional && counts[2] > capacity_positions) return fail(VPT_INVALID_ARGUMENT, kPositionsTooSmall);
+    VPT_HIP(hipMemcpy(term_offsets_out, out.term.at(m), 8 * (size_t(n_terms_out) + 1), hipMemcpyDeviceToHost));
+    if (positional) VPT_HIP(hipMemcpy(post_first_out, out.first.at(m), 8 * (size_t(counts[0]) + 1), hipMemcpyDeviceToHost));
     if (counts[0]) {
-        VPT_HIP(hipMemcpy(post_docs_out, m + o_docs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
-        VPT_HIP(hipMemcpy(post_tfs_out, m + o_tfs, 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_docs_out, out.docs.at(m), 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(post_tfs_out, out.tfs.at(m), 4 * size_t(counts[0]), hipMemcpyDeviceToHost));
     }
-    if (counts[2]) VPT_HIP(hipMemcpy(post_positions_out, m + o_ppos, 4 * size_t(counts[2]), hipMemcpyDeviceToHost));
+    if (positional && counts[2]) VPT_HIP(hipMemcpy(post_positions_out, out.ppos.at(m), 4 * size_t(counts[2]), hipMemcpyDeviceToHost));
     return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_postings_merge(const vpt_predictor* p, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                              uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t capacity, uint64_t* n_postings_out,
+                              uint64_t* n_combined_out) {
+    return postings_merge_host(p, segments, false, n_segments, n_terms_out, flags, term_offsets_out, post_docs_out, post_tfs_out, nullptr, capacity, nullptr,
+                               0, n_postings_out, n_combined_out, nullptr);
+}
+
+vpt_status vpt_postings_merge_positional(const vpt_predictor* p, const void* segments, size_t n_segments, uint32_t n_terms_out, unsigned flags,
+                                         uint64_t* term_offsets_out, uint32_t* post_docs_out, uint32_t* post_tfs_out, uint64_t* post_first_out,
+                                         uint64_t capacity, uint32_t* post_positions_out, uint64_t capacity_positions, uint64_t* n_postings_out,
+                                         uint64_t* n_combined_out, uint64_t* n_positions_out) {
+    return postings_merge_host(p, segments, true, n_segments, n_terms_out, flags, term_offsets_out, post_docs_out, post_tfs_out, post_first_out, capacity,
+                               post_positions_out, capacity_positions, n_postings_out, n_combined_out, n_positions_out);
 }
 
 // The BM25 weight of a term of document frequency df among n_documents, as tantivy's Bm25Weight computes it: one implementation for every binding.
@@ -1232,6 +1188,19 @@ vpt_status vpt_okapi_idf(uint64_t n_documents, uint64_t df, float* idf_out) {
 }
 
 namespace {
+// The candidates of the OR search: the dfs of the slots whose term is in range.  (Bounds that do not ascend: the device reports them; such a
+// list counts 0.  Counting stops at 2^32: the call refuses that.)
+uint64_t search_candidates(const uint64_t* term_offsets, uint32_t n_terms, uint64_t n_post, const int32_t* query_terms, uint64_t n_slots) {
+    uint64_t n_cand = 0;
+    for (uint64_t s = 0; s < n_slots && n_cand < (1ull << 32); ++s) {
+        const int32_t t = query_terms[s];
+        if (t < 0 || uint32_t(t) >= n_terms) continue;
+        const uint64_t a = term_offsets[t], e = term_offsets[uint32_t(t) + 1];
+        if (e > a && e <= n_post) n_cand += e - a;
+    }
+    return n_cand;
+}
+
 // The places of the boolean search as the device counts them (kernels_postings_boolean.hip): per query the df of its first MUST slot of the
 // smallest df, or, without a MUST slot, the dfs of its SHOULD slots; nothing for a query with a MUST slot out of range or of df 0.  (Arrays
 // that are no segment's or no CSR: the device reports them; such a query or list counts 0.)
@@ -1263,6 +1232,86 @@ uint64_t boolean_places(const uint64_t* term_offsets, uint32_t n_terms, uint64_t
     return places;
 }
 
+// The probes of the phrase search as the device counts them: per phrase that can match, the indexed tokens of its rarest term.  (Arrays that
+// are no segment's or no CSR: the device reports them; a query is then counted as 0.)
+uint64_t phrase_probes(const uint64_t* term_offsets, const uint64_t* post_first, uint32_t n_terms, uint64_t n_post, uint64_t n_pos,
+                       const uint64_t* query_offsets, const int32_t* query_terms, uint32_t n_queries, uint64_t n_slots) {
+    uint64_t n_probes = 0;
+    for (uint32_t q = 0; q < n_queries && n_probes < (1ull << 32); ++q) {
+        const uint64_t a = query_offsets[q], e = query_offsets[q + 1];
+        if (a >= e || e > n_slots || e - a > vpt::kPhraseMaxTerms) continue;
+        uint64_t best = ~uint64_t(0);
+        for (uint64_t s = a; s < e && best; ++s) {
+            const int32_t t = query_terms[s];
+            if (t < 0 || uint32_t(t) >= n_terms) { best = 0; break; }
+            const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
+            if (ta >= tb || tb > n_post || post_first[ta] > post_first[tb] || post_first[tb] > n_pos) { best = 0; break; }
+            best = std::min(best, post_first[tb] - post_first[ta]);
+        }
+        n_probes += best;
+    }
+    return n_probes;
+}
+
+// What a search over host arrays keeps in the one allocation of its call: the segment (phrase: with post_first and the positions), the
+// documents' lengths, the query CSR (a weight a slot, phrase: a weight a query; boolean: an occur a slot), the hit arrays (phrase: with the
+// frequencies), the counts.  The inputs have a word of slack each.
+struct SearchMem {
+    const size_t n_terms, n_post, n_pos, n_docs, n_queries, n_slots, n_out;
+    const bool phrase, boolean;
+    vptcarve::Carver c{};
+    vptcarve::Section<uint64_t> term{c, n_terms + 1};
+    vptcarve::Section<uint32_t> docs{c, n_post + 1}, tfs{c, n_post + 1};
+    vptcarve::Section<uint64_t> first{c, phrase ? n_post + 1 : 0};
+    vptcarve::Section<uint32_t> pos{c, phrase ? n_pos + 1 : 0}, dl{c, n_docs + 1};
+    vptcarve::Section<uint64_t> qoff{c, n_queries + 1};
+    vptcarve::Section<int32_t> qterms{c, n_slots + 1};
+    vptcarve::Section<float> qweights{c, phrase ? n_queries : n_slots + 1};
+    vptcarve::Section<uint8_t> qoccurs{c, boolean ? n_slots + 4 : 0};
+    vptcarve::Section<uint32_t> hit_docs{c, n_out};
+    vptcarve::Section<float> hit_scores{c, n_out};
+    vptcarve::Section<uint32_t> hit_freqs{c, phrase ? n_out : 0}, hit_counts{c, n_queries};
+    vptcarve::Section<uint64_t> match_counts{c, n_queries}, counts{c, 3};
+    SearchMem(uint32_t terms, uint64_t post, uint64_t positions, uint64_t documents, uint32_t queries, uint64_t slots, uint32_t k, bool is_phrase,
+              bool is_boolean)
+        : n_terms(terms), n_post(size_t(post)), n_pos(size_t(positions)), n_docs(size_t(documents)), n_queries(queries), n_slots(size_t(slots)),
+          n_out(size_t(queries) * k), phrase(is_phrase), boolean(is_boolean) {}
+
+    // the segment, the lengths and the query CSR go up (post_first, post_positions: the phrase search's; query_occurs: the boolean search's)
+    vpt_status upload(unsigned char* m, hipStream_t s, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                      const uint64_t* post_first, const uint32_t* post_positions, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                      const int32_t* query_terms, const float* query_weights, const uint8_t* query_occurs) const {
+        VPT_HIP(hipMemcpyAsync(term.at(m), term_offsets, 8 * (n_terms + 1), hipMemcpyHostToDevice, s));
+        if (n_post) {
+            VPT_HIP(hipMemcpyAsync(docs.at(m), post_docs, 4 * n_post, hipMemcpyHostToDevice, s));
+            VPT_HIP(hipMemcpyAsync(tfs.at(m), post_tfs, 4 * n_post, hipMemcpyHostToDevice, s));
+        }
+        if (phrase) VPT_HIP(hipMemcpyAsync(first.at(m), post_first, 8 * (n_post + 1), hipMemcpyHostToDevice, s));
+        if (n_pos) VPT_HIP(hipMemcpyAsync(pos.at(m), post_positions, 4 * n_pos, hipMemcpyHostToDevice, s));
+        if (n_docs) VPT_HIP(hipMemcpyAsync(dl.at(m), doc_lens, 4 * n_docs, hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(qoff.at(m), query_offsets, 8 * (n_queries + 1), hipMemcpyHostToDevice, s));
+        if (n_slots) VPT_HIP(hipMemcpyAsync(qterms.at(m), query_terms, 4 * n_slots, hipMemcpyHostToDevice, s));
+        if (const size_t n_weights = phrase ? n_queries : n_slots) VPT_HIP(hipMemcpyAsync(qweights.at(m), query_weights, 4 * n_weights, hipMemcpyHostToDevice, s));
+        if (boolean && n_slots) VPT_HIP(hipMemcpyAsync(qoccurs.at(m), query_occurs, n_slots, hipMemcpyHostToDevice, s));
+        return VPT_OK;
+    }
+    // an entry at or behind a query's hit count is not written on the device: zeros come back
+    vpt_status clear_hits(unsigned char* m, hipStream_t s) const {
+        VPT_HIP(hipMemsetAsync(m + hit_docs.offset, 0, hit_counts.offset - hit_docs.offset, s));
+        return VPT_OK;
+    }
+    vpt_status read_back(unsigned char* m, uint64_t* counts_out, uint32_t* hit_counts_out, uint64_t* match_counts_out, uint32_t* hit_docs_out,
+                         float* hit_scores_out, uint32_t* hit_freqs_out) const {
+        VPT_HIP(hipMemcpy(counts_out, counts.at(m), 24, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(hit_counts_out, hit_counts.at(m), 4 * n_queries, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(match_counts_out, match_counts.at(m), 8 * n_queries, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(hit_docs_out, hit_docs.at(m), 4 * n_out, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(hit_scores_out, hit_scores.at(m), 4 * n_out, hipMemcpyDeviceToHost));
+        if (phrase) VPT_HIP(hipMemcpy(hit_freqs_out, hit_freqs.at(m), 4 * n_out, hipMemcpyDeviceToHost));
+        return VPT_OK;
+    }
+};
+
 // A host segment, host documents' lengths and host queries in, the hits out: what the segment holds (term_offsets[n_terms] postings) goes to one
 // allocation of this call, the candidates (boolean false: the OR search) or the places (the boolean search) are counted from the host's arrays,
 // the device search runs once, the four outputs come back.
@@ -1274,81 +1323,38 @@ vpt_status postings_search_host(const vpt_predictor* p, const uint64_t* term_off
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!term_offsets || !query_offsets || !hit_docs_out || !hit_scores_out || !hit_counts_out || !match_counts_out || !counts_out)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
-    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(check_n_queries(n_queries));
+    VPT_TRY(check_top_k(n_queries, k));
     const uint64_t n_post = term_offsets[n_terms], n_slots = query_offsets[n_queries];
-    if (n_post >= (1ull << 32) || n_slots >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+    VPT_TRY(check_search_sizes(false, n_post, n_slots));
     if ((n_post && (!post_docs || !post_tfs)) || (n_documents && !doc_lens) || (n_slots && (!query_terms || !query_weights || (boolean && !query_occurs))))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    uint64_t n_cand = 0;   // (bounds that do not ascend: the device reports them)
-    if (boolean) {
-        n_cand = boolean_places(term_offsets, n_terms, n_post, query_offsets, query_terms, query_occurs, n_queries, n_slots);
-        if (n_cand >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
-    }
-    for (uint64_t s = 0; s < n_slots && !boolean; ++s) {
-        const int32_t t = query_terms[s];
-        if (t < 0 || uint32_t(t) >= n_terms) continue;
-        const uint64_t a = term_offsets[t], e = term_offsets[uint32_t(t) + 1];
-        if (e > a && e <= n_post) n_cand += e - a;
-        if (n_cand >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
-    }
-    if (n_documents > (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t n_out = size_t(n_queries) * k;
-    const size_t o_term = 0, o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_post) + 4), o_dl = o_tfs + pad(4 * size_t(n_post) + 4),
-                 o_qoff = o_dl + pad(4 * size_t(n_documents) + 4), o_qt = o_qoff + pad(8 * (size_t(n_queries) + 1)), o_qw = o_qt + pad(4 * size_t(n_slots) + 4),
-                 o_qo = o_qw + pad(4 * size_t(n_slots) + 4),
-                 o_hd = o_qo + pad(boolean ? size_t(n_slots) + 4 : 0), o_hs = o_hd + pad(4 * n_out), o_hc = o_hs + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
-                 o_cnt = o_mc + pad(8 * size_t(n_queries));
+    const uint64_t n_cand = boolean ? boolean_places(term_offsets, n_terms, n_post, query_offsets, query_terms, query_occurs, n_queries, n_slots)
+                                    : search_candidates(term_offsets, n_terms, n_post, query_terms, n_slots);
+    VPT_TRY(check_search_sizes(false, n_cand));
+    VPT_TRY(check_doc_range(0, n_documents));
+    const SearchMem A(n_terms, n_post, 0, n_documents, n_queries, n_slots, k, false, boolean);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
-    vpt_status st;
-    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    VPT_TRY(acquire(p, &w));
     vpt_batch* b = w.b;
     hipStream_t s = b->own_stream;
     DevBuf<unsigned char> mem;
-    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    VPT_TRY(mem.alloc(A.c.bytes()));
     unsigned char* m = mem;
-    VPT_HIP(hipMemcpyAsync(m + o_term, term_offsets, 8 * (size_t(n_terms) + 1), hipMemcpyHostToDevice, s));
-    if (n_post) {
-        VPT_HIP(hipMemcpyAsync(m + o_docs, post_docs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
-        VPT_HIP(hipMemcpyAsync(m + o_tfs, post_tfs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
-    }
-    if (n_documents) VPT_HIP(hipMemcpyAsync(m + o_dl, doc_lens, 4 * size_t(n_documents), hipMemcpyHostToDevice, s));
-    VPT_HIP(hipMemcpyAsync(m + o_qoff, query_offsets, 8 * (size_t(n_queries) + 1), hipMemcpyHostToDevice, s));
-    if (n_slots) {
-        VPT_HIP(hipMemcpyAsync(m + o_qt, query_terms, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
-        VPT_HIP(hipMemcpyAsync(m + o_qw, query_weights, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
-        if (boolean) VPT_HIP(hipMemcpyAsync(m + o_qo, query_occurs, size_t(n_slots), hipMemcpyHostToDevice, s));
-    }
-    VPT_HIP(hipMemsetAsync(m + o_hd, 0, o_hc - o_hd, s));   // an entry at or behind a query's hit count is not written on the device: zeros come back
+    VPT_TRY(A.upload(m, s, term_offsets, post_docs, post_tfs, nullptr, nullptr, doc_lens, query_offsets, query_terms, query_weights, query_occurs));
+    VPT_TRY(A.clear_hits(m, s));
     if (!boolean)
-        st = postings_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
-                                reinterpret_cast<const uint32_t*>(m + o_tfs), n_terms, n_post, doc_base, n_documents, reinterpret_cast<const uint32_t*>(m + o_dl),
-                                reinterpret_cast<const uint64_t*>(m + o_qoff), reinterpret_cast<const int32_t*>(m + o_qt),
-                                reinterpret_cast<const float*>(m + o_qw), n_queries, n_slots, k1, b_param, avgdl, k, n_cand,
-                                reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs), reinterpret_cast<uint32_t*>(m + o_hc),
-                                reinterpret_cast<uint64_t*>(m + o_mc), reinterpret_cast<uint64_t*>(m + o_cnt), s);
+        VPT_TRY(postings_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), n_terms, n_post, doc_base, n_documents, A.dl.at(m), A.qoff.at(m),
+                                       A.qterms.at(m), A.qweights.at(m), n_queries, n_slots, k1, b_param, avgdl, k, n_cand, A.hit_docs.at(m),
+                                       A.hit_scores.at(m), A.hit_counts.at(m), A.match_counts.at(m), A.counts.at(m), s));
     else
-        st = postings_boolean_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
-                                reinterpret_cast<const uint32_t*>(m + o_tfs), n_terms, n_post, doc_base, n_documents, reinterpret_cast<const uint32_t*>(m + o_dl),
-                                reinterpret_cast<const uint64_t*>(m + o_qoff), reinterpret_cast<const int32_t*>(m + o_qt),
-                                reinterpret_cast<const float*>(m + o_qw), m + o_qo, n_queries, n_slots, k1, b_param, avgdl, k, n_cand,
-                                reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs), reinterpret_cast<uint32_t*>(m + o_hc),
-                                reinterpret_cast<uint64_t*>(m + o_mc), reinterpret_cast<uint64_t*>(m + o_cnt), s);
-    if (st != VPT_OK) return st;
-    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    VPT_HIP(hipMemcpy(counts_out, m + o_cnt, 24, hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_counts_out, m + o_hc, 4 * size_t(n_queries), hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(match_counts_out, m + o_mc, 8 * size_t(n_queries), hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
-    return VPT_OK;
+        VPT_TRY(postings_boolean_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), n_terms, n_post, doc_base, n_documents, A.dl.at(m),
+                                               A.qoff.at(m), A.qterms.at(m), A.qweights.at(m), A.qoccurs.at(m), n_queries, n_slots, k1, b_param, avgdl, k,
+                                               n_cand, A.hit_docs.at(m), A.hit_scores.at(m), A.hit_counts.at(m), A.match_counts.at(m), A.counts.at(m), s));
+    VPT_TRY(vpt_batch_sync(b));
+    return A.read_back(m, counts_out, hit_counts_out, match_counts_out, hit_docs_out, hit_scores_out, nullptr);
 }
 }  // namespace
 
@@ -1385,80 +1391,35 @@ vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* te
     if (!term_offsets || !post_first || !query_offsets || !query_weights || !hit_docs_out || !hit_scores_out || !hit_freqs_out || !hit_counts_out ||
         !match_counts_out || !counts_out)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    if (n_terms == 0 || n_terms > vpt::kPostingsMaxTerms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
-    if (n_queries == 0 || n_queries > vpt::kSearchMaxQueries) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
-    if (k == 0 || uint64_t(n_queries) * k >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(check_n_queries(n_queries));
+    VPT_TRY(check_top_k(n_queries, k));
     const uint64_t n_post = term_offsets[n_terms], n_slots = query_offsets[n_queries];
-    if (n_post >= (1ull << 32) || n_slots >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    VPT_TRY(check_search_sizes(true, n_post, n_slots));
     const uint64_t n_pos = post_first[n_post];
-    if (n_pos >= (1ull << 32))
-        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
+    VPT_TRY(check_search_sizes(true, n_pos));
     if ((n_post && (!post_docs || !post_tfs)) || (n_pos && !post_positions) || (n_documents && !doc_lens) || (n_slots && !query_terms))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
-    uint64_t n_probes = 0;   // (arrays that are no segment's or no CSR: the device reports them; a query is then counted as 0)
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        const uint64_t a = query_offsets[q], e = query_offsets[q + 1];
-        if (a >= e || e > n_slots || e - a > vpt::kPhraseMaxTerms) continue;
-        uint64_t best = ~uint64_t(0);
-        for (uint64_t s = a; s < e && best; ++s) {
-            const int32_t t = query_terms[s];
-            if (t < 0 || uint32_t(t) >= n_terms) { best = 0; break; }
-            const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
-            if (ta >= tb || tb > n_post || post_first[ta] > post_first[tb] || post_first[tb] > n_pos) { best = 0; break; }
-            best = std::min(best, post_first[tb] - post_first[ta]);
-        }
-        n_probes += best;
-        if (n_probes >= (1ull << 32))
-            return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call");
-    }
-    if (n_documents > (1ull << 32)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t n_out = size_t(n_queries) * k;
-    const size_t o_term = 0, o_docs = o_term + pad(8 * (size_t(n_terms) + 1)), o_tfs = o_docs + pad(4 * size_t(n_post) + 4), o_first = o_tfs + pad(4 * size_t(n_post) + 4),
-                 o_pos = o_first + pad(8 * (size_t(n_post) + 1)), o_dl = o_pos + pad(4 * size_t(n_pos) + 4), o_qoff = o_dl + pad(4 * size_t(n_documents) + 4),
-                 o_qt = o_qoff + pad(8 * (size_t(n_queries) + 1)), o_qw = o_qt + pad(4 * size_t(n_slots) + 4), o_hd = o_qw + pad(4 * size_t(n_queries)),
-                 o_hs = o_hd + pad(4 * n_out), o_hf = o_hs + pad(4 * n_out), o_hc = o_hf + pad(4 * n_out), o_mc = o_hc + pad(4 * size_t(n_queries)),
-                 o_cnt = o_mc + pad(8 * size_t(n_queries));
+    const uint64_t n_probes = phrase_probes(term_offsets, post_first, n_terms, n_post, n_pos, query_offsets, query_terms, n_queries, n_slots);
+    VPT_TRY(check_search_sizes(true, n_probes));
+    VPT_TRY(check_doc_range(0, n_documents));
+    const SearchMem A(n_terms, n_post, n_pos, n_documents, n_queries, n_slots, k, true, false);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
-    vpt_status st;
-    if ((st = acquire(p, &w)) != VPT_OK) return st;
+    VPT_TRY(acquire(p, &w));
     vpt_batch* b = w.b;
     hipStream_t s = b->own_stream;
     DevBuf<unsigned char> mem;
-    if ((st = mem.alloc(o_cnt + 256)) != VPT_OK) return st;
+    VPT_TRY(mem.alloc(A.c.bytes()));
     unsigned char* m = mem;
-    VPT_HIP(hipMemcpyAsync(m + o_term, term_offsets, 8 * (size_t(n_terms) + 1), hipMemcpyHostToDevice, s));
-    if (n_post) {
-        VPT_HIP(hipMemcpyAsync(m + o_docs, post_docs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
-        VPT_HIP(hipMemcpyAsync(m + o_tfs, post_tfs, 4 * size_t(n_post), hipMemcpyHostToDevice, s));
-    }
-    VPT_HIP(hipMemcpyAsync(m + o_first, post_first, 8 * (size_t(n_post) + 1), hipMemcpyHostToDevice, s));
-    if (n_pos) VPT_HIP(hipMemcpyAsync(m + o_pos, post_positions, 4 * size_t(n_pos), hipMemcpyHostToDevice, s));
-    if (n_documents) VPT_HIP(hipMemcpyAsync(m + o_dl, doc_lens, 4 * size_t(n_documents), hipMemcpyHostToDevice, s));
-    VPT_HIP(hipMemcpyAsync(m + o_qoff, query_offsets, 8 * (size_t(n_queries) + 1), hipMemcpyHostToDevice, s));
-    if (n_slots) VPT_HIP(hipMemcpyAsync(m + o_qt, query_terms, 4 * size_t(n_slots), hipMemcpyHostToDevice, s));
-    VPT_HIP(hipMemcpyAsync(m + o_qw, query_weights, 4 * size_t(n_queries), hipMemcpyHostToDevice, s));
-    VPT_HIP(hipMemsetAsync(m + o_hd, 0, o_hc - o_hd, s));   // an entry at or behind a query's hit count is not written on the device: zeros come back
-    st = postings_phrase_search_device(p, b, reinterpret_cast<const uint64_t*>(m + o_term), reinterpret_cast<const uint32_t*>(m + o_docs),
-                                       reinterpret_cast<const uint32_t*>(m + o_tfs), reinterpret_cast<const uint64_t*>(m + o_first),
-                                       reinterpret_cast<const uint32_t*>(m + o_pos), n_terms, n_post, n_pos, doc_base, n_documents,
-                                       reinterpret_cast<const uint32_t*>(m + o_dl), reinterpret_cast<const uint64_t*>(m + o_qoff),
-                                       reinterpret_cast<const int32_t*>(m + o_qt), reinterpret_cast<const float*>(m + o_qw), n_queries, n_slots, k1, b_param,
-                                       avgdl, k, n_probes, reinterpret_cast<uint32_t*>(m + o_hd), reinterpret_cast<float*>(m + o_hs),
-                                       reinterpret_cast<uint32_t*>(m + o_hf), reinterpret_cast<uint32_t*>(m + o_hc), reinterpret_cast<uint64_t*>(m + o_mc),
-                                       reinterpret_cast<uint64_t*>(m + o_cnt), s);
-    if (st != VPT_OK) return st;
-    if ((st = vpt_batch_sync(b)) != VPT_OK) return st;
-    VPT_HIP(hipMemcpy(counts_out, m + o_cnt, 24, hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_counts_out, m + o_hc, 4 * size_t(n_queries), hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(match_counts_out, m + o_mc, 8 * size_t(n_queries), hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_docs_out, m + o_hd, 4 * n_out, hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_scores_out, m + o_hs, 4 * n_out, hipMemcpyDeviceToHost));
-    VPT_HIP(hipMemcpy(hit_freqs_out, m + o_hf, 4 * n_out, hipMemcpyDeviceToHost));
-    return VPT_OK;
+    VPT_TRY(A.upload(m, s, term_offsets, post_docs, post_tfs, post_first, post_positions, doc_lens, query_offsets, query_terms, query_weights, nullptr));
+    VPT_TRY(A.clear_hits(m, s));
+    VPT_TRY(postings_phrase_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
+                                          n_documents, A.dl.at(m), A.qoff.at(m), A.qterms.at(m), A.qweights.at(m), n_queries, n_slots, k1, b_param, avgdl, k,
+                                          n_probes, A.hit_docs.at(m), A.hit_scores.at(m), A.hit_freqs.at(m), A.hit_counts.at(m), A.match_counts.at(m),
+                                          A.counts.at(m), s));
+    VPT_TRY(vpt_batch_sync(b));
+    return A.read_back(m, counts_out, hit_counts_out, match_counts_out, hit_docs_out, hit_scores_out, hit_freqs_out);
 }
 
 // ---- pinned host memory for callers that want the PCIe link at full rate

@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "model.hpp"
 #include "pattern_tagger.hpp"
+#include "scratch_carve.hpp"
 #include "tables.hpp"
 #include "tag_stop.hpp"
 #include "tag_vocab.hpp"
@@ -38,6 +39,11 @@ vpt_status fail(vpt_status st, const std::string& msg) {
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess)                                                                          \
             return fail(VPT_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); \
+    } while (0)
+#define VPT_TRY(expr)                       \
+    do {                                    \
+        const vpt_status s_ = (expr);       \
+        if (s_ != VPT_OK) return s_;        \
     } while (0)
 
 // Experiment / test knobs from the environment (tools/README.md).  Read ONCE -- the table-level ones when a predictor is made
@@ -388,7 +394,7 @@ struct vpt_batch {
     DevBuf<uint64_t> d_ftoff, d_filt;
     DevBuf<int32_t> d_fids;                                         // vpt_token_stream_ids_batch: the ids beside the filter's arrays
     DevBuf<uint4> d_vrec;                                           // vpt_vocab_count_batch_device: two words per token (VocabCountParams::rec)
-    DevBuf<unsigned char> d_post;                                   // vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_merge_positional_device: PostingsMergePosParams (32 bytes more a segment; ordered a second table, general 16 bytes more a place); vpt_postings_search_device: PostingsSearchParams; vpt_postings_phrase_search_device: PostingsPhraseParams (36 bytes a query, 48 bytes a probe place, the histograms)
+    DevBuf<unsigned char> d_post;                                   // (the layouts: scratch_carve.hpp) vpt_postings_batch_device: keys, documents, index arrays, flags, scan, histograms (PostingsParams); vpt_postings_merge_device: PostingsMergeParams; vpt_postings_merge_positional_device: PostingsMergePosParams (32 bytes more a segment; ordered a second table, general 16 bytes more a place); vpt_postings_search_device: PostingsSearchParams; vpt_postings_phrase_search_device: PostingsPhraseParams (36 bytes a query, 48 bytes a probe place, the histograms)
     DevBuf<uint64_t> d_chain;                                       // vpt_tokenize_batch: where a chunk's tokenized text starts (EmitOut::chain_in / chain_out)
     // what the last fill_tags on this workspace left (TagParams, kernels.hpp): a record per token that has a tag model, sorted by position
     DevBuf<uint4> d_tag_records;
@@ -483,6 +489,52 @@ struct vpt_predictor {
 };
 
 namespace {
+
+// The argument checks that the postings calls repeat (capi_device.cpp, capi_host.cpp): one per concept, each with its one message.
+inline vpt_status bad_argument(bool bad, const char* msg) { return bad ? fail(VPT_INVALID_ARGUMENT, msg) : VPT_OK; }
+vpt_status check_batch(const vpt_predictor* p, const vpt_batch* b) {
+    return bad_argument(!p || !b || b->pred != p, "InvalidArgumentError: batch: does not belong to this predictor");
+}
+vpt_status check_n_terms(uint32_t n_terms) {
+    return bad_argument(n_terms == 0 || n_terms > vpt::kPostingsMaxTerms, "InvalidArgumentError: n_terms: must be between 1 and 2^24");
+}
+vpt_status check_n_queries(uint32_t n_queries) {
+    return bad_argument(n_queries == 0 || n_queries > vpt::kSearchMaxQueries, "InvalidArgumentError: n_queries: must be between 1 and 2^24");
+}
+vpt_status check_top_k(uint32_t n_queries, uint32_t k) {
+    return bad_argument(k == 0 || uint64_t(n_queries) * k >= (1ull << 32), "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32");
+}
+vpt_status check_doc_range(uint64_t doc_base, uint64_t n_documents) {
+    return bad_argument(doc_base > (1ull << 32) || n_documents > (1ull << 32) - doc_base,
+                        "InvalidArgumentError: doc_base: doc_base + n_documents must not exceed 2^32");
+}
+vpt_status check_n_segments(size_t n_segments) {
+    return bad_argument(n_segments == 0 || n_segments > vpt::kPostingsMergeMaxSegments, "InvalidArgumentError: n_segments: must be between 1 and 1024");
+}
+vpt_status check_pass_tokens(uint64_t capacity_in) {
+    return bad_argument(capacity_in >= (1ull << 32), "InvalidArgumentError: capacity: the postings pass takes fewer than 2^32 tokens per call");
+}
+// a segment's places (positions) behind the `sum` of those in front of it
+vpt_status check_merge_places(uint64_t sum, uint64_t n) {
+    return bad_argument(n >= (1ull << 32) || sum + n >= (1ull << 32),
+                        "InvalidArgumentError: capacity: the postings merge takes fewer than 2^32 input places per call");
+}
+vpt_status check_merge_positions(uint64_t sum, uint64_t n) {
+    return bad_argument(n >= (1ull << 32) || sum + n >= (1ull << 32),
+                        "InvalidArgumentError: capacity_positions: the postings merge takes fewer than 2^32 positions per call");
+}
+// segment s of a merge's `segments`, a plain one as a positional one without position arrays
+vpt_postings_positional_segment merge_segment(const void* segments, bool positional, size_t s) {
+    if (positional) return static_cast<const vpt_postings_positional_segment*>(segments)[s];
+    const vpt_postings_segment& in = static_cast<const vpt_postings_segment*>(segments)[s];
+    return vpt_postings_positional_segment{in.d_term_offsets, in.d_post_docs, in.d_post_tfs, nullptr, nullptr, in.n_terms, in.capacity, 0};
+}
+// two of a search's sizes (slots, postings, positions, candidates, places, probes); phrase: the phrase search's words
+vpt_status check_search_sizes(bool phrase, uint64_t a, uint64_t b = 0) {
+    return bad_argument(a >= (1ull << 32) || b >= (1ull << 32),
+                        phrase ? "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call"
+                               : "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
+}
 
 vpt_status compile(const uint8_t* bytes, size_t len, int predict_tags, vpt::CompiledModel* out) {
     if (!bytes) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: model_bytes: must not be NULL");

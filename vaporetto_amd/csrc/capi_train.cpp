@@ -192,11 +192,6 @@ struct vpt_trainer {
 namespace {
 
 vpt_status fail_arg(const std::string& msg) { return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: " + msg); }
-#define VPT_TRY(expr)                       \
-    do {                                    \
-        const vpt_status s_ = (expr);       \
-        if (s_ != VPT_OK) return s_;        \
-    } while (0)
 
 // the handle of a call that needs a trainer made with VPT_TRAIN_TAGS; args: the call's other pointers are there.  NULL: the error is set
 vpt_trainer* tag_trainer(void* th, bool args) {
