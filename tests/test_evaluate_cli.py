@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import devmem, emu, evalref, kat
+from tests.evalsuite import merge_tokens, oracle_system
 from vaporetto_amd import _lib, api, build
 from vaporetto_amd import evaluate as cli
 from vaporetto_amd.modelfmt import encode_model
@@ -121,11 +122,14 @@ def test_evaluate_batch_hand_counts_on_emulator(emulated):
 
 
 def test_evaluate_after_short_host_predicts_on_emulator(emulated):
-    """a pooled workspace that a host predict call left with a short longest-sentence hint scores long gold lines all the same"""
+    """a pooled workspace that a host predict call left with a short longest-sentence hint scores long gold lines all the same; the counters are
+    the restatement's over the oracle's system side (a tenth of the gold tokens are merged ones)"""
     raw = open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()
     pred = api.Predictor(api.Model.read_slice(raw)[0], True)
-    line = " ".join(["火星", "猫", "は", "まぁ", "社長"] * 200)   # 1 600 chars
+    line = merge_tokens(" ".join(["火星", "猫", "は", "まぁ", "社長"] * 200), 200)   # 1 600 chars
     first = pred.evaluate([line])
+    want = evalref.evaluate([line], oracle_system(raw, pred._model.tag_models(), [], False, False))
+    assert {k: first[k] for k in want} == want and min(want["fp"], want["tp"]) > 0 and 0 < want["n_cor"] < want["n_ref"]
     utf8, boff = api.pack_texts([b"ab", b"cd"])
     pred.predict_packed(utf8, boff)
     again = pred.evaluate([line], predict_tags=True)

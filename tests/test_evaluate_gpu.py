@@ -10,8 +10,8 @@ import sys
 import numpy as np
 import pytest
 
-from oracle import cbind
 from tests import devmem, evalref, kat
+from tests.evalsuite import merge_tokens, oracle_system as _oracle_system
 from tests.test_evaluate_cli import KAT_GOLD, MODES, _expected
 from tests.test_tokenized_parse import _expect, check_parsed, random_line
 from vaporetto_amd import _lib, api, build
@@ -64,42 +64,6 @@ def test_kat_hand_counts(mode):
     for gold in KAT_GOLD:
         r = p.evaluate([gold[0]], **MODES[mode])
         assert {k: r[k] for k in _expected(gold, mode)} == _expected(gold, mode), gold[0]
-
-
-def _oracle_system(raw_model, tag_models, types, graphemes, predict_tags):
-    """the system side of evalref.evaluate from the CPU oracle: the CLI's loop (evaluate/src/main.rs:103-121) -- KyteaFullwidthFilter
-    on the text, predict, KyteaWsConstFilter (a boundary between two chars of one of `types` becomes NotWordBoundary,
-    kytea_wsconst.rs:26-43), ConcatGraphemeClustersFilter, fill_tags"""
-    orc = cbind.OraclePredictor(raw_model, predict_tags=True)
-
-    def system(raws, normalised):
-        texts = [api.KyteaFullwidthFilter().filter(t) for t in raws] if normalised else list(raws)
-        utf8, boff = api.pack_texts([t.encode("utf-8") for t in texts])
-        _, labels, ooff, _ = orc.predict_batch(utf8, boff)
-        labels = labels.copy()
-        for i, t in enumerate(texts):
-            ty = api._types_of(np.frombuffer(t.encode("utf-32-le"), dtype=np.uint32))
-            for b in range(len(t) - 1):
-                if ty[b] == ty[b + 1] and int(ty[b]) in types:
-                    labels[int(ooff[i]) + b] = 0
-        if graphemes:
-            api.ConcatGraphemeClustersFilter().filter_packed(texts, ooff, labels)
-        sys_b = [list(labels[int(ooff[i]):int(ooff[i + 1])]) for i in range(len(texts))]
-        nt = orc.n_tags() if predict_tags else 0
-        if not nt:
-            return sys_b, None
-        tags, _, models = orc.fill_tags_batch(utf8, boff, ooff, labels, want_scores=False)
-        rows = []
-        for i, t in enumerate(texts):
-            g0 = int(ooff[i]) + i
-            rs = []
-            for c in range(len(t)):
-                m = int(models[g0 + c])
-                cand = tag_models[m].tags if m >= 0 else []
-                rs.append([cand[j][tags[g0 + c][j]] if m >= 0 and j < len(cand) and tags[g0 + c][j] >= 0 else None for j in range(nt)])
-            rows.append(rs)
-        return sys_b, rows
-    return system
 
 
 def _corpus(pred, texts):
@@ -184,11 +148,17 @@ def test_chunked_path_gives_the_same_counts():
 
 
 def test_evaluate_after_short_host_predicts():
-    """a pooled workspace that a host predict call left with a short longest-sentence hint scores long gold lines all the same"""
+    """a pooled workspace that a host predict call left with a short longest-sentence hint scores long gold lines all the same; the counters are
+    the restatement's over the oracle's system side (a tenth of the gold tokens are merged ones)"""
     raw = open(os.path.join(ROOT, "tests", "golden", "model.bin"), "rb").read()
     pred = _predictor(raw)
-    lines = [" ".join(["火星", "猫", "は", "まぁ", "社長"] * n) for n in (300, 2000)]   # 2 400 and 16 000 chars
+    lines = [merge_tokens(" ".join(["火星", "猫", "は", "まぁ", "社長"] * n), n) for n in (300, 2000)]   # 2 400 and 16 000 chars
     first = pred.evaluate(lines, predict_tags=True)
+    want = evalref.evaluate(lines, _oracle_system(raw, pred._model.tag_models(), [], False, True), predict_tags=True)
+    assert {k: first[k] for k in want} == want and min(want["fp"], want["tp"]) > 0
+    # (untagged gold lines are never correct against predicted tags) without them the word metric counts: tokens 16 000 chars into a sentence
+    plain, want = pred.evaluate(lines), evalref.evaluate(lines, _oracle_system(raw, pred._model.tag_models(), [], False, False))
+    assert {k: plain[k] for k in want} == want and 0 < want["n_cor"] < want["n_ref"]
     pred.predict_packed(*api.pack_texts([b"ab", b"cd"]))
     again = pred.evaluate(lines, predict_tags=True)
     assert again == first or all(again[k] == first[k] for k in ("tp", "tn", "fp", "fn", "n_sys", "n_ref", "n_cor", "n_sentences"))
