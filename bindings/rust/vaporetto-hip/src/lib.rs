@@ -624,6 +624,65 @@ impl Postings {
         Ok((hits, match_counts))
     }
 
+    /// BM25 top-k of every boolean query of CLAUSES over this segment and its position lists (`vpt_postings_clause_search`; the definition is in
+    /// include/vaporetto_hip.h).  `first` and `positions`: as in `phrase_search`.  A clause is `(terms, occur)`, occur 0 SHOULD, 1 MUST, 2
+    /// MUST_NOT: a clause of one term is a slot of that term, as in `boolean_search`; every other clause is ONE exact phrase scored by its
+    /// phrase frequency (an id outside the vocabulary makes it match nothing, and so does an empty clause).  The weight of a MUST or SHOULD
+    /// clause is the phrase weight of `phrase_search` (the f32 sum in slot order of `vpt_okapi_idf` over its terms), of a MUST_NOT clause 0.
+    /// `doc_lens`, avgdl and the return value: as in `search`.
+    pub fn clause_search(&self, predictor: &Predictor, first: &[u64], positions: &[u32], queries: &[Vec<(Vec<i32>, u8)>], doc_lens: &[u32],
+                         doc_base: u64, k: u32, k1: f32, b: f32)
+                         -> Result<(Vec<Vec<(u32, f32)>>, Vec<u64>)> {
+        if queries.is_empty() {
+            return Ok((Vec::new(), Vec::new()));
+        }
+        let n = self.term_offsets.len();
+        if n == 0 || doc_lens.is_empty() || self.docs.len() != self.tfs.len() || self.term_offsets[n - 1] != self.docs.len() as u64
+            || first.len() != self.docs.len() + 1 || first[first.len() - 1] != positions.len() as u64 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: clause_search: the arrays do not belong together".into()));
+        }
+        let avgdl = (doc_lens.iter().map(|&l| l as f64).sum::<f64>() / doc_lens.len() as f64) as f32;
+        let (mut offsets, mut clause_offsets) = (vec![0u64], vec![0u64]);
+        let (mut terms, mut weights, mut occurs) = (Vec::new(), Vec::new(), Vec::new());
+        for q in queries {
+            for (clause, occur) in q {
+                let mut sum: Option<f32> = None;
+                for &t in clause {
+                    terms.push(t);
+                    if *occur == 2 || t < 0 || (t as usize) >= n - 1 {
+                        continue;
+                    }
+                    let mut w = 0f32;
+                    check(unsafe { ffi::vpt_okapi_idf(doc_lens.len() as u64, self.df(t as usize), &mut w) })?;
+                    sum = Some(match sum { Some(s) => s + w, None => w });
+                }
+                weights.push(sum.unwrap_or(0f32));
+                occurs.push(*occur);
+                clause_offsets.push(terms.len() as u64);
+            }
+            offsets.push(occurs.len() as u64);
+        }
+        terms.push(0);
+        weights.push(0f32);
+        occurs.push(0u8);
+        let mut pos = positions.to_vec();
+        pos.push(0);
+        let n_out = queries.len() * k as usize + 1;
+        let (mut hit_docs, mut hit_scores) = (vec![0u32; n_out], vec![0f32; n_out]);
+        let (mut hit_counts, mut match_counts, mut counts) = (vec![0u32; queries.len()], vec![0u64; queries.len()], [0u64; 3]);
+        check(unsafe {
+            ffi::vpt_postings_clause_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(), first.as_ptr(),
+                                            pos.as_ptr(), (n - 1) as u32, doc_base, doc_lens.len() as u64, doc_lens.as_ptr(), offsets.as_ptr(),
+                                            clause_offsets.as_ptr(), terms.as_ptr(), weights.as_ptr(), occurs.as_ptr(), queries.len() as u32, k1, b,
+                                            avgdl, k, hit_docs.as_mut_ptr(), hit_scores.as_mut_ptr(), hit_counts.as_mut_ptr(),
+                                            match_counts.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        let hits = (0..queries.len())
+            .map(|q| (0..hit_counts[q] as usize).map(|j| (hit_docs[q * k as usize + j], hit_scores[q * k as usize + j])).collect())
+            .collect();
+        Ok((hits, match_counts))
+    }
+
     /// Exact-phrase BM25 top-k of every phrase over this segment and its position lists (`vpt_postings_phrase_search`; the definition is in
     /// include/vaporetto_hip.h).  `first` [postings + 1] and `positions` [indexed tokens]: posting q's positions are
     /// `positions[first[q] .. first[q + 1]]`, strictly ascending (what `vpt_token_stream_positional_postings_batch` returns).  `phrases`: term

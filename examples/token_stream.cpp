@@ -24,7 +24,9 @@
 // the K best documents that hold it are found on the device; the lines of --search, plus <TAB> the phrase's occurrences in the document.
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --boolean "QUERY" [--top K] < documents.txt
 // With --boolean: the query text is split on spaces into clauses, +clause is required, -clause is forbidden, any other is wanted; every token
-// of a clause takes the clause's occur (a clause of several tokens is not a phrase); the lines of --search.
+// of a clause takes the clause's occur; the lines of --search.
+//   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --boolean "QUERY" [--top K] --phrases < documents.txt
+// With --phrases as the last argument: the documents are indexed with positions and a clause of several tokens is ONE exact phrase.
 // With --segment-docs N the positional segments of N documents each are merged on the device with their position lists (the same lines come
 // out; stderr tells "segments <TAB> n <TAB> postings <TAB> n <TAB> positions <TAB> n").
 #include <cstdlib>
@@ -90,6 +92,8 @@ int main(int argc, char** argv) {
             const char* phrase = nullptr;
             const char* boolean = nullptr;
             uint32_t top = 10;
+            bool phrases = false;
+            if (n_args > 7 && std::strcmp(argv[n_args - 1], "--phrases") == 0) { phrases = true; n_args -= 1; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }   // (behind the query, too)
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
@@ -98,7 +102,7 @@ int main(int argc, char** argv) {
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }
             const uint64_t doc_base = n_args > 5 ? std::strtoull(argv[5], nullptr, 10) : 0;
             vaporetto_hip::Postings post;
-            if (phrase) {
+            if (phrase || (boolean && phrases)) {
                 if (segment_docs) {
                     std::vector<std::vector<std::string>> batches;
                     for (size_t a = 0; a < docs.size(); a += segment_docs)
@@ -107,6 +111,15 @@ int main(int argc, char** argv) {
                     std::fprintf(stderr, "segments\t%zu\tpostings\t%zu\tpositions\t%zu\n", batches.size(), post.docs.size(), post.positions.size());
                 } else {
                     post = plain.index(docs, vocab, doc_base, true, true);
+                }
+                if (boolean) {
+                    const auto found = plain.boolean_search(post, vocab, {std::string(boolean)}, plain.doc_lens(docs, vocab), doc_base, top, 1.2f, 0.75f, true, true);
+                    for (const vaporetto_hip::Postings::Hit& h : found.hits[0]) {
+                        uint32_t bits;
+                        std::memcpy(&bits, &h.score, 4);
+                        std::printf("%u\t%08x\t%.9g\n", unsigned(h.document), unsigned(bits), double(h.score));
+                    }
+                    return 0;
                 }
                 const auto found = plain.phrase_search(post, vocab, {std::string(phrase)}, plain.doc_lens(docs, vocab), doc_base, top);
                 for (const vaporetto_hip::Postings::PhraseHit& h : found.hits[0]) {

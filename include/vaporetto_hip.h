@@ -915,6 +915,96 @@ vpt_status vpt_token_stream_positional_postings_batch(const vpt_predictor *p, co
                                                       uint64_t *n_postings_out, uint64_t *n_dropped_out, uint64_t *n_positions_out);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Phrase clauses in boolean queries: phrases to posting lists, the boolean search over a segment and such lists      (tantivy's query parser
+ *                                                            makes a clause of several tokens a PhraseQuery inside the BooleanQuery: `+東京都`)
+ *
+ * vpt_postings_phrase_lists_device: a batch of phrases against ONE positional segment, each phrase's matching documents out as a posting list.
+ *   Segment: d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings, capacity_positions, doc_base
+ *   and n_documents as vpt_postings_phrase_search_device takes them (doc_base and n_documents for the range checks; no doc_lens, weights, k1,
+ *   b, avgdl or k).  Phrases, a CSR: d_phrase_offsets [n_phrases + 1], d_phrase_terms int32 [capacity_slots].  capacity_probes: as in the
+ *   phrase search.
+ *   Out: d_list_offsets uint64 [n_phrases + 1], d_list_docs / d_list_tfs uint32 [capacity_lists]: list q is the entries
+ *   [d_list_offsets[q], d_list_offsets[q + 1]); d_list_docs holds the GLOBAL numbers of the documents that match phrase q, ascending, and
+ *   d_list_tfs their pf >= 1; d_list_offsets[0] = 0, entries at or behind d_list_offsets[n_phrases] are not written.  d_counts [3] = the
+ *   probes, the list entries of all phrases, the skipped phrases.
+ *   pf and "matches" are vpt_postings_phrase_search_device's: slop 0, 64-bit starts, a repeated term is two distinct places.  A phrase matches
+ *   nothing and its list is empty when it is empty, has a slot outside [0, n_terms) (it adds 1 to d_counts[2]) or has a term of df 0.  A phrase
+ *   of one in-range term has that term's own list: its documents and its tfs.
+ *   A phrase's list never has more entries than the smallest df among its terms: the sum of those over the phrases always suffices as
+ *   capacity_lists.
+ *   Launches: the phrase search's queries, scan, probe, scan, heads and scan as they stand (no weight is looked at), then lists
+ *   (kernels_postings_phrase.hip): a lane per place, a head writes {doc_base + document, pf} at its scan index -- entries are born in (phrase,
+ *   document) order; a lane per phrase bound writes d_list_offsets by the phrase search's ranges rule.  No sort, no take.  Nothing is sized
+ *   from a value read back, no atomic decides a value, two runs give identical bytes.  Scratch of the workspace: the phrase search's.
+ *   At the call, VPT_INVALID_ARGUMENT: a NULL pointer, n_terms == 0 or > 2^24, "n_phrases: must be between 1 and 2^24", capacity_slots or
+ *   capacity_probes >= 2^32 (the phrase search's message), "capacity_lists: must be below 2^32", doc_base + n_documents above 2^32, a
+ *   workspace of another predictor.
+ *   At the sync, VPT_INVALID_ARGUMENT: the segment and query_offsets messages and the 64-term limit of vpt_postings_phrase_search_device;
+ *   capacity_probes too small (d_counts[0] holds the need); "InvalidArgumentError: capacity_lists: smaller than the number of list entries"
+ *   (d_counts[1] holds the need).  After any of these the three list arrays are as they were before the call.  Whatever the arrays hold,
+ *   nothing is read outside the stated sizes and nothing is written outside d_list_offsets [n_phrases + 1], d_list_docs / d_list_tfs
+ *   [capacity_lists], d_counts [3] and the workspace.
+ *
+ * vpt_postings_clause_search_device: vpt_postings_boolean_search_device over a segment PLUS derived lists.  Every argument of that call with
+ *   the same meaning, and d_list_offsets uint64 [n_lists + 1], d_list_docs / d_list_tfs uint32 [capacity_lists], n_lists
+ *   (n_terms + n_lists <= 2^24), capacity_lists (< 2^32): what the lists call wrote, or any arrays of that shape.  n_lists may be 0; the three
+ *   pointers are then not looked at.
+ *   A slot whose d_query_terms value t lies in [n_terms, n_terms + n_lists) names list t - n_terms, and is for the rest of the rule a term
+ *   whose list is that list: has-document, df (d_list_offsets[i + 1] - d_list_offsets[i]), the anchor choice (the first MUST slot of the
+ *   smallest df, read on the device), the veto, and c from the entry's tf -- for a list of the lists call c is bm25 of (w, pf, dl): the
+ *   bits vpt_postings_phrase_search_device gives the phrase under the same weight.  A value at or above n_terms + n_lists or below 0 is out
+ *   of range as in the boolean search.  Everything else of vpt_postings_boolean_search_device's definition, order, outputs, counts, places and
+ *   determinism holds verbatim; with n_lists = 0 the four outputs and the counts are that call's, byte for byte.
+ *   Launches: the boolean search's three kernels as one body over one or two segments (kernels_postings_boolean.hip), then the OR search's
+ *   launches from the first sort on.  Scratch: the boolean search's.
+ *   THE STATUS IS STICKY until vpt_batch_sync: a lists call and a clause search enqueued on one stream with no sync between them is the
+ *   intended use, and an error of the lists call (or of anything else enqueued since the last sync that sets one of the search, phrase or lists
+ *   bits) leaves the clause search's four outputs as they were before the call.
+ *   At the call: the boolean search's list; a NULL list pointer with n_lists > 0; "InvalidArgumentError: n_lists: n_terms + n_lists must
+ *   not exceed 2^24"; "InvalidArgumentError: capacity_lists: must be below 2^32".
+ *   At the sync: the boolean search's list; a derived list is checked as a segment's list is (bounds that descend or end above
+ *   capacity_lists, and in a list that deals out places a tf of 0, a document outside the range or not above the one before it, are
+ *   "segment: term_offsets or postings are not a segment's").  Whatever the arrays hold, nothing is read outside the boolean search's sizes,
+ *   d_list_offsets [n_lists + 1] and [0, capacity_lists) of the two list arrays, and nothing is written outside the four outputs, d_counts
+ *   [3] and the workspace.
+ *
+ * vpt_postings_phrase_lists: the lists call over HOST arrays; the probes are counted on the host, capacity_lists is the size of the caller's
+ *   list_docs_out / list_tfs_out.  counts_out [3] comes back after an error at the sync too (the need).
+ * vpt_postings_clause_search: queries of CLAUSES over a host positional segment.  query_offsets [n_queries + 1] is a CSR over the clauses,
+ *   clause_offsets [clauses + 1] a CSR over clause_terms; clause_weights / clause_occurs: one per clause.  A clause of exactly one term is a
+ *   slot of that term; every other clause is a phrase (an empty one matches nothing) whose list the lists call makes and whose slot names
+ *   that list.  One upload, the two device calls with no sync between them, one download; the probes, list entries and places are counted on
+ *   the host by the bounds above.  counts_out [3] = the places, the matches, the skipped slots plus the phrases with a term out of range. */
+vpt_status vpt_postings_phrase_lists_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets, const uint32_t *d_post_docs,
+                                            const uint32_t *d_post_tfs, const uint64_t *d_post_first, const uint32_t *d_post_positions,
+                                            uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                            uint64_t n_documents, const uint64_t *d_phrase_offsets, const int32_t *d_phrase_terms,
+                                            uint32_t n_phrases, uint64_t capacity_slots, uint64_t capacity_probes, uint64_t *d_list_offsets,
+                                            uint32_t *d_list_docs, uint32_t *d_list_tfs, uint64_t capacity_lists, uint64_t *d_counts,
+                                            void *hip_stream);
+vpt_status vpt_postings_clause_search_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets, const uint32_t *d_post_docs,
+                                             const uint32_t *d_post_tfs, uint32_t n_terms, uint64_t capacity_postings,
+                                             const uint64_t *d_list_offsets, const uint32_t *d_list_docs, const uint32_t *d_list_tfs,
+                                             uint32_t n_lists, uint64_t capacity_lists, uint64_t doc_base, uint64_t n_documents,
+                                             const uint32_t *d_doc_lens, const uint64_t *d_query_offsets, const int32_t *d_query_terms,
+                                             const float *d_query_weights, const uint8_t *d_query_occurs, uint32_t n_queries,
+                                             uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                             uint64_t capacity_candidates, uint32_t *d_hit_docs, float *d_hit_scores, uint32_t *d_hit_counts,
+                                             uint64_t *d_match_counts, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_phrase_lists(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs, const uint32_t *post_tfs,
+                                     const uint64_t *post_first, const uint32_t *post_positions, uint32_t n_terms, uint64_t doc_base,
+                                     uint64_t n_documents, const uint64_t *phrase_offsets, const int32_t *phrase_terms, uint32_t n_phrases,
+                                     uint64_t *list_offsets_out, uint32_t *list_docs_out, uint32_t *list_tfs_out, uint64_t capacity_lists,
+                                     uint64_t *counts_out);
+vpt_status vpt_postings_clause_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs, const uint32_t *post_tfs,
+                                      const uint64_t *post_first, const uint32_t *post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t *doc_lens, const uint64_t *query_offsets,
+                                      const uint64_t *clause_offsets, const int32_t *clause_terms, const float *clause_weights,
+                                      const uint8_t *clause_occurs, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                      uint32_t *hit_docs_out, float *hit_scores_out, uint32_t *hit_counts_out, uint64_t *match_counts_out,
+                                      uint64_t *counts_out);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Merging POSITIONAL segments on the device: phrase search over a corpus indexed in batches          (no item of the adapter: the merge above
  *                                                                         with the position lists carried along, so the merged index serves phrases)
  *

@@ -509,7 +509,71 @@ struct Postings {
     PhraseResult phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases, const std::vector<uint32_t>& doc_lens,
                                uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
                                const std::vector<float>* weights = nullptr) const;
+    // BM25 top-k of every boolean query of CLAUSES over this POSITIONAL segment (vpt_postings_clause_search; the definition is in
+    // vaporetto_hip.h).  A clause of one term is a slot of that term, as in boolean_search; every other clause is ONE exact phrase scored by
+    // its phrase frequency (an id outside [0, n_terms) makes it match nothing, and so does an empty clause).  weights: shaped as queries, or
+    // nullptr for the phrase weight of phrase_search per MUST / SHOULD clause and 0 per MUST_NOT clause.  counts of the result: the places, the
+    // matches, the skipped clauses.
+    struct PhraseClause { std::vector<int32_t> terms; uint8_t occur; };
+    SearchResult clause_search(const Predictor& predictor, const std::vector<std::vector<PhraseClause>>& queries, const std::vector<uint32_t>& doc_lens,
+                               uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
+                               const std::vector<std::vector<float>>* weights = nullptr) const;
 };
+
+inline Postings::SearchResult Postings::clause_search(const Predictor& predictor, const std::vector<std::vector<PhraseClause>>& queries,
+                                                      const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
+                                                      const std::vector<std::vector<float>>* weights) const {
+    SearchResult out;
+    if (queries.empty()) return out;
+    if (first.size() != docs.size() + 1)
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: clause_search: the postings were made without positions");
+    if (term_offsets.empty() || doc_lens.empty() || (weights && weights->size() != queries.size()) || docs.size() != tfs.size() ||
+        term_offsets.back() != docs.size() || first.back() != positions.size())
+        throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: clause_search: the arrays do not belong together");
+    double total = 0;
+    for (uint32_t l : doc_lens) total += double(l);
+    const float avgdl = float(total / double(doc_lens.size()));
+    std::vector<uint64_t> qoff(1, 0), coff(1, 0);
+    std::vector<int32_t> terms;
+    std::vector<float> w;
+    std::vector<uint8_t> occurs;
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (weights && (*weights)[q].size() != queries[q].size())
+            throw VaporettoError(VaporettoError::InvalidArgument, "InvalidArgumentError: weights: not shaped as the queries");
+        for (size_t j = 0; j < queries[q].size(); ++j) {
+            const PhraseClause& c = queries[q][j];
+            float sum = 0.0f;
+            bool any = false;
+            for (const int32_t t : c.terms) {
+                terms.push_back(t);
+                if (weights || c.occur == VPT_OCCUR_MUST_NOT || t < 0 || size_t(t) >= n_terms()) continue;
+                float x = 0.0f;
+                detail::check(vpt_okapi_idf(doc_lens.size(), df(size_t(t)), &x));
+                sum = any ? sum + x : x;
+                any = true;
+            }
+            w.push_back(weights ? (*weights)[q][j] : sum);
+            occurs.push_back(c.occur);
+            coff.push_back(terms.size());
+        }
+        qoff.push_back(occurs.size());
+    }
+    terms.push_back(0); w.push_back(0.0f); occurs.push_back(0);   // (data() of an empty vector may be NULL)
+    std::vector<uint32_t> pos(positions);
+    pos.push_back(0);
+    const size_t n_out = queries.size() * size_t(k) + 1;
+    std::vector<uint32_t> hd(n_out), hc(queries.size());
+    std::vector<float> hs(n_out);
+    out.match_counts.assign(queries.size(), 0);
+    detail::check(vpt_postings_clause_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(), uint32_t(n_terms()),
+                                             doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), coff.data(), terms.data(), w.data(), occurs.data(),
+                                             uint32_t(queries.size()), k1, b, avgdl, k, hd.data(), hs.data(), hc.data(), out.match_counts.data(),
+                                             out.counts));
+    out.hits.resize(queries.size());
+    for (size_t q = 0; q < queries.size(); ++q)
+        for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(Hit{hd[q * size_t(k) + j], hs[q * size_t(k) + j]});
+    return out;
+}
 
 inline Postings::PhraseResult Postings::phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases,
                                                       const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
@@ -906,11 +970,13 @@ public:
 
     // BM25 top-k of boolean query TEXTS over `postings`.  A text is split on ASCII spaces into clauses: one that starts with `+` is MUST, one
     // that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are, and every token
-    // of it is a slot of the clause's occur; an empty clause adds nothing.  A clause of several tokens is NOT made a phrase here (unlike
-    // tantivy's query parser).  Then Postings::boolean_search with the idf weights.
+    // of it is a slot of the clause's occur; an empty clause adds nothing; then Postings::boolean_search with the idf weights.  phrases (what
+    // tantivy's query parser does; `postings` indexed with positions): a clause of several tokens is ONE exact phrase -- a token without a
+    // vocabulary entry makes it match nothing -- a clause of one token a term slot, a clause without a token adds nothing; then
+    // Postings::clause_search with the phrase weights.
     Postings::SearchResult boolean_search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
                                           const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f,
-                                          float b = 0.75f, bool normalize = true) const {
+                                          float b = 0.75f, bool normalize = true, bool phrases = false) const {
         std::vector<std::string> clauses;
         std::vector<std::pair<size_t, uint8_t>> owner;
         for (size_t i = 0; i < texts.size(); ++i) {
@@ -932,6 +998,17 @@ public:
             const auto enc = encode(clauses, vocab, normalize);
             for (size_t c = 0; c < clauses.size(); ++c)
                 for (uint64_t t = enc.first[c]; t < enc.first[c + 1]; ++t) queries[owner[c].first].push_back(Postings::Clause{enc.second[t], owner[c].second});
+        }
+        if (phrases) {
+            std::vector<std::vector<Postings::PhraseClause>> cq(texts.size());
+            if (!clauses.empty()) {
+                const auto enc = encode(clauses, vocab, normalize);
+                for (size_t c = 0; c < clauses.size(); ++c)
+                    if (enc.first[c] < enc.first[c + 1])
+                        cq[owner[c].first].push_back(Postings::PhraseClause{
+                            std::vector<int32_t>(enc.second.begin() + enc.first[c], enc.second.begin() + enc.first[c + 1]), owner[c].second});
+            }
+            return postings.clause_search(predictor_, cq, doc_lens, doc_base, k, k1, b);
         }
         return postings.boolean_search(predictor_, queries, doc_lens, doc_base, k, k1, b);
     }

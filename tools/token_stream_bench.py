@@ -36,6 +36,12 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       with its idf; the phrase search over every phrase's anchor slot alone (the same probes, scans and sort, none of the other slots'
       bisections: the difference is what those bisections cost); and a device-to-device copy of half of 4 bytes a probe plus 12 bytes a hit.
       Q is halved until the probes and the OR search's candidates are at most --search-max-candidates (profiles/postings_phrase_bench.json).
+  --clause Q,L,K: with --postings, Q all-MUST queries over the one-pass segment with its position lists, each one window of L consecutive tokens
+      of a random document as ONE phrase clause plus one SHOULD term drawn by count, top K, by device events: the lists call
+      (vpt_postings_phrase_lists_device), the clause search over its lists, the two chained with no sync between them; the yardsticks of the
+      same process are the parent commit's boolean search over the same tokens as L independent MUST slots plus the SHOULD slot, and its
+      phrase search over the same phrases.  The run checks that the lists' probes and entries are the phrase search's probes and matches and
+      that the clause search's match counts are the phrase search's (profiles/postings_clause_bench.json).
   --count: the vocabulary counter's count call (kernels_vocab_count.hip, three launches) on the same CSR by device events, in the same run as
       --ids: the first call on an empty counter (insert and commit) once, then rounds of calls on the filled counter; finish's wall time once.
 Parity in the same run: the three routes' arrays equal each other on the whole batch, and equal tests/tokenref.py (the restatement on the CPU oracle)
@@ -426,6 +432,137 @@ def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host
     return out
 
 
+def clause_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_term, d_pdocs, d_ptfs, n_post, seg):
+    """--clause Q,L,K over the one-pass segment and its position lists: Q all-MUST queries, each one window of L consecutive tokens of a random
+    document as ONE phrase clause plus one SHOULD term drawn by count.  Timed: the lists call, the clause search over its lists, the two
+    chained with no sync between them; the yardsticks, in the same process: the boolean search over the same tokens as L independent MUST
+    slots (plus the SHOULD slot), and the phrase search over the same phrases"""
+    from vaporetto_amd import api
+    Q, L, K = (int(x) for x in spec.split(","))
+    d_first, d_ppos, n_idx = seg
+    term = d_term.cpu().numpy().astype(np.int64)
+    df = np.diff(term)
+    tfs = d_ptfs[:n_post].cpu().numpy().astype(np.int64)
+    count = np.add.reduceat(np.concatenate([tfs, [0]]), np.minimum(term[:-1], n_post)) * (df > 0)
+    toff = dev_off.astype(np.int64)
+    dl = np.diff(toff)
+    known = (host_ids >= 0) & (host_ids < n_terms)
+    run = np.concatenate([[0], np.cumsum(~known)])
+    long_docs = np.flatnonzero(dl >= L)
+    rng = np.random.default_rng(7)
+    phrases = []
+    for _ in range(64 * Q):
+        if len(phrases) == Q or len(long_docs) == 0:
+            break
+        d = int(long_docs[rng.integers(len(long_docs))])
+        a = int(toff[d]) + int(rng.integers(int(dl[d]) - L + 1))
+        if run[a + L] == run[a]:
+            phrases.append(host_ids[a:a + L].astype(np.int32))
+    if not phrases:
+        raise SystemExit("--clause: no window of %d tokens with vocabulary entries" % L)
+    while True:
+        terms = np.concatenate(phrases)
+        should = rng.choice(n_terms, size=len(phrases), p=count / count.sum()).astype(np.int32)
+        n_probes = int(sum(int(count[ph].min()) for ph in phrases))
+        n_bound = int(sum(int(df[ph].min()) for ph in phrases))   # the list entries at most, and so the places of both searches
+        if max(n_probes, n_bound) <= args.search_max_candidates or len(phrases) == 1:
+            break
+        phrases = phrases[:len(phrases) // 2]
+    Q = len(phrases)
+    idf = {int(t): api.bm25_idf(S, int(df[t])) for t in set(terms.tolist()) | set(should.tolist())}
+    weights = []
+    for ph in phrases:   # tantivy's phrase weight: the float32 sum in slot order
+        w = idf[int(ph[0])]
+        for t in ph[1:]:
+            w = np.float32(w + idf[int(t)])
+        weights.append(w)
+    avgdl = float(np.float32(float(dl.sum()) / S))
+    d_dl = torch.from_numpy(dl.astype(np.int32)).to(dev)
+    d_poff = torch.from_numpy(np.arange(0, Q * L + 1, L, dtype=np.int64)).to(dev)
+    d_pt = torch.from_numpy(terms).to(dev)
+    d_pw = torch.from_numpy(np.array(weights, np.float32)).to(dev)
+    d_loff = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    d_ldocs, d_ltfs = torch.zeros(n_bound + 1, dtype=torch.int32, device=dev), torch.zeros(n_bound + 1, dtype=torch.int32, device=dev)
+    d_lcnt = torch.zeros(3, dtype=torch.int64, device=dev)
+    # the clause search's slots: list q MUST under the phrase weight, the SHOULD term
+    c_terms = np.stack([n_terms + np.arange(Q, dtype=np.int32), should], axis=1).reshape(-1)
+    c_w = np.stack([np.array(weights, np.float32), np.array([idf[int(t)] for t in should], np.float32)], axis=1).reshape(-1)
+    d_cqoff = torch.from_numpy(np.arange(0, 2 * Q + 1, 2, dtype=np.int64)).to(dev)
+    d_cqt, d_cqw = torch.from_numpy(c_terms).to(dev), torch.from_numpy(c_w).to(dev)
+    d_cqo = torch.from_numpy(np.tile(np.array([1, 0], np.uint8), Q)).to(dev)
+    # the boolean yardstick's: the window's tokens as L MUST slots, the SHOULD term
+    b_terms = np.concatenate([np.stack(phrases), should[:, None]], axis=1).reshape(-1).astype(np.int32)
+    d_bqoff = torch.from_numpy(np.arange(0, Q * (L + 1) + 1, L + 1, dtype=np.int64)).to(dev)
+    d_bqt = torch.from_numpy(b_terms).to(dev)
+    d_bqw = torch.from_numpy(np.array([idf[int(t)] for t in b_terms], np.float32)).to(dev)
+    d_bqo = torch.from_numpy(np.tile(np.array([1] * L + [0], np.uint8), Q)).to(dev)
+    d_hd, d_hs, d_hf = (torch.zeros(Q * K, dtype=dt, device=dev) for dt in (torch.int32, torch.float32, torch.int32))
+    d_hc, d_mc, d_cnt = torch.zeros(Q, dtype=torch.int32, device=dev), torch.zeros(Q, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev)
+
+    def lists():
+        batch.phrase_lists_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), d_first.data_ptr(), d_ppos.data_ptr(), n_terms, n_post, n_idx, 0, S,
+                                    d_poff.data_ptr(), d_pt.data_ptr(), Q, Q * L, n_probes, d_loff.data_ptr(), d_ldocs.data_ptr(), d_ltfs.data_ptr(), n_bound,
+                                    d_lcnt.data_ptr(), stream)
+
+    def clause():
+        batch.clause_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, d_loff.data_ptr(), d_ldocs.data_ptr(),
+                                     d_ltfs.data_ptr(), Q, n_bound, 0, S, d_dl.data_ptr(), d_cqoff.data_ptr(), d_cqt.data_ptr(), d_cqw.data_ptr(),
+                                     d_cqo.data_ptr(), Q, 2 * Q, 1.2, 0.75, avgdl, K, n_bound, d_hd.data_ptr(), d_hs.data_ptr(), d_hc.data_ptr(),
+                                     d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+
+    def chained():
+        lists()
+        clause()
+
+    def boolean():
+        batch.boolean_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), n_terms, n_post, 0, S, d_dl.data_ptr(), d_bqoff.data_ptr(),
+                                      d_bqt.data_ptr(), d_bqw.data_ptr(), d_bqo.data_ptr(), Q, Q * (L + 1), 1.2, 0.75, avgdl, K, n_bound, d_hd.data_ptr(),
+                                      d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+
+    def phrase():
+        batch.phrase_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), d_first.data_ptr(), d_ppos.data_ptr(), n_terms, n_post, n_idx,
+                                     0, S, d_dl.data_ptr(), d_poff.data_ptr(), d_pt.data_ptr(), d_pw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K, n_probes,
+                                     d_hd.data_ptr(), d_hs.data_ptr(), d_hf.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(), stream)
+    out = {"spec": spec, "queries": Q, "phrase_terms": L, "k": K, "n_terms": n_terms, "documents": S, "postings": n_post, "positions": n_idx,
+           "list_bound": n_bound}
+    boolean()
+    batch.sync()
+    cnt = d_cnt.cpu().numpy()
+    out.update({"boolean_places": int(cnt[0]), "boolean_matches": int(cnt[1])})
+    phrase()
+    batch.sync()
+    cnt = d_cnt.cpu().numpy()
+    phrase_mc = d_mc.clone()
+    out.update({"probes": int(cnt[0]), "phrase_matches": int(cnt[1])})
+    chained()
+    batch.sync()
+    lcnt, cnt = d_lcnt.cpu().numpy(), d_cnt.cpu().numpy()
+    out.update({"list_entries": int(lcnt[1]), "lists_probes_equal_phrase_search": bool(int(lcnt[0]) == out["probes"]),
+                "list_entries_equal_phrase_matches": bool(int(lcnt[1]) == out["phrase_matches"]), "places": int(cnt[0]), "matches": int(cnt[1]),
+                "places_equal_list_entries": bool(int(cnt[0]) == int(lcnt[1])),   # (every query is anchored on its list: its only MUST slot)
+                "match_counts_equal_phrase_search": bool(torch.equal(d_mc, phrase_mc)), "every_query_matches": bool(int(d_mc.min().item()) >= 1),
+                "hit_counts_sum": int(d_hc.to(torch.int64).sum().item())})
+    for name, fn in (("lists", lists), ("clause", clause), ("chained", chained), ("boolean", boolean), ("phrase", phrase)):
+        fn()
+        batch.sync()
+        r = []
+        for _ in range(args.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in ev:
+                a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            r.append(med([a.elapsed_time(b) for a, b in ev]))
+        batch.sync()
+        out[name + "_ms"] = round(med(r), 4)
+        out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+    out["lists_over_phrase"] = round(out["lists_ms"] / out["phrase_ms"], 3)
+    out["clause_over_boolean"] = round(out["clause_ms"] / out["boolean_ms"], 3)
+    out["chained_over_boolean"] = round(out["chained_ms"] / out["boolean_ms"], 3)
+    out["chained_over_lists_plus_clause"] = round(out["chained_ms"] / (out["lists_ms"] + out["clause_ms"]), 3)
+    out["places_per_s"] = round(out["places"] / out["clause_ms"] * 1e3, 1)
+    return out
+
+
 def boolean_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_term, d_pdocs, d_ptfs, n_post):
     """--boolean Q,L,K over the one-pass segment; see the module's docstring"""
     from vaporetto_amd import api
@@ -544,6 +681,7 @@ def main():
     ap.add_argument("--boolean", action="append", default=[], help="with --postings: Q,L,K -- Q all-MUST queries of L terms by count, Q all-MUST windows of L tokens, the first as all-SHOULD (may be repeated)")
     ap.add_argument("--search-max-candidates", type=int, default=1 << 26)
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
+    ap.add_argument("--clause", action="append", default=[], help="with --postings: Q,L,K -- Q all-MUST queries, each a window of L tokens as ONE phrase clause plus one SHOULD term by count, top K (may be repeated)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -686,7 +824,7 @@ def main():
             if args.boolean:   # MUST / SHOULD / MUST_NOT slots over the same segment, beside the OR search over the same slots and a copy
                 row["boolean"] = [boolean_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_term, d_pdocs, d_ptfs, int(cnt[0]))
                                   for spec in args.boolean]
-            if args.phrase:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
+            if args.phrase or args.clause:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
                 n_post = int(cnt[0])
                 d_first, d_order = torch.empty(cap_ends + 2, dtype=torch.int64, device=dev), torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
                 d_ppos = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
@@ -712,6 +850,9 @@ def main():
                                     "indexed_plus_dropped_equal_tokens": bool(n_idx + int(cnt[1]) == n_tokens)}
                 row["phrase"] = [phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs,
                                              d_ptfs, n_post, (d_first, d_ppos, n_idx)) for spec in args.phrase]
+                if args.clause:   # phrase clauses in boolean queries, beside the boolean search over the tokens as slots and the phrase search
+                    row["clause"] = [clause_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_term, d_pdocs, d_ptfs, n_post,
+                                                 (d_first, d_ppos, n_idx)) for spec in args.clause]
                 del d_first, d_order, d_ppos
             del d_ids, d_term, d_pdocs, d_ptfs, d_cnt
         if args.count:   # the counter's three launches on the same CSR, beside the id pass of the same run

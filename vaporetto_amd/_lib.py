@@ -177,6 +177,14 @@ SIGNATURES = {
                                              C.c_float, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "vpt_token_stream_positional_postings_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P, _P, _P, C.c_uint, C.c_uint64, _P, _P, _P, _P, C.c_uint64,
                                                              _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vpt_postings_phrase_lists_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P,
+                                                   C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P]),
+    "vpt_postings_clause_search_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                    _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64, _P,
+                                                    _P, _P, _P, _P, _P]),
+    "vpt_postings_phrase_lists": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint64, _P]),
+    "vpt_postings_clause_search": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_float,
+                                             C.c_float, C.c_float, C.c_uint32, _P, _P, _P, _P, _P]),
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),

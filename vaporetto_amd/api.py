@@ -1669,6 +1669,53 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
 
+    def phrase_lists_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, d_post_first: int, d_post_positions: int, n_terms: int,
+                              capacity_postings: int, capacity_positions: int, doc_base: int, n_documents: int, d_phrase_offsets: int,
+                              d_phrase_terms: int, n_phrases: int, capacity_slots: int, capacity_probes: int, d_list_offsets: int, d_list_docs: int,
+                              d_list_tfs: int, capacity_lists: int, d_counts: int, stream: int = 0) -> None:
+        """Device-resident phrases to posting lists over one positional segment (vpt_postings_phrase_lists_device), raw device pointers: per
+        phrase the matching documents (global numbers, ascending) and their phrase frequencies, what clause_search_postings takes as derived
+        lists.  Enqueues and returns; errors (the phrase search's, and capacity_lists too small with the need in counts[1]) at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_phrases", n_phrases, 1 << 32), ("doc_base", doc_base, 1 << 64),
+                             ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
+                             ("capacity_positions", capacity_positions, 1 << 64), ("capacity_slots", capacity_slots, 1 << 64),
+                             ("capacity_probes", capacity_probes, 1 << 64), ("capacity_lists", capacity_lists, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_phrase_lists_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
+                                                          d_post_first or None, d_post_positions or None, int(n_terms), int(capacity_postings),
+                                                          int(capacity_positions), int(doc_base), int(n_documents), d_phrase_offsets or None,
+                                                          d_phrase_terms or None, int(n_phrases), int(capacity_slots), int(capacity_probes),
+                                                          d_list_offsets or None, d_list_docs or None, d_list_tfs or None, int(capacity_lists),
+                                                          d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
+    def clause_search_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, n_terms: int, capacity_postings: int, d_list_offsets: int,
+                               d_list_docs: int, d_list_tfs: int, n_lists: int, capacity_lists: int, doc_base: int, n_documents: int, d_doc_lens: int,
+                               d_query_offsets: int, d_query_terms: int, d_query_weights: int, d_query_occurs: int, n_queries: int, capacity_slots: int,
+                               k1: float, b: float, avgdl: float, k: int, capacity_candidates: int, d_hit_docs: int, d_hit_scores: int,
+                               d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0) -> None:
+        """Device-resident boolean search over a segment plus derived lists (vpt_postings_clause_search_device), raw device pointers:
+        boolean_search_postings' arguments and the lists phrase_lists_postings wrote; a slot's term t in [n_terms, n_terms + n_lists) names
+        list t - n_terms.  May follow phrase_lists_postings on the same stream without a sync: an error of that call leaves the outputs
+        alone.  Enqueues and returns; errors at sync()."""
+        for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_lists", n_lists, 1 << 32), ("n_queries", n_queries, 1 << 32), ("k", k, 1 << 32),
+                             ("doc_base", doc_base, 1 << 64), ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
+                             ("capacity_lists", capacity_lists, 1 << 64), ("capacity_slots", capacity_slots, 1 << 64),
+                             ("capacity_candidates", capacity_candidates, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
+        st = _lib.load().vpt_postings_clause_search_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
+                                                           int(n_terms), int(capacity_postings), d_list_offsets or None, d_list_docs or None,
+                                                           d_list_tfs or None, int(n_lists), int(capacity_lists), int(doc_base), int(n_documents),
+                                                           d_doc_lens or None, d_query_offsets or None, d_query_terms or None, d_query_weights or None,
+                                                           d_query_occurs or None, int(n_queries), int(capacity_slots), float(k1), float(b),
+                                                           float(avgdl), int(k), int(capacity_candidates), d_hit_docs or None, d_hit_scores or None,
+                                                           d_hit_counts or None, d_match_counts or None, d_counts or None, stream)
+        if st != _lib.VPT_OK:
+            _raise(st)
+
     @staticmethod
     def postings_phrase_limit() -> int:
         """the most slots a phrase may have (vpt_postings_phrase_limits)"""
@@ -2341,6 +2388,78 @@ class Postings:
         k = int(k)
         return [[(int(hd[q * k + j]), hs[q * k + j], int(hf[q * k + j])) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
+    def clause_search(self, queries, k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2, b: float = 0.75,
+                      predictor: Optional["Predictor"] = None):
+        """BM25 top-k of every boolean query of CLAUSES over this positional segment (vpt_postings_clause_search; the definition is in
+        include/vaporetto_hip.h).  A query is a sequence of clauses (terms, occur) or (terms, occur, weight): terms a sequence of term ids.  A
+        clause of one term is a slot of that term, as in boolean_search; every other clause is ONE exact phrase, scored by its phrase
+        frequency (an id outside the vocabulary makes it match nothing, and so does an empty clause).  The default weight is the phrase weight
+        of phrase_search (the float32 sum in slot order of bm25_idf over the clause's terms), 0.0 for MUST_NOT.  Returns (hits, match_counts)
+        as boolean_search does; last_search_counts: places, matches, skipped clauses."""
+        if self.first is None or self.positions is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: the postings were made without positions")
+        pred = predictor or self._predictor
+        if pred is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: no predictor (pass predictor=)")
+        doc_lens = self.doc_lens if doc_lens is None else doc_lens
+        doc_base = self.doc_base if doc_base is None else doc_base
+        if doc_lens is None or doc_base is None:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: the postings carry no doc_lens / doc_base (pass them)")
+        queries = [list(q) for q in queries]
+        flat = [x for q in queries for x in q]
+        if any(len(x) not in (2, 3) for x in flat):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: a clause is (terms, occur) or (terms, occur, weight)")
+        if any(not 0 <= int(x[1]) <= 2 for x in flat):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: occurs: a value above 2")
+        dl = np.ascontiguousarray(doc_lens, dtype=np.uint32)
+        n_docs, n_terms, n_q = len(dl), len(self.term_offsets) - 1, len(queries)
+        if n_q == 0:
+            return [], np.zeros(0, np.uint64)
+        if n_docs == 0:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: avgdl: must be between 2^-32 and 2^32")
+        avgdl = np.float32(float(int(dl.sum(dtype=np.uint64))) / float(n_docs))
+        qoff = np.zeros(n_q + 1, np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        coff = np.zeros(len(flat) + 1, np.uint64)
+        coff[1:] = np.cumsum([len(x[0]) for x in flat], dtype=np.uint64)
+        terms = np.array([t for x in flat for t in x[0]] + [0], np.int64).astype(np.int32)
+        occ = np.array([int(x[1]) for x in flat] + [0], np.uint8)
+        w = np.zeros(len(flat) + 1, np.float32)
+        df, idf = None, {}
+        for c, x in enumerate(flat):
+            if len(x) == 3:
+                w[c] = x[2]
+            elif int(x[1]) != Occur.MUST_NOT:
+                total = None
+                for t in x[0]:
+                    t = int(t)
+                    if not 0 <= t < n_terms:
+                        continue
+                    if t not in idf:
+                        df = self.df() if df is None else df
+                        idf[t] = bm25_idf(n_docs, int(df[t]))
+                    total = idf[t] if total is None else np.float32(total + idf[t])
+                w[c] = np.float32(0) if total is None else total
+        if not (0 <= int(k) < 1 << 32 and 0 <= n_terms < 1 << 32 and 0 <= n_q < 1 << 32 and 0 <= int(doc_base) < 1 << 64):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: k: must be at least 1, and n_queries * k below 2^32")
+        term = np.ascontiguousarray(self.term_offsets, dtype=np.uint64)
+        docs, tfs = np.ascontiguousarray(self.docs, dtype=np.uint32), np.ascontiguousarray(self.tfs, dtype=np.uint32)
+        first, ppos = np.ascontiguousarray(self.first, dtype=np.uint64), np.ascontiguousarray(self.positions, dtype=np.uint32)
+        if len(docs) != len(tfs) or len(first) != len(docs) + 1 or int(term[-1]) != len(docs) or int(first[-1]) != len(ppos):
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: the postings' arrays do not belong together")
+        n_out = max(n_q * int(k), 1)
+        hd, hs, hc, mc, cnt = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
+        st = _lib.load().vpt_postings_clause_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None,
+                                                    tfs.ctypes.data if len(tfs) else None, first.ctypes.data, ppos.ctypes.data if len(ppos) else None,
+                                                    n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, coff.ctypes.data,
+                                                    terms.ctypes.data, w.ctypes.data, occ.ctypes.data, n_q, float(k1), float(b), float(avgdl), int(k),
+                                                    hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        if st != _lib.VPT_OK:
+            _raise(st)
+        self.last_search_counts = cnt   # places, matches, skipped clauses
+        k = int(k)
+        return [[(int(hd[q * k + j]), hs[q * k + j]) for j in range(int(hc[q]))] for q in range(n_q)], mc
+
     def tokens(self, q: int) -> np.ndarray:
         """the token indices of posting q, ascending (needs positions)"""
         if self.first is None:
@@ -2501,11 +2620,14 @@ class VaporettoTokenizer:
         return postings.search(queries, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
 
     def boolean_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
-                       b: float = 0.75):
+                       b: float = 0.75, phrases: bool = False):
         """BM25 top-k of boolean query TEXTS over `postings`.  A text is split on ASCII spaces into CLAUSES: one that starts with `+` is MUST,
-        one that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are, and every
-        token of it is a slot of the clause's occur; an empty clause adds nothing.  A clause of several tokens is NOT made a phrase here (unlike
-        tantivy's query parser): `+東京都` requires each of its tokens somewhere in the document.  Then Postings.boolean_search.  Needs vocab=."""
+        one that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are; an empty
+        clause adds nothing.  By default every token of a clause is a slot of the clause's occur: `+東京都` requires each of its tokens
+        somewhere in the document; then Postings.boolean_search.  phrases=True (what tantivy's query parser does; `postings` from
+        index_batch(positions=True)): a clause of several tokens is ONE exact phrase -- a token without a vocabulary entry makes it match
+        nothing -- a clause of one token a term slot, and a clause that yields no token (a stop set took them all) adds nothing, as in the
+        default; then Postings.clause_search.  Needs vocab=."""
         clauses, owner = [], []
         for i, text in enumerate(texts):
             for clause in text.split(" "):
@@ -2518,7 +2640,14 @@ class VaporettoTokenizer:
         if clauses:
             toff, ids = self.encode_batch(clauses)
             for c, (i, occur) in enumerate(owner):
-                queries[i] += [(int(t), occur) for t in ids[int(toff[c]):int(toff[c + 1])]]
+                if phrases and toff[c] == toff[c + 1]:
+                    continue
+                if phrases:
+                    queries[i].append((ids[int(toff[c]):int(toff[c + 1])].tolist(), occur))
+                else:
+                    queries[i] += [(int(t), occur) for t in ids[int(toff[c]):int(toff[c + 1])]]
+        if phrases:
+            return postings.clause_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor)
         return postings.boolean_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor)
 
     def phrase_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,

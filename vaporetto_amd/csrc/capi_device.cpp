@@ -1350,18 +1350,28 @@ vpt_status check_search_arguments(bool phrase, uint32_t n_terms, uint32_t n_quer
 }
 
 // The OR search (boolean false: d_query_occurs is not looked at) and the boolean search (kernels_postings_boolean.hip: queries, slots and expand
-// of its own, then the OR search's launches as they stand) over one block of arguments, checks and scratch.
+// of its own, then the OR search's launches as they stand) over one block of arguments, checks and scratch.  lists: the clause search's derived
+// segment, or nullptr; with it the launches behind expand leave the outputs alone on the lists call's status bits too (kClauseErrors).
+struct ClauseLists {
+    const uint64_t* d_offsets;
+    const uint32_t* d_docs;
+    const uint32_t* d_tfs;
+    uint32_t n_lists;
+    uint64_t capacity;
+};
 vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs, const uint32_t* d_post_tfs,
                               uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens,
                               const uint64_t* d_query_offsets, const int32_t* d_query_terms, const float* d_query_weights, bool boolean,
                               const uint8_t* d_query_occurs, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k,
                               uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts,
-                              uint64_t* d_counts, hipStream_t stream) {
+                              uint64_t* d_counts, hipStream_t stream, const ClauseLists* lists = nullptr) {
     VPT_TRY(check_batch(p, b));
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_doc_lens || !d_query_offsets || !d_query_terms || !d_query_weights || !d_hit_docs ||
-        !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts || (boolean && !d_query_occurs))
+        !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts || (boolean && !d_query_occurs) ||
+        (lists && lists->n_lists && (!lists->d_offsets || !lists->d_docs || !lists->d_tfs)))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
     VPT_TRY(check_search_arguments(false, n_terms, n_queries, k, capacity_slots, capacity_candidates, doc_base, n_documents, k1, bm_b, avgdl));
+    if (lists) VPT_TRY(check_clause_lists(n_terms, lists->n_lists, lists->capacity));
     VPT_HIP(hipSetDevice(p->device));
     VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
     const uint64_t n = capacity_candidates, ns = capacity_slots;
@@ -1376,7 +1386,7 @@ vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64
     P.slot_df = S.slot_df.at(m); P.base = S.base.at(m); P.slot_query = S.slot_query.at(m); P.rec = S.rec.at(m); P.hit = S.hit.at(m);
     P.order = S.order.at(m); P.skey = S.skey.at(m); P.flags = S.flags.at(m); P.scan = S.scan.at(m); P.qstart = S.qstart.at(m);
     P.hit_docs = d_hit_docs; P.hit_scores = d_hit_scores; P.hit_counts = d_hit_counts; P.match_counts = d_match_counts; P.counts = d_counts;
-    P.status = b->d_ctrl;
+    P.status = b->d_ctrl; P.error_mask = lists ? vpt::kClauseErrors : vpt::kSearchErrors;
     uint64_t *hist = S.tail.hist.at(m), *hscan = S.tail.hist_scan.at(m), *part = S.tail.partials.at(m);
     vptcarve::PassList group, rank;
     group.add(0, n_documents);   // (at most four bytes: the key is relative to doc_base)
@@ -1386,6 +1396,10 @@ vpt_status search_device_impl(const vpt_predictor* p, vpt_batch* b, const uint64
     if (boolean) {
         vpt::PostingsBooleanParams B{};
         B.S = P; B.occurs = d_query_occurs; B.q_anchor = S.q_anchor.at(m); B.q_flags = S.q_flags.at(m);
+        if (lists && lists->n_lists) {   // (none: the kernels of one segment)
+            B.list_offsets = lists->d_offsets; B.list_docs = lists->d_docs; B.list_tfs = lists->d_tfs;
+            B.n_lists = lists->n_lists; B.capacity_lists = lists->capacity;
+        }
         VPT_HIP(vpt::launch_postings_boolean_queries(B, stream));
         VPT_HIP(vpt::launch_postings_boolean_slots(B, stream));
         VPT_HIP(vpt::train_scan(P.slot_df, ns, P.base, part, stream));
@@ -1428,7 +1442,36 @@ vpt_status postings_boolean_search_device(const vpt_predictor* p, vpt_batch* b, 
                               d_query_terms, d_query_weights, true, d_query_occurs, n_queries, capacity_slots, k1, bm_b, avgdl, k, capacity_candidates,
                               d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, stream);
 }
+
+// The boolean search over the segment and a derived segment of lists (the phrase lists call's output): its scratch is the boolean search's.
+vpt_status postings_clause_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                         const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, const uint64_t* d_list_offsets,
+                                         const uint32_t* d_list_docs, const uint32_t* d_list_tfs, uint32_t n_lists, uint64_t capacity_lists,
+                                         uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                         const int32_t* d_query_terms, const float* d_query_weights, const uint8_t* d_query_occurs, uint32_t n_queries,
+                                         uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
+                                         uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
+                                         hipStream_t stream) {
+    const ClauseLists lists{d_list_offsets, d_list_docs, d_list_tfs, n_lists, capacity_lists};
+    return search_device_impl(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, doc_base, n_documents, d_doc_lens, d_query_offsets,
+                              d_query_terms, d_query_weights, true, d_query_occurs, n_queries, capacity_slots, k1, bm_b, avgdl, k, capacity_candidates,
+                              d_hit_docs, d_hit_scores, d_hit_counts, d_match_counts, d_counts, stream, &lists);
+}
 }  // namespace vptc
+
+vpt_status vpt_postings_clause_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                             const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, const uint64_t* d_list_offsets,
+                                             const uint32_t* d_list_docs, const uint32_t* d_list_tfs, uint32_t n_lists, uint64_t capacity_lists,
+                                             uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                             const int32_t* d_query_terms, const float* d_query_weights, const uint8_t* d_query_occurs,
+                                             uint32_t n_queries, uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                             uint64_t capacity_candidates, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts,
+                                             uint64_t* d_match_counts, uint64_t* d_counts, void* hip_stream) {
+    return postings_clause_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, n_terms, capacity_postings, d_list_offsets, d_list_docs, d_list_tfs,
+                                         n_lists, capacity_lists, doc_base, n_documents, d_doc_lens, d_query_offsets, d_query_terms, d_query_weights,
+                                         d_query_occurs, n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_candidates, d_hit_docs, d_hit_scores,
+                                         d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
+}
 
 vpt_status vpt_postings_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
                                       const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, uint64_t doc_base, uint64_t n_documents,
@@ -1527,7 +1570,63 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
     b->last_stream = stream; b->pending = true;
     return VPT_OK;
 }
+
+// The phrase search's launches up to the second heads scan over the phrase search's scratch (what the sort and the take work in lies idle), no
+// weights, then the lists launch: nothing is sized from a value read back.
+vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                        const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions, uint32_t n_terms,
+                                        uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                        const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms, uint32_t n_phrases, uint64_t capacity_slots,
+                                        uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs, uint32_t* d_list_tfs,
+                                        uint64_t capacity_lists, uint64_t* d_counts, hipStream_t stream) {
+    VPT_TRY(check_batch(p, b));
+    if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_post_first || !d_post_positions || !d_phrase_offsets || !d_phrase_terms || !d_list_offsets ||
+        !d_list_docs || !d_list_tfs || !d_counts)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL device pointer");
+    VPT_TRY(check_n_terms(n_terms));
+    VPT_TRY(bad_argument(n_phrases == 0 || n_phrases > vpt::kSearchMaxQueries, "InvalidArgumentError: n_phrases: must be between 1 and 2^24"));
+    VPT_TRY(check_search_sizes(true, capacity_slots, capacity_probes));
+    VPT_TRY(check_clause_lists(n_terms, 0, capacity_lists));
+    VPT_TRY(check_doc_range(doc_base, n_documents));
+    VPT_HIP(hipSetDevice(p->device));
+    VPT_HIP(hipMemsetAsync(d_counts, 0, 24, stream));
+    const uint64_t n = capacity_probes, nq = n_phrases;
+    const vptcarve::PhraseScratch S(n, n_phrases);
+    VPT_TRY(b->d_post.grow(S.bytes()));
+    unsigned char* m = b->d_post;
+    vpt::PostingsPhraseParams P{};
+    P.term_offsets = d_term_offsets; P.post_docs = d_post_docs; P.post_tfs = d_post_tfs; P.post_first = d_post_first; P.post_positions = d_post_positions;
+    P.capacity_postings = capacity_postings; P.capacity_positions = capacity_positions; P.n_terms = n_terms;
+    P.doc_base = doc_base; P.n_docs = n_documents;
+    P.query_offsets = d_phrase_offsets; P.query_terms = d_phrase_terms; P.n_queries = n_phrases; P.capacity_slots = capacity_slots; P.n_places = n;
+    P.q_anchor = S.q_anchor.at(m); P.q_run = S.q_run.at(m); P.q_probes = S.q_probes.at(m); P.base = S.base.at(m); P.qstart = S.qstart.at(m);
+    P.flags = S.flags.at(m); P.plen = S.plen.at(m); P.pdoc = S.pdoc.at(m); P.pq = S.pq.at(m); P.scan = S.scan.at(m);
+    P.counts = d_counts; P.status = b->d_ctrl;
+    P.list_offsets = d_list_offsets; P.list_docs = d_list_docs; P.list_tfs = d_list_tfs; P.capacity_lists = capacity_lists;
+    uint64_t* part = S.tail.partials.at(m);
+    VPT_HIP(vpt::launch_postings_phrase_queries(P, stream));
+    VPT_HIP(vpt::train_scan(P.q_probes, nq, P.base, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_probe(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_heads(P, stream));
+    VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
+    VPT_HIP(vpt::launch_postings_phrase_lists(P, stream));
+    b->last_stream = stream; b->pending = true;
+    return VPT_OK;
+}
 }  // namespace vptc
+
+vpt_status vpt_postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                            const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions,
+                                            uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                            uint64_t n_documents, const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms, uint32_t n_phrases,
+                                            uint64_t capacity_slots, uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs,
+                                            uint32_t* d_list_tfs, uint64_t capacity_lists, uint64_t* d_counts, void* hip_stream) {
+    return postings_phrase_lists_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
+                                        capacity_positions, doc_base, n_documents, d_phrase_offsets, d_phrase_terms, n_phrases, capacity_slots,
+                                        capacity_probes, d_list_offsets, d_list_docs, d_list_tfs, capacity_lists, d_counts,
+                                        static_cast<hipStream_t>(hip_stream));
+}
 
 vpt_status vpt_postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
                                          const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms,

@@ -1422,6 +1422,245 @@ vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* te
     return A.read_back(m, counts_out, hit_counts_out, match_counts_out, hit_docs_out, hit_scores_out, hit_freqs_out);
 }
 
+namespace {
+// What a phrase's list can hold at most: the smallest df among its terms (a document of the list has a posting of every term); 0 for a phrase
+// that is empty, too long, or has a term out of range or bounds that are no list's.  The sum over the phrases always suffices as capacity_lists.
+uint64_t phrase_list_bound(const uint64_t* term_offsets, uint32_t n_terms, uint64_t n_post, const int32_t* terms, uint64_t len) {
+    if (len == 0 || len > vpt::kPhraseMaxTerms) return 0;
+    uint64_t best = ~uint64_t(0);
+    for (uint64_t j = 0; j < len; ++j) {
+        const int32_t t = terms[j];
+        if (t < 0 || uint32_t(t) >= n_terms) return 0;
+        const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
+        if (ta >= tb || tb > n_post) return 0;
+        best = std::min(best, tb - ta);
+    }
+    return best;
+}
+
+// What the two host calls keep in the one allocation of their call: the positional segment, the phrase CSR, the lists and the lists call's
+// counts; the clause search adds the documents' lengths, the slot arrays and the four outputs with the counts.  The inputs have a word of slack.
+struct ClauseMem {
+    const size_t n_terms, n_post, n_pos, n_docs, n_phrases, n_pslots, n_lists_cap, n_queries, n_slots, n_out;
+    vptcarve::Carver c{};
+    vptcarve::Section<uint64_t> term{c, n_terms + 1};
+    vptcarve::Section<uint32_t> docs{c, n_post + 1}, tfs{c, n_post + 1};
+    vptcarve::Section<uint64_t> first{c, n_post + 1};
+    vptcarve::Section<uint32_t> pos{c, n_pos + 1};
+    vptcarve::Section<uint64_t> poff{c, n_phrases + 1};
+    vptcarve::Section<int32_t> pterms{c, n_pslots + 1};
+    vptcarve::Section<uint64_t> loff{c, n_phrases + 1};
+    vptcarve::Section<uint32_t> ldocs{c, n_lists_cap + 1}, ltfs{c, n_lists_cap + 1};
+    vptcarve::Section<uint64_t> lcounts{c, 3};
+    vptcarve::Section<uint32_t> dl{c, n_docs + 1};
+    vptcarve::Section<uint64_t> qoff{c, n_queries + 1};
+    vptcarve::Section<int32_t> qterms{c, n_slots + 1};
+    vptcarve::Section<float> qweights{c, n_slots + 1};
+    vptcarve::Section<uint8_t> qoccurs{c, n_slots + 4};
+    vptcarve::Section<uint32_t> hit_docs{c, n_out};
+    vptcarve::Section<float> hit_scores{c, n_out};
+    vptcarve::Section<uint32_t> hit_counts{c, n_queries};
+    vptcarve::Section<uint64_t> match_counts{c, n_queries}, counts{c, 3};
+    ClauseMem(uint32_t terms, uint64_t post, uint64_t positions, uint64_t documents, size_t phrases, size_t phrase_slots, uint64_t lists, uint32_t queries,
+              uint64_t slots, uint32_t k)
+        : n_terms(terms), n_post(size_t(post)), n_pos(size_t(positions)), n_docs(size_t(documents)), n_phrases(phrases), n_pslots(phrase_slots),
+          n_lists_cap(size_t(lists)), n_queries(queries), n_slots(size_t(slots)), n_out(size_t(queries) * k) {}
+
+    vpt_status upload_segment(unsigned char* m, hipStream_t s, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                              const uint64_t* post_first, const uint32_t* post_positions, const uint64_t* phrase_offsets,
+                              const int32_t* phrase_terms) const {
+        VPT_HIP(hipMemcpyAsync(term.at(m), term_offsets, 8 * (n_terms + 1), hipMemcpyHostToDevice, s));
+        if (n_post) {
+            VPT_HIP(hipMemcpyAsync(docs.at(m), post_docs, 4 * n_post, hipMemcpyHostToDevice, s));
+            VPT_HIP(hipMemcpyAsync(tfs.at(m), post_tfs, 4 * n_post, hipMemcpyHostToDevice, s));
+        }
+        VPT_HIP(hipMemcpyAsync(first.at(m), post_first, 8 * (n_post + 1), hipMemcpyHostToDevice, s));
+        if (n_pos) VPT_HIP(hipMemcpyAsync(pos.at(m), post_positions, 4 * n_pos, hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(poff.at(m), phrase_offsets, 8 * (n_phrases + 1), hipMemcpyHostToDevice, s));
+        if (n_pslots) VPT_HIP(hipMemcpyAsync(pterms.at(m), phrase_terms, 4 * n_pslots, hipMemcpyHostToDevice, s));
+        return VPT_OK;
+    }
+};
+
+// the arguments both host calls check of a positional host segment; *n_post, *n_pos: what it holds
+vpt_status check_host_positional(const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs, const uint64_t* post_first,
+                                 const uint32_t* post_positions, uint32_t n_terms, uint64_t* n_post, uint64_t* n_pos) {
+    if (!term_offsets || !post_first) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    VPT_TRY(check_n_terms(n_terms));
+    *n_post = term_offsets[n_terms];
+    VPT_TRY(check_search_sizes(true, *n_post));
+    *n_pos = post_first[*n_post];
+    VPT_TRY(check_search_sizes(true, *n_pos));
+    if ((*n_post && (!post_docs || !post_tfs)) || (*n_pos && !post_positions)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    return VPT_OK;
+}
+}  // namespace
+
+// Host phrases over a host positional segment in, their posting lists out: the lists call once, over one allocation of this call.
+vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                     const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                     uint64_t n_documents, const uint64_t* phrase_offsets, const int32_t* phrase_terms, uint32_t n_phrases,
+                                     uint64_t* list_offsets_out, uint32_t* list_docs_out, uint32_t* list_tfs_out, uint64_t capacity_lists,
+                                     uint64_t* counts_out) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!phrase_offsets || !list_offsets_out || !counts_out || (capacity_lists && (!list_docs_out || !list_tfs_out)))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    uint64_t n_post = 0, n_pos = 0;
+    VPT_TRY(check_host_positional(term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, &n_post, &n_pos));
+    VPT_TRY(bad_argument(n_phrases == 0 || n_phrases > vpt::kSearchMaxQueries, "InvalidArgumentError: n_phrases: must be between 1 and 2^24"));
+    const uint64_t n_slots = phrase_offsets[n_phrases];
+    VPT_TRY(check_search_sizes(true, n_slots));
+    if (n_slots && !phrase_terms) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    VPT_TRY(check_clause_lists(n_terms, 0, capacity_lists));
+    const uint64_t n_probes = phrase_probes(term_offsets, post_first, n_terms, n_post, n_pos, phrase_offsets, phrase_terms, n_phrases, n_slots);
+    VPT_TRY(check_search_sizes(true, n_probes));
+    VPT_TRY(check_doc_range(doc_base, n_documents));
+    const ClauseMem A(n_terms, n_post, n_pos, 0, n_phrases, size_t(n_slots), capacity_lists, 0, 0, 0);
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    VPT_TRY(acquire(p, &w));
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    DevBuf<unsigned char> mem;
+    VPT_TRY(mem.alloc(A.c.bytes()));
+    unsigned char* m = mem;
+    VPT_TRY(A.upload_segment(m, s, term_offsets, post_docs, post_tfs, post_first, post_positions, phrase_offsets, phrase_terms));
+    VPT_TRY(postings_phrase_lists_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
+                                         n_documents, A.poff.at(m), A.pterms.at(m), n_phrases, n_slots, n_probes, A.loff.at(m), A.ldocs.at(m),
+                                         A.ltfs.at(m), capacity_lists, A.lcounts.at(m), s));
+    const vpt_status st = vpt_batch_sync(b);
+    VPT_HIP(hipMemcpy(counts_out, A.lcounts.at(m), 24, hipMemcpyDeviceToHost));   // (the need, when a capacity was too small)
+    if (st != VPT_OK) return st;
+    VPT_HIP(hipMemcpy(list_offsets_out, A.loff.at(m), 8 * (size_t(n_phrases) + 1), hipMemcpyDeviceToHost));
+    const uint64_t n_entries = std::min(counts_out[1], capacity_lists);
+    if (n_entries) {
+        VPT_HIP(hipMemcpy(list_docs_out, A.ldocs.at(m), 4 * n_entries, hipMemcpyDeviceToHost));
+        VPT_HIP(hipMemcpy(list_tfs_out, A.ltfs.at(m), 4 * n_entries, hipMemcpyDeviceToHost));
+    }
+    return VPT_OK;
+}
+
+// Host queries of CLAUSES over a host positional segment in, the hits out.  A clause of one term is a slot of that term; every other clause is a
+// phrase: the lists call makes its list, and the slot names it.  One upload, the two device calls on one stream with no sync between them, one
+// download; the probes, the list entries and the places are counted on the host from the segment's bounds (a list: at most the smallest df
+// among its phrase's terms).  counts_out: the clause search's, with the phrases that have a term out of range added to the skipped slots.
+vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const uint64_t* clause_offsets,
+                                      const int32_t* clause_terms, const float* clause_weights, const uint8_t* clause_occurs, uint32_t n_queries,
+                                      float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
+                                      uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
+    if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
+    if (!query_offsets || !clause_offsets || !hit_docs_out || !hit_scores_out || !hit_counts_out || !match_counts_out || !counts_out)
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    uint64_t n_post = 0, n_pos = 0;
+    VPT_TRY(check_host_positional(term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, &n_post, &n_pos));
+    VPT_TRY(check_n_queries(n_queries));
+    VPT_TRY(check_top_k(n_queries, k));
+    const uint64_t n_clauses = query_offsets[n_queries];
+    VPT_TRY(check_search_sizes(false, n_clauses));
+    const uint64_t n_cterms = clause_offsets[n_clauses];
+    VPT_TRY(check_search_sizes(true, n_cterms));
+    if ((n_documents && !doc_lens) || (n_clauses && (!clause_weights || !clause_occurs)) || (n_cterms && !clause_terms))
+        return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (query_offsets[q] > query_offsets[q + 1]) return status_from_bits(vpt::kErrBadQueryCsr);
+    for (uint64_t c = 0; c < n_clauses; ++c)
+        if (clause_offsets[c] > clause_offsets[c + 1]) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: clause_offsets: do not describe the clauses' terms");
+    VPT_TRY(check_doc_range(doc_base, n_documents));
+    // the slots: a clause of one term names it, every other clause names its phrase's list
+    std::vector<int32_t> slot_terms, phrase_terms;
+    std::vector<uint64_t> phrase_offsets{0}, slot_bound;
+    uint64_t cap_lists = 0, skipped_phrases = 0;
+    try {
+        slot_terms.reserve(size_t(n_clauses));
+        slot_bound.reserve(size_t(n_clauses));
+        for (uint64_t c = 0; c < n_clauses; ++c) {
+            const uint64_t a = clause_offsets[c], len = clause_offsets[c + 1] - a;
+            if (len == 1) {
+                const int32_t t = clause_terms[a];
+                uint64_t df = 0;
+                if (t >= 0 && uint32_t(t) < n_terms) {
+                    const uint64_t ta = term_offsets[t], tb = term_offsets[uint32_t(t) + 1];
+                    if (ta <= tb && tb <= n_post) df = tb - ta;
+                }
+                slot_terms.push_back(t >= 0 && uint32_t(t) < n_terms ? t : -1);   // (a value at or above n_terms would name a list)
+                slot_bound.push_back(df);
+                continue;
+            }
+            const uint64_t bound = phrase_list_bound(term_offsets, n_terms, n_post, clause_terms + a, len);
+            for (uint64_t j = 0; j < len; ++j)
+                if (clause_terms[a + j] < 0 || uint32_t(clause_terms[a + j]) >= n_terms) { ++skipped_phrases; break; }
+            slot_terms.push_back(int32_t(n_terms + (phrase_offsets.size() - 1)));
+            slot_bound.push_back(bound);
+            cap_lists += bound;
+            phrase_terms.insert(phrase_terms.end(), clause_terms + a, clause_terms + a + len);
+            phrase_offsets.push_back(phrase_terms.size());
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(VPT_RUNTIME_ERROR, "out of host memory while laying out the clauses");
+    }
+    const size_t n_lists = phrase_offsets.size() - 1;
+    VPT_TRY(check_clause_lists(n_terms, uint32_t(std::min<size_t>(n_lists, 1u << 25)), cap_lists));
+    // the places by the boolean search's rule, a list counted as its bound
+    uint64_t places = 0;
+    for (uint32_t q = 0; q < n_queries && places < (1ull << 32); ++q) {
+        const uint64_t a = query_offsets[q], e = query_offsets[q + 1];
+        if (e - a > vpt::kSearchMaxQuerySlots) continue;
+        uint64_t best = ~uint64_t(0), should = 0;
+        bool must = false, dead = false;
+        for (uint64_t s = a; s < e; ++s) {
+            if (clause_occurs[s] == VPT_OCCUR_MUST) {
+                must = true;
+                if (slot_bound[s] == 0) dead = true;
+                best = std::min(best, slot_bound[s]);
+            } else if (clause_occurs[s] == VPT_OCCUR_SHOULD) {
+                should += slot_bound[s];
+            }
+        }
+        if (!dead) places += must ? best : should;
+    }
+    VPT_TRY(check_search_sizes(false, places));
+    const uint64_t n_probes = n_lists ? phrase_probes(term_offsets, post_first, n_terms, n_post, n_pos, phrase_offsets.data(), phrase_terms.data(),
+                                                      uint32_t(n_lists), phrase_terms.size())
+                                      : 0;
+    VPT_TRY(check_search_sizes(true, n_probes));
+    const ClauseMem A(n_terms, n_post, n_pos, n_documents, n_lists, phrase_terms.size(), cap_lists, n_queries, n_clauses, k);
+    VPT_HIP(hipSetDevice(p->device));
+    Workspace w;
+    VPT_TRY(acquire(p, &w));
+    vpt_batch* b = w.b;
+    hipStream_t s = b->own_stream;
+    DevBuf<unsigned char> mem;
+    VPT_TRY(mem.alloc(A.c.bytes()));
+    unsigned char* m = mem;
+    VPT_TRY(A.upload_segment(m, s, term_offsets, post_docs, post_tfs, post_first, post_positions, phrase_offsets.data(), phrase_terms.data()));
+    if (n_documents) VPT_HIP(hipMemcpyAsync(A.dl.at(m), doc_lens, 4 * n_documents, hipMemcpyHostToDevice, s));
+    VPT_HIP(hipMemcpyAsync(A.qoff.at(m), query_offsets, 8 * (size_t(n_queries) + 1), hipMemcpyHostToDevice, s));
+    if (n_clauses) {
+        VPT_HIP(hipMemcpyAsync(A.qterms.at(m), slot_terms.data(), 4 * n_clauses, hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(A.qweights.at(m), clause_weights, 4 * n_clauses, hipMemcpyHostToDevice, s));
+        VPT_HIP(hipMemcpyAsync(A.qoccurs.at(m), clause_occurs, n_clauses, hipMemcpyHostToDevice, s));
+    }
+    VPT_HIP(hipMemsetAsync(m + A.hit_docs.offset, 0, A.hit_counts.offset - A.hit_docs.offset, s));   // (behind a query's hit count: zeros come back)
+    if (n_lists)
+        VPT_TRY(postings_phrase_lists_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
+                                             n_documents, A.poff.at(m), A.pterms.at(m), uint32_t(n_lists), phrase_terms.size(), n_probes, A.loff.at(m),
+                                             A.ldocs.at(m), A.ltfs.at(m), cap_lists, A.lcounts.at(m), s));
+    VPT_TRY(postings_clause_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), n_terms, n_post, A.loff.at(m), A.ldocs.at(m), A.ltfs.at(m),
+                                          uint32_t(n_lists), cap_lists, doc_base, n_documents, A.dl.at(m), A.qoff.at(m), A.qterms.at(m), A.qweights.at(m),
+                                          A.qoccurs.at(m), n_queries, n_clauses, k1, b_param, avgdl, k, places, A.hit_docs.at(m), A.hit_scores.at(m),
+                                          A.hit_counts.at(m), A.match_counts.at(m), A.counts.at(m), s));
+    VPT_TRY(vpt_batch_sync(b));
+    VPT_HIP(hipMemcpy(counts_out, A.counts.at(m), 24, hipMemcpyDeviceToHost));
+    counts_out[2] += skipped_phrases;
+    VPT_HIP(hipMemcpy(hit_counts_out, A.hit_counts.at(m), 4 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(match_counts_out, A.match_counts.at(m), 8 * size_t(n_queries), hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_docs_out, A.hit_docs.at(m), 4 * A.n_out, hipMemcpyDeviceToHost));
+    VPT_HIP(hipMemcpy(hit_scores_out, A.hit_scores.at(m), 4 * A.n_out, hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
 // ---- pinned host memory for callers that want the PCIe link at full rate
 vpt_status vpt_host_alloc(size_t bytes, void** out) {
     if (!out) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: out: must not be NULL");

@@ -314,6 +314,7 @@ constexpr const char* kVocabCounterFull = "InvalidArgumentError: vocab counter: 
 constexpr const char* kPostingsTooSmall = "InvalidArgumentError: capacity: smaller than the number of postings";
 constexpr const char* kCandidatesTooSmall = "InvalidArgumentError: capacity_candidates: smaller than the number of candidates";
 constexpr const char* kProbesTooSmall = "InvalidArgumentError: capacity_probes: smaller than the number of probes";
+constexpr const char* kListsTooSmall = "InvalidArgumentError: capacity_lists: smaller than the number of list entries";
 constexpr const char* kPositionsTooSmall = "InvalidArgumentError: capacity_positions: smaller than the number of indexed tokens";
 
 // A device allocation that a workspace owns: freed with it.  cap: elements (grow) -- the allocation has 64 bytes more -- or bytes / sizeof(T) (alloc).
@@ -535,6 +536,12 @@ vpt_status check_search_sizes(bool phrase, uint64_t a, uint64_t b = 0) {
                         phrase ? "InvalidArgumentError: capacity: the phrase search takes fewer than 2^32 slots and probes per call"
                                : "InvalidArgumentError: capacity: the postings search takes fewer than 2^32 slots and candidates per call");
 }
+// the derived lists beside a segment's n_terms: a term value names a term or a list, and a list entry has a 32-bit place
+vpt_status check_clause_lists(uint32_t n_terms, uint32_t n_lists, uint64_t capacity_lists) {
+    VPT_TRY(bad_argument(n_lists > vpt::kPostingsMaxTerms || n_terms + uint64_t(n_lists) > vpt::kPostingsMaxTerms,
+                         "InvalidArgumentError: n_lists: n_terms + n_lists must not exceed 2^24"));
+    return bad_argument(capacity_lists >= (1ull << 32), "InvalidArgumentError: capacity_lists: must be below 2^32");
+}
 
 vpt_status compile(const uint8_t* bytes, size_t len, int predict_tags, vpt::CompiledModel* out) {
     if (!bytes) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: model_bytes: must not be NULL");
@@ -591,6 +598,7 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrCandidatesTooSmall) return fail(VPT_INVALID_ARGUMENT, kCandidatesTooSmall);
     if (bits & vpt::kErrPhraseTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: a phrase of more than 64 terms");
     if (bits & vpt::kErrProbesTooSmall) return fail(VPT_INVALID_ARGUMENT, kProbesTooSmall);
+    if (bits & vpt::kErrListsTooSmall) return fail(VPT_INVALID_ARGUMENT, kListsTooSmall);
     if (bits & vpt::kErrBadPositions)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: positions: do not strictly ascend inside a document's list");
     if (bits & vpt::kErrSegmentsOverlap)
@@ -823,6 +831,22 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
                                          const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
                                          uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
                                          uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream);
+// Phrases to posting lists and the boolean search over a segment and such lists (vpt_postings_phrase_lists_device,
+// vpt_postings_clause_search_device; kernels_postings_phrase.hip, kernels_postings_boolean.hip)
+vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                        const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions, uint32_t n_terms,
+                                        uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                        const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms, uint32_t n_phrases, uint64_t capacity_slots,
+                                        uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs, uint32_t* d_list_tfs,
+                                        uint64_t capacity_lists, uint64_t* d_counts, hipStream_t stream);
+vpt_status postings_clause_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                         const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, const uint64_t* d_list_offsets,
+                                         const uint32_t* d_list_docs, const uint32_t* d_list_tfs, uint32_t n_lists, uint64_t capacity_lists,
+                                         uint64_t doc_base, uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                         const int32_t* d_query_terms, const float* d_query_weights, const uint8_t* d_query_occurs, uint32_t n_queries,
+                                         uint64_t capacity_slots, float k1, float bm_b, float avgdl, uint32_t k, uint64_t capacity_candidates,
+                                         uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts,
+                                         hipStream_t stream);
 vpt_status predict_device_impl(const vpt_predictor* p, vpt_batch* b, const uint8_t* d_utf8, const uint64_t* d_byte_offsets,
                                const uint64_t* d_out_offsets, size_t n_sentences, uint64_t total_boundaries,
                                uint64_t max_sentence_bytes, int32_t* d_scores, uint8_t* d_labels, void* hip_stream);

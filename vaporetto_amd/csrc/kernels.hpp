@@ -81,6 +81,7 @@ constexpr uint32_t kErrPhraseTooLong = 1048576u;      // the phrase search: a ph
 constexpr uint32_t kErrProbesTooSmall = 2097152u;     // the phrase search: more probes than capacity_probes
 constexpr uint32_t kErrPositionsTooSmall = 4194304u;  // the positional merge: more merged positions than capacity_positions_out
 constexpr uint32_t kErrBadOccur = 8388608u;           // the boolean search: an occur value above 2 (kernels_postings_boolean.hip)
+constexpr uint32_t kErrListsTooSmall = 16777216u;     // the phrase lists: more list entries than capacity_lists (kernels_postings_phrase.hip)
 
 
 struct ScoreParams {
@@ -460,7 +461,8 @@ hipError_t launch_postings_merge_positions_general(const PostingsMergePosParams&
 // document - doc_base, ~bits of the score}, order, skey, flags (u32) and scan (u64, [places + 1]); qstart [n_queries + 1] (u64).  The caller runs
 // train_scan (slot_df -> base) between slots and expand, train_radix_sort (rec, stride 3: the document word, then the query word) between expand
 // and heads, train_scan (flags -> scan) between heads and sum, train_radix_sort (hit, stride 3: the score word, then the query word) between
-// sum and take.  A launch behind expand that finds one of kSearchErrors in the status leaves the four outputs alone.
+// sum and take.  A launch behind expand that finds one of error_mask in the status leaves the four outputs alone: kSearchErrors, and for the
+// clause search, which is enqueued behind a lists call without a sync between them, that call's bits too (kClauseErrors).
 constexpr uint32_t kSearchMaxQuerySlots = 1024;
 constexpr uint32_t kSearchMaxQueries = 1u << 24;
 constexpr uint32_t kSearchErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrQueryTooLong | kErrCandidatesTooSmall | kErrBadOccur;
@@ -497,6 +499,7 @@ struct PostingsSearchParams {
     uint64_t* match_counts;         // [n_queries]
     uint64_t* counts;               // [3]: candidates, matches (written), skipped slots (added to: zero before the launches)
     uint32_t* status;
+    uint32_t error_mask;            // the status bits with which ranges and take write nothing
 };
 hipError_t launch_postings_search_slots(const PostingsSearchParams& P, hipStream_t stream);
 hipError_t launch_postings_search_expand(const PostingsSearchParams& P, hipStream_t stream);
@@ -508,6 +511,9 @@ hipError_t launch_postings_search_take(const PostingsSearchParams& P, hipStream_
 // smallest df.  A PLACE is a posting of the anchor, or, in a query without a MUST slot, a posting of a SHOULD slot (a candidate of the OR
 // search); S.slot_df holds a slot's places, S.n_places bounds their sum.  Scratch beside S's: q_anchor (u64) and q_flags (u32) per query.  The
 // caller runs queries, slots, train_scan (S.slot_df -> S.base), expand, then the OR search's launches from the first sort on.
+// The CLAUSE search (vpt_postings_clause_search_device) is the same three kernels over TWO segments: a term t in [S.n_terms, S.n_terms +
+// n_lists) names list t - S.n_terms of the derived segment {list_offsets, list_docs, list_tfs, capacity_lists} -- the phrase lists call's
+// output -- and is, for the rest of the rule, a term whose list is that one.  n_lists 0: one segment, the boolean search as it was.
 constexpr uint32_t kOccurShould = 0, kOccurMust = 1, kOccurMustNot = 2;
 constexpr uint64_t kBoolNoAnchor = ~uint64_t(0);      // q_anchor: the query has no MUST slot
 constexpr uint64_t kBoolDead = ~uint64_t(0) - 1;      // q_anchor: no document can match (a MUST slot of df 0 or out of range, a query that is none)
@@ -517,6 +523,11 @@ struct PostingsBooleanParams {
     const uint8_t* occurs;          // [capacity_slots]
     uint64_t* q_anchor;             // [n_queries]
     uint32_t* q_flags;              // [n_queries]
+    const uint64_t* list_offsets;   // [n_lists + 1]          (the clause search; n_lists 0: none of the four is looked at)
+    const uint32_t* list_docs;      // [capacity_lists]
+    const uint32_t* list_tfs;       // [capacity_lists]
+    uint64_t capacity_lists;
+    uint32_t n_lists;               // S.n_terms + n_lists <= kPostingsMaxTerms
 };
 hipError_t launch_postings_boolean_queries(const PostingsBooleanParams& P, hipStream_t stream);
 hipError_t launch_postings_boolean_slots(const PostingsBooleanParams& P, hipStream_t stream);
@@ -546,8 +557,14 @@ hipError_t launch_postings_positions(const PostingsPositionsParams& P, hipStream
 // between queries and probe, train_scan (flags -> scan) between probe and heads and again between heads and emit, and train_radix_sort (hit,
 // stride 3: the score word, then the query word) between emit and take.  A launch behind probe that finds one of kPhraseErrors in the status
 // leaves the five outputs alone.
+// The phrase LISTS (vpt_postings_phrase_lists_device) are the same launches up to the second heads scan, with query_weights NULL (no weight is
+// looked at), and one launch of their own behind it: a head with scan value h writes list entry h {doc_base + document, pf}, a lane per query
+// bound writes list_offsets by ranges' rule; with one of kPhraseErrors in the status, or more entries than capacity_lists (kErrListsTooSmall),
+// it writes the counts only.  No sort, no take; doc_lens, k1, b, avgdl, k and the hit arrays are not looked at.
 constexpr uint32_t kPhraseMaxTerms = 64;
 constexpr uint32_t kPhraseErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrPhraseTooLong | kErrProbesTooSmall;
+constexpr uint32_t kClauseErrors = kSearchErrors | kPhraseErrors | kErrListsTooSmall;
+constexpr uint32_t kListsVoid = kErrPhraseTooLong | kErrProbesTooSmall | kErrListsTooSmall;   // set by the lists call alone: it wrote no list
 struct PostingsPhraseParams {
     const uint64_t* term_offsets;   // [n_terms + 1]
     const uint32_t* post_docs;      // [capacity_postings]
@@ -562,7 +579,7 @@ struct PostingsPhraseParams {
     const uint32_t* doc_lens;       // [n_docs]
     const uint64_t* query_offsets;  // [n_queries + 1]
     const int32_t* query_terms;     // [capacity_slots]
-    const float* query_weights;     // [n_queries]
+    const float* query_weights;     // [n_queries]; nullptr: the lists call
     uint32_t n_queries;
     uint64_t capacity_slots;        // < 2^32
     uint64_t n_places;              // capacity_probes, < 2^32
@@ -589,12 +606,17 @@ struct PostingsPhraseParams {
     uint64_t* match_counts;         // [n_queries]
     uint64_t* counts;               // [3]: probes, matches (written), skipped queries (added to: zero before the launches)
     uint32_t* status;
+    uint64_t* list_offsets;         // [n_queries + 1]        (the lists call)
+    uint32_t* list_docs;            // [capacity_lists]
+    uint32_t* list_tfs;             // [capacity_lists]
+    uint64_t capacity_lists;
 };
 hipError_t launch_postings_phrase_queries(const PostingsPhraseParams& P, hipStream_t stream);
 hipError_t launch_postings_phrase_probe(const PostingsPhraseParams& P, hipStream_t stream);
 hipError_t launch_postings_phrase_heads(const PostingsPhraseParams& P, hipStream_t stream);
 hipError_t launch_postings_phrase_emit(const PostingsPhraseParams& P, hipStream_t stream);    // emit, then the queries' ranges
 hipError_t launch_postings_phrase_take(const PostingsPhraseParams& P, hipStream_t stream);
+hipError_t launch_postings_phrase_lists(const PostingsPhraseParams& P, hipStream_t stream);   // behind the second heads scan
 // ConcatGraphemeClustersFilter on the labels (kernels_graphemes.hip): labels[ooff[i] + b] = 0 for every boundary b of sentence i inside an extended
 // grapheme cluster of the text as it was scored.  Two launches over tiles of kGraphemeTile chars, cut by flat position.
 constexpr uint32_t kGraphemeTile = 1024;

@@ -20,6 +20,11 @@
 // No atomic decides a value (one integer add, the status OR), every loop is bounded by kSearchMaxQuerySlots slots or 64 halvings, the launch
 // boundaries are the only ordering relied on: two runs give identical bytes.  Every index is bounded before it indexes anything: a slot below
 // capacity_slots, a term inside [0, n_terms), a posting below capacity_postings, a document below n_docs, a query below n_queries.
+// ONE OR TWO SEGMENTS.  The three kernels are templates over kTwo, and every list they touch comes from term_list<kTwo>: <false> is the boolean
+// search over the postings segment as it has always been; <true> (the clause search, n_lists > 0) takes a term inside [n_terms, n_terms +
+// n_lists) as list term - n_terms of the derived segment {list_offsets, list_docs, list_tfs, capacity_lists} with the same checks against
+// that segment's capacity: a list entry below capacity_lists.  The derived lists are the caller's arrays: what they hold is trusted no more
+// than a segment is.
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
@@ -43,10 +48,42 @@ __device__ __forceinline__ uint64_t slot_count(const PostingsSearchParams& S) {
     return n_all < S.capacity_slots ? n_all : S.capacity_slots;
 }
 
-// the clamped bounds of an in-range term's list: [a, b) inside [0, capacity_postings), empty when they are no list's
-__device__ __forceinline__ void term_bounds(const PostingsSearchParams& S, uint32_t term, uint64_t* a, uint64_t* b) {
-    const uint64_t ta = S.term_offsets[term], tb = S.term_offsets[term + 1];
-    const bool sound = ta <= tb && tb <= S.capacity_postings;
+// The list of a slot's term and the segment it lies in: {offsets, docs, tfs, capacity} of the postings segment for a term inside [0, n_terms),
+// and, with kTwo (the clause search), those of the derived segment for a term inside [n_terms, n_terms + n_lists).  False: out of range.
+struct TermList {
+    const uint64_t* offsets;
+    const uint32_t* docs;
+    const uint32_t* tfs;
+    uint64_t capacity;
+    uint32_t index;   // the list's entry in offsets
+};
+// lists: whether the derived segment may be looked at (lists_usable); without it a term on that side is out of range.
+template <bool kTwo>
+__device__ __forceinline__ bool term_list(const PostingsBooleanParams& P, int32_t term, TermList* L, bool lists) {
+    if (term < 0) return false;
+    if (uint32_t(term) < P.S.n_terms) {
+        *L = TermList{P.S.term_offsets, P.S.post_docs, P.S.post_tfs, P.S.capacity_postings, uint32_t(term)};
+        return true;
+    }
+    if (kTwo && lists && uint32_t(term) - P.S.n_terms < P.n_lists) {
+        *L = TermList{P.list_offsets, P.list_docs, P.list_tfs, P.capacity_lists, uint32_t(term) - P.S.n_terms};
+        return true;
+    }
+    return false;
+}
+
+// A lists call enqueued in front of the clause search with no sync between them that found its 64-term limit or one of its capacities
+// exceeded has written no list: the arrays hold what they held, and the status says so before the first launch here (kListsVoid: bits that
+// no launch of the searches sets, so every lane of a launch reads the same).  The derived segment is then not looked at.
+template <bool kTwo>
+__device__ __forceinline__ bool lists_usable(const PostingsBooleanParams& P) {
+    return kTwo && !(*P.S.status & kListsVoid);
+}
+
+// the clamped bounds of a list: [a, b) inside [0, its segment's capacity), empty when they are no list's
+__device__ __forceinline__ void term_bounds(const TermList& L, uint64_t* a, uint64_t* b) {
+    const uint64_t ta = L.offsets[L.index], tb = L.offsets[L.index + 1];
+    const bool sound = ta <= tb && tb <= L.capacity;
     *a = sound ? ta : 0;
     *b = sound ? tb : 0;
 }
@@ -58,10 +95,12 @@ __device__ __forceinline__ bool query_slots(const PostingsSearchParams& S, uint6
     return *a <= *b && *b <= S.capacity_slots && *b - *a <= kSearchMaxQuerySlots;
 }
 
+template <bool kTwo>
 __global__ __launch_bounds__(kBoolThreads) void boolean_queries_kernel(const PostingsBooleanParams P) {
     const PostingsSearchParams& S = P.S;
     const uint64_t q = uint64_t(blockIdx.x) * kBoolThreads + threadIdx.x;
     if (q >= S.n_queries) return;
+    const bool lists = lists_usable<kTwo>(P);
     uint64_t a, b, anchor = kBoolNoAnchor, best = ~uint64_t(0);
     uint32_t flags = 0, err = 0;
     bool dead = !query_slots(S, q, &a, &b);   // (what is wrong with the CSR: the slots launch says it)
@@ -73,7 +112,8 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_queries_kernel(const Pos
             if (occur != kOccurMust) continue;
             const int32_t term = S.query_terms[s];
             uint64_t ta = 0, tb = 0;
-            if (term >= 0 && uint32_t(term) < S.n_terms) term_bounds(S, uint32_t(term), &ta, &tb);
+            TermList L;
+            if (term_list<kTwo>(P, term, &L, lists)) term_bounds(L, &ta, &tb);
             const uint64_t df = tb - ta;
             if (df == 0) dead = true;
             else if (df < best) { best = df; anchor = s; }
@@ -84,10 +124,12 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_queries_kernel(const Pos
     if (err) atomicOr(S.status, err);
 }
 
+template <bool kTwo>
 __global__ __launch_bounds__(kBoolThreads) void boolean_slots_kernel(const PostingsBooleanParams P) {
     const PostingsSearchParams& S = P.S;
     const uint64_t s = uint64_t(blockIdx.x) * kBoolThreads + threadIdx.x, gstride = uint64_t(gridDim.x) * kBoolThreads;
     uint32_t err = 0;
+    const bool lists = lists_usable<kTwo>(P);
     for (uint64_t i = s; i < S.n_queries; i += gstride) {   // every entry once over the grid
         const uint64_t a = S.query_offsets[i], b = S.query_offsets[i + 1];
         if (a > b || b > S.capacity_slots) err |= kErrBadQueryCsr;
@@ -104,9 +146,10 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_slots_kernel(const Posti
                 const int32_t term = S.query_terms[s];
                 const uint32_t occur = P.occurs[s];
                 if (bits_of(S.query_weights[s]) > 0x7F7FFFFFu) err |= kErrBadWeights;
-                if (term >= 0 && uint32_t(term) < S.n_terms) {
-                    const uint64_t a = S.term_offsets[term], b = S.term_offsets[uint32_t(term) + 1];
-                    if (a > b || b > S.capacity_postings) {
+                TermList L;
+                if (term_list<kTwo>(P, term, &L, lists)) {
+                    const uint64_t a = L.offsets[L.index], b = L.offsets[L.index + 1];
+                    if (a > b || b > L.capacity) {
                         err |= kErrBadSegment;
                     } else {
                         const uint64_t anchor = P.q_anchor[q];
@@ -127,6 +170,7 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_slots_kernel(const Posti
     if (err) atomicOr(S.status, err);
 }
 
+template <bool kTwo>
 __global__ __launch_bounds__(kBoolThreads) void boolean_expand_kernel(const PostingsBooleanParams P) {
     const PostingsSearchParams& S = P.S;
     const uint64_t p = uint64_t(blockIdx.x) * kBoolThreads + threadIdx.x;
@@ -136,18 +180,20 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_expand_kernel(const Post
         if (total > S.n_places) atomicOr(S.status, kErrCandidatesTooSmall);
     }
     if (p >= S.n_places) return;
+    const bool lists = lists_usable<kTwo>(P);
     uint32_t err = 0, doc = 0, query = S.n_queries, cbits = 0;
     if (p < total && total <= S.n_places && S.capacity_slots) {
         const uint64_t s = vocab_owner(S.base, S.capacity_slots, p);   // the last slot whose base is <= p: the one with places there
         const uint64_t i = p - S.base[s];
         const int32_t term = S.query_terms[s];
         const uint32_t q = S.slot_query[s];
-        if (S.base[s] <= p && i < S.slot_df[s] && term >= 0 && uint32_t(term) < S.n_terms && q < S.n_queries) {
-            const uint64_t start = S.term_offsets[term], at = start + i;
-            if (at >= start && at < S.capacity_postings) {
-                const uint32_t d = S.post_docs[at], tf = S.post_tfs[at];
+        TermList L;
+        if (S.base[s] <= p && i < S.slot_df[s] && term_list<kTwo>(P, term, &L, lists) && q < S.n_queries) {
+            const uint64_t start = L.offsets[L.index], at = start + i;
+            if (at >= start && at < L.capacity) {
+                const uint32_t d = L.docs[at], tf = L.tfs[at];
                 const uint64_t rel = uint64_t(d) - S.doc_base;
-                if (tf == 0 || uint64_t(d) < S.doc_base || rel >= S.n_docs || (i > 0 && S.post_docs[at - 1] >= d)) {
+                if (tf == 0 || uint64_t(d) < S.doc_base || rel >= S.n_docs || (i > 0 && L.docs[at - 1] >= d)) {
                     err = kErrBadSegment;
                 } else {
                     const uint32_t dl = S.doc_lens[rel];
@@ -168,13 +214,14 @@ __global__ __launch_bounds__(kBoolThreads) void boolean_expand_kernel(const Post
                                 const int32_t other = S.query_terms[t];
                                 bool present = false;
                                 uint32_t otf = 0;
-                                if (other >= 0 && uint32_t(other) < S.n_terms) {
+                                TermList O;
+                                if (term_list<kTwo>(P, other, &O, lists)) {
                                     uint64_t ta, tb;
-                                    term_bounds(S, uint32_t(other), &ta, &tb);
-                                    const uint64_t j = first_at_least(S.post_docs, ta, tb, uint64_t(d));
-                                    if (j < tb && S.post_docs[j] == d) {
+                                    term_bounds(O, &ta, &tb);
+                                    const uint64_t j = first_at_least(O.docs, ta, tb, uint64_t(d));
+                                    if (j < tb && O.docs[j] == d) {
                                         present = true;
-                                        otf = S.post_tfs[j];
+                                        otf = O.tfs[j];
                                     }
                                 }
                                 if (occur == kOccurMustNot ? present : (occur == kOccurMust && !present)) { keep = false; break; }
@@ -208,18 +255,27 @@ inline uint32_t blocks_of(uint64_t n) { return uint32_t((n + kBoolThreads - 1) /
 }  // namespace
 
 hipError_t launch_postings_boolean_queries(const PostingsBooleanParams& P, hipStream_t stream) {
-    hipLaunchKernelGGL(boolean_queries_kernel, dim3(blocks_of(P.S.n_queries)), dim3(kBoolThreads), 0, stream, P);
+    if (P.n_lists)
+        hipLaunchKernelGGL(boolean_queries_kernel<true>, dim3(blocks_of(P.S.n_queries)), dim3(kBoolThreads), 0, stream, P);
+    else
+        hipLaunchKernelGGL(boolean_queries_kernel<false>, dim3(blocks_of(P.S.n_queries)), dim3(kBoolThreads), 0, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_postings_boolean_slots(const PostingsBooleanParams& P, hipStream_t stream) {
     const uint64_t lanes = P.S.capacity_slots > P.S.n_queries ? P.S.capacity_slots : uint64_t(P.S.n_queries);
-    hipLaunchKernelGGL(boolean_slots_kernel, dim3(blocks_of(lanes)), dim3(kBoolThreads), 0, stream, P);
+    if (P.n_lists)
+        hipLaunchKernelGGL(boolean_slots_kernel<true>, dim3(blocks_of(lanes)), dim3(kBoolThreads), 0, stream, P);
+    else
+        hipLaunchKernelGGL(boolean_slots_kernel<false>, dim3(blocks_of(lanes)), dim3(kBoolThreads), 0, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_postings_boolean_expand(const PostingsBooleanParams& P, hipStream_t stream) {
-    hipLaunchKernelGGL(boolean_expand_kernel, dim3(blocks_of(P.S.n_places ? P.S.n_places : 1)), dim3(kBoolThreads), 0, stream, P);
+    if (P.n_lists)
+        hipLaunchKernelGGL(boolean_expand_kernel<true>, dim3(blocks_of(P.S.n_places ? P.S.n_places : 1)), dim3(kBoolThreads), 0, stream, P);
+    else
+        hipLaunchKernelGGL(boolean_expand_kernel<false>, dim3(blocks_of(P.S.n_places ? P.S.n_places : 1)), dim3(kBoolThreads), 0, stream, P);
     return hipGetLastError();
 }
 

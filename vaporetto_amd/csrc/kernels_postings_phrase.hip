@@ -29,6 +29,10 @@
 //   ranges   a lane per query bound: qstart[q] = the head scan at the query's probe base; match_counts; the lane of n_queries writes counts[1].
 //   (sort)   train_radix_sort over the score word, then the query word: stable, so (query, score descending, document ascending).
 //   take     a lane per (query, j < k): hit qstart[q] + j of the ranked order; the lane of j == 0 writes hit_counts.
+// The phrase LISTS (vpt_postings_phrase_lists_device) run queries .. the second heads scan as they stand, with no weights, and then
+//   lists    a lane per place and per query bound: a head with scan value h writes list entry h {doc_base + document, pf} -- born in (phrase,
+//            document) order, so every list ascends; list_offsets[q] = the head scan at the phrase's probe base (ranges' rule); counts[1] = the
+//            entries.  More entries than capacity_lists (kErrListsTooSmall) or one of kPhraseErrors: the counts only.  No sort, no take.
 // No atomic decides a value (one integer add, the status OR), every loop is bounded by kPhraseMaxTerms or by 64 bisection steps, the launch
 // boundaries are the only ordering relied on: two runs give identical bytes.  Every index is bounded before it indexes anything: a slot below
 // capacity_slots, a term inside [0, n_terms), a posting below capacity_postings, a position place below capacity_positions, a document below
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_queries_kernel(const Po
         uint32_t anchor = 0;
         uint64_t run = 0, probes = 0;
         const uint64_t a = P.query_offsets[q], b = P.query_offsets[q + 1];
-        if (bits_of(P.query_weights[q]) > 0x7F7FFFFFu) err |= kErrBadWeights;
+        if (P.query_weights && bits_of(P.query_weights[q]) > 0x7F7FFFFFu) err |= kErrBadWeights;   // (the lists call has no weights)
         if (a > b || b > P.capacity_slots) {
             err |= kErrBadQueryCsr;
         } else if (b - a > kPhraseMaxTerms) {
@@ -266,6 +270,29 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_take_kernel(const Posti
     if (P.hit_freqs) P.hit_freqs[g] = P.hpf[x];
 }
 
+// The lists call's one launch, behind the second heads scan: a lane per place and per query bound.  Whether the entries fit is read from
+// the scan by every lane (no lane waits for the status word of its own launch); the status holds what the launches in front found.
+__global__ __launch_bounds__(kPhraseThreads) void phrase_lists_kernel(const PostingsPhraseParams P) {
+    const uint64_t p = uint64_t(blockIdx.x) * kPhraseThreads + threadIdx.x;
+    const uint64_t n = P.n_places;
+    const uint64_t entries = P.scan[n];
+    const bool fits = entries <= P.capacity_lists;
+    if (p == 0) {
+        P.counts[1] = entries;
+        if (!fits) atomicOr(P.status, kErrListsTooSmall);
+    }
+    if (!fits || (*P.status & kPhraseErrors)) return;   // (kErrListsTooSmall of this launch is `fits`; of an earlier call: the caller's to sync)
+    if (p <= P.n_queries) {   // phrase_ranges_kernel's rule: the head scan at the query's probe base
+        const uint64_t at = P.base[p] < n ? P.base[p] : n;
+        P.list_offsets[p] = P.scan[at];
+    }
+    if (p >= n || !P.flags[p]) return;
+    const uint64_t h = P.scan[p];   // (heads in front of p: below entries <= capacity_lists)
+    if (h >= P.capacity_lists || uint64_t(P.pdoc[p]) >= P.n_docs) return;
+    P.list_docs[h] = uint32_t(P.doc_base + P.pdoc[p]);
+    P.list_tfs[h] = P.plen[p];
+}
+
 inline uint32_t blocks_of(uint64_t n) { return uint32_t((n + kPhraseThreads - 1) / kPhraseThreads); }
 
 }  // namespace
@@ -295,6 +322,12 @@ hipError_t launch_postings_phrase_heads(const PostingsPhraseParams& P, hipStream
 hipError_t launch_postings_phrase_emit(const PostingsPhraseParams& P, hipStream_t stream) {
     if (P.n_places) hipLaunchKernelGGL(phrase_emit_kernel, dim3(blocks_of(P.n_places)), dim3(kPhraseThreads), 0, stream, P);
     hipLaunchKernelGGL(phrase_ranges_kernel, dim3(blocks_of(uint64_t(P.n_queries) + 1)), dim3(kPhraseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_postings_phrase_lists(const PostingsPhraseParams& P, hipStream_t stream) {
+    const uint64_t lanes = P.n_places > P.n_queries ? P.n_places : uint64_t(P.n_queries) + 1;
+    hipLaunchKernelGGL(phrase_lists_kernel, dim3(blocks_of(lanes)), dim3(kPhraseThreads), 0, stream, P);
     return hipGetLastError();
 }
 

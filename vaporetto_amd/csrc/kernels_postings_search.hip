@@ -24,7 +24,8 @@
 // No atomic decides a value (one integer add, the status OR), no loop's trip count depends on what another lane of the launch writes, the launch
 // boundaries are the only ordering relied on: two runs give identical bytes.  Every index is bounded before it indexes anything: a term inside
 // [0, n_terms), a posting below capacity_postings, a document below n_docs, a slot below capacity_slots, a sorted index below the places, an
-// output below n_queries * k.  With one of kSearchErrors in the status, ranges and take write nothing: the four outputs stay as they were.
+// output below n_queries * k.  With one of error_mask (kSearchErrors; the clause search: kClauseErrors) in the status, ranges and take write
+// nothing: the four outputs stay as they were.
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
@@ -173,14 +174,14 @@ __global__ __launch_bounds__(kSearchThreads) void search_ranges_kernel(const Pos
     const uint64_t a = P.scan[first_at_least(P.skey, 0, n, q)];
     P.qstart[q] = a;
     if (q == P.n_queries) { P.counts[1] = a; return; }
-    if (*P.status & kSearchErrors) return;
+    if (*P.status & P.error_mask) return;
     const uint64_t b = P.scan[first_at_least(P.skey, 0, n, q + 1)];
     P.match_counts[q] = b >= a ? b - a : 0;
 }
 
 __global__ __launch_bounds__(kSearchThreads) void search_take_kernel(const PostingsSearchParams P) {
     const uint64_t g = uint64_t(blockIdx.x) * kSearchThreads + threadIdx.x;
-    if (g >= uint64_t(P.n_queries) * P.k || (*P.status & kSearchErrors)) return;
+    if (g >= uint64_t(P.n_queries) * P.k || (*P.status & P.error_mask)) return;
     const uint32_t q = uint32_t(g / P.k), j = uint32_t(g % P.k);
     const uint64_t a = P.qstart[q], b = P.qstart[q + 1];
     const uint64_t matches = b >= a ? b - a : 0;

@@ -95,8 +95,8 @@ struct MergeScratch {
     size_t bytes(bool ordered) const { return ordered ? o.bytes() : g.bytes(); }
 };
 
-// vpt_postings_search_device and, boolean, vpt_postings_boolean_search_device (PostingsSearchParams, PostingsBooleanParams): n candidate
-// places, ns slots, nq queries
+// vpt_postings_search_device and, boolean, vpt_postings_boolean_search_device and vpt_postings_clause_search_device (PostingsSearchParams,
+// PostingsBooleanParams; the clause search's derived lists are the caller's arrays, not scratch): n candidate places, ns slots, nq queries
 struct SearchScratch {
     const size_t n, ns, nq;
     const bool boolean;
@@ -112,7 +112,8 @@ struct SearchScratch {
     size_t bytes() const { return c.bytes(); }
 };
 
-// vpt_postings_phrase_search_device (PostingsPhraseParams): n probe places, nq queries
+// vpt_postings_phrase_search_device and vpt_postings_phrase_lists_device (PostingsPhraseParams; the lists call leaves hpf, order, skey, hit
+// and the sort's histograms idle): n probe places, nq queries
 struct PhraseScratch {
     const size_t n, nq;
     Carver c{};
