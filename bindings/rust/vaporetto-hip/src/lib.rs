@@ -691,6 +691,66 @@ impl Postings {
     /// (document, score, frequency) by score descending, then document ascending, and the match counts.
     pub fn phrase_search(&self, predictor: &Predictor, first: &[u64], positions: &[u32], phrases: &[Vec<i32>], doc_lens: &[u32], doc_base: u64,
                          k: u32, k1: f32, b: f32) -> Result<(Vec<Vec<(u32, f32, u32)>>, Vec<u64>)> {
+        self.phrase_search_with(predictor, first, positions, phrases, None, doc_lens, doc_base, k, k1, b)
+    }
+
+    /// `phrase_search` with a slop budget per phrase (`vpt_postings_sloppy_phrase_search`; tantivy's `PhraseQuery::set_slop`, the definition
+    /// is in include/vaporetto_hip.h): `slops[q]` in 0 ..= 31 is phrase q's; the frequency of a hit is the number of distinct occurrences
+    /// under that slop.  With every slop 0 the result is `phrase_search`'s.
+    pub fn sloppy_phrase_search(&self, predictor: &Predictor, first: &[u64], positions: &[u32], phrases: &[Vec<i32>], slops: &[u32],
+                                doc_lens: &[u32], doc_base: u64, k: u32, k1: f32, b: f32)
+                                -> Result<(Vec<Vec<(u32, f32, u32)>>, Vec<u64>)> {
+        if slops.len() != phrases.len() {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: slops: one per phrase".into()));
+        }
+        self.phrase_search_with(predictor, first, positions, phrases, Some(slops), doc_lens, doc_base, k, k1, b)
+    }
+
+    /// The posting list of every phrase under its slop (`vpt_postings_sloppy_phrase_lists`): `(list_offsets, list_docs, list_tfs)`, list q the
+    /// entries `list_offsets[q] .. list_offsets[q + 1]`: the global numbers of the documents that match phrase q, ascending, and their
+    /// phrase frequencies -- what `vpt_postings_clause_search_device` takes as derived lists.
+    pub fn sloppy_phrase_lists(&self, predictor: &Predictor, first: &[u64], positions: &[u32], phrases: &[Vec<i32>], slops: &[u32],
+                               n_documents: u64, doc_base: u64) -> Result<(Vec<u64>, Vec<u32>, Vec<u32>)> {
+        if phrases.is_empty() {
+            return Ok((vec![0u64], Vec::new(), Vec::new()));
+        }
+        let n = self.term_offsets.len();
+        if n == 0 || slops.len() != phrases.len() || self.docs.len() != self.tfs.len() || self.term_offsets[n - 1] != self.docs.len() as u64
+            || first.len() != self.docs.len() + 1 || first[first.len() - 1] != positions.len() as u64 {
+            return Err(HipError::InvalidArgument("InvalidArgumentError: sloppy_phrase_lists: the arrays do not belong together".into()));
+        }
+        let mut offsets = vec![0u64];
+        let mut terms = Vec::new();
+        let mut capacity = 0u64;   // per phrase the smallest df among its terms: what always suffices
+        for q in phrases {
+            let mut bound: Option<u64> = None;
+            for &t in q {
+                let df = if t >= 0 && (t as usize) < n - 1 { self.df(t as usize) } else { 0 };
+                bound = Some(match bound { Some(x) => x.min(df), None => df });
+                terms.push(t);
+            }
+            capacity += bound.unwrap_or(0);
+            offsets.push(terms.len() as u64);
+        }
+        terms.push(0);
+        let mut pos = positions.to_vec();
+        pos.push(0);
+        let mut list_offsets = vec![0u64; phrases.len() + 1];
+        let (mut list_docs, mut list_tfs) = (vec![0u32; capacity as usize + 1], vec![0u32; capacity as usize + 1]);
+        let mut counts = [0u64; 3];
+        check(unsafe {
+            ffi::vpt_postings_sloppy_phrase_lists(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(), first.as_ptr(),
+                                                  pos.as_ptr(), (n - 1) as u32, doc_base, n_documents, offsets.as_ptr(), terms.as_ptr(),
+                                                  slops.as_ptr(), phrases.len() as u32, list_offsets.as_mut_ptr(), list_docs.as_mut_ptr(),
+                                                  list_tfs.as_mut_ptr(), capacity, counts.as_mut_ptr())
+        })?;
+        list_docs.truncate(counts[1] as usize);
+        list_tfs.truncate(counts[1] as usize);
+        Ok((list_offsets, list_docs, list_tfs))
+    }
+
+    fn phrase_search_with(&self, predictor: &Predictor, first: &[u64], positions: &[u32], phrases: &[Vec<i32>], slops: Option<&[u32]>,
+                          doc_lens: &[u32], doc_base: u64, k: u32, k1: f32, b: f32) -> Result<(Vec<Vec<(u32, f32, u32)>>, Vec<u64>)> {
         if phrases.is_empty() {
             return Ok((Vec::new(), Vec::new()));
         }
@@ -722,10 +782,19 @@ impl Postings {
         let (mut hit_docs, mut hit_scores, mut hit_freqs) = (vec![0u32; n_out], vec![0f32; n_out], vec![0u32; n_out]);
         let (mut hit_counts, mut match_counts, mut counts) = (vec![0u32; phrases.len()], vec![0u64; phrases.len()], [0u64; 3]);
         check(unsafe {
-            ffi::vpt_postings_phrase_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(), first.as_ptr(), pos.as_ptr(),
-                                            (n - 1) as u32, doc_base, doc_lens.len() as u64, doc_lens.as_ptr(), offsets.as_ptr(), terms.as_ptr(),
-                                            weights.as_ptr(), phrases.len() as u32, k1, b, avgdl, k, hit_docs.as_mut_ptr(), hit_scores.as_mut_ptr(),
-                                            hit_freqs.as_mut_ptr(), hit_counts.as_mut_ptr(), match_counts.as_mut_ptr(), counts.as_mut_ptr())
+            match slops {
+                None => ffi::vpt_postings_phrase_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(),
+                                                        first.as_ptr(), pos.as_ptr(), (n - 1) as u32, doc_base, doc_lens.len() as u64,
+                                                        doc_lens.as_ptr(), offsets.as_ptr(), terms.as_ptr(), weights.as_ptr(), phrases.len() as u32,
+                                                        k1, b, avgdl, k, hit_docs.as_mut_ptr(), hit_scores.as_mut_ptr(), hit_freqs.as_mut_ptr(),
+                                                        hit_counts.as_mut_ptr(), match_counts.as_mut_ptr(), counts.as_mut_ptr()),
+                Some(s) => ffi::vpt_postings_sloppy_phrase_search(predictor.raw, self.term_offsets.as_ptr(), self.docs.as_ptr(), self.tfs.as_ptr(),
+                                                                  first.as_ptr(), pos.as_ptr(), (n - 1) as u32, doc_base, doc_lens.len() as u64,
+                                                                  doc_lens.as_ptr(), offsets.as_ptr(), terms.as_ptr(), weights.as_ptr(), s.as_ptr(),
+                                                                  phrases.len() as u32, k1, b, avgdl, k, hit_docs.as_mut_ptr(),
+                                                                  hit_scores.as_mut_ptr(), hit_freqs.as_mut_ptr(), hit_counts.as_mut_ptr(),
+                                                                  match_counts.as_mut_ptr(), counts.as_mut_ptr()),
+            }
         })?;
         let hits = (0..phrases.len())
             .map(|q| (0..hit_counts[q] as usize).map(|j| { let at = q * k as usize + j; (hit_docs[at], hit_scores[at], hit_freqs[at]) }).collect())

@@ -27,6 +27,9 @@
 // of a clause takes the clause's occur; the lines of --search.
 //   ./token_stream model.bin wsconst --postings vocab.txt [doc_base] [--segment-docs N] --boolean "QUERY" [--top K] --phrases < documents.txt
 // With --phrases as the last argument: the documents are indexed with positions and a clause of several tokens is ONE exact phrase.
+//   ... --phrase "QUERY" [--top K] --slop N          ... --boolean "QUERY" [--top K] --slop N --phrases
+// With --slop N behind --phrase (as the last argument) or in front of --phrases: the phrase, or every phrase clause, may be off by N (0 .. 31)
+// positions in all, as tantivy's PhraseQuery::set_slop; the same lines.
 // With --segment-docs N the positional segments of N documents each are merged on the device with their position lists (the same lines come
 // out; stderr tells "segments <TAB> n <TAB> postings <TAB> n <TAB> positions <TAB> n").
 #include <cstdlib>
@@ -93,7 +96,9 @@ int main(int argc, char** argv) {
             const char* boolean = nullptr;
             uint32_t top = 10;
             bool phrases = false;
+            uint32_t slop = 0;
             if (n_args > 7 && std::strcmp(argv[n_args - 1], "--phrases") == 0) { phrases = true; n_args -= 1; }
+            if (n_args > 8 && std::strcmp(argv[n_args - 2], "--slop") == 0) { slop = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--top") == 0) { top = uint32_t(std::strtoul(argv[n_args - 1], nullptr, 10)); n_args -= 2; }
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--segment-docs") == 0) { segment_docs = std::strtoull(argv[n_args - 1], nullptr, 10); n_args -= 2; }   // (behind the query, too)
             if (n_args > 6 && std::strcmp(argv[n_args - 2], "--search") == 0) { query = argv[n_args - 1]; n_args -= 2; }
@@ -113,7 +118,7 @@ int main(int argc, char** argv) {
                     post = plain.index(docs, vocab, doc_base, true, true);
                 }
                 if (boolean) {
-                    const auto found = plain.boolean_search(post, vocab, {std::string(boolean)}, plain.doc_lens(docs, vocab), doc_base, top, 1.2f, 0.75f, true, true);
+                    const auto found = plain.boolean_search(post, vocab, {std::string(boolean)}, plain.doc_lens(docs, vocab), doc_base, top, 1.2f, 0.75f, true, true, slop);
                     for (const vaporetto_hip::Postings::Hit& h : found.hits[0]) {
                         uint32_t bits;
                         std::memcpy(&bits, &h.score, 4);
@@ -121,7 +126,7 @@ int main(int argc, char** argv) {
                     }
                     return 0;
                 }
-                const auto found = plain.phrase_search(post, vocab, {std::string(phrase)}, plain.doc_lens(docs, vocab), doc_base, top);
+                const auto found = plain.phrase_search(post, vocab, {std::string(phrase)}, plain.doc_lens(docs, vocab), doc_base, top, 1.2f, 0.75f, true, slop);
                 for (const vaporetto_hip::Postings::PhraseHit& h : found.hits[0]) {
                     uint32_t bits;
                     std::memcpy(&bits, &h.score, 4);

@@ -1005,6 +1005,86 @@ vpt_status vpt_postings_clause_search(const vpt_predictor *p, const uint64_t *te
                                       uint64_t *counts_out);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Sloppy phrase queries on the device: a slop budget per phrase                     (tantivy's PhraseQuery::set_slop, `"東京 特許"~2`: behind a
+ *                                        morphological tokenizer a particle or another split between two query tokens makes an exact phrase miss)
+ *
+ * vpt_postings_sloppy_phrase_search_device: vpt_postings_phrase_search_device's arguments plus d_query_slops uint32 [n_queries] (NULL: every
+ *   slop 0), one slop in [0, 31] per query (vpt_postings_sloppy_phrase_limits).
+ *   THE DEFINITION.  A query is one phrase of L slots with one weight and one slop.  For slot j and document d the ADJUSTED POSITIONS are
+ *   p - j over the positions p of posting (term_j, d): signed 64-bit values, which may be negative.  An integer s is an OCCURRENCE of the
+ *   phrase in d when (1) every slot j has an adjusted position in [s, s + slop] and (2) some slot has the adjusted position s itself.
+ *   pf(q, d) = the number of distinct occurrences, clamped to 2^32 - 1; d MATCHES q when pf >= 1; the score is the exact search's, with
+ *   f = float(pf).  Put another way: one position is chosen per slot, the choice matches when max(p_j - j) - min(p_j - j) <= slop, and pf
+ *   counts the distinct minima of the matching choices.
+ *   So "A B C" with slop 1 matches `A X B C` and `A B X C` but not `A X B X C`, and "A B" matches `B A` with slop 2 and not with slop 1:
+ *   the cases the documentation of tantivy's set_slop lists.  The integer pf is THIS PROJECT'S OWN count (no tantivy source was at hand to
+ *   compare the phrase frequency of a sloppy match against); which documents match is what those cases fix.
+ *   Slots choose independently: a token may serve two slots that name the same term, so "A A" with slop 1 matches a document with a single
+ *   A (at position p: s = p - 1).  With slop 0 the definition is the exact search's: every adjusted position equals s, s >= 0 follows from slot 0, a
+ *   repeated term needs two distinct places -- with every slop 0, or d_query_slops NULL, the five outputs and d_counts are
+ *   vpt_postings_phrase_search_device's byte for byte.  The result is a function of the document: it does not depend on the anchor.
+ *   Launches: the exact search's, with the sloppy probe in probe's place (kernels_postings_phrase.hip).  A lane per probe place makes
+ *   probe's checks; with a = its anchor position - anchor slot it OWNS the occurrences s in [lo, a], lo = max(a - slop, a_prev + 1), a_prev
+ *   the adjusted position of the place before it in the same posting -- every occurrence has an anchor position in [s, s + slop] and
+ *   belongs to the lane of the first one at or after s.  Per slot (the anchor's included, a repeated term like any other): the document's
+ *   posting by bisection, one bisection to the first position >= max(lo + j, 0), a walk of at most 2 * slop + 1 places (bounded by the
+ *   count of steps, not by the values read) that sets bit p - j - lo of a 64-bit mask M_j (2 * 31 + 1 = 63 bits: the limit); C_j = M_j
+ *   smeared down by 0 .. slop; the lane's count = popcount(AND C_j & OR M_j & bits [0, a - lo]), 0 .. 32.  heads sums the counts of a
+ *   posting (the scan's difference) and clamps.  No LDS, no atomic other than the status OR.  Probes, capacity_probes, scratch, counts and
+ *   determinism: the exact search's.
+ *   At the call: the exact search's list.  At the sync: the exact search's list, and "InvalidArgumentError: query: a slop above 31"; after
+ *   any of them the five outputs are as they were.  Positions that do not ascend inside a posting: the result is unspecified and bounded
+ *   as in the exact search; nothing is read outside the stated sizes and d_query_slops [n_queries].
+ * vpt_postings_sloppy_phrase_lists_device: vpt_postings_phrase_lists_device's arguments plus d_phrase_slops uint32 [n_phrases] (NULL: all
+ *   0); the lists hold the sloppy pf and feed vpt_postings_clause_search_device unchanged.  A phrase of one in-range term has that term's
+ *   own list at any slop.  A slop above 31: the message above at the sync, no list is written, and a clause search enqueued behind it
+ *   leaves its outputs alone.
+ * vpt_postings_sloppy_phrase_limits: the most slots a phrase may have and the largest slop.
+ * vpt_postings_sloppy_phrase_search, vpt_postings_sloppy_phrase_lists: the same over HOST arrays, as vpt_postings_phrase_search and
+ *   vpt_postings_phrase_lists are (query_slops / phrase_slops NULL: all 0).
+ * vpt_postings_sloppy_clause_search: vpt_postings_clause_search with clause_slops uint32 [clauses] (NULL: all 0): the slop of every clause
+ *   that is a phrase; a one-term clause's entry is not looked at. */
+vpt_status vpt_postings_sloppy_phrase_search_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets,
+                                                    const uint32_t *d_post_docs, const uint32_t *d_post_tfs, const uint64_t *d_post_first,
+                                                    const uint32_t *d_post_positions, uint32_t n_terms, uint64_t capacity_postings,
+                                                    uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                                    const uint32_t *d_doc_lens, const uint64_t *d_query_offsets, const int32_t *d_query_terms,
+                                                    const float *d_query_weights, const uint32_t *d_query_slops, uint32_t n_queries,
+                                                    uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                                    uint64_t capacity_probes, uint32_t *d_hit_docs, float *d_hit_scores, uint32_t *d_hit_freqs,
+                                                    uint32_t *d_hit_counts, uint64_t *d_match_counts, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_sloppy_phrase_lists_device(const vpt_predictor *p, vpt_batch *b, const uint64_t *d_term_offsets,
+                                                   const uint32_t *d_post_docs, const uint32_t *d_post_tfs, const uint64_t *d_post_first,
+                                                   const uint32_t *d_post_positions, uint32_t n_terms, uint64_t capacity_postings,
+                                                   uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
+                                                   const uint64_t *d_phrase_offsets, const int32_t *d_phrase_terms,
+                                                   const uint32_t *d_phrase_slops, uint32_t n_phrases, uint64_t capacity_slots,
+                                                   uint64_t capacity_probes, uint64_t *d_list_offsets, uint32_t *d_list_docs,
+                                                   uint32_t *d_list_tfs, uint64_t capacity_lists, uint64_t *d_counts, void *hip_stream);
+vpt_status vpt_postings_sloppy_phrase_limits(uint32_t *max_phrase_terms, uint32_t *max_slop);
+vpt_status vpt_postings_sloppy_phrase_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs,
+                                             const uint32_t *post_tfs, const uint64_t *post_first, const uint32_t *post_positions,
+                                             uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint32_t *doc_lens,
+                                             const uint64_t *query_offsets, const int32_t *query_terms, const float *query_weights,
+                                             const uint32_t *query_slops, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                             uint32_t *hit_docs_out, float *hit_scores_out, uint32_t *hit_freqs_out, uint32_t *hit_counts_out,
+                                             uint64_t *match_counts_out, uint64_t *counts_out);
+vpt_status vpt_postings_sloppy_phrase_lists(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs,
+                                            const uint32_t *post_tfs, const uint64_t *post_first, const uint32_t *post_positions,
+                                            uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint64_t *phrase_offsets,
+                                            const int32_t *phrase_terms, const uint32_t *phrase_slops, uint32_t n_phrases,
+                                            uint64_t *list_offsets_out, uint32_t *list_docs_out, uint32_t *list_tfs_out,
+                                            uint64_t capacity_lists, uint64_t *counts_out);
+vpt_status vpt_postings_sloppy_clause_search(const vpt_predictor *p, const uint64_t *term_offsets, const uint32_t *post_docs,
+                                             const uint32_t *post_tfs, const uint64_t *post_first, const uint32_t *post_positions,
+                                             uint32_t n_terms, uint64_t doc_base, uint64_t n_documents, const uint32_t *doc_lens,
+                                             const uint64_t *query_offsets, const uint64_t *clause_offsets, const int32_t *clause_terms,
+                                             const float *clause_weights, const uint8_t *clause_occurs, const uint32_t *clause_slops,
+                                             uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k, uint32_t *hit_docs_out,
+                                             float *hit_scores_out, uint32_t *hit_counts_out, uint64_t *match_counts_out,
+                                             uint64_t *counts_out);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Merging POSITIONAL segments on the device: phrase search over a corpus indexed in batches          (no item of the adapter: the merge above
  *                                                                         with the position lists carried along, so the merged index serves phrases)
  *

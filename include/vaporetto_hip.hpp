@@ -500,6 +500,8 @@ struct Postings {
     // Exact-phrase BM25 top-k of every phrase over this POSITIONAL segment (vpt_postings_phrase_search; the definition is in vaporetto_hip.h).
     // phrases: term ids, each vector ONE phrase, its ids at consecutive positions in order; an id outside [0, n_terms) makes it match nothing.
     // weights: one per phrase, or nullptr for tantivy's phrase weight (the float sum, in slot order, of vpt_okapi_idf over the slots).
+    // slop: the slop of every phrase, 0 .. 31 (tantivy's set_slop; the definition is in vaporetto_hip.h); 0 is the exact call, anything else
+    // vpt_postings_sloppy_phrase_search.
     struct PhraseHit { uint32_t document; float score; uint32_t freq; };
     struct PhraseResult {
         std::vector<std::vector<PhraseHit>> hits;   // per phrase at most k, by score descending, then document ascending
@@ -508,21 +510,21 @@ struct Postings {
     };
     PhraseResult phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases, const std::vector<uint32_t>& doc_lens,
                                uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
-                               const std::vector<float>* weights = nullptr) const;
+                               const std::vector<float>* weights = nullptr, uint32_t slop = 0) const;
     // BM25 top-k of every boolean query of CLAUSES over this POSITIONAL segment (vpt_postings_clause_search; the definition is in
     // vaporetto_hip.h).  A clause of one term is a slot of that term, as in boolean_search; every other clause is ONE exact phrase scored by
     // its phrase frequency (an id outside [0, n_terms) makes it match nothing, and so does an empty clause).  weights: shaped as queries, or
     // nullptr for the phrase weight of phrase_search per MUST / SHOULD clause and 0 per MUST_NOT clause.  counts of the result: the places, the
-    // matches, the skipped clauses.
+    // matches, the skipped clauses.  slop: the slop of every clause that is a phrase (vpt_postings_sloppy_clause_search when not 0).
     struct PhraseClause { std::vector<int32_t> terms; uint8_t occur; };
     SearchResult clause_search(const Predictor& predictor, const std::vector<std::vector<PhraseClause>>& queries, const std::vector<uint32_t>& doc_lens,
                                uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f, float b = 0.75f,
-                               const std::vector<std::vector<float>>* weights = nullptr) const;
+                               const std::vector<std::vector<float>>* weights = nullptr, uint32_t slop = 0) const;
 };
 
 inline Postings::SearchResult Postings::clause_search(const Predictor& predictor, const std::vector<std::vector<PhraseClause>>& queries,
                                                       const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
-                                                      const std::vector<std::vector<float>>* weights) const {
+                                                      const std::vector<std::vector<float>>* weights, uint32_t slop) const {
     SearchResult out;
     if (queries.empty()) return out;
     if (first.size() != docs.size() + 1)
@@ -565,10 +567,18 @@ inline Postings::SearchResult Postings::clause_search(const Predictor& predictor
     std::vector<uint32_t> hd(n_out), hc(queries.size());
     std::vector<float> hs(n_out);
     out.match_counts.assign(queries.size(), 0);
-    detail::check(vpt_postings_clause_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(), uint32_t(n_terms()),
-                                             doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), coff.data(), terms.data(), w.data(), occurs.data(),
-                                             uint32_t(queries.size()), k1, b, avgdl, k, hd.data(), hs.data(), hc.data(), out.match_counts.data(),
-                                             out.counts));
+    if (slop == 0) {
+        detail::check(vpt_postings_clause_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(),
+                                                 uint32_t(n_terms()), doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), coff.data(), terms.data(),
+                                                 w.data(), occurs.data(), uint32_t(queries.size()), k1, b, avgdl, k, hd.data(), hs.data(), hc.data(),
+                                                 out.match_counts.data(), out.counts));
+    } else {
+        const std::vector<uint32_t> slops(occurs.size(), slop);
+        detail::check(vpt_postings_sloppy_clause_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(),
+                                                        uint32_t(n_terms()), doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), coff.data(),
+                                                        terms.data(), w.data(), occurs.data(), slops.data(), uint32_t(queries.size()), k1, b, avgdl, k,
+                                                        hd.data(), hs.data(), hc.data(), out.match_counts.data(), out.counts));
+    }
     out.hits.resize(queries.size());
     for (size_t q = 0; q < queries.size(); ++q)
         for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(Hit{hd[q * size_t(k) + j], hs[q * size_t(k) + j]});
@@ -577,7 +587,7 @@ inline Postings::SearchResult Postings::clause_search(const Predictor& predictor
 
 inline Postings::PhraseResult Postings::phrase_search(const Predictor& predictor, const std::vector<std::vector<int32_t>>& phrases,
                                                       const std::vector<uint32_t>& doc_lens, uint64_t doc_base, uint32_t k, float k1, float b,
-                                                      const std::vector<float>* weights) const {
+                                                      const std::vector<float>* weights, uint32_t slop) const {
     PhraseResult out;
     if (phrases.empty()) return out;
     if (first.size() != docs.size() + 1)
@@ -612,9 +622,18 @@ inline Postings::PhraseResult Postings::phrase_search(const Predictor& predictor
     std::vector<uint32_t> hd(n_out), hf(n_out), hc(phrases.size());
     std::vector<float> hs(n_out);
     out.match_counts.assign(phrases.size(), 0);
-    detail::check(vpt_postings_phrase_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(), uint32_t(n_terms()),
-                                             doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), terms.data(), w.data(), uint32_t(phrases.size()), k1, b,
-                                             avgdl, k, hd.data(), hs.data(), hf.data(), hc.data(), out.match_counts.data(), out.counts));
+    if (slop == 0) {
+        detail::check(vpt_postings_phrase_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(),
+                                                 uint32_t(n_terms()), doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), terms.data(), w.data(),
+                                                 uint32_t(phrases.size()), k1, b, avgdl, k, hd.data(), hs.data(), hf.data(), hc.data(),
+                                                 out.match_counts.data(), out.counts));
+    } else {
+        const std::vector<uint32_t> slops(phrases.size(), slop);
+        detail::check(vpt_postings_sloppy_phrase_search(predictor.raw(), term_offsets.data(), docs.data(), tfs.data(), first.data(), pos.data(),
+                                                        uint32_t(n_terms()), doc_base, doc_lens.size(), doc_lens.data(), qoff.data(), terms.data(),
+                                                        w.data(), slops.data(), uint32_t(phrases.size()), k1, b, avgdl, k, hd.data(), hs.data(),
+                                                        hf.data(), hc.data(), out.match_counts.data(), out.counts));
+    }
     out.hits.resize(phrases.size());
     for (size_t q = 0; q < phrases.size(); ++q)
         for (uint32_t j = 0; j < hc[q]; ++j) out.hits[q].push_back(PhraseHit{hd[q * size_t(k) + j], hs[q * size_t(k) + j], hf[q * size_t(k) + j]});
@@ -973,10 +992,10 @@ public:
     // of it is a slot of the clause's occur; an empty clause adds nothing; then Postings::boolean_search with the idf weights.  phrases (what
     // tantivy's query parser does; `postings` indexed with positions): a clause of several tokens is ONE exact phrase -- a token without a
     // vocabulary entry makes it match nothing -- a clause of one token a term slot, a clause without a token adds nothing; then
-    // Postings::clause_search with the phrase weights.
+    // Postings::clause_search with the phrase weights and `slop` for every phrase clause (a `~` in a text stays a character of its clause).
     Postings::SearchResult boolean_search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
                                           const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f,
-                                          float b = 0.75f, bool normalize = true, bool phrases = false) const {
+                                          float b = 0.75f, bool normalize = true, bool phrases = false, uint32_t slop = 0) const {
         std::vector<std::string> clauses;
         std::vector<std::pair<size_t, uint8_t>> owner;
         for (size_t i = 0; i < texts.size(); ++i) {
@@ -1008,20 +1027,20 @@ public:
                         cq[owner[c].first].push_back(Postings::PhraseClause{
                             std::vector<int32_t>(enc.second.begin() + enc.first[c], enc.second.begin() + enc.first[c + 1]), owner[c].second});
             }
-            return postings.clause_search(predictor_, cq, doc_lens, doc_base, k, k1, b);
+            return postings.clause_search(predictor_, cq, doc_lens, doc_base, k, k1, b, nullptr, slop);
         }
         return postings.boolean_search(predictor_, queries, doc_lens, doc_base, k, k1, b);
     }
 
     // Exact-phrase BM25 top-k of query TEXTS over a positional `postings` (index with positions): each text is tokenised and encoded as
-    // documents are and is ONE phrase -- a token without a vocabulary entry makes it match nothing -- then Postings::phrase_search.
+    // documents are and is ONE phrase -- a token without a vocabulary entry makes it match nothing -- then Postings::phrase_search (slop: its).
     Postings::PhraseResult phrase_search(const Postings& postings, const Vocabulary& vocab, const std::vector<std::string>& texts,
                                          const std::vector<uint32_t>& doc_lens, uint64_t doc_base = 0, uint32_t k = 10, float k1 = 1.2f,
-                                         float b = 0.75f, bool normalize = true) const {
+                                         float b = 0.75f, bool normalize = true, uint32_t slop = 0) const {
         const auto enc = encode(texts, vocab, normalize);
         std::vector<std::vector<int32_t>> phrases(texts.size());
         for (size_t i = 0; i < texts.size(); ++i) phrases[i].assign(enc.second.begin() + enc.first[i], enc.second.begin() + enc.first[i + 1]);
-        return postings.phrase_search(predictor_, phrases, doc_lens, doc_base, k, k1, b);
+        return postings.phrase_search(predictor_, phrases, doc_lens, doc_base, k, k1, b, nullptr, slop);
     }
 
 private:

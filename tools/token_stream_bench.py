@@ -30,6 +30,10 @@ Per workload (bench.py's configs[2] batch -- --sentences of it, 0: all -- and it
       terms drawn by count as --search draws them, all MUST; (b) Q all-MUST queries of L consecutive tokens of a random document as --phrase
       draws them, so each matches at least once (every_query_matches); (c) the queries of (a) as all-SHOULD (equals_or_search: the OR search's
       bytes).  Places against candidates, matches, times and ratios (profiles/postings_boolean_bench.json).
+  --sloppy Q,L,S,K: with --postings, the phrases --phrase Q,L,K draws (the same generator and seed), top K, timed three ways in one process by
+      device events: the exact phrase search, the sloppy search (vpt_postings_sloppy_phrase_search_device) with every slop 0 -- whose bytes
+      the run checks against the exact search's -- and the sloppy search at slop S; the probes, the matches and both ratios
+      (profiles/postings_sloppy_bench.json).
   --phrase Q,L,K: with --postings, Q phrases of L consecutive tokens of random documents (windows whose tokens all have a vocabulary entry, so
       every phrase occurs at least once), top K, over the one-pass segment with its position lists (kernels_postings_phrase.hip) by device
       events, beside yardsticks of the same process: the OR search of --search (the parent's kernels) over the same queries, every token a slot
@@ -322,11 +326,16 @@ def search_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, d_te
     return out
 
 
-def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs, d_ptfs, n_post, seg):
+def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs, d_ptfs, n_post, seg,
+                sloppy=False):
     """--phrase Q,L,K over the one-pass segment and its position lists (seg: post_first, post_positions, the indexed tokens); see the module's
-    docstring"""
+    docstring.  sloppy: --sloppy Q,L,S,K -- the phrases --phrase Q,L,K draws, timed as the exact search, the sloppy call with every slop 0 and
+    the sloppy call at S"""
     from vaporetto_amd import api
-    Q, L, K = (int(x) for x in spec.split(","))
+    if sloppy:
+        Q, L, slop, K = (int(x) for x in spec.split(","))
+    else:
+        Q, L, K = (int(x) for x in spec.split(","))
     d_first, d_ppos, n_idx = seg
     term = d_term.cpu().numpy().astype(np.int64)
     df = np.diff(term)
@@ -392,6 +401,42 @@ def phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, host
                               d_sw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K, n_cand, d_hd.data_ptr(), d_hs.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(),
                               d_cnt.data_ptr(), stream)
     out = {"spec": spec, "queries": Q, "slots_per_query": L, "k": K, "n_terms": n_terms, "documents": S, "postings": n_post, "positions": n_idx}
+    if sloppy:
+        d_zero = torch.zeros(Q, dtype=torch.int32, device=dev)
+        d_slops = torch.full((Q,), slop, dtype=torch.int32, device=dev)
+
+        def sloppy_call(d_s):
+            batch.phrase_search_postings(d_term.data_ptr(), d_pdocs.data_ptr(), d_ptfs.data_ptr(), d_first.data_ptr(), d_ppos.data_ptr(), n_terms, n_post,
+                                         n_idx, 0, S, d_dl.data_ptr(), d_qoff.data_ptr(), d_qt.data_ptr(), d_qw.data_ptr(), Q, Q * L, 1.2, 0.75, avgdl, K,
+                                         n_probes, d_hd.data_ptr(), d_hs.data_ptr(), d_hf.data_ptr(), d_hc.data_ptr(), d_mc.data_ptr(), d_cnt.data_ptr(),
+                                         stream, slops=d_s.data_ptr())
+        out["slop"] = slop
+        seen = {}
+        for name, fn in (("phrase", phrase), ("sloppy0", lambda: sloppy_call(d_zero)), ("sloppy", lambda: sloppy_call(d_slops))):
+            fn()
+            batch.sync()
+            cnt = d_cnt.cpu().numpy()
+            seen[name] = (d_hd.clone(), d_hs.clone(), d_hf.clone(), d_hc.clone(), d_mc.clone())
+            out.update({name + "_probes": int(cnt[0]), name + "_matches": int(cnt[1]), name + "_occurrences_in_hits": int(d_hf.to(torch.int64).sum().item())})
+        out["sloppy0_equals_phrase_bytes"] = bool(all(torch.equal(a, b) for a, b in zip(seen["phrase"], seen["sloppy0"])))
+        out["probes_equal_host_count"] = bool(out["phrase_probes"] == out["sloppy_probes"] == n_probes)
+        for name, fn in (("phrase", phrase), ("sloppy0", lambda: sloppy_call(d_zero)), ("sloppy", lambda: sloppy_call(d_slops))):
+            fn()
+            batch.sync()
+            r = []
+            for _ in range(args.rounds):
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+                for a, b in ev:
+                    a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                r.append(med([a.elapsed_time(b) for a, b in ev]))
+            batch.sync()
+            out[name + "_ms"] = round(med(r), 4)
+            out[name + "_rounds_ms"] = [round(x, 4) for x in r]
+        out["sloppy0_over_phrase"] = round(out["sloppy0_ms"] / out["phrase_ms"], 3)
+        out["sloppy_over_phrase"] = round(out["sloppy_ms"] / out["phrase_ms"], 3)
+        out["probes_per_s"] = round(n_probes / out["sloppy_ms"] * 1e3, 1)
+        return out
     or_search()
     batch.sync()
     cnt = d_cnt.cpu().numpy()
@@ -681,6 +726,7 @@ def main():
     ap.add_argument("--boolean", action="append", default=[], help="with --postings: Q,L,K -- Q all-MUST queries of L terms by count, Q all-MUST windows of L tokens, the first as all-SHOULD (may be repeated)")
     ap.add_argument("--search-max-candidates", type=int, default=1 << 26)
     ap.add_argument("--count-keys", type=int, default=1 << 24, help="max_keys of the counter of --count")
+    ap.add_argument("--sloppy", action="append", default=[], help="with --postings: Q,L,S,K -- the phrases of --phrase Q,L,K as the exact search, the sloppy search with every slop 0 and the sloppy search at slop S, top K (may be repeated)")
     ap.add_argument("--clause", action="append", default=[], help="with --postings: Q,L,K -- Q all-MUST queries, each a window of L tokens as ONE phrase clause plus one SHOULD term by count, top K (may be repeated)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -824,7 +870,7 @@ def main():
             if args.boolean:   # MUST / SHOULD / MUST_NOT slots over the same segment, beside the OR search over the same slots and a copy
                 row["boolean"] = [boolean_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_term, d_pdocs, d_ptfs, int(cnt[0]))
                                   for spec in args.boolean]
-            if args.phrase or args.clause:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
+            if args.phrase or args.clause or args.sloppy:   # exact phrases over the same segment with its position lists, beside the OR search and a copy
                 n_post = int(cnt[0])
                 d_first, d_order = torch.empty(cap_ends + 2, dtype=torch.int64, device=dev), torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
                 d_ppos = torch.empty(cap_ends + 1, dtype=torch.int32, device=dev)
@@ -850,6 +896,9 @@ def main():
                                     "indexed_plus_dropped_equal_tokens": bool(n_idx + int(cnt[1]) == n_tokens)}
                 row["phrase"] = [phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_soff, d_ids, cap_ends, d_term, d_pdocs,
                                              d_ptfs, n_post, (d_first, d_ppos, n_idx)) for spec in args.phrase]
+                if args.sloppy:   # a slop budget per phrase over the same phrases, beside the exact search
+                    row["sloppy"] = [phrase_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_soff, d_ids, cap_ends, d_term,
+                                                 d_pdocs, d_ptfs, n_post, (d_first, d_ppos, n_idx), sloppy=True) for spec in args.sloppy]
                 if args.clause:   # phrase clauses in boolean queries, beside the boolean search over the tokens as slots and the phrase search
                     row["clause"] = [clause_rows(torch, batch, stream, dev, args, spec, S, n_terms, dev_off, dev_ids, d_term, d_pdocs, d_ptfs, n_post,
                                                  (d_first, d_ppos, n_idx)) for spec in args.clause]

@@ -185,6 +185,18 @@ SIGNATURES = {
     "vpt_postings_phrase_lists": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint64, _P]),
     "vpt_postings_clause_search": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_float,
                                              C.c_float, C.c_float, C.c_uint32, _P, _P, _P, _P, _P]),
+    "vpt_postings_sloppy_phrase_search_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P,
+                                                           _P, _P, C.c_uint32, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64, _P, _P,
+                                                           _P, _P, _P, _P, _P]),
+    "vpt_postings_sloppy_phrase_lists_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P,
+                                                          _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P]),
+    "vpt_postings_sloppy_phrase_limits": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "vpt_postings_sloppy_phrase_search": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32, C.c_float,
+                                                    C.c_float, C.c_float, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "vpt_postings_sloppy_phrase_lists": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                   C.c_uint64, _P]),
+    "vpt_postings_sloppy_clause_search": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, C.c_uint32,
+                                                    C.c_float, C.c_float, C.c_float, C.c_uint32, _P, _P, _P, _P, _P]),
     "vpt_concat_graphemes_batch": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint, _P]),
     "vpt_concat_graphemes_batch_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, _P, _P]),
     "vpt_concat_graphemes_tile": (C.c_int, [C.POINTER(C.c_uint32)]),

@@ -1650,44 +1650,52 @@ class DeviceBatch:
                                capacity_postings: int, capacity_positions: int, doc_base: int, n_documents: int, d_doc_lens: int,
                                d_query_offsets: int, d_query_terms: int, d_query_weights: int, n_queries: int, capacity_slots: int, k1: float,
                                b: float, avgdl: float, k: int, capacity_probes: int, d_hit_docs: int, d_hit_scores: int, d_hit_freqs: int,
-                               d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0) -> None:
+                               d_hit_counts: int, d_match_counts: int, d_counts: int, stream: int = 0, slops: Optional[int] = None) -> None:
         """Device-resident exact-phrase BM25 top-k search over one positional segment (vpt_postings_phrase_search_device), raw device
-        pointers; a query is one phrase with one weight; d_hit_freqs may be 0 (NULL).  Enqueues and returns; errors at sync()."""
+        pointers; a query is one phrase with one weight; d_hit_freqs may be 0 (NULL).  slops: a device pointer to one uint32 slop per query
+        (0: NULL, every slop 0) makes it the sloppy search (vpt_postings_sloppy_phrase_search_device); None: the exact call.  Enqueues and
+        returns; errors at sync()."""
         for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_queries", n_queries, 1 << 32), ("k", k, 1 << 32), ("doc_base", doc_base, 1 << 64),
                              ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
                              ("capacity_positions", capacity_positions, 1 << 64), ("capacity_slots", capacity_slots, 1 << 64),
                              ("capacity_probes", capacity_probes, 1 << 64)):
             if not 0 <= int(v) < top:
                 raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
-        st = _lib.load().vpt_postings_phrase_search_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
-                                                           d_post_first or None, d_post_positions or None, int(n_terms), int(capacity_postings),
-                                                           int(capacity_positions), int(doc_base), int(n_documents), d_doc_lens or None,
-                                                           d_query_offsets or None, d_query_terms or None, d_query_weights or None, int(n_queries),
-                                                           int(capacity_slots), float(k1), float(b), float(avgdl), int(k), int(capacity_probes),
-                                                           d_hit_docs or None, d_hit_scores or None, d_hit_freqs or None, d_hit_counts or None,
-                                                           d_match_counts or None, d_counts or None, stream)
+        head = (self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None, d_post_first or None, d_post_positions or None,
+                int(n_terms), int(capacity_postings), int(capacity_positions), int(doc_base), int(n_documents), d_doc_lens or None,
+                d_query_offsets or None, d_query_terms or None, d_query_weights or None)
+        tail = (int(n_queries), int(capacity_slots), float(k1), float(b), float(avgdl), int(k), int(capacity_probes), d_hit_docs or None,
+                d_hit_scores or None, d_hit_freqs or None, d_hit_counts or None, d_match_counts or None, d_counts or None, stream)
+        if slops is None:
+            st = _lib.load().vpt_postings_phrase_search_device(*(head + tail))
+        else:
+            st = _lib.load().vpt_postings_sloppy_phrase_search_device(*(head + (slops or None,) + tail))
         if st != _lib.VPT_OK:
             _raise(st)
 
     def phrase_lists_postings(self, d_term_offsets: int, d_post_docs: int, d_post_tfs: int, d_post_first: int, d_post_positions: int, n_terms: int,
                               capacity_postings: int, capacity_positions: int, doc_base: int, n_documents: int, d_phrase_offsets: int,
                               d_phrase_terms: int, n_phrases: int, capacity_slots: int, capacity_probes: int, d_list_offsets: int, d_list_docs: int,
-                              d_list_tfs: int, capacity_lists: int, d_counts: int, stream: int = 0) -> None:
+                              d_list_tfs: int, capacity_lists: int, d_counts: int, stream: int = 0, slops: Optional[int] = None) -> None:
         """Device-resident phrases to posting lists over one positional segment (vpt_postings_phrase_lists_device), raw device pointers: per
         phrase the matching documents (global numbers, ascending) and their phrase frequencies, what clause_search_postings takes as derived
-        lists.  Enqueues and returns; errors (the phrase search's, and capacity_lists too small with the need in counts[1]) at sync()."""
+        lists.  slops: as in phrase_search_postings (vpt_postings_sloppy_phrase_lists_device).  Enqueues and returns; errors (the phrase
+        search's, and capacity_lists too small with the need in counts[1]) at sync()."""
         for name, v, top in (("n_terms", n_terms, 1 << 32), ("n_phrases", n_phrases, 1 << 32), ("doc_base", doc_base, 1 << 64),
                              ("n_documents", n_documents, 1 << 64), ("capacity_postings", capacity_postings, 1 << 64),
                              ("capacity_positions", capacity_positions, 1 << 64), ("capacity_slots", capacity_slots, 1 << 64),
                              ("capacity_probes", capacity_probes, 1 << 64), ("capacity_lists", capacity_lists, 1 << 64)):
             if not 0 <= int(v) < top:
                 raise VaporettoError("InvalidArgument", "InvalidArgumentError: %s: out of range" % name)
-        st = _lib.load().vpt_postings_phrase_lists_device(self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None,
-                                                          d_post_first or None, d_post_positions or None, int(n_terms), int(capacity_postings),
-                                                          int(capacity_positions), int(doc_base), int(n_documents), d_phrase_offsets or None,
-                                                          d_phrase_terms or None, int(n_phrases), int(capacity_slots), int(capacity_probes),
-                                                          d_list_offsets or None, d_list_docs or None, d_list_tfs or None, int(capacity_lists),
-                                                          d_counts or None, stream)
+        head = (self._p.handle, self._h, d_term_offsets or None, d_post_docs or None, d_post_tfs or None, d_post_first or None, d_post_positions or None,
+                int(n_terms), int(capacity_postings), int(capacity_positions), int(doc_base), int(n_documents), d_phrase_offsets or None,
+                d_phrase_terms or None)
+        tail = (int(n_phrases), int(capacity_slots), int(capacity_probes), d_list_offsets or None, d_list_docs or None, d_list_tfs or None,
+                int(capacity_lists), d_counts or None, stream)
+        if slops is None:
+            st = _lib.load().vpt_postings_phrase_lists_device(*(head + tail))
+        else:
+            st = _lib.load().vpt_postings_sloppy_phrase_lists_device(*(head + (slops or None,) + tail))
         if st != _lib.VPT_OK:
             _raise(st)
 
@@ -1724,6 +1732,15 @@ class DeviceBatch:
         if st != _lib.VPT_OK:
             _raise(st)
         return int(v.value)
+
+    @staticmethod
+    def postings_sloppy_phrase_limits():
+        """(the most slots a phrase may have, the largest slop) (vpt_postings_sloppy_phrase_limits)"""
+        v, s = C.c_uint32(), C.c_uint32()
+        st = _lib.load().vpt_postings_sloppy_phrase_limits(C.byref(v), C.byref(s))
+        if st != _lib.VPT_OK:
+            _raise(st)
+        return int(v.value), int(s.value)
 
     @staticmethod
     def postings_tile() -> int:
@@ -2138,6 +2155,22 @@ def bm25_idf(n_documents: int, df: int) -> np.float32:
     return np.float32(v.value)
 
 
+def _slops_of(slop, n: int, what: str) -> Optional[np.ndarray]:
+    """slop= of the phrase searches -> None (the int 0: the exact call) or one uint32 per phrase / clause; a value outside [0, 2^32) is refused
+    here, one above the limit by the device (vpt_postings_sloppy_phrase_limits)"""
+    if isinstance(slop, (int, np.integer)):
+        if int(slop) == 0:
+            return None
+        values = [int(slop)] * n
+    else:
+        values = [int(s) for s in slop]
+        if len(values) != n:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: slop: an int or one per %s" % what)
+    if any(not 0 <= s < 1 << 32 for s in values):
+        raise VaporettoError("InvalidArgument", "InvalidArgumentError: query: a slop above 31")
+    return np.array(values + [0], np.uint32)
+
+
 class Occur(enum.IntEnum):  # VPT_OCCUR_*: tantivy's Occur of a BooleanQuery's clause
     SHOULD = 0
     MUST = 1
@@ -2324,15 +2357,17 @@ class Postings:
         return [[(int(hd[q * k + j]), hs[q * k + j]) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
     def phrase_search(self, phrases: Sequence[Sequence[int]], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
-                      b: float = 0.75, weights=None, predictor: Optional["Predictor"] = None):
+                      b: float = 0.75, weights=None, predictor: Optional["Predictor"] = None, slop=0):
         """Exact-phrase BM25 top-k of every phrase over this positional segment (vpt_postings_phrase_search; the definition is in
         include/vaporetto_hip.h).  phrases: a sequence of term-id sequences, each ONE phrase: its ids at consecutive positions, in order; an id
         outside the vocabulary makes the phrase match nothing.  weights: one float per phrase (default: tantivy's phrase weight, the float32
         sum in slot order of bm25_idf(n_documents, df[term]) over the slots).  doc_lens / doc_base / avgdl as in search.  Returns (hits,
         match_counts): hits[q] the list of (document, score float32, freq) triples, at most k, by score descending, then document
-        ascending; freq the phrase's occurrences in the document."""
+        ascending; freq the phrase's occurrences in the document.  slop: an int for every phrase or one int per phrase, each in [0, 31]:
+        anything but the int 0 makes it the SLOPPY search (vpt_postings_sloppy_phrase_search; tantivy's set_slop, defined in the header)."""
         if self.first is None or self.positions is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: the postings were made without positions")
+        slops = _slops_of(slop, len(phrases), "phrase")
         pred = predictor or self._predictor
         if pred is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: phrase_search: no predictor (pass predictor=)")
@@ -2377,11 +2412,14 @@ class Postings:
         n_out = max(n_q * int(k), 1)
         hd, hs, hf = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_out, np.uint32)
         hc, mc, cnt = np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
-        st = _lib.load().vpt_postings_phrase_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None,
-                                                    tfs.ctypes.data if len(tfs) else None, first.ctypes.data, ppos.ctypes.data if len(ppos) else None,
-                                                    n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data,
-                                                    n_q, float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hf.ctypes.data,
-                                                    hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        head = (pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None, tfs.ctypes.data if len(tfs) else None, first.ctypes.data,
+                ppos.ctypes.data if len(ppos) else None, n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, terms.ctypes.data, w.ctypes.data)
+        tail = (n_q, float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hf.ctypes.data, hc.ctypes.data, mc.ctypes.data,
+                cnt.ctypes.data)
+        if slops is None:
+            st = _lib.load().vpt_postings_phrase_search(*(head + tail))
+        else:
+            st = _lib.load().vpt_postings_sloppy_phrase_search(*(head + (slops.ctypes.data,) + tail))
         if st != _lib.VPT_OK:
             _raise(st)
         self.last_search_counts = cnt   # probes, matches, skipped queries
@@ -2389,13 +2427,14 @@ class Postings:
         return [[(int(hd[q * k + j]), hs[q * k + j], int(hf[q * k + j])) for j in range(int(hc[q]))] for q in range(n_q)], mc
 
     def clause_search(self, queries, k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2, b: float = 0.75,
-                      predictor: Optional["Predictor"] = None):
+                      predictor: Optional["Predictor"] = None, slop: int = 0):
         """BM25 top-k of every boolean query of CLAUSES over this positional segment (vpt_postings_clause_search; the definition is in
         include/vaporetto_hip.h).  A query is a sequence of clauses (terms, occur) or (terms, occur, weight): terms a sequence of term ids.  A
         clause of one term is a slot of that term, as in boolean_search; every other clause is ONE exact phrase, scored by its phrase
         frequency (an id outside the vocabulary makes it match nothing, and so does an empty clause).  The default weight is the phrase weight
         of phrase_search (the float32 sum in slot order of bm25_idf over the clause's terms), 0.0 for MUST_NOT.  Returns (hits, match_counts)
-        as boolean_search does; last_search_counts: places, matches, skipped clauses."""
+        as boolean_search does; last_search_counts: places, matches, skipped clauses.  slop: an int in [0, 31] for every phrase clause
+        (phrase_search's; anything but 0: vpt_postings_sloppy_clause_search).  Clauses have no syntax for it."""
         if self.first is None or self.positions is None:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: the postings were made without positions")
         pred = predictor or self._predictor
@@ -2449,11 +2488,15 @@ class Postings:
             raise VaporettoError("InvalidArgument", "InvalidArgumentError: clause_search: the postings' arrays do not belong together")
         n_out = max(n_q * int(k), 1)
         hd, hs, hc, mc, cnt = np.zeros(n_out, np.uint32), np.zeros(n_out, np.float32), np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint64), np.zeros(3, np.uint64)
-        st = _lib.load().vpt_postings_clause_search(pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None,
-                                                    tfs.ctypes.data if len(tfs) else None, first.ctypes.data, ppos.ctypes.data if len(ppos) else None,
-                                                    n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, coff.ctypes.data,
-                                                    terms.ctypes.data, w.ctypes.data, occ.ctypes.data, n_q, float(k1), float(b), float(avgdl), int(k),
-                                                    hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        head = (pred.handle, term.ctypes.data, docs.ctypes.data if len(docs) else None, tfs.ctypes.data if len(tfs) else None, first.ctypes.data,
+                ppos.ctypes.data if len(ppos) else None, n_terms, int(doc_base), n_docs, dl.ctypes.data, qoff.ctypes.data, coff.ctypes.data,
+                terms.ctypes.data, w.ctypes.data, occ.ctypes.data)
+        tail = (n_q, float(k1), float(b), float(avgdl), int(k), hd.ctypes.data, hs.ctypes.data, hc.ctypes.data, mc.ctypes.data, cnt.ctypes.data)
+        slops = _slops_of(int(slop), len(flat) + 1, "clause")
+        if slops is None:
+            st = _lib.load().vpt_postings_clause_search(*(head + tail))
+        else:
+            st = _lib.load().vpt_postings_sloppy_clause_search(*(head + (slops.ctypes.data,) + tail))
         if st != _lib.VPT_OK:
             _raise(st)
         self.last_search_counts = cnt   # places, matches, skipped clauses
@@ -2620,14 +2663,15 @@ class VaporettoTokenizer:
         return postings.search(queries, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
 
     def boolean_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
-                       b: float = 0.75, phrases: bool = False):
+                       b: float = 0.75, phrases: bool = False, slop: int = 0):
         """BM25 top-k of boolean query TEXTS over `postings`.  A text is split on ASCII spaces into CLAUSES: one that starts with `+` is MUST,
         one that starts with `-` is MUST_NOT, any other is SHOULD; the rest of the clause is tokenised and encoded as documents are; an empty
         clause adds nothing.  By default every token of a clause is a slot of the clause's occur: `+東京都` requires each of its tokens
         somewhere in the document; then Postings.boolean_search.  phrases=True (what tantivy's query parser does; `postings` from
         index_batch(positions=True)): a clause of several tokens is ONE exact phrase -- a token without a vocabulary entry makes it match
         nothing -- a clause of one token a term slot, and a clause that yields no token (a stop set took them all) adds nothing, as in the
-        default; then Postings.clause_search.  Needs vocab=."""
+        default; then Postings.clause_search.  slop (with phrases=True): the slop of every phrase clause; a `~` in a text stays a character
+        of its clause.  Needs vocab=."""
         clauses, owner = [], []
         for i, text in enumerate(texts):
             for clause in text.split(" "):
@@ -2647,17 +2691,19 @@ class VaporettoTokenizer:
                 else:
                     queries[i] += [(int(t), occur) for t in ids[int(toff[c]):int(toff[c + 1])]]
         if phrases:
-            return postings.clause_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor)
+            return postings.clause_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor, slop=slop)
+        if slop:
+            raise VaporettoError("InvalidArgument", "InvalidArgumentError: boolean_search: slop needs phrases=True")
         return postings.boolean_search(queries, k, doc_lens, doc_base, k1, b, predictor=self._predictor)
 
     def phrase_search(self, postings: "Postings", texts: Sequence[str], k: int = 10, doc_lens=None, doc_base: Optional[int] = None, k1: float = 1.2,
-                      b: float = 0.75, weights=None):
+                      b: float = 0.75, weights=None, slop=0):
         """Exact-phrase BM25 top-k of query TEXTS over `postings` (index_batch(positions=True)): each text is tokenised and encoded as documents
-        are and is ONE phrase, every token a slot -- a token without a vocabulary entry makes it match nothing -- then Postings.phrase_search.
-        Needs vocab=."""
+        are and is ONE phrase, every token a slot -- a token without a vocabulary entry makes it match nothing -- then Postings.phrase_search
+        (slop: its keyword).  Needs vocab=."""
         toff, ids = self.encode_batch(list(texts))
         phrases = [ids[int(toff[i]):int(toff[i + 1])].tolist() for i in range(len(toff) - 1)]
-        return postings.phrase_search(phrases, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor)
+        return postings.phrase_search(phrases, k, doc_lens, doc_base, k1, b, weights, predictor=self._predictor, slop=slop)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[TantivyToken]]:
         utf8, boff = pack_texts([t.encode("utf-8") for t in texts])

@@ -1506,6 +1506,13 @@ vpt_status vpt_postings_phrase_limits(uint32_t* max_phrase_terms) {
     return VPT_OK;
 }
 
+vpt_status vpt_postings_sloppy_phrase_limits(uint32_t* max_phrase_terms, uint32_t* max_slop) {
+    if (!max_phrase_terms || !max_slop) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
+    *max_phrase_terms = vpt::kPhraseMaxTerms;
+    *max_slop = vpt::kPhraseMaxSlop;
+    return VPT_OK;
+}
+
 namespace vptc {
 vpt_status postings_positions_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_token_offsets, size_t n_documents, uint64_t capacity_in,
                                      const uint32_t* d_token_positions, const uint64_t* d_term_offsets, uint32_t n_terms, const uint64_t* d_post_first,
@@ -1531,7 +1538,8 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
                                          const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
                                          const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
                                          uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
-                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream) {
+                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, bool sloppy,
+                                         const uint32_t* d_query_slops, hipStream_t stream) {
     VPT_TRY(check_batch(p, b));
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_post_first || !d_post_positions || !d_doc_lens || !d_query_offsets || !d_query_terms ||
         !d_query_weights || !d_hit_docs || !d_hit_scores || !d_hit_counts || !d_match_counts || !d_counts)
@@ -1548,6 +1556,7 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
     P.capacity_postings = capacity_postings; P.capacity_positions = capacity_positions; P.n_terms = n_terms;
     P.doc_base = doc_base; P.n_docs = n_documents; P.doc_lens = d_doc_lens;
     P.query_offsets = d_query_offsets; P.query_terms = d_query_terms; P.query_weights = d_query_weights; P.n_queries = n_queries;
+    P.query_slops = sloppy ? d_query_slops : nullptr;
     P.capacity_slots = capacity_slots; P.n_places = n; P.k1 = k1; P.b = bm_b; P.avgdl = avgdl; P.k = k;
     P.q_anchor = S.q_anchor.at(m); P.q_run = S.q_run.at(m); P.q_probes = S.q_probes.at(m); P.base = S.base.at(m); P.qstart = S.qstart.at(m);
     P.flags = S.flags.at(m); P.plen = S.plen.at(m); P.pdoc = S.pdoc.at(m); P.pq = S.pq.at(m); P.hpf = S.hpf.at(m); P.order = S.order.at(m);
@@ -1560,7 +1569,7 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
     rank.add(0, n_queries);
     VPT_HIP(vpt::launch_postings_phrase_queries(P, stream));
     VPT_HIP(vpt::train_scan(P.q_probes, nq, P.base, part, stream));
-    VPT_HIP(vpt::launch_postings_phrase_probe(P, stream));
+    VPT_HIP(sloppy ? vpt::launch_postings_phrase_sloppy_probe(P, stream) : vpt::launch_postings_phrase_probe(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
     VPT_HIP(vpt::launch_postings_phrase_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
@@ -1578,7 +1587,8 @@ vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, co
                                         uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
                                         const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms, uint32_t n_phrases, uint64_t capacity_slots,
                                         uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs, uint32_t* d_list_tfs,
-                                        uint64_t capacity_lists, uint64_t* d_counts, hipStream_t stream) {
+                                        uint64_t capacity_lists, uint64_t* d_counts, bool sloppy, const uint32_t* d_phrase_slops,
+                                        hipStream_t stream) {
     VPT_TRY(check_batch(p, b));
     if (!d_term_offsets || !d_post_docs || !d_post_tfs || !d_post_first || !d_post_positions || !d_phrase_offsets || !d_phrase_terms || !d_list_offsets ||
         !d_list_docs || !d_list_tfs || !d_counts)
@@ -1599,6 +1609,7 @@ vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, co
     P.capacity_postings = capacity_postings; P.capacity_positions = capacity_positions; P.n_terms = n_terms;
     P.doc_base = doc_base; P.n_docs = n_documents;
     P.query_offsets = d_phrase_offsets; P.query_terms = d_phrase_terms; P.n_queries = n_phrases; P.capacity_slots = capacity_slots; P.n_places = n;
+    P.query_slops = sloppy ? d_phrase_slops : nullptr;
     P.q_anchor = S.q_anchor.at(m); P.q_run = S.q_run.at(m); P.q_probes = S.q_probes.at(m); P.base = S.base.at(m); P.qstart = S.qstart.at(m);
     P.flags = S.flags.at(m); P.plen = S.plen.at(m); P.pdoc = S.pdoc.at(m); P.pq = S.pq.at(m); P.scan = S.scan.at(m);
     P.counts = d_counts; P.status = b->d_ctrl;
@@ -1606,7 +1617,7 @@ vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, co
     uint64_t* part = S.tail.partials.at(m);
     VPT_HIP(vpt::launch_postings_phrase_queries(P, stream));
     VPT_HIP(vpt::train_scan(P.q_probes, nq, P.base, part, stream));
-    VPT_HIP(vpt::launch_postings_phrase_probe(P, stream));
+    VPT_HIP(sloppy ? vpt::launch_postings_phrase_sloppy_probe(P, stream) : vpt::launch_postings_phrase_probe(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
     VPT_HIP(vpt::launch_postings_phrase_heads(P, stream));
     VPT_HIP(vpt::train_scan(P.flags, n, P.scan, part, stream));
@@ -1624,7 +1635,20 @@ vpt_status vpt_postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b
                                             uint32_t* d_list_tfs, uint64_t capacity_lists, uint64_t* d_counts, void* hip_stream) {
     return postings_phrase_lists_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
                                         capacity_positions, doc_base, n_documents, d_phrase_offsets, d_phrase_terms, n_phrases, capacity_slots,
-                                        capacity_probes, d_list_offsets, d_list_docs, d_list_tfs, capacity_lists, d_counts,
+                                        capacity_probes, d_list_offsets, d_list_docs, d_list_tfs, capacity_lists, d_counts, false, nullptr,
+                                        static_cast<hipStream_t>(hip_stream));
+}
+
+vpt_status vpt_postings_sloppy_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                                   const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions,
+                                                   uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                                   uint64_t n_documents, const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms,
+                                                   const uint32_t* d_phrase_slops, uint32_t n_phrases, uint64_t capacity_slots,
+                                                   uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs, uint32_t* d_list_tfs,
+                                                   uint64_t capacity_lists, uint64_t* d_counts, void* hip_stream) {
+    return postings_phrase_lists_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
+                                        capacity_positions, doc_base, n_documents, d_phrase_offsets, d_phrase_terms, n_phrases, capacity_slots,
+                                        capacity_probes, d_list_offsets, d_list_docs, d_list_tfs, capacity_lists, d_counts, true, d_phrase_slops,
                                         static_cast<hipStream_t>(hip_stream));
 }
 
@@ -1647,7 +1671,23 @@ vpt_status vpt_postings_phrase_search_device(const vpt_predictor* p, vpt_batch* 
     return postings_phrase_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
                                          capacity_positions, doc_base, n_documents, d_doc_lens, d_query_offsets, d_query_terms, d_query_weights,
                                          n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_probes, d_hit_docs, d_hit_scores, d_hit_freqs,
-                                         d_hit_counts, d_match_counts, d_counts, static_cast<hipStream_t>(hip_stream));
+                                         d_hit_counts, d_match_counts, d_counts, false, nullptr, static_cast<hipStream_t>(hip_stream));
+}
+
+// The sloppy calls: the exact calls' arguments, checks, scratch and launches with the slops beside the queries and the sloppy probe in probe's
+// place (d_query_slops NULL: every slop 0).
+vpt_status vpt_postings_sloppy_phrase_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
+                                                    const uint32_t* d_post_tfs, const uint64_t* d_post_first, const uint32_t* d_post_positions,
+                                                    uint32_t n_terms, uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base,
+                                                    uint64_t n_documents, const uint32_t* d_doc_lens, const uint64_t* d_query_offsets,
+                                                    const int32_t* d_query_terms, const float* d_query_weights, const uint32_t* d_query_slops,
+                                                    uint32_t n_queries, uint64_t capacity_slots, float k1, float b_param, float avgdl, uint32_t k,
+                                                    uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
+                                                    uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, void* hip_stream) {
+    return postings_phrase_search_device(p, b, d_term_offsets, d_post_docs, d_post_tfs, d_post_first, d_post_positions, n_terms, capacity_postings,
+                                         capacity_positions, doc_base, n_documents, d_doc_lens, d_query_offsets, d_query_terms, d_query_weights,
+                                         n_queries, capacity_slots, k1, b_param, avgdl, k, capacity_probes, d_hit_docs, d_hit_scores, d_hit_freqs,
+                                         d_hit_counts, d_match_counts, d_counts, true, d_query_slops, static_cast<hipStream_t>(hip_stream));
 }
 
 // A snapshot: one launch over the slots leaves an entry per key of count >= min_count; those and the arena come to the host, which orders them

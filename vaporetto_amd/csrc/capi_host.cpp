@@ -1257,7 +1257,7 @@ uint64_t phrase_probes(const uint64_t* term_offsets, const uint64_t* post_first,
 // documents' lengths, the query CSR (a weight a slot, phrase: a weight a query; boolean: an occur a slot), the hit arrays (phrase: with the
 // frequencies), the counts.  The inputs have a word of slack each.
 struct SearchMem {
-    const size_t n_terms, n_post, n_pos, n_docs, n_queries, n_slots, n_out;
+    const size_t n_terms, n_post, n_pos, n_docs, n_queries, n_slots, n_out, n_slops;
     const bool phrase, boolean;
     vptcarve::Carver c{};
     vptcarve::Section<uint64_t> term{c, n_terms + 1};
@@ -1272,10 +1272,11 @@ struct SearchMem {
     vptcarve::Section<float> hit_scores{c, n_out};
     vptcarve::Section<uint32_t> hit_freqs{c, phrase ? n_out : 0}, hit_counts{c, n_queries};
     vptcarve::Section<uint64_t> match_counts{c, n_queries}, counts{c, 3};
+    vptcarve::Section<uint32_t> qslops{c, n_slops};   // (the sloppy phrase search with slops; behind everything else: no other offset moves)
     SearchMem(uint32_t terms, uint64_t post, uint64_t positions, uint64_t documents, uint32_t queries, uint64_t slots, uint32_t k, bool is_phrase,
-              bool is_boolean)
+              bool is_boolean, bool with_slops = false)
         : n_terms(terms), n_post(size_t(post)), n_pos(size_t(positions)), n_docs(size_t(documents)), n_queries(queries), n_slots(size_t(slots)),
-          n_out(size_t(queries) * k), phrase(is_phrase), boolean(is_boolean) {}
+          n_out(size_t(queries) * k), n_slops(with_slops ? queries : 0), phrase(is_phrase), boolean(is_boolean) {}
 
     // the segment, the lengths and the query CSR go up (post_first, post_positions: the phrase search's; query_occurs: the boolean search's)
     vpt_status upload(unsigned char* m, hipStream_t s, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
@@ -1379,14 +1380,16 @@ vpt_status vpt_postings_boolean_search(const vpt_predictor* p, const uint64_t* t
                                 counts_out);
 }
 
+namespace {
 // A host positional segment, host documents' lengths and host phrases in, the hits out: what the segment holds goes to one allocation of this
 // call, the probes are counted from the host's arrays as the device counts them, the device search runs once, the five outputs come back.
-vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
-                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
-                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const int32_t* query_terms,
-                                      const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
-                                      uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_freqs_out, uint32_t* hit_counts_out,
-                                      uint64_t* match_counts_out, uint64_t* counts_out) {
+// sloppy: the sloppy device call, query_slops (NULL: all 0) uploaded beside the weights.
+vpt_status phrase_search_host(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                              const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base, uint64_t n_documents,
+                              const uint32_t* doc_lens, const uint64_t* query_offsets, const int32_t* query_terms, const float* query_weights,
+                              bool sloppy, const uint32_t* query_slops, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                              uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_freqs_out, uint32_t* hit_counts_out,
+                              uint64_t* match_counts_out, uint64_t* counts_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!term_offsets || !post_first || !query_offsets || !query_weights || !hit_docs_out || !hit_scores_out || !hit_freqs_out || !hit_counts_out ||
         !match_counts_out || !counts_out)
@@ -1403,7 +1406,8 @@ vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* te
     const uint64_t n_probes = phrase_probes(term_offsets, post_first, n_terms, n_post, n_pos, query_offsets, query_terms, n_queries, n_slots);
     VPT_TRY(check_search_sizes(true, n_probes));
     VPT_TRY(check_doc_range(0, n_documents));
-    const SearchMem A(n_terms, n_post, n_pos, n_documents, n_queries, n_slots, k, true, false);
+    const bool slops = sloppy && query_slops;
+    const SearchMem A(n_terms, n_post, n_pos, n_documents, n_queries, n_slots, k, true, false, slops);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     VPT_TRY(acquire(p, &w));
@@ -1413,13 +1417,37 @@ vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* te
     VPT_TRY(mem.alloc(A.c.bytes()));
     unsigned char* m = mem;
     VPT_TRY(A.upload(m, s, term_offsets, post_docs, post_tfs, post_first, post_positions, doc_lens, query_offsets, query_terms, query_weights, nullptr));
+    if (slops) VPT_HIP(hipMemcpyAsync(A.qslops.at(m), query_slops, 4 * size_t(n_queries), hipMemcpyHostToDevice, s));
     VPT_TRY(A.clear_hits(m, s));
     VPT_TRY(postings_phrase_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
                                           n_documents, A.dl.at(m), A.qoff.at(m), A.qterms.at(m), A.qweights.at(m), n_queries, n_slots, k1, b_param, avgdl, k,
                                           n_probes, A.hit_docs.at(m), A.hit_scores.at(m), A.hit_freqs.at(m), A.hit_counts.at(m), A.match_counts.at(m),
-                                          A.counts.at(m), s));
+                                          A.counts.at(m), sloppy, slops ? A.qslops.at(m) : nullptr, s));
     VPT_TRY(vpt_batch_sync(b));
     return A.read_back(m, counts_out, hit_counts_out, match_counts_out, hit_docs_out, hit_scores_out, hit_freqs_out);
+}
+}  // namespace
+
+vpt_status vpt_postings_phrase_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const int32_t* query_terms,
+                                      const float* query_weights, uint32_t n_queries, float k1, float b_param, float avgdl, uint32_t k,
+                                      uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_freqs_out, uint32_t* hit_counts_out,
+                                      uint64_t* match_counts_out, uint64_t* counts_out) {
+    return phrase_search_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, doc_lens, query_offsets,
+                              query_terms, query_weights, false, nullptr, n_queries, k1, b_param, avgdl, k, hit_docs_out, hit_scores_out, hit_freqs_out,
+                              hit_counts_out, match_counts_out, counts_out);
+}
+
+vpt_status vpt_postings_sloppy_phrase_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                             const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                             uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                                             const int32_t* query_terms, const float* query_weights, const uint32_t* query_slops, uint32_t n_queries,
+                                             float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
+                                             uint32_t* hit_freqs_out, uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
+    return phrase_search_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, doc_lens, query_offsets,
+                              query_terms, query_weights, true, query_slops, n_queries, k1, b_param, avgdl, k, hit_docs_out, hit_scores_out,
+                              hit_freqs_out, hit_counts_out, match_counts_out, counts_out);
 }
 
 namespace {
@@ -1441,7 +1469,7 @@ uint64_t phrase_list_bound(const uint64_t* term_offsets, uint32_t n_terms, uint6
 // What the two host calls keep in the one allocation of their call: the positional segment, the phrase CSR, the lists and the lists call's
 // counts; the clause search adds the documents' lengths, the slot arrays and the four outputs with the counts.  The inputs have a word of slack.
 struct ClauseMem {
-    const size_t n_terms, n_post, n_pos, n_docs, n_phrases, n_pslots, n_lists_cap, n_queries, n_slots, n_out;
+    const size_t n_terms, n_post, n_pos, n_docs, n_phrases, n_pslots, n_lists_cap, n_queries, n_slots, n_out, n_slops;
     vptcarve::Carver c{};
     vptcarve::Section<uint64_t> term{c, n_terms + 1};
     vptcarve::Section<uint32_t> docs{c, n_post + 1}, tfs{c, n_post + 1};
@@ -1461,10 +1489,11 @@ struct ClauseMem {
     vptcarve::Section<float> hit_scores{c, n_out};
     vptcarve::Section<uint32_t> hit_counts{c, n_queries};
     vptcarve::Section<uint64_t> match_counts{c, n_queries}, counts{c, 3};
+    vptcarve::Section<uint32_t> pslops{c, n_slops};   // (the sloppy calls with slops; behind everything else)
     ClauseMem(uint32_t terms, uint64_t post, uint64_t positions, uint64_t documents, size_t phrases, size_t phrase_slots, uint64_t lists, uint32_t queries,
-              uint64_t slots, uint32_t k)
+              uint64_t slots, uint32_t k, bool with_slops = false)
         : n_terms(terms), n_post(size_t(post)), n_pos(size_t(positions)), n_docs(size_t(documents)), n_phrases(phrases), n_pslots(phrase_slots),
-          n_lists_cap(size_t(lists)), n_queries(queries), n_slots(size_t(slots)), n_out(size_t(queries) * k) {}
+          n_lists_cap(size_t(lists)), n_queries(queries), n_slots(size_t(slots)), n_out(size_t(queries) * k), n_slops(with_slops ? phrases : 0) {}
 
     vpt_status upload_segment(unsigned char* m, hipStream_t s, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
                               const uint64_t* post_first, const uint32_t* post_positions, const uint64_t* phrase_offsets,
@@ -1494,14 +1523,13 @@ vpt_status check_host_positional(const uint64_t* term_offsets, const uint32_t* p
     if ((*n_post && (!post_docs || !post_tfs)) || (*n_pos && !post_positions)) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
     return VPT_OK;
 }
-}  // namespace
 
 // Host phrases over a host positional segment in, their posting lists out: the lists call once, over one allocation of this call.
-vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
-                                     const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
-                                     uint64_t n_documents, const uint64_t* phrase_offsets, const int32_t* phrase_terms, uint32_t n_phrases,
-                                     uint64_t* list_offsets_out, uint32_t* list_docs_out, uint32_t* list_tfs_out, uint64_t capacity_lists,
-                                     uint64_t* counts_out) {
+vpt_status phrase_lists_host(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                             const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base, uint64_t n_documents,
+                             const uint64_t* phrase_offsets, const int32_t* phrase_terms, bool sloppy, const uint32_t* phrase_slops, uint32_t n_phrases,
+                             uint64_t* list_offsets_out, uint32_t* list_docs_out, uint32_t* list_tfs_out, uint64_t capacity_lists,
+                             uint64_t* counts_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!phrase_offsets || !list_offsets_out || !counts_out || (capacity_lists && (!list_docs_out || !list_tfs_out)))
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -1515,7 +1543,8 @@ vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* ter
     const uint64_t n_probes = phrase_probes(term_offsets, post_first, n_terms, n_post, n_pos, phrase_offsets, phrase_terms, n_phrases, n_slots);
     VPT_TRY(check_search_sizes(true, n_probes));
     VPT_TRY(check_doc_range(doc_base, n_documents));
-    const ClauseMem A(n_terms, n_post, n_pos, 0, n_phrases, size_t(n_slots), capacity_lists, 0, 0, 0);
+    const bool slops = sloppy && phrase_slops;
+    const ClauseMem A(n_terms, n_post, n_pos, 0, n_phrases, size_t(n_slots), capacity_lists, 0, 0, 0, slops);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     VPT_TRY(acquire(p, &w));
@@ -1525,9 +1554,10 @@ vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* ter
     VPT_TRY(mem.alloc(A.c.bytes()));
     unsigned char* m = mem;
     VPT_TRY(A.upload_segment(m, s, term_offsets, post_docs, post_tfs, post_first, post_positions, phrase_offsets, phrase_terms));
+    if (slops) VPT_HIP(hipMemcpyAsync(A.pslops.at(m), phrase_slops, 4 * size_t(n_phrases), hipMemcpyHostToDevice, s));
     VPT_TRY(postings_phrase_lists_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
                                          n_documents, A.poff.at(m), A.pterms.at(m), n_phrases, n_slots, n_probes, A.loff.at(m), A.ldocs.at(m),
-                                         A.ltfs.at(m), capacity_lists, A.lcounts.at(m), s));
+                                         A.ltfs.at(m), capacity_lists, A.lcounts.at(m), sloppy, slops ? A.pslops.at(m) : nullptr, s));
     const vpt_status st = vpt_batch_sync(b);
     VPT_HIP(hipMemcpy(counts_out, A.lcounts.at(m), 24, hipMemcpyDeviceToHost));   // (the need, when a capacity was too small)
     if (st != VPT_OK) return st;
@@ -1544,12 +1574,13 @@ vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* ter
 // phrase: the lists call makes its list, and the slot names it.  One upload, the two device calls on one stream with no sync between them, one
 // download; the probes, the list entries and the places are counted on the host from the segment's bounds (a list: at most the smallest df
 // among its phrase's terms).  counts_out: the clause search's, with the phrases that have a term out of range added to the skipped slots.
-vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
-                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
-                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const uint64_t* clause_offsets,
-                                      const int32_t* clause_terms, const float* clause_weights, const uint8_t* clause_occurs, uint32_t n_queries,
-                                      float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
-                                      uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
+// sloppy: the sloppy lists call, a phrase clause's slop from clause_slops (one per clause, NULL: all 0; a one-term clause's is not looked at).
+vpt_status clause_search_host(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                              const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base, uint64_t n_documents,
+                              const uint32_t* doc_lens, const uint64_t* query_offsets, const uint64_t* clause_offsets, const int32_t* clause_terms,
+                              const float* clause_weights, const uint8_t* clause_occurs, bool sloppy, const uint32_t* clause_slops, uint32_t n_queries,
+                              float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
+                              uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
     if (!p) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: predictor: must not be NULL");
     if (!query_offsets || !clause_offsets || !hit_docs_out || !hit_scores_out || !hit_counts_out || !match_counts_out || !counts_out)
         return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: NULL argument");
@@ -1571,6 +1602,8 @@ vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* te
     // the slots: a clause of one term names it, every other clause names its phrase's list
     std::vector<int32_t> slot_terms, phrase_terms;
     std::vector<uint64_t> phrase_offsets{0}, slot_bound;
+    std::vector<uint32_t> phrase_slops;
+    const bool slops = sloppy && clause_slops;
     uint64_t cap_lists = 0, skipped_phrases = 0;
     try {
         slot_terms.reserve(size_t(n_clauses));
@@ -1596,6 +1629,7 @@ vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* te
             cap_lists += bound;
             phrase_terms.insert(phrase_terms.end(), clause_terms + a, clause_terms + a + len);
             phrase_offsets.push_back(phrase_terms.size());
+            if (slops) phrase_slops.push_back(clause_slops[c]);
         }
     } catch (const std::bad_alloc&) {
         return fail(VPT_RUNTIME_ERROR, "out of host memory while laying out the clauses");
@@ -1625,7 +1659,7 @@ vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* te
                                                       uint32_t(n_lists), phrase_terms.size())
                                       : 0;
     VPT_TRY(check_search_sizes(true, n_probes));
-    const ClauseMem A(n_terms, n_post, n_pos, n_documents, n_lists, phrase_terms.size(), cap_lists, n_queries, n_clauses, k);
+    const ClauseMem A(n_terms, n_post, n_pos, n_documents, n_lists, phrase_terms.size(), cap_lists, n_queries, n_clauses, k, slops);
     VPT_HIP(hipSetDevice(p->device));
     Workspace w;
     VPT_TRY(acquire(p, &w));
@@ -1643,10 +1677,11 @@ vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* te
         VPT_HIP(hipMemcpyAsync(A.qoccurs.at(m), clause_occurs, n_clauses, hipMemcpyHostToDevice, s));
     }
     VPT_HIP(hipMemsetAsync(m + A.hit_docs.offset, 0, A.hit_counts.offset - A.hit_docs.offset, s));   // (behind a query's hit count: zeros come back)
+    if (slops && n_lists) VPT_HIP(hipMemcpyAsync(A.pslops.at(m), phrase_slops.data(), 4 * n_lists, hipMemcpyHostToDevice, s));
     if (n_lists)
         VPT_TRY(postings_phrase_lists_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), A.first.at(m), A.pos.at(m), n_terms, n_post, n_pos, doc_base,
                                              n_documents, A.poff.at(m), A.pterms.at(m), uint32_t(n_lists), phrase_terms.size(), n_probes, A.loff.at(m),
-                                             A.ldocs.at(m), A.ltfs.at(m), cap_lists, A.lcounts.at(m), s));
+                                             A.ldocs.at(m), A.ltfs.at(m), cap_lists, A.lcounts.at(m), sloppy, slops ? A.pslops.at(m) : nullptr, s));
     VPT_TRY(postings_clause_search_device(p, b, A.term.at(m), A.docs.at(m), A.tfs.at(m), n_terms, n_post, A.loff.at(m), A.ldocs.at(m), A.ltfs.at(m),
                                           uint32_t(n_lists), cap_lists, doc_base, n_documents, A.dl.at(m), A.qoff.at(m), A.qterms.at(m), A.qweights.at(m),
                                           A.qoccurs.at(m), n_queries, n_clauses, k1, b_param, avgdl, k, places, A.hit_docs.at(m), A.hit_scores.at(m),
@@ -1659,6 +1694,48 @@ vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* te
     VPT_HIP(hipMemcpy(hit_docs_out, A.hit_docs.at(m), 4 * A.n_out, hipMemcpyDeviceToHost));
     VPT_HIP(hipMemcpy(hit_scores_out, A.hit_scores.at(m), 4 * A.n_out, hipMemcpyDeviceToHost));
     return VPT_OK;
+}
+}  // namespace
+
+vpt_status vpt_postings_phrase_lists(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                     const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                     uint64_t n_documents, const uint64_t* phrase_offsets, const int32_t* phrase_terms, uint32_t n_phrases,
+                                     uint64_t* list_offsets_out, uint32_t* list_docs_out, uint32_t* list_tfs_out, uint64_t capacity_lists,
+                                     uint64_t* counts_out) {
+    return phrase_lists_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, phrase_offsets,
+                             phrase_terms, false, nullptr, n_phrases, list_offsets_out, list_docs_out, list_tfs_out, capacity_lists, counts_out);
+}
+
+vpt_status vpt_postings_sloppy_phrase_lists(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                            const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                            uint64_t n_documents, const uint64_t* phrase_offsets, const int32_t* phrase_terms,
+                                            const uint32_t* phrase_slops, uint32_t n_phrases, uint64_t* list_offsets_out, uint32_t* list_docs_out,
+                                            uint32_t* list_tfs_out, uint64_t capacity_lists, uint64_t* counts_out) {
+    return phrase_lists_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, phrase_offsets,
+                             phrase_terms, true, phrase_slops, n_phrases, list_offsets_out, list_docs_out, list_tfs_out, capacity_lists, counts_out);
+}
+
+vpt_status vpt_postings_clause_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                      const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                      uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets, const uint64_t* clause_offsets,
+                                      const int32_t* clause_terms, const float* clause_weights, const uint8_t* clause_occurs, uint32_t n_queries,
+                                      float k1, float b_param, float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out,
+                                      uint32_t* hit_counts_out, uint64_t* match_counts_out, uint64_t* counts_out) {
+    return clause_search_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, doc_lens, query_offsets,
+                              clause_offsets, clause_terms, clause_weights, clause_occurs, false, nullptr, n_queries, k1, b_param, avgdl, k, hit_docs_out,
+                              hit_scores_out, hit_counts_out, match_counts_out, counts_out);
+}
+
+vpt_status vpt_postings_sloppy_clause_search(const vpt_predictor* p, const uint64_t* term_offsets, const uint32_t* post_docs, const uint32_t* post_tfs,
+                                             const uint64_t* post_first, const uint32_t* post_positions, uint32_t n_terms, uint64_t doc_base,
+                                             uint64_t n_documents, const uint32_t* doc_lens, const uint64_t* query_offsets,
+                                             const uint64_t* clause_offsets, const int32_t* clause_terms, const float* clause_weights,
+                                             const uint8_t* clause_occurs, const uint32_t* clause_slops, uint32_t n_queries, float k1, float b_param,
+                                             float avgdl, uint32_t k, uint32_t* hit_docs_out, float* hit_scores_out, uint32_t* hit_counts_out,
+                                             uint64_t* match_counts_out, uint64_t* counts_out) {
+    return clause_search_host(p, term_offsets, post_docs, post_tfs, post_first, post_positions, n_terms, doc_base, n_documents, doc_lens, query_offsets,
+                              clause_offsets, clause_terms, clause_weights, clause_occurs, true, clause_slops, n_queries, k1, b_param, avgdl, k,
+                              hit_docs_out, hit_scores_out, hit_counts_out, match_counts_out, counts_out);
 }
 
 // ---- pinned host memory for callers that want the PCIe link at full rate

@@ -597,6 +597,7 @@ vpt_status status_from_bits(uint32_t bits) {
     if (bits & vpt::kErrBadOccur) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: occurs: a value above 2");
     if (bits & vpt::kErrCandidatesTooSmall) return fail(VPT_INVALID_ARGUMENT, kCandidatesTooSmall);
     if (bits & vpt::kErrPhraseTooLong) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: a phrase of more than 64 terms");
+    if (bits & vpt::kErrBadSlop) return fail(VPT_INVALID_ARGUMENT, "InvalidArgumentError: query: a slop above 31");
     if (bits & vpt::kErrProbesTooSmall) return fail(VPT_INVALID_ARGUMENT, kProbesTooSmall);
     if (bits & vpt::kErrListsTooSmall) return fail(VPT_INVALID_ARGUMENT, kListsTooSmall);
     if (bits & vpt::kErrBadPositions)
@@ -830,7 +831,8 @@ vpt_status postings_phrase_search_device(const vpt_predictor* p, vpt_batch* b, c
                                          const uint32_t* d_doc_lens, const uint64_t* d_query_offsets, const int32_t* d_query_terms,
                                          const float* d_query_weights, uint32_t n_queries, uint64_t capacity_slots, float k1, float bm_b, float avgdl,
                                          uint32_t k, uint64_t capacity_probes, uint32_t* d_hit_docs, float* d_hit_scores, uint32_t* d_hit_freqs,
-                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, hipStream_t stream);
+                                         uint32_t* d_hit_counts, uint64_t* d_match_counts, uint64_t* d_counts, bool sloppy,
+                                         const uint32_t* d_query_slops, hipStream_t stream);   // sloppy: the sloppy probe; slops NULL: all 0
 // Phrases to posting lists and the boolean search over a segment and such lists (vpt_postings_phrase_lists_device,
 // vpt_postings_clause_search_device; kernels_postings_phrase.hip, kernels_postings_boolean.hip)
 vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
@@ -838,7 +840,7 @@ vpt_status postings_phrase_lists_device(const vpt_predictor* p, vpt_batch* b, co
                                         uint64_t capacity_postings, uint64_t capacity_positions, uint64_t doc_base, uint64_t n_documents,
                                         const uint64_t* d_phrase_offsets, const int32_t* d_phrase_terms, uint32_t n_phrases, uint64_t capacity_slots,
                                         uint64_t capacity_probes, uint64_t* d_list_offsets, uint32_t* d_list_docs, uint32_t* d_list_tfs,
-                                        uint64_t capacity_lists, uint64_t* d_counts, hipStream_t stream);
+                                        uint64_t capacity_lists, uint64_t* d_counts, bool sloppy, const uint32_t* d_phrase_slops, hipStream_t stream);
 vpt_status postings_clause_search_device(const vpt_predictor* p, vpt_batch* b, const uint64_t* d_term_offsets, const uint32_t* d_post_docs,
                                          const uint32_t* d_post_tfs, uint32_t n_terms, uint64_t capacity_postings, const uint64_t* d_list_offsets,
                                          const uint32_t* d_list_docs, const uint32_t* d_list_tfs, uint32_t n_lists, uint64_t capacity_lists,

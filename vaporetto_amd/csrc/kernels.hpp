@@ -82,6 +82,7 @@ constexpr uint32_t kErrProbesTooSmall = 2097152u;     // the phrase search: more
 constexpr uint32_t kErrPositionsTooSmall = 4194304u;  // the positional merge: more merged positions than capacity_positions_out
 constexpr uint32_t kErrBadOccur = 8388608u;           // the boolean search: an occur value above 2 (kernels_postings_boolean.hip)
 constexpr uint32_t kErrListsTooSmall = 16777216u;     // the phrase lists: more list entries than capacity_lists (kernels_postings_phrase.hip)
+constexpr uint32_t kErrBadSlop = 33554432u;           // the sloppy phrase search: a slop above kPhraseMaxSlop
 
 
 struct ScoreParams {
@@ -561,10 +562,14 @@ hipError_t launch_postings_positions(const PostingsPositionsParams& P, hipStream
 // looked at), and one launch of their own behind it: a head with scan value h writes list entry h {doc_base + document, pf}, a lane per query
 // bound writes list_offsets by ranges' rule; with one of kPhraseErrors in the status, or more entries than capacity_lists (kErrListsTooSmall),
 // it writes the counts only.  No sort, no take; doc_lens, k1, b, avgdl, k and the hit arrays are not looked at.
+// The SLOPPY calls (vpt_postings_sloppy_phrase_search_device, .._lists_device) are the launches above with query_slops set and the sloppy probe
+// in probe's place: flags[p] = the occurrences the place owns, 0 .. 32 (2 * kPhraseMaxSlop + 1 = 63 bits of a 64-bit mask per slot), and pf
+// is clamped to 2^32 - 1 in heads.  Everything behind probe is the exact search's.
 constexpr uint32_t kPhraseMaxTerms = 64;
-constexpr uint32_t kPhraseErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrPhraseTooLong | kErrProbesTooSmall;
+constexpr uint32_t kPhraseMaxSlop = 31;
+constexpr uint32_t kPhraseErrors = kErrBadSegment | kErrBadQueryCsr | kErrBadWeights | kErrPhraseTooLong | kErrProbesTooSmall | kErrBadSlop;
 constexpr uint32_t kClauseErrors = kSearchErrors | kPhraseErrors | kErrListsTooSmall;
-constexpr uint32_t kListsVoid = kErrPhraseTooLong | kErrProbesTooSmall | kErrListsTooSmall;   // set by the lists call alone: it wrote no list
+constexpr uint32_t kListsVoid = kErrPhraseTooLong | kErrProbesTooSmall | kErrListsTooSmall | kErrBadSlop;   // set by the lists calls alone: no list was written
 struct PostingsPhraseParams {
     const uint64_t* term_offsets;   // [n_terms + 1]
     const uint32_t* post_docs;      // [capacity_postings]
@@ -610,9 +615,11 @@ struct PostingsPhraseParams {
     uint32_t* list_docs;            // [capacity_lists]
     uint32_t* list_tfs;             // [capacity_lists]
     uint64_t capacity_lists;
+    const uint32_t* query_slops;    // [n_queries]; nullptr: every slop 0 (and the exact calls).  The last member: no other argument moves
 };
 hipError_t launch_postings_phrase_queries(const PostingsPhraseParams& P, hipStream_t stream);
 hipError_t launch_postings_phrase_probe(const PostingsPhraseParams& P, hipStream_t stream);
+hipError_t launch_postings_phrase_sloppy_probe(const PostingsPhraseParams& P, hipStream_t stream);   // in probe's place: the sloppy calls
 hipError_t launch_postings_phrase_heads(const PostingsPhraseParams& P, hipStream_t stream);
 hipError_t launch_postings_phrase_emit(const PostingsPhraseParams& P, hipStream_t stream);    // emit, then the queries' ranges
 hipError_t launch_postings_phrase_take(const PostingsPhraseParams& P, hipStream_t stream);

@@ -29,11 +29,13 @@
 //   ranges   a lane per query bound: qstart[q] = the head scan at the query's probe base; match_counts; the lane of n_queries writes counts[1].
 //   (sort)   train_radix_sort over the score word, then the query word: stable, so (query, score descending, document ascending).
 //   take     a lane per (query, j < k): hit qstart[q] + j of the ranked order; the lane of j == 0 writes hit_counts.
+// The SLOPPY calls (vpt_postings_sloppy_phrase_search_device, .._lists_device) are the same launches with query_slops beside the queries and
+// phrase_probe_kernel<true> in probe's place: flags[p] is then the number of occurrences the place OWNS, 0 .. 32 (see the kernel).
 // The phrase LISTS (vpt_postings_phrase_lists_device) run queries .. the second heads scan as they stand, with no weights, and then
 //   lists    a lane per place and per query bound: a head with scan value h writes list entry h {doc_base + document, pf} -- born in (phrase,
 //            document) order, so every list ascends; list_offsets[q] = the head scan at the phrase's probe base (ranges' rule); counts[1] = the
 //            entries.  More entries than capacity_lists (kErrListsTooSmall) or one of kPhraseErrors: the counts only.  No sort, no take.
-// No atomic decides a value (one integer add, the status OR), every loop is bounded by kPhraseMaxTerms or by 64 bisection steps, the launch
+// No atomic decides a value (one integer add, the status OR), every loop is bounded by kPhraseMaxTerms, by 64 bisection steps or (the sloppy walk) by 2 * kPhraseMaxSlop + 1 places, the launch
 // boundaries are the only ordering relied on: two runs give identical bytes.  Every index is bounded before it indexes anything: a slot below
 // capacity_slots, a term inside [0, n_terms), a posting below capacity_postings, a position place below capacity_positions, a document below
 // n_docs, a place below capacity_probes, an output below n_queries * k.  Unsorted positions inside a posting are not seen here (positions
@@ -118,6 +120,7 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_queries_kernel(const Po
         uint64_t run = 0, probes = 0;
         const uint64_t a = P.query_offsets[q], b = P.query_offsets[q + 1];
         if (P.query_weights && bits_of(P.query_weights[q]) > 0x7F7FFFFFu) err |= kErrBadWeights;   // (the lists call has no weights)
+        if (P.query_slops && P.query_slops[q] > kPhraseMaxSlop) err |= kErrBadSlop;                 // (the exact calls have no slops)
         if (a > b || b > P.capacity_slots) {
             err |= kErrBadQueryCsr;
         } else if (b - a > kPhraseMaxTerms) {
@@ -147,6 +150,68 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_queries_kernel(const Po
     if (err) atomicOr(P.status, err);
 }
 
+// One slot of a sloppy probe: the adjusted positions p - j of posting (term_j, d) inside [lo, lo + 2 slop], as bits p - j - lo of the mask.
+// One bisection to the first position >= max(lo + j, 0), then at most 2 slop + 1 places: the count of steps bounds the walk, whatever the
+// positions hold.  false: the posting's bounds are no segment's (kErrBadSegment); *mask 0: the document has no posting of the term.
+__device__ __forceinline__ bool sloppy_slot_mask(const PostingsPhraseParams& P, uint64_t ja, uint64_t jb, uint32_t d, uint32_t j, int64_t lo,
+                                                 uint32_t reach, uint64_t* mask) {
+    *mask = 0;
+    const uint64_t y = first_at_least(P.post_docs, ja, jb, uint64_t(d));
+    if (y >= jb || P.post_docs[y] != d) return true;
+    const uint64_t y0 = P.post_first[y], y1 = P.post_first[y + 1];
+    if (y0 > y1 || y1 > P.capacity_positions) return false;
+    const int64_t from = lo + int64_t(j);   // (lo >= -94, j < 64: no wrap; above 2^32 - 1: the bisection ends at y1)
+    uint64_t z = first_at_least(P.post_positions, y0, y1, from > 0 ? uint64_t(from) : 0u);
+    uint64_t m = 0;
+    for (uint32_t t = 0; t <= reach && z < y1; ++t, ++z) {   // (reach <= 2 slop; ascending positions end the walk by themselves)
+        const int64_t off = int64_t(P.post_positions[z]) - int64_t(j) - lo;
+        if (off > int64_t(reach)) break;
+        if (off >= 0) m |= uint64_t(1) << off;   // (off <= reach <= 62)
+    }
+    *mask = m;
+    return true;
+}
+
+// What the place of anchor position post_positions[i] (posting [f0, ..) of document d, anchor slot aj) owns: see phrase_probe_kernel.
+__device__ __forceinline__ uint32_t sloppy_place_count(const PostingsPhraseParams& P, const PhraseQuery& Q, uint64_t q, uint32_t aj, uint64_t i,
+                                                       uint64_t f0, uint32_t d, uint32_t* err) {
+    uint32_t flag = 0;
+    const uint32_t raw = P.query_slops ? P.query_slops[q] : 0u;
+    const uint32_t slop = raw < kPhraseMaxSlop ? raw : kPhraseMaxSlop;   // (above it: kErrBadSlop, nothing is taken)
+    const int64_t a = int64_t(P.post_positions[i]) - int64_t(aj);
+    int64_t lo = a - int64_t(slop);
+    if (i > f0) {
+        const int64_t after = int64_t(P.post_positions[i - 1]) - int64_t(aj) + 1;
+        if (after > lo) lo = after;
+    }
+    if (lo <= a) {   // (positions that do not ascend: the place owns nothing)
+        const uint32_t own = uint32_t(a - lo);   // <= slop
+        uint64_t all = ~uint64_t(0), any = 0;
+        for (uint32_t j = 0; all && j < Q.len; ++j) {   // (at most kPhraseMaxTerms)
+            uint64_t ja, jb, m;
+            if (!phrase_term_range(P, P.query_terms[Q.a + j], &ja, &jb)) { all = 0; break; }
+            if (!sloppy_slot_mask(P, ja, jb, d, j, lo, own + slop, &m)) { *err = kErrBadSegment; all = 0; break; }
+            any |= m;
+            uint64_t c = m;
+            for (uint32_t left = slop, step = 1; left; step <<= 1) {   // smear down by 0 .. slop: 1, 2, 4, .. and the rest
+                const uint32_t by = step < left ? step : left;
+                c |= c >> by;
+                left -= by;
+            }
+            all &= c;
+        }
+        flag = uint32_t(__popcll(all & any & ((uint64_t(2) << own) - 1)));
+    }
+    return flag;
+}
+
+// SLOPPY false: the exact probe, flags[p] = 1 at an occurrence.  SLOPPY true: the place's anchor position gives a = position - anchor slot, and
+// the place OWNS the occurrences s in [lo, a], lo = max(a - slop, a_prev + 1) with a_prev the adjusted position of the place before it in the
+// same posting (read from post_positions, whichever workgroup that place's lane is in): an occurrence has an anchor position in
+// [s, s + slop] and belongs to the first one at or after s, so every occurrence is counted by exactly one lane.  Per slot j, the anchor's own
+// included and a repeated term like any other, M_j = sloppy_slot_mask; C_j = M_j smeared down by 0 .. slop (bit s: an adjusted position in
+// [s, s + slop]); flags[p] = popcount(AND C_j & OR M_j & bits [0, a - lo]), 0 .. 32.  Signed 64-bit throughout.
+template <bool SLOPPY>
 __global__ __launch_bounds__(kPhraseThreads) void phrase_probe_kernel(const PostingsPhraseParams P) {
     const uint64_t p = uint64_t(blockIdx.x) * kPhraseThreads + threadIdx.x;
     const uint64_t total = P.base[P.n_queries];
@@ -176,23 +241,27 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_probe_kernel(const Post
                     doc = uint32_t(rel);
                     query = uint32_t(q);
                     if (i == f0) plen = tf;
-                    const int64_t start = int64_t(P.post_positions[i]) - int64_t(aj);
-                    bool found = start >= 0;
-                    for (uint32_t j = 0; found && j < Q.len; ++j) {   // (at most kPhraseMaxTerms)
-                        if (j == aj) continue;
-                        uint64_t ja, jb;
-                        found = phrase_term_range(P, P.query_terms[Q.a + j], &ja, &jb);
-                        if (!found) break;
-                        const uint64_t y = first_at_least(P.post_docs, ja, jb, uint64_t(d));
-                        found = y < jb && P.post_docs[y] == d;
-                        if (!found) break;
-                        const uint64_t y0 = P.post_first[y], y1 = P.post_first[y + 1];
-                        if (y0 > y1 || y1 > P.capacity_positions) { err = kErrBadSegment; found = false; break; }
-                        const uint64_t want = uint64_t(start) + j;
-                        const uint64_t z = first_at_least(P.post_positions, y0, y1, want);
-                        found = z < y1 && uint64_t(P.post_positions[z]) == want;
+                    if constexpr (SLOPPY) {
+                        flag = sloppy_place_count(P, Q, q, aj, i, f0, d, &err);
+                    } else {
+                        const int64_t start = int64_t(P.post_positions[i]) - int64_t(aj);
+                        bool found = start >= 0;
+                        for (uint32_t j = 0; found && j < Q.len; ++j) {   // (at most kPhraseMaxTerms)
+                            if (j == aj) continue;
+                            uint64_t ja, jb;
+                            found = phrase_term_range(P, P.query_terms[Q.a + j], &ja, &jb);
+                            if (!found) break;
+                            const uint64_t y = first_at_least(P.post_docs, ja, jb, uint64_t(d));
+                            found = y < jb && P.post_docs[y] == d;
+                            if (!found) break;
+                            const uint64_t y0 = P.post_first[y], y1 = P.post_first[y + 1];
+                            if (y0 > y1 || y1 > P.capacity_positions) { err = kErrBadSegment; found = false; break; }
+                            const uint64_t want = uint64_t(start) + j;
+                            const uint64_t z = first_at_least(P.post_positions, y0, y1, want);
+                            found = z < y1 && uint64_t(P.post_positions[z]) == want;
+                        }
+                        flag = found ? 1u : 0u;
                     }
-                    flag = found ? 1u : 0u;
                 }
             } else {
                 err = kErrBadSegment;
@@ -214,9 +283,9 @@ __global__ __launch_bounds__(kPhraseThreads) void phrase_heads_kernel(const Post
     uint64_t pf = 0;
     if (len) {
         const uint64_t end = n - p < len ? n : p + len;
-        pf = P.scan[end] - P.scan[p];   // (at most len: a u32)
+        pf = P.scan[end] - P.scan[p];   // (exact: at most len, a u32; sloppy: at most 32 len)
     }
-    P.plen[p] = uint32_t(pf);
+    P.plen[p] = pf < 0xFFFFFFFFull ? uint32_t(pf) : 0xFFFFFFFFu;
     P.flags[p] = pf ? 1u : 0u;   // (probe's flags are in the scan: no lane reads them here)
 }
 
@@ -309,7 +378,12 @@ hipError_t launch_postings_phrase_queries(const PostingsPhraseParams& P, hipStre
 }
 
 hipError_t launch_postings_phrase_probe(const PostingsPhraseParams& P, hipStream_t stream) {
-    hipLaunchKernelGGL(phrase_probe_kernel, dim3(blocks_of(P.n_places ? P.n_places : 1)), dim3(kPhraseThreads), 0, stream, P);
+    hipLaunchKernelGGL((phrase_probe_kernel<false>), dim3(blocks_of(P.n_places ? P.n_places : 1)), dim3(kPhraseThreads), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_postings_phrase_sloppy_probe(const PostingsPhraseParams& P, hipStream_t stream) {
+    hipLaunchKernelGGL((phrase_probe_kernel<true>), dim3(blocks_of(P.n_places ? P.n_places : 1)), dim3(kPhraseThreads), 0, stream, P);
     return hipGetLastError();
 }
 
